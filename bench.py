@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — headline measurement of the hot path on MI355X (contract: task statement; notes in DESIGN.md §Measurement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload prove|msm|prove_sharded] [--log-n L]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload prove|msm|prove_sharded] [--log-n L] [--full]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input already resident in HBM.
   workload prove (default) : one Marlin prove() of the 2^L-constraint synthetic R1CS (BASELINE.json configs[2]; L = 20):
@@ -14,6 +15,11 @@ weak scaling, no data-path collective); `msm` gives each rank a 2^L-point shard 
 144-byte Jacobian partials after an all-gather; `prove_sharded` (strong scaling, not the default) runs ONE proof over
 all ranks: every commitment MSM split by point range, partial sums all-gathered, everything else replicated
 (simpleworks_amd.dist.enable_sharded_prover).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--full adds everything else the line has carried: the roofline and per-kernel figures (HIP events around the kernels in the
+timed loop), host verification of the last proof, the stand-alone kernel probes, the drop-in legs, the CPU baseline and, with
+N > 1, the `sharded` leg.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import hashlib
@@ -141,6 +147,24 @@ def cpu_baseline_prove(calls, N, mats, z, log_shift_1t):
             "one_thread": {"value": (N >> log_shift_1t) / tot_1, "unit": "constraints/s", "cores": 1,
                            "sample": "the same call list with every size divided by %d (N = %d) on ONE thread: MSM %.1f s, "
                                      "NTT %.1f s, mat-vec %.2f s" % (1 << log_shift_1t, N >> log_shift_1t, t1["msm"], t1["ntt"], t1["spmv"])}}
+
+
+def dump_outputs(directory, last, ctx):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy (exact: every value is an integer below 2^32).
+      prove : proof.npy            float32 [bytes]  the proof's CanonicalSerialize bytes (what generate_proof returns)
+      msm   : msm_affine_xy.npy    float64 [2, 12]  the step's G1 result normalised to affine (x, y; Montgomery Fq, 32-bit limbs,
+                                                    little-endian): the Jacobian form the step returns depends on the order of
+                                                    the additions, the point does not; the point at infinity is all zeros
+    Inputs are fixed by seeds, so the same arguments give the same files from run to run and from build to build."""
+    os.makedirs(directory, exist_ok=True)
+    if "proof" in last:
+        np.save(os.path.join(directory, "proof.npy"), np.frombuffer(last["proof"].data, dtype=np.uint8).astype(np.float32))
+    if "msm" in last:
+        jac = np.ascontiguousarray(last["msm"], dtype=np.uint64)
+        xy, inf = ctx.g1_normalize(jac)
+        if inf:
+            xy = np.zeros_like(xy)
+        np.save(os.path.join(directory, "msm_affine_xy.npy"), xy.view(np.uint32).astype(np.float64).reshape(2, 12))
 
 
 def _run_sharded_children(args, sizes, rank, world, device_index, dist, torch, coll_dev):
@@ -327,9 +351,16 @@ def main():
     ap.add_argument("--profile-all", action="store_true",
                     help="bracket EVERY kernel launch with HIP events (per-kernel table in the JSON line; costs ~2 %% of a "
                          "2^20 proof) instead of the dominant kernel only")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline / per-kernel figures, verification, stand-alone kernel probes, drop-in "
+                         "legs, the CPU baseline and (N > 1) the sharded leg.  Off: the line carries the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.sharded_child:
         sys.exit(sharded_child(args))
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # The contract is ONE JSON line on stdout.  RCCL prints a banner (hostname, library path, ...) to stdout when its
     # communicator comes up, so everything written to file descriptor 1 from here on is sent to stderr and the JSON line
@@ -338,14 +369,16 @@ def main():
     json_out = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
 
-    import torch
-    import torch.distributed as dist
     import simpleworks_amd as swm
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # SWM_BENCH_FORCE_DIST=1: take the multi-rank code path (process group, barriers, collectives) even with one rank —
     # lets a single-GPU box exercise the RCCL calls the N > 1 runs make
     use_dist = world > 1 or bool(os.environ.get("SWM_BENCH_FORCE_DIST"))
+    torch = dist = None
+    if use_dist:  # torch is only the process group's plumbing: a one-rank run does not import it
+        import torch
+        import torch.distributed as dist
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # Test hook for single-GPU boxes: SWM_BENCH_BACKEND=gloo SWM_BENCH_DEVICE=0 runs all ranks on one device (the
@@ -374,6 +407,7 @@ def main():
         bh = ctx.srs_upload(bases)
         d_sc = ctx.to_device(fr_array(n, 1000 + rank))  # any reduced limbs are valid Montgomery residues
         del bases
+        last = {}
 
         def step():
             part = ctx.msm_g1_dev(bh, d_sc, n, True)
@@ -384,7 +418,8 @@ def main():
                 acc = out[0].cpu().numpy().view(np.uint64)
                 for o in out[1:]:
                     acc = ctx.g1_add_jac(acc, o.cpu().numpy().view(np.uint64))
-                return acc
+                part = acc
+            last["msm"] = part
             return part
         dominant, units, unit = "msm_accumulate", n, "points/s"
         alg_bytes = 128.0 * n  # 96 B affine base + 32 B scalar per point, n points per launch
@@ -465,26 +500,34 @@ def main():
 
     def sync():
         ctx.synchronize()
-        torch.cuda.synchronize()
         if use_dist:
+            torch.cuda.synchronize()
             dist.barrier()
             torch.cuda.synchronize()
 
+    # the roofline and per-kernel figures come from HIP events around the kernels of the timed loop: only when the line is to
+    # carry them (--full, --profile-all); a plain run times its steps with the events off
+    profiled = args.full or args.profile_all
     for _ in range(args.warmup):
         step()
-    ctx.profile_reset()
-    ctx.profile_enable(1 if args.profile_all else 2)  # HIP events around the roofline kernels (msm_accumulate, ntt_pass, spmv_*) or around everything
+    if profiled:
+        ctx.profile_reset()
+        ctx.profile_enable(1 if args.profile_all else 2)  # HIP events around the roofline kernels (msm_accumulate, ntt_pass, spmv_*) or around everything
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     sync()
     dt = time.perf_counter() - t0
-    ctx.profile_enable(False)
-    prof = ctx.profile()
-    work_timed, calls_timed = dict(ctx.last_work), list(ctx.last_calls)
+    if profiled:
+        ctx.profile_enable(False)
+        prof = ctx.profile()
+        work_timed, calls_timed = dict(ctx.last_work), list(ctx.last_calls)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, ctx)
     standalone = {}
-    if args.workload != "msm":
+    verify_ms = None
+    if args.full and args.workload != "msm":
         verify_ms = []
         for _ in range(3):  # verify_proof runs on the host (one thread): quoted beside the proof it checks, not part of `value`
             tv = time.perf_counter()
@@ -530,7 +573,7 @@ def main():
             standalone["spmv"] = {"rows": len(rp) - 1, "nnz": int(rp[-1]), "ms": ms, "achieved": b / (ms * 1e-3) / 1e9,
                                   "form": "device-resident operands, product kernels only"}
     drop_in = None
-    if args.workload == "prove" and rank == 0 and not use_dist and not args.no_drop_in:
+    if args.full and args.workload == "prove" and rank == 0 and not use_dist and not args.no_drop_in:
         # what a source-compatible caller (its own `&mut StdRng`) sees, next to the headline: a few proofs per mode
         drop_in = {}
         for mode in ("builtin", "callback", "adopt"):
@@ -547,7 +590,7 @@ def main():
                            "fill_bytes while the GPU works on the rest of round 1; adopt = swm_rng_from_chacha with the caller's "
                            "(seed, word position), position written back: the caller's stream word for word, drawn on the GPU")
     binding = None
-    if args.workload == "prove" and rank == 0 and not use_dist and not args.no_drop_in:
+    if args.full and args.workload == "prove" and rank == 0 and not use_dist and not args.no_drop_in:
         # What generate_proof costs a caller of the Rust binding ON TOP of swm_generate_proof: tests/native/dropin_harness.cpp
         # replays the shim's per-proof call sequence (key lookup by vk digest in the process-wide cache, assignment-only pack —
         # no to_matrices(), NULL matrix pointers —, swm_generate_proof on a context of the thread's own with the SHARED key,
@@ -630,7 +673,7 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
-    # N > 1, workload prove: besides the replicas figure (value), ONE proof over all ranks through the library's own RCCL
+    # N > 1, workload prove, --full: besides the replicas figure (value), ONE proof over all ranks through the library's own RCCL
     # exchange (swm_rccl_init; point-range sharded commitment MSMs, one ncclAllGather per prover round) is measured and
     # reported as the `sharded` sub-object.  The leg runs in a FRESH CHILD PROCESS per rank (r06): this process only
     # hands the ncclUniqueId over (a torch broadcast), starts `bench.py --sharded-child ...`, reads its JSON lines under a
@@ -639,7 +682,7 @@ def main():
     # measurement above is complete before any of it starts; a failed leg is `sharded: {"error": ...}` in the line (and exit
     # code 3 with SWM_BENCH_SHARDED_STRICT=1).
     sharded_info, sharded_more = None, []
-    if use_dist and args.workload == "prove" and not os.environ.get("SWM_BENCH_NO_SHARDED"):
+    if args.full and use_dist and args.workload == "prove" and not os.environ.get("SWM_BENCH_NO_SHARDED"):
         if args.sharded_log_n:
             sizes = [int(x) for x in args.sharded_log_n.split(",") if x]
         else:
@@ -665,7 +708,7 @@ def main():
                             "proof_verifies": all(r["verifies"] for r in per_rank)})
         sharded_info, sharded_more = (results[0] if results else None), results[1:]
 
-    if rank == 0:
+    if rank == 0 and profiled:
         dom = prof[dominant]
         launches_per_step = dom["calls"] / args.steps
         work = work_timed
@@ -744,16 +787,7 @@ def main():
                                                       work["spmv_calls"] / args.steps),
                               "ms_per_step": ms / args.steps,
                               "standalone": dict(standalone.get("spmv", {}), frac=standalone.get("spmv", {}).get("achieved", 0) / HBM_PEAK_GBS)})
-        out = {
-            "metric": METRIC, "value": units * (1 if args.workload == "prove_sharded" else world) * args.steps / dt, "unit": unit, "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "strong" if args.workload == "prove_sharded" else "weak",
-            "vs_baseline": None, "dtype": "u32 limbs (384-bit Montgomery Fq for G1, 256-bit Fr)", "data": "synthetic",
-            "config": {"workload": workload, "per_gpu_units": n,
-                       "multi_gpu": {"prove": "replicas (one proof per rank)",
-                                     "prove_sharded": "one proof over all ranks: point-range sharded commitment MSMs, "
-                                                      "192-B partials all-gathered, transforms replicated",
-                                     "msm": "point-range shards, all-gather of 144-B partials"}[args.workload]},
+        extra = {
             "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source, "traffic_stale": traffic_stale,
                          "avg_launch_ms": dom["avg_ms"], "launches_per_step": launches_per_step,
@@ -768,13 +802,27 @@ def main():
                          "issue_ceiling_mixed_adds_per_s": ceiling, "issue_ceiling_source": sq_src,
                          "issue_ceiling_stale": stale(sq, "msm_accumulate")},
             "roofline_secondary": secondary,
-            "sharded": sharded_info, "sharded_more": sharded_more or None,
-            "verify_ms_host": verify_ms if args.workload != "msm" else None,
-            "rng": args.rng, "drop_in_rng": drop_in, "drop_in": binding, "overlapped": overlapped,
             "work_per_step": {k: v / args.steps for k, v in work.items()},
             "kernels_ms_per_step": {k: round(v["total_ms"] / args.steps, 4) for k, v in sorted(prof.items())},
         }
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg is reported at N = 1 only
+    if rank == 0:
+        out = {
+            "metric": METRIC, "value": units * (1 if args.workload == "prove_sharded" else world) * args.steps / dt, "unit": unit, "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "strong" if args.workload == "prove_sharded" else "weak",
+            "vs_baseline": None, "dtype": "u32 limbs (384-bit Montgomery Fq for G1, 256-bit Fr)", "data": "synthetic",
+            "config": {"workload": workload, "per_gpu_units": n,
+                       "multi_gpu": {"prove": "replicas (one proof per rank)",
+                                     "prove_sharded": "one proof over all ranks: point-range sharded commitment MSMs, "
+                                                      "192-B partials all-gathered, transforms replicated",
+                                     "msm": "point-range shards, all-gather of 144-B partials"}[args.workload]},
+            "rng": args.rng, "sharded": sharded_info, "sharded_more": sharded_more or None, "overlapped": overlapped,
+        }
+        if profiled:
+            out.update(extra)
+        if args.full:
+            out.update({"verify_ms_host": verify_ms, "drop_in_rng": drop_in, "drop_in": binding})
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg is reported at N = 1 only
             if args.workload == "msm":
                 out["cpu_baseline"] = cpu_baseline_msm(args.cpu_log_n or 18)
             else:

@@ -146,7 +146,7 @@ def test_bench_through_the_launcher_one_rank_per_gpu_with_the_sharded_leg():
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--log-n", "14", "--no-cpu-baseline", "--no-drop-in"], env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
+                          "--log-n", "14", "--full", "--no-cpu-baseline", "--no-drop-in"], env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines

@@ -8,18 +8,18 @@ tag=${1:-r01}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-python3 bench.py --steps 10 --warmup 2 > $out/bench_prove.json 2> $out/bench_prove.err
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-drop-in > $out/bench_prove_driver_flags.json 2>> $out/bench_prove.err   # the driver's flags
-python3 bench.py --log-n 22 --steps 4 --warmup 1 --no-cpu-baseline --no-drop-in > $out/bench_prove_2p22.json 2>> $out/bench_prove.err
-python3 bench.py --circuit merkle --steps 10 --warmup 2 --overlap 4 > $out/bench_merkle.json 2> $out/bench_merkle.err   # (+ four contexts on ONE shared key)
-python3 bench.py --workload msm --steps 12 --warmup 2 > $out/bench_msm.json 2> $out/bench_msm.err
-python3 bench.py --workload msm --log-n 22 --steps 8 --warmup 2 --cpu-log-n 18 > $out/bench_msm_2p22.json 2> $out/bench_msm22.err
-SWM_PROOF_MARKS=1 rocprofv3 --kernel-trace --stats -d $out/prof_prove -o run --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-drop-in > $out/prof_prove.log 2>&1
+python3 bench.py --steps 10 --warmup 2 --full > $out/bench_prove.json 2> $out/bench_prove.err
+python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-drop-in > $out/bench_prove_driver_flags.json 2>> $out/bench_prove.err   # the driver's flags
+python3 bench.py --log-n 22 --steps 4 --warmup 1 --full --no-cpu-baseline --no-drop-in > $out/bench_prove_2p22.json 2>> $out/bench_prove.err
+python3 bench.py --circuit merkle --steps 10 --warmup 2 --full --overlap 4 > $out/bench_merkle.json 2> $out/bench_merkle.err   # (+ four contexts on ONE shared key)
+python3 bench.py --workload msm --steps 12 --warmup 2 --full > $out/bench_msm.json 2> $out/bench_msm.err
+python3 bench.py --workload msm --log-n 22 --steps 8 --warmup 2 --full --cpu-log-n 18 > $out/bench_msm_2p22.json 2> $out/bench_msm22.err
+SWM_PROOF_MARKS=1 rocprofv3 --kernel-trace --stats -d $out/prof_prove -o run --output-format csv -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-drop-in > $out/prof_prove.log 2>&1
 python3 tools/trace_share.py $out/prof_prove/run_kernel_trace.csv > $out/timeline_share.txt 2>&1
 python3 tools/trace_dump.py $out/prof_prove/run_kernel_trace.csv 15 > $out/trace_dump.txt 2>&1
 python3 tools/rocprof_region.py $out/prof_prove/run_kernel_trace.csv msm_accumulate 75 > $out/region_prove.json
-rocprofv3 --kernel-trace --stats -d $out/prof_merkle -o run --output-format csv -- python3 bench.py --circuit merkle --steps 5 --warmup 1 --no-cpu-baseline --no-drop-in > $out/prof_merkle.log 2>&1
-rocprofv3 --kernel-trace --stats -d $out/prof_msm -o run --output-format csv -- python3 bench.py --workload msm --steps 12 --warmup 2 --no-cpu-baseline > $out/prof_msm.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/prof_merkle -o run --output-format csv -- python3 bench.py --circuit merkle --steps 5 --warmup 1 --full --no-cpu-baseline --no-drop-in > $out/prof_merkle.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/prof_msm -o run --output-format csv -- python3 bench.py --workload msm --steps 12 --warmup 2 --full --no-cpu-baseline > $out/prof_msm.log 2>&1
 python3 tools/rocprof_region.py $out/prof_msm/run_kernel_trace.csv msm_accumulate 12 > $out/region_msm.json
 # (the kernel traces themselves are tens of MB: summarised above, not kept)
 rm -f $out/prof_prove/run_kernel_trace.csv $out/prof_merkle/run_kernel_trace.csv $out/prof_msm/run_kernel_trace.csv

@@ -18,8 +18,8 @@ for src, dst in (("bench_prove.json", "bench_prove.json"), ("bench_msm.json", "b
                  ("prof_merkle_build/run_kernel_stats.csv", "merkle_build_2p18_kernel_stats.csv")):
     if os.path.exists(os.path.join(o, src)):
         shutil.copy(os.path.join(o, src), os.path.join(p, "%s_%s" % (pre, dst)))
-for name, launches, log, cmd in (("prove", 75, "prof_prove", "--steps 5 --warmup 1 --no-drop-in"),
-                                 ("msm", 12, "prof_msm", "--workload msm --steps 12 --warmup 2")):
+for name, launches, log, cmd in (("prove", 75, "prof_prove", "--steps 5 --warmup 1 --full --no-drop-in"),
+                                 ("msm", 12, "prof_msm", "--workload msm --steps 12 --warmup 2 --full")):
     if not os.path.exists(os.path.join(o, "region_%s.json" % name)) and not os.path.exists(os.path.join(o, log, "run_kernel_trace.csv")):
         print(name, "no kernel trace summary in this collection: timed-region file not written")
         continue
