@@ -90,18 +90,24 @@ struct MsmTwin {
     MsmTable tab2;           // LEAD: the table (with the offset) of the job that follows
     MsmJob* lead = nullptr;  // FOLLOW: the job whose sort this one takes over
 };
+// the geometry of a job's sorted array and descriptors (msm.hip: MsmShape, MsmZeroLayout): a follower takes the lead's arrays
+// only when its own geometry is the same
+struct MsmSortGeom {
+    size_t zero_words = 0, nseg_max = 0;
+    uint32_t SEG = 0, big_nseg = 0, flat_bins = 0;
+    bool operator==(const MsmSortGeom& o) const {
+        return zero_words == o.zero_words && nseg_max == o.nseg_max && SEG == o.SEG && big_nseg == o.big_nseg && flat_bins == o.flat_bins;
+    }
+};
 // what a LEAD leaves for its follower
 struct MsmTwinSrc {
     bool ready = false;
     const void* scalars = nullptr;
     int mont = 0, lane = -1;
-    unsigned c = 0;
-    const G1TE* te2 = nullptr;
-    size_t stride2 = 0, offset2 = 0;
-    // the lead's device arrays and the geometry they were built with (the follower's must be the same)
+    MsmTable tab2;  // the follower's table (MsmTwin::tab2)
+    // the lead's device arrays and the geometry they were built with
     const uint32_t *block = nullptr, *seg_start = nullptr, *seg_off = nullptr, *big_list = nullptr;
-    size_t zero_words = 0, nseg_max = 0;
-    uint32_t SEG = 0, big_nseg = 0, flat_bins = 0;
+    MsmSortGeom geom;
     hipEvent_t sorted = nullptr;  // recorded after the lead's bin sort
 };
 
@@ -125,7 +131,7 @@ struct MsmJob {
     bool needs_acc_wait = false;
     hipStream_t stream = nullptr;
     hipEvent_t acc_done = nullptr;
-    G1XYZZ *d_partial = nullptr, *d_wpart = nullptr, *d_acc = nullptr;
+    G1XYZZ *d_partial = nullptr, *d_acc = nullptr;
     const uint32_t *d_seg_off = nullptr, *d_hist = nullptr, *d_status = nullptr, *d_entries = nullptr;
     uint32_t seg = 0;  // segment bound of the accumulation: bucket b owns the partial sums d_seg_off[b] .. + ceil(d_hist[b] / seg)
     G1XYZZ* host = nullptr;  // pinned slot receiving nwin * red_blocks (A, R) pairs

@@ -3,25 +3,21 @@
 // Replaces ark_ec::msm::VariableBaseMSM::multi_scalar_mul (ark-ec 0.3.0), reached from
 // /root/reference/src/marlin/mod.rs:75,92 through KZG10::commit/open.  arkworks runs an unsigned-window Pippenger
 // with one rayon task per window; the MI355X design is different on purpose (the sum is a canonical group element,
-// so only the result has to agree):
-//
-//   1. msm_digits   one lane per scalar: Montgomery -> standard form if needed, signed-digit recoding into
-//                   W = ceil(254/c) windows (digits in [-2^(c-1), 2^(c-1)] halve the bucket count), written
-//                   window-major so that the sort streams them coalesced.           HBM: 32 B read + 4W B write / point
-//   2. msm_hist / msm_scan / msm_scatter   counting sort of (point index | sign) by (window, bucket): 64K-digit
-//                   tiles histogram in LDS (LDS atomics), one global atomic per non-empty LDS bin, single-workgroup
-//                   exclusive scan, then each tile reserves its run per bucket and ranks with LDS atomics.
-//                   Every bucket is split into balanced segments of <= 32 points.
-//   3. msm_accumulate  one lane per segment: gather 96-B affine bases through L2 / Infinity Cache, XYZZ mixed
-//                   additions (8M+2S, carry-chain integer VALU, no MFMA) -> one partial per segment.
-//                   This is the dominant kernel: n*W mixed adds.
-//   4. msm_bucket_sum / msm_big_bucket_sum   fold a bucket's segment partials: one lane per ordinary bucket, a
-//                   whole workgroup (strided sums + LDS tree) per bucket with > 16 segments, so structured scalars
-//                   (all-ones witnesses) and a short top window do not serialise on one lane.
-//   5. msm_window_reduce  per window sum_b (b+1)*S_b: lanes take 8 consecutive buckets (local running sum +
-//                   small scalar multiple for the chunk offset), LDS tree across the workgroup.
-//   6. host         sums the per-workgroup partials and does the W-term Horner fold (c doublings per window):
-//                   a 250-step serial dependency chain belongs on a CPU core, not on a 64-wide SIMD.
+// so only the result has to agree).  Two schedules: per-window buckets (msm_plan) for table-less base sets, and the
+// precomputed-window ("flat") schedule, where a resident set's window multiples (msm_table_build[_te]) let all windows
+// share ONE bucket set.  The stages of one MSM (msm_enqueue; msm_shape decides their geometry):
+//   1. msm_digits        signed-digit recoding, window-major (digits in [-2^(c-1), 2^(c-1)] halve the bucket count)
+//   2. sort by bucket    per-window: msm_hist, msm_scan_totals / _mid / _final, msm_scatter (large MSMs also msm_bin_check,
+//                        msm_partition, msm_bin_sort); flat: msm_flat_coarse_hist, msm_flat_scan_bins, msm_flat_partition,
+//                        msm_flat_bin_sort, which also writes the segment descriptors.  The second job of a twin pair copies
+//                        the first one's sort instead (msm_twin_copy).
+//   3. msm_seg_desc / msm_seg_order   buckets cut into segments of at most SEG entries, ordered by length
+//   4. msm_accumulate[_te, _te_quad]  one lane (or four) per segment: gathered bases or table rows, mixed additions
+//                        (XYZZ or twisted Edwards, no MFMA) -> one partial sum per segment.  The dominant kernel.
+//   5. msm_big_bucket_sum  buckets with many segments folded by a lane group ahead of the bucket stage
+//   6. msm_bucket_reduce[_low]  the bucket stage: sum_b (b+1) S_b per window into (A, R) pairs per workgroup, written to a
+//                        pinned host slot; deferred jobs of a prover round share one launch (msm_flush_tails)
+//   7. host              per-workgroup pairs and the Horner fold over the windows (msm_finish)
 //
 // Algorithmic bytes per point: 96 B base + 32 B scalar = 128 B.
 #include <stdlib.h>
@@ -44,6 +40,21 @@ static constexpr int RED_BLOCK = 256;
 static constexpr uint32_t SORT_TILE_MIN = 65536;  // digits per workgroup in the LDS-privatised counting sort (at least)
 static constexpr int SORT_THREADS = 1024;
 
+unsigned msm_table_windows(unsigned c) { return (254 + c - 1) / c; }
+// The 254 recoding bits in ceil(254 / c) windows whose widths differ by at most one, the widest c bits (c[0] is always the
+// widest): a short top window would put a quarter of all points into two buckets.  Bucket counts and offsets are the caller's.
+static WinLayout msm_windows(unsigned c) {
+    WinLayout L;
+    memset(&L, 0, sizeof(L));
+    L.nwin = msm_table_windows(c);
+    const unsigned base = 254 / L.nwin, extra = 254 % L.nwin;
+    for (unsigned w = 0, bit = 0; w < L.nwin; bit += L.c[w++]) {
+        L.c[w] = (uint8_t)(base + (w < extra ? 1 : 0));
+        L.bit[w] = (uint16_t)bit;
+    }
+    L.maxB = 1u << (L.c[0] - 1);
+    return L;
+}
 WinLayout msm_plan(size_t n) {
     // Target window size for the GPU schedule (NOT arkworks' ln-based rule): large enough that the n*W accumulate
     // adds dominate the fixed-latency bucket reduction, small enough that buckets stay populated.
@@ -54,51 +65,28 @@ WinLayout msm_plan(size_t n) {
     else if (n <= 98304) c = 12;
     else if (n <= 393216) c = 14;
     else c = 16;
-    WinLayout L;
-    L.nwin = (254 + c - 1) / c;
-    unsigned base = 254 / L.nwin, extra = 254 % L.nwin;
-    unsigned bit = 0;
-    L.NB = 0;
-    L.maxB = 0;
-    for (unsigned w = 0; w < L.nwin; w++) {
-        unsigned cw = base + (w < extra ? 1 : 0);
-        L.c[w] = (uint8_t)cw;
-        L.bit[w] = (uint16_t)bit;
+    WinLayout L = msm_windows(c);
+    for (unsigned w = 0; w < L.nwin; w++) {  // window w: 2^(c[w]-1) buckets of its own
         L.boff[w] = L.NB;
-        bit += cw;
-        uint32_t B = 1u << (cw - 1);
-        L.NB += B;
-        if (B > L.maxB) L.maxB = B;
+        L.NB += 1u << (L.c[w] - 1);
     }
     L.boff[L.nwin] = L.NB;
     return L;
 }
-
-unsigned msm_table_windows(unsigned c) { return (254 + c - 1) / c; }
-// Windows of the flat schedule for a table of width c: ceil(254 / c) windows whose widths differ by at most one (as in
-// msm_plan: a short top window would put a quarter of all points into two buckets), the widest being c bits; all of them
-// index ONE set of 2^(c-1) buckets.  c[0] is always the widest window.
+// Windows of the flat schedule for a table of width c: all of them index ONE set of 2^(c-1) buckets.
 WinLayout msm_table_layout(unsigned c) {
-    WinLayout L;
-    memset(&L, 0, sizeof(L));
-    L.nwin = msm_table_windows(c);
-    const unsigned base = 254 / L.nwin, extra = 254 % L.nwin;
-    unsigned bit = 0;
-    for (unsigned w = 0; w < L.nwin; w++) {
-        const unsigned cw = base + (w < extra ? 1 : 0);
-        L.c[w] = (uint8_t)cw;
-        L.bit[w] = (uint16_t)bit;
-        L.boff[w] = 0;
-        bit += cw;
-    }
-    L.NB = L.maxB = 1u << (L.c[0] - 1);
+    WinLayout L = msm_windows(c);
+    L.NB = L.maxB;
     L.boff[L.nwin] = L.NB;
     return L;
+}
+// SWM_MSM_TABLE_C: the width for every base set of the process (8 .. 22; tests/test_gpu_switches.py proves with 16 and 18), 0 when unset
+static unsigned msm_forced_table_width() {
+    static const unsigned forced = (unsigned)env_switch("SWM_MSM_TABLE_C", 0, 8, 22);
+    return forced;
 }
 unsigned msm_table_width(size_t n_bases) {
-    // SWM_MSM_TABLE_C: the width for every base set of the process (8 .. 22; tests/test_gpu_switches.py proves with 16 and 18)
-    static const long forced = env_switch("SWM_MSM_TABLE_C", 0, 8, 22);
-    if (forced) return (unsigned)forced;
+    if (const unsigned forced = msm_forced_table_width()) return forced;
     if (n_bases < 512) return 0;  // tiny base sets keep the per-window schedule
     // measured r02 (prove() at 2^10 .. 2^20 constraints, base sets of 3 x that): two bits above the size of the base
     // set up to 2^15 points — 4 .. 10 points per bucket for the MSMs of a proof, which keeps the accumulation chains
@@ -1867,45 +1855,65 @@ int msm_scale_bases_run(swm_ctx* ctx, const G1Affine* d_in, size_t n, G1Affine* 
     return SWM_OK;
 }
 
-int msm_table_build(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsigned c, G1Affine** out) {
+// The rows w = 0 .. W - 1 of the table of d_points[0 .. n) for width c, 2^(bit_w) P each: scaled affine points (row 0 is the plain
+// scaled copy of the set) or, te, twisted Edwards points.  te: *out stays null (and SWM_OK is returned) when a point has no image.
+static int msm_table_rows(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsigned c, bool te, void** out) {
     *out = nullptr;
     if (n == 0 || c < 2) return set_err(ctx, SWM_ERR_INVALID_ARG, "msm table: bad arguments");
     const WinLayout L = msm_table_layout(c);
     const unsigned W = L.nwin;
-    G1Affine* tab = nullptr;
-    hipError_t e = hipMalloc((void**)&tab, (size_t)W * n * sizeof(G1Affine));
+    const size_t row = n * (te ? sizeof(G1TE) : sizeof(G1Affine));
+    char* tab = nullptr;
+    hipError_t e = hipMalloc((void**)&tab, W * row);
     if (e != hipSuccess) (void)hipGetLastError();  // not sticky: the caller falls back to a smaller form
     if (e != hipSuccess) return set_err(ctx, SWM_ERR_OOM, "msm table (%u windows x %zu points): %s", W, n, hipGetErrorString(e));
     G1XYZZ* x = nullptr;
     Fq* pref = nullptr;
-    G1Affine* cur = nullptr;  // 2^(w c) P in the plain form, input of the next shift
+    G1Affine* cur = nullptr;  // 2^(bit_w) P in the plain form, input of the next shift
+    uint32_t* d_bad = nullptr;
+    uint32_t bad = 0;
     int rc = SWM_OK;
     do {
         if ((rc = scratch(ctx, "tab.xyzz", n * sizeof(G1XYZZ), (void**)&x)) != SWM_OK) break;
         if ((rc = scratch(ctx, "tab.pref", n * sizeof(Fq), (void**)&pref)) != SWM_OK) break;
         if ((rc = scratch(ctx, "tab.cur", n * sizeof(G1Affine), (void**)&cur)) != SWM_OK) break;
-        if ((rc = msm_scale_bases_run(ctx, d_points, n, tab)) != SWM_OK) break;
+        if (te && (rc = scratch(ctx, "tab.bad", 64, (void**)&d_bad)) != SWM_OK) break;
+        if (te && hipMemsetAsync(d_bad, 0, 4, ctx->stream) != hipSuccess) {
+            rc = set_err(ctx, SWM_ERR_HIP, "msm table: memset failed");
+            break;
+        }
         const G1Affine* src = d_points;
         const unsigned grid = (unsigned)((n + 255) / 256), gridn = (unsigned)(((n + TAB_NORM_CHUNK - 1) / TAB_NORM_CHUNK + 255) / 256);
-        for (unsigned w = 1; w < W && rc == SWM_OK; w++) {
-            hipLaunchKernelGGL(msm_table_shift, dim3(grid), dim3(256), 0, ctx->stream, src, n, (unsigned)L.c[w - 1], x);
-            hipLaunchKernelGGL(msm_table_normalize, dim3(gridn), dim3(256), 0, ctx->stream, (const G1XYZZ*)x, n, pref, cur);
+        for (unsigned w = 0; w < W && rc == SWM_OK; w++) {
+            if (w > 0) {
+                hipLaunchKernelGGL(msm_table_shift, dim3(grid), dim3(256), 0, ctx->stream, src, n, (unsigned)L.c[w - 1], x);
+                hipLaunchKernelGGL(msm_table_normalize, dim3(gridn), dim3(256), 0, ctx->stream, (const G1XYZZ*)x, n, pref, cur);
+                src = cur;
+            }
+            if (te) hipLaunchKernelGGL(msm_te_convert, dim3(gridn), dim3(256), 0, ctx->stream, src, n, pref, (G1TE*)(tab + w * row), d_bad);
             if (hipGetLastError() != hipSuccess) rc = set_err(ctx, SWM_ERR_HIP, "msm table: launch failed");
-            if (rc == SWM_OK) rc = msm_scale_bases_run(ctx, cur, n, tab + (size_t)w * n);
-            src = cur;
+            if (rc == SWM_OK && !te) rc = msm_scale_bases_run(ctx, src, n, (G1Affine*)(tab + w * row));
         }
-        if (rc == SWM_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_err(ctx, SWM_ERR_HIP, "msm table: sync failed");
+        if (rc == SWM_OK && ((te && hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
+                             hipStreamSynchronize(ctx->stream) != hipSuccess))
+            rc = set_err(ctx, SWM_ERR_HIP, "msm table: sync failed");
     } while (0);
     scratch_release(ctx, "tab.xyzz");
     scratch_release(ctx, "tab.pref");
     scratch_release(ctx, "tab.cur");
-    if (rc != SWM_OK) {
+    if (rc != SWM_OK || bad) {
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipFree(tab);
-        return rc;
+        return rc;  // bad: SWM_OK with *out == nullptr — a point without an image; the caller keeps the XYZZ form
     }
     *out = tab;
     return SWM_OK;
+}
+int msm_table_build(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsigned c, G1Affine** out) {
+    return msm_table_rows(ctx, d_points, n, c, false, (void**)out);
+}
+int msm_table_build_te(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsigned c, G1TE** out) {
+    return msm_table_rows(ctx, d_points, n, c, true, (void**)out);
 }
 
 bool msm_te_enabled() {
@@ -1930,57 +1938,6 @@ int msm_subgroup_check(swm_ctx* ctx, const G1Affine* d_points, size_t n, bool* o
     *ok = h == 0;
     return SWM_OK;
 }
-int msm_table_build_te(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsigned c, G1TE** out) {
-    *out = nullptr;
-    if (n == 0 || c < 2) return set_err(ctx, SWM_ERR_INVALID_ARG, "msm table: bad arguments");
-    const WinLayout L = msm_table_layout(c);
-    const unsigned W = L.nwin;
-    G1TE* tab = nullptr;
-    hipError_t e = hipMalloc((void**)&tab, (size_t)W * n * sizeof(G1TE));
-    if (e != hipSuccess) (void)hipGetLastError();  // not sticky: the caller falls back to a smaller form
-    if (e != hipSuccess) return set_err(ctx, SWM_ERR_OOM, "msm table (%u windows x %zu points): %s", W, n, hipGetErrorString(e));
-    G1XYZZ* x = nullptr;
-    Fq* pref = nullptr;
-    G1Affine* cur = nullptr;  // 2^(bit_w) P in the plain form, input of the next shift
-    uint32_t* d_bad = nullptr;
-    uint32_t bad = 0;
-    int rc = SWM_OK;
-    do {
-        if ((rc = scratch(ctx, "tab.xyzz", n * sizeof(G1XYZZ), (void**)&x)) != SWM_OK) break;
-        if ((rc = scratch(ctx, "tab.pref", n * sizeof(Fq), (void**)&pref)) != SWM_OK) break;
-        if ((rc = scratch(ctx, "tab.cur", n * sizeof(G1Affine), (void**)&cur)) != SWM_OK) break;
-        if ((rc = scratch(ctx, "tab.bad", 64, (void**)&d_bad)) != SWM_OK) break;
-        if (hipMemsetAsync(d_bad, 0, 4, ctx->stream) != hipSuccess) {
-            rc = set_err(ctx, SWM_ERR_HIP, "msm table: memset failed");
-            break;
-        }
-        const G1Affine* src = d_points;
-        const unsigned grid = (unsigned)((n + 255) / 256), gridn = (unsigned)(((n + TAB_NORM_CHUNK - 1) / TAB_NORM_CHUNK + 255) / 256);
-        for (unsigned w = 0; w < W && rc == SWM_OK; w++) {
-            if (w > 0) {
-                hipLaunchKernelGGL(msm_table_shift, dim3(grid), dim3(256), 0, ctx->stream, src, n, (unsigned)L.c[w - 1], x);
-                hipLaunchKernelGGL(msm_table_normalize, dim3(gridn), dim3(256), 0, ctx->stream, (const G1XYZZ*)x, n, pref, cur);
-                src = cur;
-            }
-            hipLaunchKernelGGL(msm_te_convert, dim3(gridn), dim3(256), 0, ctx->stream, src, n, pref, tab + (size_t)w * n, d_bad);
-            if (hipGetLastError() != hipSuccess) rc = set_err(ctx, SWM_ERR_HIP, "msm table: launch failed");
-        }
-        if (rc == SWM_OK && (hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                             hipStreamSynchronize(ctx->stream) != hipSuccess))
-            rc = set_err(ctx, SWM_ERR_HIP, "msm table: sync failed");
-    } while (0);
-    scratch_release(ctx, "tab.xyzz");
-    scratch_release(ctx, "tab.pref");
-    scratch_release(ctx, "tab.cur");
-    if (rc != SWM_OK || bad) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tab);
-        return rc;  // bad: SWM_OK with *out == nullptr — a point without an image; the caller keeps the XYZZ form
-    }
-    *out = tab;
-    return SWM_OK;
-}
-
 // Everything a resident base set needs for its MSMs, in one place (swm_srs_upload, the prover's committer keys):
 //   *c    table width (0: the set is too small, its table would not fit, or n * windows >= 2^31 — per-window schedule only)
 //   *te   twisted Edwards table when the set qualifies (subgroup established, SWM_MSM_TE != 0, it fits): the flat schedule
@@ -1997,7 +1954,7 @@ int msm_install_bases(swm_ctx* ctx, const G1Affine* d_points, size_t n, bool in_
     // replicated item: the table is as many bits narrower as the width rule gives for the rank's share of the set, at most
     // log2(G) - 1.  Measured per rank (tools/ubench/shard_emulate.py, same box): 2^20 constraints, G = 8: c = 20 / 18 / 17 ->
     // 23.7 / 20.9 / 20.9 ms; G = 4: flat; 2^22 constraints (1.5 M points per rank and more): 20 stays best (18: + 3 %).
-    if (*c > 12 && ctx->shard_world >= 4 && !env_switch("SWM_MSM_TABLE_C", 0, 8, 22)) {
+    if (*c > 12 && ctx->shard_world >= 4 && !msm_forced_table_width()) {
         unsigned lg = 0;
         while ((2u << lg) <= ctx->shard_world) lg++;
         const unsigned share = msm_table_width(std::max<size_t>(n / ctx->shard_world, 512));
@@ -2067,13 +2024,11 @@ static int streams_concurrent(swm_ctx* ctx, hipStream_t x, hipStream_t y, bool* 
 
 
 // ---- asynchronous form -------------------------------------------------------------------------------------
-// msm_enqueue launches every kernel of one MSM plus the download of its window sums WITHOUT host synchronisation;
-// msm_finish waits for that download and does the host Horner fold.  `lane` selects the stream + device scratch set:
-//   lane < 0 : the context's own stream (what the K1 ABI entry points use);
-//   lane >= 0: one of MSM_LANES auxiliary streams; it first waits for everything enqueued on the context's stream so far.
-// The prover alternates lanes, so that the latency-bound tail of one MSM (bucket fold, window reduction, download)
-// and the sort of the next overlap with the VALU-bound accumulation.  Scratch is per lane (stream-ordered reuse);
-// results land in per-job pinned host slots.
+// msm_enqueue launches every kernel of one MSM plus the download of its window sums WITHOUT host synchronisation (shape,
+// result slot, streams, scratch, the stages, the tail hand-off); msm_finish waits for that download and does the host fold.
+// `lane` selects the streams and the device scratch set: lane < 0, the context's own stream (the K1 ABI entry points);
+// lane >= 0, the auxiliary streams, after everything enqueued on the context's stream so far.  The prover alternates lanes, so
+// that the tail of one MSM and the sort of the next overlap with the VALU-bound accumulation.  Results land in pinned host slots.
 // Stream of one of the roles main / sort / accumulation / tail: non-blocking, default priority (stream priorities per role were
 // measured in r04 / r05 — every assignment slower, CHANGELOG.md — and are gone; what orders the kernels on the chip is s_setprio).
 hipError_t msm_create_stream(hipStream_t* out) { return hipStreamCreateWithFlags(out, hipStreamNonBlocking); }
@@ -2082,68 +2037,66 @@ bool msm_flat_applies(const MsmTable& tab, size_t n) {
     return tab.any() && !no_table && n >= ((size_t)1 << (tab.c > 8 ? tab.c - 8 : 0)) &&
            (uint64_t)tab.stride * msm_table_windows(tab.c) < (1ull << 31);
 }
-int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine* d_bases28, const void* d_scalars, size_t n,
-                int mont, MsmJob* job, MsmInfMask inf, bool defer_tail, MsmTable tab, MsmTwin twin) {
-    job->active = false;
-    job->tail_pending = false;
-    job->n = n;
-    job->twin = MsmTwinSrc();
-    job->twin_copied = nullptr;
-    job->twin_kept_lane = false;
-    if (n == 0) return SWM_OK;
-    if (n >= (1ull << 31)) return set_err(ctx, SWM_ERR_INVALID_ARG, "msm: n must be < 2^31");
-    ctx->stat_msm_calls++;
-    ctx->stat_msm_points += n;
-    ctx->log_call('m', n);
-    struct SinceWait {  // (counted when this call returns: the choices below see the jobs BEFORE this one)
-        swm_ctx* c;
-        ~SinceWait() { c->msm_since_wait++; }
-    } since_wait{ctx};
-    // the job before this one waited to learn whether anything follows it: something does, so its bucket stage takes the
-    // thin shape that runs BESIDE this job's sort and accumulation (msm_tail_shape)
-    SWM_TRY(msm_launch_lazy_tail(ctx, false));
+// Makes `st` the context's stream for a scope, so that launches, memsets, scratch growth and the profiling events all refer to it.
+struct StreamSwap {
+    swm_ctx* c;
+    hipStream_t old;
+    StreamSwap(swm_ctx* ctx, hipStream_t st) : c(ctx), old(ctx->stream) { ctx->stream = st; }
+    ~StreamSwap() { c->stream = old; }
+};
+// Bucket stage of maxB buckets on workgroups of rb chains: *log_m (log2 buckets per lane) raised until the stage fits in max_blocks
+// workgroups per window; returns the workgroups per window.
+static unsigned bucket_blocks(uint32_t maxB, unsigned rb, unsigned max_blocks, unsigned* log_m) {
+    while (((maxB >> *log_m) + rb - 1) / rb > max_blocks) (*log_m)++;
+    return std::max(1u, ((maxB >> *log_m) + rb - 1) / rb);
+}
+// A job's pinned result slot: up to 1024 (A, R) pairs, the last 16 bytes carry the status words of the job.
+static constexpr size_t SLOT_BYTES = (size_t)MAX_WIN * 32 * sizeof(G1XYZZ) + 64;
+static constexpr size_t SLOT_FLAGS_OFF = SLOT_BYTES - 16;
+
+// ---- shape: every decision about one MSM, made by msm_shape (which says what each field is); the bucket-stage fields are MsmJob's.
+struct MsmShape {
+    bool flat, te, lat, quad, low, quad_acc, one_stream, two_level;
+    int lane;
+    WinLayout pl, rl;
+    size_t total, wpart_n, nseg_max;
+    unsigned rb, max_blocks, log_m, red_blocks, blk_lo, blk_hi, blk_low, log_g, scan_tiles, flat_fb;
+    uint32_t SEG, big_nseg, flat_bins;
+    DigitShard dshard;
+    BinPlan bp;
+};
+// Fills *out for an MSM of n points on `tab`.  Launches and allocates nothing: reads ctx->msm_pipe_min and the switches only.
+static int msm_shape(swm_ctx* ctx, size_t n, const MsmTable& tab, int lane, bool defer_tail, MsmShape* out) {
+    MsmShape& s = *out = MsmShape();
     // flat schedule: the base set comes with its precomputed window multiples and the MSM is large enough to populate the
     // shared bucket set (below ~2^(c-4) points the per-window schedule with its small windows wins)
-    const bool flat = msm_flat_applies(tab, n);
-    const bool te = flat && tab.te != nullptr;  // twisted Edwards rows: accumulation and bucket stage run in that form
-    job->te = te;
-    // Twin jobs (msm.h): LEAD writes the follower's sorted array beside its own, FOLLOW copies the lead's descriptors.  Any
-    // mismatch of the shapes leaves both on the ordinary schedule.  SWM_MSM_TWIN=0: never.
-    static const bool twin_on = env_switch("SWM_MSM_TWIN", 1, 0, 1) != 0;
-    // (from 2^15 points: below, a proof is a chain of launches and the follower's wait for the lead's sort costs more than its own
-    // sort beside it — 2^14 constraints 3.88 -> 4.0 ms, 2^16 6.58 -> 6.49 ms, r06)
-    static constexpr size_t twin_min = 32768;
-    const bool twin_shape = twin_on && n >= twin_min && lane >= 0 && flat && te && tab.contiguous() && tab.scalar_stride == 1 && tab.shard_world <= 1 && !inf.mask;
-    const bool lead = twin_shape && twin.role == MsmTwin::LEAD && twin.tab2.te && twin.tab2.c == tab.c && twin.tab2.contiguous() &&
-                      twin.tab2.scalar_stride == 1 && twin.tab2.shard_world <= 1 && msm_flat_applies(twin.tab2, n) &&
-                      twin.tab2.offset + n <= twin.tab2.stride && tab.offset + n <= tab.stride;
-    MsmJob* const tsrc = twin_shape && twin.role == MsmTwin::FOLLOW ? twin.lead : nullptr;
-    bool follow = tsrc && tsrc != job && tsrc->active && tsrc->twin.ready && tsrc->twin.scalars == d_scalars && tsrc->n == n &&
-                  tsrc->twin.mont == mont && tsrc->twin.c == tab.c && tsrc->twin.te2 == tab.te && tsrc->twin.stride2 == tab.stride &&
-                  tsrc->twin.offset2 == tab.offset;
-    if (!tab.contiguous() && !flat)
+    s.flat = msm_flat_applies(tab, n);
+    s.te = s.flat && tab.te != nullptr;
+    if (!tab.contiguous() && !s.flat)
         return set_err(ctx, SWM_ERR_INTERNAL, "msm: a strided base layout needs the precomputed-window schedule");
+    if (tab.scalar_stride != 1 && !s.flat) return set_err(ctx, SWM_ERR_INTERNAL, "msm: strided scalars need the table schedule");
+    if (tab.shard_world > 1 && (!s.flat || !tab.contiguous()))
+        return set_err(ctx, SWM_ERR_INTERNAL, "msm: a bucket-range split needs the table schedule");
     // low-latency schedule (flat MSMs below ~2^18 points, where a proof is a chain of dependent additions rather than
     // a throughput problem): short segments (8 points), every bucket with more than two segments folded by a lane
     // group in msm_big_bucket_sum (a tree instead of the serial walk of the bucket stage), one bucket per lane in the
     // bucket stage
     static constexpr size_t lat_below = 262144;
-    const bool lat = flat && n < lat_below;
-    WinLayout pl = flat ? msm_table_layout(tab.c) : msm_plan(n);
+    s.lat = s.flat && n < lat_below;
+    const WinLayout& pl = s.pl = s.flat ? msm_table_layout(tab.c) : msm_plan(n);
     // rl: the layout the bucket stage and the host fold see — one window of 2^(c-1) buckets in the flat schedule
-    WinLayout rl = pl;
-    if (flat) {
-        rl.nwin = 1;
-        rl.boff[1] = rl.NB;
+    s.rl = pl;
+    if (s.flat) {
+        s.rl.nwin = 1;
+        s.rl.boff[1] = s.rl.NB;
     }
-    const size_t total = n * (size_t)pl.nwin;
-    ctx->stat_msm_digits += total;
-    if (total >= (1ull << 32)) return set_err(ctx, SWM_ERR_INVALID_ARG, "msm: n * windows must be < 2^32");
+    s.total = n * (size_t)pl.nwin;
+    if (s.total >= (1ull << 32)) return set_err(ctx, SWM_ERR_INVALID_ARG, "msm: n * windows must be < 2^32");
     // buckets per lane in the reduction: at most 16 workgroups per window (the host folds one (A, R) pair per workgroup)
     // small windows: one bucket per lane shortens the serial walk of a lone MSM (r01 sweep); inside a round's batch the
     // workgroups of all jobs have to be resident together (one per CU: 96 KB of LDS each), which four buckets per lane allow
     unsigned log_m = pl.maxB <= 2048 ? (defer_tail ? 2 : 0) : 2;
-    if (lat) log_m = 0;
+    if (s.lat) log_m = 0;
     // (A, R) pairs per window that fit a result slot and that the host folds: 16 per window, or 256 for the single
     // window of the flat schedule (one workgroup per CU either way)
     // workgroup width of the bucket stage: 256 lanes (single-wave workgroups of 64 lanes were measured in r02: the stage 1.00
@@ -2153,9 +2106,8 @@ int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine*
     // job, bucket sets up to 2^15 (r04 sweeps, CHANGELOG.md).
     static const bool quad_on = env_switch("SWM_MSM_QUAD", 1, 0, 1) != 0;
     static constexpr unsigned quad_rb = 128u, quad_blocks = 64u, quad_maxb = 32768u;
-    const bool quad = lat && te && quad_on && pl.maxB <= quad_maxb;
-    const unsigned rb = quad ? quad_rb : 256u;
-    job->quad = quad;
+    s.quad = s.lat && s.te && quad_on && pl.maxB <= quad_maxb;
+    s.rb = s.quad ? quad_rb : 256u;
     // One-lane twisted Edwards stages may take the low-LDS kernel (msm_bucket_reduce_low: 49 KB per workgroup);
     // SWM_MSM_LOW=0: always the 144-KB kernel of r02 - r04.  SWM_MSM_LOW_BLOCKS: workgroups a stage may be cut into (result slot:
     // up to 1024 (A, R) pairs; the host folds them in groups of 16).
@@ -2170,26 +2122,14 @@ int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine*
     // (r02) and for the larger jobs that join a round's launch since r05 (up to 10^6 points: 2^19 buckets -> 32 per lane).  With the
     // low-LDS kernel 128 per job (two workgroups per CU) measured SLOWER per launch: 1.43 against 1.06 ms for four 2^19-bucket jobs.
     static constexpr unsigned joint_blocks = 64u;
-    const bool low = te && !quad && rb == 256 && low_on;
-    job->low = low;
+    s.low = s.te && !s.quad && s.rb == 256 && low_on;
     // (low-latency schedule: the bucket stages of a round's four MSMs run in one launch and have to be resident together)
-    const unsigned max_blocks = quad ? quad_blocks : (flat ? (defer_tail ? joint_blocks : (low ? low_blocks : 256u)) : 16u);
-    job->max_blocks = low ? std::max(max_blocks, low_blocks) : std::max(max_blocks, 256u);
-    while (((pl.maxB >> log_m) + rb - 1) / rb > max_blocks) log_m++;
-    unsigned red_blocks = ((pl.maxB >> log_m) + rb - 1) / rb;
-    if (red_blocks == 0) red_blocks = 1;
-    // ---- stage set-up.  An asynchronous MSM (lane >= 0) is a three-stage pipeline over three auxiliary streams:
-    //   S  digits + counting sort          (HBM / LDS-atomic bound)
-    //   A  segment planning + accumulation (saturates the integer pipes)      waits for the job's sort
-    //   T  bucket stage + download         (a latency-bound chain at one wave per SIMD)   waits for the job's accumulation
-    // so that consecutive jobs keep stage A busy back to back while the tail of the previous job and the sort of the
-    // next one run beside it.  (r02 timeline: with two lanes that each ran sort -> accumulate -> tail in order, both
-    // lanes reached their tails together and ~10 ms of bucket stage per 2^20 proof ran with nothing beside it.)
-    // `lane` only selects the scratch set of the per-lane buffers (two sets: a job's sort may overwrite a set once
-    // the accumulation that last read it has finished).  lane < 0: everything on the context's stream (K1 ABI).
-    hipStream_t main_stream = ctx->stream;
-    hipStream_t st_sort = main_stream, st_acc = main_stream, st_tail = main_stream;
-    // S | A0, A1 by lane | T (two accumulations may overlap: one alone leaves bubbles at the end of its length-sorted grid).
+    const unsigned max_blocks = s.quad ? quad_blocks : (s.flat ? (defer_tail ? joint_blocks : (s.low ? low_blocks : 256u)) : 16u);
+    s.max_blocks = s.low ? std::max(max_blocks, low_blocks) : std::max(max_blocks, 256u);
+    s.red_blocks = bucket_blocks(pl.maxB, s.rb, max_blocks, &log_m);
+    s.log_m = log_m;
+    s.wpart_n = (size_t)s.rl.nwin * std::max(s.red_blocks, s.flat ? s.max_blocks : 0u) * 2;
+    if (s.wpart_n * sizeof(G1XYZZ) > SLOT_FLAGS_OFF) return set_err(ctx, SWM_ERR_INTERNAL, "msm: result slot too small");
     // Small MSMs keep a single stream: the extra event hops cost more than they hide.
     // r05: a proof whose commitments fall on both sides of the bound ran them on streams that alias (a small job's lane stream is
     // a large job's accumulation or bucket-stage stream): at 2^16 constraints — 65 535-point and 196 608-point commitments — the
@@ -2197,198 +2137,64 @@ int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine*
     // commitment of a proof up to 2^19 constraints on one stream of its lane, four lanes: 2^16 7.05 -> 6.5 ms, 2^19 29.4 -> 28.6 ms;
     // from 2^20 on the three-stage pipeline is ahead).
     const size_t pipe_min = ctx->msm_pipe_min ? ctx->msm_pipe_min : (size_t)131072;
-    const bool one_stream = n < pipe_min;
-    if (lane >= 0) {
-        // small MSMs: four single-stream lanes (scratch sets 0 .. 3 on the streams 1, 2, 3, 0), so that the launch chains of
-        // all four commitments of a prover round proceed side by side; sets 0 and 1 are shared with the pipelined form,
-        // whose accumulations run on the same streams 1 and 2 (stream order covers the reuse)
-        static constexpr int small_lanes = 4;
-        // scratch sets of the pipelined form: two — the sort of job k + 2 waits for the accumulation of job k (four sets, the
-        // sorts running further ahead, measured nothing in r04; memory: ~110 B per digit and set)
-        static constexpr int sets = 2;
-        lane %= one_stream ? small_lanes : sets;
-        if (!ctx->aux_stream[0]) {
-            // Hardware-queue placement.  ROCm 7 hands its hardware queues (four by default) to streams in creation order,
-            // bouncing: 1, 2, 3, 4, 4, 3, 2, 1, ... (rocprofv3 Queue_Id, r02).  With the context's stream and the null stream
-            // first, four auxiliary streams created in a row put the sort and the tail stream on ONE queue: tail(k) and
-            // sort(k+1) — the two phases that run between consecutive accumulations — executed one after the other
-            // (2^20 proofs: 73.0 instead of 70.1 ms).  Wanted: the context's stream, the sort stream, the first accumulation
-            // stream and the tail stream on four different queues (the second accumulation stream may share: accumulations
-            // cannot overlap, each fills the register files).  A placeholder stream before the tail stream gives that in the
-            // usual creation history; the result is PROBED (streams_concurrent) and a stream that shares a queue with an
-            // earlier role is replaced by a fresh one, a few times at most — whatever streams the host application created
-            // before.
-            static constexpr bool steer = true;
-            // The four streams are created and probed into locals and published to the context only when all of it
-            // succeeded: a failure half way must not leave aux_stream[0] set with the later entries null (every later MSM
-            // would skip this block and silently run its tail on the legacy default stream).
-            hipStream_t aux[swm_ctx::MSM_LANES] = {nullptr, nullptr, nullptr, nullptr};
-            auto setup = [&]() -> int {
-                for (int i = 0; i < 3; i++) SWM_HIP(ctx, msm_create_stream(&aux[i]));
-                if (steer) {
-                    hipStream_t ph = nullptr;
-                    SWM_HIP(ctx, hipStreamCreateWithFlags(&ph, hipStreamNonBlocking));
-                    ctx->spare_streams.push_back(ph);
-                }
-                SWM_HIP(ctx, msm_create_stream(&aux[3]));
-                if (steer) {
-                    SWM_HIP(ctx, hipStreamSynchronize(main_stream));
-                    const int roles[3] = {0, 1, 3};  // sort, accumulation 0, tail
-                    std::vector<hipStream_t> fixed = {main_stream};
-                    int budget = 8;  // replacement streams at most
-                    for (int r : roles) {
-                        for (;;) {
-                            bool clash = false;
-                            for (hipStream_t f : fixed) {
-                                bool conc = true;
-                                SWM_TRY(streams_concurrent(ctx, f, aux[r], &conc));
-                                if (!conc) {
-                                    clash = true;
-                                    break;
-                                }
-                            }
-                            if (!clash || budget-- <= 0) break;
-                            ctx->spare_streams.push_back(aux[r]);  // kept alive: destroying it would free its slot
-                            aux[r] = nullptr;
-                            SWM_HIP(ctx, msm_create_stream(&aux[r]));
-                        }
-                        fixed.push_back(aux[r]);
-                    }
-                }
-                return SWM_OK;
-            };
-            const int src = setup();
-            if (src != SWM_OK) {
-                for (hipStream_t a : aux)
-                    if (a) ctx->spare_streams.push_back(a);  // destroyed with the context
-                return src;
-            }
-            for (int i = 0; i < swm_ctx::MSM_LANES; i++) ctx->aux_stream[i] = aux[i];
-        }
-        if (one_stream) {
-            // lanes 0, 1, 2 on three different hardware queues (accumulation 0, tail, sort); lane 3 shares the
-            // second accumulation stream's queue
-            static const int lane_stream[4] = {1, 3, 0, 2};
-            st_sort = st_acc = st_tail = ctx->aux_stream[lane_stream[lane]];
-        } else {
-            st_sort = ctx->aux_stream[0];
-            st_acc = ctx->aux_stream[1 + (lane & 1)];
-            st_tail = ctx->aux_stream[3];  // (a second bucket-stage stream: 51.4 -> 57.4 ms at 2^20, r05)
-        }
-        if (!ctx->fork_event) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->fork_event, hipEventDisableTiming));
-        SWM_HIP(ctx, hipEventRecord(ctx->fork_event, main_stream));
-        SWM_HIP(ctx, hipStreamWaitEvent(st_sort, ctx->fork_event, 0));  // the scalars are ready
-        // (the waits for the previous readers of this lane's scratch set: below, once it is known whether the job uses the set)
-    }
-    hipStream_t st = st_sort;
-    const size_t slot_bytes = (size_t)MAX_WIN * 32 * sizeof(G1XYZZ) + 64;  // up to 1024 (A, R) pairs + status words
-    const size_t flags_off = slot_bytes - 16;  // the last 16 bytes of a slot carry the status words of the job
-    if ((size_t)rl.nwin * std::max(red_blocks, flat ? job->max_blocks : 0u) * 2 * sizeof(G1XYZZ) > flags_off) return set_err(ctx, SWM_ERR_INTERNAL, "msm: result slot too small");
-    if (!ctx->pinned) {  // coherent + mapped: the bucket stage writes its results straight into the slots
-        SWM_HIP(ctx, hipHostMalloc(&ctx->pinned, slot_bytes * swm_ctx::MSM_SLOTS, hipHostMallocCoherent | hipHostMallocMapped));
-        SWM_HIP(ctx, hipHostGetDevicePointer(&ctx->pinned_dev, ctx->pinned, 0));
-    }
-    int slot = ctx->next_slot;
-    if (ctx->slot_busy[slot])  // its previous job has not been collected: the download would overwrite live results
-        return set_err(ctx, SWM_ERR_INTERNAL, "msm: more than %d jobs in flight", swm_ctx::MSM_SLOTS);
-    ctx->next_slot = (ctx->next_slot + 1) % swm_ctx::MSM_SLOTS;
-    if (!ctx->slot_event[slot]) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->slot_event[slot], hipEventDisableTiming));
-    job->slot = slot;
-    job->host = reinterpret_cast<G1XYZZ*>((char*)ctx->pinned + slot_bytes * slot);
-    job->host_flags = reinterpret_cast<const uint32_t*>((char*)job->host + flags_off);
-    job->host_dev = reinterpret_cast<G1XYZZ*>((char*)ctx->pinned_dev + slot_bytes * slot);
-    job->host_flags_dev = reinterpret_cast<uint32_t*>((char*)job->host_dev + flags_off);
-    // the bucket stage writes its results straight into the pinned slot (see msm_bucket_reduce; against stream-ordered copies,
-    // r02 on one box: 2^16 proofs 11.4 vs 11.8 ms, 2^20 75.1 vs 75.7 ms)
-    job->done = ctx->slot_event[slot];
-    if (!ctx->acc_event[slot]) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->acc_event[slot], hipEventDisableTiming));
-    job->acc_done = ctx->acc_event[slot];
-    if (!ctx->sort_event[slot]) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->sort_event[slot], hipEventDisableTiming));
-    job->stream = st_tail;
-    job->pl = rl;
-    job->red_blocks = red_blocks;
-    job->blk_lo = 0;
-    job->blk_hi = red_blocks;
-    job->blk_low = 0;
-    if (tab.scalar_stride != 1 && !flat) return set_err(ctx, SWM_ERR_INTERNAL, "msm: strided scalars need the table schedule");
-    DigitShard dshard{};
+    s.one_stream = n < pipe_min;
+    // small MSMs: four single-stream lanes (scratch sets 0 .. 3 on the streams 1, 2, 3, 0), so that the launch chains of
+    // all four commitments of a prover round proceed side by side; sets 0 and 1 are shared with the pipelined form,
+    // whose accumulations run on the same streams 1 and 2 (stream order covers the reuse)
+    static constexpr int small_lanes = 4;
+    // scratch sets of the pipelined form: two — the sort of job k + 2 waits for the accumulation of job k (four sets, the
+    // sorts running further ahead, measured nothing in r04; memory: ~110 B per digit and set)
+    static constexpr int sets = 2;
+    s.lane = lane < 0 ? lane : lane % (s.one_stream ? small_lanes : sets);
+    s.blk_hi = s.red_blocks;  // (blk_lo = blk_low = 0: no bucket-range split)
     if (tab.shard_world > 1) {
-        if (!flat || !tab.contiguous()) return set_err(ctx, SWM_ERR_INTERNAL, "msm: a bucket-range split needs the table schedule");
         const unsigned G = tab.shard_world, g = tab.shard_rank;
-        const uint64_t span = (uint64_t)rb << log_m;  // buckets per bucket-stage workgroup
-        job->blk_lo = (unsigned)((uint64_t)red_blocks * g / G);
-        job->blk_hi = (unsigned)((uint64_t)red_blocks * (g + 1) / G);
+        const uint64_t span = (uint64_t)s.rb << s.log_m;  // buckets per bucket-stage workgroup
+        s.blk_lo = (unsigned)((uint64_t)s.red_blocks * g / G);
+        s.blk_hi = (unsigned)((uint64_t)s.red_blocks * (g + 1) / G);
         unsigned cfull = 0, cnarrow = 0;
         for (unsigned w = 0; w < pl.nwin; w++) cfull = std::max<unsigned>(cfull, pl.c[w]);
         for (unsigned w = 0; w < pl.nwin; w++)
             if (pl.c[w] < cfull) cnarrow = std::max<unsigned>(cnarrow, pl.c[w]);
-        if (cnarrow) job->blk_low = (unsigned)((((uint64_t)1 << (cnarrow - 1)) + span - 1) / span);  // digits of a narrow window: buckets < 2^(c - 1)
-        dshard.on = 1;
-        dshard.cfull = cfull;
-        dshard.blo = (uint32_t)std::min<uint64_t>(job->blk_lo * span, pl.NB);
-        dshard.bhi = (uint32_t)std::min<uint64_t>(job->blk_hi * span, pl.NB);
-        dshard.plo = (uint64_t)(((unsigned __int128)n * g) / G);
-        dshard.phi = (uint64_t)(((unsigned __int128)n * (g + 1)) / G);
-    }
-    job->log_m = log_m;
-    job->rb = rb;
-
-    // everything below is enqueued on `st`: temporarily make it the context's stream so that launches, memsets,
-    // scratch growth and the profiling events all refer to it
-    struct StreamSwap {
-        swm_ctx* c;
-        hipStream_t old;
-        ~StreamSwap() { c->stream = old; }
-    } swap{ctx, main_stream};
-    ctx->stream = st;
-    char nm[10][32];
-    const char* base[10] = {"hist", "segs", "bucket_off", "seg_off", "digits", "sorted", "scan_tot", "big_list", "points", "pairs"};
-    // Per-slot buffers are sized by the LARGEST request any slot has seen, not by the job at hand (r05): the eight result slots
-    // rotate through the jobs of successive proofs (15 jobs per Merkle-circuit proof: a slot meets a different commitment every
-    // proof), and a slot that had only held 131 072-point jobs grew — all streams synchronised, hipFree, hipMalloc: 2.4 ms with
-    // the GPU idle — when a 786 432-point job reached it, somewhere in each of the first dozen proofs of a key.
-    auto slot_scratch = [&](int kind, size_t bytes) {
-        if (bytes > ctx->msm_slot_bytes[kind]) ctx->msm_slot_bytes[kind] = bytes;
-        return ctx->msm_slot_bytes[kind];
-    };
-    // what the deferred bucket stage of a job still reads (histogram block with the status words, bucket / segment offsets,
-    // big-bucket list, partial sums) is kept per result SLOT; the rest is per lane (stream-ordered reuse)
-    for (int i = 0; i < 10; i++) {
-        const bool per_slot = i == 0 || i == 2 || i == 3 || i == 7 || i == 8;
-        snprintf(nm[i], sizeof(nm[i]), per_slot ? "msmS%d.%s" : "msm%d.%s", per_slot ? slot : (lane < 0 ? 9 : lane), base[i]);
+        if (cnarrow) s.blk_low = (unsigned)((((uint64_t)1 << (cnarrow - 1)) + span - 1) / span);  // digits of a narrow window: buckets < 2^(c - 1)
+        s.dshard.on = 1;
+        s.dshard.cfull = cfull;
+        s.dshard.blo = (uint32_t)std::min<uint64_t>(s.blk_lo * span, pl.NB);
+        s.dshard.bhi = (uint32_t)std::min<uint64_t>(s.blk_hi * span, pl.NB);
+        s.dshard.plo = (uint64_t)(((unsigned __int128)n * g) / G);
+        s.dshard.phi = (uint64_t)(((unsigned __int128)n * (g + 1)) / G);
     }
 
     // Segment bound.  Long segments mean one partial sum per bucket (the bucket stage walks fewer partials) but fewer,
     // longer lanes in the accumulation; they pay once the buckets alone oversubscribe the chip (r01 sweep: 128 beats
     // 32 by 10 % at 2^20 and 2^22, loses at 2^16 where 45 k buckets cannot fill 196 k lane slots).
-    uint32_t SEG = pl.NB >= 262144 ? SEG_MAX : 32;  // smaller bounds for small MSMs measured within run-to-run noise
-    if (lat) SEG = 16;  // (8 below 2^16 points until r04: with four lanes per segment the chain per entry is 2 products, not 7)
+    s.SEG = pl.NB >= 262144 ? SEG_MAX : 32;  // smaller bounds for small MSMs measured within run-to-run noise
+    if (s.lat) s.SEG = 16;  // (8 below 2^16 points until r04: with four lanes per segment the chain per entry is 2 products, not 7)
     // (r05, prefix tables: a job of |H| points on a table one bit narrower than before has ~14 entries per bucket — with 16-point
     // segments a quarter of the buckets would split in two and the bucket stage walk 2.3 instead of 2 steps per bucket)
-    if (lat && total / pl.NB >= 10) SEG = 32;
+    if (s.lat && s.total / pl.NB >= 10) s.SEG = 32;
     // segments per bucket above which a bucket is folded ahead of the bucket stage, and the lanes that fold one
-    uint32_t big_nseg = BIG_NSEG;
-    unsigned log_g = 8;
-    if (lat) {
+    s.big_nseg = BIG_NSEG;
+    s.log_g = 8;
+    if (s.lat) {
         // every bucket with more than two segments below 2^16 points; from there (16-point segments, 1 - 2 per bucket) only
         // the rare long ones: listing ~2 % of the buckets cost a ~120-us launch per MSM for a two-step shorter walk
         // (r02: 2^16 proofs 11.5 -> 10.8 ms)
-        big_nseg = n < 65536 ? 4 : 6;  // (2 with 8-point segments, until r04)
-        const size_t per_bucket = total / ((size_t)pl.NB * SEG) + 1;  // expected segments per bucket
-        log_g = 2;
-        while (log_g < 6 && ((size_t)1 << log_g) < 2 * per_bucket) log_g++;
+        s.big_nseg = n < 65536 ? 4 : 6;  // (2 with 8-point segments, until r04)
+        const size_t per_bucket = s.total / ((size_t)pl.NB * s.SEG) + 1;  // expected segments per bucket
+        s.log_g = 2;
+        while (s.log_g < 6 && ((size_t)1 << s.log_g) < 2 * per_bucket) s.log_g++;
     }
-    job->big_nseg = big_nseg;
+    // small jobs (up to 2^20 digits: r04 sweep): four lanes per segment
+    static constexpr size_t quad_acc = 1048576;
+    s.quad_acc = s.te && s.lat && s.total <= quad_acc && quad_on;
     // every bucket adds at most one short segment; the flat schedule hands out segment indices per coarse bin with the bin's
     // capacity (msm_flat_scan_bins): at most one more per bucket slot of the (padded) bins
-    const size_t nseg_max = total / SEG + pl.NB + 1 + (flat ? FLAT_MAX_FINE + FLAT_MAX_BINS : 0);
-    uint32_t *hist, *cursor, *big_count, *len_hist, *bucket_off, *seg_off, *digits, *sorted, *big_list, *tot_cnt, *tot_seg;
-    uint32_t *seg_start, *seg_len, *order;
+    s.nseg_max = s.total / s.SEG + pl.NB + 1 + (s.flat ? FLAT_MAX_FINE + FLAT_MAX_BINS : 0);
+    s.scan_tiles = (pl.NB + SCAN_TILE - 1) / SCAN_TILE;
     // two-level scatter for large MSMs (see msm_partition): bins of ~8 k entries, sized per window
-    bool two_level = !flat && n >= 262144 && pl.maxB >= 8192;
-    BinPlan bp;
-    memset(&bp, 0, sizeof(bp));
-    if (two_level) {
+    s.two_level = !s.flat && n >= 262144 && pl.maxB >= 8192;
+    if (s.two_level) {
         uint32_t target = 64;  // bins per full window: next power of two >= n / 8192, within [64, PART_MAX_BINS]
         while (target < PART_MAX_BINS && (size_t)target * 8192 < n) target <<= 1;
         for (unsigned w = 0; w < pl.nwin; w++) {
@@ -2412,275 +2218,474 @@ int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine*
             if (fb > 7) fb = 7;
             uint32_t nb = (beff + (1u << fb) - 1) >> fb;
             if (nb > PART_MAX_BINS) {
-                two_level = false;
+                s.two_level = false;
                 break;
             }
-            bp.fb[w] = (uint8_t)fb;
-            bp.nbins[w] = (uint16_t)nb;
-            bp.max_nbins = std::max(bp.max_nbins, nb);
+            s.bp.fb[w] = (uint8_t)fb;
+            s.bp.nbins[w] = (uint16_t)nb;
+            s.bp.max_nbins = std::max(s.bp.max_nbins, nb);
         }
     }
-    const uint32_t maxbins = two_level ? PART_MAX_BINS : 0;
-    // flat schedule: coarse bins of the shared bucket set (<= 4096 bins, <= 512 buckets each, ~8 k entries per bin)
-    unsigned flat_fb = 0;
-    uint32_t flat_bins = 0;
-    if (flat) {
+    if (s.flat) {
+        // flat schedule: coarse bins of the shared bucket set (<= 4096 bins, <= 512 buckets each, ~8 k entries per bin)
         // as few bins as the LDS of msm_flat_bin_sort allows (FLAT_BIN_CAP entries): every (tile, bin) run of the partition
         // costs one global atomic, and with ~2 entries per run those atomics (27 M at 2^22 points) were the whole kernel
         static constexpr size_t bin_target = 28000;  // (14 000: 52.3 - 52.5 vs 51.4 ms at 2^20, r04)
         // (small MSMs: at least ~1024 bins as long as a bin keeps 1024 entries — 64 bins meant 64 workgroups in the bin
         // sort and 1024 lanes contending for 64 LDS counters in the coarse histogram)
-        const size_t target = std::min(bin_target, std::max<size_t>(1024, total / 1024));
+        const size_t target = std::min(bin_target, std::max<size_t>(1024, s.total / 1024));
         uint32_t want = 64;
-        while (want < FLAT_MAX_BINS && (size_t)want * target < total) want <<= 1;
-        while ((pl.NB >> flat_fb) > want) flat_fb++;
-        while ((1u << flat_fb) > FLAT_MAX_FINE) flat_fb--;  // keeps the fine-count arrays of msm_flat_bin_sort within LDS
-        flat_bins = (pl.NB + (1u << flat_fb) - 1) >> flat_fb;
-        if (flat_bins > FLAT_MAX_BINS) return set_err(ctx, SWM_ERR_INTERNAL, "msm: too many coarse bins");
+        while (want < FLAT_MAX_BINS && (size_t)want * target < s.total) want <<= 1;
+        while ((pl.NB >> s.flat_fb) > want) s.flat_fb++;
+        while ((1u << s.flat_fb) > FLAT_MAX_FINE) s.flat_fb--;  // keeps the fine-count arrays of msm_flat_bin_sort within LDS
+        s.flat_bins = (pl.NB + (1u << s.flat_fb) - 1) >> s.flat_fb;
+        if (s.flat_bins > FLAT_MAX_BINS) return set_err(ctx, SWM_ERR_INTERNAL, "msm: too many coarse bins");
+        if (pl.nwin > FLAT_CUR_STRIDE) return set_err(ctx, SWM_ERR_INTERNAL, "msm: too many windows for the flat sort");
     }
-    size_t zero_words = 2 * (size_t)(pl.NB + 1) + 4 + 2 * (size_t)(SEG_MAX + 1) * LEN_STRIDE + MAX_WIN + (size_t)pl.nwin * maxbins +
-                              (flat ? (2 + 3 * (size_t)FLAT_CUR_STRIDE) * FLAT_MAX_BINS + 4 + 32 : 0);
-    zero_words = (zero_words + 63) & ~(size_t)63;  // whole 256-byte lines: the runtime then clears them with one kernel, not two
-    // the follower's arrays must have the geometry of the lead's
-    follow = follow && tsrc->twin.zero_words == zero_words && tsrc->twin.nseg_max == nseg_max && tsrc->twin.SEG == SEG &&
-             tsrc->twin.big_nseg == big_nseg && tsrc->twin.flat_bins == flat_bins;
+    return SWM_OK;
+}
+
+// ---- scratch of a job
+// The block a job zeroes before its sort (one fill, per result slot), as word offsets: hist [NB + 1] entries per bucket | cursor
+// [NB + 1] (msm_scatter) | big_count [4]: oversized buckets, the two status words (msm_digits), segments that hold entries (the
+// count of msm_seg_order) | len_hist, len_cursor: the segments per length and the run cursors of msm_seg_order, one per length
+// class | two_level_bad: one flag per window, then bin_cursor: the per-(window, bin) cursors | flat schedule: [windows x bins]
+// counts (room for 32 windows) | [bins x 32] offsets | [bins x 32] cursors (one 128-byte line per bin each) | [bins + 1] offsets |
+// [bins + 1] first segment index (the [bins x 32] blocks start on 128-byte lines: vector loads / stores of a bin's windows)
+struct MsmZeroLayout {
+    size_t hist, cursor, big_count, len_hist, len_cursor, two_level_bad, bin_cursor;
+    size_t flat_cnt, flat_win_off, flat_cur, flat_off, flat_seg_off;
+    size_t words;  // whole 256-byte lines: the runtime then clears them with one kernel, not two
+};
+static MsmZeroLayout msm_zero_layout(const MsmShape& s) {
+    MsmZeroLayout z = MsmZeroLayout();
+    const size_t lens = (size_t)(SEG_MAX + 1) * LEN_STRIDE, bins = (size_t)FLAT_CUR_STRIDE * FLAT_MAX_BINS;
+    z.hist = 0;
+    z.cursor = z.hist + s.pl.NB + 1;
+    z.big_count = z.cursor + s.pl.NB + 1;
+    z.len_hist = z.big_count + 4;
+    z.len_cursor = z.len_hist + lens;
+    z.two_level_bad = z.len_cursor + lens;
+    z.bin_cursor = z.two_level_bad + MAX_WIN;
+    size_t end = z.bin_cursor + (size_t)s.pl.nwin * (s.two_level ? PART_MAX_BINS : 0);
+    if (s.flat) {
+        z.flat_cnt = (end + 31) & ~(size_t)31;
+        z.flat_win_off = z.flat_cnt + bins;
+        z.flat_cur = z.flat_win_off + bins;
+        z.flat_off = z.flat_cur + bins;
+        z.flat_seg_off = z.flat_off + FLAT_MAX_BINS + 2;
+        end = z.flat_seg_off + FLAT_MAX_BINS + 2;
+    }
+    z.words = (end + 63) & ~(size_t)63;
+    return z;
+}
+// The named device buffers of a job.  What the deferred bucket stage of a job still reads (the zeroed block with the status words,
+// bucket / segment offsets, big-bucket list, partial sums, the low-LDS stage's sums) is kept per result SLOT ("msmS<slot>.<name>",
+// `kind`: its entry in ctx->msm_slot_bytes); the rest is per lane ("msm<lane>.<name>", lane 9 for lane < 0: stream-ordered reuse).
+enum MsmBuf { BUF_HIST, BUF_SEGS, BUF_BUCKET_OFF, BUF_SEG_OFF, BUF_DIGITS, BUF_SORTED, BUF_SCAN_TOT, BUF_BIG_LIST, BUF_POINTS, BUF_PAIRS, BUF_ACC };
+static const struct {
+    const char* name;
+    int kind;  // -1: per lane
+} msm_bufs[] = {{"hist", 0},    {"segs", -1},     {"bucket_off", 1}, {"seg_off", 2}, {"digits", -1}, {"sorted", -1},
+                {"scan_tot", -1}, {"big_list", 3}, {"points", 4},     {"pairs", -1},  {"acc", 5}};
+static int msm_buffer(swm_ctx* ctx, MsmBuf id, int slot, int lane, size_t bytes, void** out) {
+    const int kind = msm_bufs[id].kind;
+    char nm[32];
+    snprintf(nm, sizeof(nm), kind >= 0 ? "msmS%d.%s" : "msm%d.%s", kind >= 0 ? slot : (lane < 0 ? 9 : lane), msm_bufs[id].name);
+    // Per-slot buffers are sized by the LARGEST request any slot has seen, not by the job at hand (r05): the eight result slots
+    // rotate through the jobs of successive proofs (15 jobs per Merkle-circuit proof: a slot meets a different commitment every
+    // proof), and a slot that had only held 131 072-point jobs grew — all streams synchronised, hipFree, hipMalloc: 2.4 ms with
+    // the GPU idle — when a 786 432-point job reached it, somewhere in each of the first dozen proofs of a key.
+    if (kind >= 0) bytes = ctx->msm_slot_bytes[kind] = std::max(ctx->msm_slot_bytes[kind], bytes);
+    return scratch(ctx, nm, bytes, out);
+}
+struct MsmBuffers {
+    uint32_t *hist, *cursor, *big_count, *len_hist, *len_cursor, *two_level_bad, *bin_cursor;  // the zeroed block (MsmZeroLayout)
+    uint32_t *flat_cnt, *flat_win_off, *flat_cur, *flat_off, *flat_seg_off;
+    uint32_t *seg_start, *seg_len, *order, *bucket_off, *seg_off, *digits, *sorted, *tot_cnt, *tot_seg, *big_list;
+    uint2* pairs;
+    G1XYZZ *partial, *acc;  // partial[nseg_max] (then room for wpart_n points); the low-LDS bucket stage's sums, one point per lane
+};
+// follow: the segment descriptors are the twin pair's own ("msmT.segs"), not the lane's
+static int msm_buffers(swm_ctx* ctx, const MsmShape& s, const MsmZeroLayout& z, int slot, bool follow, MsmBuffers* out) {
+    MsmBuffers& b = *out = MsmBuffers();
+    SWM_TRY(msm_buffer(ctx, BUF_HIST, slot, s.lane, z.words * 4, (void**)&b.hist));
+    b.cursor = b.hist + z.cursor;
+    b.big_count = b.hist + z.big_count;
+    b.len_hist = b.hist + z.len_hist;
+    b.len_cursor = b.hist + z.len_cursor;
+    b.two_level_bad = b.hist + z.two_level_bad;
+    b.bin_cursor = b.hist + z.bin_cursor;
+    b.flat_cnt = b.hist + z.flat_cnt;
+    b.flat_win_off = b.hist + z.flat_win_off;
+    b.flat_cur = b.hist + z.flat_cur;
+    b.flat_off = b.hist + z.flat_off;
+    b.flat_seg_off = b.hist + z.flat_seg_off;
+    if (s.two_level || s.flat) SWM_TRY(msm_buffer(ctx, BUF_PAIRS, slot, s.lane, s.total * sizeof(uint2), (void**)&b.pairs));
+    if (follow) SWM_TRY(scratch(ctx, "msmT.segs", s.nseg_max * 12, (void**)&b.seg_start));
+    else SWM_TRY(msm_buffer(ctx, BUF_SEGS, slot, s.lane, s.nseg_max * 12, (void**)&b.seg_start));
+    b.seg_len = b.seg_start + s.nseg_max;
+    b.order = b.seg_len + s.nseg_max;
+    SWM_TRY(msm_buffer(ctx, BUF_BUCKET_OFF, slot, s.lane, (s.pl.NB + 1) * 4ull, (void**)&b.bucket_off));
+    SWM_TRY(msm_buffer(ctx, BUF_SEG_OFF, slot, s.lane, (s.pl.NB + 1) * 4ull, (void**)&b.seg_off));
+    SWM_TRY(msm_buffer(ctx, BUF_DIGITS, slot, s.lane, s.total * 4, (void**)&b.digits));
+    SWM_TRY(msm_buffer(ctx, BUF_SORTED, slot, s.lane, s.total * 4, (void**)&b.sorted));
+    SWM_TRY(msm_buffer(ctx, BUF_SCAN_TOT, slot, s.lane, (size_t)(s.scan_tiles + 1) * 8, (void**)&b.tot_cnt));
+    b.tot_seg = b.tot_cnt + s.scan_tiles + 1;
+    SWM_TRY(msm_buffer(ctx, BUF_BIG_LIST, slot, s.lane, (size_t)s.pl.NB * 4, (void**)&b.big_list));
+    SWM_TRY(msm_buffer(ctx, BUF_POINTS, slot, s.lane, (s.nseg_max + s.wpart_n) * sizeof(G1XYZZ), (void**)&b.partial));
+    if (s.low) SWM_TRY(msm_buffer(ctx, BUF_ACC, slot, s.lane, (size_t)s.rl.nwin * s.max_blocks * 256 * sizeof(G1XYZZ), (void**)&b.acc));
+    return SWM_OK;
+}
+
+// ---- twin roles (msm.h).  *lead: this job writes the sorted array of twin.tab2 beside its own.  Returns the lead whose sort this
+// job takes over, or null.  Any mismatch of the shapes leaves both on the ordinary schedule.  SWM_MSM_TWIN=0: never.
+static MsmJob* msm_twin_match(const MsmJob* job, const MsmShape& s, const MsmSortGeom& geom, const void* d_scalars, size_t n, int mont,
+                              const MsmInfMask& inf, const MsmTable& tab, const MsmTwin& twin, bool* lead) {
+    static const bool twin_on = env_switch("SWM_MSM_TWIN", 1, 0, 1) != 0;
+    // (from 2^15 points: below, a proof is a chain of launches and the follower's wait for the lead's sort costs more than its own
+    // sort beside it — 2^14 constraints 3.88 -> 4.0 ms, 2^16 6.58 -> 6.49 ms, r06)
+    static constexpr size_t twin_min = 32768;
+    const bool twin_shape = twin_on && n >= twin_min && s.lane >= 0 && s.flat && s.te && tab.contiguous() && tab.scalar_stride == 1 &&
+                            tab.shard_world <= 1 && !inf.mask;
+    *lead = twin_shape && twin.role == MsmTwin::LEAD && twin.tab2.te && twin.tab2.c == tab.c && twin.tab2.contiguous() &&
+             twin.tab2.scalar_stride == 1 && twin.tab2.shard_world <= 1 && msm_flat_applies(twin.tab2, n) &&
+             twin.tab2.offset + n <= twin.tab2.stride && tab.offset + n <= tab.stride;
+    MsmJob* const l = twin_shape && twin.role == MsmTwin::FOLLOW ? twin.lead : nullptr;
+    // the lead's job, scalars and table rows are this one's, and so is the geometry of its arrays
+    const bool same = l && l != job && l->active && l->twin.ready && l->twin.scalars == d_scalars && l->n == n && l->twin.mont == mont &&
+                      l->twin.tab2.c == tab.c && l->twin.tab2.te == tab.te && l->twin.tab2.stride == tab.stride &&
+                      l->twin.tab2.offset == tab.offset && l->twin.geom == geom;
+    return same ? l : nullptr;
+}
+
+// ---- streams.  Hardware-queue placement, once per context.  ROCm 7 hands its hardware queues (four by default) to streams in creation order,
+// bouncing: 1, 2, 3, 4, 4, 3, 2, 1, ... (rocprofv3 Queue_Id, r02).  With the context's stream and the null stream
+// first, four auxiliary streams created in a row put the sort and the tail stream on ONE queue: tail(k) and
+// sort(k+1) — the two phases that run between consecutive accumulations — executed one after the other
+// (2^20 proofs: 73.0 instead of 70.1 ms).  Wanted: the context's stream, the sort stream, the first accumulation
+// stream and the tail stream on four different queues (the second accumulation stream may share: accumulations
+// cannot overlap, each fills the register files).  A placeholder stream before the tail stream gives that in the
+// usual creation history; the result is PROBED (streams_concurrent) and a stream that shares a queue with an
+// earlier role is replaced by a fresh one, a few times at most — whatever streams the host application created
+// before.
+static int msm_setup_streams(swm_ctx* ctx) {
+    if (ctx->aux_stream[0]) return SWM_OK;
+    const hipStream_t main_stream = ctx->stream;
+    // The four streams are created and probed into locals and published to the context only when all of it
+    // succeeded: a failure half way must not leave aux_stream[0] set with the later entries null (every later MSM
+    // would skip this set-up and silently run its tail on the legacy default stream).
+    hipStream_t aux[swm_ctx::MSM_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    auto setup = [&]() -> int {
+        for (int i = 0; i < 3; i++) SWM_HIP(ctx, msm_create_stream(&aux[i]));
+        hipStream_t ph = nullptr;
+        SWM_HIP(ctx, hipStreamCreateWithFlags(&ph, hipStreamNonBlocking));
+        ctx->spare_streams.push_back(ph);
+        SWM_HIP(ctx, msm_create_stream(&aux[3]));
+        SWM_HIP(ctx, hipStreamSynchronize(main_stream));
+        const int roles[3] = {0, 1, 3};  // sort, accumulation 0, tail
+        std::vector<hipStream_t> fixed = {main_stream};
+        int budget = 8;  // replacement streams at most
+        for (int r : roles) {
+            for (;;) {
+                bool conc = true;  // with every earlier role
+                for (size_t f = 0; f < fixed.size() && conc; f++) SWM_TRY(streams_concurrent(ctx, fixed[f], aux[r], &conc));
+                if (conc || budget-- <= 0) break;
+                ctx->spare_streams.push_back(aux[r]);  // kept alive: destroying it would free its slot
+                aux[r] = nullptr;
+                SWM_HIP(ctx, msm_create_stream(&aux[r]));
+            }
+            fixed.push_back(aux[r]);
+        }
+        if (!ctx->fork_event) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->fork_event, hipEventDisableTiming));
+        return SWM_OK;
+    };
+    const int rc = setup();
+    if (rc != SWM_OK) {
+        for (hipStream_t a : aux)
+            if (a) ctx->spare_streams.push_back(a);  // destroyed with the context
+        return rc;
+    }
+    for (int i = 0; i < swm_ctx::MSM_LANES; i++) ctx->aux_stream[i] = aux[i];
+    return SWM_OK;
+}
+// The next pinned result slot for `job`, with its events.
+static int msm_take_slot(swm_ctx* ctx, MsmJob* job) {
+    if (!ctx->pinned) {  // coherent + mapped: the bucket stage writes its results straight into the slots
+        SWM_HIP(ctx, hipHostMalloc(&ctx->pinned, SLOT_BYTES * swm_ctx::MSM_SLOTS, hipHostMallocCoherent | hipHostMallocMapped));
+        SWM_HIP(ctx, hipHostGetDevicePointer(&ctx->pinned_dev, ctx->pinned, 0));
+    }
+    const int slot = ctx->next_slot;
+    if (ctx->slot_busy[slot])  // its previous job has not been collected: the download would overwrite live results
+        return set_err(ctx, SWM_ERR_INTERNAL, "msm: more than %d jobs in flight", swm_ctx::MSM_SLOTS);
+    ctx->next_slot = (ctx->next_slot + 1) % swm_ctx::MSM_SLOTS;
+    if (!ctx->slot_event[slot]) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->slot_event[slot], hipEventDisableTiming));
+    job->slot = slot;
+    job->host = reinterpret_cast<G1XYZZ*>((char*)ctx->pinned + SLOT_BYTES * slot);
+    job->host_flags = reinterpret_cast<const uint32_t*>((char*)job->host + SLOT_FLAGS_OFF);
+    job->host_dev = reinterpret_cast<G1XYZZ*>((char*)ctx->pinned_dev + SLOT_BYTES * slot);
+    job->host_flags_dev = reinterpret_cast<uint32_t*>((char*)job->host_dev + SLOT_FLAGS_OFF);
+    // the bucket stage writes its results straight into the pinned slot (see msm_bucket_reduce; against stream-ordered copies,
+    // r02 on one box: 2^16 proofs 11.4 vs 11.8 ms, 2^20 75.1 vs 75.7 ms)
+    job->done = ctx->slot_event[slot];
+    if (!ctx->acc_event[slot]) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->acc_event[slot], hipEventDisableTiming));
+    job->acc_done = ctx->acc_event[slot];
+    if (!ctx->sort_event[slot]) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->sort_event[slot], hipEventDisableTiming));
+    return SWM_OK;
+}
+
+// ---- stages (each enqueues on the context's stream)
+// FOLLOW: the second sorted array the lead's bin sort wrote; the descriptors: counts, first segments, the list of oversized buckets,
+// status words, length histogram, the bins' entry and segment totals, the segments.  Not the cursors and the count of live
+// segments, which the lead's msm_seg_order may be advancing at this moment: this job's own stay zero for its own.  The lead's
+// zeroed block has this job's layout (msm_twin_match: same geometry).
+static int msm_twin_copy_stage(swm_ctx* ctx, const MsmShape& s, const MsmZeroLayout& z, MsmBuffers* b, MsmJob* lead, int slot) {
+    const MsmTwinSrc& t = lead->twin;
+    SWM_TRY(scratch(ctx, "msmT.sorted", s.total * 4, (void**)&b->sorted));
+    SWM_HIP(ctx, hipStreamWaitEvent(ctx->stream, t.sorted, 0));
+    TwinCopy tc = TwinCopy();
+    auto range = [&](const uint32_t* from, uint32_t* to, size_t words) {
+        tc.src[tc.k] = from, tc.dst[tc.k] = to, tc.words[tc.k++] = (uint32_t)words;
+    };
+    range(t.block + z.hist, b->hist, s.pl.NB + 1);
+    range(t.block + z.big_count, b->big_count, 3);
+    range(t.block + z.len_hist, b->len_hist, (size_t)(SEG_MAX + 1) * LEN_STRIDE);
+    range(t.block + z.flat_off, b->flat_off, 2 * (size_t)FLAT_MAX_BINS + 4);  // flat_off | flat_seg_off
+    range(t.seg_off, b->seg_off, s.pl.NB + 1);
+    range(t.big_list, b->big_list, s.pl.NB);
+    range(t.seg_start, b->seg_start, 2 * s.nseg_max);  // seg_start | seg_len
+    SWM_LAUNCH(ctx, "msm_twin_copy", msm_twin_copy, dim3(1024), dim3(256), 0, tc);
+    if (!ctx->twin_copy_event[slot]) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->twin_copy_event[slot], hipEventDisableTiming));
+    SWM_HIP(ctx, hipEventRecord(ctx->twin_copy_event[slot], ctx->stream));
+    lead->twin_copied = ctx->twin_copy_event[slot];
+    if (t.lane >= 0) ctx->lane_copy_event[t.lane] = ctx->twin_copy_event[slot];
+    ctx->stat_msm_twins++;
+    return SWM_OK;
+}
+// Flat schedule: two-level counting sort over the shared bucket set; the fine counts written by msm_flat_bin_sort are the
+// histogram the scans consume, and the bins are contiguous bucket ranges, so `sorted` is in bucket order.
+// lead (a twin pair's LEAD, filled in but for `ready`): the bin sort also writes the sorted array of lead->tab2, and lead->sorted
+// is recorded after it.
+static int msm_sort_flat(swm_ctx* ctx, const MsmShape& s, const MsmBuffers& b, const MsmTable& tab, size_t n, MsmTwinSrc* lead) {
+    const WinLayout& pl = s.pl;
+    uint32_t ctile = 65536;  // digits per workgroup of the coarse histogram: at least ~256 workgroups
+    while (ctile > 4096 && (size_t)ctile * 256 > s.total) ctile >>= 1;
+    // digits per workgroup of the partition: 16 K (r04: half the (tile, bin) runs and reserving atomics of 8 K tiles, one
+    // workgroup per CU instead of two — prove 2^20 51.6 -> 51.0 ms, and the transforms beside it run a quarter faster) as long
+    // as the pairs and the three per-bin arrays fit the 160 KB of LDS (up to 2 048 bins); 8 K above
+    const size_t lds_bins = (3 * (size_t)((s.flat_bins + 3) & ~3u) + 1024) * 4;
+    const bool tile16 = 16384 * sizeof(uint2) + lds_bins <= 160 * 1024;
+    const uint32_t part_tile = tile16 ? 16384u : 8192u;
+    const size_t lds_part = (size_t)part_tile * sizeof(uint2) + lds_bins;
+    SWM_TRY(allow_big_lds(ctx, tile16 ? 10 : 5, tile16 ? (const void*)msm_flat_partition<16> : (const void*)msm_flat_partition<8>, lds_part));
+    const size_t lds_bin = ((size_t)FLAT_BIN_CAP + 2 * ((size_t)1 << s.flat_fb)) * 4;
+    SWM_TRY(allow_big_lds(ctx, 6, (const void*)msm_flat_bin_sort<BIN_THREADS>, lds_bin));
+    // (256-lane forms of the partition and the bin sort for sorts that run beside an accumulation: built and measured in r05 —
+    // 51.15 vs 50.8 ms at 2^20 with the issue priorities in place — and removed in r06)
+    SWM_LAUNCH(ctx, "msm_flat_hist", msm_flat_coarse_hist, dim3((unsigned)((n + ctile - 1) / ctile), pl.nwin), dim3(SORT_THREADS), 0,
+               b.digits, n, s.flat_fb, s.flat_bins, ctile, b.flat_cnt);
+    unsigned scan_threads = 64;
+    const bool one_bin_per_lane = s.flat_bins <= 1024;
+    while (scan_threads * (one_bin_per_lane ? 1 : 4) < s.flat_bins) scan_threads <<= 1;
+    SWM_LAUNCH(ctx, "msm_flat_hist", one_bin_per_lane ? msm_flat_scan_bins<1> : msm_flat_scan_bins<4>, dim3(1), dim3(scan_threads), 0,
+               b.flat_cnt, s.flat_bins, pl.nwin, b.flat_off, b.flat_win_off, s.flat_fb, s.SEG, b.flat_seg_off);
+    SWM_LAUNCH(ctx, "msm_flat_partition", tile16 ? msm_flat_partition<16> : msm_flat_partition<8>,
+               dim3((unsigned)((n + part_tile - 1) / part_tile), pl.nwin), dim3(1024), lds_part, b.digits, n, (uint32_t)tab.stride,
+               (uint32_t)tab.offset, tab.blk_log, (uint32_t)tab.bstride, s.flat_fb, s.flat_bins, b.flat_win_off, pl.nwin, b.flat_cur, b.pairs);
+    // (bucket / segment offsets, segment descriptors, the length histogram and the list of oversized buckets come out of
+    // the bin sort: no scans over the bucket histogram, no msm_seg_desc)
+    const FlatSegOut fso{b.hist,    b.bucket_off, b.seg_off, b.seg_start, b.seg_len, b.len_hist,
+                         b.big_count, b.big_list, s.SEG,     s.big_nseg,  s.te ? 1u : 0u};
+    TwinOut two{nullptr, 1u, 0u, 0u};
+    if (lead) {
+        // (the array is read by the accumulation of the previous pair's follower)
+        SWM_TRY(scratch(ctx, "msmT.sorted", s.total * 4, (void**)&two.sorted2));
+        if (ctx->twin_sorted_event) SWM_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->twin_sorted_event, 0));
+        two.tstride = (uint32_t)tab.stride;
+        two.dstride = (uint32_t)lead->tab2.stride - (uint32_t)tab.stride;
+        two.doff = (uint32_t)lead->tab2.offset - (uint32_t)tab.offset;
+    }
+    SWM_LAUNCH(ctx, "msm_flat_bin_sort", msm_flat_bin_sort<BIN_THREADS>, dim3(s.flat_bins), dim3(BIN_THREADS), lds_bin,
+               (const uint2*)b.pairs, s.flat_fb, pl.NB, b.flat_off, b.flat_seg_off, fso, b.sorted, two);
+    if (lead) {
+        SWM_HIP(ctx, hipEventRecord(lead->sorted, ctx->stream));
+        lead->ready = true;
+    }
+    return SWM_OK;
+}
+// Per-window schedule: counting sort by (window, bucket), with the two-level scatter for large MSMs.
+static int msm_sort_windows(swm_ctx* ctx, const MsmShape& s, const MsmBuffers& b, size_t n) {
+    const WinLayout& pl = s.pl;
+    // tile size: flat between 2^15 and 2^18 on MI355X (the scatter is bound by its 4-byte scattered writes: 73 G digits/s)
+    const uint32_t SORT_TILE = SORT_TILE_MIN;
+    unsigned tiles = (unsigned)((n + SORT_TILE - 1) / SORT_TILE);
+    size_t lds_sort = (size_t)pl.maxB * 4;
+    SWM_TRY(allow_big_lds(ctx, 0, (const void*)msm_hist, lds_sort));
+    SWM_TRY(allow_big_lds(ctx, 1, (const void*)msm_scatter, lds_sort));
+    SWM_LAUNCH(ctx, "msm_hist", msm_hist, dim3(tiles, pl.nwin), dim3(SORT_THREADS), lds_sort, b.digits, n, pl, SORT_TILE, b.hist);
+    SWM_LAUNCH(ctx, "msm_scan", msm_scan_totals, dim3(s.scan_tiles), dim3(SCAN_BLOCK), 0, b.hist, pl.NB, s.SEG, b.tot_cnt, b.tot_seg);
+    SWM_LAUNCH(ctx, "msm_scan", msm_scan_mid, dim3(1), dim3(SCAN_BLOCK), 0, b.tot_cnt, b.tot_seg, s.scan_tiles);
+    SWM_LAUNCH(ctx, "msm_scan", msm_scan_final, dim3(s.scan_tiles), dim3(SCAN_BLOCK), 0, b.hist, pl.NB, s.SEG, b.tot_cnt, b.tot_seg,
+               s.scan_tiles, b.bucket_off, b.seg_off, b.big_count, b.big_list, s.big_nseg);
+    if (s.two_level) {
+        SWM_TRY(allow_big_lds(ctx, 3, (const void*)msm_partition, (size_t)PART_TILE * sizeof(uint2)));
+        SWM_TRY(allow_big_lds(ctx, 4, (const void*)msm_bin_sort, (size_t)BIN_CAP * 4));
+        SWM_LAUNCH(ctx, "msm_bin_check", msm_bin_check, dim3((s.bp.max_nbins + 255) / 256, pl.nwin), dim3(256), 0, b.bucket_off, pl,
+                   s.bp, b.two_level_bad);
+        SWM_LAUNCH(ctx, "msm_partition", msm_partition, dim3((unsigned)((n + PART_TILE - 1) / PART_TILE), pl.nwin), dim3(1024),
+                   (size_t)PART_TILE * sizeof(uint2), b.digits, n, pl, s.bp, b.bucket_off, b.bin_cursor, b.two_level_bad, b.pairs);
+        SWM_LAUNCH(ctx, "msm_bin_sort", msm_bin_sort, dim3(s.bp.max_nbins, pl.nwin), dim3(BIN_THREADS), (size_t)BIN_CAP * 4,
+                   (const uint2*)b.pairs, pl, s.bp, b.bucket_off, b.two_level_bad, b.sorted);
+    }
+    SWM_LAUNCH(ctx, "msm_scatter", msm_scatter, dim3(tiles, pl.nwin), dim3(SORT_THREADS), lds_sort, b.digits, n, pl, SORT_TILE,
+               b.bucket_off, b.cursor, b.sorted, s.two_level ? (const uint32_t*)b.two_level_bad : (const uint32_t*)nullptr);
+    return SWM_OK;
+}
+// Stage A: segments ordered by length, one partial sum per segment (msm_accumulate*), oversized buckets folded ahead of the
+// bucket stage (msm_big_bucket_sum).
+static int msm_accumulate_stage(swm_ctx* ctx, const MsmShape& s, const MsmBuffers& b, const MsmTable& tab, const G1Affine* d_bases,
+                                const G1Affine* d_bases28) {
+    unsigned grid_s = (unsigned)((s.nseg_max + ORD_THREADS - 1) / ORD_THREADS);
+    // segment indices in use (a device word): the flat schedule's bins hand them out by capacity, the per-window schedule densely
+    const uint32_t* seg_space = s.flat ? b.flat_seg_off + s.flat_bins : b.seg_off + s.pl.NB;
+    uint32_t* nseg_live = b.big_count + 3;  // segments that hold entries = lanes of work for the accumulation
+    if (!s.flat)
+        SWM_LAUNCH(ctx, "msm_seg_order", msm_seg_desc, dim3(grid_s), dim3(ORD_THREADS), 0, b.bucket_off, b.seg_off, s.pl.NB, s.SEG,
+                   b.seg_start, b.seg_len, b.len_hist);
+    SWM_LAUNCH(ctx, "msm_seg_order", msm_seg_order, dim3((unsigned)((s.nseg_max + ORD2_THREADS * ORD2_U - 1) / (ORD2_THREADS * ORD2_U))),
+               dim3(ORD2_THREADS), 0, b.seg_len, seg_space, s.SEG, (const uint32_t*)b.len_hist, b.len_cursor, nseg_live, b.order);
+    unsigned acc_grid = (unsigned)((s.nseg_max + 255) / 256);
+    const dim3 big_grid(std::min<unsigned>((s.pl.NB + (RED_BLOCK >> s.log_g) - 1) / (RED_BLOCK >> s.log_g), s.lat ? 2048 : 512));
+    if (s.te) {
+        if (s.quad_acc)
+            SWM_LAUNCH(ctx, "msm_accumulate", msm_accumulate_te_quad, dim3((unsigned)((s.nseg_max + 63) / 64)), dim3(256), 0, tab.te,
+                       b.sorted, b.seg_start, b.seg_len, b.order, nseg_live, b.partial);
+        else
+            SWM_LAUNCH(ctx, "msm_accumulate", msm_accumulate_te, dim3(acc_grid), dim3(256), 0, tab.te, b.sorted, b.seg_start, b.seg_len,
+                       b.order, nseg_live, b.partial);
+    } else {
+        SWM_LAUNCH(ctx, "msm_accumulate", msm_accumulate, dim3(acc_grid), dim3(256), 0,
+                   s.flat ? (const G1Affine*)nullptr : d_bases, s.flat ? tab.t28 : d_bases28, b.sorted, b.seg_start, b.seg_len, b.order,
+                   nseg_live, b.partial);
+    }
+    SWM_LAUNCH(ctx, "msm_big_bucket_sum", s.te ? msm_big_bucket_sum<FormTE> : msm_big_bucket_sum<FormXYZZ>, big_grid, dim3(RED_BLOCK),
+               RED_BLOCK * sizeof(G1XYZZ), b.partial, b.seg_off, b.hist, s.SEG, b.big_count, b.big_list, s.log_g);
+    return SWM_OK;
+}
+int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine* d_bases28, const void* d_scalars, size_t n,
+                int mont, MsmJob* job, MsmInfMask inf, bool defer_tail, MsmTable tab, MsmTwin twin) {
+    job->active = false;
+    job->tail_pending = false;
+    job->n = n;
+    job->twin = MsmTwinSrc();
+    job->twin_copied = nullptr;
+    job->twin_kept_lane = false;
+    if (n == 0) return SWM_OK;
+    if (n >= (1ull << 31)) return set_err(ctx, SWM_ERR_INVALID_ARG, "msm: n must be < 2^31");
+    ctx->stat_msm_calls++;
+    ctx->stat_msm_points += n;
+    ctx->log_call('m', n);
+    struct SinceWait {  // (counted when this call returns: the choices below see the jobs BEFORE this one)
+        swm_ctx* c;
+        ~SinceWait() { c->msm_since_wait++; }
+    } since_wait{ctx};
+    // the job before this one waited to learn whether anything follows it: something does, so its bucket stage takes the
+    // thin shape that runs BESIDE this job's sort and accumulation (msm_tail_shape)
+    SWM_TRY(msm_launch_lazy_tail(ctx, false));
+    MsmShape s;
+    SWM_TRY(msm_shape(ctx, n, tab, lane, defer_tail, &s));
+    ctx->stat_msm_digits += s.total;
+    const MsmZeroLayout z = msm_zero_layout(s);
+    const MsmSortGeom geom{z.words, s.nseg_max, s.SEG, s.big_nseg, s.flat_bins};
+    bool lead = false;
+    MsmJob* const follow = msm_twin_match(job, s, geom, d_scalars, n, mont, inf, tab, twin, &lead);
+    // An asynchronous MSM (lane >= 0) is a three-stage pipeline over three auxiliary streams:
+    //   S  digits + counting sort          (HBM / LDS-atomic bound)
+    //   A  segment planning + accumulation (saturates the integer pipes)      waits for the job's sort
+    //   T  bucket stage + download         (a latency-bound chain at one wave per SIMD)   waits for the job's accumulation
+    // so that consecutive jobs keep stage A busy back to back while the tail of the previous job and the sort of the
+    // next one run beside it.  (r02 timeline: with two lanes that each ran sort -> accumulate -> tail in order, both
+    // lanes reached their tails together and ~10 ms of bucket stage per 2^20 proof ran with nothing beside it.)
+    // `lane` only selects the scratch set of the per-lane buffers (two sets: a job's sort may overwrite a set once
+    // the accumulation that last read it has finished).  lane < 0: everything on the context's stream (K1 ABI).
+    // S | A0, A1 by lane | T (two accumulations may overlap: one alone leaves bubbles at the end of its length-sorted grid).
+    // Single-stream lanes 0, 1, 2 sit on three different hardware queues (accumulation 0, tail, sort); lane 3 shares the
+    // second accumulation stream's queue.
+    hipStream_t st_sort = ctx->stream, st_acc = ctx->stream, st_tail = ctx->stream;
+    if (s.lane >= 0) {
+        SWM_TRY(msm_setup_streams(ctx));
+        static const int lane_stream[4] = {1, 3, 0, 2};
+        st_sort = ctx->aux_stream[s.one_stream ? lane_stream[s.lane] : 0];
+        st_acc = s.one_stream ? st_sort : ctx->aux_stream[1 + (s.lane & 1)];
+        st_tail = s.one_stream ? st_sort : ctx->aux_stream[3];  // (a second bucket-stage stream: 51.4 -> 57.4 ms at 2^20, r05)
+        SWM_HIP(ctx, hipEventRecord(ctx->fork_event, ctx->stream));
+        SWM_HIP(ctx, hipStreamWaitEvent(st_sort, ctx->fork_event, 0));  // the scalars are ready
+    }
+    SWM_TRY(msm_take_slot(ctx, job));
+    const int slot = job->slot;
+    job->te = s.te;
+    job->quad = s.quad;
+    job->low = s.low;
+    job->max_blocks = s.max_blocks;
+    job->stream = st_tail;
+    job->pl = s.rl;
+    job->red_blocks = s.red_blocks;
+    job->blk_lo = s.blk_lo;
+    job->blk_hi = s.blk_hi;
+    job->blk_low = s.blk_low;
+    job->log_m = s.log_m;
+    job->rb = s.rb;
+    job->big_nseg = s.big_nseg;
+
+    StreamSwap swap(ctx, st_sort);
     if (follow) {
         // A follower touches nothing of its lane's scratch set — its sorted array and its segment descriptors live in the pair's own
         // buffers, free once the previous pair's follower has accumulated (the lead waited for that before its bin sort) — so the
         // NEXT job may take this lane's set: the caller gets the lane back (pipelined form: job->twin_kept_lane), and that job's sort
         // runs beside the lead's accumulation instead of waiting for it (two sets: the sort of job k + 2 waits for accumulation k).
-        snprintf(nm[1], sizeof(nm[1]), "msmT.segs");
-        job->twin_kept_lane = !one_stream;
-    } else if (lane >= 0) {
+        job->twin_kept_lane = !s.one_stream;
+    } else if (s.lane >= 0) {
         // the scratch set of this lane was last read by the accumulation of the job two back
         // (single-stream jobs too: their stream is not necessarily the one the set's previous reader ran on)
-        if (ctx->set_acc_event[lane]) SWM_HIP(ctx, hipStreamWaitEvent(st_sort, ctx->set_acc_event[lane], 0));
+        if (ctx->set_acc_event[s.lane]) SWM_HIP(ctx, hipStreamWaitEvent(st_sort, ctx->set_acc_event[s.lane], 0));
         // ... and, when that job led a twin pair, copied by its follower
-        if (ctx->lane_copy_event[lane]) SWM_HIP(ctx, hipStreamWaitEvent(st_sort, ctx->lane_copy_event[lane], 0));
+        if (ctx->lane_copy_event[s.lane]) SWM_HIP(ctx, hipStreamWaitEvent(st_sort, ctx->lane_copy_event[s.lane], 0));
     }
-    SWM_TRY(scratch(ctx, nm[0], slot_scratch(0, zero_words * 4), (void**)&hist));
-    cursor = hist + pl.NB + 1;
-    big_count = cursor + pl.NB + 1;
-    len_hist = big_count + 4;
-    uint32_t* len_cursor = len_hist + (SEG_MAX + 1) * LEN_STRIDE;       // the run cursors of msm_seg_order, one per length class
-    uint32_t* two_level_bad = len_cursor + (SEG_MAX + 1) * LEN_STRIDE;  // one flag per window, then the per-(window, bin) cursors
-    uint32_t* bin_cursor = two_level_bad + MAX_WIN;
-    // [windows x bins] counts (room for 32 windows) | [bins x 32] offsets | [bins x 32] cursors (one 128-byte line per bin each) |
-    // [bins + 1] offsets | [bins + 1] first segment index
-    // (the [bins x 32] blocks start on 128-byte lines: vector loads / stores of a bin's windows)
-    uint32_t* flat_cnt = hist + ((((size_t)(bin_cursor - hist) + (size_t)pl.nwin * maxbins) + 31) & ~(size_t)31);
-    uint32_t* flat_win_off = flat_cnt + (size_t)FLAT_CUR_STRIDE * FLAT_MAX_BINS;
-    uint32_t* flat_cur = flat_win_off + (size_t)FLAT_CUR_STRIDE * FLAT_MAX_BINS;
-    uint32_t* flat_off = flat_cur + (size_t)FLAT_CUR_STRIDE * FLAT_MAX_BINS;
-    uint32_t* flat_seg_off = flat_off + FLAT_MAX_BINS + 2;  // [bins + 1] first segment index of every bin
-    uint2* pairs = nullptr;
-    if (two_level || flat) SWM_TRY(scratch(ctx, nm[9], total * sizeof(uint2), (void**)&pairs));
-    SWM_TRY(scratch(ctx, nm[1], nseg_max * 12, (void**)&seg_start));
-    seg_len = seg_start + nseg_max;
-    order = seg_len + nseg_max;
-    SWM_TRY(scratch(ctx, nm[2], slot_scratch(1, (pl.NB + 1) * 4ull), (void**)&bucket_off));
-    SWM_TRY(scratch(ctx, nm[3], slot_scratch(2, (pl.NB + 1) * 4ull), (void**)&seg_off));
-    SWM_TRY(scratch(ctx, nm[4], total * 4, (void**)&digits));
-    SWM_TRY(scratch(ctx, nm[5], total * 4, (void**)&sorted));
-    const unsigned scan_tiles = (pl.NB + SCAN_TILE - 1) / SCAN_TILE;
-    SWM_TRY(scratch(ctx, nm[6], (size_t)(scan_tiles + 1) * 8, (void**)&tot_cnt));
-    tot_seg = tot_cnt + scan_tiles + 1;
-    SWM_TRY(scratch(ctx, nm[7], slot_scratch(3, (size_t)pl.NB * 4), (void**)&big_list));
-    // XYZZ scratch: partial[nseg_max] | wpart[nwin * red_blocks * 2]
-    G1XYZZ *partial, *wpart;
-    const size_t wpart_n = (size_t)rl.nwin * std::max(red_blocks, flat ? job->max_blocks : 0u) * 2;
-    SWM_TRY(scratch(ctx, nm[8], slot_scratch(4, (nseg_max + wpart_n) * sizeof(G1XYZZ)), (void**)&partial));
-    wpart = partial + nseg_max;
-    job->d_acc = nullptr;
-    if (low) {  // the lanes' weighted sums of the low-LDS bucket stage: one point per lane, per result slot like `partial`
-        char nma[32];
-        snprintf(nma, sizeof(nma), "msmS%d.acc", slot);
-        SWM_TRY(scratch(ctx, nma, slot_scratch(5, (size_t)rl.nwin * job->max_blocks * 256 * sizeof(G1XYZZ)), (void**)&job->d_acc));
-    }
-
-    SWM_HIP(ctx, zero_fill_async(hist, zero_words * 4, ctx->stream));  // (a kernel with issue priority, not the runtime's fill: fill.cuh)
-    const Fr* sc = reinterpret_cast<const Fr*>(d_scalars);
-    unsigned grid_n = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16);
+    MsmBuffers b;
+    SWM_TRY(msm_buffers(ctx, s, z, slot, follow != nullptr, &b));
+    job->d_acc = b.acc;
+    SWM_HIP(ctx, zero_fill_async(b.hist, z.words * 4, ctx->stream));  // (a kernel with issue priority, not the runtime's fill: fill.cuh)
     if (follow) {
-        // the second sorted array the lead's bin sort wrote; the descriptors: counts, first segments, the list of oversized buckets,
-        // status words, length histogram, the bins' entry and segment totals, the segments.  Not the cursors and the count of live
-        // segments, which the lead's msm_seg_order may be advancing at this moment: this job's own stay zero for its own.
-        SWM_TRY(scratch(ctx, "msmT.sorted", total * 4, (void**)&sorted));
-        SWM_HIP(ctx, hipStreamWaitEvent(ctx->stream, tsrc->twin.sorted, 0));
-        const uint32_t* a = tsrc->twin.block;
-        TwinCopy tc;
-        memset(&tc, 0, sizeof(tc));
-        auto range = [&](const uint32_t* from, uint32_t* to, size_t words) {
-            tc.src[tc.k] = from;
-            tc.dst[tc.k] = to;
-            tc.words[tc.k] = (uint32_t)words;
-            tc.k++;
-        };
-        range(a, hist, pl.NB + 1);
-        range(a + (big_count - hist), big_count, 3);
-        range(a + (len_hist - hist), len_hist, (size_t)(SEG_MAX + 1) * LEN_STRIDE);
-        range(a + (flat_off - hist), flat_off, 2 * (size_t)FLAT_MAX_BINS + 4);
-        range(tsrc->twin.seg_off, seg_off, pl.NB + 1);
-        range(tsrc->twin.big_list, big_list, pl.NB);
-        range(tsrc->twin.seg_start, seg_start, 2 * nseg_max);  // seg_start | seg_len
-        SWM_LAUNCH(ctx, "msm_twin_copy", msm_twin_copy, dim3(1024), dim3(256), 0, tc);
-        if (!ctx->twin_copy_event[slot]) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->twin_copy_event[slot], hipEventDisableTiming));
-        SWM_HIP(ctx, hipEventRecord(ctx->twin_copy_event[slot], ctx->stream));
-        tsrc->twin_copied = ctx->twin_copy_event[slot];
-        if (tsrc->twin.lane >= 0) ctx->lane_copy_event[tsrc->twin.lane] = ctx->twin_copy_event[slot];
-        ctx->stat_msm_twins++;
+        SWM_TRY(msm_twin_copy_stage(ctx, s, z, &b, follow, slot));
     } else {
-    SWM_LAUNCH(ctx, "msm_digits", msm_digits, dim3(grid_n), dim3(256), 0, sc, n, mont, pl, digits, inf.mask, inf.first,
-               big_count + 1 /* zeroed with the histogram */, dshard, tab.scalar_stride != 1 ? tab.blk_log : 31u,
-               tab.scalar_stride != 1 ? tab.bstride : (size_t)0);
-    if (flat) {
-        // two-level counting sort over the shared bucket set; the fine counts written by msm_flat_bin_sort are the
-        // histogram the scans consume, and the bins are contiguous bucket ranges, so `sorted` is in bucket order
-        uint32_t ctile = 65536;  // digits per workgroup of the coarse histogram: at least ~256 workgroups
-        while (ctile > 4096 && (size_t)ctile * 256 > total) ctile >>= 1;
-        if (pl.nwin > FLAT_CUR_STRIDE) return set_err(ctx, SWM_ERR_INTERNAL, "msm: too many windows for the flat sort");
-        // digits per workgroup of the partition: 16 K (r04: half the (tile, bin) runs and reserving atomics of 8 K tiles, one
-        // workgroup per CU instead of two — prove 2^20 51.6 -> 51.0 ms, and the transforms beside it run a quarter faster) as long
-        // as the pairs and the three per-bin arrays fit the 160 KB of LDS (up to 2 048 bins); 8 K above
-        const size_t lds_bins = (3 * (size_t)((flat_bins + 3) & ~3u) + 1024) * 4;
-        const bool tile16 = 16384 * sizeof(uint2) + lds_bins <= 160 * 1024;
-        const uint32_t part_tile = tile16 ? 16384u : 8192u;
-        const size_t lds_part = (size_t)part_tile * sizeof(uint2) + lds_bins;
-        SWM_TRY(allow_big_lds(ctx, tile16 ? 10 : 5, tile16 ? (const void*)msm_flat_partition<16> : (const void*)msm_flat_partition<8>, lds_part));
-        const size_t lds_bin = ((size_t)FLAT_BIN_CAP + 2 * ((size_t)1 << flat_fb)) * 4;
-        SWM_TRY(allow_big_lds(ctx, 6, (const void*)msm_flat_bin_sort<BIN_THREADS>, lds_bin));
-        // (256-lane forms of the partition and the bin sort for sorts that run beside an accumulation: built and measured in r05 —
-        // 51.15 vs 50.8 ms at 2^20 with the issue priorities in place — and removed in r06)
-        SWM_LAUNCH(ctx, "msm_flat_hist", msm_flat_coarse_hist, dim3((unsigned)((n + ctile - 1) / ctile), pl.nwin), dim3(SORT_THREADS), 0,
-                   digits, n, flat_fb, flat_bins, ctile, flat_cnt);
-        unsigned scan_threads = 64;
-        const bool one_bin_per_lane = flat_bins <= 1024;
-        while (scan_threads * (one_bin_per_lane ? 1 : 4) < flat_bins) scan_threads <<= 1;
-        if (one_bin_per_lane)
-            SWM_LAUNCH(ctx, "msm_flat_hist", msm_flat_scan_bins<1>, dim3(1), dim3(scan_threads), 0, flat_cnt, flat_bins, pl.nwin, flat_off, flat_win_off,
-                   flat_fb, SEG, flat_seg_off);
-        else
-            SWM_LAUNCH(ctx, "msm_flat_hist", msm_flat_scan_bins<4>, dim3(1), dim3(scan_threads), 0, flat_cnt, flat_bins, pl.nwin, flat_off, flat_win_off,
-                   flat_fb, SEG, flat_seg_off);
-        if (tile16)
-            SWM_LAUNCH(ctx, "msm_flat_partition", msm_flat_partition<16>, dim3((unsigned)((n + part_tile - 1) / part_tile), pl.nwin),
-                   dim3(1024), lds_part, digits, n, (uint32_t)tab.stride, (uint32_t)tab.offset, tab.blk_log, (uint32_t)tab.bstride, flat_fb,
-                   flat_bins, flat_win_off, pl.nwin, flat_cur, pairs);
-        else
-            SWM_LAUNCH(ctx, "msm_flat_partition", msm_flat_partition<8>, dim3((unsigned)((n + part_tile - 1) / part_tile), pl.nwin),
-                   dim3(1024), lds_part, digits, n, (uint32_t)tab.stride, (uint32_t)tab.offset, tab.blk_log, (uint32_t)tab.bstride, flat_fb,
-                   flat_bins, flat_win_off, pl.nwin, flat_cur, pairs);
-        // (bucket / segment offsets, segment descriptors, the length histogram and the list of oversized buckets come out of
-        // the bin sort: no scans over the bucket histogram, no msm_seg_desc)
-        const FlatSegOut fso{hist, bucket_off, seg_off, seg_start, seg_len, len_hist, big_count, big_list, SEG, big_nseg, te ? 1u : 0u};
-        TwinOut two{nullptr, 1u, 0u, 0u};
-        if (lead) {
-            // (the array is read by the accumulation of the previous pair's follower)
-            SWM_TRY(scratch(ctx, "msmT.sorted", total * 4, (void**)&two.sorted2));
-            if (ctx->twin_sorted_event) SWM_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->twin_sorted_event, 0));
-            two.tstride = (uint32_t)tab.stride;
-            two.dstride = (uint32_t)twin.tab2.stride - (uint32_t)tab.stride;
-            two.doff = (uint32_t)twin.tab2.offset - (uint32_t)tab.offset;
-        }
-        SWM_LAUNCH(ctx, "msm_flat_bin_sort", msm_flat_bin_sort<BIN_THREADS>, dim3(flat_bins), dim3(BIN_THREADS), lds_bin,
-                   (const uint2*)pairs, flat_fb, pl.NB, flat_off, flat_seg_off, fso, sorted, two);
-        if (lead) {
-            MsmTwinSrc& t = job->twin;
-            t.scalars = d_scalars;
-            t.mont = mont;
-            t.lane = lane;
-            t.c = tab.c;
-            t.te2 = twin.tab2.te;
-            t.stride2 = twin.tab2.stride;
-            t.offset2 = twin.tab2.offset;
-            t.block = hist;
-            t.seg_start = seg_start;
-            t.seg_off = seg_off;
-            t.big_list = big_list;
-            t.zero_words = zero_words;
-            t.nseg_max = nseg_max;
-            t.SEG = SEG;
-            t.big_nseg = big_nseg;
-            t.flat_bins = flat_bins;
-            t.sorted = ctx->sort_event[slot];
-            SWM_HIP(ctx, hipEventRecord(t.sorted, ctx->stream));
-            t.ready = true;
-        }
-    } else {
-        // tile size: flat between 2^15 and 2^18 on MI355X (the scatter is bound by its 4-byte scattered writes: 73 G digits/s)
-        const uint32_t SORT_TILE = SORT_TILE_MIN;
-        unsigned tiles = (unsigned)((n + SORT_TILE - 1) / SORT_TILE);
-        size_t lds_sort = (size_t)pl.maxB * 4;
-        SWM_TRY(allow_big_lds(ctx, 0, (const void*)msm_hist, lds_sort));
-        SWM_TRY(allow_big_lds(ctx, 1, (const void*)msm_scatter, lds_sort));
-        SWM_LAUNCH(ctx, "msm_hist", msm_hist, dim3(tiles, pl.nwin), dim3(SORT_THREADS), lds_sort, digits, n, pl, SORT_TILE, hist);
-        SWM_LAUNCH(ctx, "msm_scan", msm_scan_totals, dim3(scan_tiles), dim3(SCAN_BLOCK), 0, hist, pl.NB, SEG, tot_cnt, tot_seg);
-        SWM_LAUNCH(ctx, "msm_scan", msm_scan_mid, dim3(1), dim3(SCAN_BLOCK), 0, tot_cnt, tot_seg, scan_tiles);
-        SWM_LAUNCH(ctx, "msm_scan", msm_scan_final, dim3(scan_tiles), dim3(SCAN_BLOCK), 0, hist, pl.NB, SEG, tot_cnt, tot_seg,
-                   scan_tiles, bucket_off, seg_off, big_count, big_list, big_nseg);
-        if (two_level) {
-            SWM_TRY(allow_big_lds(ctx, 3, (const void*)msm_partition, (size_t)PART_TILE * sizeof(uint2)));
-            SWM_TRY(allow_big_lds(ctx, 4, (const void*)msm_bin_sort, (size_t)BIN_CAP * 4));
-            SWM_LAUNCH(ctx, "msm_bin_check", msm_bin_check, dim3((bp.max_nbins + 255) / 256, pl.nwin), dim3(256), 0, bucket_off, pl, bp,
-                       two_level_bad);
-            SWM_LAUNCH(ctx, "msm_partition", msm_partition, dim3((unsigned)((n + PART_TILE - 1) / PART_TILE), pl.nwin), dim3(1024),
-                       (size_t)PART_TILE * sizeof(uint2), digits, n, pl, bp, bucket_off, bin_cursor, two_level_bad, pairs);
-            SWM_LAUNCH(ctx, "msm_bin_sort", msm_bin_sort, dim3(bp.max_nbins, pl.nwin), dim3(BIN_THREADS), (size_t)BIN_CAP * 4,
-                       (const uint2*)pairs, pl, bp, bucket_off, two_level_bad, sorted);
-        }
-        SWM_LAUNCH(ctx, "msm_scatter", msm_scatter, dim3(tiles, pl.nwin), dim3(SORT_THREADS), lds_sort, digits, n, pl,
-                   SORT_TILE, bucket_off, cursor, sorted, two_level ? (const uint32_t*)two_level_bad : (const uint32_t*)nullptr);
+        const unsigned grid_n = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16);
+        SWM_LAUNCH(ctx, "msm_digits", msm_digits, dim3(grid_n), dim3(256), 0, reinterpret_cast<const Fr*>(d_scalars), n, mont, s.pl,
+                   b.digits, inf.mask, inf.first, b.big_count + 1 /* zeroed with the histogram */, s.dshard,
+                   tab.scalar_stride != 1 ? tab.blk_log : 31u, tab.scalar_stride != 1 ? tab.bstride : (size_t)0);
+        if (lead)  // what the follower takes: the arrays of this job's slot, ready once the bin sort has recorded `sorted`
+            job->twin = {false, d_scalars, mont, s.lane, twin.tab2, b.hist, b.seg_start, b.seg_off, b.big_list, geom, ctx->sort_event[slot]};
+        if (s.flat) SWM_TRY(msm_sort_flat(ctx, s, b, tab, n, lead ? &job->twin : nullptr));
+        else SWM_TRY(msm_sort_windows(ctx, s, b, n));
     }
-    }  // (!follow)
-    // ---- stage A
-    if (st_acc != st_sort) {
+    if (st_acc != st_sort) {  // stage A
         SWM_HIP(ctx, hipEventRecord(ctx->sort_event[slot], st_sort));
         SWM_HIP(ctx, hipStreamWaitEvent(st_acc, ctx->sort_event[slot], 0));
         ctx->stream = st_acc;
     }
-    unsigned grid_s = (unsigned)((nseg_max + ORD_THREADS - 1) / ORD_THREADS);
-    // segment indices in use (a device word): the flat schedule's bins hand them out by capacity, the per-window schedule densely
-    const uint32_t* seg_space = flat ? flat_seg_off + flat_bins : seg_off + pl.NB;
-    uint32_t* nseg_live = big_count + 3;  // segments that hold entries = lanes of work for the accumulation
-    if (!flat)
-        SWM_LAUNCH(ctx, "msm_seg_order", msm_seg_desc, dim3(grid_s), dim3(ORD_THREADS), 0, bucket_off, seg_off, pl.NB,
-                   SEG, seg_start, seg_len, len_hist);
-    SWM_LAUNCH(ctx, "msm_seg_order", msm_seg_order, dim3((unsigned)((nseg_max + ORD2_THREADS * ORD2_U - 1) / (ORD2_THREADS * ORD2_U))),
-               dim3(ORD2_THREADS), 0, seg_len, seg_space, SEG, (const uint32_t*)len_hist, len_cursor, nseg_live, order);
-    unsigned acc_grid = (unsigned)((nseg_max + 255) / 256);
-    const dim3 big_grid(std::min<unsigned>((pl.NB + (RED_BLOCK >> log_g) - 1) / (RED_BLOCK >> log_g), lat ? 2048 : 512));
-    if (te) {
-        // small jobs (up to 2^20 digits: r04 sweep): four lanes per segment
-        static constexpr size_t quad_acc = 1048576;
-        if (lat && total <= quad_acc && quad_on)
-            SWM_LAUNCH(ctx, "msm_accumulate", msm_accumulate_te_quad, dim3((unsigned)((nseg_max + 63) / 64)), dim3(256), 0, tab.te, sorted,
-                       seg_start, seg_len, order, nseg_live, partial);
-        else
-            SWM_LAUNCH(ctx, "msm_accumulate", msm_accumulate_te, dim3(acc_grid), dim3(256), 0, tab.te, sorted, seg_start,
-                       seg_len, order, nseg_live, partial);
-        SWM_LAUNCH(ctx, "msm_big_bucket_sum", msm_big_bucket_sum<FormTE>, big_grid, dim3(RED_BLOCK), RED_BLOCK * sizeof(G1XYZZ),
-                   partial, seg_off, hist, SEG, big_count, big_list, log_g);
-    } else {
-        SWM_LAUNCH(ctx, "msm_accumulate", msm_accumulate, dim3(acc_grid), dim3(256), 0,
-                   flat ? (const G1Affine*)nullptr : d_bases, flat ? tab.t28 : d_bases28, sorted, seg_start, seg_len, order,
-                   nseg_live, partial);
-        SWM_LAUNCH(ctx, "msm_big_bucket_sum", msm_big_bucket_sum<FormXYZZ>, big_grid, dim3(RED_BLOCK), RED_BLOCK * sizeof(G1XYZZ),
-                   partial, seg_off, hist, SEG, big_count, big_list, log_g);
-    }
+    SWM_TRY(msm_accumulate_stage(ctx, s, b, tab, d_bases, d_bases28));
     job->needs_acc_wait = st_tail != ctx->stream || defer_tail;  // the tail runs on another stream (or later, with others)
-    job->d_partial = partial;
-    job->d_wpart = wpart;
-    job->d_seg_off = seg_off;
-    job->d_hist = hist;
-    job->seg = SEG;
-    job->d_status = big_count + 1;
-    job->d_entries = flat ? flat_off + flat_bins : bucket_off + pl.NB;  // entries the sort placed
+    job->d_partial = b.partial;
+    job->d_seg_off = b.seg_off;
+    job->d_hist = b.hist;
+    job->seg = s.SEG;
+    job->d_status = b.big_count + 1;
+    job->d_entries = s.flat ? b.flat_off + s.flat_bins : b.bucket_off + s.pl.NB;  // entries the sort placed
     job->active = true;
     job->tail_pending = true;
     ctx->slot_busy[slot] = true;
-    if (lane >= 0 || defer_tail) {
+    if (s.lane >= 0 || defer_tail) {
         SWM_HIP(ctx, hipEventRecord(job->acc_done, ctx->stream));
-        if (lane >= 0 && !follow) ctx->set_acc_event[lane] = job->acc_done;
+        if (s.lane >= 0 && !follow) ctx->set_acc_event[s.lane] = job->acc_done;
         if (follow) ctx->twin_sorted_event = job->acc_done;
     }
     job->joint_tail = defer_tail;
@@ -2688,7 +2693,7 @@ int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine*
         ctx->pending_tails.push_back(job);
         return SWM_OK;
     }
-    if (flat && !lat && lane >= 0 && rb == 256 && tab.shard_world <= 1) {
+    if (s.flat && !s.lat && s.lane >= 0 && s.rb == 256 && tab.shard_world <= 1) {
         ctx->lazy_tail = job;  // shaped and launched by the next msm_enqueue (thin) or by the flush of the round (wide)
         return SWM_OK;
     }
@@ -2707,10 +2712,8 @@ static void msm_tail_shape(MsmJob* j, bool wide) {
     // log2 buckets per lane: thin 32 (16 / 8 per lane: 51.5 / 52.5 vs 52.0 ms, r05); wide 4 before the workgroup cap applies
     // (the cap is the job's max_blocks: 256, which makes it 8 per lane for 2^19 buckets)
     static constexpr unsigned thin_log_m = 5u, wide_log_m = 2u;
-    unsigned log_m = wide ? wide_log_m : thin_log_m;
-    while (((j->pl.maxB >> log_m) + j->rb - 1) / j->rb > j->max_blocks) log_m++;
-    j->log_m = log_m;
-    j->red_blocks = std::max(1u, ((j->pl.maxB >> log_m) + j->rb - 1) / j->rb);
+    j->log_m = wide ? wide_log_m : thin_log_m;
+    j->red_blocks = bucket_blocks(j->pl.maxB, j->rb, j->max_blocks, &j->log_m);
     j->blk_hi = j->red_blocks;  // (no bucket-range share on this path: blk_lo = 0, blk_low = 0)
 }
 // Measured in r06 and not kept (CHANGELOG.md): (i) the WIDE stage with four lanes per chain (msm_bucket_reduce<256, FormTEQuad>, 1024
@@ -2732,13 +2735,8 @@ int msm_launch_lazy_tail(swm_ctx* ctx, bool wide) {
 // One bucket-stage launch + the downloads for k <= TAIL_MAX jobs, on the stream of the last one.
 int msm_launch_tails(swm_ctx* ctx, MsmJob** jobs, int k) {
     if (k <= 0) return SWM_OK;
-    hipStream_t st = jobs[k - 1]->stream;
-    struct StreamSwap {
-        swm_ctx* c;
-        hipStream_t old;
-        ~StreamSwap() { c->stream = old; }
-    } swap{ctx, ctx->stream};
-    ctx->stream = st;
+    const hipStream_t st = jobs[k - 1]->stream;
+    StreamSwap swap(ctx, st);
     TailBatch batch;
     memset(&batch, 0, sizeof(batch));
     unsigned max_red = 1, max_win = 1;
@@ -2808,14 +2806,14 @@ static void msm_joint_shape(MsmJob** jobs, size_t k) {
         unsigned total = 0;
         bool ok = true;
         for (size_t i = 0; i < k; i++) {
-            const unsigned nb = std::max(1u, ((jobs[i]->pl.maxB >> log_m) + 255u) / 256u);
-            ok = ok && nb <= jobs[i]->max_blocks;
-            total += nb;
+            unsigned lm = log_m;
+            total += bucket_blocks(jobs[i]->pl.maxB, jobs[i]->rb, jobs[i]->max_blocks, &lm);
+            ok = ok && lm == log_m;  // (fits: bucket_blocks did not have to raise it)
         }
         if (!ok || total > 256) continue;
         for (size_t i = 0; i < k; i++) {
             jobs[i]->log_m = log_m;
-            jobs[i]->red_blocks = std::max(1u, ((jobs[i]->pl.maxB >> log_m) + 255u) / 256u);
+            jobs[i]->red_blocks = bucket_blocks(jobs[i]->pl.maxB, jobs[i]->rb, jobs[i]->max_blocks, &jobs[i]->log_m);
             jobs[i]->blk_hi = jobs[i]->red_blocks;
         }
         return;
