@@ -257,9 +257,7 @@ HostCsr import_csr(const uint32_t* rowptr, const uint32_t* col, const uint64_t* 
 }
 
 // ark-marlin constraint_systems.rs: pad_input_for_indexer_and_prover + make_matrices_square.
-// with_matrices = false (prover): only the assignment and the padded shape are needed — z_A, z_B come from the
-// index's matrices, as in ark-marlin's prover_init.
-PaddedR1cs pad_and_square(const swm_r1cs* cs, bool with_matrices = true) {
+PaddedR1cs pad_and_square(const swm_r1cs* cs) {
     if (!cs || cs->num_instance == 0 || !cs->instance) throw MarlinError(SWM_ERR_INVALID_ARG, "r1cs: bad arguments");
     PaddedR1cs p;
     for (size_t i = 0; i < cs->num_instance; i++) p.inst.push_back(fp_from_limbs<Fr>((const uint32_t*)(cs->instance + 4 * i)));
@@ -271,14 +269,11 @@ PaddedR1cs pad_and_square(const swm_r1cs* cs, bool with_matrices = true) {
     size_t nvars = p.inst.size() + p.wit.size();
     size_t ncons = cs->num_constraints;
     size_t total_cols = nvars;
-    if (with_matrices) {
-        p.a = import_csr(cs->a_rowptr, cs->a_col, cs->a_val, ncons, cs->num_instance, shift, total_cols);
-        p.b = import_csr(cs->b_rowptr, cs->b_col, cs->b_val, ncons, cs->num_instance, shift, total_cols);
-        p.c = import_csr(cs->c_rowptr, cs->c_col, cs->c_val, ncons, cs->num_instance, shift, total_cols);
-    }
+    p.a = import_csr(cs->a_rowptr, cs->a_col, cs->a_val, ncons, cs->num_instance, shift, total_cols);
+    p.b = import_csr(cs->b_rowptr, cs->b_col, cs->b_val, ncons, cs->num_instance, shift, total_cols);
+    p.c = import_csr(cs->c_rowptr, cs->c_col, cs->c_val, ncons, cs->num_instance, shift, total_cols);
     if (nvars > ncons) {
-        if (with_matrices)
-            for (HostCsr* m : {&p.a, &p.b, &p.c}) m->rowptr.resize(nvars + 1, m->rowptr.back());
+        for (HostCsr* m : {&p.a, &p.b, &p.c}) m->rowptr.resize(nvars + 1, m->rowptr.back());
         ncons = nvars;
     } else {
         p.wit.resize(p.wit.size() + (ncons - nvars), fp_one<Fr>());  // dummy unconstrained variables (value one)
@@ -1112,162 +1107,274 @@ void upload_small(swm_ctx* ctx, void* dst, const void* src, size_t bytes) {
     }
     hip_check(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), "h2d");
 }
-std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* cs, ChaChaRng& zk, bool uncompressed = false) {
-    PhaseTrace tr(ctx);
-    static const bool proof_marks = env_flag("SWM_TRACE") || env_flag("SWM_PROOF_MARKS");
-    if (proof_marks) hipLaunchKernelGGL(swm_proof_begin, dim3(1), dim3(1), 0, ctx->stream);
-    // padded shape (pad_input_for_indexer_and_prover + make_matrices_square); the witness itself is uploaded straight
-    // from the caller's buffer, padding is filled on the device
+// padded shape (pad_input_for_indexer_and_prover + make_matrices_square); the witness itself is uploaded straight
+// from the caller's buffer, padding is filled on the device
+struct ProveShape {
+    std::vector<Fr> inst;  // padded to a power of two
+    size_t nwit_orig = 0, nwit = 0, ncons = 0;
+};
+ProveShape prove_shape(const swm_r1cs* cs, const swm_pk& pk) {
     if (!cs || cs->num_instance == 0 || !cs->instance || (cs->num_witness && !cs->witness))
         throw MarlinError(SWM_ERR_INVALID_ARG, "r1cs: bad arguments");
-    struct {
-        std::vector<Fr> inst;
-        size_t nwit_orig, nwit, ncons;
-    } pr;
-    for (size_t i = 0; i < cs->num_instance; i++) pr.inst.push_back(fp_from_limbs<Fr>((const uint32_t*)(cs->instance + 4 * i)));
-    if (!fp_is_one(pr.inst[0])) throw MarlinError(SWM_ERR_INVALID_ARG, "r1cs: instance[0] must be one");
-    pr.inst.resize(HDomain(pr.inst.size()).size, fp_zero<Fr>());
-    pr.nwit_orig = cs->num_witness;
-    {
-        size_t nv = pr.inst.size() + cs->num_witness, nc = cs->num_constraints;
-        pr.nwit = nv > nc ? cs->num_witness : cs->num_witness + (nc - nv);
-        pr.ncons = nv > nc ? nv : nc;
-    }
-    tr.mark("pad_and_square");
-    if (pr.ncons != pk.info.num_constraints || pr.inst.size() + pr.nwit != pk.info.num_variables ||
-        pr.inst.size() != pk.info.num_instance_variables)
+    ProveShape s;
+    for (size_t i = 0; i < cs->num_instance; i++) s.inst.push_back(fp_from_limbs<Fr>((const uint32_t*)(cs->instance + 4 * i)));
+    if (!fp_is_one(s.inst[0])) throw MarlinError(SWM_ERR_INVALID_ARG, "r1cs: instance[0] must be one");
+    s.inst.resize(HDomain(s.inst.size()).size, fp_zero<Fr>());
+    s.nwit_orig = cs->num_witness;
+    const size_t nv = s.inst.size() + cs->num_witness, nc = cs->num_constraints;
+    s.nwit = nv > nc ? cs->num_witness : cs->num_witness + (nc - nv);
+    s.ncons = nv > nc ? nv : nc;
+    if (s.ncons != pk.info.num_constraints || s.inst.size() + s.nwit != pk.info.num_variables ||
+        s.inst.size() != pk.info.num_instance_variables)
         throw MarlinError(SWM_ERR_MISMATCH, "InstanceDoesNotMatchIndex");
-    shard_agree(ctx, pk);  // one proof over several ranks: all of them split the work the same way, or none starts
-    ctx->emulated_exchange = false;
-    const uint64_t H = pk.H, K = pk.K, X = pk.X, Bsz = pk.B;
-    const uint64_t M = 4 * H;  // mul_domain = next_pow2(3|H| + 1)
-    const unsigned logM = pk.logH + 2;
-    const size_t nvars = pk.info.num_variables, ninst = pr.inst.size();
-    HDomain dh(H), dk(K), dx(X);
-    std::vector<Fr> public_input(pr.inst.begin() + 1, pr.inst.end());
+    return s;
+}
+// One proof over G ranks: which rounds run on a rank's share.  A domain of 2^log points can be split when G is a power of two
+// up to 16 and every rank's share holds at least 16 BLOCKS of G points (ntt_sharded_run).
+bool shard_fits(unsigned SG, unsigned slog_g, unsigned log) { return SG > 1 && (1u << slog_g) == SG && SG <= 16 && log >= 2 * slog_g + 4; }
+struct ShardPlan {
+    unsigned SG = 0, slog_g = 0;  // ranks, log2 of that
+    bool r1 = false, r2 = false, r3 = false;
+    size_t sm = 0;          // coefficients (evaluations) of H per rank
+    size_t Mloc = 0, Mblk = 0;  // the rank's points of the 4|H| domain and its BLOCKS size (r2), or the whole domain
+    size_t rank = 0;
+};
+ShardPlan shard_plan(swm_ctx* ctx, const swm_pk& pk) {
+    ShardPlan sp;
+    sp.SG = ctx->shard_world;
+    sp.rank = ctx->shard_rank;
+    while ((1u << sp.slog_g) < sp.SG) sp.slog_g++;
+    const size_t M = 4 * pk.H;
+    sp.r1 = shard_fits(sp.SG, sp.slog_g, pk.logH) && !env_flag("SWM_SHARD_R1_OFF") && commit_cyclic_possible(ctx, pk, pk.H / sp.SG);
+    sp.r2 = shard_fits(sp.SG, sp.slog_g, pk.logH + 2) && !env_flag("SWM_SHARD_R2_OFF");
+    sp.r3 = sp.r2 && shard_fits(sp.SG, sp.slog_g, pk.logB) && pk.K % sp.SG == 0;
+    sp.sm = pk.H / (sp.SG ? sp.SG : 1);
+    sp.Mloc = sp.r2 ? M / sp.SG : M;
+    sp.Mblk = sp.r2 ? sp.Mloc / sp.SG : M;
+    return sp;
+}
+// The rank's share of coeffs[0 .. n) zero-extended to 2^log coefficients, in evaluation form: the CYCLIC share (coefficient
+// rank + G j at j) goes through the sharded forward transform, which leaves the rank's BLOCKS of evaluations.
+DVec shard_evals(swm_ctx* ctx, const ShardPlan& sp, const Fr* coeffs, size_t n, unsigned log) {
+    const size_t len = ((size_t)1 << log) / sp.SG;
+    DVec loc(ctx, len);
+    Fr* out = loc.p;
+    const size_t s_rank = sp.rank, s_world = sp.SG;
+    ew(ctx, "shard_take_cyclic", len, [=] __device__(size_t j) {
+        const size_t i = s_rank + s_world * j;
+        out[j] = i < n ? coeffs[i] : fp_zero<Fr>();
+    });
+    rc_check(ctx, ntt_sharded_run(ctx, loc.p, log, 0, 0));
+    return loc;
+}
+// dst[0 .. n) from the ranks' CYCLIC shares of `per` elements each: element i is element i / G of rank i mod G
+void shard_gather_cyclic(swm_ctx* ctx, const Fr* loc, size_t per, unsigned lg, Fr* dst, size_t n) {
+    DVec all(ctx, per << lg);
+    rc_check(ctx, shard_allgather_dev(ctx, loc, per * sizeof(Fr), all.p));
+    const Fr* src = all.p;
+    ew(ctx, "shard_interleave", n, [=] __device__(size_t i) { dst[i] = src[(i & (((size_t)1 << lg) - 1)) * per + (i >> lg)]; });
+}
+// poly += rho * (X^H - 1); poly has H + 1 slots, slot H = 0
+void add_rho_vh(swm_ctx* ctx, Fr* poly, uint64_t H, const Fr& rho) {
+    ew(ctx, "add_rho_vh", 1, [=] __device__(size_t) {
+        poly[0] = fp_sub(poly[0], rho);
+        poly[H] = fp_add(poly[H], rho);
+    });
+}
+// (h, X g) = divide_by_vanishing_poly(q, H) over q[0 .. total), part = |H|; or on a rank's CYCLIC share with part = |H| / G:
+// coefficient j + k|H| of q sits on the same rank, |H| / G places further
+void div_vh(swm_ctx* ctx, const Fr* q, size_t part, size_t total, Fr* h, Fr* g) {
+    ew(ctx, "div_vh", 3 * part, [=] __device__(size_t j) {
+        Fr acc = q[j + part];
+        if (j + 2 * part < total) acc = fp_add(acc, q[j + 2 * part]);
+        if (j + 3 * part < total) acc = fp_add(acc, q[j + 3 * part]);
+        h[j] = acc;
+        if (j < part) g[j] = fp_add(q[j], acc);
+    });
+}
+// h = q / v_K over q[0 .. total), part = |K|; or on a rank's CYCLIC share with part = |K| / G (as div_vh)
+void div_vk(swm_ctx* ctx, const Fr* q, size_t part, size_t total, Fr* h) {
+    ew(ctx, "div_vk", 3 * part, [=] __device__(size_t j) {
+        Fr acc = fp_zero<Fr>();
+        for (uint64_t i = 1; j + i * part < total; i++) acc = fp_add(acc, q[j + i * part]);
+        h[j] = acc;
+    });
+}
+// alpha^|H| - X^|H| on the 4|H| domain, where X^|H| = i4^(i mod 4), i4 = w4^|H| a primitive fourth root of unity
+struct RAlphaNumerators {
+    Fr n0, n1, n2, n3;
+};
+RAlphaNumerators r_alpha_numerators(const Fr& alpha, unsigned logH, uint64_t M) {
+    Fr aH = alpha;
+    for (unsigned i = 0; i < logH; i++) aH = fp_sqr(aH);
+    Fr i4 = HDomain(M).gen;
+    for (unsigned i = 0; i < logH; i++) i4 = fp_sqr(i4);
+    return {fp_sub(aH, fp_one<Fr>()), fp_sub(aH, i4), fp_sub(aH, fp_sqr(i4)), fp_sub(aH, fp_mul(fp_sqr(i4), i4))};
+}
+// round 3's a - b f at point i of the 4|K| domain, from the index's twelve evaluations there
+struct IndexOnB {
+    const Fr *ar, *ac, *arc, *av;  // row, col, row_col, val of A
+    const Fr *br, *bc, *brc, *bv;
+    const Fr *cr, *cc, *crc, *cv;
+};
+struct Round3Challenges {
+    Fr alpha, beta, ab, eta_a, eta_b, eta_c, vhab;  // ab = beta alpha, vhab = v_H(alpha) v_H(beta)
+};
+__device__ __forceinline__ Fr round3_a_minus_bf(const IndexOnB& x, const Round3Challenges& c, size_t i, const Fr& f) {
+    Fr da = fp_add(fp_sub(fp_sub(c.ab, fp_mul(x.ar[i], c.alpha)), fp_mul(c.beta, x.ac[i])), x.arc[i]);
+    Fr db = fp_add(fp_sub(fp_sub(c.ab, fp_mul(x.br[i], c.alpha)), fp_mul(c.beta, x.bc[i])), x.brc[i]);
+    Fr dc = fp_add(fp_sub(fp_sub(c.ab, fp_mul(x.cr[i], c.alpha)), fp_mul(c.beta, x.cc[i])), x.crc[i]);
+    Fr dbc = fp_mul(db, dc);
+    Fr t = fp_add(fp_add(fp_mul(fp_mul(c.eta_a, x.av[i]), dbc), fp_mul(fp_mul(fp_mul(c.eta_b, x.bv[i]), da), dc)),
+                  fp_mul(fp_mul(fp_mul(c.eta_c, x.cv[i]), da), db));
+    Fr a_val = fp_mul(c.vhab, t);
+    Fr b_val = fp_mul(da, dbc);
+    return fp_sub(a_val, fp_mul(b_val, f));
+}
+// What the stages of one proof share.  The device buffers are declared in the order the stages allocate them, so that they
+// return to the context's pool in the same order as when they were the locals of one function.
+struct ProveState {
+    ChaChaRng& zk;
+    PhaseTrace& tr;
+    const ProveShape shape;
+    const ShardPlan sp;
+    const uint64_t H, K, X, Bsz, M;  // M: mul_domain = next_pow2(3|H| + 1)
+    const unsigned logM;
+    const size_t nvars, ninst;
+    const size_t mask_len;  // degree 3|H| + 2 zk_bound - 3
+    const HDomain dh;
+    const std::vector<Fr> public_input;
     FiatShamirRng fs;
-    fs_init(fs, pk.vk, public_input);
-    // every commitment of a small proof on ONE stream of its lane (msm_enqueue: a proof that mixes single-stream and pipelined
-    // jobs runs them on aliasing streams); SWM_PROVE_ONE_STREAM_LOG: the largest log2 |H| this applies to
-    // (default 19, 0 = never; measured r05, alternating runs: 2^16 7.0 -> 6.5 ms, 2^17 11.2 -> 10.8, 2^18 17.7 -> 17.5, 2^19 29.4 -> 28.6,
-    // Merkle circuit 15.0 -> 14.7; at 2^20 the pipelined form is 1 ms ahead: 49.6 vs 50.6)
-    struct PipeMinScope {
-        swm_ctx* c;
-        ~PipeMinScope() { c->msm_pipe_min = 0; }
-    } pipe_scope{ctx};
-    static const unsigned one_stream_log = (unsigned)env_switch("SWM_PROVE_ONE_STREAM_LOG", 19, 0, 47);
-    ctx->msm_pipe_min = pk.logH <= one_stream_log ? ~(size_t)0 : 0;
-
-    // ---- the zero-knowledge draws of round 1 do not depend on the witness: rho_w, rho_a, rho_b, then the mask polynomial
-    // (arkworks' order).  The mask is sampled and its commitment — the largest MSM of the round, 3|H| points — enqueued
-    // BEFORE the witness upload: a pageable host buffer of 32 MB per 2^20 variables takes ~5 ms to reach HBM, during
-    // which the GPU had nothing to do (r02 timeline).
-    const Fr rho_w = zk.rand_fr(), rho_a = zk.rand_fr(), rho_b = zk.rand_fr();
-    LPoly P_w, P_za, P_zb, P_mask, P_t, P_g1, P_h1, P_g2, P_h2;
+    VerifierState st;
+    Fr rho_w, rho_a, rho_b;
     int lane = 0;
-    // Every commitment MSM is enqueued as soon as its polynomial exists (enqueueing a round's commitments together once ALL its
-    // polynomials are built — so that the transforms do not run beside an accumulation — measured no gain in r02 / r04: the early
-    // MSMs cover more than the slowed transforms cost; CHANGELOG.md).
-    auto begin_commit = [&](const Fr* coeffs, size_t n, bool has_bound, uint64_t bound, bool hiding, CommitJob* job, int /*tag*/) {
-        pc_commit_begin(ctx, pk, &lane, coeffs, n, has_bound, bound, hiding, job);
-    };
-    auto flush_commits = [&] { commit_flush(ctx); };
-    CommitJob j1[4];
-    // mask polynomial: 3|H| uniform coefficients drawn from the caller's rng, H-sum forced to zero
-    const size_t mask_len = 3 * H;  // degree 3|H| + 2 zk_bound - 3
-    DVec mask(ctx, mask_len);
+    LPoly P_w, P_za, P_zb, P_mask, P_t, P_g1, P_h1, P_g2, P_h2;
+    LPoly idx_polys[12];
+    std::map<std::string, LPoly*> polys;
+    CommitJob j1[4], j2[3], j3[2];
+    std::vector<Commitment> comms1 = std::vector<Commitment>(4), comms2 = std::vector<Commitment>(3),
+                            comms3 = std::vector<Commitment>(2);
+    bool mask_late = false;  // the mask is drawn from a caller-owned generator after the rest of round 1 is enqueued
+    unsigned mask_pieces = 1;
+    AsyncMsm mask_part[2];
+    bool ra_closed_form = false;
+    LcSet lcs;
+    DVec mask, z, za_evals, zb_evals, za_loc, zb_loc, x_poly, x_evals, w_poly, za_poly, zb_poly, e_za, e_zb, e_z;
+    DVec r_alpha_evals, e_ra, t_poly, q1, h1, g1x, f, h2;
+
+    ProveState(const swm_pk& pk, ChaChaRng& rng, PhaseTrace& t, ProveShape shp, const ShardPlan& plan)
+        : zk(rng), tr(t), shape(std::move(shp)), sp(plan), H(pk.H), K(pk.K), X(pk.X), Bsz(pk.B), M(4 * pk.H),
+          logM(pk.logH + 2), nvars(pk.info.num_variables), ninst(shape.inst.size()), mask_len(3 * pk.H), dh(pk.H),
+          public_input(shape.inst.begin() + 1, shape.inst.end()) {
+        fs_init(fs, pk.vk, public_input);
+        for (int m = 0; m < 3; m++) {
+            const DVec* v[4] = {&pk.ar[m].row, &pk.ar[m].col, &pk.ar[m].val, &pk.ar[m].row_col};
+            for (int j = 0; j < 4; j++) {
+                idx_polys[4 * m + j].p = v[j]->p;
+                idx_polys[4 * m + j].n = K;
+                polys[kIndexerPolys[4 * m + j]] = &idx_polys[4 * m + j];
+            }
+        }
+        polys["w"] = &P_w; polys["z_a"] = &P_za; polys["z_b"] = &P_zb; polys["mask_poly"] = &P_mask;
+        polys["t"] = &P_t; polys["g_1"] = &P_g1; polys["h_1"] = &P_h1; polys["g_2"] = &P_g2; polys["h_2"] = &P_h2;
+    }
+};
+
+// ---- round 1: the mask polynomial, 3|H| uniform coefficients drawn from the caller's rng with the H-sum forced to zero,
+// and its commitment
+void draw_mask(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    const uint64_t H = s.H;
+    Fr* mp = s.mask.p;
+    if (s.mask_pieces > 1) {
+        // ONE draw of 3|H| coefficients; whenever the host learns how many are in place (sample_fr_bulk: `progress`) the pieces
+        // that are complete are committed: [1, H) | [H, 2H) | [2H, 3H) (three pieces; two: [1, H) | [H, 3H)).  One draw, not
+        // three: every draw ends with a geometric tail of ever shorter runs (a run may not reach beyond the candidate that
+        // completes the draw), ~1.5 ms each.
+        CommitJob& job = s.j1[3];
+        job.has_bound = false;
+        job.hiding = false;
+        unsigned done_pieces = 0;
+        struct PieceEvent {  // destroyed on every way out (commit_enqueue may throw from inside the draw's progress callback)
+            hipEvent_t e = nullptr;
+            ~PieceEvent() {
+                if (e) (void)hipEventDestroy(e);
+            }
+        } piece_guard;
+        hip_check(ctx, hipEventCreateWithFlags(&piece_guard.e, hipEventDisableTiming), "event");
+        const hipEvent_t piece_ev = piece_guard.e;
+        auto enqueue_piece = [&](unsigned pc) {  // the elements of the piece are written by kernels already on the copy stream
+            hip_check(ctx, hipEventRecord(piece_ev, ctx->copy_stream), "record");
+            hip_check(ctx, hipStreamWaitEvent(ctx->stream, piece_ev, 0), "wait");
+            if (pc == 0) commit_enqueue(ctx, &s.lane, pk, 1, mp + 1, H - 1, &job.plain);
+            else if (s.mask_pieces == 3) commit_enqueue(ctx, &s.lane, pk, pc * H, mp + pc * H, H, &s.mask_part[pc - 1]);
+            else if (pc == 2) commit_enqueue(ctx, &s.lane, pk, H, mp + H, 2 * H, &s.mask_part[0]);
+        };
+        const std::function<void(size_t)> progress = [&](size_t have) {
+            while (done_pieces < 2 && have >= (size_t)(done_pieces + 1) * H) enqueue_piece(done_pieces++);
+        };
+        sample_fr_bulk(ctx, s.zk, mp, s.mask_len, s.mask_late, &progress);
+        while (done_pieces < 3) enqueue_piece(done_pieces++);  // (after the draw ctx->stream waits for all of it anyway)
+    } else {
+        sample_fr_bulk(ctx, s.zk, mp, s.mask_len, s.mask_late);
+    }
+    ew(ctx, "mask_fix", 1, [=] __device__(size_t) {
+        // remainder mod v_H at coefficient 0 = c[0] + c[H] + c[2H]; subtracting it from c[0] leaves -(c[H] + c[2H])
+        mp[0] = fp_neg(fp_add(mp[H], mp[2 * H]));
+    });
+    s.P_mask.p = mp;
+    s.P_mask.n = s.mask_len;
+    // (the mask's 3|H|-point commitment enqueued behind w's or behind z_B's instead of first: + 0.4 ... + 1.9 ms at 2^20, r05)
+    if (s.mask_pieces == 1) pc_commit_begin(ctx, pk, &s.lane, s.P_mask.p, s.P_mask.n, false, 0, false, &s.j1[3]);
+}
+void begin_mask(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    s.mask = DVec(ctx, s.mask_len);
     // A caller-owned generator (swm_rng_from_callback) produces the mask on the HOST, through its fill_bytes: ~170 MB at
     // |H| = 2^20, i.e. tens of milliseconds of the caller's ChaCha.  That draw is therefore requested AFTER the rest of
     // round 1 has been enqueued (witness upload, mat-vecs, the three other polynomials and their commitments, the
     // challenge-independent transforms of round 2), so that the GPU works while the host draws.  The draw ORDER is
-    // untouched: nothing between here and there touches `zk` (rho_w, rho_a, rho_b were drawn above, the blinding
+    // untouched: nothing between here and there touches `zk` (rho_w, rho_a, rho_b were drawn before, the blinding
     // polynomials are drawn after the round's last commitment is enqueued, as before).
-    const bool mask_late = zk.ext != nullptr;
+    s.mask_late = s.zk.ext != nullptr;
     // r05: with a caller-owned generator the commitment is computed IN PIECES — the MSM over the coefficients [1, |H|) is
     // enqueued as soon as the first |H| coefficients are there and runs while the host draws the next |H|, and so on; what is
     // exposed behind the draw is a third of the MSM instead of all of it.  Coefficient 0 is only known after the whole draw
-    // (mask_fix below): its term [c_0] g is one scalar multiplication on the host.  A commitment is a sum over coefficients, so
+    // (mask_fix): its term [c_0] g is one scalar multiplication on the host.  A commitment is a sum over coefficients, so
     // the pieces add up to the same group element: same bytes (test_callback_rng_reproduces_golden_bytes).  SWM_MASK_PIECES=1:
     // one piece (r02 - r04).  Sharded proofs keep one piece (their commitments are split over the ranks already).
     static const unsigned mask_pieces_env = (unsigned)env_switch("SWM_MASK_PIECES", 3, 1, 3);
-    const unsigned mask_pieces = mask_late && ctx->shard_world <= 1 && H >= 4096 ? mask_pieces_env : 1u;
-    AsyncMsm mask_part[2];
-    auto draw_mask = [&] {
-        Fr* mp = mask.p;
-        if (mask_pieces > 1) {
-            // ONE draw of 3|H| coefficients; whenever the host learns how many are in place (sample_fr_bulk: `progress`) the pieces
-            // that are complete are committed: [1, H) | [H, 2H) | [2H, 3H) (three pieces; two: [1, H) | [H, 3H)).  One draw, not
-            // three: every draw ends with a geometric tail of ever shorter runs (a run may not reach beyond the candidate that
-            // completes the draw), ~1.5 ms each.
-            j1[3].has_bound = false;
-            j1[3].hiding = false;
-            unsigned done_pieces = 0;
-            struct PieceEvent {  // destroyed on every way out (commit_enqueue may throw from inside the draw's progress callback)
-                hipEvent_t e = nullptr;
-                ~PieceEvent() {
-                    if (e) (void)hipEventDestroy(e);
-                }
-            } piece_guard;
-            hip_check(ctx, hipEventCreateWithFlags(&piece_guard.e, hipEventDisableTiming), "event");
-            const hipEvent_t piece_ev = piece_guard.e;
-            auto enqueue_piece = [&](unsigned pc) {  // the elements of the piece are written by kernels already on the copy stream
-                hip_check(ctx, hipEventRecord(piece_ev, ctx->copy_stream), "record");
-                hip_check(ctx, hipStreamWaitEvent(ctx->stream, piece_ev, 0), "wait");
-                if (pc == 0) commit_enqueue(ctx, &lane, pk, 1, mp + 1, H - 1, &j1[3].plain);
-                else if (mask_pieces == 3) commit_enqueue(ctx, &lane, pk, pc * H, mp + pc * H, H, &mask_part[pc - 1]);
-                else if (pc == 2) commit_enqueue(ctx, &lane, pk, H, mp + H, 2 * H, &mask_part[0]);
-            };
-            const std::function<void(size_t)> progress = [&](size_t have) {
-                while (done_pieces < 2 && have >= (size_t)(done_pieces + 1) * H) enqueue_piece(done_pieces++);
-            };
-            sample_fr_bulk(ctx, zk, mp, mask_len, mask_late, &progress);
-            while (done_pieces < 3) enqueue_piece(done_pieces++);  // (after the draw ctx->stream waits for all of it anyway)
-        } else {
-            sample_fr_bulk(ctx, zk, mask.p, mask_len, mask_late);
-        }
-        ew(ctx, "mask_fix", 1, [=] __device__(size_t) {
-            // remainder mod v_H at coefficient 0 = c[0] + c[H] + c[2H]; subtracting it from c[0] leaves -(c[H] + c[2H])
-            mp[0] = fp_neg(fp_add(mp[H], mp[2 * H]));
-        });
-        P_mask.p = mask.p; P_mask.n = mask_len;
-        // (the mask's 3|H|-point commitment enqueued behind w's or behind z_B's instead of first: + 0.4 ... + 1.9 ms at 2^20, r05)
-        if (mask_pieces == 1) begin_commit(P_mask.p, P_mask.n, false, 0, false, &j1[3], 0);
-    };
-    if (mask_late) sample_fr_ext_mark(ctx);  // the transfers of the late draw only wait for what precedes the allocation
-    else draw_mask();
+    s.mask_pieces = s.mask_late && ctx->shard_world <= 1 && s.H >= 4096 ? mask_pieces_env : 1u;
+    if (s.mask_late) sample_fr_ext_mark(ctx);  // the transfers of the late draw only wait for what precedes the allocation
+    else draw_mask(ctx, pk, s);
+}
 
-    // ---- z on the device, z_A = A z, z_B = B z  (K3)
-    DVec z(ctx, nvars);
+// ---- z on the device, z_A = A z, z_B = B z  (K3)
+// One proof over G GPUs: z_A = A z and z_B = B z are computed BY ROWS — every rank the rows of its blocks
+// (the BLOCKS layout of ntt.hip; z is the witness every rank was handed, so no broadcast is needed) — interpolated by the
+// sharded inverse transform (one all-to-all each), which leaves the coefficients CYCLIC over the ranks, and committed
+// where they are (commit_enqueue_cyclic): no gather between mat-vec, transform and MSM.  The rest of the proof still
+// works on whole polynomials, so the pieces are all-gathered once afterwards (H x 32 B per polynomial over all links).
+void upload_witness(swm_ctx* ctx, const swm_pk& pk, ProveState& s, const swm_r1cs* cs) {
+    const ProveShape& shape = s.shape;
+    s.z = DVec(ctx, s.nvars);
     // (the staging area is free again: whatever the previous proof of this context staged was consumed before that proof returned)
     ctx->h2d_stage_used = 0;
-    upload_small(ctx, z.p, pr.inst.data(), ninst * sizeof(Fr));
-    if (pr.nwit_orig) upload_small(ctx, z.p + ninst, cs->witness, pr.nwit_orig * sizeof(Fr));
-    if (pr.nwit > pr.nwit_orig) {  // dummy unconstrained variables have the value one
-        Fr* zp = z.p + ninst + pr.nwit_orig;
-        ew(ctx, "z_pad", pr.nwit - pr.nwit_orig, [=] __device__(size_t i) { zp[i] = fp_one<Fr>(); });
+    upload_small(ctx, s.z.p, shape.inst.data(), s.ninst * sizeof(Fr));
+    if (shape.nwit_orig) upload_small(ctx, s.z.p + s.ninst, cs->witness, shape.nwit_orig * sizeof(Fr));
+    if (shape.nwit > shape.nwit_orig) {  // dummy unconstrained variables have the value one
+        Fr* zp = s.z.p + s.ninst + shape.nwit_orig;
+        ew(ctx, "z_pad", shape.nwit - shape.nwit_orig, [=] __device__(size_t i) { zp[i] = fp_one<Fr>(); });
     }
-    // One proof over G GPUs: z_A = A z and z_B = B z are computed BY ROWS — every rank the rows of its blocks
-    // (the BLOCKS layout of ntt.hip; z is the witness every rank was handed, so no broadcast is needed) — interpolated by the
-    // sharded inverse transform (one all-to-all each), which leaves the coefficients CYCLIC over the ranks, and committed
-    // where they are (commit_enqueue_cyclic): no gather between mat-vec, transform and MSM.  The rest of the proof still
-    // works on whole polynomials, so the pieces are all-gathered once afterwards (H x 32 B per polynomial over all links).
-    const unsigned SG = ctx->shard_world;
-    unsigned slog_g = 0;
-    while ((1u << slog_g) < SG) slog_g++;
-    const bool shard_r1 = SG > 1 && (1u << slog_g) == SG && SG <= 16 && pk.logH >= 2 * slog_g + 4 && !env_flag("SWM_SHARD_R1_OFF") &&
-                          commit_cyclic_possible(ctx, pk, H / SG);
-    const size_t sm = H / (SG ? SG : 1);  // coefficients (evaluations) per rank
-    DVec za_evals, zb_evals, za_loc, zb_loc;
-    if (shard_r1) {
-        za_loc = dv_zeros(ctx, sm + 1);
-        zb_loc = dv_zeros(ctx, sm + 1);
-        const unsigned blk_log = pk.logH - 2 * slog_g;
-        const size_t row0 = (size_t)ctx->shard_rank << blk_log;
+    if (s.sp.r1) {
+        const size_t sm = s.sp.sm;
+        s.za_loc = dv_zeros(ctx, sm + 1);
+        s.zb_loc = dv_zeros(ctx, sm + 1);
+        const unsigned blk_log = pk.logH - 2 * s.sp.slog_g;
+        const size_t row0 = s.sp.rank << blk_log;
         auto rows_of_my_blocks = [&](const DevCsr& mtx, Fr* out) {
             const uint32_t* rowptr = mtx.rowptr.p;
             const uint32_t* col = mtx.col.p;
             const Fr* val = mtx.val.p;
-            const Fr* zz = z.p;
+            const Fr* zz = s.z.p;
             const size_t nrows = mtx.rows;
             ctx->stat_spmv_calls++;
             ctx->stat_spmv_rows += sm;
@@ -1283,30 +1390,53 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
                 out[x] = acc;
             });
         };
-        rows_of_my_blocks(pk.a, za_loc.p);
-        rows_of_my_blocks(pk.b, zb_loc.p);
+        rows_of_my_blocks(pk.a, s.za_loc.p);
+        rows_of_my_blocks(pk.b, s.zb_loc.p);
     } else {
-        za_evals = dv_zeros(ctx, H);
-        zb_evals = dv_zeros(ctx, H);
-        rc_check(ctx, spmv_run(ctx, pk.a.rowptr.p, pk.a.col.p, pk.a.val.p, z.p, za_evals.p, pk.a.rows, &pk.a.plan));
-        rc_check(ctx, spmv_run(ctx, pk.b.rowptr.p, pk.b.col.p, pk.b.val.p, z.p, zb_evals.p, pk.b.rows, &pk.b.plan));
+        s.za_evals = dv_zeros(ctx, s.H);
+        s.zb_evals = dv_zeros(ctx, s.H);
+        rc_check(ctx, spmv_run(ctx, pk.a.rowptr.p, pk.a.col.p, pk.a.val.p, s.z.p, s.za_evals.p, pk.a.rows, &pk.a.plan));
+        rc_check(ctx, spmv_run(ctx, pk.b.rowptr.p, pk.b.col.p, pk.b.val.p, s.z.p, s.zb_evals.p, pk.b.rows, &pk.b.plan));
     }
+}
 
-    tr.mark("upload z, z_A, z_B");
-    // ================= round 1
+// sharded form of "interpolate, add rho v_H, commit" for z_A or z_B: the rank's evaluations `loc` become its CYCLIC
+// coefficients, committed where they are; `poly` receives the whole polynomial
+void sharded_interpolate_and_commit(swm_ctx* ctx, const swm_pk& pk, ProveState& s, DVec& loc, const Fr& rho, DVec& poly,
+                                    CommitJob* job) {
+    const uint64_t H = s.H;
+    const size_t sm = s.sp.sm;
+    rc_check(ctx, ntt_sharded_run(ctx, loc.p, pk.logH, 1, 1));  // evaluations in BLOCKS -> coefficients rank + G j at loc[j]
+    shard_gather_cyclic(ctx, loc.p, sm, s.sp.slog_g, poly.p, H);  // the whole polynomial for the replicated rest of the proof
+    add_rho_vh(ctx, poly.p, H, rho);
+    if (ctx->shard_rank == 0) {  // coefficients 0 and H = 0 + G (H / G) both live on rank 0
+        Fr* lp = loc.p;
+        const size_t top = sm;
+        ew(ctx, "add_rho_vh", 1, [=] __device__(size_t) {
+            lp[0] = fp_sub(lp[0], rho);
+            lp[top] = rho;
+        });
+    }
+    job->has_bound = false;
+    job->hiding = true;
+    commit_enqueue_cyclic(ctx, &s.lane, pk, loc.p, ctx->shard_rank == 0 ? sm + 1 : sm, &job->plain);
+}
+// ---- round 1: w, z_A and z_B as polynomials, and their commitments
+void round1_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    const uint64_t H = s.H, X = s.X;
     // x_poly = interpolate(formatted input over X); x_evals = FFT_H(x_poly)
-    DVec x_poly(ctx, X);
-    x_poly.upload(pr.inst.data(), X);
-    dv_ntt(ctx, x_poly, pk.logX, true);
-    DVec x_evals = dv_ntt_from(ctx, x_poly.p, X, pk.logH, false);
+    s.x_poly = DVec(ctx, X);
+    s.x_poly.upload(s.shape.inst.data(), X);
+    dv_ntt(ctx, s.x_poly, pk.logX, true);
+    s.x_evals = dv_ntt_from(ctx, s.x_poly.p, X, pk.logH, false);
     // w evaluations on H: 0 on the X-subgroup positions, w_extended[k - k/ratio - 1] - x_evals[k] elsewhere
     const uint64_t ratio = H / X;
-    const size_t nwit = pr.nwit;
-    DVec w_poly = dv_zeros(ctx, H + 1);
+    const size_t nwit = s.shape.nwit, ninst = s.ninst;
+    s.w_poly = dv_zeros(ctx, H + 1);
     {
-        Fr* out = w_poly.p;
-        const Fr* zz = z.p;
-        const Fr* xe = x_evals.p;
+        Fr* out = s.w_poly.p;
+        const Fr* zz = s.z.p;
+        const Fr* xe = s.x_evals.p;
         ew(ctx, "w_evals", H, [=] __device__(size_t k) {
             Fr v = fp_zero<Fr>();
             if (k % ratio != 0) {
@@ -1317,321 +1447,256 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
             out[k] = v;
         });
     }
-    {
-        rc_check(ctx, ntt_run(ctx, w_poly.p, pk.logH, 1, 0));  // in place on the first H of its H + 1 slots
-    }
-    auto add_rho_vh = [&](Fr* poly, const Fr& rho) {  // poly += rho * (X^H - 1); poly has H + 1 slots, slot H = 0
-        ew(ctx, "add_rho_vh", 1, [=] __device__(size_t) {
-            poly[0] = fp_sub(poly[0], rho);
-            poly[H] = fp_add(poly[H], rho);
-        });
-    };
-    add_rho_vh(w_poly.p, rho_w);
+    rc_check(ctx, ntt_run(ctx, s.w_poly.p, pk.logH, 1, 0));  // in place on the first H of its H + 1 slots
+    add_rho_vh(ctx, s.w_poly.p, H, s.rho_w);
     // divide by v_X (exact): quotient = strided suffix sums, w_poly <- quotient (degree <= H - X)
-    suffix_recurrence(ctx, w_poly.p, H + 1, X, fr_one());
-    const Fr* w_coeffs = w_poly.p + X;  // quotient[j] = s[j + X]
-    const size_t w_len = H + 1 - X;
-    P_w.p = w_coeffs; P_w.n = w_len; P_w.hiding = true;
-    begin_commit(P_w.p, P_w.n, false, 0, true, &j1[0], 1);
-    DVec za_poly = dv_zeros(ctx, H + 1), zb_poly = dv_zeros(ctx, H + 1);
-    // sharded form of "interpolate, add rho v_H, commit" for one of the two polynomials
-    auto sharded_interpolate_and_commit = [&](DVec& loc, const Fr& rho, DVec& poly, CommitJob* job) {
-        rc_check(ctx, ntt_sharded_run(ctx, loc.p, pk.logH, 1, 1));  // evaluations in BLOCKS -> coefficients rank + G j at loc[j]
-        {   // the whole polynomial for the replicated rest of the proof: all-gather the pieces, interleave
-            DVec all(ctx, H);
-            rc_check(ctx, shard_allgather_dev(ctx, loc.p, sm * sizeof(Fr), all.p));
-            const Fr* src = all.p;
-            Fr* dst = poly.p;
-            const unsigned lg = slog_g;
-            const size_t per = sm;
-            ew(ctx, "shard_interleave", H, [=] __device__(size_t i) { dst[i] = src[(i & (((size_t)1 << lg) - 1)) * per + (i >> lg)]; });
-        }
-        add_rho_vh(poly.p, rho);
-        if (ctx->shard_rank == 0) {  // coefficients 0 and H = 0 + G (H / G) both live on rank 0
-            Fr* lp = loc.p;
-            const size_t top = sm;
-            ew(ctx, "add_rho_vh", 1, [=] __device__(size_t) {
-                lp[0] = fp_sub(lp[0], rho);
-                lp[top] = rho;
-            });
-        }
-        job->has_bound = false;
-        job->hiding = true;
-        commit_enqueue_cyclic(ctx, &lane, pk, loc.p, ctx->shard_rank == 0 ? sm + 1 : sm, &job->plain);
-    };
-    if (shard_r1) {
-        sharded_interpolate_and_commit(za_loc, rho_a, za_poly, &j1[1]);
-        sharded_interpolate_and_commit(zb_loc, rho_b, zb_poly, &j1[2]);
+    suffix_recurrence(ctx, s.w_poly.p, H + 1, X, fr_one());
+    s.P_w.p = s.w_poly.p + X;  // quotient[j] = s[j + X]
+    s.P_w.n = H + 1 - X;
+    s.P_w.hiding = true;
+    pc_commit_begin(ctx, pk, &s.lane, s.P_w.p, s.P_w.n, false, 0, true, &s.j1[0]);
+    s.za_poly = dv_zeros(ctx, H + 1);
+    s.zb_poly = dv_zeros(ctx, H + 1);
+    s.P_za.p = s.za_poly.p; s.P_za.n = H + 1; s.P_za.hiding = true;
+    s.P_zb.p = s.zb_poly.p; s.P_zb.n = H + 1; s.P_zb.hiding = true;
+    if (s.sp.r1) {
+        sharded_interpolate_and_commit(ctx, pk, s, s.za_loc, s.rho_a, s.za_poly, &s.j1[1]);
+        sharded_interpolate_and_commit(ctx, pk, s, s.zb_loc, s.rho_b, s.zb_poly, &s.j1[2]);
     } else {
-        rc_check(ctx, ntt_run_from(ctx, za_poly.p, pk.logH, 1, 0, za_evals.p, H));  // evaluations -> the first H of H + 1 slots
-        add_rho_vh(za_poly.p, rho_a);
-        rc_check(ctx, ntt_run_from(ctx, zb_poly.p, pk.logH, 1, 0, zb_evals.p, H));
-        add_rho_vh(zb_poly.p, rho_b);
-    }
-    P_za.p = za_poly.p; P_za.n = H + 1; P_za.hiding = true;
-    P_zb.p = zb_poly.p; P_zb.n = H + 1; P_zb.hiding = true;
-    if (!shard_r1) {
+        rc_check(ctx, ntt_run_from(ctx, s.za_poly.p, pk.logH, 1, 0, s.za_evals.p, H));  // evaluations -> the first H of H + 1 slots
+        add_rho_vh(ctx, s.za_poly.p, H, s.rho_a);
+        rc_check(ctx, ntt_run_from(ctx, s.zb_poly.p, pk.logH, 1, 0, s.zb_evals.p, H));
+        add_rho_vh(ctx, s.zb_poly.p, H, s.rho_b);
         // (enqueue order only: the results are awaited and blinded in label order; z_B's ahead of z_A's: + 0.9 ms at 2^20, r05)
-        begin_commit(P_za.p, P_za.n, false, 0, true, &j1[1], 2);
-        begin_commit(P_zb.p, P_zb.n, false, 0, true, &j1[2], 2);
+        pc_commit_begin(ctx, pk, &s.lane, s.P_za.p, s.P_za.n, false, 0, true, &s.j1[1]);
+        pc_commit_begin(ctx, pk, &s.lane, s.P_zb.p, s.P_zb.n, false, 0, true, &s.j1[2]);
     }
-    tr.mark("round 1 polynomials");
-    std::vector<Commitment> comms1(4);
-    if (!mask_late) flush_commits();  // round 1: all four commitments enqueued here; small ones share one bucket-stage launch
-    // Challenge-independent part of round 2, issued now so that it runs under the round-1 commitments instead of
-    // after them: z_A, z_B and z = w v_X + x in evaluation form on the 4|H| domain.
-    // Round 2 over G ranks (r03): the four transforms of size 4|H| into the product domain, the pointwise outer-sumcheck form and
-    // the transform back run on a rank's share — CYCLIC coefficients (every rank holds the polynomials: it takes g, g + G, ...)
-    // -> BLOCKS evaluations by ONE all-to-all each (ntt_sharded_run), pointwise on the blocks, BLOCKS -> CYCLIC back; the mask
-    // and the division by v_H are local in the CYCLIC layout (G divides |H|: index j + k|H| stays on its rank).  h_1 and X g_1 are
-    // all-gathered afterwards (4|H| x 32 B per proof): the openings work on whole polynomials.  SWM_SHARD_R2_OFF disables it.
-    const bool shard_r2 = SG > 1 && (1u << slog_g) == SG && SG <= 16 && logM >= 2 * slog_g + 4 && !env_flag("SWM_SHARD_R2_OFF");
-    const size_t Mloc = shard_r2 ? M / SG : M, Mblk = shard_r2 ? Mloc / SG : M;
-    const size_t s_rank = ctx->shard_rank, s_world = SG;
-    auto on_mul_domain = [&](const Fr* coeffs, size_t n) {
-        if (!shard_r2) return dv_ntt_from(ctx, coeffs, n, logM, false);
-        DVec loc(ctx, Mloc);
-        Fr* out = loc.p;
-        ew(ctx, "shard_take_cyclic", Mloc, [=] __device__(size_t j) {
-            const size_t i = s_rank + s_world * j;
-            out[j] = i < n ? coeffs[i] : fp_zero<Fr>();
-        });
-        rc_check(ctx, ntt_sharded_run(ctx, loc.p, logM, 0, 0));
-        return loc;
-    };
-    DVec e_za = on_mul_domain(za_poly.p, H + 1);
-    DVec e_zb = on_mul_domain(zb_poly.p, H + 1);
-    DVec e_z;
-    {
-        DVec z_poly = dv_zeros(ctx, H + 1);
-        Fr* out = z_poly.p;
-        const Fr* wc = w_coeffs;
-        const Fr* xp = x_poly.p;
-        ew(ctx, "z_poly", H + 1, [=] __device__(size_t i) {
-            Fr v = fp_zero<Fr>();
-            if (i >= X && i - X < w_len) v = wc[i - X];
-            if (i < w_len) v = fp_sub(v, wc[i]);
-            if (i < X) v = fp_add(v, xp[i]);
-            out[i] = v;
-        });
-        e_z = on_mul_domain(z_poly.p, H + 1);
-    }
-    if (mask_late) {  // everything else of the round is in flight: now the host draws the mask from the caller's generator
-        draw_mask();
-        flush_commits();
-    }
-    tr.tick("r1: pre-work enqueued");
+}
+
+// Round 2 over G ranks (r03): the four transforms of size 4|H| into the product domain, the pointwise outer-sumcheck form and
+// the transform back run on a rank's share — CYCLIC coefficients (every rank holds the polynomials: it takes g, g + G, ...)
+// -> BLOCKS evaluations by ONE all-to-all each (ntt_sharded_run), pointwise on the blocks, BLOCKS -> CYCLIC back; the mask
+// and the division by v_H are local in the CYCLIC layout (G divides |H|: index j + k|H| stays on its rank).  h_1 and X g_1 are
+// all-gathered afterwards (4|H| x 32 B per proof): the openings work on whole polynomials.  SWM_SHARD_R2_OFF disables it.
+DVec on_mul_domain(swm_ctx* ctx, const ProveState& s, const Fr* coeffs, size_t n) {
+    if (!s.sp.r2) return dv_ntt_from(ctx, coeffs, n, s.logM, false);
+    return shard_evals(ctx, s.sp, coeffs, n, s.logM);
+}
+// ---- the challenge-independent part of round 2, issued before the round-1 commitments are awaited so that it runs under
+// them: z_A, z_B and z = w v_X + x in evaluation form on the 4|H| domain
+void round2_prework(swm_ctx* ctx, ProveState& s) {
+    const uint64_t H = s.H, X = s.X;
+    s.e_za = on_mul_domain(ctx, s, s.za_poly.p, H + 1);
+    s.e_zb = on_mul_domain(ctx, s, s.zb_poly.p, H + 1);
+    DVec z_poly = dv_zeros(ctx, H + 1);
+    Fr* out = z_poly.p;
+    const Fr* wc = s.P_w.p;
+    const size_t w_len = s.P_w.n;
+    const Fr* xp = s.x_poly.p;
+    ew(ctx, "z_poly", H + 1, [=] __device__(size_t i) {
+        Fr v = fp_zero<Fr>();
+        if (i >= X && i - X < w_len) v = wc[i - X];
+        if (i < w_len) v = fp_sub(v, wc[i]);
+        if (i < X) v = fp_add(v, xp[i]);
+        out[i] = v;
+    });
+    s.e_z = on_mul_domain(ctx, s, z_poly.p, H + 1);
+}
+
+// ---- end of round 1: blinding, the rest of a mask committed in pieces, the commitments
+void round1_commitments(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
     // blinding draws and hiding terms (label order: w, z_a, z_b, mask) while the MSMs run
-    pc_commit_blind(pk, &j1[0], &zk, &P_w.rand);
-    pc_commit_blind(pk, &j1[1], &zk, &P_za.rand);
-    pc_commit_blind(pk, &j1[2], &zk, &P_zb.rand);
-    pc_commit_blind(pk, &j1[3], nullptr, &P_mask.rand);
-    if (mask_pieces > 1) {  // the other pieces of the mask commitment and the term of coefficient 0
-        Fr c0 = mask.download(0, 1)[0];
+    pc_commit_blind(pk, &s.j1[0], &s.zk, &s.P_w.rand);
+    pc_commit_blind(pk, &s.j1[1], &s.zk, &s.P_za.rand);
+    pc_commit_blind(pk, &s.j1[2], &s.zk, &s.P_zb.rand);
+    pc_commit_blind(pk, &s.j1[3], nullptr, &s.P_mask.rand);
+    if (s.mask_pieces > 1) {  // the other pieces of the mask commitment and the term of coefficient 0
+        Fr c0 = s.mask.download(0, 1)[0];
         Fr c0s = fp_to_std(c0);
         G1XYZZ extra = g1_mul_limbs(pk.vk.vk.g, c0s.v, 8);
-        for (unsigned k = 0; k + 1 < mask_pieces; k++) g1_add(extra, commit_wait(ctx, &mask_part[k]));
-        j1[3].has_extra = true;
-        j1[3].extra = extra;
+        for (unsigned k = 0; k + 1 < s.mask_pieces; k++) g1_add(extra, commit_wait(ctx, &s.mask_part[k]));
+        s.j1[3].has_extra = true;
+        s.j1[3].extra = extra;
     }
-    commit_gather(ctx, {&j1[0].plain, &j1[1].plain, &j1[2].plain, &j1[3].plain});
-    pc_commit_end_round(ctx, pk, {&j1[0], &j1[1], &j1[2], &j1[3]}, {&zk, &zk, &zk, nullptr},
-                        {&P_w.rand, &P_za.rand, &P_zb.rand, &P_mask.rand}, comms1.data());
-    tr.mark("round 1 commitments");
-    fs_absorb_commitments(fs, comms1);
-    VerifierState st;
-    st.alpha = fs.sample_outside(dh);
-    st.eta_a = fs.rand_fr();
-    st.eta_b = fs.rand_fr();
-    st.eta_c = fs.rand_fr();
+    commit_gather(ctx, {&s.j1[0].plain, &s.j1[1].plain, &s.j1[2].plain, &s.j1[3].plain});
+    pc_commit_end_round(ctx, pk, {&s.j1[0], &s.j1[1], &s.j1[2], &s.j1[3]}, {&s.zk, &s.zk, &s.zk, nullptr},
+                        {&s.P_w.rand, &s.P_za.rand, &s.P_zb.rand, &s.P_mask.rand}, s.comms1.data());
+}
 
-    // ================= round 2
-    const Fr alpha = st.alpha, eta_a = st.eta_a, eta_b = st.eta_b, eta_c = st.eta_c;
-    // r(alpha, X) = (alpha^|H| - X^|H|) / (alpha - X) is needed on H (input of the transposed mat-vecs) and on the 4|H| domain
-    // (outer sumcheck).  On the 4|H| domain X^|H| takes the four values i4^(i mod 4), i4 a primitive fourth root of unity, so both
-    // come from ONE batch inversion of alpha - w4^i over 4|H| points — instead of an inversion over H, an inverse transform of
-    // size |H| and a forward one of size 4|H| (r03).  H is every fourth point of that domain.  (alpha on the 4|H| domain —
-    // probability 2^-231 — would make a denominator vanish: the transforms are kept for that case.)
-    DVec r_alpha_evals(ctx, H), e_ra;
-    bool ra_closed_form;
+// r(alpha, X) = v_H(alpha) / (alpha - X) on H
+void r_alpha_on_h(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    const Fr alpha = s.st.alpha;
+    PowTable wh = root_pow_table(ctx, pk.logH);
+    Fr* rh = s.r_alpha_evals.p;
+    ew(ctx, "r_alpha_den", s.H, [=] __device__(size_t i) { rh[i] = fp_sub(alpha, wh.at(i)); });
+    rc_check(ctx, batch_inverse_run(ctx, rh, s.H));
+    Fr vh = s.dh.vanishing(alpha);
+    ew(ctx, "r_alpha_scale", s.H, [=] __device__(size_t i) { rh[i] = fp_mul(rh[i], vh); });
+}
+// ---- round 2: r(alpha, X) = (alpha^|H| - X^|H|) / (alpha - X) is needed on H (input of the transposed mat-vecs) and on the
+// 4|H| domain (outer sumcheck).  On the 4|H| domain X^|H| takes four values (r_alpha_numerators), so both come from ONE batch
+// inversion of alpha - w4^i over 4|H| points — instead of an inversion over H, an inverse transform of size |H| and a forward
+// one of size 4|H| (r03).  H is every fourth point of that domain.  (alpha on the 4|H| domain — probability 2^-231 — would
+// make a denominator vanish: the transforms are kept for that case, round2_q1.)
+void r_alpha(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    const Fr alpha = s.st.alpha;
+    const uint64_t M = s.M;
+    s.r_alpha_evals = DVec(ctx, s.H);
     {
         Fr a4h = alpha;
-        for (unsigned i = 0; i < logM; i++) a4h = fp_sqr(a4h);
-        ra_closed_form = !fp_is_one(a4h) && !env_flag("SWM_RALPHA_TRANSFORMS");  // (test hook: the path of the 2^-231 case)
+        for (unsigned i = 0; i < s.logM; i++) a4h = fp_sqr(a4h);
+        s.ra_closed_form = !fp_is_one(a4h) && !env_flag("SWM_RALPHA_TRANSFORMS");  // (test hook: the path of the 2^-231 case)
     }
-    if (ra_closed_form && shard_r2) {
+    if (!s.ra_closed_form) return r_alpha_on_h(ctx, pk, s);
+    if (s.sp.r2) {
         // the rank's BLOCKS indices of the 4|H| domain for the product form; r(alpha, .) on H (every rank needs all of it for the
         // transposed mat-vecs) by its own inversion over |H| points
-        e_ra = DVec(ctx, Mloc);
-        PowTable wt = root_pow_table(ctx, logM);
-        Fr* out = e_ra.p;
-        const size_t mloc = Mloc, mblk = Mblk;
-        ew(ctx, "r_alpha_den", Mloc, [=] __device__(size_t p) {
+        const size_t mloc = s.sp.Mloc, mblk = s.sp.Mblk, s_rank = s.sp.rank;
+        s.e_ra = DVec(ctx, mloc);
+        PowTable wt = root_pow_table(ctx, s.logM);
+        Fr* out = s.e_ra.p;
+        ew(ctx, "r_alpha_den", mloc, [=] __device__(size_t p) {
             const size_t i = mloc * (p / mblk) + s_rank * mblk + (p % mblk);
             out[p] = fp_sub(alpha, wt.at(i));
         });
-        rc_check(ctx, batch_inverse_run(ctx, out, Mloc));
-        Fr aH = alpha;
-        for (unsigned i = 0; i < pk.logH; i++) aH = fp_sqr(aH);
-        HDomain d4(M);
-        Fr i4 = d4.gen;
-        for (unsigned i = 0; i < pk.logH; i++) i4 = fp_sqr(i4);
-        Fr n0 = fp_sub(aH, fp_one<Fr>()), n1 = fp_sub(aH, i4), n2 = fp_sub(aH, fp_sqr(i4)), n3 = fp_sub(aH, fp_mul(fp_sqr(i4), i4));
-        ew(ctx, "r_alpha_scale", Mloc, [=] __device__(size_t p) {
+        rc_check(ctx, batch_inverse_run(ctx, out, mloc));
+        const RAlphaNumerators nu = r_alpha_numerators(alpha, pk.logH, M);
+        ew(ctx, "r_alpha_scale", mloc, [=] __device__(size_t p) {
             const size_t i = mloc * (p / mblk) + s_rank * mblk + (p % mblk);
             const unsigned q = (unsigned)(i & 3);
-            out[p] = fp_mul(out[p], q == 0 ? n0 : q == 1 ? n1 : q == 2 ? n2 : n3);
+            out[p] = fp_mul(out[p], q == 0 ? nu.n0 : q == 1 ? nu.n1 : q == 2 ? nu.n2 : nu.n3);
         });
-        PowTable wh = root_pow_table(ctx, pk.logH);
-        Fr* rh = r_alpha_evals.p;
-        ew(ctx, "r_alpha_den", H, [=] __device__(size_t i) { rh[i] = fp_sub(alpha, wh.at(i)); });
-        rc_check(ctx, batch_inverse_run(ctx, rh, H));
-        Fr vh = dh.vanishing(alpha);
-        ew(ctx, "r_alpha_scale", H, [=] __device__(size_t i) { rh[i] = fp_mul(rh[i], vh); });
-    } else if (ra_closed_form) {
-        e_ra = DVec(ctx, M);
-        PowTable wt = root_pow_table(ctx, logM);
-        Fr* out = e_ra.p;
+        r_alpha_on_h(ctx, pk, s);
+    } else {
+        s.e_ra = DVec(ctx, M);
+        PowTable wt = root_pow_table(ctx, s.logM);
+        Fr* out = s.e_ra.p;
         ew(ctx, "r_alpha_den", M, [=] __device__(size_t i) { out[i] = fp_sub(alpha, wt.at(i)); });
         rc_check(ctx, batch_inverse_run(ctx, out, M));
-        Fr aH = alpha;
-        for (unsigned i = 0; i < pk.logH; i++) aH = fp_sqr(aH);
-        HDomain d4(M);
-        Fr i4 = d4.gen;  // w4^|H|
-        for (unsigned i = 0; i < pk.logH; i++) i4 = fp_sqr(i4);
-        Fr n0 = fp_sub(aH, fp_one<Fr>()), n1 = fp_sub(aH, i4), n2 = fp_sub(aH, fp_sqr(i4)), n3 = fp_sub(aH, fp_mul(fp_sqr(i4), i4));
-        Fr* rh = r_alpha_evals.p;
+        const RAlphaNumerators nu = r_alpha_numerators(alpha, pk.logH, M);
+        Fr* rh = s.r_alpha_evals.p;
         ew(ctx, "r_alpha_scale", M, [=] __device__(size_t i) {
             const unsigned q = (unsigned)(i & 3);
-            Fr v = fp_mul(out[i], q == 0 ? n0 : q == 1 ? n1 : q == 2 ? n2 : n3);
+            Fr v = fp_mul(out[i], q == 0 ? nu.n0 : q == 1 ? nu.n1 : q == 2 ? nu.n2 : nu.n3);
             out[i] = v;
             if (q == 0) rh[i >> 2] = v;
         });
-    } else {
-        PowTable wt = root_pow_table(ctx, pk.logH);
-        Fr* out = r_alpha_evals.p;
-        ew(ctx, "r_alpha_den", H, [=] __device__(size_t i) { out[i] = fp_sub(alpha, wt.at(i)); });
-        rc_check(ctx, batch_inverse_run(ctx, out, H));
-        Fr vh = dh.vanishing(alpha);
-        ew(ctx, "r_alpha_scale", H, [=] __device__(size_t i) { out[i] = fp_mul(out[i], vh); });
     }
-    // t evaluations on H: t[reindex(c)] = sum_M eta_M (M^T r_alpha)[c]
-    DVec t_poly = dv_zeros(ctx, H);
+}
+
+// ---- round 2: t evaluations on H, t[reindex(c)] = sum_M eta_M (M^T r_alpha)[c], interpolated, and its commitment
+void round2_t(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    const uint64_t H = s.H, X = s.X;
+    const size_t nvars = s.nvars;
+    const Fr eta_a = s.st.eta_a, eta_b = s.st.eta_b, eta_c = s.st.eta_c;
+    s.t_poly = dv_zeros(ctx, H);
     {
         DVec ta(ctx, nvars), tb(ctx, nvars), tc(ctx, nvars);
-        rc_check(ctx, spmv_run(ctx, pk.at.rowptr.p, pk.at.col.p, pk.at.val.p, r_alpha_evals.p, ta.p, nvars, &pk.at.plan));
-        rc_check(ctx, spmv_run(ctx, pk.bt.rowptr.p, pk.bt.col.p, pk.bt.val.p, r_alpha_evals.p, tb.p, nvars, &pk.bt.plan));
-        rc_check(ctx, spmv_run(ctx, pk.ct.rowptr.p, pk.ct.col.p, pk.ct.val.p, r_alpha_evals.p, tc.p, nvars, &pk.ct.plan));
-        Fr* out = t_poly.p;
+        const Fr* ra = s.r_alpha_evals.p;
+        rc_check(ctx, spmv_run(ctx, pk.at.rowptr.p, pk.at.col.p, pk.at.val.p, ra, ta.p, nvars, &pk.at.plan));
+        rc_check(ctx, spmv_run(ctx, pk.bt.rowptr.p, pk.bt.col.p, pk.bt.val.p, ra, tb.p, nvars, &pk.bt.plan));
+        rc_check(ctx, spmv_run(ctx, pk.ct.rowptr.p, pk.ct.col.p, pk.ct.val.p, ra, tc.p, nvars, &pk.ct.plan));
+        Fr* out = s.t_poly.p;
         const Fr *pa = ta.p, *pb = tb.p, *pc = tc.p;
         ew(ctx, "t_evals", nvars, [=] __device__(size_t c) {
             Fr v = fp_add(fp_add(fp_mul(eta_a, pa[c]), fp_mul(eta_b, pb[c])), fp_mul(eta_c, pc[c]));
             out[reindex_by_subdomain(H, X, c)] = v;
         });
-        dv_ntt(ctx, t_poly, pk.logH, true);
+        dv_ntt(ctx, s.t_poly, pk.logH, true);
     }
-    tr.tick("r2: t polynomial enqueued");
-    CommitJob j2[3];
-    P_t.p = t_poly.p; P_t.n = H;
-    begin_commit(P_t.p, P_t.n, false, 0, false, &j2[0], 3);  // overlaps the 4|H|-domain work below
-    DVec q1(ctx, Mloc);  // the whole product domain, or the rank's share of it (shard_r2)
+    s.tr.tick("r2: t polynomial enqueued");
+    s.P_t.p = s.t_poly.p;
+    s.P_t.n = H;
+    pc_commit_begin(ctx, pk, &s.lane, s.P_t.p, s.P_t.n, false, 0, false, &s.j2[0]);  // overlaps the 4|H|-domain work below
+}
+
+// ---- round 2: q_1 = r(alpha, X) sum_M eta_M z_M - t z + mask on the 4|H| domain, and (h_1, X g_1) = q_1 / v_H
+void round2_q1(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    const uint64_t H = s.H, M = s.M;
+    const size_t Mloc = s.sp.Mloc;
+    const Fr eta_a = s.st.eta_a, eta_b = s.st.eta_b, eta_c = s.st.eta_c;
+    s.q1 = DVec(ctx, Mloc);  // the whole product domain, or the rank's share of it (shard_r2)
     {
-        if (!ra_closed_form) {
-            DVec ra_poly = dv_ntt_from(ctx, r_alpha_evals.p, H, pk.logH, true);
-            e_ra = on_mul_domain(ra_poly.p, H);
+        if (!s.ra_closed_form) {
+            DVec ra_poly = dv_ntt_from(ctx, s.r_alpha_evals.p, H, pk.logH, true);
+            s.e_ra = on_mul_domain(ctx, s, ra_poly.p, H);
         }
-        DVec e_t = on_mul_domain(t_poly.p, H);
-        Fr* out = q1.p;
-        const Fr *pra = e_ra.p, *pza = e_za.p, *pzb = e_zb.p, *pt = e_t.p, *pz = e_z.p;
+        DVec e_t = on_mul_domain(ctx, s, s.t_poly.p, H);
+        Fr* out = s.q1.p;
+        const Fr *pra = s.e_ra.p, *pza = s.e_za.p, *pzb = s.e_zb.p, *pt = e_t.p, *pz = s.e_z.p;
         ew(ctx, "round2_pointwise", Mloc, [=] __device__(size_t i) {
             Fr a = pza[i], b = pzb[i];
             Fr summed = fp_add(fp_add(fp_mul(eta_c, fp_mul(a, b)), fp_mul(eta_a, a)), fp_mul(eta_b, b));
             out[i] = fp_sub(fp_mul(pra[i], summed), fp_mul(pz[i], pt[i]));
         });
-        e_za.release();
-        e_zb.release();
-        e_z.release();
-        const Fr* mp = mask.p;
-        if (shard_r2) {
-            rc_check(ctx, ntt_sharded_run(ctx, q1.p, logM, 1, 1));  // BLOCKS evaluations -> CYCLIC coefficients: q1[j] = q_1[rank + G j]
+        s.e_za.release();
+        s.e_zb.release();
+        s.e_z.release();
+        const Fr* mp = s.mask.p;
+        const size_t mask_len = s.mask_len;
+        if (s.sp.r2) {
+            rc_check(ctx, ntt_sharded_run(ctx, s.q1.p, s.logM, 1, 1));  // BLOCKS evaluations -> CYCLIC coefficients: q1[j] = q_1[rank + G j]
+            const size_t s_rank = s.sp.rank, s_world = s.sp.SG;
             ew(ctx, "q1_add_mask", Mloc, [=] __device__(size_t j) {
                 const size_t i = s_rank + s_world * j;
                 if (i < mask_len) out[j] = fp_add(out[j], mp[i]);
             });
         } else {
-            dv_ntt(ctx, q1, logM, true);
+            dv_ntt(ctx, s.q1, s.logM, true);
             ew(ctx, "q1_add_mask", mask_len, [=] __device__(size_t i) { out[i] = fp_add(out[i], mp[i]); });
         }
     }
-    // (h_1, X g_1) = divide_by_vanishing_poly(q_1, H)
-    DVec h1(ctx, 3 * H), g1x(ctx, H);
-    if (shard_r2) {
-        // local in the CYCLIC layout: coefficient j + k|H| of q_1 sits on the same rank, |H| / G places further
-        const size_t Hl = H / SG;
-        DVec loc(ctx, 4 * Hl), all(ctx, 4 * Hl * SG);  // [h_1 share: 3 Hl | (X g_1) share: Hl]
-        Fr* pl = loc.p;
-        const Fr* q = q1.p;
-        const size_t mloc = Mloc;
-        ew(ctx, "div_vh", 3 * Hl, [=] __device__(size_t j) {
-            Fr acc = q[j + Hl];
-            if (j + 2 * Hl < mloc) acc = fp_add(acc, q[j + 2 * Hl]);
-            if (j + 3 * Hl < mloc) acc = fp_add(acc, q[j + 3 * Hl]);
-            pl[j] = acc;
-            if (j < Hl) pl[3 * Hl + j] = fp_add(q[j], acc);
-        });
-        rc_check(ctx, shard_allgather_dev(ctx, loc.p, 4 * Hl * sizeof(Fr), all.p));
-        Fr* ph = h1.p;
-        Fr* pg = g1x.p;
-        const Fr* pa = all.p;
-        const unsigned lg = slog_g;
-        ew(ctx, "shard_interleave", 3 * H, [=] __device__(size_t i) {
-            const size_t r = i & (((size_t)1 << lg) - 1), j = i >> lg;
-            ph[i] = pa[r * 4 * Hl + j];
-            if (i < Hl << lg) pg[i] = pa[r * 4 * Hl + 3 * Hl + j];  // |H| of them
-        });
-    } else {
-        Fr* ph = h1.p;
-        Fr* pg = g1x.p;
-        const Fr* q = q1.p;
-        ew(ctx, "div_vh", 3 * H, [=] __device__(size_t j) {
-            Fr acc = q[j + H];
-            if (j + 2 * H < M) acc = fp_add(acc, q[j + 2 * H]);
-            if (j + 3 * H < M) acc = fp_add(acc, q[j + 3 * H]);
-            ph[j] = acc;
-            if (j < H) pg[j] = fp_add(q[j], acc);
-        });
-    }
-    tr.mark("round 2 polynomials");
-    std::vector<Commitment> comms2(3);
-    {
-        P_g1.p = g1x.p + 1; P_g1.n = H - 1; P_g1.has_bound = true; P_g1.bound = H - 2; P_g1.hiding = true;
-        P_h1.p = h1.p; P_h1.n = 2 * H + 1;  // degree <= 2|H| + 2 zk_bound - 2 (higher slots are zero)
-        begin_commit(P_h1.p, P_h1.n, false, 0, false, &j2[2], 4);  // largest first
-        begin_commit(P_g1.p, P_g1.n, true, H - 2, true, &j2[1], 5);
-        flush_commits();
-        // the sumcheck remainder check needs a download; do it while the MSMs run
-        Fr rem0 = g1x.download(0, 1)[0];
-        bool unsat = !fp_is_zero(rem0);
-        pc_commit_blind(pk, &j2[0], nullptr, &P_t.rand);
-        pc_commit_blind(pk, &j2[1], &zk, &P_g1.rand);
-        pc_commit_blind(pk, &j2[2], nullptr, &P_h1.rand);
-        commit_gather(ctx, {&j2[0].plain, &j2[1].plain, &j2[1].shifted, &j2[2].plain});
-        pc_commit_end_round(ctx, pk, {&j2[0], &j2[1], &j2[2]}, {nullptr, &zk, nullptr}, {&P_t.rand, &P_g1.rand, &P_h1.rand},
-                            comms2.data());
-        // (measurement builds only, -DSWM_MEASURE_HOOKS: a proof during which an EMULATED exchange actually ran — capi.hip — has wrong
-        // values by construction and only its time is of interest; the shipped library has no such path)
-        if (unsat && !ctx->emulated_exchange)
-            throw MarlinError(SWM_ERR_UNSATISFIED, "outer sumcheck does not hold: constraint system is not satisfied");
-    }
-    tr.mark("round 2 commitments");
-    fs_absorb_commitments(fs, comms2);
-    st.beta = fs.sample_outside(dh);
-    const Fr beta = st.beta;
+    s.h1 = DVec(ctx, 3 * H);
+    s.g1x = DVec(ctx, H);
+    if (!s.sp.r2) return div_vh(ctx, s.q1.p, H, M, s.h1.p, s.g1x.p);
+    const size_t Hl = H / s.sp.SG;
+    DVec loc(ctx, 4 * Hl), all(ctx, 4 * Hl * s.sp.SG);  // [h_1 share: 3 Hl | (X g_1) share: Hl]
+    div_vh(ctx, s.q1.p, Hl, Mloc, loc.p, loc.p + 3 * Hl);
+    rc_check(ctx, shard_allgather_dev(ctx, loc.p, 4 * Hl * sizeof(Fr), all.p));
+    Fr* ph = s.h1.p;
+    Fr* pg = s.g1x.p;
+    const Fr* pa = all.p;
+    const unsigned lg = s.sp.slog_g;
+    ew(ctx, "shard_interleave", 3 * H, [=] __device__(size_t i) {
+        const size_t r = i & (((size_t)1 << lg) - 1), j = i >> lg;
+        ph[i] = pa[r * 4 * Hl + j];
+        if (i < Hl << lg) pg[i] = pa[r * 4 * Hl + 3 * Hl + j];  // |H| of them
+    });
+}
 
-    // ================= round 3
-    Fr vh_alpha = dh.vanishing(alpha), vh_beta = dh.vanishing(beta);
-    Fr vhab = fp_mul(vh_alpha, vh_beta);
-    DVec f(ctx, K);
+// ---- round 2: the commitments to t, g_1, h_1 and the outer sumcheck's remainder check
+void round2_commitments(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    const uint64_t H = s.H;
+    s.P_g1.p = s.g1x.p + 1; s.P_g1.n = H - 1; s.P_g1.has_bound = true; s.P_g1.bound = H - 2; s.P_g1.hiding = true;
+    s.P_h1.p = s.h1.p; s.P_h1.n = 2 * H + 1;  // degree <= 2|H| + 2 zk_bound - 2 (higher slots are zero)
+    pc_commit_begin(ctx, pk, &s.lane, s.P_h1.p, s.P_h1.n, false, 0, false, &s.j2[2]);  // largest first
+    pc_commit_begin(ctx, pk, &s.lane, s.P_g1.p, s.P_g1.n, true, H - 2, true, &s.j2[1]);
+    commit_flush(ctx);
+    // the sumcheck remainder check needs a download; do it while the MSMs run
+    Fr rem0 = s.g1x.download(0, 1)[0];
+    bool unsat = !fp_is_zero(rem0);
+    pc_commit_blind(pk, &s.j2[0], nullptr, &s.P_t.rand);
+    pc_commit_blind(pk, &s.j2[1], &s.zk, &s.P_g1.rand);
+    pc_commit_blind(pk, &s.j2[2], nullptr, &s.P_h1.rand);
+    commit_gather(ctx, {&s.j2[0].plain, &s.j2[1].plain, &s.j2[1].shifted, &s.j2[2].plain});
+    pc_commit_end_round(ctx, pk, {&s.j2[0], &s.j2[1], &s.j2[2]}, {nullptr, &s.zk, nullptr},
+                        {&s.P_t.rand, &s.P_g1.rand, &s.P_h1.rand}, s.comms2.data());
+    // (measurement builds only, -DSWM_MEASURE_HOOKS: a proof during which an EMULATED exchange actually ran — capi.hip — has wrong
+    // values by construction and only its time is of interest; the shipped library has no such path)
+    if (unsat && !ctx->emulated_exchange)
+        throw MarlinError(SWM_ERR_UNSATISFIED, "outer sumcheck does not hold: constraint system is not satisfied");
+}
+
+// ---- round 3: f on K, its commitment (as g_2), and h_2 = (a - b f) / v_K via evaluations on the 4|K| domain.
+// Over G ranks the second part runs the way round 2 does: f into the 4|K| domain, the pointwise form a - b f (the key's twelve
+// arrays read at the rank's BLOCKS indices) and the transform back on a rank's share; the division by v_K is local in the
+// CYCLIC layout; h_2 is all-gathered afterwards (3|K| x 32 B).
+void round3_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    const uint64_t K = s.K, Bsz = s.Bsz;
+    const Fr alpha = s.st.alpha, beta = s.st.beta;
+    const Fr eta_a = s.st.eta_a, eta_b = s.st.eta_b, eta_c = s.st.eta_c;
+    const Fr vhab = fp_mul(s.dh.vanishing(alpha), s.dh.vanishing(beta));
+    s.f = DVec(ctx, K);
     {
         // the three denominator vectors share one buffer and ONE batch inversion: its cost is the serial Fermat chain of
         // a lane (~0.4 ms whatever the length), so three launches would pay it three times
@@ -1642,7 +1707,7 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
             ew(ctx, "round3_den_K", K, [=] __device__(size_t i) { out[i] = fp_mul(fp_sub(beta, rk[i]), fp_sub(alpha, ck[i])); });
         }
         rc_check(ctx, batch_inverse_run(ctx, inv.p, 3 * K));
-        Fr* out = f.p;
+        Fr* out = s.f.p;
         const Fr *ia = inv.p, *ib = inv.p + K, *ic = inv.p + 2 * K;
         const Fr *va = pk.ar[0].val_K.p, *vb = pk.ar[1].val_K.p, *vc = pk.ar[2].val_K.p;
         ew(ctx, "round3_f_K", K, [=] __device__(size_t i) {
@@ -1650,112 +1715,46 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
                           fp_mul(fp_mul(eta_c, vc[i]), ic[i]));
             out[i] = fp_mul(vhab, t);
         });
-        dv_ntt(ctx, f, pk.logK, true);
+        dv_ntt(ctx, s.f, pk.logK, true);
     }
-    CommitJob j3[2];
-    P_g2.p = f.p + 1; P_g2.n = K - 1; P_g2.has_bound = true; P_g2.bound = K - 2;
-    begin_commit(P_g2.p, P_g2.n, true, K - 2, false, &j3[0], 6);  // overlaps the 4|K|-domain work below
-    // h_2 = (a - b f) / v_K via evaluations on the 4K domain
-    DVec h2(ctx, 3 * K);
-    // Round 3 over G ranks, the same way as round 2 (shard_r2 above): f into the 4|K| domain, the pointwise form a - b f (the key's
-    // twelve arrays read at the rank's BLOCKS indices) and the transform back on a rank's share; the division by v_K is local in
-    // the CYCLIC layout; h_2 is all-gathered afterwards (3|K| x 32 B).
-    const bool shard_r3 = shard_r2 && pk.logB >= 2 * slog_g + 4 && K % SG == 0;
-    if (shard_r3) {
-        const size_t Bloc = Bsz / SG, Bblk = Bloc / SG, Kl = K / SG;
-        DVec e_f(ctx, Bloc);
-        {
-            Fr* o = e_f.p;
-            const Fr* src = f.p;
-            ew(ctx, "shard_take_cyclic", Bloc, [=] __device__(size_t j) {
-                const size_t i = s_rank + s_world * j;
-                o[j] = i < K ? src[i] : fp_zero<Fr>();
-            });
-            rc_check(ctx, ntt_sharded_run(ctx, e_f.p, pk.logB, 0, 0));
-        }
+    s.P_g2.p = s.f.p + 1; s.P_g2.n = K - 1; s.P_g2.has_bound = true; s.P_g2.bound = K - 2;
+    pc_commit_begin(ctx, pk, &s.lane, s.P_g2.p, s.P_g2.n, true, K - 2, false, &s.j3[0]);  // overlaps the 4|K|-domain work below
+    s.h2 = DVec(ctx, 3 * K);
+    const IndexOnB ix{pk.ar[0].row_B.p, pk.ar[0].col_B.p, pk.ar[0].row_col_B.p, pk.ar[0].val_B.p,
+                      pk.ar[1].row_B.p, pk.ar[1].col_B.p, pk.ar[1].row_col_B.p, pk.ar[1].val_B.p,
+                      pk.ar[2].row_B.p, pk.ar[2].col_B.p, pk.ar[2].row_col_B.p, pk.ar[2].val_B.p};
+    const Round3Challenges ch{alpha, beta, fp_mul(beta, alpha), eta_a, eta_b, eta_c, vhab};
+    if (s.sp.r3) {
+        const size_t Bloc = Bsz / s.sp.SG, Bblk = Bloc / s.sp.SG, Kl = K / s.sp.SG, s_rank = s.sp.rank;
+        DVec e_f = shard_evals(ctx, s.sp, s.f.p, K, pk.logB);
         DVec ab(ctx, Bloc);
         Fr* out = ab.p;
         const Fr* pf = e_f.p;
-        const Fr *ar_ = pk.ar[0].row_B.p, *ac_ = pk.ar[0].col_B.p, *arc = pk.ar[0].row_col_B.p, *av = pk.ar[0].val_B.p;
-        const Fr *br_ = pk.ar[1].row_B.p, *bc_ = pk.ar[1].col_B.p, *brc = pk.ar[1].row_col_B.p, *bv = pk.ar[1].val_B.p;
-        const Fr *cr_ = pk.ar[2].row_B.p, *cc_ = pk.ar[2].col_B.p, *crc = pk.ar[2].row_col_B.p, *cv = pk.ar[2].val_B.p;
-        Fr ab_const = fp_mul(beta, alpha);
         ew(ctx, "round3_pointwise_B", Bloc, [=] __device__(size_t p) {
             const size_t i = Bloc * (p / Bblk) + s_rank * Bblk + (p % Bblk);  // BLOCKS: the rank's indices of the 4|K| domain
-            Fr da = fp_add(fp_sub(fp_sub(ab_const, fp_mul(ar_[i], alpha)), fp_mul(beta, ac_[i])), arc[i]);
-            Fr db = fp_add(fp_sub(fp_sub(ab_const, fp_mul(br_[i], alpha)), fp_mul(beta, bc_[i])), brc[i]);
-            Fr dc = fp_add(fp_sub(fp_sub(ab_const, fp_mul(cr_[i], alpha)), fp_mul(beta, cc_[i])), crc[i]);
-            Fr dbc = fp_mul(db, dc);
-            Fr t = fp_add(fp_add(fp_mul(fp_mul(eta_a, av[i]), dbc), fp_mul(fp_mul(fp_mul(eta_b, bv[i]), da), dc)),
-                          fp_mul(fp_mul(fp_mul(eta_c, cv[i]), da), db));
-            Fr a_val = fp_mul(vhab, t);
-            Fr b_val = fp_mul(da, dbc);
-            out[p] = fp_sub(a_val, fp_mul(b_val, pf[p]));
+            out[p] = round3_a_minus_bf(ix, ch, i, pf[p]);
         });
         rc_check(ctx, ntt_sharded_run(ctx, ab.p, pk.logB, 1, 1));  // -> CYCLIC coefficients: ab[j] = (a - b f)[rank + G j]
-        DVec loc(ctx, 3 * Kl), all(ctx, 3 * Kl * SG);
-        Fr* pl = loc.p;
-        const Fr* q = ab.p;
-        ew(ctx, "div_vk", 3 * Kl, [=] __device__(size_t j) {
-            Fr acc = fp_zero<Fr>();
-            for (uint64_t i = 1; j + i * Kl < Bloc; i++) acc = fp_add(acc, q[j + i * Kl]);
-            pl[j] = acc;
-        });
-        rc_check(ctx, shard_allgather_dev(ctx, loc.p, 3 * Kl * sizeof(Fr), all.p));
-        Fr* ph = h2.p;
-        const Fr* pa = all.p;
-        const unsigned lg = slog_g;
-        ew(ctx, "shard_interleave", 3 * K, [=] __device__(size_t i) {
-            ph[i] = pa[(i & (((size_t)1 << lg) - 1)) * 3 * Kl + (i >> lg)];
-        });
+        DVec loc(ctx, 3 * Kl);
+        div_vk(ctx, ab.p, Kl, Bloc, loc.p);
+        shard_gather_cyclic(ctx, loc.p, 3 * Kl, s.sp.slog_g, s.h2.p, 3 * K);
     } else {
-        DVec e_f = dv_ntt_from(ctx, f.p, K, pk.logB, false);
+        DVec e_f = dv_ntt_from(ctx, s.f.p, K, pk.logB, false);
         DVec ab(ctx, Bsz);
         Fr* out = ab.p;
         const Fr* pf = e_f.p;
-        const Fr *ar_ = pk.ar[0].row_B.p, *ac_ = pk.ar[0].col_B.p, *arc = pk.ar[0].row_col_B.p, *av = pk.ar[0].val_B.p;
-        const Fr *br_ = pk.ar[1].row_B.p, *bc_ = pk.ar[1].col_B.p, *brc = pk.ar[1].row_col_B.p, *bv = pk.ar[1].val_B.p;
-        const Fr *cr_ = pk.ar[2].row_B.p, *cc_ = pk.ar[2].col_B.p, *crc = pk.ar[2].row_col_B.p, *cv = pk.ar[2].val_B.p;
-        Fr ab_const = fp_mul(beta, alpha);
-        ew(ctx, "round3_pointwise_B", Bsz, [=] __device__(size_t i) {
-            Fr da = fp_add(fp_sub(fp_sub(ab_const, fp_mul(ar_[i], alpha)), fp_mul(beta, ac_[i])), arc[i]);
-            Fr db = fp_add(fp_sub(fp_sub(ab_const, fp_mul(br_[i], alpha)), fp_mul(beta, bc_[i])), brc[i]);
-            Fr dc = fp_add(fp_sub(fp_sub(ab_const, fp_mul(cr_[i], alpha)), fp_mul(beta, cc_[i])), crc[i]);
-            Fr dbc = fp_mul(db, dc);
-            Fr t = fp_add(fp_add(fp_mul(fp_mul(eta_a, av[i]), dbc), fp_mul(fp_mul(fp_mul(eta_b, bv[i]), da), dc)),
-                          fp_mul(fp_mul(fp_mul(eta_c, cv[i]), da), db));
-            Fr a_val = fp_mul(vhab, t);
-            Fr b_val = fp_mul(da, dbc);
-            out[i] = fp_sub(a_val, fp_mul(b_val, pf[i]));
-        });
+        ew(ctx, "round3_pointwise_B", Bsz, [=] __device__(size_t i) { out[i] = round3_a_minus_bf(ix, ch, i, pf[i]); });
         dv_ntt(ctx, ab, pk.logB, true);
-        Fr* ph = h2.p;
-        const Fr* q = ab.p;
-        ew(ctx, "div_vk", 3 * K, [=] __device__(size_t j) {
-            Fr acc = fp_zero<Fr>();
-            for (uint64_t i = 1; j + i * K < Bsz; i++) acc = fp_add(acc, q[j + i * K]);
-            ph[j] = acc;
-        });
+        div_vk(ctx, ab.p, K, Bsz, s.h2.p);
     }
-    tr.mark("round 3 polynomials");
-    std::vector<Commitment> comms3(2);
-    P_h2.p = h2.p; P_h2.n = 3 * K >= 3 ? 3 * K - 3 : 0;  // degree <= 3|K| - 4
-    begin_commit(P_h2.p, P_h2.n, false, 0, false, &j3[1], 7);
-    flush_commits();
-    // ================= evaluations, part 1: everything asked at beta depends on rounds 1-2 only, so it is enqueued here
-    // and runs under the round-3 commitments
-    std::map<std::string, LPoly*> polys;
-    LPoly idx_polys[12];
-    for (int m = 0; m < 3; m++) {
-        const DVec* v[4] = {&pk.ar[m].row, &pk.ar[m].col, &pk.ar[m].val, &pk.ar[m].row_col};
-        for (int j = 0; j < 4; j++) {
-            idx_polys[4 * m + j].p = v[j]->p;
-            idx_polys[4 * m + j].n = K;
-            polys[kIndexerPolys[4 * m + j]] = &idx_polys[4 * m + j];
-        }
-    }
-    polys["w"] = &P_w; polys["z_a"] = &P_za; polys["z_b"] = &P_zb; polys["mask_poly"] = &P_mask;
-    polys["t"] = &P_t; polys["g_1"] = &P_g1; polys["h_1"] = &P_h1; polys["g_2"] = &P_g2; polys["h_2"] = &P_h2;
+    s.P_h2.p = s.h2.p;
+    s.P_h2.n = 3 * K >= 3 ? 3 * K - 3 : 0;  // degree <= 3|K| - 4
+}
+
+// ---- evaluations.  Everything asked at beta depends on rounds 1-2 only, so it is enqueued before the round-3 commitments
+// are awaited and runs under them; then gamma and the evaluations at gamma; then the linear combinations.  Returns the
+// proof's evaluations (label order).
+std::vector<Fr> evaluations(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
     // every evaluation the linear combinations can ask for, enqueued back to back and downloaded once
     std::map<std::pair<std::string, bool>, Fr> eval_cache;  // (label, at_gamma)
     {
@@ -1765,38 +1764,34 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
         want.push_back({"g_2", true});
         want.push_back({"h_2", true});
         DVec slots(ctx, want.size());
-        EvalPoint ep_beta = eval_point(ctx, beta);
-        std::vector<EvalItem> at_beta;
-        for (size_t i = 0; i < want.size(); i++) {
-            if (want[i].second) continue;
-            LPoly* lp = polys.at(want[i].first);
-            at_beta.push_back({lp->p, lp->n, slots.p + i});
-        }
-        poly_eval_many(ctx, at_beta, ep_beta);
-        commit_gather(ctx, {&j3[0].plain, &j3[0].shifted, &j3[1].plain});
-        pc_commit_end_round(ctx, pk, {&j3[0], &j3[1]}, {nullptr, nullptr}, {&P_g2.rand, &P_h2.rand}, comms3.data());
-        tr.mark("round 3 commitments");
-        fs_absorb_commitments(fs, comms3);
-        st.gamma = fs.rand_fr();
-        // part 2: the evaluations at gamma
-        EvalPoint ep_gamma = eval_point(ctx, st.gamma);
-        std::vector<EvalItem> at_gamma;
-        for (size_t i = 0; i < want.size(); i++) {
-            if (!want[i].second) continue;
-            LPoly* lp = polys.at(want[i].first);
-            at_gamma.push_back({lp->p, lp->n, slots.p + i});
-        }
-        poly_eval_many(ctx, at_gamma, ep_gamma);
+        auto enqueue_at = [&](bool at_gamma, const EvalPoint& ep) {
+            std::vector<EvalItem> items;
+            for (size_t i = 0; i < want.size(); i++) {
+                if (want[i].second != at_gamma) continue;
+                LPoly* lp = s.polys.at(want[i].first);
+                items.push_back({lp->p, lp->n, slots.p + i});
+            }
+            poly_eval_many(ctx, items, ep);
+        };
+        EvalPoint ep_beta = eval_point(ctx, s.st.beta);
+        enqueue_at(false, ep_beta);
+        commit_gather(ctx, {&s.j3[0].plain, &s.j3[0].shifted, &s.j3[1].plain});
+        pc_commit_end_round(ctx, pk, {&s.j3[0], &s.j3[1]}, {nullptr, nullptr}, {&s.P_g2.rand, &s.P_h2.rand}, s.comms3.data());
+        s.tr.mark("round 3 commitments");
+        fs_absorb_commitments(s.fs, s.comms3);
+        s.st.gamma = s.fs.rand_fr();
+        EvalPoint ep_gamma = eval_point(ctx, s.st.gamma);
+        enqueue_at(true, ep_gamma);
         std::vector<Fr> vals = slots.download(0, want.size());
         for (size_t i = 0; i < want.size(); i++) eval_cache[want[i]] = vals[i];
     }
-    const Fr gamma = st.gamma;
+    const Fr beta = s.st.beta, gamma = s.st.gamma;
     auto poly_at = [&](const std::string& label, const Fr& point) {
         bool at_gamma = fp_eq(point, gamma);
         auto key = std::make_pair(label, at_gamma);
         auto it = eval_cache.find(key);
         if (it != eval_cache.end()) return it->second;
-        LPoly* lp = polys.at(label);
+        LPoly* lp = s.polys.at(label);
         Fr v = poly_eval(ctx, lp->p, lp->n, point);
         eval_cache[key] = v;
         return v;
@@ -1806,11 +1801,11 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
         for (auto& t : terms) acc = fp_add(acc, t.second.empty() ? t.first : fp_mul(t.first, poly_at(t.second, point)));
         return acc;
     };
-    LcSet lcs = construct_linear_combinations(pk.info, public_input, provider, st);
+    s.lcs = construct_linear_combinations(pk.info, s.public_input, provider, s.st);
     std::vector<std::pair<std::string, Fr>> evals;
     for (auto& q : kQuerySet) {
         const Fr& pt = std::string(q.point) == "beta" ? beta : gamma;
-        Fr v = provider(q.label, lcs.at(q.label), pt);
+        Fr v = provider(q.label, s.lcs.at(q.label), pt);
         if (lc_has_zero_eval(q.label)) {
             if (!fp_is_zero(v) && !ctx->emulated_exchange)  // (see the outer sumcheck's check)
                 throw MarlinError(SWM_ERR_UNSATISFIED, std::string(q.label) + " does not evaluate to zero: constraint system is not satisfied");
@@ -1819,15 +1814,15 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
         evals.push_back({q.label, v});
     }
     std::sort(evals.begin(), evals.end(), [](auto& a, auto& b) { return a.first < b.first; });
-    tr.mark("evaluations");
-    Proof proof;
-    for (auto& e : evals) proof.evaluations.push_back(e.second);
-    fs_absorb_evals(fs, proof.evaluations);
-    Fr xi = fs.challenge_u128();
+    std::vector<Fr> out;
+    for (auto& e : evals) out.push_back(e.second);
+    return out;
+}
 
-    // ================= MarlinKZG10::open_combinations: per query point, labels in sorted order, challenges xi^0, xi^1, ...
-    // Phase 1 builds the combined polynomial, its witness and the shifted witnesses for BOTH points and enqueues all
-    // their MSMs; phase 2 waits and adds the host-side hiding terms.  Nothing is awaited before everything is enqueued.
+// ---- MarlinKZG10::open_combinations: per query point, labels in sorted order, challenges xi^0, xi^1, ...
+// Phase 1 builds the combined polynomial, its witness and the shifted witnesses for BOTH points and enqueues all
+// their MSMs; phase 2 waits and adds the host-side hiding terms.  Nothing is awaited before everything is enqueued.
+std::vector<PcProof> open_combinations(swm_ctx* ctx, const swm_pk& pk, ProveState& s, const Fr& xi) {
     struct ShiftedTerm {
         LPoly* lp;
         Fr ch;
@@ -1853,7 +1848,7 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
     for (int pi = 0; pi < 2; pi++) {
         const char* pl = points[pi];
         PointOpen& o = po[pi];
-        o.point = pi == 0 ? beta : gamma;
+        o.point = pi == 0 ? s.st.beta : s.st.gamma;
         const Fr point = o.point;
         std::vector<std::string> labels;
         for (auto& q : kQuerySet)
@@ -1861,18 +1856,18 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
         std::sort(labels.begin(), labels.end());
         size_t plen = 0;
         for (auto& l : labels)
-            for (auto& t : lcs.at(l))
-                if (!t.second.empty()) plen = std::max(plen, polys.at(t.second)->n);
+            for (auto& t : s.lcs.at(l))
+                if (!t.second.empty()) plen = std::max(plen, s.polys.at(t.second)->n);
         o.comb = DVec(ctx, plen ? plen : 1);
         CombineTerms cterms;
         int nterms = 0;
         Fr ch = fr_one();
         for (auto& l : labels) {
-            const LcTerms& terms = lcs.at(l);
+            const LcTerms& terms = s.lcs.at(l);
             bool single_bounded = false;
             for (auto& t : terms) {
                 if (t.second.empty()) continue;
-                LPoly* lp = polys.at(t.second);
+                LPoly* lp = s.polys.at(t.second);
                 if (terms.size() == 1 && lp->has_bound) single_bounded = true;
                 else if (lp->has_bound) throw MarlinError(SWM_ERR_INTERNAL, "EquationHasDegreeBounds");
                 Fr k = fp_mul(ch, t.first);
@@ -1885,7 +1880,7 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
             }
             ch = fp_mul(ch, xi);
             if (single_bounded) {
-                LPoly* lp = polys.at(terms[0].second);
+                LPoly* lp = s.polys.at(terms[0].second);
                 o.shifted_terms.push_back({lp, ch});
                 hp_add_scaled(o.shifted_r, lp->rand.shifted_rand, ch);
                 if (!hp_is_zero(lp->rand.shifted_rand)) hp_add_scaled(o.shifted_r_witness, hp_div_linear(lp->rand.shifted_rand, point), ch);
@@ -1903,11 +1898,11 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
             });
         }
         // witness = p / (X - point) against the powers; degree-bounded members: shifted witnesses against the shifted powers
-        tr.tick(pi == 0 ? "open beta: combination enqueued" : "open gamma: combination enqueued");
+        s.tr.tick(pi == 0 ? "open beta: combination enqueued" : "open gamma: combination enqueued");
         o.wq = div_linear(ctx, o.comb.p, plen, point);
-        tr.tick("  witness quotient enqueued");
-        commit_enqueue(ctx, &lane, pk, 0, o.wq.work.p + 1, plen ? plen - 1 : 0, &o.wjob);
-        tr.tick("  witness commitment enqueued");
+        s.tr.tick("  witness quotient enqueued");
+        commit_enqueue(ctx, &s.lane, pk, 0, o.wq.work.p + 1, plen ? plen - 1 : 0, &o.wjob);
+        s.tr.tick("  witness commitment enqueued");
         o.sq.resize(o.shifted_terms.size());
         o.sjobs.resize(o.shifted_terms.size());
         for (size_t i = 0; i < o.shifted_terms.size(); i++) {
@@ -1917,16 +1912,16 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
             Fr* q = o.sq[i].work.p;
             size_t qn = stt.lp->n ? stt.lp->n - 1 : 0;
             ew(ctx, "open_scale", qn, [=] __device__(size_t t) { q[t + 1] = fp_mul(q[t + 1], k); });
-            tr.tick("  shifted quotient enqueued");
-            commit_enqueue(ctx, &lane, pk, pk.srs_max_degree - stt.lp->bound, q + 1, qn, &o.sjobs[i]);
-            tr.tick("  shifted commitment enqueued");
+            s.tr.tick("  shifted quotient enqueued");
+            commit_enqueue(ctx, &s.lane, pk, pk.srs_max_degree - stt.lp->bound, q + 1, qn, &o.sjobs[i]);
+            s.tr.tick("  shifted commitment enqueued");
         }
     }
     commit_flush(ctx);  // both opening points: up to four bucket stages, one launch
-    tr.tick("open: bucket stages enqueued");
+    s.tr.tick("open: bucket stages enqueued");
     // hiding terms of the two witnesses and the random evaluations: host work that does not depend on the MSMs in flight
     G1XYZZ hide[2];
-    PcProof pps[2];
+    std::vector<PcProof> pps(2);
     for (int pi = 0; pi < 2; pi++) {
         PointOpen& o = po[pi];
         hide[pi] = g1_xyzz_identity();
@@ -1952,12 +1947,86 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
         g1_add(wit[pi], hide[pi]);
     }
     g1_to_affine_batch(wit, 2, wit_aff);
-    for (int pi = 0; pi < 2; pi++) {
-        pps[pi].w = wit_aff[pi];
-        proof.pc_proof.push_back(pps[pi]);
+    for (int pi = 0; pi < 2; pi++) pps[pi].w = wit_aff[pi];
+    return pps;
+}
+
+std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* cs, ChaChaRng& zk, bool uncompressed = false) {
+    PhaseTrace tr(ctx);
+    static const bool proof_marks = env_flag("SWM_TRACE") || env_flag("SWM_PROOF_MARKS");
+    if (proof_marks) hipLaunchKernelGGL(swm_proof_begin, dim3(1), dim3(1), 0, ctx->stream);
+    ProveShape shape = prove_shape(cs, pk);
+    tr.mark("pad_and_square");
+    shard_agree(ctx, pk);  // one proof over several ranks: all of them split the work the same way, or none starts
+    ctx->emulated_exchange = false;
+    ProveState s(pk, zk, tr, std::move(shape), shard_plan(ctx, pk));
+    // every commitment of a small proof on ONE stream of its lane (msm_enqueue: a proof that mixes single-stream and pipelined
+    // jobs runs them on aliasing streams); SWM_PROVE_ONE_STREAM_LOG: the largest log2 |H| this applies to
+    // (default 19, 0 = never; measured r05, alternating runs: 2^16 7.0 -> 6.5 ms, 2^17 11.2 -> 10.8, 2^18 17.7 -> 17.5, 2^19 29.4 -> 28.6,
+    // Merkle circuit 15.0 -> 14.7; at 2^20 the pipelined form is 1 ms ahead: 49.6 vs 50.6)
+    struct PipeMinScope {
+        swm_ctx* c;
+        ~PipeMinScope() { c->msm_pipe_min = 0; }
+    } pipe_scope{ctx};
+    static const unsigned one_stream_log = (unsigned)env_switch("SWM_PROVE_ONE_STREAM_LOG", 19, 0, 47);
+    ctx->msm_pipe_min = pk.logH <= one_stream_log ? ~(size_t)0 : 0;
+
+    // ================= round 1
+    // The zero-knowledge draws of round 1 do not depend on the witness: rho_w, rho_a, rho_b, then the mask polynomial
+    // (arkworks' order).  The mask is sampled and its commitment — the largest MSM of the round, 3|H| points — enqueued
+    // BEFORE the witness upload: a pageable host buffer of 32 MB per 2^20 variables takes ~5 ms to reach HBM, during
+    // which the GPU had nothing to do (r02 timeline).
+    // Every commitment MSM is enqueued as soon as its polynomial exists (enqueueing a round's commitments together once ALL its
+    // polynomials are built — so that the transforms do not run beside an accumulation — measured no gain in r02 / r04: the early
+    // MSMs cover more than the slowed transforms cost; CHANGELOG.md).
+    s.rho_w = zk.rand_fr();
+    s.rho_a = zk.rand_fr();
+    s.rho_b = zk.rand_fr();
+    begin_mask(ctx, pk, s);
+    upload_witness(ctx, pk, s, cs);
+    tr.mark("upload z, z_A, z_B");
+    round1_polys(ctx, pk, s);
+    tr.mark("round 1 polynomials");
+    if (!s.mask_late) commit_flush(ctx);  // round 1: all four commitments enqueued here; small ones share one bucket-stage launch
+    round2_prework(ctx, s);
+    if (s.mask_late) {  // everything else of the round is in flight: now the host draws the mask from the caller's generator
+        draw_mask(ctx, pk, s);
+        commit_flush(ctx);
     }
+    tr.tick("r1: pre-work enqueued");
+    round1_commitments(ctx, pk, s);
+    tr.mark("round 1 commitments");
+    fs_absorb_commitments(s.fs, s.comms1);
+    s.st.alpha = s.fs.sample_outside(s.dh);
+    s.st.eta_a = s.fs.rand_fr();
+    s.st.eta_b = s.fs.rand_fr();
+    s.st.eta_c = s.fs.rand_fr();
+
+    // ================= round 2
+    r_alpha(ctx, pk, s);
+    round2_t(ctx, pk, s);
+    round2_q1(ctx, pk, s);
+    tr.mark("round 2 polynomials");
+    round2_commitments(ctx, pk, s);
+    tr.mark("round 2 commitments");
+    fs_absorb_commitments(s.fs, s.comms2);
+    s.st.beta = s.fs.sample_outside(s.dh);
+
+    // ================= round 3
+    round3_polys(ctx, pk, s);
+    tr.mark("round 3 polynomials");
+    pc_commit_begin(ctx, pk, &s.lane, s.P_h2.p, s.P_h2.n, false, 0, false, &s.j3[1]);
+    commit_flush(ctx);
+
+    // ================= evaluations and openings
+    Proof proof;
+    proof.evaluations = evaluations(ctx, pk, s);
+    tr.mark("evaluations");
+    fs_absorb_evals(s.fs, proof.evaluations);
+    const Fr xi = s.fs.challenge_u128();
+    proof.pc_proof = open_combinations(ctx, pk, s, xi);
     tr.mark("openings");
-    proof.commitments = {comms1, comms2, comms3};
+    proof.commitments = {s.comms1, s.comms2, s.comms3};
     return serialize_proof(proof, uncompressed);
 }
 
