@@ -360,6 +360,30 @@ int swm_selftest_pairing(unsigned *failed);
  * a != 0, computed on the CPU by the same function the GPU lanes run; *fallbacks counts inputs whose 17 rounds did not end
  * in (0, 1) (the kernels then use the exact loop; expected 0). */
 int swm_selftest_fr_inv(const uint64_t *a_mont, uint64_t *out_mont, size_t n, unsigned *fallbacks);
+/* Device self-test of the transform's 29-bit lazy-limb arithmetic (csrc/fr29.cuh) and of the single-element inversions
+ * (csrc/frinv.cuh), one GPU lane per element on raw limbs: a9, b9, out9 hold n x 9 uint32 limbs (value = sum l[i] 2^(29 i)),
+ * 8-word operands (memory format) in limbs 0..7 with limb 8 zero, and 8-word results likewise.  Ops:
+ *   0 fr29_mul_fenced(a, b) (the asm multiplier)   1 fr29_mul(a, b) (its C form)   2 fr29_normalize(a)
+ *   3 fr29_cond_sub(a, 2r)   4 fr29_cond_sub(a, r)   5 fr29_canonical(a, below_2r = 1)   6 fr29_canonical(a, 0)
+ *   7 fr29_sub(a, b, spread9)   8 fr29_unpack(a words)   9 fr29_pack(a) (words)
+ *   10 fr_inv_single(a words)   11 fr_inv_single_exact(a words) (the fallback loop, run directly)
+ * spread9 is read by op 7 only. */
+int swm_selftest_fr29(swm_ctx *ctx, int op, const uint32_t *a9, const uint32_t *b9, const uint32_t *spread9, uint32_t *out9,
+                      size_t n);
+/* Device self-test of the polynomial drivers of the prover (csrc/devops.cuh) on host data in the memory (Montgomery) form,
+ * n x 4 uint64 per vector, z one element.  Ops:
+ *   0 suffix_recurrence(data, n, m, z) in place: data[k] <- data[k] + z data[k + m], k descending (division by X^m - z)
+ *   1 div_linear(data, n, z): out[0] = p(z), out[1..n) = the quotient of p by (X - z)
+ *   2 poly_eval(data, n, z): out[0] = p(z)
+ *   3 poly_eval_many at z over npieces pieces (pieces[2 i] = offset, pieces[2 i + 1] = length) of data: out[i]
+ *   4..7 ntt_run_from: the transform of data[0..n) zero-extended to 2^m elements into out; op - 4 = inverse + 2 coset;
+ *        data receives the source as the device holds it afterwards
+ *   8 scan_exclusive_u32 of data as n uint32 words: out[0..n) as uint32, the total (mod 2^32) at out[n] */
+int swm_selftest_poly(swm_ctx *ctx, int op, void *data, size_t n, size_t m, const uint64_t z[4], const uint64_t *pieces,
+                      size_t npieces, void *out);
+/* The bulk Fr sampler of the prover (sample_fr_bulk) on a generator handle: `need` elements drawn into a device buffer and
+ * downloaded to out_mont (n x 4 uint64, Montgomery form), advancing rng as `need` successive swm_rng_rand_fr calls would. */
+int swm_selftest_sample_fr(swm_ctx *ctx, swm_rng *rng, size_t need, uint64_t *out_mont);
 
 #ifdef __cplusplus
 }

@@ -101,6 +101,9 @@ ABI = {
     "swm_selftest_mul_throughput": (_int, [_vp, _int, _sz, _int, ctypes.POINTER(ctypes.c_float)]),
     "swm_selftest_pairing": (_int, [ctypes.POINTER(ctypes.c_uint)]),
     "swm_selftest_fr_inv": (_int, [_u64p, _u64p, _sz, ctypes.POINTER(ctypes.c_uint)]),
+    "swm_selftest_fr29": (_int, [_vp, _int, _u32p, _u32p, _u32p, _u32p, _sz]),
+    "swm_selftest_poly": (_int, [_vp, _int, ctypes.c_void_p, _sz, _sz, _u64p, _u64p, _sz, ctypes.c_void_p]),
+    "swm_selftest_sample_fr": (_int, [_vp, _vp, _sz, _u64p]),
 }
 
 
@@ -439,6 +442,73 @@ class Context:
         out = np.zeros((a.shape[0], 18), dtype=np.uint64)
         self._check(self.lib.swm_selftest_g1_add(self.h, _p64(a), _p64(b), _p64(out), a.shape[0]), "swm_selftest_g1_add")
         return out
+
+    FR29_OPS = {"mul": 0, "mul_c": 1, "normalize": 2, "cond_sub_2r": 3, "cond_sub_r": 4, "canonical_below_2r": 5,
+                "canonical": 6, "sub": 7, "unpack": 8, "pack": 9, "inv": 10, "inv_exact": 11}
+
+    def selftest_fr29(self, op, a9, b9=None, spread9=None):
+        """swm_selftest_fr29: one op of csrc/fr29.cuh / frinv.cuh per row of a9 (n x 9 uint32 limbs) -> n x 9 limbs."""
+        a = np.ascontiguousarray(a9, dtype=np.uint32).reshape(-1, 9)
+        b = np.ascontiguousarray(b9 if b9 is not None else a, dtype=np.uint32).reshape(-1, 9)
+        assert b.shape == a.shape
+        sp = np.ascontiguousarray(spread9 if spread9 is not None else np.zeros(9), dtype=np.uint32).reshape(9)
+        out = np.zeros_like(a)
+        self._check(self.lib.swm_selftest_fr29(self.h, self.FR29_OPS[op], _p32(a), _p32(b), _p32(sp), _p32(out), a.shape[0]),
+                    "swm_selftest_fr29")
+        return out
+
+    def _poly(self, op, data, n, m, z, pieces, out):
+        zz = np.ascontiguousarray(z if z is not None else np.zeros(4), dtype=np.uint64).reshape(4)
+        pc = np.ascontiguousarray(pieces if pieces is not None else np.zeros(2), dtype=np.uint64).reshape(-1)
+        self._check(self.lib.swm_selftest_poly(self.h, op, data.ctypes.data, n, m, _p64(zz), _p64(pc), pc.size // 2,
+                                               out.ctypes.data if out is not None else None), "swm_selftest_poly")
+
+    def selftest_suffix_recurrence(self, a_mont, m, z_mont):
+        """a[k] <- a[k] + z a[k + m], k descending (devops.cuh suffix_recurrence), on a copy of a (n x 4, Montgomery)."""
+        a = np.ascontiguousarray(a_mont, dtype=np.uint64).reshape(-1, 4).copy()
+        self._poly(0, a, a.shape[0], m, z_mont, None, None)
+        return a
+
+    def selftest_div_linear(self, p_mont, z_mont):
+        """(p(z), quotient of p by X - z) as one n x 4 array: row 0, rows 1..n."""
+        p = np.ascontiguousarray(p_mont, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros_like(p)
+        self._poly(1, p, p.shape[0], 0, z_mont, None, out)
+        return out
+
+    def selftest_poly_eval(self, p_mont, z_mont):
+        p = np.ascontiguousarray(p_mont, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros(4, dtype=np.uint64)
+        self._poly(2, p, p.shape[0], 0, z_mont, None, out)
+        return out
+
+    def selftest_poly_eval_many(self, buf_mont, pieces, z_mont):
+        """pieces: (offset, length) pairs into buf -> one value per piece (poly_eval_many)."""
+        buf = np.ascontiguousarray(buf_mont, dtype=np.uint64).reshape(-1, 4)
+        pc = np.asarray(pieces, dtype=np.uint64).reshape(-1, 2)
+        out = np.zeros((pc.shape[0], 4), dtype=np.uint64)
+        self._poly(3, buf, buf.shape[0], 0, z_mont, pc, out)
+        return out
+
+    def selftest_ntt_from(self, src_mont, log_n, inverse=False, coset=False):
+        """(transform of src zero-extended to 2^log_n elements, the source as the device left it)."""
+        src = np.ascontiguousarray(src_mont, dtype=np.uint64).reshape(-1, 4).copy()
+        out = np.zeros((1 << log_n, 4), dtype=np.uint64)
+        self._poly(4 + int(bool(inverse)) + 2 * int(bool(coset)), src, src.shape[0], log_n, None, None, out)
+        return out, src
+
+    def selftest_scan(self, words):
+        """(exclusive prefix sums of uint32 words, total), both mod 2^32 (scan_exclusive_u32)."""
+        w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        out = np.zeros(w.size + 1, dtype=np.uint32)
+        self._poly(8, w, w.size, 0, None, None, out)
+        return out[:-1], int(out[-1])
+
+    def selftest_sample_fr(self, rng, need):
+        """sample_fr_bulk on a generator handle (simpleworks_amd.marlin.Rng): need x 4 uint64, Montgomery form."""
+        out = np.zeros((max(need, 1), 4), dtype=np.uint64)
+        self._check(self.lib.swm_selftest_sample_fr(self.h, rng.h, need, _p64(out)), "swm_selftest_sample_fr")
+        return out[:need]
 
     def selftest_mul_throughput(self, which, threads, iters):
         ms = ctypes.c_float(0)

@@ -27,6 +27,7 @@ int batch_inverse_run(swm_ctx* ctx, void* d, size_t n);
 int selftest_mul_run(swm_ctx* ctx, int which, const void* a, const void* b, void* out, size_t n);
 int selftest_chain_run(swm_ctx* ctx, int which, void* out, size_t threads, int iters);
 int selftest_g1_add_run(swm_ctx* ctx, const void* a, const void* b, void* out, size_t n);
+int selftest_fr29_run(swm_ctx* ctx, int op, const void* a, const void* b, const uint32_t* sp9, void* out, size_t n);
 
 // detail of the last failure of a context-free entry point (verify / codecs), per calling thread
 static thread_local char tls_err[512] = {0};
@@ -901,6 +902,23 @@ int swm_selftest_mul(swm_ctx* ctx, int which, const uint64_t* a, const uint64_t*
     SWM_HIP(ctx, hipMemcpyAsync(db, b, n * es, hipMemcpyHostToDevice, ctx->stream));
     SWM_TRY(selftest_mul_run(ctx, which, da, db, da, n));
     SWM_HIP(ctx, hipMemcpyAsync(out, da, n * es, hipMemcpyDeviceToHost, ctx->stream));
+    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SWM_OK;
+}
+int swm_selftest_fr29(swm_ctx* ctx, int op, const uint32_t* a9, const uint32_t* b9, const uint32_t* spread9, uint32_t* out9,
+                      size_t n) {
+    const bool two = op == 0 || op == 1 || op == 7;
+    if (!ctx || op < 0 || op > 11 || (n && (!a9 || !out9 || (two && !b9))) || (op == 7 && !spread9)) return SWM_ERR_INVALID_ARG;
+    SWM_ON_DEVICE(ctx);
+    if (n == 0) return SWM_OK;
+    const size_t bytes = n * 36;
+    char *da = nullptr, *db = nullptr;
+    SWM_TRY(scratch(ctx, "stage.a", bytes + 64, (void**)&da));
+    SWM_TRY(scratch(ctx, "stage.b", bytes + 64, (void**)&db));
+    SWM_HIP(ctx, hipMemcpyAsync(da, a9, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (two) SWM_HIP(ctx, hipMemcpyAsync(db, b9, bytes, hipMemcpyHostToDevice, ctx->stream));
+    SWM_TRY(selftest_fr29_run(ctx, op, da, db, op == 7 ? spread9 : nullptr, da, n));
+    SWM_HIP(ctx, hipMemcpyAsync(out9, da, bytes, hipMemcpyDeviceToHost, ctx->stream));
     SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SWM_OK;
 }

@@ -654,6 +654,7 @@ static __global__ void __launch_bounds__(SC_BLOCK) scan_final(const uint32_t* in
 }
 // out[i] = sum_{j < i} in[j]; *total (device word at tot[ntiles]) is returned through `total_out` on the host
 inline uint32_t scan_exclusive_u32(swm_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n) {
+    if (n == 0) return 0;  // (a grid of zero workgroups is an invalid launch)
     unsigned ntiles = (unsigned)((n + SC_TILE - 1) / SC_TILE);
     DBuf<uint32_t> tot(ctx, ntiles + 1);
     hipLaunchKernelGGL(scan_totals, dim3(ntiles), dim3(SC_BLOCK), 0, ctx->stream, in, n, tot.p);

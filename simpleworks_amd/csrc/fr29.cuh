@@ -12,8 +12,10 @@
 // keep whatever factor they came with (2^256, the memory format of the rest of the library) and need no conversion at all:
 // unpacking 8 x 32 -> 9 x 29 bits is all that happens on a load.
 // Bounds (asserted limb by limb and column by column by tools/check_ntt29.py, which emulates this file):
-//   normalised: limbs 0..7 < 2^29, limb 8 takes what is left;  lazy: limbs < 2^32;
-//   fr29_mul(a, b): a lazy, b normalised, a b < 2^261 r  =>  result normalised, < 2r;
+//   normalised: limbs 0..7 < 2^29, limb 8 takes what is left;  lazy: limbs < 2^32 (fr29_normalize: <= 2^32 - 8);
+//   fr29_mul(a, b): a lazy with limbs < 3 x 2^30, b normalised, a b < 2^261 r  =>  result normalised, < 2r (the limb bound keeps
+//     every 64-bit column sum below 2^64: 9 x 3 x 2^59 + 8 x 2^58 + the carry; limbs of a up to 2^32 - 1 overflow column 7 when b
+//     is large, e.g. all nine at 2^32 - 1 times b = 2^249 - 1, although a b < 2^261 r; the transform's operands stay below 2.5 x 2^30);
 //   a - b is a + SPREAD - b, SPREAD = limbs of k r with 2^29 (or 2 x 2^29) borrowed into every limb, k >= the bound of b.
 #pragma once
 #include "ff.cuh"
@@ -61,7 +63,7 @@ __device__ __forceinline__ Fr29 fr29_const(const uint32_t (&c)[9]) {
     for (int i = 0; i < 9; i++) r.l[i] = c[i];
     return r;
 }
-// carry propagation: limbs < 2^32 in, limbs 0..7 < 2^29 out (limb 8 takes what is left)
+// carry propagation: limbs <= 2^32 - 8 in (the carry out of a limb is at most 7), limbs 0..7 < 2^29 out (limb 8 takes what is left)
 __device__ __forceinline__ Fr29 fr29_normalize(const Fr29& a) {
     Fr29 r;
     uint32_t c = 0;
@@ -90,7 +92,8 @@ __device__ __forceinline__ Fr29 fr29_sub(const Fr29& a, const Fr29& b, const Spr
     for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + sp.l[i] - b.l[i];
     return r;
 }
-// a b 2^-261 mod r (result normalised, < 2r).  a may be lazy, b normalised (a table entry or a product), a b < 2^261 r.
+// a b 2^-261 mod r (result normalised, < 2r).  a may be lazy (limbs < 3 x 2^30), b normalised (a table entry or a product),
+// a b < 2^261 r.
 __device__ __forceinline__ Fr29 fr29_mul(const Fr29& a, const Fr29& b) {
     Fr29 r;
     uint32_t m[9];

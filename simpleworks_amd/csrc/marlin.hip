@@ -2526,6 +2526,75 @@ int swm_r1cs_is_satisfied(swm_ctx* ctx, const swm_r1cs* cs, int* ok, size_t* fir
     SWM_GUARD(ctx, is_satisfied_impl(ctx, cs, ok, first_bad));
 }
 
+// ------------------------------------------------------------------------------------------------ K4 self-tests
+// The prover's own host drivers of devops.cuh on host data (include/swmarlin.h: swm_selftest_poly names the ops).
+static void selftest_poly_impl(swm_ctx* ctx, int op, void* data, size_t n, size_t m, const uint64_t* z, const uint64_t* pieces,
+                               size_t npieces, void* out) {
+    Fr zz = fp_zero<Fr>();
+    if (z) memcpy(zz.v, z, 32);
+    if (op == 8) {  // exclusive scan of n u32 words: out[0..n) and the total at out[n]
+        DBuf<uint32_t> in(ctx, n), res(ctx, n);
+        if (n) in.upload((const uint32_t*)data, n);
+        const uint32_t total = scan_exclusive_u32(ctx, in.p, res.p, n);
+        std::vector<uint32_t> h = res.download(0, n);
+        if (n) memcpy(out, h.data(), n * 4);
+        ((uint32_t*)out)[n] = total;
+        return;
+    }
+    DVec a(ctx, n);
+    if (n) a.upload((const Fr*)data, n);
+    if (op == 0) {  // suffix_recurrence(a, n, m, z) in place
+        suffix_recurrence(ctx, a.p, n, m, zz);
+        std::vector<Fr> h = a.download(0, n);
+        if (n) memcpy(data, h.data(), n * sizeof(Fr));
+    } else if (op == 1) {  // div_linear: out[0] = p(z), out[1..n) = the quotient by (X - z)
+        DivResult r = div_linear(ctx, a.p, n, zz);
+        std::vector<Fr> h = r.work.download(0, n);
+        if (n) memcpy(out, h.data(), n * sizeof(Fr));
+    } else if (op == 2) {  // poly_eval: out[0] = p(z)
+        const Fr v = poly_eval(ctx, a.p, n, zz);
+        memcpy(out, v.v, sizeof(Fr));
+    } else if (op == 3) {  // poly_eval_many over the pieces (offset, length) of data, one result each
+        for (size_t i = 0; i < npieces; i++)
+            if (pieces[2 * i] > n || pieces[2 * i + 1] > n - pieces[2 * i]) throw MarlinError(SWM_ERR_INVALID_ARG, "piece out of range");
+        DVec res(ctx, npieces);
+        std::vector<EvalItem> items;
+        for (size_t i = 0; i < npieces; i++) items.push_back({a.p + pieces[2 * i], (size_t)pieces[2 * i + 1], res.p + i});
+        EvalPoint ep = eval_point(ctx, zz);
+        poly_eval_many(ctx, items, ep);
+        std::vector<Fr> h = res.download(0, npieces);
+        if (npieces) memcpy(out, h.data(), npieces * sizeof(Fr));
+    } else {  // ops 4 - 7: dv_ntt_from of data[0..n) into 2^m elements, inverse = bit 0, coset = bit 1 of op - 4; data gets the
+              // source back as the device holds it afterwards
+        DVec t = dv_ntt_from(ctx, a.p, n, (unsigned)m, ((op - 4) & 1) != 0, ((op - 4) & 2) != 0);
+        std::vector<Fr> h = t.download(0, t.n);
+        memcpy(out, h.data(), t.n * sizeof(Fr));
+        std::vector<Fr> s = a.download(0, n);
+        if (n) memcpy(data, s.data(), n * sizeof(Fr));
+    }
+}
+int swm_selftest_poly(swm_ctx* ctx, int op, void* data, size_t n, size_t m, const uint64_t z[4], const uint64_t* pieces,
+                      size_t npieces, void* out) {
+    if (!ctx || op < 0 || op > 8 || (n && !data)) return SWM_ERR_INVALID_ARG;
+    if ((op >= 1 && op <= 3 && !z) || (op == 0 && (!z || m == 0)) || (op != 0 && !out) || (op == 3 && npieces && !pieces))
+        return SWM_ERR_INVALID_ARG;
+    if (op >= 4 && op <= 7 && (m < 1 || m > 28 || n > ((size_t)1 << m))) return SWM_ERR_INVALID_ARG;
+    SWM_ON_DEVICE(ctx);
+    SWM_GUARD(ctx, selftest_poly_impl(ctx, op, data, n, m, z, pieces, npieces, out));
+}
+// sample_fr_bulk on a generator handle into a device buffer, then the download
+static void selftest_sample_impl(swm_ctx* ctx, ChaChaRng& rng, size_t need, uint64_t* out_mont) {
+    DVec d(ctx, need);
+    sample_fr_bulk(ctx, rng, d.p, need);
+    std::vector<Fr> h = d.download(0, need);
+    if (need) memcpy(out_mont, h.data(), need * sizeof(Fr));
+}
+int swm_selftest_sample_fr(swm_ctx* ctx, swm_rng* rng, size_t need, uint64_t* out_mont) {
+    if (!ctx || !rng || (need && !out_mont)) return SWM_ERR_INVALID_ARG;
+    SWM_ON_DEVICE(ctx);
+    SWM_GUARD(ctx, selftest_sample_impl(ctx, rng->r, need, out_mont));
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ pairing self-test (host only)

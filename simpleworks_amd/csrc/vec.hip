@@ -205,6 +205,47 @@ __global__ void __launch_bounds__(256) selftest_g1_add_kernel(const G1Affine* a,
     out[i] = g1_to_jacobian(twice);
 }
 
+// the 29-bit lazy-limb primitives of fr29.cuh and the single-element inversions of frinv.cuh, one lane per element, on raw
+// limbs (include/swmarlin.h: swm_selftest_fr29 names the ops).  8-word operands (unpack, inversions) sit in limbs 0..7.
+__global__ void __launch_bounds__(256) selftest_fr29_kernel(int op, const Fr29* a, const Fr29* b, Spread29 sp, Fr29* out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Fr29 x = a[i];
+    Fr w;
+#pragma unroll
+    for (int k = 0; k < 8; k++) w.v[k] = x.l[k];
+    Fr29 r = fr29_const(Fr29Consts::P);
+    auto words = [&](const Fr& v) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) r.l[k] = v.v[k];
+        r.l[8] = 0;
+    };
+    switch (op) {
+        case 0: r = fr29_mul_fenced(x, b[i]); break;
+        case 1: r = fr29_mul(x, b[i]); break;
+        case 2: r = fr29_normalize(x); break;
+        case 3: r = fr29_cond_sub(x, Fr29Consts::P2); break;
+        case 4: r = fr29_cond_sub(x, Fr29Consts::P); break;
+        case 5: r = fr29_canonical(x, true); break;
+        case 6: r = fr29_canonical(x, false); break;
+        case 7: r = fr29_sub(x, b[i], sp); break;
+        case 8: r = fr29_unpack(w); break;
+        case 9: words(fr29_pack(x)); break;
+        case 10: words(fr_inv_single(w)); break;
+        case 11: words(fr_inv_single_exact(w)); break;
+        default: break;  // (unknown ops are refused by the entry point; r stays r)
+    }
+    out[i] = r;
+}
+int selftest_fr29_run(swm_ctx* ctx, int op, const void* a, const void* b, const uint32_t* sp9, void* out, size_t n) {
+    if (n == 0) return SWM_OK;
+    Spread29 sp;
+    for (int k = 0; k < 9; k++) sp.l[k] = sp9 ? sp9[k] : 0u;
+    SWM_LAUNCH(ctx, "selftest_fr29", selftest_fr29_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, op, (const Fr29*)a,
+               (const Fr29*)b, sp, (Fr29*)out, n);
+    return SWM_OK;
+}
+
 int selftest_mul_run(swm_ctx* ctx, int which, const void* a, const void* b, void* out, size_t n) {
     unsigned grid = (unsigned)((n + 255) / 256);
     if (which == 6)

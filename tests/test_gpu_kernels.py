@@ -81,6 +81,23 @@ def test_device_lazy_limb_multipliers(ctx):
     assert out == [((a + 8 * Q) * (b + 32 * Q) + (8 * Q - a) * b) * inv % Q for a, b in zip(A, B)]
 
 
+def test_device_lazy_limb_squarer(ctx):
+    """fq28.cuh's dedicated squarer (which = 5) on a lazy operand a + b formed limb by limb, a and b < 2^377 (every limb of
+    the sum < 2^29: the rule of tools/check_mul28.py): (a + b)^2 2^-392 mod q, canonical, at the edges of that rule."""
+    import random
+    Q = 0x01AE3A4617C510EAC63B05C06CA1493B1A22D9F300F5138F1EF3622FBA094800170B5D44300000008508C00000000001
+    rnd = random.Random(6)
+    top = (1 << 377) - 1
+    full28 = sum(((1 << 28) - 1) << (28 * i) for i in range(13)) + (((1 << 377 - 28 * 13) - 1) << (28 * 13))
+    edge = [0, 1, 2, Q - 1, Q, Q + 1, top - Q, top, top - 1, full28, 1 << 376, (1 << 28) - 1, 1 << 28]
+    A = [rnd.randrange(1 << 377) for _ in range(4000)] + [x for x in edge for _ in edge]
+    B = [rnd.randrange(1 << 377) for _ in range(4000)] + [y for _ in edge for y in edge]
+    assert max(A + B) <= top
+    inv = pow(1 << 392, -1, Q)
+    out = limbs_to_ints(ctx.selftest_mul(5, ints_to_limbs(A, 6), ints_to_limbs(B, 6)))
+    assert out == [(a + b) * (a + b) * inv % Q for a, b in zip(A, B)]
+
+
 def test_device_group_law(ctx, orc):
     g = golden("g1.json")
     a_pts = [_pt(c["a"]) for c in g["adds"]] + [_pt(c["a"]) for c in g["adds"]]
