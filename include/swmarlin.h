@@ -241,6 +241,32 @@ int swm_proof_recode(const uint8_t *bytes, size_t len, int to_uncompressed, uint
 int swm_verify_proof(const swm_vk *vk, const uint64_t *public_inputs, size_t n, const uint8_t *proof, size_t len,
                      swm_rng *rng, int *ok);
 
+/* Batch form of swm_verify_proof for `count` proofs against one verifying key (an extension: the reference verifies one proof
+ * per call).  On `ctx`'s GPU: one kernel checks every point of the batch, one MSM per pairing input, one two-pairing product.
+ *   public_inputs: count x n_inputs x 4 Montgomery limbs (proof i's inputs at offset 4 * n_inputs * i), as swm_verify_proof.
+ *   proofs[i], lens[i]: proof bytes.  flags: 0 = the compressed form, SWM_PROOF_UNCOMPRESSED = the form of
+ *   swm_generate_proof_ex (every point still checked: on the curve and in the prime-order subgroup).
+ *   *ok = 1 iff every proof parses and is accepted.
+ *   results (may be NULL): per proof, 1 = accepted, 0 = rejected, or the negative status swm_verify_proof returns for those
+ *   bytes (SWM_ERR_SERIALIZATION for a malformed proof or point).
+ * Return value: SWM_OK unless an argument is bad (SWM_ERR_INVALID_ARG: ctx, vk, rng, ok, proofs, lens or one proofs[i] NULL,
+ * public_inputs NULL with n_inputs != 0, unknown flags) or the device fails.  A malformed proof does NOT fail the call, unlike
+ * swm_verify_proof: it makes *ok = 0 and sets its results[i], so that one bad proof cannot hide the verdicts on the others.
+ * count == 0: *ok = 1; nothing is launched and nothing is drawn (proofs, lens may then be NULL).
+ * Randomness: proof i gets two 128-bit randomizers r[i][0], r[i][1] (one per opening point), drawn from rng with the gen_u128 of
+ * swm_verify_proof, in proof order, 2 x count draws whatever the outcome: the generator ends where count sequential
+ * swm_verify_proof calls on well-formed proofs leave it.  Unlike the single verifier, whose first randomizer is 1, both are
+ * random, so two invalid proofs cannot cancel.
+ * Soundness: the batch accepts iff e(-TW, beta_h) e(TC, h) = 1 with TW = sum_i (r[i][0] w_i0 + r[i][1] w_i1) and TC the same
+ * combination of each proof's batch_check sums.  That product is a linear form in the randomizers whose coefficients are the
+ * proofs' own opening checks, so a batch with at least one invalid proof is accepted with probability at most about 2^-128.
+ * After a failed batch (and results != NULL) each proof that parsed is checked on its own with its own two randomizers: its own
+ * pairing product gives results[i].  When the batch passes, every results[i] is 1.  For count == 1 the decision equals
+ * swm_verify_proof's. */
+int swm_verify_proofs_batch(swm_ctx *ctx, const swm_vk *vk, const uint64_t *public_inputs, size_t n_inputs,
+                            const uint8_t *const *proofs, const size_t *lens, size_t count, unsigned flags, swm_rng *rng,
+                            int *ok, int *results);
+
 /* serialization.rs: serialize_/deserialize_verifying_key, deserialize_proof (validation of the byte string) */
 int swm_vk_serialize(const swm_vk *vk, uint8_t *out, size_t cap, size_t *len);
 int swm_vk_deserialize(const uint8_t *bytes, size_t len, swm_vk **out);
@@ -384,6 +410,12 @@ int swm_selftest_poly(swm_ctx *ctx, int op, void *data, size_t n, size_t m, cons
 /* The bulk Fr sampler of the prover (sample_fr_bulk) on a generator handle: `need` elements drawn into a device buffer and
  * downloaded to out_mont (n x 4 uint64, Montgomery form), advancing rng as `need` successive swm_rng_rand_fr calls would. */
 int swm_selftest_sample_fr(swm_ctx *ctx, swm_rng *rng, size_t need, uint64_t *out_mont);
+/* swm_verify_proofs_batch, also returning the batch's two G1 pairing inputs after affine normalisation: tw_xy = TW (before its
+ * negation) and tc_xy = TC, each x || y as 6 + 6 uint64 Montgomery limbs, (0, 0) for the identity, summed over the proofs that
+ * reach the pairing (parsed, and not rejected before the randomizers).  Either output may be NULL. */
+int swm_selftest_verify_batch(swm_ctx *ctx, const swm_vk *vk, const uint64_t *public_inputs, size_t n_inputs,
+                              const uint8_t *const *proofs, const size_t *lens, size_t count, unsigned flags, swm_rng *rng,
+                              int *ok, int *results, uint64_t tw_xy[12], uint64_t tc_xy[12]);
 
 #ifdef __cplusplus
 }

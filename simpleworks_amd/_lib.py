@@ -104,6 +104,10 @@ ABI = {
     "swm_selftest_fr29": (_int, [_vp, _int, _u32p, _u32p, _u32p, _u32p, _sz]),
     "swm_selftest_poly": (_int, [_vp, _int, ctypes.c_void_p, _sz, _sz, _u64p, _u64p, _sz, ctypes.c_void_p]),
     "swm_selftest_sample_fr": (_int, [_vp, _vp, _sz, _u64p]),
+    "swm_verify_proofs_batch": (_int, [_vp, _vp, _u64p, _sz, _vp, ctypes.POINTER(_sz), _sz, ctypes.c_uint, _vp,
+                                       ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "swm_selftest_verify_batch": (_int, [_vp, _vp, _u64p, _sz, _vp, ctypes.POINTER(_sz), _sz, ctypes.c_uint, _vp,
+                                         ctypes.POINTER(_int), ctypes.POINTER(_int), _u64p, _u64p]),
 }
 
 

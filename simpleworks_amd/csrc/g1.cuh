@@ -191,6 +191,44 @@ SWM_HD bool g1_is_on_curve(const G1Affine& p) {
     return fp_eq(lhs, rhs);
 }
 
+// ------------------------------------------------------------------------------------------------ square root in Fq
+// (shared by the device point decoders: g1_decompress_kernel in marlin.hip, the batch verifier's point check in verify.hip)
+struct FqSqrtConsts {
+    static constexpr uint32_t HALF[12] = SWM_FQ_PM1_HALF;
+    static constexpr uint32_t T[12] = SWM_FQ_TS_T;
+    static constexpr uint32_t TP1H[12] = SWM_FQ_TS_T_PLUS1_HALF;
+    static constexpr uint32_t C[12] = SWM_FQ_TS_C_MONT;
+};
+// Tonelli-Shanks as in host/hostmath.h, device side
+__device__ bool fq_sqrt_dev(const Fq& a, Fq* out) {
+    if (fp_is_zero(a)) {
+        *out = a;
+        return true;
+    }
+    if (!fp_is_one(fp_pow(a, FqSqrtConsts::HALF, 12))) return false;
+    Fq c;
+    for (int k = 0; k < 12; k++) c.v[k] = FqSqrtConsts::C[k];
+    Fq x = fp_pow(a, FqSqrtConsts::TP1H, 12);
+    Fq b = fp_pow(a, FqSqrtConsts::T, 12);
+    int m = SWM_FQ_TWO_ADICITY;
+    while (!fp_is_one(b)) {
+        int i = 0;
+        Fq bb = b;
+        while (!fp_is_one(bb)) {
+            bb = fp_sqr(bb);
+            i++;
+        }
+        Fq g = c;
+        for (int k = 0; k < m - i - 1; k++) g = fp_sqr(g);
+        x = fp_mul(x, g);
+        c = fp_sqr(g);
+        b = fp_mul(b, c);
+        m = i;
+    }
+    *out = x;
+    return true;
+}
+
 // ------------------------------------------------------------------------------------------------ twisted Edwards form
 // G1 is also the a = -1 twisted Edwards curve  -x^2 + y^2 = 1 + d x^2 y^2  (constants and the map: tools/gen_constants.py):
 //     x = f (x_w + 1) / y_w,   y = (s (x_w + 1) - 1) / (s (x_w + 1) + 1),   s = 1/sqrt(3), f = sqrt(-(A + 2)/B).

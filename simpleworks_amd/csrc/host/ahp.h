@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <utility>
 #include "blake2s.h"
 #include "chacha.h"
 #include "marlin_types.h"
@@ -210,19 +211,50 @@ LcSet construct_linear_combinations(const IndexInfo& info, const std::vector<Fr>
 }
 
 // ------------------------------------------------------------------------------------------------ verifier
-// Marlin::verify + MarlinKZG10::check_combinations + KZG10::batch_check.  `rng` is the caller's generator
-// (the batch_check randomiser is drawn from it, as in arkworks).
-inline bool verify(const VerifyingKey& vk, std::vector<Fr> public_input, const Proof& proof, ChaChaRng& rng) {
-    const bool vtrace = env_flag("SWM_TRACE");
-    auto vnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double vt0 = vnow();
-    auto vmark = [&](const char* what) {
-        if (vtrace) {
-            double t = vnow();
-            fprintf(stderr, "[swm trace] verify: %-28s %7.3f ms\n", what, t - vt0);
-            vt0 = t;
+// Marlin::verify + MarlinKZG10::check_combinations + KZG10::batch_check, split at the randomizers.
+//
+// verify_plan() does the per-proof part — transcript, construct_linear_combinations, check_combinations and the batch_check
+// coefficients — and writes what is left as (base, scalar) terms: KZG10::batch_check with randomizers r0, r1 for the two
+// opening points (beta, gamma) is
+//     tw = r0 w_0 + r1 w_1,    tc = r0 C_0 + r1 C_1,    accept iff e(-tw, beta_h) e(tc, h) = 1,
+// with C_i = z_i w_i + (combined commitment of point i) - v_i g - random_v_i gamma_g; plan.c[i] lists C_i as terms.  A base is
+// a point of the proof (index < kPlanVkBase: its G1 points in byte order, which for the proofs the plan accepts is the 9
+// commitments with the shifted g_1 and g_2 after their own, then the 2 opening witnesses: 13) or of the verifying key
+// (kPlanVkBase + j: j < 12 the index commitments, 12 = g, 13 = gamma_g, 14 + k = degree_bounds_and_shift_powers[k]).
+// Constant terms of the linear combinations are folded into the claimed evaluations, i.e. into g's scalar.
+// verify() runs the plan with r0 = 1 (arkworks); the batch verifier (verify.hip) with two random r per proof.
+static const uint32_t kPlanVkBase = 1u << 16;
+static const uint32_t kPlanProofPoints = 13;  // points of a proof the plan accepts
+struct PlanTerm {
+    uint32_t base;
+    Fr s;
+};
+struct VerifyPlan {
+    std::vector<PlanTerm> c[2];
+    uint32_t w[2] = {0, 0};  // the base of opening i's witness
+};
+inline uint32_t plan_vk_bases(const VerifyingKey& vk) { return 14 + (uint32_t)vk.vk.degree_bounds_and_shift_powers.size(); }
+inline const G1Affine& plan_vk_base(const VerifyingKey& vk, uint32_t j) {
+    if (j < 12) return vk.index_comms[j].comm;
+    if (j == 12) return vk.vk.g;
+    if (j == 13) return vk.vk.gamma_g;
+    return vk.vk.degree_bounds_and_shift_powers[j - 14].second;
+}
+// the G1 points of a proof in byte order (deserialize_proof reads them in this order)
+template <class P>  // Proof or const Proof
+inline std::vector<decltype(&std::declval<P&>().pc_proof[0].w)> proof_points(P& proof) {
+    std::vector<decltype(&proof.pc_proof[0].w)> out;
+    for (auto& rnd : proof.commitments)
+        for (auto& c : rnd) {
+            out.push_back(&c.comm);
+            if (c.has_shifted) out.push_back(&c.shifted);
         }
-    };
+    for (auto& p : proof.pc_proof) out.push_back(&p.w);
+    return out;
+}
+
+// false: verify() would reject the proof before drawing a randomizer.  Throws MarlinError where verify() throws.
+inline bool verify_plan(const VerifyingKey& vk, std::vector<Fr> public_input, const Proof& proof, VerifyPlan& plan) {
     HDomain dx(public_input.size() + 1);
     size_t padded = std::max<size_t>(public_input.size(), dx.size - 1);
     public_input.resize(padded, fp_zero<Fr>());
@@ -242,34 +274,36 @@ inline bool verify(const VerifyingKey& vk, std::vector<Fr> public_input, const P
     st.beta = fs.sample_outside(dh);
     fs_absorb_commitments(fs, proof.commitments[2]);
     st.gamma = fs.rand_fr();
-    // labelled commitments with their degree bounds
+    // labelled commitments with their degree bounds, as plan bases
     struct LComm {
-        Commitment c;
-        bool has_bound;
+        uint32_t comm, shifted;
+        bool has_shifted, has_bound;
         uint64_t bound;
     };
     std::map<std::string, LComm> commitments;
-    for (int i = 0; i < 12; i++) commitments[kIndexerPolys[i]] = {vk.index_comms[i], false, 0};
+    for (uint32_t i = 0; i < 12; i++) commitments[kIndexerPolys[i]] = {kPlanVkBase + i, 0, false, false, 0};
+    uint32_t pt = 0;  // proof point index, byte order
     {
         int k = 0;
         for (auto& rnd : proof.commitments)
             for (auto& c : rnd) {
                 std::string l = kProverPolys[k++];
-                LComm lc{c, false, 0};
-                if (l == "g_1") lc = {c, true, dh.size - 2};
-                if (l == "g_2") lc = {c, true, dk.size - 2};
+                LComm lc{pt++, 0, c.has_shifted, false, 0};
+                if (c.has_shifted) lc.shifted = pt++;
+                if (l == "g_1") lc.has_bound = true, lc.bound = dh.size - 2;
+                if (l == "g_2") lc.has_bound = true, lc.bound = dk.size - 2;
                 if (lc.has_bound != c.has_shifted) return false;
                 commitments[l] = lc;
             }
     }
+    plan.w[0] = pt;
+    plan.w[1] = pt + 1;
     fs_absorb_evals(fs, proof.evaluations);
     Fr xi = fs.challenge_u128();
     // evaluations keyed by LC label
     std::map<std::string, Fr> evaluations;
-    std::map<std::string, std::string> point_of;
     std::vector<std::string> eval_labels;
     for (auto& q : kQuerySet) {
-        point_of[q.label] = q.point;
         if (lc_has_zero_eval(q.label)) evaluations[q.label] = fp_zero<Fr>();
         else eval_labels.push_back(q.label);
     }
@@ -277,16 +311,17 @@ inline bool verify(const VerifyingKey& vk, std::vector<Fr> public_input, const P
     if (eval_labels.size() != proof.evaluations.size()) return false;
     for (size_t i = 0; i < eval_labels.size(); i++) evaluations[eval_labels[i]] = proof.evaluations[i];
     auto provider = [&](const std::string& label, const LcTerms&, const Fr&) { return evaluations.at(label); };
-    vmark("transcript");
     LcSet lcs = construct_linear_combinations(vk.info, public_input, provider, st);
-    vmark("linear combinations");
-    // check_combinations: combine commitments, fold constant terms into the claimed evaluations
-    std::map<std::string, LComm> lc_comms;
-    for (auto& kv : lcs) {
-        const std::string& label = kv.first;
-        std::vector<std::pair<G1Affine, Fr>> comm_terms, shifted_terms;  // summed by one Straus chain each (g1_msm_host)
+    // check_combinations: each LC commitment as terms, constant terms folded into the claimed evaluations
+    struct LcComm {
+        std::vector<PlanTerm> comm, shifted;
         bool has_bound = false;
         uint64_t bound = 0;
+    };
+    std::map<std::string, LcComm> lc_comms;
+    for (auto& kv : lcs) {
+        const std::string& label = kv.first;
+        LcComm out;
         for (auto& term : kv.second) {
             if (term.second.empty()) {
                 evaluations[label] = fp_sub(evaluations[label], term.first);
@@ -295,78 +330,103 @@ inline bool verify(const VerifyingKey& vk, std::vector<Fr> public_input, const P
             const LComm& cur = commitments.at(term.second);
             if (kv.second.size() == 1 && cur.has_bound) {
                 if (!fp_is_one(term.first)) return false;
-                has_bound = true;
-                bound = cur.bound;
+                out.has_bound = true;
+                out.bound = cur.bound;
             } else if (cur.has_bound) {
                 return false;  // EquationHasDegreeBounds
             }
-            comm_terms.push_back({cur.c.comm, term.first});
-            if (cur.c.has_shifted) shifted_terms.push_back({cur.c.shifted, term.first});
+            out.comm.push_back({cur.comm, term.first});
+            if (cur.has_shifted) out.shifted.push_back({cur.shifted, term.first});
         }
-        LComm out;
-        out.c.comm = g1_to_affine(g1_msm_host(comm_terms));
-        out.c.has_shifted = has_bound;
-        if (has_bound) out.c.shifted = g1_to_affine(g1_msm_host(shifted_terms));
-        out.has_bound = has_bound;
-        out.bound = bound;
+        if (!out.has_bound) out.shifted.clear();
         lc_comms[label] = out;
     }
-    vmark("combined commitments");
     // batch_check: per query point (beta, then gamma), labels in sorted order, challenges xi^0, xi^1, ...
-    struct Combined {
-        G1Affine c;
-        Fr z, v;
-    };
-    std::vector<Combined> combined;
     const char* points[2] = {"beta", "gamma"};
-    for (auto pl : points) {
+    for (int i = 0; i < 2; i++) {
         std::vector<std::string> labels;
         for (auto& q : kQuerySet)
-            if (std::string(q.point) == pl) labels.push_back(q.label);
+            if (std::string(q.point) == points[i]) labels.push_back(q.label);
         std::sort(labels.begin(), labels.end());
-        std::vector<std::pair<G1Affine, Fr>> cc_terms;
+        std::vector<PlanTerm>& c = plan.c[i];
         Fr cv = fp_zero<Fr>();
         Fr ch = fp_one<Fr>();  // xi^ctr
         for (auto& l : labels) {
-            const LComm& lc = lc_comms.at(l);
+            const LcComm& lc = lc_comms.at(l);
             const Fr& v = evaluations.at(l);
-            cc_terms.push_back({lc.c.comm, ch});
+            for (auto& t : lc.comm) c.push_back({t.base, fp_mul(t.s, ch)});
             cv = fp_add(cv, fp_mul(v, ch));
             ch = fp_mul(ch, xi);
             if (lc.has_bound) {
-                const G1Affine* sp = nullptr;
-                for (auto& ds : vk.vk.degree_bounds_and_shift_powers)
-                    if (ds.first == lc.bound) sp = &ds.second;
+                uint32_t sp = 0;
+                const auto& dbs = vk.vk.degree_bounds_and_shift_powers;
+                for (size_t k = 0; k < dbs.size(); k++)
+                    if (dbs[k].first == lc.bound) sp = kPlanVkBase + 14 + (uint32_t)k;
                 if (!sp) return false;
-                // (shifted - v * shift_power) * ch as two terms of the same sum
-                cc_terms.push_back({lc.c.shifted, ch});
-                cc_terms.push_back({*sp, fp_neg(fp_mul(v, ch))});
+                // (shifted - v * shift_power) * ch
+                for (auto& t : lc.shifted) c.push_back({t.base, fp_mul(t.s, ch)});
+                c.push_back({sp, fp_neg(fp_mul(v, ch))});
                 ch = fp_mul(ch, xi);
             }
         }
-        combined.push_back({g1_to_affine(g1_msm_host(cc_terms)), std::string(pl) == "beta" ? st.beta : st.gamma, cv});
-    }
-    vmark("batched openings");
-    // total_c = sum_i randomizer_i (z_i w_i + c_i) - g_mult g - gamma_g_mult gamma_g,  total_w = sum_i randomizer_i w_i
-    std::vector<std::pair<G1Affine, Fr>> c_terms, w_terms;
-    Fr randomizer = fp_one<Fr>(), g_mult = fp_zero<Fr>(), gamma_g_mult = fp_zero<Fr>();
-    for (size_t i = 0; i < combined.size(); i++) {
         const PcProof& pp = proof.pc_proof[i];
-        g_mult = fp_add(g_mult, fp_mul(randomizer, combined[i].v));
-        if (pp.has_random_v) gamma_g_mult = fp_add(gamma_g_mult, fp_mul(randomizer, pp.random_v));
-        c_terms.push_back({pp.w, fp_mul(randomizer, combined[i].z)});
-        c_terms.push_back({combined[i].c, randomizer});
-        w_terms.push_back({pp.w, randomizer});
-        uint64_t rv[2];
-        rng.gen_u128(rv);
-        randomizer = fr_from_u128(rv);
+        c.push_back({plan.w[i], i == 0 ? st.beta : st.gamma});
+        c.push_back({kPlanVkBase + 12, fp_neg(cv)});
+        if (pp.has_random_v) c.push_back({kPlanVkBase + 13, fp_neg(pp.random_v)});
     }
-    c_terms.push_back({vk.vk.g, fp_neg(g_mult)});
-    c_terms.push_back({vk.vk.gamma_g, fp_neg(gamma_g_mult)});
-    G1Affine tw = g1_to_affine(g1_msm_host(w_terms)), tc = g1_to_affine(g1_msm_host(c_terms));
+    return true;
+}
+
+// One proof's pairing inputs (tw before its negation, tc) from its plan and randomizers, by host Straus (g1_msm_host) over the
+// plan's terms merged per base.  pts: the proof's points in byte order.
+inline void plan_pairing_inputs(const VerifyingKey& vk, const G1Affine* const* pts, const VerifyPlan& plan, const Fr r[2],
+                                G1Affine* tw, G1Affine* tc) {
+    const uint32_t nvk = plan_vk_bases(vk);
+    std::vector<Fr> sp(kPlanProofPoints, fp_zero<Fr>()), sv(nvk, fp_zero<Fr>());
+    for (int i = 0; i < 2; i++)
+        for (auto& t : plan.c[i]) {
+            Fr& dst = t.base >= kPlanVkBase ? sv[t.base - kPlanVkBase] : sp[t.base];
+            dst = fp_add(dst, fp_mul(r[i], t.s));
+        }
+    std::vector<std::pair<G1Affine, Fr>> c_terms, w_terms;
+    for (uint32_t j = 0; j < kPlanProofPoints; j++) c_terms.push_back({*pts[j], sp[j]});
+    for (uint32_t j = 0; j < nvk; j++) c_terms.push_back({plan_vk_base(vk, j), sv[j]});
+    for (int i = 0; i < 2; i++) w_terms.push_back({*pts[plan.w[i]], r[i]});
+    *tw = g1_to_affine(g1_msm_host(w_terms));
+    *tc = g1_to_affine(g1_msm_host(c_terms));
+}
+inline bool pairing_check(const VerifyingKey& vk, G1Affine tw, const G1Affine& tc) {
     if (!g1_is_inf(tw)) tw = g1_neg(tw);
+    return product_of_pairings_is_one({{tw, vk.vk.beta_h}, {tc, vk.vk.h}});
+}
+
+// `rng` is the caller's generator (the batch_check randomiser is drawn from it, as in arkworks: after each of the two
+// openings, the second draw unused).
+inline bool verify(const VerifyingKey& vk, std::vector<Fr> public_input, const Proof& proof, ChaChaRng& rng) {
+    const bool vtrace = env_flag("SWM_TRACE");
+    auto vnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double vt0 = vnow();
+    auto vmark = [&](const char* what) {
+        if (vtrace) {
+            double t = vnow();
+            fprintf(stderr, "[swm trace] verify: %-28s %7.3f ms\n", what, t - vt0);
+            vt0 = t;
+        }
+    };
+    VerifyPlan plan;
+    if (!verify_plan(vk, std::move(public_input), proof, plan)) return false;
+    vmark("transcript + combinations");
+    Fr r[2];
+    uint64_t rv[2];
+    r[0] = fp_one<Fr>();
+    rng.gen_u128(rv);
+    r[1] = fr_from_u128(rv);
+    rng.gen_u128(rv);
+    std::vector<const G1Affine*> pts = proof_points(proof);
+    G1Affine tw, tc;
+    plan_pairing_inputs(vk, pts.data(), plan, r, &tw, &tc);
     vmark("pairing inputs");
-    const bool ok = product_of_pairings_is_one({{tw, vk.vk.beta_h}, {tc, vk.vk.h}});
+    const bool ok = pairing_check(vk, tw, tc);
     vmark("two pairings");
     return ok;
 }

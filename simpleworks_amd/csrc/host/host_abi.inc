@@ -6,22 +6,7 @@
 // Needs before inclusion: swmarlin.h, host/ahp.h, host/host_handles.h, declarations of swm::set_err and swm::drain_streams.
 #include <memory>
 #include <new>
-#define SWM_GUARD(ctx, body)                                  \
-    try {                                                     \
-        body;                                                 \
-        return SWM_OK;                                        \
-    } catch (const MarlinError& e) {                          \
-        drain_streams(ctx);                                   \
-        set_err(ctx, e.code, "%s", e.what());                 \
-        return e.code;                                        \
-    } catch (const std::bad_alloc&) {                         \
-        drain_streams(ctx);                                   \
-        return SWM_ERR_OOM;                                   \
-    } catch (const std::exception& e) {                       \
-        drain_streams(ctx);                                   \
-        set_err(ctx, SWM_ERR_INTERNAL, "%s", e.what());       \
-        return SWM_ERR_INTERNAL;                              \
-    }
+// (SWM_GUARD: host/host_handles.h)
 
 extern "C" {
 

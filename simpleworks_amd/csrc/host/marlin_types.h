@@ -138,6 +138,9 @@ struct ByteReader {
     const uint8_t* p;
     size_t n, pos = 0;
     bool uncompressed = false;  // G1 points in the serialize_uncompressed form (ByteWriter::uncompressed); still CHECKED here
+    // != nullptr: g1() only takes the point's bytes, records where they are and returns the identity — the batch verifier
+    // (verify.hip) checks all points of a batch in one kernel instead
+    std::vector<const uint8_t*>* defer_g1 = nullptr;
     ByteReader(const uint8_t* d, size_t len) : p(d), n(len) {}
     const uint8_t* take(size_t k) {
         if (k > n - pos) throw MarlinError(SWM_ERR_SERIALIZATION, "unexpected end of input");  // (pos <= n always: no wrap for a huge k)
@@ -162,6 +165,10 @@ struct ByteReader {
         return r;
     }
     G1Affine g1() {
+        if (defer_g1) {
+            defer_g1->push_back(take(uncompressed ? 96 : 48));
+            return g1_affine_identity();
+        }
         if (uncompressed) {  // deserialize_uncompressed: x, y | flags, then on-curve (this reader: always) and subgroup checks
             uint8_t u[96];
             memcpy(u, take(96), 96);
@@ -250,9 +257,12 @@ inline std::vector<uint8_t> serialize_proof(const Proof& pr, bool uncompressed =
     return w.b;
 }
 
-inline Proof deserialize_proof(const uint8_t* data, size_t len, bool uncompressed = false) {
+// defer_g1: see ByteReader (the points of the result are then identities, their encodings listed in byte order)
+inline Proof deserialize_proof(const uint8_t* data, size_t len, bool uncompressed = false,
+                               std::vector<const uint8_t*>* defer_g1 = nullptr) {
     ByteReader r(data, len);
     r.uncompressed = uncompressed;
+    r.defer_g1 = defer_g1;
     Proof pr;
     uint64_t nr = r.u64();
     if (nr > 16) throw MarlinError(SWM_ERR_SERIALIZATION, "bad round count");

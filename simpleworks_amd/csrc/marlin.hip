@@ -2044,41 +2044,7 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
 // curve and subgroup checks CanonicalDeserialize performs).  When a key is loaded, only what defines it is used — the
 // matrices, the committer key, the verifying key; everything derived from the matrices (arithmetisation polynomials and
 // their evaluation tables) is parsed for shape and then recomputed on the device rather than trusted.
-struct FqSqrtConsts {
-    static constexpr uint32_t HALF[12] = SWM_FQ_PM1_HALF;
-    static constexpr uint32_t T[12] = SWM_FQ_TS_T;
-    static constexpr uint32_t TP1H[12] = SWM_FQ_TS_T_PLUS1_HALF;
-    static constexpr uint32_t C[12] = SWM_FQ_TS_C_MONT;
-};
-// Tonelli-Shanks as in host/hostmath.h, device side
-__device__ bool fq_sqrt_dev(const Fq& a, Fq* out) {
-    if (fp_is_zero(a)) {
-        *out = a;
-        return true;
-    }
-    if (!fp_is_one(fp_pow(a, FqSqrtConsts::HALF, 12))) return false;
-    Fq c;
-    for (int k = 0; k < 12; k++) c.v[k] = FqSqrtConsts::C[k];
-    Fq x = fp_pow(a, FqSqrtConsts::TP1H, 12);
-    Fq b = fp_pow(a, FqSqrtConsts::T, 12);
-    int m = SWM_FQ_TWO_ADICITY;
-    while (!fp_is_one(b)) {
-        int i = 0;
-        Fq bb = b;
-        while (!fp_is_one(bb)) {
-            bb = fp_sqr(bb);
-            i++;
-        }
-        Fq g = c;
-        for (int k = 0; k < m - i - 1; k++) g = fp_sqr(g);
-        x = fp_mul(x, g);
-        c = fp_sqr(g);
-        b = fp_mul(b, c);
-        m = i;
-    }
-    *out = x;
-    return true;
-}
+// (FqSqrtConsts and fq_sqrt_dev, the device square root: g1.cuh)
 // affine -> ark-serialize compressed form (48 bytes: x little-endian, bit 7 of the last byte = y is the larger root,
 // bit 6 = infinity)
 __global__ void __launch_bounds__(256) g1_compress_kernel(const G1Affine* __restrict__ in, size_t n, uint32_t* __restrict__ out) {

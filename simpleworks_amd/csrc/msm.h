@@ -162,6 +162,8 @@ int msm_launch_lazy_tail(swm_ctx* ctx, bool wide);  // the held-back bucket stag
 int msm_flush_tails(swm_ctx* ctx);
 int msm_finish(swm_ctx* ctx, MsmJob* job, G1XYZZ* result);
 int msm_finish_many(swm_ctx* ctx, MsmJob** jobs, int k, G1XYZZ* results);  // a round's jobs: one wait, folds side by side
+// The context's host worker pool (created on first use): the MSM folds, the batch verifier's per-proof plans (verify.hip).
+HostPool* host_pool_of(swm_ctx* ctx);
 int msm_run(swm_ctx* ctx, const G1Affine* d_bases, const G1Affine* d_bases28, const void* d_scalars, size_t n, int mont,
             G1XYZZ* result, MsmInfMask inf = MsmInfMask(), MsmTable tab = MsmTable());
 

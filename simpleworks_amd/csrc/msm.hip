@@ -2970,7 +2970,7 @@ static bool msm_fold(const MsmJob* job, HostPool* pool, G1XYZZ* result, const G1
 // the machine: hardware threads / ranks on the node (LOCAL_WORLD_SIZE of the launcher, or the context's shard world for ranks
 // that are threads of one process) minus the proving thread — eight ranks with 15 polling workers each would be 120 spinning
 // threads beside the provers, torch and the RCCL proxies.  SWM_POOL_WORKERS overrides.
-static HostPool* host_pool_of(swm_ctx* ctx) {
+HostPool* host_pool_of(swm_ctx* ctx) {
     if (!ctx->host_pool) {
         unsigned hw = std::thread::hardware_concurrency();
         unsigned want = hw > 1 ? std::min(hw - 1, hw >= 32 ? 15u : 7u) : 0u;

@@ -438,6 +438,39 @@ def verify_proof(verifying_key, public_inputs, proof, rng):
     return bool(ok.value)
 
 
+def _batch_args(public_inputs, proofs):
+    """(inputs, n_inputs, pointer array, lengths, keep-alive buffers) for swm_verify_proofs_batch."""
+    data = [pr.data if isinstance(pr, MarlinProof) else bytes(pr) for pr in proofs]
+    count = len(data)
+    n_inputs = len(public_inputs[0]) if count else 0
+    if len(public_inputs) != count or any(len(p) != n_inputs for p in public_inputs):
+        raise ValueError("verify_proofs: one list of public inputs per proof, all of the same length")
+    pi = _to_mont_limbs([x for p in public_inputs for x in p])
+    bufs = [(ctypes.c_uint8 * max(1, len(b))).from_buffer_copy(b.ljust(1, b"\0")) for b in data]
+    ptrs = (ctypes.c_void_p * max(1, count))(*[ctypes.addressof(b) for b in bufs])
+    lens = (ctypes.c_size_t * max(1, count))(*[len(b) for b in data])
+    return pi, n_inputs, ptrs, lens, bufs
+
+
+def verify_proofs(verifying_key, public_inputs, proofs, rng, *, ctx=None, per_proof=False, uncompressed=False):
+    """Batch form of verify_proof on the GPU (swm_verify_proofs_batch): every proof against one verifying key, one pairing
+    check for the batch.  public_inputs: one list of ints per proof; proofs: MarlinProof objects or proof bytes
+    (uncompressed=True: the form of generate_proof_uncompressed).  Returns True iff every proof parses and is accepted; with
+    per_proof=True, (that, [1 accepted / 0 rejected / negative SWM_ERR_* code of a malformed proof, per proof]).  Draws two
+    128-bit randomizers per proof from rng, as that many verify_proof calls on well-formed proofs would."""
+    ctx = ctx or default_context()
+    pi, n_inputs, ptrs, lens, _bufs = _batch_args(public_inputs, proofs)
+    count = len(proofs)
+    ok = ctypes.c_int(0)
+    res = (ctypes.c_int * max(1, count))()
+    _check(ctx.lib.swm_verify_proofs_batch(ctx.h, verifying_key.h, _p64(pi) if len(pi) else None, n_inputs, ptrs, lens, count,
+                                           1 if uncompressed else 0, rng.h, ctypes.byref(ok), res if per_proof else None),
+           "swm_verify_proofs_batch", ctx)
+    if per_proof:
+        return bool(ok.value), [int(res[i]) for i in range(count)]
+    return bool(ok.value)
+
+
 class MarlinInst:
     """`MarlinInst` (= ark_marlin::Marlin<Fr, MultiPC, FS>, src/marlin/mod.rs:14) as the reference's in-tree callers use
     it: associated functions that take a ConstraintSynthesizer — SimpleMerkleTree::{new, prove, verify}

@@ -77,6 +77,13 @@ extern "C" {
     pub fn swm_proof_recode(bytes: *const u8, len: usize, to_uncompressed: c_int, out: *mut u8, cap: usize, out_len: *mut usize) -> c_int;
     pub fn swm_verify_proof(vk: *const swm_vk, public_inputs: *const u64, n: usize, proof: *const u8, len: usize,
                             rng: *mut swm_rng, ok: *mut c_int) -> c_int;
+    // batch form (an extension beyond the reference's calls): `count` proofs against one key, one pairing check on the GPU
+    pub fn swm_verify_proofs_batch(ctx: *mut swm_ctx, vk: *const swm_vk, public_inputs: *const u64, n_inputs: usize,
+                                   proofs: *const *const u8, lens: *const usize, count: usize, flags: c_uint, rng: *mut swm_rng,
+                                   ok: *mut c_int, results: *mut c_int) -> c_int;
+    pub fn swm_selftest_verify_batch(ctx: *mut swm_ctx, vk: *const swm_vk, public_inputs: *const u64, n_inputs: usize,
+                                     proofs: *const *const u8, lens: *const usize, count: usize, flags: c_uint, rng: *mut swm_rng,
+                                     ok: *mut c_int, results: *mut c_int, tw_xy: *mut u64, tc_xy: *mut u64) -> c_int;
 
     // src/marlin/serialization.rs:5-45 (ark-serialize bytes in both directions)
     pub fn swm_vk_serialize(vk: *const swm_vk, out: *mut u8, cap: usize, len: *mut usize) -> c_int;

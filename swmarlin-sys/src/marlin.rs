@@ -504,6 +504,58 @@ fn verify<R: RngCore + 'static>(vk: &VerifyingKey, public_inputs: &[Fr], proof: 
     out.map(|_| ok != 0)
 }
 
+/// Batch form of `verify_proof` (an extension: the reference verifies one proof per call): every proof against one key, with
+/// one pairing check for the batch on this thread's GPU context (`swm_verify_proofs_batch`).  `public_inputs[i]` belongs to
+/// `proofs[i]`.  `Ok(true)` iff every proof is accepted; a proof that does not verify or does not parse gives `Ok(false)`.
+/// Draws two 128-bit randomizers per proof from `rng`, as that many `verify_proof` calls would.
+pub fn verify_proofs(
+    verifying_key: &VerifyingKey,
+    public_inputs: &[Vec<ConstraintF>],
+    proofs: &[MarlinProof],
+    rng: &mut StdRng,
+) -> Result<bool> {
+    verify_batch(verifying_key, public_inputs, proofs, rng).map_err(|e| anyhow!("{:?}", e))
+}
+
+fn verify_batch<R: RngCore + 'static>(vk: &VerifyingKey, public_inputs: &[Vec<Fr>], proofs: &[MarlinProof], rng: &mut R)
+    -> std::result::Result<bool, SwmError> {
+    if public_inputs.len() != proofs.len() {
+        return Err(SwmError { code: -1, what: "verify_proofs", detail: "one list of public inputs per proof".into() });
+    }
+    let n_inputs = public_inputs.first().map_or(0, |p| p.len());
+    if public_inputs.iter().any(|p| p.len() != n_inputs) {
+        return Err(SwmError { code: -1, what: "verify_proofs", detail: "public input lists of different lengths".into() });
+    }
+    let (_, vk_bytes) = vk_key(vk)?;
+    let mut bytes: Vec<Vec<u8>> = Vec::with_capacity(proofs.len());
+    for p in proofs {
+        let mut b = Vec::new();
+        p.serialize(&mut b).map_err(|e| SwmError { code: -7, what: "Proof::serialize", detail: format!("{:?}", e) })?;
+        bytes.push(b);
+    }
+    let ptrs: Vec<*const u8> = bytes.iter().map(|b| b.as_ptr()).collect();
+    let lens: Vec<usize> = bytes.iter().map(|b| b.len()).collect();
+    let inputs: Vec<u64> = public_inputs.iter().flat_map(|p| p.iter().flat_map(|f| fr_limbs(f))).collect();
+    let mut vk_h = std::ptr::null_mut();
+    check(unsafe { swm_vk_deserialize(vk_bytes.as_ptr(), vk_bytes.len(), &mut vk_h) }, "swm_vk_deserialize", std::ptr::null_mut())?;
+    let mut ok: c_int = 0;
+    let out = with_state(|st| {
+        with_rng(rng, |r| {
+            check(
+                unsafe {
+                    swm_verify_proofs_batch(st.ctx, vk_h, if inputs.is_empty() { std::ptr::null() } else { inputs.as_ptr() },
+                                            n_inputs, ptrs.as_ptr(), lens.as_ptr(), proofs.len(), 0, r, &mut ok,
+                                            std::ptr::null_mut())
+                },
+                "swm_verify_proofs_batch",
+                st.ctx,
+            )
+        })
+    });
+    unsafe { swm_vk_destroy(vk_h) };
+    out.map(|_| ok != 0)
+}
+
 // ------------------------------------------------------------------------------------------------ MarlinInst
 /// `MarlinInst` as every in-tree caller of the reference uses it — `SimpleMerkleTree::{new, prove, verify}`
 /// (/root/reference/src/merkle_tree/simple_merkle_tree.rs:39,83,119,148), `examples/manual-constraints.rs:89-99`,
