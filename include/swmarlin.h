@@ -404,7 +404,11 @@ int swm_selftest_fr29(swm_ctx *ctx, int op, const uint32_t *a9, const uint32_t *
  *   3 poly_eval_many at z over npieces pieces (pieces[2 i] = offset, pieces[2 i + 1] = length) of data: out[i]
  *   4..7 ntt_run_from: the transform of data[0..n) zero-extended to 2^m elements into out; op - 4 = inverse + 2 coset;
  *        data receives the source as the device holds it afterwards
- *   8 scan_exclusive_u32 of data as n uint32 words: out[0..n) as uint32, the total (mod 2^32) at out[n] */
+ *   8 scan_exclusive_u32 of data as n uint32 words: out[0..n) as uint32, the total (mod 2^32) at out[n]
+ *   9 ntt_cosets_fwd: the polynomial data[0..n), n <= 2^(m+1), on the npieces cosets w_(4 N)^k <w_N> (N = 2^m, k = pieces[c] <= 3,
+ *     one uint64 each): out[c N + j] = p(w_(4 N)^(4 j + k))
+ *  10 ntt_cosets_inv and the recombination: data = n = 3 N evaluations on the cosets k = 0, 1, 2 (N each, natural order) ->
+ *     out = the 3 N coefficients of the polynomial of degree < 3 N that takes them */
 int swm_selftest_poly(swm_ctx *ctx, int op, void *data, size_t n, size_t m, const uint64_t z[4], const uint64_t *pieces,
                       size_t npieces, void *out);
 /* The bulk Fr sampler of the prover (sample_fr_bulk) on a generator handle: `need` elements drawn into a device buffer and

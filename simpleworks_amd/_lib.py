@@ -501,6 +501,24 @@ class Context:
         self._poly(4 + int(bool(inverse)) + 2 * int(bool(coset)), src, src.shape[0], log_n, None, None, out)
         return out, src
 
+    def selftest_ntt_cosets(self, coeffs_mont, log_n, ks):
+        """The polynomial coeffs (at most 2^(log_n + 1) of them) on the cosets w_(4n)^k <w_n>, k in ks (n = 2^log_n):
+        len(ks) x n x 4, coset c at [c] in natural order (ntt_cosets_fwd)."""
+        src = np.ascontiguousarray(coeffs_mont, dtype=np.uint64).reshape(-1, 4).copy()
+        kk = np.ascontiguousarray(ks, dtype=np.uint64).reshape(-1)
+        out = np.zeros((kk.size << log_n, 4), dtype=np.uint64)
+        self._check(self.lib.swm_selftest_poly(self.h, 9, src.ctypes.data, src.shape[0], log_n, _p64(np.zeros(4, np.uint64)),
+                                               _p64(kk), kk.size, out.ctypes.data), "swm_selftest_poly")
+        return out.reshape(kk.size, 1 << log_n, 4)
+
+    def selftest_intt_cosets3(self, evals_mont, log_n):
+        """Evaluations on the cosets 0, 1, 2 (3 x 2^log_n, natural order) -> the 3 * 2^log_n coefficients of the polynomial of
+        degree < 3 * 2^log_n that takes them (ntt_cosets_inv and the prover's recombination)."""
+        ev = np.ascontiguousarray(evals_mont, dtype=np.uint64).reshape(-1, 4).copy()
+        out = np.zeros_like(ev)
+        self._poly(10, ev, ev.shape[0], log_n, None, None, out)
+        return out
+
     def selftest_scan(self, words):
         """(exclusive prefix sums of uint32 words, total), both mod 2^32 (scan_exclusive_u32)."""
         w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)

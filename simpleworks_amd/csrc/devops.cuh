@@ -22,6 +22,8 @@ namespace swm {
 
 int ntt_run(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int coset);
 int ntt_run_from(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int coset, const void* first_src, size_t src_len);
+int ntt_cosets_fwd(swm_ctx* ctx, const void* coeffs, size_t len, unsigned log_n, const unsigned* ks, unsigned ncos, void* out);
+int ntt_cosets_inv(swm_ctx* ctx, void* data, unsigned log_n, unsigned ncos);
 // one transform of 2^log_n elements over the ranks of the context's sharding (ntt.hip): in place on the rank's n / G
 // elements, CYCLIC -> BLOCKS layout (blocks_in = 0) or BLOCKS -> CYCLIC (blocks_in = 1), one all-to-all
 int ntt_sharded_run(swm_ctx* ctx, void* d_local, unsigned log_n, int inverse, int blocks_in);

@@ -1200,6 +1200,26 @@ void div_vk(swm_ctx* ctx, const Fr* q, size_t part, size_t total, Fr* h) {
         h[j] = acc;
     });
 }
+// Round 2 on three cosets of H (s_k H, s_k = w_4|H|^k, k = 0, 1, 2: the points i = k mod 4 of the 4|H| domain) instead of the whole
+// 4|H| domain: q_1 - mask has degree 3|H| - 1 (deg r(alpha, X) = |H| - 1, deg z_A = deg z_B = |H| with zk bound 1; t z: 2|H| - 1), so
+// three cosets determine it (tests/test_outer_cosets_degree.py checks the bound on the model).  Coset 0 is H itself, where every
+// factor is known without a transform; cosets 1 and 2 come from ntt_cosets_fwd (two |H|-point transforms in one launch per pass
+// instead of a 4|H|-point one) and the way back is ntt_cosets_inv plus cosets3_solve.  -DSWM_OUTER_COSETS=0 builds the 4|H| path.
+#ifndef SWM_OUTER_COSETS
+#define SWM_OUTER_COSETS 1
+#endif
+static constexpr uint64_t OUTER_COSETS_MIN_H = 16;
+// u_k = p0 + c^k p1 + c^2k p2 (k = 0, 1, 2; c = w_4, c^2 = -1; what ntt_cosets_inv leaves) -> the three blocks p0, p1, p2
+struct Cosets3 {
+    Fr p0, p1, p2;
+};
+__device__ __forceinline__ Cosets3 cosets3_solve(const Fr& u0, const Fr& u1, const Fr& u2, const Fr& iota, const Fr& half) {
+    const Fr p1 = fp_mul(fp_sub(u0, u2), half);
+    const Fr e = fp_mul(fp_add(u0, u2), half);  // p0 + p2
+    const Fr d = fp_sub(u1, fp_mul(iota, p1));  // p0 - p2
+    return {fp_mul(fp_add(e, d), half), p1, fp_mul(fp_sub(e, d), half)};
+}
+static Fr fr_half() { return fp_inv(fp_from_u64<Fr>(2)); }
 // alpha^|H| - X^|H| on the 4|H| domain, where X^|H| = i4^(i mod 4), i4 = w4^|H| a primitive fourth root of unity
 struct RAlphaNumerators {
     Fr n0, n1, n2, n3;
@@ -1258,6 +1278,7 @@ struct ProveState {
     unsigned mask_pieces = 1;
     AsyncMsm mask_part[2];
     bool ra_closed_form = false;
+    bool cosets = false;  // round 2 on the cosets 0, 1, 2 of H (SWM_OUTER_COSETS): e_za, e_zb, e_z, e_ra hold cosets 1 | 2
     LcSet lcs;
     DVec mask, z, za_evals, zb_evals, za_loc, zb_loc, x_poly, x_evals, w_poly, za_poly, zb_poly, e_za, e_zb, e_z;
     DVec r_alpha_evals, e_ra, t_poly, q1, h1, g1x, f, h2;
@@ -1484,10 +1505,20 @@ DVec on_mul_domain(swm_ctx* ctx, const ProveState& s, const Fr* coeffs, size_t n
 }
 // ---- the challenge-independent part of round 2, issued before the round-1 commitments are awaited so that it runs under
 // them: z_A, z_B and z = w v_X + x in evaluation form on the 4|H| domain
+DVec on_cosets12(swm_ctx* ctx, const ProveState& s, const Fr* coeffs, size_t n) {
+    static const unsigned ks[2] = {1, 2};
+    DVec v(ctx, 2 * s.H);
+    rc_check(ctx, ntt_cosets_fwd(ctx, coeffs, n, s.dh.log, ks, 2, v.p));
+    return v;
+}
 void round2_prework(swm_ctx* ctx, ProveState& s) {
     const uint64_t H = s.H, X = s.X;
-    s.e_za = on_mul_domain(ctx, s, s.za_poly.p, H + 1);
-    s.e_zb = on_mul_domain(ctx, s, s.zb_poly.p, H + 1);
+    // single-GPU rounds (the sharded ones and the r(alpha, X)-by-transforms test hook keep the 4|H| domain)
+    s.cosets = SWM_OUTER_COSETS && !s.sp.r1 && !s.sp.r2 && H >= OUTER_COSETS_MIN_H && s.mask_len == 3 * H &&
+               !env_flag("SWM_RALPHA_TRANSFORMS");
+    auto on_domain = [&](const Fr* coeffs, size_t n) { return s.cosets ? on_cosets12(ctx, s, coeffs, n) : on_mul_domain(ctx, s, coeffs, n); };
+    s.e_za = on_domain(s.za_poly.p, H + 1);
+    s.e_zb = on_domain(s.zb_poly.p, H + 1);
     DVec z_poly = dv_zeros(ctx, H + 1);
     Fr* out = z_poly.p;
     const Fr* wc = s.P_w.p;
@@ -1500,7 +1531,7 @@ void round2_prework(swm_ctx* ctx, ProveState& s) {
         if (i < X) v = fp_add(v, xp[i]);
         out[i] = v;
     });
-    s.e_z = on_mul_domain(ctx, s, z_poly.p, H + 1);
+    s.e_z = on_domain(z_poly.p, H + 1);
 }
 
 // ---- end of round 1: blinding, the rest of a mask committed in pieces, the commitments
@@ -1567,6 +1598,23 @@ void r_alpha(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
             out[p] = fp_mul(out[p], q == 0 ? nu.n0 : q == 1 ? nu.n1 : q == 2 ? nu.n2 : nu.n3);
         });
         r_alpha_on_h(ctx, pk, s);
+    } else if (s.cosets) {
+        // point i = 4 j + k of the 4|H| domain at k |H| + j: one inversion over the 3|H| points of cosets 0, 1, 2
+        const uint64_t H = s.H;
+        const unsigned logH = pk.logH;
+        s.e_ra = DVec(ctx, 3 * H);
+        PowTable wt = root_pow_table(ctx, s.logM);
+        Fr* out = s.e_ra.p;
+        ew(ctx, "r_alpha_den", 3 * H, [=] __device__(size_t p) { out[p] = fp_sub(alpha, wt.at(((p & (H - 1)) << 2) + (p >> logH))); });
+        rc_check(ctx, batch_inverse_run(ctx, out, 3 * H));
+        const RAlphaNumerators nu = r_alpha_numerators(alpha, pk.logH, M);
+        Fr* rh = s.r_alpha_evals.p;
+        ew(ctx, "r_alpha_scale", 3 * H, [=] __device__(size_t p) {
+            const size_t q = p >> logH;
+            Fr v = fp_mul(out[p], q == 0 ? nu.n0 : q == 1 ? nu.n1 : nu.n2);
+            out[p] = v;
+            if (q == 0) rh[p] = v;
+        });
     } else {
         s.e_ra = DVec(ctx, M);
         PowTable wt = root_pow_table(ctx, s.logM);
@@ -1602,6 +1650,25 @@ void round2_t(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
             Fr v = fp_add(fp_add(fp_mul(eta_a, pa[c]), fp_mul(eta_b, pb[c])), fp_mul(eta_c, pc[c]));
             out[reindex_by_subdomain(H, X, c)] = v;
         });
+        if (s.cosets) {
+            // coset 0 (= H) of q_1 - mask from what is known on H: r(alpha, .), z_A and z_B (their hiding terms vanish on H),
+            // t (before its interpolation) and z = w v_X + x (the assignment where w_evals put it, x's evaluations on the X-subgroup)
+            s.q1 = DVec(ctx, 3 * H);
+            Fr* q = s.q1.p;
+            const Fr *rh = s.r_alpha_evals.p, *za = s.za_evals.p, *zb = s.zb_evals.p, *th = s.t_poly.p, *zz = s.z.p, *xe = s.x_evals.p;
+            const uint64_t ratio = H / X;
+            const size_t nwit = s.shape.nwit, ninst = s.ninst;
+            ew(ctx, "round2_pointwise_h", H, [=] __device__(size_t k) {
+                Fr zk = xe[k];
+                if (k % ratio != 0) {
+                    const size_t wi = k - k / ratio - 1;
+                    zk = wi < nwit ? zz[ninst + wi] : fp_zero<Fr>();
+                }
+                const Fr a = za[k], b = zb[k];
+                const Fr summed = fp_add(fp_add(fp_mul(eta_c, fp_mul(a, b)), fp_mul(eta_a, a)), fp_mul(eta_b, b));
+                q[k] = fp_sub(fp_mul(rh[k], summed), fp_mul(zk, th[k]));
+            });
+        }
         dv_ntt(ctx, s.t_poly, pk.logH, true);
     }
     s.tr.tick("r2: t polynomial enqueued");
@@ -1611,7 +1678,49 @@ void round2_t(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
 }
 
 // ---- round 2: q_1 = r(alpha, X) sum_M eta_M z_M - t z + mask on the 4|H| domain, and (h_1, X g_1) = q_1 / v_H
+// On cosets 1 and 2 (coset 0 is in place since round2_t), back through three |H|-point inverse transforms, and the three blocks
+// of q_1 - mask recovered, the mask added and v_H divided out in one pass: h_1 = q[H, 3H) + q[2H, 3H) X^H, X g_1 = q0 + q1 + q2
+void round2_q1_cosets(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    const uint64_t H = s.H;
+    const Fr eta_a = s.st.eta_a, eta_b = s.st.eta_b, eta_c = s.st.eta_c;
+    if (!s.ra_closed_form) {
+        DVec ra_poly = dv_ntt_from(ctx, s.r_alpha_evals.p, H, pk.logH, true);
+        DVec e12 = on_cosets12(ctx, s, ra_poly.p, H);
+        s.e_ra = DVec(ctx, 3 * H);
+        hip_check(ctx, hipMemcpyAsync(s.e_ra.p + H, e12.p, 2 * H * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream), "copy");
+    }
+    {
+        DVec e_t = on_cosets12(ctx, s, s.t_poly.p, H);
+        Fr* out = s.q1.p + H;
+        const Fr *pra = s.e_ra.p + H, *pza = s.e_za.p, *pzb = s.e_zb.p, *pt = e_t.p, *pz = s.e_z.p;
+        ew(ctx, "round2_pointwise", 2 * H, [=] __device__(size_t i) {
+            Fr a = pza[i], b = pzb[i];
+            Fr summed = fp_add(fp_add(fp_mul(eta_c, fp_mul(a, b)), fp_mul(eta_a, a)), fp_mul(eta_b, b));
+            out[i] = fp_sub(fp_mul(pra[i], summed), fp_mul(pz[i], pt[i]));
+        });
+        s.e_za.release();
+        s.e_zb.release();
+        s.e_z.release();
+    }
+    rc_check(ctx, ntt_cosets_inv(ctx, s.q1.p, pk.logH, 3));
+    s.h1 = DVec(ctx, 3 * H);
+    s.g1x = DVec(ctx, H);
+    const Fr* q = s.q1.p;
+    const Fr* mp = s.mask.p;
+    Fr *h = s.h1.p, *g = s.g1x.p;
+    const Fr iota = HDomain(4).gen, half = fr_half();
+    ew(ctx, "q1_cosets_solve_div_vh", H, [=] __device__(size_t j) {
+        const Cosets3 c = cosets3_solve(q[j], q[j + H], q[j + 2 * H], iota, half);
+        const Fr p0 = fp_add(c.p0, mp[j]), p1 = fp_add(c.p1, mp[j + H]), p2 = fp_add(c.p2, mp[j + 2 * H]);
+        const Fr hj = fp_add(p1, p2);
+        h[j] = hj;
+        h[j + H] = p2;
+        h[j + 2 * H] = fp_zero<Fr>();
+        g[j] = fp_add(p0, hj);
+    });
+}
 void round2_q1(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
+    if (s.cosets) return round2_q1_cosets(ctx, pk, s);
     const uint64_t H = s.H, M = s.M;
     const size_t Mloc = s.sp.Mloc;
     const Fr eta_a = s.st.eta_a, eta_b = s.st.eta_b, eta_c = s.st.eta_c;
@@ -1697,6 +1806,9 @@ void round3_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
     const Fr eta_a = s.st.eta_a, eta_b = s.st.eta_b, eta_c = s.st.eta_c;
     const Fr vhab = fp_mul(s.dh.vanishing(alpha), s.dh.vanishing(beta));
     s.f = DVec(ctx, K);
+    // f on K is kept (SWM_OUTER_COSETS): coset 0 of the 4|K| domain, so that f's forward transform covers cosets 1 - 3 only
+    const bool f_cosets = SWM_OUTER_COSETS && !s.sp.r3 && Bsz == 4 * K && K >= OUTER_COSETS_MIN_H;
+    DVec f_K;
     {
         // the three denominator vectors share one buffer and ONE batch inversion: its cost is the serial Fermat chain of
         // a lane (~0.4 ms whatever the length), so three launches would pay it three times
@@ -1710,12 +1822,17 @@ void round3_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
         Fr* out = s.f.p;
         const Fr *ia = inv.p, *ib = inv.p + K, *ic = inv.p + 2 * K;
         const Fr *va = pk.ar[0].val_K.p, *vb = pk.ar[1].val_K.p, *vc = pk.ar[2].val_K.p;
+        if (f_cosets) {
+            f_K = DVec(ctx, K);
+            out = f_K.p;
+        }
         ew(ctx, "round3_f_K", K, [=] __device__(size_t i) {
             Fr t = fp_add(fp_add(fp_mul(fp_mul(eta_a, va[i]), ia[i]), fp_mul(fp_mul(eta_b, vb[i]), ib[i])),
                           fp_mul(fp_mul(eta_c, vc[i]), ic[i]));
             out[i] = fp_mul(vhab, t);
         });
-        dv_ntt(ctx, s.f, pk.logK, true);
+        if (f_cosets) rc_check(ctx, ntt_run_from(ctx, s.f.p, pk.logK, 1, 0, f_K.p, K));
+        else dv_ntt(ctx, s.f, pk.logK, true);
     }
     s.P_g2.p = s.f.p + 1; s.P_g2.n = K - 1; s.P_g2.has_bound = true; s.P_g2.bound = K - 2;
     pc_commit_begin(ctx, pk, &s.lane, s.P_g2.p, s.P_g2.n, true, K - 2, false, &s.j3[0]);  // overlaps the 4|K|-domain work below
@@ -1738,6 +1855,21 @@ void round3_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
         DVec loc(ctx, 3 * Kl);
         div_vk(ctx, ab.p, Kl, Bloc, loc.p);
         shard_gather_cyclic(ctx, loc.p, 3 * Kl, s.sp.slog_g, s.h2.p, 3 * K);
+    } else if (f_cosets) {
+        // point i of the 4|K| domain: f from coset i mod 4 at i / 4 (coset 0: the kept evaluations on K)
+        static const unsigned ks[3] = {1, 2, 3};
+        DVec e_f(ctx, 3 * K);
+        rc_check(ctx, ntt_cosets_fwd(ctx, s.f.p, K, pk.logK, ks, 3, e_f.p));
+        DVec ab(ctx, Bsz);
+        Fr* out = ab.p;
+        const Fr *pf = e_f.p, *fk = f_K.p;
+        const unsigned logK = pk.logK;
+        ew(ctx, "round3_pointwise_B", Bsz, [=] __device__(size_t i) {
+            const size_t k = i & 3, j = i >> 2;
+            out[i] = round3_a_minus_bf(ix, ch, i, k ? pf[((k - 1) << logK) + j] : fk[j]);
+        });
+        dv_ntt(ctx, ab, pk.logB, true);
+        div_vk(ctx, ab.p, K, Bsz, s.h2.p);
     } else {
         DVec e_f = dv_ntt_from(ctx, s.f.p, K, pk.logB, false);
         DVec ab(ctx, Bsz);
@@ -2509,6 +2641,32 @@ static void selftest_poly_impl(swm_ctx* ctx, int op, void* data, size_t n, size_
     }
     DVec a(ctx, n);
     if (n) a.upload((const Fr*)data, n);
+    if (op == 9) {  // ntt_cosets_fwd of data[0..n) (n <= 2^(m+1)) onto the npieces cosets pieces[c] of 2^m points: out[c 2^m + j]
+        unsigned ks[4];
+        for (size_t c = 0; c < npieces; c++) ks[c] = (unsigned)pieces[c];
+        DVec t(ctx, npieces << m);
+        rc_check(ctx, ntt_cosets_fwd(ctx, a.p, n, (unsigned)m, ks, (unsigned)npieces, t.p));
+        std::vector<Fr> h = t.download(0, t.n);
+        memcpy(out, h.data(), t.n * sizeof(Fr));
+        return;
+    }
+    if (op == 10) {  // data = evaluations on the cosets 0, 1, 2 of 2^m points -> out = the 3 2^m coefficients (degree < 3 2^m)
+        const size_t N = (size_t)1 << m;
+        rc_check(ctx, ntt_cosets_inv(ctx, a.p, (unsigned)m, 3));
+        DVec t(ctx, 3 * N);
+        const Fr* u = a.p;
+        Fr* o = t.p;
+        const Fr iota = HDomain(4).gen, half = fr_half();
+        ew(ctx, "cosets3_solve", N, [=] __device__(size_t j) {
+            const Cosets3 c = cosets3_solve(u[j], u[j + N], u[j + 2 * N], iota, half);
+            o[j] = c.p0;
+            o[j + N] = c.p1;
+            o[j + 2 * N] = c.p2;
+        });
+        std::vector<Fr> h = t.download(0, t.n);
+        memcpy(out, h.data(), t.n * sizeof(Fr));
+        return;
+    }
     if (op == 0) {  // suffix_recurrence(a, n, m, z) in place
         suffix_recurrence(ctx, a.p, n, m, zz);
         std::vector<Fr> h = a.download(0, n);
@@ -2541,10 +2699,16 @@ static void selftest_poly_impl(swm_ctx* ctx, int op, void* data, size_t n, size_
 }
 int swm_selftest_poly(swm_ctx* ctx, int op, void* data, size_t n, size_t m, const uint64_t z[4], const uint64_t* pieces,
                       size_t npieces, void* out) {
-    if (!ctx || op < 0 || op > 8 || (n && !data)) return SWM_ERR_INVALID_ARG;
+    if (!ctx || op < 0 || op > 10 || (n && !data)) return SWM_ERR_INVALID_ARG;
     if ((op >= 1 && op <= 3 && !z) || (op == 0 && (!z || m == 0)) || (op != 0 && !out) || (op == 3 && npieces && !pieces))
         return SWM_ERR_INVALID_ARG;
     if (op >= 4 && op <= 7 && (m < 1 || m > 28 || n > ((size_t)1 << m))) return SWM_ERR_INVALID_ARG;
+    if (op == 9) {
+        if (m < 1 || m > 26 || n > ((size_t)2 << m) || npieces < 1 || npieces > 4 || !pieces) return SWM_ERR_INVALID_ARG;
+        for (size_t c = 0; c < npieces; c++)
+            if (pieces[c] > 3) return SWM_ERR_INVALID_ARG;
+    }
+    if (op == 10 && (m < 1 || m > 26 || n != ((size_t)3 << m))) return SWM_ERR_INVALID_ARG;
     SWM_ON_DEVICE(ctx);
     SWM_GUARD(ctx, selftest_poly_impl(ctx, op, data, n, m, z, pieces, npieces, out));
 }

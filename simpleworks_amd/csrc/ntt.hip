@@ -42,6 +42,13 @@ struct NttPassArgs {
     int scale_out;        // multiply output by n_inv (last pass of an inverse transform)
     int coset_out;        // ... and by g^-i
     Fr n_inv;
+    // several transforms of size n in one launch (blockIdx.y = c): transform c reads src + c src_cstride and writes
+    // dst + c dst_cstride; its coset factor is cs^(cos_k[c] i) — cos_k = 1 for g^i, k for s_k^i = w_4n^(k i) on the 4n-root tables.
+    // fold_in: first pass of a coset transform of up to 2n coefficients, input i + n folds onto input i times fold[c] (= s_k^n)
+    uint64_t src_cstride, dst_cstride;
+    uint32_t cos_k[4];
+    int fold_in;
+    Fr fold[4];
 };
 
 __device__ __forceinline__ Fr two_level_pow(const Fr* lo, const Fr* hi, uint64_t e) {
@@ -64,6 +71,9 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass(NttPassArgs a) {
     const uint64_t j0 = (uint64_t)blockIdx.x * J;
     const uint64_t ns_mask = (1ull << a.log_ns) - 1;
     const unsigned tw_shift = a.log_n - a.log_ns - a.log_r;  // w_{Ns R} = w_n^(2^tw_shift)
+    const Fr* src = a.src + blockIdx.y * a.src_cstride;
+    Fr* dst = a.dst + blockIdx.y * a.dst_cstride;
+    const uint64_t cs_k = a.cos_k[blockIdx.y];
     // ---- load (+ inter-pass twiddle, + coset scaling).  A tile has at most 1024 elements (ntt_run): four per lane, all
     // four global loads issued before the first twiddle multiplication so that their latencies overlap.
     for (unsigned e0 = 0; e0 < R * J; e0 += 4 * NTT_THREADS) {
@@ -73,7 +83,8 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass(NttPassArgs a) {
             unsigned e = e0 + threadIdx.x + u * NTT_THREADS;
             if (e < R * J) {
                 const uint64_t at = j0 + e % J + (uint64_t)(e / J) * stride;
-                xs[u] = at < a.src_len ? a.src[at] : fp_zero<Fr>();
+                xs[u] = at < a.src_len ? src[at] : fp_zero<Fr>();
+                if (a.fold_in && at + n < a.src_len) xs[u] = fp_add(xs[u], fp_mul(a.fold[blockIdx.y], src[at + n]));
             }
         }
 #pragma unroll
@@ -83,7 +94,7 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass(NttPassArgs a) {
             unsigned jj = e % J, t = e / J;
             uint64_t idx = j0 + jj + (uint64_t)t * stride;
             Fr x = xs[u];
-            if (a.coset_in) x = fp_mul(x, two_level_pow(a.cs_lo, a.cs_hi, idx));
+            if (a.coset_in) x = fp_mul(x, two_level_pow(a.cs_lo, a.cs_hi, idx * cs_k));
             if (a.log_ns != 0 && t != 0) {
                 uint64_t k = (j0 + jj) & ns_mask;
                 if (k) x = fp_mul(x, two_level_pow(a.tw_lo, a.tw_hi, (k * t) << tw_shift));
@@ -150,10 +161,10 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass(NttPassArgs a) {
         Fr x = tile[bitrev_u(u, a.log_r) * J + jj];
         if (a.scale_out) {
             Fr s = a.n_inv;
-            if (a.coset_out) s = fp_mul(s, two_level_pow(a.cs_lo, a.cs_hi, o));
+            if (a.coset_out) s = fp_mul(s, two_level_pow(a.cs_lo, a.cs_hi, o * cs_k));
             x = fp_mul(x, s);
         }
-        a.dst[o] = x;
+        dst[o] = x;
     }
 }
 
@@ -218,6 +229,9 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) ntt_pass_lazy(NttLazyArgs args
     const uint64_t j0 = (uint64_t)blockIdx.x * J;
     const uint64_t ns_mask = (1ull << a.log_ns) - 1;
     const unsigned tw_shift = a.log_n - a.log_ns - a.log_r;
+    const Fr* src = a.src + blockIdx.y * a.src_cstride;
+    Fr* dst = a.dst + blockIdx.y * a.dst_cstride;
+    const uint64_t cs_k = a.cos_k[blockIdx.y];
     // ---- load: unpack, coset factor, inter-pass twiddle (w^0 = one included: every loaded value of a later pass is a product)
     for (unsigned e0 = 0; e0 < R * J; e0 += 4 * NTT_THREADS) {
         Fr xs[4];
@@ -226,7 +240,9 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) ntt_pass_lazy(NttLazyArgs args
             unsigned e = e0 + threadIdx.x + u * NTT_THREADS;
             if (e < R * J) {
                 const uint64_t at = j0 + e % J + (uint64_t)(e / J) * stride;
-                xs[u] = at < a.src_len ? a.src[at] : fp_zero<Fr>();
+                xs[u] = at < a.src_len ? src[at] : fp_zero<Fr>();
+                // (fold: canonical 8 x 32-bit arithmetic on the loaded value, so the input bound of the pass is unchanged)
+                if (a.fold_in && at + n < a.src_len) xs[u] = fp_add(xs[u], fp_mul(a.fold[blockIdx.y], src[at + n]));
             }
         }
 #pragma unroll
@@ -236,7 +252,7 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) ntt_pass_lazy(NttLazyArgs args
             unsigned jj = e % J, t = e / J;
             uint64_t idx = j0 + jj + (uint64_t)t * stride;
             Fr29 x = fr29_unpack(xs[u]);
-            if (a.coset_in) x = fr29_mul_fenced(x, two_level_pow29(a.cs_lo, a.cs_hi, idx));
+            if (a.coset_in) x = fr29_mul_fenced(x, two_level_pow29(a.cs_lo, a.cs_hi, idx * cs_k));
             if (a.log_ns != 0) {
                 uint64_t k = (j0 + jj) & ns_mask;
                 // per-pass table (one multiplication less per element; 32 B more traffic on a kernel at 5 % of HBM), else the
@@ -308,12 +324,12 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) ntt_pass_lazy(NttLazyArgs args
         Fr29 x = tile_get(tile, bitrev_u(u, a.log_r) * J + jj);
         if (a.scale_out) {
             Fr29 sc = fr29_unpack(a.n_inv);
-            if (a.coset_out) sc = fr29_mul_fenced(two_level_pow29(a.cs_lo, a.cs_hi, o), sc);
+            if (a.coset_out) sc = fr29_mul_fenced(two_level_pow29(a.cs_lo, a.cs_hi, o * cs_k), sc);
             x = fr29_canonical(fr29_mul_fenced(x, sc), true);
         } else if (args.last_pass) {
             x = fr29_canonical(x, P.out_below_2r != 0);
         }
-        a.dst[o] = fr29_pack(x);
+        dst[o] = fr29_pack(x);
     }
 }
 
@@ -476,17 +492,47 @@ int ntt_run_from(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int co
 int ntt_run(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int coset) {
     return ntt_run_from(ctx, d_data, log_n, inverse, coset, nullptr, 0);
 }
+// ncos transforms of size n = 2^log_n in one launch per pass (blockIdx.y = c), transform c on d_data + c n.  coset: 0 none,
+// 1 the generator-22 coset (ncos = 1), 2 the cosets s_k <w_n> with s_k = w_4n^(ks[c]) (forward: coefficient i + n folds onto
+// coefficient i, src_len <= 2n; inverse: the s_k^-j unscaling).  first_src (forward only when ncos > 1): every transform reads it.
+static int ntt_run_multi(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int coset, const void* first_src, size_t src_len,
+                         unsigned ncos, const unsigned* ks);
 // The transform of first_src[0 .. src_len) zero-extended to 2^log_n elements, written to d_data (which need not be
 // initialised; first_src is left as it was and must not overlap d_data).  The first pass reads first_src and takes the
 // missing inputs as zero: no padded copy in front of the transform.  first_src == nullptr: in place on d_data.
 int ntt_run_from(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int coset, const void* first_src, size_t src_len) {
+    if (first_src && src_len > (1ull << std::min(log_n, 62u))) src_len = 1ull << log_n;
+    return ntt_run_multi(ctx, d_data, log_n, inverse, coset ? 1 : 0, first_src, src_len, 1, nullptr);
+}
+// The evaluations of the polynomial coeffs[0 .. len), len <= 2n, on the cosets s_k <w_n> (s_k = w_4n^k, k = ks[c]), i.e. at the
+// points of the 4n-point domain with index k mod 4: out + c n holds coset ks[c] in natural order (out[c n + j] = p(w_4n^(4 j + k))).
+// The points i = k mod 4 of a 4n-point transform of the same polynomial, at two thirds (2 cosets) or three quarters of its
+// elements and in one pass fewer: p(s_k w^j) = sum_{i < n} (p_i + s_k^n p_(i + n)) s_k^i w^(i j), s_k^n = w_4^k.
+int ntt_cosets_fwd(swm_ctx* ctx, const void* coeffs, size_t len, unsigned log_n, const unsigned* ks, unsigned ncos, void* out) {
+    if (ncos < 1 || ncos > 4 || log_n > 28 || len > (2ull << log_n)) return set_err(ctx, SWM_ERR_INVALID_ARG, "ntt cosets: bad shape");
+    for (unsigned c = 0; c < ncos; c++)
+        if (ks[c] > 3) return set_err(ctx, SWM_ERR_INVALID_ARG, "ntt cosets: coset index > 3");
+    return ntt_run_multi(ctx, out, log_n, 0, 2, coeffs, len, ncos, ks);
+}
+// In place on data[0 .. ncos n): coset c (k = c) from its n evaluations back to sum_m p_(j + m n) w_4^(k m) at j — the polynomial
+// modulo X^n - s_k^n.  With ncos = 3 and deg p < 3n: u_k = p0 + w_4^k p1 + w_4^(2k) p2 (cosets3_solve in the prover recovers the
+// three blocks of coefficients).
+int ntt_cosets_inv(swm_ctx* ctx, void* data, unsigned log_n, unsigned ncos) {
+    if (ncos < 1 || ncos > 4 || log_n > 28) return set_err(ctx, SWM_ERR_INVALID_ARG, "ntt cosets: bad shape");
+    const unsigned ks[4] = {0, 1, 2, 3};
+    return ntt_run_multi(ctx, data, log_n, 1, 2, nullptr, 0, ncos, ks);
+}
+static int ntt_run_multi(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int coset, const void* first_src, size_t src_len,
+                         unsigned ncos, const unsigned* ks) {
     if (log_n > 30) return set_err(ctx, SWM_ERR_INVALID_ARG, "ntt: log_n > 30 unsupported");
     const uint64_t n = 1ull << log_n;
-    if (first_src && src_len > n) src_len = n;
-    ctx->stat_ntt_calls++;
-    ctx->log_call('n', log_n);
-    ctx->stat_ntt_elems += n;
+    for (unsigned c = 0; c < ncos; c++) {  // one call-list entry per transform: the replayed call list stays what ran
+        ctx->stat_ntt_calls++;
+        ctx->log_call('n', log_n);
+        ctx->stat_ntt_elems += n;
+    }
     Fr* data = reinterpret_cast<Fr*>(d_data);
+    const uint64_t total = n * ncos;
     // pass plan
     const unsigned maxr = NTT_MAX_LOG_R;
     // arithmetic: lazy 29-bit limbs (fr29.cuh, ntt_pass_lazy) unless SWM_NTT_LAZY=0 asks for the 32-bit-limb kernel of r01 / r02
@@ -494,7 +540,14 @@ int ntt_run_from(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int co
     static const bool lazy = env_switch("SWM_NTT_LAZY", 1, 0, 1) != 0;
     NttTables *rt = nullptr, *ct = nullptr;
     SWM_TRY(get_root_tables_form(ctx, log_n, inverse, lazy, &rt));
-    if (coset) SWM_TRY(get_coset_tables(ctx, log_n, inverse, &ct, lazy));
+    if (coset == 1) SWM_TRY(get_coset_tables(ctx, log_n, inverse, &ct, lazy));
+    if (coset == 2) SWM_TRY(get_root_tables_form(ctx, log_n + 2, inverse, lazy, &ct));  // s_k^i = w_4n^(k i), k i < 3n
+    Fr fold[4];
+    for (unsigned c = 0; c < 4; c++) {
+        fold[c] = fp_one<Fr>();
+        if (coset == 2 && c < ncos)
+            for (unsigned e = 0; e < ks[c]; e++) fold[c] = fp_mul(fold[c], host_root_of_unity(2, false));  // s_k^n = w_4^k
+    }
     Fr n_inv = fp_one<Fr>();
     if (inverse) n_inv = fp_inv(fp_from_u64<Fr>(n));
     if (lazy) n_inv = fp_mul(n_inv, fp_from_u64<Fr>(32));  // radix 2^261
@@ -509,14 +562,14 @@ int ntt_run_from(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int co
         }
     }
     Fr *tmp = nullptr, *tmp2 = nullptr;
-    SWM_TRY(scratch(ctx, "ntt.tmp", n * sizeof(Fr), (void**)&tmp));
+    SWM_TRY(scratch(ctx, "ntt.tmp", total * sizeof(Fr), (void**)&tmp));
     // The last pass has to land in `data`.  Even pass counts ping-pong data <-> tmp; an odd count of three or more goes
     // data -> tmp -> tmp2 -> ... -> data through a second scratch buffer (one more n-element buffer in HBM instead of a
     // full device-to-device copy in front of every such transform); a single pass (n <= 2^10) copies, it is tiny.
-    if (npass % 2 == 1 && npass >= 3) SWM_TRY(scratch(ctx, "ntt.tmp2", n * sizeof(Fr), (void**)&tmp2));
+    if (npass % 2 == 1 && npass >= 3) SWM_TRY(scratch(ctx, "ntt.tmp2", total * sizeof(Fr), (void**)&tmp2));
     const Fr* src = first_src ? reinterpret_cast<const Fr*>(first_src) : data;
     if (npass == 1 && !first_src) {
-        SWM_HIP(ctx, hipMemcpyAsync(tmp, data, n * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+        SWM_HIP(ctx, hipMemcpyAsync(tmp, data, total * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
         src = tmp;
     }
     unsigned log_ns = 0;
@@ -541,6 +594,13 @@ int ntt_run_from(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int co
         a.scale_out = (inverse && p == npass - 1) ? 1 : 0;
         a.coset_out = (coset && inverse && p == npass - 1) ? 1 : 0;
         a.n_inv = n_inv;
+        a.src_cstride = (p == 0 && first_src) ? 0 : n;  // every transform of a call folds the same coefficients
+        a.dst_cstride = n;
+        a.fold_in = (coset == 2 && a.coset_in && src_len > n) ? 1 : 0;
+        for (unsigned c = 0; c < 4; c++) {
+            a.cos_k[c] = coset == 2 ? (c < ncos ? ks[c] : 0) : 1;
+            a.fold[c] = fold[c];
+        }
         uint64_t cols = n >> a.log_r;
         if (lazy) {
             NttLazyArgs la;
@@ -557,7 +617,7 @@ int ntt_run_from(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int co
             const size_t elems = (size_t)J << a.log_r;
             size_t shmem = (elems + (elems >> 5) + 1) * 36;  // tile_slot: one slot of padding per 32 elements
             if (shmem < 64) shmem = 64;
-            dim3 grid((unsigned)(cols / J)), block(NTT_THREADS);
+            dim3 grid((unsigned)(cols / J), ncos), block(NTT_THREADS);
             if (shmem > 64 * 1024) {  // only the experimental tile sizes: J = 1
                 static std::atomic<size_t> granted[64];
                 if (J != 1 || shmem > 160 * 1024) return set_err(ctx, SWM_ERR_INVALID_ARG, "ntt: tile does not fit LDS");
@@ -576,14 +636,14 @@ int ntt_run_from(swm_ctx* ctx, void* d_data, unsigned log_n, int inverse, int co
         } else if (npass == 1) {
             size_t shmem = sizeof(Fr) << a.log_r;
             if (shmem < 64) shmem = 64;
-            SWM_LAUNCH(ctx, "ntt_pass", ntt_pass<1>, dim3((unsigned)cols), dim3(NTT_THREADS), shmem, a);
+            SWM_LAUNCH(ctx, "ntt_pass", ntt_pass<1>, dim3((unsigned)cols, ncos), dim3(NTT_THREADS), shmem, a);
         } else {
             unsigned J = (log_n >= 19 ? 1024u : 512u) >> a.log_r;
             if (J < 1) J = 1;
             if (J > 16) J = 16;
             while (J > cols) J >>= 1;
             size_t shmem = (sizeof(Fr) * J) << a.log_r;
-            dim3 grid((unsigned)(cols / J)), block(NTT_THREADS);
+            dim3 grid((unsigned)(cols / J), ncos), block(NTT_THREADS);
             switch (J) {
                 case 1: SWM_LAUNCH(ctx, "ntt_pass", ntt_pass<1>, grid, block, shmem, a); break;
                 case 2: SWM_LAUNCH(ctx, "ntt_pass", ntt_pass<2>, grid, block, shmem, a); break;
