@@ -430,9 +430,10 @@ inline void suffix_recurrence(swm_ctx* ctx, Fr* a, size_t n, size_t m, const Fr&
 struct DivResult {
     DVec work;  // work[0] = p(x); work[1..n) = quotient of p / (X - x)
 };
-inline DivResult div_linear(swm_ctx* ctx, const Fr* p, size_t n, const Fr& x) {
+// cap > n: the buffer gets cap elements, zero from n on (room above the quotient for the caller)
+inline DivResult div_linear(swm_ctx* ctx, const Fr* p, size_t n, const Fr& x, size_t cap = 0) {
     DivResult r;
-    r.work = dv_copy_padded(ctx, p, n, n ? n : 1);
+    r.work = dv_copy_padded(ctx, p, n, std::max<size_t>({n, cap, 1}));
     if (n == 0) r.work.zero();
     suffix_recurrence(ctx, r.work.p, n, 1, x);
     return r;

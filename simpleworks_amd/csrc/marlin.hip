@@ -114,10 +114,13 @@ struct swm_pk {
     // flat schedule runs on them and d_*28 are the n-point scaled copies only
     G1TE* d_powers_te = nullptr;
     G1TE* d_shifted_te = nullptr;
+    // whether bases_at serves the n powers from `offset` on out of the powers' own table: an MSM against them can then be
+    // folded into one against the powers from 0 on (open_combinations)
+    bool in_powers(size_t offset, size_t n) const { return offset + n <= n_powers; }
     // bases for an MSM of n points starting at SRS power `offset`
     void bases_at(size_t offset, size_t n, const G1Affine** b, const G1Affine** b28, MsmTable* tab) const {
         *tab = MsmTable();
-        if (offset + n <= n_powers) {
+        if (in_powers(offset, n)) {
             *b = d_powers + offset;
             *b28 = d_powers28 + offset;
             if (tab_c) *tab = MsmTable{d_powers_te ? nullptr : d_powers28, n_powers, tab_c, offset, d_powers_te};
@@ -1954,6 +1957,21 @@ std::vector<Fr> evaluations(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
 // ---- MarlinKZG10::open_combinations: per query point, labels in sorted order, challenges xi^0, xi^1, ...
 // Phase 1 builds the combined polynomial, its witness and the shifted witnesses for BOTH points and enqueues all
 // their MSMs; phase 2 waits and adds the host-side hiding terms.  Nothing is awaited before everything is enqueued.
+// A point's witness is MSM(powers, wq) + MSM(powers from off on, k sq) (+ hiding), off = srs_max_degree - bound.  Where the
+// shifted powers are a sub-range of the powers (swm_pk::in_powers: an SRS of the circuit's own degree) both read one table and
+//   MSM(powers, wq) + MSM(powers + off, k sq) = MSM(powers, wq + X^off k sq)
+// (G1 has order r, the scalars add in Fr): ONE job per point, and a position costs one mixed addition instead of two wherever
+// both quotients are non-zero.  The fold comes after both divisions: the shifted witness is X^off (g / (X - z)), not the quotient
+// of X^off g.  -DSWM_OPEN_FOLD=0 builds the two-job path, which a key with shifted powers on a table of their own takes anyway.
+#ifndef SWM_OPEN_FOLD
+#define SWM_OPEN_FOLD 1
+#endif
+// wq[t] += k * sq[t], t < n (wq: the plain quotient from X^off on; sq: the bounded member's quotient)
+__global__ void __launch_bounds__(256) open_fold_shifted(Fr* __restrict__ wq, const Fr* __restrict__ sq, size_t n, Fr k) {
+    SWM_LIGHT_KERNEL();
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x)
+        wq[t] = fp_add(wq[t], fp_mul(sq[t], k));
+}
 std::vector<PcProof> open_combinations(swm_ctx* ctx, const swm_pk& pk, ProveState& s, const Fr& xi) {
     struct ShiftedTerm {
         LPoly* lp;
@@ -1972,6 +1990,8 @@ std::vector<PcProof> open_combinations(swm_ctx* ctx, const swm_pk& pk, ProveStat
         std::vector<DivResult> sq;
         AsyncMsm wjob;
         std::vector<AsyncMsm> sjobs;
+        AsyncMsm folded_slot;  // a folded point's place in the sharded exchange (below): never a job, always the identity
+        bool folded = false;
         HPoly r_comb, shifted_r, shifted_r_witness;
         std::vector<ShiftedTerm> shifted_terms;
     };
@@ -2029,27 +2049,53 @@ std::vector<PcProof> open_combinations(swm_ctx* ctx, const swm_pk& pk, ProveStat
                 out[i] = acc;
             });
         }
-        // witness = p / (X - point) against the powers; degree-bounded members: shifted witnesses against the shifted powers
+        // witness = p / (X - point) against the powers; degree-bounded members: shifted witnesses against the shifted powers,
+        // folded into the plain quotient where both read the powers' table (then the job follows BOTH divisions)
         s.tr.tick(pi == 0 ? "open beta: combination enqueued" : "open gamma: combination enqueued");
-        o.wq = div_linear(ctx, o.comb.p, plen, point);
+        size_t wn = plen ? plen - 1 : 0;  // coefficients of the (merged) witness quotient
+        std::vector<bool> folded(o.shifted_terms.size(), false);
+        for (size_t i = 0; i < o.shifted_terms.size(); i++) {
+            const LPoly* lp = o.shifted_terms[i].lp;
+            const size_t off = pk.srs_max_degree - lp->bound, qn = lp->n ? lp->n - 1 : 0;
+            folded[i] = SWM_OPEN_FOLD && qn && pk.in_powers(off, qn);
+            if (folded[i]) wn = std::max(wn, off + qn);
+        }
+        o.wq = div_linear(ctx, o.comb.p, plen, point, wn + 1);  // zero above the quotient
         s.tr.tick("  witness quotient enqueued");
-        commit_enqueue(ctx, &s.lane, pk, 0, o.wq.work.p + 1, plen ? plen - 1 : 0, &o.wjob);
-        s.tr.tick("  witness commitment enqueued");
+        const bool fold_any = std::find(folded.begin(), folded.end(), true) != folded.end();
+        if (!fold_any) {
+            commit_enqueue(ctx, &s.lane, pk, 0, o.wq.work.p + 1, wn, &o.wjob);
+            s.tr.tick("  witness commitment enqueued");
+        }
         o.sq.resize(o.shifted_terms.size());
-        o.sjobs.resize(o.shifted_terms.size());
+        o.sjobs.reserve(o.shifted_terms.size());  // (jobs in flight are referred to by address)
         for (size_t i = 0; i < o.shifted_terms.size(); i++) {
             auto& stt = o.shifted_terms[i];
             o.sq[i] = div_linear(ctx, stt.lp->p, stt.lp->n, point);
             Fr k = stt.ch;
             Fr* q = o.sq[i].work.p;
-            size_t qn = stt.lp->n ? stt.lp->n - 1 : 0;
+            const size_t off = pk.srs_max_degree - stt.lp->bound, qn = stt.lp->n ? stt.lp->n - 1 : 0;
+            if (folded[i]) {
+                const unsigned grid = (unsigned)std::min<size_t>((qn + 255) / 256, 256 * 32);
+                LAUNCHX(ctx, "open_fold_shifted", open_fold_shifted, dim3(grid), dim3(256), 0, o.wq.work.p + 1 + off, q + 1, qn, k);
+                s.tr.tick("  shifted quotient folded");
+                continue;
+            }
             ew(ctx, "open_scale", qn, [=] __device__(size_t t) { q[t + 1] = fp_mul(q[t + 1], k); });
             s.tr.tick("  shifted quotient enqueued");
-            commit_enqueue(ctx, &s.lane, pk, pk.srs_max_degree - stt.lp->bound, q + 1, qn, &o.sjobs[i]);
+            o.sjobs.emplace_back();
+            commit_enqueue(ctx, &s.lane, pk, off, q + 1, qn, &o.sjobs.back());
             s.tr.tick("  shifted commitment enqueued");
         }
+        if (fold_any) {
+            commit_enqueue(ctx, &s.lane, pk, 0, o.wq.work.p + 1, wn, &o.wjob);
+            s.tr.tick("  witness commitment enqueued");
+            o.folded = true;
+            o.folded_slot.sharded = o.wjob.sharded;
+            o.folded_slot.result = g1_xyzz_identity();
+        }
     }
-    commit_flush(ctx);  // both opening points: up to four bucket stages, one launch
+    commit_flush(ctx);  // both opening points: two bucket stages (four when the shifted witnesses are jobs of their own), one launch
     s.tr.tick("open: bucket stages enqueued");
     // hiding terms of the two witnesses and the random evaluations: host work that does not depend on the MSMs in flight
     G1XYZZ hide[2];
@@ -2068,14 +2114,16 @@ std::vector<PcProof> open_combinations(swm_ctx* ctx, const swm_pk& pk, ProveStat
                 pps[pi].random_v = fp_add(pps[pi].random_v, host_poly_eval(o.shifted_r, o.point));
         }
     }
-    commit_gather(ctx, {&po[0].wjob, po[0].sjobs.empty() ? nullptr : &po[0].sjobs[0], &po[1].wjob,
-                        po[1].sjobs.empty() ? nullptr : &po[1].sjobs[0]});
+    // sharded proving: the openings' exchange is one record of four partial sums per rank, whichever way a point's witness was
+    // computed: a folded point's second sum is the identity (192 bytes; the record's size does not depend on the key)
+    auto second = [](PointOpen& o) { return !o.sjobs.empty() ? &o.sjobs[0] : o.folded ? &o.folded_slot : nullptr; };
+    commit_gather(ctx, {&po[0].wjob, second(po[0]), &po[1].wjob, second(po[1])});
     G1XYZZ wit[2];
     G1Affine wit_aff[2];
     for (int pi = 0; pi < 2; pi++) {
         PointOpen& o = po[pi];
         wit[pi] = commit_wait(ctx, &o.wjob);
-        for (size_t i = 0; i < o.shifted_terms.size(); i++) g1_add(wit[pi], commit_wait(ctx, &o.sjobs[i]));
+        for (AsyncMsm& sj : o.sjobs) g1_add(wit[pi], commit_wait(ctx, &sj));
         g1_add(wit[pi], hide[pi]);
     }
     g1_to_affine_batch(wit, 2, wit_aff);
