@@ -2245,6 +2245,19 @@ static int msm_shape(swm_ctx* ctx, size_t n, const MsmTable& tab, int lane, bool
     return SWM_OK;
 }
 
+// SWM_TRACE: one line per MSM with the decisions above — which schedule, which sort, which geometry (tests/test_gpu_msm_schedules.py
+// holds every case to the schedule it names).  c / c_top: widths of the widest and of the top window; fb0 / nbins0 and fb_top /
+// nbins_top: the bin plan of the first and of the top window of a two-level sort (0 otherwise).
+static void msm_trace_shape(size_t n, const MsmShape& s) {
+    const unsigned top = s.pl.nwin - 1;
+    fprintf(stderr,
+            "[swm] msm shape: n=%zu flat=%d te=%d lat=%d two_level=%d c=%u c_top=%u nwin=%u SEG=%u big_nseg=%u flat_fb=%u flat_bins=%u "
+            "fb0=%u nbins0=%u fb_top=%u nbins_top=%u\n",
+            n, (int)s.flat, (int)s.te, (int)s.lat, (int)s.two_level, (unsigned)s.pl.c[0], (unsigned)s.pl.c[top], s.pl.nwin, s.SEG,
+            s.big_nseg, s.flat_fb, s.flat_bins, s.two_level ? (unsigned)s.bp.fb[0] : 0u, s.two_level ? (unsigned)s.bp.nbins[0] : 0u,
+            s.two_level ? (unsigned)s.bp.fb[top] : 0u, s.two_level ? (unsigned)s.bp.nbins[top] : 0u);
+}
+
 // ---- scratch of a job
 // The block a job zeroes before its sort (one fill, per result slot), as word offsets: hist [NB + 1] entries per bucket | cursor
 // [NB + 1] (msm_scatter) | big_count [4]: oversized buckets, the two status words (msm_digits), segments that hold entries (the
@@ -2594,6 +2607,8 @@ int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine*
     SWM_TRY(msm_launch_lazy_tail(ctx, false));
     MsmShape s;
     SWM_TRY(msm_shape(ctx, n, tab, lane, defer_tail, &s));
+    static const bool trace_shape = env_flag("SWM_TRACE");
+    if (trace_shape) msm_trace_shape(n, s);
     ctx->stat_msm_digits += s.total;
     const MsmZeroLayout z = msm_zero_layout(s);
     const MsmSortGeom geom{z.words, s.nseg_max, s.SEG, s.big_nseg, s.flat_bins};

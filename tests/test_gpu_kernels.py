@@ -133,6 +133,9 @@ def test_msm_golden(ctx, orc):
 
 @pytest.mark.parametrize("log_n", [10, 13, 16, 17, 18, 19])
 def test_msm_vs_oracle(ctx, orc, log_n):
+    """Schedule today: swm_srs_upload gives each of these sets a twisted Edwards table (c = lg n + 2 up to 2^14 points, lg n + 1
+    above), so every call runs the FLAT schedule on TE rows — the low-latency variant up to 2^17, the throughput variant
+    (n >= 262144) at 2^18 and 2^19.  The per-window schedule and the XYZZ rows are tests/test_gpu_msm_schedules.py."""
     from pyref.prng import fr_array
     n = 1 << log_n
     g = golden("msm.json")
@@ -197,7 +200,10 @@ def test_msm_empty_and_single(ctx, orc):
 
 
 def test_msm_pathological_buckets(ctx, orc):
-    """All scalars equal / all ones at 2^16: one bucket per window holds every point (oversized-bucket path)."""
+    """All scalars equal / all ones at 2^16.  Schedule today: flat, TE rows (c = 17), low-latency variant — the windows share one
+    bucket set, so each distinct digit of the scalar is one bucket of 2^16 entries per window that has it: many-segment buckets
+    written by the whole workgroup of msm_flat_bin_sort, their bins placed in HBM, folded by msm_big_bucket_sum.  (The per-window
+    sort's oversized-bucket fallback that this test was written for: tests/test_gpu_msm_schedules.py.)"""
     from pyref.prng import fr_array
     n = 1 << 16
     G = orc.points_to_mont([_pt(golden("g1.json")["generator"])])
@@ -227,9 +233,11 @@ def test_msm_edge_sizes_and_scalars(ctx, orc):
 
 
 def test_msm_structured_2_20(ctx, orc):
-    """Full-size schedule (c = 16, 128-point segments) on the inputs that stress it: every point in one bucket per
-    window (closed form: bases are [tau^i]G, so MSM(s, s, ..) = [s (tau^n - 1)/(tau - 1)]G) and the 25 % zeros /
-    25 % ones / 50 % uniform mix of SURVEY.md §8d against the CPU oracle."""
+    """Full size (2^20 points) on the inputs that stress the sort: every point in one bucket per window (closed form: bases are
+    [tau^i]G, so MSM(s, s, ..) = [s (tau^n - 1)/(tau - 1)]G) and the 25 % zeros / 25 % ones / 50 % uniform mix of SURVEY.md §8d
+    against the CPU oracle.  Schedule today: flat, TE rows, table width c = 20 (13 windows on one set of 2^19 buckets), throughput
+    variant with 128-point segments — not the per-window c = 16 plan this test was written for (that one, at the sizes where it
+    engages: tests/test_gpu_msm_schedules.py)."""
     from pyref.prng import fr_array
     n = 1 << 20
     tau = h2i(golden("msm.json")["tau"])
@@ -329,7 +337,9 @@ def test_ntt_roundtrip_2_24_and_linearity(ctx, orc):
 
 def test_msm_infinity_bases(ctx, orc):
     """The point at infinity (x = y = 0) is a valid base (ark-ec VariableBaseMSM accepts zero bases): first, middle,
-    last and only position of a bucket, at a size where whole segments run through the 28-bit fast path."""
+    last and only position of a bucket.  Schedule today: both set sizes carry TE tables (4096 points: c = 14; 2^17: c = 18), so
+    the full-length calls and the 64-point call at an offset run the flat schedule on TE rows, low-latency variant; the one-point
+    set has no table and runs the per-window schedule."""
     from pyref.prng import fr_array
     g = golden("msm.json")
     G = orc.points_to_mont([_pt(golden("g1.json")["generator"])])
@@ -390,7 +400,8 @@ def test_msm_rejects_non_canonical_scalars(ctx, orc):
 
 
 def test_msm_vs_oracle_2_22(ctx, orc):
-    """BASELINE configs[3] size: 2^22 points, uniform scalars, bit-exact against the C oracle (all host threads)."""
+    """BASELINE configs[3] size: 2^22 points, uniform scalars, bit-exact against the C oracle (all host threads).  Schedule today:
+    flat, TE rows, c = 20, throughput variant; the only case of this file with more than 1024 coarse bins (msm_flat_scan_bins<4>)."""
     from pyref.prng import fr_array
     n = 1 << 22
     G = orc.points_to_mont([_pt(golden("g1.json")["generator"])])
@@ -492,7 +503,7 @@ def test_msm_table_schedule_offsets_and_shapes(ctx, orc):
     """A resident base set with precomputed-window tables: MSMs at an offset, of uneven length, with structured scalars,
     through the flat schedule (60000 points: the low-latency variant with its lane-group fold of multi-segment buckets)
     and — on the same set — through the per-window schedule that MSMs too small for the shared bucket set keep
-    (700 points, read from the first table row)."""
+    (700 points, read from the first table row).  Schedule today: TE table of width c = 18, flat from 2^(c - 8) = 1024 points."""
     from pyref.prng import fr_array
     n = 1 << 17
     G = orc.points_to_mont([_pt(golden("g1.json")["generator"])])
@@ -539,7 +550,8 @@ def test_msm_small_sets_low_latency_schedule(ctx, orc, n):
 
 
 def test_msm_uniform_2_20_vs_oracle(ctx, orc):
-    """The headline MSM size against the C restatement of VariableBaseMSM (2^19 and 2^22 are covered above)."""
+    """The headline MSM size against the C restatement of VariableBaseMSM (2^19 and 2^22 are covered above).  Schedule today:
+    flat, TE rows, c = 20, throughput variant."""
     from pyref.prng import fr_array
     n = 1 << 20
     G = orc.points_to_mont([_pt(golden("g1.json")["generator"])])
