@@ -61,8 +61,7 @@ void drain_streams(swm_ctx* ctx) {
 int scratch(swm_ctx* ctx, const char* name, size_t bytes, void** out) {
     DevBuf& b = ctx->scratch[name];
     if (b.cap < bytes) {
-        static const bool trace = env_flag("SWM_TRACE");
-        if (trace) fprintf(stderr, "[swm scratch] %s grows %zu -> %zu%s\n", name, b.cap, bytes, b.p ? " (all streams synchronised)" : "");
+        if (sw(SW_TRACE) >= 1) fprintf(stderr, "[swm scratch] %s grows %zu -> %zu%s\n", name, b.cap, bytes, b.p ? " (all streams synchronised)" : "");
         if (b.p) {
             // in-flight kernels — on this stream or on one of the MSM stage streams — may still read the old buffer
             SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -97,8 +96,7 @@ int pool_alloc(swm_ctx* ctx, size_t bytes, void** out, size_t* cap) {
         ctx->pool.erase(it);
         return SWM_OK;
     }
-    static const bool trace = env_flag("SWM_TRACE");
-    if (trace) fprintf(stderr, "[swm pool] miss: hipMalloc(%zu) (%zu cached blocks)\n", bytes, ctx->pool.size());
+    if (sw(SW_TRACE) >= 1) fprintf(stderr, "[swm pool] miss: hipMalloc(%zu) (%zu cached blocks)\n", bytes, ctx->pool.size());
     hipError_t e = hipMalloc(out, bytes);
     if (e != hipSuccess) {
         // release cached blocks and retry once
@@ -205,7 +203,7 @@ RcclApi& rccl() {
     static RcclApi api = [] {
         RcclApi a;
         void* h = nullptr;
-        if (const char* forced = swm::env_path("SWM_RCCL_PATH")) {
+        if (const char* forced = swm::sw_path(swm::SW_RCCL_PATH)) {
             h = dlopen(forced, RTLD_NOW | RTLD_GLOBAL);
             a.how = "SWM_RCCL_PATH";
             if (!h) {
@@ -308,7 +306,7 @@ int shard_alltoall_dev(swm_ctx* ctx, const void* d_send, void* d_recv, size_t by
     ctx->stat_exchange_bytes += bytes_per_peer * (world - 1);
     // (a world of one normally copies; with SWM_SHARD_FORCE — the one-GPU test hook of the RCCL path — the communicator's
     // single rank sends to itself, which a grouped ncclSend / ncclRecv pair allows)
-    if (world <= 1 && !(ctx->rccl_comm && env_flag("SWM_SHARD_FORCE"))) {
+    if (world <= 1 && !(ctx->rccl_comm && sw(SW_SHARD_FORCE))) {
         SWM_HIP(ctx, hipMemcpyAsync(d_recv, d_send, bytes_per_peer, hipMemcpyDeviceToDevice, ctx->stream));
         return SWM_OK;
     }
@@ -317,7 +315,7 @@ int shard_alltoall_dev(swm_ctx* ctx, const void* d_send, void* d_recv, size_t by
     // library those tools build with -DSWM_MEASURE_HOOKS, never into the shipped one): ONE context plays rank R of G and every
     // slot of a device exchange receives this rank's own chunk by a device copy — wrong values, the right amount of work on this
     // rank.  The context remembers that an emulated exchange ran (the prover then skips its satisfiability checks).
-    static const bool emulate = env_flag("SWM_SHARD_EMULATE");
+    static const bool emulate = sw(SW_SHARD_EMULATE) != 0;
     if (emulate && !ctx->rccl_comm) {
         ctx->emulated_exchange = true;
         // (slot p receives the chunk ROTATED by a p-dependent number of elements: G identical chunks would make every polynomial
@@ -361,12 +359,12 @@ int shard_allgather_dev(swm_ctx* ctx, const void* d_send, size_t bytes, void* d_
     const unsigned world = ctx->shard_world;
     ctx->stat_exchanges++;
     ctx->stat_exchange_bytes += bytes;
-    if (world <= 1 && !(ctx->rccl_comm && env_flag("SWM_SHARD_FORCE"))) {
+    if (world <= 1 && !(ctx->rccl_comm && sw(SW_SHARD_FORCE))) {
         SWM_HIP(ctx, hipMemcpyAsync(d_recv, d_send, bytes, hipMemcpyDeviceToDevice, ctx->stream));
         return SWM_OK;
     }
 #ifdef SWM_MEASURE_HOOKS
-    static const bool emulate = env_flag("SWM_SHARD_EMULATE");
+    static const bool emulate = sw(SW_SHARD_EMULATE) != 0;
     if (emulate && !ctx->rccl_comm) {
         ctx->emulated_exchange = true;
         for (unsigned p = 0; p < world; p++) {  // (rotated per slot, as in shard_alltoall_dev)

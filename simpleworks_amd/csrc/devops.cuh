@@ -825,7 +825,7 @@ inline void sample_fr_bulk(swm_ctx* ctx, ChaChaRng& rng, Fr* out, size_t need, b
         size_t have = 0, unc = 0;
         uint32_t* d_base = reinterpret_cast<uint32_t*>(dev + 2 * slot_bytes);
         hip_check(ctx, zero_fill_async(d_base, 4, cs), "clear");  // (the runtime's fill kernel waited 2 ms beside round 1's accumulations: fill.cuh)
-        static const bool trace = env_flag("SWM_TRACE");
+        static const bool trace = sw(SW_TRACE) >= 1;
         static constexpr bool count_all = false;  // (true: the r02 - r04 behaviour, every run counted on the host: + 3.4 ms at 2^20, r05)
         double t_cb = 0, t_count = 0, t_wait = 0;
         int readbacks = 0;
@@ -966,7 +966,7 @@ inline void sample_fr_bulk(swm_ctx* ctx, ChaChaRng& rng, Fr* out, size_t need, b
         size_t m = (size_t)((double)want / 0.58 * 1.02) + 2048;
         // test hook: only as many candidates as elements still missing, so that the retry branch below runs several times
         // (the acceptance rate is r / 2^253 = 0.58) — tests/test_gpu_marlin.py pins it against the sequential stream
-        if (env_flag("SWM_SAMPLE_TIGHT")) m = want;
+        if (sw(SW_SAMPLE_TIGHT)) m = want;
         DVec cand(ctx, m);
         DBuf<uint32_t> flag(ctx, m), rank(ctx, m), last(ctx, 1);
         ChaChaKey key;

@@ -403,7 +403,7 @@ inline bool pairing_check(const VerifyingKey& vk, G1Affine tw, const G1Affine& t
 // `rng` is the caller's generator (the batch_check randomiser is drawn from it, as in arkworks: after each of the two
 // openings, the second draw unused).
 inline bool verify(const VerifyingKey& vk, std::vector<Fr> public_input, const Proof& proof, ChaChaRng& rng) {
-    const bool vtrace = env_flag("SWM_TRACE");
+    const bool vtrace = sw(SW_TRACE) >= 1;
     auto vnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double vt0 = vnow();
     auto vmark = [&](const char* what) {

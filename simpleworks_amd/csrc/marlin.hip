@@ -10,7 +10,6 @@
 //   * only the three gamma-powers KZG hiding needs are generated at setup (arkworks generates max_degree + 2).
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>  // environ
 #include <algorithm>
 #include <chrono>
 #include <functional>
@@ -378,16 +377,6 @@ uint64_t ahp_max_degree(uint64_t num_constraints, uint64_t num_variables, uint64
 }
 
 // ================================================================================================ commitments
-// MSM of a device coefficient vector against SRS powers starting at `offset` -> host XYZZ (synchronous form)
-G1XYZZ commit_dev(swm_ctx* ctx, const swm_pk& pk, size_t offset, const Fr* coeffs, size_t n) {
-    if (n == 0) return g1_xyzz_identity();
-    const G1Affine *b, *b28;
-    MsmTable tab;
-    pk.bases_at(offset, n, &b, &b28, &tab);
-    G1XYZZ r;
-    rc_check(ctx, msm_run(ctx, b, b28, coeffs, n, 1, &r, MsmInfMask(), tab));
-    return r;
-}
 // One proof over G ranks only works when every rank takes the SAME decisions about how commitments are split and which
 // rounds run on a rank's share: those depend on state that is local to a rank — whether its key has window tables (decided
 // by the free HBM the rank saw, msm_install_bases), their widths, the experiment switches of its process.  A rank that
@@ -397,33 +386,19 @@ G1XYZZ commit_dev(swm_ctx* ctx, const swm_pk& pk, size_t offset, const Fr* coeff
 void shard_agree(swm_ctx* ctx, const swm_pk& pk) {
     if (ctx->shard_world <= 1) return;
     struct Rec {
-        uint32_t tab_c, shtab_c, te, switches, n_powers_lo, n_shifted_lo, world, env_hash;
+        uint32_t tab_c, shtab_c, te, reserved, n_powers_lo, n_shifted_lo, world, env_hash;
     } mine;
-    auto on = [](const char* name) { return env_flag(name) ? 1u : 0u; };
     mine.tab_c = pk.tab_c;
     mine.shtab_c = pk.shtab_c;
     mine.te = (pk.d_powers_te ? 1u : 0u) | (pk.d_shifted_te ? 2u : 0u);
-    // bits 8 ..: the block size of the block-cyclic split as the process sets it (commit_enqueue clamps it by the polynomial's
-    // length, the same on every rank): two ranks with different blocks would cover some coefficients twice and others never
-    const unsigned blk = (unsigned)env_switch("SWM_SHARD_BLOCK_LOG", 12, 0, 20);
-    mine.switches = on("SWM_SHARD_BUCKETS") | on("SWM_SHARD_RANGE") << 1 | on("SWM_SHARD_R1_OFF") << 2 | on("SWM_SHARD_R2_OFF") << 3 |
-                    on("SWM_MSM_NO_TABLE") << 4 | blk << 8;
+    mine.reserved = 0;
     mine.n_powers_lo = (uint32_t)pk.n_powers;
     mine.n_shifted_lo = (uint32_t)pk.n_shifted;
     mine.world = ctx->shard_world;
-    // every other switch that shapes the split or the schedule (SWM_SHARD_*, SWM_MSM_*: table schedule thresholds, lane and
-    // segment choices ...), as one word: FNV-1a over the sorted NAME=value strings.  Schedule-only switches would not break a
-    // proof, but ranks that differ in them were not meant to: refused alike
-    {
-        std::vector<std::string> kv;
-        for (char** e = environ; e && *e; e++)
-            if (!strncmp(*e, "SWM_SHARD_", 10) || !strncmp(*e, "SWM_MSM_", 8)) kv.emplace_back(*e);
-        std::sort(kv.begin(), kv.end());
-        uint32_t h = 2166136261u;
-        for (const std::string& x : kv)
-            for (size_t i = 0; i <= x.size(); i++) h = (h ^ (uint8_t)(i < x.size() ? x[i] : 0)) * 16777619u;
-        mine.env_hash = h;
-    }
+    // every switch that can change a result, the split or the schedule, as this process acts on it (two ranks with different blocks
+    // of the block-cyclic split would cover some coefficients twice and others never; ranks that differ in a schedule-only switch
+    // were not meant to: refused alike)
+    mine.env_hash = switch_fingerprint();
     std::vector<Rec> all(ctx->shard_world);
     rc_check(ctx, shard_exchange(ctx, &mine, sizeof(Rec), all.data()));
     for (unsigned g = 0; g < ctx->shard_world; g++)
@@ -432,9 +407,8 @@ void shard_agree(swm_ctx* ctx, const swm_pk& pk) {
                               "sharded proving: rank " + std::to_string(g) + " and rank 0 disagree on the key's window tables (widths " +
                                   std::to_string(all[g].tab_c) + "/" + std::to_string(all[g].shtab_c) + " vs " + std::to_string(all[0].tab_c) + "/" +
                                   std::to_string(all[0].shtab_c) + ", forms " + std::to_string(all[g].te) + " vs " + std::to_string(all[0].te) +
-                                  ") or on the sharding switches (" + std::to_string(all[g].switches) + "/" + std::to_string(all[g].env_hash) + " vs " +
-                                  std::to_string(all[0].switches) + "/" + std::to_string(all[0].env_hash) +
-                                  "): every rank must build its key with the same free memory and the same SWM_SHARD_* / SWM_MSM_* environment");
+                                  ") or on the path and sharding switches of switches.h (fingerprint " + std::to_string(all[g].env_hash) + " vs " +
+                                  std::to_string(all[0].env_hash) + "): every rank must build its key with the same free memory and the same switches");
 }
 // asynchronous form: alternates between the two MSM lanes of the context
 // With swm_set_msm_sharding active the context only takes its own point range of every MSM and the partial sums are
@@ -456,7 +430,7 @@ void commit_enqueue(swm_ctx* ctx, int* lane, const swm_pk& pk, size_t offset, co
     size_t lo = 0, hi = n;
     out->have_result = false;
     out->result = g1_xyzz_identity();  // an empty range (n = 0, or a rank's empty shard) contributes the identity
-    const bool force_exchange = env_flag("SWM_SHARD_FORCE");  // test hook: exchange with a world of one
+    const bool force_exchange = sw(SW_SHARD_FORCE) != 0;  // test hook: exchange with a world of one
     out->sharded = ctx->shard_world > 1 || (force_exchange && (ctx->rccl_comm || ctx->shard_allgather));
     // Split of a replicated polynomial's commitment over the ranks (every rank holds all n coefficients):
     //  * CYCLIC (default, table schedule): rank g takes the coefficients g, g + G, ... (strided scalars, table rows g + G j).
@@ -467,8 +441,8 @@ void commit_enqueue(swm_ctx* ctx, int* lane, const swm_pk& pk, size_t offset, co
     //    AND bucket stage shrink with G.  Measured per rank on one GPU (tools/ubench/shard_emulate.py): it balances two ranks
     //    and loses at eight (1/8 of the buckets at full depth are too few lanes for the accumulation), so it is not the default.
     // (The switches are read per call: tests flip them.)
-    const bool by_bucket = env_flag("SWM_SHARD_BUCKETS");
-    const bool by_range = env_flag("SWM_SHARD_RANGE");
+    const bool by_bucket = sw(SW_SHARD_BUCKETS) != 0;
+    const bool by_range = sw(SW_SHARD_RANGE) != 0;
     const bool table_split = out->sharded && ctx->shard_world > 1 && n && msm_flat_applies(tab, n) && tab.contiguous();
     size_t first = 0, count = n;   // scalars coeffs[first + map(i)], i < count (map: the table's block map when the scalars are strided)
     if (table_split && by_bucket) {
@@ -481,7 +455,7 @@ void commit_enqueue(swm_ctx* ctx, int* lane, const swm_pk& pk, size_t offset, co
         // table rows are runs of 2^L x 192 B instead of every G-th row: the accumulation's gathers are sensitive to that
         // (per rank at 2^22 and G = 8: 5.4 G additions/s cyclic, 7 - 8 G/s for contiguous ranges: profiles/r04_shard_emulate.jsonl)
         const size_t G = ctx->shard_world, g = ctx->shard_rank;
-        unsigned L = (unsigned)env_switch("SWM_SHARD_BLOCK_LOG", 12, 0, 20);
+        unsigned L = (unsigned)sw(SW_SHARD_BLOCK_LOG);
         while (L > 0 && ((size_t)8 * G << L) > n) L--;
         const size_t B = (size_t)1 << L, nblocks = (n + B - 1) / B;
         const size_t mine = nblocks > g ? (nblocks - g + G - 1) / G : 0;            // blocks g, g + G, ... below nblocks
@@ -518,7 +492,7 @@ void commit_enqueue(swm_ctx* ctx, int* lane, const swm_pk& pk, size_t offset, co
     // lone waves — was the critical path; the stages of a round's jobs in ONE launch (64 workgroups each, 32 buckets per lane, all
     // resident together) share one chain latency: 2^18: 19.3 -> 17.1 ms, Merkle circuit 17.5 -> 15.1 ms (profiles/r05_*).
     // (SWM_MSM_BATCH_BELOW: the bound in points, 0 = every job keeps its own bucket stage; tests/test_gpu_switches.py)
-    static const long batch_env = env_switch("SWM_MSM_BATCH_BELOW", -1, 0, 1L << 31);
+    static const long batch_env = sw(SW_MSM_BATCH_BELOW);
     const long batch_below = batch_env >= 0 ? batch_env : (tab.any() ? (tab.te ? 1000000 : 200000) : 32768);
     if (tab.scalar_stride != 1) {
         rc_check(ctx, msm_enqueue(ctx, (*lane)++, b, b28, coeffs + first, count, 1, &out->job, MsmInfMask(),
@@ -562,7 +536,7 @@ void commit_enqueue_cyclic(swm_ctx* ctx, int* lane, const swm_pk& pk, const Fr* 
     tab.offset += rank;
     tab.blk_log = 0;
     tab.bstride = G;
-    static const long batch_env = env_switch("SWM_MSM_BATCH_BELOW", -1, 0, 1L << 31);
+    static const long batch_env = sw(SW_MSM_BATCH_BELOW);
     const long batch_below = batch_env >= 0 ? batch_env : 200000;
     rc_check(ctx, msm_enqueue(ctx, (*lane)++, b, b28, local, n_local, 1, &out->job, MsmInfMask(),
                               (long)n_local <= batch_below, tab));
@@ -738,36 +712,6 @@ __global__ void __launch_bounds__(256) srs_fixed_base(const G1Affine* __restrict
     }
     out[i] = acc;
 }
-// Jacobian-free batch normalisation: 16 consecutive points per lane, prefix products parked in `pref`
-static constexpr int NORM_CHUNK = 16;
-__global__ void __launch_bounds__(256) srs_normalize(const G1XYZZ* __restrict__ in, size_t n, Fq* __restrict__ pref,
-                                                     G1Affine* __restrict__ out) {
-    size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    size_t lo = t * NORM_CHUNK;
-    if (lo >= n) return;
-    size_t hi = lo + NORM_CHUNK < n ? lo + NORM_CHUNK : n;
-    Fq acc = fp_one<Fq>();
-    for (size_t i = lo; i < hi; i++) {
-        pref[i] = acc;
-        if (!fp_is_zero(in[i].zz)) acc = fp_mul(acc, fp_mul(in[i].zz, in[i].zzz));
-    }
-    Fq inv = fp_inv(acc);
-    for (size_t i = hi; i-- > lo;) {
-        G1XYZZ p = in[i];
-        G1Affine a;
-        if (fp_is_zero(p.zz)) {
-            a.x = fp_zero<Fq>();
-            a.y = fp_zero<Fq>();
-        } else {
-            Fq zi = fp_mul(inv, pref[i]);
-            inv = fp_mul(inv, fp_mul(p.zz, p.zzz));
-            a.x = fp_mul(p.x, fp_mul(zi, p.zzz));
-            a.y = fp_mul(p.y, fp_mul(zi, p.zz));
-        }
-        out[i] = a;
-    }
-}
-
 G1Affine g1_rand(ChaChaRng& rng) {
     static const uint32_t cof[4] = SWM_G1_COFACTOR;
     for (;;) {
@@ -866,9 +810,7 @@ swm_srs* universal_setup(swm_ctx* ctx, size_t nc, size_t nv, size_t nnz, ChaChaR
     hip_check(ctx, hipMalloc((void**)&srs->d_powers, n * sizeof(G1Affine)), "hipMalloc(srs)");
     LAUNCHX(ctx, "srs_fixed_base", srs_fixed_base, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d_tab.p, bt.view(),
                n, d_x.p);
-    size_t nt = (n + NORM_CHUNK - 1) / NORM_CHUNK;
-    LAUNCHX(ctx, "srs_normalize", srs_normalize, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, d_x.p, n, d_pref.p,
-               srs->d_powers);
+    rc_check(ctx, msm_normalize_run(ctx, d_x.p, n, d_pref.p, srs->d_powers));
     hip_check(ctx, hipStreamSynchronize(ctx->stream), "sync");
     return srs.release();
 }
@@ -1072,8 +1014,7 @@ struct PhaseTrace {
     bool host_only;  // SWM_TRACE=2: host timestamps only (no synchronisation: the schedule is left undisturbed)
     std::chrono::steady_clock::time_point start;
     explicit PhaseTrace(swm_ctx* c)
-        : ctx(c), on(env_switch("SWM_TRACE", 0, 0, 2) != 0), t0(std::chrono::steady_clock::now()),
-          host_only(env_switch("SWM_TRACE", 0, 0, 2) == 2), start(t0) {}
+        : ctx(c), on(sw(SW_TRACE) >= 1), t0(std::chrono::steady_clock::now()), host_only(sw(SW_TRACE) == 2), start(t0) {}
     void tick(const char* what) {
         if (!host_only) return;
         fprintf(stderr, "[swm host] %-34s at %8.3f ms\n", what,
@@ -1148,8 +1089,8 @@ ShardPlan shard_plan(swm_ctx* ctx, const swm_pk& pk) {
     sp.rank = ctx->shard_rank;
     while ((1u << sp.slog_g) < sp.SG) sp.slog_g++;
     const size_t M = 4 * pk.H;
-    sp.r1 = shard_fits(sp.SG, sp.slog_g, pk.logH) && !env_flag("SWM_SHARD_R1_OFF") && commit_cyclic_possible(ctx, pk, pk.H / sp.SG);
-    sp.r2 = shard_fits(sp.SG, sp.slog_g, pk.logH + 2) && !env_flag("SWM_SHARD_R2_OFF");
+    sp.r1 = shard_fits(sp.SG, sp.slog_g, pk.logH) && !sw(SW_SHARD_R1_OFF) && commit_cyclic_possible(ctx, pk, pk.H / sp.SG);
+    sp.r2 = shard_fits(sp.SG, sp.slog_g, pk.logH + 2) && !sw(SW_SHARD_R2_OFF);
     sp.r3 = sp.r2 && shard_fits(sp.SG, sp.slog_g, pk.logB) && pk.K % sp.SG == 0;
     sp.sm = pk.H / (sp.SG ? sp.SG : 1);
     sp.Mloc = sp.r2 ? M / sp.SG : M;
@@ -1365,8 +1306,7 @@ void begin_mask(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
     // (mask_fix): its term [c_0] g is one scalar multiplication on the host.  A commitment is a sum over coefficients, so
     // the pieces add up to the same group element: same bytes (test_callback_rng_reproduces_golden_bytes).  SWM_MASK_PIECES=1:
     // one piece (r02 - r04).  Sharded proofs keep one piece (their commitments are split over the ranks already).
-    static const unsigned mask_pieces_env = (unsigned)env_switch("SWM_MASK_PIECES", 3, 1, 3);
-    s.mask_pieces = s.mask_late && ctx->shard_world <= 1 && s.H >= 4096 ? mask_pieces_env : 1u;
+    s.mask_pieces = s.mask_late && ctx->shard_world <= 1 && s.H >= 4096 ? (unsigned)sw(SW_MASK_PIECES) : 1u;
     if (s.mask_late) sample_fr_ext_mark(ctx);  // the transfers of the late draw only wait for what precedes the allocation
     else draw_mask(ctx, pk, s);
 }
@@ -1518,7 +1458,7 @@ void round2_prework(swm_ctx* ctx, ProveState& s) {
     const uint64_t H = s.H, X = s.X;
     // single-GPU rounds (the sharded ones and the r(alpha, X)-by-transforms test hook keep the 4|H| domain)
     s.cosets = SWM_OUTER_COSETS && !s.sp.r1 && !s.sp.r2 && H >= OUTER_COSETS_MIN_H && s.mask_len == 3 * H &&
-               !env_flag("SWM_RALPHA_TRANSFORMS");
+               !sw(SW_RALPHA_TRANSFORMS);
     auto on_domain = [&](const Fr* coeffs, size_t n) { return s.cosets ? on_cosets12(ctx, s, coeffs, n) : on_mul_domain(ctx, s, coeffs, n); };
     s.e_za = on_domain(s.za_poly.p, H + 1);
     s.e_zb = on_domain(s.zb_poly.p, H + 1);
@@ -1579,7 +1519,7 @@ void r_alpha(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
     {
         Fr a4h = alpha;
         for (unsigned i = 0; i < s.logM; i++) a4h = fp_sqr(a4h);
-        s.ra_closed_form = !fp_is_one(a4h) && !env_flag("SWM_RALPHA_TRANSFORMS");  // (test hook: the path of the 2^-231 case)
+        s.ra_closed_form = !fp_is_one(a4h) && !sw(SW_RALPHA_TRANSFORMS);  // (test hook: the path of the 2^-231 case)
     }
     if (!s.ra_closed_form) return r_alpha_on_h(ctx, pk, s);
     if (s.sp.r2) {
@@ -2133,8 +2073,7 @@ std::vector<PcProof> open_combinations(swm_ctx* ctx, const swm_pk& pk, ProveStat
 
 std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* cs, ChaChaRng& zk, bool uncompressed = false) {
     PhaseTrace tr(ctx);
-    static const bool proof_marks = env_flag("SWM_TRACE") || env_flag("SWM_PROOF_MARKS");
-    if (proof_marks) hipLaunchKernelGGL(swm_proof_begin, dim3(1), dim3(1), 0, ctx->stream);
+    if (sw(SW_TRACE) >= 1 || sw(SW_PROOF_MARKS)) hipLaunchKernelGGL(swm_proof_begin, dim3(1), dim3(1), 0, ctx->stream);
     ProveShape shape = prove_shape(cs, pk);
     tr.mark("pad_and_square");
     shard_agree(ctx, pk);  // one proof over several ranks: all of them split the work the same way, or none starts
@@ -2148,8 +2087,7 @@ std::vector<uint8_t> prove_impl(swm_ctx* ctx, const swm_pk& pk, const swm_r1cs* 
         swm_ctx* c;
         ~PipeMinScope() { c->msm_pipe_min = 0; }
     } pipe_scope{ctx};
-    static const unsigned one_stream_log = (unsigned)env_switch("SWM_PROVE_ONE_STREAM_LOG", 19, 0, 47);
-    ctx->msm_pipe_min = pk.logH <= one_stream_log ? ~(size_t)0 : 0;
+    ctx->msm_pipe_min = pk.logH <= (unsigned)sw(SW_PROVE_ONE_STREAM_LOG) ? ~(size_t)0 : 0;
 
     // ================= round 1
     // The zero-knowledge draws of round 1 do not depend on the witness: rho_w, rho_a, rho_b, then the mask polynomial

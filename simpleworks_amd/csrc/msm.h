@@ -61,13 +61,14 @@ int msm_table_build(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsigned c
 // their checked deserialisation; msm_subgroup_check establishes it for caller-supplied sets.  *out stays null (and the
 // call returns SWM_OK) when a point has no image under the map — the caller then keeps the XYZZ table.
 int msm_table_build_te(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsigned c, G1TE** out);
+// out[i] = in[i] as an affine point (the identity becomes (0, 0)), by the table builder's batch normalisation on the context's
+// stream; pref: n field elements of scratch.  Profiled as "srs_normalize" (its caller is the universal setup).
+int msm_normalize_run(swm_ctx* ctx, const G1XYZZ* in, size_t n, Fq* pref, G1Affine* out);
 // *ok = every point is the identity (0, 0) or lies on the curve and in the prime-order subgroup ([r]P = O)
 int msm_subgroup_check(swm_ctx* ctx, const G1Affine* d_points, size_t n, bool* ok);
 // scaled copy + the best table that fits for a resident base set (see msm.hip); frees nothing of the caller's
 int msm_install_bases(swm_ctx* ctx, const G1Affine* d_points, size_t n, bool in_subgroup, G1Affine** d28, G1TE** te, unsigned* c,
                       uint32_t* d_inf_mask = nullptr);
-// SWM_MSM_TE=0 keeps the XYZZ tables everywhere (A/B measurements)
-bool msm_te_enabled();
 // HBM left for a table of `bytes` bytes? (hipMemGetInfo, keeping a quarter of the free memory for the prover's temporaries)
 bool msm_table_fits(size_t bytes);
 

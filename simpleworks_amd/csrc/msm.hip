@@ -80,13 +80,8 @@ WinLayout msm_table_layout(unsigned c) {
     L.boff[L.nwin] = L.NB;
     return L;
 }
-// SWM_MSM_TABLE_C: the width for every base set of the process (8 .. 22; tests/test_gpu_switches.py proves with 16 and 18), 0 when unset
-static unsigned msm_forced_table_width() {
-    static const unsigned forced = (unsigned)env_switch("SWM_MSM_TABLE_C", 0, 8, 22);
-    return forced;
-}
 unsigned msm_table_width(size_t n_bases) {
-    if (const unsigned forced = msm_forced_table_width()) return forced;
+    if (const unsigned forced = (unsigned)sw(SW_MSM_TABLE_C)) return forced;  // one width for every base set of the process
     if (n_bases < 512) return 0;  // tiny base sets keep the per-window schedule
     // measured r02 (prove() at 2^10 .. 2^20 constraints, base sets of 3 x that): two bits above the size of the base
     // set up to 2^15 points — 4 .. 10 points per bucket for the MSMs of a proof, which keeps the accumulation chains
@@ -769,6 +764,7 @@ __global__ void __launch_bounds__(256) msm_table_shift(const G1Affine* __restric
     for (unsigned j = 1; j < k; j++) acc = g1_dbl(acc);
     out[i] = acc;
 }
+// Jacobian-free batch normalisation: 16 consecutive points per lane, prefix products parked in `pref`
 static constexpr int TAB_NORM_CHUNK = 16;
 __global__ void __launch_bounds__(256) msm_table_normalize(const G1XYZZ* __restrict__ in, size_t n, Fq* __restrict__ pref,
                                                            G1Affine* __restrict__ out) {
@@ -1915,11 +1911,12 @@ int msm_table_build(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsigned c
 int msm_table_build_te(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsigned c, G1TE** out) {
     return msm_table_rows(ctx, d_points, n, c, true, (void**)out);
 }
-
-bool msm_te_enabled() {
-    static const bool on = env_switch("SWM_MSM_TE", 1, 0, 1) != 0;  // 0: XYZZ tables everywhere (the form of sets outside the subgroup)
-    return on;
+int msm_normalize_run(swm_ctx* ctx, const G1XYZZ* in, size_t n, Fq* pref, G1Affine* out) {
+    const unsigned grid = (unsigned)(((n + TAB_NORM_CHUNK - 1) / TAB_NORM_CHUNK + 255) / 256);
+    SWM_LAUNCH(ctx, "srs_normalize", msm_table_normalize, dim3(grid), dim3(256), 0, in, n, pref, out);
+    return SWM_OK;
 }
+
 bool msm_table_fits(size_t bytes) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return true;  // cannot tell: let the allocation decide
@@ -1954,17 +1951,17 @@ int msm_install_bases(swm_ctx* ctx, const G1Affine* d_points, size_t n, bool in_
     // replicated item: the table is as many bits narrower as the width rule gives for the rank's share of the set, at most
     // log2(G) - 1.  Measured per rank (tools/ubench/shard_emulate.py, same box): 2^20 constraints, G = 8: c = 20 / 18 / 17 ->
     // 23.7 / 20.9 / 20.9 ms; G = 4: flat; 2^22 constraints (1.5 M points per rank and more): 20 stays best (18: + 3 %).
-    if (*c > 12 && ctx->shard_world >= 4 && !msm_forced_table_width()) {
+    if (*c > 12 && ctx->shard_world >= 4 && !sw(SW_MSM_TABLE_C)) {
         unsigned lg = 0;
         while ((2u << lg) <= ctx->shard_world) lg++;
         const unsigned share = msm_table_width(std::max<size_t>(n / ctx->shard_world, 512));
         const unsigned delta = share && share < *c ? std::min(*c - share, lg - 1) : 0;
         *c = std::max(12u, *c - delta);
     }
-    if (env_flag("SWM_TRACE")) fprintf(stderr, "[swm] base set of %zu points: table width %u (world %u)\n", n, *c, ctx->shard_world);
+    if (sw(SW_TRACE) >= 1) fprintf(stderr, "[swm] base set of %zu points: table width %u (world %u)\n", n, *c, ctx->shard_world);
     if (*c && (uint64_t)n * msm_table_windows(*c) >= (1ull << 31)) *c = 0;  // the sort addresses table rows with 31 bits
     const unsigned W = *c ? msm_table_windows(*c) : 0;
-    if (*c && msm_te_enabled()) {
+    if (*c && sw(SW_MSM_TE)) {
         bool ok = in_subgroup;
         if (!ok) SWM_TRY(msm_subgroup_check(ctx, d_points, n, &ok));
         if (ok && msm_table_fits((size_t)W * n * sizeof(G1TE) + n * sizeof(G1Affine))) {
@@ -2033,7 +2030,7 @@ static int streams_concurrent(swm_ctx* ctx, hipStream_t x, hipStream_t y, bool* 
 // measured in r04 / r05 — every assignment slower, CHANGELOG.md — and are gone; what orders the kernels on the chip is s_setprio).
 hipError_t msm_create_stream(hipStream_t* out) { return hipStreamCreateWithFlags(out, hipStreamNonBlocking); }
 bool msm_flat_applies(const MsmTable& tab, size_t n) {
-    static const bool no_table = env_flag("SWM_MSM_NO_TABLE");  // the per-window schedule for every set (what table-less sets run)
+    static const bool no_table = sw(SW_MSM_NO_TABLE) != 0;  // the per-window schedule for every set (what table-less sets run)
     return tab.any() && !no_table && n >= ((size_t)1 << (tab.c > 8 ? tab.c - 8 : 0)) &&
            (uint64_t)tab.stride * msm_table_windows(tab.c) < (1ull << 31);
 }
@@ -2104,7 +2101,7 @@ static int msm_shape(swm_ctx* ctx, size_t n, const MsmTable& tab, int lane, bool
     // Low-latency schedule on twisted Edwards rows: every chain of the bucket stage is worked by a quad of lanes (FormTEQuad;
     // SWM_MSM_QUAD=0: one lane per chain as for large jobs): 128 chains per workgroup (512 threads), at most 64 workgroups per
     // job, bucket sets up to 2^15 (r04 sweeps, CHANGELOG.md).
-    static const bool quad_on = env_switch("SWM_MSM_QUAD", 1, 0, 1) != 0;
+    static const bool quad_on = sw(SW_MSM_QUAD) != 0;
     static constexpr unsigned quad_rb = 128u, quad_blocks = 64u, quad_maxb = 32768u;
     s.quad = s.lat && s.te && quad_on && pl.maxB <= quad_maxb;
     s.rb = s.quad ? quad_rb : 256u;
@@ -2114,7 +2111,7 @@ static int msm_shape(swm_ctx* ctx, size_t n, const MsmTable& tab, int lane, bool
     // r05, last collection: in the JOINT stage of deferred jobs (shaped by msm_joint_shape) it is worth 0.1 - 0.3 ms per mid-size
     // proof (2^16 7.2 -> 7.07, 2^18 17.2 -> 16.9, Merkle circuit 15.0 -> 14.7 ms); for the thin stages of large jobs it costs
     // 0.8 ms at 2^20 (two workgroups per CU).  SWM_MSM_LOW: 2 (default) = joint stages only, 1 = every one-lane stage, 0 = never.
-    static const long low_mode = env_switch("SWM_MSM_LOW", 2, 0, 2);
+    static const long low_mode = sw(SW_MSM_LOW);
     const bool low_on = low_mode == 1 || (low_mode == 2 && defer_tail);
     static constexpr unsigned low_blocks = 256u;
     // (joint stages of small jobs: SWM_MSM_JOINT_BLOCKS workgroups per job — with the low-LDS kernel twelve waves per CU are resident)
@@ -2355,7 +2352,7 @@ static int msm_buffers(swm_ctx* ctx, const MsmShape& s, const MsmZeroLayout& z, 
 // job takes over, or null.  Any mismatch of the shapes leaves both on the ordinary schedule.  SWM_MSM_TWIN=0: never.
 static MsmJob* msm_twin_match(const MsmJob* job, const MsmShape& s, const MsmSortGeom& geom, const void* d_scalars, size_t n, int mont,
                               const MsmInfMask& inf, const MsmTable& tab, const MsmTwin& twin, bool* lead) {
-    static const bool twin_on = env_switch("SWM_MSM_TWIN", 1, 0, 1) != 0;
+    static const bool twin_on = sw(SW_MSM_TWIN) != 0;
     // (from 2^15 points: below, a proof is a chain of launches and the follower's wait for the lead's sort costs more than its own
     // sort beside it — 2^14 constraints 3.88 -> 4.0 ms, 2^16 6.58 -> 6.49 ms, r06)
     static constexpr size_t twin_min = 32768;
@@ -2607,7 +2604,7 @@ int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine*
     SWM_TRY(msm_launch_lazy_tail(ctx, false));
     MsmShape s;
     SWM_TRY(msm_shape(ctx, n, tab, lane, defer_tail, &s));
-    static const bool trace_shape = env_flag("SWM_TRACE");
+    static const bool trace_shape = sw(SW_TRACE) >= 1;
     if (trace_shape) msm_trace_shape(n, s);
     ctx->stat_msm_digits += s.total;
     const MsmZeroLayout z = msm_zero_layout(s);
@@ -2990,24 +2987,21 @@ HostPool* host_pool_of(swm_ctx* ctx) {
         unsigned hw = std::thread::hardware_concurrency();
         unsigned want = hw > 1 ? std::min(hw - 1, hw >= 32 ? 15u : 7u) : 0u;
         unsigned ranks = std::max(1u, ctx->shard_world);
-        ranks = std::max(ranks, (unsigned)env_switch("LOCAL_WORLD_SIZE", 1, 1, 4096));  // (torchrun's: ranks that share this host's cores)
+        ranks = std::max(ranks, (unsigned)sw(SW_LOCAL_WORLD_SIZE));  // (torchrun's: ranks that share this host's cores)
         if (ranks > 1 && hw) want = std::min(want, std::max(1u, hw / ranks) - 1);
-        want = (unsigned)env_switch("SWM_POOL_WORKERS", (long)want, 0, 64);  // (diagnostic: the host fold's worker threads)
+        if (const long forced = sw(SW_POOL_WORKERS); forced >= 0) want = (unsigned)forced;  // (diagnostic: the host fold's worker threads)
         ctx->host_pool = new HostPool(want);
     }
     return ctx->host_pool;
 }
-// how long the workers poll for the fold that follows a wait (microseconds; SWM_POOL_SPIN_US, 0 = they sleep)
-static unsigned pool_spin_us() {
-    static const unsigned us = (unsigned)env_switch("SWM_POOL_SPIN_US", 1500, 0, 100000);
-    return us;
-}
+// how long the workers poll for the fold that follows a wait (microseconds, 0 = they sleep)
+static unsigned pool_spin_us() { return (unsigned)sw(SW_POOL_SPIN_US); }
 
 int msm_finish(swm_ctx* ctx, MsmJob* job, G1XYZZ* result) {
     *result = g1_xyzz_identity();
     ctx->msm_since_wait = 0;
     if (!job->active) return SWM_OK;
-    static const bool trace = env_flag("SWM_TRACE");
+    static const bool trace = sw(SW_TRACE) >= 1;
     auto tw0 = std::chrono::steady_clock::now();
     if (pool_spin_us()) host_pool_of(ctx)->arm(pool_spin_us());  // the fold follows the wait at once: the workers poll for it meanwhile
     SWM_TRY(msm_finish_wait(ctx, job));
@@ -3024,7 +3018,7 @@ int msm_finish(swm_ctx* ctx, MsmJob* job, G1XYZZ* result) {
 // per host worker (a fold is a serial chain of ~3 additions per workgroup result: four of them back to back were
 // ~0.25 ms between the last kernel of a round and its Fiat-Shamir challenge).
 int msm_finish_many(swm_ctx* ctx, MsmJob** jobs, int k, G1XYZZ* results) {
-    static const bool trace = env_flag("SWM_TRACE");
+    static const bool trace = sw(SW_TRACE) >= 1;
     ctx->msm_since_wait = 0;
     auto tw0 = std::chrono::steady_clock::now();
     std::vector<int> live;

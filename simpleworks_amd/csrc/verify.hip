@@ -150,7 +150,7 @@ G1Affine msm_affine(swm_ctx* ctx, const G1Affine* d_bases, const Fr* h_scalars, 
 void verify_batch_impl(swm_ctx* ctx, const VerifyingKey& vk, const uint64_t* public_inputs, size_t n_inputs,
                        const uint8_t* const* proofs, const size_t* lens, size_t count, bool uncompressed, ChaChaRng& rng,
                        int* ok, int* results, G1Affine* tw_out, G1Affine* tc_out) {
-    static const bool trace = env_flag("SWM_TRACE");
+    static const bool trace = sw(SW_TRACE) >= 1;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t0 = now();
     auto mark = [&](const char* what) {
