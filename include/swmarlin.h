@@ -282,6 +282,36 @@ int swm_proof_validate(const uint8_t *bytes, size_t len);
  * swm_pk_serialize with out == NULL only reports the length. */
 int swm_pk_serialize(swm_ctx *ctx, const swm_pk *pk, uint8_t *out, size_t cap, size_t *len);
 int swm_pk_deserialize(swm_ctx *ctx, const uint8_t *bytes, size_t len, swm_pk **out);
+/* The other two forms arkworks 0.3 gives every CanonicalSerialize type, for both keys (the functions above speak the first):
+ *   flags = 0                                          serialize / deserialize: compressed, checked — the functions above, byte for
+ *                                                      byte and check for check;
+ *   flags = SWM_KEY_UNCOMPRESSED                       serialize_uncompressed / deserialize_uncompressed: checked;
+ *   flags = SWM_KEY_UNCOMPRESSED | SWM_KEY_UNCHECKED   readers only: deserialize_unchecked.
+ * Anything else — unknown bits, SWM_KEY_UNCHECKED without SWM_KEY_UNCOMPRESSED or on a writer — is SWM_ERR_INVALID_ARG.  Writers
+ * with out == NULL report the length.
+ * Layout [U: ark-ec 0.3, unpinned like the rest]: the compressed layout with every point widened, nested ones included (the vk's
+ * index_comms, g, gamma_g, h, beta_h and shift powers; the committer key's powers, shifted powers and gamma powers).  G1: 96 bytes,
+ * x then y, the infinity flag in bit 6 of the last byte, the identity as (0, 1).  G2: 192 bytes, x.c0, x.c1, y.c0, y.c1, the flag in
+ * the last byte of y.c1, the identity as (0, (1, 0)).  Field elements, lengths, Option tags, labels, matrices and domains are the
+ * same bytes in both forms.  A 2^20 key grows by 48 bytes for each of its ~4.2 M points.
+ * What a reader checks per point:
+ *   uncompressed, checked   flags != 0xC0, both coordinates < q, y^2 = x^3 + b, [r]P = O.  No square root.
+ *   unchecked               flags and canonical coordinates only (arkworks refuses those too: Fp::deserialize is the same in every
+ *                           mode).  Neither the curve equation nor the subgroup test is evaluated.
+ * Every structural check (counts, index info, matrix shapes, domains), the comparison of the committer key with the embedded
+ * verifying key, and the recomputation of everything derived from the matrices run in all three modes.  The two power ranges of an
+ * uncompressed proving key are decoded on the GPU and stay there.
+ * UNCHECKED IS THE CALLER'S ASSERTION that the bytes came from this library (swm_pk_serialize_ex / swm_vk_serialize_ex) or from a
+ * checked load — a key handed back in the process that made it, or read from the process's own store.  The key is installed as
+ * lying in the prime-order subgroup, so its MSMs run on the twisted Edwards tables, whose addition law is only complete there.  A
+ * false assertion gives wrong proofs (or a verifying key that accepts nothing), never a fault: no kernel indexes memory by point
+ * data.  Bytes from anywhere else go through a checked reader. */
+#define SWM_KEY_UNCOMPRESSED 1u
+#define SWM_KEY_UNCHECKED 2u
+int swm_pk_serialize_ex(swm_ctx *ctx, const swm_pk *pk, unsigned flags, uint8_t *out, size_t cap, size_t *len);
+int swm_pk_deserialize_ex(swm_ctx *ctx, const uint8_t *bytes, size_t len, unsigned flags, swm_pk **out);
+int swm_vk_serialize_ex(const swm_vk *vk, unsigned flags, uint8_t *out, size_t cap, size_t *len);
+int swm_vk_deserialize_ex(const uint8_t *bytes, size_t len, unsigned flags, swm_vk **out);
 
 /* K3 as the reference exercises it: ConstraintSystem::is_satisfied (src/merkle_tree/simple_merkle_tree.rs:197-199):
  * A z o B z == C z on the GPU.  *ok = 1 when satisfied, else *first_bad = index of the first unsatisfied row. */
@@ -373,6 +403,13 @@ int swm_selftest_exchange(swm_ctx *ctx, const void *d_send, void *d_recv, size_t
 int swm_selftest_mul(swm_ctx *ctx, int which, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);
 /* out[i] = jacobian(a[i] (+) b[i]) with a, b affine (n x 12 limbs): exercises the mixed/XYZZ adders incl. doubling. */
 int swm_selftest_g1_add(swm_ctx *ctx, const uint64_t *a_xy, const uint64_t *b_xy, uint64_t *out_jac, size_t n);
+/* The point kernels of the uncompressed key forms (csrc/marlin.hip), one GPU lane per point, on host buffers.  Ops:
+ *   0 g1_encode_uncompressed_kernel: in = n x 12 uint64 (affine Montgomery x, y; (0, 0) = the identity), out = n x 96 bytes
+ *   1 g1_decode_uncompressed_kernel<checked>: in = n x 96 bytes, out = n x 12 uint64; *bad = the OR over all points of
+ *     1 (flags 0xC0 or a coordinate >= q), 2 (not on the curve), 4 (not in the prime-order subgroup); a refused point reads (0, 0)
+ *   2 the same, unchecked: only bit 1 can be set
+ * bad may be NULL for op 0. */
+int swm_selftest_g1_codec(swm_ctx *ctx, int op, const void *in, size_t n, void *out, unsigned *bad);
 /* Throughput probe: `iters` dependent Montgomery multiplications per thread on `threads` threads; returns ms. */
 int swm_selftest_mul_throughput(swm_ctx *ctx, int which, size_t threads, int iters, float *ms);
 /* Host pairing code of the verifier against itself (no GPU): bit k of *failed is set when identity k does not hold —

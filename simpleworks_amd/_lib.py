@@ -84,6 +84,10 @@ ABI = {
     "swm_proof_validate": (_int, [ctypes.c_void_p, _sz]),
     "swm_pk_serialize": (_int, [_vp, _vp, ctypes.c_void_p, _sz, ctypes.POINTER(_sz)]),
     "swm_pk_deserialize": (_int, [_vp, ctypes.c_void_p, _sz, ctypes.POINTER(_vp)]),
+    "swm_pk_serialize_ex": (_int, [_vp, _vp, ctypes.c_uint, ctypes.c_void_p, _sz, ctypes.POINTER(_sz)]),
+    "swm_pk_deserialize_ex": (_int, [_vp, ctypes.c_void_p, _sz, ctypes.c_uint, ctypes.POINTER(_vp)]),
+    "swm_vk_serialize_ex": (_int, [_vp, ctypes.c_uint, ctypes.c_void_p, _sz, ctypes.POINTER(_sz)]),
+    "swm_vk_deserialize_ex": (_int, [ctypes.c_void_p, _sz, ctypes.c_uint, ctypes.POINTER(_vp)]),
     "swm_r1cs_is_satisfied": (_int, [_vp, ctypes.c_void_p, ctypes.POINTER(_int), ctypes.POINTER(_sz)]),
     "swm_blake2s": (_int, [ctypes.c_void_p, _sz, ctypes.c_void_p]),
     "swm_chacha_block": (_int, [ctypes.c_void_p, ctypes.c_uint64, _int, ctypes.c_void_p]),
@@ -98,6 +102,7 @@ ABI = {
     "swm_profile_json": (_int, [_vp, ctypes.c_char_p, _sz]),
     "swm_selftest_mul": (_int, [_vp, _int, _u64p, _u64p, _u64p, _sz]),
     "swm_selftest_g1_add": (_int, [_vp, _u64p, _u64p, _u64p, _sz]),
+    "swm_selftest_g1_codec": (_int, [_vp, _int, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint)]),
     "swm_selftest_mul_throughput": (_int, [_vp, _int, _sz, _int, ctypes.POINTER(ctypes.c_float)]),
     "swm_selftest_pairing": (_int, [ctypes.POINTER(ctypes.c_uint)]),
     "swm_selftest_fr_inv": (_int, [_u64p, _u64p, _sz, ctypes.POINTER(ctypes.c_uint)]),
@@ -446,6 +451,24 @@ class Context:
         out = np.zeros((a.shape[0], 18), dtype=np.uint64)
         self._check(self.lib.swm_selftest_g1_add(self.h, _p64(a), _p64(b), _p64(out), a.shape[0]), "swm_selftest_g1_add")
         return out
+
+    G1_CODEC_OPS = {"encode": 0, "decode": 1, "decode_unchecked": 2}
+
+    def selftest_g1_codec(self, op, data, n):
+        """swm_selftest_g1_codec: the point kernels of the uncompressed key forms on n points.  "encode": data = n x 12 uint64 affine
+        Montgomery limbs -> n x 96 bytes; "decode" / "decode_unchecked": data = n x 96 bytes -> (n x 12 uint64, bad bits)."""
+        bad = ctypes.c_uint(0)
+        if op == "encode":
+            a = np.ascontiguousarray(data, dtype=np.uint64).reshape(n, 12)
+            out = np.zeros(n * 96, dtype=np.uint8)
+            self._check(self.lib.swm_selftest_g1_codec(self.h, 0, a.ctypes.data, n, out.ctypes.data, None), "swm_selftest_g1_codec")
+            return out.tobytes()
+        a = np.frombuffer(bytes(data), dtype=np.uint8).copy()
+        assert a.size == n * 96
+        out = np.zeros((n, 12), dtype=np.uint64)
+        self._check(self.lib.swm_selftest_g1_codec(self.h, self.G1_CODEC_OPS[op], a.ctypes.data, n, out.ctypes.data, ctypes.byref(bad)),
+                    "swm_selftest_g1_codec")
+        return out, bad.value
 
     FR29_OPS = {"mul": 0, "mul_c": 1, "normalize": 2, "cond_sub_2r": 3, "cond_sub_r": 4, "canonical_below_2r": 5,
                 "canonical": 6, "sub": 7, "unpack": 8, "pack": 9, "inv": 10, "inv_exact": 11}

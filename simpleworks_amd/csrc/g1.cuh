@@ -229,6 +229,34 @@ __device__ bool fq_sqrt_dev(const Fq& a, Fq* out) {
     return true;
 }
 
+// ------------------------------------------------------------------------------------------------ point decoding
+// The two tests every device point decoder shares (g1_decompress_kernel and the g1_decode_uncompressed_kernel pair in marlin.hip,
+// verify_points_kernel in verify.hip), and the status bits they report.
+enum : uint32_t { G1_BAD_ENCODING = 1, G1_OFF_CURVE = 2, G1_OFF_SUBGROUP = 4 };
+// a < q for 12 words in STANDARD form (Fp::deserialize refuses anything else, in every mode of ark-serialize)
+__device__ inline bool fq_std_lt_p(const Fq& a) {
+    for (int k = 11; k >= 0; k--) {
+        if (a.v[k] < FqParams::P[k]) return true;
+        if (a.v[k] > FqParams::P[k]) return false;
+    }
+    return false;
+}
+// [r]P == O for an affine point ON THE CURVE: double-and-add over the 253 bits of r, 252 doublings + the mixed additions of r's
+// set bits on the 32-bit multiplier, one lane per point.  No barrier, no shared state: lanes may diverge around it.
+__device__ inline bool g1_in_subgroup_dev(const G1Affine& p) {
+    G1XYZZ acc = g1_xyzz_identity();
+    bool started = false;
+#pragma unroll 1
+    for (int b = 252; b >= 0; b--) {
+        if (started) acc = g1_dbl(acc);
+        if ((FrParams::P[b >> 5] >> (b & 31)) & 1) {
+            g1_add_mixed(acc, p);
+            started = true;
+        }
+    }
+    return g1_is_inf(acc);
+}
+
 // ------------------------------------------------------------------------------------------------ twisted Edwards form
 // G1 is also the a = -1 twisted Edwards curve  -x^2 + y^2 = 1 + d x^2 y^2  (constants and the map: tools/gen_constants.py):
 //     x = f (x_w + 1) / y_w,   y = (s (x_w + 1) - 1) / (s (x_w + 1) + 1),   s = 1/sqrt(3), f = sqrt(-(A + 2)/B).

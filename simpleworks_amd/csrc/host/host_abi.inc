@@ -110,11 +110,17 @@ int swm_verify_proof(const swm_vk* vk, const uint64_t* public_inputs, size_t n, 
     });
 }
 
-int swm_vk_serialize(const swm_vk* vk, uint8_t* out, size_t cap, size_t* len) {
-    if (!vk || !len) return SWM_ERR_INVALID_ARG;
+// flags of the key codecs (include/swmarlin.h): which of arkworks' three forms.  writer: SWM_KEY_UNCHECKED is a reader's flag.
+static bool key_flags_ok(unsigned flags, bool writer) {
+    if (flags & ~(unsigned)(SWM_KEY_UNCOMPRESSED | SWM_KEY_UNCHECKED)) return false;
+    if ((flags & SWM_KEY_UNCHECKED) && (writer || !(flags & SWM_KEY_UNCOMPRESSED))) return false;
+    return true;
+}
+int swm_vk_serialize_ex(const swm_vk* vk, unsigned flags, uint8_t* out, size_t cap, size_t* len) {
+    if (!vk || !len || !key_flags_ok(flags, true)) return SWM_ERR_INVALID_ARG;
     swm_ctx* none = nullptr;
     SWM_GUARD(none, {
-        std::vector<uint8_t> b = serialize_verifying_key(vk->vk);
+        std::vector<uint8_t> b = serialize_verifying_key(vk->vk, (flags & SWM_KEY_UNCOMPRESSED) != 0);
         *len = b.size();
         if (out) {
             if (b.size() > cap) throw MarlinError(SWM_ERR_INVALID_ARG, "buffer too small");
@@ -122,15 +128,17 @@ int swm_vk_serialize(const swm_vk* vk, uint8_t* out, size_t cap, size_t* len) {
         }
     });
 }
-int swm_vk_deserialize(const uint8_t* bytes, size_t len, swm_vk** out) {
-    if (!bytes || !out) return SWM_ERR_INVALID_ARG;
+int swm_vk_serialize(const swm_vk* vk, uint8_t* out, size_t cap, size_t* len) { return swm_vk_serialize_ex(vk, 0, out, cap, len); }
+int swm_vk_deserialize_ex(const uint8_t* bytes, size_t len, unsigned flags, swm_vk** out) {
+    if (!bytes || !out || !key_flags_ok(flags, false)) return SWM_ERR_INVALID_ARG;
     swm_ctx* none = nullptr;
     SWM_GUARD(none, {
         std::unique_ptr<swm_vk> v(new swm_vk());
-        v->vk = deserialize_verifying_key(bytes, len);
+        v->vk = deserialize_verifying_key(bytes, len, (flags & SWM_KEY_UNCOMPRESSED) != 0, !(flags & SWM_KEY_UNCHECKED));
         *out = v.release();
     });
 }
+int swm_vk_deserialize(const uint8_t* bytes, size_t len, swm_vk** out) { return swm_vk_deserialize_ex(bytes, len, 0, out); }
 int swm_proof_validate(const uint8_t* bytes, size_t len) {
     if (!bytes) return SWM_ERR_INVALID_ARG;
     swm_ctx* none = nullptr;

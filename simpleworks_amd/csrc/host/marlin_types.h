@@ -116,6 +116,21 @@ struct ByteWriter {
         raw(t, 48);
     }
     void ser_g2(const G2Affine& p) {
+        if (uncompressed) {  // x.c0, x.c1, y.c0, y.c1; the flags in the last byte of y.c1; the identity is (0, (1, 0), infinity)
+            uint8_t u[192];
+            if (p.inf) {
+                memset(u, 0, 192);
+                fp_to_bytes(fp_one<Fq>(), u + 96);
+                u[191] |= 0x40;
+            } else {
+                fp_to_bytes(p.x.c0, u);
+                fp_to_bytes(p.x.c1, u + 48);
+                fp_to_bytes(p.y.c0, u + 96);
+                fp_to_bytes(p.y.c1, u + 144);
+            }
+            raw(u, 192);
+            return;
+        }
         uint8_t t[96];
         if (p.inf) {
             memset(t, 0, 96);
@@ -137,7 +152,10 @@ struct ByteWriter {
 struct ByteReader {
     const uint8_t* p;
     size_t n, pos = 0;
-    bool uncompressed = false;  // G1 points in the serialize_uncompressed form (ByteWriter::uncompressed); still CHECKED here
+    bool uncompressed = false;  // points in the serialize_uncompressed form (ByteWriter::uncompressed); CHECKED unless:
+    // false (only with uncompressed): deserialize_unchecked — flags and canonical coordinates are still required (Fp::deserialize is
+    // the same in every mode), the curve equation and [r]P = O are not evaluated.  The caller vouches for the bytes.
+    bool checked = true;
     // != nullptr: g1() only takes the point's bytes, records where they are and returns the identity — the batch verifier
     // (verify.hip) checks all points of a batch in one kernel instead
     std::vector<const uint8_t*>* defer_g1 = nullptr;
@@ -178,6 +196,7 @@ struct ByteReader {
             G1Affine r;
             if (!fp_from_bytes(u, &r.x) || !fp_from_bytes(u + 48, &r.y)) throw MarlinError(SWM_ERR_SERIALIZATION, "G1 coordinate out of range");
             if (fl & 0x40) return g1_affine_identity();
+            if (!checked) return r;
             if (!fp_eq(fp_sqr(r.y), fp_add(fp_mul(fp_sqr(r.x), r.x), fp_one<Fq>()))) throw MarlinError(SWM_ERR_SERIALIZATION, "G1 point not on curve");
             if (!g1_is_inf(g1_mul_limbs(r, FrParams::P, 8))) throw MarlinError(SWM_ERR_SERIALIZATION, "G1 point not in the prime-order subgroup");
             return r;
@@ -204,6 +223,23 @@ struct ByteReader {
         return r;
     }
     G2Affine g2() {
+        if (uncompressed) {  // x.c0, x.c1, y.c0, y.c1 | flags; then y^2 = x^3 + b and [r]P = O unless !checked
+            uint8_t u[192];
+            memcpy(u, take(192), 192);
+            uint8_t fl = u[191] & 0xC0;
+            u[191] &= 0x3F;
+            if (fl == 0xC0) throw MarlinError(SWM_ERR_SERIALIZATION, "G2 invalid flags");
+            G2Affine r;
+            r.inf = false;
+            if (!fp_from_bytes(u, &r.x.c0) || !fp_from_bytes(u + 48, &r.x.c1) || !fp_from_bytes(u + 96, &r.y.c0) ||
+                !fp_from_bytes(u + 144, &r.y.c1))
+                throw MarlinError(SWM_ERR_SERIALIZATION, "G2 coordinate out of range");
+            if (fl & 0x40) return g2_identity();
+            if (!checked) return r;
+            if (!(r.y.square() == r.x.square() * r.x + g2_coeff_b())) throw MarlinError(SWM_ERR_SERIALIZATION, "G2 point not on curve");
+            if (!g2_mul(r, FrParams::P, 8).inf) throw MarlinError(SWM_ERR_SERIALIZATION, "G2 point not in the prime-order subgroup");
+            return r;
+        }
         uint8_t t[96];
         memcpy(t, take(96), 96);
         uint8_t flags = t[95] & 0xC0;
@@ -301,8 +337,9 @@ inline Proof deserialize_proof(const uint8_t* data, size_t len, bool uncompresse
     return pr;
 }
 
-inline std::vector<uint8_t> serialize_verifying_key(const VerifyingKey& vk) {
+inline std::vector<uint8_t> serialize_verifying_key(const VerifyingKey& vk, bool uncompressed = false) {
     ByteWriter w;
+    w.uncompressed = uncompressed;
     w.u64(vk.info.num_variables);
     w.u64(vk.info.num_constraints);
     w.u64(vk.info.num_non_zero);
@@ -350,8 +387,10 @@ inline VerifyingKey read_verifying_key(ByteReader& r) {
     vk.vk.supported_degree = r.u64();
     return vk;
 }
-inline VerifyingKey deserialize_verifying_key(const uint8_t* data, size_t len) {
+inline VerifyingKey deserialize_verifying_key(const uint8_t* data, size_t len, bool uncompressed = false, bool checked = true) {
     ByteReader r(data, len);
+    r.uncompressed = uncompressed;
+    r.checked = checked;
     VerifyingKey vk = read_verifying_key(r);
     if (r.pos != len) throw MarlinError(SWM_ERR_SERIALIZATION, "trailing bytes");
     return vk;

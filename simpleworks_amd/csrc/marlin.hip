@@ -2189,34 +2189,85 @@ __global__ void __launch_bounds__(256) g1_decompress_kernel(const uint32_t* __re
     for (int k = 0; k < 12; k++) xs.v[k] = in[12 * i + k];
     const uint32_t flags = xs.v[11] >> 30;
     xs.v[11] &= 0x3fffffffu;
-    bool lt = false;
-    for (int k = 11; k >= 0; k--) {
-        if (xs.v[k] < FqParams::P[k]) { lt = true; break; }
-        if (xs.v[k] > FqParams::P[k]) break;
-    }
     G1Affine r = g1_affine_identity();
-    if (flags == 3 || !lt) {
-        atomicOr(bad, 1u);
+    if (flags == 3 || !fq_std_lt_p(xs)) {
+        atomicOr(bad, (uint32_t)G1_BAD_ENCODING);
     } else if (!(flags & 1)) {
         r.x = fp_from_std(xs);
         Fq y;
         if (!fq_sqrt_dev(fp_add(fp_mul(fp_sqr(r.x), r.x), fp_one<Fq>()), &y)) {
-            atomicOr(bad, 2u);
+            atomicOr(bad, (uint32_t)G1_OFF_CURVE);
         } else {
             Fq ny = fp_neg(y);
             bool y_is_larger = fp_cmp_std(fp_to_std(y), fp_to_std(ny)) > 0;
             r.y = (y_is_larger == ((flags & 2) != 0)) ? y : ny;
-            // subgroup: [r]P == O, double-and-add over the 253 bits of r
-            G1XYZZ acc = g1_xyzz_identity();
-            bool started = false;
-            for (int b = 252; b >= 0; b--) {
-                if (started) acc = g1_dbl(acc);
-                if ((FrParams::P[b >> 5] >> (b & 31)) & 1) {
-                    g1_add_mixed(acc, r);
-                    started = true;
-                }
-            }
-            if (!g1_is_inf(acc)) atomicOr(bad, 4u);
+            if (!g1_in_subgroup_dev(r)) atomicOr(bad, (uint32_t)G1_OFF_SUBGROUP);  // [r]P == O (g1.cuh)
+        }
+    }
+    out[i] = r;
+}
+// affine -> the serialize_uncompressed form [U: ark-ec 0.3] (ByteWriter::ser_g1 with `uncompressed`): 24 words, x then y in standard
+// form, bit 6 of the last byte (bit 30 of word 23) = infinity, the identity as (0, 1).  One lane per point.
+// Stores: a lane writes its 96 bytes as six 16-byte stores at a stride of 96 bytes, which no single instruction coalesces.  A
+// wave's 64 points are 6144 CONTIGUOUS bytes, though, and its six stores cover them completely within a few instructions, so the
+// L2 merges them into whole 128-byte lines before they reach HBM; a transpose through LDS would make each instruction contiguous
+// at the price of 24 KB of LDS per workgroup and a barrier that every lane has to reach.  Left out: the kernel runs once per key
+// write, moves 96 B per point next to two Montgomery multiplications, and is followed by a device-to-host copy of the same bytes
+// over PCIe, which is an order of magnitude slower than either.  (Not measured; tools/pk_load_time.py times the writer as a whole.)
+__global__ void __launch_bounds__(256) g1_encode_uncompressed_kernel(const G1Affine* __restrict__ in, size_t n, uint32_t* __restrict__ out) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const G1Affine p = in[i];
+    uint32_t w[24];
+    if (g1_is_inf(p)) {
+        for (int k = 0; k < 24; k++) w[k] = 0;
+        w[12] = 1;
+        w[23] = 0x40000000u;
+    } else {
+        const Fq xs = fp_to_std(p.x), ys = fp_to_std(p.y);
+        for (int k = 0; k < 12; k++) {
+            w[k] = xs.v[k];
+            w[12 + k] = ys.v[k];
+        }
+    }
+    uint4* o = reinterpret_cast<uint4*>(out + 24 * i);  // 96-byte records in a 16-byte aligned buffer
+    for (int k = 0; k < 6; k++) o[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+}
+// the serialize_uncompressed form -> affine.  Both instantiations refuse what Fp / SWFlags refuse in every mode of ark-serialize
+// (flags 0xC0, a coordinate >= q: G1_BAD_ENCODING).  Checked = deserialize_uncompressed: y^2 = x^3 + 1 (G1_OFF_CURVE) and [r]P = O
+// (G1_OFF_SUBGROUP), no square root.  !Checked = deserialize_unchecked: the coordinates are taken as they are.  *bad collects the
+// bits of all lanes (as g1_decompress_kernel); a refused point is written as the identity.  No barrier, no LDS: a lane that meets
+// the identity or fails early simply has less to do.  Nothing downstream indexes memory by point data, so an unchecked point that
+// is not on the curve can make a proof wrong but not make a kernel fault.
+template <bool Checked>
+__global__ void __launch_bounds__(256) g1_decode_uncompressed_kernel(const uint32_t* __restrict__ in, size_t n, G1Affine* __restrict__ out,
+                                                                     uint32_t* __restrict__ bad) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4* src = reinterpret_cast<const uint4*>(in + 24 * i);
+    Fq xs, ys;
+    for (int k = 0; k < 3; k++) {
+        const uint4 a = src[k], b = src[3 + k];
+        xs.v[4 * k] = a.x; xs.v[4 * k + 1] = a.y; xs.v[4 * k + 2] = a.z; xs.v[4 * k + 3] = a.w;
+        ys.v[4 * k] = b.x; ys.v[4 * k + 1] = b.y; ys.v[4 * k + 2] = b.z; ys.v[4 * k + 3] = b.w;
+    }
+    const uint32_t flags = ys.v[11] >> 30;
+    ys.v[11] &= 0x3fffffffu;
+    G1Affine r = g1_affine_identity();
+    if (flags == 3 || !fq_std_lt_p(xs) || !fq_std_lt_p(ys)) {
+        atomicOr(bad, (uint32_t)G1_BAD_ENCODING);
+    } else if (!(flags & 1)) {  // (flags & 1: infinity; its coordinates were range-checked and are otherwise ignored)
+        G1Affine q;
+        q.x = fp_from_std(xs);
+        q.y = fp_from_std(ys);
+        if (!Checked) {
+            r = q;
+        } else if (!fp_eq(fp_sqr(q.y), fp_add(fp_mul(fp_sqr(q.x), q.x), fp_one<Fq>()))) {
+            atomicOr(bad, (uint32_t)G1_OFF_CURVE);
+        } else if (!g1_in_subgroup_dev(q)) {
+            atomicOr(bad, (uint32_t)G1_OFF_SUBGROUP);
+        } else {
+            r = q;
         }
     }
     out[i] = r;
@@ -2244,14 +2295,18 @@ void put_domain(ByteWriter& w, const HDomain& d) {  // GeneralEvaluationDomain::
     w.fr(d.gen_inv);
     w.fr(fp_inv(fp_from_u64<Fr>(22)));  // generator_inv = multiplicative_generator^-1
 }
-void put_g1_vec_dev(swm_ctx* ctx, ByteWriter& w, const G1Affine* d, size_t n) {  // Vec<G1Affine>, compressed
+void put_g1_vec_dev(swm_ctx* ctx, ByteWriter& w, const G1Affine* d, size_t n) {  // Vec<G1Affine>, in the writer's form
     w.u64(n);
     if (!n) return;
-    DBuf<uint32_t> tmp(ctx, n * 12);
-    LAUNCHX(ctx, "g1_compress", g1_compress_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d, n, tmp.p);
+    const size_t words = w.uncompressed ? 24 : 12;
+    DBuf<uint32_t> tmp(ctx, n * words);
+    if (w.uncompressed)
+        LAUNCHX(ctx, "g1_encode_uncompressed", g1_encode_uncompressed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d, n, tmp.p);
+    else
+        LAUNCHX(ctx, "g1_compress", g1_compress_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d, n, tmp.p);
     size_t at = w.b.size();
-    w.b.resize(at + n * 48);
-    hip_check(ctx, hipMemcpyAsync(w.b.data() + at, tmp.p, n * 48, hipMemcpyDeviceToHost, ctx->stream), "d2h");
+    w.b.resize(at + n * words * 4);
+    hip_check(ctx, hipMemcpyAsync(w.b.data() + at, tmp.p, n * words * 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
     hip_check(ctx, hipStreamSynchronize(ctx->stream), "sync");
 }
 void put_matrix(ByteWriter& w, const HostCsr& m) {
@@ -2273,9 +2328,10 @@ size_t trimmed_len(swm_ctx* ctx, const Fr* d, size_t n) {
     return n;
 }
 
-std::vector<uint8_t> pk_serialize(swm_ctx* ctx, const swm_pk& pk) {
+std::vector<uint8_t> pk_serialize(swm_ctx* ctx, const swm_pk& pk, bool uncompressed = false) {
     ByteWriter w;
-    std::vector<uint8_t> vkb = serialize_verifying_key(pk.vk);
+    w.uncompressed = uncompressed;  // every point below, on the host (gamma powers) and on the device (the two power ranges)
+    std::vector<uint8_t> vkb = serialize_verifying_key(pk.vk, uncompressed);
     w.raw(vkb.data(), vkb.size());
     w.u64(pk.vk.index_comms.size());  // index_comm_rands: no hiding -> empty blinding polynomial, no shifted rand
     for (size_t i = 0; i < pk.vk.index_comms.size(); i++) {
@@ -2342,8 +2398,32 @@ std::vector<G1Affine> get_g1_vec_dev(swm_ctx* ctx, ByteReader& r, uint64_t max_n
     return out;
 }
 
-swm_pk* pk_deserialize(swm_ctx* ctx, const uint8_t* bytes, size_t len) {
+// Vec<G1Affine> in the serialize_uncompressed form -> affine points that STAY on the device, decoded there (and, when `checked`,
+// tested against the curve equation and [r]P = O)
+DBuf<G1Affine> get_g1_vec_unc_dev(swm_ctx* ctx, ByteReader& r, uint64_t max_n, bool checked) {
+    uint64_t n = r.u64();
+    if (n > max_n) throw MarlinError(SWM_ERR_SERIALIZATION, "bad point count");
+    if (!n) return DBuf<G1Affine>();
+    const uint8_t* src = r.take(n * 96);
+    DBuf<uint32_t> in(ctx, n * 24), bad(ctx, 1);
+    DBuf<G1Affine> pts(ctx, n);
+    bad.zero();
+    hip_check(ctx, hipMemcpyAsync(in.p, src, n * 96, hipMemcpyHostToDevice, ctx->stream), "h2d");
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (checked) LAUNCHX(ctx, "g1_decode_uncompressed", g1_decode_uncompressed_kernel<true>, grid, block, 0, in.p, n, pts.p, bad.p);
+    else LAUNCHX(ctx, "g1_decode_unchecked", g1_decode_uncompressed_kernel<false>, grid, block, 0, in.p, n, pts.p, bad.p);
+    uint32_t b = bad.download(0, 1)[0];  // (synchronises: `in` is no longer read when it goes back to the pool)
+    if (b) throw MarlinError(SWM_ERR_SERIALIZATION, b & G1_OFF_SUBGROUP ? "committer key: point not in the prime-order subgroup"
+                                                        : (b & G1_OFF_CURVE ? "committer key: point not on the curve" : "committer key: invalid point encoding"));
+    return pts;
+}
+
+// uncompressed / checked: which of arkworks' three forms the bytes are in (include/swmarlin.h, swm_pk_deserialize_ex).  The
+// structural checks, the committer-key / verifying-key comparison and the recomputation of the derived tables are the same in all.
+swm_pk* pk_deserialize(swm_ctx* ctx, const uint8_t* bytes, size_t len, bool uncompressed = false, bool checked = true) {
     ByteReader r(bytes, len);
+    r.uncompressed = uncompressed;
+    r.checked = checked;
     std::unique_ptr<swm_pk> pk(new swm_pk());
     {   // everything in front of the committer key is parsed and checked on the host (host/pk_codec.h: the same text runs under
         // ASan / UBSan in tests/native/host_fuzz.cpp)
@@ -2358,9 +2438,20 @@ swm_pk* pk_deserialize(swm_ctx* ctx, const uint8_t* bytes, size_t len) {
         pk->X = pre.X; pk->logX = pre.logX;
         pk->B = pre.B; pk->logB = pre.logB;
     }
-    std::vector<G1Affine> powers = get_g1_vec_dev(ctx, r, 1ull << 31);
-    std::vector<G1Affine> shifted;
-    if (r.boolean()) shifted = get_g1_vec_dev(ctx, r, 1ull << 31);
+    // the two power ranges: the compressed form comes back to the host, the uncompressed one stays on the device and only the
+    // points the comparison below reads are downloaded
+    std::vector<G1Affine> powers, shifted;
+    DBuf<G1Affine> d_powers, d_shifted;
+    if (uncompressed) {
+        d_powers = get_g1_vec_unc_dev(ctx, r, 1ull << 31, checked);
+        if (r.boolean()) d_shifted = get_g1_vec_unc_dev(ctx, r, 1ull << 31, checked);
+    } else {
+        powers = get_g1_vec_dev(ctx, r, 1ull << 31);
+        if (r.boolean()) shifted = get_g1_vec_dev(ctx, r, 1ull << 31);
+    }
+    const size_t n_powers = uncompressed ? d_powers.n : powers.size(), n_shifted = uncompressed ? d_shifted.n : shifted.size();
+    auto power_at = [&](size_t i) { return uncompressed ? d_powers.download(i, 1)[0] : powers[i]; };
+    auto shifted_at = [&](size_t i) { return uncompressed ? d_shifted.download(i, 1)[0] : shifted[i]; };
     uint64_t ng = r.u64();
     if (ng > 16) throw MarlinError(SWM_ERR_SERIALIZATION, "bad gamma count");
     for (uint64_t i = 0; i < ng; i++) pk->gamma_powers.push_back(r.g1());
@@ -2373,8 +2464,8 @@ swm_pk* pk_deserialize(swm_ctx* ctx, const uint8_t* bytes, size_t len) {
     pk->srs_max_degree = r.u64();
     if (r.pos != len) throw MarlinError(SWM_ERR_SERIALIZATION, "trailing bytes");
     const uint64_t max_bound = std::max(pk->H, pk->K) - 2;
-    if (powers.size() < ahp_max_degree(pk->info.num_constraints, pk->info.num_variables, pk->info.num_non_zero) + 1 ||
-        powers.size() > pk->srs_max_degree + 1 || shifted.size() != max_bound + 1 || pk->gamma_powers.size() < 3 ||
+    if (n_powers < ahp_max_degree(pk->info.num_constraints, pk->info.num_variables, pk->info.num_non_zero) + 1 ||
+        n_powers > pk->srs_max_degree + 1 || n_shifted != max_bound + 1 || pk->gamma_powers.size() < 3 ||
         pk->srs_max_degree != pk->vk.vk.max_degree)
         throw MarlinError(SWM_ERR_SERIALIZATION, "committer key does not fit the index");
     {   // the committer key has to be the one the embedded verifying key was trimmed from: a key whose halves disagree would
@@ -2385,14 +2476,18 @@ swm_pk* pk_deserialize(swm_ctx* ctx, const uint8_t* bytes, size_t len) {
         std::sort(want.begin(), want.end());
         want.erase(std::unique(want.begin(), want.end()), want.end());
         const auto& dbs = pk->vk.vk.degree_bounds_and_shift_powers;
-        bool ok = bounds == want && dbs.size() == want.size() && same(powers[0], pk->vk.vk.g) &&
+        bool ok = bounds == want && dbs.size() == want.size() && same(power_at(0), pk->vk.vk.g) &&
                   same(pk->gamma_powers[0], pk->vk.vk.gamma_g);
         for (size_t i = 0; ok && i < dbs.size(); i++)
-            ok = dbs[i].first == want[i] && same(shifted[max_bound - dbs[i].first], dbs[i].second);
+            ok = dbs[i].first == want[i] && same(shifted_at(max_bound - dbs[i].first), dbs[i].second);
         if (!ok) throw MarlinError(SWM_ERR_SERIALIZATION, "committer key and verifying key of the proving key disagree");
     }
-    install_committer_key(ctx, *pk, powers.data(), powers.size(), shifted.data(), shifted.size(), /*device_src=*/false,
-                          /*in_subgroup=*/true);  // g1_decompress_kernel checked [r]P = O for every point
+    // in_subgroup: the checked readers' kernels tested [r]P = O for every point; for an unchecked key it is the caller's
+    // assertion (include/swmarlin.h) — the twisted Edwards tables built on it compute wrong sums for other points, nothing worse
+    if (uncompressed)
+        install_committer_key(ctx, *pk, d_powers.p, n_powers, d_shifted.p, n_shifted, /*device_src=*/true, /*in_subgroup=*/true);
+    else
+        install_committer_key(ctx, *pk, powers.data(), n_powers, shifted.data(), n_shifted, /*device_src=*/false, /*in_subgroup=*/true);
     pk->gtab = build_gamma_table(pk->gamma_powers);
     pk->a = upload_csr(ctx, pk->ha);
     pk->b = upload_csr(ctx, pk->hb);
@@ -2587,11 +2682,11 @@ int swm_generate_proof_ex(swm_ctx* ctx, const swm_pk* pk, const swm_r1cs* cs, sw
     });
 }
 
-int swm_pk_serialize(swm_ctx* ctx, const swm_pk* pk, uint8_t* out, size_t cap, size_t* len) {
-    if (!ctx || !pk || !len) return SWM_ERR_INVALID_ARG;
+int swm_pk_serialize_ex(swm_ctx* ctx, const swm_pk* pk, unsigned flags, uint8_t* out, size_t cap, size_t* len) {
+    if (!ctx || !pk || !len || !key_flags_ok(flags, true)) return SWM_ERR_INVALID_ARG;
     SWM_ON_DEVICE(ctx);
     SWM_GUARD(ctx, {
-        std::vector<uint8_t> b = pk_serialize(ctx, *pk);
+        std::vector<uint8_t> b = pk_serialize(ctx, *pk, (flags & SWM_KEY_UNCOMPRESSED) != 0);
         *len = b.size();
         if (out) {
             if (b.size() > cap) throw MarlinError(SWM_ERR_INVALID_ARG, "buffer too small");
@@ -2599,10 +2694,16 @@ int swm_pk_serialize(swm_ctx* ctx, const swm_pk* pk, uint8_t* out, size_t cap, s
         }
     });
 }
-int swm_pk_deserialize(swm_ctx* ctx, const uint8_t* bytes, size_t len, swm_pk** out) {
-    if (!ctx || !bytes || !out) return SWM_ERR_INVALID_ARG;
+int swm_pk_serialize(swm_ctx* ctx, const swm_pk* pk, uint8_t* out, size_t cap, size_t* len) {
+    return swm_pk_serialize_ex(ctx, pk, 0, out, cap, len);
+}
+int swm_pk_deserialize_ex(swm_ctx* ctx, const uint8_t* bytes, size_t len, unsigned flags, swm_pk** out) {
+    if (!ctx || !bytes || !out || !key_flags_ok(flags, false)) return SWM_ERR_INVALID_ARG;
     SWM_ON_DEVICE(ctx);
-    SWM_GUARD(ctx, *out = pk_deserialize(ctx, bytes, len));
+    SWM_GUARD(ctx, *out = pk_deserialize(ctx, bytes, len, (flags & SWM_KEY_UNCOMPRESSED) != 0, !(flags & SWM_KEY_UNCHECKED)));
+}
+int swm_pk_deserialize(swm_ctx* ctx, const uint8_t* bytes, size_t len, swm_pk** out) {
+    return swm_pk_deserialize_ex(ctx, bytes, len, 0, out);
 }
 int swm_r1cs_is_satisfied(swm_ctx* ctx, const swm_r1cs* cs, int* ok, size_t* first_bad) {
     if (!ctx || !cs || !ok) return SWM_ERR_INVALID_ARG;
@@ -2709,6 +2810,36 @@ int swm_selftest_sample_fr(swm_ctx* ctx, swm_rng* rng, size_t need, uint64_t* ou
     if (!ctx || !rng || (need && !out_mont)) return SWM_ERR_INVALID_ARG;
     SWM_ON_DEVICE(ctx);
     SWM_GUARD(ctx, selftest_sample_impl(ctx, rng->r, need, out_mont));
+}
+
+// the key codec's point kernels on host buffers (include/swmarlin.h names the ops)
+static void selftest_g1_codec_impl(swm_ctx* ctx, int op, const void* in, size_t n, void* out, unsigned* bad) {
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (op == 0) {
+        DBuf<G1Affine> pts(ctx, n);
+        DBuf<uint32_t> enc(ctx, n * 24);
+        pts.upload((const G1Affine*)in, n);
+        LAUNCHX(ctx, "g1_encode_uncompressed", g1_encode_uncompressed_kernel, grid, block, 0, pts.p, n, enc.p);
+        std::vector<uint32_t> h = enc.download(0, n * 24);
+        memcpy(out, h.data(), n * 96);
+        return;
+    }
+    DBuf<uint32_t> enc(ctx, n * 24), flag(ctx, 1);
+    DBuf<G1Affine> pts(ctx, n);
+    flag.zero();
+    enc.upload((const uint32_t*)in, n * 24);
+    if (op == 1) LAUNCHX(ctx, "g1_decode_uncompressed", g1_decode_uncompressed_kernel<true>, grid, block, 0, enc.p, n, pts.p, flag.p);
+    else LAUNCHX(ctx, "g1_decode_unchecked", g1_decode_uncompressed_kernel<false>, grid, block, 0, enc.p, n, pts.p, flag.p);
+    *bad = flag.download(0, 1)[0];
+    std::vector<G1Affine> h = pts.download(0, n);
+    memcpy(out, h.data(), n * sizeof(G1Affine));
+}
+int swm_selftest_g1_codec(swm_ctx* ctx, int op, const void* in, size_t n, void* out, unsigned* bad) {
+    if (!ctx || op < 0 || op > 2 || (n && (!in || !out)) || (op != 0 && !bad) || n > ((size_t)1 << 31)) return SWM_ERR_INVALID_ARG;
+    SWM_ON_DEVICE(ctx);
+    if (op != 0) *bad = 0;
+    if (n == 0) return SWM_OK;
+    SWM_GUARD(ctx, selftest_g1_codec_impl(ctx, op, in, n, out, bad));
 }
 
 }  // extern "C"

@@ -31,15 +31,8 @@ using namespace swm;
 namespace {
 
 // per-point status of verify_points_kernel (0 = a valid point in the prime-order subgroup, or the identity)
-enum : uint32_t { PT_OK = 0, PT_ENCODING = 1, PT_NOT_ON_CURVE = 2, PT_NOT_IN_SUBGROUP = 4 };
-
-__device__ bool fq_std_lt_p(const Fq& a) {
-    for (int k = 11; k >= 0; k--) {
-        if (a.v[k] < FqParams::P[k]) return true;
-        if (a.v[k] > FqParams::P[k]) return false;
-    }
-    return false;
-}
+// (the bits of g1.cuh's decoders; fq_std_lt_p and the [r]P ladder, g1_in_subgroup_dev, are shared with the key codec's kernels)
+enum : uint32_t { PT_OK = 0, PT_ENCODING = G1_BAD_ENCODING, PT_NOT_ON_CURVE = G1_OFF_CURVE, PT_NOT_IN_SUBGROUP = G1_OFF_SUBGROUP };
 
 // ByteReader::g1 (host/marlin_types.h) for every point of a batch, one lane per point: flags, x (and y) < q, the square root and
 // the choice of y (compressed: 12 words, x with the flags in the top bits of word 11) or the curve equation (uncompressed: 24
@@ -84,19 +77,7 @@ __global__ void __launch_bounds__(64) verify_points_kernel(const uint32_t* __res
                 r.y = (y_is_larger == ((flags & 2) != 0)) ? y : ny;
             }
         }
-        if (st == PT_OK) {  // subgroup: [r]P == O, double-and-add over the 253 bits of r
-            G1XYZZ acc = g1_xyzz_identity();
-            bool started = false;
-#pragma unroll 1
-            for (int b = 252; b >= 0; b--) {
-                if (started) acc = g1_dbl(acc);
-                if ((FrParams::P[b >> 5] >> (b & 31)) & 1) {
-                    g1_add_mixed(acc, r);
-                    started = true;
-                }
-            }
-            if (!g1_is_inf(acc)) st = PT_NOT_IN_SUBGROUP;
-        }
+        if (st == PT_OK && !g1_in_subgroup_dev(r)) st = PT_NOT_IN_SUBGROUP;  // [r]P == O
     }
     out[i] = st == PT_OK ? r : g1_affine_identity();
     status[i] = st;

@@ -14,6 +14,9 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 pub const SWM_OK: c_int = 0;
 pub const SWM_ERR_UNSATISFIED: c_int = -5;
 pub const SWM_PROOF_UNCOMPRESSED: c_uint = 1;
+/// swm_{pk,vk}_{serialize,deserialize}_ex: the serialize_uncompressed layout; readers only, with the former: deserialize_unchecked
+pub const SWM_KEY_UNCOMPRESSED: c_uint = 1;
+pub const SWM_KEY_UNCHECKED: c_uint = 2;
 
 /// struct swm_r1cs: a synthesised constraint system as flat arrays (instance[0] is the constant one).
 #[repr(C)]
@@ -91,6 +94,11 @@ extern "C" {
     pub fn swm_proof_validate(bytes: *const u8, len: usize) -> c_int;
     pub fn swm_pk_serialize(ctx: *mut swm_ctx, pk: *const swm_pk, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
     pub fn swm_pk_deserialize(ctx: *mut swm_ctx, bytes: *const u8, len: usize, out: *mut *mut swm_pk) -> c_int;
+    // the other two forms of a key: flags = 0 is the function above; SWM_KEY_UNCOMPRESSED; readers: | SWM_KEY_UNCHECKED
+    pub fn swm_vk_serialize_ex(vk: *const swm_vk, flags: c_uint, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    pub fn swm_vk_deserialize_ex(bytes: *const u8, len: usize, flags: c_uint, out: *mut *mut swm_vk) -> c_int;
+    pub fn swm_pk_serialize_ex(ctx: *mut swm_ctx, pk: *const swm_pk, flags: c_uint, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    pub fn swm_pk_deserialize_ex(ctx: *mut swm_ctx, bytes: *const u8, len: usize, flags: c_uint, out: *mut *mut swm_pk) -> c_int;
     pub fn swm_r1cs_is_satisfied(ctx: *mut swm_ctx, cs: *const swm_r1cs, ok: *mut c_int, first_bad: *mut usize) -> c_int;
 
     // one proof over several GPUs

@@ -16,6 +16,9 @@
 //! * `UniversalSRS`        -> `swm_srs_export` / `swm_srs_import` (the fields of kzg10::UniversalParams).
 //! * `ProvingKey`, `VerifyingKey`, `MarlinProof` -> their CanonicalSerialize bytes, which the library reads and writes
 //!                            (`swm_pk_*`, `swm_vk_*`, proof bytes) — the interchange format src/marlin/serialization.rs defines.
+//!                            Keys the library built leave it as `serialize_uncompressed` bytes and are read with
+//!                            `deserialize_unchecked` (`index`); a key goes back in unchecked only if this process took it out
+//!                            of the library, checked otherwise (`resident_pk`).  Like the rest of the crate: never compiled.
 //! Device-resident twins of keys are cached PER PROCESS AND DEVICE (`KEYS`: a mutex-guarded LRU of at most `PK_CACHE`
 //! reference-counted handles, by a digest of the verifying key and the committer-key shape): a key is resident per device,
 //! read-only, and every proving thread attaches its own context to the one copy (`swm_pk_attach`) — eight proving threads
@@ -94,9 +97,23 @@ struct SharedPk(*mut swm_pk);
 unsafe impl Send for SharedPk {} // an opaque, internally synchronised (atomic refcount, read-only) library handle
 struct KeyCache {
     entries: Vec<(c_int, [u8; 32], SharedPk)>, // (device, digest, handle)
+    /// Digests of the keys `index()` took OUT of the library in this process (kept when their entry is evicted; 32 bytes each).
+    /// Such a key goes back in unchecked: its points were computed by the library, and `ProvingKey::serialize_uncompressed`
+    /// writes them as they are.  Every other key — read from disk, built by arkworks, received from a peer — goes in checked.
+    /// The digest is `pk_key`: the verifying key and the committer key's shape, not its ~4 M points.  A caller who alters the
+    /// committer key of a key this process issued gets wrong proofs (as from arkworks' own prover with that key), not a fault.
+    issued: Vec<[u8; 32]>,
 }
-static KEYS: std::sync::Mutex<KeyCache> = std::sync::Mutex::new(KeyCache { entries: Vec::new() });
+static KEYS: std::sync::Mutex<KeyCache> = std::sync::Mutex::new(KeyCache { entries: Vec::new(), issued: Vec::new() });
 impl KeyCache {
+    fn mark_issued(&mut self, key: [u8; 32]) {
+        if !self.issued.contains(&key) {
+            self.issued.push(key);
+        }
+    }
+    fn was_issued(&self, key: &[u8; 32]) -> bool {
+        self.issued.contains(key)
+    }
     /// The cached handle with one more reference taken for the caller's context (`swm_pk_attach`), or None.
     fn get_attached(&mut self, ctx: *mut swm_ctx, device: c_int, key: &[u8; 32]) -> std::result::Result<Option<*mut swm_pk>, SwmError> {
         let i = match self.entries.iter().position(|(d, k, _)| *d == device && k == key) {
@@ -395,9 +412,14 @@ fn index(srs: &UniversalSRS, cs: ConstraintSystemRef) -> std::result::Result<(Pr
         let r1cs = packed.as_ffi();
         check(unsafe { swm_generate_proving_and_verifying_keys(ctx, srs_h, &r1cs, &mut pk_h, &mut vk_h) },
               "swm_generate_proving_and_verifying_keys", ctx)?;
-        let vk_bytes = bytes_of(|p, cap, len| unsafe { swm_vk_serialize(vk_h, p, cap, len) }, "swm_vk_serialize", ctx);
+        // Both keys leave in the serialize_uncompressed form and are read with deserialize_unchecked: the bytes were written by the
+        // library in this process a moment ago.  The checked compressed path (`ProvingKey::deserialize`) would take one Fq square
+        // root and one 253-bit subgroup ladder per committer-key point, ~4.2 M of them at 2^20 constraints, single-threaded:
+        // minutes by the review's estimate — an ESTIMATE: this crate has never been compiled, nothing here is measured on the
+        // Rust side (tools/pk_load_time.py times the library's own three readers).
+        let vk_bytes = bytes_of(|p, cap, len| unsafe { swm_vk_serialize_ex(vk_h, SWM_KEY_UNCOMPRESSED, p, cap, len) }, "swm_vk_serialize_ex", ctx);
         unsafe { swm_vk_destroy(vk_h) };
-        let pk_bytes = bytes_of(|p, cap, len| unsafe { swm_pk_serialize(ctx, pk_h, p, cap, len) }, "swm_pk_serialize", ctx);
+        let pk_bytes = bytes_of(|p, cap, len| unsafe { swm_pk_serialize_ex(ctx, pk_h, SWM_KEY_UNCOMPRESSED, p, cap, len) }, "swm_pk_serialize_ex", ctx);
         let (vk_bytes, pk_bytes) = match (vk_bytes, pk_bytes) {
             (Ok(v), Ok(p)) => (v, p),
             (Err(e), _) | (_, Err(e)) => {
@@ -405,16 +427,23 @@ fn index(srs: &UniversalSRS, cs: ConstraintSystemRef) -> std::result::Result<(Pr
                 return Err(e);
             }
         };
-        let de = |e: ark_serialize::SerializationError| SwmError { code: -7, what: "CanonicalDeserialize", detail: format!("{:?}", e) };
-        let vk = VerifyingKey::deserialize(&mut vk_bytes.as_slice()).map_err(de);
-        let pk = ProvingKey::deserialize(&mut pk_bytes.as_slice()).map_err(de);
-        match (pk, vk) {
-            (Ok(pk), Ok(vk)) => {
+        let de = |e: ark_serialize::SerializationError| SwmError { code: -7, what: "CanonicalDeserialize::deserialize_unchecked", detail: format!("{:?}", e) };
+        let vk = VerifyingKey::deserialize_unchecked(&mut vk_bytes.as_slice()).map_err(de);
+        let pk = ProvingKey::deserialize_unchecked(&mut pk_bytes.as_slice()).map_err(de);
+        // the cache's digest is over the COMPRESSED verifying key (vk_key: what resident_pk computes from a ProvingKey later)
+        let keyed = match (pk, vk) {
+            (Ok(pk), Ok(vk)) => vk_key(&vk).map(|(_, compressed)| (pk_key(&pk, &compressed), pk, vk)),
+            (Err(e), _) | (_, Err(e)) => Err(e),
+        };
+        match keyed {
+            Ok((key, pk, vk)) => {
                 // the process-wide cache takes over this thread's reference: any thread's generate_proof finds the twin
-                KEYS.lock().unwrap_or_else(|p| p.into_inner()).put(st.device, pk_key(&pk, &vk_bytes), pk_h);
+                let mut keys = KEYS.lock().unwrap_or_else(|p| p.into_inner());
+                keys.mark_issued(key);
+                keys.put(st.device, key, pk_h);
                 Ok((pk, vk))
             }
-            (Err(e), _) | (_, Err(e)) => {
+            Err(e) => {
                 unsafe { swm_pk_destroy(ctx, pk_h) };
                 Err(e)
             }
@@ -430,12 +459,16 @@ fn resident_pk(st: &mut State, pk: &ProvingKey) -> std::result::Result<*mut swm_
     if let Some(h) = KEYS.lock().unwrap_or_else(|p| p.into_inner()).get_attached(st.ctx, st.device, &key)? {
         return Ok(h);
     }
-    // a key this process has not seen on this device (deserialised from disk, built by arkworks): move it in through its
-    // bytes — outside the lock (seconds at 2^20); two threads racing on the same new key both import, the second put wins
+    // a key that is not resident on this device: move it in through its bytes — outside the lock (seconds at 2^20); two threads
+    // racing on the same new key both import, the second put wins.  The uncompressed form either way (no square roots on the
+    // device); UNCHECKED only for a key that came out of this library in this process and was evicted since (`issued`).  Anything
+    // else — deserialised from disk, built by arkworks — gets the curve and subgroup checks of deserialize_uncompressed.
+    let issued = KEYS.lock().unwrap_or_else(|p| p.into_inner()).was_issued(&key);
+    let flags = if issued { SWM_KEY_UNCOMPRESSED | SWM_KEY_UNCHECKED } else { SWM_KEY_UNCOMPRESSED };
     let mut bytes = Vec::new();
-    pk.serialize(&mut bytes).map_err(|e| SwmError { code: -7, what: "ProvingKey::serialize", detail: format!("{:?}", e) })?;
+    pk.serialize_uncompressed(&mut bytes).map_err(|e| SwmError { code: -7, what: "ProvingKey::serialize_uncompressed", detail: format!("{:?}", e) })?;
     let mut h = std::ptr::null_mut();
-    check(unsafe { swm_pk_deserialize(st.ctx, bytes.as_ptr(), bytes.len(), &mut h) }, "swm_pk_deserialize", st.ctx)?;
+    check(unsafe { swm_pk_deserialize_ex(st.ctx, bytes.as_ptr(), bytes.len(), flags, &mut h) }, "swm_pk_deserialize_ex", st.ctx)?;
     check(unsafe { swm_pk_retain(h) }, "swm_pk_retain", st.ctx)?; // one reference for the cache, one for this call
     KEYS.lock().unwrap_or_else(|p| p.into_inner()).put(st.device, key, h);
     Ok(h)
