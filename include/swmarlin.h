@@ -433,6 +433,27 @@ int swm_selftest_fr_inv(const uint64_t *a_mont, uint64_t *out_mont, size_t n, un
  * spread9 is read by op 7 only. */
 int swm_selftest_fr29(swm_ctx *ctx, int op, const uint32_t *a9, const uint32_t *b9, const uint32_t *spread9, uint32_t *out9,
                       size_t n);
+/* Device self-test of the MSM's 28-bit point layer (csrc/fq28.cuh and the streamed forms of csrc/msm.hip), one GPU lane per
+ * element (the quad ops: one quad of lanes per element), 256-lane workgroups, on host buffers.  Operands and results are RAW slots
+ * of the 28-bit domain: a, b, out hold n x 4 x 6 uint64 — the in-memory G1XYZZ of the bucket stage, four integers < 2^384 whose
+ * value is a field element times 2^392 (XYZZ: x, y, zz, zzz; twisted Edwards: X, Y, T, Z) — so the caller chooses the
+ * representative limb for limb.  A row operand is the 192 bytes of a table row (3 x 16 uint32: y - x, y + x, 2dxy).  flags (n
+ * words, NULL = zeros): bit 0 = the sign (`neg`) or `act` bit of the element, bit 1 = the sign of op 7's second point.  Ops:
+ *   0 p28_dbl<MulInline>(a)   1 p28_add<MulInline>(a, b)   2 p28_add<MulFenced>(a, b) (p28_add_ool)
+ *   3 p28_slot_add(out, a, b)   4 p28_slot_add with dst == pa (out = a first)   5 p28_slot_dbl(out, a)
+ *   6 p28_store_384(p28_load(a)): out in the memory form (radix 2^384, canonical)
+ *   7 madd28: the accumulator built from the affine point in slots x, y of a and flag bit 0 as msm_accumulate builds a segment's
+ *     first entry, then one madd28 with the point in slots x, y of b and flag bit 1; status[i] = its `ok`, out = the accumulator
+ *   8 msm_te_convert: a = n x 12 uint64 affine points (memory form, (0, 0) = the identity) -> out = n rows, status[0] = *bad
+ *   9 te28_from_row(row a, neg)   10 te28_madd_row(acc a, row b, neg)   11 te28_slot_add(out, a, b)
+ *   12 te28_slot_add with dst == pa   13 te28_slot_add(out, a, a)   14 te28_slot_add_sync(out, a, b, act, barrier on): a slot
+ *     whose lane sits out reads back as bytes 0xA5   15 te28_store_384(a)
+ *   16 te28_quad_from_row(row a, neg)   17 te28_quad_madd_row(a one coordinate per lane, row b, neg)   18 te28_quad_add(out, a, b)
+ *   19 te28_quad_add(out, a, a)   20 te28_quad_store_identity(out)
+ * out_jac (optional, ops 9 - 14 and 16 - 20 only): n x 18 uint64, g1_to_jacobian(g1te_to_xyzz(te28_store_384(out[i]))) computed
+ * on the device — the Weierstrass point a twisted Edwards result stands for.  status (optional): n words, written by ops 7 and 8. */
+int swm_selftest_p28(swm_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, const uint32_t *flags, uint64_t *out,
+                     uint64_t *out_jac, uint32_t *status, size_t n);
 /* Device self-test of the polynomial drivers of the prover (csrc/devops.cuh) on host data in the memory (Montgomery) form,
  * n x 4 uint64 per vector, z one element.  Ops:
  *   0 suffix_recurrence(data, n, m, z) in place: data[k] <- data[k] + z data[k + m], k descending (division by X^m - z)

@@ -107,6 +107,7 @@ ABI = {
     "swm_selftest_pairing": (_int, [ctypes.POINTER(ctypes.c_uint)]),
     "swm_selftest_fr_inv": (_int, [_u64p, _u64p, _sz, ctypes.POINTER(ctypes.c_uint)]),
     "swm_selftest_fr29": (_int, [_vp, _int, _u32p, _u32p, _u32p, _u32p, _sz]),
+    "swm_selftest_p28": (_int, [_vp, _int, _u64p, _u64p, _u32p, _u64p, _u64p, _u32p, _sz]),
     "swm_selftest_poly": (_int, [_vp, _int, ctypes.c_void_p, _sz, _sz, _u64p, _u64p, _sz, ctypes.c_void_p]),
     "swm_selftest_sample_fr": (_int, [_vp, _vp, _sz, _u64p]),
     "swm_verify_proofs_batch": (_int, [_vp, _vp, _u64p, _sz, _vp, ctypes.POINTER(_sz), _sz, ctypes.c_uint, _vp,
@@ -483,6 +484,33 @@ class Context:
         self._check(self.lib.swm_selftest_fr29(self.h, self.FR29_OPS[op], _p32(a), _p32(b), _p32(sp), _p32(out), a.shape[0]),
                     "swm_selftest_fr29")
         return out
+
+    P28_OPS = {"dbl": 0, "add": 1, "add_ool": 2, "slot_add": 3, "slot_add_inplace": 4, "slot_dbl": 5, "store_384": 6, "madd28": 7,
+               "rows": 8, "te_from_row": 9, "te_madd_row": 10, "te_slot_add": 11, "te_slot_add_inplace": 12, "te_slot_add_self": 13,
+               "te_slot_add_sync": 14, "te_store_384": 15, "quad_from_row": 16, "quad_madd_row": 17, "quad_add": 18,
+               "quad_add_self": 19, "quad_store_identity": 20}
+
+    def selftest_p28(self, op, a, b=None, flags=None, backmap=False, n=None):
+        """swm_selftest_p28: one routine of the MSM's 28-bit point layer per element, on raw slots (n x 24 uint64; "rows": a = n x 12
+        uint64 affine points).  Returns (out n x 24 uint64, status n uint32, jac n x 18 uint64 or None when backmap is off)."""
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 12 if op == "rows" else 24)
+            n = a.shape[0]
+        if n is None:
+            raise ValueError("selftest_p28: an op without operand a needs n")
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 24)
+            assert b.shape[0] == n
+        if flags is not None:
+            flags = np.ascontiguousarray(flags, dtype=np.uint32).reshape(-1)
+            assert flags.shape[0] == n
+        out = np.zeros((n, 24), dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        jac = np.zeros((n, 18), dtype=np.uint64) if backmap else None
+        self._check(self.lib.swm_selftest_p28(self.h, self.P28_OPS[op], _p64(a) if a is not None else None,
+                                              _p64(b) if b is not None else None, _p32(flags) if flags is not None else None,
+                                              _p64(out), _p64(jac) if backmap else None, _p32(status), n), "swm_selftest_p28")
+        return out, status[:n], jac
 
     def _poly(self, op, data, n, m, z, pieces, out):
         zz = np.ascontiguousarray(z if z is not None else np.zeros(4), dtype=np.uint64).reshape(4)

@@ -920,6 +920,35 @@ int swm_selftest_fr29(swm_ctx* ctx, int op, const uint32_t* a9, const uint32_t* 
     SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SWM_OK;
 }
+int swm_selftest_p28(swm_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, const uint32_t* flags, uint64_t* out, uint64_t* out_jac,
+                     uint32_t* status, size_t n) {
+    const bool rows = op == 8, te = (op >= 9 && op <= 14) || (op >= 16 && op <= 20);
+    const bool two = op == 1 || op == 2 || op == 3 || op == 4 || op == 7 || op == 10 || op == 11 || op == 12 || op == 14 || op == 17 || op == 18;
+    if (!ctx || op < 0 || op > 20 || (n && (!out || (op != 20 && !a) || (two && !b))) || (out_jac && !te)) return SWM_ERR_INVALID_ARG;
+    SWM_ON_DEVICE(ctx);
+    if (n == 0) return SWM_OK;
+    const size_t in_bytes = n * (rows ? 96 : 192), out_bytes = n * 192;
+    char *da = nullptr, *db = nullptr, *dc = nullptr, *dd = nullptr;
+    SWM_TRY(scratch(ctx, "stage.a", out_bytes + 64, (void**)&da));
+    SWM_TRY(scratch(ctx, "stage.b", out_bytes + 64, (void**)&db));
+    SWM_TRY(scratch(ctx, "stage.c", out_bytes + 64, (void**)&dc));
+    // stage.d: the back-mapped points (n x 144 bytes) | msm_te_convert's prefix products (n x 48) | flags (n words) | status (n words)
+    SWM_TRY(scratch(ctx, "stage.d", n * 200 + 64, (void**)&dd));
+    char* d_pref = dd + n * 144;
+    uint32_t *d_flags = (uint32_t*)(dd + n * 192), *d_status = d_flags + n;
+    if (a) SWM_HIP(ctx, hipMemcpyAsync(da, a, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (two) SWM_HIP(ctx, hipMemcpyAsync(db, b, out_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (flags) SWM_HIP(ctx, hipMemcpyAsync(d_flags, flags, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    else SWM_HIP(ctx, hipMemsetAsync(d_flags, 0, n * 4, ctx->stream));
+    SWM_HIP(ctx, hipMemsetAsync(d_status, 0, n * 4, ctx->stream));
+    SWM_HIP(ctx, hipMemsetAsync(dc, 0xA5, out_bytes, ctx->stream));  // what a slot that no lane writes reads back as
+    SWM_TRY(selftest_p28_run(ctx, op, da, db, d_flags, dc, out_jac ? dd : nullptr, d_pref, d_status, n));
+    SWM_HIP(ctx, hipMemcpyAsync(out, dc, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_jac) SWM_HIP(ctx, hipMemcpyAsync(out_jac, dd, n * 144, hipMemcpyDeviceToHost, ctx->stream));
+    if (status) SWM_HIP(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SWM_OK;
+}
 int swm_selftest_g1_add(swm_ctx* ctx, const uint64_t* a_xy, const uint64_t* b_xy, uint64_t* out_jac, size_t n) {
     if (!ctx || !a_xy || !b_xy || !out_jac) return SWM_ERR_INVALID_ARG;
     SWM_ON_DEVICE(ctx);

@@ -328,11 +328,17 @@ __device__ __forceinline__ void p28_store(XYZZ& m, const P28& p) {
 }
 
 // doubling (EFD dbl-2008-s-1, a = 0); identity stays identity (zz, zzz are multiplied)
+// A point of order two — (-1, 0): any curve point is a legal base — has y = 0 mod p, but its y slot holds a non-zero multiple of p
+// whenever a generic addition produced it (mul2 returns an N value, not a canonical one).  u^2 then comes back as the INTEGER p
+// (a Montgomery product of non-zero operands is never 0) and zz3 = v zz would be p as well: congruent to zero, yet not the
+// "zz == 0 exactly" that marks the identity, and every later sum with it would stay at zz = p.  So the double of such a point is
+// returned as the identity itself.
 template <class M = MulInline>
 __device__ __forceinline__ P28 p28_dbl(const P28& p) {
     P28 r;
     Fq28 u = fq28_add(p.y, p.y);             // limbs < 2^29, value < 12p
     Fq28 v = M::sqr(u);                    // N
+    if (fq28_is_zero_mod_p(v)) return p28_identity();
     Fq28 w = M::mul(u, v);                 // N
     Fq28 s = M::mul(p.x, v);               // N
     Fq28 xx = M::sqr(p.x);                 // N

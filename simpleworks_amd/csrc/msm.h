@@ -167,5 +167,10 @@ int msm_finish_many(swm_ctx* ctx, MsmJob** jobs, int k, G1XYZZ* results);  // a 
 HostPool* host_pool_of(swm_ctx* ctx);
 int msm_run(swm_ctx* ctx, const G1Affine* d_bases, const G1Affine* d_bases28, const void* d_scalars, size_t n, int mont,
             G1XYZZ* result, MsmInfMask inf = MsmInfMask(), MsmTable tab = MsmTable());
+// One op of the point-layer self-test (msm.hip, "point-layer self-test"; include/swmarlin.h: swm_selftest_p28) on n elements of
+// device buffers: d_jac (optional) receives the Weierstrass image of every twisted Edwards result, d_pref is msm_te_convert's
+// scratch (n field elements), d_status one word per element (zeroed by the caller).
+int selftest_p28_run(swm_ctx* ctx, int op, const void* da, const void* db, const uint32_t* d_flags, void* d_out, void* d_jac,
+                     void* d_pref, uint32_t* d_status, size_t n);
 
 }  // namespace swm

@@ -1303,6 +1303,10 @@ __device__ __forceinline__ void p28_slot_dbl(G1XYZZ* dst, const G1XYZZ* pa) {
     Fq28 y = fq28_unpack(pa->y);
     Fq28 u = fq28_add(y, y);                    // limbs < 2^29, value < 12p
     Fq28 v = M::sqr(u);
+    if (fq28_is_zero_mod_p(v)) {                // y = 0 mod p, a point of order two: its double is the identity, zz EXACTLY 0 (p28_dbl)
+        p28_store(*dst, p28_identity());
+        return;
+    }
     Fq28 w = M::mul(u, v);
     Fq28 ny;                                    // 8p - Y1 > 0 (Y1 < 6p), limbs < 2^29
 #pragma unroll
@@ -3101,6 +3105,183 @@ int msm_run(swm_ctx* ctx, const G1Affine* d_bases, const G1Affine* d_bases28, co
     MsmJob job;
     SWM_TRY(msm_enqueue(ctx, -1, d_bases, d_bases28, d_scalars, n, mont, &job, inf, false, tab));
     return msm_finish(ctx, &job, result);
+}
+
+// ---------------------------------------------------------------------------------------------- point-layer self-test
+// The routines of the 28-bit point layer (fq28.cuh and the streamed forms above), one call per element on operands the CALLER
+// chose limb for limb (include/swmarlin.h: swm_selftest_p28 names the ops).  a, b, out: raw slots of the 28-bit domain (a row
+// operand: the 192 bytes of a G1TE); flags: bit 0 = the sign / `act` bit of the element, bit 1 = the sign of madd28's second point.
+enum : int {
+    P28T_DBL = 0, P28T_ADD, P28T_ADD_OOL, P28T_SLOT_ADD, P28T_SLOT_ADD_INPLACE, P28T_SLOT_DBL, P28T_STORE_384, P28T_MADD28,
+    P28T_ROWS, P28T_TE_FROM_ROW, P28T_TE_MADD_ROW, P28T_TE_SLOT_ADD, P28T_TE_SLOT_ADD_INPLACE, P28T_TE_SLOT_ADD_SELF,
+    P28T_TE_SLOT_ADD_SYNC, P28T_TE_STORE_384, P28T_QUAD_FROM_ROW, P28T_QUAD_MADD_ROW, P28T_QUAD_ADD, P28T_QUAD_ADD_SELF,
+    P28T_QUAD_STORE_IDENTITY, P28T_COUNT
+};
+__device__ __forceinline__ T28 t28_load(const G1XYZZ& m) {
+    T28 r;
+    r.x = fq28_unpack(m.x);
+    r.y = fq28_unpack(m.y);
+    r.t = fq28_unpack(m.zz);
+    r.z = fq28_unpack(m.zzz);
+    return r;
+}
+__device__ __forceinline__ void t28_store(G1XYZZ& m, const T28& p) {
+    m.x = fq28_pack(p.x);
+    m.y = fq28_pack(p.y);
+    m.zz = fq28_pack(p.t);
+    m.zzz = fq28_pack(p.z);
+}
+__global__ void __launch_bounds__(256) selftest_p28_kernel(int op, const G1XYZZ* a, const G1XYZZ* b, const uint32_t* flags, G1XYZZ* out,
+                                                           uint32_t* status, size_t n) {
+    const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
+    const bool live = i < n;
+    const uint32_t fl = live ? flags[i] : 0u;
+    if (op == P28T_TE_SLOT_ADD_SYNC) {  // every lane of the workgroup reaches the barrier; the lanes past n and those without the bit sit out
+        const size_t j = live ? i : 0;
+        te28_slot_add_sync(&out[j], &a[j], &b[j], live && (fl & 1u) != 0, true);
+        return;
+    }
+    if (!live) return;
+    const bool neg = (fl & 1u) != 0;
+    switch (op) {
+    case P28T_DBL:
+        p28_store(out[i], p28_dbl<MulInline>(p28_load(a[i])));
+        break;
+    case P28T_ADD: {
+        P28 p = p28_load(a[i]);
+        p28_add<MulInline>(p, p28_load(b[i]));
+        p28_store(out[i], p);
+        break;
+    }
+    case P28T_ADD_OOL: {
+        P28 p = p28_load(a[i]);
+        p28_add_ool(p, p28_load(b[i]));
+        p28_store(out[i], p);
+        break;
+    }
+    case P28T_SLOT_ADD:
+        p28_slot_add(&out[i], &a[i], &b[i]);
+        break;
+    case P28T_SLOT_ADD_INPLACE:
+        out[i] = a[i];
+        p28_slot_add(&out[i], &out[i], &b[i]);
+        break;
+    case P28T_SLOT_DBL:
+        p28_slot_dbl(&out[i], &a[i]);
+        break;
+    case P28T_STORE_384:
+        p28_store_384(out[i], p28_load(a[i]));
+        break;
+    case P28T_MADD28: {
+        // the first entry of a segment and the operand of every later one, as msm_accumulate forms them: slots x, y of a and of b
+        // hold two affine points of the scaled base set
+        Acc28 acc;
+        acc.x = fq28_unpack(a[i].x);
+        Fq28 y = fq28_unpack(a[i].y);
+        if (neg) {
+            Fq28 z;
+#pragma unroll
+            for (int k = 0; k < 14; k++) z.l[k] = Fq28Consts::SPREAD4[k] - y.l[k];
+            y = fq28_normalize(z);
+        }
+        acc.y = y;
+        acc.zz = fq28_const(Fq28Consts::ONE);
+        acc.zzz = acc.zz;
+        Fq28 x2 = fq28_unpack(b[i].x), y2 = fq28_unpack(b[i].y);
+        if (fl & 2u) {
+#pragma unroll
+            for (int k = 0; k < 14; k++) y2.l[k] = Fq28Consts::SPREAD4[k] - y2.l[k];
+        }
+        status[i] = madd28(acc, x2, y2) ? 1u : 0u;
+        P28 o{acc.x, acc.y, acc.zz, acc.zzz};
+        p28_store(out[i], o);
+        break;
+    }
+    case P28T_TE_FROM_ROW: {
+        const G1TE* row = reinterpret_cast<const G1TE*>(&a[i]);
+        t28_store(out[i], te28_from_row(te28_load_coord(row->ymx), te28_load_coord(row->ypx), te28_load_coord(row->kt), neg));
+        break;
+    }
+    case P28T_TE_MADD_ROW: {
+        T28 acc = t28_load(a[i]);
+        te28_madd_row(acc, reinterpret_cast<const G1TE*>(&b[i]), neg);
+        t28_store(out[i], acc);
+        break;
+    }
+    case P28T_TE_SLOT_ADD:
+        te28_slot_add(&out[i], &a[i], &b[i]);
+        break;
+    case P28T_TE_SLOT_ADD_INPLACE:
+        out[i] = a[i];
+        te28_slot_add(&out[i], &out[i], &b[i]);
+        break;
+    case P28T_TE_SLOT_ADD_SELF:
+        te28_slot_add(&out[i], &a[i], &a[i]);
+        break;
+    case P28T_TE_STORE_384:
+        te28_store_384(out[i], a[i]);
+        break;
+    default:
+        break;
+    }
+}
+// the quad forms: four lanes per element, every lane handed the same pointers
+__global__ void __launch_bounds__(256) selftest_p28_quad_kernel(int op, const G1XYZZ* a, const G1XYZZ* b, const uint32_t* flags,
+                                                                G1XYZZ* out, size_t n) {
+    const size_t i = (blockIdx.x * (size_t)256 + threadIdx.x) >> 2;
+    const unsigned q = threadIdx.x & 3u;
+    if (i >= n) return;  // (uniform over a quad)
+    const bool neg = (flags[i] & 1u) != 0;
+    switch (op) {
+    case P28T_QUAD_FROM_ROW:
+        reinterpret_cast<Fq*>(&out[i])[q] = fq28_pack(te28_quad_from_row(reinterpret_cast<const G1TE*>(&a[i]), neg, q));
+        break;
+    case P28T_QUAD_MADD_ROW: {
+        Fq28 own = fq28_unpack(reinterpret_cast<const Fq*>(&a[i])[q]);
+        te28_quad_madd_row(own, reinterpret_cast<const G1TE*>(&b[i]), neg, q);
+        reinterpret_cast<Fq*>(&out[i])[q] = fq28_pack(own);
+        break;
+    }
+    case P28T_QUAD_ADD:
+        te28_quad_add(&out[i], &a[i], &b[i], q);
+        break;
+    case P28T_QUAD_ADD_SELF:
+        te28_quad_add(&out[i], &a[i], &a[i], q);
+        break;
+    case P28T_QUAD_STORE_IDENTITY:
+        te28_quad_store_identity(&out[i], q);
+        break;
+    default:
+        break;
+    }
+}
+// a twisted Edwards slot of the 28-bit domain -> the Weierstrass point it stands for, by the maps the bucket stage and the host
+// fold apply to a total (te28_store_384, g1te_to_xyzz), as a Jacobian point in the memory form
+__global__ void __launch_bounds__(256) selftest_p28_backmap_kernel(const G1XYZZ* slots, G1Jac* out, size_t n) {
+    const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (i >= n) return;
+    G1XYZZ m;
+    te28_store_384(m, slots[i]);
+    out[i] = g1_to_jacobian(g1te_to_xyzz(m));
+}
+int selftest_p28_run(swm_ctx* ctx, int op, const void* da, const void* db, const uint32_t* d_flags, void* d_out, void* d_jac,
+                     void* d_pref, uint32_t* d_status, size_t n) {
+    if (op < 0 || op >= P28T_COUNT) return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_p28: no such op");
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (op == P28T_ROWS) {
+        const unsigned gridn = (unsigned)(((n + TAB_NORM_CHUNK - 1) / TAB_NORM_CHUNK + 255) / 256);
+        SWM_LAUNCH(ctx, "selftest_p28_rows", msm_te_convert, dim3(gridn), dim3(256), 0, (const G1Affine*)da, n, (Fq*)d_pref, (G1TE*)d_out,
+                   d_status);
+    } else if (op >= P28T_QUAD_FROM_ROW) {
+        SWM_LAUNCH(ctx, "selftest_p28_quad", selftest_p28_quad_kernel, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, op,
+                   (const G1XYZZ*)da, (const G1XYZZ*)db, d_flags, (G1XYZZ*)d_out, n);
+    } else {
+        SWM_LAUNCH(ctx, "selftest_p28", selftest_p28_kernel, dim3(grid), dim3(256), 0, op, (const G1XYZZ*)da, (const G1XYZZ*)db, d_flags,
+                   (G1XYZZ*)d_out, d_status, n);
+    }
+    if (d_jac)
+        SWM_LAUNCH(ctx, "selftest_p28_backmap", selftest_p28_backmap_kernel, dim3(grid), dim3(256), 0, (const G1XYZZ*)d_out, (G1Jac*)d_jac, n);
+    return SWM_OK;
 }
 
 }  // namespace swm

@@ -529,3 +529,121 @@ def test_flat_te_more_than_1024_bins_and_queue_overflow(refs):
     recs = refs.child(n, env, [case])
     check_kernels(recs["hbm"], FLAT_KERNELS, TWO_LEVEL_KERNELS + ("msm_scatter",))
     assert refs.got(recs["hbm"]) == refs.affine(refs.msm(sc))
+
+
+# ------------------------------------------------------------------------------------------------ duplicate and opposite bases
+# Equal and opposite bases are what sends an XYZZ accumulation off its generic formula: madd28 returns false and the segment is
+# redone by the cold path of msm_accumulate (from the raw bases in the per-window schedule, from table rows rescaled by 2^376 in
+# the flat one), p28_slot_add takes its pp == 0 branch in the bucket stage; the twisted Edwards schedules must not notice.  Rows of
+# the [tau^i]G set are overwritten in place:
+DUP_RUNS = ((100, 2), (110, 3), (200, 129))   # (first row, length) of runs of one point: 2, 3, and SEG + 1 for the largest SEG (128)
+DUP_PAIR, DUP_TRIPLE, DUP_HOLE, DUP_ORDER2, DUP_SMALL_X = 400, 410, 420, 430, 440
+
+
+def dup_bases(refs, n, order2):
+    """bases[:n] with runs of equal points, P next to -P, (P, -P, P) and (P, O, P); order2: also (P, T2 - P, P, T2 - P) for
+    T2 = (q - 1, 0) and the curve point (2, 3), which take the set out of the prime-order subgroup (XYZZ rows)."""
+    from oracle_lib import Q
+    from pyref.bls12_377 import g1_add, g1_neg
+    b = np.ascontiguousarray(refs.bases[:n]).copy()
+
+    def negated(row):
+        out = row.copy()
+        out[6:] = ints_to_limbs([(Q - limbs_to_ints(row[None, 6:])[0]) % Q], 6)[0]
+        return out
+
+    for first, length in DUP_RUNS:
+        b[first:first + length] = b[first]
+    b[DUP_PAIR + 1] = negated(b[DUP_PAIR])
+    b[DUP_TRIPLE + 1] = negated(b[DUP_TRIPLE])
+    b[DUP_TRIPLE + 2] = b[DUP_TRIPLE]
+    b[DUP_HOLE + 1] = 0
+    b[DUP_HOLE + 2] = b[DUP_HOLE]
+    if order2:
+        pt = refs.orc.points_from_mont(np.ascontiguousarray(b[DUP_ORDER2:DUP_ORDER2 + 1]))[0]
+        other = refs.orc.points_to_mont([g1_add((Q - 1, 0), g1_neg(pt))])[0]
+        b[DUP_ORDER2 + 1] = other
+        b[DUP_ORDER2 + 2] = b[DUP_ORDER2]
+        b[DUP_ORDER2 + 3] = other
+        b[DUP_SMALL_X] = refs.orc.points_to_mont([(2, 3)])[0]
+    return b
+
+
+class DupSet:
+    def __init__(self, refs, n, order2):
+        self.refs, self.n = refs, n
+        self.bases = dup_bases(refs, n, order2)
+        self.path = os.path.join(refs.tmp, "dup_%d_%d.npy" % (n, int(order2)))
+        np.save(self.path, self.bases)
+        self.scalars = {"equal": equal(BIG253, n), "uniform": np.ascontiguousarray(refs.uniform[:n])}   # BIG253 is odd
+        self.want = {k: refs.affine(refs.orc.msm(self.bases, sc, threads=refs.threads)) for k, sc in self.scalars.items()}
+
+    def run(self, env, expect, present, absent=()):
+        cases = [{"name": k, "scalars": sc, "expect": expect} for k, sc in self.scalars.items()]
+        recs = run_child(self.refs.tmp, self.path, self.n, env, cases)
+        for k in self.scalars:
+            check_kernels(recs[k], present, absent)
+            assert self.refs.got(recs[k]) == self.want[k], k
+
+
+@pytest.fixture(scope="module")
+def dup_small(refs):
+    return {order2: DupSet(refs, 2048, order2) for order2 in (False, True)}
+
+
+@pytest.fixture(scope="module")
+def dup_large(refs):
+    return {order2: DupSet(refs, 262144, order2) for order2 in (False, True)}
+
+
+def test_duplicate_base_sets_are_what_they_claim():
+    """No device: the rows of the duplicate sets are the points the cases are named after, and on the curve (on the first 512
+    points of the set, which hold every overwritten row)."""
+    import types
+    from oracle_lib import Q
+    from pyref.bls12_377 import g1_add, g1_is_on_curve, g1_neg
+    orc = Oracle()
+    G = orc.points_to_mont([tuple(h2i(v) for v in golden("g1.json")["generator"])])
+    small = types.SimpleNamespace(orc=orc, bases=orc.srs_bases(512, h2i(golden("msm.json")["tau"]), G))
+    pts = orc.points_from_mont(dup_bases(small, 512, True))
+    assert BIG253 & 1 and all(g1_is_on_curve(p) for p in pts)
+    for first, length in DUP_RUNS:
+        assert len(set(pts[first:first + length])) == 1 and pts[first - 1] != pts[first] != pts[first + length]
+    assert pts[DUP_PAIR + 1] == g1_neg(pts[DUP_PAIR]) and pts[DUP_TRIPLE + 1] == g1_neg(pts[DUP_TRIPLE]) and pts[DUP_TRIPLE + 2] == pts[DUP_TRIPLE]
+    assert pts[DUP_HOLE + 1] is None and pts[DUP_HOLE + 2] == pts[DUP_HOLE]
+    assert g1_add(pts[DUP_ORDER2], pts[DUP_ORDER2 + 1]) == (Q - 1, 0) and g1_add((Q - 1, 0), (Q - 1, 0)) is None
+    assert pts[DUP_ORDER2 + 2] == pts[DUP_ORDER2] and pts[DUP_ORDER2 + 3] == pts[DUP_ORDER2 + 1] and pts[DUP_SMALL_X] == (2, 3)
+
+
+DUP_XYZZ_ABSENT = TWO_LEVEL_KERNELS + ("msm_flat_bin_sort",)
+
+
+@pytest.mark.gpu
+def test_duplicates_per_window_raw_bases(dup_small):
+    """SWM_MSM_NO_TABLE at 2048 points: msm_accumulate on the raw bases — its cold path with bases != nullptr — and
+    msm_bucket_reduce<XYZZ>; the subgroup set and the set with (P, T2 - P, P, T2 - P) under equal odd and uniform scalars."""
+    for order2 in (False, True):
+        dup_small[order2].run(NO_TABLE, {"flat": 0, "te": 0, "two_level": 0}, PER_WINDOW_KERNELS, DUP_XYZZ_ABSENT)
+
+
+@pytest.mark.gpu
+def test_duplicates_xyzz_table_rows(dup_small):
+    """A set with one point outside the subgroup gets XYZZ table rows: the cold path rescales rows by 2^376 (bases == nullptr)."""
+    dup_small[True].run({}, {"flat": 1, "te": 0, "lat": 1}, FLAT_KERNELS, TWO_LEVEL_KERNELS + ("msm_scatter",))
+
+
+@pytest.mark.gpu
+def test_duplicates_flat_xyzz_throughput(dup_large):
+    for order2 in (False, True):
+        dup_large[order2].run({"SWM_MSM_TE": "0"}, {"flat": 1, "te": 0, "lat": 0, "SEG": 128}, FLAT_KERNELS, TWO_LEVEL_KERNELS + ("msm_scatter",))
+
+
+@pytest.mark.gpu
+def test_duplicates_flat_te_low_latency_quad(dup_small):
+    """twisted Edwards rows, four lanes per segment and per chain: the unified law takes equal, opposite and identity rows."""
+    dup_small[False].run({}, {"flat": 1, "te": 1, "lat": 1}, FLAT_KERNELS, TWO_LEVEL_KERNELS + ("msm_scatter",))
+
+
+@pytest.mark.gpu
+def test_duplicates_flat_te_throughput(dup_large):
+    dup_large[False].run({}, {"flat": 1, "te": 1, "lat": 0}, FLAT_KERNELS, TWO_LEVEL_KERNELS + ("msm_scatter",))
