@@ -123,7 +123,8 @@ __device__ __forceinline__ Fr29 fr29_mul(const Fr29& a, const Fr29& b) {
 // The same product as one hand-ordered asm statement (r04; text from tools/gen_mul28_asm.py fr29, reasoning in fq28.cuh at
 // fq28_mul_asm): the 153 multiply-adds in one chain through v[0:1], low columns closed by add (2^29 - 1) / v_bfi_b32 / shift,
 // high columns by mask / shift: 197 instructions where the compiler's schedule of fr29_mul takes ~238.  Same limbs bit for bit
-// (tools/check_ntt29.py asserts the carry rule; every NTT test compares with the oracle).  A statement is its own fence.
+// (tools/check_ntt29.py asserts the carry rule; every NTT test compares with the oracle, on random and on extremal inputs
+// (tests/test_gpu_ntt_edges.py)).  A statement is its own fence.
 #include "fr29_mul_asm.inc"
 __device__ __forceinline__ Fr29 fr29_mul_fenced(const Fr29& a, const Fr29& b) {
     Fr29 r;

@@ -2,7 +2,10 @@
 """Bit-level emulation of the lazy 29-bit transform arithmetic of simpleworks_amd/csrc/fr29.cuh + ntt.hip (ntt_pass_lazy): every
 uint32 limb operation and every 64-bit column sum is checked for wrap-around, the value bounds the host plan assumes are asserted,
 and whole small transforms (every pass plan up to 2^12, forward / inverse / coset) are compared with a direct DFT in Python
-integers.  CPU only; run: python tools/check_ntt29.py"""
+integers.  Besides random data it feeds the inputs at which the plan's bounds are tight (edge_inputs / tile_patterns: constants,
+combs of r - 1 and 0 at every butterfly distance, single elements, root orbits), whole transforms of those against their closed
+forms; tests/test_gpu_ntt_edges.py runs the same inputs through the device code.  CPU only, about six minutes of pure Python
+(tests/test_ntt29_emulation.py runs a ten-second subset); run: python tools/check_ntt29.py"""
 import random, sys
 
 R = 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001
@@ -165,15 +168,22 @@ def root(log_n, inverse):
     return pow(w, R - 2, R) if inverse else w
 
 
-def ntt_lazy(x, log_n, inverse, coset, maxr=10):
-    """whole transform with the kernel's pass plan (Stockham index maps of ntt_pass), lazy arithmetic, natural in / out"""
-    n = 1 << log_n
+def pass_radices(log_n, maxr=10):
+    """log_r of every pass (ntt_run_multi: as few passes as maxr allows, the larger radices first)"""
     npass = 1 if log_n <= maxr else (log_n + maxr - 1) // maxr
     radices, rem = [], log_n
     for p in range(npass):
         r = (rem + (npass - p) - 1) // (npass - p)
         radices.append(r)
         rem -= r
+    return radices
+
+
+def ntt_lazy(x, log_n, inverse, coset, maxr=10):
+    """whole transform with the kernel's pass plan (Stockham index maps of ntt_pass), lazy arithmetic, natural in / out"""
+    n = 1 << log_n
+    radices = pass_radices(log_n, maxr)
+    npass = len(radices)
     w = root(log_n, inverse)
     g = pow(GEN, R - 2, R) if inverse else GEN
     to29 = lambda v: limbs(v % R * R261 % R)          # twiddles: x 2^261 (Montgomery form of the lazy domain)
@@ -235,6 +245,157 @@ def dft(x, log_n, inverse, coset):
     return out
 
 
+# ---- inputs at the edges of the plan's bounds.  An input is a description, materialised here as Python integers and in
+# tests/test_gpu_ntt_edges.py as numpy limbs; the values are MEMORY integers (the transform is linear and the lazy kernel keeps the
+# factor the data came with, so r - 1 in memory is the extreme whatever it stands for):
+#   ("const", c)          every element c
+#   ("comb", p, hi)       r - 1 where bit p of the index is 0 and 0 elsewhere (hi = 1: the largest differences at the butterfly level
+#                         that pairs indices 2^p apart), or the complement (hi = 0: the most negative differences)
+#   ("single", i)         r - 1 at index i, 0 elsewhere
+#   ("fill", i, rev)      r - 1 everywhere except a 0 at index i (rev = 0), or the reverse (which is a single)
+#   ("orbit", s)          x_i = (r - 1) w^(s i): the forward transform is n (r - 1) at index -s mod n and exactly 0 elsewhere
+TOP = R - 1
+
+
+def edge_inputs(log_n, radix0=None, reduced=False):
+    """The input descriptions for a transform of 2^log_n elements whose first pass has radix 2^radix0.  reduced: the combs only at
+    the levels next to the pass boundary and at both ends (what the sizes above 2^13 run on the device)."""
+    n = 1 << log_n
+    radix0 = pass_radices(log_n)[0] if radix0 is None else radix0
+    stride = n >> radix0
+    ps = sorted({0, radix0 - 1, radix0, log_n - 1} & set(range(log_n))) if reduced else range(log_n)
+    out = [("const", TOP), ("const", 1), ("const", 0)]
+    out += [("comb", p, hi) for p in ps for hi in (1, 0)]
+    if not reduced:
+        out += [("single", i) for i in sorted({0, 1, n // 2 - 1, n // 2, n - 1, stride - 1, stride, stride + 1} & set(range(n)))]
+        out += [("fill", i, rev) for i in sorted({0, n - 1}) for rev in (0, 1)]
+    out += [("orbit", s) for s in sorted({1 % n, n // 2, n - 1})]
+    return out
+
+
+def materialize(d, log_n):
+    n = 1 << log_n
+    if d[0] == "const":
+        return [d[1]] * n
+    if d[0] == "comb":
+        return [TOP if ((i >> d[1]) & 1) != d[2] else 0 for i in range(n)]
+    if d[0] == "single":
+        return [TOP if i == d[1] else 0 for i in range(n)]
+    if d[0] == "fill":
+        return [(TOP if i == d[1] else 0) if d[2] else (0 if i == d[1] else TOP) for i in range(n)]
+    assert d[0] == "orbit"
+    w, x, out = pow(root(log_n, False), d[1], R), TOP, []
+    for i in range(n):
+        out.append(x)
+        x = x * w % R
+    return out
+
+
+_powers = {}
+
+
+def root_powers(log_n):
+    if log_n not in _powers:
+        w, x, t = root(log_n, False), 1, []
+        for i in range(1 << log_n):
+            t.append(x)
+            x = x * w % R
+        _powers[log_n] = t
+    return _powers[log_n]
+
+
+def closed_form(d, log_n, inverse, coset):
+    """The transform of input d in Python integers WITHOUT a transform: the polynomial sum x_i z^i of every family has a closed
+    form, evaluated at z_k = 22^coset w^k (forward) or w^-k (inverse, then 1/n and 22^-k)."""
+    n, W = 1 << log_n, root_powers(log_n)
+    mask = n - 1
+    sgn = -1 if inverse else 1
+    g = GEN if (coset and not inverse) else 1          # z_k = g w^(sgn k)
+    gn = pow(g, n, R)                                   # z_k^n
+    gpow = [pow(g, 1 << b, R) for b in range(log_n)]
+
+    def geom(ys):                                       # sum_{i < n} y^i for every y of ys (y^n = gn), one inversion for all
+        den = [(y - 1) % R or 1 for y in ys]
+        pre, acc = [], 1
+        for v in den:
+            pre.append(acc)
+            acc = acc * v % R
+        inv, out = pow(acc, -1, R), [0] * len(ys)
+        for k in range(len(ys) - 1, -1, -1):
+            out[k] = n % R if ys[k] == 1 else (gn - 1) * (inv * pre[k] % R) % R
+            inv = inv * den[k] % R
+        return out
+
+    def z_pow(k, e):                                    # z_k^e
+        return pow(g, e, R) * W[(sgn * k * e) & mask] % R
+
+    def poly(d):
+        if d[0] == "const":
+            return [d[1] * v % R for v in geom([g * W[(sgn * k) & mask] % R for k in range(n)])]
+        if d[0] == "single":
+            return [TOP * z_pow(k, d[1]) % R for k in range(n)]
+        if d[0] == "fill":
+            one = poly(("single", d[1]))
+            return one if d[2] else [(a - b) % R for a, b in zip(poly(("const", TOP)), one)]
+        if d[0] == "orbit":
+            return [TOP * v % R for v in geom([g * W[(d[1] + sgn * k) & mask] % R for k in range(n)])]
+        assert d[0] == "comb"                           # prod over b != p of (1 + z^(2^b)), times z^(2^p) for the complement
+        out = []
+        for k in range(n):
+            acc = TOP if d[2] else TOP * gpow[d[1]] % R * W[((sgn * k) << d[1]) & mask] % R
+            for b in range(log_n):
+                if b != d[1]:
+                    acc = acc * (1 + gpow[b] * W[((sgn * k) << b) & mask]) % R
+            out.append(acc)
+        return out
+
+    out = poly(d)
+    if inverse:
+        ni, gi, s = pow(n, -1, R), pow(GEN, -1, R) if coset else 1, 1
+        for k in range(n):
+            out[k] = out[k] * ni % R * s % R
+            s = s * gi % R
+    return out
+
+
+def tile_patterns(log_r, b0):
+    """Whole tiles at the input bound b0 r of a pass: all at the top, all zero, and top / 0 alternating at every butterfly distance"""
+    Rn, top = 1 << log_r, b0 * R - 1
+    yield [top] * Rn
+    yield [0] * Rn
+    for p in range(log_r):
+        for hi in (1, 0):
+            yield [top if ((i >> p) & 1) != hi else 0 for i in range(Rn)]
+
+
+def check_tiles(max_log_r):
+    """every pattern through one tile of every size up to 2^max_log_r and both input bounds: only the assertions speak"""
+    count = 0
+    for log_r in range(1, max_log_r + 1):
+        tw = [limbs(pow(root(log_r, False), e, R) * R261 % R) for e in range(max((1 << log_r) >> 1, 1))]
+        for b0 in (1, 2):
+            for xs in tile_patterns(log_r, b0):
+                tile_transform([limbs(v) for v in xs], log_r, tw, b0)
+                count += 1
+    return count
+
+
+def check_edge_transforms(plans, variants=((False, False), (False, True), (True, False), (True, True)), reduced=False):
+    """whole transforms of the edge inputs with the kernel's plan against the closed forms (and so the closed forms, which the
+    device test uses, against the emulated arithmetic)"""
+    count = 0
+    for log_n, maxr in plans:
+        for d in edge_inputs(log_n, pass_radices(log_n, maxr)[0], reduced):
+            x = materialize(d, log_n)
+            for inverse, coset in variants:
+                assert ntt_lazy(x, log_n, inverse, coset, maxr) == closed_form(d, log_n, inverse, coset), (d, log_n, maxr, inverse, coset)
+                count += 1
+    return count
+
+
+PLANS = ((1, 10), (2, 10), (3, 10), (5, 10), (6, 10), (7, 3), (8, 4), (9, 3), (6, 2), (10, 10))
+
+
 def main():
     random.seed(11)
     # worst-case limbs through one multiplication: lazy operand with every lower limb at 2.5 * 2^30 and the value at the 446 r edge
@@ -248,13 +409,21 @@ def main():
             xs[0] = limbs(b0 * R - 1)
             tile_transform(xs, log_r, tw, b0)
     checked = 0
-    for log_n, maxr in ((1, 10), (2, 10), (3, 10), (5, 10), (6, 10), (7, 3), (8, 4), (9, 3), (6, 2), (10, 10)):
+    for log_n, maxr in PLANS:
         x = [random.randrange(R) for _ in range(1 << log_n)]
         for inverse in (False, True):
             for coset in (False, True):
                 assert ntt_lazy(x, log_n, inverse, coset, maxr) == dft(x, log_n, inverse, coset), (log_n, maxr, inverse, coset)
                 checked += 1
-    print("fr29 emulation OK: %d transforms equal the direct DFT; no uint32 / uint64 wrap, all plan bounds hold" % checked)
+    for log_n in (1, 2, 3, 5, 6):                    # the closed forms themselves against the direct DFT (quadratic: small sizes)
+        for d in edge_inputs(log_n):
+            for inverse in (False, True):
+                for coset in (False, True):
+                    assert closed_form(d, log_n, inverse, coset) == dft(materialize(d, log_n), log_n, inverse, coset), (d, log_n)
+    tiles = check_tiles(12)
+    edges = check_edge_transforms(PLANS)
+    print("fr29 emulation OK: %d transforms equal the direct DFT, %d extremal tiles and %d transforms of extremal inputs (equal to "
+          "their closed forms); no uint32 / uint64 wrap, all plan bounds hold" % (checked, tiles, edges))
 
 
 if __name__ == "__main__":
