@@ -14,6 +14,7 @@
 #include <chrono>
 #include <functional>
 #include <memory>
+#include <type_traits>
 #include "devops.cuh"
 #include "g1.cuh"
 #include "host/ahp.h"
@@ -1167,6 +1168,10 @@ static Fr fr_half() { return fp_inv(fp_from_u64<Fr>(2)); }
 // alpha^|H| - X^|H| on the 4|H| domain, where X^|H| = i4^(i mod 4), i4 = w4^|H| a primitive fourth root of unity
 struct RAlphaNumerators {
     Fr n0, n1, n2, n3;
+    __device__ __forceinline__ Fr at(size_t i) const {
+        const unsigned q = (unsigned)(i & 3);
+        return q == 0 ? n0 : q == 1 ? n1 : q == 2 ? n2 : n3;
+    }
 };
 RAlphaNumerators r_alpha_numerators(const Fr& alpha, unsigned logH, uint64_t M) {
     Fr aH = alpha;
@@ -1174,6 +1179,36 @@ RAlphaNumerators r_alpha_numerators(const Fr& alpha, unsigned logH, uint64_t M) 
     Fr i4 = HDomain(M).gen;
     for (unsigned i = 0; i < logH; i++) i4 = fp_sqr(i4);
     return {fp_sub(aH, fp_one<Fr>()), fp_sub(aH, i4), fp_sub(aH, fp_sqr(i4)), fp_sub(aH, fp_mul(fp_sqr(i4), i4))};
+}
+// Which point i of a product domain (4|H| in round 2, 4|K| in round 3; D = H or K) position p of a buffer of evaluations holds:
+//   dense:  point p;
+//   blocks: a rank's share of a sharded proof (the BLOCKS layout of ntt.hip), `loc` points in blocks of `blk`;
+//   cosets: point 4 j + k at k |D| + j (coset k of D in one piece).
+struct DenseMap {
+    __host__ __device__ size_t index(size_t p) const { return p; }
+};
+struct BlocksMap {
+    size_t loc, blk, rank;
+    __host__ __device__ size_t index(size_t p) const { return loc * (p / blk) + rank * blk + (p % blk); }
+};
+struct CosetsMap {
+    unsigned logD;
+    __host__ __device__ size_t index(size_t p) const { return ((p & (((size_t)1 << logD) - 1)) << 2) + (p >> logD); }
+    __host__ __device__ size_t position(size_t i) const { return ((i & 3) << logD) + (i >> 2); }
+};
+// f(map) for the layout of a round: `sharded` (a share of `loc` points), else `cosets` of a domain of 2^logD points, else dense.
+// f is instantiated once per layout, and so is every pointwise kernel in it: none of them branches on the layout.
+template <class F>
+void with_product_map(const ShardPlan& sp, bool sharded, size_t loc, bool cosets, unsigned logD, F&& f) {
+    if (sharded) f(BlocksMap{loc, loc / sp.SG, sp.rank});
+    else if (cosets) f(CosetsMap{logD});
+    else f(DenseMap{});
+}
+// round 2's outer-sumcheck form at one point: q_1 - mask = r(alpha, .) (eta_c z_A z_B + eta_a z_A + eta_b z_B) - z t
+__device__ __forceinline__ Fr round2_outer_form(const Fr& eta_a, const Fr& eta_b, const Fr& eta_c, const Fr& ra, const Fr& a,
+                                                const Fr& b, const Fr& z, const Fr& t) {
+    const Fr summed = fp_add(fp_add(fp_mul(eta_c, fp_mul(a, b)), fp_mul(eta_a, a)), fp_mul(eta_b, b));
+    return fp_sub(fp_mul(ra, summed), fp_mul(z, t));
 }
 // round 3's a - b f at point i of the 4|K| domain, from the index's twelve evaluations there
 struct IndexOnB {
@@ -1222,7 +1257,7 @@ struct ProveState {
     unsigned mask_pieces = 1;
     AsyncMsm mask_part[2];
     bool ra_closed_form = false;
-    bool cosets = false;  // round 2 on the cosets 0, 1, 2 of H (SWM_OUTER_COSETS): e_za, e_zb, e_z, e_ra hold cosets 1 | 2
+    bool cosets = false;  // round 2 on the cosets 0, 1, 2 of H (SWM_OUTER_COSETS): e_za, e_zb, e_z hold cosets 1 | 2
     LcSet lcs;
     DVec mask, z, za_evals, zb_evals, za_loc, zb_loc, x_poly, x_evals, w_poly, za_poly, zb_poly, e_za, e_zb, e_z;
     DVec r_alpha_evals, e_ra, t_poly, q1, h1, g1x, f, h2;
@@ -1442,26 +1477,23 @@ void round1_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
 // -> BLOCKS evaluations by ONE all-to-all each (ntt_sharded_run), pointwise on the blocks, BLOCKS -> CYCLIC back; the mask
 // and the division by v_H are local in the CYCLIC layout (G divides |H|: index j + k|H| stays on its rank).  h_1 and X g_1 are
 // all-gathered afterwards (4|H| x 32 B per proof): the openings work on whole polynomials.  SWM_SHARD_R2_OFF disables it.
-DVec on_mul_domain(swm_ctx* ctx, const ProveState& s, const Fr* coeffs, size_t n) {
-    if (!s.sp.r2) return dv_ntt_from(ctx, coeffs, n, s.logM, false);
-    return shard_evals(ctx, s.sp, coeffs, n, s.logM);
-}
-// ---- the challenge-independent part of round 2, issued before the round-1 commitments are awaited so that it runs under
-// them: z_A, z_B and z = w v_X + x in evaluation form on the 4|H| domain
-DVec on_cosets12(swm_ctx* ctx, const ProveState& s, const Fr* coeffs, size_t n) {
+// coeffs[0 .. n) in evaluation form in the proof's round-2 layout: the 4|H| domain, the rank's BLOCKS of it, or cosets 1 | 2 of H
+// (coset 0 is H itself and needs no transform)
+DVec on_round2_layout(swm_ctx* ctx, const ProveState& s, const Fr* coeffs, size_t n) {
+    if (s.sp.r2) return shard_evals(ctx, s.sp, coeffs, n, s.logM);
+    if (!s.cosets) return dv_ntt_from(ctx, coeffs, n, s.logM, false);
     static const unsigned ks[2] = {1, 2};
     DVec v(ctx, 2 * s.H);
     rc_check(ctx, ntt_cosets_fwd(ctx, coeffs, n, s.dh.log, ks, 2, v.p));
     return v;
 }
+// ---- the challenge-independent part of round 2, issued before the round-1 commitments are awaited so that it runs under
+// them: z_A, z_B and z = w v_X + x in evaluation form in the round's layout
 void round2_prework(swm_ctx* ctx, ProveState& s) {
     const uint64_t H = s.H, X = s.X;
-    // single-GPU rounds (the sharded ones and the r(alpha, X)-by-transforms test hook keep the 4|H| domain)
-    s.cosets = SWM_OUTER_COSETS && !s.sp.r1 && !s.sp.r2 && H >= OUTER_COSETS_MIN_H && s.mask_len == 3 * H &&
-               !sw(SW_RALPHA_TRANSFORMS);
-    auto on_domain = [&](const Fr* coeffs, size_t n) { return s.cosets ? on_cosets12(ctx, s, coeffs, n) : on_mul_domain(ctx, s, coeffs, n); };
-    s.e_za = on_domain(s.za_poly.p, H + 1);
-    s.e_zb = on_domain(s.zb_poly.p, H + 1);
+    s.cosets = SWM_OUTER_COSETS && !s.sp.r1 && !s.sp.r2 && H >= OUTER_COSETS_MIN_H;  // single-GPU rounds (the sharded ones keep 4|H|)
+    s.e_za = on_round2_layout(ctx, s, s.za_poly.p, H + 1);
+    s.e_zb = on_round2_layout(ctx, s, s.zb_poly.p, H + 1);
     DVec z_poly = dv_zeros(ctx, H + 1);
     Fr* out = z_poly.p;
     const Fr* wc = s.P_w.p;
@@ -1474,7 +1506,7 @@ void round2_prework(swm_ctx* ctx, ProveState& s) {
         if (i < X) v = fp_add(v, xp[i]);
         out[i] = v;
     });
-    s.e_z = on_domain(z_poly.p, H + 1);
+    s.e_z = on_round2_layout(ctx, s, z_poly.p, H + 1);
 }
 
 // ---- end of round 1: blinding, the rest of a mask committed in pieces, the commitments
@@ -1509,12 +1541,11 @@ void r_alpha_on_h(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
 }
 // ---- round 2: r(alpha, X) = (alpha^|H| - X^|H|) / (alpha - X) is needed on H (input of the transposed mat-vecs) and on the
 // 4|H| domain (outer sumcheck).  On the 4|H| domain X^|H| takes four values (r_alpha_numerators), so both come from ONE batch
-// inversion of alpha - w4^i over 4|H| points — instead of an inversion over H, an inverse transform of size |H| and a forward
-// one of size 4|H| (r03).  H is every fourth point of that domain.  (alpha on the 4|H| domain — probability 2^-231 — would
-// make a denominator vanish: the transforms are kept for that case, round2_q1.)
+// inversion of alpha - w4^i over the points of the round's layout — instead of an inversion over H, an inverse transform of size
+// |H| and a forward one into the layout (r03).  H is every fourth point of that domain.  (alpha on the 4|H| domain — probability
+// 2^-231 — would make a denominator vanish: the transforms are kept for that case, round2_q1; SWM_RALPHA_TRANSFORMS=1 takes it.)
 void r_alpha(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
     const Fr alpha = s.st.alpha;
-    const uint64_t M = s.M;
     s.r_alpha_evals = DVec(ctx, s.H);
     {
         Fr a4h = alpha;
@@ -1522,57 +1553,26 @@ void r_alpha(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
         s.ra_closed_form = !fp_is_one(a4h) && !sw(SW_RALPHA_TRANSFORMS);  // (test hook: the path of the 2^-231 case)
     }
     if (!s.ra_closed_form) return r_alpha_on_h(ctx, pk, s);
-    if (s.sp.r2) {
-        // the rank's BLOCKS indices of the 4|H| domain for the product form; r(alpha, .) on H (every rank needs all of it for the
-        // transposed mat-vecs) by its own inversion over |H| points
-        const size_t mloc = s.sp.Mloc, mblk = s.sp.Mblk, s_rank = s.sp.rank;
-        s.e_ra = DVec(ctx, mloc);
-        PowTable wt = root_pow_table(ctx, s.logM);
-        Fr* out = s.e_ra.p;
-        ew(ctx, "r_alpha_den", mloc, [=] __device__(size_t p) {
-            const size_t i = mloc * (p / mblk) + s_rank * mblk + (p % mblk);
-            out[p] = fp_sub(alpha, wt.at(i));
-        });
-        rc_check(ctx, batch_inverse_run(ctx, out, mloc));
-        const RAlphaNumerators nu = r_alpha_numerators(alpha, pk.logH, M);
-        ew(ctx, "r_alpha_scale", mloc, [=] __device__(size_t p) {
-            const size_t i = mloc * (p / mblk) + s_rank * mblk + (p % mblk);
-            const unsigned q = (unsigned)(i & 3);
-            out[p] = fp_mul(out[p], q == 0 ? nu.n0 : q == 1 ? nu.n1 : q == 2 ? nu.n2 : nu.n3);
-        });
-        r_alpha_on_h(ctx, pk, s);
-    } else if (s.cosets) {
-        // point i = 4 j + k of the 4|H| domain at k |H| + j: one inversion over the 3|H| points of cosets 0, 1, 2
-        const uint64_t H = s.H;
-        const unsigned logH = pk.logH;
-        s.e_ra = DVec(ctx, 3 * H);
-        PowTable wt = root_pow_table(ctx, s.logM);
-        Fr* out = s.e_ra.p;
-        ew(ctx, "r_alpha_den", 3 * H, [=] __device__(size_t p) { out[p] = fp_sub(alpha, wt.at(((p & (H - 1)) << 2) + (p >> logH))); });
-        rc_check(ctx, batch_inverse_run(ctx, out, 3 * H));
-        const RAlphaNumerators nu = r_alpha_numerators(alpha, pk.logH, M);
-        Fr* rh = s.r_alpha_evals.p;
-        ew(ctx, "r_alpha_scale", 3 * H, [=] __device__(size_t p) {
-            const size_t q = p >> logH;
-            Fr v = fp_mul(out[p], q == 0 ? nu.n0 : q == 1 ? nu.n1 : nu.n2);
+    // one inversion over the layout's points: the rank's BLOCKS, cosets 0 | 1 | 2 of H, or all of the 4|H| domain
+    const size_t n = s.cosets ? 3 * s.H : s.sp.Mloc;
+    s.e_ra = DVec(ctx, n);
+    PowTable wt = root_pow_table(ctx, s.logM);
+    Fr* out = s.e_ra.p;
+    Fr* rh = s.r_alpha_evals.p;
+    const RAlphaNumerators nu = r_alpha_numerators(alpha, pk.logH, s.M);
+    with_product_map(s.sp, s.sp.r2, n, s.cosets, pk.logH, [&](auto map) {
+        ew(ctx, "r_alpha_den", n, [=] __device__(size_t p) { out[p] = fp_sub(alpha, wt.at(map.index(p))); });
+        rc_check(ctx, batch_inverse_run(ctx, out, n));
+        ew(ctx, "r_alpha_scale", n, [=] __device__(size_t p) {
+            const size_t i = map.index(p);
+            const Fr v = fp_mul(out[p], nu.at(i));
             out[p] = v;
-            if (q == 0) rh[p] = v;
+            if constexpr (!std::is_same_v<decltype(map), BlocksMap>)
+                if ((i & 3) == 0) rh[i >> 2] = v;
         });
-    } else {
-        s.e_ra = DVec(ctx, M);
-        PowTable wt = root_pow_table(ctx, s.logM);
-        Fr* out = s.e_ra.p;
-        ew(ctx, "r_alpha_den", M, [=] __device__(size_t i) { out[i] = fp_sub(alpha, wt.at(i)); });
-        rc_check(ctx, batch_inverse_run(ctx, out, M));
-        const RAlphaNumerators nu = r_alpha_numerators(alpha, pk.logH, M);
-        Fr* rh = s.r_alpha_evals.p;
-        ew(ctx, "r_alpha_scale", M, [=] __device__(size_t i) {
-            const unsigned q = (unsigned)(i & 3);
-            Fr v = fp_mul(out[i], q == 0 ? nu.n0 : q == 1 ? nu.n1 : q == 2 ? nu.n2 : nu.n3);
-            out[i] = v;
-            if (q == 0) rh[i >> 2] = v;
-        });
-    }
+    });
+    // (a rank's share holds a part of H only, and every rank needs all of it for the transposed mat-vecs: its own inversion)
+    if (s.sp.r2) r_alpha_on_h(ctx, pk, s);
 }
 
 // ---- round 2: t evaluations on H, t[reindex(c)] = sum_M eta_M (M^T r_alpha)[c], interpolated, and its commitment
@@ -1607,9 +1607,7 @@ void round2_t(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
                     const size_t wi = k - k / ratio - 1;
                     zk = wi < nwit ? zz[ninst + wi] : fp_zero<Fr>();
                 }
-                const Fr a = za[k], b = zb[k];
-                const Fr summed = fp_add(fp_add(fp_mul(eta_c, fp_mul(a, b)), fp_mul(eta_a, a)), fp_mul(eta_b, b));
-                q[k] = fp_sub(fp_mul(rh[k], summed), fp_mul(zk, th[k]));
+                q[k] = round2_outer_form(eta_a, eta_b, eta_c, rh[k], za[k], zb[k], zk, th[k]);
             });
         }
         dv_ntt(ctx, s.t_poly, pk.logH, true);
@@ -1620,100 +1618,75 @@ void round2_t(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
     pc_commit_begin(ctx, pk, &s.lane, s.P_t.p, s.P_t.n, false, 0, false, &s.j2[0]);  // overlaps the 4|H|-domain work below
 }
 
-// ---- round 2: q_1 = r(alpha, X) sum_M eta_M z_M - t z + mask on the 4|H| domain, and (h_1, X g_1) = q_1 / v_H
-// On cosets 1 and 2 (coset 0 is in place since round2_t), back through three |H|-point inverse transforms, and the three blocks
-// of q_1 - mask recovered, the mask added and v_H divided out in one pass: h_1 = q[H, 3H) + q[2H, 3H) X^H, X g_1 = q0 + q1 + q2
-void round2_q1_cosets(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
-    const uint64_t H = s.H;
-    const Fr eta_a = s.st.eta_a, eta_b = s.st.eta_b, eta_c = s.st.eta_c;
-    if (!s.ra_closed_form) {
-        DVec ra_poly = dv_ntt_from(ctx, s.r_alpha_evals.p, H, pk.logH, true);
-        DVec e12 = on_cosets12(ctx, s, ra_poly.p, H);
-        s.e_ra = DVec(ctx, 3 * H);
-        hip_check(ctx, hipMemcpyAsync(s.e_ra.p + H, e12.p, 2 * H * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream), "copy");
-    }
-    {
-        DVec e_t = on_cosets12(ctx, s, s.t_poly.p, H);
-        Fr* out = s.q1.p + H;
-        const Fr *pra = s.e_ra.p + H, *pza = s.e_za.p, *pzb = s.e_zb.p, *pt = e_t.p, *pz = s.e_z.p;
-        ew(ctx, "round2_pointwise", 2 * H, [=] __device__(size_t i) {
-            Fr a = pza[i], b = pzb[i];
-            Fr summed = fp_add(fp_add(fp_mul(eta_c, fp_mul(a, b)), fp_mul(eta_a, a)), fp_mul(eta_b, b));
-            out[i] = fp_sub(fp_mul(pra[i], summed), fp_mul(pz[i], pt[i]));
-        });
-        s.e_za.release();
-        s.e_zb.release();
-        s.e_z.release();
-    }
-    rc_check(ctx, ntt_cosets_inv(ctx, s.q1.p, pk.logH, 3));
-    s.h1 = DVec(ctx, 3 * H);
-    s.g1x = DVec(ctx, H);
-    const Fr* q = s.q1.p;
-    const Fr* mp = s.mask.p;
-    Fr *h = s.h1.p, *g = s.g1x.p;
-    const Fr iota = HDomain(4).gen, half = fr_half();
-    ew(ctx, "q1_cosets_solve_div_vh", H, [=] __device__(size_t j) {
-        const Cosets3 c = cosets3_solve(q[j], q[j + H], q[j + 2 * H], iota, half);
-        const Fr p0 = fp_add(c.p0, mp[j]), p1 = fp_add(c.p1, mp[j + H]), p2 = fp_add(c.p2, mp[j + 2 * H]);
-        const Fr hj = fp_add(p1, p2);
-        h[j] = hj;
-        h[j + H] = p2;
-        h[j + 2 * H] = fp_zero<Fr>();
-        g[j] = fp_add(p0, hj);
-    });
-}
+// ---- round 2: q_1 = r(alpha, X) sum_M eta_M z_M - t z + mask in the round's layout, and (h_1, X g_1) = q_1 / v_H
+// On cosets the form covers cosets 1 | 2 (coset 0 is in place since round2_t); the way back is three |H|-point inverse transforms,
+// then the three blocks of q_1 - mask recovered, the mask added and v_H divided out in one pass: h_1 = q[H, 3H) + q[2H, 3H) X^H,
+// X g_1 = q0 + q1 + q2
 void round2_q1(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
-    if (s.cosets) return round2_q1_cosets(ctx, pk, s);
     const uint64_t H = s.H, M = s.M;
     const size_t Mloc = s.sp.Mloc;
     const Fr eta_a = s.st.eta_a, eta_b = s.st.eta_b, eta_c = s.st.eta_c;
-    s.q1 = DVec(ctx, Mloc);  // the whole product domain, or the rank's share of it (shard_r2)
+    const size_t off = s.cosets ? H : 0, n = s.cosets ? 2 * H : Mloc;  // what the form is evaluated on, and where in q1
+    if (!s.cosets) s.q1 = DVec(ctx, Mloc);  // the whole product domain, or the rank's share of it (shard_r2)
+    const Fr* mp = s.mask.p;
     {
+        const Fr* pra = s.e_ra.p + off;  // (r_alpha's closed form covers coset 0 too)
         if (!s.ra_closed_form) {
             DVec ra_poly = dv_ntt_from(ctx, s.r_alpha_evals.p, H, pk.logH, true);
-            s.e_ra = on_mul_domain(ctx, s, ra_poly.p, H);
+            s.e_ra = on_round2_layout(ctx, s, ra_poly.p, H);
+            pra = s.e_ra.p;
         }
-        DVec e_t = on_mul_domain(ctx, s, s.t_poly.p, H);
-        Fr* out = s.q1.p;
-        const Fr *pra = s.e_ra.p, *pza = s.e_za.p, *pzb = s.e_zb.p, *pt = e_t.p, *pz = s.e_z.p;
-        ew(ctx, "round2_pointwise", Mloc, [=] __device__(size_t i) {
-            Fr a = pza[i], b = pzb[i];
-            Fr summed = fp_add(fp_add(fp_mul(eta_c, fp_mul(a, b)), fp_mul(eta_a, a)), fp_mul(eta_b, b));
-            out[i] = fp_sub(fp_mul(pra[i], summed), fp_mul(pz[i], pt[i]));
+        DVec e_t = on_round2_layout(ctx, s, s.t_poly.p, H);
+        Fr* out = s.q1.p + off;
+        const Fr *pza = s.e_za.p, *pzb = s.e_zb.p, *pt = e_t.p, *pz = s.e_z.p;
+        ew(ctx, "round2_pointwise", n, [=] __device__(size_t i) {
+            out[i] = round2_outer_form(eta_a, eta_b, eta_c, pra[i], pza[i], pzb[i], pz[i], pt[i]);
         });
         s.e_za.release();
         s.e_zb.release();
         s.e_z.release();
-        const Fr* mp = s.mask.p;
-        const size_t mask_len = s.mask_len;
-        if (s.sp.r2) {
-            rc_check(ctx, ntt_sharded_run(ctx, s.q1.p, s.logM, 1, 1));  // BLOCKS evaluations -> CYCLIC coefficients: q1[j] = q_1[rank + G j]
-            const size_t s_rank = s.sp.rank, s_world = s.sp.SG;
-            ew(ctx, "q1_add_mask", Mloc, [=] __device__(size_t j) {
-                const size_t i = s_rank + s_world * j;
-                if (i < mask_len) out[j] = fp_add(out[j], mp[i]);
-            });
-        } else {
-            dv_ntt(ctx, s.q1, s.logM, true);
-            ew(ctx, "q1_add_mask", mask_len, [=] __device__(size_t i) { out[i] = fp_add(out[i], mp[i]); });
-        }
     }
     s.h1 = DVec(ctx, 3 * H);
     s.g1x = DVec(ctx, H);
-    if (!s.sp.r2) return div_vh(ctx, s.q1.p, H, M, s.h1.p, s.g1x.p);
-    const size_t Hl = H / s.sp.SG;
-    DVec loc(ctx, 4 * Hl), all(ctx, 4 * Hl * s.sp.SG);  // [h_1 share: 3 Hl | (X g_1) share: Hl]
-    div_vh(ctx, s.q1.p, Hl, Mloc, loc.p, loc.p + 3 * Hl);
-    rc_check(ctx, shard_allgather_dev(ctx, loc.p, 4 * Hl * sizeof(Fr), all.p));
-    Fr* ph = s.h1.p;
-    Fr* pg = s.g1x.p;
-    const Fr* pa = all.p;
-    const unsigned lg = s.sp.slog_g;
-    ew(ctx, "shard_interleave", 3 * H, [=] __device__(size_t i) {
-        const size_t r = i & (((size_t)1 << lg) - 1), j = i >> lg;
-        ph[i] = pa[r * 4 * Hl + j];
-        if (i < Hl << lg) pg[i] = pa[r * 4 * Hl + 3 * Hl + j];  // |H| of them
-    });
+    Fr* q = s.q1.p;
+    if (s.cosets) {
+        rc_check(ctx, ntt_cosets_inv(ctx, q, pk.logH, 3));
+        Fr *h = s.h1.p, *g = s.g1x.p;
+        const Fr iota = HDomain(4).gen, half = fr_half();
+        ew(ctx, "q1_cosets_solve_div_vh", H, [=] __device__(size_t j) {
+            const Cosets3 c = cosets3_solve(q[j], q[j + H], q[j + 2 * H], iota, half);
+            const Fr p0 = fp_add(c.p0, mp[j]), p1 = fp_add(c.p1, mp[j + H]), p2 = fp_add(c.p2, mp[j + 2 * H]);
+            const Fr hj = fp_add(p1, p2);
+            h[j] = hj;
+            h[j + H] = p2;
+            h[j + 2 * H] = fp_zero<Fr>();
+            g[j] = fp_add(p0, hj);
+        });
+    } else if (!s.sp.r2) {
+        dv_ntt(ctx, s.q1, s.logM, true);
+        ew(ctx, "q1_add_mask", s.mask_len, [=] __device__(size_t i) { q[i] = fp_add(q[i], mp[i]); });
+        div_vh(ctx, q, H, M, s.h1.p, s.g1x.p);
+    } else {
+        rc_check(ctx, ntt_sharded_run(ctx, q, s.logM, 1, 1));  // BLOCKS evaluations -> CYCLIC coefficients: q1[j] = q_1[rank + G j]
+        const size_t s_rank = s.sp.rank, s_world = s.sp.SG, mask_len = s.mask_len;
+        ew(ctx, "q1_add_mask", Mloc, [=] __device__(size_t j) {
+            const size_t i = s_rank + s_world * j;
+            if (i < mask_len) q[j] = fp_add(q[j], mp[i]);
+        });
+        const size_t Hl = H / s.sp.SG;
+        DVec loc(ctx, 4 * Hl), all(ctx, 4 * Hl * s.sp.SG);  // [h_1 share: 3 Hl | (X g_1) share: Hl]
+        div_vh(ctx, q, Hl, Mloc, loc.p, loc.p + 3 * Hl);
+        rc_check(ctx, shard_allgather_dev(ctx, loc.p, 4 * Hl * sizeof(Fr), all.p));
+        Fr* ph = s.h1.p;
+        Fr* pg = s.g1x.p;
+        const Fr* pa = all.p;
+        const unsigned lg = s.sp.slog_g;
+        ew(ctx, "shard_interleave", 3 * H, [=] __device__(size_t i) {
+            const size_t r = i & (((size_t)1 << lg) - 1), j = i >> lg;
+            ph[i] = pa[r * 4 * Hl + j];
+            if (i < Hl << lg) pg[i] = pa[r * 4 * Hl + 3 * Hl + j];  // |H| of them
+        });
+    }
 }
 
 // ---- round 2: the commitments to t, g_1, h_1 and the outer sumcheck's remainder check
@@ -1784,44 +1757,43 @@ void round3_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
                       pk.ar[1].row_B.p, pk.ar[1].col_B.p, pk.ar[1].row_col_B.p, pk.ar[1].val_B.p,
                       pk.ar[2].row_B.p, pk.ar[2].col_B.p, pk.ar[2].row_col_B.p, pk.ar[2].val_B.p};
     const Round3Challenges ch{alpha, beta, fp_mul(beta, alpha), eta_a, eta_b, eta_c, vhab};
-    if (s.sp.r3) {
-        const size_t Bloc = Bsz / s.sp.SG, Bblk = Bloc / s.sp.SG, Kl = K / s.sp.SG, s_rank = s.sp.rank;
-        DVec e_f = shard_evals(ctx, s.sp, s.f.p, K, pk.logB);
+    // f in the round's layout (cosets: 1 - 3 behind the kept coset 0, f_K), a - b f there, and back to coefficients.  On cosets
+    // only f is laid out that way: a - b f itself is dense, so that one 4|K|-point transform takes it back.
+    const size_t Bloc = s.sp.r3 ? Bsz / s.sp.SG : Bsz;
+    with_product_map(s.sp, s.sp.r3, Bloc, f_cosets, pk.logK, [&](auto map) {
+        constexpr bool blocks = std::is_same_v<decltype(map), BlocksMap>, cosets = std::is_same_v<decltype(map), CosetsMap>;
+        DVec e_f;
+        if constexpr (blocks) {
+            e_f = shard_evals(ctx, s.sp, s.f.p, K, pk.logB);
+        } else if constexpr (cosets) {
+            static const unsigned ks[3] = {1, 2, 3};
+            e_f = DVec(ctx, 3 * K);
+            rc_check(ctx, ntt_cosets_fwd(ctx, s.f.p, K, pk.logK, ks, 3, e_f.p));
+        } else {
+            e_f = dv_ntt_from(ctx, s.f.p, K, pk.logB, false);
+        }
         DVec ab(ctx, Bloc);
         Fr* out = ab.p;
-        const Fr* pf = e_f.p;
-        ew(ctx, "round3_pointwise_B", Bloc, [=] __device__(size_t p) {
-            const size_t i = Bloc * (p / Bblk) + s_rank * Bblk + (p % Bblk);  // BLOCKS: the rank's indices of the 4|K| domain
-            out[p] = round3_a_minus_bf(ix, ch, i, pf[p]);
-        });
-        rc_check(ctx, ntt_sharded_run(ctx, ab.p, pk.logB, 1, 1));  // -> CYCLIC coefficients: ab[j] = (a - b f)[rank + G j]
-        DVec loc(ctx, 3 * Kl);
-        div_vk(ctx, ab.p, Kl, Bloc, loc.p);
-        shard_gather_cyclic(ctx, loc.p, 3 * Kl, s.sp.slog_g, s.h2.p, 3 * K);
-    } else if (f_cosets) {
-        // point i of the 4|K| domain: f from coset i mod 4 at i / 4 (coset 0: the kept evaluations on K)
-        static const unsigned ks[3] = {1, 2, 3};
-        DVec e_f(ctx, 3 * K);
-        rc_check(ctx, ntt_cosets_fwd(ctx, s.f.p, K, pk.logK, ks, 3, e_f.p));
-        DVec ab(ctx, Bsz);
-        Fr* out = ab.p;
         const Fr *pf = e_f.p, *fk = f_K.p;
-        const unsigned logK = pk.logK;
-        ew(ctx, "round3_pointwise_B", Bsz, [=] __device__(size_t i) {
-            const size_t k = i & 3, j = i >> 2;
-            out[i] = round3_a_minus_bf(ix, ch, i, k ? pf[((k - 1) << logK) + j] : fk[j]);
+        ew(ctx, "round3_pointwise_B", Bloc, [=] __device__(size_t p) {
+            if constexpr (cosets) {
+                const size_t at = map.position(p);
+                out[p] = round3_a_minus_bf(ix, ch, p, at < K ? fk[at] : pf[at - K]);
+            } else {
+                out[p] = round3_a_minus_bf(ix, ch, map.index(p), pf[p]);
+            }
         });
-        dv_ntt(ctx, ab, pk.logB, true);
-        div_vk(ctx, ab.p, K, Bsz, s.h2.p);
-    } else {
-        DVec e_f = dv_ntt_from(ctx, s.f.p, K, pk.logB, false);
-        DVec ab(ctx, Bsz);
-        Fr* out = ab.p;
-        const Fr* pf = e_f.p;
-        ew(ctx, "round3_pointwise_B", Bsz, [=] __device__(size_t i) { out[i] = round3_a_minus_bf(ix, ch, i, pf[i]); });
-        dv_ntt(ctx, ab, pk.logB, true);
-        div_vk(ctx, ab.p, K, Bsz, s.h2.p);
-    }
+        if constexpr (blocks) {
+            const size_t Kl = K / s.sp.SG;
+            rc_check(ctx, ntt_sharded_run(ctx, ab.p, pk.logB, 1, 1));  // -> CYCLIC coefficients: ab[j] = (a - b f)[rank + G j]
+            DVec loc(ctx, 3 * Kl);
+            div_vk(ctx, ab.p, Kl, Bloc, loc.p);
+            shard_gather_cyclic(ctx, loc.p, 3 * Kl, s.sp.slog_g, s.h2.p, 3 * K);
+        } else {
+            dv_ntt(ctx, ab, pk.logB, true);
+            div_vk(ctx, ab.p, K, Bsz, s.h2.p);
+        }
+    });
     s.P_h2.p = s.h2.p;
     s.P_h2.n = 3 * K >= 3 ? 3 * K - 3 : 0;  // degree <= 3|K| - 4
 }

@@ -861,6 +861,35 @@ def test_sharded_round1_golden_bytes_2p12(M, S, W, world):
         assert exchanges >= 4 + 4 + 6 + 3, exchanges   # + round 3: f into the 4|K| domain and back, the all-gather of h_2
 
 
+@pytest.mark.parametrize("name", ["synthetic_8", "synthetic_32", "synthetic_2p12"])
+def test_ralpha_by_transforms_in_every_layout(M, S, W, name, monkeypatch):
+    """SWM_RALPHA_TRANSFORMS=1 (r(alpha, X) rebuilt by transforms: what a proof does when alpha lands on the 4|H| domain) under the
+    layout the proof takes anyway, at the smallest shape of each: dense (|H| = 8 < 16), cosets 1 | 2 of H (|H| = 32) and a
+    rank's BLOCKS (2^12 constraints over two thread-ranks).  The model's bytes, and the proof verifies."""
+    monkeypatch.setenv("SWM_RALPHA_TRANSFORMS", "1")
+    sharded = name == "synthetic_2p12"
+    case = golden("marlin_large.json" if sharded else "marlin.json")[name]
+    if sharded:
+        cs, public = W.synthetic_r1cs(case["num_constraints"], h2i(case["a"]), h2i(case["b"]))
+    else:
+        cs = W.synthetic_circuit(case["num_constraints"], h2i(case["a"]), h2i(case["b"]))
+        public = [h2i(x) for x in case["public_input"]]
+
+    def build(ctx):
+        rng = M.generate_rand()
+        srs = M.generate_universal_srs(*case["srs"], rng, ctx=ctx)
+        pk, vk = M.generate_proving_and_verifying_keys(srs, cs)
+        proof = M.generate_proof(cs, pk, rng)
+        out = (S.serialize_proof(proof).hex(), M.verify_proof(vk, public, proof, rng))
+        pk.free()
+        srs.free()
+        return out
+
+    for proof_hex, accepted in (_run_sharded(2, build) if sharded else [build(None)]):
+        assert proof_hex == case["proof"]
+        assert accepted
+
+
 @pytest.mark.parametrize("split", ["SWM_SHARD_RANGE", "SWM_SHARD_BUCKETS"])
 def test_sharded_small_key_by_ranges_golden_bytes_2p12(M, S, W, split, monkeypatch):
     """The other two splits of the commitments on a SMALL key (2^12 constraints: low-latency schedule, accumulation and bucket
