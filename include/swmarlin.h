@@ -347,6 +347,42 @@ int swm_merkle_tree_build(swm_ctx *ctx, const swm_pedersen *leaf_params, const s
 int swm_merkle_tree_build_dev(swm_ctx *ctx, const swm_pedersen *leaf_params, const swm_pedersen *two_to_one_params,
                               const void *d_leaves, size_t leaf_len, size_t n_leaves, void *d_nodes);
 
+/* ---------------------------------------------------------------------------------------------- Schnorr signatures
+ * The reference's native signature scheme, SimpleSchnorr = Schnorr<EdwardsProjective> on ed-on-BLS12-377, batched: one GPU lane per
+ * key, signature or check.  Replaces, on the GPU,
+ *   src/schnorr_signature/schnorr.rs:57-62     setup: generator = prime_subgroup_generator(), salt = None
+ *   src/schnorr_signature/schnorr.rs:64-80     keygen: pk = x G
+ *   src/schnorr_signature/schnorr.rs:82-124    sign: R = k G, e = Blake2s([salt] || pk || R || message), s = k - e x
+ *   src/schnorr_signature/schnorr.rs:126-160   verify: R' = s G + e pk, accept iff Blake2s([salt] || pk || R' || message) == e
+ * (callers: examples/schnorr-signature/main.rs:79-100, examples/simple-payments).  e enters the arithmetic as
+ * from_le_bytes_mod_order of the 32 digest bytes.  The random draws of keygen and sign stay with the caller, who hands in the
+ * secret keys and one nonce per signature.
+ * Wire forms.  A point: x || y, 32 little-endian bytes each in standard form (to_bytes! of the twisted Edwards affine point [U];
+ * the same bytes that enter the hash).  A secret key or nonce: 32 little-endian bytes, < the group order
+ * l = 2111115437357092606062206234695386632838870926408408195193685246394721360383.  A signature: prover_response (32 little-endian
+ * bytes) || verifier_challenge (32 bytes), schnorr.rs:43-46.  Messages: `count` messages of `msg_len` bytes back to back; msg_len = 0
+ * is legal and `messages` may then be NULL.
+ * swm_schnorr_create: Parameters { generator, salt } resident on the GPU with a table of the generator's window multiples.  An
+ * off-curve generator (or a coordinate >= r) is refused with SWM_ERR_INVALID_ARG.
+ * swm_schnorr_keygen / swm_schnorr_sign: a secret or nonce >= l, or a public key off the curve, refuses the WHOLE call with
+ * SWM_ERR_INVALID_ARG and nothing is written.  sign hashes public_keys_xy[i] as given (sk.public_key of the reference).
+ * swm_schnorr_verify: ok[i] = 1 iff signature i verifies.  A response >= l or a public key off the curve (no arkworks value holds
+ * either) gives ok[i] = 0; the call still returns SWM_OK.  An on-curve key outside the prime subgroup is computed exactly as
+ * pk.mul(e) with the reduced e: the addition law is complete on the whole curve.
+ * swm_schnorr_commitments: the claimed commitment s G + e pk of schnorr.rs:140-143 as affine bytes, from the signature's two halves
+ * alone — what makes the arithmetic testable at inputs no valid signature reaches.  A key off the curve or a response >= l refuses
+ * the call.  count = 0 returns SWM_OK everywhere and launches nothing. */
+typedef struct swm_schnorr swm_schnorr;
+int swm_schnorr_create(swm_ctx *ctx, const uint8_t generator_xy[64], const uint8_t *salt32_or_null, swm_schnorr **out);
+void swm_schnorr_destroy(swm_ctx *ctx, swm_schnorr *params);
+int swm_schnorr_keygen(swm_ctx *ctx, const swm_schnorr *params, const uint8_t *secret_keys, size_t count, uint8_t *public_keys_xy);
+int swm_schnorr_sign(swm_ctx *ctx, const swm_schnorr *params, const uint8_t *secret_keys, const uint8_t *public_keys_xy,
+                     const uint8_t *nonces, const uint8_t *messages, size_t msg_len, size_t count, uint8_t *signatures);
+int swm_schnorr_verify(swm_ctx *ctx, const swm_schnorr *params, const uint8_t *public_keys_xy, const uint8_t *messages, size_t msg_len,
+                       const uint8_t *signatures, size_t count, uint8_t *ok);
+int swm_schnorr_commitments(swm_ctx *ctx, const swm_schnorr *params, const uint8_t *public_keys_xy, const uint8_t *signatures,
+                            size_t count, uint8_t *commitments_xy);
+
 /* ---------------------------------------------------------------------------------------------- one proof over several GPUs
  * every commitment MSM of swm_generate_proof / swm_generate_proving_and_verifying_keys is split by
  * point range — rank g of `world` takes coefficients and SRS powers [g n / world, (g+1) n / world) — and the

@@ -6,6 +6,7 @@ Layout (only what the path needs):
   _lib.py          ctypes binding of include/swmarlin.h (fails loudly when the library or the GPU is missing)
   marlin.py        mirror of src/marlin/mod.rs (generate_universal_srs / ..._keys / generate_proof / verify_proof)
   serialization.py mirror of src/marlin/serialization.rs
+  hash.py          mirror of src/hash/mod.rs (Pedersen CRH) and the MerkleTree calls; schnorr.py: mirror of src/schnorr_signature/schnorr.rs
   workloads.py     the BASELINE.json circuits; dist.py: one proof / one MSM over several GPUs
 
 There is no CPU fallback anywhere in this package; the CPU oracle lives in oracle/ and is test infrastructure.

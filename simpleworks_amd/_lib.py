@@ -97,6 +97,12 @@ ABI = {
     "swm_pedersen_hash_dev": (_int, [_vp, _vp, _vp, _sz, _sz, _vp]),
     "swm_merkle_tree_build": (_int, [_vp, _vp, _vp, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
     "swm_merkle_tree_build_dev": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp]),
+    "swm_schnorr_create": (_int, [_vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_vp)]),
+    "swm_schnorr_destroy": (None, [_vp, _vp]),
+    "swm_schnorr_keygen": (_int, [_vp, _vp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_schnorr_sign": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
+    "swm_schnorr_verify": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_schnorr_commitments": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
     "swm_profile_enable": (_int, [_vp, _int]),
     "swm_profile_reset": (_int, [_vp]),
     "swm_profile_json": (_int, [_vp, ctypes.c_char_p, _sz]),
@@ -422,6 +428,65 @@ class Context:
     def merkle_tree_build_dev(self, leaf_handle, two_to_one_handle, d_leaves, leaf_len, n_leaves, d_nodes):
         self._check(self.lib.swm_merkle_tree_build_dev(self.h, leaf_handle, two_to_one_handle, d_leaves.ptr, leaf_len, n_leaves,
                                                        d_nodes.ptr), "swm_merkle_tree_build_dev")
+
+    # ---- Schnorr signatures (include/swmarlin.h; simpleworks_amd/schnorr.py is the caller-facing mirror)
+    @staticmethod
+    def _rows(a, width, count=None):
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        assert a.ndim == 2 and (width is None or a.shape[1] == width) and (count is None or a.shape[0] == count), a.shape
+        return a
+
+    def schnorr_create(self, generator_xy, salt=None):
+        """generator_xy: 64 bytes (x || y, little-endian standard form); salt: 32 bytes or None."""
+        g = np.frombuffer(bytes(generator_xy), dtype=np.uint8)
+        assert g.size == 64 and (salt is None or len(salt) == 32)
+        s = np.frombuffer(bytes(salt), dtype=np.uint8) if salt is not None else None
+        h = _vp()
+        self._check(self.lib.swm_schnorr_create(self.h, g.ctypes.data, s.ctypes.data if s is not None else None, ctypes.byref(h)),
+                    "swm_schnorr_create")
+        return h
+
+    def schnorr_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_schnorr_destroy(self.h, handle)
+
+    def schnorr_keygen(self, handle, secret_keys, out=None):
+        """secret_keys: uint8 [count, 32] -> uint8 [count, 64] public keys (x || y)."""
+        sk = self._rows(secret_keys, 32)
+        out = np.empty((sk.shape[0], 64), dtype=np.uint8) if out is None else out
+        self._check(self.lib.swm_schnorr_keygen(self.h, handle, sk.ctypes.data, sk.shape[0], out.ctypes.data), "swm_schnorr_keygen")
+        return out
+
+    def schnorr_sign(self, handle, secret_keys, public_keys, nonces, messages, out=None):
+        """messages: uint8 [count, msg_len] (msg_len may be 0) -> uint8 [count, 64] signatures (response || challenge)."""
+        sk = self._rows(secret_keys, 32)
+        n = sk.shape[0]
+        pk, k = self._rows(public_keys, 64, n), self._rows(nonces, 32, n)
+        m = self._rows(messages, None, n)
+        out = np.empty((n, 64), dtype=np.uint8) if out is None else out
+        self._check(self.lib.swm_schnorr_sign(self.h, handle, sk.ctypes.data, pk.ctypes.data, k.ctypes.data,
+                                              m.ctypes.data if m.shape[1] else None, m.shape[1], n, out.ctypes.data), "swm_schnorr_sign")
+        return out
+
+    def schnorr_verify(self, handle, public_keys, messages, signatures):
+        """-> uint8 [count]: 1 where the signature verifies."""
+        pk = self._rows(public_keys, 64)
+        n = pk.shape[0]
+        sig = self._rows(signatures, 64, n)
+        m = self._rows(messages, None, n)
+        ok = np.empty(n, dtype=np.uint8)
+        self._check(self.lib.swm_schnorr_verify(self.h, handle, pk.ctypes.data, m.ctypes.data if m.shape[1] else None, m.shape[1],
+                                                sig.ctypes.data, n, ok.ctypes.data), "swm_schnorr_verify")
+        return ok
+
+    def schnorr_commitments(self, handle, public_keys, signatures, out=None):
+        """-> uint8 [count, 64]: s G + e pk of every (public key, signature), affine x || y."""
+        pk = self._rows(public_keys, 64)
+        sig = self._rows(signatures, 64, pk.shape[0])
+        out = np.empty((pk.shape[0], 64), dtype=np.uint8) if out is None else out
+        self._check(self.lib.swm_schnorr_commitments(self.h, handle, pk.ctypes.data, sig.ctypes.data, pk.shape[0], out.ctypes.data),
+                    "swm_schnorr_commitments")
+        return out
 
     # ---- measurement
     def profile_enable(self, on=True):

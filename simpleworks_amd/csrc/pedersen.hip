@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "context.h"
+#include "ed.cuh"
 #include "ff.cuh"
 #include "frinv.cuh"
 #include "swmarlin.h"
@@ -34,58 +35,6 @@ struct swm_pedersen {
 };
 
 namespace swm {
-
-struct EdExt {
-    Fr x, y, t, z;
-};
-struct EdRow {  // an affine point as the mixed addition wants it; the identity is (1, 1, 0)
-    Fr ymx, ypx, kt;
-};
-static constexpr uint64_t ED_D = 3021;
-
-SWM_HD EdExt ed_identity() {
-    EdExt p;
-    p.x = fp_zero<Fr>();
-    p.y = fp_one<Fr>();
-    p.t = fp_zero<Fr>();
-    p.z = fp_one<Fr>();
-    return p;
-}
-// add-2008-hwcd-3 (a = -1), 8 multiplications + one by 2d
-SWM_HD EdExt ed_add(const EdExt& p, const EdExt& q, const Fr& k2d) {
-    Fr a = fp_mul(fp_sub(p.y, p.x), fp_sub(q.y, q.x));
-    Fr b = fp_mul(fp_add(p.y, p.x), fp_add(q.y, q.x));
-    Fr c = fp_mul(fp_mul(p.t, k2d), q.t);
-    Fr d = fp_dbl(fp_mul(p.z, q.z));
-    Fr e = fp_sub(b, a), f = fp_sub(d, c), g = fp_add(d, c), h = fp_add(b, a);
-    EdExt r;
-    r.x = fp_mul(e, f);
-    r.y = fp_mul(g, h);
-    r.t = fp_mul(e, h);
-    r.z = fp_mul(f, g);
-    return r;
-}
-// madd-2008-hwcd-3 against a tabulated affine point: 7 multiplications
-SWM_HD void ed_madd(EdExt& p, const EdRow& q) {
-    Fr a = fp_mul(fp_sub(p.y, p.x), q.ymx);
-    Fr b = fp_mul(fp_add(p.y, p.x), q.ypx);
-    Fr c = fp_mul(p.t, q.kt);
-    Fr d = fp_dbl(p.z);
-    Fr e = fp_sub(b, a), f = fp_sub(d, c), g = fp_add(d, c), h = fp_add(b, a);
-    p.x = fp_mul(e, f);
-    p.y = fp_mul(g, h);
-    p.t = fp_mul(e, h);
-    p.z = fp_mul(f, g);
-}
-
-__device__ __forceinline__ EdExt ed_shfl_xor(const EdExt& p, int mask) {
-    EdExt r;
-    const uint32_t* s = reinterpret_cast<const uint32_t*>(&p);
-    uint32_t* d = reinterpret_cast<uint32_t*>(&r);
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(EdExt) / 4); i++) d[i] = (uint32_t)__shfl_xor((int)s[i], mask, 64);
-    return r;
-}
 
 // `count` hashes, `lanes` (a power of two <= 64) lanes each.  Input h = in[h * stride .. + len), digest h = 32 bytes at out[32 h].
 __global__ void __launch_bounds__(256) pedersen_hash_kernel(const EdRow* __restrict__ table, unsigned num_windows, unsigned ws,

@@ -1,0 +1,599 @@
+// schnorr.hip — the reference's native Schnorr scheme on ed-on-BLS12-377, batched: keygen, sign and verify with one lane per item.
+//
+// What the reference does there (src/schnorr_signature/schnorr.rs, SimpleSchnorr = Schnorr<EdwardsProjective>, one call per item):
+//   :57-62     setup    salt = None, generator = prime_subgroup_generator()
+//   :64-80     keygen   x = ScalarField::rand, pk = x G
+//   :82-124    sign     k = ScalarField::rand, R = k G, e = Blake2s([salt] || to_bytes![pk] || to_bytes![R] || message),
+//                       s = k - from_le_bytes_mod_order(e) x; the signature is (s, e)
+//   :126-160   verify   R' = s G + from_le_bytes_mod_order(e) pk; accept iff Blake2s([salt] || pk || R' || message) == e
+// to_bytes! of an affine point is x || y, 32 little-endian bytes each in standard form [U].
+//
+// On the GPU.  The curve is pedersen.hip's (ed.cuh over ff.cuh's Fr).  s G comes from a table of the generator's window
+// multiples, 32 windows of 8 bits (768 KB, resident in L2): one mixed addition per non-zero byte of s.  e Y is a signed
+// 4-bit-digit ladder over a per-signature table of 1 Y .. 8 Y in cached form: e + 0x0777..7 read nibble by nibble gives the 63
+// digits nibble - 7 in [-7, 8], so there is no carry chain; 4 doublings and at most one addition per digit.  That table is 1 KB
+// per lane and indexed at run time, so it lives in a global buffer laid out [entry][word][signature]: lanes that pick the same
+// entry read neighbouring words.  One inversion per item (frinv.cuh), then the hash, streamed block by block from the five
+// 32-byte pieces and the message without assembling the input anywhere.
+// The scalar field (order l, 251 bits) needs no Montgomery form: a canonical test, a reduction of 256 bits by at most six
+// conditional subtractions (2^256 / l < 55), and for signing one 256 x 256 product reduced bit by bit.
+// The addition law is complete (ed.cuh): identity, doublings, keys of order 2 and 4 and e = 0 take the common path.
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "context.h"
+#include "ed.cuh"
+#include "ff.cuh"
+#include "frinv.cuh"
+#include "swmarlin.h"
+
+namespace swm {
+
+// ---------------------------------------------------------------------------------------------- the scalar field
+struct EdScalar {  // l = 2111115437357092606062206234695386632838870926408408195193685246394721360383, little-endian words
+    static constexpr uint32_t L[8] = {0xc33fd9ffu, 0xb95aee9au, 0xc43c8afeu, 0x5293a3afu, 0x970dec00u, 0x982d1347u, 0xa68b2955u, 0x04aad957u};
+};
+// word i of l 2^k, k <= 5 (l < 2^251)
+SWM_HD constexpr uint32_t sc_l_shifted(int i, int k) {
+    return k == 0 ? EdScalar::L[i] : (EdScalar::L[i] << k) | (i ? EdScalar::L[i - 1] >> (32 - k) : 0u);
+}
+// a -= l 2^K when that does not go negative; returns whether it subtracted
+template <int K> SWM_HD bool sc_cond_sub(uint32_t (&a)[8]) {
+    uint32_t d[8], borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        uint64_t t = (uint64_t)a[i] - sc_l_shifted(i, K) - borrow;
+        d[i] = (uint32_t)t;
+        borrow = (uint32_t)(t >> 63);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) a[i] = borrow ? a[i] : d[i];
+    return borrow == 0;
+}
+SWM_HD bool sc_is_canonical(const uint32_t (&a)[8]) {
+    uint32_t t[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) t[i] = a[i];
+    return !sc_cond_sub<0>(t);
+}
+// from_le_bytes_mod_order of 32 bytes: a < 2^256 < 55 l, so the quotient has six bits
+SWM_HD void sc_reduce(uint32_t (&a)[8]) {
+    sc_cond_sub<5>(a);
+    sc_cond_sub<4>(a);
+    sc_cond_sub<3>(a);
+    sc_cond_sub<2>(a);
+    sc_cond_sub<1>(a);
+    sc_cond_sub<0>(a);
+}
+// k - x e mod l (k, x, e < l): schoolbook product, then one shift-and-subtract step per bit.  Once per signature, beside
+// the ~2 000 field products of k G.
+SWM_HD void sc_mulsub(const uint32_t (&k)[8], const uint32_t (&x)[8], const uint32_t (&e)[8], uint32_t (&out)[8]) {
+    uint32_t p[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) p[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        uint64_t c = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            c += (uint64_t)x[i] * e[j] + p[i + j];
+            p[i + j] = (uint32_t)c;
+            c >>= 32;
+        }
+        p[i + 8] = (uint32_t)c;
+    }
+    uint32_t r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int w = 15; w >= 0; w--) {
+        uint32_t word = p[w];
+#pragma unroll 1
+        for (int b = 0; b < 32; b++) {  // r = 2 r + bit < 2 l, then back below l
+#pragma unroll
+            for (int i = 7; i > 0; i--) r[i] = (r[i] << 1) | (r[i - 1] >> 31);
+            r[0] = (r[0] << 1) | (word >> 31);
+            word <<= 1;
+            sc_cond_sub<0>(r);
+        }
+    }
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        uint64_t t = (uint64_t)k[i] - r[i] - borrow;
+        out[i] = (uint32_t)t;
+        borrow = (uint32_t)(t >> 63);
+    }
+    const uint32_t mask = 0u - borrow;
+    uint32_t carry = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        uint64_t t = (uint64_t)out[i] + (EdScalar::L[i] & mask) + carry;
+        out[i] = (uint32_t)t;
+        carry = (uint32_t)(t >> 32);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- BLAKE2s-256 (RFC 7693), unkeyed
+struct B2s {
+    static constexpr uint32_t IV[8] = {0x6A09E667u, 0xBB67AE85u, 0x3C6EF372u, 0xA54FF53Au, 0x510E527Fu, 0x9B05688Cu, 0x1F83D9ABu, 0x5BE0CD19u};
+    static constexpr uint8_t SIGMA[10][16] = {
+        {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
+        {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
+        {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
+        {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
+        {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0}};
+};
+SWM_HD uint32_t b2s_rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+// one compression; `t` = bytes hashed so far including this block.  The rounds are unrolled so that every index into m is a constant.
+SWM_HD void b2s_compress(uint32_t (&h)[8], const uint32_t (&m)[16], uint64_t t, bool last) {
+    uint32_t v[16];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        v[i] = h[i];
+        v[i + 8] = B2s::IV[i];
+    }
+    v[12] ^= (uint32_t)t;
+    v[13] ^= (uint32_t)(t >> 32);
+    if (last) v[14] = ~v[14];
+#define SWM_B2S_G(a, b, c, d, x, y)       \
+    v[a] = v[a] + v[b] + (x);             \
+    v[d] = b2s_rotr(v[d] ^ v[a], 16);     \
+    v[c] = v[c] + v[d];                   \
+    v[b] = b2s_rotr(v[b] ^ v[c], 12);     \
+    v[a] = v[a] + v[b] + (y);             \
+    v[d] = b2s_rotr(v[d] ^ v[a], 8);      \
+    v[c] = v[c] + v[d];                   \
+    v[b] = b2s_rotr(v[b] ^ v[c], 7);
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        SWM_B2S_G(0, 4, 8, 12, m[B2s::SIGMA[r][0]], m[B2s::SIGMA[r][1]])
+        SWM_B2S_G(1, 5, 9, 13, m[B2s::SIGMA[r][2]], m[B2s::SIGMA[r][3]])
+        SWM_B2S_G(2, 6, 10, 14, m[B2s::SIGMA[r][4]], m[B2s::SIGMA[r][5]])
+        SWM_B2S_G(3, 7, 11, 15, m[B2s::SIGMA[r][6]], m[B2s::SIGMA[r][7]])
+        SWM_B2S_G(0, 5, 10, 15, m[B2s::SIGMA[r][8]], m[B2s::SIGMA[r][9]])
+        SWM_B2S_G(1, 6, 11, 12, m[B2s::SIGMA[r][10]], m[B2s::SIGMA[r][11]])
+        SWM_B2S_G(2, 7, 8, 13, m[B2s::SIGMA[r][12]], m[B2s::SIGMA[r][13]])
+        SWM_B2S_G(3, 4, 9, 14, m[B2s::SIGMA[r][14]], m[B2s::SIGMA[r][15]])
+    }
+#undef SWM_B2S_G
+#pragma unroll
+    for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
+}
+
+// what a kernel needs of a swm_schnorr
+struct SchnorrDev {
+    const EdRow* table;  // [32 windows][256]: row (w, v) = v 2^(8 w) G
+    Fr k2d, d;
+    uint32_t salt[8];
+    uint32_t has_salt;
+};
+
+// Blake2s([salt] || pk.x || pk.y || R.x || R.y || message) -> h.  The input is a run of 32-byte pieces: five that sit in
+// registers (the salt one skipped when there is none), then the message.  Block b holds pieces 2 b and 2 b + 1; a word of a
+// register piece is picked by a select on the piece number, a word of the message is read from memory, zero past its end.
+SWM_HD void schnorr_hash(const SchnorrDev& P, const uint32_t (&px)[8], const uint32_t (&py)[8], const uint32_t (&rx)[8],
+                         const uint32_t (&ry)[8], const uint8_t* msg, size_t len, uint32_t (&h)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) h[i] = B2s::IV[i];
+    h[0] ^= 0x01010000u ^ 32u;  // digest length 32, no key, fanout = depth = 1
+    const size_t skip = P.has_salt ? 0 : 1;
+    const size_t total = (5 - skip) * 32 + len;
+    const size_t nblocks = (total + 63) / 64;  // >= 2
+#pragma unroll 1
+    for (size_t b = 0; b < nblocks; b++) {
+        uint32_t m[16];
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+            const size_t q = 2 * b + half + skip;
+            if (q < 5) {
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+                    m[8 * half + j] = q == 0 ? P.salt[j] : q == 1 ? px[j] : q == 2 ? py[j] : q == 3 ? rx[j] : ry[j];
+            } else {
+                const size_t off = (q - 5) * 32;
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    uint32_t w = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const size_t o = off + 4 * j + k;
+                        if (o < len) w |= (uint32_t)msg[o] << (8 * k);
+                    }
+                    m[8 * half + j] = w;
+                }
+            }
+        }
+        const bool last = b + 1 == nblocks;
+        b2s_compress(h, m, last ? (uint64_t)total : (uint64_t)64 * (b + 1), last);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- points in and out
+SWM_HD void load_words(const uint8_t* p, uint32_t (&w)[8]) {  // p is 4-byte aligned (the staging layout below)
+    const uint32_t* s = reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = s[i];
+}
+SWM_HD void store_words(uint8_t* p, const uint32_t (&w)[8]) {
+    uint32_t* d = reinterpret_cast<uint32_t*>(p);
+#pragma unroll
+    for (int i = 0; i < 8; i++) d[i] = w[i];
+}
+SWM_HD bool fr_from_words(const uint32_t (&w)[8], Fr* out) {  // canonical (< r) or refused
+    Fr s, r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        s.v[i] = w[i];
+        r.v[i] = FrParams::P[i];
+    }
+    if (fp_cmp_std(s, r) >= 0) return false;
+    *out = fp_from_std(s);
+    return true;
+}
+// x || y (standard form) -> the point, or false when a coordinate is >= r or -x^2 + y^2 != 1 + d x^2 y^2
+SWM_HD bool schnorr_point(const SchnorrDev& P, const uint32_t (&xs)[8], const uint32_t (&ys)[8], EdExt* out) {
+    Fr x, y;
+    if (!fr_from_words(xs, &x) || !fr_from_words(ys, &y)) return false;
+    Fr x2 = fp_sqr(x), y2 = fp_sqr(y);
+    if (!fp_eq(fp_sub(y2, x2), fp_add(fp_one<Fr>(), fp_mul(P.d, fp_mul(x2, y2))))) return false;
+    out->x = x;
+    out->y = y;
+    out->t = fp_mul(x, y);
+    out->z = fp_one<Fr>();
+    return true;
+}
+SWM_HD void schnorr_affine(const EdExt& p, uint32_t (&xs)[8], uint32_t (&ys)[8]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const Fr zi = fr_inv_single(p.z);  // Z != 0: the law is complete
+#else
+    const Fr zi = fp_inv(p.z);  // (host: the lane functions of this file also run on a CPU, which is how they were first checked)
+#endif
+    const Fr x = fp_to_std(fp_mul(p.x, zi)), y = fp_to_std(fp_mul(p.y, zi));
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        xs[i] = x.v[i];
+        ys[i] = y.v[i];
+    }
+}
+
+// acc += s G: byte w of s picks row (w, byte) of the table
+SWM_HD void schnorr_fixed_mul(EdExt& acc, const EdRow* table, const uint32_t (&s)[8]) {
+    uint32_t t[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) t[i] = s[i];
+#pragma unroll 1
+    for (unsigned w = 0; w < 32; w++) {
+        const unsigned v = t[0] & 255u;
+#pragma unroll
+        for (int i = 0; i < 7; i++) t[i] = (t[i] >> 8) | (t[i + 1] << 24);
+        t[7] >>= 8;
+        if (v) ed_madd(acc, table[(w << 8) + v]);
+    }
+}
+
+// the per-signature table: entry k (k + 1 times Y, cached form) is 32 words, word j at tab[(32 k + j) stride]
+SWM_HD void cached_store(uint32_t* tab, size_t stride, unsigned k, const EdCached& c) {
+    uint32_t* p = tab + (size_t)32 * k * stride;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        p[(size_t)i * stride] = c.ymx.v[i];
+        p[(size_t)(8 + i) * stride] = c.ypx.v[i];
+        p[(size_t)(16 + i) * stride] = c.kt.v[i];
+        p[(size_t)(24 + i) * stride] = c.z2.v[i];
+    }
+}
+SWM_HD EdCached cached_load(const uint32_t* tab, size_t stride, unsigned k) {
+    const uint32_t* p = tab + (size_t)32 * k * stride;
+    EdCached c;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        c.ymx.v[i] = p[(size_t)i * stride];
+        c.ypx.v[i] = p[(size_t)(8 + i) * stride];
+        c.kt.v[i] = p[(size_t)(16 + i) * stride];
+        c.z2.v[i] = p[(size_t)(24 + i) * stride];
+    }
+    return c;
+}
+
+// s G + e Y (schnorr.rs:140-143), e < l.  `tab` is this lane's column of the table buffer.
+SWM_HD EdExt schnorr_commitment(const SchnorrDev& P, const EdExt& Y, const uint32_t (&s)[8], const uint32_t (&e)[8], uint32_t* tab,
+                                size_t stride) {
+    const EdCached c1 = ed_to_cached(Y, P.k2d);
+    cached_store(tab, stride, 0, c1);
+    EdExt run = Y;
+#pragma unroll 1
+    for (unsigned k = 1; k < 8; k++) {
+        ed_add_cached(run, c1);
+        cached_store(tab, stride, k, ed_to_cached(run, P.k2d));
+    }
+    // e + 0x0777..7 < 2^251 + 2^251: 63 nibbles, nibble i - 7 = digit i in [-7, 8], sum of digit i 16^i = e
+    uint32_t d[8], carry = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        uint64_t t = (uint64_t)e[i] + (i == 7 ? 0x07777777u : 0x77777777u) + carry;
+        d[i] = (uint32_t)t;
+        carry = (uint32_t)(t >> 32);
+    }
+#pragma unroll
+    for (int i = 7; i > 0; i--) d[i] = (d[i] << 4) | (d[i - 1] >> 28);  // nibble 63 is zero: start at nibble 62
+    d[0] <<= 4;
+    EdExt acc = ed_identity();
+#pragma unroll 1
+    for (int i = 0; i < 63; i++) {
+        if (i) {
+#pragma unroll 1
+            for (int j = 0; j < 4; j++) ed_dbl(acc);
+        }
+        const int dg = (int)(d[7] >> 28) - 7;
+#pragma unroll
+        for (int k = 7; k > 0; k--) d[k] = (d[k] << 4) | (d[k - 1] >> 28);
+        d[0] <<= 4;
+        if (dg) {
+            EdCached c = cached_load(tab, stride, (unsigned)(dg < 0 ? -dg : dg) - 1u);
+            if (dg < 0) c = ed_cached_neg(c);
+            ed_add_cached(acc, c);
+        }
+    }
+    schnorr_fixed_mul(acc, P.table, s);
+    return acc;
+}
+
+// ---------------------------------------------------------------------------------------------- kernels: one lane per item
+// A refused input lowers *bad to the smallest refused index (0xffffffff: none); the host then returns without copying anything out.
+__device__ __forceinline__ void refuse(unsigned* bad, size_t i) { atomicMin(bad, (unsigned)(i < 0xfffffffeu ? i : 0xfffffffeu)); }
+
+__global__ void __launch_bounds__(256) schnorr_keygen_kernel(SchnorrDev P, const uint8_t* __restrict__ secrets, size_t count,
+                                                             uint8_t* __restrict__ out, unsigned* __restrict__ bad) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    uint32_t x[8], px[8], py[8];
+    load_words(secrets + 32 * i, x);
+    if (!sc_is_canonical(x)) return refuse(bad, i);
+    EdExt acc = ed_identity();
+    schnorr_fixed_mul(acc, P.table, x);
+    schnorr_affine(acc, px, py);
+    store_words(out + 64 * i, px);
+    store_words(out + 64 * i + 32, py);
+}
+
+__global__ void __launch_bounds__(256) schnorr_sign_kernel(SchnorrDev P, const uint8_t* __restrict__ secrets, const uint8_t* __restrict__ pks,
+                                                           const uint8_t* __restrict__ nonces, const uint8_t* __restrict__ msgs, size_t msg_len,
+                                                           size_t count, uint8_t* __restrict__ out, unsigned* __restrict__ bad) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    uint32_t x[8], k[8], px[8], py[8], rx[8], ry[8], h[8], e[8], s[8];
+    load_words(secrets + 32 * i, x);
+    load_words(nonces + 32 * i, k);
+    load_words(pks + 64 * i, px);
+    load_words(pks + 64 * i + 32, py);
+    EdExt Y;
+    if (!sc_is_canonical(x) || !sc_is_canonical(k) || !schnorr_point(P, px, py, &Y)) return refuse(bad, i);
+    EdExt acc = ed_identity();
+    schnorr_fixed_mul(acc, P.table, k);
+    schnorr_affine(acc, rx, ry);
+    schnorr_hash(P, px, py, rx, ry, msgs + i * msg_len, msg_len, h);
+#pragma unroll
+    for (int j = 0; j < 8; j++) e[j] = h[j];
+    sc_reduce(e);
+    sc_mulsub(k, x, e, s);
+    store_words(out + 64 * i, s);
+    store_words(out + 64 * i + 32, h);
+}
+
+// items [base, base + n); lane j of the launch owns column j of `tab`.  COMMIT: the claimed commitment as affine bytes, a bad
+// input refuses the call; otherwise one result byte, and a bad input is a signature that does not verify.
+template <bool COMMIT>
+__global__ void __launch_bounds__(256) schnorr_verify_kernel(SchnorrDev P, const uint8_t* __restrict__ pks, const uint8_t* __restrict__ sigs,
+                                                             const uint8_t* __restrict__ msgs, size_t msg_len, size_t base, size_t n,
+                                                             uint32_t* __restrict__ tab, size_t stride, uint8_t* __restrict__ out,
+                                                             unsigned* __restrict__ bad) {
+    const size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const size_t i = base + j;
+    uint32_t px[8], py[8], s[8], c[8], e[8], rx[8], ry[8];
+    load_words(pks + 64 * i, px);
+    load_words(pks + 64 * i + 32, py);
+    load_words(sigs + 64 * i, s);
+    load_words(sigs + 64 * i + 32, c);
+    EdExt Y;
+    if (!sc_is_canonical(s) || !schnorr_point(P, px, py, &Y)) {
+        if (COMMIT)
+            refuse(bad, i);
+        else
+            out[i] = 0;
+        return;
+    }
+#pragma unroll
+    for (int w = 0; w < 8; w++) e[w] = c[w];
+    sc_reduce(e);
+    const EdExt acc = schnorr_commitment(P, Y, s, e, tab + j, stride);
+    schnorr_affine(acc, rx, ry);
+    if (COMMIT) {
+        store_words(out + 64 * i, rx);
+        store_words(out + 64 * i + 32, ry);
+    } else {
+        uint32_t h[8], diff = 0;
+        schnorr_hash(P, px, py, rx, ry, msgs + i * msg_len, msg_len, h);
+#pragma unroll
+        for (int w = 0; w < 8; w++) diff |= h[w] ^ c[w];
+        out[i] = diff == 0;
+    }
+}
+
+}  // namespace swm
+
+struct swm_schnorr {
+    void* d_table = nullptr;  // 32 x 256 rows (swm::EdRow)
+    uint32_t salt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool has_salt = false;
+};
+
+using namespace swm;
+
+namespace {
+
+constexpr unsigned SCH_WINDOWS = 32, SCH_ROWS = 256;
+constexpr size_t SCH_CHUNK = (size_t)1 << 18;  // signatures per verify launch: bounds the table buffer at 256 MB
+
+SchnorrDev dev_params(const swm_schnorr* p) {
+    SchnorrDev d;
+    d.table = reinterpret_cast<const EdRow*>(p->d_table);
+    d.k2d = fp_from_u64<Fr>(2 * ED_D);
+    d.d = fp_from_u64<Fr>(ED_D);
+    for (int i = 0; i < 8; i++) d.salt[i] = p->salt[i];
+    d.has_salt = p->has_salt ? 1u : 0u;
+    return d;
+}
+
+enum SchnorrOp { OP_KEYGEN, OP_SIGN, OP_VERIFY, OP_COMMIT };
+
+// Stages the inputs (each array starts at a multiple of 32 count bytes: word-aligned), runs the kernel of `op`, and copies the
+// result out only when no input was refused.
+int schnorr_run(swm_ctx* ctx, const swm_schnorr* p, SchnorrOp op, const uint8_t* secrets, const uint8_t* pks, const uint8_t* nonces,
+                const uint8_t* sigs, const uint8_t* msgs, size_t msg_len, size_t count, uint8_t* out, const char* what) {
+    const size_t out_item = op == OP_VERIFY ? 1 : 64;
+    const size_t n_sk = secrets ? 32 * count : 0, n_pk = pks ? 64 * count : 0, n_k = nonces ? 32 * count : 0, n_sig = sigs ? 64 * count : 0;
+    const size_t n_msg = msgs ? msg_len * count : 0;
+    uint8_t *d_in = nullptr, *d_res = nullptr;
+    SWM_TRY(scratch(ctx, "stage.a", n_sk + n_pk + n_k + n_sig + n_msg + 32, (void**)&d_in));
+    SWM_TRY(scratch(ctx, "stage.b", 256 + out_item * count, (void**)&d_res));
+    uint8_t *d_sk = d_in, *d_pk = d_sk + n_sk, *d_k = d_pk + n_pk, *d_sig = d_k + n_k, *d_msg = d_sig + n_sig;
+    unsigned* d_bad = reinterpret_cast<unsigned*>(d_res);
+    uint8_t* d_out = d_res + 256;
+    if (n_sk) SWM_HIP(ctx, hipMemcpyAsync(d_sk, secrets, n_sk, hipMemcpyHostToDevice, ctx->stream));
+    if (n_pk) SWM_HIP(ctx, hipMemcpyAsync(d_pk, pks, n_pk, hipMemcpyHostToDevice, ctx->stream));
+    if (n_k) SWM_HIP(ctx, hipMemcpyAsync(d_k, nonces, n_k, hipMemcpyHostToDevice, ctx->stream));
+    if (n_sig) SWM_HIP(ctx, hipMemcpyAsync(d_sig, sigs, n_sig, hipMemcpyHostToDevice, ctx->stream));
+    if (n_msg) SWM_HIP(ctx, hipMemcpyAsync(d_msg, msgs, n_msg, hipMemcpyHostToDevice, ctx->stream));
+    SWM_HIP(ctx, hipMemsetAsync(d_bad, 0xff, sizeof(unsigned), ctx->stream));
+    const SchnorrDev P = dev_params(p);
+    const dim3 block(256);
+    if (op == OP_KEYGEN) {
+        SWM_LAUNCH(ctx, "schnorr_keygen", schnorr_keygen_kernel, dim3((unsigned)((count + 255) / 256)), block, 0, P, d_sk, count, d_out, d_bad);
+    } else if (op == OP_SIGN) {
+        SWM_LAUNCH(ctx, "schnorr_sign", schnorr_sign_kernel, dim3((unsigned)((count + 255) / 256)), block, 0, P, d_sk, d_pk, d_k, d_msg, msg_len,
+                   count, d_out, d_bad);
+    } else {
+        const size_t lanes = count < SCH_CHUNK ? count : SCH_CHUNK;
+        const size_t stride = (lanes + 63) & ~(size_t)63;
+        uint32_t* d_tab = nullptr;
+        SWM_TRY(scratch(ctx, "schnorr.tab", (size_t)8 * 32 * sizeof(uint32_t) * stride, (void**)&d_tab));
+        for (size_t base = 0; base < count; base += SCH_CHUNK) {
+            const size_t n = count - base < SCH_CHUNK ? count - base : SCH_CHUNK;
+            const dim3 grid((unsigned)((n + 255) / 256));
+            if (op == OP_VERIFY)
+                SWM_LAUNCH(ctx, "schnorr_verify", schnorr_verify_kernel<false>, grid, block, 0, P, d_pk, d_sig, d_msg, msg_len, base, n, d_tab,
+                           stride, d_out, d_bad);
+            else
+                SWM_LAUNCH(ctx, "schnorr_commitments", schnorr_verify_kernel<true>, grid, block, 0, P, d_pk, d_sig, d_msg, msg_len, base, n,
+                           d_tab, stride, d_out, d_bad);
+        }
+    }
+    unsigned bad = 0;
+    SWM_HIP(ctx, hipMemcpyAsync(&bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (bad != 0xffffffffu)
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: item %u%s holds a scalar >= the group order or a point off ed-on-BLS12-377", what, bad,
+                       bad == 0xfffffffeu ? " (or a later one)" : "");
+    SWM_HIP(ctx, hipMemcpyAsync(out, d_out, out_item * count, hipMemcpyDeviceToHost, ctx->stream));
+    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SWM_OK;
+}
+
+void words_from_bytes(const uint8_t* b, uint32_t (&w)[8]) {
+    for (int i = 0; i < 8; i++) w[i] = (uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 | (uint32_t)b[4 * i + 3] << 24;
+}
+
+}  // namespace
+
+extern "C" {
+
+int swm_schnorr_create(swm_ctx* ctx, const uint8_t generator_xy[64], const uint8_t* salt32_or_null, swm_schnorr** out) {
+    if (!ctx || !generator_xy || !out) return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_create: bad arguments");
+    SWM_ON_DEVICE(ctx);
+    swm_schnorr* p = new swm_schnorr;
+    if (salt32_or_null) {
+        words_from_bytes(salt32_or_null, p->salt);
+        p->has_salt = true;
+    }
+    const SchnorrDev P = dev_params(p);
+    uint32_t gx[8], gy[8];
+    words_from_bytes(generator_xy, gx);
+    words_from_bytes(generator_xy + 32, gy);
+    EdExt base;
+    if (!schnorr_point(P, gx, gy, &base)) {
+        delete p;
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_create: the generator is not a point of ed-on-BLS12-377");
+    }
+    std::vector<EdRow> rows((size_t)SCH_WINDOWS * SCH_ROWS);
+    for (unsigned w = 0; w < SCH_WINDOWS; w++) {  // base = 2^(8 w) G
+        EdExt acc = ed_identity();
+        for (unsigned v = 0; v < SCH_ROWS; v++) {  // acc = v base
+            const Fr zi = fp_inv(acc.z);
+            const Fr x = fp_mul(acc.x, zi), y = fp_mul(acc.y, zi);
+            EdRow& r = rows[(size_t)w * SCH_ROWS + v];
+            r.ymx = fp_sub(y, x);
+            r.ypx = fp_add(y, x);
+            r.kt = fp_mul(P.k2d, fp_mul(x, y));
+            acc = ed_add(acc, base, P.k2d);
+        }
+        base = acc;  // 256 base
+    }
+    hipError_t e = hipMalloc(&p->d_table, rows.size() * sizeof(EdRow));
+    if (e == hipSuccess) e = hipMemcpyAsync(p->d_table, rows.data(), rows.size() * sizeof(EdRow), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // `rows` goes out of scope
+    if (e != hipSuccess) {
+        if (p->d_table) (void)hipFree(p->d_table);
+        delete p;
+        (void)hipGetLastError();
+        return set_err(ctx, e == hipErrorOutOfMemory ? SWM_ERR_OOM : SWM_ERR_HIP, "schnorr_create: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return SWM_OK;
+}
+
+void swm_schnorr_destroy(swm_ctx* ctx, swm_schnorr* p) {
+    if (!p) return;
+    DeviceGuard guard(ctx);
+    if (ctx) drain_streams(ctx);
+    if (p->d_table) (void)hipFree(p->d_table);
+    delete p;
+}
+
+int swm_schnorr_keygen(swm_ctx* ctx, const swm_schnorr* p, const uint8_t* secret_keys, size_t count, uint8_t* public_keys_xy) {
+    if (!ctx || !p || (count && (!secret_keys || !public_keys_xy))) return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_keygen: bad arguments");
+    SWM_ON_DEVICE(ctx);
+    if (!count) return SWM_OK;
+    return schnorr_run(ctx, p, OP_KEYGEN, secret_keys, nullptr, nullptr, nullptr, nullptr, 0, count, public_keys_xy, "schnorr_keygen");
+}
+
+int swm_schnorr_sign(swm_ctx* ctx, const swm_schnorr* p, const uint8_t* secret_keys, const uint8_t* public_keys_xy, const uint8_t* nonces,
+                     const uint8_t* messages, size_t msg_len, size_t count, uint8_t* signatures) {
+    if (!ctx || !p || (count && (!secret_keys || !public_keys_xy || !nonces || !signatures || (msg_len && !messages))))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_sign: bad arguments");
+    SWM_ON_DEVICE(ctx);
+    if (!count) return SWM_OK;
+    return schnorr_run(ctx, p, OP_SIGN, secret_keys, public_keys_xy, nonces, nullptr, msg_len ? messages : nullptr, msg_len, count, signatures,
+                       "schnorr_sign");
+}
+
+int swm_schnorr_verify(swm_ctx* ctx, const swm_schnorr* p, const uint8_t* public_keys_xy, const uint8_t* messages, size_t msg_len,
+                       const uint8_t* signatures, size_t count, uint8_t* ok) {
+    if (!ctx || !p || (count && (!public_keys_xy || !signatures || !ok || (msg_len && !messages))))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_verify: bad arguments");
+    SWM_ON_DEVICE(ctx);
+    if (!count) return SWM_OK;
+    return schnorr_run(ctx, p, OP_VERIFY, nullptr, public_keys_xy, nullptr, signatures, msg_len ? messages : nullptr, msg_len, count, ok,
+                       "schnorr_verify");
+}
+
+int swm_schnorr_commitments(swm_ctx* ctx, const swm_schnorr* p, const uint8_t* public_keys_xy, const uint8_t* signatures, size_t count,
+                            uint8_t* commitments_xy) {
+    if (!ctx || !p || (count && (!public_keys_xy || !signatures || !commitments_xy)))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_commitments: bad arguments");
+    SWM_ON_DEVICE(ctx);
+    if (!count) return SWM_OK;
+    return schnorr_run(ctx, p, OP_COMMIT, nullptr, public_keys_xy, nullptr, signatures, nullptr, 0, count, commitments_xy, "schnorr_commitments");
+}
+
+}  // extern "C"

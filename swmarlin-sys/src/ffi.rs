@@ -10,6 +10,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_vk { _p: [u8; 0] }
 #[repr(C)] pub struct swm_bases { _p: [u8; 0] }
 #[repr(C)] pub struct swm_pedersen { _p: [u8; 0] }
+#[repr(C)] pub struct swm_schnorr { _p: [u8; 0] }
 
 pub const SWM_OK: c_int = 0;
 pub const SWM_ERR_UNSATISFIED: c_int = -5;
@@ -125,4 +126,17 @@ extern "C" {
                              digests: *mut u8) -> c_int;
     pub fn swm_merkle_tree_build(ctx: *mut swm_ctx, leaf_params: *const swm_pedersen, two_to_one_params: *const swm_pedersen,
                                  leaves: *const u8, leaf_len: usize, n_leaves: usize, nodes: *mut u8) -> c_int;
+
+    // the native Schnorr scheme of src/schnorr_signature/schnorr.rs:57-160, batched (points: x || y, 32 LE bytes each; a signature:
+    // prover_response || verifier_challenge; secrets and nonces are the caller's draws)
+    pub fn swm_schnorr_create(ctx: *mut swm_ctx, generator_xy: *const u8, salt32_or_null: *const u8, out: *mut *mut swm_schnorr) -> c_int;
+    pub fn swm_schnorr_destroy(ctx: *mut swm_ctx, params: *mut swm_schnorr);
+    pub fn swm_schnorr_keygen(ctx: *mut swm_ctx, params: *const swm_schnorr, secret_keys: *const u8, count: usize,
+                              public_keys_xy: *mut u8) -> c_int;
+    pub fn swm_schnorr_sign(ctx: *mut swm_ctx, params: *const swm_schnorr, secret_keys: *const u8, public_keys_xy: *const u8,
+                            nonces: *const u8, messages: *const u8, msg_len: usize, count: usize, signatures: *mut u8) -> c_int;
+    pub fn swm_schnorr_verify(ctx: *mut swm_ctx, params: *const swm_schnorr, public_keys_xy: *const u8, messages: *const u8,
+                              msg_len: usize, signatures: *const u8, count: usize, ok: *mut u8) -> c_int;
+    pub fn swm_schnorr_commitments(ctx: *mut swm_ctx, params: *const swm_schnorr, public_keys_xy: *const u8, signatures: *const u8,
+                                   count: usize, commitments_xy: *mut u8) -> c_int;
 }
