@@ -347,6 +347,39 @@ int swm_merkle_tree_build(swm_ctx *ctx, const swm_pedersen *leaf_params, const s
 int swm_merkle_tree_build_dev(swm_ctx *ctx, const swm_pedersen *leaf_params, const swm_pedersen *two_to_one_params,
                               const void *d_leaves, size_t leaf_len, size_t n_leaves, void *d_nodes);
 
+/* ---------------------------------------------------------------------------------------------- Merkle membership witness
+ * The assignment of the membership circuit (MerkleTreeVerificationU8, src/merkle_tree/merkle_tree_verification_u8.rs:25-58, as
+ * this library lays it out: simpleworks_amd/workloads.py, build_merkle_membership with 256-bit digests) synthesised on the
+ * GPU: what SimpleMerkleTree::prove (src/merkle_tree/simple_merkle_tree.rs:105-123) hands to the prover, without running the
+ * constraint synthesizer on the host.  The circuit's shape depends on the tree height and the byte-operation count only.
+ *   levels L = height - 1;  num_instance = 10 (one, root, 8 leaf bits);  num_witness = 42 + 3581 L + 8 gadget_byte_ops.
+ * swm_merkle_circuit_shape needs no GPU.  SWM_ERR_INVALID_ARG: height < 2 or > 64, a NULL output.
+ * swm_merkle_circuit_create: both parameter sets must have 4-bit windows, the leaf set >= 2 and the two-to-one set >= 128 of
+ * them; 64 L + gadget_byte_ops <= 32768 (else SWM_ERR_INVALID_ARG).  The handle refers to the two swm_pedersen: keep them.
+ * swm_merkle_witness: `count` paths in one launch.  leaves: count bytes; indices: count leaf indices, each < 2^L; siblings:
+ * count x L x 32 bytes, the sibling digest of every level bottom up, canonical little-endian (a value >= r is
+ * SWM_ERR_INVALID_ARG).  witness: count x num_witness x 4 Montgomery limbs, in the circuit's variable order; roots (may be
+ * NULL): count x 32 bytes, the root each path arrives at, canonical little-endian.  count = 0 launches nothing.
+ * swm_merkle_witness_dev: the same on device buffers.  What the host form refuses is reported per path instead: d_status
+ * (count words, may be NULL) is 0 for a path that was computed, 1 for a sibling >= r, 2 for an index >= 2^L; the witness
+ * and the root of such a path are zero, the other paths of the batch are unaffected.
+ * swm_merkle_prove: witness on the device, then the proof of swm_generate_proof_ex(flags) with the public input
+ * (root, 8 leaf bits): the witness reaches the prover by a device-to-device copy.  `root` (canonical little-endian) is an
+ * input: a wrong root, or a path that does not lead to it, is SWM_ERR_UNSATISFIED; a key of another shape SWM_ERR_MISMATCH. */
+typedef struct swm_merkle_circuit swm_merkle_circuit;
+int swm_merkle_circuit_shape(size_t height, size_t gadget_byte_ops, size_t *num_instance, size_t *num_witness,
+                             size_t *num_constraints);
+int swm_merkle_circuit_create(swm_ctx *ctx, const swm_pedersen *leaf_params, const swm_pedersen *two_to_one_params, size_t height,
+                              size_t gadget_byte_ops, swm_merkle_circuit **out);
+void swm_merkle_circuit_destroy(swm_ctx *ctx, swm_merkle_circuit *circuit);
+int swm_merkle_witness(swm_ctx *ctx, const swm_merkle_circuit *circuit, const uint8_t *leaves, const uint64_t *indices,
+                       const uint8_t *siblings, size_t count, uint64_t *witness, uint8_t *roots);
+int swm_merkle_witness_dev(swm_ctx *ctx, const swm_merkle_circuit *circuit, const void *d_leaves, const void *d_indices,
+                           const void *d_siblings, size_t count, void *d_witness, void *d_roots, void *d_status);
+int swm_merkle_prove(swm_ctx *ctx, const swm_pk *pk, const swm_merkle_circuit *circuit, const uint8_t root[32], uint8_t leaf,
+                     uint64_t index, const uint8_t *siblings, swm_rng *rng, unsigned flags, uint8_t *proof_out, size_t cap,
+                     size_t *len);
+
 /* ---------------------------------------------------------------------------------------------- Schnorr signatures
  * The reference's native signature scheme, SimpleSchnorr = Schnorr<EdwardsProjective> on ed-on-BLS12-377, batched: one GPU lane per
  * key, signature or check.  Replaces, on the GPU,

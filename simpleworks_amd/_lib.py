@@ -97,6 +97,13 @@ ABI = {
     "swm_pedersen_hash_dev": (_int, [_vp, _vp, _vp, _sz, _sz, _vp]),
     "swm_merkle_tree_build": (_int, [_vp, _vp, _vp, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
     "swm_merkle_tree_build_dev": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp]),
+    "swm_merkle_circuit_shape": (_int, [_sz, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "swm_merkle_circuit_create": (_int, [_vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_vp)]),
+    "swm_merkle_circuit_destroy": (None, [_vp, _vp]),
+    "swm_merkle_witness": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_merkle_witness_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "swm_merkle_prove": (_int, [_vp, _vp, _vp, ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_void_p, _vp, ctypes.c_uint,
+                                ctypes.c_void_p, _sz, ctypes.POINTER(_sz)]),
     "swm_schnorr_create": (_int, [_vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_vp)]),
     "swm_schnorr_destroy": (None, [_vp, _vp]),
     "swm_schnorr_keygen": (_int, [_vp, _vp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
@@ -428,6 +435,36 @@ class Context:
     def merkle_tree_build_dev(self, leaf_handle, two_to_one_handle, d_leaves, leaf_len, n_leaves, d_nodes):
         self._check(self.lib.swm_merkle_tree_build_dev(self.h, leaf_handle, two_to_one_handle, d_leaves.ptr, leaf_len, n_leaves,
                                                        d_nodes.ptr), "swm_merkle_tree_build_dev")
+
+    # ---- Merkle membership witness (include/swmarlin.h; simpleworks_amd/hash.py, MerkleCircuit, is the caller-facing mirror)
+    def merkle_circuit_create(self, leaf_handle, two_to_one_handle, height, gadget_byte_ops):
+        h = _vp()
+        self._check(self.lib.swm_merkle_circuit_create(self.h, leaf_handle, two_to_one_handle, height, gadget_byte_ops, ctypes.byref(h)),
+                    "swm_merkle_circuit_create")
+        return h
+
+    def merkle_circuit_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_merkle_circuit_destroy(self.h, handle)
+
+    def merkle_witness(self, handle, num_witness, leaves, indices, siblings):
+        """leaves uint8 [count], indices uint64 [count], siblings uint8 [count, levels, 32] (canonical little-endian) ->
+        (witness uint64 [count, num_witness, 4] Montgomery limbs, roots uint8 [count, 32])."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint8)
+        indices = np.ascontiguousarray(indices, dtype=np.uint64)
+        siblings = np.ascontiguousarray(siblings, dtype=np.uint8)
+        count = leaves.shape[0]
+        assert leaves.ndim == 1 and indices.shape == (count,) and siblings.ndim == 3 and siblings.shape[0] == count and siblings.shape[2] == 32
+        witness = np.empty((count, num_witness, 4), dtype=np.uint64)
+        roots = np.empty((count, 32), dtype=np.uint8)
+        self._check(self.lib.swm_merkle_witness(self.h, handle, leaves.ctypes.data, indices.ctypes.data, siblings.ctypes.data, count,
+                                                witness.ctypes.data, roots.ctypes.data), "swm_merkle_witness")
+        return witness, roots
+
+    def merkle_witness_dev(self, handle, d_leaves, d_indices, d_siblings, count, d_witness, d_roots=None, d_status=None):
+        self._check(self.lib.swm_merkle_witness_dev(self.h, handle, d_leaves.ptr, d_indices.ptr, d_siblings.ptr, count, d_witness.ptr,
+                                                    d_roots.ptr if d_roots else None, d_status.ptr if d_status else None),
+                    "swm_merkle_witness_dev")
 
     # ---- Schnorr signatures (include/swmarlin.h; simpleworks_amd/schnorr.py is the caller-facing mirror)
     @staticmethod

@@ -58,6 +58,9 @@ struct swm_ctx {
     void* pinned_dev = nullptr;  // device address of `pinned`
     void* h2d_stage = nullptr;   // small pinned staging area for the witness upload of small proofs (marlin.hip, upload_small)
     size_t h2d_stage_used = 0;
+    // device source of the witness for the NEXT proof on this context (upload_witness copies from it instead of from
+    // swm_r1cs::witness); set and cleared by swm_merkle_prove around its call of the prover, null everywhere else
+    const void* witness_dev = nullptr;
     hipEvent_t slot_event[MSM_SLOTS] = {nullptr};
     bool slot_busy[MSM_SLOTS] = {false};  // enqueued and not yet collected by msm_finish
     hipEvent_t acc_event[MSM_SLOTS] = {nullptr};  // "partial sums ready" per slot (stage A -> stage T, deferred bucket stages)

@@ -6,6 +6,7 @@
 // Needs before inclusion: swmarlin.h, host/ahp.h, host/host_handles.h, declarations of swm::set_err and swm::drain_streams.
 #include <memory>
 #include <new>
+#include "merkle_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
 extern "C" {
@@ -169,6 +170,23 @@ int swm_chacha_block(const uint8_t key[32], uint64_t counter, int rounds, uint8_
     for (int i = 0; i < 8; i++) memcpy(&k[i], key + 4 * i, 4);
     chacha_block(k, counter, rounds, o);
     memcpy(out, o, 64);
+    return SWM_OK;
+}
+
+
+// The membership circuit's shape from the tree height alone (merkle_shape.h; the layout is build_merkle_membership's)
+int swm_merkle_circuit_shape(size_t height, size_t gadget_byte_ops, size_t* num_instance, size_t* num_witness,
+                             size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "merkle_circuit_shape: NULL output");
+    MerkleShape s;
+    if (!merkle_shape(height, gadget_byte_ops, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG, "merkle_circuit_shape: height %zu with %zu byte operations (2 <= height <= %zu)",
+                       height, gadget_byte_ops, (size_t)MW_MAX_HEIGHT);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
     return SWM_OK;
 }
 

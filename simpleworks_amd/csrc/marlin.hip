@@ -1358,7 +1358,9 @@ void upload_witness(swm_ctx* ctx, const swm_pk& pk, ProveState& s, const swm_r1c
     // (the staging area is free again: whatever the previous proof of this context staged was consumed before that proof returned)
     ctx->h2d_stage_used = 0;
     upload_small(ctx, s.z.p, shape.inst.data(), s.ninst * sizeof(Fr));
-    if (shape.nwit_orig) upload_small(ctx, s.z.p + s.ninst, cs->witness, shape.nwit_orig * sizeof(Fr));
+    if (shape.nwit_orig && ctx->witness_dev)  // a witness synthesised on this device (merkle_witness.hip): no host round trip
+        hip_check(ctx, hipMemcpyAsync(s.z.p + s.ninst, ctx->witness_dev, shape.nwit_orig * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream), "d2d");
+    else if (shape.nwit_orig) upload_small(ctx, s.z.p + s.ninst, cs->witness, shape.nwit_orig * sizeof(Fr));
     if (shape.nwit > shape.nwit_orig) {  // dummy unconstrained variables have the value one
         Fr* zp = s.z.p + s.ninst + shape.nwit_orig;
         ew(ctx, "z_pad", shape.nwit - shape.nwit_orig, [=] __device__(size_t i) { zp[i] = fp_one<Fr>(); });

@@ -27,12 +27,8 @@
 #include "ed.cuh"
 #include "ff.cuh"
 #include "frinv.cuh"
+#include "pedersen.h"
 #include "swmarlin.h"
-
-struct swm_pedersen {
-    void* d_table = nullptr;  // num_windows x 2^window_size rows (swm::EdRow)
-    unsigned num_windows = 0, window_size = 0;
-};
 
 namespace swm {
 

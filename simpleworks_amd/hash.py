@@ -13,7 +13,7 @@ evaluation path here (the checker lives under oracle/).
 """
 import numpy as np
 
-from .marlin import R_MODULUS, default_context, generate_rand
+from .marlin import R_MODULUS, default_context, generate_rand, merkle_circuit_shape
 
 ED_D = 3021            # ed-on-BLS12-377: -x^2 + y^2 = 1 + 3021 x^2 y^2 over BLS12-377 Fr
 ED_COFACTOR = 4
@@ -183,3 +183,44 @@ class MerkleTree:
 
     def int_levels(self):
         return [[int.from_bytes(r.tobytes(), "little") for r in lvl] for lvl in self.levels]
+
+
+class MerkleCircuit:
+    """The membership circuit of a tree of `height` levels over (LeafHash, TwoToOneHash), resident on the GPU
+    (swm_merkle_circuit): synthesises the witness vector of workloads.build_merkle_membership (256-bit digests) for batches of
+    (leaf, leaf index, authentication path) without running the builder.  Refers to the two PedersenCRH: keep them alive."""
+
+    def __init__(self, leaf_crh, two_to_one_crh, height, gadget_byte_ops=0):
+        self.ctx = leaf_crh.ctx
+        self.leaf_crh, self.two_to_one_crh = leaf_crh, two_to_one_crh
+        self.height, self.gadget_byte_ops = height, gadget_byte_ops
+        self.h = self.ctx.merkle_circuit_create(leaf_crh.h, two_to_one_crh.h, height, gadget_byte_ops)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        return merkle_circuit_shape(self.height, self.gadget_byte_ops)
+
+    def witness_many(self, leaves, indices, siblings):
+        """leaves: u8 values; indices: leaf indices; siblings: per path the sibling digests bottom up, as ints or as 32
+        little-endian bytes each.  One launch.  Returns (witness uint64 [count, num_witness, 4] Montgomery limbs, roots as ints)."""
+        levels = self.height - 1
+        rows = []
+        for path in siblings:
+            if len(path) != levels:
+                raise ValueError("a path of this circuit has %d siblings" % levels)
+            rows.append(b"".join(bytes(s) if isinstance(s, (bytes, bytearray, np.ndarray)) else int(s).to_bytes(32, "little") for s in path))
+        sib = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), levels, 32)
+        witness, roots = self.ctx.merkle_witness(self.h, self.shape()[1], np.asarray(list(leaves), dtype=np.uint8),
+                                                 np.asarray(list(indices), dtype=np.uint64), sib)
+        return witness, [int.from_bytes(r.tobytes(), "little") for r in roots]
+
+    def free(self):
+        if self.h:
+            self.ctx.merkle_circuit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass

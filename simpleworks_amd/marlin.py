@@ -426,6 +426,30 @@ def generate_proof_uncompressed(constraint_system, proving_key, rng):
     return bytes(buf[: n.value])
 
 
+def merkle_circuit_shape(height, gadget_byte_ops=0):
+    """swm_merkle_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the membership circuit of a tree of that
+    height — what workloads.build_merkle_membership emits with 256-bit digests."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_merkle_circuit_shape(height, gadget_byte_ops, ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)),
+           "swm_merkle_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_merkle_proof(proving_key, circuit, root, leaf, leaf_index, siblings, rng, uncompressed=False):
+    """swm_merkle_prove: SimpleMerkleTree::prove (src/merkle_tree/simple_merkle_tree.rs:105-123) with the circuit's witness
+    synthesised on the GPU (hash.MerkleCircuit) and handed to the prover on the device.  root / siblings: ints (standard form).
+    Returns the proof bytes (uncompressed=True: the form of generate_proof_uncompressed)."""
+    ctx = proving_key.ctx
+    root_b = (ctypes.c_uint8 * 32).from_buffer_copy(int(root).to_bytes(32, "little"))
+    sib = b"".join(int(s).to_bytes(32, "little") for s in siblings)
+    sib_b = (ctypes.c_uint8 * max(1, len(sib))).from_buffer_copy(sib.ljust(1, b"\0"))
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    _check(ctx.lib.swm_merkle_prove(ctx.h, proving_key.h, circuit.h, root_b, leaf, leaf_index, sib_b, rng.h, 1 if uncompressed else 0,
+                                    buf, len(buf), ctypes.byref(n)), "swm_merkle_prove", ctx)
+    return bytes(buf[: n.value])
+
+
 def verify_proof(verifying_key, public_inputs, proof, rng):
     """src/marlin/mod.rs:79-86.  public_inputs: field elements as ints (e.g. the bit-expanded inputs of
     src/merkle_tree/simple_merkle_tree.rs:129-143)."""

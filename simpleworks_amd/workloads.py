@@ -640,6 +640,7 @@ class SimpleMerkleTree:
         blank_root = self.params.root_from_path(0, 0, blank_path)
         dummy = MerkleTreeVerificationU8(self.params, blank_root, 0, 0, blank_path, gadget_byte_ops)
         self.gadget_byte_ops = gadget_byte_ops
+        self._circuit = None
         self.proving_key, self.verifying_key = M.MarlinInst.index(universal_srs, dummy)   # :83
         universal_srs.free()
 
@@ -658,6 +659,38 @@ class SimpleMerkleTree:
         proof = self._M.MarlinInst.prove(self.proving_key, circuit, rng)         # :119
         return self._S.serialize_proof(proof)                                    # proof.serialize(&mut bytes)
 
+    def _merkle_circuit(self):
+        """The circuit's witness synthesiser on the GPU (hash.MerkleCircuit), created on first use."""
+        if self.params.digest_bits != 256:
+            raise ValueError("the GPU witness synthesis covers the reference's 256-bit digests only; use prove()")
+        if self._circuit is None:
+            from .hash import MerkleCircuit
+            leaf_crh, inner_crh = self.params.crh(self.proving_key.ctx)
+            self._circuit = MerkleCircuit(leaf_crh, inner_crh, merkle_tree_height(len(self.leaves)), self.gadget_byte_ops)
+        return self._circuit
+
+    def prove_on_gpu(self, leaf, merkle_path):
+        """prove() without the host round trip: the circuit's witness is synthesised on the GPU and handed to the prover on the
+        device (swm_merkle_prove).  Same bytes as prove()."""
+        circuit = self._merkle_circuit()
+        leaf_index, siblings = merkle_path
+        rng = self._M.generate_rand()
+        return self._M.generate_merkle_proof(self.proving_key, circuit, self.root(), leaf, leaf_index, siblings, rng)
+
+    def prove_many(self, leaves, merkle_paths):
+        """One batched witness launch for all paths, then one proof each (a fresh generate_rand() per proof, as prove())."""
+        circuit = self._merkle_circuit()
+        ni, nw, nc = circuit.shape()
+        witness, _ = circuit.witness_many(leaves, [p[0] for p in merkle_paths], [p[1] for p in merkle_paths])
+        root = self.root()
+        proofs = []
+        for i, leaf in enumerate(leaves):
+            instance = self._M._to_mont_limbs([1, root] + [(leaf >> k) & 1 for k in range(8)])
+            rng = self._M.generate_rand()
+            proof = self._M.generate_proof(self._M.AssignmentOnly(instance, witness[i], nc), self.proving_key, rng)
+            proofs.append(self._S.serialize_proof(proof))
+        return proofs
+
     def verify(self, proof_bytes, input_u8):
         input_vec = [self.root()] + [(input_u8 >> i) & 1 for i in range(8)]      # :129-143
         proof = self._S.deserialize_proof(proof_bytes)
@@ -665,4 +698,6 @@ class SimpleMerkleTree:
         return self._M.MarlinInst.verify(self.verifying_key, input_vec, proof, rng)   # :148
 
     def free(self):
+        if self._circuit is not None:
+            self._circuit.free()
         self.proving_key.free()

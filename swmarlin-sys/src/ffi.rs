@@ -11,6 +11,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_bases { _p: [u8; 0] }
 #[repr(C)] pub struct swm_pedersen { _p: [u8; 0] }
 #[repr(C)] pub struct swm_schnorr { _p: [u8; 0] }
+#[repr(C)] pub struct swm_merkle_circuit { _p: [u8; 0] }
 
 pub const SWM_OK: c_int = 0;
 pub const SWM_ERR_UNSATISFIED: c_int = -5;
@@ -126,6 +127,22 @@ extern "C" {
                              digests: *mut u8) -> c_int;
     pub fn swm_merkle_tree_build(ctx: *mut swm_ctx, leaf_params: *const swm_pedersen, two_to_one_params: *const swm_pedersen,
                                  leaves: *const u8, leaf_len: usize, n_leaves: usize, nodes: *mut u8) -> c_int;
+
+    // the membership circuit's witness on the GPU: SimpleMerkleTree::prove (src/merkle_tree/simple_merkle_tree.rs:105-123) without
+    // running the constraint synthesizer on the host (roots and siblings: 32 canonical LE bytes; witness: Montgomery limbs)
+    pub fn swm_merkle_circuit_shape(height: usize, gadget_byte_ops: usize, num_instance: *mut usize, num_witness: *mut usize,
+                                    num_constraints: *mut usize) -> c_int;
+    pub fn swm_merkle_circuit_create(ctx: *mut swm_ctx, leaf_params: *const swm_pedersen, two_to_one_params: *const swm_pedersen,
+                                     height: usize, gadget_byte_ops: usize, out: *mut *mut swm_merkle_circuit) -> c_int;
+    pub fn swm_merkle_circuit_destroy(ctx: *mut swm_ctx, circuit: *mut swm_merkle_circuit);
+    pub fn swm_merkle_witness(ctx: *mut swm_ctx, circuit: *const swm_merkle_circuit, leaves: *const u8, indices: *const u64,
+                              siblings: *const u8, count: usize, witness: *mut u64, roots: *mut u8) -> c_int;
+    pub fn swm_merkle_witness_dev(ctx: *mut swm_ctx, circuit: *const swm_merkle_circuit, d_leaves: *const c_void,
+                                  d_indices: *const c_void, d_siblings: *const c_void, count: usize, d_witness: *mut c_void,
+                                  d_roots: *mut c_void, d_status: *mut c_void) -> c_int;
+    pub fn swm_merkle_prove(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_merkle_circuit, root: *const u8, leaf: u8,
+                            index: u64, siblings: *const u8, rng: *mut swm_rng, flags: c_uint, proof_out: *mut u8, cap: usize,
+                            len: *mut usize) -> c_int;
 
     // the native Schnorr scheme of src/schnorr_signature/schnorr.rs:57-160, batched (points: x || y, 32 LE bytes each; a signature:
     // prover_response || verifier_challenge; secrets and nonces are the caller's draws)
