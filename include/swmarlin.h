@@ -416,6 +416,46 @@ int swm_schnorr_verify(swm_ctx *ctx, const swm_schnorr *params, const uint8_t *p
 int swm_schnorr_commitments(swm_ctx *ctx, const swm_schnorr *params, const uint8_t *public_keys_xy, const uint8_t *signatures,
                             size_t count, uint8_t *commitments_xy);
 
+/* ---------------------------------------------------------------------------------------------- Poseidon sponge
+ * The reference's native Poseidon hash, PoseidonSponge<Fq> of ark-sponge 0.3.0 over Fq of ed-on-BLS12-377 (= BLS12-377 Fr),
+ * batched: one GPU lane per hash.  Replaces, on the GPU,
+ *   src/hash/mod.rs:30-43      poseidon2_hash(input): sponge.absorb(&input), squeeze_native_field_elements(1)
+ *   src/hash/helpers.rs        the parameter set (8 full and 29 partial rounds, alpha = 17, a 3 x 3 MDS matrix, 37 x 3 round keys)
+ * The sponge [U]: rate 2, capacity 1, state width 3, all zero at the start.  Round i of full_rounds + partial_rounds: state[k] +=
+ * ark[i][k]; x -> x^alpha on all three entries in the first and last full_rounds / 2 rounds, on state[0] alone between them;
+ * state = mds . state (new[a] = sum_b mds[a][b] state[b]).  Absorbing: permute when two elements have gone in since the last
+ * permutation, then state[idx] += e (the rate section is state[0..2]); nothing is done for an empty list.  Squeezing: permute,
+ * then copy state[0], state[1]; permute again after every two outputs.
+ * Bytes become elements [U] by prefixing the input with its length as 8 little-endian bytes and cutting the result into chunks of 31
+ * bytes, each read as a little-endian integer (the last chunk may be shorter).  swm_poseidon_pack_bytes does that on the host and
+ * needs no GPU: n_elems = (8 + len + 30) / 31 is always written; cap_elems below it is SWM_ERR_INVALID_ARG and elems stays untouched.
+ * A field element crosses this interface as 32 canonical little-endian bytes.
+ * swm_poseidon_create: the caller's parameters (mds row-major, 9 x 32 bytes; ark round after round, (F + P) x 3 x 32 bytes) go to the
+ * device; the library embeds no constants.  SWM_ERR_INVALID_ARG: an entry >= r, full_rounds odd or < 2, full_rounds + partial_rounds
+ * > 255, alpha < 2 or > 65535.
+ * swm_poseidon_hash_fr: `count` items of n_in elements each (0 <= n_in <= 4096), back to back; every item yields n_out squeezed
+ * elements (1 <= n_out <= 16): out is count x n_out x 32 bytes.  n_in = 2, n_out = 1 is a two-to-one compression.  An element >= r
+ * refuses the WHOLE call with SWM_ERR_INVALID_ARG and nothing is written.
+ * swm_poseidon_hash_fr_dev: the same on device buffers.  What the host form refuses is reported per item instead: d_status (count
+ * words, may be NULL) is 0 for an item that was computed and 1 for an element >= r; the output of such an item is zeros, the other
+ * items of the batch are unaffected.
+ * swm_poseidon_hash_bytes: `count` inputs of input_len bytes each (0 <= input_len <= 65536), back to back; length prefix and packing
+ * happen in the kernel; digests: count x 32 bytes.  With input_len = 0 `inputs` may be NULL.  _dev: device pointers (outputs 4-byte
+ * aligned).  count = 0 returns SWM_OK everywhere and launches nothing. */
+typedef struct swm_poseidon swm_poseidon;
+int swm_poseidon_create(swm_ctx *ctx, size_t full_rounds, size_t partial_rounds, uint64_t alpha, const uint8_t *mds,
+                        const uint8_t *ark, swm_poseidon **out);
+void swm_poseidon_destroy(swm_ctx *ctx, swm_poseidon *params);
+int swm_poseidon_hash_fr(swm_ctx *ctx, const swm_poseidon *params, const uint8_t *elems, size_t n_in, size_t count, size_t n_out,
+                         uint8_t *out);
+int swm_poseidon_hash_fr_dev(swm_ctx *ctx, const swm_poseidon *params, const void *d_elems, size_t n_in, size_t count, size_t n_out,
+                             void *d_out, void *d_status);
+int swm_poseidon_hash_bytes(swm_ctx *ctx, const swm_poseidon *params, const uint8_t *inputs, size_t input_len, size_t count,
+                            uint8_t *digests);
+int swm_poseidon_hash_bytes_dev(swm_ctx *ctx, const swm_poseidon *params, const void *d_inputs, size_t input_len, size_t count,
+                                void *d_digests);
+int swm_poseidon_pack_bytes(const uint8_t *input, size_t len, uint8_t *elems, size_t cap_elems, size_t *n_elems);
+
 /* ---------------------------------------------------------------------------------------------- one proof over several GPUs
  * every commitment MSM of swm_generate_proof / swm_generate_proving_and_verifying_keys is split by
  * point range — rank g of `world` takes coefficients and SRS powers [g n / world, (g+1) n / world) — and the

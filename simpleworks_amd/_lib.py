@@ -110,6 +110,13 @@ ABI = {
     "swm_schnorr_sign": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
     "swm_schnorr_verify": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p, _sz, ctypes.c_void_p]),
     "swm_schnorr_commitments": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_poseidon_create": (_int, [_vp, _sz, _sz, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_vp)]),
+    "swm_poseidon_destroy": (None, [_vp, _vp]),
+    "swm_poseidon_hash_fr": (_int, [_vp, _vp, ctypes.c_void_p, _sz, _sz, _sz, ctypes.c_void_p]),
+    "swm_poseidon_hash_fr_dev": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    "swm_poseidon_hash_bytes": (_int, [_vp, _vp, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
+    "swm_poseidon_hash_bytes_dev": (_int, [_vp, _vp, _vp, _sz, _sz, _vp]),
+    "swm_poseidon_pack_bytes": (_int, [ctypes.c_void_p, _sz, ctypes.c_void_p, _sz, ctypes.POINTER(_sz)]),
     "swm_profile_enable": (_int, [_vp, _int]),
     "swm_profile_reset": (_int, [_vp]),
     "swm_profile_json": (_int, [_vp, ctypes.c_char_p, _sz]),
@@ -144,6 +151,20 @@ def rccl_unique_id():
     if rc != 0:
         raise SwmError(rc, "swm_rccl_unique_id", load_library().swm_last_error(None).decode(errors="replace"))
     return bytes(buf)
+
+
+def poseidon_pack_bytes(data):
+    """swm_poseidon_pack_bytes: the field elements (ints) that stand for a byte string in the Poseidon sponge; needs no GPU."""
+    data = bytes(data)
+    lib = load_library()
+    n = _sz(0)
+    cap = (8 + len(data) + 30) // 31
+    out = np.empty((cap, 32), dtype=np.uint8)
+    src = np.frombuffer(data, dtype=np.uint8)
+    rc = lib.swm_poseidon_pack_bytes(src.ctypes.data if len(data) else None, len(data), out.ctypes.data, cap, ctypes.byref(n))
+    if rc != 0:
+        raise SwmError(rc, "swm_poseidon_pack_bytes", lib.swm_last_error(None).decode(errors="replace"))
+    return [int.from_bytes(out[i].tobytes(), "little") for i in range(n.value)]
 
 
 class SwmError(RuntimeError):
@@ -524,6 +545,47 @@ class Context:
         self._check(self.lib.swm_schnorr_commitments(self.h, handle, pk.ctypes.data, sig.ctypes.data, pk.shape[0], out.ctypes.data),
                     "swm_schnorr_commitments")
         return out
+
+    # ---- Poseidon sponge (include/swmarlin.h; simpleworks_amd/hash.py, PoseidonSponge, is the caller-facing mirror)
+    def poseidon_create(self, full_rounds, partial_rounds, alpha, mds, ark):
+        """mds: 9 x 32 bytes (row-major), ark: (full_rounds + partial_rounds) x 3 x 32 bytes, canonical little-endian."""
+        m = np.frombuffer(bytes(mds), dtype=np.uint8)
+        a = np.frombuffer(bytes(ark), dtype=np.uint8)
+        assert m.size == 9 * 32 and a.size == 96 * (full_rounds + partial_rounds)
+        h = _vp()
+        self._check(self.lib.swm_poseidon_create(self.h, full_rounds, partial_rounds, alpha, m.ctypes.data, a.ctypes.data, ctypes.byref(h)),
+                    "swm_poseidon_create")
+        return h
+
+    def poseidon_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_poseidon_destroy(self.h, handle)
+
+    def poseidon_hash_fr(self, handle, elems, n_out=1, out=None):
+        """elems: uint8 [count, n_in, 32] (canonical little-endian) -> uint8 [count, n_out, 32]."""
+        e = np.ascontiguousarray(elems, dtype=np.uint8)
+        assert e.ndim == 3 and e.shape[2] == 32
+        out = np.empty((e.shape[0], n_out, 32), dtype=np.uint8) if out is None else out
+        self._check(self.lib.swm_poseidon_hash_fr(self.h, handle, e.ctypes.data if e.size else None, e.shape[1], e.shape[0], n_out,
+                                                  out.ctypes.data), "swm_poseidon_hash_fr")
+        return out
+
+    def poseidon_hash_fr_dev(self, handle, d_elems, n_in, count, n_out, d_out, d_status=None):
+        self._check(self.lib.swm_poseidon_hash_fr_dev(self.h, handle, d_elems.ptr if d_elems else None, n_in, count, n_out, d_out.ptr,
+                                                      d_status.ptr if d_status else None), "swm_poseidon_hash_fr_dev")
+
+    def poseidon_hash_bytes(self, handle, inputs):
+        """inputs: uint8 [count, input_len] (input_len may be 0) -> uint8 [count, 32] digests."""
+        a = np.ascontiguousarray(inputs, dtype=np.uint8)
+        assert a.ndim == 2
+        out = np.empty((a.shape[0], 32), dtype=np.uint8)
+        self._check(self.lib.swm_poseidon_hash_bytes(self.h, handle, a.ctypes.data if a.size else None, a.shape[1], a.shape[0],
+                                                     out.ctypes.data), "swm_poseidon_hash_bytes")
+        return out
+
+    def poseidon_hash_bytes_dev(self, handle, d_inputs, input_len, count, d_digests):
+        self._check(self.lib.swm_poseidon_hash_bytes_dev(self.h, handle, d_inputs.ptr if d_inputs else None, input_len, count,
+                                                         d_digests.ptr), "swm_poseidon_hash_bytes_dev")
 
     # ---- measurement
     def profile_enable(self, on=True):

@@ -190,4 +190,25 @@ int swm_merkle_circuit_shape(size_t height, size_t gadget_byte_ops, size_t* num_
     return SWM_OK;
 }
 
+// Absorb for [u8] of ark-sponge 0.3.0 [U]: the length as 8 little-endian bytes, then the input, cut into chunks of 31 bytes
+// (CAPACITY / 8 = 252 / 8), each a little-endian integer (< 2^248 < r) written as 32 bytes.  The kernel of poseidon.hip packs
+// the same way; this is the rule on the host, for callers that mix bytes and elements.
+int swm_poseidon_pack_bytes(const uint8_t* input, size_t len, uint8_t* elems, size_t cap_elems, size_t* n_elems) {
+    swm_ctx* none = nullptr;
+    if (!n_elems || (len && !input) || len > ((size_t)1 << 40))
+        return set_err(none, SWM_ERR_INVALID_ARG, "poseidon_pack_bytes: bad arguments");
+    const size_t total = 8 + len, need = (total + 30) / 31;
+    *n_elems = need;
+    if (cap_elems < need || !elems)
+        return set_err(none, SWM_ERR_INVALID_ARG, "poseidon_pack_bytes: %zu bytes make %zu elements, room for %zu", len, need, cap_elems);
+    for (size_t e = 0; e < need; e++) {
+        uint8_t* o = elems + 32 * e;
+        for (size_t j = 0; j < 32; j++) {
+            const size_t pos = 31 * e + j;  // position in (length || input)
+            o[j] = (j == 31 || pos >= total) ? 0 : pos < 8 ? (uint8_t)((uint64_t)len >> (8 * pos)) : input[pos - 8];
+        }
+    }
+    return SWM_OK;
+}
+
 }  // extern "C"

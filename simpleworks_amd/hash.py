@@ -1,4 +1,5 @@
-"""Native Pedersen hash and Pedersen Merkle tree, computed on the GPU (csrc/pedersen.hip through include/swmarlin.h).
+"""Native Pedersen hash, Pedersen Merkle tree and Poseidon sponge, computed on the GPU (csrc/pedersen.hip and csrc/poseidon.hip
+through include/swmarlin.h).
 
 Caller-facing mirror of what the reference reaches through ark-crypto-primitives 0.3:
     src/hash/mod.rs:13-28                           pedersen_hash(input): LeafWindow 144 x 4, parameters from a fresh test_rng
@@ -6,13 +7,18 @@ Caller-facing mirror of what the reference reaches through ark-crypto-primitives
                                                     MerkleTree::<MerkleConfig>::new(&leaf_crh_params, &two_to_one_crh_params, leaves)
     src/merkle_tree/simple_merkle_tree.rs:99-103    tree.generate_proof(leaf_index), tree.root()
     src/merkle_tree/common.rs:11-30                 the two window shapes
+and through ark-sponge 0.3:
+    src/hash/mod.rs:30-43                           poseidon2_hash(input): PoseidonSponge<Fq>, absorb the bytes, squeeze one element
 
 Host side (this file): sampling the parameters — CRH::setup is a few hundred curve operations, done with Python integers the
 way ark-ec samples a twisted Edwards point [U] — and the tree's bookkeeping.  Every hash runs on the GPU; there is no CPU
 evaluation path here (the checker lives under oracle/).
 """
+import json
+
 import numpy as np
 
+from ._lib import poseidon_pack_bytes  # noqa: F401  (the sponge's byte-to-element rule on the host)
 from .marlin import R_MODULUS, default_context, generate_rand, merkle_circuit_shape
 
 ED_D = 3021            # ed-on-BLS12-377: -x^2 + y^2 = 1 + 3021 x^2 y^2 over BLS12-377 Fr
@@ -224,3 +230,82 @@ class MerkleCircuit:
             self.free()
         except Exception:
             pass
+
+
+class PoseidonParameters:
+    """ark_sponge::poseidon::PoseidonParameters<Fq> as PoseidonParameters::new(full_rounds, partial_rounds, alpha, mds, ark) builds
+    it [U]: rate 2, capacity 1, a 3 x 3 matrix and full_rounds + partial_rounds rows of three round keys.  Entries are integers,
+    reduced mod r here as F::from_str reduces the decimal strings of src/hash/helpers.rs.  The values are the caller's: this package
+    restates no constant table."""
+
+    def __init__(self, full_rounds, partial_rounds, alpha, mds, ark):
+        self.full_rounds, self.partial_rounds, self.alpha = int(full_rounds), int(partial_rounds), int(alpha)
+        self.mds = [[int(v) % R_MODULUS for v in row] for row in mds]
+        self.ark = [[int(v) % R_MODULUS for v in row] for row in ark]
+        if len(self.mds) != 3 or any(len(row) != 3 for row in self.mds):
+            raise ValueError("mds must be 3 x 3 (rate 2 + capacity 1)")
+        if len(self.ark) != self.full_rounds + self.partial_rounds or any(len(row) != 3 for row in self.ark):
+            raise ValueError("ark must hold full_rounds + partial_rounds rows of 3 entries")
+
+    @classmethod
+    def from_json(cls, path):
+        """{"full_rounds", "partial_rounds", "alpha", "mds": 3 x 3, "ark": rounds x 3}, entries as decimal strings or integers."""
+        with open(path) as f:
+            d = json.load(f)
+        return cls(d["full_rounds"], d["partial_rounds"], d["alpha"], d["mds"], d["ark"])
+
+
+def _fr_rows(items):
+    """items: a uint8 array [count, n_in, 32], or a sequence of equally long sequences of ints / 32-byte strings."""
+    if isinstance(items, np.ndarray):
+        return np.ascontiguousarray(items, dtype=np.uint8)
+    rows = [b"".join(bytes(e) if isinstance(e, (bytes, bytearray, np.ndarray)) else int(e).to_bytes(32, "little") for e in item)
+            for item in items]
+    if len({len(r) for r in rows}) > 1:
+        raise ValueError("the items of one call hold the same number of elements")
+    n_in = len(rows[0]) // 32 if rows else 0
+    return np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), n_in, 32)
+
+
+class PoseidonSponge:
+    """PoseidonSponge<Fq> with its parameters resident on the GPU (swm_poseidon): every call absorbs into a fresh sponge per item
+    and squeezes, one GPU lane per item."""
+
+    def __init__(self, params, ctx=None):
+        self.ctx = ctx or default_context()
+        self.params = params
+        mds = b"".join(v.to_bytes(32, "little") for row in params.mds for v in row)
+        ark = b"".join(v.to_bytes(32, "little") for row in params.ark for v in row)
+        self.h = self.ctx.poseidon_create(params.full_rounds, params.partial_rounds, params.alpha, mds, ark)
+
+    def hash_many(self, inputs):
+        """inputs: uint8 [count, input_len] -> uint8 [count, 32]: absorb(&input) and squeeze_native_field_elements(1) of each,
+        as 32 little-endian bytes."""
+        return self.ctx.poseidon_hash_bytes(self.h, inputs)
+
+    def hash_elements_many(self, items, n_out=1):
+        """items: per item the same number of field elements (ints or 32 little-endian bytes each; or uint8 [count, n_in, 32])
+        -> uint8 [count, n_out, 32].  Two elements in and one out is a two-to-one compression."""
+        return self.ctx.poseidon_hash_fr(self.h, _fr_rows(items), n_out)
+
+    def free(self):
+        if self.h:
+            self.ctx.poseidon_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def poseidon2_hash(data, params, ctx=None):
+    """src/hash/mod.rs:32-43: a sponge over `params` (the reference takes helpers::poseidon_parameters_for_test()), absorb the
+    bytes, the first squeezed element -> Fq (as an integer)."""
+    sponge = PoseidonSponge(params, ctx)
+    try:
+        a = np.frombuffer(bytes(data), dtype=np.uint8).reshape(1, -1)
+        return int.from_bytes(sponge.hash_many(a)[0].tobytes(), "little")
+    finally:
+        sponge.free()

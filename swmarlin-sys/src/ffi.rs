@@ -12,6 +12,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_pedersen { _p: [u8; 0] }
 #[repr(C)] pub struct swm_schnorr { _p: [u8; 0] }
 #[repr(C)] pub struct swm_merkle_circuit { _p: [u8; 0] }
+#[repr(C)] pub struct swm_poseidon { _p: [u8; 0] }
 
 pub const SWM_OK: c_int = 0;
 pub const SWM_ERR_UNSATISFIED: c_int = -5;
@@ -156,4 +157,19 @@ extern "C" {
                               msg_len: usize, signatures: *const u8, count: usize, ok: *mut u8) -> c_int;
     pub fn swm_schnorr_commitments(ctx: *mut swm_ctx, params: *const swm_schnorr, public_keys_xy: *const u8, signatures: *const u8,
                                    count: usize, commitments_xy: *mut u8) -> c_int;
+
+    // the native Poseidon hash of src/hash/mod.rs:30-43 (PoseidonSponge<Fq>, rate 2), batched; a field element: 32 canonical LE bytes;
+    // the parameters are the caller's (mds: 9 elements row-major, ark: (full + partial) x 3)
+    pub fn swm_poseidon_create(ctx: *mut swm_ctx, full_rounds: usize, partial_rounds: usize, alpha: u64, mds: *const u8, ark: *const u8,
+                               out: *mut *mut swm_poseidon) -> c_int;
+    pub fn swm_poseidon_destroy(ctx: *mut swm_ctx, params: *mut swm_poseidon);
+    pub fn swm_poseidon_hash_fr(ctx: *mut swm_ctx, params: *const swm_poseidon, elems: *const u8, n_in: usize, count: usize,
+                                n_out: usize, out: *mut u8) -> c_int;
+    pub fn swm_poseidon_hash_fr_dev(ctx: *mut swm_ctx, params: *const swm_poseidon, d_elems: *const c_void, n_in: usize, count: usize,
+                                    n_out: usize, d_out: *mut c_void, d_status: *mut c_void) -> c_int;
+    pub fn swm_poseidon_hash_bytes(ctx: *mut swm_ctx, params: *const swm_poseidon, inputs: *const u8, input_len: usize, count: usize,
+                                   digests: *mut u8) -> c_int;
+    pub fn swm_poseidon_hash_bytes_dev(ctx: *mut swm_ctx, params: *const swm_poseidon, d_inputs: *const c_void, input_len: usize,
+                                       count: usize, d_digests: *mut c_void) -> c_int;
+    pub fn swm_poseidon_pack_bytes(input: *const u8, len: usize, elems: *mut u8, cap_elems: usize, n_elems: *mut usize) -> c_int;
 }

@@ -42,9 +42,10 @@ def u32(x):
     return x
 
 
-def mul(a, b):
-    """fr29_mul: a may be lazy (limbs < 2^32), b normalised (limbs < 2^29: a table entry, or the product of two); a b < 2^261 r."""
-    assert all(0 <= x < 1 << 32 for x in a) and all(0 <= x < 1 << 29 for x in b[:8]) and b[8] < 1 << 23
+def mul(a, b, top_bits=23):
+    """fr29_mul: a may be lazy (limbs < 2^32), b normalised (limbs < 2^29: a table entry, or the product of two); a b < 2^261 r.
+    top_bits: what the caller promises for b's top limb (the transform: a value < 2r; tools/check_poseidon29.py: < 9r)."""
+    assert all(0 <= x < 1 << 32 for x in a) and all(0 <= x < 1 << 29 for x in b[:8]) and b[8] < 1 << top_bits
     assert val(a) * val(b) < (1 << 261) * R, "product too large for a result below 2r"
     m, r, acc = [0] * 9, [0] * 9, 0
     for k in range(9):
