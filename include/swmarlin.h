@@ -416,6 +416,42 @@ int swm_schnorr_verify(swm_ctx *ctx, const swm_schnorr *params, const uint8_t *p
 int swm_schnorr_commitments(swm_ctx *ctx, const swm_schnorr *params, const uint8_t *public_keys_xy, const uint8_t *signatures,
                             size_t count, uint8_t *commitments_xy);
 
+/* ---------------------------------------------------------------------------------------------- Schnorr verification witness
+ * The assignment of the Schnorr verification circuit (SimpleSchnorrSignatureVerification, examples/simple-payments/transaction.rs:
+ * 33-71, as this library lays it out: simpleworks_amd/workloads.py, build_schnorr_verification) synthesised on the GPU: what
+ * transaction.rs:108-126 hands to the prover, without running the constraint synthesizer on the host.  The circuit's shape depends
+ * on the message length and on whether the parameters carry a salt:
+ *   blocks B = ceil((128 + 32 salted + msg_len) / 64);  num_instance = 1 (no public input);
+ *   num_witness = 6649 + 8 msg_len + 21472 B;  num_constraints = 6672 + 8 msg_len + 21792 B.
+ * The circuit multiplies by s and e as 256-bit integers, unreduced and unchecked, and has no subgroup check: for a key in the
+ * prime subgroup it accepts exactly what swm_schnorr_verify accepts among responses < l; for an on-curve key outside the subgroup
+ * e Y and (e mod l) Y differ and the two may disagree.
+ * swm_schnorr_circuit_shape needs no GPU.  SWM_ERR_INVALID_ARG: msg_len > 65536, a NULL output.
+ * swm_schnorr_circuit_create: the shape of `params` (its salt) and msg_len.  The handle refers to the swm_schnorr: keep it.
+ * swm_schnorr_witness: `count` signatures in one launch, one workgroup each.  public_keys_xy: count x 64 bytes; messages: count x
+ * msg_len bytes (may be NULL when msg_len = 0); signatures: count x 64 bytes.  A key coordinate >= r or a point off the curve
+ * refuses the WHOLE call with SWM_ERR_INVALID_ARG and nothing is written.  witness: count x num_witness x 4 Montgomery limbs, in
+ * the circuit's variable order; ok (may be NULL): count bytes, 1 where the digest equals the challenge, i.e. where the witness
+ * satisfies the circuit.  A batch whose witnesses exceed 1 GiB is staged through the device in chunks of floor(1 GiB /
+ * (32 num_witness)) signatures (at least one).  count = 0 launches nothing.
+ * swm_schnorr_witness_dev: the same on device buffers (keys and signatures 4-byte aligned), no chunking.  What the host form refuses
+ * is reported per item instead: d_status (count words, may be NULL) is 0 for an item that was computed and 1 for a bad key; the
+ * witness of such an item is zero and its ok byte 0, the other items of the batch are unaffected.
+ * swm_schnorr_prove: witness on the device, then the proof of swm_generate_proof_ex(flags) with the empty public input: the
+ * witness reaches the prover by a device-to-device copy.  A signature that does not verify is SWM_ERR_UNSATISFIED, a key indexed
+ * for another shape SWM_ERR_MISMATCH. */
+typedef struct swm_schnorr_circuit swm_schnorr_circuit;
+int swm_schnorr_circuit_shape(size_t msg_len, int salted, size_t *num_instance, size_t *num_witness, size_t *num_constraints);
+int swm_schnorr_circuit_create(swm_ctx *ctx, const swm_schnorr *params, size_t msg_len, swm_schnorr_circuit **out);
+void swm_schnorr_circuit_destroy(swm_ctx *ctx, swm_schnorr_circuit *circuit);
+int swm_schnorr_witness(swm_ctx *ctx, const swm_schnorr_circuit *circuit, const uint8_t *public_keys_xy, const uint8_t *messages,
+                        const uint8_t *signatures, size_t count, uint64_t *witness, uint8_t *ok);
+int swm_schnorr_witness_dev(swm_ctx *ctx, const swm_schnorr_circuit *circuit, const void *d_public_keys, const void *d_messages,
+                            const void *d_signatures, size_t count, void *d_witness, void *d_ok, void *d_status);
+int swm_schnorr_prove(swm_ctx *ctx, const swm_pk *pk, const swm_schnorr_circuit *circuit, const uint8_t public_key_xy[64],
+                      const uint8_t *message, const uint8_t signature[64], swm_rng *rng, unsigned flags, uint8_t *proof_out,
+                      size_t cap, size_t *len);
+
 /* ---------------------------------------------------------------------------------------------- Poseidon sponge
  * The reference's native Poseidon hash, PoseidonSponge<Fq> of ark-sponge 0.3.0 over Fq of ed-on-BLS12-377 (= BLS12-377 Fr),
  * batched: one GPU lane per hash.  Replaces, on the GPU,

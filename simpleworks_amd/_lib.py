@@ -110,6 +110,13 @@ ABI = {
     "swm_schnorr_sign": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
     "swm_schnorr_verify": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p, _sz, ctypes.c_void_p]),
     "swm_schnorr_commitments": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_schnorr_circuit_shape": (_int, [_sz, _int, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "swm_schnorr_circuit_create": (_int, [_vp, _vp, _sz, ctypes.POINTER(_vp)]),
+    "swm_schnorr_circuit_destroy": (None, [_vp, _vp]),
+    "swm_schnorr_witness": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_schnorr_witness_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "swm_schnorr_prove": (_int, [_vp, _vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _vp, ctypes.c_uint,
+                                 ctypes.POINTER(ctypes.c_uint8), _sz, ctypes.POINTER(_sz)]),
     "swm_poseidon_create": (_int, [_vp, _sz, _sz, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_vp)]),
     "swm_poseidon_destroy": (None, [_vp, _vp]),
     "swm_poseidon_hash_fr": (_int, [_vp, _vp, ctypes.c_void_p, _sz, _sz, _sz, ctypes.c_void_p]),
@@ -545,6 +552,34 @@ class Context:
         self._check(self.lib.swm_schnorr_commitments(self.h, handle, pk.ctypes.data, sig.ctypes.data, pk.shape[0], out.ctypes.data),
                     "swm_schnorr_commitments")
         return out
+
+    # ---- Schnorr verification witness (include/swmarlin.h; simpleworks_amd/schnorr.py, SchnorrCircuit, is the caller-facing mirror)
+    def schnorr_circuit_create(self, params_handle, msg_len):
+        h = _vp()
+        self._check(self.lib.swm_schnorr_circuit_create(self.h, params_handle, msg_len, ctypes.byref(h)), "swm_schnorr_circuit_create")
+        return h
+
+    def schnorr_circuit_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_schnorr_circuit_destroy(self.h, handle)
+
+    def schnorr_witness(self, handle, num_witness, public_keys, messages, signatures):
+        """public_keys uint8 [count, 64], messages uint8 [count, msg_len], signatures uint8 [count, 64] ->
+        (witness uint64 [count, num_witness, 4] Montgomery limbs, ok uint8 [count])."""
+        pk = self._rows(public_keys, 64)
+        n = pk.shape[0]
+        sig = self._rows(signatures, 64, n)
+        m = self._rows(messages, None, n)
+        witness = np.empty((n, num_witness, 4), dtype=np.uint64)
+        ok = np.empty(n, dtype=np.uint8)
+        self._check(self.lib.swm_schnorr_witness(self.h, handle, pk.ctypes.data, m.ctypes.data if m.shape[1] else None, sig.ctypes.data, n,
+                                                 witness.ctypes.data, ok.ctypes.data), "swm_schnorr_witness")
+        return witness, ok
+
+    def schnorr_witness_dev(self, handle, d_public_keys, d_messages, d_signatures, count, d_witness, d_ok=None, d_status=None):
+        self._check(self.lib.swm_schnorr_witness_dev(self.h, handle, d_public_keys.ptr, d_messages.ptr if d_messages else None,
+                                                     d_signatures.ptr, count, d_witness.ptr, d_ok.ptr if d_ok else None,
+                                                     d_status.ptr if d_status else None), "swm_schnorr_witness_dev")
 
     # ---- Poseidon sponge (include/swmarlin.h; simpleworks_amd/hash.py, PoseidonSponge, is the caller-facing mirror)
     def poseidon_create(self, full_rounds, partial_rounds, alpha, mds, ark):

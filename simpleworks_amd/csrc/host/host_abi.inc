@@ -7,6 +7,7 @@
 #include <memory>
 #include <new>
 #include "merkle_shape.h"
+#include "schnorr_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
 extern "C" {
@@ -184,6 +185,21 @@ int swm_merkle_circuit_shape(size_t height, size_t gadget_byte_ops, size_t* num_
     if (!merkle_shape(height, gadget_byte_ops, &s))
         return set_err(none, SWM_ERR_INVALID_ARG, "merkle_circuit_shape: height %zu with %zu byte operations (2 <= height <= %zu)",
                        height, gadget_byte_ops, (size_t)MW_MAX_HEIGHT);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// The Schnorr verification circuit's shape from the message length and the presence of a salt (schnorr_shape.h; the layout is
+// build_schnorr_verification's)
+int swm_schnorr_circuit_shape(size_t msg_len, int salted, size_t* num_instance, size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "schnorr_circuit_shape: NULL output");
+    SchnorrShape s;
+    if (!schnorr_shape(msg_len, salted != 0, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG, "schnorr_circuit_shape: msg_len %zu (at most %zu)", msg_len, (size_t)SV_MAX_MSG_LEN);
     *num_instance = s.num_instance;
     *num_witness = s.num_witness;
     *num_constraints = s.num_constraints;

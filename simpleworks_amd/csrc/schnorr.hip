@@ -26,6 +26,7 @@
 #include "ed.cuh"
 #include "ff.cuh"
 #include "frinv.cuh"
+#include "schnorr.h"
 #include "swmarlin.h"
 
 namespace swm {
@@ -421,12 +422,6 @@ __global__ void __launch_bounds__(256) schnorr_verify_kernel(SchnorrDev P, const
 }
 
 }  // namespace swm
-
-struct swm_schnorr {
-    void* d_table = nullptr;  // 32 x 256 rows (swm::EdRow)
-    uint32_t salt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool has_salt = false;
-};
 
 using namespace swm;
 

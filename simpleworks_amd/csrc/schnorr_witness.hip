@@ -1,0 +1,533 @@
+// schnorr_witness.hip — the witness of the Schnorr verification circuit, synthesised on the GPU: the step between a signature
+// (schnorr.hip) and its proof (marlin.hip).
+//
+// What the reference does there: every transaction of examples/simple-payments (transaction.rs:33-71, :89-139) proves a
+// SimpleSchnorrSignatureVerification, and MarlinInst::prove runs its generate_constraints into a fresh constraint system — the
+// whole circuit, on one CPU thread, per proof.  The prover reads only the ASSIGNMENT (the matrices are the key's) and the
+// circuit's shape depends on the message length and on whether there is a salt, so what is left per proof is the witness
+// vector.  Its order and values are those of simpleworks_amd/workloads.py, build_schnorr_verification: that function is the
+// specification, host/schnorr_shape.h the offsets and the Blake2s schedule.
+//
+// On the GPU: one workgroup of 256 lanes per signature, lane i on bit i of s and of e.
+//   fix   lane i takes s_i ? 2^i G : identity from the resident 8-bit window table of swm_schnorr (window i / 8, entry
+//         1 << (i % 8)); an inclusive scan with the unified addition (shuffles inside a wave, LDS between the four) gives the
+//         prefix sums, ONE shared inversion makes them affine, and the six witnesses of step i are pointwise from P_{i-1}, P_i.
+//   dbl   2^i Y is sequential: lane 0 doubles in extended coordinates into LDS; one shared inversion makes all 256 affine;
+//         xy, xx, yy and the next point are pointwise.
+//   sel / add   Q_i = e_i ? P_i : identity, a scan for acc_i, a third shared inversion, seven pointwise witnesses per step.
+//   sum   R' = s G + acc_255 on the last lane, which holds both.
+//   dec   the four coordinates in standard form, expanded to 0/1 elements by all lanes.
+//   b2s   one lane runs each compression on plain words and records every sum (with its carries) and every xor into LDS
+//         (sv_b2s_compress_record); all lanes expand the recorded words at the offsets of sv_b2s_slot.
+// The law is complete (ed.cuh): the identity, keys of order 2 and 4, keys outside the subgroup, s = 0 and e = 0 take the common
+// path and no Z is zero.  ok[i] = 1 when the digest equals the challenge: the comparison rows hold exactly then.
+#include <hip/hip_runtime.h>
+
+#include <memory>
+
+#include "context.h"
+#include "ed.cuh"
+#include "ff.cuh"
+#include "frinv.cuh"
+#include "host/schnorr_shape.h"
+#include "schnorr.h"
+#include "swmarlin.h"
+
+struct swm_schnorr_circuit {
+    const swm_schnorr* params = nullptr;
+    swm::SchnorrShape shape;
+};
+
+namespace swm {
+
+static constexpr unsigned SV_LANES = 256;  // = bits of a scalar
+static constexpr unsigned SV_WAVES = SV_LANES / 64;
+
+struct SvShared {
+    Fr ax[SV_LANES], ay[SV_LANES];                // affine points handed to the neighbouring lane
+    Fr px[SV_LANES], py[SV_LANES], pz[SV_LANES];  // the doubling chain, extended (T is not needed to go affine)
+    EdExt wave_sum[SV_WAVES];
+    Fr wave_prod[SV_WAVES];
+    Fr inv;
+    uint64_t rec[SV_BLOCK_WORDS];
+    uint32_t piece[5][8];  // salt | Y.x | Y.y | R'.x | R'.y, the words that enter the hash
+    uint32_t m[16], h[8];
+    uint32_t sbits[8], ebits[8];
+    uint32_t bad;
+};
+
+__device__ __forceinline__ Fr sv_shfl_up(const Fr& a, unsigned d) {
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)__shfl_up((int)a.v[i], d, 64);
+    return r;
+}
+__device__ __forceinline__ Fr sv_shfl_down(const Fr& a, unsigned d) {
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)__shfl_down((int)a.v[i], d, 64);
+    return r;
+}
+__device__ __forceinline__ EdExt sv_ed_shfl_up(const EdExt& p, unsigned d) {
+    EdExt r;
+    r.x = sv_shfl_up(p.x, d);
+    r.y = sv_shfl_up(p.y, d);
+    r.t = sv_shfl_up(p.t, d);
+    r.z = sv_shfl_up(p.z, d);
+    return r;
+}
+
+// Inclusive scan of one point per lane over the 256 lanes.  Called by all lanes; synchronises.
+__device__ __noinline__ EdExt sv_scan(EdExt acc, const Fr k2d, SvShared& sh) {
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll 1
+    for (unsigned d = 1; d < 64; d <<= 1) {
+        const EdExt o = sv_ed_shfl_up(acc, d);
+        if (lane >= d) acc = ed_add(o, acc, k2d);
+    }
+    if (lane == 63) sh.wave_sum[wave] = acc;
+    __syncthreads();
+    if (wave) {
+        EdExt below = sh.wave_sum[0];
+#pragma unroll 1
+        for (unsigned k = 1; k < wave; k++) below = ed_add(below, sh.wave_sum[k], k2d);
+        acc = ed_add(below, acc, k2d);
+    }
+    __syncthreads();  // wave_sum[] has been read
+    return acc;
+}
+
+// 1 / z of every lane with ONE inversion: prefix and suffix products over the lanes, the inverse of the total on one lane
+// (frinv.cuh), two multiplications back.  No z is zero.  Called by all lanes; synchronises.
+__device__ __noinline__ Fr sv_batch_inv(const Fr z, SvShared& sh) {
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    Fr pre = z, suf = z;  // inclusive products over the lanes below / above, within the wave
+#pragma unroll 1
+    for (unsigned d = 1; d < 64; d <<= 1) {
+        const Fr o = sv_shfl_up(pre, d);
+        const Fr u = sv_shfl_down(suf, d);
+        if (lane >= d) pre = fp_mul(o, pre);
+        if (lane + d < 64) suf = fp_mul(u, suf);
+    }
+    if (lane == 63) sh.wave_prod[wave] = pre;
+    __syncthreads();
+    Fr below = sv_shfl_up(pre, 1), above = sv_shfl_down(suf, 1);  // exclusive
+    if (lane == 0) below = fp_one<Fr>();
+    if (lane == 63) above = fp_one<Fr>();
+#pragma unroll 1
+    for (unsigned k = 0; k < SV_WAVES; k++) {
+        if (k < wave) below = fp_mul(sh.wave_prod[k], below);
+        if (k > wave) above = fp_mul(above, sh.wave_prod[k]);
+    }
+    if (tid == 0) {
+        Fr total = sh.wave_prod[0];
+#pragma unroll 1
+        for (unsigned k = 1; k < SV_WAVES; k++) total = fp_mul(total, sh.wave_prod[k]);
+        sh.inv = fr_inv_single(total);
+    }
+    __syncthreads();
+    const Fr r = fp_mul(fp_mul(below, above), sh.inv);
+    __syncthreads();  // wave_prod[] and inv have been read
+    return r;
+}
+
+__device__ __forceinline__ EdExt sv_from_affine(const Fr& x, const Fr& y) {
+    EdExt p;
+    p.x = x;
+    p.y = y;
+    p.t = fp_mul(x, y);
+    p.z = fp_one<Fr>();
+    return p;
+}
+
+// x1y2, y1x2, y1y2, x1x2, their product, x3, y3 of (x1, y1) + (x2, y2) = (x3, y3)
+__device__ __forceinline__ void sv_add_witnesses(Fr* o, const Fr& x1, const Fr& y1, const Fr& x2, const Fr& y2, const Fr& x3, const Fr& y3) {
+    const Fr a = fp_mul(x1, y2), b = fp_mul(y1, x2);
+    o[0] = a;
+    o[1] = b;
+    o[2] = fp_mul(y1, y2);
+    o[3] = fp_mul(x1, x2);
+    o[4] = fp_mul(a, b);
+    o[5] = x3;
+    o[6] = y3;
+}
+
+SWM_HD bool sv_canonical(const uint32_t* w, Fr* mont) {
+    Fr s, r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        s.v[i] = w[i];
+        r.v[i] = FrParams::P[i];
+    }
+    if (fp_cmp_std(s, r) >= 0) return false;
+    *mont = fp_from_std(s);
+    return true;
+}
+// -x^2 + y^2 == 1 + d x^2 y^2
+SWM_HD bool sv_on_curve(const Fr& x, const Fr& y, const Fr& d) {
+    const Fr x2 = fp_sqr(x), y2 = fp_sqr(y);
+    return fp_eq(fp_sub(y2, x2), fp_add(fp_one<Fr>(), fp_mul(d, fp_mul(x2, y2))));
+}
+
+struct SvParams {
+    const EdRow* table;  // [32 windows][256]: row (w, v) = v 2^(8 w) G
+    Fr k2d, d, half;
+    uint32_t salt[8];
+    uint32_t salted;
+    uint32_t msg_len, blocks, hash_len;
+    uint32_t sig_at, fix_at, dbl_at, sel_at, add_at, sum_at, dec_at, b2s_at;
+    size_t num_witness;
+};
+
+// Block p = signature p.  keys: 64 bytes each, sigs: 64 bytes each (both 4-byte aligned), msgs: msg_len bytes each.
+__global__ void __launch_bounds__(SV_LANES) schnorr_witness_kernel(SvParams P, const uint8_t* __restrict__ keys, const uint8_t* __restrict__ msgs,
+                                                                   const uint8_t* __restrict__ sigs, Fr* __restrict__ witness,
+                                                                   uint8_t* __restrict__ ok, uint32_t* __restrict__ status) {
+    __shared__ SvShared sh;
+    const unsigned tid = threadIdx.x;
+    const size_t item = blockIdx.x;
+    Fr* w = witness + item * P.num_witness;
+    const uint32_t* key = reinterpret_cast<const uint32_t*>(keys + 64 * item);
+    const uint32_t* sig = reinterpret_cast<const uint32_t*>(sigs + 64 * item);
+    const uint8_t* msg = msgs + item * (size_t)P.msg_len;
+    const Fr one = fp_one<Fr>(), zero = fp_zero<Fr>();
+
+    // what the host form refuses: a key coordinate that is no canonical field element, a point off the curve
+    if (tid < 8) {
+        sh.piece[0][tid] = P.salt[tid];
+        sh.piece[1][tid] = key[tid];
+        sh.piece[2][tid] = key[8 + tid];
+        sh.sbits[tid] = sig[tid];
+        sh.ebits[tid] = sig[8 + tid];
+    }
+    Fr yx = zero, yy = one;
+    if (tid == 0) {
+        uint32_t kx[8], ky[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            kx[i] = key[i];
+            ky[i] = key[8 + i];
+        }
+        const bool good = sv_canonical(kx, &yx) && sv_canonical(ky, &yy) && sv_on_curve(yx, yy, P.d);
+        sh.bad = good ? 0u : 1u;
+    }
+    __syncthreads();
+    if (sh.bad) {
+        uint4* wz = reinterpret_cast<uint4*>(w);
+        for (size_t i = tid; i < 2 * P.num_witness; i += SV_LANES) wz[i] = make_uint4(0, 0, 0, 0);
+        if (tid == 0) {
+            if (ok) ok[item] = 0;
+            if (status) status[item] = 1;
+        }
+        return;
+    }
+    if (status && tid == 0) status[item] = 0;
+    const unsigned sbit = (sh.sbits[tid >> 5] >> (tid & 31)) & 1u, ebit = (sh.ebits[tid >> 5] >> (tid & 31)) & 1u;
+
+    // key, msg, sig
+    if (tid == 0) {
+        w[SV_KEY_AT] = yx;
+        w[SV_KEY_AT + 1] = yy;
+        w[SV_KEY_AT + 2] = fp_sqr(yx);
+        w[SV_KEY_AT + 3] = fp_sqr(yy);
+    }
+    for (unsigned i = tid; i < 8 * P.msg_len; i += SV_LANES) w[SV_MSG_AT + i] = (msg[i >> 3] >> (i & 7)) & 1u ? one : zero;
+    w[P.sig_at + tid] = sbit ? one : zero;
+    w[P.sig_at + SV_LANES + tid] = ebit ? one : zero;
+
+    // fix: prefix sums of s_i 2^i G
+    const EdRow* row = P.table + (((tid >> 3) << 8) + (1u << (tid & 7)));
+    Fr fx, fy;  // P_tid, affine
+    {
+        EdExt acc = ed_identity();
+        if (sbit) ed_madd(acc, *row);
+        acc = sv_scan(acc, P.k2d, sh);
+        const Fr zi = sv_batch_inv(acc.z, sh);
+        fx = fp_mul(acc.x, zi);
+        fy = fp_mul(acc.y, zi);
+        sh.ax[tid] = fx;
+        sh.ay[tid] = fy;
+        __syncthreads();
+        if (tid) {
+            Fr* o = w + P.fix_at + SV_FIX_STEP * (size_t)(tid - 1);
+            const Fr X = sh.ax[tid - 1], Y = sh.ay[tid - 1];
+            const Fr t = fp_mul(X, Y);
+            o[0] = t;
+            if (sbit) {
+                const EdRow g = *row;
+                const Fr cx = fp_mul(P.half, fp_sub(g.ypx, g.ymx)), cy = fp_mul(P.half, fp_add(g.ypx, g.ymx));
+                const Fr cym1 = fp_sub(cy, one);
+                o[1] = t;
+                o[2] = fp_add(fp_mul(cym1, X), fp_mul(cx, Y));
+                o[3] = fp_add(fp_mul(cym1, Y), fp_mul(cx, X));
+            } else {
+                o[1] = zero;
+                o[2] = zero;
+                o[3] = zero;
+            }
+            o[4] = fx;
+            o[5] = fy;
+        }
+    }
+
+    // dbl: P_0 = Y, P_{i+1} = 2 P_i — sequential, one lane
+    if (tid == 0) {
+        EdExt p = sv_from_affine(yx, yy);
+#pragma unroll 1
+        for (unsigned i = 0; i < SV_LANES; i++) {
+            sh.px[i] = p.x;
+            sh.py[i] = p.y;
+            sh.pz[i] = p.z;
+            ed_dbl(p);
+        }
+    }
+    __syncthreads();  // also: ax / ay of the fixed base have been read
+    Fr bx, by;  // P_tid = 2^tid Y, affine
+    {
+        const Fr zi = sv_batch_inv(sh.pz[tid], sh);
+        bx = fp_mul(sh.px[tid], zi);
+        by = fp_mul(sh.py[tid], zi);
+        sh.ax[tid] = bx;
+        sh.ay[tid] = by;
+        __syncthreads();
+        if (tid + 1 < SV_LANES) {
+            Fr* o = w + P.dbl_at + SV_DBL_STEP * (size_t)tid;
+            o[0] = fp_mul(bx, by);
+            o[1] = fp_sqr(bx);
+            o[2] = fp_sqr(by);
+            o[3] = sh.ax[tid + 1];
+            o[4] = sh.ay[tid + 1];
+        }
+    }
+
+    // sel, add: Q_i = e_i P_i, acc_i = acc_{i-1} + Q_i
+    const Fr qx = ebit ? bx : zero, qy = ebit ? by : one;
+    w[P.sel_at + SV_SEL_STEP * (size_t)tid] = qx;
+    w[P.sel_at + SV_SEL_STEP * (size_t)tid + 1] = qy;
+    Fr cx, cy;  // acc_tid, affine
+    {
+        EdExt acc = sv_from_affine(qx, qy);
+        acc = sv_scan(acc, P.k2d, sh);  // (its barriers: ax / ay of the doubling chain have been read)
+        const Fr zi = sv_batch_inv(acc.z, sh);
+        cx = fp_mul(acc.x, zi);
+        cy = fp_mul(acc.y, zi);
+        sh.ax[tid] = cx;
+        sh.ay[tid] = cy;
+        __syncthreads();
+        if (tid) sv_add_witnesses(w + P.add_at + SV_ADD_STEP * (size_t)(tid - 1), sh.ax[tid - 1], sh.ay[tid - 1], qx, qy, cx, cy);
+    }
+
+    // sum: R' = s G + e Y on the last lane, which holds both
+    if (tid == SV_LANES - 1) {
+        const EdExt r = ed_add(sv_from_affine(fx, fy), sv_from_affine(cx, cy), P.k2d);
+        const Fr zi = fr_inv_single(r.z);
+        const Fr rx = fp_mul(r.x, zi), ry = fp_mul(r.y, zi);
+        sv_add_witnesses(w + P.sum_at, fx, fy, cx, cy, rx, ry);
+        const Fr sx = fp_to_std(rx), sy = fp_to_std(ry);
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            sh.piece[3][i] = sx.v[i];
+            sh.piece[4][i] = sy.v[i];
+        }
+    }
+    __syncthreads();
+
+    // dec
+#pragma unroll
+    for (unsigned c = 0; c < 4; c++) w[P.dec_at + 256 * c + tid] = (sh.piece[1 + c][tid >> 5] >> (tid & 31)) & 1u ? one : zero;
+
+    // b2s: the input is salt (if any) | Y.x | Y.y | R'.x | R'.y | message, zero-padded to whole blocks
+    if (tid == 0) sv_b2s_init(sh.h);
+    const unsigned skip = P.salted ? 0u : 1u;
+    for (unsigned blk = 0; blk < P.blocks; blk++) {
+        if (tid < 16) {
+            const unsigned word = 16 * blk + tid, q = (word >> 3) + skip;
+            uint32_t v = 0;
+            if (q < 5) {
+                v = sh.piece[q][word & 7];
+            } else {
+                const unsigned off = 4 * (word - 8 * (5 - skip));
+#pragma unroll
+                for (unsigned k = 0; k < 4; k++)
+                    if (off + k < P.msg_len) v |= (uint32_t)msg[off + k] << (8 * k);
+            }
+            sh.m[tid] = v;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const bool last = blk + 1 == P.blocks;
+            sv_b2s_compress_record(sh.h, sh.m, last ? (uint64_t)P.hash_len : (uint64_t)64 * (blk + 1), last, sh.rec);
+        }
+        __syncthreads();
+        Fr* bw = w + P.b2s_at + SV_BLOCK_WITNESSES * (size_t)blk;
+        // 64 bit positions per recorded word keep the index arithmetic to shifts; positions past a word's width are skipped
+        for (unsigned i = tid; i < 64 * (unsigned)SV_BLOCK_WORDS; i += SV_LANES) {
+            const unsigned k = i >> 6, bit = i & 63;
+            const SvSlot s = sv_b2s_slot(k);
+            if (bit < s.bits) bw[s.at + bit] = (sh.rec[k] >> bit) & 1u ? one : zero;
+        }
+        __syncthreads();  // rec[] and m[] are rewritten by the next block
+    }
+    if (ok && tid == 0) {
+        uint32_t diff = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) diff |= sh.h[i] ^ sh.ebits[i];
+        ok[item] = diff == 0;
+    }
+}
+
+static int schnorr_witness_run(swm_ctx* ctx, const swm_schnorr_circuit* c, const uint8_t* d_keys, const uint8_t* d_msgs, const uint8_t* d_sigs,
+                               size_t count, Fr* d_witness, uint8_t* d_ok, uint32_t* d_status) {
+    if (!count) return SWM_OK;
+    if (count > 0x7FFFFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_witness: %zu signatures in one call", count);
+    const SchnorrShape& s = c->shape;
+    SvParams P;
+    P.table = reinterpret_cast<const EdRow*>(c->params->d_table);
+    P.k2d = fp_from_u64<Fr>(2 * ED_D);
+    P.d = fp_from_u64<Fr>(ED_D);
+    P.half = fp_inv(fp_from_u64<Fr>(2));
+    for (int i = 0; i < 8; i++) P.salt[i] = c->params->salt[i];
+    P.salted = s.salted ? 1u : 0u;
+    P.msg_len = (uint32_t)s.msg_len;
+    P.blocks = (uint32_t)s.blocks;
+    P.hash_len = (uint32_t)s.hash_len;
+    P.sig_at = (uint32_t)s.sig_at;
+    P.fix_at = (uint32_t)s.fix_at;
+    P.dbl_at = (uint32_t)s.dbl_at;
+    P.sel_at = (uint32_t)s.sel_at;
+    P.add_at = (uint32_t)s.add_at;
+    P.sum_at = (uint32_t)s.sum_at;
+    P.dec_at = (uint32_t)s.dec_at;
+    P.b2s_at = (uint32_t)s.b2s_at;
+    P.num_witness = s.num_witness;
+    SWM_LAUNCH(ctx, "schnorr_witness", schnorr_witness_kernel, dim3((unsigned)count), dim3(SV_LANES), 0, P, d_keys, d_msgs, d_sigs, d_witness,
+               d_ok, d_status);
+    return SWM_OK;
+}
+
+// the host form's check: what the device form reports per item
+static int schnorr_check_keys(swm_ctx* ctx, const uint8_t* keys, size_t count) {
+    const Fr d = fp_from_u64<Fr>(ED_D);
+    for (size_t p = 0; p < count; p++) {
+        uint32_t kx[8], ky[8];
+        for (int i = 0; i < 8; i++) {
+            const uint8_t *a = keys + 64 * p + 4 * i, *b = a + 32;
+            kx[i] = (uint32_t)a[0] | (uint32_t)a[1] << 8 | (uint32_t)a[2] << 16 | (uint32_t)a[3] << 24;
+            ky[i] = (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24;
+        }
+        Fr x, y;
+        if (!sv_canonical(kx, &x) || !sv_canonical(ky, &y) || !sv_on_curve(x, y, d))
+            return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_witness: item %zu: the public key is not a point of ed-on-BLS12-377", p);
+    }
+    return SWM_OK;
+}
+
+// inputs of `count` signatures into one staging buffer: keys | signatures | messages (the first two stay word-aligned)
+static int schnorr_stage_inputs(swm_ctx* ctx, const swm_schnorr_circuit* c, const uint8_t* keys, const uint8_t* msgs, const uint8_t* sigs,
+                                size_t count, const uint8_t** d_keys, const uint8_t** d_msgs, const uint8_t** d_sigs) {
+    const size_t ml = c->shape.msg_len;
+    uint8_t* d_in = nullptr;
+    SWM_TRY(scratch(ctx, "stage.a", count * (128 + ml) + 16, (void**)&d_in));
+    SWM_HIP(ctx, hipMemcpyAsync(d_in, keys, 64 * count, hipMemcpyHostToDevice, ctx->stream));
+    SWM_HIP(ctx, hipMemcpyAsync(d_in + 64 * count, sigs, 64 * count, hipMemcpyHostToDevice, ctx->stream));
+    if (ml) SWM_HIP(ctx, hipMemcpyAsync(d_in + 128 * count, msgs, ml * count, hipMemcpyHostToDevice, ctx->stream));
+    *d_keys = d_in;
+    *d_sigs = d_in + 64 * count;
+    *d_msgs = d_in + 128 * count;
+    return SWM_OK;
+}
+
+// The host form holds at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
+static constexpr size_t SV_STAGE_BYTES = (size_t)1 << 30;
+
+}  // namespace swm
+
+using namespace swm;
+
+extern "C" {
+
+int swm_schnorr_circuit_create(swm_ctx* ctx, const swm_schnorr* params, size_t msg_len, swm_schnorr_circuit** out) {
+    if (!ctx || !params || !out) return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_circuit_create: bad arguments");
+    SchnorrShape shape;
+    if (!schnorr_shape(msg_len, params->has_salt, &shape))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_circuit_create: msg_len %zu (at most %zu)", msg_len, (size_t)SV_MAX_MSG_LEN);
+    std::unique_ptr<swm_schnorr_circuit> c(new swm_schnorr_circuit);
+    c->params = params;
+    c->shape = shape;
+    *out = c.release();
+    return SWM_OK;
+}
+
+void swm_schnorr_circuit_destroy(swm_ctx* ctx, swm_schnorr_circuit* c) {
+    if (!c) return;
+    DeviceGuard guard(ctx);
+    if (ctx) drain_streams(ctx);
+    delete c;
+}
+
+int swm_schnorr_witness_dev(swm_ctx* ctx, const swm_schnorr_circuit* c, const void* d_public_keys, const void* d_messages,
+                            const void* d_signatures, size_t count, void* d_witness, void* d_ok, void* d_status) {
+    if (!ctx || !c || (count && (!d_public_keys || !d_signatures || !d_witness || (c->shape.msg_len && !d_messages))))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_witness: bad arguments");
+    if (((uintptr_t)d_public_keys | (uintptr_t)d_signatures) & 3)
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_witness: keys and signatures must be 4-byte aligned");
+    SWM_ON_DEVICE(ctx);
+    return schnorr_witness_run(ctx, c, (const uint8_t*)d_public_keys, (const uint8_t*)d_messages, (const uint8_t*)d_signatures, count,
+                               (Fr*)d_witness, (uint8_t*)d_ok, (uint32_t*)d_status);
+}
+
+int swm_schnorr_witness(swm_ctx* ctx, const swm_schnorr_circuit* c, const uint8_t* public_keys_xy, const uint8_t* messages,
+                        const uint8_t* signatures, size_t count, uint64_t* witness, uint8_t* ok) {
+    if (!ctx || !c || (count && (!public_keys_xy || !signatures || !witness || (c->shape.msg_len && !messages))))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_witness: bad arguments");
+    if (!count) return SWM_OK;
+    SWM_TRY(schnorr_check_keys(ctx, public_keys_xy, count));
+    SWM_ON_DEVICE(ctx);
+    const size_t item = c->shape.num_witness * sizeof(Fr), ml = c->shape.msg_len;
+    const size_t per = SV_STAGE_BYTES / item ? SV_STAGE_BYTES / item : 1;  // signatures per chunk
+    for (size_t base = 0; base < count; base += per) {
+        const size_t n = count - base < per ? count - base : per;
+        const uint8_t *d_keys, *d_msgs, *d_sigs;
+        SWM_TRY(schnorr_stage_inputs(ctx, c, public_keys_xy + 64 * base, ml ? messages + ml * base : nullptr, signatures + 64 * base, n, &d_keys,
+                                     &d_msgs, &d_sigs));
+        uint8_t* d_out = nullptr;
+        SWM_TRY(scratch(ctx, "schnorr.w", n * item + n, (void**)&d_out));
+        SWM_TRY(schnorr_witness_run(ctx, c, d_keys, d_msgs, d_sigs, n, (Fr*)d_out, d_out + n * item, nullptr));
+        SWM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t*>(witness) + base * item, d_out, n * item, hipMemcpyDeviceToHost, ctx->stream));
+        if (ok) SWM_HIP(ctx, hipMemcpyAsync(ok + base, d_out + n * item, n, hipMemcpyDeviceToHost, ctx->stream));
+        SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffers are reused by the next chunk
+    }
+    return SWM_OK;
+}
+
+int swm_schnorr_prove(swm_ctx* ctx, const swm_pk* pk, const swm_schnorr_circuit* c, const uint8_t public_key_xy[64], const uint8_t* message,
+                      const uint8_t signature[64], swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
+    if (!ctx || !pk || !c || !public_key_xy || !signature || !rng || !proof_out || !len || (c->shape.msg_len && !message))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_prove: bad arguments");
+    SWM_TRY(schnorr_check_keys(ctx, public_key_xy, 1));
+    const SchnorrShape& s = c->shape;
+    Fr* d_w = nullptr;
+    {
+        SWM_ON_DEVICE(ctx);
+        const uint8_t *d_keys, *d_msgs, *d_sigs;
+        SWM_TRY(scratch(ctx, "schnorr.w", s.num_witness * sizeof(Fr) + 1, (void**)&d_w));
+        SWM_TRY(schnorr_stage_inputs(ctx, c, public_key_xy, message, signature, 1, &d_keys, &d_msgs, &d_sigs));
+        SWM_TRY(schnorr_witness_run(ctx, c, d_keys, d_msgs, d_sigs, 1, d_w, nullptr, nullptr));
+        SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    const Fr inst = fp_one<Fr>();  // no public input (transaction.rs verifies with an empty vector)
+    swm_r1cs cs = {};
+    cs.num_instance = s.num_instance;
+    cs.num_witness = s.num_witness;
+    cs.num_constraints = s.num_constraints;
+    cs.instance = reinterpret_cast<const uint64_t*>(&inst);
+    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
+    struct DevWitnessScope {
+        swm_ctx* c;
+        ~DevWitnessScope() { c->witness_dev = nullptr; }
+    } scope{ctx};
+    ctx->witness_dev = d_w;
+    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+}
+
+}  // extern "C"

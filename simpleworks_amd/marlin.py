@@ -450,6 +450,36 @@ def generate_merkle_proof(proving_key, circuit, root, leaf, leaf_index, siblings
     return bytes(buf[: n.value])
 
 
+def schnorr_circuit_shape(msg_len, salted=False):
+    """swm_schnorr_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the Schnorr verification circuit for
+    messages of msg_len bytes, with or without a salt — what workloads.build_schnorr_verification emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_schnorr_circuit_shape(msg_len, 1 if salted else 0, ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)),
+           "swm_schnorr_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_schnorr_proof(proving_key, circuit, public_key, message, signature, rng, uncompressed=False):
+    """swm_schnorr_prove: the proof of SimpleSchnorrSignatureVerification (examples/simple-payments/transaction.rs:108-126) with the
+    circuit's witness synthesised on the GPU (schnorr.SchnorrCircuit) and handed to the prover on the device.  public_key: 64 bytes
+    (x || y) or a pair of ints; message: msg_len bytes; signature: 64 bytes.  No public input: verify with [].
+    Returns the proof bytes (uncompressed=True: the form of generate_proof_uncompressed)."""
+    ctx = proving_key.ctx
+    if not isinstance(public_key, (bytes, bytearray)):
+        public_key = int(public_key[0]).to_bytes(32, "little") + int(public_key[1]).to_bytes(32, "little")
+    message, signature = bytes(message), bytes(signature)
+    if len(public_key) != 64 or len(signature) != 64 or len(message) != circuit.msg_len:
+        raise ValueError("generate_schnorr_proof: a 64-byte key, a 64-byte signature and a message of %d bytes" % circuit.msg_len)
+    key_b = (ctypes.c_uint8 * 64).from_buffer_copy(bytes(public_key))
+    sig_b = (ctypes.c_uint8 * 64).from_buffer_copy(signature)
+    msg_b = (ctypes.c_uint8 * max(1, len(message))).from_buffer_copy(message.ljust(1, b"\0"))
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    _check(ctx.lib.swm_schnorr_prove(ctx.h, proving_key.h, circuit.h, key_b, msg_b, sig_b, rng.h, 1 if uncompressed else 0,
+                                     buf, len(buf), ctypes.byref(n)), "swm_schnorr_prove", ctx)
+    return bytes(buf[: n.value])
+
+
 def verify_proof(verifying_key, public_inputs, proof, rng):
     """src/marlin/mod.rs:79-86.  public_inputs: field elements as ints (e.g. the bit-expanded inputs of
     src/merkle_tree/simple_merkle_tree.rs:129-143)."""

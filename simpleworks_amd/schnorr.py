@@ -81,6 +81,46 @@ class Signature:
         return Signature(int.from_bytes(b[:32], "little"), b[32:64])
 
 
+class SchnorrCircuit:
+    """The Schnorr verification circuit for messages of `msg_len` bytes under `params` (its generator and salt), resident on the
+    GPU (swm_schnorr_circuit): synthesises the witness vector of workloads.build_schnorr_verification for batches of
+    (public key, message, signature) without running the builder.  Refers to the Parameters: keep them alive."""
+
+    def __init__(self, params, msg_len):
+        self.ctx, self.params, self.msg_len = params.ctx, params, int(msg_len)
+        self.h = self.ctx.schnorr_circuit_create(params.h, self.msg_len)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        from .marlin import schnorr_circuit_shape
+        return schnorr_circuit_shape(self.msg_len, self.params.salt is not None)
+
+    def witness_many(self, public_keys, messages, signatures):
+        """public_keys uint8 [count, 64], messages uint8 [count, msg_len] (or byte strings of that length), signatures uint8
+        [count, 64].  One launch per staged chunk.  Returns (witness uint64 [count, num_witness, 4] Montgomery limbs, ok bool
+        [count]: the signature verifies in the circuit's sense, i.e. the witness satisfies it)."""
+        pk = np.ascontiguousarray(public_keys, dtype=np.uint8).reshape(-1, 64)
+        sig = np.ascontiguousarray(signatures, dtype=np.uint8).reshape(-1, 64)
+        if not isinstance(messages, np.ndarray):
+            if any(len(m) != self.msg_len for m in messages):
+                raise ValueError("a message of this circuit has %d bytes" % self.msg_len)
+            messages = np.frombuffer(b"".join(bytes(m) for m in messages), dtype=np.uint8)
+        m = np.ascontiguousarray(messages, dtype=np.uint8).reshape(pk.shape[0], self.msg_len)
+        witness, ok = self.ctx.schnorr_witness(self.h, self.shape()[1], pk, m, sig)
+        return witness, ok != 0
+
+    def free(self):
+        if self.h:
+            self.ctx.schnorr_circuit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def _scalars(values):
     return np.frombuffer(b"".join(v.to_bytes(32, "little") for v in values), dtype=np.uint8).reshape(len(values), 32)
 

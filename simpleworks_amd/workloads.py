@@ -701,3 +701,283 @@ class SimpleMerkleTree:
         if self._circuit is not None:
             self._circuit.free()
         self.proving_key.free()
+
+
+# ===================================================================================================================
+# The reference's second real circuit: SimpleSchnorrSignatureVerification (examples/simple-payments/transaction.rs:33-71,
+# :89-139) — SchnorrSignatureVerifyGadget::verify over a witness key, a witness message and a witness signature, no public
+# input.  As with the membership circuit the gadgets of ark-r1cs-std are not available here, so the row layout is OURS:
+# same statement (R' = s G + e Y, Blake2s([salt] || Y || R' || message) == e), same byte conventions (to_bytes! of a point
+# is x || y, 32 little-endian bytes each), our own rows.  build_schnorr_verification is the layout contract of
+# csrc/host/schnorr_shape.h and csrc/schnorr_witness.hip.
+#
+# Variable order (everything is a witness; schnorr_circuit_layout gives the offsets):
+#   key      x, y, xx, yy and the on-curve row (d xx) yy = yy - xx - 1                                 4 witnesses,    3 rows
+#   msg      8 booleans per byte, least significant first                                        8 msg_len,        8 msg_len
+#   sig      256 booleans of prover_response s, 256 of verifier_challenge e                          512,          512
+#   fix      s G: 255 conditional additions of the constants 2^i G (_cond_add_const), i = 1 .. 255   255 x 6,      255 x 6
+#   dbl      P_0 = Y, P_{i+1} = 2 P_i: xy, xx, yy, x', y' per doubling, i = 0 .. 254                 255 x 5,      255 x 5
+#   sel      Q_i = e_i P_i: qx = e_i x, qy = 1 + e_i (y - 1), i = 0 .. 255                           256 x 2,      256 x 2
+#   add      acc_0 = Q_0, acc_i = acc_{i-1} + Q_i: x1y2, y1x2, y1y2, x1x2, their product, x3, y3      255 x 7,      255 x 7
+#   sum      R' = s G + e Y, one more addition                                                       7,            7
+#   dec      Y.x, Y.y, R'.x, R'.y as 256 booleans each, a packing row and `0 * 0 = bit` for bits 253..255   1024,   1040
+#   b2s      per 64-byte block 80 G functions of 262 witnesses / 266 rows, then 16 xors of the feed-forward   21472,  21792
+#   cmp      digest word i == challenge word i, eight packed rows                                    0,            8
+# Neither s nor e is range-checked and the circuit multiplies by the 256-bit INTEGERS, as the reference's gadget does
+# (scalar_mul_le over to_bits_le of the bytes).  For a key in the prime subgroup that equals the native check (l Y = 0);
+# for an on-curve key outside it e Y and (e mod l) Y differ, so circuit and native verify may disagree there.  There is no
+# subgroup check: the addition law is complete (a = -1 a square, d a non-square), every denominator is non-zero.
+# Blake2s has a UNIFORM shape: the IV, the parameter word, the counter, the finalisation flag, the salt and the zero
+# padding enter as multiples of `one`, and every xor and every sum costs its rows and witnesses whether or not an
+# operand is constant — the shape is a function of the block count alone.
+# ===================================================================================================================
+SCHNORR_MAX_MSG_LEN = 65536
+_B2S_IV = (0x6A09E667, 0xBB67AE85, 0x3C6EF372, 0xA54FF53A, 0x510E527F, 0x9B05688C, 0x1F83D9AB, 0x5BE0CD19)
+_B2S_SIGMA = ((0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15), (14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3),
+              (11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4), (7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8),
+              (9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13), (2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9),
+              (12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11), (13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10),
+              (6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5), (10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0))
+_B2S_G_LANES = ((0, 4, 8, 12), (1, 5, 9, 13), (2, 6, 10, 14), (3, 7, 11, 15), (0, 5, 10, 15), (1, 6, 11, 12), (2, 7, 8, 13), (3, 4, 9, 14))
+SV_G_WITNESSES = 34 + 32 + 33 + 32 + 34 + 32 + 33 + 32      # 262
+SV_BLOCK_WITNESSES = 80 * SV_G_WITNESSES + 16 * 32            # 21472
+SV_BLOCK_ROWS = 80 * (SV_G_WITNESSES + 4) + 16 * 32           # 21792
+
+
+def schnorr_circuit_layout(msg_len, salted):
+    """Offsets of the witness groups of build_schnorr_verification and its three counts, as csrc/host/schnorr_shape.h states them."""
+    if not 0 <= msg_len <= SCHNORR_MAX_MSG_LEN:
+        raise ValueError("msg_len %d (0 .. %d)" % (msg_len, SCHNORR_MAX_MSG_LEN))
+    lay = {"key": 0, "msg": 4}
+    lay["sig"] = lay["msg"] + 8 * msg_len
+    lay["fix"] = lay["sig"] + 512
+    lay["dbl"] = lay["fix"] + 255 * 6
+    lay["sel"] = lay["dbl"] + 255 * 5
+    lay["add"] = lay["sel"] + 256 * 2
+    lay["sum"] = lay["add"] + 255 * 7
+    lay["dec"] = lay["sum"] + 7
+    lay["b2s"] = lay["dec"] + 4 * 256
+    lay["hash_len"] = (160 if salted else 128) + msg_len
+    lay["blocks"] = (lay["hash_len"] + 63) // 64
+    lay["num_instance"] = 1
+    lay["num_witness"] = lay["b2s"] + SV_BLOCK_WITNESSES * lay["blocks"]
+    lay["num_constraints"] = (3 + 8 * msg_len + 512 + 255 * 6 + 255 * 5 + 256 * 2 + 255 * 7 + 7 + 4 * 260
+                              + SV_BLOCK_ROWS * lay["blocks"] + 8)
+    # digest word i: the second xor of the last block's feed-forward
+    lay["digest"] = lay["b2s"] + SV_BLOCK_WITNESSES * (lay["blocks"] - 1) + 80 * SV_G_WITNESSES + 32
+    return lay
+
+
+_SV_GENERATOR_POWERS = {}
+
+
+def _sv_generator_powers(generator):
+    """2^i G, i = 0 .. 255: circuit constants."""
+    if generator not in _SV_GENERATOR_POWERS:
+        row = [generator]
+        for _ in range(255):
+            row.append(ed_add(row[-1], row[-1]))
+        _SV_GENERATOR_POWERS[generator] = row
+    return _SV_GENERATOR_POWERS[generator]
+
+
+def _sv_witness(cs, v):
+    v %= R_MODULUS
+    return _LC([(1, cs.new_witness_variable(v))], v)
+
+
+def _sv_product(cs, a, b):
+    w = _sv_witness(cs, a.value * b.value)
+    cs.enforce_constraint(a.terms, b.terms, w.terms)
+    return w
+
+
+def _sv_const(one, v):
+    v %= R_MODULUS
+    return _LC([(v, one)], v) if v else _LC([], 0)
+
+
+def _sv_quotient(cs, num, den):
+    """q with the row q den = num; den is never zero (complete law)."""
+    q = _sv_witness(cs, num.value * pow(den.value, -1, R_MODULUS))
+    cs.enforce_constraint(q.terms, den.terms, num.terms)
+    return q
+
+
+def _sv_double(cs, one, p):
+    """2 (x, y) for a = -1 on the curve: x' (yy - xx) = 2 xy, y' (2 - yy + xx) = yy + xx (yy - xx = 1 + d xx yy there).
+    Five rows, five witnesses: xy, xx, yy, x', y'."""
+    x, y = p
+    xy, xx, yy = _sv_product(cs, x, y), _sv_product(cs, x, x), _sv_product(cs, y, y)
+    x3 = _sv_quotient(cs, xy.scaled(2), yy.minus(xx))
+    y3 = _sv_quotient(cs, yy.plus(xx), _sv_const(one, 2).minus(yy).plus(xx))
+    return x3, y3
+
+
+def _sv_add(cs, one, p, q):
+    """Unified affine addition: x1y2, y1x2, y1y2, x1x2, t = (x1y2)(y1x2), x3 (1 + d t) = x1y2 + y1x2, y3 (1 - d t) = y1y2 + x1x2.
+    Seven rows, seven witnesses."""
+    (x1, y1), (x2, y2) = p, q
+    a, b, c, e = _sv_product(cs, x1, y2), _sv_product(cs, y1, x2), _sv_product(cs, y1, y2), _sv_product(cs, x1, x2)
+    dt = _sv_product(cs, a, b).scaled(ED_D)
+    x3 = _sv_quotient(cs, a.plus(b), _sv_const(one, 1).plus(dt))
+    y3 = _sv_quotient(cs, c.plus(e), _sv_const(one, 1).minus(dt))
+    return x3, y3
+
+
+def _sv_pack(bits):
+    """sum 2^i bits[i] with the terms of one variable merged."""
+    acc, value = {}, 0
+    for i, b in enumerate(bits):
+        value += b.value << i
+        for c, v in b.terms:
+            acc[v] = (acc.get(v, 0) + (c << i)) % R_MODULUS
+    return _LC([(c, v) for v, c in acc.items() if c], value)
+
+
+def _sv_decompose(cs, one, coord):
+    """to_bytes of a coordinate, as build_merkle_membership decomposes a digest."""
+    bits = [_boolean_witness(cs, one, (coord.value >> i) & 1) for i in range(256)]
+    cs.enforce_constraint(_sv_pack(bits).minus(coord).terms, [(1, one)], [])
+    for i in range(253, 256):
+        cs.enforce_constraint([], [], bits[i].terms)
+    return bits
+
+
+def _sv_xor(cs, a, b):
+    """Word xor: one row (2a) b = a + b - c and one witness per bit, constant operands included."""
+    out = []
+    for x, y in zip(a, b):
+        c = _sv_witness(cs, x.value ^ y.value)
+        cs.enforce_constraint(x.scaled(2).terms, y.terms, x.plus(y).minus(c).terms)
+        out.append(c)
+    return out
+
+
+def _sv_sum(cs, one, words):
+    """Sum of two or three words mod 2^32: 33 or 34 boolean result bits and one packing row; returns the low 32."""
+    total = sum(b.value << i for w in words for i, b in enumerate(w))
+    bits = [_boolean_witness(cs, one, (total >> i) & 1) for i in range(31 + len(words))]
+    operands = _LC([], 0)
+    for w in words:
+        operands = operands.plus(_sv_pack(w))
+    cs.enforce_constraint(_sv_pack(bits).minus(_sv_pack([operands])).terms, [(1, one)], [])
+    return bits[:32]
+
+
+def _sv_rotr(w, n):
+    return w[n:] + w[:n]
+
+
+def _sv_const_word(one, v):
+    return [_sv_const(one, (v >> i) & 1) for i in range(32)]
+
+
+def _sv_blake2s(cs, one, stream, total):
+    """Blake2s-256, unkeyed, over the bit stream (a list of boolean _LC, least significant bit of each byte first) of
+    `total` bytes -> the eight digest words."""
+    h = [_sv_const_word(one, iv ^ (0x01010020 if i == 0 else 0)) for i, iv in enumerate(_B2S_IV)]
+    blocks = max(1, (total + 63) // 64)
+    zero = _sv_const(one, 0)
+    stream = stream + [zero] * (512 * blocks - len(stream))
+    for blk in range(blocks):
+        m = [stream[512 * blk + 32 * k:512 * blk + 32 * k + 32] for k in range(16)]
+        last = blk + 1 == blocks
+        t = total if last else 64 * (blk + 1)
+        v = list(h) + [_sv_const_word(one, iv) for iv in _B2S_IV]
+        v[12] = _sv_const_word(one, _B2S_IV[4] ^ (t & 0xFFFFFFFF))
+        v[13] = _sv_const_word(one, _B2S_IV[5] ^ (t >> 32))
+        if last:
+            v[14] = _sv_const_word(one, _B2S_IV[6] ^ 0xFFFFFFFF)
+        for r in range(10):
+            s = _B2S_SIGMA[r]
+            for g, (a, b, c, d) in enumerate(_B2S_G_LANES):
+                v[a] = _sv_sum(cs, one, [v[a], v[b], m[s[2 * g]]])
+                v[d] = _sv_rotr(_sv_xor(cs, v[d], v[a]), 16)
+                v[c] = _sv_sum(cs, one, [v[c], v[d]])
+                v[b] = _sv_rotr(_sv_xor(cs, v[b], v[c]), 12)
+                v[a] = _sv_sum(cs, one, [v[a], v[b], m[s[2 * g + 1]]])
+                v[d] = _sv_rotr(_sv_xor(cs, v[d], v[a]), 8)
+                v[c] = _sv_sum(cs, one, [v[c], v[d]])
+                v[b] = _sv_rotr(_sv_xor(cs, v[b], v[c]), 7)
+        h = [_sv_xor(cs, _sv_xor(cs, h[i], v[i]), v[i + 8]) for i in range(8)]
+    return h
+
+
+def build_schnorr_verification(cs, generator, salt, public_key, message, signature):
+    """Emits the Schnorr verification circuit into `cs` (builder vocabulary as build_merkle_membership).  generator, public_key:
+    affine points as ints (the key must be on the curve; no subgroup check); salt: 32 bytes or None; message: bytes; signature:
+    64 bytes, prover_response || verifier_challenge.  No public input: returns [].
+    Every witness but the comparison is computed honestly whatever the signature says, so a signature that does not verify
+    violates comparison rows only (the last eight rows).  s and e enter as 256-bit integers, unreduced: for a key outside the
+    prime subgroup e Y differs from the native scheme's (e mod l) Y (see the block comment above)."""
+    message, signature = bytes(message), bytes(signature)
+    if len(signature) != 64 or (salt is not None and len(salt) != 32) or len(message) > SCHNORR_MAX_MSG_LEN:
+        raise ValueError("schnorr verification circuit: a 64-byte signature, a 32-byte salt or None, at most %d message bytes"
+                         % SCHNORR_MAX_MSG_LEN)
+    if not ed_on_curve(public_key) or not ed_on_curve(generator):
+        raise ValueError("schnorr verification circuit: the key and the generator must be points of ed-on-BLS12-377")
+    one = cs.one()
+    # key
+    y_x, y_y = _sv_witness(cs, public_key[0]), _sv_witness(cs, public_key[1])
+    xx, yy = _sv_product(cs, y_x, y_x), _sv_product(cs, y_y, y_y)
+    cs.enforce_constraint(xx.scaled(ED_D).terms, yy.terms, yy.minus(xx).minus(_sv_const(one, 1)).terms)
+    # msg, sig
+    msg_bits = [_boolean_witness(cs, one, (byte >> i) & 1) for byte in message for i in range(8)]
+    sig_bits = [_boolean_witness(cs, one, (byte >> i) & 1) for byte in signature for i in range(8)]
+    s_bits, e_bits = sig_bits[:256], sig_bits[256:]
+    # fix
+    acc = None
+    for b, g in zip(s_bits, _sv_generator_powers(tuple(generator))):
+        acc = _cond_add_const(cs, one, acc, g, b)
+    s_g = acc
+    # dbl
+    powers = [(y_x, y_y)]
+    for _ in range(255):
+        powers.append(_sv_double(cs, one, powers[-1]))
+    # sel
+    picks = []
+    for b, (px, py) in zip(e_bits, powers):
+        qx = _sv_product(cs, b, px)
+        qy = _sv_witness(cs, 1 + b.value * (py.value - 1))
+        cs.enforce_constraint(b.terms, py.minus(_sv_const(one, 1)).terms, qy.minus(_sv_const(one, 1)).terms)
+        picks.append((qx, qy))
+    # add
+    acc = picks[0]
+    for q in picks[1:]:
+        acc = _sv_add(cs, one, acc, q)
+    # sum
+    r_x, r_y = _sv_add(cs, one, s_g, acc)
+    # dec
+    coords = [_sv_decompose(cs, one, c) for c in (y_x, y_y, r_x, r_y)]
+    # b2s
+    stream = []
+    if salt is not None:
+        stream += [_sv_const(one, (byte >> i) & 1) for byte in bytes(salt) for i in range(8)]
+    for c in coords:
+        stream += c
+    stream += msg_bits
+    digest = _sv_blake2s(cs, one, stream, len(stream) // 8)
+    # cmp
+    for i, word in enumerate(digest):
+        cs.enforce_constraint(_sv_pack(word).minus(_sv_pack(e_bits[32 * i:32 * i + 32])).terms, [(1, one)], [])
+    return []
+
+
+def schnorr_verification_circuit(generator=ED_GENERATOR, salt=None, public_key=None, message=b"", signature=bytes(64)):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs) with public_inputs = []."""
+    cs = ConstraintSystem()
+    public = build_schnorr_verification(cs, generator, salt, public_key if public_key is not None else generator, message, signature)
+    return cs, public
+
+
+class SimpleSchnorrSignatureVerification:
+    """The ConstraintSynthesizer of examples/simple-payments/transaction.rs:33-71 for MarlinInst.index / prove (:108-126):
+    constants = scheme parameters, witnesses = key, message, signature."""
+
+    def __init__(self, generator, salt, public_key, message, signature):
+        self.generator, self.salt, self.public_key = generator, salt, public_key
+        self.message, self.signature = bytes(message), bytes(signature)
+
+    def generate_constraints(self, cs):
+        build_schnorr_verification(cs, self.generator, self.salt, self.public_key, self.message, self.signature)

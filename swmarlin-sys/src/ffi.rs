@@ -12,6 +12,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_pedersen { _p: [u8; 0] }
 #[repr(C)] pub struct swm_schnorr { _p: [u8; 0] }
 #[repr(C)] pub struct swm_merkle_circuit { _p: [u8; 0] }
+#[repr(C)] pub struct swm_schnorr_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_poseidon { _p: [u8; 0] }
 
 pub const SWM_OK: c_int = 0;
@@ -157,6 +158,22 @@ extern "C" {
                               msg_len: usize, signatures: *const u8, count: usize, ok: *mut u8) -> c_int;
     pub fn swm_schnorr_commitments(ctx: *mut swm_ctx, params: *const swm_schnorr, public_keys_xy: *const u8, signatures: *const u8,
                                    count: usize, commitments_xy: *mut u8) -> c_int;
+
+    // the Schnorr verification circuit's witness on the GPU: the proof of examples/simple-payments/transaction.rs:108-126 without
+    // running the constraint synthesizer on the host (no public input; witness: Montgomery limbs; ok: one byte per signature)
+    pub fn swm_schnorr_circuit_shape(msg_len: usize, salted: c_int, num_instance: *mut usize, num_witness: *mut usize,
+                                     num_constraints: *mut usize) -> c_int;
+    pub fn swm_schnorr_circuit_create(ctx: *mut swm_ctx, params: *const swm_schnorr, msg_len: usize,
+                                      out: *mut *mut swm_schnorr_circuit) -> c_int;
+    pub fn swm_schnorr_circuit_destroy(ctx: *mut swm_ctx, circuit: *mut swm_schnorr_circuit);
+    pub fn swm_schnorr_witness(ctx: *mut swm_ctx, circuit: *const swm_schnorr_circuit, public_keys_xy: *const u8, messages: *const u8,
+                               signatures: *const u8, count: usize, witness: *mut u64, ok: *mut u8) -> c_int;
+    pub fn swm_schnorr_witness_dev(ctx: *mut swm_ctx, circuit: *const swm_schnorr_circuit, d_public_keys: *const c_void,
+                                   d_messages: *const c_void, d_signatures: *const c_void, count: usize, d_witness: *mut c_void,
+                                   d_ok: *mut c_void, d_status: *mut c_void) -> c_int;
+    pub fn swm_schnorr_prove(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_schnorr_circuit, public_key_xy: *const u8,
+                             message: *const u8, signature: *const u8, rng: *mut swm_rng, flags: c_uint, proof_out: *mut u8,
+                             cap: usize, len: *mut usize) -> c_int;
 
     // the native Poseidon hash of src/hash/mod.rs:30-43 (PoseidonSponge<Fq>, rate 2), batched; a field element: 32 canonical LE bytes;
     // the parameters are the caller's (mds: 9 elements row-major, ark: (full + partial) x 3)
