@@ -380,6 +380,66 @@ int swm_merkle_prove(swm_ctx *ctx, const swm_pk *pk, const swm_merkle_circuit *c
                      uint64_t index, const uint8_t *siblings, swm_rng *rng, unsigned flags, uint8_t *proof_out, size_t cap,
                      size_t *len);
 
+/* ---------------------------------------------------------------------------------------------- resident Merkle tree
+ * The account tree of examples/simple-payments kept on the GPU between calls: what the ledger's state machine does to its
+ * MerkleTree<MerkleConfig>, without rebuilding the tree from every leaf for one changed balance.  Replaces, on the GPU,
+ *   examples/simple-payments/ledger.rs:106-112      MerkleTree::blank(&leaf_crh_params, &two_to_one_crh_params, height)
+ *   examples/simple-payments/ledger.rs:140-142      tree.update(id, &account_info.to_bytes_le())   (register)
+ *   examples/simple-payments/ledger.rs:166-173      the same, once per changed balance (twice per applied transaction: :187-188)
+ *   examples/simple-payments/ledger.rs:124-126      tree.root()
+ *   examples/simple-payments/transaction.rs:163-166 tree.generate_proof(sender)
+ *   examples/simple-payments/transaction.rs:167-173 path.verify(&leaf_crh_params, &two_to_one_crh_params, &root, &leaf)
+ * `height` is arkworks' height and counts the leaf level [U]: n = 2^(height - 1) leaves, L = height - 1 two-to-one levels,
+ * 2 <= height <= 31.  The node layout is swm_merkle_tree_build's: n leaf digests | n / 2 | ... | root, (2 n - 1) x 32 bytes, one
+ * device buffer owned by the handle.  The handle refers to the two swm_pedersen: keep them.  Limits (SWM_ERR_INVALID_ARG): the
+ * height; leaf_len = 0 or leaf_len x 8 beyond the leaf set's capacity; a two-to-one set of fewer than 512 bits.  An allocation
+ * failure is SWM_ERR_OOM.
+ * swm_merkle_tree_create_blank: MerkleTree::blank [U] — every leaf digest is LeafDigest::default(), 32 zero bytes and the hash of
+ * nothing; every node of level l + 1 is the two-to-one hash of two equal nodes of level l.  L dependent hashes and a fill.
+ * swm_merkle_tree_create_from_leaves: MerkleTree::new over n_leaves (a power of two, 2 .. 2^30) leaves of leaf_len bytes.
+ * swm_merkle_tree_update: `count` (index, leaf) pairs, leaf i of the batch at leaves + i x leaf_len, with the meaning of
+ * tree.update(index, leaf) [U] applied in batch order: a repeated index keeps its LAST leaf, and every ancestor of a touched leaf
+ * is recomputed once.  The indices are on the host in both forms; the leaves on the host, or (_dev) on the device.  Everything is
+ * checked before the first launch: an index >= n or a leaf_len other than the tree's is SWM_ERR_INVALID_ARG and the tree is as it
+ * was.  Levels with more than 4 dirty nodes run one launch each; from the first level with at most 4, one workgroup finishes the
+ * tree in a single launch, so one or two updates cost two launches whatever the height.  Launches are ordered by the context's
+ * stream alone.  _dev returns without waiting when at most 4 leaves are touched.
+ * swm_merkle_tree_root: the root, 32 canonical little-endian bytes.  swm_merkle_tree_nodes: all (2 n - 1) x 32 bytes.
+ * swm_merkle_tree_dev_nodes: the device buffer itself and its node count (needs no context; valid until destroy).
+ * swm_merkle_tree_paths: siblings of `count` leaves, count x L x 32 bytes, bottom up (level[l][(i >> l) ^ 1]) — the form
+ * swm_merkle_witness takes.  An index >= n is SWM_ERR_INVALID_ARG.  _dev: indices (uint64) and output on the device, so a path goes
+ * straight into swm_merkle_witness_dev; an index >= n cannot be refused there and its path reads as zeros.
+ * swm_merkle_verify_paths: Path::verify [U] for `count` paths in one launch, without a tree: hash the leaf, then L times the
+ * two-to-one hash of (current || sibling) or (sibling || current) by bit l of the index, and compare with the root.  roots: one
+ * root for all paths (root_stride = 0) or one per path (root_stride = 32); leaves: count x leaf_len bytes; indices: count uint64;
+ * siblings: count x L x 32 bytes bottom up.  ok: count bytes, 1 where the path leads to its root.  status (count words, may be
+ * NULL) as swm_merkle_witness_dev reports it: 0 computed, 1 a sibling or root >= r, 2 an index >= 2^L; ok = 0 for 1 and 2, the
+ * other paths of the batch are unaffected and the call returns SWM_OK.  _dev: every pointer on the device (roots, siblings and
+ * status 4-byte aligned).  count = 0 returns SWM_OK everywhere and launches nothing. */
+typedef struct swm_merkle_tree swm_merkle_tree;
+int swm_merkle_tree_create_blank(swm_ctx *ctx, const swm_pedersen *leaf_params, const swm_pedersen *two_to_one_params, size_t height,
+                                 size_t leaf_len, swm_merkle_tree **out);
+int swm_merkle_tree_create_from_leaves(swm_ctx *ctx, const swm_pedersen *leaf_params, const swm_pedersen *two_to_one_params,
+                                       const uint8_t *leaves, size_t leaf_len, size_t n_leaves, swm_merkle_tree **out);
+int swm_merkle_tree_create_from_leaves_dev(swm_ctx *ctx, const swm_pedersen *leaf_params, const swm_pedersen *two_to_one_params,
+                                           const void *d_leaves, size_t leaf_len, size_t n_leaves, swm_merkle_tree **out);
+void swm_merkle_tree_destroy(swm_ctx *ctx, swm_merkle_tree *tree);
+int swm_merkle_tree_update(swm_ctx *ctx, swm_merkle_tree *tree, const uint64_t *indices, const uint8_t *leaves, size_t leaf_len,
+                           size_t count);
+int swm_merkle_tree_update_dev(swm_ctx *ctx, swm_merkle_tree *tree, const uint64_t *indices, const void *d_leaves, size_t leaf_len,
+                               size_t count);
+int swm_merkle_tree_root(swm_ctx *ctx, const swm_merkle_tree *tree, uint8_t root[32]);
+int swm_merkle_tree_paths(swm_ctx *ctx, const swm_merkle_tree *tree, const uint64_t *indices, size_t count, uint8_t *siblings);
+int swm_merkle_tree_paths_dev(swm_ctx *ctx, const swm_merkle_tree *tree, const void *d_indices, size_t count, void *d_siblings);
+int swm_merkle_tree_nodes(swm_ctx *ctx, const swm_merkle_tree *tree, uint8_t *nodes);
+int swm_merkle_tree_dev_nodes(const swm_merkle_tree *tree, void **d_nodes, size_t *n_nodes);
+int swm_merkle_verify_paths(swm_ctx *ctx, const swm_pedersen *leaf_params, const swm_pedersen *two_to_one_params, size_t height,
+                            const uint8_t *roots, size_t root_stride, const uint8_t *leaves, size_t leaf_len, const uint64_t *indices,
+                            const uint8_t *siblings, size_t count, uint8_t *ok, uint32_t *status);
+int swm_merkle_verify_paths_dev(swm_ctx *ctx, const swm_pedersen *leaf_params, const swm_pedersen *two_to_one_params, size_t height,
+                                const void *d_roots, size_t root_stride, const void *d_leaves, size_t leaf_len, const void *d_indices,
+                                const void *d_siblings, size_t count, void *d_ok, void *d_status);
+
 /* ---------------------------------------------------------------------------------------------- Schnorr signatures
  * The reference's native signature scheme, SimpleSchnorr = Schnorr<EdwardsProjective> on ed-on-BLS12-377, batched: one GPU lane per
  * key, signature or check.  Replaces, on the GPU,

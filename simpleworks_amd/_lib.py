@@ -104,6 +104,20 @@ ABI = {
     "swm_merkle_witness_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "swm_merkle_prove": (_int, [_vp, _vp, _vp, ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_void_p, _vp, ctypes.c_uint,
                                 ctypes.c_void_p, _sz, ctypes.POINTER(_sz)]),
+    "swm_merkle_tree_create_blank": (_int, [_vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_vp)]),
+    "swm_merkle_tree_create_from_leaves": (_int, [_vp, _vp, _vp, ctypes.c_void_p, _sz, _sz, ctypes.POINTER(_vp)]),
+    "swm_merkle_tree_create_from_leaves_dev": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, ctypes.POINTER(_vp)]),
+    "swm_merkle_tree_destroy": (None, [_vp, _vp]),
+    "swm_merkle_tree_update": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, _sz]),
+    "swm_merkle_tree_update_dev": (_int, [_vp, _vp, ctypes.c_void_p, _vp, _sz, _sz]),
+    "swm_merkle_tree_root": (_int, [_vp, _vp, ctypes.c_void_p]),
+    "swm_merkle_tree_paths": (_int, [_vp, _vp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_merkle_tree_paths_dev": (_int, [_vp, _vp, _vp, _sz, _vp]),
+    "swm_merkle_tree_nodes": (_int, [_vp, _vp, ctypes.c_void_p]),
+    "swm_merkle_tree_dev_nodes": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
+    "swm_merkle_verify_paths": (_int, [_vp, _vp, _vp, _sz, ctypes.c_void_p, _sz, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.c_void_p, _sz,
+                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_merkle_verify_paths_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
     "swm_schnorr_create": (_int, [_vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_vp)]),
     "swm_schnorr_destroy": (None, [_vp, _vp]),
     "swm_schnorr_keygen": (_int, [_vp, _vp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
@@ -493,6 +507,95 @@ class Context:
         self._check(self.lib.swm_merkle_witness_dev(self.h, handle, d_leaves.ptr, d_indices.ptr, d_siblings.ptr, count, d_witness.ptr,
                                                     d_roots.ptr if d_roots else None, d_status.ptr if d_status else None),
                     "swm_merkle_witness_dev")
+
+    # ---- resident Merkle tree (include/swmarlin.h; simpleworks_amd/hash.py, DeviceMerkleTree, is the caller-facing mirror)
+    def merkle_tree_create_blank(self, leaf_handle, two_to_one_handle, height, leaf_len):
+        h = _vp()
+        self._check(self.lib.swm_merkle_tree_create_blank(self.h, leaf_handle, two_to_one_handle, height, leaf_len, ctypes.byref(h)),
+                    "swm_merkle_tree_create_blank")
+        return h
+
+    def merkle_tree_create_from_leaves(self, leaf_handle, two_to_one_handle, leaves):
+        """leaves: uint8 [n, leaf_len]."""
+        a = np.ascontiguousarray(leaves, dtype=np.uint8)
+        assert a.ndim == 2
+        h = _vp()
+        self._check(self.lib.swm_merkle_tree_create_from_leaves(self.h, leaf_handle, two_to_one_handle, a.ctypes.data, a.shape[1], a.shape[0],
+                                                                ctypes.byref(h)), "swm_merkle_tree_create_from_leaves")
+        return h
+
+    def merkle_tree_create_from_leaves_dev(self, leaf_handle, two_to_one_handle, d_leaves, leaf_len, n_leaves):
+        h = _vp()
+        self._check(self.lib.swm_merkle_tree_create_from_leaves_dev(self.h, leaf_handle, two_to_one_handle, d_leaves.ptr, leaf_len, n_leaves,
+                                                                    ctypes.byref(h)), "swm_merkle_tree_create_from_leaves_dev")
+        return h
+
+    def merkle_tree_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_merkle_tree_destroy(self.h, handle)
+
+    def merkle_tree_update(self, handle, indices, leaves):
+        """indices: leaf indices; leaves: uint8 [count, leaf_len], applied in order (a repeated index keeps its last leaf)."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        a = np.ascontiguousarray(leaves, dtype=np.uint8)
+        assert idx.ndim == 1 and a.ndim == 2 and a.shape[0] == idx.shape[0]
+        self._check(self.lib.swm_merkle_tree_update(self.h, handle, idx.ctypes.data, a.ctypes.data, a.shape[1], idx.shape[0]),
+                    "swm_merkle_tree_update")
+
+    def merkle_tree_update_dev(self, handle, indices, d_leaves, leaf_len):
+        """indices on the host, the leaf bytes (len(indices) x leaf_len) on the device."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        self._check(self.lib.swm_merkle_tree_update_dev(self.h, handle, idx.ctypes.data, d_leaves.ptr, leaf_len, idx.shape[0]),
+                    "swm_merkle_tree_update_dev")
+
+    def merkle_tree_root(self, handle):
+        out = np.empty(32, dtype=np.uint8)
+        self._check(self.lib.swm_merkle_tree_root(self.h, handle, out.ctypes.data), "swm_merkle_tree_root")
+        return out
+
+    def merkle_tree_dev_nodes(self, handle):
+        """(device pointer of the node buffer, node count)."""
+        p, n = _vp(), _sz(0)
+        self._check(self.lib.swm_merkle_tree_dev_nodes(handle, ctypes.byref(p), ctypes.byref(n)), "swm_merkle_tree_dev_nodes")
+        return p.value, n.value
+
+    def merkle_tree_nodes(self, handle):
+        """uint8 [2 n - 1, 32]: n leaf digests | n / 2 | ... | root."""
+        out = np.empty((self.merkle_tree_dev_nodes(handle)[1], 32), dtype=np.uint8)
+        self._check(self.lib.swm_merkle_tree_nodes(self.h, handle, out.ctypes.data), "swm_merkle_tree_nodes")
+        return out
+
+    def merkle_tree_paths(self, handle, levels, indices):
+        """-> uint8 [count, levels, 32]: the siblings of each leaf, bottom up."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        out = np.empty((idx.shape[0], levels, 32), dtype=np.uint8)
+        self._check(self.lib.swm_merkle_tree_paths(self.h, handle, idx.ctypes.data, idx.shape[0], out.ctypes.data), "swm_merkle_tree_paths")
+        return out
+
+    def merkle_tree_paths_dev(self, handle, d_indices, count, d_siblings):
+        self._check(self.lib.swm_merkle_tree_paths_dev(self.h, handle, d_indices.ptr, count, d_siblings.ptr), "swm_merkle_tree_paths_dev")
+
+    def merkle_verify_paths(self, leaf_handle, two_to_one_handle, height, roots, leaves, indices, siblings):
+        """roots uint8 [32] (one for all paths) or [count, 32]; leaves uint8 [count, leaf_len]; indices uint64 [count]; siblings uint8
+        [count, height - 1, 32] -> (ok uint8 [count], status uint32 [count])."""
+        roots = np.ascontiguousarray(roots, dtype=np.uint8)
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint8)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        sib = np.ascontiguousarray(siblings, dtype=np.uint8)
+        count = idx.shape[0]
+        assert leaves.ndim == 2 and leaves.shape[0] == count and sib.shape == (count, height - 1, 32)
+        assert roots.shape in ((32,), (count, 32))
+        ok, status = np.zeros(count, dtype=np.uint8), np.zeros(count, dtype=np.uint32)
+        self._check(self.lib.swm_merkle_verify_paths(self.h, leaf_handle, two_to_one_handle, height, roots.ctypes.data,
+                                                     32 if roots.ndim == 2 else 0, leaves.ctypes.data, leaves.shape[1], idx.ctypes.data,
+                                                     sib.ctypes.data, count, ok.ctypes.data, status.ctypes.data), "swm_merkle_verify_paths")
+        return ok, status
+
+    def merkle_verify_paths_dev(self, leaf_handle, two_to_one_handle, height, d_roots, root_stride, d_leaves, leaf_len, d_indices, d_siblings,
+                                count, d_ok, d_status=None):
+        self._check(self.lib.swm_merkle_verify_paths_dev(self.h, leaf_handle, two_to_one_handle, height, d_roots.ptr, root_stride, d_leaves.ptr,
+                                                         leaf_len, d_indices.ptr, d_siblings.ptr, count, d_ok.ptr,
+                                                         d_status.ptr if d_status else None), "swm_merkle_verify_paths_dev")
 
     # ---- Schnorr signatures (include/swmarlin.h; simpleworks_amd/schnorr.py is the caller-facing mirror)
     @staticmethod

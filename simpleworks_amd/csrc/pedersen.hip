@@ -27,6 +27,7 @@
 #include "ed.cuh"
 #include "ff.cuh"
 #include "frinv.cuh"
+#include "pedersen.cuh"
 #include "pedersen.h"
 #include "swmarlin.h"
 
@@ -44,32 +45,18 @@ __global__ void __launch_bounds__(256) pedersen_hash_kernel(const EdRow* __restr
     EdExt acc = ed_identity();
     if (live) {
         const uint8_t* msg = in + h * stride;
-        const size_t nbits = len * 8;
-        const unsigned used = (unsigned)min((size_t)num_windows, (nbits + ws - 1) / ws);  // windows past the input are zero bits
-        const unsigned mask = (1u << ws) - 1u;
-#pragma unroll 1
-        for (unsigned w = lane; w < used; w += lanes) {
-            const size_t bit = (size_t)w * ws, byte = bit >> 3;
-            unsigned v = msg[byte];
-            if (byte + 1 < len) v |= (unsigned)msg[byte + 1] << 8;
-            v = (v >> (bit & 7)) & mask;
-            if (v) ed_madd(acc, table[((size_t)w << ws) + v]);
-        }
+        acc = ped_partial(table, num_windows, ws, [msg](size_t i) { return (unsigned)msg[i]; }, len, lanes, lane);
     }
-#pragma unroll 1
-    for (unsigned s = lanes >> 1; s; s >>= 1) {
-        EdExt other = ed_shfl_xor(acc, (int)s);
-        acc = ed_add(acc, other, k2d);
-    }
+    acc = ped_join(acc, lanes, k2d);
     if (live && lane == 0) {
-        Fr x = fp_to_std(fp_mul(acc.x, fr_inv_single(acc.z)));  // Z != 0: the law is complete
+        const Fr x = ped_digest(acc);
         uint32_t* o = reinterpret_cast<uint32_t*>(out + 32 * h);  // device buffers of this library are 256-byte aligned
 #pragma unroll
         for (int i = 0; i < 8; i++) o[i] = x.v[i];
     }
 }
 
-static unsigned lanes_for(size_t count) {
+unsigned lanes_for(size_t count) {
     // ~2^17 lanes keep the chip busy; fewer hashes than that are spread over more lanes each
     unsigned l = 1;
     while (l < 64 && (size_t)l * count < ((size_t)1 << 17)) l <<= 1;

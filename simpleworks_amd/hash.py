@@ -1,5 +1,5 @@
-"""Native Pedersen hash, Pedersen Merkle tree and Poseidon sponge, computed on the GPU (csrc/pedersen.hip and csrc/poseidon.hip
-through include/swmarlin.h).
+"""Native Pedersen hash, Pedersen Merkle tree and Poseidon sponge, computed on the GPU (csrc/pedersen.hip, csrc/merkle_tree.hip and
+csrc/poseidon.hip through include/swmarlin.h).
 
 Caller-facing mirror of what the reference reaches through ark-crypto-primitives 0.3:
     src/hash/mod.rs:13-28                           pedersen_hash(input): LeafWindow 144 x 4, parameters from a fresh test_rng
@@ -7,6 +7,9 @@ Caller-facing mirror of what the reference reaches through ark-crypto-primitives
                                                     MerkleTree::<MerkleConfig>::new(&leaf_crh_params, &two_to_one_crh_params, leaves)
     src/merkle_tree/simple_merkle_tree.rs:99-103    tree.generate_proof(leaf_index), tree.root()
     src/merkle_tree/common.rs:11-30                 the two window shapes
+    examples/simple-payments/ledger.rs:106-173      MerkleTree::blank, tree.update, tree.root (DeviceMerkleTree: the tree stays on
+                                                    the GPU between calls)
+    examples/simple-payments/transaction.rs:163-173 tree.generate_proof, Path::verify (generate_proofs, verify_paths)
 and through ark-sponge 0.3:
     src/hash/mod.rs:30-43                           poseidon2_hash(input): PoseidonSponge<Fq>, absorb the bytes, squeeze one element
 
@@ -189,6 +192,104 @@ class MerkleTree:
 
     def int_levels(self):
         return [[int.from_bytes(r.tobytes(), "little") for r in lvl] for lvl in self.levels]
+
+
+class DeviceMerkleTree:
+    """ark_crypto_primitives::merkle_tree::MerkleTree over (LeafHash, TwoToOneHash) that stays on the GPU (swm_merkle_tree): the
+    account tree of examples/simple-payments/ledger.rs.  blank / new / update / root / generate_proof carry arkworks' names and
+    meaning [U]; update_many and generate_proofs are the batched forms (one call each).  Refers to the two PedersenCRH: keep them
+    alive."""
+
+    def __init__(self, leaf_crh, two_to_one_crh, handle, height, leaf_len):
+        self.ctx = leaf_crh.ctx
+        self.leaf_crh, self.two_to_one_crh = leaf_crh, two_to_one_crh
+        self.h, self._height, self.leaf_len = handle, height, leaf_len
+
+    @staticmethod
+    def blank(leaf_crh, two_to_one_crh, height, leaf_len):
+        """MerkleTree::blank: 2^(height - 1) leaves whose digests are 32 zero bytes (the hash of nothing); `height` counts the leaf
+        level.  leaf_len: the bytes of every leaf that update() will write."""
+        h = leaf_crh.ctx.merkle_tree_create_blank(leaf_crh.h, two_to_one_crh.h, height, leaf_len)
+        return DeviceMerkleTree(leaf_crh, two_to_one_crh, h, height, leaf_len)
+
+    @staticmethod
+    def new(leaf_crh, two_to_one_crh, leaves):
+        a = _leaf_bytes(leaves)
+        h = leaf_crh.ctx.merkle_tree_create_from_leaves(leaf_crh.h, two_to_one_crh.h, a)
+        return DeviceMerkleTree(leaf_crh, two_to_one_crh, h, a.shape[0].bit_length(), a.shape[1])
+
+    def update(self, index, leaf):
+        """tree.update(index, &leaf)."""
+        self.update_many([index], [leaf])
+
+    def update_many(self, indices, leaves):
+        """The updates in order, in one call: a repeated index keeps its last leaf, every ancestor is hashed once."""
+        indices = [int(i) for i in indices]
+        if len(indices) != len(leaves):
+            raise ValueError("one leaf per index")
+        if indices:
+            self.ctx.merkle_tree_update(self.h, np.asarray(indices, dtype=np.uint64), _leaf_bytes(leaves))
+
+    def root(self):
+        return int.from_bytes(self.ctx.merkle_tree_root(self.h).tobytes(), "little")
+
+    def height(self):
+        """tree.height() of ark-crypto-primitives: levels including the leaves."""
+        return self._height
+
+    def generate_proofs(self, indices):
+        """-> uint8 [count, height - 1, 32]: per leaf the sibling digests bottom up, the form MerkleCircuit.witness_many and
+        verify_paths take.  One launch."""
+        return self.ctx.merkle_tree_paths(self.h, self._height - 1, np.asarray([int(i) for i in indices], dtype=np.uint64))
+
+    def generate_proof(self, index):
+        """Path of leaf `index`, as MerkleTree.generate_proof returns it: the siblings bottom up, as integers."""
+        if not 0 <= index < 1 << (self._height - 1):
+            raise IndexError("leaf index out of range")
+        return [int.from_bytes(s.tobytes(), "little") for s in self.generate_proofs([index])[0]]
+
+    def to_merkle_tree(self):
+        """Downloads every node into a MerkleTree."""
+        nodes = self.ctx.merkle_tree_nodes(self.h)
+        levels, off, cnt = [], 0, 1 << (self._height - 1)
+        while cnt >= 1:
+            levels.append(nodes[off:off + cnt])
+            off += cnt
+            cnt >>= 1
+        return MerkleTree(levels)
+
+    def free(self):
+        if self.h:
+            self.ctx.merkle_tree_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def verify_paths(leaf_crh, two_to_one_crh, height, roots, leaves, indices, siblings):
+    """Path::verify(&leaf_params, &two_to_one_params, &root, &leaf) for a batch, in one launch and without a tree
+    (swm_merkle_verify_paths).  roots: one root for all paths (an int or 32 bytes) or one per path (a sequence of those, or uint8
+    [count, 32]); leaves: as MerkleTree.new takes them; siblings: per path the siblings bottom up (ints, 32-byte strings, or uint8
+    [count, height - 1, 32]).  Returns ok, bool [count]; a sibling or root that is no canonical field element, or an index beyond the
+    leaves, is not ok."""
+    def one(r):
+        return bytes(r) if isinstance(r, (bytes, bytearray, np.ndarray)) else int(r).to_bytes(32, "little")
+    if isinstance(roots, np.ndarray):
+        r = np.ascontiguousarray(roots, dtype=np.uint8)
+    elif isinstance(roots, (list, tuple)):
+        r = np.frombuffer(b"".join(one(x) for x in roots), dtype=np.uint8).reshape(len(roots), 32)
+    else:
+        r = np.frombuffer(one(roots), dtype=np.uint8)
+    idx = np.asarray([int(i) for i in indices], dtype=np.uint64)
+    sib = _fr_rows(siblings)
+    if not idx.shape[0]:
+        return np.zeros(0, dtype=bool)
+    ok, _ = leaf_crh.ctx.merkle_verify_paths(leaf_crh.h, two_to_one_crh.h, height, r, _leaf_bytes(leaves), idx, sib)
+    return ok != 0
 
 
 class MerkleCircuit:

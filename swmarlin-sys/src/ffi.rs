@@ -12,6 +12,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_pedersen { _p: [u8; 0] }
 #[repr(C)] pub struct swm_schnorr { _p: [u8; 0] }
 #[repr(C)] pub struct swm_merkle_circuit { _p: [u8; 0] }
+#[repr(C)] pub struct swm_merkle_tree { _p: [u8; 0] }
 #[repr(C)] pub struct swm_schnorr_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_poseidon { _p: [u8; 0] }
 
@@ -145,6 +146,36 @@ extern "C" {
     pub fn swm_merkle_prove(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_merkle_circuit, root: *const u8, leaf: u8,
                             index: u64, siblings: *const u8, rng: *mut swm_rng, flags: c_uint, proof_out: *mut u8, cap: usize,
                             len: *mut usize) -> c_int;
+
+    // the account tree of examples/simple-payments resident on the GPU: MerkleTree::blank / new, batched tree.update, tree.root,
+    // tree.generate_proof and Path::verify (ledger.rs:106-173, transaction.rs:163-173); `height` counts the leaf level; digests and
+    // siblings: 32 canonical LE bytes; update indices are host memory in both forms
+    pub fn swm_merkle_tree_create_blank(ctx: *mut swm_ctx, leaf_params: *const swm_pedersen, two_to_one_params: *const swm_pedersen,
+                                        height: usize, leaf_len: usize, out: *mut *mut swm_merkle_tree) -> c_int;
+    pub fn swm_merkle_tree_create_from_leaves(ctx: *mut swm_ctx, leaf_params: *const swm_pedersen, two_to_one_params: *const swm_pedersen,
+                                              leaves: *const u8, leaf_len: usize, n_leaves: usize, out: *mut *mut swm_merkle_tree) -> c_int;
+    pub fn swm_merkle_tree_create_from_leaves_dev(ctx: *mut swm_ctx, leaf_params: *const swm_pedersen,
+                                                  two_to_one_params: *const swm_pedersen, d_leaves: *const c_void, leaf_len: usize,
+                                                  n_leaves: usize, out: *mut *mut swm_merkle_tree) -> c_int;
+    pub fn swm_merkle_tree_destroy(ctx: *mut swm_ctx, tree: *mut swm_merkle_tree);
+    pub fn swm_merkle_tree_update(ctx: *mut swm_ctx, tree: *mut swm_merkle_tree, indices: *const u64, leaves: *const u8, leaf_len: usize,
+                                  count: usize) -> c_int;
+    pub fn swm_merkle_tree_update_dev(ctx: *mut swm_ctx, tree: *mut swm_merkle_tree, indices: *const u64, d_leaves: *const c_void,
+                                      leaf_len: usize, count: usize) -> c_int;
+    pub fn swm_merkle_tree_root(ctx: *mut swm_ctx, tree: *const swm_merkle_tree, root: *mut u8) -> c_int;
+    pub fn swm_merkle_tree_paths(ctx: *mut swm_ctx, tree: *const swm_merkle_tree, indices: *const u64, count: usize,
+                                 siblings: *mut u8) -> c_int;
+    pub fn swm_merkle_tree_paths_dev(ctx: *mut swm_ctx, tree: *const swm_merkle_tree, d_indices: *const c_void, count: usize,
+                                     d_siblings: *mut c_void) -> c_int;
+    pub fn swm_merkle_tree_nodes(ctx: *mut swm_ctx, tree: *const swm_merkle_tree, nodes: *mut u8) -> c_int;
+    pub fn swm_merkle_tree_dev_nodes(tree: *const swm_merkle_tree, d_nodes: *mut *mut c_void, n_nodes: *mut usize) -> c_int;
+    pub fn swm_merkle_verify_paths(ctx: *mut swm_ctx, leaf_params: *const swm_pedersen, two_to_one_params: *const swm_pedersen,
+                                   height: usize, roots: *const u8, root_stride: usize, leaves: *const u8, leaf_len: usize,
+                                   indices: *const u64, siblings: *const u8, count: usize, ok: *mut u8, status: *mut u32) -> c_int;
+    pub fn swm_merkle_verify_paths_dev(ctx: *mut swm_ctx, leaf_params: *const swm_pedersen, two_to_one_params: *const swm_pedersen,
+                                       height: usize, d_roots: *const c_void, root_stride: usize, d_leaves: *const c_void,
+                                       leaf_len: usize, d_indices: *const c_void, d_siblings: *const c_void, count: usize,
+                                       d_ok: *mut c_void, d_status: *mut c_void) -> c_int;
 
     // the native Schnorr scheme of src/schnorr_signature/schnorr.rs:57-160, batched (points: x || y, 32 LE bytes each; a signature:
     // prover_response || verifier_challenge; secrets and nonces are the caller's draws)
