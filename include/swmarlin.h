@@ -552,6 +552,46 @@ int swm_poseidon_hash_bytes_dev(swm_ctx *ctx, const swm_poseidon *params, const 
                                 void *d_digests);
 int swm_poseidon_pack_bytes(const uint8_t *input, size_t len, uint8_t *elems, size_t cap_elems, size_t *n_elems);
 
+/* ---------------------------------------------------------------------------------------------- Poseidon hash witness
+ * The assignment of the Poseidon hash circuit (the gadget of src/gadgets/poseidon.rs:12-31 as this library lays it out:
+ * simpleworks_amd/workloads.py, build_poseidon_hash) synthesised on the GPU, one lane per item, without running the constraint
+ * synthesizer on the host.  The statement: "I know an input whose sponge output is the public `outputs`".  Two forms:
+ *   bytes_form != 0   n_in input bytes as 8 n_in witness bits (byte-major, least significant first), n_out = 1: the digest of
+ *                     swm_poseidon_hash_bytes is the one public input (the reference's unit test publishes nothing instead);
+ *   bytes_form == 0   n_in witness elements (0 .. 4096), n_out public outputs (1 .. 16): swm_poseidon_hash_fr.
+ * Then, per permutation, round and S-box, the chain of x^alpha: m = floor(log2 alpha) + popcount(alpha) - 1 values.  With S = 3
+ * full_rounds + partial_rounds, E = ceil((8 + n_in) / 31) or n_in elements absorbed, and P = ceil(E / 2) + ceil(n_out / 2) -
+ * (E > 0) permutations:
+ *   num_instance = 1 + n_out;  num_witness = (8 n_in or n_in) + P S m;  num_constraints = (8 n_in or 0) + P S m + n_out.
+ * Nothing is folded into constants: the shape depends on (full_rounds, partial_rounds, alpha, form, n_in, n_out) alone.
+ * swm_poseidon_circuit_shape needs no GPU.  SWM_ERR_INVALID_ARG: a parameter shape swm_poseidon_create refuses, n_in > 65536
+ * bytes or > 4096 elements, n_out outside 1 .. 16 or not 1 in the bytes form, a NULL output.
+ * swm_poseidon_circuit_create: the shape of `params` and the lengths.  The handle refers to the swm_poseidon: keep it.
+ * swm_poseidon_witness: `count` items in one launch.  inputs: count x n_in bytes, or count x n_in x 32 bytes (canonical
+ * little-endian elements); may be NULL when n_in = 0.  An element >= r refuses the WHOLE call with SWM_ERR_INVALID_ARG and nothing
+ * is written.  witness: count x num_witness x 4 Montgomery limbs, in the circuit's variable order; outputs (may be NULL): count x
+ * n_out x 32 canonical bytes, the public inputs.  A batch whose witnesses exceed 1 GiB is staged through the device in chunks of
+ * floor(1 GiB / (32 num_witness)) items (at least one).  count = 0 launches nothing.
+ * swm_poseidon_witness_dev: the same on device buffers (witness 16-byte aligned; elements, outputs and status 4-byte aligned), no chunking.  What the host
+ * form refuses is reported per item instead: d_status (count words, may be NULL) is 0 for an item that was computed and 1 for an
+ * element >= r; the witness and the outputs of such an item are zero, the other items of the batch are unaffected.
+ * swm_poseidon_prove: witness on the device, then the proof of swm_generate_proof_ex(flags) with the n_out outputs as the public
+ * input; the witness reaches the prover by a device-to-device copy.  outputs: n_out x 32 canonical bytes, what the verifier is
+ * given.  There is no unsatisfied case: the library computes the digest it proves.  A key indexed for another shape is
+ * SWM_ERR_MISMATCH. */
+typedef struct swm_poseidon_circuit swm_poseidon_circuit;
+int swm_poseidon_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64_t alpha, int bytes_form, size_t n_in, size_t n_out,
+                               size_t *num_instance, size_t *num_witness, size_t *num_constraints);
+int swm_poseidon_circuit_create(swm_ctx *ctx, const swm_poseidon *params, int bytes_form, size_t n_in, size_t n_out,
+                                swm_poseidon_circuit **out);
+void swm_poseidon_circuit_destroy(swm_ctx *ctx, swm_poseidon_circuit *circuit);
+int swm_poseidon_witness(swm_ctx *ctx, const swm_poseidon_circuit *circuit, const uint8_t *inputs, size_t count, uint64_t *witness,
+                         uint8_t *outputs);
+int swm_poseidon_witness_dev(swm_ctx *ctx, const swm_poseidon_circuit *circuit, const void *d_inputs, size_t count, void *d_witness,
+                             void *d_outputs, void *d_status);
+int swm_poseidon_prove(swm_ctx *ctx, const swm_pk *pk, const swm_poseidon_circuit *circuit, const uint8_t *input, swm_rng *rng,
+                       unsigned flags, uint8_t *outputs, uint8_t *proof_out, size_t cap, size_t *len);
+
 /* ---------------------------------------------------------------------------------------------- one proof over several GPUs
  * every commitment MSM of swm_generate_proof / swm_generate_proving_and_verifying_keys is split by
  * point range — rank g of `world` takes coefficients and SRS powers [g n / world, (g+1) n / world) — and the

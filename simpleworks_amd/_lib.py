@@ -138,6 +138,14 @@ ABI = {
     "swm_poseidon_hash_bytes": (_int, [_vp, _vp, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
     "swm_poseidon_hash_bytes_dev": (_int, [_vp, _vp, _vp, _sz, _sz, _vp]),
     "swm_poseidon_pack_bytes": (_int, [ctypes.c_void_p, _sz, ctypes.c_void_p, _sz, ctypes.POINTER(_sz)]),
+    "swm_poseidon_circuit_shape": (_int, [_sz, _sz, ctypes.c_uint64, _int, _sz, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz),
+                                          ctypes.POINTER(_sz)]),
+    "swm_poseidon_circuit_create": (_int, [_vp, _vp, _int, _sz, _sz, ctypes.POINTER(_vp)]),
+    "swm_poseidon_circuit_destroy": (None, [_vp, _vp]),
+    "swm_poseidon_witness": (_int, [_vp, _vp, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_poseidon_witness_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "swm_poseidon_prove": (_int, [_vp, _vp, _vp, ctypes.c_void_p, _vp, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, _sz,
+                                  ctypes.POINTER(_sz)]),
     "swm_profile_enable": (_int, [_vp, _int]),
     "swm_profile_reset": (_int, [_vp]),
     "swm_profile_json": (_int, [_vp, ctypes.c_char_p, _sz]),
@@ -724,6 +732,33 @@ class Context:
     def poseidon_hash_bytes_dev(self, handle, d_inputs, input_len, count, d_digests):
         self._check(self.lib.swm_poseidon_hash_bytes_dev(self.h, handle, d_inputs.ptr if d_inputs else None, input_len, count,
                                                          d_digests.ptr), "swm_poseidon_hash_bytes_dev")
+
+    # ---- Poseidon hash witness (include/swmarlin.h; simpleworks_amd/hash.py, PoseidonCircuit, is the caller-facing mirror)
+    def poseidon_circuit_create(self, params_handle, bytes_form, n_in, n_out=1):
+        h = _vp()
+        self._check(self.lib.swm_poseidon_circuit_create(self.h, params_handle, 1 if bytes_form else 0, n_in, n_out, ctypes.byref(h)),
+                    "swm_poseidon_circuit_create")
+        return h
+
+    def poseidon_circuit_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_poseidon_circuit_destroy(self.h, handle)
+
+    def poseidon_witness(self, handle, num_witness, n_out, inputs, outputs=None):
+        """inputs: uint8 [count, input_len] (bytes form) or uint8 [count, n_in, 32] (elements form) ->
+        (witness uint64 [count, num_witness, 4] Montgomery limbs, outputs uint8 [count, n_out, 32])."""
+        a = np.ascontiguousarray(inputs, dtype=np.uint8)
+        n = a.shape[0]
+        witness = np.empty((n, num_witness, 4), dtype=np.uint64)
+        outputs = np.empty((n, n_out, 32), dtype=np.uint8) if outputs is None else outputs
+        self._check(self.lib.swm_poseidon_witness(self.h, handle, a.ctypes.data if a.size else None, n, witness.ctypes.data,
+                                                  outputs.ctypes.data), "swm_poseidon_witness")
+        return witness, outputs
+
+    def poseidon_witness_dev(self, handle, d_inputs, count, d_witness, d_outputs=None, d_status=None):
+        self._check(self.lib.swm_poseidon_witness_dev(self.h, handle, d_inputs.ptr if d_inputs else None, count,
+                                                      d_witness.ptr if d_witness else None, d_outputs.ptr if d_outputs else None,
+                                                      d_status.ptr if d_status else None), "swm_poseidon_witness_dev")
 
     # ---- measurement
     def profile_enable(self, on=True):

@@ -8,6 +8,7 @@
 #include <new>
 #include "merkle_shape.h"
 #include "schnorr_shape.h"
+#include "poseidon_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
 extern "C" {
@@ -224,6 +225,26 @@ int swm_poseidon_pack_bytes(const uint8_t* input, size_t len, uint8_t* elems, si
             o[j] = (j == 31 || pos >= total) ? 0 : pos < 8 ? (uint8_t)((uint64_t)len >> (8 * pos)) : input[pos - 8];
         }
     }
+    return SWM_OK;
+}
+
+// The Poseidon hash circuit's shape from the parameter shape, the form and the lengths (poseidon_shape.h; the layout is
+// build_poseidon_hash's)
+int swm_poseidon_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64_t alpha, int bytes_form, size_t n_in, size_t n_out,
+                               size_t* num_instance, size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "poseidon_circuit_shape: NULL output");
+    PoseidonShape s;
+    if (!poseidon_shape(full_rounds, partial_rounds, alpha, bytes_form != 0, n_in, n_out, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG,
+                       "poseidon_circuit_shape: %zu + %zu rounds, alpha %llu, %zu %s in, %zu out (full rounds even and >= 2, at most %zu "
+                       "rounds, alpha 2 .. %llu, at most %zu bytes and one output or %zu elements and 1 .. %zu outputs)",
+                       full_rounds, partial_rounds, (unsigned long long)alpha, n_in, bytes_form ? "bytes" : "elements", n_out,
+                       (size_t)PC_MAX_ROUNDS, (unsigned long long)PC_MAX_ALPHA, (size_t)PC_MAX_BYTES, (size_t)PC_MAX_IN, (size_t)PC_MAX_OUT);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
     return SWM_OK;
 }
 

@@ -22,7 +22,7 @@ import json
 import numpy as np
 
 from ._lib import poseidon_pack_bytes  # noqa: F401  (the sponge's byte-to-element rule on the host)
-from .marlin import R_MODULUS, default_context, generate_rand, merkle_circuit_shape
+from .marlin import R_MODULUS, default_context, generate_rand, merkle_circuit_shape, poseidon_circuit_shape
 
 ED_D = 3021            # ed-on-BLS12-377: -x^2 + y^2 = 1 + 3021 x^2 y^2 over BLS12-377 Fr
 ED_COFACTOR = 4
@@ -392,6 +392,59 @@ class PoseidonSponge:
     def free(self):
         if self.h:
             self.ctx.poseidon_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PoseidonCircuit:
+    """The Poseidon hash circuit over a resident sponge (swm_poseidon_circuit): synthesises the witness vector of
+    workloads.build_poseidon_hash for batches of inputs without running the builder, one GPU lane per input.  input_len: the bytes
+    form (n_out = 1, the digest is the public input); n_in: the elements form.  Refers to the PoseidonSponge: keep it alive."""
+
+    def __init__(self, sponge, input_len=None, n_in=None, n_out=1):
+        if (input_len is None) == (n_in is None):
+            raise ValueError("either input_len (bytes form) or n_in (elements form)")
+        self.ctx, self.sponge = sponge.ctx, sponge
+        self.bytes_form, self.input_len, self.n_in, self.n_out = n_in is None, input_len, n_in, n_out
+        self.h = self.ctx.poseidon_circuit_create(sponge.h, self.bytes_form, input_len if self.bytes_form else n_in, n_out)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        return poseidon_circuit_shape(self.sponge.params, self.input_len, self.n_in, self.n_out)
+
+    def pack_inputs(self, inputs):
+        """bytes form: equally long byte strings or uint8 [count, input_len]; elements form: as PoseidonSponge.hash_elements_many."""
+        if not self.bytes_form:
+            a = _fr_rows(inputs)
+            if a.shape[0] == 0:
+                a = a.reshape(0, self.n_in, 32)
+            if a.shape[1] != self.n_in:
+                raise ValueError("an item of this circuit holds %d elements" % self.n_in)
+            return a
+        if isinstance(inputs, np.ndarray):
+            a = np.ascontiguousarray(inputs, dtype=np.uint8)
+        else:
+            rows = [bytes(m) for m in inputs]
+            if any(len(m) != self.input_len for m in rows):
+                raise ValueError("an input of this circuit is %d bytes long" % self.input_len)
+            a = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), self.input_len)
+        if a.ndim != 2 or a.shape[1] != self.input_len:
+            raise ValueError("an input of this circuit is %d bytes long" % self.input_len)
+        return a.reshape(a.shape[0], self.input_len)
+
+    def witness_many(self, inputs):
+        """One launch (chunks above 1 GiB of witnesses).  Returns (witness uint64 [count, num_witness, 4], outputs uint8 [count, n_out, 32]): the
+        public inputs as canonical little-endian bytes)."""
+        return self.ctx.poseidon_witness(self.h, self.shape()[1], self.n_out, self.pack_inputs(inputs))
+
+    def free(self):
+        if self.h:
+            self.ctx.poseidon_circuit_destroy(self.h)
             self.h = None
 
     def __del__(self):

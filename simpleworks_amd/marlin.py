@@ -480,6 +480,39 @@ def generate_schnorr_proof(proving_key, circuit, public_key, message, signature,
     return bytes(buf[: n.value])
 
 
+def poseidon_circuit_shape(params, input_len=None, n_in=None, n_out=1):
+    """swm_poseidon_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the Poseidon hash circuit over the shape
+    of `params` (a hash.PoseidonParameters) — what workloads.build_poseidon_hash emits.  input_len: the bytes form; n_in: the
+    elements form."""
+    if (input_len is None) == (n_in is None):
+        raise ValueError("poseidon_circuit_shape: either input_len (bytes form) or n_in (elements form)")
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_poseidon_circuit_shape(params.full_rounds, params.partial_rounds, params.alpha, 1 if n_in is None else 0,
+                                                     input_len if n_in is None else n_in, n_out, ctypes.byref(ni), ctypes.byref(nw),
+                                                     ctypes.byref(nc)), "swm_poseidon_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_poseidon_proof(proving_key, circuit, data_or_elements, rng, uncompressed=False):
+    """swm_poseidon_prove: the proof of workloads.PoseidonHashCircuit with the circuit's witness synthesised on the GPU
+    (hash.PoseidonCircuit) and handed to the prover on the device.  data_or_elements: input_len bytes (bytes form) or n_in field
+    elements as ints or 32-byte strings (elements form).  Returns (proof bytes, outputs): the outputs, as ints, are the public
+    input to verify with."""
+    ctx = proving_key.ctx
+    item = circuit.pack_inputs([data_or_elements])
+    if item.shape[0] != 1:
+        raise ValueError("generate_poseidon_proof: one input")
+    raw = item.tobytes()
+    in_b = (ctypes.c_uint8 * max(1, len(raw))).from_buffer_copy(raw.ljust(1, b"\0"))
+    out_b = (ctypes.c_uint8 * (32 * circuit.n_out))()
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    _check(ctx.lib.swm_poseidon_prove(ctx.h, proving_key.h, circuit.h, in_b, rng.h, 1 if uncompressed else 0, out_b, buf, len(buf),
+                                      ctypes.byref(n)), "swm_poseidon_prove", ctx)
+    out = bytes(out_b)
+    return bytes(buf[: n.value]), [int.from_bytes(out[32 * j:32 * j + 32], "little") for j in range(circuit.n_out)]
+
+
 def verify_proof(verifying_key, public_inputs, proof, rng):
     """src/marlin/mod.rs:79-86.  public_inputs: field elements as ints (e.g. the bit-expanded inputs of
     src/merkle_tree/simple_merkle_tree.rs:129-143)."""

@@ -981,3 +981,184 @@ class SimpleSchnorrSignatureVerification:
 
     def generate_constraints(self, cs):
         build_schnorr_verification(cs, self.generator, self.salt, self.public_key, self.message, self.signature)
+
+
+# ===================================================================================================================
+# The reference's third circuit: the Poseidon hash gadget (src/gadgets/poseidon.rs:12-31 — PoseidonSpongeVar::new, absorb,
+# squeeze_field_elements(1) — over the native sponge of src/hash/mod.rs:30-43).  As with the other two circuits the row layout
+# is OURS, not arkworks': same statement ("I know an input whose sponge output is the public `outputs`"), our own rows.
+# build_poseidon_hash is the layout contract of csrc/host/poseidon_shape.h and csrc/poseidon_witness.hip.
+#
+# Two forms, as the native kernel's:
+#   bytes     what gadgets::poseidon2_hash(&Vec<UInt8>) synthesises: n bytes as 8 n witness bits (as transaction.rs:52-55
+#             allocates its message), one output.  The digest is the ONE PUBLIC INPUT — a departure from the reference's unit
+#             test, which allocates the message as input and publishes nothing.
+#   elements  absorb of n_in field elements (witnesses), squeeze_field_elements(n_out): n_out public outputs.
+# Variable order (poseidon_circuit_layout gives the offsets):
+#   instance  one, then the n_out outputs
+#   bits      bytes form: 8 n booleans, byte-major, least significant first, a booleanity row each       8 n,       8 n
+#             the absorbed elements are linear combinations of them: the 31-byte chunks of (n as 8 little-endian bytes, a
+#             constant, then the input bits) — the packing of swm_poseidon_pack_bytes; no rows, no variables
+#   elements  elements form: the n_in elements, no rows of their own                                    n_in,      0
+#   sponge    per permutation, per round, per S-box of the round (entries 0, 1, 2 in a full round, entry 0 in a partial one):
+#             the chain of x^alpha over x = state[k] + ark[i][k] (a linear combination), left to right over the bits of alpha
+#             below the top one: a square per bit, then a product by x where the bit is set; every square and product is one
+#             witness and one row: m(alpha) = floor(log2 alpha) + popcount(alpha) - 1 per S-box           P S m,     P S m
+#   out       one row per output: (state entry) * one = output_j                                         0,         n_out
+# The matrix step and the round keys are linear and add nothing; an entry that passes partial rounds without an S-box stays a
+# linear combination of earlier chain ends (up to 3 + partial_rounds terms and the constant).
+# NO CONSTANT FOLDING: in the first round of the first permutation state[2] + ark is a constant (state[1] too for a short
+# input) and still costs its chain: the shape depends on (full, partial, alpha, form, n_in, n_out) alone.
+# The permutation schedule is the native sponge's: in_blocks = ceil(E / 2) absorbing steps, out_blocks = ceil(n_out / 2)
+# squeezing steps, a permutation before every step but a first absorbing one: P = in_blocks + out_blocks - (in_blocks > 0).
+# ===================================================================================================================
+POSEIDON_MAX_BYTES, POSEIDON_MAX_IN, POSEIDON_MAX_OUT = 65536, 4096, 16
+
+
+def _ps_shape_args(params, input_len, n_in, n_out):
+    """-> (bytes form?, input length or element count, elements absorbed)."""
+    if (input_len is None) == (n_in is None):
+        raise ValueError("poseidon circuit: either input_len (bytes form) or n_in (elements form)")
+    full, partial, alpha = params.full_rounds, params.partial_rounds, params.alpha
+    if full < 2 or full & 1 or partial < 0 or full + partial > 255 or not 2 <= alpha <= 65535:
+        raise ValueError("poseidon circuit: full rounds even and >= 2, at most 255 rounds, alpha 2 .. 65535")
+    if input_len is not None:
+        if not 0 <= input_len <= POSEIDON_MAX_BYTES or n_out != 1:
+            raise ValueError("poseidon circuit: the bytes form takes 0 .. %d bytes and gives one output" % POSEIDON_MAX_BYTES)
+        return True, input_len, (8 + input_len + 30) // 31
+    if not 0 <= n_in <= POSEIDON_MAX_IN or not 1 <= n_out <= POSEIDON_MAX_OUT:
+        raise ValueError("poseidon circuit: 0 .. %d elements in, 1 .. %d out" % (POSEIDON_MAX_IN, POSEIDON_MAX_OUT))
+    return False, n_in, n_in
+
+
+def poseidon_circuit_layout(params, input_len=None, n_in=None, n_out=1):
+    """Offsets of the witness groups of build_poseidon_hash and its three counts, as csrc/host/poseidon_shape.h states them."""
+    bytes_form, n, elems = _ps_shape_args(params, input_len, n_in, n_out)
+    lay = {"bits" if bytes_form else "elements": 0, "sponge": 8 * n if bytes_form else n}
+    in_blocks, out_blocks = (elems + 1) // 2, (n_out + 1) // 2
+    lay["permutations"] = in_blocks + out_blocks - (1 if in_blocks else 0)
+    lay["sboxes"] = 3 * params.full_rounds + params.partial_rounds
+    lay["chain"] = params.alpha.bit_length() - 1 + bin(params.alpha).count("1") - 1
+    values = lay["permutations"] * lay["sboxes"] * lay["chain"]
+    lay["num_instance"] = 1 + n_out
+    lay["num_witness"] = lay["sponge"] + values
+    lay["num_constraints"] = (8 * n if bytes_form else 0) + values + n_out
+    return lay
+
+
+class _PsLC:
+    """A linear combination with its value whose terms are merged per variable: a state entry of the sponge."""
+    __slots__ = ("coeffs", "value")
+
+    def __init__(self, coeffs=None, value=0):
+        self.coeffs, self.value = dict(coeffs or {}), value % R_MODULUS
+
+    def add(self, k, other):
+        """self += k * other"""
+        for var, c in other.coeffs.items():
+            self.coeffs[var] = (self.coeffs.get(var, 0) + k * c) % R_MODULUS
+        self.value = (self.value + k * other.value) % R_MODULUS
+        return self
+
+    @property
+    def terms(self):
+        return [(c, var) for var, c in self.coeffs.items() if c]
+
+
+def build_poseidon_hash(cs, params, data=None, elements=None, n_out=1):
+    """Emits the Poseidon hash circuit into `cs` (builder vocabulary as build_schnorr_verification).  params: a
+    hash.PoseidonParameters; data: bytes (the bytes form, n_out = 1) or elements: field elements as ints < r (the elements form).
+    The outputs are the public inputs, allocated after `one` in squeezing order; returns them as a list of ints.  The builder
+    computes every value itself through the values of its linear combinations: there is no unsatisfied honest case."""
+    if (data is None) == (elements is None):
+        raise ValueError("poseidon circuit: either data (bytes form) or elements (elements form)")
+    if data is not None:
+        data = bytes(data)
+        _ps_shape_args(params, len(data), None, n_out)
+    else:
+        elements = [int(e) for e in elements]
+        _ps_shape_args(params, None, len(elements), n_out)
+        if any(not 0 <= e < R_MODULUS for e in elements):
+            raise ValueError("poseidon circuit: an element is not a canonical field element")
+    full, partial, alpha = params.full_rounds, params.partial_rounds, params.alpha
+    one = cs.one()
+
+    def const(v):
+        return _PsLC({one: v % R_MODULUS}, v)
+
+    def product(a, b):
+        v = a.value * b.value % R_MODULUS
+        w = _PsLC({cs.new_witness_variable(v): 1}, v)
+        cs.enforce_constraint(a.terms, b.terms, w.terms)
+        return w
+
+    # bits / elements
+    if data is not None:
+        bits = [_boolean_witness(cs, one, (byte >> i) & 1) for byte in data for i in range(8)]
+        total = 8 + len(data)
+        absorbed = []
+        for at in range(0, total, 31):
+            e = _PsLC()
+            for j in range(min(31, total - at)):
+                pos = at + j
+                if pos < 8:
+                    e.add(((len(data) >> (8 * pos)) & 0xFF) << (8 * j), const(1))
+                else:
+                    for i in range(8):
+                        b = bits[8 * (pos - 8) + i]
+                        e.add(1 << (8 * j + i), _PsLC({b.terms[0][1]: 1}, b.value))
+            absorbed.append(e)
+    else:
+        absorbed = [_PsLC({cs.new_witness_variable(e): 1}, e) for e in elements]
+
+    def permute(state):
+        for i in range(full + partial):
+            is_full = i < full // 2 or i >= full // 2 + partial
+            t = [_PsLC(s.coeffs, s.value).add(params.ark[i][k], const(1)) for k, s in enumerate(state)]
+            for k in range(3 if is_full else 1):
+                acc = t[k]
+                for b in range(alpha.bit_length() - 2, -1, -1):
+                    acc = product(acc, acc)
+                    if (alpha >> b) & 1:
+                        acc = product(acc, t[k])
+                t[k] = acc
+            state = [_PsLC().add(params.mds[a][0], t[0]).add(params.mds[a][1], t[1]).add(params.mds[a][2], t[2]) for a in range(3)]
+        return state
+
+    # sponge: the absorbing blocks of two elements, then the squeezing blocks of two outputs
+    state = [_PsLC(), _PsLC(), _PsLC()]
+    in_blocks, out_blocks = (len(absorbed) + 1) // 2, (n_out + 1) // 2
+    squeezed = []
+    for step in range(in_blocks + out_blocks):
+        if step > 0 or in_blocks == 0:
+            state = permute(state)
+        if step < in_blocks:
+            for k, e in enumerate(absorbed[2 * step:2 * step + 2]):
+                state[k].add(1, e)
+        else:
+            squeezed += [_PsLC(s.coeffs, s.value) for s in state[:2]]
+    # out
+    public = []
+    for s in squeezed[:n_out]:
+        out = cs.new_input_variable(s.value)
+        cs.enforce_constraint(s.terms, [(1, one)], [(1, out)])
+        public.append(s.value)
+    return public
+
+
+def poseidon_hash_circuit(params, data=None, elements=None, n_out=1):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs) with public_inputs = the outputs."""
+    cs = ConstraintSystem()
+    public = build_poseidon_hash(cs, params, data, elements, n_out)
+    return cs, public
+
+
+class PoseidonHashCircuit:
+    """The ConstraintSynthesizer of the Poseidon hash statement for MarlinInst.index / prove: constants = the sponge parameters,
+    witness = the input, public input = the outputs."""
+
+    def __init__(self, params, data=None, elements=None, n_out=1):
+        self.params, self.data, self.elements, self.n_out = params, data, elements, n_out
+
+    def generate_constraints(self, cs):
+        build_poseidon_hash(cs, self.params, self.data, self.elements, self.n_out)

@@ -15,6 +15,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_merkle_tree { _p: [u8; 0] }
 #[repr(C)] pub struct swm_schnorr_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_poseidon { _p: [u8; 0] }
+#[repr(C)] pub struct swm_poseidon_circuit { _p: [u8; 0] }
 
 pub const SWM_OK: c_int = 0;
 pub const SWM_ERR_UNSATISFIED: c_int = -5;
@@ -220,4 +221,21 @@ extern "C" {
     pub fn swm_poseidon_hash_bytes_dev(ctx: *mut swm_ctx, params: *const swm_poseidon, d_inputs: *const c_void, input_len: usize,
                                        count: usize, d_digests: *mut c_void) -> c_int;
     pub fn swm_poseidon_pack_bytes(input: *const u8, len: usize, elems: *mut u8, cap_elems: usize, n_elems: *mut usize) -> c_int;
+
+    // the Poseidon hash circuit's witness on the GPU (the gadget of src/gadgets/poseidon.rs:12-31 in this library's row layout): the
+    // outputs are the public input; witness: Montgomery limbs; outputs: canonical LE bytes.  (Declarations only: nothing in this
+    // crate is compiled or linked by the library's own build or tests.)
+    pub fn swm_poseidon_circuit_shape(full_rounds: usize, partial_rounds: usize, alpha: u64, bytes_form: c_int, n_in: usize,
+                                      n_out: usize, num_instance: *mut usize, num_witness: *mut usize,
+                                      num_constraints: *mut usize) -> c_int;
+    pub fn swm_poseidon_circuit_create(ctx: *mut swm_ctx, params: *const swm_poseidon, bytes_form: c_int, n_in: usize, n_out: usize,
+                                       out: *mut *mut swm_poseidon_circuit) -> c_int;
+    pub fn swm_poseidon_circuit_destroy(ctx: *mut swm_ctx, circuit: *mut swm_poseidon_circuit);
+    pub fn swm_poseidon_witness(ctx: *mut swm_ctx, circuit: *const swm_poseidon_circuit, inputs: *const u8, count: usize,
+                                witness: *mut u64, outputs: *mut u8) -> c_int;
+    pub fn swm_poseidon_witness_dev(ctx: *mut swm_ctx, circuit: *const swm_poseidon_circuit, d_inputs: *const c_void, count: usize,
+                                    d_witness: *mut c_void, d_outputs: *mut c_void, d_status: *mut c_void) -> c_int;
+    pub fn swm_poseidon_prove(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_poseidon_circuit, input: *const u8,
+                              rng: *mut swm_rng, flags: c_uint, outputs: *mut u8, proof_out: *mut u8, cap: usize,
+                              len: *mut usize) -> c_int;
 }
