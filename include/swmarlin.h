@@ -476,6 +476,44 @@ int swm_schnorr_verify(swm_ctx *ctx, const swm_schnorr *params, const uint8_t *p
 int swm_schnorr_commitments(swm_ctx *ctx, const swm_schnorr *params, const uint8_t *public_keys_xy, const uint8_t *signatures,
                             size_t count, uint8_t *commitments_xy);
 
+/* ---------------------------------------------------------------------------------------------- ElGamal encryption
+ * The reference's native encryption scheme, ElGamal<EdwardsProjective> on ed-on-BLS12-377 (ark-crypto-primitives 0.3,
+ * encryption/elgamal/mod.rs [U], exercised by tests/encrypt.rs:11-28), batched: one GPU lane per key, encryption or decryption.
+ *   setup    generator = C::rand(rng): a random point of the prime subgroup
+ *   keygen   pk = sk G
+ *   encrypt  c1 = r G, c2 = m + r pk; the ciphertext is (c1, c2)
+ *   decrypt  m = c2 - sk c1
+ * The random draws of setup, keygen and Randomness::rand stay with the caller, who hands in the generator, the secret keys and one
+ * scalar of randomness per encryption.
+ * Wire forms: those of the Schnorr block.  A point (generator, public key, plaintext, each half of a ciphertext): x || y, 32
+ * little-endian bytes each in standard form.  A secret key or randomness: 32 little-endian bytes, < the group order l.  A ciphertext:
+ * c1.x || c1.y || c2.x || c2.y, 128 bytes.
+ * swm_elgamal_create: Parameters { generator } resident on the GPU with a table of the generator's window multiples.
+ * swm_elgamal_key_create: ONE public key resident with a table of ITS window multiples, for swm_elgamal_encrypt_to.  Either refuses a
+ * point off the curve (or a coordinate >= r) with SWM_ERR_INVALID_ARG; any on-curve point is accepted, in the prime subgroup or not.
+ * swm_elgamal_keygen: public_keys_xy[i] = secret_keys[i] G.
+ * swm_elgamal_encrypt: ciphertext i of messages_xy[i] under public_keys_xy[i] with randomness[i]; one scalar multiplication of a
+ * per-item point each (launches of at most 2^18 items over a 256 MB table buffer).
+ * swm_elgamal_encrypt_to: the same bytes for every message under the one resident key, from two table walks: what a caller with
+ * many messages for one recipient should use.
+ * swm_elgamal_decrypt: messages_xy[i] = c2_i - secret_keys[i] c1_i; needs no parameters (the generator takes no part).
+ * A scalar >= l, a coordinate >= r or a point off the curve (no arkworks value holds any of them) — in a secret key, the randomness,
+ * a public key, a message or either half of a ciphertext — refuses the WHOLE call with SWM_ERR_INVALID_ARG and nothing is written.
+ * On-curve points outside the prime subgroup, the identity and the scalar 0 are computed exactly as arkworks' mul and add compute
+ * them: the addition law is complete on the whole curve.  count = 0 returns SWM_OK everywhere and launches nothing. */
+typedef struct swm_elgamal swm_elgamal;
+typedef struct swm_elgamal_key swm_elgamal_key;
+int swm_elgamal_create(swm_ctx *ctx, const uint8_t generator_xy[64], swm_elgamal **out);
+void swm_elgamal_destroy(swm_ctx *ctx, swm_elgamal *params);
+int swm_elgamal_keygen(swm_ctx *ctx, const swm_elgamal *params, const uint8_t *secret_keys, size_t count, uint8_t *public_keys_xy);
+int swm_elgamal_key_create(swm_ctx *ctx, const uint8_t public_key_xy[64], swm_elgamal_key **out);
+void swm_elgamal_key_destroy(swm_ctx *ctx, swm_elgamal_key *key);
+int swm_elgamal_encrypt(swm_ctx *ctx, const swm_elgamal *params, const uint8_t *public_keys_xy, const uint8_t *messages_xy,
+                        const uint8_t *randomness, size_t count, uint8_t *ciphertexts);
+int swm_elgamal_encrypt_to(swm_ctx *ctx, const swm_elgamal *params, const swm_elgamal_key *key, const uint8_t *messages_xy,
+                           const uint8_t *randomness, size_t count, uint8_t *ciphertexts);
+int swm_elgamal_decrypt(swm_ctx *ctx, const uint8_t *secret_keys, const uint8_t *ciphertexts, size_t count, uint8_t *messages_xy);
+
 /* ---------------------------------------------------------------------------------------------- Schnorr verification witness
  * The assignment of the Schnorr verification circuit (SimpleSchnorrSignatureVerification, examples/simple-payments/transaction.rs:
  * 33-71, as this library lays it out: simpleworks_amd/workloads.py, build_schnorr_verification) synthesised on the GPU: what

@@ -7,8 +7,10 @@ Layout (only what the path needs):
   marlin.py        mirror of src/marlin/mod.rs (generate_universal_srs / ..._keys / generate_proof / verify_proof)
   serialization.py mirror of src/marlin/serialization.rs
   hash.py          mirror of src/hash/mod.rs (Pedersen CRH) and the MerkleTree calls; schnorr.py: mirror of src/schnorr_signature/schnorr.rs
+  elgamal.py       mirror of ark-crypto-primitives' ElGamal on ed-on-BLS12-377 as tests/encrypt.rs calls it
   workloads.py     the BASELINE.json circuits; dist.py: one proof / one MSM over several GPUs
 
 There is no CPU fallback anywhere in this package; the CPU oracle lives in oracle/ and is test infrastructure.
 """
 from ._lib import SwmError, load_library, Context  # noqa: F401
+from . import elgamal  # noqa: F401,E402

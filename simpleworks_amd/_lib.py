@@ -124,6 +124,14 @@ ABI = {
     "swm_schnorr_sign": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
     "swm_schnorr_verify": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p, _sz, ctypes.c_void_p]),
     "swm_schnorr_commitments": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_elgamal_create": (_int, [_vp, ctypes.c_void_p, ctypes.POINTER(_vp)]),
+    "swm_elgamal_destroy": (None, [_vp, _vp]),
+    "swm_elgamal_keygen": (_int, [_vp, _vp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_elgamal_key_create": (_int, [_vp, ctypes.c_void_p, ctypes.POINTER(_vp)]),
+    "swm_elgamal_key_destroy": (None, [_vp, _vp]),
+    "swm_elgamal_encrypt": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_elgamal_encrypt_to": (_int, [_vp, _vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_elgamal_decrypt": (_int, [_vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
     "swm_schnorr_circuit_shape": (_int, [_sz, _int, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
     "swm_schnorr_circuit_create": (_int, [_vp, _vp, _sz, ctypes.POINTER(_vp)]),
     "swm_schnorr_circuit_destroy": (None, [_vp, _vp]),
@@ -662,6 +670,66 @@ class Context:
         out = np.empty((pk.shape[0], 64), dtype=np.uint8) if out is None else out
         self._check(self.lib.swm_schnorr_commitments(self.h, handle, pk.ctypes.data, sig.ctypes.data, pk.shape[0], out.ctypes.data),
                     "swm_schnorr_commitments")
+        return out
+
+    # ---- ElGamal encryption (include/swmarlin.h; simpleworks_amd/elgamal.py is the caller-facing mirror)
+    def _elgamal_table(self, create, name, point_xy):
+        g = np.frombuffer(bytes(point_xy), dtype=np.uint8)
+        assert g.size == 64
+        h = _vp()
+        self._check(create(self.h, g.ctypes.data, ctypes.byref(h)), name)
+        return h
+
+    def elgamal_create(self, generator_xy):
+        """generator_xy: 64 bytes (x || y, little-endian standard form)."""
+        return self._elgamal_table(self.lib.swm_elgamal_create, "swm_elgamal_create", generator_xy)
+
+    def elgamal_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_elgamal_destroy(self.h, handle)
+
+    def elgamal_key_create(self, public_key_xy):
+        """One public key (64 bytes) resident with its table: the `key` of elgamal_encrypt_to."""
+        return self._elgamal_table(self.lib.swm_elgamal_key_create, "swm_elgamal_key_create", public_key_xy)
+
+    def elgamal_key_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_elgamal_key_destroy(self.h, handle)
+
+    def elgamal_keygen(self, handle, secret_keys, out=None):
+        """secret_keys: uint8 [count, 32] -> uint8 [count, 64] public keys (x || y)."""
+        sk = self._rows(secret_keys, 32)
+        out = np.empty((sk.shape[0], 64), dtype=np.uint8) if out is None else out
+        self._check(self.lib.swm_elgamal_keygen(self.h, handle, sk.ctypes.data, sk.shape[0], out.ctypes.data), "swm_elgamal_keygen")
+        return out
+
+    def elgamal_encrypt(self, handle, public_keys, messages, randomness, out=None):
+        """public_keys, messages: uint8 [count, 64]; randomness: uint8 [count, 32] -> uint8 [count, 128] ciphertexts (c1 || c2)."""
+        pk = self._rows(public_keys, 64)
+        n = pk.shape[0]
+        m, r = self._rows(messages, 64, n), self._rows(randomness, 32, n)
+        out = np.empty((n, 128), dtype=np.uint8) if out is None else out
+        self._check(self.lib.swm_elgamal_encrypt(self.h, handle, pk.ctypes.data, m.ctypes.data, r.ctypes.data, n, out.ctypes.data),
+                    "swm_elgamal_encrypt")
+        return out
+
+    def elgamal_encrypt_to(self, handle, key_handle, messages, randomness, out=None):
+        """Every message under the one resident key -> uint8 [count, 128]."""
+        m = self._rows(messages, 64)
+        n = m.shape[0]
+        r = self._rows(randomness, 32, n)
+        out = np.empty((n, 128), dtype=np.uint8) if out is None else out
+        self._check(self.lib.swm_elgamal_encrypt_to(self.h, handle, key_handle, m.ctypes.data, r.ctypes.data, n, out.ctypes.data),
+                    "swm_elgamal_encrypt_to")
+        return out
+
+    def elgamal_decrypt(self, secret_keys, ciphertexts, out=None):
+        """secret_keys: uint8 [count, 32]; ciphertexts: uint8 [count, 128] -> uint8 [count, 64] messages."""
+        sk = self._rows(secret_keys, 32)
+        n = sk.shape[0]
+        ct = self._rows(ciphertexts, 128, n)
+        out = np.empty((n, 64), dtype=np.uint8) if out is None else out
+        self._check(self.lib.swm_elgamal_decrypt(self.h, sk.ctypes.data, ct.ctypes.data, n, out.ctypes.data), "swm_elgamal_decrypt")
         return out
 
     # ---- Schnorr verification witness (include/swmarlin.h; simpleworks_amd/schnorr.py, SchnorrCircuit, is the caller-facing mirror)

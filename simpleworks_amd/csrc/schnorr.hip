@@ -8,7 +8,8 @@
 //   :126-160   verify   R' = s G + from_le_bytes_mod_order(e) pk; accept iff Blake2s([salt] || pk || R' || message) == e
 // to_bytes! of an affine point is x || y, 32 little-endian bytes each in standard form [U].
 //
-// On the GPU.  The curve is pedersen.hip's (ed.cuh over ff.cuh's Fr).  s G comes from a table of the generator's window
+// On the GPU.  The curve is pedersen.hip's (ed.cuh over ff.cuh's Fr); the two scalar multiplications are ed_mul.cuh's, shared with
+// elgamal.hip.  s G comes from a table of the generator's window
 // multiples, 32 windows of 8 bits (768 KB, resident in L2): one mixed addition per non-zero byte of s.  e Y is a signed
 // 4-bit-digit ladder over a per-signature table of 1 Y .. 8 Y in cached form: e + 0x0777..7 read nibble by nibble gives the 63
 // digits nibble - 7 in [-7, 8], so there is no carry chain; 4 doublings and at most one addition per digit.  That table is 1 KB
@@ -20,44 +21,14 @@
 // The addition law is complete (ed.cuh): identity, doublings, keys of order 2 and 4 and e = 0 take the common path.
 #include <hip/hip_runtime.h>
 
-#include <vector>
-
 #include "context.h"
-#include "ed.cuh"
-#include "ff.cuh"
-#include "frinv.cuh"
+#include "ed_mul.cuh"
 #include "schnorr.h"
 #include "swmarlin.h"
 
 namespace swm {
 
-// ---------------------------------------------------------------------------------------------- the scalar field
-struct EdScalar {  // l = 2111115437357092606062206234695386632838870926408408195193685246394721360383, little-endian words
-    static constexpr uint32_t L[8] = {0xc33fd9ffu, 0xb95aee9au, 0xc43c8afeu, 0x5293a3afu, 0x970dec00u, 0x982d1347u, 0xa68b2955u, 0x04aad957u};
-};
-// word i of l 2^k, k <= 5 (l < 2^251)
-SWM_HD constexpr uint32_t sc_l_shifted(int i, int k) {
-    return k == 0 ? EdScalar::L[i] : (EdScalar::L[i] << k) | (i ? EdScalar::L[i - 1] >> (32 - k) : 0u);
-}
-// a -= l 2^K when that does not go negative; returns whether it subtracted
-template <int K> SWM_HD bool sc_cond_sub(uint32_t (&a)[8]) {
-    uint32_t d[8], borrow = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        uint64_t t = (uint64_t)a[i] - sc_l_shifted(i, K) - borrow;
-        d[i] = (uint32_t)t;
-        borrow = (uint32_t)(t >> 63);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; i++) a[i] = borrow ? a[i] : d[i];
-    return borrow == 0;
-}
-SWM_HD bool sc_is_canonical(const uint32_t (&a)[8]) {
-    uint32_t t[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) t[i] = a[i];
-    return !sc_cond_sub<0>(t);
-}
+// ---------------------------------------------------------------------------------------------- the scalar field, beyond ed_mul.cuh's canonical test
 // from_le_bytes_mod_order of 32 bytes: a < 2^256 < 55 l, so the quotient has six bits
 SWM_HD void sc_reduce(uint32_t (&a)[8]) {
     sc_cond_sub<5>(a);
@@ -209,139 +180,16 @@ SWM_HD void schnorr_hash(const SchnorrDev& P, const uint32_t (&px)[8], const uin
     }
 }
 
-// ---------------------------------------------------------------------------------------------- points in and out
-SWM_HD void load_words(const uint8_t* p, uint32_t (&w)[8]) {  // p is 4-byte aligned (the staging layout below)
-    const uint32_t* s = reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; i++) w[i] = s[i];
-}
-SWM_HD void store_words(uint8_t* p, const uint32_t (&w)[8]) {
-    uint32_t* d = reinterpret_cast<uint32_t*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; i++) d[i] = w[i];
-}
-SWM_HD bool fr_from_words(const uint32_t (&w)[8], Fr* out) {  // canonical (< r) or refused
-    Fr s, r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        s.v[i] = w[i];
-        r.v[i] = FrParams::P[i];
-    }
-    if (fp_cmp_std(s, r) >= 0) return false;
-    *out = fp_from_std(s);
-    return true;
-}
-// x || y (standard form) -> the point, or false when a coordinate is >= r or -x^2 + y^2 != 1 + d x^2 y^2
-SWM_HD bool schnorr_point(const SchnorrDev& P, const uint32_t (&xs)[8], const uint32_t (&ys)[8], EdExt* out) {
-    Fr x, y;
-    if (!fr_from_words(xs, &x) || !fr_from_words(ys, &y)) return false;
-    Fr x2 = fp_sqr(x), y2 = fp_sqr(y);
-    if (!fp_eq(fp_sub(y2, x2), fp_add(fp_one<Fr>(), fp_mul(P.d, fp_mul(x2, y2))))) return false;
-    out->x = x;
-    out->y = y;
-    out->t = fp_mul(x, y);
-    out->z = fp_one<Fr>();
-    return true;
-}
-SWM_HD void schnorr_affine(const EdExt& p, uint32_t (&xs)[8], uint32_t (&ys)[8]) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const Fr zi = fr_inv_single(p.z);  // Z != 0: the law is complete
-#else
-    const Fr zi = fp_inv(p.z);  // (host: the lane functions of this file also run on a CPU, which is how they were first checked)
-#endif
-    const Fr x = fp_to_std(fp_mul(p.x, zi)), y = fp_to_std(fp_mul(p.y, zi));
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        xs[i] = x.v[i];
-        ys[i] = y.v[i];
-    }
-}
-
-// acc += s G: byte w of s picks row (w, byte) of the table
-SWM_HD void schnorr_fixed_mul(EdExt& acc, const EdRow* table, const uint32_t (&s)[8]) {
-    uint32_t t[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) t[i] = s[i];
-#pragma unroll 1
-    for (unsigned w = 0; w < 32; w++) {
-        const unsigned v = t[0] & 255u;
-#pragma unroll
-        for (int i = 0; i < 7; i++) t[i] = (t[i] >> 8) | (t[i + 1] << 24);
-        t[7] >>= 8;
-        if (v) ed_madd(acc, table[(w << 8) + v]);
-    }
-}
-
-// the per-signature table: entry k (k + 1 times Y, cached form) is 32 words, word j at tab[(32 k + j) stride]
-SWM_HD void cached_store(uint32_t* tab, size_t stride, unsigned k, const EdCached& c) {
-    uint32_t* p = tab + (size_t)32 * k * stride;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        p[(size_t)i * stride] = c.ymx.v[i];
-        p[(size_t)(8 + i) * stride] = c.ypx.v[i];
-        p[(size_t)(16 + i) * stride] = c.kt.v[i];
-        p[(size_t)(24 + i) * stride] = c.z2.v[i];
-    }
-}
-SWM_HD EdCached cached_load(const uint32_t* tab, size_t stride, unsigned k) {
-    const uint32_t* p = tab + (size_t)32 * k * stride;
-    EdCached c;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        c.ymx.v[i] = p[(size_t)i * stride];
-        c.ypx.v[i] = p[(size_t)(8 + i) * stride];
-        c.kt.v[i] = p[(size_t)(16 + i) * stride];
-        c.z2.v[i] = p[(size_t)(24 + i) * stride];
-    }
-    return c;
-}
-
-// s G + e Y (schnorr.rs:140-143), e < l.  `tab` is this lane's column of the table buffer.
+// s G + e Y (schnorr.rs:140-143), e < l: the ladder, then the table walk.  `tab` is this lane's column of the table buffer.
 SWM_HD EdExt schnorr_commitment(const SchnorrDev& P, const EdExt& Y, const uint32_t (&s)[8], const uint32_t (&e)[8], uint32_t* tab,
                                 size_t stride) {
-    const EdCached c1 = ed_to_cached(Y, P.k2d);
-    cached_store(tab, stride, 0, c1);
-    EdExt run = Y;
-#pragma unroll 1
-    for (unsigned k = 1; k < 8; k++) {
-        ed_add_cached(run, c1);
-        cached_store(tab, stride, k, ed_to_cached(run, P.k2d));
-    }
-    // e + 0x0777..7 < 2^251 + 2^251: 63 nibbles, nibble i - 7 = digit i in [-7, 8], sum of digit i 16^i = e
-    uint32_t d[8], carry = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        uint64_t t = (uint64_t)e[i] + (i == 7 ? 0x07777777u : 0x77777777u) + carry;
-        d[i] = (uint32_t)t;
-        carry = (uint32_t)(t >> 32);
-    }
-#pragma unroll
-    for (int i = 7; i > 0; i--) d[i] = (d[i] << 4) | (d[i - 1] >> 28);  // nibble 63 is zero: start at nibble 62
-    d[0] <<= 4;
-    EdExt acc = ed_identity();
-#pragma unroll 1
-    for (int i = 0; i < 63; i++) {
-        if (i) {
-#pragma unroll 1
-            for (int j = 0; j < 4; j++) ed_dbl(acc);
-        }
-        const int dg = (int)(d[7] >> 28) - 7;
-#pragma unroll
-        for (int k = 7; k > 0; k--) d[k] = (d[k] << 4) | (d[k - 1] >> 28);
-        d[0] <<= 4;
-        if (dg) {
-            EdCached c = cached_load(tab, stride, (unsigned)(dg < 0 ? -dg : dg) - 1u);
-            if (dg < 0) c = ed_cached_neg(c);
-            ed_add_cached(acc, c);
-        }
-    }
-    schnorr_fixed_mul(acc, P.table, s);
+    EdExt acc = ed_ladder_mul(Y, e, P.k2d, tab, stride);
+    ed_fixed_mul(acc, P.table, s);
     return acc;
 }
 
 // ---------------------------------------------------------------------------------------------- kernels: one lane per item
-// A refused input lowers *bad to the smallest refused index (0xffffffff: none); the host then returns without copying anything out.
-__device__ __forceinline__ void refuse(unsigned* bad, size_t i) { atomicMin(bad, (unsigned)(i < 0xfffffffeu ? i : 0xfffffffeu)); }
+// A refused input lowers *bad (refuse, ed_mul.cuh); the host then returns without copying anything out.
 
 __global__ void __launch_bounds__(256) schnorr_keygen_kernel(SchnorrDev P, const uint8_t* __restrict__ secrets, size_t count,
                                                              uint8_t* __restrict__ out, unsigned* __restrict__ bad) {
@@ -351,8 +199,8 @@ __global__ void __launch_bounds__(256) schnorr_keygen_kernel(SchnorrDev P, const
     load_words(secrets + 32 * i, x);
     if (!sc_is_canonical(x)) return refuse(bad, i);
     EdExt acc = ed_identity();
-    schnorr_fixed_mul(acc, P.table, x);
-    schnorr_affine(acc, px, py);
+    ed_fixed_mul(acc, P.table, x);
+    ed_affine(acc, px, py);
     store_words(out + 64 * i, px);
     store_words(out + 64 * i + 32, py);
 }
@@ -368,10 +216,10 @@ __global__ void __launch_bounds__(256) schnorr_sign_kernel(SchnorrDev P, const u
     load_words(pks + 64 * i, px);
     load_words(pks + 64 * i + 32, py);
     EdExt Y;
-    if (!sc_is_canonical(x) || !sc_is_canonical(k) || !schnorr_point(P, px, py, &Y)) return refuse(bad, i);
+    if (!sc_is_canonical(x) || !sc_is_canonical(k) || !ed_point_from_words(P.d, px, py, &Y)) return refuse(bad, i);
     EdExt acc = ed_identity();
-    schnorr_fixed_mul(acc, P.table, k);
-    schnorr_affine(acc, rx, ry);
+    ed_fixed_mul(acc, P.table, k);
+    ed_affine(acc, rx, ry);
     schnorr_hash(P, px, py, rx, ry, msgs + i * msg_len, msg_len, h);
 #pragma unroll
     for (int j = 0; j < 8; j++) e[j] = h[j];
@@ -397,7 +245,7 @@ __global__ void __launch_bounds__(256) schnorr_verify_kernel(SchnorrDev P, const
     load_words(sigs + 64 * i, s);
     load_words(sigs + 64 * i + 32, c);
     EdExt Y;
-    if (!sc_is_canonical(s) || !schnorr_point(P, px, py, &Y)) {
+    if (!sc_is_canonical(s) || !ed_point_from_words(P.d, px, py, &Y)) {
         if (COMMIT)
             refuse(bad, i);
         else
@@ -408,7 +256,7 @@ __global__ void __launch_bounds__(256) schnorr_verify_kernel(SchnorrDev P, const
     for (int w = 0; w < 8; w++) e[w] = c[w];
     sc_reduce(e);
     const EdExt acc = schnorr_commitment(P, Y, s, e, tab + j, stride);
-    schnorr_affine(acc, rx, ry);
+    ed_affine(acc, rx, ry);
     if (COMMIT) {
         store_words(out + 64 * i, rx);
         store_words(out + 64 * i + 32, ry);
@@ -427,8 +275,7 @@ using namespace swm;
 
 namespace {
 
-constexpr unsigned SCH_WINDOWS = 32, SCH_ROWS = 256;
-constexpr size_t SCH_CHUNK = (size_t)1 << 18;  // signatures per verify launch: bounds the table buffer at 256 MB
+constexpr size_t SCH_CHUNK = ED_LADDER_CHUNK;  // signatures per verify launch
 
 SchnorrDev dev_params(const swm_schnorr* p) {
     SchnorrDev d;
@@ -472,7 +319,7 @@ int schnorr_run(swm_ctx* ctx, const swm_schnorr* p, SchnorrOp op, const uint8_t*
         const size_t lanes = count < SCH_CHUNK ? count : SCH_CHUNK;
         const size_t stride = (lanes + 63) & ~(size_t)63;
         uint32_t* d_tab = nullptr;
-        SWM_TRY(scratch(ctx, "schnorr.tab", (size_t)8 * 32 * sizeof(uint32_t) * stride, (void**)&d_tab));
+        SWM_TRY(scratch(ctx, "schnorr.tab", ED_LADDER_TABLE_WORDS * sizeof(uint32_t) * stride, (void**)&d_tab));
         for (size_t base = 0; base < count; base += SCH_CHUNK) {
             const size_t n = count - base < SCH_CHUNK ? count - base : SCH_CHUNK;
             const dim3 grid((unsigned)((n + 255) / 256));
@@ -495,10 +342,6 @@ int schnorr_run(swm_ctx* ctx, const swm_schnorr* p, SchnorrOp op, const uint8_t*
     return SWM_OK;
 }
 
-void words_from_bytes(const uint8_t* b, uint32_t (&w)[8]) {
-    for (int i = 0; i < 8; i++) w[i] = (uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 | (uint32_t)b[4 * i + 3] << 24;
-}
-
 }  // namespace
 
 extern "C" {
@@ -516,32 +359,14 @@ int swm_schnorr_create(swm_ctx* ctx, const uint8_t generator_xy[64], const uint8
     words_from_bytes(generator_xy, gx);
     words_from_bytes(generator_xy + 32, gy);
     EdExt base;
-    if (!schnorr_point(P, gx, gy, &base)) {
+    if (!ed_point_from_words(P.d, gx, gy, &base)) {
         delete p;
         return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_create: the generator is not a point of ed-on-BLS12-377");
     }
-    std::vector<EdRow> rows((size_t)SCH_WINDOWS * SCH_ROWS);
-    for (unsigned w = 0; w < SCH_WINDOWS; w++) {  // base = 2^(8 w) G
-        EdExt acc = ed_identity();
-        for (unsigned v = 0; v < SCH_ROWS; v++) {  // acc = v base
-            const Fr zi = fp_inv(acc.z);
-            const Fr x = fp_mul(acc.x, zi), y = fp_mul(acc.y, zi);
-            EdRow& r = rows[(size_t)w * SCH_ROWS + v];
-            r.ymx = fp_sub(y, x);
-            r.ypx = fp_add(y, x);
-            r.kt = fp_mul(P.k2d, fp_mul(x, y));
-            acc = ed_add(acc, base, P.k2d);
-        }
-        base = acc;  // 256 base
-    }
-    hipError_t e = hipMalloc(&p->d_table, rows.size() * sizeof(EdRow));
-    if (e == hipSuccess) e = hipMemcpyAsync(p->d_table, rows.data(), rows.size() * sizeof(EdRow), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // `rows` goes out of scope
-    if (e != hipSuccess) {
-        if (p->d_table) (void)hipFree(p->d_table);
+    const int rc = ed_window_table_upload(ctx, base, P.k2d, &p->d_table, "schnorr_create");
+    if (rc != SWM_OK) {
         delete p;
-        (void)hipGetLastError();
-        return set_err(ctx, e == hipErrorOutOfMemory ? SWM_ERR_OOM : SWM_ERR_HIP, "schnorr_create: %s", hipGetErrorString(e));
+        return rc;
     }
     *out = p;
     return SWM_OK;

@@ -1,0 +1,137 @@
+"""ElGamal encryption on ed-on-BLS12-377, computed on the GPU (csrc/elgamal.hip through include/swmarlin.h).
+
+Caller-facing mirror of what the reference reaches through ark-crypto-primitives 0.3 (encryption/elgamal/mod.rs [U],
+ElGamal<EdwardsProjective>, as tests/encrypt.rs:11-28 calls it), name for name:
+    setup(rng)                          -> Parameters { generator = C::rand(rng) }
+    keygen(params, rng)                 -> (PublicKey, SecretKey(ScalarField::rand(rng)))
+    Randomness::rand(rng)               -> rand_randomness(rng);   JubJub::rand(rng) -> rand_plaintext(rng)
+    encrypt(params, pk, message, r)     -> Ciphertext (c1, c2) = (r G, message + r pk)
+    decrypt(params, sk, ciphertext)     -> message = c2 - sk c1
+plus keygen_many / encrypt_many / decrypt_many, the batched forms: one GPU lane per key, encryption or decryption.  A caller with
+many messages for one recipient hands encrypt_many a ResidentKey: the key is tabulated once on the GPU and every encryption is
+two table walks instead of a 252-doubling ladder.
+
+Host side (this file): the random draws and the bookkeeping.  A point is drawn the way ark-ec samples a twisted Edwards point
+(hash.ed_rand), a scalar the way ark-ff's UniformRand does (schnorr.rand_scalar) [U].  Plaintext = PublicKey = an affine point
+(x, y); every curve operation runs on the GPU; there is no CPU evaluation path here.
+"""
+import numpy as np
+
+from .hash import ed_rand
+from .marlin import default_context
+from .schnorr import GROUP_ORDER, point_bytes, point_from_bytes, rand_scalar  # noqa: F401  (the wire forms are Schnorr's)
+
+
+class Parameters:
+    """elgamal::Parameters { generator } with the generator's table resident on the GPU."""
+
+    def __init__(self, generator, ctx=None):
+        self.ctx = ctx or default_context()
+        self.generator = generator
+        self.h = self.ctx.elgamal_create(point_bytes(generator))
+
+    def free(self):
+        if self.h:
+            self.ctx.elgamal_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ResidentKey:
+    """One recipient's public key resident on the GPU with its table (swm_elgamal_key): what encrypt_many takes in place of a
+    key array when every message goes to the same recipient."""
+
+    def __init__(self, pk, ctx=None):
+        self.ctx = ctx or default_context()
+        self.pk = pk
+        self.h = self.ctx.elgamal_key_create(point_bytes(pk))
+
+    def free(self):
+        if self.h:
+            self.ctx.elgamal_key_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class SecretKey:
+    """elgamal::SecretKey(pub ScalarField)."""
+
+    def __init__(self, secret_key):
+        self.secret_key = secret_key
+
+
+def _scalars(values):
+    return np.frombuffer(b"".join(v.to_bytes(32, "little") for v in values), dtype=np.uint8).reshape(len(values), 32)
+
+
+def _points(points):
+    return np.frombuffer(b"".join(point_bytes(p) for p in points), dtype=np.uint8).reshape(len(points), 64)
+
+
+def setup(rng, ctx=None):
+    """AsymmetricEncryptionScheme::setup: the generator is one draw of C::rand."""
+    return Parameters(ed_rand(rng), ctx)
+
+
+def rand_randomness(rng):
+    """Randomness::rand(rng): one scalar."""
+    return rand_scalar(rng)
+
+
+def rand_plaintext(rng):
+    """JubJub::rand(rng).into(): a random point of the prime subgroup."""
+    return ed_rand(rng)
+
+
+def keygen_many(params, rng, count):
+    """count keys -> (public keys uint8 [count, 64], secret keys uint8 [count, 32]); one draw per key."""
+    sk = _scalars([rand_scalar(rng) for _ in range(count)])
+    return params.ctx.elgamal_keygen(params.h, sk), sk
+
+
+def encrypt_many(params, pks, messages, rs):
+    """One ciphertext per (public key, message, randomness) -> uint8 [count, 128] (c1.x || c1.y || c2.x || c2.y).
+    messages uint8 [count, 64], rs uint8 [count, 32]; pks uint8 [count, 64], or a ResidentKey under which every message is
+    encrypted."""
+    m = np.ascontiguousarray(messages, dtype=np.uint8).reshape(-1, 64)
+    r = np.ascontiguousarray(rs, dtype=np.uint8).reshape(-1, 32)
+    if isinstance(pks, ResidentKey):
+        return params.ctx.elgamal_encrypt_to(params.h, pks.h, m, r)
+    return params.ctx.elgamal_encrypt(params.h, np.ascontiguousarray(pks, dtype=np.uint8).reshape(-1, 64), m, r)
+
+
+def decrypt_many(params, sks, ciphertexts):
+    """-> uint8 [count, 64] messages.  ciphertexts uint8 [count, 128]; sks uint8 [count, 32], or one secret key (32 bytes, a
+    SecretKey or an int) for the whole batch."""
+    ct = np.ascontiguousarray(ciphertexts, dtype=np.uint8).reshape(-1, 128)
+    if isinstance(sks, SecretKey):
+        sks = sks.secret_key
+    sk = _scalars([sks]) if isinstance(sks, int) else np.ascontiguousarray(sks, dtype=np.uint8).reshape(-1, 32)
+    if sk.shape[0] == 1 and ct.shape[0] != 1:
+        sk = np.ascontiguousarray(np.broadcast_to(sk, (ct.shape[0], 32)))
+    return params.ctx.elgamal_decrypt(sk, ct)
+
+
+def keygen(params, rng):
+    pk, sk = keygen_many(params, rng, 1)
+    return point_from_bytes(pk[0].tobytes()), SecretKey(int.from_bytes(sk[0].tobytes(), "little"))
+
+
+def encrypt(params, pk, message, r):
+    ct = encrypt_many(params, _points([pk]), _points([message]), _scalars([r]))[0].tobytes()
+    return point_from_bytes(ct[:64]), point_from_bytes(ct[64:])
+
+
+def decrypt(params, sk, ciphertext):
+    ct = np.frombuffer(point_bytes(ciphertext[0]) + point_bytes(ciphertext[1]), dtype=np.uint8)
+    return point_from_bytes(decrypt_many(params, sk, ct)[0].tobytes())
