@@ -630,6 +630,45 @@ int swm_poseidon_witness_dev(swm_ctx *ctx, const swm_poseidon_circuit *circuit, 
 int swm_poseidon_prove(swm_ctx *ctx, const swm_pk *pk, const swm_poseidon_circuit *circuit, const uint8_t *input, swm_rng *rng,
                        unsigned flags, uint8_t *outputs, uint8_t *proof_out, size_t cap, size_t *len);
 
+/* ---------------------------------------------------------------------------------------------- Blake2s random oracle
+ * The reference's random oracle, unkeyed BLAKE2s-256 (RFC 7693), batched: one GPU lane per hash.  Replaces, on the GPU,
+ *   src/schnorr_signature/blake2s.rs, examples/simple-payments/random_oracle/blake2s/mod.rs      RO::evaluate(&(), input)
+ * (RO::setup returns the unit: there are no parameters and no handle.)
+ * swm_blake2s_hash: `count` inputs of input_len bytes each (0 <= input_len <= 65536), back to back; digests: count x 32 bytes.  With
+ * input_len = 0 `inputs` may be NULL.  SWM_ERR_INVALID_ARG: input_len > 65536, a NULL output.  count = 0 returns SWM_OK and launches
+ * nothing.
+ * swm_blake2s_hash_dev: the same on device buffers, both bases 4-byte aligned.  Item i starts at byte i x input_len, word-aligned or
+ * not: the kernel reads it correctly either way and touches no byte past count x input_len. */
+int swm_blake2s_hash(swm_ctx *ctx, const uint8_t *inputs, size_t input_len, size_t count, uint8_t *digests);
+int swm_blake2s_hash_dev(swm_ctx *ctx, const void *d_inputs, size_t input_len, size_t count, void *d_digests);
+
+/* ---------------------------------------------------------------------------------------------- Blake2s hash witness
+ * The assignment of the Blake2s hash circuit (the gadget of examples/simple-payments/random_oracle/blake2s/constraints.rs as this
+ * library lays it out: simpleworks_amd/workloads.py, build_blake2s_hash) synthesised on the GPU, one workgroup per item, without
+ * running the constraint synthesizer on the host.  The statement: "I know input_len bytes whose Blake2s digest is the public
+ * digest".  The digest is public as two field elements (the reference's unit test publishes nothing instead): the instance is
+ * one, lo, hi with lo = digest bytes 0 .. 15 and hi = bytes 16 .. 31 as little-endian integers, both below 2^128.  Witnesses: 8
+ * input_len input bits (byte-major, least significant first), then per 64-byte block the 21 472 bits of the Schnorr circuit's
+ * Blake2s block (80 G functions of 262, 16 words of the feed-forward); the digest bits are the second xor of the last block's
+ * feed-forward.  With B = max(1, ceil(input_len / 64)):
+ *   num_instance = 3;  num_witness = 8 input_len + 21472 B;  num_constraints = 8 input_len + 21792 B + 2.
+ * Nothing is folded into constants: the shape depends on input_len alone, and there is no handle.
+ * swm_blake2s_circuit_shape needs no GPU.  SWM_ERR_INVALID_ARG: input_len > 65536, a NULL output.
+ * swm_blake2s_witness: `count` items in one launch.  inputs: count x input_len bytes; may be NULL when input_len = 0.  witness:
+ * count x num_witness x 4 Montgomery limbs, in the circuit's variable order; digests (may be NULL): count x 32 bytes.  Every byte
+ * string is a valid input: no item is refused.  A batch whose witnesses exceed 1 GiB is staged through the device in chunks of
+ * floor(1 GiB / (32 num_witness)) items (at least one).  count = 0 launches nothing.
+ * swm_blake2s_witness_dev: the same on device buffers (witness 16-byte aligned; inputs and digests 4-byte aligned, items back to
+ * back as for swm_blake2s_hash_dev), no chunking.
+ * swm_blake2s_prove: witness on the device, then the proof of swm_generate_proof_ex(flags) with (lo, hi) as the public input; the
+ * witness reaches the prover by a device-to-device copy.  digest_out: the 32 bytes the verifier derives (lo, hi) from.  There is
+ * no unsatisfied case: the library computes the digest it proves.  A key indexed for another input_len is SWM_ERR_MISMATCH. */
+int swm_blake2s_circuit_shape(size_t input_len, size_t *num_instance, size_t *num_witness, size_t *num_constraints);
+int swm_blake2s_witness(swm_ctx *ctx, const uint8_t *inputs, size_t input_len, size_t count, uint64_t *witness, uint8_t *digests);
+int swm_blake2s_witness_dev(swm_ctx *ctx, const void *d_inputs, size_t input_len, size_t count, void *d_witness, void *d_digests);
+int swm_blake2s_prove(swm_ctx *ctx, const swm_pk *pk, const uint8_t *input, size_t input_len, swm_rng *rng, unsigned flags,
+                      uint8_t digest_out[32], uint8_t *proof_out, size_t cap, size_t *len);
+
 /* ---------------------------------------------------------------------------------------------- one proof over several GPUs
  * every commitment MSM of swm_generate_proof / swm_generate_proving_and_verifying_keys is split by
  * point range — rank g of `world` takes coefficients and SRS powers [g n / world, (g+1) n / world) — and the

@@ -8,9 +8,11 @@ Layout (only what the path needs):
   serialization.py mirror of src/marlin/serialization.rs
   hash.py          mirror of src/hash/mod.rs (Pedersen CRH) and the MerkleTree calls; schnorr.py: mirror of src/schnorr_signature/schnorr.rs
   elgamal.py       mirror of ark-crypto-primitives' ElGamal on ed-on-BLS12-377 as tests/encrypt.rs calls it
+  random_oracle.py mirror of the Blake2s random oracle (src/schnorr_signature/blake2s.rs) and its circuit's witness
   workloads.py     the BASELINE.json circuits; dist.py: one proof / one MSM over several GPUs
 
 There is no CPU fallback anywhere in this package; the CPU oracle lives in oracle/ and is test infrastructure.
 """
 from ._lib import SwmError, load_library, Context  # noqa: F401
 from . import elgamal  # noqa: F401,E402
+from . import random_oracle  # noqa: F401,E402

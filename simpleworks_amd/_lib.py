@@ -154,6 +154,13 @@ ABI = {
     "swm_poseidon_witness_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "swm_poseidon_prove": (_int, [_vp, _vp, _vp, ctypes.c_void_p, _vp, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, _sz,
                                   ctypes.POINTER(_sz)]),
+    "swm_blake2s_hash": (_int, [_vp, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
+    "swm_blake2s_hash_dev": (_int, [_vp, _vp, _sz, _sz, _vp]),
+    "swm_blake2s_circuit_shape": (_int, [_sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "swm_blake2s_witness": (_int, [_vp, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_blake2s_witness_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "swm_blake2s_prove": (_int, [_vp, _vp, ctypes.c_void_p, _sz, _vp, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, _sz,
+                                 ctypes.POINTER(_sz)]),
     "swm_profile_enable": (_int, [_vp, _int]),
     "swm_profile_reset": (_int, [_vp]),
     "swm_profile_json": (_int, [_vp, ctypes.c_char_p, _sz]),
@@ -827,6 +834,39 @@ class Context:
         self._check(self.lib.swm_poseidon_witness_dev(self.h, handle, d_inputs.ptr if d_inputs else None, count,
                                                       d_witness.ptr if d_witness else None, d_outputs.ptr if d_outputs else None,
                                                       d_status.ptr if d_status else None), "swm_poseidon_witness_dev")
+
+    # ---- Blake2s random oracle and its circuit's witness (include/swmarlin.h; simpleworks_amd/random_oracle.py is the caller-facing
+    # mirror).  A device buffer is a DeviceBuffer or a raw device address (an int: a tensor's data_ptr()).
+    @staticmethod
+    def _dev_ptr(buf):
+        return None if buf is None else buf if isinstance(buf, int) else buf.ptr
+
+    def blake2s_hash(self, inputs):
+        """inputs: uint8 [count, input_len] (input_len may be 0) -> uint8 [count, 32] digests."""
+        a = np.ascontiguousarray(inputs, dtype=np.uint8)
+        assert a.ndim == 2
+        out = np.zeros((a.shape[0], 32), dtype=np.uint8)
+        self._check(self.lib.swm_blake2s_hash(self.h, a.ctypes.data if a.size else None, a.shape[1], a.shape[0], out.ctypes.data),
+                    "swm_blake2s_hash")
+        return out
+
+    def blake2s_hash_dev(self, d_inputs, input_len, count, d_digests):
+        self._check(self.lib.swm_blake2s_hash_dev(self.h, self._dev_ptr(d_inputs), input_len, count, self._dev_ptr(d_digests)),
+                    "swm_blake2s_hash_dev")
+
+    def blake2s_witness(self, num_witness, inputs):
+        """inputs: uint8 [count, input_len] -> (witness uint64 [count, num_witness, 4] Montgomery limbs, digests uint8 [count, 32])."""
+        a = np.ascontiguousarray(inputs, dtype=np.uint8)
+        assert a.ndim == 2
+        witness = np.zeros((a.shape[0], num_witness, 4), dtype=np.uint64)
+        digests = np.zeros((a.shape[0], 32), dtype=np.uint8)
+        self._check(self.lib.swm_blake2s_witness(self.h, a.ctypes.data if a.size else None, a.shape[1], a.shape[0], witness.ctypes.data,
+                                                 digests.ctypes.data), "swm_blake2s_witness")
+        return witness, digests
+
+    def blake2s_witness_dev(self, d_inputs, input_len, count, d_witness, d_digests=None):
+        self._check(self.lib.swm_blake2s_witness_dev(self.h, self._dev_ptr(d_inputs), input_len, count, self._dev_ptr(d_witness),
+                                                     self._dev_ptr(d_digests)), "swm_blake2s_witness_dev")
 
     # ---- measurement
     def profile_enable(self, on=True):

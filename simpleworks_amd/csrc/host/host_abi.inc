@@ -9,6 +9,7 @@
 #include "merkle_shape.h"
 #include "schnorr_shape.h"
 #include "poseidon_shape.h"
+#include "blake2s_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
 extern "C" {
@@ -242,6 +243,20 @@ int swm_poseidon_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64
                        "rounds, alpha 2 .. %llu, at most %zu bytes and one output or %zu elements and 1 .. %zu outputs)",
                        full_rounds, partial_rounds, (unsigned long long)alpha, n_in, bytes_form ? "bytes" : "elements", n_out,
                        (size_t)PC_MAX_ROUNDS, (unsigned long long)PC_MAX_ALPHA, (size_t)PC_MAX_BYTES, (size_t)PC_MAX_IN, (size_t)PC_MAX_OUT);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// The Blake2s hash circuit's shape from the input length (blake2s_shape.h; the layout is build_blake2s_hash's)
+int swm_blake2s_circuit_shape(size_t input_len, size_t* num_instance, size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "blake2s_circuit_shape: NULL output");
+    Blake2sShape s;
+    if (!blake2s_shape(input_len, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG, "blake2s_circuit_shape: input_len %zu (at most %zu)", input_len, (size_t)BH_MAX_INPUT_LEN);
     *num_instance = s.num_instance;
     *num_witness = s.num_witness;
     *num_constraints = s.num_constraints;

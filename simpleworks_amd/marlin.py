@@ -513,6 +513,30 @@ def generate_poseidon_proof(proving_key, circuit, data_or_elements, rng, uncompr
     return bytes(buf[: n.value]), [int.from_bytes(out[32 * j:32 * j + 32], "little") for j in range(circuit.n_out)]
 
 
+def blake2s_circuit_shape(input_len):
+    """swm_blake2s_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the Blake2s hash circuit over input_len
+    bytes — what workloads.build_blake2s_hash emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_blake2s_circuit_shape(input_len, ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)),
+           "swm_blake2s_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_blake2s_proof(proving_key, input, rng, uncompressed=False):
+    """swm_blake2s_prove: the proof of workloads.Blake2sHashCircuit with the circuit's witness synthesised on the GPU and handed to
+    the prover on the device.  input: the preimage bytes (the key must be indexed for their length).  Returns (proof bytes,
+    digest): verify with workloads.blake2s_public_inputs(digest)."""
+    ctx = proving_key.ctx
+    raw = bytes(input)
+    in_b = (ctypes.c_uint8 * max(1, len(raw))).from_buffer_copy(raw.ljust(1, b"\0"))
+    out_b = (ctypes.c_uint8 * 32)()
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    _check(ctx.lib.swm_blake2s_prove(ctx.h, proving_key.h, in_b, len(raw), rng.h, 1 if uncompressed else 0, out_b, buf, len(buf),
+                                     ctypes.byref(n)), "swm_blake2s_prove", ctx)
+    return bytes(buf[: n.value]), bytes(out_b)
+
+
 def verify_proof(verifying_key, public_inputs, proof, rng):
     """src/marlin/mod.rs:79-86.  public_inputs: field elements as ints (e.g. the bit-expanded inputs of
     src/merkle_tree/simple_merkle_tree.rs:129-143)."""

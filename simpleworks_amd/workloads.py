@@ -1162,3 +1162,85 @@ class PoseidonHashCircuit:
 
     def generate_constraints(self, cs):
         build_poseidon_hash(cs, self.params, self.data, self.elements, self.n_out)
+
+
+# ===================================================================================================================
+# The reference's random oracle as a circuit of its own: Blake2s over a witness byte string (src/schnorr_signature/blake2s.rs
+# and examples/simple-payments/random_oracle/blake2s/{mod,constraints}.rs — RO::evaluate natively, ROGadget::evaluate over
+# evaluate_blake2s in the gadget; the second file's unit test hashes [1u8; 32] both ways, compares the 32 bytes and asks
+# cs.is_satisfied()).  The statement is "I know input_len bytes whose Blake2s digest is the public digest".  The reference's
+# unit test publishes nothing; as with the Poseidon circuit the digest is public here, because a hash proof with no public
+# digest states nothing.  The hash rows are _sv_blake2s's, unchanged: build_blake2s_hash is the layout contract of
+# csrc/host/blake2s_shape.h and csrc/blake2s_witness.hip.
+#
+# Variable order (blake2s_circuit_layout gives the offsets), B = max(1, ceil(input_len / 64)) blocks:
+#   instance  one, lo, hi: digest bytes 0 .. 15 and 16 .. 31 as little-endian integers (words 0 .. 3 and 4 .. 7), both below
+#             2^128 and so canonical
+#   bits      8 input_len booleans, byte-major, least significant first, a booleanity row each      8 input_len,  8 input_len
+#   b2s       per 64-byte block 80 G functions of 262 witnesses / 266 rows, then 16 xors of the feed-forward  21472 B,  21792 B
+#   pack      (sum 2^j d_j - lo) * one = 0 over the 128 low digest bits, the same for hi                0,          2
+# The digest bits are the second xor of the last block's feed-forward.  NO CONSTANT FOLDING: the IV, the counter, the
+# finalisation flag and the zero padding enter as multiples of `one` (see the Schnorr block comment): the shape depends on
+# input_len alone.
+# ===================================================================================================================
+BLAKE2S_MAX_INPUT_LEN = 65536
+
+
+def blake2s_circuit_layout(input_len):
+    """Offsets of the witness groups of build_blake2s_hash and its three counts, as csrc/host/blake2s_shape.h states them."""
+    if not 0 <= input_len <= BLAKE2S_MAX_INPUT_LEN:
+        raise ValueError("input_len %d (0 .. %d)" % (input_len, BLAKE2S_MAX_INPUT_LEN))
+    blocks = max(1, (input_len + 63) // 64)
+    lay = {"bits": 0, "b2s": 8 * input_len, "blocks": blocks}
+    lay["num_instance"] = 3
+    lay["num_witness"] = lay["b2s"] + SV_BLOCK_WITNESSES * blocks
+    lay["num_constraints"] = 8 * input_len + SV_BLOCK_ROWS * blocks + 2
+    # digest word i: the second xor of the last block's feed-forward (64 witnesses per word: the first xor, then the second)
+    lay["digest"] = lay["b2s"] + SV_BLOCK_WITNESSES * (blocks - 1) + 80 * SV_G_WITNESSES + 32
+    return lay
+
+
+def blake2s_public_inputs(digest):
+    """The two public inputs of the Blake2s hash circuit for a 32-byte digest: [lo, hi]."""
+    digest = bytes(digest)
+    if len(digest) != 32:
+        raise ValueError("a Blake2s digest is 32 bytes")
+    return [int.from_bytes(digest[:16], "little"), int.from_bytes(digest[16:], "little")]
+
+
+def build_blake2s_hash(cs, data):
+    """Emits the Blake2s hash circuit into `cs` (builder vocabulary as build_schnorr_verification).  data: 0 .. 65536 bytes.
+    The digest halves are the public inputs, allocated after `one`; returns them as [lo, hi].  Every value is computed by the
+    builder: there is no unsatisfied honest case."""
+    data = bytes(data)
+    if len(data) > BLAKE2S_MAX_INPUT_LEN:
+        raise ValueError("blake2s circuit: at most %d input bytes" % BLAKE2S_MAX_INPUT_LEN)
+    one = cs.one()
+    bits = [_boolean_witness(cs, one, (byte >> i) & 1) for byte in data for i in range(8)]
+    digest = _sv_blake2s(cs, one, bits, len(data))
+    digest_bits = [b for word in digest for b in word]
+    public = []
+    for half in (digest_bits[:128], digest_bits[128:]):
+        packed = _sv_pack(half)
+        out = cs.new_input_variable(packed.value)
+        cs.enforce_constraint(packed.minus(_LC([(1, out)], packed.value)).terms, [(1, one)], [])
+        public.append(packed.value)
+    return public
+
+
+def blake2s_hash_circuit(data):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs) with public_inputs = [lo, hi]."""
+    cs = ConstraintSystem()
+    public = build_blake2s_hash(cs, data)
+    return cs, public
+
+
+class Blake2sHashCircuit:
+    """The ConstraintSynthesizer of the Blake2s preimage statement for MarlinInst.index / prove: witness = the input bytes,
+    public input = the two halves of the digest."""
+
+    def __init__(self, data):
+        self.data = bytes(data)
+
+    def generate_constraints(self, cs):
+        build_blake2s_hash(cs, self.data)

@@ -238,4 +238,16 @@ extern "C" {
     pub fn swm_poseidon_prove(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_poseidon_circuit, input: *const u8,
                               rng: *mut swm_rng, flags: c_uint, outputs: *mut u8, proof_out: *mut u8, cap: usize,
                               len: *mut usize) -> c_int;
+    // the Blake2s random oracle, batched, and its circuit's witness (no handle: the shape follows from input_len)
+    pub fn swm_blake2s_hash(ctx: *mut swm_ctx, inputs: *const u8, input_len: usize, count: usize, digests: *mut u8) -> c_int;
+    pub fn swm_blake2s_hash_dev(ctx: *mut swm_ctx, d_inputs: *const c_void, input_len: usize, count: usize,
+                                d_digests: *mut c_void) -> c_int;
+    pub fn swm_blake2s_circuit_shape(input_len: usize, num_instance: *mut usize, num_witness: *mut usize,
+                                     num_constraints: *mut usize) -> c_int;
+    pub fn swm_blake2s_witness(ctx: *mut swm_ctx, inputs: *const u8, input_len: usize, count: usize, witness: *mut u64,
+                               digests: *mut u8) -> c_int;
+    pub fn swm_blake2s_witness_dev(ctx: *mut swm_ctx, d_inputs: *const c_void, input_len: usize, count: usize,
+                                   d_witness: *mut c_void, d_digests: *mut c_void) -> c_int;
+    pub fn swm_blake2s_prove(ctx: *mut swm_ctx, pk: *const swm_pk, input: *const u8, input_len: usize, rng: *mut swm_rng,
+                             flags: c_uint, digest_out: *mut u8, proof_out: *mut u8, cap: usize, len: *mut usize) -> c_int;
 }

@@ -1,0 +1,286 @@
+"""The Blake2s random oracle on the GPU (csrc/blake2s.hip: swm_blake2s_hash, swm_blake2s_hash_dev) against hashlib, and its circuit's
+witness (csrc/blake2s_witness.hip: swm_blake2s_witness, swm_blake2s_witness_dev, swm_blake2s_prove) against its specification,
+workloads.build_blake2s_hash run on the CPU: exact equality of the whole witness vector in Montgomery limbs and of the digests, and
+generate_blake2s_proof against generate_proof on the builder's system, byte for byte.
+Items lie back to back, so an odd length leaves every second item off a word boundary: that is where the kernels' reader can go
+wrong, and the lengths below are chosen for it.  The builder costs about a tenth of a second per 64-byte block, so whole-witness
+equality is affordable at one to three blocks."""
+import hashlib
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+R = 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001
+KNOWN = ((b"abc", "508c5e8c327c14e2e1a72ba34eeb452f37458b209ed63a294d999b4c86675982"),          # RFC 7693, appendix B
+         (bytes([1] * 32), "5da8bcf5e934a097c5a5a62fa8dd942da80501ee8de6df858499c6181325e369"),  # the reference's unit test
+         (b"", "69217a3079908094e11121d042354a7c1f55b6482ca1a51e1b250dfd1ed0eef9"))
+
+
+class _WitnessOnly:
+    """The builder's vocabulary, keeping the assignment and dropping the rows."""
+
+    def __init__(self):
+        self.witness = []
+        self.public = []
+
+    @staticmethod
+    def one():
+        return ("i", 0)
+
+    def new_input_variable(self, value):
+        self.public.append(int(value) % R)
+        return ("i", len(self.public))
+
+    def new_witness_variable(self, value):
+        self.witness.append(int(value) % R)
+        return ("w", len(self.witness) - 1)
+
+    def enforce_constraint(self, a, b, c):
+        pass
+
+
+@pytest.fixture(scope="module")
+def M():
+    from simpleworks_amd import marlin
+    return marlin
+
+
+@pytest.fixture(scope="module")
+def W():
+    from simpleworks_amd import workloads
+    return workloads
+
+
+@pytest.fixture(scope="module")
+def RO():
+    from simpleworks_amd import random_oracle
+    return random_oracle
+
+
+@pytest.fixture(scope="module")
+def ctx(M):
+    return M.default_context()
+
+
+def batch(count, length, seed=0):
+    """uint8 [count, length], seeded; every item differs."""
+    rng = np.random.default_rng(1000 * length + count + 7919 * seed)
+    return rng.integers(0, 256, size=(count, length), dtype=np.uint8)
+
+
+def digests_of(a):
+    return np.frombuffer(b"".join(hashlib.blake2s(row.tobytes()).digest() for row in a), dtype=np.uint8).reshape(len(a), 32)
+
+
+@pytest.fixture(scope="module")
+def oracle(M, W):
+    """bytes -> (the builder's witness as Montgomery limbs, the digest); built once per input."""
+    seen = {}
+
+    def get(data):
+        data = bytes(data)
+        if data not in seen:
+            cs = _WitnessOnly()
+            public = W.build_blake2s_hash(cs, data)
+            digest = hashlib.blake2s(data).digest()
+            assert public == cs.public == W.blake2s_public_inputs(digest)
+            seen[data] = (M._to_mont_limbs(cs.witness), digest)
+        return seen[data]
+    return get
+
+
+def _same(got, want, what):
+    assert got.shape == want.shape, what
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert bad.size == 0, "%s: %d witnesses differ, the first at %d" % (what, bad.size, bad[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------- native hash
+@pytest.mark.parametrize("length", [0, 1, 3, 32, 55, 63, 64, 65, 127, 128, 129, 1000])
+def test_hash_lengths_against_hashlib(RO, length):
+    """130 items: more than two waves, and for an odd length items at all four byte offsets within a word."""
+    a = batch(130, length)
+    assert np.array_equal(RO.evaluate_many(a), digests_of(a))
+
+
+@pytest.mark.parametrize("count", [1, 63, 64, 65, 129, 1000])
+def test_hash_counts_at_the_wave_and_workgroup_edges(RO, count):
+    a = batch(count, 32)
+    assert np.array_equal(RO.evaluate_many(a), digests_of(a))
+
+
+def test_hash_one_item_of_the_longest_length(RO, ctx):
+    from simpleworks_amd._lib import SwmError
+    a = batch(1, 65536)
+    assert np.array_equal(RO.evaluate_many(a), digests_of(a))
+    with pytest.raises(SwmError) as e:
+        RO.evaluate_many(np.zeros((1, 65537), dtype=np.uint8))
+    assert e.value.code == -1
+    out = np.zeros(32, dtype=np.uint8)
+    assert ctx.lib.swm_blake2s_hash(ctx.h, a.ctypes.data, 32, 1, None) == -1           # a NULL output
+    assert ctx.lib.swm_blake2s_hash(ctx.h, a.ctypes.data, 65537, 1, out.ctypes.data) == -1
+
+
+@pytest.mark.parametrize("length", [32, 65, 3])
+def test_hash_device_form_on_a_torch_buffer(ctx, length):
+    import torch
+    count = 130
+    a = batch(count, length, seed=1)
+    d_in = torch.from_numpy(a.reshape(-1).copy()).cuda()
+    d_out = torch.full((count * 32,), 0x5A, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ctx.blake2s_hash_dev(d_in.data_ptr(), length, count, d_out.data_ptr())
+    ctx.synchronize()
+    assert np.array_equal(d_out.cpu().numpy().reshape(count, 32), digests_of(a))
+
+
+def test_hash_of_nothing(RO, ctx):
+    out = np.full(32, 0x5A, dtype=np.uint8)
+    assert ctx.lib.swm_blake2s_hash(ctx.h, None, 32, 0, out.ctypes.data) == 0
+    assert ctx.lib.swm_blake2s_hash_dev(ctx.h, None, 32, 0, out.ctypes.data) == 0
+    assert (out == 0x5A).all()
+    assert RO.evaluate_many(np.zeros((0, 32), dtype=np.uint8)).shape == (0, 32)
+
+
+def test_known_answers_and_the_reference_names(RO):
+    for data, digest in KNOWN:
+        assert hashlib.blake2s(data).hexdigest() == digest
+        assert RO.RO.evaluate(RO.RO.setup(None), data).hex() == digest
+    parameters = RO.RO.setup(None)
+    assert parameters == ()
+    assert RO.RO.evaluate(parameters, [1] * 32).hex() == KNOWN[1][1]
+
+
+# ---------------------------------------------------------------------------------------------------------------- witness
+@pytest.mark.parametrize("length", [0, 1, 32, 63, 64, 65, 129])
+def test_witness_equals_the_builders(RO, oracle, length):
+    """All zero, all 0xFF and a seeded random input: one, two and three blocks, full and partial last blocks."""
+    msgs = [bytes(length), bytes([0xFF] * length), batch(1, length, seed=2)[0].tobytes()]
+    c = RO.Blake2sCircuit(length)
+    blocks = max(1, (length + 63) // 64)
+    assert c.shape() == (3, 8 * length + 21472 * blocks, 8 * length + 21792 * blocks + 2)
+    witness, digests = c.witness_many(msgs)
+    assert witness.shape == (3, c.shape()[1], 4) and digests.shape == (3, 32)
+    for i, m in enumerate(msgs):
+        want, digest = oracle(m)
+        _same(witness[i], want, "length %d item %d" % (length, i))
+        assert digests[i].tobytes() == digest
+
+
+@pytest.mark.parametrize("count", [1, 64, 65, 130])
+def test_witness_batches(RO, oracle, count):
+    """Two inputs alternate through the batch: every item's witness is the builder's for its input, every digest the native
+    kernel's."""
+    two = batch(2, 32, seed=3)
+    a = two[[0 if i % 3 else 1 for i in range(count)]]
+    c = RO.Blake2sCircuit(32)
+    witness, digests = c.witness_many(a)
+    assert np.array_equal(digests, RO.evaluate_many(a))
+    for i in range(count):
+        want, digest = oracle(a[i].tobytes())
+        _same(witness[i], want, "item %d of %d" % (i, count))
+        assert digests[i].tobytes() == digest
+
+
+def test_witness_of_unaligned_items(RO, oracle):
+    """65 bytes, three items: items 1 and 2 start one and two bytes past a word boundary, and each has two blocks."""
+    a = batch(3, 65, seed=4)
+    witness, digests = RO.Blake2sCircuit(65).witness_many(a)
+    for i in range(3):
+        want, digest = oracle(a[i].tobytes())
+        _same(witness[i], want, "item %d" % i)
+        assert digests[i].tobytes() == digest
+
+
+def test_witness_device_form_and_an_empty_batch(RO, ctx, oracle):
+    count, length = 3, 65
+    a = batch(count, length, seed=4)
+    c = RO.Blake2sCircuit(length)
+    nw = c.shape()[1]
+    d_in, d_w, d_dg = ctx.to_device(a), ctx.alloc(count * nw * 32), ctx.alloc(count * 32)
+    d_w.upload(np.full(count * nw * 32, 0x5A, dtype=np.uint8))
+    d_dg.upload(np.full(count * 32, 0x5A, dtype=np.uint8))
+    ctx.blake2s_witness_dev(d_in, length, count, d_w, d_dg)
+    ctx.synchronize()
+    witness = d_w.download((count, nw, 4))
+    assert np.array_equal(d_dg.download((count, 32), np.uint8), digests_of(a))
+    for i in range(count):
+        _same(witness[i], oracle(a[i].tobytes())[0], "item %d" % i)
+    # without digests: the same witnesses
+    d_w.upload(np.full(count * nw * 32, 0x5A, dtype=np.uint8))
+    ctx.blake2s_witness_dev(d_in, length, count, d_w, None)
+    ctx.synchronize()
+    assert np.array_equal(d_w.download((count, nw, 4)), witness)
+    # count = 0: SWM_OK, nothing launched, buffers may be NULL
+    assert ctx.lib.swm_blake2s_witness(ctx.h, None, length, 0, None, None) == 0
+    assert ctx.lib.swm_blake2s_witness_dev(ctx.h, None, length, 0, None, None) == 0
+    w0, d0 = c.witness_many(np.zeros((0, length), dtype=np.uint8))
+    assert w0.shape == (0, nw, 4) and d0.shape == (0, 32)
+    assert ctx.lib.swm_blake2s_witness(ctx.h, a.ctypes.data, 65537, 1, witness.ctypes.data, None) == -1
+    for b in (d_in, d_w, d_dg):
+        b.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------- proof
+def _index(M, W, data):
+    cs = M.MarlinInst._synthesize(W.Blake2sHashCircuit(data))
+    packed = cs.pack()
+    nnz = max(int(m[0][-1]) for m in packed.mats)
+    srs = M.MarlinInst.universal_setup(cs.num_constraints, len(cs.instance) + len(cs.witness), nnz, M.generate_rand())
+    pk, vk = M.MarlinInst.index_from_constraint_system(srs, packed)
+    srs.free()
+    return cs, pk, vk
+
+
+@pytest.fixture(scope="module")
+def keys32(M, W):
+    """The reference's own case, [1u8; 32], indexed once."""
+    cs, pk, vk = _index(M, W, bytes([1] * 32))
+    yield cs, pk, vk
+    pk.free()
+
+
+def test_proof_equals_the_builders(M, W, keys32):
+    """generate_blake2s_proof is byte-identical to generate_proof on the builder's system with the same rng state."""
+    from simpleworks_amd import serialization as Ser
+    cs, pk, _ = keys32
+    data = bytes([1] * 32)
+    want = M.generate_proof(cs, pk, M.generate_rand())
+    got, digest = M.generate_blake2s_proof(pk, data, M.generate_rand())
+    assert digest.hex() == KNOWN[1][1] and cs.instance[1:] == W.blake2s_public_inputs(digest)
+    assert got == Ser.serialize_proof(want)
+    # the prover is as it was for the next caller: the device source does not outlive the call
+    assert Ser.serialize_proof(M.generate_proof(cs, pk, M.generate_rand())) == got
+
+
+def test_proof_verifies_with_the_digest_and_with_no_other(M, W, keys32):
+    _, pk, vk = keys32
+    got, digest = M.generate_blake2s_proof(pk, bytes([1] * 32), M.generate_rand())
+    lo, hi = W.blake2s_public_inputs(digest)
+    assert M.verify_proof(vk, [lo, hi], M.MarlinProof(got), M.generate_rand())
+    assert not M.verify_proof(vk, [(lo + 1) % R, hi], M.MarlinProof(got), M.generate_rand())
+    # another preimage of the same length under the same key
+    other = bytes(range(32))
+    got, digest = M.generate_blake2s_proof(pk, other, M.generate_rand())
+    assert digest == hashlib.blake2s(other).digest()
+    assert M.verify_proof(vk, W.blake2s_public_inputs(digest), M.MarlinProof(got), M.generate_rand())
+
+
+def test_a_key_of_another_length_does_not_match(M, keys32):
+    _, pk, _ = keys32
+    with pytest.raises(M.MarlinError) as e:
+        M.generate_blake2s_proof(pk, bytes([1] * 31), M.generate_rand())
+    assert e.value.code == -8
+
+
+def test_a_two_block_proof_verifies(M, W):
+    data = bytes((3 * i + 1) & 0xFF for i in range(65))
+    _, pk, vk = _index(M, W, data)
+    try:
+        got, digest = M.generate_blake2s_proof(pk, data, M.generate_rand())
+        assert digest == hashlib.blake2s(data).digest()
+        assert M.verify_proof(vk, W.blake2s_public_inputs(digest), M.MarlinProof(got), M.generate_rand())
+    finally:
+        pk.free()
