@@ -154,6 +154,26 @@ ABI = {
     "swm_poseidon_witness_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "swm_poseidon_prove": (_int, [_vp, _vp, _vp, ctypes.c_void_p, _vp, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, _sz,
                                   ctypes.POINTER(_sz)]),
+    "swm_poseidon_tree_create_blank": (_int, [_vp, _vp, _sz, _sz, ctypes.POINTER(_vp)]),
+    "swm_poseidon_tree_create_from_leaves": (_int, [_vp, _vp, ctypes.c_void_p, _sz, _sz, ctypes.POINTER(_vp)]),
+    "swm_poseidon_tree_destroy": (None, [_vp, _vp]),
+    "swm_poseidon_tree_update": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, _sz]),
+    "swm_poseidon_tree_root": (_int, [_vp, _vp, ctypes.c_void_p]),
+    "swm_poseidon_tree_paths": (_int, [_vp, _vp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_poseidon_tree_nodes": (_int, [_vp, _vp, ctypes.c_void_p]),
+    "swm_poseidon_tree_dev_nodes": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
+    "swm_poseidon_verify_paths": (_int, [_vp, _vp, _sz, ctypes.c_void_p, _sz, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.c_void_p, _sz,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_poseidon_tree_circuit_shape": (_int, [_sz, _sz, ctypes.c_uint64, _sz, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz),
+                                               ctypes.POINTER(_sz)]),
+    "swm_poseidon_tree_circuit_create": (_int, [_vp, _vp, _sz, _sz, ctypes.POINTER(_vp)]),
+    "swm_poseidon_tree_circuit_destroy": (None, [_vp, _vp]),
+    "swm_poseidon_tree_witness": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_poseidon_tree_witness_at": (_int, [_vp, _vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "swm_poseidon_tree_prove": (_int, [_vp, _vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, _vp, ctypes.c_uint,
+                                       ctypes.c_void_p, _sz, ctypes.POINTER(_sz)]),
+    "swm_poseidon_tree_prove_at": (_int, [_vp, _vp, _vp, _vp, ctypes.c_void_p, ctypes.c_uint64, _vp, ctypes.c_uint, ctypes.c_void_p, _sz,
+                                          ctypes.POINTER(_sz)]),
     "swm_blake2s_hash": (_int, [_vp, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
     "swm_blake2s_hash_dev": (_int, [_vp, _vp, _sz, _sz, _vp]),
     "swm_blake2s_circuit_shape": (_int, [_sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
@@ -834,6 +854,110 @@ class Context:
         self._check(self.lib.swm_poseidon_witness_dev(self.h, handle, d_inputs.ptr if d_inputs else None, count,
                                                       d_witness.ptr if d_witness else None, d_outputs.ptr if d_outputs else None,
                                                       d_status.ptr if d_status else None), "swm_poseidon_witness_dev")
+
+    # ---- resident Poseidon Merkle tree and its membership witness (include/swmarlin.h; simpleworks_amd/hash.py, PoseidonMerkleTree and
+    # PoseidonMembershipCircuit, are the caller-facing mirrors)
+    def poseidon_tree_create_blank(self, params_handle, height, leaf_len):
+        h = _vp()
+        self._check(self.lib.swm_poseidon_tree_create_blank(self.h, params_handle, height, leaf_len, ctypes.byref(h)),
+                    "swm_poseidon_tree_create_blank")
+        return h
+
+    def poseidon_tree_create_from_leaves(self, params_handle, leaves):
+        """leaves: uint8 [n, leaf_len]."""
+        a = np.ascontiguousarray(leaves, dtype=np.uint8)
+        assert a.ndim == 2
+        h = _vp()
+        self._check(self.lib.swm_poseidon_tree_create_from_leaves(self.h, params_handle, a.ctypes.data, a.shape[1], a.shape[0], ctypes.byref(h)),
+                    "swm_poseidon_tree_create_from_leaves")
+        return h
+
+    def poseidon_tree_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_poseidon_tree_destroy(self.h, handle)
+
+    def poseidon_tree_update(self, handle, indices, leaves):
+        """indices: leaf indices; leaves: uint8 [count, leaf_len], applied in order (a repeated index keeps its last leaf)."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        a = np.ascontiguousarray(leaves, dtype=np.uint8)
+        assert a.ndim == 2 and a.shape[0] == idx.shape[0]
+        self._check(self.lib.swm_poseidon_tree_update(self.h, handle, idx.ctypes.data, a.ctypes.data, a.shape[1], idx.shape[0]),
+                    "swm_poseidon_tree_update")
+
+    def poseidon_tree_root(self, handle):
+        out = np.empty(32, dtype=np.uint8)
+        self._check(self.lib.swm_poseidon_tree_root(self.h, handle, out.ctypes.data), "swm_poseidon_tree_root")
+        return out
+
+    def poseidon_tree_dev_nodes(self, handle):
+        """(device pointer of the node buffer, node count)."""
+        p, n = _vp(), _sz(0)
+        self._check(self.lib.swm_poseidon_tree_dev_nodes(handle, ctypes.byref(p), ctypes.byref(n)), "swm_poseidon_tree_dev_nodes")
+        return p.value, n.value
+
+    def poseidon_tree_nodes(self, handle):
+        """uint8 [2 n - 1, 32]: n leaf digests | n / 2 | ... | root."""
+        out = np.empty((self.poseidon_tree_dev_nodes(handle)[1], 32), dtype=np.uint8)
+        self._check(self.lib.swm_poseidon_tree_nodes(self.h, handle, out.ctypes.data), "swm_poseidon_tree_nodes")
+        return out
+
+    def poseidon_tree_paths(self, handle, levels, indices):
+        """-> uint8 [count, levels, 32]: the siblings of each leaf, bottom up."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        out = np.empty((idx.shape[0], levels, 32), dtype=np.uint8)
+        self._check(self.lib.swm_poseidon_tree_paths(self.h, handle, idx.ctypes.data, idx.shape[0], out.ctypes.data), "swm_poseidon_tree_paths")
+        return out
+
+    def poseidon_verify_paths(self, params_handle, height, roots, leaves, indices, siblings):
+        """roots uint8 [32] (one for all paths) or [count, 32]; leaves uint8 [count, leaf_len]; indices uint64 [count]; siblings uint8
+        [count, height - 1, 32] -> (ok uint8 [count], status uint32 [count])."""
+        roots = np.ascontiguousarray(roots, dtype=np.uint8)
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint8)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        sib = np.ascontiguousarray(siblings, dtype=np.uint8)
+        count = idx.shape[0]
+        assert leaves.ndim == 2 and leaves.shape[0] == count and sib.shape == (count, height - 1, 32)
+        assert roots.shape in ((32,), (count, 32))
+        ok, status = np.zeros(count, dtype=np.uint8), np.zeros(count, dtype=np.uint32)
+        self._check(self.lib.swm_poseidon_verify_paths(self.h, params_handle, height, roots.ctypes.data, 32 if roots.ndim == 2 else 0,
+                                                       leaves.ctypes.data, leaves.shape[1], idx.ctypes.data, sib.ctypes.data, count,
+                                                       ok.ctypes.data, status.ctypes.data), "swm_poseidon_verify_paths")
+        return ok, status
+
+    def poseidon_tree_circuit_create(self, params_handle, height, leaf_len):
+        h = _vp()
+        self._check(self.lib.swm_poseidon_tree_circuit_create(self.h, params_handle, height, leaf_len, ctypes.byref(h)),
+                    "swm_poseidon_tree_circuit_create")
+        return h
+
+    def poseidon_tree_circuit_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_poseidon_tree_circuit_destroy(self.h, handle)
+
+    def poseidon_tree_witness(self, handle, num_witness, leaves, indices, siblings):
+        """leaves uint8 [count, leaf_len], indices uint64 [count], siblings uint8 [count, levels, 32] (canonical little-endian) ->
+        (witness uint64 [count, num_witness, 4] Montgomery limbs, roots uint8 [count, 32])."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint8)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        sib = np.ascontiguousarray(siblings, dtype=np.uint8)
+        count = idx.shape[0]
+        assert leaves.ndim == 2 and leaves.shape[0] == count and sib.ndim == 3 and sib.shape[0] == count and sib.shape[2] == 32
+        witness = np.empty((count, num_witness, 4), dtype=np.uint64)
+        roots = np.empty((count, 32), dtype=np.uint8)
+        self._check(self.lib.swm_poseidon_tree_witness(self.h, handle, leaves.ctypes.data, idx.ctypes.data, sib.ctypes.data, count,
+                                                       witness.ctypes.data, roots.ctypes.data), "swm_poseidon_tree_witness")
+        return witness, roots
+
+    def poseidon_tree_witness_at(self, handle, tree_handle, num_witness, leaves, indices):
+        """The same for leaves of a resident tree: -> witness uint64 [count, num_witness, 4]."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint8)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        count = idx.shape[0]
+        assert leaves.ndim == 2 and leaves.shape[0] == count
+        witness = np.empty((count, num_witness, 4), dtype=np.uint64)
+        self._check(self.lib.swm_poseidon_tree_witness_at(self.h, handle, tree_handle, leaves.ctypes.data, idx.ctypes.data, count,
+                                                          witness.ctypes.data), "swm_poseidon_tree_witness_at")
+        return witness
 
     # ---- Blake2s random oracle and its circuit's witness (include/swmarlin.h; simpleworks_amd/random_oracle.py is the caller-facing
     # mirror).  A device buffer is a DeviceBuffer or a raw device address (an int: a tensor's data_ptr()).

@@ -9,6 +9,7 @@
 #include "merkle_shape.h"
 #include "schnorr_shape.h"
 #include "poseidon_shape.h"
+#include "poseidon_tree_shape.h"
 #include "blake2s_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
@@ -243,6 +244,26 @@ int swm_poseidon_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64
                        "rounds, alpha 2 .. %llu, at most %zu bytes and one output or %zu elements and 1 .. %zu outputs)",
                        full_rounds, partial_rounds, (unsigned long long)alpha, n_in, bytes_form ? "bytes" : "elements", n_out,
                        (size_t)PC_MAX_ROUNDS, (unsigned long long)PC_MAX_ALPHA, (size_t)PC_MAX_BYTES, (size_t)PC_MAX_IN, (size_t)PC_MAX_OUT);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// The shape of the membership circuit over a Poseidon Merkle tree from the parameter shape, the height and the leaf length
+// (poseidon_tree_shape.h; the layout is build_poseidon_membership's)
+int swm_poseidon_tree_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64_t alpha, size_t height, size_t leaf_len,
+                                    size_t* num_instance, size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "poseidon_tree_circuit_shape: NULL output");
+    PoseidonTreeShape s;
+    if (!poseidon_tree_shape(full_rounds, partial_rounds, alpha, height, leaf_len, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG,
+                       "poseidon_tree_circuit_shape: %zu + %zu rounds, alpha %llu, height %zu, leaves of %zu bytes (full rounds even and >= 2, "
+                       "at most %zu rounds, alpha 2 .. %llu, %zu <= height <= %zu, 1 .. %zu bytes)",
+                       full_rounds, partial_rounds, (unsigned long long)alpha, height, leaf_len, (size_t)PC_MAX_ROUNDS,
+                       (unsigned long long)PC_MAX_ALPHA, (size_t)PT_MIN_HEIGHT, (size_t)PT_MAX_HEIGHT, (size_t)PT_MAX_LEAF_LEN);
     *num_instance = s.num_instance;
     *num_witness = s.num_witness;
     *num_constraints = s.num_constraints;

@@ -25,6 +25,7 @@
 
 #include "context.h"
 #include "host/merkle_dirty.h"
+#include "merkle_nodes.cuh"
 #include "pedersen.cuh"
 #include "pedersen.h"
 #include "swmarlin.h"
@@ -52,8 +53,6 @@ struct MtTail {
     uint32_t count[MT_MAX_LEVELS];         // [l]: dirty nodes of level l + 1 (<= MT_TAIL for l >= first)
     uint32_t node[MT_MAX_LEVELS][MT_TAIL];
 };
-
-__device__ __forceinline__ size_t mt_level_offset(unsigned levels, unsigned l) { return ((size_t)2 << levels) - (((size_t)2 << levels) >> l); }
 
 // Job j hashes the `len` bytes at in + src[j] * stride into the digest out + 32 dst[j].  Leaves: src = position in the batch,
 // dst = leaf index.  A two-to-one level: src = dst = parent, in = the level below (stride 64), out = the parent's level.
@@ -139,28 +138,6 @@ __global__ void __launch_bounds__(64) merkle_blank_chain_kernel(const EdRow* __r
             for (int i = 0; i < 8; i++) msg[i] = msg[8 + i] = chain[8 * (l + 1) + i] = x.v[i];
         }
         __syncthreads();
-    }
-}
-
-// every node of level l = chain[l]; i runs over the 16-byte halves of the nodes
-__global__ void __launch_bounds__(256) merkle_blank_fill_kernel(const uint4* __restrict__ chain, unsigned levels, uint4* __restrict__ nodes) {
-    const size_t halves = 2 * (((size_t)2 << levels) - 1);
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < halves; i += (size_t)gridDim.x * blockDim.x) {
-        const unsigned long long from_root = (((unsigned long long)2 << levels) - 2) - (i >> 1);  // 0 at the root
-        const unsigned level = levels - (63u - (unsigned)__clzll((long long)(from_root + 1)));
-        nodes[i] = chain[2 * level + (i & 1)];
-    }
-}
-
-// word i of the output: sibling of level l of path p, bottom up; an index beyond the leaves reads as zeros
-__global__ void __launch_bounds__(256) merkle_paths_kernel(const uint32_t* __restrict__ nodes, unsigned levels,
-                                                           const uint64_t* __restrict__ indices, size_t count, uint32_t* __restrict__ out) {
-    const size_t words = count * levels * 8;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t s = i >> 3, p = s / levels;
-        const unsigned l = (unsigned)(s % levels);
-        const uint64_t index = indices[p];
-        out[i] = (index >> levels) ? 0u : nodes[8 * (mt_level_offset(levels, l) + ((index >> l) ^ 1)) + (i & 7)];
     }
 }
 

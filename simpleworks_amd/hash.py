@@ -1,5 +1,5 @@
-"""Native Pedersen hash, Pedersen Merkle tree and Poseidon sponge, computed on the GPU (csrc/pedersen.hip, csrc/merkle_tree.hip and
-csrc/poseidon.hip through include/swmarlin.h).
+"""Native Pedersen hash, Pedersen Merkle tree, Poseidon sponge and Poseidon Merkle tree, computed on the GPU (csrc/pedersen.hip,
+csrc/merkle_tree.hip, csrc/poseidon.hip and csrc/poseidon_tree.hip through include/swmarlin.h).
 
 Caller-facing mirror of what the reference reaches through ark-crypto-primitives 0.3:
     src/hash/mod.rs:13-28                           pedersen_hash(input): LeafWindow 144 x 4, parameters from a fresh test_rng
@@ -12,6 +12,8 @@ Caller-facing mirror of what the reference reaches through ark-crypto-primitives
     examples/simple-payments/transaction.rs:163-173 tree.generate_proof, Path::verify (generate_proofs, verify_paths)
 and through ark-sponge 0.3:
     src/hash/mod.rs:30-43                           poseidon2_hash(input): PoseidonSponge<Fq>, absorb the bytes, squeeze one element
+PoseidonMerkleTree, verify_poseidon_paths and PoseidonMembershipCircuit have no counterpart in the reference: a Merkle tree over that
+sponge with DeviceMerkleTree's calls, and the witness of its membership circuit.
 
 Host side (this file): sampling the parameters — CRH::setup is a few hundred curve operations, done with Python integers the
 way ark-ec samples a twisted Edwards point [U] — and the tree's bookkeeping.  Every hash runs on the GPU; there is no CPU
@@ -22,7 +24,8 @@ import json
 import numpy as np
 
 from ._lib import poseidon_pack_bytes  # noqa: F401  (the sponge's byte-to-element rule on the host)
-from .marlin import R_MODULUS, default_context, generate_rand, merkle_circuit_shape, poseidon_circuit_shape
+from .marlin import (R_MODULUS, default_context, generate_rand, merkle_circuit_shape, poseidon_circuit_shape,
+                     poseidon_membership_circuit_shape)
 
 ED_D = 3021            # ed-on-BLS12-377: -x^2 + y^2 = 1 + 3021 x^2 y^2 over BLS12-377 Fr
 ED_COFACTOR = 4
@@ -445,6 +448,135 @@ class PoseidonCircuit:
     def free(self):
         if self.h:
             self.ctx.poseidon_circuit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PoseidonMerkleTree:
+    """A Merkle tree over a PoseidonSponge that stays on the GPU (swm_poseidon_tree): leaf digest = the byte sponge of the leaf
+    (poseidon2_hash), inner node = the two-to-one form, hash_elements_many([a, b], 1).  The calls carry DeviceMerkleTree's names and
+    meaning.  Refers to the PoseidonSponge: keep it alive."""
+
+    def __init__(self, sponge, handle, height, leaf_len):
+        self.ctx, self.sponge = sponge.ctx, sponge
+        self.h, self._height, self.leaf_len = handle, height, leaf_len
+
+    @staticmethod
+    def blank(sponge, height, leaf_len):
+        """2^(height - 1) leaves whose digests are 32 zero bytes (the hash of nothing); `height` counts the leaf level.  leaf_len: the
+        bytes of every leaf that update() will write."""
+        return PoseidonMerkleTree(sponge, sponge.ctx.poseidon_tree_create_blank(sponge.h, height, leaf_len), height, leaf_len)
+
+    @staticmethod
+    def new(sponge, leaves):
+        a = _leaf_bytes(leaves)
+        return PoseidonMerkleTree(sponge, sponge.ctx.poseidon_tree_create_from_leaves(sponge.h, a), a.shape[0].bit_length(), a.shape[1])
+
+    def update(self, index, leaf):
+        self.update_many([index], [leaf])
+
+    def update_many(self, indices, leaves):
+        """The updates in order, in one call: a repeated index keeps its last leaf, every ancestor is hashed once."""
+        indices = [int(i) for i in indices]
+        if len(indices) != len(leaves):
+            raise ValueError("one leaf per index")
+        if indices:
+            self.ctx.poseidon_tree_update(self.h, np.asarray(indices, dtype=np.uint64), _leaf_bytes(leaves))
+
+    def root(self):
+        return int.from_bytes(self.ctx.poseidon_tree_root(self.h).tobytes(), "little")
+
+    def height(self):
+        """Levels including the leaves."""
+        return self._height
+
+    def generate_proofs(self, indices):
+        """-> uint8 [count, height - 1, 32]: per leaf the sibling digests bottom up, the form PoseidonMembershipCircuit.witness_many
+        and verify_poseidon_paths take.  One launch."""
+        return self.ctx.poseidon_tree_paths(self.h, self._height - 1, np.asarray([int(i) for i in indices], dtype=np.uint64))
+
+    def generate_proof(self, index):
+        """Path of leaf `index`: the siblings bottom up, as integers."""
+        if not 0 <= index < 1 << (self._height - 1):
+            raise IndexError("leaf index out of range")
+        return [int.from_bytes(s.tobytes(), "little") for s in self.generate_proofs([index])[0]]
+
+    def to_merkle_tree(self):
+        """Downloads every node into a MerkleTree."""
+        nodes = self.ctx.poseidon_tree_nodes(self.h)
+        levels, off, cnt = [], 0, 1 << (self._height - 1)
+        while cnt >= 1:
+            levels.append(nodes[off:off + cnt])
+            off += cnt
+            cnt >>= 1
+        return MerkleTree(levels)
+
+    def free(self):
+        if self.h:
+            self.ctx.poseidon_tree_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _root_rows(roots):
+    def one(r):
+        return bytes(r) if isinstance(r, (bytes, bytearray, np.ndarray)) else int(r).to_bytes(32, "little")
+    if isinstance(roots, np.ndarray):
+        return np.ascontiguousarray(roots, dtype=np.uint8)
+    if isinstance(roots, (list, tuple)):
+        return np.frombuffer(b"".join(one(x) for x in roots), dtype=np.uint8).reshape(len(roots), 32)
+    return np.frombuffer(one(roots), dtype=np.uint8)
+
+
+def verify_poseidon_paths(sponge, height, roots, leaves, indices, siblings, with_status=False):
+    """verify_paths for a Poseidon tree (swm_poseidon_verify_paths): one launch, no tree.  Arguments as verify_paths.  Returns ok, bool
+    [count] (with_status: also the status words: 0 computed, 1 a sibling or root >= r, 2 an index beyond the leaves)."""
+    idx = np.asarray([int(i) for i in indices], dtype=np.uint64)
+    if not idx.shape[0]:
+        return (np.zeros(0, dtype=bool), np.zeros(0, dtype=np.uint32)) if with_status else np.zeros(0, dtype=bool)
+    ok, status = sponge.ctx.poseidon_verify_paths(sponge.h, height, _root_rows(roots), _leaf_bytes(leaves), idx, _fr_rows(siblings))
+    return (ok != 0, status) if with_status else ok != 0
+
+
+class PoseidonMembershipCircuit:
+    """The membership circuit over a Poseidon Merkle tree of `height` levels with leaves of leaf_len bytes, resident on the GPU
+    (swm_poseidon_tree_circuit): synthesises the witness vector of workloads.build_poseidon_membership for batches of (leaf, leaf
+    index, authentication path) without running the builder.  Refers to the PoseidonSponge: keep it alive."""
+
+    def __init__(self, sponge, height, leaf_len):
+        self.ctx, self.sponge = sponge.ctx, sponge
+        self.height, self.leaf_len = height, leaf_len
+        self.h = self.ctx.poseidon_tree_circuit_create(sponge.h, height, leaf_len)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        return poseidon_membership_circuit_shape(self.sponge.params, self.height, self.leaf_len)
+
+    def witness_many(self, leaves, indices, siblings):
+        """leaves: as PoseidonMerkleTree.new takes them; siblings: per path the sibling digests bottom up.  Returns (witness uint64
+        [count, num_witness, 4] Montgomery limbs, roots as ints)."""
+        witness, roots = self.ctx.poseidon_tree_witness(self.h, self.shape()[1], _leaf_bytes(leaves),
+                                                        np.asarray([int(i) for i in indices], dtype=np.uint64), _fr_rows(siblings))
+        return witness, [int.from_bytes(r.tobytes(), "little") for r in roots]
+
+    def witness_at(self, tree, leaves, indices):
+        """The same for leaves that a PoseidonMerkleTree holds: siblings and running digests are read from its nodes on the device."""
+        return self.ctx.poseidon_tree_witness_at(self.h, tree.h, self.shape()[1], _leaf_bytes(leaves),
+                                                 np.asarray([int(i) for i in indices], dtype=np.uint64))
+
+    def free(self):
+        if self.h:
+            self.ctx.poseidon_tree_circuit_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -513,6 +513,44 @@ def generate_poseidon_proof(proving_key, circuit, data_or_elements, rng, uncompr
     return bytes(buf[: n.value]), [int.from_bytes(out[32 * j:32 * j + 32], "little") for j in range(circuit.n_out)]
 
 
+def poseidon_membership_circuit_shape(params, height, leaf_len):
+    """swm_poseidon_tree_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the membership circuit over a Poseidon
+    Merkle tree of that height with leaves of leaf_len bytes — what workloads.build_poseidon_membership emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_poseidon_tree_circuit_shape(params.full_rounds, params.partial_rounds, params.alpha, height, leaf_len,
+                                                          ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)),
+           "swm_poseidon_tree_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_poseidon_membership_proof(proving_key, circuit, root, leaf, leaf_index, siblings, rng, uncompressed=False, tree=None):
+    """swm_poseidon_tree_prove: the proof of workloads.PoseidonMerkleTreeVerification with the circuit's witness synthesised on the GPU
+    (hash.PoseidonMembershipCircuit) and handed to the prover on the device.  root / siblings: ints (standard form); leaf: leaf_len
+    bytes.  tree: a hash.PoseidonMerkleTree that holds the leaf — root and siblings are then read from it on the device
+    (swm_poseidon_tree_prove_at) and the two arguments are ignored.  The public input to verify with is [root] + the leaf bits.
+    Returns the proof bytes (uncompressed=True: the form of generate_proof_uncompressed)."""
+    ctx = proving_key.ctx
+    leaf = bytes(leaf)
+    if len(leaf) != circuit.leaf_len:
+        raise ValueError("generate_poseidon_membership_proof: a leaf of %d bytes" % circuit.leaf_len)
+    leaf_b = (ctypes.c_uint8 * len(leaf)).from_buffer_copy(leaf)
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    flags = 1 if uncompressed else 0
+    if tree is not None:
+        _check(ctx.lib.swm_poseidon_tree_prove_at(ctx.h, proving_key.h, circuit.h, tree.h, leaf_b, leaf_index, rng.h, flags, buf, len(buf),
+                                                  ctypes.byref(n)), "swm_poseidon_tree_prove_at", ctx)
+        return bytes(buf[: n.value])
+    root_b = (ctypes.c_uint8 * 32).from_buffer_copy(int(root).to_bytes(32, "little"))
+    sib = b"".join(int(s).to_bytes(32, "little") for s in siblings)
+    if len(sib) != 32 * (circuit.height - 1):
+        raise ValueError("generate_poseidon_membership_proof: a path of %d siblings" % (circuit.height - 1))
+    sib_b = (ctypes.c_uint8 * len(sib)).from_buffer_copy(sib)
+    _check(ctx.lib.swm_poseidon_tree_prove(ctx.h, proving_key.h, circuit.h, root_b, leaf_b, leaf_index, sib_b, rng.h, flags, buf, len(buf),
+                                           ctypes.byref(n)), "swm_poseidon_tree_prove", ctx)
+    return bytes(buf[: n.value])
+
+
 def blake2s_circuit_shape(input_len):
     """swm_blake2s_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the Blake2s hash circuit over input_len
     bytes — what workloads.build_blake2s_hash emits."""

@@ -1065,6 +1065,50 @@ class _PsLC:
         return [(c, var) for var, c in self.coeffs.items() if c]
 
 
+def _ps_product(cs, a, b):
+    """One witness and one row: w = a * b."""
+    v = a.value * b.value % R_MODULUS
+    w = _PsLC({cs.new_witness_variable(v): 1}, v)
+    cs.enforce_constraint(a.terms, b.terms, w.terms)
+    return w
+
+
+def _ps_absorb_bytes(one, bits, n):
+    """The elements the sponge absorbs for n bytes given as 8 n (variable, value) bits, byte-major and least significant first:
+    the 31-byte chunks of (n as 8 little-endian bytes, a constant, then the bits) as linear combinations."""
+    total = 8 + n
+    absorbed = []
+    for at in range(0, total, 31):
+        e = _PsLC()
+        for j in range(min(31, total - at)):
+            pos = at + j
+            if pos < 8:
+                e.add(((n >> (8 * pos)) & 0xFF) << (8 * j), _PsLC({one: 1}, 1))
+            else:
+                for i in range(8):
+                    var, value = bits[8 * (pos - 8) + i]
+                    e.add(1 << (8 * j + i), _PsLC({var: 1}, value))
+        absorbed.append(e)
+    return absorbed
+
+
+def _ps_permute(cs, one, params, state):
+    """One permutation over three _PsLC entries: a chain of squares and products per S-box, nothing folded into constants."""
+    full, partial, alpha = params.full_rounds, params.partial_rounds, params.alpha
+    for i in range(full + partial):
+        is_full = i < full // 2 or i >= full // 2 + partial
+        t = [_PsLC(s.coeffs, s.value).add(params.ark[i][k], _PsLC({one: 1}, 1)) for k, s in enumerate(state)]
+        for k in range(3 if is_full else 1):
+            acc = t[k]
+            for b in range(alpha.bit_length() - 2, -1, -1):
+                acc = _ps_product(cs, acc, acc)
+                if (alpha >> b) & 1:
+                    acc = _ps_product(cs, acc, t[k])
+            t[k] = acc
+        state = [_PsLC().add(params.mds[a][0], t[0]).add(params.mds[a][1], t[1]).add(params.mds[a][2], t[2]) for a in range(3)]
+    return state
+
+
 def build_poseidon_hash(cs, params, data=None, elements=None, n_out=1):
     """Emits the Poseidon hash circuit into `cs` (builder vocabulary as build_schnorr_verification).  params: a
     hash.PoseidonParameters; data: bytes (the bytes form, n_out = 1) or elements: field elements as ints < r (the elements form).
@@ -1080,50 +1124,17 @@ def build_poseidon_hash(cs, params, data=None, elements=None, n_out=1):
         _ps_shape_args(params, None, len(elements), n_out)
         if any(not 0 <= e < R_MODULUS for e in elements):
             raise ValueError("poseidon circuit: an element is not a canonical field element")
-    full, partial, alpha = params.full_rounds, params.partial_rounds, params.alpha
     one = cs.one()
-
-    def const(v):
-        return _PsLC({one: v % R_MODULUS}, v)
-
-    def product(a, b):
-        v = a.value * b.value % R_MODULUS
-        w = _PsLC({cs.new_witness_variable(v): 1}, v)
-        cs.enforce_constraint(a.terms, b.terms, w.terms)
-        return w
 
     # bits / elements
     if data is not None:
         bits = [_boolean_witness(cs, one, (byte >> i) & 1) for byte in data for i in range(8)]
-        total = 8 + len(data)
-        absorbed = []
-        for at in range(0, total, 31):
-            e = _PsLC()
-            for j in range(min(31, total - at)):
-                pos = at + j
-                if pos < 8:
-                    e.add(((len(data) >> (8 * pos)) & 0xFF) << (8 * j), const(1))
-                else:
-                    for i in range(8):
-                        b = bits[8 * (pos - 8) + i]
-                        e.add(1 << (8 * j + i), _PsLC({b.terms[0][1]: 1}, b.value))
-            absorbed.append(e)
+        absorbed = _ps_absorb_bytes(one, [(b.terms[0][1], b.value) for b in bits], len(data))
     else:
         absorbed = [_PsLC({cs.new_witness_variable(e): 1}, e) for e in elements]
 
     def permute(state):
-        for i in range(full + partial):
-            is_full = i < full // 2 or i >= full // 2 + partial
-            t = [_PsLC(s.coeffs, s.value).add(params.ark[i][k], const(1)) for k, s in enumerate(state)]
-            for k in range(3 if is_full else 1):
-                acc = t[k]
-                for b in range(alpha.bit_length() - 2, -1, -1):
-                    acc = product(acc, acc)
-                    if (alpha >> b) & 1:
-                        acc = product(acc, t[k])
-                t[k] = acc
-            state = [_PsLC().add(params.mds[a][0], t[0]).add(params.mds[a][1], t[1]).add(params.mds[a][2], t[2]) for a in range(3)]
-        return state
+        return _ps_permute(cs, one, params, state)
 
     # sponge: the absorbing blocks of two elements, then the squeezing blocks of two outputs
     state = [_PsLC(), _PsLC(), _PsLC()]
@@ -1162,6 +1173,129 @@ class PoseidonHashCircuit:
 
     def generate_constraints(self, cs):
         build_poseidon_hash(cs, self.params, self.data, self.elements, self.n_out)
+
+
+# ===================================================================================================================
+# Membership in a Poseidon Merkle tree (csrc/poseidon_tree.hip): "the public leaf bytes hash to a leaf of the tree with public
+# root" — MerkleTreeVerificationU8 with leaf_len bytes instead of one and the Poseidon sponge instead of the Pedersen hash.  The
+# tree is this library's own definition: leaf digest = the bytes-form sponge of the leaf, inner node H2(a, b) = state (a, b, 0),
+# one permutation, state[0].  build_poseidon_membership is the layout contract of csrc/host/poseidon_tree_shape.h and
+# csrc/poseidon_tree_witness.hip, written in build_poseidon_hash's vocabulary (_PsLC, no constant folding, the same chain order).
+# With n = leaf_len, E = ceil((8 + n) / 31), P_leaf = ceil(E / 2), m the chain length of alpha, C = (3 F + P) m, L = height - 1:
+#   instance  one, root, the 8 n leaf bits (byte-major, least significant first: the order SimpleMerkleTree::verify builds)
+#   witness   b_0 .. b_{L-1} (bit l of the leaf index) | s_0 .. s_{L-1} (siblings) | d_0 .. d_{L-1}, d_l = b_l (s_l - cur_l) |
+#             the leaf sponge, P_leaf C chain values | level 0 .. L - 1, C chain values each over the state
+#             (cur_l + d_l, s_l - d_l, 0); cur_{l+1} = state[0] after the permutation          3 L + (P_leaf + L) C
+#   rows      8 n booleanity rows of the leaf bits | the leaf chain rows | per level: booleanity of b_l, b_l (s_l - cur_l) = d_l,
+#             C chain rows | cur_L * one = root                                                8 n + P_leaf C + L (2 + C) + 1
+# ===================================================================================================================
+POSEIDON_MEMBERSHIP_MAX_LEAF_LEN = 256
+
+
+def poseidon_membership_layout(params, height, leaf_len):
+    """Offsets of the witness groups of build_poseidon_membership and its three counts, as csrc/host/poseidon_tree_shape.h states
+    them."""
+    _ps_shape_args(params, leaf_len, None, 1)
+    if not 2 <= height <= 31 or not 1 <= leaf_len <= POSEIDON_MEMBERSHIP_MAX_LEAF_LEN:
+        raise ValueError("poseidon membership circuit: 2 <= height <= 31, leaves of 1 .. %d bytes" % POSEIDON_MEMBERSHIP_MAX_LEAF_LEN)
+    levels = height - 1
+    elems = (8 + leaf_len + 30) // 31
+    lay = {"levels": levels, "leaf_permutations": (elems + 1) // 2}
+    lay["chain"] = params.alpha.bit_length() - 1 + bin(params.alpha).count("1") - 1
+    c = lay["permutation_values"] = (3 * params.full_rounds + params.partial_rounds) * lay["chain"]
+    lay.update(bits=0, siblings=levels, deltas=2 * levels, leaf=3 * levels, level0=3 * levels + lay["leaf_permutations"] * c)
+    lay["num_instance"] = 2 + 8 * leaf_len
+    lay["num_witness"] = 3 * levels + (lay["leaf_permutations"] + levels) * c
+    lay["num_constraints"] = 8 * leaf_len + lay["leaf_permutations"] * c + levels * (2 + c) + 1
+    return lay
+
+
+def build_poseidon_membership(cs, params, leaf, leaf_index, siblings, root=None):
+    """Emits the circuit into `cs`.  params: a hash.PoseidonParameters; leaf: the leaf's bytes; siblings: ints, bottom up.  `root`
+    overrides the public root (a wrong one gives an unsatisfied system: the final row fails).  Every witness is allocated in the
+    order of the header above, before or as its rows are emitted; returns the public inputs [root] + leaf bits."""
+    leaf = bytes(leaf)
+    siblings = [int(s) % R_MODULUS for s in siblings]
+    levels = len(siblings)
+    poseidon_membership_layout(params, levels + 1, len(leaf))
+    one = cs.one()
+    bit_values = [(byte >> i) & 1 for byte in leaf for i in range(8)]
+    # the walk in values first: the root is an instance variable and d_l needs cur_l, both allocated before the rows
+    values = _PsNullSystem()
+    c = _ps_leaf_digest(values, None, params, [(None, v) for v in bit_values], len(leaf)).value
+    cur_values = []
+    for lvl, s in enumerate(siblings):
+        cur_values.append(c)
+        a, b = (s, c) if (leaf_index >> lvl) & 1 else (c, s)
+        c = _ps_permute(values, None, params, [_PsLC({}, a), _PsLC({}, b), _PsLC()])[0].value
+    pub_root = c if root is None else int(root) % R_MODULUS
+    root_v = _PsLC({cs.new_input_variable(pub_root): 1}, pub_root)
+    leaf_bits = [(cs.new_input_variable(v), v) for v in bit_values]
+    dirs = [_PsLC({cs.new_witness_variable((leaf_index >> lvl) & 1): 1}, (leaf_index >> lvl) & 1) for lvl in range(levels)]
+    sibs = [_PsLC({cs.new_witness_variable(s): 1}, s) for s in siblings]
+    deltas = []
+    for lvl in range(levels):
+        v = dirs[lvl].value * (siblings[lvl] - cur_values[lvl]) % R_MODULUS
+        deltas.append(_PsLC({cs.new_witness_variable(v): 1}, v))
+    # rows
+    for var, _ in leaf_bits:
+        cs.enforce_constraint([(1, var)], [(1, one), (R_MODULUS - 1, var)], [])
+    cur = _ps_leaf_digest(cs, one, params, leaf_bits, len(leaf))
+    for lvl in range(levels):
+        b, s, d = dirs[lvl], sibs[lvl], deltas[lvl]
+        cs.enforce_constraint(b.terms, [(1, one), (R_MODULUS - 1, b.terms[0][1])], [])
+        cs.enforce_constraint(b.terms, _PsLC(s.coeffs, s.value).add(R_MODULUS - 1, cur).terms, d.terms)
+        left = _PsLC(cur.coeffs, cur.value).add(1, d)
+        right = _PsLC(s.coeffs, s.value).add(R_MODULUS - 1, d)
+        cur = _ps_permute(cs, one, params, [left, right, _PsLC()])[0]
+    cs.enforce_constraint(cur.terms, [(1, one)], root_v.terms)
+    return [pub_root] + bit_values
+
+
+class _PsNullSystem:
+    """A builder that records nothing: _ps_permute over it computes values only."""
+
+    def new_witness_variable(self, v):
+        return None
+
+    def enforce_constraint(self, a, b, c):
+        pass
+
+
+def _ps_leaf_digest(cs, one, params, bits, n):
+    """The bytes-form sponge over n bytes given as (variable, value) bits, one output: state[0] after the last permutation."""
+    state = [_PsLC(), _PsLC(), _PsLC()]
+    absorbed = _ps_absorb_bytes(one, bits, n)
+    for step in range((len(absorbed) + 1) // 2):
+        if step > 0:
+            state = _ps_permute(cs, one, params, state)
+        for k, e in enumerate(absorbed[2 * step:2 * step + 2]):
+            state[k].add(1, e)
+    return _ps_permute(cs, one, params, state)[0]
+
+
+def poseidon_membership_circuit(params, height=4, leaf=b"\xa7", leaf_index=0, siblings=None, seed=7, root=None):
+    """The circuit as a ConstraintSystem; without `siblings` they are random digests (the other leaves are not needed to prove one
+    path).  Returns (cs, public_inputs)."""
+    if siblings is None:
+        g = _SplitMix(seed)
+        siblings = [g.fr() for _ in range(height - 1)]
+    assert len(siblings) == height - 1
+    cs = ConstraintSystem()
+    public = build_poseidon_membership(cs, params, leaf, leaf_index, siblings, root)
+    return cs, public
+
+
+class PoseidonMerkleTreeVerification:
+    """The ConstraintSynthesizer of the Poseidon membership statement for MarlinInst.index / prove: constants = the sponge
+    parameters, public = root + leaf, witness = leaf index + authentication path."""
+
+    def __init__(self, params, root, leaf, leaf_index, authentication_path):
+        self.params, self.root, self.leaf, self.leaf_index = params, root, leaf, leaf_index
+        self.authentication_path = list(authentication_path)
+
+    def generate_constraints(self, cs):
+        build_poseidon_membership(cs, self.params, self.leaf, self.leaf_index, self.authentication_path, root=self.root)
 
 
 # ===================================================================================================================

@@ -16,6 +16,8 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_schnorr_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_poseidon { _p: [u8; 0] }
 #[repr(C)] pub struct swm_poseidon_circuit { _p: [u8; 0] }
+#[repr(C)] pub struct swm_poseidon_tree { _p: [u8; 0] }
+#[repr(C)] pub struct swm_poseidon_tree_circuit { _p: [u8; 0] }
 
 pub const SWM_OK: c_int = 0;
 pub const SWM_ERR_UNSATISFIED: c_int = -5;
@@ -238,6 +240,39 @@ extern "C" {
     pub fn swm_poseidon_prove(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_poseidon_circuit, input: *const u8,
                               rng: *mut swm_rng, flags: c_uint, outputs: *mut u8, proof_out: *mut u8, cap: usize,
                               len: *mut usize) -> c_int;
+    // the resident Poseidon Merkle tree (leaf digest: the byte sponge; inner node: the two-to-one form) and the path check
+    pub fn swm_poseidon_tree_create_blank(ctx: *mut swm_ctx, params: *const swm_poseidon, height: usize, leaf_len: usize,
+                                          out: *mut *mut swm_poseidon_tree) -> c_int;
+    pub fn swm_poseidon_tree_create_from_leaves(ctx: *mut swm_ctx, params: *const swm_poseidon, leaves: *const u8, leaf_len: usize,
+                                                n_leaves: usize, out: *mut *mut swm_poseidon_tree) -> c_int;
+    pub fn swm_poseidon_tree_destroy(ctx: *mut swm_ctx, tree: *mut swm_poseidon_tree);
+    pub fn swm_poseidon_tree_update(ctx: *mut swm_ctx, tree: *mut swm_poseidon_tree, indices: *const u64, leaves: *const u8,
+                                    leaf_len: usize, count: usize) -> c_int;
+    pub fn swm_poseidon_tree_root(ctx: *mut swm_ctx, tree: *const swm_poseidon_tree, root: *mut u8) -> c_int;
+    pub fn swm_poseidon_tree_paths(ctx: *mut swm_ctx, tree: *const swm_poseidon_tree, indices: *const u64, count: usize,
+                                   siblings: *mut u8) -> c_int;
+    pub fn swm_poseidon_tree_nodes(ctx: *mut swm_ctx, tree: *const swm_poseidon_tree, nodes: *mut u8) -> c_int;
+    pub fn swm_poseidon_tree_dev_nodes(tree: *const swm_poseidon_tree, d_nodes: *mut *mut c_void, n_nodes: *mut usize) -> c_int;
+    pub fn swm_poseidon_verify_paths(ctx: *mut swm_ctx, params: *const swm_poseidon, height: usize, roots: *const u8,
+                                     root_stride: usize, leaves: *const u8, leaf_len: usize, indices: *const u64,
+                                     siblings: *const u8, count: usize, ok: *mut u8, status: *mut u32) -> c_int;
+    // the membership circuit over that tree: public input (root, leaf bits); witness: Montgomery limbs
+    pub fn swm_poseidon_tree_circuit_shape(full_rounds: usize, partial_rounds: usize, alpha: u64, height: usize, leaf_len: usize,
+                                           num_instance: *mut usize, num_witness: *mut usize, num_constraints: *mut usize) -> c_int;
+    pub fn swm_poseidon_tree_circuit_create(ctx: *mut swm_ctx, params: *const swm_poseidon, height: usize, leaf_len: usize,
+                                            out: *mut *mut swm_poseidon_tree_circuit) -> c_int;
+    pub fn swm_poseidon_tree_circuit_destroy(ctx: *mut swm_ctx, circuit: *mut swm_poseidon_tree_circuit);
+    pub fn swm_poseidon_tree_witness(ctx: *mut swm_ctx, circuit: *const swm_poseidon_tree_circuit, leaves: *const u8,
+                                     indices: *const u64, siblings: *const u8, count: usize, witness: *mut u64,
+                                     roots: *mut u8) -> c_int;
+    pub fn swm_poseidon_tree_witness_at(ctx: *mut swm_ctx, circuit: *const swm_poseidon_tree_circuit, tree: *const swm_poseidon_tree,
+                                        leaves: *const u8, indices: *const u64, count: usize, witness: *mut u64) -> c_int;
+    pub fn swm_poseidon_tree_prove(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_poseidon_tree_circuit, root: *const u8,
+                                   leaf: *const u8, index: u64, siblings: *const u8, rng: *mut swm_rng, flags: c_uint,
+                                   proof_out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    pub fn swm_poseidon_tree_prove_at(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_poseidon_tree_circuit,
+                                      tree: *const swm_poseidon_tree, leaf: *const u8, index: u64, rng: *mut swm_rng, flags: c_uint,
+                                      proof_out: *mut u8, cap: usize, len: *mut usize) -> c_int;
     // the Blake2s random oracle, batched, and its circuit's witness (no handle: the shape follows from input_len)
     pub fn swm_blake2s_hash(ctx: *mut swm_ctx, inputs: *const u8, input_len: usize, count: usize, digests: *mut u8) -> c_int;
     pub fn swm_blake2s_hash_dev(ctx: *mut swm_ctx, d_inputs: *const c_void, input_len: usize, count: usize,
