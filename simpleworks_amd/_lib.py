@@ -139,6 +139,17 @@ ABI = {
     "swm_schnorr_witness_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "swm_schnorr_prove": (_int, [_vp, _vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _vp, ctypes.c_uint,
                                  ctypes.POINTER(ctypes.c_uint8), _sz, ctypes.POINTER(_sz)]),
+    "swm_elgamal_circuit_shape": (_int, [ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "swm_elgamal_circuit_create": (_int, [_vp, _vp, ctypes.POINTER(_vp)]),
+    "swm_elgamal_circuit_destroy": (None, [_vp, _vp]),
+    "swm_elgamal_witness": (_int, [_vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_elgamal_witness_to": (_int, [_vp, _vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_elgamal_witness_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "swm_elgamal_witness_to_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "swm_elgamal_prove": (_int, [_vp, _vp, _vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _vp, ctypes.c_uint,
+                                 ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), _sz, ctypes.POINTER(_sz)]),
+    "swm_elgamal_prove_to": (_int, [_vp, _vp, _vp, _vp, ctypes.c_void_p, ctypes.c_void_p, _vp, ctypes.c_uint,
+                                    ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), _sz, ctypes.POINTER(_sz)]),
     "swm_poseidon_create": (_int, [_vp, _sz, _sz, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_vp)]),
     "swm_poseidon_destroy": (None, [_vp, _vp]),
     "swm_poseidon_hash_fr": (_int, [_vp, _vp, ctypes.c_void_p, _sz, _sz, _sz, ctypes.c_void_p]),
@@ -786,6 +797,44 @@ class Context:
         self._check(self.lib.swm_schnorr_witness_dev(self.h, handle, d_public_keys.ptr, d_messages.ptr if d_messages else None,
                                                      d_signatures.ptr, count, d_witness.ptr, d_ok.ptr if d_ok else None,
                                                      d_status.ptr if d_status else None), "swm_schnorr_witness_dev")
+
+    # ---- ElGamal encryption witness (include/swmarlin.h; simpleworks_amd/elgamal.py, ElGamalCircuit, is the caller-facing mirror)
+    def elgamal_circuit_create(self, params_handle):
+        h = _vp()
+        self._check(self.lib.swm_elgamal_circuit_create(self.h, params_handle, ctypes.byref(h)), "swm_elgamal_circuit_create")
+        return h
+
+    def elgamal_circuit_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_elgamal_circuit_destroy(self.h, handle)
+
+    def elgamal_witness(self, handle, num_witness, public_keys, messages, randomness, key_handle=None):
+        """messages uint8 [count, 64], randomness uint8 [count, 32]; public_keys uint8 [count, 64], or key_handle: a resident key
+        for the whole batch -> (witness uint64 [count, num_witness, 4] Montgomery limbs, ciphertexts uint8 [count, 128])."""
+        m = self._rows(messages, 64)
+        n = m.shape[0]
+        r = self._rows(randomness, 32, n)
+        witness = np.empty((n, num_witness, 4), dtype=np.uint64)
+        ct = np.empty((n, 128), dtype=np.uint8)
+        if key_handle is not None:
+            self._check(self.lib.swm_elgamal_witness_to(self.h, handle, key_handle, m.ctypes.data, r.ctypes.data, n, witness.ctypes.data,
+                                                        ct.ctypes.data), "swm_elgamal_witness_to")
+        else:
+            pk = self._rows(public_keys, 64, n)
+            self._check(self.lib.swm_elgamal_witness(self.h, handle, pk.ctypes.data, m.ctypes.data, r.ctypes.data, n, witness.ctypes.data,
+                                                     ct.ctypes.data), "swm_elgamal_witness")
+        return witness, ct
+
+    def elgamal_witness_dev(self, handle, d_public_keys, d_messages, d_randomness, count, d_witness, d_ciphertexts, d_status=None,
+                            key_handle=None):
+        """The device form; with key_handle (a resident key) d_public_keys is not read and may be None."""
+        status = d_status.ptr if d_status else None
+        if key_handle is not None:
+            self._check(self.lib.swm_elgamal_witness_to_dev(self.h, handle, key_handle, d_messages.ptr, d_randomness.ptr, count, d_witness.ptr,
+                                                            d_ciphertexts.ptr, status), "swm_elgamal_witness_to_dev")
+        else:
+            self._check(self.lib.swm_elgamal_witness_dev(self.h, handle, d_public_keys.ptr, d_messages.ptr, d_randomness.ptr, count,
+                                                         d_witness.ptr, d_ciphertexts.ptr, status), "swm_elgamal_witness_dev")
 
     # ---- Poseidon sponge (include/swmarlin.h; simpleworks_amd/hash.py, PoseidonSponge, is the caller-facing mirror)
     def poseidon_create(self, full_rounds, partial_rounds, alpha, mds, ark):

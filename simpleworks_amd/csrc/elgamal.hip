@@ -20,15 +20,11 @@
 #include <hip/hip_runtime.h>
 
 #include "context.h"
-#include "ed_mul.cuh"
-#include "swmarlin.h"
+#include <string.h>
 
-struct swm_elgamal {
-    void* d_table = nullptr;  // 32 x 256 rows (swm::EdRow): row (w, v) = v 2^(8 w) G
-};
-struct swm_elgamal_key {
-    void* d_table = nullptr;  // the same of one public key
-};
+#include "ed_mul.cuh"
+#include "elgamal.h"
+#include "swmarlin.h"
 
 namespace swm {
 
@@ -266,7 +262,9 @@ int swm_elgamal_create(swm_ctx* ctx, const uint8_t generator_xy[64], swm_elgamal
 void swm_elgamal_destroy(swm_ctx* ctx, swm_elgamal* p) { destroy(ctx, p); }
 
 int swm_elgamal_key_create(swm_ctx* ctx, const uint8_t public_key_xy[64], swm_elgamal_key** out) {
-    return create(ctx, public_key_xy, out, "elgamal_key_create");
+    SWM_TRY(create(ctx, public_key_xy, out, "elgamal_key_create"));
+    memcpy((*out)->xy, public_key_xy, 64);  // canonical and on the curve: table_of accepted it
+    return SWM_OK;
 }
 
 void swm_elgamal_key_destroy(swm_ctx* ctx, swm_elgamal_key* key) { destroy(ctx, key); }

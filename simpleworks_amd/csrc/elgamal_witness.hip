@@ -1,0 +1,434 @@
+// elgamal_witness.hip — the witness of the ElGamal encryption circuit, synthesised on the GPU: the step between an encryption
+// (elgamal.hip) and the proof that its ciphertext is well formed (marlin.hip).
+//
+// The statement is ark-crypto-primitives' ElGamalEncGadget's: "I know a message point m and randomness r such that (c1, c2) =
+// (r G, m + r pk)", pk, c1 and c2 public.  The prover reads only the ASSIGNMENT (the matrices are the key's) and the circuit has
+// one shape, so what is left per proof is the witness vector and the ciphertext it proves.  Order and values are those of
+// simpleworks_amd/workloads.py, build_elgamal_encryption: that function is the specification, host/elgamal_shape.h the offsets.
+// The circuit is the curve half of the Schnorr verification circuit, and so is the kernel (ed_witness.cuh holds what both share).
+//
+// On the GPU: one workgroup of 256 lanes per encryption, lane i on bit i of r.  Two instantiations of one body:
+//   fix   lane i takes r_i ? 2^i G : identity from the generator's resident table (swm_elgamal: window i / 8, entry
+//         1 << (i % 8)); an inclusive scan gives the prefix sums, ONE shared inversion makes them affine, and the six witnesses
+//         of step i are pointwise from P_{i-1}, P_i.  Lane 255 then holds c1 = r G.
+//   dbl   per-item key: 2^i pk is sequential — lane 0 doubles in extended coordinates into LDS and a second shared inversion
+//         makes all 256 affine.  Resident key (swm_elgamal_key): lane i READS 2^i pk from the key's table, the same row of the
+//         same layout, already affine (x = (ypx - ymx) / 2, y = (ypx + ymx) / 2): no chain, no inversion, no LDS for it.
+//         xy, xx, yy and the next point are pointwise either way; the circuit keeps its dbl rows because the key is a variable.
+//   sel / add   Q_i = r_i ? P_i : identity, a scan for acc_i, the last shared inversion, seven pointwise witnesses per step.
+//   sum   c2 = m + acc_255 on the last lane, in extended coordinates BEFORE that inversion: the lane hands the product of both
+//         Z to it and takes the two inverses apart with two multiplications, so the sum costs no inversion of its own.
+// The ciphertext leaves the last lane in standard form, in the byte order of swm_elgamal_encrypt.
+// The law is complete (ed.cuh): r = 0, the identity, keys and messages of order 2 and 4 or outside the prime subgroup and
+// c2 = identity take the common path and no Z is zero.  There is no unsatisfied case: the kernel computes the ciphertext.
+//
+// The domain of r: ANY 256-bit value.  The circuit multiplies by the integer, unreduced, and has no range check (as s and e in
+// the Schnorr circuit): lanes 251 .. 255 are lanes like the others.  For r < l the ciphertext bytes are swm_elgamal_encrypt's;
+// for r >= l that call refuses, and this one proves the integer multiple (on a key of the prime subgroup: r mod l).
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <memory>
+
+#include "context.h"
+#include "ed.cuh"
+#include "ed_witness.cuh"
+#include "elgamal.h"
+#include "ff.cuh"
+#include "frinv.cuh"
+#include "host/elgamal_shape.h"
+#include "swmarlin.h"
+
+struct swm_elgamal_circuit {
+    const swm_elgamal* params = nullptr;
+    swm::ElGamalShape shape;
+};
+
+namespace swm {
+
+// the doubling chain of a per-item key, extended (T is not needed to go affine); a resident key needs none
+template <bool RESIDENT> struct EwChain {
+    Fr px[SV_LANES], py[SV_LANES], pz[SV_LANES];
+};
+template <> struct EwChain<true> {};
+
+template <bool RESIDENT> struct EwShared : SvScanShared, EwChain<RESIDENT> {
+    Fr ax[SV_LANES], ay[SV_LANES];  // affine points handed to the neighbouring lane
+    Fr mx, my;                      // the message, for the last lane
+    uint32_t rbits[8];
+    uint32_t bad;
+};
+
+struct EwParams {
+    const EdRow* table;      // the generator's: [32 windows][256], row (w, v) = v 2^(8 w) G
+    const EdRow* key_table;  // the resident key's, same layout (RESIDENT only)
+    Fr k2d, d, half;
+};
+
+// 64 bytes x || y (4-byte aligned) -> the point in Montgomery form, or false for what the host form refuses: a coordinate that
+// is no canonical field element, a point off the curve
+SWM_HD bool ew_load_point(const uint32_t* xy, const Fr& d, Fr* x, Fr* y) {
+    uint32_t xs[8], ys[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        xs[i] = xy[i];
+        ys[i] = xy[8 + i];
+    }
+    return sv_canonical(xs, x) && sv_canonical(ys, y) && sv_on_curve(*x, *y, d);
+}
+
+// Block p = encryption p.  keys (per-item form only), msgs: 64 bytes each; rs: 32 bytes each; cts: 128 bytes each; all 4-byte
+// aligned, the witness 16-byte aligned.
+template <bool RESIDENT>
+__global__ void __launch_bounds__(SV_LANES) elgamal_witness_kernel(EwParams P, const uint8_t* __restrict__ keys, const uint8_t* __restrict__ msgs,
+                                                                   const uint8_t* __restrict__ rs, Fr* __restrict__ witness,
+                                                                   uint8_t* __restrict__ cts, uint32_t* __restrict__ status) {
+    __shared__ EwShared<RESIDENT> sh;
+    const unsigned tid = threadIdx.x;
+    const size_t item = blockIdx.x;
+    Fr* w = witness + item * EW_NUM_WITNESS;
+    uint32_t* ct = reinterpret_cast<uint32_t*>(cts + 128 * item);
+    const Fr one = fp_one<Fr>(), zero = fp_zero<Fr>();
+
+    if (tid < 8) sh.rbits[tid] = reinterpret_cast<const uint32_t*>(rs + 32 * item)[tid];
+    Fr kx = zero, ky = one;  // the key on lane 0 (per-item form)
+    if (tid == 0) {
+        Fr mx = zero, my = one;
+        bool good = ew_load_point(reinterpret_cast<const uint32_t*>(msgs + 64 * item), P.d, &mx, &my);
+        if (!RESIDENT) good = ew_load_point(reinterpret_cast<const uint32_t*>(keys + 64 * item), P.d, &kx, &ky) && good;
+        sh.mx = mx;
+        sh.my = my;
+        sh.bad = good ? 0u : 1u;
+    }
+    __syncthreads();
+    if (sh.bad) {
+        uint4* wz = reinterpret_cast<uint4*>(w);
+        for (size_t i = tid; i < 2 * EW_NUM_WITNESS; i += SV_LANES) wz[i] = make_uint4(0, 0, 0, 0);
+        if (tid < 32) ct[tid] = 0;
+        if (status && tid == 0) status[item] = 1;
+        return;
+    }
+    if (status && tid == 0) status[item] = 0;
+    const unsigned bit = (sh.rbits[tid >> 5] >> (tid & 31)) & 1u;
+    const unsigned row_at = ((tid >> 3) << 8) + (1u << (tid & 7));  // 2^tid of a tabulated base
+
+    // msg, rnd
+    if (tid == 0) {
+        const Fr mx = sh.mx, my = sh.my;
+        w[EW_MSG_AT] = mx;
+        w[EW_MSG_AT + 1] = my;
+        w[EW_MSG_AT + 2] = fp_sqr(mx);
+        w[EW_MSG_AT + 3] = fp_sqr(my);
+    }
+    w[EW_RND_AT + tid] = bit ? one : zero;
+
+    // fix: prefix sums of r_i 2^i G
+    const EdRow* row = P.table + row_at;
+    Fr fx, fy;  // P_tid, affine
+    {
+        EdExt acc = ed_identity();
+        if (bit) ed_madd(acc, *row);
+        acc = sv_scan(acc, P.k2d, sh);
+        const Fr zi = sv_batch_inv(acc.z, sh);
+        fx = fp_mul(acc.x, zi);
+        fy = fp_mul(acc.y, zi);
+        sh.ax[tid] = fx;
+        sh.ay[tid] = fy;
+        __syncthreads();
+        if (tid) {
+            Fr* o = w + EW_FIX_AT + EW_FIX_STEP * (size_t)(tid - 1);
+            const Fr X = sh.ax[tid - 1], Y = sh.ay[tid - 1];
+            const Fr t = fp_mul(X, Y);
+            o[0] = t;
+            if (bit) {
+                const EdRow g = *row;
+                const Fr cx = fp_mul(P.half, fp_sub(g.ypx, g.ymx)), cy = fp_mul(P.half, fp_add(g.ypx, g.ymx));
+                const Fr cym1 = fp_sub(cy, one);
+                o[1] = t;
+                o[2] = fp_add(fp_mul(cym1, X), fp_mul(cx, Y));
+                o[3] = fp_add(fp_mul(cym1, Y), fp_mul(cx, X));
+            } else {
+                o[1] = zero;
+                o[2] = zero;
+                o[3] = zero;
+            }
+            o[4] = fx;
+            o[5] = fy;
+        }
+    }
+
+    // dbl: P_0 = pk, P_{i+1} = 2 P_i
+    Fr bx, by;  // P_tid = 2^tid pk, affine
+    if constexpr (RESIDENT) {
+        const EdRow g = P.key_table[row_at];
+        bx = fp_mul(P.half, fp_sub(g.ypx, g.ymx));
+        by = fp_mul(P.half, fp_add(g.ypx, g.ymx));
+        __syncthreads();  // ax / ay of the fixed base have been read
+    } else {
+        if (tid == 0) {  // sequential, one lane
+            EdExt p = sv_from_affine(kx, ky);
+#pragma unroll 1
+            for (unsigned i = 0; i < SV_LANES; i++) {
+                sh.px[i] = p.x;
+                sh.py[i] = p.y;
+                sh.pz[i] = p.z;
+                ed_dbl(p);
+            }
+        }
+        __syncthreads();  // also: ax / ay of the fixed base have been read
+        const Fr zi = sv_batch_inv(sh.pz[tid], sh);
+        bx = fp_mul(sh.px[tid], zi);
+        by = fp_mul(sh.py[tid], zi);
+    }
+    {
+        sh.ax[tid] = bx;
+        sh.ay[tid] = by;
+        __syncthreads();
+        const Fr xx = fp_sqr(bx), yy = fp_sqr(by);
+        if (tid == 0) {  // key: the squares of pk's coordinates
+            w[EW_KEY_AT] = xx;
+            w[EW_KEY_AT + 1] = yy;
+        }
+        if (tid + 1 < SV_LANES) {
+            Fr* o = w + EW_DBL_AT + EW_DBL_STEP * (size_t)tid;
+            o[0] = fp_mul(bx, by);
+            o[1] = xx;
+            o[2] = yy;
+            o[3] = sh.ax[tid + 1];
+            o[4] = sh.ay[tid + 1];
+        }
+    }
+
+    // sel, add: Q_i = r_i P_i, acc_i = acc_{i-1} + Q_i;  sum: c2 = m + acc_255 on the last lane
+    const Fr qx = bit ? bx : zero, qy = bit ? by : one;
+    w[EW_SEL_AT + EW_SEL_STEP * (size_t)tid] = qx;
+    w[EW_SEL_AT + EW_SEL_STEP * (size_t)tid + 1] = qy;
+    {
+        const bool last = tid == SV_LANES - 1;
+        EdExt acc = sv_from_affine(qx, qy);
+        acc = sv_scan(acc, P.k2d, sh);  // (its barriers: ax / ay of the doubling chain have been read)
+        EdExt sum = acc;
+        Fr z = acc.z;
+        if (last) {
+            sum = ed_add(sv_from_affine(sh.mx, sh.my), acc, P.k2d);
+            z = fp_mul(acc.z, sum.z);  // one inversion for both: 1 / Z_acc = Z_sum / z, 1 / Z_sum = Z_acc / z
+        }
+        Fr zi = sv_batch_inv(z, sh);
+        Fr zs = zi;
+        if (last) {
+            zs = fp_mul(zi, acc.z);
+            zi = fp_mul(zi, sum.z);
+        }
+        const Fr cx = fp_mul(acc.x, zi), cy = fp_mul(acc.y, zi);  // acc_tid, affine
+        sh.ax[tid] = cx;
+        sh.ay[tid] = cy;
+        __syncthreads();
+        if (tid) sv_add_witnesses(w + EW_ADD_AT + EW_ADD_STEP * (size_t)(tid - 1), sh.ax[tid - 1], sh.ay[tid - 1], qx, qy, cx, cy);
+        if (last) {
+            const Fr sx = fp_mul(sum.x, zs), sy = fp_mul(sum.y, zs);
+            sv_add_witnesses(w + EW_SUM_AT, sh.mx, sh.my, cx, cy, sx, sy);
+            const Fr c1x = fp_to_std(fx), c1y = fp_to_std(fy), c2x = fp_to_std(sx), c2y = fp_to_std(sy);
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                ct[i] = c1x.v[i];
+                ct[8 + i] = c1y.v[i];
+                ct[16 + i] = c2x.v[i];
+                ct[24 + i] = c2y.v[i];
+            }
+        }
+    }
+}
+
+// key = NULL: the per-item form (d_keys: 64 bytes each); otherwise every item is encrypted to the resident key and d_keys is unused
+static int elgamal_witness_run(swm_ctx* ctx, const swm_elgamal_circuit* c, const swm_elgamal_key* key, const uint8_t* d_keys,
+                               const uint8_t* d_msgs, const uint8_t* d_rs, size_t count, Fr* d_witness, uint8_t* d_cts, uint32_t* d_status) {
+    if (!count) return SWM_OK;
+    if (count > 0x7FFFFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "elgamal_witness: %zu encryptions in one call", count);
+    EwParams P;
+    P.table = reinterpret_cast<const EdRow*>(c->params->d_table);
+    P.key_table = key ? reinterpret_cast<const EdRow*>(key->d_table) : nullptr;
+    P.k2d = fp_from_u64<Fr>(2 * ED_D);
+    P.d = fp_from_u64<Fr>(ED_D);
+    P.half = fp_inv(fp_from_u64<Fr>(2));
+    if (key)
+        SWM_LAUNCH(ctx, "elgamal_witness_to", elgamal_witness_kernel<true>, dim3((unsigned)count), dim3(SV_LANES), 0, P, d_keys, d_msgs, d_rs,
+                   d_witness, d_cts, d_status);
+    else
+        SWM_LAUNCH(ctx, "elgamal_witness", elgamal_witness_kernel<false>, dim3((unsigned)count), dim3(SV_LANES), 0, P, d_keys, d_msgs, d_rs,
+                   d_witness, d_cts, d_status);
+    return SWM_OK;
+}
+
+// the host form's check: what the device form reports per item
+static int elgamal_check_points(swm_ctx* ctx, const char* what, const char* which, const uint8_t* points, size_t count) {
+    const Fr d = fp_from_u64<Fr>(ED_D);
+    for (size_t p = 0; p < count; p++) {
+        uint32_t xy[16];
+        for (int i = 0; i < 16; i++) {
+            const uint8_t* a = points + 64 * p + 4 * i;
+            xy[i] = (uint32_t)a[0] | (uint32_t)a[1] << 8 | (uint32_t)a[2] << 16 | (uint32_t)a[3] << 24;
+        }
+        Fr x, y;
+        if (!ew_load_point(xy, d, &x, &y))
+            return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: item %zu: the %s is not a point of ed-on-BLS12-377", what, p, which);
+    }
+    return SWM_OK;
+}
+
+// inputs of `count` encryptions into one staging buffer: keys (per-item form) | messages | randomness, all word-aligned
+static int elgamal_stage_inputs(swm_ctx* ctx, const uint8_t* keys, const uint8_t* msgs, const uint8_t* rs, size_t count, const uint8_t** d_keys,
+                                const uint8_t** d_msgs, const uint8_t** d_rs) {
+    const size_t n_key = keys ? 64 * count : 0;
+    uint8_t* d_in = nullptr;
+    SWM_TRY(scratch(ctx, "stage.a", n_key + 96 * count + 16, (void**)&d_in));
+    if (keys) SWM_HIP(ctx, hipMemcpyAsync(d_in, keys, n_key, hipMemcpyHostToDevice, ctx->stream));
+    SWM_HIP(ctx, hipMemcpyAsync(d_in + n_key, msgs, 64 * count, hipMemcpyHostToDevice, ctx->stream));
+    SWM_HIP(ctx, hipMemcpyAsync(d_in + n_key + 64 * count, rs, 32 * count, hipMemcpyHostToDevice, ctx->stream));
+    *d_keys = keys ? d_in : nullptr;
+    *d_msgs = d_in + n_key;
+    *d_rs = d_in + n_key + 64 * count;
+    return SWM_OK;
+}
+
+// The host form holds at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
+static constexpr size_t EW_STAGE_BYTES = (size_t)1 << 30;
+
+static int elgamal_witness_host(swm_ctx* ctx, const swm_elgamal_circuit* c, const swm_elgamal_key* key, const uint8_t* keys, const uint8_t* msgs,
+                                const uint8_t* rs, size_t count, uint64_t* witness, uint8_t* cts, const char* what) {
+    if (!ctx || !c || (count && (!msgs || !rs || !witness || !cts || (!key && !keys)))) return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: bad arguments", what);
+    if (!count) return SWM_OK;
+    if (!key) SWM_TRY(elgamal_check_points(ctx, what, "public key", keys, count));
+    SWM_TRY(elgamal_check_points(ctx, what, "message", msgs, count));
+    SWM_ON_DEVICE(ctx);
+    const size_t item = EW_NUM_WITNESS * sizeof(Fr);
+    const size_t per = EW_STAGE_BYTES / item;  // encryptions per chunk
+    for (size_t base = 0; base < count; base += per) {
+        const size_t n = count - base < per ? count - base : per;
+        const uint8_t *d_keys, *d_msgs, *d_rs;
+        SWM_TRY(elgamal_stage_inputs(ctx, key ? nullptr : keys + 64 * base, msgs + 64 * base, rs + 32 * base, n, &d_keys, &d_msgs, &d_rs));
+        uint8_t* d_out = nullptr;
+        SWM_TRY(scratch(ctx, "elgamal.w", n * item + 128 * n, (void**)&d_out));
+        SWM_TRY(elgamal_witness_run(ctx, c, key, d_keys, d_msgs, d_rs, n, (Fr*)d_out, d_out + n * item, nullptr));
+        SWM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t*>(witness) + base * item, d_out, n * item, hipMemcpyDeviceToHost, ctx->stream));
+        SWM_HIP(ctx, hipMemcpyAsync(cts + 128 * base, d_out + n * item, 128 * n, hipMemcpyDeviceToHost, ctx->stream));
+        SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffers are reused by the next chunk
+    }
+    return SWM_OK;
+}
+
+static int elgamal_witness_device(swm_ctx* ctx, const swm_elgamal_circuit* c, const swm_elgamal_key* key, const void* d_keys, const void* d_msgs,
+                                  const void* d_rs, size_t count, void* d_witness, void* d_cts, void* d_status, const char* what) {
+    if (!ctx || !c || (count && (!d_msgs || !d_rs || !d_witness || !d_cts || (!key && !d_keys))))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: bad arguments", what);
+    if ((((uintptr_t)d_keys | (uintptr_t)d_msgs | (uintptr_t)d_rs | (uintptr_t)d_cts | (uintptr_t)d_status) & 3) || ((uintptr_t)d_witness & 15))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: the witness must be 16-byte aligned, every other buffer 4-byte aligned", what);
+    SWM_ON_DEVICE(ctx);
+    return elgamal_witness_run(ctx, c, key, (const uint8_t*)d_keys, (const uint8_t*)d_msgs, (const uint8_t*)d_rs, count, (Fr*)d_witness,
+                               (uint8_t*)d_cts, (uint32_t*)d_status);
+}
+
+static int elgamal_prove(swm_ctx* ctx, const swm_pk* pk, const swm_elgamal_circuit* c, const swm_elgamal_key* key, const uint8_t* public_key_xy,
+                         const uint8_t* message_xy, const uint8_t* randomness, swm_rng* rng, unsigned flags, uint8_t* ciphertext_out,
+                         uint8_t* proof_out, size_t cap, size_t* len, const char* what) {
+    if (!ctx || !pk || !c || !public_key_xy || !message_xy || !randomness || !rng || !ciphertext_out || !proof_out || !len)
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: bad arguments", what);
+    if (!key) SWM_TRY(elgamal_check_points(ctx, what, "public key", public_key_xy, 1));
+    SWM_TRY(elgamal_check_points(ctx, what, "message", message_xy, 1));
+    const ElGamalShape& s = c->shape;
+    Fr* d_w = nullptr;
+    uint8_t ct[128];
+    {
+        SWM_ON_DEVICE(ctx);
+        const uint8_t *d_keys, *d_msgs, *d_rs;
+        uint8_t* d_out = nullptr;
+        SWM_TRY(scratch(ctx, "elgamal.w", s.num_witness * sizeof(Fr) + 128, (void**)&d_out));
+        SWM_TRY(elgamal_stage_inputs(ctx, key ? nullptr : public_key_xy, message_xy, randomness, 1, &d_keys, &d_msgs, &d_rs));
+        d_w = reinterpret_cast<Fr*>(d_out);
+        SWM_TRY(elgamal_witness_run(ctx, c, key, d_keys, d_msgs, d_rs, 1, d_w, d_out + s.num_witness * sizeof(Fr), nullptr));
+        SWM_HIP(ctx, hipMemcpyAsync(ct, d_out + s.num_witness * sizeof(Fr), 128, hipMemcpyDeviceToHost, ctx->stream));
+        SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    // public input: one, pk, c1, c2 (in the prover's Montgomery form); every coordinate is canonical — checked above, or the kernel's
+    Fr inst[EW_NUM_INSTANCE];
+    inst[0] = fp_one<Fr>();
+    for (int j = 0; j < 6; j++) {
+        const uint8_t* a = j < 2 ? public_key_xy + 32 * j : ct + 32 * (j - 2);
+        uint32_t wds[8];
+        for (int i = 0; i < 8; i++) wds[i] = (uint32_t)a[4 * i] | (uint32_t)a[4 * i + 1] << 8 | (uint32_t)a[4 * i + 2] << 16 | (uint32_t)a[4 * i + 3] << 24;
+        if (!sv_canonical(wds, &inst[1 + j])) return set_err(ctx, SWM_ERR_INTERNAL, "%s: a coordinate of the instance is not canonical", what);
+    }
+    memcpy(ciphertext_out, ct, 128);
+    swm_r1cs cs = {};
+    cs.num_instance = s.num_instance;
+    cs.num_witness = s.num_witness;
+    cs.num_constraints = s.num_constraints;
+    cs.instance = reinterpret_cast<const uint64_t*>(inst);
+    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
+    struct DevWitnessScope {
+        swm_ctx* c;
+        ~DevWitnessScope() { c->witness_dev = nullptr; }
+    } scope{ctx};
+    ctx->witness_dev = d_w;
+    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+}
+
+}  // namespace swm
+
+using namespace swm;
+
+extern "C" {
+
+int swm_elgamal_circuit_create(swm_ctx* ctx, const swm_elgamal* params, swm_elgamal_circuit** out) {
+    if (!ctx || !params || !out) return set_err(ctx, SWM_ERR_INVALID_ARG, "elgamal_circuit_create: bad arguments");
+    std::unique_ptr<swm_elgamal_circuit> c(new swm_elgamal_circuit);
+    c->params = params;
+    c->shape = elgamal_shape();
+    *out = c.release();
+    return SWM_OK;
+}
+
+void swm_elgamal_circuit_destroy(swm_ctx* ctx, swm_elgamal_circuit* c) {
+    if (!c) return;
+    DeviceGuard guard(ctx);
+    if (ctx) drain_streams(ctx);
+    delete c;
+}
+
+int swm_elgamal_witness(swm_ctx* ctx, const swm_elgamal_circuit* c, const uint8_t* public_keys_xy, const uint8_t* messages_xy,
+                        const uint8_t* randomness, size_t count, uint64_t* witness, uint8_t* ciphertexts) {
+    return elgamal_witness_host(ctx, c, nullptr, public_keys_xy, messages_xy, randomness, count, witness, ciphertexts, "elgamal_witness");
+}
+
+int swm_elgamal_witness_to(swm_ctx* ctx, const swm_elgamal_circuit* c, const swm_elgamal_key* key, const uint8_t* messages_xy,
+                           const uint8_t* randomness, size_t count, uint64_t* witness, uint8_t* ciphertexts) {
+    if (!key) return set_err(ctx, SWM_ERR_INVALID_ARG, "elgamal_witness_to: bad arguments");
+    return elgamal_witness_host(ctx, c, key, nullptr, messages_xy, randomness, count, witness, ciphertexts, "elgamal_witness_to");
+}
+
+int swm_elgamal_witness_dev(swm_ctx* ctx, const swm_elgamal_circuit* c, const void* d_public_keys, const void* d_messages, const void* d_randomness,
+                            size_t count, void* d_witness, void* d_ciphertexts, void* d_status) {
+    return elgamal_witness_device(ctx, c, nullptr, d_public_keys, d_messages, d_randomness, count, d_witness, d_ciphertexts, d_status,
+                                  "elgamal_witness");
+}
+
+int swm_elgamal_witness_to_dev(swm_ctx* ctx, const swm_elgamal_circuit* c, const swm_elgamal_key* key, const void* d_messages,
+                               const void* d_randomness, size_t count, void* d_witness, void* d_ciphertexts, void* d_status) {
+    if (!key) return set_err(ctx, SWM_ERR_INVALID_ARG, "elgamal_witness_to: bad arguments");
+    return elgamal_witness_device(ctx, c, key, nullptr, d_messages, d_randomness, count, d_witness, d_ciphertexts, d_status, "elgamal_witness_to");
+}
+
+int swm_elgamal_prove(swm_ctx* ctx, const swm_pk* pk, const swm_elgamal_circuit* c, const uint8_t public_key_xy[64], const uint8_t message_xy[64],
+                      const uint8_t randomness[32], swm_rng* rng, unsigned flags, uint8_t ciphertext_out[128], uint8_t* proof_out, size_t cap,
+                      size_t* len) {
+    return elgamal_prove(ctx, pk, c, nullptr, public_key_xy, message_xy, randomness, rng, flags, ciphertext_out, proof_out, cap, len,
+                         "elgamal_prove");
+}
+
+int swm_elgamal_prove_to(swm_ctx* ctx, const swm_pk* pk, const swm_elgamal_circuit* c, const swm_elgamal_key* key, const uint8_t message_xy[64],
+                         const uint8_t randomness[32], swm_rng* rng, unsigned flags, uint8_t ciphertext_out[128], uint8_t* proof_out, size_t cap,
+                         size_t* len) {
+    if (!key) return set_err(ctx, SWM_ERR_INVALID_ARG, "elgamal_prove_to: bad arguments");
+    return elgamal_prove(ctx, pk, c, key, key->xy, message_xy, randomness, rng, flags, ciphertext_out, proof_out, cap, len, "elgamal_prove_to");
+}
+
+}  // extern "C"

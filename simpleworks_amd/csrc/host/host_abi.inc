@@ -8,6 +8,7 @@
 #include <new>
 #include "merkle_shape.h"
 #include "schnorr_shape.h"
+#include "elgamal_shape.h"
 #include "poseidon_shape.h"
 #include "poseidon_tree_shape.h"
 #include "blake2s_shape.h"
@@ -203,6 +204,18 @@ int swm_schnorr_circuit_shape(size_t msg_len, int salted, size_t* num_instance, 
     SchnorrShape s;
     if (!schnorr_shape(msg_len, salted != 0, &s))
         return set_err(none, SWM_ERR_INVALID_ARG, "schnorr_circuit_shape: msg_len %zu (at most %zu)", msg_len, (size_t)SV_MAX_MSG_LEN);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// The ElGamal encryption circuit's one shape (elgamal_shape.h; the layout is build_elgamal_encryption's)
+int swm_elgamal_circuit_shape(size_t* num_instance, size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "elgamal_circuit_shape: NULL output");
+    const ElGamalShape s = elgamal_shape();
     *num_instance = s.num_instance;
     *num_witness = s.num_witness;
     *num_constraints = s.num_constraints;

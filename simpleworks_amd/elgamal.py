@@ -9,7 +9,8 @@ ElGamal<EdwardsProjective>, as tests/encrypt.rs:11-28 calls it), name for name:
     decrypt(params, sk, ciphertext)     -> message = c2 - sk c1
 plus keygen_many / encrypt_many / decrypt_many, the batched forms: one GPU lane per key, encryption or decryption.  A caller with
 many messages for one recipient hands encrypt_many a ResidentKey: the key is tabulated once on the GPU and every encryption is
-two table walks instead of a 252-doubling ladder.
+two table walks instead of a 252-doubling ladder.  ElGamalCircuit synthesises, for such batches, the witness of the encryption
+circuit (workloads.build_elgamal_encryption) and the ciphertext it proves; marlin.generate_elgamal_proof proves one.
 
 Host side (this file): the random draws and the bookkeeping.  A point is drawn the way ark-ec samples a twisted Edwards point
 (hash.ed_rand), a scalar the way ark-ff's UniformRand does (schnorr.rand_scalar) [U].  Plaintext = PublicKey = an affine point
@@ -54,6 +55,56 @@ class ResidentKey:
     def free(self):
         if self.h:
             self.ctx.elgamal_key_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ElGamalCircuit:
+    """The ElGamal encryption circuit under `params` (its generator), resident on the GPU (swm_elgamal_circuit): synthesises the
+    witness vector of workloads.build_elgamal_encryption, and the ciphertext it proves, for batches of (public key, message,
+    randomness) without running the builder.  Refers to the Parameters: keep them alive.
+    The randomness is ANY 32 bytes: the circuit multiplies by the 256-bit integer, unreduced.  Below the group order the
+    ciphertexts are encrypt_many's; at or above it encrypt_many refuses and the circuit proves the integer multiple."""
+
+    def __init__(self, params):
+        if not isinstance(params, Parameters) or not params.h:
+            raise ValueError("ElGamalCircuit: live elgamal.Parameters")
+        self.ctx, self.params = params.ctx, params
+        self.h = self.ctx.elgamal_circuit_create(params.h)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        from .marlin import elgamal_circuit_shape
+        return elgamal_circuit_shape()
+
+    def witness_many(self, pks, messages, rs):
+        """messages uint8 [count, 64], rs uint8 [count, 32]; pks uint8 [count, 64], or a ResidentKey under which every message
+        is encrypted (lane i then reads 2^i pk from the key's table instead of waiting for a doubling chain).  One launch per
+        staged chunk.  Returns (witness uint64 [count, 5371, 4] Montgomery limbs, ciphertexts uint8 [count, 128])."""
+        if not self.h or not self.params.h:
+            raise ValueError("ElGamalCircuit: the circuit or its Parameters have been freed")
+        m = np.ascontiguousarray(messages, dtype=np.uint8).reshape(-1, 64)
+        r = np.ascontiguousarray(rs, dtype=np.uint8).reshape(-1, 32)
+        if m.shape[0] != r.shape[0]:
+            raise ValueError("witness_many: %d messages, %d scalars of randomness" % (m.shape[0], r.shape[0]))
+        nw = self.shape()[1]
+        if isinstance(pks, ResidentKey):
+            if not pks.h:
+                raise ValueError("witness_many: the ResidentKey has been freed")
+            return self.ctx.elgamal_witness(self.h, nw, None, m, r, key_handle=pks.h)
+        pk = np.ascontiguousarray(pks, dtype=np.uint8).reshape(-1, 64)
+        if pk.shape[0] != m.shape[0]:
+            raise ValueError("witness_many: %d keys, %d messages" % (pk.shape[0], m.shape[0]))
+        return self.ctx.elgamal_witness(self.h, nw, pk, m, r)
+
+    def free(self):
+        if self.h:
+            self.ctx.elgamal_circuit_destroy(self.h)
             self.h = None
 
     def __del__(self):

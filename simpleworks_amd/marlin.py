@@ -480,6 +480,48 @@ def generate_schnorr_proof(proving_key, circuit, public_key, message, signature,
     return bytes(buf[: n.value])
 
 
+def elgamal_circuit_shape():
+    """swm_elgamal_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the ElGamal encryption circuit — what
+    workloads.build_elgamal_encryption emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_elgamal_circuit_shape(ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)), "swm_elgamal_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_elgamal_proof(proving_key, circuit, public_key, message, randomness, rng, uncompressed=False):
+    """swm_elgamal_prove / swm_elgamal_prove_to: the proof of workloads.ElGamalEncryption with the circuit's witness synthesised on
+    the GPU (elgamal.ElGamalCircuit) and handed to the prover on the device.  public_key: 64 bytes (x || y), a pair of ints, or an
+    elgamal.ResidentKey; message: 64 bytes or a pair of ints; randomness: 32 little-endian bytes or an int below 2^256 (unreduced).
+    Returns (proof bytes, ciphertext bytes): verify with workloads.elgamal_public_inputs(public_key, ciphertext).
+    uncompressed=True: the proof in the form of generate_proof_uncompressed."""
+    from .elgamal import ResidentKey
+    ctx = proving_key.ctx
+
+    def point(p):
+        return bytes(p) if isinstance(p, (bytes, bytearray)) else int(p[0]).to_bytes(32, "little") + int(p[1]).to_bytes(32, "little")
+    message = point(message)
+    randomness = bytes(randomness) if isinstance(randomness, (bytes, bytearray)) else int(randomness).to_bytes(32, "little")
+    if len(message) != 64 or len(randomness) != 32:
+        raise ValueError("generate_elgamal_proof: a 64-byte message and 32 bytes of randomness")
+    msg_b = (ctypes.c_uint8 * 64).from_buffer_copy(message)
+    r_b = (ctypes.c_uint8 * 32).from_buffer_copy(randomness)
+    ct_b = (ctypes.c_uint8 * 128)()
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    flags = 1 if uncompressed else 0
+    if isinstance(public_key, ResidentKey):
+        _check(ctx.lib.swm_elgamal_prove_to(ctx.h, proving_key.h, circuit.h, public_key.h, msg_b, r_b, rng.h, flags, ct_b, buf, len(buf),
+                                            ctypes.byref(n)), "swm_elgamal_prove_to", ctx)
+    else:
+        public_key = point(public_key)
+        if len(public_key) != 64:
+            raise ValueError("generate_elgamal_proof: a 64-byte key")
+        key_b = (ctypes.c_uint8 * 64).from_buffer_copy(public_key)
+        _check(ctx.lib.swm_elgamal_prove(ctx.h, proving_key.h, circuit.h, key_b, msg_b, r_b, rng.h, flags, ct_b, buf, len(buf),
+                                         ctypes.byref(n)), "swm_elgamal_prove", ctx)
+    return bytes(buf[: n.value]), bytes(ct_b)
+
+
 def poseidon_circuit_shape(params, input_len=None, n_in=None, n_out=1):
     """swm_poseidon_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the Poseidon hash circuit over the shape
     of `params` (a hash.PoseidonParameters) — what workloads.build_poseidon_hash emits.  input_len: the bytes form; n_in: the

@@ -1378,3 +1378,144 @@ class Blake2sHashCircuit:
 
     def generate_constraints(self, cs):
         build_blake2s_hash(cs, self.data)
+
+
+# ===================================================================================================================
+# The ElGamal encryption statement (ark-crypto-primitives' ElGamalEncGadget over the scheme of tests/encrypt.rs:11-28, native in
+# csrc/elgamal.hip): "I know a message point m and randomness r such that (c1, c2) = (r G, m + r pk)", with pk, c1 and c2
+# public.  As with the other circuits the row layout is OURS: it is the curve half of the Schnorr verification circuit (fix, dbl,
+# sel, add, sum) with no hash and no bit decomposition of a coordinate, built from the same helpers.  build_elgamal_encryption
+# is the layout contract of csrc/host/elgamal_shape.h and csrc/elgamal_witness.hip.
+#
+# Variable order (elgamal_circuit_layout gives the offsets):
+#   instance  one, pk.x, pk.y, c1.x, c1.y, c2.x, c2.y (the claimed values)
+#   key       xx, yy of pk; x x = xx, y y = yy and the on-curve row (d xx) yy = yy - xx - 1               2 witnesses,   3 rows
+#   msg       m.x, m.y, xx, yy; the same three rows                                                      4,             3
+#   rnd       256 booleans of r, least significant first, no range check                                 256,           256
+#   fix       r G: 255 conditional additions of the constants 2^i G (_cond_add_const), i = 1 .. 255       255 x 6,       255 x 6
+#   dbl       P_0 = pk, P_{i+1} = 2 P_i: xy, xx, yy, x', y' per doubling, i = 0 .. 254                    255 x 5,       255 x 5
+#   sel       Q_i = r_i P_i: qx = r_i x, qy = 1 + r_i (y - 1), i = 0 .. 255                               256 x 2,       256 x 2
+#   add       acc_0 = Q_0, acc_i = acc_{i-1} + Q_i                                                       255 x 7,       255 x 7
+#   sum       m + acc_255, m the first operand                                                           7,             7
+#   out       (r G).x - c1.x, (r G).y - c1.y, sum.x - c2.x, sum.y - c2.y, each times one = 0             0,             4
+# r enters as a 256-bit INTEGER, unreduced and without a range check, as s and e do in the Schnorr circuit: for r below the group
+# order l the ciphertext is the native scheme's; for r >= l (which the native calls refuse) the circuit proves the integer
+# multiple, which on a key of the prime subgroup is the encryption with r mod l.  No subgroup check on m or pk: the addition law
+# is complete, every denominator is non-zero.  Every witness is computed honestly whatever ciphertext is claimed, so a wrong claim
+# violates `out` rows only.
+# ===================================================================================================================
+def elgamal_circuit_layout():
+    """Offsets of the witness groups of build_elgamal_encryption and its three counts, as csrc/host/elgamal_shape.h states them."""
+    lay = {"key": 0, "msg": 2, "rnd": 6}
+    lay["fix"] = lay["rnd"] + 256
+    lay["dbl"] = lay["fix"] + 255 * 6
+    lay["sel"] = lay["dbl"] + 255 * 5
+    lay["add"] = lay["sel"] + 256 * 2
+    lay["sum"] = lay["add"] + 255 * 7
+    lay["num_instance"] = 7
+    lay["num_witness"] = lay["sum"] + 7
+    lay["num_constraints"] = 3 + 3 + 256 + 255 * 6 + 255 * 5 + 256 * 2 + 255 * 7 + 7 + 4
+    lay["out"] = lay["num_constraints"] - 4  # the first of the four rows a wrong claimed ciphertext violates
+    return lay
+
+
+def _elgamal_randomness(randomness):
+    if isinstance(randomness, (bytes, bytearray)):
+        if len(randomness) != 32:
+            raise ValueError("elgamal encryption circuit: the randomness is 32 little-endian bytes or an integer below 2^256")
+        return int.from_bytes(bytes(randomness), "little")
+    r = int(randomness)
+    if not 0 <= r < 1 << 256:
+        raise ValueError("elgamal encryption circuit: the randomness is 32 little-endian bytes or an integer below 2^256")
+    return r
+
+
+def elgamal_public_inputs(public_key, ciphertext):
+    """The six public inputs of the ElGamal encryption circuit, in instance order: pk.x, pk.y, c1.x, c1.y, c2.x, c2.y.
+    ciphertext: ((c1.x, c1.y), (c2.x, c2.y)), or the 128 bytes of encrypt_many; public_key: a pair of ints or 64 bytes."""
+    def point(p):
+        if isinstance(p, (bytes, bytearray)):
+            if len(p) != 64:
+                raise ValueError("a point is 64 bytes, x || y")
+            return [int.from_bytes(bytes(p[:32]), "little"), int.from_bytes(bytes(p[32:]), "little")]
+        return [int(p[0]), int(p[1])]
+    if isinstance(ciphertext, (bytes, bytearray)):
+        if len(ciphertext) != 128:
+            raise ValueError("a ciphertext is 128 bytes, c1 || c2")
+        ciphertext = (bytes(ciphertext[:64]), bytes(ciphertext[64:]))
+    return point(public_key) + point(ciphertext[0]) + point(ciphertext[1])
+
+
+def build_elgamal_encryption(cs, generator, public_key, message, randomness, ciphertext=None):
+    """Emits the ElGamal encryption circuit into `cs` (builder vocabulary as build_schnorr_verification).  generator, public_key,
+    message: affine points as ints, all on the curve (no subgroup check); randomness: an integer below 2^256 or 32 little-endian
+    bytes, unreduced; ciphertext: the CLAIMED ((c1.x, c1.y), (c2.x, c2.y)), or None for the one the inputs give.  The public inputs
+    are allocated first; returns them: [pk.x, pk.y, c1.x, c1.y, c2.x, c2.y].
+    Every witness is computed honestly whatever is claimed, so a wrong claim violates the four `out` rows only."""
+    generator, public_key, message = tuple(generator), tuple(public_key), tuple(message)
+    if not ed_on_curve(generator) or not ed_on_curve(public_key) or not ed_on_curve(message):
+        raise ValueError("elgamal encryption circuit: the generator, the key and the message must be points of ed-on-BLS12-377")
+    r = _elgamal_randomness(randomness)
+    if ciphertext is None:
+        ciphertext = (ed_mul(generator, r), ed_add(message, ed_mul(public_key, r)))
+    public = elgamal_public_inputs(public_key, ciphertext)
+    one = cs.one()
+    inst = [_LC([(1, cs.new_input_variable(v % R_MODULUS))], v) for v in public]
+    k_x, k_y = inst[0], inst[1]
+
+    def on_curve(x, y):
+        xx, yy = _sv_product(cs, x, x), _sv_product(cs, y, y)
+        cs.enforce_constraint(xx.scaled(ED_D).terms, yy.terms, yy.minus(xx).minus(_sv_const(one, 1)).terms)
+    # key
+    on_curve(k_x, k_y)
+    # msg
+    m_x, m_y = _sv_witness(cs, message[0]), _sv_witness(cs, message[1])
+    on_curve(m_x, m_y)
+    # rnd
+    r_bits = [_boolean_witness(cs, one, (r >> i) & 1) for i in range(256)]
+    # fix
+    acc = None
+    for b, g in zip(r_bits, _sv_generator_powers(generator)):
+        acc = _cond_add_const(cs, one, acc, g, b)
+    r_g = acc
+    # dbl
+    powers = [(k_x, k_y)]
+    for _ in range(255):
+        powers.append(_sv_double(cs, one, powers[-1]))
+    # sel
+    picks = []
+    for b, (px, py) in zip(r_bits, powers):
+        qx = _sv_product(cs, b, px)
+        qy = _sv_witness(cs, 1 + b.value * (py.value - 1))
+        cs.enforce_constraint(b.terms, py.minus(_sv_const(one, 1)).terms, qy.minus(_sv_const(one, 1)).terms)
+        picks.append((qx, qy))
+    # add
+    acc = picks[0]
+    for q in picks[1:]:
+        acc = _sv_add(cs, one, acc, q)
+    # sum
+    total = _sv_add(cs, one, (m_x, m_y), acc)
+    # out
+    for got, claimed in zip(r_g + total, inst[2:]):
+        cs.enforce_constraint(got.minus(claimed).terms, [(1, one)], [])
+    return public
+
+
+def elgamal_encryption_circuit(generator=ED_GENERATOR, public_key=None, message=None, randomness=0, ciphertext=None):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs).  A missing key or message is the generator."""
+    cs = ConstraintSystem()
+    public = build_elgamal_encryption(cs, generator, public_key if public_key is not None else generator,
+                                      message if message is not None else generator, randomness, ciphertext)
+    return cs, public
+
+
+class ElGamalEncryption:
+    """The ConstraintSynthesizer of the ElGamal encryption statement for MarlinInst.index / prove: constant = the generator,
+    witnesses = message and randomness, public inputs = key and ciphertext (elgamal_public_inputs)."""
+
+    def __init__(self, generator, public_key, message, randomness, ciphertext=None):
+        self.generator, self.public_key, self.message = generator, public_key, message
+        self.randomness, self.ciphertext = randomness, ciphertext
+
+    def generate_constraints(self, cs):
+        build_elgamal_encryption(cs, self.generator, self.public_key, self.message, self.randomness, self.ciphertext)
