@@ -752,6 +752,65 @@ int swm_poseidon_tree_prove_at(swm_ctx *ctx, const swm_pk *pk, const swm_poseido
                                const uint8_t *leaf, uint64_t index, swm_rng *rng, unsigned flags, uint8_t *proof_out, size_t cap,
                                size_t *len);
 
+/* ---------------------------------------------------------------------------------------------- Payment circuit witness
+ * The assignment of the payment circuit (simpleworks_amd/workloads.py, build_payment) synthesised on the GPU: Transaction::validate
+ * of examples/simple-payments as ONE statement over a Poseidon account tree with 72-byte leaves (x || y || balance).  Public
+ * input: root, sender, recipient, amount.  Witness: the Schnorr verification circuit over the 10 message bytes sender || recipient
+ * || amount, unchanged (its bits of Y.x and Y.y are the first 64 bytes of the sender's leaf); 64 balance bits; 64 bits of (balance -
+ * amount) mod 2^64; the sender's membership block (the witness section of the Poseidon membership circuit); 576 recipient leaf
+ * bits; the recipient's membership block.  With S / S_rows the Schnorr circuit's counts for msg_len 10, L = height - 1 and C as
+ * above:  num_instance = 5;  num_witness = S + 704 + 2 (3 L + (2 + L) C);  num_constraints = S_rows + 708 + 2 (8 + 2 C + L (2 + C) + 1).
+ * swm_payment_circuit_shape needs no GPU.  SWM_ERR_INVALID_ARG: a parameter shape swm_poseidon_create refuses, a height outside
+ * 2 .. 9 (an account id is one byte), a NULL output.
+ * swm_payment_circuit_create: the handle refers to the swm_schnorr and the swm_poseidon: keep them.
+ * Inputs per payment: 10 message bytes, 64 signature bytes, the two leaves of 72 bytes; the leaf indices are message bytes 0 and 1.
+ * flags (one byte per payment): bit 0 = the signature verifies under the sender leaf's key, bit 1 = amount <= balance.  Every
+ * witness is computed whatever the flags say; the system is satisfied only when they are 3 and both leaves are the tree's.
+ * swm_payment_witness: no tree; the two sibling arrays are count x L x 32 bytes bottom up.  Refuses the WHOLE call with
+ * SWM_ERR_INVALID_ARG: a sender key that is no canonical point of the curve, a sibling >= r, an id >= 2^L.  witness: count x
+ * num_witness x 4 Montgomery limbs; sender_roots / recipient_roots (may be NULL): count x 32 bytes, the roots the two paths lead
+ * to.  A batch whose witnesses exceed 1 GiB is staged in chunks.
+ * swm_payment_witness_at: siblings and running digests are read from a resident tree of the circuit's parameters and height with
+ * 72-byte leaves (otherwise SWM_ERR_INVALID_ARG).  The leaves are NOT compared with the tree.
+ * swm_payment_witness_dev: device buffers in and out (signatures, siblings, status and roots 4-byte aligned, the witness 16-byte
+ * aligned), no chunking; `tree` may be NULL, then both sibling arrays are read.  What the host forms refuse is reported in
+ * d_status (uint32 per payment): bit 0 = the key (the Schnorr block of that payment is zero, nothing else of it), bit 1 = a sibling
+ * >= r (it is hashed as the 256-bit value given: that path's membership block and its walked root are then unspecified, the rest of
+ * the payment's witness is as usual), bit 2 = an id >= 2^L (the membership blocks are those of the id's low L bits).  Messages and
+ * leaves are read byte by byte and need no alignment.
+ * swm_payment_prove_at: one payment against a resident tree, then the proof of swm_generate_proof_ex(flags) with the public input
+ * (the tree's root, sender, recipient, amount).  SWM_ERR_UNSATISFIED: flags other than 3, or a leaf that is not the tree's.
+ * swm_payment_prove_many_at: one witness pass for `count` payments (chunks as above), then one prover call per payment whose flag
+ * byte is 3, in order, each reading its slice on the device.  proofs_out: count x proof_cap bytes.  lens[i] = 0 for a payment without
+ * a proof: item_flags[i] != 3 (skipped, the prover is not called), or item_flags[i] = 3 and the prover found the system
+ * unsatisfied (a leaf that is not the tree's); the block goes on after either.  Any other prover error ends the call with that code;
+ * lens and item_flags are zeroed for the whole block before the first launch, so every entry is written whatever the return value,
+ * and lens[i] != 0 exactly for the payments that have a proof. */
+typedef struct swm_payment_circuit swm_payment_circuit;
+int swm_payment_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64_t alpha, size_t height, int salted, size_t *num_instance,
+                              size_t *num_witness, size_t *num_constraints);
+int swm_payment_circuit_create(swm_ctx *ctx, const swm_schnorr *schnorr, const swm_poseidon *poseidon, size_t height,
+                               swm_payment_circuit **out);
+void swm_payment_circuit_destroy(swm_ctx *ctx, swm_payment_circuit *circuit);
+int swm_payment_witness(swm_ctx *ctx, const swm_payment_circuit *circuit, const uint8_t *messages, const uint8_t *signatures,
+                        const uint8_t *sender_leaves, const uint8_t *recipient_leaves, const uint8_t *sender_siblings,
+                        const uint8_t *recipient_siblings, size_t count, uint64_t *witness, uint8_t *flags, uint8_t *sender_roots,
+                        uint8_t *recipient_roots);
+int swm_payment_witness_at(swm_ctx *ctx, const swm_payment_circuit *circuit, const swm_poseidon_tree *tree, const uint8_t *messages,
+                           const uint8_t *signatures, const uint8_t *sender_leaves, const uint8_t *recipient_leaves, size_t count,
+                           uint64_t *witness, uint8_t *flags);
+int swm_payment_witness_dev(swm_ctx *ctx, const swm_payment_circuit *circuit, const swm_poseidon_tree *tree, const void *d_messages,
+                            const void *d_signatures, const void *d_sender_leaves, const void *d_recipient_leaves,
+                            const void *d_sender_siblings, const void *d_recipient_siblings, size_t count, void *d_witness,
+                            void *d_flags, void *d_status, void *d_sender_roots, void *d_recipient_roots);
+int swm_payment_prove_at(swm_ctx *ctx, const swm_pk *pk, const swm_payment_circuit *circuit, const swm_poseidon_tree *tree,
+                         const uint8_t message[10], const uint8_t signature[64], const uint8_t sender_leaf[72],
+                         const uint8_t recipient_leaf[72], swm_rng *rng, unsigned flags, uint8_t *proof_out, size_t cap, size_t *len);
+int swm_payment_prove_many_at(swm_ctx *ctx, const swm_pk *pk, const swm_payment_circuit *circuit, const swm_poseidon_tree *tree,
+                              const uint8_t *messages, const uint8_t *signatures, const uint8_t *sender_leaves,
+                              const uint8_t *recipient_leaves, size_t count, swm_rng *rng, unsigned flags, uint8_t *proofs_out,
+                              size_t proof_cap, size_t *lens, uint8_t *item_flags);
+
 /* ---------------------------------------------------------------------------------------------- Blake2s random oracle
  * The reference's random oracle, unkeyed BLAKE2s-256 (RFC 7693), batched: one GPU lane per hash.  Replaces, on the GPU,
  *   src/schnorr_signature/blake2s.rs, examples/simple-payments/random_oracle/blake2s/mod.rs      RO::evaluate(&(), input)

@@ -32,11 +32,7 @@
 #include "poseidon_tree.h"
 #include "merkle_nodes.cuh"
 #include "swmarlin.h"
-
-struct swm_poseidon_tree_circuit {
-    const swm_poseidon* params = nullptr;
-    swm::PoseidonTreeShape shape;
-};
+#include "witness_runs.h"
 
 namespace swm {
 
@@ -75,7 +71,7 @@ __global__ void __launch_bounds__(256) poseidon_tree_gather_kernel(const uint32_
 
 struct PtwArgs {
     unsigned levels, leaf_blocks;
-    size_t leaf_len, n_elems, count, num_witness, bits_at, siblings_at, deltas_at, leaf_at, levels_at, perm_values;
+    size_t leaf_len, n_elems, count, stride, bits_at, siblings_at, deltas_at, leaf_at, levels_at, perm_values;
 };
 
 __device__ __forceinline__ void ptw_store(Fr* dst, const Fr& v) {
@@ -101,7 +97,7 @@ __global__ void __launch_bounds__(PS_LANES) poseidon_tree_record_kernel(const ui
         const size_t lane_item = blockIdx.x * (size_t)PS_LANES + threadIdx.x;
         const bool act = lane_item < T.count;
         const size_t item = act ? lane_item : T.count - 1;
-        Fr* wp = witness + item * T.num_witness + T.leaf_at;
+        Fr* wp = witness + item * T.stride + T.leaf_at;
         bool unused = false;
 #pragma unroll 1
         for (size_t e = 0; e < T.n_elems; e += 2) {
@@ -122,7 +118,7 @@ __global__ void __launch_bounds__(PS_LANES) poseidon_tree_record_kernel(const ui
     const Fr cur = pt_load(digests + 8 * (p * (T.levels + 1) + l)), s = pt_load(siblings + 8 * (p * T.levels + l));
     const bool right = (indices[p] >> l) & 1u;
     const Fr d = right ? fp_sub(s, cur) : fp_zero<Fr>();  // both < r: the difference mod r, in standard form as they are
-    Fr* w = witness + p * T.num_witness;
+    Fr* w = witness + p * T.stride;
     if (act) {
         ptw_store(w + T.bits_at + l, right ? fp_one<Fr>() : fp_zero<Fr>());
         ptw_store(w + T.siblings_at + l, fp_from_std(s));
@@ -134,10 +130,10 @@ __global__ void __launch_bounds__(PS_LANES) poseidon_tree_record_kernel(const ui
     pw_permute(ps_tab, A, alpha_top, s0, s1, s2, wp, act, 0xFFFFFFFFu);
 }
 
-// `count` witnesses into d_witness (count x num_witness elements, 16-byte aligned).  With a tree the digests and the siblings are
+// `count` witnesses into d_witness (item i at d_witness + i * stride, 16-byte aligned).  With a tree the digests and the siblings are
 // gathered from its nodes (d_siblings is not read); without one the paths are walked and d_roots (may be NULL) takes their roots.
-static int ptw_run(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const swm_poseidon_tree* tree, const uint8_t* d_leaves,
-                   const uint64_t* d_indices, const uint8_t* d_siblings, size_t count, Fr* d_witness, uint32_t* d_roots) {
+int ptw_run(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const swm_poseidon_tree* tree, const uint8_t* d_leaves, const uint64_t* d_indices,
+            const uint8_t* d_siblings, size_t count, Fr* d_witness, size_t stride, uint32_t* d_roots) {
     if (!count) return SWM_OK;
     const PoseidonTreeShape& s = c->shape;
     const swm_poseidon* p = c->params;
@@ -169,7 +165,7 @@ static int ptw_run(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const swm_p
     T.leaf_len = s.leaf_len;
     T.n_elems = s.elems;
     T.count = count;
-    T.num_witness = s.num_witness;
+    T.stride = stride;
     T.bits_at = s.bits_at;
     T.siblings_at = s.siblings_at;
     T.deltas_at = s.deltas_at;
@@ -239,7 +235,7 @@ static int ptw_host(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const swm_
         SWM_TRY(ptw_stage(ctx, s, leaves + base * s.leaf_len, indices + base, siblings ? siblings + base * s.levels * 32 : nullptr, n, &d_leaves,
                           &d_indices, &d_siblings));
         SWM_TRY(scratch(ctx, "ptree.w", n * item + 32 * n, (void**)&d_out));
-        SWM_TRY(ptw_run(ctx, c, tree, d_leaves, d_indices, d_siblings, n, (Fr*)d_out, roots ? (uint32_t*)(d_out + n * item) : nullptr));
+        SWM_TRY(ptw_run(ctx, c, tree, d_leaves, d_indices, d_siblings, n, (Fr*)d_out, s.num_witness, roots ? (uint32_t*)(d_out + n * item) : nullptr));
         SWM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t*>(witness) + base * item, d_out, n * item, hipMemcpyDeviceToHost, ctx->stream));
         if (roots) SWM_HIP(ctx, hipMemcpyAsync(roots + 32 * base, d_out + n * item, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
         SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffers are reused by the next chunk
@@ -256,7 +252,7 @@ static int ptw_one(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const swm_p
     uint8_t* d_out = nullptr;
     SWM_TRY(ptw_stage(ctx, s, leaf, &index, siblings, 1, &d_leaves, &d_indices, &d_siblings));
     SWM_TRY(scratch(ctx, "ptree.w", s.num_witness * sizeof(Fr) + 32, (void**)&d_out));
-    SWM_TRY(ptw_run(ctx, c, tree, d_leaves, d_indices, d_siblings, 1, (Fr*)d_out, nullptr));
+    SWM_TRY(ptw_run(ctx, c, tree, d_leaves, d_indices, d_siblings, 1, (Fr*)d_out, s.num_witness, nullptr));
     SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `index` was staged from this frame
     *d_w = (Fr*)d_out;
     return SWM_OK;

@@ -33,11 +33,7 @@
 #include "host/schnorr_shape.h"
 #include "schnorr.h"
 #include "swmarlin.h"
-
-struct swm_schnorr_circuit {
-    const swm_schnorr* params = nullptr;
-    swm::SchnorrShape shape;
-};
+#include "witness_runs.h"
 
 namespace swm {
 
@@ -60,6 +56,7 @@ struct SvParams {
     uint32_t msg_len, blocks, hash_len;
     uint32_t sig_at, fix_at, dbl_at, sel_at, add_at, sum_at, dec_at, b2s_at;
     size_t num_witness;
+    size_t stride;  // elements between two items' witnesses: num_witness, or more when the circuit is a block of a larger one
 };
 
 // Block p = signature p.  keys: 64 bytes each, sigs: 64 bytes each (both 4-byte aligned), msgs: msg_len bytes each.
@@ -69,7 +66,7 @@ __global__ void __launch_bounds__(SV_LANES) schnorr_witness_kernel(SvParams P, c
     __shared__ SvShared sh;
     const unsigned tid = threadIdx.x;
     const size_t item = blockIdx.x;
-    Fr* w = witness + item * P.num_witness;
+    Fr* w = witness + item * P.stride;
     const uint32_t* key = reinterpret_cast<const uint32_t*>(keys + 64 * item);
     const uint32_t* sig = reinterpret_cast<const uint32_t*>(sigs + 64 * item);
     const uint8_t* msg = msgs + item * (size_t)P.msg_len;
@@ -259,8 +256,8 @@ __global__ void __launch_bounds__(SV_LANES) schnorr_witness_kernel(SvParams P, c
     }
 }
 
-static int schnorr_witness_run(swm_ctx* ctx, const swm_schnorr_circuit* c, const uint8_t* d_keys, const uint8_t* d_msgs, const uint8_t* d_sigs,
-                               size_t count, Fr* d_witness, uint8_t* d_ok, uint32_t* d_status) {
+int schnorr_witness_run(swm_ctx* ctx, const swm_schnorr_circuit* c, const uint8_t* d_keys, const uint8_t* d_msgs, const uint8_t* d_sigs,
+                        size_t count, Fr* d_witness, size_t stride, uint8_t* d_ok, uint32_t* d_status) {
     if (!count) return SWM_OK;
     if (count > 0x7FFFFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_witness: %zu signatures in one call", count);
     const SchnorrShape& s = c->shape;
@@ -283,13 +280,14 @@ static int schnorr_witness_run(swm_ctx* ctx, const swm_schnorr_circuit* c, const
     P.dec_at = (uint32_t)s.dec_at;
     P.b2s_at = (uint32_t)s.b2s_at;
     P.num_witness = s.num_witness;
+    P.stride = stride;
     SWM_LAUNCH(ctx, "schnorr_witness", schnorr_witness_kernel, dim3((unsigned)count), dim3(SV_LANES), 0, P, d_keys, d_msgs, d_sigs, d_witness,
                d_ok, d_status);
     return SWM_OK;
 }
 
 // the host form's check: what the device form reports per item
-static int schnorr_check_keys(swm_ctx* ctx, const uint8_t* keys, size_t count) {
+int schnorr_check_keys(swm_ctx* ctx, const uint8_t* keys, size_t count) {
     const Fr d = fp_from_u64<Fr>(ED_D);
     for (size_t p = 0; p < count; p++) {
         uint32_t kx[8], ky[8];
@@ -356,7 +354,7 @@ int swm_schnorr_witness_dev(swm_ctx* ctx, const swm_schnorr_circuit* c, const vo
         return set_err(ctx, SWM_ERR_INVALID_ARG, "schnorr_witness: keys and signatures must be 4-byte aligned");
     SWM_ON_DEVICE(ctx);
     return schnorr_witness_run(ctx, c, (const uint8_t*)d_public_keys, (const uint8_t*)d_messages, (const uint8_t*)d_signatures, count,
-                               (Fr*)d_witness, (uint8_t*)d_ok, (uint32_t*)d_status);
+                               (Fr*)d_witness, c->shape.num_witness, (uint8_t*)d_ok, (uint32_t*)d_status);
 }
 
 int swm_schnorr_witness(swm_ctx* ctx, const swm_schnorr_circuit* c, const uint8_t* public_keys_xy, const uint8_t* messages,
@@ -375,7 +373,7 @@ int swm_schnorr_witness(swm_ctx* ctx, const swm_schnorr_circuit* c, const uint8_
                                      &d_msgs, &d_sigs));
         uint8_t* d_out = nullptr;
         SWM_TRY(scratch(ctx, "schnorr.w", n * item + n, (void**)&d_out));
-        SWM_TRY(schnorr_witness_run(ctx, c, d_keys, d_msgs, d_sigs, n, (Fr*)d_out, d_out + n * item, nullptr));
+        SWM_TRY(schnorr_witness_run(ctx, c, d_keys, d_msgs, d_sigs, n, (Fr*)d_out, c->shape.num_witness, d_out + n * item, nullptr));
         SWM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t*>(witness) + base * item, d_out, n * item, hipMemcpyDeviceToHost, ctx->stream));
         if (ok) SWM_HIP(ctx, hipMemcpyAsync(ok + base, d_out + n * item, n, hipMemcpyDeviceToHost, ctx->stream));
         SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffers are reused by the next chunk
@@ -395,7 +393,7 @@ int swm_schnorr_prove(swm_ctx* ctx, const swm_pk* pk, const swm_schnorr_circuit*
         const uint8_t *d_keys, *d_msgs, *d_sigs;
         SWM_TRY(scratch(ctx, "schnorr.w", s.num_witness * sizeof(Fr) + 1, (void**)&d_w));
         SWM_TRY(schnorr_stage_inputs(ctx, c, public_key_xy, message, signature, 1, &d_keys, &d_msgs, &d_sigs));
-        SWM_TRY(schnorr_witness_run(ctx, c, d_keys, d_msgs, d_sigs, 1, d_w, nullptr, nullptr));
+        SWM_TRY(schnorr_witness_run(ctx, c, d_keys, d_msgs, d_sigs, 1, d_w, s.num_witness, nullptr, nullptr));
         SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     const Fr inst = fp_one<Fr>();  // no public input (transaction.rs verifies with an empty vector)

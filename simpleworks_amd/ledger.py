@@ -48,22 +48,26 @@ def transaction_message(sender, recipient, amount):
 class Parameters:
     """ledger::Parameters { sig_params, leaf_crh_params, two_to_one_crh_params }, all three resident on the GPU."""
 
-    def __init__(self, sig_params, leaf_crh, two_to_one_crh):
+    def __init__(self, sig_params, leaf_crh, two_to_one_crh, poseidon=None):
         self.sig_params, self.leaf_crh, self.two_to_one_crh = sig_params, leaf_crh, two_to_one_crh
         self.leaf_crh_params, self.two_to_one_crh_params = leaf_crh, two_to_one_crh   # the reference's field names
+        self.poseidon = poseidon     # a hash.PoseidonSponge, or None: what a State with account_tree="poseidon" hashes with
 
     @classmethod
-    def sample(cls, rng, ctx=None):
-        """ledger.rs:42-51: the three setups draw from the one rng in this order (the Schnorr setup draws nothing)."""
+    def sample(cls, rng, ctx=None, poseidon=None):
+        """ledger.rs:42-51: the three setups draw from the one rng in this order (the Schnorr setup draws nothing).  poseidon: a
+        hash.PoseidonParameters, kept as a resident PoseidonSponge (it draws nothing either)."""
         sig = schnorr.setup(rng, ctx)
         leaf = H.PedersenCRH.setup(rng, H.LEAF_WINDOWS, H.WINDOW_SIZE, ctx)
         inner = H.PedersenCRH.setup(rng, H.TWO_TO_ONE_WINDOWS, H.WINDOW_SIZE, ctx)
-        return cls(sig, leaf, inner)
+        return cls(sig, leaf, inner, H.PoseidonSponge(poseidon, sig.ctx) if poseidon is not None else None)
 
     def free(self):
         self.sig_params.free()
         self.leaf_crh.free()
         self.two_to_one_crh.free()
+        if self.poseidon is not None:
+            self.poseidon.free()
 
 
 class AccountInformation:
@@ -76,10 +80,55 @@ class AccountInformation:
         return schnorr.point_bytes(self.public_key) + self.balance.to_bytes(8, "little")
 
 
-class State:
-    """ledger::State.  The account tree is a hash.DeviceMerkleTree; ids are AccountId(u8), the first one handed out is 1."""
+class PaymentCircuit:
+    """The payment circuit over resident Schnorr and Poseidon parameters (swm_payment_circuit): synthesises the witness vector of
+    workloads.build_payment for batches of payments without running the builder.  A payment is (message, signature, sender leaf,
+    recipient leaf); the leaf indices are the message's first two bytes.  Refers to both parameter sets: keep them alive."""
 
-    def __init__(self, num_accounts, parameters):
+    def __init__(self, sig_params, sponge, height):
+        self.ctx, self.sig_params, self.sponge, self.height = sig_params.ctx, sig_params, sponge, height
+        self.h = self.ctx.payment_circuit_create(sig_params.h, sponge.h, height)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        from .marlin import payment_circuit_shape
+        return payment_circuit_shape(self.sponge.params, self.height, self.sig_params.salt is not None)
+
+    @staticmethod
+    def _columns(payments):
+        cols = [np.frombuffer(b"".join(bytes(p[k]) for p in payments), dtype=np.uint8).reshape(len(payments), -1) for k in range(4)]
+        if [c.shape[1] for c in cols] != [MESSAGE_LEN, 64, LEAF_LEN, LEAF_LEN]:
+            raise ValueError("a payment is a %d-byte message, a 64-byte signature and two %d-byte leaves" % (MESSAGE_LEN, LEAF_LEN))
+        return cols
+
+    def witness_many(self, payments, sender_siblings, recipient_siblings):
+        """No tree: the siblings per path bottom up, as hash.PoseidonMembershipCircuit.witness_many takes them.  Returns (witness
+        uint64 [count, num_witness, 4] Montgomery limbs, flags uint8 [count], sender roots, recipient roots as ints)."""
+        w, flags, rs, rr = self.ctx.payment_witness(self.h, self.shape()[1], self.height - 1, *self._columns(payments),
+                                                    H._fr_rows(sender_siblings), H._fr_rows(recipient_siblings))
+        return (w, flags, [int.from_bytes(r.tobytes(), "little") for r in rs], [int.from_bytes(r.tobytes(), "little") for r in rr])
+
+    def witness_at(self, tree, payments):
+        """The same against a hash.PoseidonMerkleTree that holds both leaves: (witness, flags)."""
+        return self.ctx.payment_witness_at(self.h, tree.h, self.shape()[1], *self._columns(payments))
+
+    def free(self):
+        if self.h:
+            self.ctx.payment_circuit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class State:
+    """ledger::State.  The account tree is a hash.DeviceMerkleTree, or with account_tree="poseidon" a hash.PoseidonMerkleTree over
+    parameters.poseidon; ids are AccountId(u8), the first one handed out is 1."""
+
+    def __init__(self, num_accounts, parameters, account_tree="pedersen"):
         """ledger.rs:106-112 hands ark_std::log2(num_accounts) to MerkleTree::blank as the HEIGHT, and arkworks' height counts the
         leaf level: 32 accounts give height 5 and 2^4 = 16 leaves.  Mirrored as it stands.  Registering past the last leaf
         raises (the reference panics in tree.update: "should exist")."""
@@ -87,11 +136,22 @@ class State:
         height = ark_log2(num_accounts)
         if height < 2:
             raise ValueError("State: %d accounts give a tree of height %d (MerkleTree::blank needs 2)" % (num_accounts, height))
-        self.account_merkle_tree = H.DeviceMerkleTree.blank(parameters.leaf_crh, parameters.two_to_one_crh, height, LEAF_LEN)
+        if account_tree not in ("pedersen", "poseidon"):
+            raise ValueError("State: account_tree is \"pedersen\" or \"poseidon\"")
+        self.account_tree = account_tree
+        if account_tree == "poseidon":
+            if parameters.poseidon is None:
+                raise ValueError("State: a Poseidon account tree needs Parameters.sample(.., poseidon=...)")
+            if height > 9:
+                raise ValueError("State: a Poseidon account tree has at most 256 leaves (an account id is one byte)")
+            self.account_merkle_tree = H.PoseidonMerkleTree.blank(parameters.poseidon, height, LEAF_LEN)
+        else:
+            self.account_merkle_tree = H.DeviceMerkleTree.blank(parameters.leaf_crh, parameters.two_to_one_crh, height, LEAF_LEN)
         self.next_available_account = 1
         self.id_to_account_info = {}
         self.pub_key_to_id = {}
         self._proof_keys = None      # (SchnorrCircuit, proving key, verifying key), derived once
+        self._payment_keys = None    # (PaymentCircuit, proving key, verifying key), the same for a Poseidon account tree
 
     def root(self):
         return self.account_merkle_tree.root()
@@ -160,11 +220,35 @@ class State:
             self._proof_keys = (schnorr.SchnorrCircuit(sig, MESSAGE_LEN), pk, vk)
         return self._proof_keys
 
+    def payment_keys(self, rng):
+        """The payment circuit (this ledger's parameters and tree height) with its Marlin keys, derived once as proof_keys derives
+        the signature circuit's.  The matrices depend on the shape alone: any payment's system indexes them."""
+        if self.account_tree != "poseidon":
+            raise ValueError("payment_keys: the payment circuit is over a Poseidon account tree")
+        if self._payment_keys is None:
+            from . import marlin as M
+            from . import workloads as W
+            sig, sponge = self.parameters.sig_params, self.parameters.poseidon
+            height = self.account_merkle_tree.height()
+            leaf = AccountInformation(sig.generator, 0).to_bytes_le()
+            cs, _ = W.payment_circuit(sponge.params, height, bytes(MESSAGE_LEN), bytes(64), leaf, [0] * (height - 1), leaf,
+                                      [0] * (height - 1), sig.generator, sig.salt)
+            packed = cs.pack()
+            nnz = max(int(m[0][-1]) for m in packed.mats)
+            srs = M.MarlinInst.universal_setup(cs.num_constraints, len(cs.instance) + len(cs.witness), nnz, rng, sig.ctx)
+            try:
+                pk, vk = M.MarlinInst.index_from_constraint_system(srs, packed)
+            finally:
+                srs.free()
+            self._payment_keys = (PaymentCircuit(sig, sponge, height), pk, vk)
+        return self._payment_keys
+
     def free(self):
-        if self._proof_keys is not None:
-            self._proof_keys[0].free()
-            self._proof_keys[1].free()
-            self._proof_keys = None
+        for keys in (self._proof_keys, self._payment_keys):
+            if keys is not None:
+                keys[0].free()
+                keys[1].free()
+        self._proof_keys = self._payment_keys = None
         self.account_merkle_tree.free()
 
 
@@ -174,6 +258,20 @@ def _prove_signature(state, public_key, message, signature, rng):
     circuit, pk, vk = state.proof_keys(rng)
     proof = M.generate_schnorr_proof(pk, circuit, public_key, message, signature.to_bytes(), rng)
     return M.verify_proof(vk, [], M.MarlinProof(proof), rng)
+
+
+def verify_payment(vk, public_inputs, proof, rng):
+    """The verifier of a payment proof: public_inputs = [root, sender, recipient, amount] (workloads.payment_public_inputs)."""
+    from . import marlin as M
+    return M.verify_proof(vk, [int(v) for v in public_inputs], proof if isinstance(proof, M.MarlinProof) else M.MarlinProof(proof), rng)
+
+
+def _payment_leaves(state, tx):
+    """(sender leaf, recipient leaf) as the state holds them, or None when the recipient has no account."""
+    recipient = state.id_to_account_info.get(tx.recipient)
+    if recipient is None:
+        return None
+    return state.id_to_account_info[tx.sender].to_bytes_le(), recipient.to_bytes_le()
 
 
 class Transaction:
@@ -191,6 +289,20 @@ class Transaction:
         sig = schnorr.sign(parameters.sig_params, sender_sk, transaction_message(sender, recipient, amount), rng)
         return Transaction(sender, recipient, amount, sig)
 
+    def prove_payment(self, parameters, state, rng):
+        """-> (proof bytes, public inputs) of the payment circuit against a state with a Poseidon account tree, as it stands now.
+        KeyError when sender or recipient has no account; MarlinError (SWM_ERR_UNSATISFIED) when the payment is not valid."""
+        from . import marlin as M
+        from . import workloads as W
+        if self.sender not in state.id_to_account_info or self.recipient not in state.id_to_account_info:
+            raise KeyError("sender or recipient not found")
+        circuit, pk, _ = state.payment_keys(rng)
+        tree = state.account_merkle_tree
+        sender_leaf, recipient_leaf = _payment_leaves(state, self)
+        public = W.payment_public_inputs(tree.root(), self.message())
+        proof = M.generate_payment_proof(pk, circuit, tree, self.message(), self.signature.to_bytes(), sender_leaf, recipient_leaf, rng)
+        return proof, public
+
     def validate(self, parameters, state, rng, prove=True):
         """transaction.rs:148-185.  KeyError when the sender has no account (the reference's Err).  Otherwise the conjunction of
           1. the sender's leaf is in the account tree: generate_proofs, then verify_paths against the root;
@@ -203,10 +315,20 @@ class Transaction:
             raise KeyError("sender not found")
         tree = state.account_merkle_tree
         path = tree.generate_proofs([self.sender])
-        result = bool(H.verify_paths(parameters.leaf_crh, parameters.two_to_one_crh, tree.height(), tree.root(), [info.to_bytes_le()],
-                                     [self.sender], path)[0])
+        poseidon = state.account_tree == "poseidon"
+        if poseidon:
+            result = bool(H.verify_poseidon_paths(parameters.poseidon, tree.height(), tree.root(), [info.to_bytes_le()], [self.sender],
+                                                  path)[0])
+        else:
+            result = bool(H.verify_paths(parameters.leaf_crh, parameters.two_to_one_crh, tree.height(), tree.root(), [info.to_bytes_le()],
+                                         [self.sender], path)[0])
         sig_ok = schnorr.verify(parameters.sig_params, info.public_key, self.message(), self.signature)
-        if sig_ok and prove:
+        if poseidon and prove:
+            # the one proof states all four checks: made only for a payment that passes them (an invalid one has no proof)
+            if result and sig_ok and self.amount <= info.balance and self.recipient in state.id_to_account_info:
+                proof, public = self.prove_payment(parameters, state, rng)
+                sig_ok = verify_payment(state.payment_keys(rng)[2], public, proof, rng)
+        elif sig_ok and prove:
             sig_ok = _prove_signature(state, info.public_key, self.message(), self.signature, rng)
         result &= sig_ok
         result &= self.amount <= info.balance
@@ -226,15 +348,35 @@ def validate_many(parameters, state, txs, rng=None, prove=False):
     senders = [txs[i].sender for i in known]
     tree = state.account_merkle_tree
     paths = tree.generate_proofs(senders)
-    in_tree = H.verify_paths(parameters.leaf_crh, parameters.two_to_one_crh, tree.height(), tree.root(),
-                             [info.to_bytes_le() for info in infos], senders, paths)
+    poseidon = state.account_tree == "poseidon"
+    if poseidon:
+        in_tree = H.verify_poseidon_paths(parameters.poseidon, tree.height(), tree.root(), [info.to_bytes_le() for info in infos], senders,
+                                          paths)
+    else:
+        in_tree = H.verify_paths(parameters.leaf_crh, parameters.two_to_one_crh, tree.height(), tree.root(),
+                                 [info.to_bytes_le() for info in infos], senders, paths)
     keys = np.frombuffer(b"".join(schnorr.point_bytes(info.public_key) for info in infos), dtype=np.uint8).reshape(-1, 64)
     msgs = np.frombuffer(b"".join(txs[i].message() for i in known), dtype=np.uint8).reshape(-1, MESSAGE_LEN)
     sigs = np.frombuffer(b"".join(txs[i].signature.to_bytes() for i in known), dtype=np.uint8).reshape(-1, 64)
     signed = schnorr.verify_many(parameters.sig_params, keys, msgs, sigs)
+    proved = {}
+    if poseidon and prove:
+        # one witness pass and one prover call per payment that passes the native checks
+        from . import marlin as M
+        from . import workloads as W
+        circuit, pk, vk = state.payment_keys(rng)
+        good = [k for k, i in enumerate(known) if in_tree[k] and signed[k] and txs[i].amount <= infos[k].balance
+                and txs[i].recipient in state.id_to_account_info]
+        block = [(txs[known[k]].message(), txs[known[k]].signature.to_bytes()) + _payment_leaves(state, txs[known[k]]) for k in good]
+        proofs, _ = M.generate_payment_proofs(pk, circuit, tree, block, rng)
+        root = tree.root()
+        for k, proof in zip(good, proofs):
+            proved[k] = proof is not None and verify_payment(vk, W.payment_public_inputs(root, txs[known[k]].message()), proof, rng)
     for k, i in enumerate(known):
         tx, sig_ok = txs[i], bool(signed[k])
-        if sig_ok and prove:
+        if poseidon and prove:
+            sig_ok = sig_ok and proved.get(k, False)
+        elif sig_ok and prove:
             sig_ok = _prove_signature(state, infos[k].public_key, tx.message(), tx.signature, rng)
         out[i] = bool(in_tree[k]) and sig_ok and tx.amount <= infos[k].balance and tx.recipient in state.id_to_account_info
     return out

@@ -593,6 +593,57 @@ def generate_poseidon_membership_proof(proving_key, circuit, root, leaf, leaf_in
     return bytes(buf[: n.value])
 
 
+def payment_circuit_shape(params, height, salted=False):
+    """swm_payment_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the payment circuit over a Poseidon account
+    tree of that height, with or without a Schnorr salt — what workloads.build_payment emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_payment_circuit_shape(params.full_rounds, params.partial_rounds, params.alpha, height, 1 if salted else 0,
+                                                    ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)), "swm_payment_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def _payment_bytes(message, signature, sender_leaf, recipient_leaf):
+    parts = [bytes(message), bytes(signature), bytes(sender_leaf), bytes(recipient_leaf)]
+    if [len(p) for p in parts] != [10, 64, 72, 72]:
+        raise ValueError("a payment is a 10-byte message, a 64-byte signature and two 72-byte leaves")
+    return parts
+
+
+def generate_payment_proof(proving_key, circuit, tree, message, signature, sender_leaf, recipient_leaf, rng, uncompressed=False):
+    """swm_payment_prove_at: the proof of workloads.PaymentValidation with the circuit's witness synthesised on the GPU
+    (ledger.PaymentCircuit) against the resident account tree `tree` (a hash.PoseidonMerkleTree) and handed to the prover on the
+    device.  The public input to verify with is workloads.payment_public_inputs(tree.root(), message).  A payment that is not valid
+    (signature, balance, either leaf) raises with SWM_ERR_UNSATISFIED.  Returns the proof bytes."""
+    ctx = proving_key.ctx
+    bufs = [(ctypes.c_uint8 * len(p)).from_buffer_copy(p) for p in _payment_bytes(message, signature, sender_leaf, recipient_leaf)]
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    _check(ctx.lib.swm_payment_prove_at(ctx.h, proving_key.h, circuit.h, tree.h, bufs[0], bufs[1], bufs[2], bufs[3], rng.h,
+                                        1 if uncompressed else 0, buf, len(buf), ctypes.byref(n)), "swm_payment_prove_at", ctx)
+    return bytes(buf[: n.value])
+
+
+def generate_payment_proofs(proving_key, circuit, tree, payments, rng, uncompressed=False):
+    """swm_payment_prove_many_at: one witness pass for the whole block, then one prover call per valid payment, in order.  payments:
+    (message, signature, sender_leaf, recipient_leaf) each.  Returns (proofs, flags): proofs[i] is the proof bytes, or None for a
+    payment whose flag byte (bit 0: the signature verifies, bit 1: amount <= balance) is not 3, and for one whose flag byte is 3
+    but whose system the prover found unsatisfied (a leaf that is not the tree's)."""
+    ctx = proving_key.ctx
+    count = len(payments)
+    if not count:
+        return [], []
+    cols = list(zip(*[_payment_bytes(*p) for p in payments]))
+    bufs = [(ctypes.c_uint8 * (count * len(col[0]))).from_buffer_copy(b"".join(col)) for col in cols]
+    cap = 4096
+    out = (ctypes.c_uint8 * (cap * count))()
+    lens = (ctypes.c_size_t * count)()
+    flags = (ctypes.c_uint8 * count)()
+    _check(ctx.lib.swm_payment_prove_many_at(ctx.h, proving_key.h, circuit.h, tree.h, bufs[0], bufs[1], bufs[2], bufs[3], count, rng.h,
+                                             1 if uncompressed else 0, out, cap, lens, flags), "swm_payment_prove_many_at", ctx)
+    raw = bytes(out)
+    return [raw[cap * i:cap * i + lens[i]] if lens[i] else None for i in range(count)], list(flags)
+
+
 def blake2s_circuit_shape(input_len):
     """swm_blake2s_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the Blake2s hash circuit over input_len
     bytes — what workloads.build_blake2s_hash emits."""

@@ -1519,3 +1519,190 @@ class ElGamalEncryption:
 
     def generate_constraints(self, cs):
         build_elgamal_encryption(cs, self.generator, self.public_key, self.message, self.randomness, self.ciphertext)
+
+
+# ===================================================================================================================
+# The payment circuit: Transaction::validate of examples/simple-payments (transaction.rs:89-139) as ONE statement over a
+# Poseidon account tree.  The reference proves the signature alone, with no public input; the sender's path, the balance
+# and the recipient's account are checked natively against state a third party does not hold.  Here the four checks are
+# rows of one system whose public inputs name the ledger: root, sender, recipient, amount.  The two existing blocks go in
+# verbatim: build_payment is the layout contract of csrc/host/payment_shape.h and csrc/payment_witness.hip.
+# With S / S_rows the counts of the Schnorr circuit over 10-byte messages, L = height - 1, C the chain values of one
+# permutation and M = 3 L + (2 + L) C the witnesses of one membership block over 72-byte leaves (two leaf permutations):
+#   instance  one, root, sender, recipient, amount
+#   witness   the Schnorr block (its 80 message bits are sender || recipient || amount; its `dec` bits of Y.x and Y.y are the
+#             first 64 bytes of the sender's leaf) | 64 balance bits | 64 bits of diff = (balance - amount) mod 2^64 | the
+#             sender's membership block | 576 recipient leaf bits | the recipient's membership block     S + 704 + 2 M
+#   rows      the Schnorr rows | booleanity of balance and diff | pack(balance) - pack(amount bits) - pack(diff) = 0 |
+#             pack(msg[0:8]) = sender, pack(msg[8:16]) = recipient, pack(msg[16:80]) = amount | the sender's membership:
+#             eight index rows (index bit l = id bit l for l < L, id bit l = 0 above), the leaf chain, per level booleanity,
+#             the delta row and C chain rows, the root row | booleanity of the recipient's leaf bits | the recipient's
+#             membership, the same                                         S_rows + 708 + 2 (8 + 2 C + L (2 + C) + 1)
+# balance, amount and diff are below 2^64, far below r: the packing row's field identity is the integer one, and it holds
+# exactly when amount <= balance.  A blank leaf's digest is 32 zero bytes and the hash of nothing, so membership of ANY
+# 72-byte leaf at index `recipient` states that the recipient has an account.  Ids are one byte: 2 <= height <= 9.
+# Every witness is computed honestly whatever the inputs say: a bad signature fails comparison rows of the Schnorr block
+# only, an overdraft the packing row only, a leaf that is not in the tree its membership's root row only.
+# ===================================================================================================================
+PAYMENT_MSG_LEN, PAYMENT_LEAF_LEN = 10, 72
+
+
+def payment_circuit_layout(params, height, salted=False):
+    """Offsets of the witness groups of build_payment and its three counts, as csrc/host/payment_shape.h states them.
+    "schnorr" and "membership" are the two blocks' own layouts (offsets relative to the block)."""
+    if not 2 <= height <= 9:
+        raise ValueError("payment circuit: 2 <= height <= 9 (an account id is one byte)")
+    sv = schnorr_circuit_layout(PAYMENT_MSG_LEN, salted)
+    mb = poseidon_membership_layout(params, height, PAYMENT_LEAF_LEN)
+    levels, c = mb["levels"], mb["permutation_values"]
+    lay = {"schnorr": sv, "membership": mb, "levels": levels, "membership_witnesses": mb["num_witness"]}
+    lay["balance"] = sv["num_witness"]
+    lay["diff"] = lay["balance"] + 64
+    lay["sender"] = lay["diff"] + 64
+    lay["recipient_bits"] = lay["sender"] + mb["num_witness"]
+    lay["recipient"] = lay["recipient_bits"] + 8 * PAYMENT_LEAF_LEN
+    lay["num_instance"] = 5
+    lay["num_witness"] = sv["num_witness"] + 704 + 2 * (3 * levels + (2 + levels) * c)
+    block_rows = 8 + 2 * c + levels * (2 + c) + 1
+    lay["num_constraints"] = sv["num_constraints"] + 708 + 2 * block_rows
+    lay["pack_row"] = sv["num_constraints"] + 128
+    lay["tie_rows"] = lay["pack_row"] + 1            # sender, recipient, amount
+    lay["sender_rows"] = lay["tie_rows"] + 3
+    lay["sender_root_row"] = lay["sender_rows"] + block_rows - 1
+    lay["recipient_bit_rows"] = lay["sender_root_row"] + 1
+    lay["recipient_rows"] = lay["recipient_bit_rows"] + 8 * PAYMENT_LEAF_LEN
+    lay["recipient_root_row"] = lay["recipient_rows"] + block_rows - 1
+    return lay
+
+
+def payment_public_inputs(root, message):
+    """The four public inputs of the payment circuit, in instance order: root (an int), then sender, recipient and amount out of
+    the 10 message bytes (ledger.transaction_message)."""
+    message = bytes(message)
+    if len(message) != PAYMENT_MSG_LEN:
+        raise ValueError("a payment message is %d bytes: sender, recipient, amount as u64" % PAYMENT_MSG_LEN)
+    return [int(root) % R_MODULUS, message[0], message[1], int.from_bytes(message[2:], "little")]
+
+
+def _py_membership(cs, one, params, leaf_bits, id_bits, index, siblings, root_v):
+    """One membership block: the witness section of build_poseidon_membership over leaf bits that already are variables, the
+    eight rows that tie the index bits to the id bits, and build_poseidon_membership's rows after its booleanity rows.
+    Returns the walked root's value."""
+    levels = len(siblings)
+    values = _PsNullSystem()
+    c = _ps_leaf_digest(values, None, params, [(None, v) for _, v in leaf_bits], PAYMENT_LEAF_LEN).value
+    cur_values = []
+    for lvl, s in enumerate(siblings):
+        cur_values.append(c)
+        a, b = (s, c) if (index >> lvl) & 1 else (c, s)
+        c = _ps_permute(values, None, params, [_PsLC({}, a), _PsLC({}, b), _PsLC()])[0].value
+    dirs = [_PsLC({cs.new_witness_variable((index >> lvl) & 1): 1}, (index >> lvl) & 1) for lvl in range(levels)]
+    sibs = [_PsLC({cs.new_witness_variable(s): 1}, s) for s in siblings]
+    deltas = []
+    for lvl in range(levels):
+        v = dirs[lvl].value * (siblings[lvl] - cur_values[lvl]) % R_MODULUS
+        deltas.append(_PsLC({cs.new_witness_variable(v): 1}, v))
+    for lvl in range(8):
+        if lvl < levels:
+            cs.enforce_constraint([(1, dirs[lvl].terms[0][1]), (R_MODULUS - 1, id_bits[lvl])], [(1, one)], [])
+        else:
+            cs.enforce_constraint([(1, id_bits[lvl])], [(1, one)], [])
+    cur = _ps_leaf_digest(cs, one, params, leaf_bits, PAYMENT_LEAF_LEN)
+    for lvl in range(levels):
+        b, s, d = dirs[lvl], sibs[lvl], deltas[lvl]
+        cs.enforce_constraint(b.terms, [(1, one), (R_MODULUS - 1, b.terms[0][1])], [])
+        cs.enforce_constraint(b.terms, _PsLC(s.coeffs, s.value).add(R_MODULUS - 1, cur).terms, d.terms)
+        left = _PsLC(cur.coeffs, cur.value).add(1, d)
+        right = _PsLC(s.coeffs, s.value).add(R_MODULUS - 1, d)
+        cur = _ps_permute(cs, one, params, [left, right, _PsLC()])[0]
+    cs.enforce_constraint(cur.terms, [(1, one)], root_v)
+    return c
+
+
+def build_payment(cs, generator, salt, params, height, message, signature, sender_leaf, sender_siblings, recipient_leaf,
+                  recipient_siblings, root=None):
+    """Emits the payment circuit into `cs`.  generator, salt: the Schnorr parameters; params: a hash.PoseidonParameters; message:
+    the 10 bytes sender || recipient || amount; signature: 64 bytes; the two leaves: 72 bytes each, x || y || balance (the sender's
+    key must be a canonical point of the curve); the two paths: ints, bottom up, height - 1 each.  `root` overrides the public
+    root, which otherwise is the root the sender's path leads to.  Returns the public inputs [root, sender, recipient, amount]."""
+    message, signature = bytes(message), bytes(signature)
+    sender_leaf, recipient_leaf = bytes(sender_leaf), bytes(recipient_leaf)
+    levels = height - 1
+    if not 2 <= height <= 9 or len(sender_siblings) != levels or len(recipient_siblings) != levels:
+        raise ValueError("payment circuit: 2 <= height <= 9 and two paths of height - 1 siblings")
+    if len(message) != PAYMENT_MSG_LEN or len(sender_leaf) != PAYMENT_LEAF_LEN or len(recipient_leaf) != PAYMENT_LEAF_LEN:
+        raise ValueError("payment circuit: a message of %d bytes and two leaves of %d" % (PAYMENT_MSG_LEN, PAYMENT_LEAF_LEN))
+    sender, recipient, amount = message[0], message[1], int.from_bytes(message[2:], "little")
+    if sender >> levels or recipient >> levels:
+        raise ValueError("payment circuit: an account id at or above 2^%d" % levels)
+    key = (int.from_bytes(sender_leaf[:32], "little"), int.from_bytes(sender_leaf[32:64], "little"))
+    if key[0] >= R_MODULUS or key[1] >= R_MODULUS:
+        raise ValueError("payment circuit: the sender's key is not canonical")
+    balance = int.from_bytes(sender_leaf[64:], "little")
+    sender_siblings = [int(s) % R_MODULUS for s in sender_siblings]
+    recipient_siblings = [int(s) % R_MODULUS for s in recipient_siblings]
+    one = cs.one()
+    base = len(cs.witness)
+    build_schnorr_verification(cs, generator, salt, key, message, signature)
+    lay = schnorr_circuit_layout(PAYMENT_MSG_LEN, salt is not None)
+    assert len(cs.witness) - base == lay["num_witness"]
+    msg = [("w", base + lay["msg"] + i) for i in range(80)]
+    key_bits = [(("w", base + lay["dec"] + i), cs.witness[base + lay["dec"] + i]) for i in range(512)]
+    # the root needs the sender's walk: in values first, as build_poseidon_membership does
+    if root is None:
+        values = _PsNullSystem()
+        bits = [(None, (byte >> i) & 1) for byte in sender_leaf for i in range(8)]
+        c = _ps_leaf_digest(values, None, params, bits, PAYMENT_LEAF_LEN).value
+        for lvl, s in enumerate(sender_siblings):
+            a, b = (s, c) if (sender >> lvl) & 1 else (c, s)
+            c = _ps_permute(values, None, params, [_PsLC({}, a), _PsLC({}, b), _PsLC()])[0].value
+        root = c
+    public = payment_public_inputs(root, message)
+    root_i, sender_i, recipient_i, amount_i = [cs.new_input_variable(v) for v in public]
+
+    def boolean(v):
+        var = cs.new_witness_variable(v)
+        cs.enforce_constraint([(1, var)], [(1, one), (R_MODULUS - 1, var)], [])
+        return var
+    # balance, diff
+    bal = [boolean((balance >> i) & 1) for i in range(64)]
+    diff_v = (balance - amount) % (1 << 64)
+    diff = [boolean((diff_v >> i) & 1) for i in range(64)]
+    cs.enforce_constraint([(1 << i, bal[i]) for i in range(64)] + [(R_MODULUS - (1 << i), msg[16 + i]) for i in range(64)]
+                          + [(R_MODULUS - (1 << i), diff[i]) for i in range(64)], [(1, one)], [])
+    # the message is the public input
+    cs.enforce_constraint([(1 << i, msg[i]) for i in range(8)], [(1, one)], [(1, sender_i)])
+    cs.enforce_constraint([(1 << i, msg[8 + i]) for i in range(8)], [(1, one)], [(1, recipient_i)])
+    cs.enforce_constraint([(1 << i, msg[16 + i]) for i in range(64)], [(1, one)], [(1, amount_i)])
+    # sender
+    sender_bits = key_bits + [(bal[i], (balance >> i) & 1) for i in range(64)]
+    _py_membership(cs, one, params, sender_bits, msg[0:8], sender, sender_siblings, [(1, root_i)])
+    # recipient
+    recipient_bits = [(boolean(v), v) for v in ((byte >> i) & 1 for byte in recipient_leaf for i in range(8))]
+    _py_membership(cs, one, params, recipient_bits, msg[8:16], recipient, recipient_siblings, [(1, root_i)])
+    return public
+
+
+def payment_circuit(params, height, message, signature, sender_leaf, sender_siblings, recipient_leaf, recipient_siblings,
+                    generator=ED_GENERATOR, salt=None, root=None):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs)."""
+    cs = ConstraintSystem()
+    public = build_payment(cs, generator, salt, params, height, message, signature, sender_leaf, sender_siblings, recipient_leaf,
+                           recipient_siblings, root)
+    return cs, public
+
+
+class PaymentValidation:
+    """The ConstraintSynthesizer of the payment statement for MarlinInst.index / prove: constants = the Schnorr and the sponge
+    parameters, public = root, sender, recipient, amount, witness = signature, the two leaves and their paths."""
+
+    def __init__(self, generator, salt, params, height, root, message, signature, sender_leaf, sender_path, recipient_leaf,
+                 recipient_path):
+        self.generator, self.salt, self.params, self.height, self.root = generator, salt, params, height, root
+        self.message, self.signature = bytes(message), bytes(signature)
+        self.sender_leaf, self.sender_path = bytes(sender_leaf), list(sender_path)
+        self.recipient_leaf, self.recipient_path = bytes(recipient_leaf), list(recipient_path)
+
+    def generate_constraints(self, cs):
+        build_payment(cs, self.generator, self.salt, self.params, self.height, self.message, self.signature, self.sender_leaf,
+                      self.sender_path, self.recipient_leaf, self.recipient_path, root=self.root)
