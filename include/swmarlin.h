@@ -811,6 +811,56 @@ int swm_payment_prove_many_at(swm_ctx *ctx, const swm_pk *pk, const swm_payment_
                               const uint8_t *recipient_leaves, size_t count, swm_rng *rng, unsigned flags, uint8_t *proofs_out,
                               size_t proof_cap, size_t *lens, uint8_t *item_flags);
 
+/* ---------------------------------------------------------------------------------------------- Transfer circuit: the state transition
+ * The assignment of the transfer circuit (simpleworks_amd/workloads.py, build_transfer) synthesised on the GPU for a BLOCK of
+ * transfers applied in order: State::apply_transaction of examples/simple-payments (ledger.rs:176-193) read sequentially as one
+ * statement.  Public input: old_root, new_root, sender, recipient, amount.  Witness: the payment circuit's up to and with the
+ * sender's membership block (against old_root); the sender's update block (the debited leaf walked with the same index bits and
+ * siblings); the intermediate root R1; 576 bits of the recipient's leaf IN THE TREE OF R1 and its membership block against R1; 64
+ * bits of (rbalance + amount) mod 2^64; the recipient's update block, whose root row is against new_root.  With the payment
+ * circuit's S, S_rows, L, C and M = 3 L + (2 + L) C:  num_instance = 6;  num_witness = S + 769 + 4 M - 4 L;
+ * num_constraints = S_rows + 773 + 2 (8 + 2 C + L (2 + C) + 1) + 2 (2 C + L (1 + C) + 1).
+ * swm_transfer_circuit_shape needs no GPU; it refuses what swm_payment_circuit_shape refuses.
+ * swm_transfer_circuit_create: the handle refers to the swm_schnorr and the swm_poseidon: keep them.
+ * swm_transfer_witness_at: `tree` is a resident tree of the circuit's parameters and height with 72-byte leaves (otherwise
+ * SWM_ERR_INVALID_ARG); accounts_inout is the account table, ALL 2^L leaves of 72 bytes in id order, an all-zero leaf = no account.
+ * One launch hashes the table and compares it with the tree's leaf level (an all-zero leaf against the zero digest): any
+ * difference refuses the WHOLE call with SWM_ERR_INVALID_ARG and leaves tree and table as they were.  Then transfer i is witnessed
+ * against the tree and the table as transfers 0 .. i-1 left them, and APPLIED to both exactly when flags[i] has bits 0 .. 3 set and
+ * status[i] is 0.  flags (one byte per transfer): bit 0 = the signature verifies under the sender leaf's key, bit 1 = amount <=
+ * balance, bit 2 = rbalance + amount < 2^64, bit 3 = both leaves hold an account, bit 4 = applied.  status (uint32 per transfer): bit
+ * 0 = the sender's key is no canonical point of the curve (a blank sender: the Schnorr block of that transfer is zero), bit 2 = an
+ * id >= 2^L (the blocks are those of the id's low L bits), bit 3 = sender == recipient.  The circuit reads a transfer to oneself as
+ * the sequential no-op, the reference's apply_transaction reads both balances first and adds the amount: the two disagree, so
+ * such a transfer is refused here.  Every witness is computed whatever the verdict: a refused transfer's witness is that of the
+ * transfer tried against the state it met (an unsatisfied system, or for status bit 3 a satisfied one that is not proved), and
+ * its old and new root are equal.  witness: count x num_witness x 4 Montgomery limbs; old_roots, new_roots: count x 32 bytes.  On
+ * return the tree holds the last new root and accounts_inout the balances after the block.  A block whose witnesses exceed 1 GiB
+ * goes in chunks, in order.
+ * swm_transfer_prove_many_at: the same single witness pass, then one prover call per APPLIED transfer, in order, each reading its
+ * slice on the device, with the public input (old_roots[i], new_roots[i], sender, recipient, amount).  proofs_out: count x
+ * proof_cap bytes; lens[i] = 0 exactly for the refused transfers.  THE TREE IS ADVANCED BEFORE THE PROOFS ARE MADE: a prover error
+ * after that is a library error (it ends the call with its code), and tree and table stay advanced.  old_roots / new_roots may be
+ * NULL here.
+ * swm_transfer_prove_at: one transfer; *len = 0 and bit 4 of *flag clear for a refused one. */
+typedef struct swm_transfer_circuit swm_transfer_circuit;
+int swm_transfer_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64_t alpha, size_t height, int salted, size_t *num_instance,
+                               size_t *num_witness, size_t *num_constraints);
+int swm_transfer_circuit_create(swm_ctx *ctx, const swm_schnorr *schnorr, const swm_poseidon *poseidon, size_t height,
+                                swm_transfer_circuit **out);
+void swm_transfer_circuit_destroy(swm_ctx *ctx, swm_transfer_circuit *circuit);
+int swm_transfer_witness_at(swm_ctx *ctx, const swm_transfer_circuit *circuit, swm_poseidon_tree *tree, uint8_t *accounts_inout,
+                            const uint8_t *messages, const uint8_t *signatures, size_t count, uint64_t *witnesses_out, uint8_t *old_roots,
+                            uint8_t *new_roots, uint8_t *flags, uint32_t *status);
+int swm_transfer_prove_many_at(swm_ctx *ctx, const swm_pk *pk, const swm_transfer_circuit *circuit, swm_poseidon_tree *tree,
+                               uint8_t *accounts_inout, const uint8_t *messages, const uint8_t *signatures, size_t count, swm_rng *rng,
+                               unsigned prove_flags, uint8_t *proofs_out, size_t proof_cap, size_t *lens, uint8_t *old_roots,
+                               uint8_t *new_roots, uint8_t *flags, uint32_t *status);
+int swm_transfer_prove_at(swm_ctx *ctx, const swm_pk *pk, const swm_transfer_circuit *circuit, swm_poseidon_tree *tree,
+                          uint8_t *accounts_inout, const uint8_t message[10], const uint8_t signature[64], swm_rng *rng,
+                          unsigned prove_flags, uint8_t *proof_out, size_t cap, size_t *len, uint8_t old_root[32], uint8_t new_root[32],
+                          uint8_t *flag, uint32_t *status);
+
 /* ---------------------------------------------------------------------------------------------- Blake2s random oracle
  * The reference's random oracle, unkeyed BLAKE2s-256 (RFC 7693), batched: one GPU lane per hash.  Replaces, on the GPU,
  *   src/schnorr_signature/blake2s.rs, examples/simple-payments/random_oracle/blake2s/mod.rs      RO::evaluate(&(), input)

@@ -196,6 +196,15 @@ ABI = {
                                                                                    ctypes.POINTER(_sz)]),
     "swm_payment_prove_many_at": (_int, [_vp, _vp, _vp, _vp] + [ctypes.c_void_p] * 4 + [_sz, _vp, ctypes.c_uint, ctypes.c_void_p, _sz,
                                                                                         ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_transfer_circuit_shape": (_int, [_sz, _sz, ctypes.c_uint64, _sz, _int, ctypes.POINTER(_sz), ctypes.POINTER(_sz),
+                                           ctypes.POINTER(_sz)]),
+    "swm_transfer_circuit_create": (_int, [_vp, _vp, _vp, _sz, ctypes.POINTER(_vp)]),
+    "swm_transfer_circuit_destroy": (None, [_vp, _vp]),
+    "swm_transfer_witness_at": (_int, [_vp, _vp, _vp] + [ctypes.c_void_p] * 3 + [_sz] + [ctypes.c_void_p] * 5),
+    "swm_transfer_prove_many_at": (_int, [_vp, _vp, _vp, _vp] + [ctypes.c_void_p] * 3 + [_sz, _vp, ctypes.c_uint, ctypes.c_void_p, _sz]
+                                   + [ctypes.c_void_p] * 5),
+    "swm_transfer_prove_at": (_int, [_vp, _vp, _vp, _vp] + [ctypes.c_void_p] * 3 + [_vp, ctypes.c_uint, ctypes.c_void_p, _sz]
+                              + [ctypes.c_void_p] * 5),
     "swm_blake2s_hash": (_int, [_vp, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
     "swm_blake2s_hash_dev": (_int, [_vp, _vp, _sz, _sz, _vp]),
     "swm_blake2s_circuit_shape": (_int, [_sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
@@ -1069,6 +1078,34 @@ class Context:
                                                      p(d_recipient_leaves), p(d_sender_siblings), p(d_recipient_siblings), count,
                                                      p(d_witness), p(d_flags), p(d_status), p(d_sender_roots), p(d_recipient_roots)),
                     "swm_payment_witness_dev")
+
+    # ---- Transfer circuit witness (include/swmarlin.h; simpleworks_amd/ledger.py, TransferCircuit, is the caller-facing mirror)
+    def transfer_circuit_create(self, schnorr_handle, poseidon_handle, height):
+        h = _vp()
+        self._check(self.lib.swm_transfer_circuit_create(self.h, schnorr_handle, poseidon_handle, height, ctypes.byref(h)),
+                    "swm_transfer_circuit_create")
+        return h
+
+    def transfer_circuit_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_transfer_circuit_destroy(self.h, handle)
+
+    def transfer_witness_at(self, handle, tree_handle, num_witness, accounts, messages, signatures):
+        """accounts uint8 [2^L, 72] (all-zero = no account), messages uint8 [count, 10], signatures uint8 [count, 64] -> (witness uint64
+        [count, num_witness, 4] Montgomery limbs, accounts after the block, old roots uint8 [count, 32], new roots, flags uint8
+        [count], status uint32 [count]).  The tree is advanced."""
+        m = self._rows(messages, 10)
+        n = m.shape[0]
+        sig = self._rows(signatures, 64, n)
+        acc = np.array(accounts, dtype=np.uint8, order="C", copy=True)
+        assert acc.ndim == 2 and acc.shape[1] == 72
+        witness = np.empty((n, num_witness, 4), dtype=np.uint64)
+        old, new = np.empty((n, 32), dtype=np.uint8), np.empty((n, 32), dtype=np.uint8)
+        flags, status = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32)
+        self._check(self.lib.swm_transfer_witness_at(self.h, handle, tree_handle, acc.ctypes.data, m.ctypes.data, sig.ctypes.data, n,
+                                                     witness.ctypes.data, old.ctypes.data, new.ctypes.data, flags.ctypes.data,
+                                                     status.ctypes.data), "swm_transfer_witness_at")
+        return witness, acc, old, new, flags, status
 
     # ---- Blake2s random oracle and its circuit's witness (include/swmarlin.h; simpleworks_amd/random_oracle.py is the caller-facing
     # mirror).  A device buffer is a DeviceBuffer or a raw device address (an int: a tensor's data_ptr()).

@@ -13,6 +13,7 @@
 #include "poseidon_tree_shape.h"
 #include "blake2s_shape.h"
 #include "payment_shape.h"
+#include "transfer_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
 extern "C" {
@@ -295,6 +296,25 @@ int swm_payment_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64_
     if (!payment_shape(full_rounds, partial_rounds, alpha, height, salted != 0, &s))
         return set_err(none, SWM_ERR_INVALID_ARG,
                        "payment_circuit_shape: %zu + %zu rounds, alpha %llu, height %zu (full rounds even and >= 2, at most %zu rounds, alpha "
+                       "2 .. %llu, %zu <= height <= %zu)",
+                       full_rounds, partial_rounds, (unsigned long long)alpha, height, (size_t)PC_MAX_ROUNDS, (unsigned long long)PC_MAX_ALPHA,
+                       (size_t)PY_MIN_HEIGHT, (size_t)PY_MAX_HEIGHT);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// The transfer circuit's shape, from the same arguments (transfer_shape.h; the layout is build_transfer's)
+int swm_transfer_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64_t alpha, size_t height, int salted, size_t* num_instance,
+                               size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "transfer_circuit_shape: NULL output");
+    TransferShape s;
+    if (!transfer_shape(full_rounds, partial_rounds, alpha, height, salted != 0, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG,
+                       "transfer_circuit_shape: %zu + %zu rounds, alpha %llu, height %zu (full rounds even and >= 2, at most %zu rounds, alpha "
                        "2 .. %llu, %zu <= height <= %zu)",
                        full_rounds, partial_rounds, (unsigned long long)alpha, height, (size_t)PC_MAX_ROUNDS, (unsigned long long)PC_MAX_ALPHA,
                        (size_t)PY_MIN_HEIGHT, (size_t)PY_MAX_HEIGHT);

@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(256) poseidon_tree_gather_kernel(const uint32_
 }
 
 struct PtwArgs {
-    unsigned levels, leaf_blocks;
+    unsigned levels, leaf_blocks, own_path;
     size_t leaf_len, n_elems, count, stride, bits_at, siblings_at, deltas_at, leaf_at, levels_at, perm_values;
 };
 
@@ -120,14 +120,52 @@ __global__ void __launch_bounds__(PS_LANES) poseidon_tree_record_kernel(const ui
     const Fr d = right ? fp_sub(s, cur) : fp_zero<Fr>();  // both < r: the difference mod r, in standard form as they are
     Fr* w = witness + p * T.stride;
     if (act) {
-        ptw_store(w + T.bits_at + l, right ? fp_one<Fr>() : fp_zero<Fr>());
-        ptw_store(w + T.siblings_at + l, fp_from_std(s));
+        if (T.own_path) {
+            ptw_store(w + T.bits_at + l, right ? fp_one<Fr>() : fp_zero<Fr>());
+            ptw_store(w + T.siblings_at + l, fp_from_std(s));
+        }
         ptw_store(w + T.deltas_at + l, fp_from_std(d));
     }
     s0 = fr29_mul_fenced(fr29_unpack(right ? s : cur), to_mont);  // cur_l + d_l
     s1 = fr29_mul_fenced(fr29_unpack(right ? cur : s), to_mont);  // s_l - d_l
     Fr* wp = w + T.levels_at + (size_t)l * T.perm_values;
     pw_permute(ps_tab, A, alpha_top, s0, s1, s2, wp, act, 0xFFFFFFFFu);
+}
+
+// The record half: `count` blocks from given digests (count x (L + 1) x 8 words, cur_0 .. cur_L) and siblings (count x L x 8 words).
+// own_path false: an update block, which walks another block's path again: no b_l and s_l are stored and its groups start 2 L
+// elements earlier (deltas | leaf chain | levels).
+int ptw_record(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const uint8_t* d_leaves, const uint64_t* d_indices, const uint32_t* d_dig,
+               const uint32_t* d_sib, size_t count, Fr* d_witness, size_t stride, bool own_path) {
+    if (!count) return SWM_OK;
+    const PoseidonTreeShape& s = c->shape;
+    const swm_poseidon* p = c->params;
+    const unsigned levels = (unsigned)s.levels;
+    PwArgs A = {};
+    A.rows = (unsigned)p->rows;
+    A.half_full = p->full_rounds / 2;
+    A.partial = p->partial_rounds;
+    A.alpha = p->alpha;
+    A.chain = (unsigned)s.chain;
+    pw_std_limbs(fp_one<Fr>(), &A.to_std);  // the words of Montgomery(1) ARE 2^256 mod r
+    PtwArgs T = {};
+    T.levels = levels;
+    T.leaf_blocks = pt_blocks(count);
+    T.leaf_len = s.leaf_len;
+    T.n_elems = s.elems;
+    T.count = count;
+    T.stride = stride;
+    const size_t skip = own_path ? 0 : 2 * s.levels;
+    T.own_path = own_path ? 1u : 0u;
+    T.bits_at = s.bits_at;
+    T.siblings_at = s.siblings_at;
+    T.deltas_at = s.deltas_at - skip;
+    T.leaf_at = s.leaf_at - skip;
+    T.levels_at = s.levels_at - skip;
+    T.perm_values = s.perm_values;
+    SWM_LAUNCH(ctx, "poseidon_tree_record", poseidon_tree_record_kernel, dim3(T.leaf_blocks + pt_blocks(count * levels)), dim3(PS_LANES),
+               pt_lds(p), pt_table(p), A, T, d_leaves, d_indices, d_sib, d_dig, d_witness);
+    return SWM_OK;
 }
 
 // `count` witnesses into d_witness (item i at d_witness + i * stride, 16-byte aligned).  With a tree the digests and the siblings are
@@ -152,29 +190,7 @@ int ptw_run(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const swm_poseidon
         SWM_LAUNCH(ctx, "poseidon_tree_walk", poseidon_tree_walk_kernel, dim3(pt_blocks(count)), dim3(PS_LANES), pt_lds(p), pt_table(p),
                    pt_params(p), levels, d_leaves, s.leaf_len, d_indices, d_siblings, count, d_dig, d_roots);
     }
-    PwArgs A = {};
-    A.rows = (unsigned)p->rows;
-    A.half_full = p->full_rounds / 2;
-    A.partial = p->partial_rounds;
-    A.alpha = p->alpha;
-    A.chain = (unsigned)s.chain;
-    pw_std_limbs(fp_one<Fr>(), &A.to_std);  // the words of Montgomery(1) ARE 2^256 mod r
-    PtwArgs T = {};
-    T.levels = levels;
-    T.leaf_blocks = pt_blocks(count);
-    T.leaf_len = s.leaf_len;
-    T.n_elems = s.elems;
-    T.count = count;
-    T.stride = stride;
-    T.bits_at = s.bits_at;
-    T.siblings_at = s.siblings_at;
-    T.deltas_at = s.deltas_at;
-    T.leaf_at = s.leaf_at;
-    T.levels_at = s.levels_at;
-    T.perm_values = s.perm_values;
-    SWM_LAUNCH(ctx, "poseidon_tree_record", poseidon_tree_record_kernel, dim3(T.leaf_blocks + pt_blocks(count * levels)), dim3(PS_LANES),
-               pt_lds(p), pt_table(p), A, T, d_leaves, d_indices, d_sib, (const uint32_t*)d_dig, d_witness);
-    return SWM_OK;
+    return ptw_record(ctx, c, d_leaves, d_indices, d_dig, d_sib, count, d_witness, stride, true);
 }
 
 // the host forms' checks: an index < 2^L, every sibling (may be NULL: a resident tree's) a canonical field element

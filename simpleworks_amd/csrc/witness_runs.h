@@ -37,5 +37,10 @@ int schnorr_check_keys(swm_ctx* ctx, const uint8_t* keys, size_t count);
 // without one the paths are walked and d_roots (may be NULL) takes their roots.
 int ptw_run(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const swm_poseidon_tree* tree, const uint8_t* d_leaves, const uint64_t* d_indices,
             const uint8_t* d_siblings, size_t count, Fr* d_witness, size_t stride, uint32_t* d_roots);
+// Its record half alone, from digests (count x (L + 1) x 8 words, cur_0 .. cur_L per path) and siblings (count x L x 8 words) that
+// the caller has: one launch.  own_path false: an update block (transfer_witness.hip), which walks another block's path with
+// another leaf: deltas | leaf chain | levels from d_witness on, no bits and no siblings of its own.
+int ptw_record(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const uint8_t* d_leaves, const uint64_t* d_indices, const uint32_t* d_dig,
+               const uint32_t* d_sib, size_t count, Fr* d_witness, size_t stride, bool own_path);
 
 }  // namespace swm

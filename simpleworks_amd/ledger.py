@@ -124,6 +124,47 @@ class PaymentCircuit:
             pass
 
 
+class TransferCircuit:
+    """The transfer circuit over resident Schnorr and Poseidon parameters (swm_transfer_circuit): synthesises the witness vector of
+    workloads.build_transfer for a block of transfers applied in order, and advances the tree and the account table through the
+    block.  A transfer is (message, signature).  Refers to both parameter sets: keep them alive."""
+
+    def __init__(self, sig_params, sponge, height):
+        self.ctx, self.sig_params, self.sponge, self.height = sig_params.ctx, sig_params, sponge, height
+        self.h = self.ctx.transfer_circuit_create(sig_params.h, sponge.h, height)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        from .marlin import transfer_circuit_shape
+        return transfer_circuit_shape(self.sponge.params, self.height, self.sig_params.salt is not None)
+
+    def witness_at(self, tree, accounts, transfers):
+        """Against a hash.PoseidonMerkleTree whose leaf level is the table `accounts` (2^L leaves of 72 bytes, all-zero = no
+        account): (witness uint64 [count, num_witness, 4], accounts after the block as bytes, old roots, new roots as ints, flags
+        uint8 [count], status uint32 [count]).  The tree is advanced."""
+        acc = np.frombuffer(b"".join(bytes(a) for a in accounts), dtype=np.uint8).reshape(-1, LEAF_LEN)
+        if acc.shape[0] != 1 << (self.height - 1):
+            raise ValueError("the account table is 2^(height - 1) leaves of %d bytes" % LEAF_LEN)
+        msgs = np.frombuffer(b"".join(bytes(t[0]) for t in transfers), dtype=np.uint8).reshape(len(transfers), -1)
+        sigs = np.frombuffer(b"".join(bytes(t[1]) for t in transfers), dtype=np.uint8).reshape(len(transfers), -1)
+        if msgs.shape[1] != MESSAGE_LEN or sigs.shape[1] != 64:
+            raise ValueError("a transfer is a %d-byte message and a 64-byte signature" % MESSAGE_LEN)
+        w, acc, old, new, flags, status = self.ctx.transfer_witness_at(self.h, tree.h, self.shape()[1], acc, msgs, sigs)
+        ints = lambda rows: [int.from_bytes(r.tobytes(), "little") for r in rows]
+        return w, [a.tobytes() for a in acc], ints(old), ints(new), flags, status
+
+    def free(self):
+        if self.h:
+            self.ctx.transfer_circuit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class State:
     """ledger::State.  The account tree is a hash.DeviceMerkleTree, or with account_tree="poseidon" a hash.PoseidonMerkleTree over
     parameters.poseidon; ids are AccountId(u8), the first one handed out is 1."""
@@ -152,6 +193,7 @@ class State:
         self.pub_key_to_id = {}
         self._proof_keys = None      # (SchnorrCircuit, proving key, verifying key), derived once
         self._payment_keys = None    # (PaymentCircuit, proving key, verifying key), the same for a Poseidon account tree
+        self._transfer_keys = None   # (TransferCircuit, proving key, verifying key), the same
 
     def root(self):
         return self.account_merkle_tree.root()
@@ -243,12 +285,67 @@ class State:
             self._payment_keys = (PaymentCircuit(sig, sponge, height), pk, vk)
         return self._payment_keys
 
+    def transfer_keys(self, rng):
+        """The transfer circuit (this ledger's parameters and tree height) with its Marlin keys, derived once as payment_keys
+        derives the payment circuit's."""
+        if self.account_tree != "poseidon":
+            raise ValueError("transfer_keys: the transfer circuit is over a Poseidon account tree")
+        if self._transfer_keys is None:
+            from . import marlin as M
+            from . import workloads as W
+            sig, sponge = self.parameters.sig_params, self.parameters.poseidon
+            height = self.account_merkle_tree.height()
+            leaf = AccountInformation(sig.generator, 0).to_bytes_le()
+            cs, _ = W.transfer_circuit(sponge.params, height, bytes(MESSAGE_LEN), bytes(64), leaf, [0] * (height - 1), leaf,
+                                       [0] * (height - 1), sig.generator, sig.salt)
+            packed = cs.pack()
+            nnz = max(int(m[0][-1]) for m in packed.mats)
+            srs = M.MarlinInst.universal_setup(cs.num_constraints, len(cs.instance) + len(cs.witness), nnz, rng, sig.ctx)
+            try:
+                pk, vk = M.MarlinInst.index_from_constraint_system(srs, packed)
+            finally:
+                srs.free()
+            self._transfer_keys = (TransferCircuit(sig, sponge, height), pk, vk)
+        return self._transfer_keys
+
+    def account_table(self):
+        """All 2^L leaves of the account tree as the state holds them, 72 bytes each; all-zero where there is no account."""
+        blank = bytes(LEAF_LEN)
+        return [self.id_to_account_info[i].to_bytes_le() if i in self.id_to_account_info else blank
+                for i in range(1 << (self.account_merkle_tree.height() - 1))]
+
+    def apply_transactions(self, pp, txs, rng, prove=True):
+        """A block of transactions applied in order, the state transition of each proved: one witness pass on the GPU advances the
+        account tree through the whole block, then (with prove) one proof per applied transaction, whose public inputs are
+        (old_root, new_root, sender, recipient, amount).  A Poseidon state only.  -> a list of (applied, proof or None, public
+        inputs), one per transaction; a refused transaction leaves the state as it was and publishes equal roots.  Unlike
+        apply_transaction, a payment to oneself is refused (the circuit reads it as a no-op, apply_transaction adds the amount)."""
+        if self.account_tree != "poseidon":
+            raise ValueError("apply_transactions: the transfer circuit is over a Poseidon account tree")
+        from . import marlin as M
+        from . import workloads as W
+        txs = list(txs)
+        if not txs:
+            return []
+        circuit, pk, _ = self.transfer_keys(rng)
+        block = [(tx.message(), tx.signature.to_bytes()) for tx in txs]
+        tree = self.account_merkle_tree
+        if prove:
+            proofs, public, flags, _, table = M.generate_transfer_proofs(pk, circuit, tree, self.account_table(), block, rng)
+        else:
+            _, table, old, new, flags, _ = circuit.witness_at(tree, self.account_table(), block)
+            proofs = [None] * len(txs)
+            public = [W.transfer_public_inputs(o, n, m) for o, n, (m, _) in zip(old, new, block)]
+        for i, info in self.id_to_account_info.items():
+            info.balance = int.from_bytes(table[i][64:], "little")
+        return [(bool(f & 16), proof, pub) for f, proof, pub in zip(flags, proofs, public)]
+
     def free(self):
-        for keys in (self._proof_keys, self._payment_keys):
+        for keys in (self._proof_keys, self._payment_keys, self._transfer_keys):
             if keys is not None:
                 keys[0].free()
                 keys[1].free()
-        self._proof_keys = self._payment_keys = None
+        self._proof_keys = self._payment_keys = self._transfer_keys = None
         self.account_merkle_tree.free()
 
 
@@ -262,6 +359,13 @@ def _prove_signature(state, public_key, message, signature, rng):
 
 def verify_payment(vk, public_inputs, proof, rng):
     """The verifier of a payment proof: public_inputs = [root, sender, recipient, amount] (workloads.payment_public_inputs)."""
+    from . import marlin as M
+    return M.verify_proof(vk, [int(v) for v in public_inputs], proof if isinstance(proof, M.MarlinProof) else M.MarlinProof(proof), rng)
+
+
+def verify_transfer(vk, public_inputs, proof, rng):
+    """The verifier of a transfer proof: public_inputs = [old_root, new_root, sender, recipient, amount]
+    (workloads.transfer_public_inputs)."""
     from . import marlin as M
     return M.verify_proof(vk, [int(v) for v in public_inputs], proof if isinstance(proof, M.MarlinProof) else M.MarlinProof(proof), rng)
 

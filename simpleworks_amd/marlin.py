@@ -644,6 +644,74 @@ def generate_payment_proofs(proving_key, circuit, tree, payments, rng, uncompres
     return [raw[cap * i:cap * i + lens[i]] if lens[i] else None for i in range(count)], list(flags)
 
 
+def transfer_circuit_shape(params, height, salted=False):
+    """swm_transfer_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the transfer circuit over a Poseidon
+    account tree of that height, with or without a Schnorr salt — what workloads.build_transfer emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_transfer_circuit_shape(params.full_rounds, params.partial_rounds, params.alpha, height, 1 if salted else 0,
+                                                     ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)), "swm_transfer_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_transfer_proofs(proving_key, circuit, tree, accounts, transfers, rng, uncompressed=False):
+    """swm_transfer_prove_many_at: the block `transfers` ((message, signature) each) applied IN ORDER to the resident account tree
+    `tree` (a hash.PoseidonMerkleTree) and to the account table `accounts` (2^L leaves of 72 bytes, all-zero = no account): one
+    witness pass over the whole block, then one prover call per applied transfer.  The tree is advanced before the proofs are made.
+    Returns (proofs, public, flags, status, accounts after the block): proofs[i] is the proof bytes or None for a refused transfer,
+    public[i] = workloads.transfer_public_inputs(old_root_i, new_root_i, message_i) (equal roots for a refused one), flags and
+    status as include/swmarlin.h lists them."""
+    import numpy as np
+    from . import workloads as W
+    ctx = proving_key.ctx
+    count = len(transfers)
+    acc = np.array([np.frombuffer(bytes(a), dtype=np.uint8) for a in accounts], dtype=np.uint8, order="C")
+    if acc.ndim != 2 or acc.shape[1] != 72 or acc.shape[0] != 1 << (circuit.height - 1):
+        raise ValueError("the account table is 2^(height - 1) leaves of 72 bytes")
+    if not count:
+        return [], [], [], [], [bytes(a) for a in acc]
+    msgs, sigs = [bytes(t[0]) for t in transfers], [bytes(t[1]) for t in transfers]
+    if any(len(m) != 10 for m in msgs) or any(len(s) != 64 for s in sigs):
+        raise ValueError("a transfer is a 10-byte message and a 64-byte signature")
+    m_b = (ctypes.c_uint8 * (10 * count)).from_buffer_copy(b"".join(msgs))
+    s_b = (ctypes.c_uint8 * (64 * count)).from_buffer_copy(b"".join(sigs))
+    cap = 4096
+    out = (ctypes.c_uint8 * (cap * count))()
+    lens = (ctypes.c_size_t * count)()
+    old, new = (ctypes.c_uint8 * (32 * count))(), (ctypes.c_uint8 * (32 * count))()
+    flags, status = (ctypes.c_uint8 * count)(), (ctypes.c_uint32 * count)()
+    _check(ctx.lib.swm_transfer_prove_many_at(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, m_b, s_b, count, rng.h,
+                                              1 if uncompressed else 0, out, cap, lens, old, new, flags, status),
+           "swm_transfer_prove_many_at", ctx)
+    raw, old, new = bytes(out), bytes(old), bytes(new)
+    public = [W.transfer_public_inputs(int.from_bytes(old[32 * i:32 * i + 32], "little"), int.from_bytes(new[32 * i:32 * i + 32], "little"),
+                                       msgs[i]) for i in range(count)]
+    return ([raw[cap * i:cap * i + lens[i]] if lens[i] else None for i in range(count)], public, list(flags), list(status),
+            [bytes(a) for a in acc])
+
+
+def generate_transfer_proof(proving_key, circuit, tree, accounts, message, signature, rng, uncompressed=False):
+    """swm_transfer_prove_at: one transfer; returns (proof or None, public inputs, flag, status, accounts after it)."""
+    import numpy as np
+    from . import workloads as W
+    ctx = proving_key.ctx
+    acc = np.array([np.frombuffer(bytes(a), dtype=np.uint8) for a in accounts], dtype=np.uint8, order="C")
+    if acc.ndim != 2 or acc.shape[1] != 72 or acc.shape[0] != 1 << (circuit.height - 1):
+        raise ValueError("the account table is 2^(height - 1) leaves of 72 bytes")
+    message, signature = bytes(message), bytes(signature)
+    if len(message) != 10 or len(signature) != 64:
+        raise ValueError("a transfer is a 10-byte message and a 64-byte signature")
+    m_b, s_b = (ctypes.c_uint8 * 10).from_buffer_copy(message), (ctypes.c_uint8 * 64).from_buffer_copy(signature)
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    old, new = (ctypes.c_uint8 * 32)(), (ctypes.c_uint8 * 32)()
+    flag, status = ctypes.c_uint8(0), ctypes.c_uint32(0)
+    _check(ctx.lib.swm_transfer_prove_at(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, m_b, s_b, rng.h, 1 if uncompressed else 0,
+                                         buf, len(buf), ctypes.byref(n), old, new, ctypes.byref(flag), ctypes.byref(status)),
+           "swm_transfer_prove_at", ctx)
+    public = W.transfer_public_inputs(int.from_bytes(bytes(old), "little"), int.from_bytes(bytes(new), "little"), message)
+    return (bytes(buf[: n.value]) if n.value else None, public, flag.value, status.value, [bytes(a) for a in acc])
+
+
 def blake2s_circuit_shape(input_len):
     """swm_blake2s_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the Blake2s hash circuit over input_len
     bytes — what workloads.build_blake2s_hash emits."""

@@ -1584,10 +1584,10 @@ def payment_public_inputs(root, message):
     return [int(root) % R_MODULUS, message[0], message[1], int.from_bytes(message[2:], "little")]
 
 
-def _py_membership(cs, one, params, leaf_bits, id_bits, index, siblings, root_v):
+def _py_membership(cs, one, params, leaf_bits, id_bits, index, siblings, root_v, keep=None):
     """One membership block: the witness section of build_poseidon_membership over leaf bits that already are variables, the
     eight rows that tie the index bits to the id bits, and build_poseidon_membership's rows after its booleanity rows.
-    Returns the walked root's value."""
+    Returns the walked root's value.  keep (a list): receives the b_l and the s_l, for a block that walks the same path again."""
     levels = len(siblings)
     values = _PsNullSystem()
     c = _ps_leaf_digest(values, None, params, [(None, v) for _, v in leaf_bits], PAYMENT_LEAF_LEN).value
@@ -1602,6 +1602,8 @@ def _py_membership(cs, one, params, leaf_bits, id_bits, index, siblings, root_v)
     for lvl in range(levels):
         v = dirs[lvl].value * (siblings[lvl] - cur_values[lvl]) % R_MODULUS
         deltas.append(_PsLC({cs.new_witness_variable(v): 1}, v))
+    if keep is not None:
+        keep.extend([dirs, sibs])
     for lvl in range(8):
         if lvl < levels:
             cs.enforce_constraint([(1, dirs[lvl].terms[0][1]), (R_MODULUS - 1, id_bits[lvl])], [(1, one)], [])
@@ -1706,3 +1708,205 @@ class PaymentValidation:
     def generate_constraints(self, cs):
         build_payment(cs, self.generator, self.salt, self.params, self.height, self.message, self.signature, self.sender_leaf,
                       self.sender_path, self.recipient_leaf, self.recipient_path, root=self.root)
+
+
+# ===================================================================================================================
+# The ledger's state transition as one circuit: State::apply_transaction of examples/simple-payments (ledger.rs:176-193) read
+# sequentially over a Poseidon account tree.  Transaction::validate holds against old_root; debiting the sender gives the
+# intermediate root R1, a witness; crediting the recipient in the tree of R1 gives new_root.  build_transfer is the layout contract
+# of csrc/host/transfer_shape.h and csrc/transfer_witness.hip.  With the payment circuit's S, S_rows, L, C and M (above) and
+# U = M - 2 L = L + (2 + L) C the witnesses of one update block:
+#   instance  one, old_root, new_root, sender, recipient, amount
+#   witness   build_payment's up to and with the sender's membership block (against old_root)        S + 128 + M
+#             the sender's update block: d'_l = b_l (s_l - cur'_l) | the leaf chain over Y.x || Y.y || diff | L level chains,
+#             walked with the membership block's OWN b_l and s_l                                      U
+#             R1                                                                                      1
+#             576 recipient leaf bits | the recipient's membership block against R1                   576 + M
+#             64 bits of sum = (rbalance + amount) mod 2^64                                           64
+#             the recipient's update block over key bits || sum, the recipient block's b_l and s_l    U
+#   rows      build_payment's up to and with the sender's root row | the sender's update: the leaf chain, per level the delta row
+#             and C chain rows, cur'_L = R1 | booleanity of the recipient's bits | the recipient's membership, root row against
+#             R1 | booleanity of sum, pack(rbalance) + pack(amount) - pack(sum) = 0 | the recipient's update, root row against
+#             new_root                S_rows + 132 + B + 576 + B + 65 + 2 (2 C + L (1 + C) + 1),  B = 8 + 2 C + L (2 + C) + 1
+# rbalance, amount and sum are below 2^64: the sum row's field identity is the integer one and holds exactly when the addition
+# does not overflow (checked_add), as the diff row stands for checked_sub.  An id at or above 2^L walks the path of its low L bits
+# and fails an index row.  sender == recipient is the sequential no-op here (the recipient's leaf in the R1 tree is the debited
+# leaf); the reference's apply_transaction reads both balances first and ADDS the amount, so the library's entry points refuse
+# such a transfer and prove nothing for it.
+# ===================================================================================================================
+def transfer_circuit_layout(params, height, salted=False):
+    """Offsets of the witness groups and the named rows of build_transfer and its three counts, as csrc/host/transfer_shape.h
+    states them."""
+    py = payment_circuit_layout(params, height, salted)
+    mb = py["membership"]
+    levels, c, m = py["levels"], mb["permutation_values"], mb["num_witness"]
+    u = m - 2 * levels
+    lay = {"payment": py, "schnorr": py["schnorr"], "membership": mb, "levels": levels, "membership_witnesses": m, "update_witnesses": u}
+    for k in ("balance", "diff", "sender"):
+        lay[k] = py[k]
+    lay["sender_update"] = lay["sender"] + m
+    lay["r1"] = lay["sender_update"] + u
+    lay["recipient_bits"] = lay["r1"] + 1
+    lay["recipient"] = lay["recipient_bits"] + 8 * PAYMENT_LEAF_LEN
+    lay["sum"] = lay["recipient"] + m
+    lay["recipient_update"] = lay["sum"] + 64
+    lay["num_instance"] = 6
+    lay["num_witness"] = lay["recipient_update"] + u
+    # an update block's own offsets
+    lay["update"] = {"deltas": 0, "leaf": levels, "level0": levels + 2 * c}
+    block_rows = 8 + 2 * c + levels * (2 + c) + 1
+    update_rows = 2 * c + levels * (1 + c) + 1
+    for k in ("pack_row", "tie_rows", "sender_rows", "sender_root_row"):
+        lay[k] = py[k]
+    lay["sender_update_rows"] = lay["sender_root_row"] + 1
+    lay["sender_r1_row"] = lay["sender_update_rows"] + update_rows - 1
+    lay["recipient_bit_rows"] = lay["sender_r1_row"] + 1
+    lay["recipient_rows"] = lay["recipient_bit_rows"] + 8 * PAYMENT_LEAF_LEN
+    lay["recipient_r1_row"] = lay["recipient_rows"] + block_rows - 1
+    lay["sum_rows"] = lay["recipient_r1_row"] + 1
+    lay["sum_pack_row"] = lay["sum_rows"] + 64
+    lay["recipient_update_rows"] = lay["sum_pack_row"] + 1
+    lay["new_root_row"] = lay["recipient_update_rows"] + update_rows - 1
+    lay["num_constraints"] = lay["new_root_row"] + 1
+    return lay
+
+
+def transfer_public_inputs(old_root, new_root, message):
+    """The five public inputs of the transfer circuit, in instance order: old_root, new_root (ints), then sender, recipient and
+    amount out of the 10 message bytes."""
+    return [int(old_root) % R_MODULUS, int(new_root) % R_MODULUS] + payment_public_inputs(0, message)[1:]
+
+
+def _tr_walk(params, leaf_bits, index, siblings):
+    """The values cur_0 .. cur_L of a leaf's walk."""
+    values = _PsNullSystem()
+    c = _ps_leaf_digest(values, None, params, [(None, v) for _, v in leaf_bits], PAYMENT_LEAF_LEN).value
+    curs = [c]
+    for lvl, s in enumerate(siblings):
+        a, b = (s, c) if (index >> lvl) & 1 else (c, s)
+        c = _ps_permute(values, None, params, [_PsLC({}, a), _PsLC({}, b), _PsLC()])[0].value
+        curs.append(c)
+    return curs
+
+
+def _tr_update(cs, one, params, leaf_bits, dirs, sibs, root_v):
+    """One update block: another leaf walked up the path of a membership block (its b_l and s_l, no variables of their own).
+    Returns the walked root's value."""
+    levels = len(sibs)
+    index = sum(d.value << lvl for lvl, d in enumerate(dirs))
+    curs = _tr_walk(params, leaf_bits, index, [s.value for s in sibs])
+    deltas = []
+    for lvl in range(levels):
+        v = dirs[lvl].value * (sibs[lvl].value - curs[lvl]) % R_MODULUS
+        deltas.append(_PsLC({cs.new_witness_variable(v): 1}, v))
+    cur = _ps_leaf_digest(cs, one, params, leaf_bits, PAYMENT_LEAF_LEN)
+    for lvl in range(levels):
+        b, s, d = dirs[lvl], sibs[lvl], deltas[lvl]
+        cs.enforce_constraint(b.terms, _PsLC(s.coeffs, s.value).add(R_MODULUS - 1, cur).terms, d.terms)
+        left = _PsLC(cur.coeffs, cur.value).add(1, d)
+        right = _PsLC(s.coeffs, s.value).add(R_MODULUS - 1, d)
+        cur = _ps_permute(cs, one, params, [left, right, _PsLC()])[0]
+    if root_v is None:      # the root is a witness of this block's own: allocated after the chains, tied by the last row
+        return cur
+    cs.enforce_constraint(cur.terms, [(1, one)], root_v)
+    return cur.value
+
+
+def build_transfer(cs, generator, salt, params, height, message, signature, sender_leaf, sender_siblings, recipient_leaf,
+                   recipient_siblings, old_root=None, new_root=None, r1=None):
+    """Emits the transfer circuit into `cs`.  The arguments are build_payment's, with two differences: recipient_leaf and
+    recipient_siblings are those of the INTERMEDIATE tree (after the sender's debit), and an id at or above 2^(height - 1) is
+    taken by its low bits.  old_root, new_root, r1 override the two public roots and the witness R1, which otherwise are the
+    walked values.  Returns the public inputs [old_root, new_root, sender, recipient, amount]."""
+    message, signature = bytes(message), bytes(signature)
+    sender_leaf, recipient_leaf = bytes(sender_leaf), bytes(recipient_leaf)
+    levels = height - 1
+    if not 2 <= height <= 9 or len(sender_siblings) != levels or len(recipient_siblings) != levels:
+        raise ValueError("transfer circuit: 2 <= height <= 9 and two paths of height - 1 siblings")
+    if len(message) != PAYMENT_MSG_LEN or len(sender_leaf) != PAYMENT_LEAF_LEN or len(recipient_leaf) != PAYMENT_LEAF_LEN:
+        raise ValueError("transfer circuit: a message of %d bytes and two leaves of %d" % (PAYMENT_MSG_LEN, PAYMENT_LEAF_LEN))
+    mask = (1 << levels) - 1
+    sender, recipient, amount = message[0] & mask, message[1] & mask, int.from_bytes(message[2:], "little")
+    key = (int.from_bytes(sender_leaf[:32], "little"), int.from_bytes(sender_leaf[32:64], "little"))
+    if key[0] >= R_MODULUS or key[1] >= R_MODULUS:
+        raise ValueError("transfer circuit: the sender's key is not canonical")
+    balance = int.from_bytes(sender_leaf[64:], "little")
+    rbalance = int.from_bytes(recipient_leaf[64:], "little")
+    sender_siblings = [int(s) % R_MODULUS for s in sender_siblings]
+    recipient_siblings = [int(s) % R_MODULUS for s in recipient_siblings]
+    diff_v, sum_v = (balance - amount) % (1 << 64), (rbalance + amount) % (1 << 64)
+
+    def leaf_values(leaf, value):
+        return [(None, (byte >> i) & 1) for byte in leaf[:64] + value.to_bytes(8, "little") for i in range(8)]
+    old_v = _tr_walk(params, leaf_values(sender_leaf, balance), sender, sender_siblings)[-1]
+    r1_v = _tr_walk(params, leaf_values(sender_leaf, diff_v), sender, sender_siblings)[-1]
+    new_v = _tr_walk(params, leaf_values(recipient_leaf, sum_v), recipient, recipient_siblings)[-1]
+    old_root = old_v if old_root is None else int(old_root) % R_MODULUS
+    new_root = new_v if new_root is None else int(new_root) % R_MODULUS
+    r1 = r1_v if r1 is None else int(r1) % R_MODULUS
+    one = cs.one()
+    base = len(cs.witness)
+    build_schnorr_verification(cs, generator, salt, key, message, signature)
+    lay = schnorr_circuit_layout(PAYMENT_MSG_LEN, salt is not None)
+    assert len(cs.witness) - base == lay["num_witness"]
+    msg = [("w", base + lay["msg"] + i) for i in range(80)]
+    key_bits = [(("w", base + lay["dec"] + i), cs.witness[base + lay["dec"] + i]) for i in range(512)]
+    public = transfer_public_inputs(old_root, new_root, message)
+    old_i, new_i, sender_i, recipient_i, amount_i = [cs.new_input_variable(v) for v in public]
+
+    def boolean(v):
+        var = cs.new_witness_variable(v)
+        cs.enforce_constraint([(1, var)], [(1, one), (R_MODULUS - 1, var)], [])
+        return var
+
+    def pack(bits, sign=1):
+        return [((1 << i) if sign > 0 else R_MODULUS - (1 << i), b) for i, b in enumerate(bits)]
+    # balance, diff, the ties: build_payment's
+    bal = [boolean((balance >> i) & 1) for i in range(64)]
+    diff = [boolean((diff_v >> i) & 1) for i in range(64)]
+    cs.enforce_constraint(pack(bal) + pack(msg[16:80], -1) + pack(diff, -1), [(1, one)], [])
+    cs.enforce_constraint(pack(msg[0:8]), [(1, one)], [(1, sender_i)])
+    cs.enforce_constraint(pack(msg[8:16]), [(1, one)], [(1, recipient_i)])
+    cs.enforce_constraint(pack(msg[16:80]), [(1, one)], [(1, amount_i)])
+    # the sender: in the old tree, then debited
+    path = []
+    _py_membership(cs, one, params, key_bits + [(bal[i], (balance >> i) & 1) for i in range(64)], msg[0:8], sender, sender_siblings,
+                   [(1, old_i)], keep=path)
+    cur = _tr_update(cs, one, params, key_bits + [(diff[i], (diff_v >> i) & 1) for i in range(64)], path[0], path[1], None)
+    r1_w = cs.new_witness_variable(r1)
+    cs.enforce_constraint(cur.terms, [(1, one)], [(1, r1_w)])
+    # the recipient: in the tree of R1, then credited
+    recipient_bits = [(boolean(v), v) for v in ((byte >> i) & 1 for byte in recipient_leaf for i in range(8))]
+    path = []
+    _py_membership(cs, one, params, recipient_bits, msg[8:16], recipient, recipient_siblings, [(1, r1_w)], keep=path)
+    total = [boolean((sum_v >> i) & 1) for i in range(64)]
+    cs.enforce_constraint(pack([b for b, _ in recipient_bits[512:]]) + pack(msg[16:80]) + pack(total, -1), [(1, one)], [])
+    _tr_update(cs, one, params, recipient_bits[:512] + [(total[i], (sum_v >> i) & 1) for i in range(64)], path[0], path[1], [(1, new_i)])
+    return public
+
+
+def transfer_circuit(params, height, message, signature, sender_leaf, sender_siblings, recipient_leaf, recipient_siblings,
+                     generator=ED_GENERATOR, salt=None, old_root=None, new_root=None, r1=None):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs)."""
+    cs = ConstraintSystem()
+    public = build_transfer(cs, generator, salt, params, height, message, signature, sender_leaf, sender_siblings, recipient_leaf,
+                            recipient_siblings, old_root, new_root, r1)
+    return cs, public
+
+
+class TransferValidation:
+    """The ConstraintSynthesizer of the transfer statement for MarlinInst.index / prove: constants = the Schnorr and the sponge
+    parameters, public = old_root, new_root, sender, recipient, amount, witness = signature, the sender's leaf and path in the old
+    tree, the recipient's in the intermediate one."""
+
+    def __init__(self, generator, salt, params, height, old_root, new_root, message, signature, sender_leaf, sender_path,
+                 recipient_leaf, recipient_path):
+        self.generator, self.salt, self.params, self.height = generator, salt, params, height
+        self.old_root, self.new_root = old_root, new_root
+        self.message, self.signature = bytes(message), bytes(signature)
+        self.sender_leaf, self.sender_path = bytes(sender_leaf), list(sender_path)
+        self.recipient_leaf, self.recipient_path = bytes(recipient_leaf), list(recipient_path)
+
+    def generate_constraints(self, cs):
+        build_transfer(cs, self.generator, self.salt, self.params, self.height, self.message, self.signature, self.sender_leaf,
+                       self.sender_path, self.recipient_leaf, self.recipient_path, old_root=self.old_root, new_root=self.new_root)
