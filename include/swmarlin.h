@@ -1022,6 +1022,14 @@ int swm_selftest_p28(swm_ctx *ctx, int op, const uint64_t *a, const uint64_t *b,
  *     out = the 3 N coefficients of the polynomial of degree < 3 N that takes them */
 int swm_selftest_poly(swm_ctx *ctx, int op, void *data, size_t n, size_t m, const uint64_t z[4], const uint64_t *pieces,
                       size_t npieces, void *out);
+/* Device self-test of the planned sparse mat-vec (csrc/spmv.hip) as the prover and swm_r1cs_is_satisfied run it: the host CSR
+ * (rowptr: rows + 1 words from 0, monotone; col < z_len; val: nnz x 4 uint64, Montgomery form) is uploaded the way a key's matrix
+ * is, which records its plan (rows above 64 entries cut into chunks of 2048), and out = M z (rows x 4 uint64) is computed with
+ * that plan; the device result starts as bytes 0xFF, so a row that the schedule leaves unwritten shows.  plan_counts (optional):
+ * [0] = the number of chunks, [1] = the number of long rows of the plan.
+ * SWM_ERR_INVALID_ARG: rows = 0, z_len = 0, a NULL pointer, row pointers that do not start at 0 or decrease, a column >= z_len. */
+int swm_selftest_spmv_plan(swm_ctx *ctx, const uint32_t *rowptr, const uint32_t *col, const uint64_t *val, size_t rows,
+                           const uint64_t *z, size_t z_len, uint64_t *out, uint32_t plan_counts[2]);
 /* The bulk Fr sampler of the prover (sample_fr_bulk) on a generator handle: `need` elements drawn into a device buffer and
  * downloaded to out_mont (n x 4 uint64, Montgomery form), advancing rng as `need` successive swm_rng_rand_fr calls would. */
 int swm_selftest_sample_fr(swm_ctx *ctx, swm_rng *rng, size_t need, uint64_t *out_mont);

@@ -461,6 +461,9 @@ def index(srs, cs):
     ics = pad_and_square(cs)
     a, b, c = ics.to_matrices()
     num_non_zero = max(sum(len(r) for r in m) for m in (a, b, c))
+    if num_non_zero < 2:
+        # |K| = 1: the degree bound |K| - 2 of g_2 does not exist (it underflows in ark-marlin as well)
+        raise MarlinError("index: |K| < 2: the densest of A, B, C needs at least two non-zero entries")
     balance_matrices(a, b)
     num_constraints = ics.num_constraints
     num_variables = len(ics.instance) + len(ics.witness)

@@ -224,6 +224,7 @@ ABI = {
     "swm_selftest_fr29": (_int, [_vp, _int, _u32p, _u32p, _u32p, _u32p, _sz]),
     "swm_selftest_p28": (_int, [_vp, _int, _u64p, _u64p, _u32p, _u64p, _u64p, _u32p, _sz]),
     "swm_selftest_poly": (_int, [_vp, _int, ctypes.c_void_p, _sz, _sz, _u64p, _u64p, _sz, ctypes.c_void_p]),
+    "swm_selftest_spmv_plan": (_int, [_vp, _u32p, _u32p, _u64p, _sz, _u64p, _sz, _u64p, _u32p]),
     "swm_selftest_sample_fr": (_int, [_vp, _vp, _sz, _u64p]),
     "swm_verify_proofs_batch": (_int, [_vp, _vp, _u64p, _sz, _vp, ctypes.POINTER(_sz), _sz, ctypes.c_uint, _vp,
                                        ctypes.POINTER(_int), ctypes.POINTER(_int)]),
@@ -1293,6 +1294,21 @@ class Context:
         out = np.zeros(w.size + 1, dtype=np.uint32)
         self._poly(8, w, w.size, 0, None, None, out)
         return out[:-1], int(out[-1])
+
+    def selftest_spmv_plan(self, rowptr, col, val_mont, z_mont):
+        """swm_selftest_spmv_plan: M z by the planned schedule (the plan recorded when a key's matrix is uploaded).  Returns
+        (rows x 4 uint64, number of chunks, number of long rows of the plan)."""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.uint32)
+        col = np.ascontiguousarray(col, dtype=np.uint32)
+        val = np.ascontiguousarray(val_mont, dtype=np.uint64).reshape(-1, 4)
+        z = np.ascontiguousarray(z_mont, dtype=np.uint64).reshape(-1, 4)
+        rows = rowptr.shape[0] - 1
+        out = np.zeros((rows, 4), dtype=np.uint64)
+        counts = np.zeros(2, dtype=np.uint32)
+        self._check(self.lib.swm_selftest_spmv_plan(self.h, _p32(rowptr), _p32(col) if col.size else None,
+                                                    _p64(val) if val.size else None, rows, _p64(z), z.shape[0], _p64(out),
+                                                    _p32(counts)), "swm_selftest_spmv_plan")
+        return out, int(counts[0]), int(counts[1])
 
     def selftest_sample_fr(self, rng, need):
         """sample_fr_bulk on a generator handle (simpleworks_amd.marlin.Rng): need x 4 uint64, Montgomery form."""

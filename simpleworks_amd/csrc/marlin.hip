@@ -930,6 +930,9 @@ void index_impl(swm_ctx* ctx, const swm_srs* srs, const swm_r1cs* cs, swm_pk** o
     PaddedR1cs p = pad_and_square(cs);
     std::unique_ptr<swm_pk> pk(new swm_pk());
     size_t nnz = std::max(p.a.nnz(), std::max(p.b.nnz(), p.c.nnz()));
+    // |K| = 1 has no degree bound |K| - 2 (ark-marlin underflows there as well): refused before anything touches the device
+    if (nnz < 2)
+        throw MarlinError(SWM_ERR_INVALID_ARG, "index: |K| < 2: the densest of A, B, C needs at least two non-zero entries");
     balance_matrices(p.a, p.b);
     pk->info.num_constraints = p.ncons;
     pk->info.num_variables = p.inst.size() + p.wit.size();
@@ -2772,6 +2775,40 @@ int swm_selftest_poly(swm_ctx* ctx, int op, void* data, size_t n, size_t m, cons
     if (op == 10 && (m < 1 || m > 26 || n != ((size_t)3 << m))) return SWM_ERR_INVALID_ARG;
     SWM_ON_DEVICE(ctx);
     SWM_GUARD(ctx, selftest_poly_impl(ctx, op, data, n, m, z, pieces, npieces, out));
+}
+// spmv_run with the plan upload_csr records for a key's matrix, on a host CSR in the memory form
+static void selftest_spmv_plan_impl(swm_ctx* ctx, const uint32_t* rowptr, const uint32_t* col, const uint64_t* val, size_t rows,
+                                    const uint64_t* z, size_t z_len, uint64_t* out, uint32_t* plan_counts) {
+    const size_t nnz = rowptr[rows];
+    HostCsr m;
+    m.rowptr.assign(rowptr, rowptr + rows + 1);
+    m.col.assign(col, col + nnz);
+    m.val.resize(nnz);
+    if (nnz) memcpy(m.val.data(), val, nnz * sizeof(Fr));
+    DevCsr d = upload_csr(ctx, m);
+    DVec dz(ctx, z_len), o(ctx, rows);
+    dz.upload((const Fr*)z, z_len);
+    // a row that no kernel of the schedule writes must show: the pool may hand back a block that holds an earlier result
+    hip_check(ctx, hipMemsetAsync(o.p, 0xFF, rows * sizeof(Fr), ctx->stream), "memset");
+    rc_check(ctx, spmv_run(ctx, d.rowptr.p, d.col.p, d.val.p, dz.p, o.p, rows, &d.plan));
+    std::vector<Fr> h = o.download(0, rows);
+    memcpy(out, h.data(), rows * sizeof(Fr));
+    if (plan_counts) {
+        plan_counts[0] = d.plan.n_chunks;
+        plan_counts[1] = d.plan.n_lrows;
+    }
+}
+int swm_selftest_spmv_plan(swm_ctx* ctx, const uint32_t* rowptr, const uint32_t* col, const uint64_t* val, size_t rows,
+                           const uint64_t* z, size_t z_len, uint64_t* out, uint32_t plan_counts[2]) {
+    if (!ctx || !rowptr || !rows || rows >= ((size_t)1 << 31) || !z || !z_len || !out || rowptr[0] != 0) return SWM_ERR_INVALID_ARG;
+    for (size_t r = 0; r < rows; r++)
+        if (rowptr[r + 1] < rowptr[r]) return SWM_ERR_INVALID_ARG;
+    const size_t nnz = rowptr[rows];
+    if (nnz && (!col || !val)) return SWM_ERR_INVALID_ARG;
+    for (size_t k = 0; k < nnz; k++)
+        if (col[k] >= z_len) return SWM_ERR_INVALID_ARG;
+    SWM_ON_DEVICE(ctx);
+    SWM_GUARD(ctx, selftest_spmv_plan_impl(ctx, rowptr, col, val, rows, z, z_len, out, plan_counts));
 }
 // sample_fr_bulk on a generator handle into a device buffer, then the download
 static void selftest_sample_impl(swm_ctx* ctx, ChaChaRng& rng, size_t need, uint64_t* out_mont) {
