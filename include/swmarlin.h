@@ -811,6 +811,70 @@ int swm_payment_prove_many_at(swm_ctx *ctx, const swm_pk *pk, const swm_payment_
                               const uint8_t *recipient_leaves, size_t count, swm_rng *rng, unsigned flags, uint8_t *proofs_out,
                               size_t proof_cap, size_t *lens, uint8_t *item_flags);
 
+/* ---------------------------------------------------------------------------------------------- Pedersen payment circuit witness
+ * The assignment of the payment circuit over a PEDERSEN account tree (simpleworks_amd/workloads.py, build_pedersen_payment)
+ * synthesised on the GPU: the statement, the public input (root, sender, recipient, amount), the flag byte and the status word are
+ * the payment circuit's above; the tree is the swm_merkle_tree of examples/simple-payments, a leaf CRH of at least 144 windows of 4
+ * bits (one 72-byte leaf exactly) and a two-to-one CRH of at least 128.  Witness: the Schnorr verification circuit over the 10
+ * message bytes, unchanged; 64 balance bits; 64 bits of (balance - amount) mod 2^64; the sender's membership section; 576 recipient
+ * leaf bits; the recipient's membership section.  A section is the leaf hash (575 conditional additions of six witnesses) and L =
+ * height - 1 level blocks of the membership circuit (3581 witnesses, 3588 rows each).  With S / S_rows the Schnorr circuit's counts
+ * for msg_len 10:  num_instance = 5;  num_witness = S + 704 + 2 (3450 + 3581 L);  num_constraints = S_rows + 708 + 2 (3459 + 3588 L).
+ * swm_pedersen_payment_circuit_shape needs no GPU.  SWM_ERR_INVALID_ARG: a height outside 2 .. 9 (an account id is one byte), a NULL
+ * output.
+ * swm_pedersen_payment_circuit_create: the handle refers to the swm_schnorr and the two swm_pedersen: keep them.  SWM_ERR_INVALID_ARG:
+ * windows of other than 4 bits, fewer than 144 leaf or 128 two-to-one windows.
+ * Inputs per payment: 10 message bytes, 64 signature bytes, the two leaves of 72 bytes; the leaf indices are message bytes 0 and 1.
+ * flags (one byte per payment): bit 0 = the signature verifies under the sender leaf's key, bit 1 = amount <= balance.  Every
+ * witness is computed whatever the flags say; the system is satisfied only when they are 3 and both leaves are the tree's.
+ * swm_pedersen_payment_witness: no tree; the two sibling arrays are count x L x 32 bytes bottom up.  Refuses the WHOLE call with
+ * SWM_ERR_INVALID_ARG: a sender key that is no canonical point of the curve, a sibling >= r, an id >= 2^L.  witness: count x
+ * num_witness x 4 Montgomery limbs; sender_roots / recipient_roots (may be NULL): count x 32 bytes, the roots the two paths lead
+ * to.  A batch whose witnesses exceed 1 GiB is staged in chunks.
+ * swm_pedersen_payment_witness_at: siblings and running digests are read from a resident tree; SWM_ERR_INVALID_ARG for a tree whose
+ * height, leaf length (72) or two swm_pedersen handles are not the circuit's.  The leaves are NOT compared with the tree: a leaf
+ * that is not the tree's gives a satisfied leaf hash and an unsatisfied select row at level 0.
+ * swm_pedersen_payment_witness_dev: device buffers in and out (signatures, siblings, status and roots 4-byte aligned, the witness
+ * 16-byte aligned), no chunking; `tree` may be NULL, then both sibling arrays are read.  What the host forms refuse is reported in
+ * d_status (uint32 per payment): bit 0 = the key (the Schnorr block of that payment is zero, nothing else of it), bit 1 = a sibling
+ * >= r (it is hashed as the 256-bit value given: that path's membership section and its walked root are then unspecified, the rest
+ * of the payment's witness is as usual), bit 2 = an id >= 2^L (the membership sections are those of the id's low L bits).
+ * Messages and leaves are read byte by byte and need no alignment.
+ * swm_pedersen_payment_prove_at: one payment against a resident tree, then the proof of swm_generate_proof_ex(flags) with the
+ * public input (the tree's root, sender, recipient, amount).  SWM_ERR_UNSATISFIED: flags other than 3, or a leaf that is not the
+ * tree's.
+ * swm_pedersen_payment_prove_many_at: one witness pass for `count` payments (chunks as above), then one prover call per payment
+ * whose flag byte is 3, in order, each reading its slice on the device.  proofs_out: count x proof_cap bytes.  lens[i] = 0 for a
+ * payment without a proof: item_flags[i] != 3 (skipped, the prover is not called), or item_flags[i] = 3 and the prover found the
+ * system unsatisfied (a leaf that is not the tree's); the block goes on after either.  Any other prover error ends the call with
+ * that code; lens and item_flags are zeroed for the whole block before the first launch, so every entry is written whatever the
+ * return value, and lens[i] != 0 exactly for the payments that have a proof. */
+typedef struct swm_pedersen_payment_circuit swm_pedersen_payment_circuit;
+int swm_pedersen_payment_circuit_shape(size_t height, int salted, size_t *num_instance, size_t *num_witness, size_t *num_constraints);
+int swm_pedersen_payment_circuit_create(swm_ctx *ctx, const swm_schnorr *schnorr, const swm_pedersen *leaf_params,
+                                        const swm_pedersen *two_to_one_params, size_t height, swm_pedersen_payment_circuit **out);
+void swm_pedersen_payment_circuit_destroy(swm_ctx *ctx, swm_pedersen_payment_circuit *circuit);
+int swm_pedersen_payment_witness(swm_ctx *ctx, const swm_pedersen_payment_circuit *circuit, const uint8_t *messages,
+                                 const uint8_t *signatures, const uint8_t *sender_leaves, const uint8_t *sender_siblings,
+                                 const uint8_t *recipient_leaves, const uint8_t *recipient_siblings, size_t count, uint64_t *witness,
+                                 uint8_t *flags, uint8_t *sender_roots, uint8_t *recipient_roots);
+int swm_pedersen_payment_witness_at(swm_ctx *ctx, const swm_pedersen_payment_circuit *circuit, const swm_merkle_tree *tree,
+                                    const uint8_t *messages, const uint8_t *signatures, const uint8_t *sender_leaves,
+                                    const uint8_t *recipient_leaves, size_t count, uint64_t *witness, uint8_t *flags);
+int swm_pedersen_payment_witness_dev(swm_ctx *ctx, const swm_pedersen_payment_circuit *circuit, const swm_merkle_tree *tree,
+                                     const void *d_messages, const void *d_signatures, const void *d_sender_leaves,
+                                     const void *d_recipient_leaves, const void *d_sender_siblings, const void *d_recipient_siblings,
+                                     size_t count, void *d_witness, void *d_flags, void *d_status, void *d_sender_roots,
+                                     void *d_recipient_roots);
+int swm_pedersen_payment_prove_at(swm_ctx *ctx, const swm_pk *pk, const swm_pedersen_payment_circuit *circuit, const swm_merkle_tree *tree,
+                                  const uint8_t message[10], const uint8_t signature[64], const uint8_t sender_leaf[72],
+                                  const uint8_t recipient_leaf[72], swm_rng *rng, unsigned flags, uint8_t *proof_out, size_t cap,
+                                  size_t *len);
+int swm_pedersen_payment_prove_many_at(swm_ctx *ctx, const swm_pk *pk, const swm_pedersen_payment_circuit *circuit,
+                                       const swm_merkle_tree *tree, const uint8_t *messages, const uint8_t *signatures,
+                                       const uint8_t *sender_leaves, const uint8_t *recipient_leaves, size_t count, swm_rng *rng,
+                                       unsigned flags, uint8_t *proofs_out, size_t proof_cap, size_t *lens, uint8_t *item_flags);
+
 /* ---------------------------------------------------------------------------------------------- Transfer circuit: the state transition
  * The assignment of the transfer circuit (simpleworks_amd/workloads.py, build_transfer) synthesised on the GPU for a BLOCK of
  * transfers applied in order: State::apply_transaction of examples/simple-payments (ledger.rs:176-193) read sequentially as one

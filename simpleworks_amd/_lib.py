@@ -196,6 +196,16 @@ ABI = {
                                                                                    ctypes.POINTER(_sz)]),
     "swm_payment_prove_many_at": (_int, [_vp, _vp, _vp, _vp] + [ctypes.c_void_p] * 4 + [_sz, _vp, ctypes.c_uint, ctypes.c_void_p, _sz,
                                                                                         ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_pedersen_payment_circuit_shape": (_int, [_sz, _int, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "swm_pedersen_payment_circuit_create": (_int, [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(_vp)]),
+    "swm_pedersen_payment_circuit_destroy": (None, [_vp, _vp]),
+    "swm_pedersen_payment_witness": (_int, [_vp, _vp] + [ctypes.c_void_p] * 6 + [_sz] + [ctypes.c_void_p] * 4),
+    "swm_pedersen_payment_witness_at": (_int, [_vp, _vp, _vp] + [ctypes.c_void_p] * 4 + [_sz, ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_pedersen_payment_witness_dev": (_int, [_vp, _vp, _vp] + [_vp] * 6 + [_sz] + [_vp] * 5),
+    "swm_pedersen_payment_prove_at": (_int, [_vp, _vp, _vp, _vp] + [ctypes.c_void_p] * 4 + [_vp, ctypes.c_uint, ctypes.c_void_p, _sz,
+                                                                                         ctypes.POINTER(_sz)]),
+    "swm_pedersen_payment_prove_many_at": (_int, [_vp, _vp, _vp, _vp] + [ctypes.c_void_p] * 4 + [_sz, _vp, ctypes.c_uint, ctypes.c_void_p,
+                                                                                              _sz, ctypes.c_void_p, ctypes.c_void_p]),
     "swm_transfer_circuit_shape": (_int, [_sz, _sz, ctypes.c_uint64, _sz, _int, ctypes.POINTER(_sz), ctypes.POINTER(_sz),
                                            ctypes.POINTER(_sz)]),
     "swm_transfer_circuit_create": (_int, [_vp, _vp, _vp, _sz, ctypes.POINTER(_vp)]),
@@ -1079,6 +1089,53 @@ class Context:
                                                      p(d_recipient_leaves), p(d_sender_siblings), p(d_recipient_siblings), count,
                                                      p(d_witness), p(d_flags), p(d_status), p(d_sender_roots), p(d_recipient_roots)),
                     "swm_payment_witness_dev")
+
+    # ---- Pedersen payment circuit witness (include/swmarlin.h; simpleworks_amd/ledger.py, PedersenPaymentCircuit, is the caller-facing
+    # mirror)
+    def pedersen_payment_circuit_create(self, schnorr_handle, leaf_handle, two_to_one_handle, height):
+        h = _vp()
+        self._check(self.lib.swm_pedersen_payment_circuit_create(self.h, schnorr_handle, leaf_handle, two_to_one_handle, height,
+                                                                 ctypes.byref(h)), "swm_pedersen_payment_circuit_create")
+        return h
+
+    def pedersen_payment_circuit_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_pedersen_payment_circuit_destroy(self.h, handle)
+
+    def pedersen_payment_witness(self, handle, num_witness, levels, messages, signatures, sender_leaves, recipient_leaves, sender_siblings,
+                                 recipient_siblings):
+        """As payment_witness, over a Pedersen account tree."""
+        m, sig, sl, rl, n = self._payment_rows(messages, signatures, sender_leaves, recipient_leaves)
+        ss = np.ascontiguousarray(sender_siblings, dtype=np.uint8)
+        rs = np.ascontiguousarray(recipient_siblings, dtype=np.uint8)
+        assert ss.shape == (n, levels, 32) and rs.shape == (n, levels, 32)
+        witness = np.empty((n, num_witness, 4), dtype=np.uint64)
+        flags = np.empty(n, dtype=np.uint8)
+        roots_s, roots_r = np.empty((n, 32), dtype=np.uint8), np.empty((n, 32), dtype=np.uint8)
+        self._check(self.lib.swm_pedersen_payment_witness(self.h, handle, m.ctypes.data, sig.ctypes.data, sl.ctypes.data, ss.ctypes.data,
+                                                          rl.ctypes.data, rs.ctypes.data, n, witness.ctypes.data, flags.ctypes.data,
+                                                          roots_s.ctypes.data, roots_r.ctypes.data), "swm_pedersen_payment_witness")
+        return witness, flags, roots_s, roots_r
+
+    def pedersen_payment_witness_at(self, handle, tree_handle, num_witness, messages, signatures, sender_leaves, recipient_leaves):
+        """The same against a resident tree: -> (witness uint64 [count, num_witness, 4], flags uint8 [count])."""
+        m, sig, sl, rl, n = self._payment_rows(messages, signatures, sender_leaves, recipient_leaves)
+        witness = np.empty((n, num_witness, 4), dtype=np.uint64)
+        flags = np.empty(n, dtype=np.uint8)
+        self._check(self.lib.swm_pedersen_payment_witness_at(self.h, handle, tree_handle, m.ctypes.data, sig.ctypes.data, sl.ctypes.data,
+                                                             rl.ctypes.data, n, witness.ctypes.data, flags.ctypes.data),
+                    "swm_pedersen_payment_witness_at")
+        return witness, flags
+
+    def pedersen_payment_witness_dev(self, handle, tree_handle, d_messages, d_signatures, d_sender_leaves, d_recipient_leaves,
+                                     d_sender_siblings, d_recipient_siblings, count, d_witness, d_flags, d_status, d_sender_roots=None,
+                                     d_recipient_roots=None):
+        """Device buffers (DeviceBuffer or raw addresses) in and out; tree_handle or the two sibling buffers may be None."""
+        p = self._dev_ptr
+        self._check(self.lib.swm_pedersen_payment_witness_dev(self.h, handle, tree_handle, p(d_messages), p(d_signatures), p(d_sender_leaves),
+                                                              p(d_recipient_leaves), p(d_sender_siblings), p(d_recipient_siblings), count,
+                                                              p(d_witness), p(d_flags), p(d_status), p(d_sender_roots),
+                                                              p(d_recipient_roots)), "swm_pedersen_payment_witness_dev")
 
     # ---- Transfer circuit witness (include/swmarlin.h; simpleworks_amd/ledger.py, TransferCircuit, is the caller-facing mirror)
     def transfer_circuit_create(self, schnorr_handle, poseidon_handle, height):

@@ -26,19 +26,10 @@
 #include "context.h"
 #include "host/merkle_dirty.h"
 #include "merkle_nodes.cuh"
+#include "merkle_tree.h"
 #include "pedersen.cuh"
 #include "pedersen.h"
 #include "swmarlin.h"
-
-struct swm_merkle_tree {
-    const swm_pedersen* leaf = nullptr;
-    const swm_pedersen* inner = nullptr;
-    size_t height = 0, leaf_len = 0;
-    uint8_t* d_nodes = nullptr;  // (2 n - 1) x 32 bytes, owned
-    size_t levels() const { return height - 1; }
-    size_t n() const { return (size_t)1 << (height - 1); }
-    size_t num_nodes() const { return 2 * n() - 1; }
-};
 
 namespace swm {
 
@@ -140,17 +131,6 @@ __global__ void __launch_bounds__(64) merkle_blank_chain_kernel(const EdRow* __r
         __syncthreads();
     }
 }
-
-struct MtMsg64 {  // 64 message bytes in registers; a byte is picked by selects, never by a dynamic register index
-    uint32_t w[16];
-    __device__ __forceinline__ unsigned operator()(size_t i) const {
-        const unsigned k = (unsigned)(i >> 2);
-        uint32_t v = w[0];
-#pragma unroll
-        for (unsigned j = 1; j < 16; j++) v = k == j ? w[j] : v;
-        return (v >> (8 * (i & 3))) & 0xFFu;
-    }
-};
 
 __device__ __forceinline__ bool mt_canonical(const uint32_t* v) {
     Fr s, r;

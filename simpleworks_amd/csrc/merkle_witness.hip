@@ -9,15 +9,7 @@
 // host/merkle_shape.h the offsets.
 //
 // On the GPU: one workgroup of 128 lanes per path, one lane per 4-bit window of a two-to-one hash (the leaf hash uses two).
-// Every witness of a hash is a pointwise function of the affine prefix sums P_k = sum_{i <= k} bit_i G_i:
-//   1. lane w looks its window's point up in the resident table of swm_pedersen (one mixed addition from the identity);
-//   2. an exclusive scan of the 128 window points with the unified addition: shuffles inside a wave, LDS between the two;
-//   3. from its prefix each lane walks its four bits with mixed additions against the rows 1 << j: the 512 running sums;
-//   4. ONE inversion normalises all 512: products of four Z per lane, a prefix and a suffix product scan over the lanes, the
-//      inverse of the total on one lane (frinv.cuh), three multiplications back to each lane's product and six to its four Z;
-//   5. the six witnesses of step k — t = X Y, b t, m1, m2, X3, Y3 — from P_{k-1}, P_k and the generator's (cx, cy), which the
-//      table row 1 << j gives as ((y + x) -+ (y - x)) / 2.
-// The law is complete (ed.cuh): identity windows, zero bits and repeated points take the same path and no Z is zero.
+// A hash with the witnesses of its conditional additions is mw_hash_stage of merkle_stage.cuh, its two-wave form.
 // Only the levels of a path are sequential (a level hashes the digest of the one below).  The byte-operation block is a
 // table-driven walk over plain bytes in LDS — its schedule depends on (levels, operations) only — expanded to 0/1 elements.
 #include <hip/hip_runtime.h>
@@ -30,6 +22,7 @@
 #include "ff.cuh"
 #include "frinv.cuh"
 #include "host/merkle_shape.h"
+#include "merkle_stage.cuh"
 #include "pedersen.h"
 #include "swmarlin.h"
 
@@ -45,136 +38,11 @@ namespace swm {
 static constexpr unsigned MW_LANES = 128;  // = windows of a two-to-one hash
 
 struct MwShared {
-    EdExt wave_total;             // sum of wave 0's window points
-    Fr cross[2];                  // wave 0's Z product | wave 1's; then the inverse of the total
-    Fr last_x[MW_LANES], last_y[MW_LANES];  // each lane's last affine running sum (the next lane's P_{k-1})
+    MwStage<2> hash;              // the hash stage's own (merkle_stage.cuh)
     MerkleByteOp stage[MW_LANES];
     uint32_t bits[16];            // left || right of the level, canonical little-endian words
-    uint32_t cur[8];              // the running digest, canonical
     uint32_t bad;
 };
-
-__device__ __forceinline__ Fr fr_shfl_up(const Fr& a, unsigned d) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)__shfl_up((int)a.v[i], d, 64);
-    return r;
-}
-__device__ __forceinline__ Fr fr_shfl_down(const Fr& a, unsigned d) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)__shfl_down((int)a.v[i], d, 64);
-    return r;
-}
-__device__ __forceinline__ EdExt ed_shfl_up(const EdExt& p, unsigned d) {
-    EdExt r;
-    r.x = fr_shfl_up(p.x, d);
-    r.y = fr_shfl_up(p.y, d);
-    r.t = fr_shfl_up(p.t, d);
-    r.z = fr_shfl_up(p.z, d);
-    return r;
-}
-
-// One Pedersen hash of `nbits` bits (4 per lane; `nib` is zero on the lanes past the input) with the witnesses of its
-// conditional additions: step k = 1 .. nbits - 1 at out[6 (k - 1) .. + 6).  Leaves the digest, canonical, in sh.cur (the caller
-// synchronises before reading it).  Called by all 128 lanes.
-__device__ __noinline__ void mw_hash_stage(const EdRow* __restrict__ table, unsigned nib, unsigned nbits, Fr* __restrict__ out,
-                                           const Fr k2d, const Fr half, MwShared& sh) {
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const EdRow* rows = table + ((size_t)tid << 4);  // only read where nib has a bit: never past the windows the input fills
-    // 1. + 2.
-    EdExt acc = ed_identity();
-    if (nib) ed_madd(acc, rows[nib]);
-#pragma unroll 1
-    for (unsigned d = 1; d < 64; d <<= 1) {
-        const EdExt o = ed_shfl_up(acc, d);
-        if (lane >= d) acc = ed_add(o, acc, k2d);
-    }
-    if (tid == 63) sh.wave_total = acc;
-    __syncthreads();
-    if (wave) acc = ed_add(sh.wave_total, acc, k2d);
-    EdExt q = ed_shfl_up(acc, 1);
-    if (lane == 0) q = wave ? sh.wave_total : ed_identity();
-    // 3.
-    Fr px[4], py[4], pz[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        if ((nib >> j) & 1u) ed_madd(q, rows[1u << j]);
-        px[j] = q.x;
-        py[j] = q.y;
-        pz[j] = q.z;
-    }
-    // 4.
-    const Fr a1 = fp_mul(pz[0], pz[1]), a2 = fp_mul(a1, pz[2]), prod = fp_mul(a2, pz[3]);
-    Fr pre = prod, suf = prod;  // inclusive products over the lanes below / above
-#pragma unroll 1
-    for (unsigned d = 1; d < 64; d <<= 1) {
-        const Fr o = fr_shfl_up(pre, d);
-        const Fr u = fr_shfl_down(suf, d);
-        if (lane >= d) pre = fp_mul(o, pre);
-        if (lane + d < 64) suf = fp_mul(u, suf);
-    }
-    if (tid == 63) sh.cross[0] = pre;
-    if (tid == 64) sh.cross[1] = suf;
-    __syncthreads();
-    if (wave) pre = fp_mul(sh.cross[0], pre);
-    else suf = fp_mul(suf, sh.cross[1]);
-    Fr below = fr_shfl_up(pre, 1), above = fr_shfl_down(suf, 1);  // exclusive
-    if (lane == 0) below = wave ? sh.cross[0] : fp_one<Fr>();
-    if (lane == 63) above = wave ? fp_one<Fr>() : sh.cross[1];
-    __syncthreads();  // cross[] has been read
-    if (tid == MW_LANES - 1) sh.cross[0] = fr_inv_single(pre);  // the total: no Z is zero
-    __syncthreads();
-    const Fr inv_prod = fp_mul(fp_mul(below, above), sh.cross[0]);
-    Fr iz[4];
-    iz[3] = fp_mul(inv_prod, a2);
-    const Fr inv_a2 = fp_mul(inv_prod, pz[3]);
-    iz[2] = fp_mul(inv_a2, a1);
-    const Fr inv_a1 = fp_mul(inv_a2, pz[2]);
-    iz[1] = fp_mul(inv_a1, pz[0]);
-    iz[0] = fp_mul(inv_a1, pz[1]);
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        px[j] = fp_mul(px[j], iz[j]);
-        py[j] = fp_mul(py[j], iz[j]);
-    }
-    sh.last_x[tid] = px[3];
-    sh.last_y[tid] = py[3];
-    __syncthreads();
-    // 5.
-    Fr X = tid ? sh.last_x[tid - 1] : fp_zero<Fr>();
-    Fr Y = tid ? sh.last_y[tid - 1] : fp_one<Fr>();
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const unsigned k = 4 * tid + j;
-        if (k >= 1 && k < nbits) {  // the first bit of a hash is linear in the bit: no witness
-            Fr* o = out + MW_COND_ADD * (size_t)(k - 1);
-            const Fr t = fp_mul(X, Y);
-            o[0] = t;
-            if ((nib >> j) & 1u) {
-                const EdRow g = rows[1u << j];
-                const Fr cx = fp_mul(half, fp_sub(g.ypx, g.ymx)), cy = fp_mul(half, fp_add(g.ypx, g.ymx));
-                const Fr cym1 = fp_sub(cy, fp_one<Fr>());
-                o[1] = t;
-                o[2] = fp_add(fp_mul(cym1, X), fp_mul(cx, Y));
-                o[3] = fp_add(fp_mul(cym1, Y), fp_mul(cx, X));
-            } else {
-                o[1] = fp_zero<Fr>();
-                o[2] = fp_zero<Fr>();
-                o[3] = fp_zero<Fr>();
-            }
-            o[4] = px[j];
-            o[5] = py[j];
-        }
-        X = px[j];
-        Y = py[j];
-    }
-    if (tid == MW_LANES - 1) {  // lanes past the input carry the total along: the last lane always holds the hash
-        const Fr x = fp_to_std(px[3]);
-#pragma unroll
-        for (int i = 0; i < 8; i++) sh.cur[i] = x.v[i];
-    }
-}
 
 // Block p = path p.  pool (dynamic LDS): 64 levels + ops bytes.
 __global__ void __launch_bounds__(MW_LANES) merkle_witness_kernel(const EdRow* __restrict__ leaf_table, const EdRow* __restrict__ inner_table,
@@ -217,13 +85,13 @@ __global__ void __launch_bounds__(MW_LANES) merkle_witness_kernel(const EdRow* _
 
     // leaf hash: 8 bits, two windows
     const unsigned leaf = leaves[path];
-    mw_hash_stage(leaf_table, tid < 2 ? (leaf >> (4 * tid)) & 15u : 0u, (unsigned)MW_LEAF_BITS, w, k2d, half, sh);
+    mw_hash_stage(leaf_table, tid < 2 ? (leaf >> (4 * tid)) & 15u : 0u, (unsigned)MW_LEAF_BITS, w, k2d, half, sh.hash);
     __syncthreads();
 
     for (unsigned lvl = 0; lvl < levels; lvl++) {
         const unsigned dir = (unsigned)(index >> lvl) & 1u;
         if (tid < 8) {  // left = dir ? sibling : cur, right = the other one
-            const uint32_t s = sib[8 * lvl + tid], c = sh.cur[tid];
+            const uint32_t s = sib[8 * lvl + tid], c = sh.hash.cur[tid];
             sh.bits[tid] = dir ? s : c;
             sh.bits[8 + tid] = dir ? c : s;
         }
@@ -243,10 +111,10 @@ __global__ void __launch_bounds__(MW_LANES) merkle_witness_kernel(const EdRow* _
         for (unsigned i = tid; i < 2 * MW_DIGEST_BITS; i += MW_LANES) lw[MW_LEVEL_BITS_AT + i] = (sh.bits[i >> 5] >> (i & 31)) & 1u ? one : zero;
         if (tid < 16) reinterpret_cast<uint32_t*>(pool)[16 * lvl + tid] = sh.bits[tid];
         const unsigned nib = (sh.bits[tid >> 3] >> (4 * (tid & 7))) & 15u;
-        mw_hash_stage(inner_table, nib, 2 * (unsigned)MW_DIGEST_BITS, lw + MW_LEVEL_ADDS_AT, k2d, half, sh);
+        mw_hash_stage(inner_table, nib, 2 * (unsigned)MW_DIGEST_BITS, lw + MW_LEVEL_ADDS_AT, k2d, half, sh.hash);
         __syncthreads();
     }
-    if (roots && tid < 8) reinterpret_cast<uint32_t*>(roots + 32 * path)[tid] = sh.cur[tid];
+    if (roots && tid < 8) reinterpret_cast<uint32_t*>(roots + 32 * path)[tid] = sh.hash.cur[tid];
 
     // byte operations: results depend on earlier results, so one lane walks the schedule; the table comes in by 128 entries
     const unsigned base_len = 64 * levels;

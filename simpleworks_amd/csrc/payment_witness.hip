@@ -130,6 +130,27 @@ __global__ void __launch_bounds__(PY_LANES) payment_bits_kernel(PyArgs A, const 
     q[1] = make_uint4(v.v[4], v.v[5], v.v[6], v.v[7]);
 }
 
+int payment_prep_run(swm_ctx* ctx, const uint8_t* d_msgs, const uint8_t* d_sender_leaves, size_t n, unsigned levels, uint32_t* d_keys,
+                     uint64_t* d_idx_s, uint64_t* d_idx_r) {
+    SWM_LAUNCH(ctx, "payment_prep", payment_prep_kernel, dim3((unsigned)((16 * n + PY_LANES - 1) / PY_LANES)), dim3(PY_LANES), 0, d_msgs,
+               d_sender_leaves, n, levels, d_keys, d_idx_s, d_idx_r);
+    return SWM_OK;
+}
+
+int payment_bits_run(swm_ctx* ctx, size_t n, size_t stride, size_t balance_at, size_t recipient_bits_at, unsigned levels, const uint8_t* d_msgs,
+                     const uint8_t* d_sender_leaves, const uint8_t* d_recipient_leaves, const uint32_t* d_sender_sib,
+                     const uint32_t* d_recipient_sib, const uint8_t* d_sig_ok, Fr* d_w, uint8_t* d_flags, uint32_t* d_status) {
+    PyArgs A;
+    A.count = n;
+    A.stride = stride;
+    A.balance_at = balance_at;
+    A.recipient_bits_at = recipient_bits_at;
+    A.levels = levels;
+    SWM_LAUNCH(ctx, "payment_bits", payment_bits_kernel, dim3((unsigned)((PY_BIT_WITNESSES * n + PY_LANES - 1) / PY_LANES)), dim3(PY_LANES), 0, A,
+               d_msgs, d_sender_leaves, d_recipient_leaves, d_sender_sib, d_recipient_sib, d_sig_ok, d_w, d_flags, d_status);
+    return SWM_OK;
+}
+
 // n payments on device buffers.  d_sigs and the siblings 4-byte aligned, d_witness 16-byte aligned.  tree: may be NULL, then the
 // two sibling arrays are read and d_roots_s / d_roots_r (may be NULL) take the walked roots.  d_flags, d_status: per item.
 static int py_run(swm_ctx* ctx, const swm_payment_circuit* c, const swm_poseidon_tree* tree, const uint8_t* d_msgs, const uint8_t* d_sigs,
@@ -144,26 +165,19 @@ static int py_run(swm_ctx* ctx, const swm_payment_circuit* c, const swm_poseidon
     uint64_t* d_idx_s = reinterpret_cast<uint64_t*>(aux + 64 * n);
     uint64_t* d_idx_r = d_idx_s + n;
     uint8_t* d_sig_ok = aux + 80 * n;
-    SWM_LAUNCH(ctx, "payment_prep", payment_prep_kernel, dim3((unsigned)((16 * n + PY_LANES - 1) / PY_LANES)), dim3(PY_LANES), 0, d_msgs,
-               d_sender_leaves, n, (unsigned)s.levels, d_keys, d_idx_s, d_idx_r);
+    SWM_TRY(payment_prep_run(ctx, d_msgs, d_sender_leaves, n, (unsigned)s.levels, d_keys, d_idx_s, d_idx_r));
     SWM_TRY(schnorr_witness_run(ctx, &c->schnorr, aux, d_msgs, d_sigs, n, d_w, s.num_witness, d_sig_ok, d_status));
     SWM_TRY(ptw_run(ctx, &c->tree, tree, d_sender_leaves, d_idx_s, d_sender_sib, n, d_w + s.sender_at, s.num_witness, d_roots_s));
     SWM_TRY(ptw_run(ctx, &c->tree, tree, d_recipient_leaves, d_idx_r, d_recipient_sib, n, d_w + s.recipient_at, s.num_witness, d_roots_r));
-    PyArgs A;
-    A.count = n;
-    A.stride = s.num_witness;
-    A.balance_at = s.balance_at;
-    A.recipient_bits_at = s.recipient_bits_at;
-    A.levels = (unsigned)s.levels;
-    SWM_LAUNCH(ctx, "payment_bits", payment_bits_kernel, dim3((unsigned)((PY_BIT_WITNESSES * n + PY_LANES - 1) / PY_LANES)), dim3(PY_LANES), 0, A,
-               d_msgs, d_sender_leaves, d_recipient_leaves, tree ? nullptr : reinterpret_cast<const uint32_t*>(d_sender_sib),
-               tree ? nullptr : reinterpret_cast<const uint32_t*>(d_recipient_sib), (const uint8_t*)d_sig_ok, d_w, d_flags, d_status);
-    return SWM_OK;
+    return payment_bits_run(ctx, n, s.num_witness, s.balance_at, s.recipient_bits_at, (unsigned)s.levels, d_msgs, d_sender_leaves,
+                            d_recipient_leaves, tree ? nullptr : reinterpret_cast<const uint32_t*>(d_sender_sib),
+                            tree ? nullptr : reinterpret_cast<const uint32_t*>(d_recipient_sib), d_sig_ok, d_w, d_flags, d_status);
 }
 
 // the host forms' checks: what the device form reports per item
-static int py_check(swm_ctx* ctx, const char* what, const PaymentShape& s, const uint8_t* msgs, const uint8_t* sender_leaves,
+int py_check(swm_ctx* ctx, const char* what, size_t height, const uint8_t* msgs, const uint8_t* sender_leaves,
                     const uint8_t* sender_sib, const uint8_t* recipient_sib, size_t count) {
+    const size_t levels = height - 1;
     uint8_t key[64];
     Fr v;
     for (size_t p = 0; p < count; p++) {
@@ -171,13 +185,13 @@ static int py_check(swm_ctx* ctx, const char* what, const PaymentShape& s, const
         if (schnorr_check_keys(ctx, key, 1) != SWM_OK)
             return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: item %zu: the sender's key is not a point of ed-on-BLS12-377", what, p);
         for (int k = 0; k < 2; k++)
-            if ((size_t)msgs[PY_MSG_LEN * p + k] >> s.levels)
+            if ((size_t)msgs[PY_MSG_LEN * p + k] >> levels)
                 return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: item %zu: account id %u in a tree of height %zu", what, p,
-                               (unsigned)msgs[PY_MSG_LEN * p + k], s.height);
+                               (unsigned)msgs[PY_MSG_LEN * p + k], height);
         for (int k = 0; k < 2; k++) {
             const uint8_t* sib = k ? recipient_sib : sender_sib;
-            for (size_t l = 0; sib && l < s.levels; l++)
-                if (!ps_load_std(sib + 32 * (p * s.levels + l), &v))
+            for (size_t l = 0; sib && l < levels; l++)
+                if (!ps_load_std(sib + 32 * (p * levels + l), &v))
                     return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: item %zu: sibling %zu of the %s's path is not a canonical field element", what,
                                    p, l, k ? "recipient" : "sender");
         }
@@ -192,20 +206,16 @@ static int py_check_tree(swm_ctx* ctx, const char* what, const swm_payment_circu
     return SWM_OK;
 }
 
-static int py_drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
+int py_drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
     if (rc != SWM_OK) drain_streams(ctx);
     return rc;
 }
 
-struct PyStaged {
-    const uint8_t *msgs, *sigs, *sender_leaves, *recipient_leaves, *sender_sib, *recipient_sib;
-};
-
 // signatures | sender leaves | recipient leaves | the two sibling arrays | messages of n payments into "stage.a": all but the
 // messages stay word-aligned
-static int py_stage(swm_ctx* ctx, const PaymentShape& s, const uint8_t* msgs, const uint8_t* sigs, const uint8_t* sender_leaves,
+int py_stage(swm_ctx* ctx, size_t levels, const uint8_t* msgs, const uint8_t* sigs, const uint8_t* sender_leaves,
                     const uint8_t* recipient_leaves, const uint8_t* sender_sib, const uint8_t* recipient_sib, size_t n, PyStaged* out) {
-    const size_t sib = sender_sib ? n * s.levels * 32 : 0;
+    const size_t sib = sender_sib ? n * levels * 32 : 0;
     uint8_t* d = nullptr;
     SWM_TRY(scratch(ctx, "stage.a", n * (64 + 2 * PY_LEAF_LEN + PY_MSG_LEN) + 2 * sib + 16, (void**)&d));
     out->sigs = d;
@@ -227,23 +237,9 @@ static int py_stage(swm_ctx* ctx, const PaymentShape& s, const uint8_t* msgs, co
     return SWM_OK;
 }
 
-// The host forms hold at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
-static constexpr size_t PY_STAGE_BYTES = (size_t)1 << 30;
-
-struct PyOut {  // "payment.w": witnesses | sender roots | recipient roots | status | flags
-    Fr* w;
-    uint32_t *roots_s, *roots_r, *status;
-    uint8_t* flags;
-};
-
-// n payments staged and run; the results stay in "payment.w"
-static int py_chunk(swm_ctx* ctx, const swm_payment_circuit* c, const swm_poseidon_tree* tree, const uint8_t* msgs, const uint8_t* sigs,
-                    const uint8_t* sender_leaves, const uint8_t* recipient_leaves, const uint8_t* sender_sib, const uint8_t* recipient_sib, size_t n,
-                    PyOut* out) {
-    const PaymentShape& s = c->shape;
-    const size_t item = s.num_witness * sizeof(Fr);
-    PyStaged in;
-    SWM_TRY(py_stage(ctx, s, msgs, sigs, sender_leaves, recipient_leaves, sender_sib, recipient_sib, n, &in));
+// "payment.w" laid out for n payments of num_witness elements
+int py_out(swm_ctx* ctx, size_t num_witness, size_t n, PyOut* out) {
+    const size_t item = num_witness * sizeof(Fr);
     uint8_t* d_out = nullptr;
     SWM_TRY(scratch(ctx, "payment.w", n * (item + 64 + 4 + 1) + 16, (void**)&d_out));
     out->w = reinterpret_cast<Fr*>(d_out);
@@ -251,6 +247,16 @@ static int py_chunk(swm_ctx* ctx, const swm_payment_circuit* c, const swm_poseid
     out->roots_r = out->roots_s + 8 * n;
     out->status = out->roots_r + 8 * n;
     out->flags = reinterpret_cast<uint8_t*>(out->status + n);
+    return SWM_OK;
+}
+
+// n payments staged and run; the results stay in "payment.w"
+static int py_chunk(swm_ctx* ctx, const swm_payment_circuit* c, const swm_poseidon_tree* tree, const uint8_t* msgs, const uint8_t* sigs,
+                    const uint8_t* sender_leaves, const uint8_t* recipient_leaves, const uint8_t* sender_sib, const uint8_t* recipient_sib, size_t n,
+                    PyOut* out) {
+    PyStaged in;
+    SWM_TRY(py_stage(ctx, c->shape.levels, msgs, sigs, sender_leaves, recipient_leaves, sender_sib, recipient_sib, n, &in));
+    SWM_TRY(py_out(ctx, c->shape.num_witness, n, out));
     return py_run(ctx, c, tree, in.msgs, in.sigs, in.sender_leaves, in.recipient_leaves, in.sender_sib, in.recipient_sib, n, out->w, out->flags,
                   out->status, out->roots_s, out->roots_r);
 }
@@ -277,16 +283,15 @@ static int py_host(swm_ctx* ctx, const swm_payment_circuit* c, const swm_poseido
 }
 
 // the prover over item `i` of a chunk's device witnesses; public input one, root, sender, recipient, amount
-static int py_prove_item(swm_ctx* ctx, const swm_pk* pk, const swm_payment_circuit* c, const Fr& root_mont, const uint8_t* msg, const Fr* d_w,
-                         swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
-    const PaymentShape& s = c->shape;
+int py_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size_t num_constraints, const Fr& root_mont, const uint8_t* msg,
+                  const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
     uint64_t amount = 0;
     for (int k = 0; k < 8; k++) amount |= (uint64_t)msg[2 + k] << (8 * k);
     const Fr inst[5] = {fp_one<Fr>(), root_mont, fp_from_u64<Fr>(msg[0]), fp_from_u64<Fr>(msg[1]), fp_from_u64<Fr>(amount)};
     swm_r1cs cs = {};
-    cs.num_instance = s.num_instance;
-    cs.num_witness = s.num_witness;
-    cs.num_constraints = s.num_constraints;
+    cs.num_instance = 5;
+    cs.num_witness = num_witness;
+    cs.num_constraints = num_constraints;
     cs.instance = reinterpret_cast<const uint64_t*>(inst);
     cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
     struct DevWitnessScope {
@@ -297,9 +302,10 @@ static int py_prove_item(swm_ctx* ctx, const swm_pk* pk, const swm_payment_circu
     return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
 }
 
-static int py_tree_root(swm_ctx* ctx, const swm_poseidon_tree* tree, Fr* root_mont) {
+// the root of a resident tree (its last node, d_root) in Montgomery form; synchronises the stream
+int py_root_mont(swm_ctx* ctx, const uint8_t* d_root, Fr* root_mont) {
     uint8_t root[32];
-    SWM_HIP(ctx, hipMemcpyAsync(root, tree->d_nodes + 32 * (tree->num_nodes() - 1), 32, hipMemcpyDeviceToHost, ctx->stream));
+    SWM_HIP(ctx, hipMemcpyAsync(root, d_root, 32, hipMemcpyDeviceToHost, ctx->stream));
     SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     Fr r;
     (void)ps_load_std(root, &r);  // a node of the tree is canonical
@@ -343,7 +349,7 @@ int swm_payment_witness(swm_ctx* ctx, const swm_payment_circuit* c, const uint8_
     if (!ctx || !c || (count && (!messages || !signatures || !sender_leaves || !recipient_leaves || !sender_siblings || !recipient_siblings || !witness)))
         return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_witness: bad arguments");
     if (!count) return SWM_OK;
-    SWM_TRY(py_check(ctx, "payment_witness", c->shape, messages, sender_leaves, sender_siblings, recipient_siblings, count));
+    SWM_TRY(py_check(ctx, "payment_witness", c->shape.height, messages, sender_leaves, sender_siblings, recipient_siblings, count));
     SWM_ON_DEVICE(ctx);
     return py_drained(ctx, py_host(ctx, c, nullptr, messages, signatures, sender_leaves, recipient_leaves, sender_siblings, recipient_siblings,
                                    count, witness, flags, sender_roots, recipient_roots));
@@ -356,7 +362,7 @@ int swm_payment_witness_at(swm_ctx* ctx, const swm_payment_circuit* c, const swm
         return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_witness_at: bad arguments");
     SWM_TRY(py_check_tree(ctx, "payment_witness_at", c, tree));
     if (!count) return SWM_OK;
-    SWM_TRY(py_check(ctx, "payment_witness_at", c->shape, messages, sender_leaves, nullptr, nullptr, count));
+    SWM_TRY(py_check(ctx, "payment_witness_at", c->shape.height, messages, sender_leaves, nullptr, nullptr, count));
     SWM_ON_DEVICE(ctx);
     return py_drained(ctx, py_host(ctx, c, tree, messages, signatures, sender_leaves, recipient_leaves, nullptr, nullptr, count, witness, flags,
                                    nullptr, nullptr));
@@ -387,15 +393,16 @@ int swm_payment_prove_at(swm_ctx* ctx, const swm_pk* pk, const swm_payment_circu
     if (!ctx || !pk || !c || !tree || !message || !signature || !sender_leaf || !recipient_leaf || !rng || !proof_out || !len)
         return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_prove_at: bad arguments");
     SWM_TRY(py_check_tree(ctx, "payment_prove_at", c, tree));
-    SWM_TRY(py_check(ctx, "payment_prove_at", c->shape, message, sender_leaf, nullptr, nullptr, 1));
+    SWM_TRY(py_check(ctx, "payment_prove_at", c->shape.height, message, sender_leaf, nullptr, nullptr, 1));
     PyOut o;
     Fr root;
     {
         SWM_ON_DEVICE(ctx);
         SWM_TRY(py_drained(ctx, py_chunk(ctx, c, tree, message, signature, sender_leaf, recipient_leaf, nullptr, nullptr, 1, &o)));
-        SWM_TRY(py_tree_root(ctx, tree, &root));  // its synchronisation: the inputs were staged from the caller's buffers
+        // its synchronisation: the inputs were staged from the caller's buffers
+        SWM_TRY(py_root_mont(ctx, tree->d_nodes + 32 * (tree->num_nodes() - 1), &root));
     }
-    return py_prove_item(ctx, pk, c, root, message, o.w, rng, flags, proof_out, cap, len);
+    return py_prove_item(ctx, pk, c->shape.num_witness, c->shape.num_constraints, root, message, o.w, rng, flags, proof_out, cap, len);
 }
 
 int swm_payment_prove_many_at(swm_ctx* ctx, const swm_pk* pk, const swm_payment_circuit* c, const swm_poseidon_tree* tree,
@@ -407,7 +414,7 @@ int swm_payment_prove_many_at(swm_ctx* ctx, const swm_pk* pk, const swm_payment_
         return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_prove_many_at: bad arguments");
     SWM_TRY(py_check_tree(ctx, "payment_prove_many_at", c, tree));
     if (!count) return SWM_OK;
-    SWM_TRY(py_check(ctx, "payment_prove_many_at", c->shape, messages, sender_leaves, nullptr, nullptr, count));
+    SWM_TRY(py_check(ctx, "payment_prove_many_at", c->shape.height, messages, sender_leaves, nullptr, nullptr, count));
     const PaymentShape& s = c->shape;
     const size_t item = s.num_witness * sizeof(Fr);
     const size_t per = PY_STAGE_BYTES / item ? PY_STAGE_BYTES / item : 1;
@@ -424,13 +431,13 @@ int swm_payment_prove_many_at(swm_ctx* ctx, const swm_pk* pk, const swm_payment_
             SWM_TRY(py_drained(ctx, py_chunk(ctx, c, tree, messages + PY_MSG_LEN * base, signatures + 64 * base, sender_leaves + PY_LEAF_LEN * base,
                                              recipient_leaves + PY_LEAF_LEN * base, nullptr, nullptr, n, &o)));
             SWM_HIP(ctx, hipMemcpyAsync(item_flags + base, o.flags, n, hipMemcpyDeviceToHost, ctx->stream));
-            SWM_TRY(py_tree_root(ctx, tree, &root));
+            SWM_TRY(py_root_mont(ctx, tree->d_nodes + 32 * (tree->num_nodes() - 1), &root));
         }
         for (size_t i = 0; i < n; i++) {
             if (item_flags[base + i] != 3) continue;  // reported, not proved: its system is unsatisfied
             size_t len = 0;
-            const int rc = py_prove_item(ctx, pk, c, root, messages + PY_MSG_LEN * (base + i), o.w + i * s.num_witness, rng, flags,
-                                         proofs_out + (base + i) * proof_cap, proof_cap, &len);
+            const int rc = py_prove_item(ctx, pk, s.num_witness, s.num_constraints, root, messages + PY_MSG_LEN * (base + i), o.w + i * s.num_witness,
+                                         rng, flags, proofs_out + (base + i) * proof_cap, proof_cap, &len);
             if (rc == SWM_ERR_UNSATISFIED) continue;  // flags 3 and a leaf that is not the tree's: no proof, lens stays 0, the block goes on
             if (rc != SWM_OK) return rc;
             lens[base + i] = len;

@@ -37,6 +37,17 @@ __device__ __forceinline__ EdExt ped_join(EdExt acc, unsigned lanes, const Fr& k
     return acc;
 }
 
+struct MtMsg64 {  // 64 message bytes in registers; a byte is picked by selects, never by a dynamic register index
+    uint32_t w[16];
+    __device__ __forceinline__ unsigned operator()(size_t i) const {
+        const unsigned k = (unsigned)(i >> 2);
+        uint32_t v = w[0];
+#pragma unroll
+        for (unsigned j = 1; j < 16; j++) v = k == j ? w[j] : v;
+        return (v >> (8 * (i & 3))) & 0xFFu;
+    }
+};
+
 // TECompressor: the affine x coordinate, canonical.  Z != 0: the law is complete.
 __device__ __forceinline__ Fr ped_digest(const EdExt& acc) { return fp_to_std(fp_mul(acc.x, fr_inv_single(acc.z))); }
 

@@ -1,7 +1,8 @@
 // witness_runs.h — the two witness launchers that another circuit's unit may reuse for a block of its own witness vector
 // (payment_witness.hip does): schnorr_witness.hip and poseidon_tree_witness.hip define them next to their kernels.  Both write
 // item i's block at d_witness + i * stride; the stand-alone circuits pass their own num_witness as the stride, a composed circuit
-// its larger one with d_witness moved to the block's first element.
+// its larger one with d_witness moved to the block's first element.  And the parts of a payment's witness pass that do not depend
+// on the account tree's hash (payment_witness.hip defines them; pedersen_payment_witness.hip calls them with its own offsets).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -13,6 +14,7 @@
 #include "poseidon.h"
 #include "poseidon_tree.h"
 #include "schnorr.h"
+#include "swmarlin.h"
 
 struct swm_schnorr_circuit {
     const swm_schnorr* params = nullptr;
@@ -42,5 +44,44 @@ int ptw_run(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const swm_poseidon
 // another leaf: deltas | leaf chain | levels from d_witness on, no bits and no siblings of its own.
 int ptw_record(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const uint8_t* d_leaves, const uint64_t* d_indices, const uint32_t* d_dig,
                const uint32_t* d_sib, size_t count, Fr* d_witness, size_t stride, bool own_path);
+
+// ---- a payment (payment_witness.hip): messages of 10 bytes, leaves of 72, whatever the tree hashes with
+// The 72-byte sender leaves unzipped into the 64-byte key array the Schnorr kernel reads, and the two id bytes of each message as
+// uint64 leaf indices masked to `levels` bits.
+int payment_prep_run(swm_ctx* ctx, const uint8_t* d_msgs, const uint8_t* d_sender_leaves, size_t n, unsigned levels, uint32_t* d_keys,
+                     uint64_t* d_idx_s, uint64_t* d_idx_r);
+// The 704 bit witnesses (64 balance bits and 64 diff bits from balance_at, 576 recipient leaf bits from recipient_bits_at), the flag
+// byte (bit 0: d_sig_ok, bit 1: amount <= balance) and the status word completed: bit 1 a sibling >= r (the two sibling arrays may
+// be NULL: a resident tree's), bit 2 an id at or above 2^levels.
+int payment_bits_run(swm_ctx* ctx, size_t n, size_t stride, size_t balance_at, size_t recipient_bits_at, unsigned levels, const uint8_t* d_msgs,
+                     const uint8_t* d_sender_leaves, const uint8_t* d_recipient_leaves, const uint32_t* d_sender_sib,
+                     const uint32_t* d_recipient_sib, const uint8_t* d_sig_ok, Fr* d_w, uint8_t* d_flags, uint32_t* d_status);
+// the host forms' checks: what the device form reports per item (the sibling arrays may be NULL)
+int py_check(swm_ctx* ctx, const char* what, size_t height, const uint8_t* msgs, const uint8_t* sender_leaves, const uint8_t* sender_sib,
+             const uint8_t* recipient_sib, size_t count);
+int py_drained(swm_ctx* ctx, int rc);  // an error leaves nothing of this call queued behind it
+
+struct PyStaged {
+    const uint8_t *msgs, *sigs, *sender_leaves, *recipient_leaves, *sender_sib, *recipient_sib;
+};
+// signatures | sender leaves | recipient leaves | the two sibling arrays (may be NULL) | messages of n payments into "stage.a"
+int py_stage(swm_ctx* ctx, size_t levels, const uint8_t* msgs, const uint8_t* sigs, const uint8_t* sender_leaves,
+             const uint8_t* recipient_leaves, const uint8_t* sender_sib, const uint8_t* recipient_sib, size_t n, PyStaged* out);
+
+// The host forms hold at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
+static constexpr size_t PY_STAGE_BYTES = (size_t)1 << 30;
+
+struct PyOut {  // "payment.w": witnesses | sender roots | recipient roots | status | flags
+    Fr* w;
+    uint32_t *roots_s, *roots_r, *status;
+    uint8_t* flags;
+};
+int py_out(swm_ctx* ctx, size_t num_witness, size_t n, PyOut* out);
+
+// the prover over one item's device witnesses; public input one, root, sender, recipient, amount
+int py_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size_t num_constraints, const Fr& root_mont, const uint8_t* msg,
+                  const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len);
+// a resident tree's root (d_root: its last node) in Montgomery form; synchronises the stream
+int py_root_mont(swm_ctx* ctx, const uint8_t* d_root, Fr* root_mont);
 
 }  // namespace swm

@@ -124,6 +124,45 @@ class PaymentCircuit:
             pass
 
 
+class PedersenPaymentCircuit:
+    """The payment circuit over resident Schnorr parameters and the two Pedersen CRHs of the reference's account tree
+    (swm_pedersen_payment_circuit): synthesises the witness vector of workloads.build_pedersen_payment for batches of payments
+    without running the builder.  A payment is (message, signature, sender leaf, recipient leaf); the leaf indices are the message's
+    first two bytes.  Refers to the three parameter sets: keep them alive."""
+
+    def __init__(self, sig_params, leaf_crh, two_to_one_crh, height):
+        self.ctx, self.sig_params, self.height = sig_params.ctx, sig_params, height
+        self.leaf_crh, self.two_to_one_crh = leaf_crh, two_to_one_crh
+        self.h = self.ctx.pedersen_payment_circuit_create(sig_params.h, leaf_crh.h, two_to_one_crh.h, height)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        from .marlin import pedersen_payment_circuit_shape
+        return pedersen_payment_circuit_shape(self.height, self.sig_params.salt is not None)
+
+    def witness_many(self, payments, sender_siblings, recipient_siblings):
+        """No tree: the siblings per path bottom up, as ints.  Returns (witness uint64 [count, num_witness, 4] Montgomery limbs,
+        flags uint8 [count], sender roots, recipient roots as ints)."""
+        w, flags, rs, rr = self.ctx.pedersen_payment_witness(self.h, self.shape()[1], self.height - 1, *PaymentCircuit._columns(payments),
+                                                             H._fr_rows(sender_siblings), H._fr_rows(recipient_siblings))
+        return (w, flags, [int.from_bytes(r.tobytes(), "little") for r in rs], [int.from_bytes(r.tobytes(), "little") for r in rr])
+
+    def witness_at(self, tree, payments):
+        """The same against a hash.DeviceMerkleTree that holds both leaves: (witness, flags)."""
+        return self.ctx.pedersen_payment_witness_at(self.h, tree.h, self.shape()[1], *PaymentCircuit._columns(payments))
+
+    def free(self):
+        if self.h:
+            self.ctx.pedersen_payment_circuit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class TransferCircuit:
     """The transfer circuit over resident Schnorr and Poseidon parameters (swm_transfer_circuit): synthesises the witness vector of
     workloads.build_transfer for a block of transfers applied in order, and advances the tree and the account table through the
@@ -194,6 +233,7 @@ class State:
         self._proof_keys = None      # (SchnorrCircuit, proving key, verifying key), derived once
         self._payment_keys = None    # (PaymentCircuit, proving key, verifying key), the same for a Poseidon account tree
         self._transfer_keys = None   # (TransferCircuit, proving key, verifying key), the same
+        self._pedersen_payment_keys = None   # (PedersenPaymentCircuit, proving key, verifying key), for a Pedersen account tree
 
     def root(self):
         return self.account_merkle_tree.root()
@@ -285,6 +325,30 @@ class State:
             self._payment_keys = (PaymentCircuit(sig, sponge, height), pk, vk)
         return self._payment_keys
 
+    def pedersen_payment_keys(self, rng):
+        """The payment circuit over this ledger's Pedersen account tree (its parameters and tree height) with its Marlin keys,
+        derived once as payment_keys derives the Poseidon form's."""
+        if self.account_tree != "pedersen":
+            raise ValueError("pedersen_payment_keys: the Pedersen payment circuit is over a Pedersen account tree")
+        if self._pedersen_payment_keys is None:
+            from . import marlin as M
+            from . import workloads as W
+            sig, leaf_crh, inner_crh = self.parameters.sig_params, self.parameters.leaf_crh, self.parameters.two_to_one_crh
+            height = self.account_merkle_tree.height()
+            params = W.MerkleParams(generators=(leaf_crh.generators, inner_crh.generators))
+            leaf = AccountInformation(sig.generator, 0).to_bytes_le()
+            cs, _ = W.pedersen_payment_circuit(params, height, bytes(MESSAGE_LEN), bytes(64), leaf, [0] * (height - 1), leaf,
+                                               [0] * (height - 1), sig.generator, sig.salt, root=0)
+            packed = cs.pack()
+            nnz = max(int(m[0][-1]) for m in packed.mats)
+            srs = M.MarlinInst.universal_setup(cs.num_constraints, len(cs.instance) + len(cs.witness), nnz, rng, sig.ctx)
+            try:
+                pk, vk = M.MarlinInst.index_from_constraint_system(srs, packed)
+            finally:
+                srs.free()
+            self._pedersen_payment_keys = (PedersenPaymentCircuit(sig, leaf_crh, inner_crh, height), pk, vk)
+        return self._pedersen_payment_keys
+
     def transfer_keys(self, rng):
         """The transfer circuit (this ledger's parameters and tree height) with its Marlin keys, derived once as payment_keys
         derives the payment circuit's."""
@@ -341,11 +405,11 @@ class State:
         return [(bool(f & 16), proof, pub) for f, proof, pub in zip(flags, proofs, public)]
 
     def free(self):
-        for keys in (self._proof_keys, self._payment_keys, self._transfer_keys):
+        for keys in (self._proof_keys, self._payment_keys, self._transfer_keys, self._pedersen_payment_keys):
             if keys is not None:
                 keys[0].free()
                 keys[1].free()
-        self._proof_keys = self._payment_keys = self._transfer_keys = None
+        self._proof_keys = self._payment_keys = self._transfer_keys = self._pedersen_payment_keys = None
         self.account_merkle_tree.free()
 
 
@@ -405,6 +469,22 @@ class Transaction:
         sender_leaf, recipient_leaf = _payment_leaves(state, self)
         public = W.payment_public_inputs(tree.root(), self.message())
         proof = M.generate_payment_proof(pk, circuit, tree, self.message(), self.signature.to_bytes(), sender_leaf, recipient_leaf, rng)
+        return proof, public
+
+    def prove_pedersen_payment(self, parameters, state, rng):
+        """-> (proof bytes, public inputs) of the payment circuit against a state with a Pedersen account tree (the default one), as
+        it stands now.  KeyError when sender or recipient has no account; MarlinError (SWM_ERR_UNSATISFIED) when the payment is not
+        valid.  verify_payment serves: the public input order is the Poseidon form's."""
+        from . import marlin as M
+        from . import workloads as W
+        if self.sender not in state.id_to_account_info or self.recipient not in state.id_to_account_info:
+            raise KeyError("sender or recipient not found")
+        circuit, pk, _ = state.pedersen_payment_keys(rng)
+        tree = state.account_merkle_tree
+        sender_leaf, recipient_leaf = _payment_leaves(state, self)
+        public = W.pedersen_payment_public_inputs(tree.root(), self.message())
+        proof = M.generate_pedersen_payment_proof(pk, circuit, tree, self.message(), self.signature.to_bytes(), sender_leaf, recipient_leaf,
+                                                  rng)
         return proof, public
 
     def validate(self, parameters, state, rng, prove=True):
@@ -483,4 +563,27 @@ def validate_many(parameters, state, txs, rng=None, prove=False):
         elif sig_ok and prove:
             sig_ok = _prove_signature(state, infos[k].public_key, tx.message(), tx.signature, rng)
         out[i] = bool(in_tree[k]) and sig_ok and tx.amount <= infos[k].balance and tx.recipient in state.id_to_account_info
+    return out
+
+
+def prove_pedersen_payments(parameters, state, txs, rng):
+    """The block form of Transaction.prove_pedersen_payment against ONE state with a Pedersen account tree (none of the transactions
+    applied): one witness pass for the block, then one prover call per payment that is valid.  -> a list with (proof bytes, public
+    inputs) per transaction, None where it has no proof: sender or recipient without an account, a signature that does not verify,
+    an amount above the balance."""
+    from . import marlin as M
+    from . import workloads as W
+    txs = list(txs)
+    circuit, pk, _ = state.pedersen_payment_keys(rng)
+    known = [i for i, tx in enumerate(txs) if tx.sender in state.id_to_account_info and tx.recipient in state.id_to_account_info]
+    out = [None] * len(txs)
+    if not known:
+        return out
+    tree = state.account_merkle_tree
+    block = [(txs[i].message(), txs[i].signature.to_bytes()) + _payment_leaves(state, txs[i]) for i in known]
+    proofs, _ = M.generate_pedersen_payment_proofs(pk, circuit, tree, block, rng)
+    root = tree.root()
+    for i, proof in zip(known, proofs):
+        if proof is not None:
+            out[i] = (proof, W.pedersen_payment_public_inputs(root, txs[i].message()))
     return out

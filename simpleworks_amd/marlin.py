@@ -644,6 +644,51 @@ def generate_payment_proofs(proving_key, circuit, tree, payments, rng, uncompres
     return [raw[cap * i:cap * i + lens[i]] if lens[i] else None for i in range(count)], list(flags)
 
 
+def pedersen_payment_circuit_shape(height, salted=False):
+    """swm_pedersen_payment_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the payment circuit over a Pedersen
+    account tree of that height, with or without a Schnorr salt — what workloads.build_pedersen_payment emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_pedersen_payment_circuit_shape(height, 1 if salted else 0, ctypes.byref(ni), ctypes.byref(nw),
+                                                             ctypes.byref(nc)), "swm_pedersen_payment_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_pedersen_payment_proof(proving_key, circuit, tree, message, signature, sender_leaf, recipient_leaf, rng, uncompressed=False):
+    """swm_pedersen_payment_prove_at: the proof of workloads.PedersenPaymentValidation with the circuit's witness synthesised on the
+    GPU (ledger.PedersenPaymentCircuit) against the resident account tree `tree` (a hash.DeviceMerkleTree) and handed to the prover
+    on the device.  The public input to verify with is workloads.pedersen_payment_public_inputs(tree.root(), message).  A payment
+    that is not valid (signature, balance, either leaf) raises with SWM_ERR_UNSATISFIED.  Returns the proof bytes."""
+    ctx = proving_key.ctx
+    bufs = [(ctypes.c_uint8 * len(p)).from_buffer_copy(p) for p in _payment_bytes(message, signature, sender_leaf, recipient_leaf)]
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    _check(ctx.lib.swm_pedersen_payment_prove_at(ctx.h, proving_key.h, circuit.h, tree.h, bufs[0], bufs[1], bufs[2], bufs[3], rng.h,
+                                                 1 if uncompressed else 0, buf, len(buf), ctypes.byref(n)),
+           "swm_pedersen_payment_prove_at", ctx)
+    return bytes(buf[: n.value])
+
+
+def generate_pedersen_payment_proofs(proving_key, circuit, tree, payments, rng, uncompressed=False):
+    """swm_pedersen_payment_prove_many_at: generate_payment_proofs over a Pedersen account tree.  Returns (proofs, flags): proofs[i]
+    is the proof bytes, or None for a payment whose flag byte is not 3, and for one whose flag byte is 3 but whose system the prover
+    found unsatisfied (a leaf that is not the tree's)."""
+    ctx = proving_key.ctx
+    count = len(payments)
+    if not count:
+        return [], []
+    cols = list(zip(*[_payment_bytes(*p) for p in payments]))
+    bufs = [(ctypes.c_uint8 * (count * len(col[0]))).from_buffer_copy(b"".join(col)) for col in cols]
+    cap = 4096
+    out = (ctypes.c_uint8 * (cap * count))()
+    lens = (ctypes.c_size_t * count)()
+    flags = (ctypes.c_uint8 * count)()
+    _check(ctx.lib.swm_pedersen_payment_prove_many_at(ctx.h, proving_key.h, circuit.h, tree.h, bufs[0], bufs[1], bufs[2], bufs[3], count,
+                                                      rng.h, 1 if uncompressed else 0, out, cap, lens, flags),
+           "swm_pedersen_payment_prove_many_at", ctx)
+    raw = bytes(out)
+    return [raw[cap * i:cap * i + lens[i]] if lens[i] else None for i in range(count)], list(flags)
+
+
 def transfer_circuit_shape(params, height, salted=False):
     """swm_transfer_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the transfer circuit over a Poseidon
     account tree of that height, with or without a Schnorr salt — what workloads.build_transfer emits."""

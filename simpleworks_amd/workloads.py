@@ -486,6 +486,41 @@ def _boolean_witness(cs, one, v):
     return b
 
 
+def _mw_level(cs, one, params, cur, dir_v, sib, byte_pool=None):
+    """One level of a Pedersen membership path: dir | sibling | left | the bits of left and right | the conditional additions of
+    the two-to-one hash over them.  cur: the running digest (an _LC).  Returns (the direction bit, the parent digest), both _LC;
+    byte_pool (a list) receives the bytes of the decomposed digests."""
+    d = params.digest_bits
+    ws = len(params.inner_gens[0])
+    dirbit = _boolean_witness(cs, one, dir_v)
+    s = _LC([(1, cs.new_witness_variable(sib % R_MODULUS))], sib)
+    # left = dir ? sibling : cur  (one row), right = cur + sibling - left (linear)
+    left_v = s.value if dirbit.value else cur.value
+    left = _LC([(1, cs.new_witness_variable(left_v))], left_v)
+    cs.enforce_constraint(dirbit.terms, s.minus(cur).terms, left.minus(cur).terms)
+    right = cur.plus(s).minus(left)
+    bits = []
+    for child in (left, right):
+        cb = [_boolean_witness(cs, one, (child.value >> i) & 1) for i in range(d)]
+        packed = _LC([], 0)
+        for i, b in enumerate(cb):
+            packed = packed.plus(b.scaled(1 << i))
+        if d < 256:  # toy digests: the bits above digest_bits travel in one unconstrained witness
+            hi = child.value >> d
+            packed = packed.plus(_LC([(1 << d, cs.new_witness_variable(hi))], hi << d))
+        cs.enforce_constraint(packed.minus(child).terms, [(1, one)], [])
+        for i in range(253, d):  # canonical range: r < 2^253, the top bits are zero — rows `0 * 0 = bit`
+            cs.enforce_constraint([], [], cb[i].terms)
+        bits += cb
+        if byte_pool is not None:
+            for i in range(0, d - 7, 8):
+                byte_pool.append(cb[i:i + 8])
+    acc = None
+    for k, b in enumerate(bits):
+        acc = _cond_add_const(cs, one, acc, params.inner_gens[k // ws][k % ws], b)
+    return dirbit, acc[0]
+
+
 def build_merkle_membership(cs, params, leaf_u8, leaf_index, siblings, gadget_byte_ops=0, root=None):
     """Emits the membership circuit into `cs` (any builder with ark-relations' vocabulary: new_input_variable,
     new_witness_variable, enforce_constraint(a, b, c), one()).  Public inputs, in order: root, then the 8 leaf bits
@@ -495,7 +530,6 @@ def build_merkle_membership(cs, params, leaf_u8, leaf_index, siblings, gadget_by
     the decomposed digests: 8 new boolean witnesses and 8-16 rows each, half of them with empty A and B
     (src/gadgets/uint8.rs:117-118, :165-167).  Returns the public-input list [root, b0..b7]."""
     one = cs.one()
-    d = params.digest_bits
     true_root = params.root_from_path(leaf_u8, leaf_index, siblings)
     pub_root = true_root if root is None else root % R_MODULUS
     root_v = _LC([(1, cs.new_input_variable(pub_root))], pub_root)
@@ -511,34 +545,8 @@ def build_merkle_membership(cs, params, leaf_u8, leaf_index, siblings, gadget_by
         acc = _cond_add_const(cs, one, acc, params.leaf_gens[k // ws][k % ws], b)
     cur = acc[0]
     byte_pool = []
-    ws = len(params.inner_gens[0])
     for lvl, sib in enumerate(siblings):
-        dirbit = _boolean_witness(cs, one, (leaf_index >> lvl) & 1)
-        s = _LC([(1, cs.new_witness_variable(sib % R_MODULUS))], sib)
-        # left = dir ? sibling : cur  (one row), right = cur + sibling - left (linear)
-        left_v = s.value if dirbit.value else cur.value
-        left = _LC([(1, cs.new_witness_variable(left_v))], left_v)
-        cs.enforce_constraint(dirbit.terms, s.minus(cur).terms, left.minus(cur).terms)
-        right = cur.plus(s).minus(left)
-        bits = []
-        for child in (left, right):
-            cb = [_boolean_witness(cs, one, (child.value >> i) & 1) for i in range(d)]
-            packed = _LC([], 0)
-            for i, b in enumerate(cb):
-                packed = packed.plus(b.scaled(1 << i))
-            if d < 256:  # toy digests: the bits above digest_bits travel in one unconstrained witness
-                hi = child.value >> d
-                packed = packed.plus(_LC([(1 << d, cs.new_witness_variable(hi))], hi << d))
-            cs.enforce_constraint(packed.minus(child).terms, [(1, one)], [])
-            for i in range(253, d):  # canonical range: r < 2^253, the top bits are zero — rows `0 * 0 = bit`
-                cs.enforce_constraint([], [], cb[i].terms)
-            bits += cb
-            for i in range(0, d - 7, 8):
-                byte_pool.append(cb[i:i + 8])
-        acc = None
-        for k, b in enumerate(bits):
-            acc = _cond_add_const(cs, one, acc, params.inner_gens[k // ws][k % ws], b)
-        cur = acc[0]
+        _, cur = _mw_level(cs, one, params, cur, (leaf_index >> lvl) & 1, sib, byte_pool)
     cs.enforce_constraint(cur.minus(root_v).terms, [(1, one)], [])  # is_member.enforce_equal(TRUE)
     # optional block of simpleworks UInt8 gadget rows over the path bytes
     for op in range(gadget_byte_ops):
@@ -1910,3 +1918,169 @@ class TransferValidation:
     def generate_constraints(self, cs):
         build_transfer(cs, self.generator, self.salt, self.params, self.height, self.message, self.signature, self.sender_leaf,
                        self.sender_path, self.recipient_leaf, self.recipient_path, old_root=self.old_root, new_root=self.new_root)
+
+
+# ===================================================================================================================
+# The payment statement over the reference's own account tree: the Pedersen Merkle tree of examples/simple-payments
+# (ledger.rs:54-88), a leaf CRH of 144 windows of 4 bits (one 72-byte AccountInformation exactly) and a two-to-one CRH of 128.
+# build_payment row for row except the two membership sections.  build_pedersen_payment is the layout contract of
+# csrc/host/pedersen_payment_shape.h and csrc/pedersen_payment_witness.hip.  With S, S_rows the Schnorr circuit's counts over the
+# 10-byte message, L = height - 1 and M = 3450 + 3581 L the witnesses of one membership section:
+#   instance  one, root, sender, recipient, amount
+#   witness   the Schnorr block | 64 balance bits | 64 diff bits | the sender's section | 576 recipient leaf bits | the
+#             recipient's section                                                                  S + 128 + M + 576 + M
+#             a section: the leaf hash, 575 conditional additions (bits 1 .. 575 of the leaf, six witnesses each: t, b t, m1, m2,
+#             X3, Y3 of _cond_add_const against the LEAF generators), then L level blocks of _mw_level (dir | sibling | left |
+#             2 x 256 bits | 511 x 6), exactly build_merkle_membership's with digest_bits = 256
+#   rows      the Schnorr block's | booleanity of balance and diff, the packing row, three tie rows | the sender's section: 3450
+#             rows of the leaf hash, 3588 per level, eight index rows (dir_l = id bit l for l < L, id bit l = 0 above), the root
+#             row | booleanity of the recipient's bits | the recipient's section     S_rows + 132 + 576 + 2 (3459 + 3588 L)
+# There is no byte-operation block.  The sender's leaf bits are the `dec` bits of Y.x and Y.y and the balance bits; the
+# recipient's leaf is any 72 bytes.  Every witness is computed honestly whatever the inputs say: a bad signature fails comparison
+# rows of the Schnorr block only, an overdraft the packing row only, a leaf that is not the tree's a select or root row of its
+# section only (with sibling arrays every select row holds and the root row fails).
+# ===================================================================================================================
+PEDERSEN_PAYMENT_LEAF_WITNESSES = (8 * PAYMENT_LEAF_LEN - 1) * 6         # 3450
+PEDERSEN_PAYMENT_LEVEL_WITNESSES = 3 + 512 + 511 * 6                      # 3581 (merkle_shape.h, MW_LEVEL_WITNESSES)
+PEDERSEN_PAYMENT_LEVEL_ROWS = 2 + 2 * (256 + 1 + 3) + 511 * 6             # 3588 (MW_LEVEL_ROWS)
+
+
+def pedersen_payment_circuit_layout(height, salted=False):
+    """Offsets of the witness groups and the named rows of build_pedersen_payment and its three counts, as
+    csrc/host/pedersen_payment_shape.h states them.  "schnorr" is the Schnorr block's own layout."""
+    if not 2 <= height <= 9:
+        raise ValueError("pedersen payment circuit: 2 <= height <= 9 (an account id is one byte)")
+    sv = schnorr_circuit_layout(PAYMENT_MSG_LEN, salted)
+    levels = height - 1
+    m = PEDERSEN_PAYMENT_LEAF_WITNESSES + PEDERSEN_PAYMENT_LEVEL_WITNESSES * levels
+    section_rows = PEDERSEN_PAYMENT_LEAF_WITNESSES + PEDERSEN_PAYMENT_LEVEL_ROWS * levels + 8 + 1
+    lay = {"schnorr": sv, "levels": levels, "membership_witnesses": m, "section_rows": section_rows}
+    lay["balance"] = sv["num_witness"]
+    lay["diff"] = lay["balance"] + 64
+    lay["sender"] = lay["diff"] + 64
+    lay["recipient_bits"] = lay["sender"] + m
+    lay["recipient"] = lay["recipient_bits"] + 8 * PAYMENT_LEAF_LEN
+    lay["num_instance"] = 5
+    lay["num_witness"] = lay["recipient"] + m
+    lay["pack_row"] = sv["num_constraints"] + 128
+    lay["tie_rows"] = lay["pack_row"] + 1            # sender, recipient, amount
+    lay["sender_rows"] = lay["tie_rows"] + 3
+    lay["sender_root_row"] = lay["sender_rows"] + section_rows - 1
+    lay["recipient_bit_rows"] = lay["sender_root_row"] + 1
+    lay["recipient_rows"] = lay["recipient_bit_rows"] + 8 * PAYMENT_LEAF_LEN
+    lay["recipient_root_row"] = lay["recipient_rows"] + section_rows - 1
+    lay["num_constraints"] = lay["recipient_root_row"] + 1
+    return lay
+
+
+pedersen_payment_public_inputs = payment_public_inputs
+
+
+def _pp_leaf_bits(leaf):
+    return [(byte >> i) & 1 for byte in bytes(leaf) for i in range(8)]
+
+
+def pedersen_payment_root(merkle_params, leaf, index, siblings):
+    """The root the path of a 72-byte leaf leads to: Path::verify's walk in integers."""
+    cur = pedersen_hash_bits(_pp_leaf_bits(leaf), merkle_params.leaf_gens)
+    for lvl, s in enumerate(siblings):
+        cur = merkle_params.inner_hash(s, cur) if (index >> lvl) & 1 else merkle_params.inner_hash(cur, s)
+    return cur
+
+
+def _pp_membership(cs, one, merkle_params, leaf_bits, id_bits, index, siblings, root_v):
+    """One membership section over leaf bits that already are variables (a list of _LC): the leaf hash, the levels, the eight rows
+    that tie the level directions to the id bits, the root row."""
+    ws = len(merkle_params.leaf_gens[0])
+    acc = None
+    for k, b in enumerate(leaf_bits):
+        acc = _cond_add_const(cs, one, acc, merkle_params.leaf_gens[k // ws][k % ws], b)
+    cur = acc[0]
+    dirs = []
+    for lvl, s in enumerate(siblings):
+        dirbit, cur = _mw_level(cs, one, merkle_params, cur, (index >> lvl) & 1, s)
+        dirs.append(dirbit)
+    for lvl in range(8):
+        if lvl < len(siblings):
+            cs.enforce_constraint(dirs[lvl].terms + [(R_MODULUS - 1, id_bits[lvl])], [(1, one)], [])
+        else:
+            cs.enforce_constraint([(1, id_bits[lvl])], [(1, one)], [])
+    cs.enforce_constraint(cur.terms, [(1, one)], root_v)
+
+
+def build_pedersen_payment(cs, generator, salt, merkle_params, height, message, signature, sender_leaf, sender_siblings,
+                           recipient_leaf, recipient_siblings, root=None):
+    """Emits the payment circuit over a Pedersen account tree into `cs`.  generator, salt: the Schnorr parameters; merkle_params: a
+    MerkleParams with 256-bit digests, at least 144 leaf and 128 two-to-one windows of 4 bits; the other arguments and the result
+    as build_payment's.  `root` overrides the public root, which otherwise is the root the sender's path leads to."""
+    message, signature = bytes(message), bytes(signature)
+    sender_leaf, recipient_leaf = bytes(sender_leaf), bytes(recipient_leaf)
+    levels = height - 1
+    if not 2 <= height <= 9 or len(sender_siblings) != levels or len(recipient_siblings) != levels:
+        raise ValueError("pedersen payment circuit: 2 <= height <= 9 and two paths of height - 1 siblings")
+    if len(message) != PAYMENT_MSG_LEN or len(sender_leaf) != PAYMENT_LEAF_LEN or len(recipient_leaf) != PAYMENT_LEAF_LEN:
+        raise ValueError("pedersen payment circuit: a message of %d bytes and two leaves of %d" % (PAYMENT_MSG_LEN, PAYMENT_LEAF_LEN))
+    if (merkle_params.digest_bits != 256 or len(merkle_params.leaf_gens[0]) != 4 or len(merkle_params.inner_gens[0]) != 4
+            or len(merkle_params.leaf_gens) < 2 * PAYMENT_LEAF_LEN or len(merkle_params.inner_gens) < 128):
+        raise ValueError("pedersen payment circuit: 256-bit digests, 144 leaf and 128 two-to-one windows of 4 bits")
+    sender, recipient, amount = message[0], message[1], int.from_bytes(message[2:], "little")
+    if sender >> levels or recipient >> levels:
+        raise ValueError("pedersen payment circuit: an account id at or above 2^%d" % levels)
+    key = (int.from_bytes(sender_leaf[:32], "little"), int.from_bytes(sender_leaf[32:64], "little"))
+    if key[0] >= R_MODULUS or key[1] >= R_MODULUS:
+        raise ValueError("pedersen payment circuit: the sender's key is not canonical")
+    balance = int.from_bytes(sender_leaf[64:], "little")
+    sender_siblings = [int(s) % R_MODULUS for s in sender_siblings]
+    recipient_siblings = [int(s) % R_MODULUS for s in recipient_siblings]
+    one = cs.one()
+    base = len(cs.witness)
+    build_schnorr_verification(cs, generator, salt, key, message, signature)
+    lay = schnorr_circuit_layout(PAYMENT_MSG_LEN, salt is not None)
+    assert len(cs.witness) - base == lay["num_witness"]
+    msg = [("w", base + lay["msg"] + i) for i in range(80)]
+    key_bits = [_LC([(1, ("w", base + lay["dec"] + i))], cs.witness[base + lay["dec"] + i]) for i in range(512)]
+    if root is None:
+        root = pedersen_payment_root(merkle_params, sender_leaf, sender, sender_siblings)
+    public = pedersen_payment_public_inputs(root, message)
+    root_i, sender_i, recipient_i, amount_i = [cs.new_input_variable(v) for v in public]
+    # balance, diff
+    bal = [_boolean_witness(cs, one, (balance >> i) & 1) for i in range(64)]
+    diff_v = (balance - amount) % (1 << 64)
+    diff = [_boolean_witness(cs, one, (diff_v >> i) & 1) for i in range(64)]
+    cs.enforce_constraint([(1 << i, bal[i].terms[0][1]) for i in range(64)] + [(R_MODULUS - (1 << i), msg[16 + i]) for i in range(64)]
+                          + [(R_MODULUS - (1 << i), diff[i].terms[0][1]) for i in range(64)], [(1, one)], [])
+    # the message is the public input
+    cs.enforce_constraint([(1 << i, msg[i]) for i in range(8)], [(1, one)], [(1, sender_i)])
+    cs.enforce_constraint([(1 << i, msg[8 + i]) for i in range(8)], [(1, one)], [(1, recipient_i)])
+    cs.enforce_constraint([(1 << i, msg[16 + i]) for i in range(64)], [(1, one)], [(1, amount_i)])
+    # sender, recipient
+    _pp_membership(cs, one, merkle_params, key_bits + bal, msg[0:8], sender, sender_siblings, [(1, root_i)])
+    recipient_bits = [_boolean_witness(cs, one, v) for v in _pp_leaf_bits(recipient_leaf)]
+    _pp_membership(cs, one, merkle_params, recipient_bits, msg[8:16], recipient, recipient_siblings, [(1, root_i)])
+    return public
+
+
+def pedersen_payment_circuit(merkle_params, height, message, signature, sender_leaf, sender_siblings, recipient_leaf,
+                             recipient_siblings, generator=ED_GENERATOR, salt=None, root=None):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs)."""
+    cs = ConstraintSystem()
+    public = build_pedersen_payment(cs, generator, salt, merkle_params, height, message, signature, sender_leaf, sender_siblings,
+                                    recipient_leaf, recipient_siblings, root)
+    return cs, public
+
+
+class PedersenPaymentValidation:
+    """The ConstraintSynthesizer of the payment statement over a Pedersen account tree for MarlinInst.index / prove: constants =
+    the Schnorr and the two CRH parameter sets, public = root, sender, recipient, amount, witness = signature, the two leaves and
+    their paths."""
+
+    def __init__(self, generator, salt, merkle_params, height, root, message, signature, sender_leaf, sender_path, recipient_leaf,
+                 recipient_path):
+        self.generator, self.salt, self.merkle_params, self.height, self.root = generator, salt, merkle_params, height, root
+        self.message, self.signature = bytes(message), bytes(signature)
+        self.sender_leaf, self.sender_path = bytes(sender_leaf), list(sender_path)
+        self.recipient_leaf, self.recipient_path = bytes(recipient_leaf), list(recipient_path)
+
+    def generate_constraints(self, cs):
+        build_pedersen_payment(cs, self.generator, self.salt, self.merkle_params, self.height, self.message, self.signature,
+                               self.sender_leaf, self.sender_path, self.recipient_leaf, self.recipient_path, root=self.root)

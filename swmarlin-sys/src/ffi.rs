@@ -19,6 +19,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_poseidon_tree { _p: [u8; 0] }
 #[repr(C)] pub struct swm_poseidon_tree_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_payment_circuit { _p: [u8; 0] }
+#[repr(C)] pub struct swm_pedersen_payment_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_transfer_circuit { _p: [u8; 0] }
 
 pub const SWM_OK: c_int = 0;
@@ -301,6 +302,35 @@ extern "C" {
                                      sender_leaves: *const u8, recipient_leaves: *const u8, count: usize, rng: *mut swm_rng,
                                      flags: c_uint, proofs_out: *mut u8, proof_cap: usize, lens: *mut usize,
                                      item_flags: *mut u8) -> c_int;
+    // the payment circuit over a Pedersen account tree (swm_merkle_tree): the same entries
+    pub fn swm_pedersen_payment_circuit_shape(height: usize, salted: c_int, num_instance: *mut usize, num_witness: *mut usize,
+                                              num_constraints: *mut usize) -> c_int;
+    pub fn swm_pedersen_payment_circuit_create(ctx: *mut swm_ctx, schnorr: *const swm_schnorr, leaf_params: *const swm_pedersen,
+                                               two_to_one_params: *const swm_pedersen, height: usize,
+                                               out: *mut *mut swm_pedersen_payment_circuit) -> c_int;
+    pub fn swm_pedersen_payment_circuit_destroy(ctx: *mut swm_ctx, circuit: *mut swm_pedersen_payment_circuit);
+    pub fn swm_pedersen_payment_witness(ctx: *mut swm_ctx, circuit: *const swm_pedersen_payment_circuit, messages: *const u8,
+                                        signatures: *const u8, sender_leaves: *const u8, sender_siblings: *const u8,
+                                        recipient_leaves: *const u8, recipient_siblings: *const u8, count: usize, witness: *mut u64,
+                                        flags: *mut u8, sender_roots: *mut u8, recipient_roots: *mut u8) -> c_int;
+    pub fn swm_pedersen_payment_witness_at(ctx: *mut swm_ctx, circuit: *const swm_pedersen_payment_circuit, tree: *const swm_merkle_tree,
+                                           messages: *const u8, signatures: *const u8, sender_leaves: *const u8,
+                                           recipient_leaves: *const u8, count: usize, witness: *mut u64, flags: *mut u8) -> c_int;
+    pub fn swm_pedersen_payment_witness_dev(ctx: *mut swm_ctx, circuit: *const swm_pedersen_payment_circuit, tree: *const swm_merkle_tree,
+                                            d_messages: *const c_void, d_signatures: *const c_void, d_sender_leaves: *const c_void,
+                                            d_recipient_leaves: *const c_void, d_sender_siblings: *const c_void,
+                                            d_recipient_siblings: *const c_void, count: usize, d_witness: *mut c_void,
+                                            d_flags: *mut c_void, d_status: *mut c_void, d_sender_roots: *mut c_void,
+                                            d_recipient_roots: *mut c_void) -> c_int;
+    pub fn swm_pedersen_payment_prove_at(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_pedersen_payment_circuit,
+                                         tree: *const swm_merkle_tree, message: *const u8, signature: *const u8, sender_leaf: *const u8,
+                                         recipient_leaf: *const u8, rng: *mut swm_rng, flags: c_uint, proof_out: *mut u8, cap: usize,
+                                         len: *mut usize) -> c_int;
+    pub fn swm_pedersen_payment_prove_many_at(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_pedersen_payment_circuit,
+                                              tree: *const swm_merkle_tree, messages: *const u8, signatures: *const u8,
+                                              sender_leaves: *const u8, recipient_leaves: *const u8, count: usize, rng: *mut swm_rng,
+                                              flags: c_uint, proofs_out: *mut u8, proof_cap: usize, lens: *mut usize,
+                                              item_flags: *mut u8) -> c_int;
     // the transfer circuit: a block of transfers applied in order, the resident tree and the account table advanced on the GPU
     pub fn swm_transfer_circuit_shape(full_rounds: usize, partial_rounds: usize, alpha: u64, height: usize, salted: c_int,
                                       num_instance: *mut usize, num_witness: *mut usize, num_constraints: *mut usize) -> c_int;
