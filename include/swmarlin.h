@@ -925,6 +925,45 @@ int swm_transfer_prove_at(swm_ctx *ctx, const swm_pk *pk, const swm_transfer_cir
                           unsigned prove_flags, uint8_t *proof_out, size_t cap, size_t *len, uint8_t old_root[32], uint8_t new_root[32],
                           uint8_t *flag, uint32_t *status);
 
+/* ---------------------------------------------------------------------------------------------- Transfer circuit over the Pedersen tree
+ * The SHAPE of the transfer circuit over a PEDERSEN account tree (simpleworks_amd/workloads.py, build_pedersen_transfer): the
+ * transfer circuit's statement and public input (old_root, new_root, sender, recipient, amount) over the sections of the Pedersen
+ * payment circuit.  Witness: the Pedersen payment circuit's up to and with the sender's membership section (against old_root); the
+ * sender's update section (the debited leaf: the leaf hash, then L update levels, each a level block walked with the membership
+ * section's own direction bit and sibling: 3579 witnesses, 3587 rows); the intermediate root R1; 576 bits of the recipient's leaf
+ * IN THE TREE OF R1 and its membership section against R1; 64 bits of (rbalance + amount) mod 2^64; the recipient's update
+ * section, whose root row is against new_root.  With S / S_rows the Schnorr circuit's counts for msg_len 10, M = 3450 + 3581 L and
+ * U = 3450 + 3579 L:  num_instance = 6;  num_witness = S + 769 + 2 M + 2 U;
+ * num_constraints = S_rows + 773 + 2 (3459 + 3588 L) + 2 (3451 + 3587 L).
+ * swm_pedersen_transfer_circuit_shape needs no GPU; it refuses what swm_pedersen_payment_circuit_shape refuses.
+ * swm_pedersen_transfer_circuit_create: the handle refers to the swm_schnorr and the two swm_pedersen: keep them.  It refuses what
+ * swm_pedersen_payment_circuit_create refuses.
+ * swm_pedersen_transfer_witness_at: the arguments, the flag byte (bits 0 .. 4), the status word, the applied / refused decision and
+ * what a refused transfer leaves are swm_transfer_witness_at's; `tree` is a resident swm_merkle_tree whose height, leaf length (72)
+ * and two swm_pedersen handles are the circuit's (otherwise SWM_ERR_INVALID_ARG).  The table is compared with the tree's leaf level
+ * by a launch of its own before anything is changed (an all-zero leaf against MerkleTree::blank's leaf digest, zero): any difference
+ * refuses the WHOLE call with SWM_ERR_INVALID_ARG and leaves tree and table as they were.  A transfer to a BLANK recipient is a
+ * satisfied system here (a blank leaf is the hash of 72 zero bytes) and is refused all the same: flag bit 3 clear.  A block whose
+ * witnesses exceed 1 GiB goes in chunks, in order (167 transfers per chunk at height 9).
+ * swm_pedersen_transfer_prove_many_at / _prove_at: as swm_transfer_prove_many_at / _prove_at; lens[i] = 0 exactly for the refused
+ * transfers; THE TREE IS ADVANCED BEFORE THE PROOFS ARE MADE. */
+typedef struct swm_pedersen_transfer_circuit swm_pedersen_transfer_circuit;
+int swm_pedersen_transfer_circuit_shape(size_t height, int salted, size_t *num_instance, size_t *num_witness, size_t *num_constraints);
+int swm_pedersen_transfer_circuit_create(swm_ctx *ctx, const swm_schnorr *schnorr, const swm_pedersen *leaf_params,
+                                         const swm_pedersen *two_to_one_params, size_t height, swm_pedersen_transfer_circuit **out);
+void swm_pedersen_transfer_circuit_destroy(swm_ctx *ctx, swm_pedersen_transfer_circuit *circuit);
+int swm_pedersen_transfer_witness_at(swm_ctx *ctx, const swm_pedersen_transfer_circuit *circuit, swm_merkle_tree *tree,
+                                     uint8_t *accounts_inout, const uint8_t *messages, const uint8_t *signatures, size_t count,
+                                     uint64_t *witnesses_out, uint8_t *old_roots, uint8_t *new_roots, uint8_t *flags, uint32_t *status);
+int swm_pedersen_transfer_prove_many_at(swm_ctx *ctx, const swm_pk *pk, const swm_pedersen_transfer_circuit *circuit, swm_merkle_tree *tree,
+                                        uint8_t *accounts_inout, const uint8_t *messages, const uint8_t *signatures, size_t count,
+                                        swm_rng *rng, unsigned prove_flags, uint8_t *proofs_out, size_t proof_cap, size_t *lens,
+                                        uint8_t *old_roots, uint8_t *new_roots, uint8_t *flags, uint32_t *status);
+int swm_pedersen_transfer_prove_at(swm_ctx *ctx, const swm_pk *pk, const swm_pedersen_transfer_circuit *circuit, swm_merkle_tree *tree,
+                                   uint8_t *accounts_inout, const uint8_t message[10], const uint8_t signature[64], swm_rng *rng,
+                                   unsigned prove_flags, uint8_t *proof_out, size_t cap, size_t *len, uint8_t old_root[32],
+                                   uint8_t new_root[32], uint8_t *flag, uint32_t *status);
+
 /* ---------------------------------------------------------------------------------------------- Blake2s random oracle
  * The reference's random oracle, unkeyed BLAKE2s-256 (RFC 7693), batched: one GPU lane per hash.  Replaces, on the GPU,
  *   src/schnorr_signature/blake2s.rs, examples/simple-payments/random_oracle/blake2s/mod.rs      RO::evaluate(&(), input)

@@ -15,6 +15,7 @@
 #include "payment_shape.h"
 #include "pedersen_payment_shape.h"
 #include "transfer_shape.h"
+#include "pedersen_transfer_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
 extern "C" {
@@ -335,6 +336,21 @@ int swm_transfer_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64
                        "2 .. %llu, %zu <= height <= %zu)",
                        full_rounds, partial_rounds, (unsigned long long)alpha, height, (size_t)PC_MAX_ROUNDS, (unsigned long long)PC_MAX_ALPHA,
                        (size_t)PY_MIN_HEIGHT, (size_t)PY_MAX_HEIGHT);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// The transfer circuit's shape over a Pedersen account tree (pedersen_transfer_shape.h; the layout is build_pedersen_transfer's)
+int swm_pedersen_transfer_circuit_shape(size_t height, int salted, size_t* num_instance, size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "pedersen_transfer_circuit_shape: NULL output");
+    PedersenTransferShape s;
+    if (!pedersen_transfer_shape(height, salted != 0, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG, "pedersen_transfer_circuit_shape: height %zu (%zu <= height <= %zu)", height,
+                       (size_t)PP_MIN_HEIGHT, (size_t)PP_MAX_HEIGHT);
     *num_instance = s.num_instance;
     *num_witness = s.num_witness;
     *num_constraints = s.num_constraints;

@@ -21,7 +21,9 @@
 //   leaves    pp_record_leaf_kernel   2 n workgroups: the leaf hash of each side
 //   levels    pp_record_level_kernel  2 n L workgroups: dir | sibling | left | 512 bits | the level's hash
 //   bits      payment_bits_kernel     (payment_witness.hip) the 704 bit witnesses, the flag byte, the refusals
-// six launches, whatever n.  No atomics, no cooperative launch; stream order is the only ordering.
+// six launches, whatever n.  No atomics, no cooperative launch; stream order is the only ordering.  The two record kernels take
+// their sections as arguments (witness_runs.h: PpArgs, pp_record_run): two per payment here, four per transfer in
+// pedersen_transfer_witness.hip, whose update sections are the level stage's update flavour.
 // flag byte, status: those of payment_witness.hip.  With a resident tree nothing compares the leaves with the tree: a leaf that is
 // not the tree's records a satisfied leaf hash and a level 0 whose `left` is the tree's digest, so that level's select row fails:
 // the honest witness of a false statement, which the prover reports.
@@ -139,41 +141,32 @@ __global__ void __launch_bounds__(256) pp_walk_kernel(const EdRow* __restrict__ 
     }
 }
 
-struct PpArgs {
-    size_t stride, sender_at, recipient_at;
-    unsigned levels;
-};
-
-// Workgroup q = 2 item + side: the leaf hash of that side, 144 windows on 192 lanes.
-__global__ void __launch_bounds__(PP_LEAF_LANES) pp_record_leaf_kernel(const EdRow* __restrict__ leaf_table, PpArgs A,
-                                                                       const uint8_t* __restrict__ sender_leaves,
-                                                                       const uint8_t* __restrict__ recipient_leaves, Fr* __restrict__ witness,
+// Workgroup item x sections + k: the leaf hash of section k of that item (witness_runs.h: PpArgs), 144 windows on 192 lanes.
+__global__ void __launch_bounds__(PP_LEAF_LANES) pp_record_leaf_kernel(const EdRow* __restrict__ leaf_table, PpArgs A, Fr* __restrict__ witness,
                                                                        Fr k2d, Fr half) {
     __shared__ MwStage<3> sh;
     const unsigned tid = threadIdx.x;
-    const size_t item = blockIdx.x >> 1;
-    const bool side = blockIdx.x & 1;
-    const uint8_t* leaf = (side ? recipient_leaves : sender_leaves) + item * PP_LEAF_LEN;
+    const size_t item = blockIdx.x / A.sections;
+    const PpSection& S = A.s[blockIdx.x % A.sections];
+    const uint8_t* leaf = S.leaves + item * PP_LEAF_LEN;
     const unsigned nib = tid < PP_LEAF_WINDOWS ? (leaf[tid >> 1] >> (4 * (tid & 1))) & 15u : 0u;
-    mw_hash_stage<3>(leaf_table, nib, (unsigned)PP_LEAF_BITS, witness + item * A.stride + (side ? A.recipient_at : A.sender_at), k2d, half, sh);
+    mw_hash_stage<3>(leaf_table, nib, (unsigned)PP_LEAF_BITS, witness + item * A.stride + S.at, k2d, half, sh);
 }
 
-// Workgroup (2 item + side) L + l: level l of that side, 128 windows on 128 lanes.  dir | sibling | left | the 512 bits of
-// left || right | the hash's witnesses, from cur_l and the sibling as they stand in memory.
-__global__ void __launch_bounds__(PP_LEVEL_LANES) pp_record_level_kernel(const EdRow* __restrict__ inner_table, PpArgs A,
-                                                                         const uint64_t* __restrict__ idx_s, const uint64_t* __restrict__ idx_r,
-                                                                         const uint32_t* __restrict__ sib_s, const uint32_t* __restrict__ sib_r,
-                                                                         const uint32_t* __restrict__ digests, Fr* __restrict__ witness, Fr k2d,
-                                                                         Fr half) {
+// Workgroup (item x sections + k) L + l: level l of section k of that item, 128 windows on 128 lanes.  dir | sibling | left | the
+// 512 bits of left || right | the hash's witnesses, from cur_l and the sibling as they stand in memory.  An update section's level
+// has no dir and no sibling of its own: left, the bits and the hash's witnesses sit two elements earlier.
+__global__ void __launch_bounds__(PP_LEVEL_LANES) pp_record_level_kernel(const EdRow* __restrict__ inner_table, PpArgs A, Fr* __restrict__ witness,
+                                                                         Fr k2d, Fr half) {
     __shared__ MwStage<2> sh;
     __shared__ uint32_t bits[16];  // left || right, canonical little-endian words
     const unsigned tid = threadIdx.x;
-    const size_t q = blockIdx.x / A.levels, item = q >> 1;
+    const size_t q = blockIdx.x / A.levels, item = q / A.sections;
     const unsigned l = blockIdx.x % A.levels;
-    const bool side = q & 1;
-    const unsigned dir = (unsigned)((side ? idx_r : idx_s)[item] >> l) & 1u;
-    const uint32_t* sib = (side ? sib_r : sib_s) + 8 * (item * A.levels + l);
-    const uint32_t* cur = digests + 8 * (q * (A.levels + 1) + l);
+    const PpSection& S = A.s[q % A.sections];
+    const unsigned dir = (unsigned)(S.idx[item] >> l) & 1u;
+    const uint32_t* sib = S.sib + 8 * (item * A.levels + l);
+    const uint32_t* cur = S.dig + item * A.dig_stride + 8 * l;
     if (tid < 8) {  // left = dir ? sibling : cur, right = the other one
         const uint32_t s = sib[tid], c = cur[tid];
         bits[tid] = dir ? s : c;
@@ -181,7 +174,10 @@ __global__ void __launch_bounds__(PP_LEVEL_LANES) pp_record_level_kernel(const E
     }
     __syncthreads();
     const Fr one = fp_one<Fr>(), zero = fp_zero<Fr>();
-    Fr* lw = witness + item * A.stride + (side ? A.recipient_at : A.sender_at) + PP_LEAF_WITNESSES + MW_LEVEL_WITNESSES * (size_t)l;
+    const bool update = S.update != 0;
+    // lw: where this level's dir would be; an update level starts at its left, lw + 2
+    Fr* lw = witness + item * A.stride + S.at + PP_LEAF_WITNESSES + (update ? MW_LEVEL_WITNESSES - 2 : MW_LEVEL_WITNESSES) * (size_t)l -
+             (update ? 2 : 0);
     if (tid == 0) {
         Fr s, left;
 #pragma unroll
@@ -189,8 +185,10 @@ __global__ void __launch_bounds__(PP_LEVEL_LANES) pp_record_level_kernel(const E
             s.v[i] = sib[i];
             left.v[i] = bits[i];
         }
-        lw[0] = dir ? one : zero;
-        lw[1] = fp_from_std(s);
+        if (!update) {
+            lw[0] = dir ? one : zero;
+            lw[1] = fp_from_std(s);
+        }
         lw[2] = fp_from_std(left);
     }
     for (unsigned i = tid; i < 2 * MW_DIGEST_BITS; i += PP_LEVEL_LANES) lw[MW_LEVEL_BITS_AT + i] = (bits[i >> 5] >> (i & 31)) & 1u ? one : zero;
@@ -199,6 +197,15 @@ __global__ void __launch_bounds__(PP_LEVEL_LANES) pp_record_level_kernel(const E
 }
 
 static const EdRow* pp_rows(const swm_pedersen* p) { return reinterpret_cast<const EdRow*>(p->d_table); }
+
+int pp_record_run(swm_ctx* ctx, const swm_pedersen* leaf, const swm_pedersen* inner, const PpArgs& A, size_t n, Fr* d_w) {
+    const Fr k2d = fp_from_u64<Fr>(2 * ED_D), half = fp_inv(fp_from_u64<Fr>(2));
+    SWM_LAUNCH(ctx, "pedersen_payment_leaves", pp_record_leaf_kernel, dim3((unsigned)(A.sections * n)), dim3(PP_LEAF_LANES), 0, pp_rows(leaf), A,
+               d_w, k2d, half);
+    SWM_LAUNCH(ctx, "pedersen_payment_levels", pp_record_level_kernel, dim3((unsigned)(A.sections * n * A.levels)), dim3(PP_LEVEL_LANES), 0,
+               pp_rows(inner), A, d_w, k2d, half);
+    return SWM_OK;
+}
 
 // n payments on device buffers.  d_sigs and the siblings 4-byte aligned, d_witness 16-byte aligned.  tree: may be NULL, then the
 // two sibling arrays are read and d_roots_s / d_roots_r (may be NULL) take the walked roots.  d_flags, d_status: per item.
@@ -221,7 +228,6 @@ static int pp_run(swm_ctx* ctx, const swm_pedersen_payment_circuit* c, const swm
     SWM_TRY(payment_prep_run(ctx, d_msgs, d_sender_leaves, n, levels, d_keys, d_idx_s, d_idx_r));
     SWM_TRY(schnorr_witness_run(ctx, &c->schnorr, aux, d_msgs, d_sigs, n, d_w, s.num_witness, d_sig_ok, d_status));
     const uint32_t *d_sib_s = reinterpret_cast<const uint32_t*>(d_sender_sib), *d_sib_r = reinterpret_cast<const uint32_t*>(d_recipient_sib);
-    const Fr k2d = fp_from_u64<Fr>(2 * ED_D), half = fp_inv(fp_from_u64<Fr>(2));
     if (tree) {
         const size_t words = dig_words + 2 * side_words;
         const unsigned blocks = (unsigned)std::min<size_t>((words + 255) / 256, 1u << 16);
@@ -233,17 +239,17 @@ static int pp_run(swm_ctx* ctx, const swm_pedersen_payment_circuit* c, const swm
         const unsigned lanes = lanes_for(2 * n);
         SWM_LAUNCH(ctx, "pedersen_payment_walk", pp_walk_kernel, dim3((unsigned)((2 * n * lanes + 255) / 256)), dim3(256), 0, pp_rows(c->leaf),
                    c->leaf->num_windows, pp_rows(c->inner), c->inner->num_windows, levels, d_sender_leaves, d_recipient_leaves,
-                   (const uint64_t*)d_idx_s, (const uint64_t*)d_idx_r, d_sib_s, d_sib_r, n, lanes, k2d, d_dig, d_roots_s, d_roots_r);
+                   (const uint64_t*)d_idx_s, (const uint64_t*)d_idx_r, d_sib_s, d_sib_r, n, lanes, fp_from_u64<Fr>(2 * ED_D), d_dig, d_roots_s,
+                   d_roots_r);
     }
-    PpArgs A;
+    PpArgs A = {};
     A.stride = s.num_witness;
-    A.sender_at = s.sender_at;
-    A.recipient_at = s.recipient_at;
+    A.dig_stride = 2 * (size_t)(levels + 1) * 8;  // path q = 2 item + side
     A.levels = levels;
-    SWM_LAUNCH(ctx, "pedersen_payment_leaves", pp_record_leaf_kernel, dim3((unsigned)(2 * n)), dim3(PP_LEAF_LANES), 0, pp_rows(c->leaf), A,
-               d_sender_leaves, d_recipient_leaves, d_w, k2d, half);
-    SWM_LAUNCH(ctx, "pedersen_payment_levels", pp_record_level_kernel, dim3((unsigned)(2 * n * levels)), dim3(PP_LEVEL_LANES), 0,
-               pp_rows(c->inner), A, (const uint64_t*)d_idx_s, (const uint64_t*)d_idx_r, d_sib_s, d_sib_r, (const uint32_t*)d_dig, d_w, k2d, half);
+    A.sections = 2;
+    A.s[0] = {d_sender_leaves, d_dig, d_sib_s, d_idx_s, s.sender_at, 0u};
+    A.s[1] = {d_recipient_leaves, d_dig + (size_t)(levels + 1) * 8, d_sib_r, d_idx_r, s.recipient_at, 0u};
+    SWM_TRY(pp_record_run(ctx, c->leaf, c->inner, A, n, d_w));
     return payment_bits_run(ctx, n, s.num_witness, s.balance_at, s.recipient_bits_at, levels, d_msgs, d_sender_leaves, d_recipient_leaves,
                             tree ? nullptr : d_sib_s, tree ? nullptr : d_sib_r, d_sig_ok, d_w, d_flags, d_status);
 }

@@ -254,6 +254,27 @@ __global__ void __launch_bounds__(TR_LANES) transfer_bits_kernel(TrBitsArgs A, c
     q[1] = make_uint4(v.v[4], v.v[5], v.v[6], v.v[7]);
 }
 
+int transfer_prep_run(swm_ctx* ctx, const uint8_t* d_msgs, const uint8_t* d_accounts, size_t n, unsigned levels, uint32_t* d_keys) {
+    SWM_LAUNCH(ctx, "transfer_prep", transfer_prep_kernel, dim3((unsigned)((16 * n + TR_LANES - 1) / TR_LANES)), dim3(TR_LANES), 0, d_msgs,
+               d_accounts, n, levels, d_keys);
+    return SWM_OK;
+}
+
+int transfer_bits_run(swm_ctx* ctx, size_t n, size_t stride, size_t balance_at, size_t sum_at, size_t r1_at, size_t recipient_bits_at,
+                      unsigned levels, const uint8_t* d_leaves, const uint32_t* d_sender_new_dig, Fr* d_w) {
+    TrBitsArgs A;
+    A.count = n;
+    A.stride = stride;
+    A.balance_at = balance_at;
+    A.sum_at = sum_at;
+    A.r1_at = r1_at;
+    A.recipient_bits_at = recipient_bits_at;
+    A.levels = levels;
+    SWM_LAUNCH(ctx, "transfer_bits", transfer_bits_kernel, dim3((unsigned)((TR_BIT_WITNESSES * n + TR_LANES - 1) / TR_LANES)), dim3(TR_LANES), 0, A,
+               d_leaves, d_sender_new_dig, d_w);
+    return SWM_OK;
+}
+
 // "transfer.aux" for n transfers: every piece a multiple of 8 bytes but the last two
 static size_t tr_aux_bytes(size_t n, size_t levels) {
     return 64 * n + 4 * (4 * n * (levels + 1) * 8 + 2 * n * levels * 8) + 16 * n + 64 * n + 4 * n + 8 + 4 * PY_LEAF_LEN * n + 2 * n + 64;
@@ -278,8 +299,7 @@ static int tr_run(swm_ctx* ctx, const swm_transfer_circuit* c, swm_poseidon_tree
     O.leaves = reinterpret_cast<uint8_t*>(O.verdict + 2);
     O.flags = O.leaves + 4 * PY_LEAF_LEN * n;
     uint8_t* d_sig_ok = O.flags + n;
-    SWM_LAUNCH(ctx, "transfer_prep", transfer_prep_kernel, dim3((unsigned)((16 * n + TR_LANES - 1) / TR_LANES)), dim3(TR_LANES), 0, d_msgs,
-               (const uint8_t*)d_accounts, n, levels, d_keys);
+    SWM_TRY(transfer_prep_run(ctx, d_msgs, d_accounts, n, levels, d_keys));
     SWM_TRY(schnorr_witness_run(ctx, &c->schnorr, aux, d_msgs, d_sigs, n, d_w, s.num_witness, d_sig_ok, O.status));
     SWM_LAUNCH(ctx, "transfer_advance", transfer_advance_kernel, dim3(1), dim3(TR_LANES), pt_lds(p), pt_table(p), pt_params(p), levels, n,
                reinterpret_cast<uint32_t*>(tree->d_nodes), d_accounts, d_msgs, (const uint8_t*)d_sig_ok, O);
@@ -288,16 +308,7 @@ static int tr_run(swm_ctx* ctx, const swm_transfer_circuit* c, swm_poseidon_tree
     for (int k = 0; k < 4; k++)
         SWM_TRY(ptw_record(ctx, &c->tree, O.leaves + k * leaves, O.idx + (k / 2) * n, O.dig + k * dig, O.sib + (k / 2) * sib, n, d_w + at[k],
                            s.num_witness, k % 2 == 0));
-    TrBitsArgs A;
-    A.count = n;
-    A.stride = s.num_witness;
-    A.balance_at = s.balance_at;
-    A.sum_at = s.sum_at;
-    A.r1_at = s.r1_at;
-    A.recipient_bits_at = s.recipient_bits_at;
-    A.levels = levels;
-    SWM_LAUNCH(ctx, "transfer_bits", transfer_bits_kernel, dim3((unsigned)((TR_BIT_WITNESSES * n + TR_LANES - 1) / TR_LANES)), dim3(TR_LANES), 0, A,
-               (const uint8_t*)O.leaves, (const uint32_t*)(O.dig + dig), d_w);
+    SWM_TRY(transfer_bits_run(ctx, n, s.num_witness, s.balance_at, s.sum_at, s.r1_at, s.recipient_bits_at, levels, O.leaves, O.dig + dig, d_w));
     *out = O;
     return SWM_OK;
 }
@@ -362,9 +373,8 @@ static int tr_download_accounts(swm_ctx* ctx, const swm_transfer_circuit* c, con
 }
 
 // the prover over one item of a chunk's device witnesses; public input one, old_root, new_root, sender, recipient, amount
-static int tr_prove_item(swm_ctx* ctx, const swm_pk* pk, const swm_transfer_circuit* c, const uint8_t* old_root, const uint8_t* new_root,
-                         const uint8_t* msg, const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
-    const TransferShape& s = c->shape;
+int transfer_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size_t num_constraints, const uint8_t* old_root, const uint8_t* new_root,
+                        const uint8_t* msg, const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
     uint64_t amount = 0;
     for (int k = 0; k < 8; k++) amount |= (uint64_t)msg[2 + k] << (8 * k);
     Fr r0, r1;
@@ -372,9 +382,9 @@ static int tr_prove_item(swm_ctx* ctx, const swm_pk* pk, const swm_transfer_circ
     (void)ps_load_std(new_root, &r1);
     const Fr inst[6] = {fp_one<Fr>(), fp_from_std(r0), fp_from_std(r1), fp_from_u64<Fr>(msg[0]), fp_from_u64<Fr>(msg[1]), fp_from_u64<Fr>(amount)};
     swm_r1cs cs = {};
-    cs.num_instance = s.num_instance;
-    cs.num_witness = s.num_witness;
-    cs.num_constraints = s.num_constraints;
+    cs.num_instance = TR_INSTANCE;
+    cs.num_witness = num_witness;
+    cs.num_constraints = num_constraints;
     cs.instance = reinterpret_cast<const uint64_t*>(inst);
     cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
     struct DevWitnessScope {
@@ -383,6 +393,12 @@ static int tr_prove_item(swm_ctx* ctx, const swm_pk* pk, const swm_transfer_circ
     } scope{ctx};
     ctx->witness_dev = d_w;
     return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+}
+
+static int tr_prove_item(swm_ctx* ctx, const swm_pk* pk, const swm_transfer_circuit* c, const uint8_t* old_root, const uint8_t* new_root,
+                         const uint8_t* msg, const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
+    return transfer_prove_item(ctx, pk, c->shape.num_witness, c->shape.num_constraints, old_root, new_root, msg, d_w, rng, flags, proof_out, cap,
+                               len);
 }
 
 // The block in chunks.  witness (may be NULL): the host copy of every item; pk (may be NULL): one proof per applied transfer.

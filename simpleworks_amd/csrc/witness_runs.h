@@ -78,6 +78,38 @@ struct PyOut {  // "payment.w": witnesses | sender roots | recipient roots | sta
 };
 int py_out(swm_ctx* ctx, size_t num_witness, size_t n, PyOut* out);
 
+// ---- Pedersen sections (pedersen_payment_witness.hip): the leaf stages and the level stages of every section of n items, one
+// launch each.  Section k of item i: the 72-byte leaf at leaves + 72 i, cur_0 .. cur_L at dig + dig_stride i (words), the L
+// siblings at sib + 8 L i, the leaf index idx[i]; its witnesses from d_w + stride i + at.  update: an update section (the transfer
+// circuit over the Pedersen tree): a level stores no dir and no sibling, its groups two elements earlier.
+static constexpr unsigned PP_MAX_SECTIONS = 4;
+struct PpSection {
+    const uint8_t* leaves;
+    const uint32_t *dig, *sib;
+    const uint64_t* idx;
+    size_t at;
+    unsigned update;
+};
+struct PpArgs {
+    size_t stride, dig_stride;
+    unsigned levels, sections;
+    PpSection s[PP_MAX_SECTIONS];
+};
+int pp_record_run(swm_ctx* ctx, const swm_pedersen* leaf, const swm_pedersen* inner, const PpArgs& A, size_t n, Fr* d_w);
+
+// ---- a block of transfers (transfer_witness.hip), whatever the tree hashes with
+// The senders' keys out of the account table (2^levels leaves of 72 bytes): 16 words per transfer for the Schnorr kernel.
+int transfer_prep_run(swm_ctx* ctx, const uint8_t* d_msgs, const uint8_t* d_accounts, size_t n, unsigned levels, uint32_t* d_keys);
+// The 769 loose elements of a transfer: balance, diff, sum and the recipient's bits out of d_leaves (4 x n x 72 bytes: sender old |
+// sender new | recipient in the tree of R1 | recipient new), R1 = the last of the sender's new digests (n x (levels + 1) x 8 words).
+int transfer_bits_run(swm_ctx* ctx, size_t n, size_t stride, size_t balance_at, size_t sum_at, size_t r1_at, size_t recipient_bits_at,
+                      unsigned levels, const uint8_t* d_leaves, const uint32_t* d_sender_new_dig, Fr* d_w);
+
+// the prover over one transfer's device witnesses; public input one, old_root, new_root (32 canonical bytes each), sender,
+// recipient, amount
+int transfer_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size_t num_constraints, const uint8_t* old_root, const uint8_t* new_root,
+                        const uint8_t* msg, const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len);
+
 // the prover over one item's device witnesses; public input one, root, sender, recipient, amount
 int py_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size_t num_constraints, const Fr& root_mont, const uint8_t* msg,
                   const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len);

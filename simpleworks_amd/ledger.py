@@ -204,6 +204,48 @@ class TransferCircuit:
             pass
 
 
+class PedersenTransferCircuit:
+    """The transfer circuit over resident Schnorr parameters and the two Pedersen CRHs of the reference's account tree
+    (swm_pedersen_transfer_circuit): synthesises the witness vector of workloads.build_pedersen_transfer for a block of transfers
+    applied in order, and advances the tree and the account table through the block.  A transfer is (message, signature).  Refers to
+    the three parameter sets: keep them alive."""
+
+    def __init__(self, sig_params, leaf_crh, two_to_one_crh, height):
+        self.ctx, self.sig_params, self.height = sig_params.ctx, sig_params, height
+        self.leaf_crh, self.two_to_one_crh = leaf_crh, two_to_one_crh
+        self.h = self.ctx.pedersen_transfer_circuit_create(sig_params.h, leaf_crh.h, two_to_one_crh.h, height)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        from .marlin import pedersen_transfer_circuit_shape
+        return pedersen_transfer_circuit_shape(self.height, self.sig_params.salt is not None)
+
+    def witness_at(self, tree, accounts, transfers, fill=None):
+        """TransferCircuit.witness_at against a hash.DeviceMerkleTree whose leaf level is the table `accounts`: the same results.
+        The tree is advanced."""
+        acc = np.frombuffer(b"".join(bytes(a) for a in accounts), dtype=np.uint8).reshape(-1, LEAF_LEN)
+        if acc.shape[0] != 1 << (self.height - 1):
+            raise ValueError("the account table is 2^(height - 1) leaves of %d bytes" % LEAF_LEN)
+        msgs = np.frombuffer(b"".join(bytes(t[0]) for t in transfers), dtype=np.uint8).reshape(len(transfers), -1)
+        sigs = np.frombuffer(b"".join(bytes(t[1]) for t in transfers), dtype=np.uint8).reshape(len(transfers), -1)
+        if msgs.shape[1] != MESSAGE_LEN or sigs.shape[1] != 64:
+            raise ValueError("a transfer is a %d-byte message and a 64-byte signature" % MESSAGE_LEN)
+        w, acc, old, new, flags, status = self.ctx.pedersen_transfer_witness_at(self.h, tree.h, self.shape()[1], acc, msgs, sigs, fill)
+        ints = lambda rows: [int.from_bytes(r.tobytes(), "little") for r in rows]
+        return w, [a.tobytes() for a in acc], ints(old), ints(new), flags, status
+
+    def free(self):
+        if self.h:
+            self.ctx.pedersen_transfer_circuit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class State:
     """ledger::State.  The account tree is a hash.DeviceMerkleTree, or with account_tree="poseidon" a hash.PoseidonMerkleTree over
     parameters.poseidon; ids are AccountId(u8), the first one handed out is 1."""
@@ -234,6 +276,7 @@ class State:
         self._payment_keys = None    # (PaymentCircuit, proving key, verifying key), the same for a Poseidon account tree
         self._transfer_keys = None   # (TransferCircuit, proving key, verifying key), the same
         self._pedersen_payment_keys = None   # (PedersenPaymentCircuit, proving key, verifying key), for a Pedersen account tree
+        self._pedersen_transfer_keys = None  # (PedersenTransferCircuit, proving key, verifying key), the same
 
     def root(self):
         return self.account_merkle_tree.root()
@@ -372,6 +415,30 @@ class State:
             self._transfer_keys = (TransferCircuit(sig, sponge, height), pk, vk)
         return self._transfer_keys
 
+    def pedersen_transfer_keys(self, rng):
+        """The transfer circuit over this ledger's Pedersen account tree (its parameters and tree height) with its Marlin keys,
+        derived once as pedersen_payment_keys derives the payment circuit's."""
+        if self.account_tree != "pedersen":
+            raise ValueError("pedersen_transfer_keys: the Pedersen transfer circuit is over a Pedersen account tree")
+        if self._pedersen_transfer_keys is None:
+            from . import marlin as M
+            from . import workloads as W
+            sig, leaf_crh, inner_crh = self.parameters.sig_params, self.parameters.leaf_crh, self.parameters.two_to_one_crh
+            height = self.account_merkle_tree.height()
+            params = W.MerkleParams(generators=(leaf_crh.generators, inner_crh.generators))
+            leaf = AccountInformation(sig.generator, 0).to_bytes_le()
+            cs, _ = W.pedersen_transfer_circuit(params, height, bytes(MESSAGE_LEN), bytes(64), leaf, [0] * (height - 1), leaf,
+                                                [0] * (height - 1), sig.generator, sig.salt, old_root=0, new_root=0, r1=0)
+            packed = cs.pack()
+            nnz = max(int(m[0][-1]) for m in packed.mats)
+            srs = M.MarlinInst.universal_setup(cs.num_constraints, len(cs.instance) + len(cs.witness), nnz, rng, sig.ctx)
+            try:
+                pk, vk = M.MarlinInst.index_from_constraint_system(srs, packed)
+            finally:
+                srs.free()
+            self._pedersen_transfer_keys = (PedersenTransferCircuit(sig, leaf_crh, inner_crh, height), pk, vk)
+        return self._pedersen_transfer_keys
+
     def account_table(self):
         """All 2^L leaves of the account tree as the state holds them, 72 bytes each; all-zero where there is no account."""
         blank = bytes(LEAF_LEN)
@@ -381,21 +448,35 @@ class State:
     def apply_transactions(self, pp, txs, rng, prove=True):
         """A block of transactions applied in order, the state transition of each proved: one witness pass on the GPU advances the
         account tree through the whole block, then (with prove) one proof per applied transaction, whose public inputs are
-        (old_root, new_root, sender, recipient, amount).  A Poseidon state only.  -> a list of (applied, proof or None, public
-        inputs), one per transaction; a refused transaction leaves the state as it was and publishes equal roots.  Unlike
-        apply_transaction, a payment to oneself is refused (the circuit reads it as a no-op, apply_transaction adds the amount)."""
+        (old_root, new_root, sender, recipient, amount).  A Poseidon state only (a Pedersen state: apply_pedersen_transactions).
+        -> a list of (applied, proof or None, public inputs), one per transaction; a refused transaction leaves the state as it
+        was and publishes equal roots.  Unlike apply_transaction, a payment to oneself is refused (the circuit reads it as a no-op,
+        apply_transaction adds the amount)."""
         if self.account_tree != "poseidon":
             raise ValueError("apply_transactions: the transfer circuit is over a Poseidon account tree")
+        return self._apply_block(txs, rng, prove)
+
+    def apply_pedersen_transactions(self, pp, txs, rng, prove=True):
+        """apply_transactions over the default Pedersen account tree, through the Pedersen transfer circuit
+        (workloads.build_pedersen_transfer): the same results; verify_transfer with pedersen_transfer_keys(rng)[2] serves.  A
+        Pedersen state only.  Besides a payment to oneself, a payment to an id without an account is refused."""
+        if self.account_tree != "pedersen":
+            raise ValueError("apply_pedersen_transactions: the Pedersen transfer circuit is over a Pedersen account tree")
+        return self._apply_block(txs, rng, prove)
+
+    def _apply_block(self, txs, rng, prove):
         from . import marlin as M
         from . import workloads as W
         txs = list(txs)
         if not txs:
             return []
-        circuit, pk, _ = self.transfer_keys(rng)
+        pedersen = self.account_tree == "pedersen"
+        circuit, pk, _ = self.pedersen_transfer_keys(rng) if pedersen else self.transfer_keys(rng)
         block = [(tx.message(), tx.signature.to_bytes()) for tx in txs]
         tree = self.account_merkle_tree
         if prove:
-            proofs, public, flags, _, table = M.generate_transfer_proofs(pk, circuit, tree, self.account_table(), block, rng)
+            prover = M.generate_pedersen_transfer_proofs if pedersen else M.generate_transfer_proofs
+            proofs, public, flags, _, table = prover(pk, circuit, tree, self.account_table(), block, rng)
         else:
             _, table, old, new, flags, _ = circuit.witness_at(tree, self.account_table(), block)
             proofs = [None] * len(txs)
@@ -405,11 +486,11 @@ class State:
         return [(bool(f & 16), proof, pub) for f, proof, pub in zip(flags, proofs, public)]
 
     def free(self):
-        for keys in (self._proof_keys, self._payment_keys, self._transfer_keys, self._pedersen_payment_keys):
+        for keys in (self._proof_keys, self._payment_keys, self._transfer_keys, self._pedersen_payment_keys, self._pedersen_transfer_keys):
             if keys is not None:
                 keys[0].free()
                 keys[1].free()
-        self._proof_keys = self._payment_keys = self._transfer_keys = self._pedersen_payment_keys = None
+        self._proof_keys = self._payment_keys = self._transfer_keys = self._pedersen_payment_keys = self._pedersen_transfer_keys = None
         self.account_merkle_tree.free()
 
 
@@ -428,8 +509,8 @@ def verify_payment(vk, public_inputs, proof, rng):
 
 
 def verify_transfer(vk, public_inputs, proof, rng):
-    """The verifier of a transfer proof: public_inputs = [old_root, new_root, sender, recipient, amount]
-    (workloads.transfer_public_inputs)."""
+    """The verifier of a transfer proof over either account tree: public_inputs = [old_root, new_root, sender, recipient, amount]
+    (workloads.transfer_public_inputs = pedersen_transfer_public_inputs)."""
     from . import marlin as M
     return M.verify_proof(vk, [int(v) for v in public_inputs], proof if isinstance(proof, M.MarlinProof) else M.MarlinProof(proof), rng)
 

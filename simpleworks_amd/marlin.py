@@ -698,7 +698,16 @@ def transfer_circuit_shape(params, height, salted=False):
     return ni.value, nw.value, nc.value
 
 
-def generate_transfer_proofs(proving_key, circuit, tree, accounts, transfers, rng, uncompressed=False):
+def pedersen_transfer_circuit_shape(height, salted=False):
+    """swm_pedersen_transfer_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the transfer circuit over a
+    Pedersen account tree of that height, with or without a Schnorr salt — what workloads.build_pedersen_transfer emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_pedersen_transfer_circuit_shape(height, 1 if salted else 0, ctypes.byref(ni), ctypes.byref(nw),
+                                                              ctypes.byref(nc)), "swm_pedersen_transfer_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_transfer_proofs(proving_key, circuit, tree, accounts, transfers, rng, uncompressed=False, _entry="swm_transfer_prove_many_at"):
     """swm_transfer_prove_many_at: the block `transfers` ((message, signature) each) applied IN ORDER to the resident account tree
     `tree` (a hash.PoseidonMerkleTree) and to the account table `accounts` (2^L leaves of 72 bytes, all-zero = no account): one
     witness pass over the whole block, then one prover call per applied transfer.  The tree is advanced before the proofs are made.
@@ -724,9 +733,8 @@ def generate_transfer_proofs(proving_key, circuit, tree, accounts, transfers, rn
     lens = (ctypes.c_size_t * count)()
     old, new = (ctypes.c_uint8 * (32 * count))(), (ctypes.c_uint8 * (32 * count))()
     flags, status = (ctypes.c_uint8 * count)(), (ctypes.c_uint32 * count)()
-    _check(ctx.lib.swm_transfer_prove_many_at(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, m_b, s_b, count, rng.h,
-                                              1 if uncompressed else 0, out, cap, lens, old, new, flags, status),
-           "swm_transfer_prove_many_at", ctx)
+    _check(getattr(ctx.lib, _entry)(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, m_b, s_b, count, rng.h,
+                                    1 if uncompressed else 0, out, cap, lens, old, new, flags, status), _entry, ctx)
     raw, old, new = bytes(out), bytes(old), bytes(new)
     public = [W.transfer_public_inputs(int.from_bytes(old[32 * i:32 * i + 32], "little"), int.from_bytes(new[32 * i:32 * i + 32], "little"),
                                        msgs[i]) for i in range(count)]
@@ -734,7 +742,7 @@ def generate_transfer_proofs(proving_key, circuit, tree, accounts, transfers, rn
             [bytes(a) for a in acc])
 
 
-def generate_transfer_proof(proving_key, circuit, tree, accounts, message, signature, rng, uncompressed=False):
+def generate_transfer_proof(proving_key, circuit, tree, accounts, message, signature, rng, uncompressed=False, _entry="swm_transfer_prove_at"):
     """swm_transfer_prove_at: one transfer; returns (proof or None, public inputs, flag, status, accounts after it)."""
     import numpy as np
     from . import workloads as W
@@ -750,11 +758,22 @@ def generate_transfer_proof(proving_key, circuit, tree, accounts, message, signa
     n = ctypes.c_size_t(0)
     old, new = (ctypes.c_uint8 * 32)(), (ctypes.c_uint8 * 32)()
     flag, status = ctypes.c_uint8(0), ctypes.c_uint32(0)
-    _check(ctx.lib.swm_transfer_prove_at(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, m_b, s_b, rng.h, 1 if uncompressed else 0,
-                                         buf, len(buf), ctypes.byref(n), old, new, ctypes.byref(flag), ctypes.byref(status)),
-           "swm_transfer_prove_at", ctx)
+    _check(getattr(ctx.lib, _entry)(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, m_b, s_b, rng.h, 1 if uncompressed else 0,
+                                    buf, len(buf), ctypes.byref(n), old, new, ctypes.byref(flag), ctypes.byref(status)), _entry, ctx)
     public = W.transfer_public_inputs(int.from_bytes(bytes(old), "little"), int.from_bytes(bytes(new), "little"), message)
     return (bytes(buf[: n.value]) if n.value else None, public, flag.value, status.value, [bytes(a) for a in acc])
+
+
+def generate_pedersen_transfer_proofs(proving_key, circuit, tree, accounts, transfers, rng, uncompressed=False):
+    """swm_pedersen_transfer_prove_many_at: generate_transfer_proofs over the reference's Pedersen account tree — `tree` a
+    hash.DeviceMerkleTree with 72-byte leaves, `circuit` a ledger.PedersenTransferCircuit.  The same arguments and results; public[i] =
+    workloads.pedersen_transfer_public_inputs(old_root_i, new_root_i, message_i)."""
+    return generate_transfer_proofs(proving_key, circuit, tree, accounts, transfers, rng, uncompressed, "swm_pedersen_transfer_prove_many_at")
+
+
+def generate_pedersen_transfer_proof(proving_key, circuit, tree, accounts, message, signature, rng, uncompressed=False):
+    """swm_pedersen_transfer_prove_at: one transfer; returns (proof or None, public inputs, flag, status, accounts after it)."""
+    return generate_transfer_proof(proving_key, circuit, tree, accounts, message, signature, rng, uncompressed, "swm_pedersen_transfer_prove_at")
 
 
 def blake2s_circuit_shape(input_len):

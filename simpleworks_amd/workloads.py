@@ -486,14 +486,21 @@ def _boolean_witness(cs, one, v):
     return b
 
 
-def _mw_level(cs, one, params, cur, dir_v, sib, byte_pool=None):
+def _mw_level(cs, one, params, cur, dir_v, sib, byte_pool=None, shared=None, keep=None):
     """One level of a Pedersen membership path: dir | sibling | left | the bits of left and right | the conditional additions of
     the two-to-one hash over them.  cur: the running digest (an _LC).  Returns (the direction bit, the parent digest), both _LC;
-    byte_pool (a list) receives the bytes of the decomposed digests."""
+    byte_pool (a list) receives the bytes of the decomposed digests.  shared = (direction bit, sibling), both _LC: the level is
+    walked with these variables of another level instead of its own — no dir, no sibling, no booleanity row (an update level:
+    left | bits | additions); dir_v and sib are not read then.  keep (a list) receives this level's (direction bit, sibling)."""
     d = params.digest_bits
     ws = len(params.inner_gens[0])
-    dirbit = _boolean_witness(cs, one, dir_v)
-    s = _LC([(1, cs.new_witness_variable(sib % R_MODULUS))], sib)
+    if shared is None:
+        dirbit = _boolean_witness(cs, one, dir_v)
+        s = _LC([(1, cs.new_witness_variable(sib % R_MODULUS))], sib)
+    else:
+        dirbit, s = shared
+    if keep is not None:
+        keep.append((dirbit, s))
     # left = dir ? sibling : cur  (one row), right = cur + sibling - left (linear)
     left_v = s.value if dirbit.value else cur.value
     left = _LC([(1, cs.new_witness_variable(left_v))], left_v)
@@ -1988,9 +1995,9 @@ def pedersen_payment_root(merkle_params, leaf, index, siblings):
     return cur
 
 
-def _pp_membership(cs, one, merkle_params, leaf_bits, id_bits, index, siblings, root_v):
+def _pp_membership(cs, one, merkle_params, leaf_bits, id_bits, index, siblings, root_v, keep=None):
     """One membership section over leaf bits that already are variables (a list of _LC): the leaf hash, the levels, the eight rows
-    that tie the level directions to the id bits, the root row."""
+    that tie the level directions to the id bits, the root row.  keep (a list) receives every level's (direction bit, sibling)."""
     ws = len(merkle_params.leaf_gens[0])
     acc = None
     for k, b in enumerate(leaf_bits):
@@ -1998,7 +2005,7 @@ def _pp_membership(cs, one, merkle_params, leaf_bits, id_bits, index, siblings, 
     cur = acc[0]
     dirs = []
     for lvl, s in enumerate(siblings):
-        dirbit, cur = _mw_level(cs, one, merkle_params, cur, (index >> lvl) & 1, s)
+        dirbit, cur = _mw_level(cs, one, merkle_params, cur, (index >> lvl) & 1, s, keep=keep)
         dirs.append(dirbit)
     for lvl in range(8):
         if lvl < len(siblings):
@@ -2084,3 +2091,180 @@ class PedersenPaymentValidation:
     def generate_constraints(self, cs):
         build_pedersen_payment(cs, self.generator, self.salt, self.merkle_params, self.height, self.message, self.signature,
                                self.sender_leaf, self.sender_path, self.recipient_leaf, self.recipient_path, root=self.root)
+
+
+# ===================================================================================================================
+# The transfer statement over the Pedersen account tree: build_transfer's statement (old_root -> new_root, R1 between them) over
+# build_pedersen_payment's sections.  build_pedersen_transfer is the layout contract of csrc/host/pedersen_transfer_shape.h and
+# csrc/pedersen_transfer_witness.hip.  With
+# S, S_rows, L and M as above and U = 3450 + 3579 L the witnesses of one update section:
+#   instance  one, old_root, new_root, sender, recipient, amount
+#   witness   build_pedersen_payment's up to and with the sender's section (against old_root)          S + 128 + M
+#             the sender's update section: the leaf hash over Y.x || Y.y || diff (575 x 6), then L update levels — _mw_level
+#             walked with the membership section's OWN dir_l and s_l: left' | 2 x 256 bits | 511 x 6     U
+#             R1                                                                                         1
+#             576 recipient leaf bits | the recipient's section against R1                               576 + M
+#             64 bits of sum = (rbalance + amount) mod 2^64                                              64
+#             the recipient's update section over key bits || sum, the recipient section's dir_l, s_l    U
+#   rows      build_pedersen_payment's up to and with the sender's root row | the sender's update: 3450 rows of the leaf hash, 3587
+#             per level (a level's without the booleanity of dir), cur'_L = R1 | booleanity of the recipient's bits | the
+#             recipient's section, root row against R1 | booleanity of sum, pack(rbalance) + pack(amount) - pack(sum) = 0 | the
+#             recipient's update, root row against new_root       S_rows + 773 + 2 (3459 + 3588 L) + 2 (3451 + 3587 L)
+# Ids are masked and every witness is computed honestly, as in build_transfer; sender == recipient is the same sequential no-op
+# there and is for the entry points to refuse.
+# ===================================================================================================================
+PEDERSEN_TRANSFER_LEVEL_WITNESSES = PEDERSEN_PAYMENT_LEVEL_WITNESSES - 2   # 3579: no dir, no sibling
+PEDERSEN_TRANSFER_LEVEL_ROWS = PEDERSEN_PAYMENT_LEVEL_ROWS - 1             # 3587: no booleanity row of dir
+
+
+def pedersen_transfer_circuit_layout(height, salted=False):
+    """Offsets of the witness groups and the named rows of build_pedersen_transfer and its three counts, as
+    csrc/host/pedersen_transfer_shape.h states them.  "update" holds an update section's own offsets."""
+    pp = pedersen_payment_circuit_layout(height, salted)
+    levels, m, section_rows = pp["levels"], pp["membership_witnesses"], pp["section_rows"]
+    u = PEDERSEN_PAYMENT_LEAF_WITNESSES + PEDERSEN_TRANSFER_LEVEL_WITNESSES * levels
+    update_rows = PEDERSEN_PAYMENT_LEAF_WITNESSES + PEDERSEN_TRANSFER_LEVEL_ROWS * levels + 1      # with its root row
+    lay = {"payment": pp, "schnorr": pp["schnorr"], "levels": levels, "membership_witnesses": m, "update_witnesses": u,
+           "section_rows": section_rows, "update_rows": update_rows}
+    for k in ("balance", "diff", "sender"):
+        lay[k] = pp[k]
+    lay["sender_update"] = lay["sender"] + m
+    lay["r1"] = lay["sender_update"] + u
+    lay["recipient_bits"] = lay["r1"] + 1
+    lay["recipient"] = lay["recipient_bits"] + 8 * PAYMENT_LEAF_LEN
+    lay["sum"] = lay["recipient"] + m
+    lay["recipient_update"] = lay["sum"] + 64
+    lay["num_instance"] = 6
+    lay["num_witness"] = lay["recipient_update"] + u
+    lay["update"] = {"leaf": 0, "level0": PEDERSEN_PAYMENT_LEAF_WITNESSES, "level_witnesses": PEDERSEN_TRANSFER_LEVEL_WITNESSES,
+                     "level_rows": PEDERSEN_TRANSFER_LEVEL_ROWS}
+    for k in ("pack_row", "tie_rows", "sender_rows", "sender_root_row"):
+        lay[k] = pp[k]
+    lay["sender_update_rows"] = lay["sender_root_row"] + 1
+    lay["sender_r1_row"] = lay["sender_update_rows"] + update_rows - 1
+    lay["recipient_bit_rows"] = lay["sender_r1_row"] + 1
+    lay["recipient_rows"] = lay["recipient_bit_rows"] + 8 * PAYMENT_LEAF_LEN
+    lay["recipient_r1_row"] = lay["recipient_rows"] + section_rows - 1
+    lay["sum_rows"] = lay["recipient_r1_row"] + 1
+    lay["sum_pack_row"] = lay["sum_rows"] + 64
+    lay["recipient_update_rows"] = lay["sum_pack_row"] + 1
+    lay["new_root_row"] = lay["recipient_update_rows"] + update_rows - 1
+    lay["num_constraints"] = lay["new_root_row"] + 1
+    return lay
+
+
+pedersen_transfer_public_inputs = transfer_public_inputs
+
+
+def _pt_update(cs, one, merkle_params, leaf_bits, path):
+    """One update section: another leaf (bits that already are variables) walked up the path of a membership section — its
+    (dir_l, s_l) pairs, no variables of their own.  Returns the walked root, an _LC."""
+    ws = len(merkle_params.leaf_gens[0])
+    acc = None
+    for k, b in enumerate(leaf_bits):
+        acc = _cond_add_const(cs, one, acc, merkle_params.leaf_gens[k // ws][k % ws], b)
+    cur = acc[0]
+    for shared in path:
+        _, cur = _mw_level(cs, one, merkle_params, cur, None, None, shared=shared)
+    return cur
+
+
+def build_pedersen_transfer(cs, generator, salt, merkle_params, height, message, signature, sender_leaf, sender_siblings,
+                            recipient_leaf, recipient_siblings, old_root=None, new_root=None, r1=None):
+    """Emits the transfer circuit over a Pedersen account tree into `cs`.  generator, salt, merkle_params as
+    build_pedersen_payment's; the other arguments as build_transfer's: recipient_leaf and recipient_siblings are those of the
+    INTERMEDIATE tree (after the sender's debit), and an id at or above 2^(height - 1) is taken by its low bits.  old_root, new_root,
+    r1 override the two public roots and the witness R1, which otherwise are the walked values.  Returns the public inputs
+    [old_root, new_root, sender, recipient, amount]."""
+    message, signature = bytes(message), bytes(signature)
+    sender_leaf, recipient_leaf = bytes(sender_leaf), bytes(recipient_leaf)
+    levels = height - 1
+    if not 2 <= height <= 9 or len(sender_siblings) != levels or len(recipient_siblings) != levels:
+        raise ValueError("pedersen transfer circuit: 2 <= height <= 9 and two paths of height - 1 siblings")
+    if len(message) != PAYMENT_MSG_LEN or len(sender_leaf) != PAYMENT_LEAF_LEN or len(recipient_leaf) != PAYMENT_LEAF_LEN:
+        raise ValueError("pedersen transfer circuit: a message of %d bytes and two leaves of %d" % (PAYMENT_MSG_LEN, PAYMENT_LEAF_LEN))
+    if (merkle_params.digest_bits != 256 or len(merkle_params.leaf_gens[0]) != 4 or len(merkle_params.inner_gens[0]) != 4
+            or len(merkle_params.leaf_gens) < 2 * PAYMENT_LEAF_LEN or len(merkle_params.inner_gens) < 128):
+        raise ValueError("pedersen transfer circuit: 256-bit digests, 144 leaf and 128 two-to-one windows of 4 bits")
+    mask = (1 << levels) - 1
+    sender, recipient, amount = message[0] & mask, message[1] & mask, int.from_bytes(message[2:], "little")
+    key = (int.from_bytes(sender_leaf[:32], "little"), int.from_bytes(sender_leaf[32:64], "little"))
+    if key[0] >= R_MODULUS or key[1] >= R_MODULUS:
+        raise ValueError("pedersen transfer circuit: the sender's key is not canonical")
+    balance = int.from_bytes(sender_leaf[64:], "little")
+    rbalance = int.from_bytes(recipient_leaf[64:], "little")
+    sender_siblings = [int(s) % R_MODULUS for s in sender_siblings]
+    recipient_siblings = [int(s) % R_MODULUS for s in recipient_siblings]
+    diff_v, sum_v = (balance - amount) % (1 << 64), (rbalance + amount) % (1 << 64)
+    if old_root is None:
+        old_root = pedersen_payment_root(merkle_params, sender_leaf, sender, sender_siblings)
+    if new_root is None:
+        new_root = pedersen_payment_root(merkle_params, recipient_leaf[:64] + sum_v.to_bytes(8, "little"), recipient, recipient_siblings)
+    if r1 is None:
+        r1 = pedersen_payment_root(merkle_params, sender_leaf[:64] + diff_v.to_bytes(8, "little"), sender, sender_siblings)
+    one = cs.one()
+    base = len(cs.witness)
+    build_schnorr_verification(cs, generator, salt, key, message, signature)
+    lay = schnorr_circuit_layout(PAYMENT_MSG_LEN, salt is not None)
+    assert len(cs.witness) - base == lay["num_witness"]
+    msg = [("w", base + lay["msg"] + i) for i in range(80)]
+    key_bits = [_LC([(1, ("w", base + lay["dec"] + i))], cs.witness[base + lay["dec"] + i]) for i in range(512)]
+    public = pedersen_transfer_public_inputs(old_root, new_root, message)
+    old_i, new_i, sender_i, recipient_i, amount_i = [cs.new_input_variable(v) for v in public]
+
+    def bits(v, n=64):
+        return [_boolean_witness(cs, one, (v >> i) & 1) for i in range(n)]
+
+    def pack(lcs, sign=1):
+        return [((1 << i) if sign > 0 else R_MODULUS - (1 << i), b.terms[0][1]) for i, b in enumerate(lcs)]
+    amount_bits = [_LC([(1, v)], 0) for v in msg[16:80]]       # pack reads the variables only
+    # balance, diff, the ties: build_pedersen_payment's
+    bal = bits(balance)
+    diff = bits(diff_v)
+    cs.enforce_constraint(pack(bal) + pack(amount_bits, -1) + pack(diff, -1), [(1, one)], [])
+    cs.enforce_constraint([(1 << i, msg[i]) for i in range(8)], [(1, one)], [(1, sender_i)])
+    cs.enforce_constraint([(1 << i, msg[8 + i]) for i in range(8)], [(1, one)], [(1, recipient_i)])
+    cs.enforce_constraint(pack(amount_bits), [(1, one)], [(1, amount_i)])
+    # the sender: in the old tree, then debited
+    path = []
+    _pp_membership(cs, one, merkle_params, key_bits + bal, msg[0:8], sender, sender_siblings, [(1, old_i)], keep=path)
+    cur = _pt_update(cs, one, merkle_params, key_bits + diff, path)
+    r1_w = _LC([(1, cs.new_witness_variable(int(r1) % R_MODULUS))], int(r1))
+    cs.enforce_constraint(cur.terms, [(1, one)], r1_w.terms)
+    # the recipient: in the tree of R1, then credited
+    recipient_bits = [_boolean_witness(cs, one, v) for v in _pp_leaf_bits(recipient_leaf)]
+    path = []
+    _pp_membership(cs, one, merkle_params, recipient_bits, msg[8:16], recipient, recipient_siblings, r1_w.terms, keep=path)
+    total = bits(sum_v)
+    cs.enforce_constraint(pack(recipient_bits[512:]) + pack(amount_bits) + pack(total, -1), [(1, one)], [])
+    cur = _pt_update(cs, one, merkle_params, recipient_bits[:512] + total, path)
+    cs.enforce_constraint(cur.terms, [(1, one)], [(1, new_i)])
+    return public
+
+
+def pedersen_transfer_circuit(merkle_params, height, message, signature, sender_leaf, sender_siblings, recipient_leaf,
+                              recipient_siblings, generator=ED_GENERATOR, salt=None, old_root=None, new_root=None, r1=None):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs)."""
+    cs = ConstraintSystem()
+    public = build_pedersen_transfer(cs, generator, salt, merkle_params, height, message, signature, sender_leaf, sender_siblings,
+                                     recipient_leaf, recipient_siblings, old_root, new_root, r1)
+    return cs, public
+
+
+class PedersenTransferValidation:
+    """The ConstraintSynthesizer of the transfer statement over a Pedersen account tree for MarlinInst.index / prove: constants =
+    the Schnorr and the two CRH parameter sets, public = old_root, new_root, sender, recipient, amount, witness = signature, the
+    sender's leaf and path in the old tree, the recipient's in the intermediate one."""
+
+    def __init__(self, generator, salt, merkle_params, height, old_root, new_root, message, signature, sender_leaf, sender_path,
+                 recipient_leaf, recipient_path):
+        self.generator, self.salt, self.merkle_params, self.height = generator, salt, merkle_params, height
+        self.old_root, self.new_root = old_root, new_root
+        self.message, self.signature = bytes(message), bytes(signature)
+        self.sender_leaf, self.sender_path = bytes(sender_leaf), list(sender_path)
+        self.recipient_leaf, self.recipient_path = bytes(recipient_leaf), list(recipient_path)
+
+    def generate_constraints(self, cs):
+        build_pedersen_transfer(cs, self.generator, self.salt, self.merkle_params, self.height, self.message, self.signature,
+                                self.sender_leaf, self.sender_path, self.recipient_leaf, self.recipient_path, old_root=self.old_root,
+                                new_root=self.new_root)

@@ -21,6 +21,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_payment_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_pedersen_payment_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_transfer_circuit { _p: [u8; 0] }
+#[repr(C)] pub struct swm_pedersen_transfer_circuit { _p: [u8; 0] }
 
 pub const SWM_OK: c_int = 0;
 pub const SWM_ERR_UNSATISFIED: c_int = -5;
@@ -331,6 +332,26 @@ extern "C" {
                                               sender_leaves: *const u8, recipient_leaves: *const u8, count: usize, rng: *mut swm_rng,
                                               flags: c_uint, proofs_out: *mut u8, proof_cap: usize, lens: *mut usize,
                                               item_flags: *mut u8) -> c_int;
+    // the transfer circuit over a Pedersen account tree: a block of transfers applied in order to a resident swm_merkle_tree
+    pub fn swm_pedersen_transfer_circuit_shape(height: usize, salted: c_int, num_instance: *mut usize, num_witness: *mut usize,
+                                               num_constraints: *mut usize) -> c_int;
+    pub fn swm_pedersen_transfer_circuit_create(ctx: *mut swm_ctx, schnorr: *const swm_schnorr, leaf_params: *const swm_pedersen,
+                                                two_to_one_params: *const swm_pedersen, height: usize,
+                                                out: *mut *mut swm_pedersen_transfer_circuit) -> c_int;
+    pub fn swm_pedersen_transfer_circuit_destroy(ctx: *mut swm_ctx, circuit: *mut swm_pedersen_transfer_circuit);
+    pub fn swm_pedersen_transfer_witness_at(ctx: *mut swm_ctx, circuit: *const swm_pedersen_transfer_circuit, tree: *mut swm_merkle_tree,
+                                            accounts_inout: *mut u8, messages: *const u8, signatures: *const u8, count: usize,
+                                            witnesses_out: *mut u64, old_roots: *mut u8, new_roots: *mut u8, flags: *mut u8,
+                                            status: *mut u32) -> c_int;
+    pub fn swm_pedersen_transfer_prove_many_at(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_pedersen_transfer_circuit,
+                                               tree: *mut swm_merkle_tree, accounts_inout: *mut u8, messages: *const u8,
+                                               signatures: *const u8, count: usize, rng: *mut swm_rng, prove_flags: c_uint,
+                                               proofs_out: *mut u8, proof_cap: usize, lens: *mut usize, old_roots: *mut u8,
+                                               new_roots: *mut u8, flags: *mut u8, status: *mut u32) -> c_int;
+    pub fn swm_pedersen_transfer_prove_at(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_pedersen_transfer_circuit,
+                                          tree: *mut swm_merkle_tree, accounts_inout: *mut u8, message: *const u8, signature: *const u8,
+                                          rng: *mut swm_rng, prove_flags: c_uint, proof_out: *mut u8, cap: usize, len: *mut usize,
+                                          old_root: *mut u8, new_root: *mut u8, flag: *mut u8, status: *mut u32) -> c_int;
     // the transfer circuit: a block of transfers applied in order, the resident tree and the account table advanced on the GPU
     pub fn swm_transfer_circuit_shape(full_rounds: usize, partial_rounds: usize, alpha: u64, height: usize, salted: c_int,
                                       num_instance: *mut usize, num_witness: *mut usize, num_constraints: *mut usize) -> c_int;
