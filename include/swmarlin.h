@@ -1133,6 +1133,25 @@ int swm_selftest_poly(swm_ctx *ctx, int op, void *data, size_t n, size_t m, cons
  * SWM_ERR_INVALID_ARG: rows = 0, z_len = 0, a NULL pointer, row pointers that do not start at 0 or decrease, a column >= z_len. */
 int swm_selftest_spmv_plan(swm_ctx *ctx, const uint32_t *rowptr, const uint32_t *col, const uint64_t *val, size_t rows,
                            const uint64_t *z, size_t z_len, uint64_t *out, uint32_t plan_counts[2]);
+/* Device self-test of the ASYNCHRONOUS entry of the G1 MSM (csrc/msm.hip: msm_enqueue with lane >= 0), which swm_msm_g1 never
+ * reaches: one round of k <= 8 jobs enqueued the way the prover enqueues the commitments of a round — lanes from a running counter
+ * that a twin pair's follower hands back, then one flush of the deferred bucket stages and one wait for all jobs.
+ * sets: nsets resident base sets.  scalars: the nvec scalar vectors back to back (4 uint64 each; Montgomery form when
+ * scalars_montgomery != 0, else standard form), vector v at the elements vec_off[v] .. vec_off[v + 1] (nvec + 1 offsets from 0,
+ * monotone); every vector is uploaded once, so jobs that name the same vector read the same device buffer.
+ * jobs: k x 5 uint64 — the index of the job's base set, the offset of its first point in that set, the index of its scalar vector,
+ * its length n (the first n scalars of the vector), its twin role: 0 none, 1 LEAD of the job after it (that job's table and offset
+ * are what the lead's second sorted array is written for), 2 FOLLOW of the job before it.  Every job gets the table of its set as
+ * swm_msm_g1_dev hands it over, and the set's infinity mask when it has one.
+ * defer_tail: 0 every job launches its own bucket stage, 1 every job leaves it to the joint launch of the round, 2 the prover's rule
+ * (jobs up to SWM_MSM_BATCH_BELOW points do).  pipe_min: 0, or the size from which a job takes the three-stream pipeline instead
+ * of one stream of its lane, for the duration of this call.
+ * out_jac: k x 18 uint64, the results as swm_msm_g1 writes them.  twins: the number of jobs of this call that took their lead's sort.
+ * SWM_ERR_INVALID_ARG: a NULL pointer, k = 0 or k > 8, an index out of range, offset + n beyond the set, n beyond the vector, a
+ * FOLLOW with no job before it, a LEAD with no job after it or whose n scalars do not fit that job's set at that job's offset. */
+int swm_selftest_msm_jobs(swm_ctx *ctx, const swm_bases *const *sets, size_t nsets, const uint64_t *scalars, const size_t *vec_off,
+                          size_t nvec, int scalars_montgomery, const uint64_t *jobs, size_t k, int defer_tail, size_t pipe_min,
+                          uint64_t *out_jac, uint64_t *twins);
 /* The bulk Fr sampler of the prover (sample_fr_bulk) on a generator handle: `need` elements drawn into a device buffer and
  * downloaded to out_mont (n x 4 uint64, Montgomery form), advancing rng as `need` successive swm_rng_rand_fr calls would. */
 int swm_selftest_sample_fr(swm_ctx *ctx, swm_rng *rng, size_t need, uint64_t *out_mont);

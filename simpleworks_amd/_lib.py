@@ -244,6 +244,8 @@ ABI = {
     "swm_selftest_poly": (_int, [_vp, _int, ctypes.c_void_p, _sz, _sz, _u64p, _u64p, _sz, ctypes.c_void_p]),
     "swm_selftest_spmv_plan": (_int, [_vp, _u32p, _u32p, _u64p, _sz, _u64p, _sz, _u64p, _u32p]),
     "swm_selftest_sample_fr": (_int, [_vp, _vp, _sz, _u64p]),
+    "swm_selftest_msm_jobs": (_int, [_vp, ctypes.POINTER(_vp), _sz, _u64p, ctypes.POINTER(_sz), _sz, _int, _u64p, _sz, _int, _sz,
+                                     _u64p, _u64p]),
     "swm_verify_proofs_batch": (_int, [_vp, _vp, _u64p, _sz, _vp, ctypes.POINTER(_sz), _sz, ctypes.c_uint, _vp,
                                        ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "swm_selftest_verify_batch": (_int, [_vp, _vp, _u64p, _sz, _vp, ctypes.POINTER(_sz), _sz, ctypes.c_uint, _vp,
@@ -1404,6 +1406,26 @@ class Context:
                                                     _p64(val) if val.size else None, rows, _p64(z), z.shape[0], _p64(out),
                                                     _p32(counts)), "swm_selftest_spmv_plan")
         return out, int(counts[0]), int(counts[1])
+
+    MSM_ROLES = {None: 0, "none": 0, "lead": 1, "follow": 2}
+    MSM_DEFER = {"off": 0, "on": 1, "prover": 2}
+
+    def selftest_msm_jobs(self, sets, vectors, jobs, montgomery=False, defer_tail="prover", pipe_min=0):
+        """swm_selftest_msm_jobs: one round of asynchronous MSM jobs, enqueued as the prover enqueues the commitments of a round.
+        sets: Bases; vectors: scalar arrays (n x 4 uint64, Montgomery form when `montgomery`), each uploaded once; jobs: tuples
+        (set index, offset, vector index, n, role) with role None / "lead" (of the next job) / "follow" (of the previous one).
+        Returns (k x 18 uint64 Jacobian results, number of jobs that took their lead's sort)."""
+        vecs = [np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4) for v in vectors]
+        off = (ctypes.c_size_t * (len(vecs) + 1))(*np.cumsum([0] + [v.shape[0] for v in vecs]).tolist())
+        flat = np.ascontiguousarray(np.concatenate(vecs)) if vecs else np.zeros((1, 4), dtype=np.uint64)
+        handles = (_vp * max(len(sets), 1))(*[b.h for b in sets])
+        spec = np.ascontiguousarray([[s, o, v, n, self.MSM_ROLES[r]] for s, o, v, n, r in jobs], dtype=np.uint64).reshape(-1, 5)
+        out = np.zeros((max(spec.shape[0], 1), 18), dtype=np.uint64)
+        twins = np.zeros(1, dtype=np.uint64)
+        self._check(self.lib.swm_selftest_msm_jobs(self.h, handles, len(sets), _p64(flat), off, len(vecs), 1 if montgomery else 0,
+                                                   _p64(spec), spec.shape[0], self.MSM_DEFER[defer_tail], pipe_min, _p64(out),
+                                                   _p64(twins)), "swm_selftest_msm_jobs")
+        return out[:spec.shape[0]], int(twins[0])
 
     def selftest_sample_fr(self, rng, need):
         """sample_fr_bulk on a generator handle (simpleworks_amd.marlin.Rng): need x 4 uint64, Montgomery form."""

@@ -981,5 +981,95 @@ int swm_selftest_mul_throughput(swm_ctx* ctx, int which, size_t threads, int ite
     (void)hipEventDestroy(e1);
     return SWM_OK;
 }
+// One round of asynchronous MSM jobs, enqueued the way commit_enqueue (marlin.hip) enqueues the commitments of a prover round:
+// lanes from a running counter that a follower hands back, the twin roles of msm.h, then msm_flush_tails and msm_finish_many.
+int swm_selftest_msm_jobs(swm_ctx* ctx, const swm_bases* const* sets, size_t nsets, const uint64_t* scalars, const size_t* vec_off,
+                          size_t nvec, int scalars_montgomery, const uint64_t* jobs, size_t k, int defer_tail, size_t pipe_min,
+                          uint64_t* out_jac, uint64_t* twins) {
+    if (!ctx || !sets || !scalars || !vec_off || !jobs || !out_jac || !twins || nsets == 0 || nvec == 0 || k == 0 ||
+        k > (size_t)swm_ctx::MSM_SLOTS || defer_tail < 0 || defer_tail > 2)
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_jobs: bad arguments");
+    for (size_t i = 0; i < nsets; i++)
+        if (!sets[i]) return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_jobs: base set %zu is null", i);
+    for (size_t v = 0; v < nvec; v++)
+        if (vec_off[v] > vec_off[v + 1]) return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_jobs: vector offsets decrease");
+    struct Spec {
+        const swm_bases* set;
+        size_t offset, vec, n;
+        MsmTwin::Role role;
+    };
+    std::vector<Spec> spec(k);
+    for (size_t i = 0; i < k; i++) {
+        const uint64_t* j = jobs + 5 * i;
+        if (j[0] >= nsets || j[2] >= nvec || j[4] > 2)
+            return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_jobs: job %zu names set %llu, vector %llu, role %llu", i,
+                           (unsigned long long)j[0], (unsigned long long)j[2], (unsigned long long)j[4]);
+        spec[i] = {sets[j[0]], (size_t)j[1], (size_t)j[2], (size_t)j[3], (MsmTwin::Role)j[4]};
+        const Spec& s = spec[i];
+        if (s.offset > s.set->n || s.n > s.set->n - s.offset)
+            return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_jobs: job %zu: %zu scalars at offset %zu exceed %zu bases", i, s.n,
+                           s.offset, s.set->n);
+        if (s.n > vec_off[s.vec + 1] - vec_off[s.vec])
+            return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_jobs: job %zu: %zu scalars of a vector of %zu", i, s.n,
+                           vec_off[s.vec + 1] - vec_off[s.vec]);
+        if (s.role == MsmTwin::FOLLOW && i == 0) return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_jobs: a FOLLOW with no job before it");
+        if (s.role == MsmTwin::LEAD && i + 1 == k) return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_jobs: a LEAD with no job after it");
+    }
+    for (size_t i = 0; i + 1 < k; i++)  // the rows a LEAD writes for the job after it lie inside that job's set
+        if (spec[i].role == MsmTwin::LEAD && (spec[i + 1].offset > spec[i + 1].set->n || spec[i].n > spec[i + 1].set->n - spec[i + 1].offset))
+            return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_jobs: job %zu leads %zu scalars at offset %zu of a set of %zu bases", i,
+                           spec[i].n, spec[i + 1].offset, spec[i + 1].set->n);
+    SWM_ON_DEVICE(ctx);
+    // every vector once: jobs that name the same vector get the same device pointer (msm_twin_match compares pointers)
+    char* d = nullptr;
+    SWM_TRY(scratch(ctx, "stage.scalars", vec_off[nvec] * 32 + 32, (void**)&d));
+    if (vec_off[nvec]) SWM_HIP(ctx, hipMemcpyAsync(d, scalars, vec_off[nvec] * 32, hipMemcpyHostToDevice, ctx->stream));
+    struct PipeMinScope {  // (as prove_impl: the value holds for the jobs of this call only)
+        swm_ctx* c;
+        size_t old;
+        ~PipeMinScope() { c->msm_pipe_min = old; }
+    } pipe_scope{ctx, ctx->msm_pipe_min};
+    if (pipe_min) ctx->msm_pipe_min = pipe_min;
+    auto table_of = [](const Spec& s) {  // as swm_msm_g1_dev
+        const swm_bases* b = s.set;
+        return b->table_c ? MsmTable{b->d_te ? nullptr : reinterpret_cast<const G1Affine*>(b->d_points28), b->n, b->table_c, s.offset,
+                                     reinterpret_cast<const G1TE*>(b->d_te)}
+                          : MsmTable();
+    };
+    const uint64_t twins_before = ctx->stat_msm_twins;
+    std::vector<MsmJob> job(k);  // (the jobs stay at their addresses until msm_finish_many)
+    std::vector<MsmJob*> jp(k);
+    std::vector<G1XYZZ> res(k);
+    auto round = [&]() -> int {
+        int lane = 0;
+        for (size_t i = 0; i < k; i++) {
+            const Spec& s = spec[i];
+            const MsmTable tab = table_of(s);
+            MsmTwin tw;
+            tw.role = s.role;
+            if (s.role == MsmTwin::LEAD) tw.tab2 = table_of(spec[i + 1]);
+            if (s.role == MsmTwin::FOLLOW) tw.lead = &job[i - 1];
+            // the prover's rule (commit_enqueue): small jobs leave their bucket stage to the round's joint launch
+            const long batch_env = sw(SW_MSM_BATCH_BELOW);
+            const long batch_below = batch_env >= 0 ? batch_env : (tab.any() ? (tab.te ? 1000000 : 200000) : 32768);
+            const bool defer = defer_tail == 2 ? (long)s.n <= batch_below : defer_tail == 1;
+            jp[i] = &job[i];
+            SWM_TRY(msm_enqueue(ctx, lane++, reinterpret_cast<const G1Affine*>(s.set->d_points) + s.offset,
+                                reinterpret_cast<const G1Affine*>(s.set->d_points28) + s.offset, d + vec_off[s.vec] * 32, s.n,
+                                scalars_montgomery, &job[i], MsmInfMask{s.set->d_inf_mask, s.offset}, defer, tab, tw));
+            if (job[i].twin_kept_lane) lane--;  // a follower leaves its lane's scratch set to the next job
+        }
+        SWM_TRY(msm_flush_tails(ctx));
+        return msm_finish_many(ctx, jp.data(), (int)k, res.data());
+    };
+    const int rc = round();
+    if (rc != SWM_OK) {  // scratch must not be reused under kernels still in flight
+        drain_streams(ctx);
+        return rc;
+    }
+    for (size_t i = 0; i < k; i++) write_jac(res[i], out_jac + 18 * i);
+    *twins = ctx->stat_msm_twins - twins_before;
+    return SWM_OK;
+}
 
 }  // extern "C"

@@ -19,8 +19,9 @@ bit-exact on the affine point.
 
 Known and NOT covered, because no small shape reaches them:
   * the 4096-bin / 8 K-tile form of msm_flat_partition (more than 57 M digits);
-  * the second sorted array of a twin pair written from an oversized bin (only the prover's job pairing gets there);
-  * the `ns >= 2^24` clause of flat_seg_write."""
+  * the `ns >= 2^24` clause of flat_seg_write.
+(The second sorted array of a twin pair written from an oversized bin, and everything else only the asynchronous entry reaches, is
+covered by tests/test_gpu_msm_async.py.)"""
 import json
 import os
 import subprocess

@@ -60,7 +60,7 @@ SETTINGS = (
     {"SWM_MSM_TE": "0"},                                        # XYZZ tables (what sets outside the prime-order subgroup get)
     {"SWM_MSM_TABLE_C": "15"},                                  # narrower window tables (what a rank of a sharded proof takes)
     {"SWM_MSM_TABLE_C": "18", "SWM_MSM_BATCH_BELOW": "0"},      # ... wider ones; every job with a bucket stage of its own
-    {"SWM_MSM_TABLE_C": "18", "SWM_MSM_TWIN": "0"},             # ... and every job with a sort of its own (test_twin_jobs below)
+    {"SWM_MSM_TABLE_C": "18", "SWM_MSM_TWIN": "0"},             # ... and every job with a sort of its own (test_twin_jobs below; against the oracle: test_gpu_msm_async.py)
     {"SWM_MSM_BATCH_BELOW": "4000000"},                         # every job in the round's joint bucket stage
     {"SWM_MSM_LOW": "1"}, {"SWM_MSM_LOW": "0"},                 # the low-LDS bucket stage everywhere / nowhere (default: joint stages)
     {"SWM_MSM_QUAD": "0"},                                      # small MSMs: one lane per chain / per segment
