@@ -1122,7 +1122,10 @@ int swm_selftest_p28(swm_ctx *ctx, int op, const uint64_t *a, const uint64_t *b,
  *   9 ntt_cosets_fwd: the polynomial data[0..n), n <= 2^(m+1), on the npieces cosets w_(4 N)^k <w_N> (N = 2^m, k = pieces[c] <= 3,
  *     one uint64 each): out[c N + j] = p(w_(4 N)^(4 j + k))
  *  10 ntt_cosets_inv and the recombination: data = n = 3 N evaluations on the cosets k = 0, 1, 2 (N each, natural order) ->
- *     out = the 3 N coefficients of the polynomial of degree < 3 N that takes them */
+ *     out = the 3 N coefficients of the polynomial of degree < 3 N that takes them
+ *  11 the division by (X - z) out of place (suffix_recurrence_from, what div_linear runs): out = m elements, m >= n and m >= 1,
+ *     whose device buffer starts as bytes 0xFF: out[0] = p(z), out[1..n) = the quotient, out[n..m) = 0; data receives the source
+ *     as the device holds it afterwards (it must be unchanged) */
 int swm_selftest_poly(swm_ctx *ctx, int op, void *data, size_t n, size_t m, const uint64_t z[4], const uint64_t *pieces,
                       size_t npieces, void *out);
 /* Device self-test of the planned sparse mat-vec (csrc/spmv.hip) as the prover and swm_r1cs_is_satisfied run it: the host CSR

@@ -1346,6 +1346,14 @@ class Context:
         self._poly(1, p, p.shape[0], 0, z_mont, None, out)
         return out
 
+    def selftest_div_linear_from(self, p_mont, z_mont, cap):
+        """Division by X - z out of place into a buffer of cap >= n elements pre-filled with bytes 0xFF:
+        (cap x 4 result: p(z), the quotient, zeros from n on; the source as the device left it)."""
+        p = np.ascontiguousarray(p_mont, dtype=np.uint64).reshape(-1, 4).copy()
+        out = np.zeros((cap, 4), dtype=np.uint64)
+        self._poly(11, p, p.shape[0], cap, z_mont, None, out)
+        return out, p
+
     def selftest_poly_eval(self, p_mont, z_mont):
         p = np.ascontiguousarray(p_mont, dtype=np.uint64).reshape(-1, 4)
         out = np.zeros(4, dtype=np.uint64)

@@ -116,13 +116,30 @@ inline DVec dv_zeros(swm_ctx* ctx, size_t n) {
     v.zero();
     return v;
 }
-// copy of src[0..len) zero-extended to n elements
-inline DVec dv_copy_padded(swm_ctx* ctx, const Fr* src, size_t len, size_t n) {
-    DVec v(ctx, n);
-    if (len > n) len = n;
-    if (len) hip_check(ctx, hipMemcpyAsync(v.p, src, len * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream), "d2d");
-    if (n > len) hip_check(ctx, zero_fill_async(v.p + len, (n - len) * sizeof(Fr), ctx->stream), "memset");
-    return v;
+// dst[0..len) = src[0..len), dst[len..n) = 0, in 16-byte pieces.  A kernel of this library for the reason fill.cuh gives: the
+// runtime's copy kernel has no issue priority and waits behind an accumulation in flight.
+static __global__ void __launch_bounds__(256) copy_pad_kernel(uint4* __restrict__ dst, const uint4* __restrict__ src, size_t len,
+                                                              size_t n) {
+    SWM_LIGHT_KERNEL();
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        dst[i] = i < len ? src[i] : make_uint4(0u, 0u, 0u, 0u);
+}
+// dst[0..len) = src[0..len), dst[len..n) = 0 (len <= n; dst and src do not overlap)
+inline void dv_copy_pad_into(swm_ctx* ctx, Fr* dst, const Fr* src, size_t len, size_t n) {
+    if (n == 0) return;
+    if ((((uintptr_t)dst | (uintptr_t)src) & 15) != 0) {  // (never the case for pool blocks and element offsets into them)
+        if (len) hip_check(ctx, hipMemcpyAsync(dst, src, len * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream), "d2d");
+        if (n > len) hip_check(ctx, zero_fill_async(dst + len, (n - len) * sizeof(Fr), ctx->stream), "memset");
+        return;
+    }
+    static_assert(sizeof(Fr) == 2 * sizeof(uint4), "element = two 16-byte pieces");
+    const unsigned grid = (unsigned)std::min<size_t>((2 * n + 255) / 256, 2048);
+    prof_begin(ctx, "copy_pad");
+    hipLaunchKernelGGL(copy_pad_kernel, dim3(grid), dim3(256), 0, ctx->stream, reinterpret_cast<uint4*>(dst),
+                       reinterpret_cast<const uint4*>(src), 2 * len, 2 * n);
+    prof_end(ctx);
+    hip_check(ctx, hipGetLastError(), "copy_pad");
 }
 
 // first kernel of every proof when SWM_TRACE / SWM_PROOF_MARKS is set: the delimiter tools/trace_dump.py and trace_share.py cut a
@@ -304,7 +321,10 @@ static __global__ void __launch_bounds__(256) rec_tile_total29(const Fr* __restr
     }
     if (t == 0) totals[blockIdx.x] = fp_mul(sm[0], rc.zpow[0]);
 }
-static __global__ void __launch_bounds__(256) rec_tile_scan29(Fr* __restrict__ a, size_t n, RecConsts rc,
+// Reads src[0..n), writes dst[0..n) and clears dst[n..cap): in place with dst == src (a workgroup reads its whole tile before it
+// writes any of it, and no other workgroup touches that tile), out of place otherwise — src is then left as it was.  The grid covers
+// cap; workgroups past the last tile of n only clear.
+static __global__ void __launch_bounds__(256) rec_tile_scan29(const Fr* src, Fr* dst, size_t n, size_t cap, RecConsts rc,
                                                               const Fr* __restrict__ tile_true /* S_b */, size_t ntiles) {
     SWM_LIGHT_KERNEL();
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -312,11 +332,19 @@ static __global__ void __launch_bounds__(256) rec_tile_scan29(Fr* __restrict__ a
     Fr* hs = tile + RT_TILE + 256;                   // 257 heads, each < 2r
     const size_t b = blockIdx.x, base = b * RT_TILE;
     const unsigned t = threadIdx.x;
+    if (b >= ntiles) {  // (uniform per workgroup: before the first barrier)
+#pragma unroll
+        for (int j = 0; j < RT_PER; j++) {
+            size_t k = base + j * 256 + t;
+            if (k < cap) dst[k] = fp_zero<Fr>();
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < RT_PER; j++) {
         unsigned e = j * 256 + t;
         size_t k = base + e;
-        tile[rt_pad(e)] = k < n ? a[k] : fp_zero<Fr>();
+        tile[rt_pad(e)] = k < n ? src[k] : fp_zero<Fr>();
     }
     __syncthreads();
     // local scan of this lane's 8 consecutive elements (carry-in 0): element + product, < 3r with limbs < 2^30
@@ -355,12 +383,14 @@ static __global__ void __launch_bounds__(256) rec_tile_scan29(Fr* __restrict__ a
     for (int j = 0; j < RT_PER; j++) {
         unsigned e = j * 256 + t;
         size_t k = base + e;
-        if (k < n) a[k] = tile[rt_pad(e)];
+        if (k < n) dst[k] = tile[rt_pad(e)];
+        else if (k < cap) dst[k] = fp_zero<Fr>();
     }
 }
 
 inline void suffix_recurrence(swm_ctx* ctx, Fr* a, size_t n, size_t m, const Fr& z);
-inline void suffix_recurrence_tiled(swm_ctx* ctx, Fr* a, size_t n, const Fr& z) {
+// dst[k] = sum_{i >= 0} z^i src[k + i], k < n, and dst[n..cap) = 0 (cap >= n); dst == src: in place
+inline void suffix_recurrence_tiled(swm_ctx* ctx, const Fr* src, Fr* dst, size_t n, size_t cap, const Fr& z) {
     size_t ntiles = (n + RT_TILE - 1) / RT_TILE;
     RecConsts rc;
     rc.zpow[0] = fp_one<Fr>();
@@ -375,7 +405,7 @@ inline void suffix_recurrence_tiled(swm_ctx* ctx, Fr* a, size_t n, const Fr& z) 
     for (int k = 0; k < 9; k++) rc29.zstep[k] = fp_mul(rc.zstep[k], two5);
     rc29.z256 = fp_mul(rc.z256, two5);
     prof_begin(ctx, "rec_tile_total");
-    hipLaunchKernelGGL(rec_tile_total29, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, (const Fr*)a, n, rc29, (const Fr*)zlow.p, totals.p);
+    hipLaunchKernelGGL(rec_tile_total29, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, src, n, rc29, (const Fr*)zlow.p, totals.p);
     prof_end(ctx);
     hip_check(ctx, hipGetLastError(), "rec_tile_total");
     Fr ztile = rc.z256;
@@ -389,7 +419,9 @@ inline void suffix_recurrence_tiled(swm_ctx* ctx, Fr* a, size_t n, const Fr& z) 
         attr_set[ctx->device & 63].store(true, std::memory_order_release);
     }
     prof_begin(ctx, "rec_tile_scan");
-    hipLaunchKernelGGL(rec_tile_scan29, dim3((unsigned)ntiles), dim3(256), lds, ctx->stream, a, n, rc29, (const Fr*)totals.p, ntiles);
+    const size_t grid = (std::max(n, cap) + RT_TILE - 1) / RT_TILE;
+    hipLaunchKernelGGL(rec_tile_scan29, dim3((unsigned)grid), dim3(256), lds, ctx->stream, src, dst, n, std::max(n, cap), rc29,
+                       (const Fr*)totals.p, ntiles);
     prof_end(ctx);
     hip_check(ctx, hipGetLastError(), "rec_tile_scan");
 }
@@ -397,7 +429,7 @@ inline void suffix_recurrence_tiled(swm_ctx* ctx, Fr* a, size_t n, const Fr& z) 
 inline void suffix_recurrence(swm_ctx* ctx, Fr* a, size_t n, size_t m, const Fr& z) {
     if (n == 0) return;
     if (m == 1 && n >= 4 * (size_t)RT_TILE) {
-        suffix_recurrence_tiled(ctx, a, n, z);
+        suffix_recurrence_tiled(ctx, a, a, n, n, z);
         return;
     }
     size_t rows = (n + m - 1) / m;
@@ -430,11 +462,29 @@ inline void suffix_recurrence(swm_ctx* ctx, Fr* a, size_t n, size_t m, const Fr&
 struct DivResult {
     DVec work;  // work[0] = p(x); work[1..n) = quotient of p / (X - x)
 };
+// The recurrence with m = 1 out of place: dst[0..n) from src[0..n), dst[n..cap) = 0; src is left as it was.  At the tiled sizes
+// the two passes read the source themselves (no copy in front); below them a copy by a kernel of this library, then in place.
+inline void suffix_recurrence_from(swm_ctx* ctx, const Fr* src, Fr* dst, size_t n, size_t cap, const Fr& z) {
+    if (cap < n) cap = n;
+    if (n >= 4 * (size_t)RT_TILE) {
+        suffix_recurrence_tiled(ctx, src, dst, n, cap, z);
+        return;
+    }
+    dv_copy_pad_into(ctx, dst, src, n, cap);
+    suffix_recurrence(ctx, dst, n, 1, z);
+}
 // cap > n: the buffer gets cap elements, zero from n on (room above the quotient for the caller)
 inline DivResult div_linear(swm_ctx* ctx, const Fr* p, size_t n, const Fr& x, size_t cap = 0) {
     DivResult r;
-    r.work = dv_copy_padded(ctx, p, n, std::max<size_t>({n, cap, 1}));
-    if (n == 0) r.work.zero();
+    const size_t len = std::max<size_t>({n, cap, 1});
+    r.work = DVec(ctx, len);
+    suffix_recurrence_from(ctx, p, r.work.p, n, len, x);
+    return r;
+}
+// The same on a polynomial that already sits in its work buffer, zero from n on: divided where it is
+inline DivResult div_linear_in_place(swm_ctx* ctx, DVec&& work, size_t n, const Fr& x) {
+    DivResult r;
+    r.work = std::move(work);
     suffix_recurrence(ctx, r.work.p, n, 1, x);
     return r;
 }

@@ -1122,11 +1122,12 @@ void shard_gather_cyclic(swm_ctx* ctx, const Fr* loc, size_t per, unsigned lg, F
     const Fr* src = all.p;
     ew(ctx, "shard_interleave", n, [=] __device__(size_t i) { dst[i] = src[(i & (((size_t)1 << lg) - 1)) * per + (i >> lg)]; });
 }
-// poly += rho * (X^H - 1); poly has H + 1 slots, slot H = 0
+// poly += rho * (X^H - 1); poly has H + 1 slots of which the first H hold a polynomial of degree < H: slot H is written, not read
+// (the buffers come from the pool without a fill: a transform overwrites the first H slots, this the last)
 void add_rho_vh(swm_ctx* ctx, Fr* poly, uint64_t H, const Fr& rho) {
     ew(ctx, "add_rho_vh", 1, [=] __device__(size_t) {
         poly[0] = fp_sub(poly[0], rho);
-        poly[H] = fp_add(poly[H], rho);
+        poly[H] = rho;
     });
 }
 // (h, X g) = divide_by_vanishing_poly(q, H) over q[0 .. total), part = |H|; or on a rank's CYCLIC share with part = |H| / G:
@@ -1220,16 +1221,17 @@ struct IndexOnB {
     const Fr *cr, *cc, *crc, *cv;
 };
 struct Round3Challenges {
-    Fr alpha, beta, ab, eta_a, eta_b, eta_c, vhab;  // ab = beta alpha, vhab = v_H(alpha) v_H(beta)
+    Fr alpha, beta, ab, ve_a, ve_b, ve_c;  // ab = beta alpha, ve_M = v_H(alpha) v_H(beta) eta_M
 };
+// With u_M = ve_M val_M:  a = u_a (d_b d_c) + d_a (u_b d_c + u_c d_b),  b = d_a (d_b d_c):  6 products for the denominators, 3 for
+// the u, 5 for a, 2 for b f and b: 16 (the form that multiplies every term out takes 18; same field element, so the same bytes).
 __device__ __forceinline__ Fr round3_a_minus_bf(const IndexOnB& x, const Round3Challenges& c, size_t i, const Fr& f) {
     Fr da = fp_add(fp_sub(fp_sub(c.ab, fp_mul(x.ar[i], c.alpha)), fp_mul(c.beta, x.ac[i])), x.arc[i]);
     Fr db = fp_add(fp_sub(fp_sub(c.ab, fp_mul(x.br[i], c.alpha)), fp_mul(c.beta, x.bc[i])), x.brc[i]);
     Fr dc = fp_add(fp_sub(fp_sub(c.ab, fp_mul(x.cr[i], c.alpha)), fp_mul(c.beta, x.cc[i])), x.crc[i]);
     Fr dbc = fp_mul(db, dc);
-    Fr t = fp_add(fp_add(fp_mul(fp_mul(c.eta_a, x.av[i]), dbc), fp_mul(fp_mul(fp_mul(c.eta_b, x.bv[i]), da), dc)),
-                  fp_mul(fp_mul(fp_mul(c.eta_c, x.cv[i]), da), db));
-    Fr a_val = fp_mul(c.vhab, t);
+    Fr ua = fp_mul(c.ve_a, x.av[i]), ub = fp_mul(c.ve_b, x.bv[i]), uc = fp_mul(c.ve_c, x.cv[i]);
+    Fr a_val = fp_add(fp_mul(ua, dbc), fp_mul(da, fp_add(fp_mul(ub, dc), fp_mul(uc, db))));
     Fr b_val = fp_mul(da, dbc);
     return fp_sub(a_val, fp_mul(b_val, f));
 }
@@ -1262,7 +1264,7 @@ struct ProveState {
     bool ra_closed_form = false;
     bool cosets = false;  // round 2 on the cosets 0, 1, 2 of H (SWM_OUTER_COSETS): e_za, e_zb, e_z hold cosets 1 | 2
     LcSet lcs;
-    DVec mask, z, za_evals, zb_evals, za_loc, zb_loc, x_poly, x_evals, w_poly, za_poly, zb_poly, e_za, e_zb, e_z;
+    DVec mask, z, za_evals, zb_evals, za_loc, zb_loc, x_poly, w_poly, za_poly, zb_poly, e_za, e_zb, e_z;
     DVec r_alpha_evals, e_ra, t_poly, q1, h1, g1x, f, h2;
 
     ProveState(const swm_pk& pk, ChaChaRng& rng, PhaseTrace& t, ProveShape shp, const ShardPlan& plan)
@@ -1428,30 +1430,36 @@ void sharded_interpolate_and_commit(swm_ctx* ctx, const swm_pk& pk, ProveState& 
 // ---- round 1: w, z_A and z_B as polynomials, and their commitments
 void round1_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
     const uint64_t H = s.H, X = s.X;
-    // x_poly = interpolate(formatted input over X); x_evals = FFT_H(x_poly)
+    // x_poly = interpolate(formatted input over X)
     s.x_poly = DVec(ctx, X);
     s.x_poly.upload(s.shape.inst.data(), X);
     dv_ntt(ctx, s.x_poly, pk.logX, true);
-    s.x_evals = dv_ntt_from(ctx, s.x_poly.p, X, pk.logH, false);
-    // w evaluations on H: 0 on the X-subgroup positions, w_extended[k - k/ratio - 1] - x_evals[k] elsewhere
+    // w v_X = interp_H(z - x on H) = interp_H(z) - x: interpolation is linear and deg x < |X| <= |H|, so x is never evaluated on H.
+    // The assignment on H: the instance (the head of z) on the X-subgroup positions, w_extended[k - k/ratio - 1] elsewhere; one
+    // inverse transform; x_poly subtracted from the first |X| coefficients (tests/test_known_work_identities.py).
     const uint64_t ratio = H / X;
     const size_t nwit = s.shape.nwit, ninst = s.ninst;
-    s.w_poly = dv_zeros(ctx, H + 1);
+    s.w_poly = DVec(ctx, H + 1);  // no fill: w_evals writes the first H slots, add_rho_vh slot H
     {
         Fr* out = s.w_poly.p;
         const Fr* zz = s.z.p;
-        const Fr* xe = s.x_evals.p;
         ew(ctx, "w_evals", H, [=] __device__(size_t k) {
-            Fr v = fp_zero<Fr>();
-            if (k % ratio != 0) {
+            Fr v;
+            if (k % ratio == 0) {
+                v = zz[k / ratio];
+            } else {
                 size_t wi = k - k / ratio - 1;
-                Fr wv = wi < nwit ? zz[ninst + wi] : fp_zero<Fr>();
-                v = fp_sub(wv, xe[k]);
+                v = wi < nwit ? zz[ninst + wi] : fp_zero<Fr>();
             }
             out[k] = v;
         });
     }
     rc_check(ctx, ntt_run(ctx, s.w_poly.p, pk.logH, 1, 0));  // in place on the first H of its H + 1 slots
+    {
+        Fr* out = s.w_poly.p;
+        const Fr* xp = s.x_poly.p;
+        ew(ctx, "w_sub_x", X, [=] __device__(size_t i) { out[i] = fp_sub(out[i], xp[i]); });
+    }
     add_rho_vh(ctx, s.w_poly.p, H, s.rho_w);
     // divide by v_X (exact): quotient = strided suffix sums, w_poly <- quotient (degree <= H - X)
     suffix_recurrence(ctx, s.w_poly.p, H + 1, X, fr_one());
@@ -1459,8 +1467,8 @@ void round1_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
     s.P_w.n = H + 1 - X;
     s.P_w.hiding = true;
     pc_commit_begin(ctx, pk, &s.lane, s.P_w.p, s.P_w.n, false, 0, true, &s.j1[0]);
-    s.za_poly = dv_zeros(ctx, H + 1);
-    s.zb_poly = dv_zeros(ctx, H + 1);
+    s.za_poly = DVec(ctx, H + 1);  // no fill: the inverse transform (or the gather of a sharded one) writes the first H slots,
+    s.zb_poly = DVec(ctx, H + 1);  // add_rho_vh slot H
     s.P_za.p = s.za_poly.p; s.P_za.n = H + 1; s.P_za.hiding = true;
     s.P_zb.p = s.zb_poly.p; s.P_zb.n = H + 1; s.P_zb.hiding = true;
     if (s.sp.r1) {
@@ -1499,7 +1507,7 @@ void round2_prework(swm_ctx* ctx, ProveState& s) {
     s.cosets = SWM_OUTER_COSETS && !s.sp.r1 && !s.sp.r2 && H >= OUTER_COSETS_MIN_H;  // single-GPU rounds (the sharded ones keep 4|H|)
     s.e_za = on_round2_layout(ctx, s, s.za_poly.p, H + 1);
     s.e_zb = on_round2_layout(ctx, s, s.zb_poly.p, H + 1);
-    DVec z_poly = dv_zeros(ctx, H + 1);
+    DVec z_poly(ctx, H + 1);  // (every slot is written below)
     Fr* out = z_poly.p;
     const Fr* wc = s.P_w.p;
     const size_t w_len = s.P_w.n;
@@ -1600,15 +1608,18 @@ void round2_t(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
         });
         if (s.cosets) {
             // coset 0 (= H) of q_1 - mask from what is known on H: r(alpha, .), z_A and z_B (their hiding terms vanish on H),
-            // t (before its interpolation) and z = w v_X + x (the assignment where w_evals put it, x's evaluations on the X-subgroup)
+            // t (before its interpolation) and z = w v_X + x (the assignment where w_evals put it: x on the X-subgroup is the
+            // instance, the head of s.z)
             s.q1 = DVec(ctx, 3 * H);
             Fr* q = s.q1.p;
-            const Fr *rh = s.r_alpha_evals.p, *za = s.za_evals.p, *zb = s.zb_evals.p, *th = s.t_poly.p, *zz = s.z.p, *xe = s.x_evals.p;
+            const Fr *rh = s.r_alpha_evals.p, *za = s.za_evals.p, *zb = s.zb_evals.p, *th = s.t_poly.p, *zz = s.z.p;
             const uint64_t ratio = H / X;
             const size_t nwit = s.shape.nwit, ninst = s.ninst;
             ew(ctx, "round2_pointwise_h", H, [=] __device__(size_t k) {
-                Fr zk = xe[k];
-                if (k % ratio != 0) {
+                Fr zk;
+                if (k % ratio == 0) {
+                    zk = zz[k / ratio];
+                } else {
                     const size_t wi = k - k / ratio - 1;
                     zk = wi < nwit ? zz[ninst + wi] : fp_zero<Fr>();
                 }
@@ -1761,7 +1772,7 @@ void round3_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
     const IndexOnB ix{pk.ar[0].row_B.p, pk.ar[0].col_B.p, pk.ar[0].row_col_B.p, pk.ar[0].val_B.p,
                       pk.ar[1].row_B.p, pk.ar[1].col_B.p, pk.ar[1].row_col_B.p, pk.ar[1].val_B.p,
                       pk.ar[2].row_B.p, pk.ar[2].col_B.p, pk.ar[2].row_col_B.p, pk.ar[2].val_B.p};
-    const Round3Challenges ch{alpha, beta, fp_mul(beta, alpha), eta_a, eta_b, eta_c, vhab};
+    const Round3Challenges ch{alpha, beta, fp_mul(beta, alpha), fp_mul(vhab, eta_a), fp_mul(vhab, eta_b), fp_mul(vhab, eta_c)};
     // f in the round's layout (cosets: 1 - 3 behind the kept coset 0, f_K), a - b f there, and back to coefficients.  On cosets
     // only f is laid out that way: a - b f itself is dense, so that one 4|K|-point transform takes it back.
     const size_t Bloc = s.sp.r3 ? Bsz / s.sp.SG : Bsz;
@@ -1779,13 +1790,16 @@ void round3_polys(swm_ctx* ctx, const swm_pk& pk, ProveState& s) {
         }
         DVec ab(ctx, Bloc);
         Fr* out = ab.p;
-        const Fr *pf = e_f.p, *fk = f_K.p;
+        // Every fourth point of the 4|K| domain is a point of K, where f IS a / b (round3_f_K; row_col = row col there): a - b f
+        // vanishes on coset 0 exactly and is written as zero, not computed.  On cosets f_K is then not read here.
+        const bool on_K_every_4th = Bsz == 4 * K;  // (|K| = 2 has a product domain of 2|K| points: computed everywhere)
+        const Fr* pf = e_f.p;
         ew(ctx, "round3_pointwise_B", Bloc, [=] __device__(size_t p) {
-            if constexpr (cosets) {
-                const size_t at = map.position(p);
-                out[p] = round3_a_minus_bf(ix, ch, p, at < K ? fk[at] : pf[at - K]);
+            if constexpr (cosets) {  // (a - b f is dense: p is the point; f sits at cosets 1 | 2 | 3 behind the kept coset 0)
+                out[p] = (p & 3) == 0 ? fp_zero<Fr>() : round3_a_minus_bf(ix, ch, p, pf[map.position(p) - K]);
             } else {
-                out[p] = round3_a_minus_bf(ix, ch, map.index(p), pf[p]);
+                const size_t i = map.index(p);
+                out[p] = on_K_every_4th && (i & 3) == 0 ? fp_zero<Fr>() : round3_a_minus_bf(ix, ch, i, pf[p]);
             }
         });
         if constexpr (blocks) {
@@ -1902,7 +1916,6 @@ std::vector<PcProof> open_combinations(swm_ctx* ctx, const swm_pk& pk, ProveStat
     };
     struct PointOpen {
         Fr point;
-        DVec comb;
         DivResult wq;
         std::vector<DivResult> sq;
         AsyncMsm wjob;
@@ -1927,7 +1940,6 @@ std::vector<PcProof> open_combinations(swm_ctx* ctx, const swm_pk& pk, ProveStat
         for (auto& l : labels)
             for (auto& t : s.lcs.at(l))
                 if (!t.second.empty()) plen = std::max(plen, s.polys.at(t.second)->n);
-        o.comb = DVec(ctx, plen ? plen : 1);
         CombineTerms cterms;
         int nterms = 0;
         Fr ch = fr_one();
@@ -1956,19 +1968,8 @@ std::vector<PcProof> open_combinations(swm_ctx* ctx, const swm_pk& pk, ProveStat
                 ch = fp_mul(ch, xi);
             }
         }
-        {   // comb[i] = sum_j k_j * src_j[i]: every polynomial is read once, the combination written once
-            Fr* out = o.comb.p;
-            const int nt = nterms;
-            ew(ctx, "open_combine", plen, [=] __device__(size_t i) {
-                Fr acc = fp_zero<Fr>();
-                for (int j = 0; j < nt; j++)
-                    if (i < cterms.len[j]) acc = fp_add(acc, fp_mul(cterms.k[j], cterms.src[j][i]));
-                out[i] = acc;
-            });
-        }
         // witness = p / (X - point) against the powers; degree-bounded members: shifted witnesses against the shifted powers,
         // folded into the plain quotient where both read the powers' table (then the job follows BOTH divisions)
-        s.tr.tick(pi == 0 ? "open beta: combination enqueued" : "open gamma: combination enqueued");
         size_t wn = plen ? plen - 1 : 0;  // coefficients of the (merged) witness quotient
         std::vector<bool> folded(o.shifted_terms.size(), false);
         for (size_t i = 0; i < o.shifted_terms.size(); i++) {
@@ -1977,7 +1978,20 @@ std::vector<PcProof> open_combinations(swm_ctx* ctx, const swm_pk& pk, ProveStat
             folded[i] = SWM_OPEN_FOLD && qn && pk.in_powers(off, qn);
             if (folded[i]) wn = std::max(wn, off + qn);
         }
-        o.wq = div_linear(ctx, o.comb.p, plen, point, wn + 1);  // zero above the quotient
+        {   // comb[i] = sum_j k_j * src_j[i]: every polynomial is read once, the combination written once — straight into the
+            // buffer it is divided in, zero above it (i >= every length) up to the room the folded quotients need
+            DVec work(ctx, std::max<size_t>(plen, wn + 1));
+            Fr* out = work.p;
+            const int nt = nterms;
+            ew(ctx, "open_combine", work.n, [=] __device__(size_t i) {
+                Fr acc = fp_zero<Fr>();
+                for (int j = 0; j < nt; j++)
+                    if (i < cterms.len[j]) acc = fp_add(acc, fp_mul(cterms.k[j], cterms.src[j][i]));
+                out[i] = acc;
+            });
+            s.tr.tick(pi == 0 ? "open beta: combination enqueued" : "open gamma: combination enqueued");
+            o.wq = div_linear_in_place(ctx, std::move(work), plen, point);
+        }
         s.tr.tick("  witness quotient enqueued");
         const bool fold_any = std::find(folded.begin(), folded.end(), true) != folded.end();
         if (!fold_any) {
@@ -2731,6 +2745,17 @@ static void selftest_poly_impl(swm_ctx* ctx, int op, void* data, size_t n, size_
         memcpy(out, h.data(), t.n * sizeof(Fr));
         return;
     }
+    if (op == 11) {  // suffix_recurrence_from: data[0..n) divided by (X - z) into a buffer of m >= n elements that starts as bytes 0xFF
+        const size_t cap = std::max<size_t>(m, 1);
+        DVec dst(ctx, cap);
+        hip_check(ctx, hipMemsetAsync(dst.p, 0xFF, cap * sizeof(Fr), ctx->stream), "memset");
+        suffix_recurrence_from(ctx, a.p, dst.p, n, cap, zz);
+        std::vector<Fr> h = dst.download(0, cap);
+        memcpy(out, h.data(), cap * sizeof(Fr));
+        std::vector<Fr> src = a.download(0, n);
+        if (n) memcpy(data, src.data(), n * sizeof(Fr));
+        return;
+    }
     if (op == 0) {  // suffix_recurrence(a, n, m, z) in place
         suffix_recurrence(ctx, a.p, n, m, zz);
         std::vector<Fr> h = a.download(0, n);
@@ -2763,7 +2788,8 @@ static void selftest_poly_impl(swm_ctx* ctx, int op, void* data, size_t n, size_
 }
 int swm_selftest_poly(swm_ctx* ctx, int op, void* data, size_t n, size_t m, const uint64_t z[4], const uint64_t* pieces,
                       size_t npieces, void* out) {
-    if (!ctx || op < 0 || op > 10 || (n && !data)) return SWM_ERR_INVALID_ARG;
+    if (!ctx || op < 0 || op > 11 || (n && !data)) return SWM_ERR_INVALID_ARG;
+    if (op == 11 && (!z || m < n || m < 1)) return SWM_ERR_INVALID_ARG;
     if ((op >= 1 && op <= 3 && !z) || (op == 0 && (!z || m == 0)) || (op != 0 && !out) || (op == 3 && npieces && !pieces))
         return SWM_ERR_INVALID_ARG;
     if (op >= 4 && op <= 7 && (m < 1 || m > 28 || n > ((size_t)1 << m))) return SWM_ERR_INVALID_ARG;
