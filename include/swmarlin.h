@@ -1003,6 +1003,42 @@ int swm_blake2s_witness_dev(swm_ctx *ctx, const void *d_inputs, size_t input_len
 int swm_blake2s_prove(swm_ctx *ctx, const swm_pk *pk, const uint8_t *input, size_t input_len, swm_rng *rng, unsigned flags,
                       uint8_t digest_out[32], uint8_t *proof_out, size_t cap, size_t *len);
 
+/* ---------------------------------------------------------------------------------------------- integer programs
+ * The reference's gadget vocabulary (src/gadgets/{uint8,uint16,uint32,uint64,uint128,boolean}.rs behind src/gadgets/traits.rs, and
+ * ark's enforce_equal / is_eq / conditionally_select) as ONE circuit per program: a straight-line tape of typed instructions over
+ * SSA registers (format "SWMPROG1", ops, types, limits and the out-of-scope list: simpleworks_amd/csrc/host/program_shape.h; the
+ * circuit and its deviations from the reference's gadgets: simpleworks_amd/workloads.py, build_program).  All executions of one
+ * program share the tape, so the shape depends on the tape alone and the witnesses of a batch are synthesised on the GPU.
+ * Instance: one, the bits of the public inputs (least significant first, declaration order), the bits of the outputs (OUTPUT order).
+ * An item's inputs: input_bytes = the sum of its inputs' sizes (BOOL: one byte, bit 0 counts; U8 .. U128: 1 .. 16 bytes), each
+ * value little-endian, in declaration order: public first.  Its outputs: the same form, in OUTPUT order.  Its status byte: bit 0 a
+ * SUB underflowed, bit 1 a DIV had a zero divisor, bit 2 an ASSERT_EQ failed.  Every witness is computed whatever the status says
+ * (the wrapped difference; q = 0, rem = a and the wrapped b - 1 - rem); the system is satisfied exactly when the status is 0.
+ * swm_program_circuit_shape needs no GPU.  SWM_ERR_INVALID_ARG: anything the validator refuses (a bad magic word, length, op, type,
+ * operand, immediate or reserved byte; MUL / DIV on U128; more than 4096 instructions or 2^20 witnesses per item), a NULL output.
+ * swm_program_create validates the tape, compiles the plan and uploads it; the handle belongs to the context's device.
+ * swm_program_witness: `count` items.  witness: count x num_witness x 4 Montgomery limbs in the circuit's variable order; outputs:
+ * count x output_bytes; status: count bytes.  A batch whose witnesses exceed 1 GiB is staged through the device in chunks of
+ * floor(1 GiB / (32 num_witness)) items (at least one).  count = 0 launches nothing.
+ * swm_program_witness_dev: the same on device buffers (witness 16-byte aligned; d_status may be NULL), no chunking.
+ * swm_program_prove: one item's witness on the device, then the proof of swm_generate_proof_ex(flags); output (output_bytes) and
+ * status_out (may be NULL) are written first.  SWM_ERR_UNSATISFIED for a non-zero status: nothing is drawn from rng.
+ * swm_program_prove_many: one witness pass per chunk, then one prover call per item of status 0, in order on the same rng.
+ * lens[i] = 0 for the others; every entry of lens and status is written whatever the return value. */
+typedef struct swm_program swm_program;
+int swm_program_circuit_shape(const uint8_t *tape, size_t len, size_t *num_instance, size_t *num_witness, size_t *num_constraints);
+int swm_program_create(swm_ctx *ctx, const uint8_t *tape, size_t len, swm_program **out);
+void swm_program_destroy(swm_ctx *ctx, swm_program *program);
+int swm_program_witness(swm_ctx *ctx, const swm_program *program, const uint8_t *inputs, size_t count, uint64_t *witness,
+                        uint8_t *outputs, uint8_t *status);
+int swm_program_witness_dev(swm_ctx *ctx, const swm_program *program, const void *d_inputs, size_t count, void *d_witness,
+                            void *d_outputs, void *d_status);
+int swm_program_prove(swm_ctx *ctx, const swm_pk *pk, const swm_program *program, const uint8_t *input, swm_rng *rng, unsigned flags,
+                      uint8_t *output, uint8_t *status_out, uint8_t *proof_out, size_t cap, size_t *len);
+int swm_program_prove_many(swm_ctx *ctx, const swm_pk *pk, const swm_program *program, const uint8_t *inputs, size_t count,
+                           swm_rng *rng, unsigned flags, uint8_t *outputs, uint8_t *status, uint8_t *proofs_out, size_t proof_cap,
+                           size_t *lens);
+
 /* ---------------------------------------------------------------------------------------------- one proof over several GPUs
  * every commitment MSM of swm_generate_proof / swm_generate_proving_and_verifying_keys is split by
  * point range — rank g of `world` takes coefficients and SRS powers [g n / world, (g+1) n / world) — and the

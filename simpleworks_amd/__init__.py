@@ -9,6 +9,7 @@ Layout (only what the path needs):
   hash.py          mirror of src/hash/mod.rs (Pedersen CRH) and the MerkleTree calls; schnorr.py: mirror of src/schnorr_signature/schnorr.rs
   elgamal.py       mirror of ark-crypto-primitives' ElGamal on ed-on-BLS12-377 as tests/encrypt.rs calls it
   random_oracle.py mirror of the Blake2s random oracle (src/schnorr_signature/blake2s.rs) and its circuit's witness
+  program.py       mirror of the integer gadgets (src/gadgets/traits.rs) as a tape builder, and the witness of a program's circuit
   workloads.py     the BASELINE.json circuits; dist.py: one proof / one MSM over several GPUs
 
 There is no CPU fallback anywhere in this package; the CPU oracle lives in oracle/ and is test infrastructure.

@@ -230,6 +230,15 @@ ABI = {
     "swm_blake2s_witness_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "swm_blake2s_prove": (_int, [_vp, _vp, ctypes.c_void_p, _sz, _vp, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, _sz,
                                  ctypes.POINTER(_sz)]),
+    "swm_program_circuit_shape": (_int, [ctypes.c_void_p, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "swm_program_create": (_int, [_vp, ctypes.c_void_p, _sz, ctypes.POINTER(_vp)]),
+    "swm_program_destroy": (None, [_vp, _vp]),
+    "swm_program_witness": (_int, [_vp, _vp, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "swm_program_witness_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "swm_program_prove": (_int, [_vp, _vp, _vp, ctypes.c_void_p, _vp, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz,
+                                 ctypes.POINTER(_sz)]),
+    "swm_program_prove_many": (_int, [_vp, _vp, _vp, ctypes.c_void_p, _sz, _vp, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, _sz, ctypes.c_void_p]),
     "swm_profile_enable": (_int, [_vp, _int]),
     "swm_profile_reset": (_int, [_vp]),
     "swm_profile_json": (_int, [_vp, ctypes.c_char_p, _sz]),

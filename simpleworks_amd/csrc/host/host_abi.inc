@@ -16,6 +16,7 @@
 #include "pedersen_payment_shape.h"
 #include "transfer_shape.h"
 #include "pedersen_transfer_shape.h"
+#include "program_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
 extern "C" {
@@ -365,6 +366,20 @@ int swm_blake2s_circuit_shape(size_t input_len, size_t* num_instance, size_t* nu
     Blake2sShape s;
     if (!blake2s_shape(input_len, &s))
         return set_err(none, SWM_ERR_INVALID_ARG, "blake2s_circuit_shape: input_len %zu (at most %zu)", input_len, (size_t)BH_MAX_INPUT_LEN);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// An integer program's circuit shape from its tape (program_shape.h: the validator; the layout is build_program's)
+int swm_program_circuit_shape(const uint8_t* tape, size_t len, size_t* num_instance, size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "program_circuit_shape: NULL output");
+    ProgramShape s;
+    const char* why = "";
+    if (!program_shape(tape, len, &s, &why)) return set_err(none, SWM_ERR_INVALID_ARG, "program_circuit_shape: %s", why);
     *num_instance = s.num_instance;
     *num_witness = s.num_witness;
     *num_constraints = s.num_constraints;

@@ -800,6 +800,58 @@ def generate_blake2s_proof(proving_key, input, rng, uncompressed=False):
     return bytes(buf[: n.value]), bytes(out_b)
 
 
+def program_circuit_shape(program):
+    """swm_program_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the circuit of an integer program — tape
+    bytes or a program.Program — what workloads.build_program emits.  Raises MarlinError(SWM_ERR_INVALID_ARG) for a tape the validator
+    refuses."""
+    tape = bytes(program.tape() if hasattr(program, "tape") else program)
+    buf = (ctypes.c_uint8 * max(1, len(tape))).from_buffer_copy(tape.ljust(1, b"\0"))
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_program_circuit_shape(buf, len(tape), ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)),
+           "swm_program_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_program_proof(proving_key, circuit, public, private, rng, uncompressed=False):
+    """swm_program_prove: the proof of workloads.ProgramSynthesizer(program, public, private) with the circuit's witness synthesised
+    on the GPU (circuit: a program.ProgramCircuit) and handed to the prover on the device.  Returns (proof bytes, output values):
+    verify with workloads.program_public_inputs(program, public, outputs).  An execution with a non-zero status (a SUB that
+    underflows, a zero divisor, a failed enforce_equal) raises with SWM_ERR_UNSATISFIED."""
+    from .program import pack_inputs, unpack_outputs
+    ctx = proving_key.ctx
+    row = pack_inputs(circuit.tape, [public], [private])
+    out_b = (ctypes.c_uint8 * max(1, circuit.layout["output_bytes"]))()
+    status = ctypes.c_uint8(0)
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    _check(ctx.lib.swm_program_prove(ctx.h, proving_key.h, circuit.h, row.ctypes.data if row.size else None, rng.h, 1 if uncompressed else 0,
+                                     out_b, ctypes.byref(status), buf, len(buf), ctypes.byref(n)), "swm_program_prove", ctx)
+    outputs = unpack_outputs(circuit.tape, np.frombuffer(bytes(out_b)[:circuit.layout["output_bytes"]], dtype=np.uint8).reshape(1, -1))[0]
+    return bytes(buf[: n.value]), outputs
+
+
+def generate_program_proofs(proving_key, circuit, public, private, rng, uncompressed=False):
+    """swm_program_prove_many: one witness pass for the batch, then one prover call per execution of status 0, in order on `rng`.
+    Returns (proofs, outputs, status): proofs[i] is the proof bytes, or None for an execution whose status byte is not 0."""
+    from .program import pack_inputs, unpack_outputs
+    ctx = proving_key.ctx
+    rows = pack_inputs(circuit.tape, public, private)
+    count = rows.shape[0]
+    if not count:
+        return [], [], []
+    cap = 4096
+    out = (ctypes.c_uint8 * (cap * count))()
+    lens = (ctypes.c_size_t * count)()
+    status = (ctypes.c_uint8 * count)()
+    out_b = np.zeros((count, circuit.layout["output_bytes"]), dtype=np.uint8)
+    _check(ctx.lib.swm_program_prove_many(ctx.h, proving_key.h, circuit.h, rows.ctypes.data if rows.size else None, count, rng.h,
+                                          1 if uncompressed else 0, out_b.ctypes.data if out_b.size else None, status, out, cap, lens),
+           "swm_program_prove_many", ctx)
+    raw = bytes(out)
+    return ([raw[cap * i:cap * i + lens[i]] if lens[i] else None for i in range(count)], unpack_outputs(circuit.tape, out_b),
+            list(status))
+
+
 def verify_proof(verifying_key, public_inputs, proof, rng):
     """src/marlin/mod.rs:79-86.  public_inputs: field elements as ints (e.g. the bit-expanded inputs of
     src/merkle_tree/simple_merkle_tree.rs:129-143)."""

@@ -2268,3 +2268,395 @@ class PedersenTransferValidation:
         build_pedersen_transfer(cs, self.generator, self.salt, self.merkle_params, self.height, self.message, self.signature,
                                 self.sender_leaf, self.sender_path, self.recipient_leaf, self.recipient_path, old_root=self.old_root,
                                 new_root=self.new_root)
+
+
+# ===================================================================================================================
+# Integer programs: the reference's gadget vocabulary (src/gadgets/{uint8,uint16,uint32,uint64,uint128,boolean}.rs behind the
+# traits of src/gadgets/traits.rs, plus ark's enforce_equal / is_eq / conditionally_select) as ONE circuit per program.  A
+# program is a straight-line TAPE of typed instructions over SSA registers; all executions of one program share it, so the
+# shape depends on the tape alone and the witness of a batch is synthesised on the GPU (csrc/program_witness.hip).
+# build_program is the layout contract of csrc/host/program_shape.h.
+#
+# The tape: a 32-byte header (magic "SWMPROG1", u32 instruction count, zeros) and 32 bytes per instruction:
+#   [0] op  [1] type  [2:4] a  [4:6] b  [6:8] c (register indices, little-endian)  [8:16] zero  [16:32] immediate (little-endian)
+# Types BOOL, U8 .. U128 (codes 0 .. 5).  Inputs come first, public then private; every instruction but ASSERT_EQ and OUTPUT
+# defines the next register.  `type` is the type of the operands (for GT .. EQ the result is BOOL).  The immediate is the value of
+# CONST, the positions of SHL / SHR / ROTL / ROTR (below 2^32), and zero elsewhere; unused operand fields are zero.
+#
+# A register is W bit references: a witness variable, an instance variable or a constant (a multiple of `one`: NO CONSTANT
+# FOLDING, an op over constants allocates what it allocates over variables), each with an optional negation.  NOT / NAND / NOR,
+# the shifts, the rotations and GTE / LTE cost nothing beyond what they negate or rewire.  With p(x) = sum 2^i x_i:
+#   instance  one, the bits of the public inputs (least significant first, declaration order), the bits of the outputs (OUTPUT
+#             order): the reference's own convention (traits.rs:150-228, simple_merkle_tree.rs:129-143)
+#   INPUT     private: W booleans, (1 - x) x = 0 each, as UInt8::new_witness                         W witnesses,      W rows
+#   AND OR    r_i:  a_i b_i = r_i;  (1 - a_i)(1 - b_i) = 1 - r_i        (NAND / NOR: the negated r)    W,              W
+#   XOR       r_i:  (2 a_i) b_i = a_i + b_i - r_i                                                   W,              W
+#   ADD       s_0 .. s_W (sum, carry), booleanity, (p(a) + p(b) - p(s)) one = 0                       W + 1,          W + 2
+#   SUB       d_0 .. d_{W-1}, booleanity, (p(a) - p(b) - p(d)) one = 0: no solution when a < b         W,              W + 1
+#   MUL       p_0 .. p_{2W-1}, booleanity, p(a) p(b) = p(p)                         (W <= 64)         2 W,            2 W + 1
+#   DIV       q, rem, t = b - 1 - rem (W bits each), booleanity, p(q) p(b) = p(a) - p(rem),
+#             (p(b) - 1 - p(rem) - p(t)) one = 0: rem < b and b != 0                (W <= 64)         3 W,            3 W + 2
+#   GT        s_0 .. s_W of a - b - 1 + 2^W, booleanity, one packing row; s_W is the answer          W + 1,          W + 2
+#             (LT swaps the operands; GTE = not LT; LTE = not GT)
+#   EQ        inv, e with z = p(a) - p(b):  z inv = 1 - e,  z e = 0                                   2,              2
+#   SELECT    r_i:  c (a_i - b_i) = r_i - b_i                                                       W,              W
+#   ASSERT_EQ (a_i - b_i) one = 0                                                                   0,              W
+#   OUTPUT    an instance variable o_i per bit, (bit_i - o_i) one = 0                                 0,              W
+# No row rests on an integer that can reach r: the widest is the 129-bit sum of ADD / GT on U128; a product is below 2^128.
+#
+# Deviations from the reference's gadgets, all towards soundness.  Its compare_ord (helpers.rs:51-76) allocates the answer as a
+# free witness; here the answer is the top bit of a range-checked difference.  Its div steers on .value() and allocates the
+# quotient freely; here q and rem are bound by q b = a - rem and rem < b.  Its shifts and rotations allocate fresh witnesses;
+# here they rewire bit references.  Its sub and div refuse at synthesis time (ensure!, uint8.rs:277, :305); here every witness is
+# computed whatever happens — an underflowing SUB writes the wrapped difference, a zero divisor q = 0, rem = a and the wrapped t —
+# and a STATUS byte says why the system is unsatisfied: bit 0 SUB underflow, bit 1 DIV by zero, bit 2 ASSERT_EQ failed.  The
+# system is satisfied exactly when the status is 0.
+# Out of scope, refused by the validator: MUL and DIV on U128 (the 256-bit product does not fit the field), Int8, Address,
+# FieldGadget, the byte conversions.  Limits: 4096 instructions, 16-bit register indices, 2^20 witnesses per item.
+# ===================================================================================================================
+PROGRAM_MAGIC = b"SWMPROG1"
+PROGRAM_WORD = 32
+PROGRAM_MAX_INSTRUCTIONS = 4096
+PROGRAM_MAX_WITNESS = 1 << 20
+PROGRAM_TYPES = ("BOOL", "U8", "U16", "U32", "U64", "U128")
+PROGRAM_OPS = ("", "INPUT_PUBLIC", "INPUT_PRIVATE", "CONST", "AND", "OR", "XOR", "NAND", "NOR", "NOT", "ADD", "SUB", "MUL", "DIV", "SHL",
+               "SHR", "ROTL", "ROTR", "GT", "GTE", "LT", "LTE", "EQ", "SELECT", "ASSERT_EQ", "OUTPUT")
+PROGRAM_OP = {name: code for code, name in enumerate(PROGRAM_OPS) if name}
+PROGRAM_STATUS_UNDERFLOW, PROGRAM_STATUS_DIV_ZERO, PROGRAM_STATUS_ASSERT = 1, 2, 4
+
+
+def program_type_width(t):
+    return 1 if t == 0 else 4 << t
+
+
+def program_type_bytes(t):
+    return 1 if t == 0 else (4 << t) // 8
+
+
+def program_word(op, t=0, a=0, b=0, c=0, imm=0):
+    """One instruction word of a tape."""
+    op = PROGRAM_OP[op] if isinstance(op, str) else op
+    return bytes([op, t]) + a.to_bytes(2, "little") + b.to_bytes(2, "little") + c.to_bytes(2, "little") + bytes(8) + imm.to_bytes(16, "little")
+
+
+def program_header(n):
+    return PROGRAM_MAGIC + n.to_bytes(4, "little") + bytes(20)
+
+
+def program_parse(program):
+    """The validator of csrc/host/program_shape.h in Python: tape bytes (or an object with .tape()) -> a list of
+    (op name, type, a, b, c, imm) and the register types.  ValueError for what the library refuses with SWM_ERR_INVALID_ARG."""
+    tape = bytes(program.tape() if hasattr(program, "tape") else program)
+    if len(tape) < PROGRAM_WORD or tape[:8] != PROGRAM_MAGIC or any(tape[12:32]):
+        raise ValueError("program: no tape header")
+    n = int.from_bytes(tape[8:12], "little")
+    if n > PROGRAM_MAX_INSTRUCTIONS or len(tape) != PROGRAM_WORD * (1 + n):
+        raise ValueError("program: %d instructions in %d bytes (at most %d)" % (n, len(tape), PROGRAM_MAX_INSTRUCTIONS))
+    ins, regs, phase, witnesses = [], [], 0, 0
+    for k in range(n):
+        w = tape[PROGRAM_WORD * (1 + k): PROGRAM_WORD * (2 + k)]
+        op, t = w[0], w[1]
+        a, b, c = (int.from_bytes(w[2 + 2 * j: 4 + 2 * j], "little") for j in range(3))
+        imm = int.from_bytes(w[16:], "little")
+        if not 1 <= op < len(PROGRAM_OPS) or t >= len(PROGRAM_TYPES) or any(w[8:16]):
+            raise ValueError("program: instruction %d: op %d, type %d" % (k, op, t))
+        name, W = PROGRAM_OPS[op], program_type_width(t)
+
+        def operands(*types):
+            given = (a, b, c)
+            for j in range(3):
+                if j < len(types):
+                    if given[j] >= len(regs) or regs[given[j]] != types[j]:
+                        raise ValueError("program: instruction %d (%s): operand %d" % (k, name, j))
+                elif given[j]:
+                    raise ValueError("program: instruction %d (%s): unused operand %d is set" % (k, name, j))
+        if name in ("INPUT_PUBLIC", "INPUT_PRIVATE"):
+            this = 1 if name == "INPUT_PUBLIC" else 2
+            if this < phase or imm:
+                raise ValueError("program: instruction %d: inputs come first, public then private" % k)
+            phase = this
+            operands()
+            witnesses += W if this == 2 else 0
+            result = t
+        else:
+            phase = 3
+            if name not in ("CONST", "SHL", "SHR", "ROTL", "ROTR") and imm:
+                raise ValueError("program: instruction %d (%s): an immediate" % (k, name))
+            if name == "CONST":
+                operands()
+                if imm >> W:
+                    raise ValueError("program: instruction %d: a constant of more than %d bits" % (k, W))
+                result = t
+            elif name in ("AND", "OR", "XOR", "NAND", "NOR"):
+                operands(t, t)
+                witnesses += W
+                result = t
+            elif name == "NOT":
+                operands(t)
+                result = t
+            elif name in ("ADD", "SUB", "MUL", "DIV"):
+                if t == 0 or (t == 5 and name in ("MUL", "DIV")):
+                    raise ValueError("program: instruction %d: %s on %s" % (k, name, PROGRAM_TYPES[t]))
+                operands(t, t)
+                witnesses += {"ADD": W + 1, "SUB": W, "MUL": 2 * W, "DIV": 3 * W}[name]
+                result = t
+            elif name in ("SHL", "SHR", "ROTL", "ROTR"):
+                if t == 0 or imm >> 32:
+                    raise ValueError("program: instruction %d: %s on %s by %d" % (k, name, PROGRAM_TYPES[t], imm))
+                operands(t)
+                result = t
+            elif name in ("GT", "GTE", "LT", "LTE"):
+                if t == 0:
+                    raise ValueError("program: instruction %d: %s on BOOL" % (k, name))
+                operands(t, t)
+                witnesses += W + 1
+                result = 0
+            elif name == "EQ":
+                operands(t, t)
+                witnesses += 2
+                result = 0
+            elif name == "SELECT":
+                operands(0, t, t)
+                witnesses += W
+                result = t
+            else:  # ASSERT_EQ, OUTPUT
+                operands(*((t, t) if name == "ASSERT_EQ" else (t,)))
+                result = None
+        if result is not None:
+            regs.append(result)
+        ins.append((name, t, a, b, c, imm))
+    if witnesses > PROGRAM_MAX_WITNESS:
+        raise ValueError("program: %d witnesses per item (at most %d)" % (witnesses, PROGRAM_MAX_WITNESS))
+    return ins, regs
+
+
+_PG_WITNESSES = {"AND": (1, 0), "OR": (1, 0), "XOR": (1, 0), "NAND": (1, 0), "NOR": (1, 0), "ADD": (1, 1), "SUB": (1, 0), "MUL": (2, 0),
+                 "DIV": (3, 0), "GT": (1, 1), "GTE": (1, 1), "LT": (1, 1), "LTE": (1, 1), "EQ": (0, 2), "SELECT": (1, 0)}
+_PG_ROWS = {"AND": (1, 0), "OR": (1, 0), "XOR": (1, 0), "NAND": (1, 0), "NOR": (1, 0), "ADD": (1, 2), "SUB": (1, 1), "MUL": (2, 1),
+            "DIV": (3, 2), "GT": (1, 2), "GTE": (1, 2), "LT": (1, 2), "LTE": (1, 2), "EQ": (0, 2), "SELECT": (1, 0), "ASSERT_EQ": (1, 0),
+            "OUTPUT": (1, 0)}
+
+
+def program_circuit_layout(program):
+    """The three counts of build_program and, per instruction, the offset of its first witness and of its first row (the per-op
+    formulas of the block comment, as csrc/host/program_shape.h states them), plus the byte sizes of an item's inputs and outputs."""
+    ins, _ = program_parse(program)
+    lay = {"witness_at": [], "row_at": [], "input_bytes": 0, "public_bytes": 0, "output_bytes": 0}
+    ni, nw, nc = 1, 0, 0
+    for name, t, a, b, c, imm in ins:
+        W = program_type_width(t)
+        lay["witness_at"].append(nw)
+        lay["row_at"].append(nc)
+        if name == "INPUT_PUBLIC":
+            ni += W
+            lay["public_bytes"] += program_type_bytes(t)
+        elif name == "INPUT_PRIVATE":
+            nw += W
+            nc += W
+        else:
+            k, extra = _PG_WITNESSES.get(name, (0, 0))
+            nw += k * W + extra
+            k, extra = _PG_ROWS.get(name, (0, 0))
+            nc += k * W + extra
+            if name == "OUTPUT":
+                ni += W
+                lay["output_bytes"] += program_type_bytes(t)
+        if name.startswith("INPUT"):
+            lay["input_bytes"] += program_type_bytes(t)
+    lay["num_instance"], lay["num_witness"], lay["num_constraints"] = ni, nw, nc
+    return lay
+
+
+def _pg_bits(v, n):
+    return [(v >> i) & 1 for i in range(n)]
+
+
+def program_public_inputs(program, public_values, outputs):
+    """The public inputs of a program's circuit (without `one`): the bits of the public input values, then the bits of the output
+    values, least significant first, in declaration / OUTPUT order."""
+    ins, _ = program_parse(program)
+    pub = [program_type_width(t) for name, t, *_ in ins if name == "INPUT_PUBLIC"]
+    out = [program_type_width(t) for name, t, *_ in ins if name == "OUTPUT"]
+    if len(pub) != len(public_values) or len(out) != len(outputs):
+        raise ValueError("program: %d public inputs and %d outputs" % (len(pub), len(out)))
+    return [b for W, v in zip(pub + out, list(public_values) + list(outputs)) for b in _pg_bits(int(v), W)]
+
+
+def build_program(cs, program, public_values=(), private_values=()):
+    """Emits the circuit of `program` (tape bytes or a simpleworks_amd.program.Program) into `cs` and computes its assignment for
+    one execution.  Returns (public inputs, output values, status byte): every witness is computed whatever the status says."""
+    ins, _ = program_parse(program)
+    one = cs.one()
+    R = R_MODULUS
+    public_values, private_values = list(public_values), list(private_values)
+    declared = [sum(1 for nm, *_ in ins if nm == kind) for kind in ("INPUT_PUBLIC", "INPUT_PRIVATE")]
+    if declared != [len(public_values), len(private_values)]:
+        raise ValueError("program: %d public and %d private inputs" % tuple(declared))
+    regs = []      # (value, [bit reference]); a bit reference: (variable or None, negated, value)
+    outputs, public, status = [], [], 0
+
+    def bit_value(b):
+        return b[2]
+
+    def lc(pairs, constant=0):
+        """sum k * bit (+ constant) as a term list, by variable in order of first appearance."""
+        acc = {}
+        if constant:
+            acc[one] = constant
+        for k, (var, neg, val) in pairs:
+            if var is None:
+                if val:
+                    acc[one] = acc.get(one, 0) + k
+            elif neg:
+                acc[one] = acc.get(one, 0) + k
+                acc[var] = acc.get(var, 0) - k
+            else:
+                acc[var] = acc.get(var, 0) + k
+        return [(c % R, v) for v, c in acc.items() if c % R]
+
+    def packed(bits, sign=1):
+        return [(sign << i, b) for i, b in enumerate(bits)]
+
+    def fresh(v):
+        return (cs.new_witness_variable(v), False, v)
+
+    def boolean(v):
+        b = fresh(v)
+        cs.enforce_constraint([(1, one), (R - 1, b[0])], [(1, b[0])], [])
+        return b
+
+    def negated(b):
+        return (b[0], not b[1], 1 - b[2])
+
+    def decompose(v, n):
+        return [boolean(x) for x in _pg_bits(v, n)]
+
+    n_pub = n_priv = 0
+    for name, t, a, b, c, imm in ins:
+        W = program_type_width(t)
+        mask = (1 << W) - 1
+        if name == "INPUT_PUBLIC":
+            v = int(public_values[n_pub]) & mask
+            n_pub += 1
+            bits = [(cs.new_input_variable(x), False, x) for x in _pg_bits(v, W)]
+            public += [x[2] for x in bits]
+            regs.append((v, bits))
+        elif name == "INPUT_PRIVATE":
+            v = int(private_values[n_priv]) & mask
+            n_priv += 1
+            regs.append((v, decompose(v, W)))
+        elif name == "CONST":
+            regs.append((imm, [(None, False, x) for x in _pg_bits(imm, W)]))
+        elif name in ("AND", "OR", "XOR", "NAND", "NOR"):
+            (va, xa), (vb, xb) = regs[a], regs[b]
+            base = name[1:] if name[0] == "N" else name
+            v = va & vb if base == "AND" else va | vb if base == "OR" else va ^ vb
+            out = []
+            for i in range(W):
+                r = fresh((v >> i) & 1)
+                if base == "AND":
+                    cs.enforce_constraint(lc([(1, xa[i])]), lc([(1, xb[i])]), lc([(1, r)]))
+                elif base == "OR":
+                    cs.enforce_constraint(lc([(1, negated(xa[i]))]), lc([(1, negated(xb[i]))]), lc([(1, negated(r))]))
+                else:
+                    cs.enforce_constraint(lc([(2, xa[i])]), lc([(1, xb[i])]), lc([(1, xa[i]), (1, xb[i]), (-1, r)]))
+                out.append(r)
+            if name[0] == "N":
+                v, out = v ^ mask, [negated(r) for r in out]
+            regs.append((v, out))
+        elif name == "NOT":
+            va, xa = regs[a]
+            regs.append((va ^ mask, [negated(x) for x in xa]))
+        elif name == "ADD":
+            (va, xa), (vb, xb) = regs[a], regs[b]
+            s = decompose(va + vb, W + 1)
+            cs.enforce_constraint(lc(packed(xa) + packed(xb) + packed(s, -1)), [(1, one)], [])
+            regs.append(((va + vb) & mask, s[:W]))
+        elif name == "SUB":
+            (va, xa), (vb, xb) = regs[a], regs[b]
+            if va < vb:
+                status |= PROGRAM_STATUS_UNDERFLOW
+            d = decompose((va - vb) & mask, W)
+            cs.enforce_constraint(lc(packed(xa) + packed(xb, -1) + packed(d, -1)), [(1, one)], [])
+            regs.append(((va - vb) & mask, d))
+        elif name == "MUL":
+            (va, xa), (vb, xb) = regs[a], regs[b]
+            p = decompose(va * vb, 2 * W)
+            cs.enforce_constraint(lc(packed(xa)), lc(packed(xb)), lc(packed(p)))
+            regs.append((va * vb & mask, p[:W]))
+        elif name == "DIV":
+            (va, xa), (vb, xb) = regs[a], regs[b]
+            if vb == 0:
+                status |= PROGRAM_STATUS_DIV_ZERO
+            vq, vr = (va // vb, va % vb) if vb else (0, va)
+            q, rem, tt = decompose(vq, W), decompose(vr, W), decompose((vb - 1 - vr) & mask, W)
+            cs.enforce_constraint(lc(packed(q)), lc(packed(xb)), lc(packed(xa) + packed(rem, -1)))
+            cs.enforce_constraint(lc(packed(xb) + packed(rem, -1) + packed(tt, -1), -1), [(1, one)], [])
+            regs.append((vq, q))
+        elif name in ("SHL", "SHR", "ROTL", "ROTR"):
+            va, xa = regs[a]
+            zero = (None, False, 0)
+            if name == "SHL":
+                out = [xa[i - imm] if i >= imm else zero for i in range(W)]
+                v = (va << imm) & mask if imm < W else 0
+            elif name == "SHR":
+                out = [xa[i + imm] if i + imm < W else zero for i in range(W)]
+                v = va >> imm if imm < W else 0
+            else:
+                k = imm % W if name == "ROTL" else (W - imm % W) % W
+                out = [xa[(i - k) % W] for i in range(W)]
+                v = ((va << k) | (va >> (W - k))) & mask
+            regs.append((v, out))
+        elif name in ("GT", "GTE", "LT", "LTE"):
+            (va, xa), (vb, xb) = (regs[a], regs[b]) if name in ("GT", "LTE") else (regs[b], regs[a])
+            s = decompose(va - vb - 1 + (1 << W), W + 1)
+            cs.enforce_constraint(lc(packed(xa) + packed(xb, -1) + packed(s, -1), (1 << W) - 1), [(1, one)], [])
+            top = s[W] if name in ("GT", "LT") else negated(s[W])
+            regs.append((top[2], [top]))
+        elif name == "EQ":
+            (va, xa), (vb, xb) = regs[a], regs[b]
+            z = lc(packed(xa) + packed(xb, -1))
+            inv = fresh(pow((va - vb) % R, -1, R) if va != vb else 0)
+            e = fresh(1 if va == vb else 0)
+            cs.enforce_constraint(z, [(1, inv[0])], lc([(1, negated(e))]))
+            cs.enforce_constraint(z, [(1, e[0])], [])
+            regs.append((e[2], [e]))
+        elif name == "SELECT":
+            (vc, xc), (va, xa), (vb, xb) = regs[a], regs[b], regs[c]
+            v = va if vc else vb
+            out = []
+            for i in range(W):
+                r = fresh((v >> i) & 1)
+                cs.enforce_constraint(lc([(1, xc[0])]), lc([(1, xa[i]), (-1, xb[i])]), lc([(1, r), (-1, xb[i])]))
+                out.append(r)
+            regs.append((v, out))
+        elif name == "ASSERT_EQ":
+            (va, xa), (vb, xb) = regs[a], regs[b]
+            if va != vb:
+                status |= PROGRAM_STATUS_ASSERT
+            for i in range(W):
+                cs.enforce_constraint(lc([(1, xa[i]), (-1, xb[i])]), [(1, one)], [])
+        else:  # OUTPUT
+            va, xa = regs[a]
+            outputs.append(va)
+            for i in range(W):
+                o = cs.new_input_variable(bit_value(xa[i]))
+                cs.enforce_constraint(lc([(1, xa[i]), (-1, (o, False, xa[i][2]))]), [(1, one)], [])
+    return public + [x for W, v in zip([program_type_width(t) for nm, t, *_ in ins if nm == "OUTPUT"], outputs) for x in _pg_bits(v, W)], outputs, status
+
+
+def program_circuit(program, public=(), private=()):
+    """The circuit of one execution as a ConstraintSystem; returns (cs, public_inputs)."""
+    cs = ConstraintSystem()
+    public_inputs, _, _ = build_program(cs, program, public, private)
+    return cs, public_inputs
+
+
+class ProgramSynthesizer:
+    """The ConstraintSynthesizer of one execution of a program, for MarlinInst.index / prove."""
+
+    def __init__(self, program, public=(), private=()):
+        self.program, self.public, self.private = program, list(public), list(private)
+
+    def generate_constraints(self, cs):
+        build_program(cs, self.program, self.public, self.private)

@@ -22,6 +22,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_pedersen_payment_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_transfer_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_pedersen_transfer_circuit { _p: [u8; 0] }
+#[repr(C)] pub struct swm_program { _p: [u8; 0] }
 
 pub const SWM_OK: c_int = 0;
 pub const SWM_ERR_UNSATISFIED: c_int = -5;
@@ -383,4 +384,19 @@ extern "C" {
                                    d_witness: *mut c_void, d_digests: *mut c_void) -> c_int;
     pub fn swm_blake2s_prove(ctx: *mut swm_ctx, pk: *const swm_pk, input: *const u8, input_len: usize, rng: *mut swm_rng,
                              flags: c_uint, digest_out: *mut u8, proof_out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    // integer programs: a tape of typed gadget ops as one circuit, its witnesses synthesised on the GPU (program_shape.h)
+    pub fn swm_program_circuit_shape(tape: *const u8, len: usize, num_instance: *mut usize, num_witness: *mut usize,
+                                     num_constraints: *mut usize) -> c_int;
+    pub fn swm_program_create(ctx: *mut swm_ctx, tape: *const u8, len: usize, out: *mut *mut swm_program) -> c_int;
+    pub fn swm_program_destroy(ctx: *mut swm_ctx, program: *mut swm_program);
+    pub fn swm_program_witness(ctx: *mut swm_ctx, program: *const swm_program, inputs: *const u8, count: usize, witness: *mut u64,
+                               outputs: *mut u8, status: *mut u8) -> c_int;
+    pub fn swm_program_witness_dev(ctx: *mut swm_ctx, program: *const swm_program, d_inputs: *const c_void, count: usize,
+                                   d_witness: *mut c_void, d_outputs: *mut c_void, d_status: *mut c_void) -> c_int;
+    pub fn swm_program_prove(ctx: *mut swm_ctx, pk: *const swm_pk, program: *const swm_program, input: *const u8, rng: *mut swm_rng,
+                             flags: c_uint, output: *mut u8, status_out: *mut u8, proof_out: *mut u8, cap: usize,
+                             len: *mut usize) -> c_int;
+    pub fn swm_program_prove_many(ctx: *mut swm_ctx, pk: *const swm_pk, program: *const swm_program, inputs: *const u8, count: usize,
+                                  rng: *mut swm_rng, flags: c_uint, outputs: *mut u8, status: *mut u8, proofs_out: *mut u8,
+                                  proof_cap: usize, lens: *mut usize) -> c_int;
 }
