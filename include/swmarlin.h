@@ -1092,6 +1092,10 @@ int swm_profile_json(swm_ctx *ctx, char *buf, size_t buflen);
 /* the device-buffer exchanges of the sharded transform over whatever sharding the context has: alltoall != 0 — chunk c of
  * d_send (bytes_per_peer bytes) to rank c, chunk i of d_recv from rank i; else an all-gather of bytes_per_peer bytes */
 int swm_selftest_exchange(swm_ctx *ctx, const void *d_send, void *d_recv, size_t bytes_per_peer, int alltoall);
+/* Exists for tests: the most witness bytes the host forms of the circuit units (swm_*_witness, _witness_at, _prove_many*) hold on
+ * this context's device at a time, 1 GiB by default; a larger batch goes through in chunks.  A small value puts a chunk seam
+ * inside a small batch: a chunk is floor(bytes / witness bytes of one item) items, at least one.  bytes = 0 restores the default. */
+int swm_selftest_witness_stage(swm_ctx *ctx, size_t bytes);
 int swm_selftest_mul(swm_ctx *ctx, int which, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);
 /* out[i] = jacobian(a[i] (+) b[i]) with a, b affine (n x 12 limbs): exercises the mixed/XYZZ adders incl. doubling. */
 int swm_selftest_g1_add(swm_ctx *ctx, const uint64_t *a_xy, const uint64_t *b_xy, uint64_t *out_jac, size_t n);

@@ -1,5 +1,6 @@
 """ctypes binding of libswmarlin.so (include/swmarlin.h).  The product path: every call here ends in a
 hand-written gfx950 kernel.  Missing library or missing GPU is an error, never a silent fallback."""
+import contextlib
 import ctypes
 import json
 import os
@@ -242,6 +243,7 @@ ABI = {
     "swm_profile_enable": (_int, [_vp, _int]),
     "swm_profile_reset": (_int, [_vp]),
     "swm_profile_json": (_int, [_vp, ctypes.c_char_p, _sz]),
+    "swm_selftest_witness_stage": (_int, [_vp, _sz]),
     "swm_selftest_mul": (_int, [_vp, _int, _u64p, _u64p, _u64p, _sz]),
     "swm_selftest_g1_add": (_int, [_vp, _u64p, _u64p, _u64p, _sz]),
     "swm_selftest_g1_codec": (_int, [_vp, _int, ctypes.c_void_p, _sz, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint)]),
@@ -1443,6 +1445,16 @@ class Context:
                                                    _p64(spec), spec.shape[0], self.MSM_DEFER[defer_tail], pipe_min, _p64(out),
                                                    _p64(twins)), "swm_selftest_msm_jobs")
         return out[:spec.shape[0]], int(twins[0])
+
+    @contextlib.contextmanager
+    def selftest_witness_stage(self, nbytes):
+        """swm_selftest_witness_stage for the length of a `with` block: the circuit units' host forms hold at most `nbytes` of
+        witnesses on the device at a time, the default (1 GiB) again afterwards.  For tests that put a chunk seam inside a small batch."""
+        self._check(self.lib.swm_selftest_witness_stage(self.h, nbytes), "swm_selftest_witness_stage")
+        try:
+            yield
+        finally:
+            self.lib.swm_selftest_witness_stage(self.h, 0)
 
     def selftest_sample_fr(self, rng, need):
         """sample_fr_bulk on a generator handle (simpleworks_amd.marlin.Rng): need x 4 uint64, Montgomery form."""

@@ -23,6 +23,7 @@
 #include "ff.cuh"
 #include "host/blake2s_shape.h"
 #include "swmarlin.h"
+#include "witness_host.h"
 
 namespace swm {
 
@@ -100,19 +101,10 @@ static int blake2s_shape_or_err(swm_ctx* ctx, const char* what, size_t input_len
     return SWM_OK;
 }
 
-// The host form holds at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
-static constexpr size_t BW_STAGE_BYTES = (size_t)1 << 30;
-
-static int bw_drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
-    if (rc != SWM_OK) drain_streams(ctx);
-    return rc;
-}
-
 static int blake2s_witness_host(swm_ctx* ctx, const Blake2sShape& s, const uint8_t* inputs, size_t count, uint64_t* witness, uint8_t* digests) {
     const size_t item = s.num_witness * sizeof(Fr), len = s.input_len;
-    const size_t per = BW_STAGE_BYTES / item ? BW_STAGE_BYTES / item : 1;  // items per chunk
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
+    for (const WitnessChunk ch : WitnessChunks(witness_stage_items(ctx, item), count)) {
+        const size_t base = ch.base, n = ch.count;
         uint8_t *d_in = nullptr, *d_out = nullptr;
         SWM_TRY(scratch(ctx, "stage.a", n * len + 32, (void**)&d_in));
         SWM_TRY(scratch(ctx, "blake2s.w", n * item + 32 * n, (void**)&d_out));
@@ -160,7 +152,7 @@ int swm_blake2s_witness_dev(swm_ctx* ctx, const void* d_inputs, size_t input_len
     if (((uintptr_t)d_witness & 15) || ((uintptr_t)d_inputs & 3) || ((uintptr_t)d_digests & 3))
         return set_err(ctx, SWM_ERR_INVALID_ARG, "blake2s_witness: the witness must be 16-byte aligned, inputs and digests 4-byte aligned");
     SWM_ON_DEVICE(ctx);
-    return bw_drained(ctx, blake2s_witness_run(ctx, s, d_inputs, count, d_witness, d_digests));
+    return drained(ctx, blake2s_witness_run(ctx, s, d_inputs, count, d_witness, d_digests));
 }
 
 int swm_blake2s_witness(swm_ctx* ctx, const uint8_t* inputs, size_t input_len, size_t count, uint64_t* witness, uint8_t* digests) {
@@ -171,7 +163,7 @@ int swm_blake2s_witness(swm_ctx* ctx, const uint8_t* inputs, size_t input_len, s
     if (!count) return SWM_OK;
     if (count > 0x7FFFFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "blake2s_witness: %zu items in one call", count);
     SWM_ON_DEVICE(ctx);
-    return bw_drained(ctx, blake2s_witness_host(ctx, s, inputs, count, witness, digests));
+    return drained(ctx, blake2s_witness_host(ctx, s, inputs, count, witness, digests));
 }
 
 int swm_blake2s_prove(swm_ctx* ctx, const swm_pk* pk, const uint8_t* input, size_t input_len, swm_rng* rng, unsigned flags,
@@ -184,22 +176,11 @@ int swm_blake2s_prove(swm_ctx* ctx, const swm_pk* pk, const uint8_t* input, size
     uint8_t digest[32];
     {
         SWM_ON_DEVICE(ctx);
-        SWM_TRY(bw_drained(ctx, blake2s_witness_one(ctx, s, input, &d_w, digest)));
+        SWM_TRY(drained(ctx, blake2s_witness_one(ctx, s, input, &d_w, digest)));
     }
     const Fr inst[3] = {fp_one<Fr>(), bw_half(digest), bw_half(digest + 16)};  // one, lo, hi
     memcpy(digest_out, digest, 32);
-    swm_r1cs cs = {};
-    cs.num_instance = s.num_instance;
-    cs.num_witness = s.num_witness;
-    cs.num_constraints = s.num_constraints;
-    cs.instance = reinterpret_cast<const uint64_t*>(inst);
-    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
-    struct DevWitnessScope {
-        swm_ctx* c;
-        ~DevWitnessScope() { c->witness_dev = nullptr; }
-    } scope{ctx};
-    ctx->witness_dev = d_w;
-    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+    return prove_device_witness(ctx, pk, s.num_instance, s.num_witness, s.num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
 }
 
 }  // extern "C"

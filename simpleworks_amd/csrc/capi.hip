@@ -881,6 +881,11 @@ int swm_profile_json(swm_ctx* ctx, char* buf, size_t buflen) {
 }
 
 // ------------------------------------------------------------------------------------------------ self-tests
+int swm_selftest_witness_stage(swm_ctx* ctx, size_t bytes) {
+    if (!ctx) return SWM_ERR_INVALID_ARG;
+    ctx->witness_stage_bytes = bytes ? bytes : WITNESS_STAGE_BYTES;
+    return SWM_OK;
+}
 int swm_selftest_exchange(swm_ctx* ctx, const void* d_send, void* d_recv, size_t bytes_per_peer, int alltoall) {
     if (!ctx || !d_send || !d_recv) return SWM_ERR_INVALID_ARG;
     SWM_ON_DEVICE(ctx);

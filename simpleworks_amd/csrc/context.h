@@ -9,6 +9,7 @@
 #include <vector>
 #include "../../include/swmarlin.h"
 #include "host/pool.h"
+#include "host/witness_chunks.h"
 #include "switches.h"
 
 namespace swm {
@@ -59,8 +60,11 @@ struct swm_ctx {
     void* h2d_stage = nullptr;   // small pinned staging area for the witness upload of small proofs (marlin.hip, upload_small)
     size_t h2d_stage_used = 0;
     // device source of the witness for the NEXT proof on this context (upload_witness copies from it instead of from
-    // swm_r1cs::witness); set and cleared by swm_merkle_prove around its call of the prover, null everywhere else
+    // swm_r1cs::witness); set and cleared by prove_device_witness (witness_host.h) around its call of the prover, null everywhere else
     const void* witness_dev = nullptr;
+    // the most witness bytes a circuit unit's host form holds on the device at a time (witness_host.h); moved by
+    // swm_selftest_witness_stage alone, so that a test can put a chunk seam inside a small batch
+    size_t witness_stage_bytes = swm::WITNESS_STAGE_BYTES;
     hipEvent_t slot_event[MSM_SLOTS] = {nullptr};
     bool slot_busy[MSM_SLOTS] = {false};  // enqueued and not yet collected by msm_finish
     hipEvent_t acc_event[MSM_SLOTS] = {nullptr};  // "partial sums ready" per slot (stage A -> stage T, deferred bucket stages)

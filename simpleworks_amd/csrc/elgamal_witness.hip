@@ -38,6 +38,7 @@
 #include "frinv.cuh"
 #include "host/elgamal_shape.h"
 #include "swmarlin.h"
+#include "witness_host.h"
 
 struct swm_elgamal_circuit {
     const swm_elgamal* params = nullptr;
@@ -290,9 +291,6 @@ static int elgamal_stage_inputs(swm_ctx* ctx, const uint8_t* keys, const uint8_t
     return SWM_OK;
 }
 
-// The host form holds at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
-static constexpr size_t EW_STAGE_BYTES = (size_t)1 << 30;
-
 static int elgamal_witness_host(swm_ctx* ctx, const swm_elgamal_circuit* c, const swm_elgamal_key* key, const uint8_t* keys, const uint8_t* msgs,
                                 const uint8_t* rs, size_t count, uint64_t* witness, uint8_t* cts, const char* what) {
     if (!ctx || !c || (count && (!msgs || !rs || !witness || !cts || (!key && !keys)))) return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: bad arguments", what);
@@ -301,9 +299,8 @@ static int elgamal_witness_host(swm_ctx* ctx, const swm_elgamal_circuit* c, cons
     SWM_TRY(elgamal_check_points(ctx, what, "message", msgs, count));
     SWM_ON_DEVICE(ctx);
     const size_t item = EW_NUM_WITNESS * sizeof(Fr);
-    const size_t per = EW_STAGE_BYTES / item;  // encryptions per chunk
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
+    for (const WitnessChunk ch : WitnessChunks(witness_stage_items(ctx, item), count)) {
+        const size_t base = ch.base, n = ch.count;
         const uint8_t *d_keys, *d_msgs, *d_rs;
         SWM_TRY(elgamal_stage_inputs(ctx, key ? nullptr : keys + 64 * base, msgs + 64 * base, rs + 32 * base, n, &d_keys, &d_msgs, &d_rs));
         uint8_t* d_out = nullptr;
@@ -358,18 +355,7 @@ static int elgamal_prove(swm_ctx* ctx, const swm_pk* pk, const swm_elgamal_circu
         if (!sv_canonical(wds, &inst[1 + j])) return set_err(ctx, SWM_ERR_INTERNAL, "%s: a coordinate of the instance is not canonical", what);
     }
     memcpy(ciphertext_out, ct, 128);
-    swm_r1cs cs = {};
-    cs.num_instance = s.num_instance;
-    cs.num_witness = s.num_witness;
-    cs.num_constraints = s.num_constraints;
-    cs.instance = reinterpret_cast<const uint64_t*>(inst);
-    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
-    struct DevWitnessScope {
-        swm_ctx* c;
-        ~DevWitnessScope() { c->witness_dev = nullptr; }
-    } scope{ctx};
-    ctx->witness_dev = d_w;
-    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+    return prove_device_witness(ctx, pk, s.num_instance, s.num_witness, s.num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
 }
 
 }  // namespace swm
@@ -388,10 +374,7 @@ int swm_elgamal_circuit_create(swm_ctx* ctx, const swm_elgamal* params, swm_elga
 }
 
 void swm_elgamal_circuit_destroy(swm_ctx* ctx, swm_elgamal_circuit* c) {
-    if (!c) return;
-    DeviceGuard guard(ctx);
-    if (ctx) drain_streams(ctx);
-    delete c;
+    destroy_circuit(ctx, c);
 }
 
 int swm_elgamal_witness(swm_ctx* ctx, const swm_elgamal_circuit* c, const uint8_t* public_keys_xy, const uint8_t* messages_xy,

@@ -1,13 +1,11 @@
 // pedersen_transfer_shape.h — the SHAPE of the transfer circuit over a Pedersen account tree (simpleworks_amd/workloads.py,
 // build_pedersen_transfer): transfer_shape.h's statement (old_root -> new_root, R1 between them) over the sections of
-// pedersen_payment_shape.h, and the plan by which a block of transfers is cut into witness chunks.  Plain C++, no GPU headers, no
-// library state: shared by host_abi.inc (swm_pedersen_transfer_circuit_shape), by pedersen_transfer_witness.hip (which lays the witness
-// vector out by these offsets and cuts a block by this plan) and by tests/native/pedersen_transfer_shape_check.cpp.
+// pedersen_payment_shape.h.  Plain C++, no GPU headers, no library state: shared by host_abi.inc
+// (swm_pedersen_transfer_circuit_shape), by pedersen_transfer_witness.hip (which lays the witness vector out by these offsets; a block
+// is cut into chunks by witness_chunks.h) and by tests/native/pedersen_transfer_shape_check.cpp.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-
-#include <vector>
 
 #include "pedersen_payment_shape.h"
 
@@ -30,7 +28,6 @@ static constexpr size_t PT_UPDATE_LEVEL_ROWS = MW_LEVEL_ROWS - 1;            // 
 static constexpr size_t PT_UPDATE_LEVEL_BITS_AT = MW_LEVEL_BITS_AT - 2;      // 1: after left'
 static constexpr size_t PT_UPDATE_LEVEL_ADDS_AT = MW_LEVEL_ADDS_AT - 2;      // 513
 static constexpr size_t PT_BIT_WITNESSES = 3 * PP_AMOUNT_BITS + PP_LEAF_BITS + 1;  // 769: balance, diff, sum, recipient bits, r1
-static constexpr size_t PT_STAGE_BYTES = (size_t)1 << 30;  // the witnesses of one chunk held on the device at a time
 
 struct PedersenTransferShape {
     size_t height = 0, levels = 0;
@@ -80,35 +77,6 @@ inline bool pedersen_transfer_shape(size_t height, bool salted, PedersenTransfer
     s.new_root_row = s.sum_pack_row + s.update_rows;
     s.num_constraints = s.new_root_row + 1;
     *out = s;
-    return true;
-}
-
-// A block of transfers goes through the device in chunks, IN ORDER: transfer i + 1 is witnessed against the state transfer i left.
-struct PtChunk {
-    size_t base = 0, count = 0;  // transfers [base, base + count)
-};
-
-// How many transfers of `item_bytes` witness bytes each fit `cap_bytes`: at least one (a single transfer is never refused for its
-// size).  0: item_bytes = 0.
-inline size_t pedersen_transfer_chunk_items(size_t item_bytes, size_t cap_bytes) {
-    if (item_bytes == 0) return 0;
-    const size_t per = cap_bytes / item_bytes;
-    return per ? per : 1;
-}
-
-// The chunk list of a block of `count` transfers: consecutive, in order, every chunk but the last full.  count = 0 gives no
-// chunk.  false: item_bytes = 0.
-inline bool pedersen_transfer_plan(size_t item_bytes, size_t count, size_t cap_bytes, std::vector<PtChunk>* out) {
-    out->clear();
-    const size_t per = pedersen_transfer_chunk_items(item_bytes, cap_bytes);
-    if (per == 0) return false;
-    for (size_t base = 0; base < count;) {
-        PtChunk c;
-        c.base = base;
-        c.count = count - base < per ? count - base : per;
-        out->push_back(c);
-        base += c.count;
-    }
     return true;
 }
 

@@ -25,6 +25,7 @@
 #include "merkle_stage.cuh"
 #include "pedersen.h"
 #include "swmarlin.h"
+#include "witness_host.h"
 
 struct swm_merkle_circuit {
     const swm_pedersen* leaf = nullptr;
@@ -229,11 +230,9 @@ int swm_merkle_circuit_create(swm_ctx* ctx, const swm_pedersen* leaf, const swm_
 }
 
 void swm_merkle_circuit_destroy(swm_ctx* ctx, swm_merkle_circuit* c) {
-    if (!c) return;
-    DeviceGuard guard(ctx);
-    if (ctx) drain_streams(ctx);
-    if (c->d_ops) (void)hipFree(c->d_ops);
-    delete c;
+    destroy_circuit(ctx, c, [](swm_merkle_circuit* m) {
+        if (m->d_ops) (void)hipFree(m->d_ops);
+    });
 }
 
 int swm_merkle_witness_dev(swm_ctx* ctx, const swm_merkle_circuit* c, const void* d_leaves, const void* d_indices, const void* d_siblings,
@@ -289,18 +288,7 @@ int swm_merkle_prove(swm_ctx* ctx, const swm_pk* pk, const swm_merkle_circuit* c
     for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)root[4 * i] | (uint32_t)root[4 * i + 1] << 8 | (uint32_t)root[4 * i + 2] << 16 | (uint32_t)root[4 * i + 3] << 24;
     inst[1] = fp_from_std(r);
     for (int i = 0; i < 8; i++) inst[2 + i] = (leaf >> i) & 1 ? fp_one<Fr>() : fp_zero<Fr>();
-    swm_r1cs cs = {};
-    cs.num_instance = s.num_instance;
-    cs.num_witness = s.num_witness;
-    cs.num_constraints = s.num_constraints;
-    cs.instance = reinterpret_cast<const uint64_t*>(inst);
-    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
-    struct DevWitnessScope {
-        swm_ctx* c;
-        ~DevWitnessScope() { c->witness_dev = nullptr; }
-    } scope{ctx};
-    ctx->witness_dev = d_w;
-    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+    return prove_device_witness(ctx, pk, s.num_instance, s.num_witness, s.num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
 }
 
 }  // extern "C"

@@ -33,6 +33,7 @@
 #include "poseidon_tree.h"
 #include "schnorr.h"
 #include "swmarlin.h"
+#include "ledger_witness_host.h"
 #include "witness_runs.h"
 
 struct swm_payment_circuit {
@@ -206,11 +207,6 @@ static int py_check_tree(swm_ctx* ctx, const char* what, const swm_payment_circu
     return SWM_OK;
 }
 
-int py_drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
-    if (rc != SWM_OK) drain_streams(ctx);
-    return rc;
-}
-
 // signatures | sender leaves | recipient leaves | the two sibling arrays | messages of n payments into "stage.a": all but the
 // messages stay word-aligned
 int py_stage(swm_ctx* ctx, size_t levels, const uint8_t* msgs, const uint8_t* sigs, const uint8_t* sender_leaves,
@@ -250,56 +246,13 @@ int py_out(swm_ctx* ctx, size_t num_witness, size_t n, PyOut* out) {
     return SWM_OK;
 }
 
-// n payments staged and run; the results stay in "payment.w"
-static int py_chunk(swm_ctx* ctx, const swm_payment_circuit* c, const swm_poseidon_tree* tree, const uint8_t* msgs, const uint8_t* sigs,
-                    const uint8_t* sender_leaves, const uint8_t* recipient_leaves, const uint8_t* sender_sib, const uint8_t* recipient_sib, size_t n,
-                    PyOut* out) {
-    PyStaged in;
-    SWM_TRY(py_stage(ctx, c->shape.levels, msgs, sigs, sender_leaves, recipient_leaves, sender_sib, recipient_sib, n, &in));
-    SWM_TRY(py_out(ctx, c->shape.num_witness, n, out));
-    return py_run(ctx, c, tree, in.msgs, in.sigs, in.sender_leaves, in.recipient_leaves, in.sender_sib, in.recipient_sib, n, out->w, out->flags,
-                  out->status, out->roots_s, out->roots_r);
-}
-
-static int py_host(swm_ctx* ctx, const swm_payment_circuit* c, const swm_poseidon_tree* tree, const uint8_t* msgs, const uint8_t* sigs,
-                   const uint8_t* sender_leaves, const uint8_t* recipient_leaves, const uint8_t* sender_sib, const uint8_t* recipient_sib,
-                   size_t count, uint64_t* witness, uint8_t* flags, uint8_t* sender_roots, uint8_t* recipient_roots) {
-    const PaymentShape& s = c->shape;
-    const size_t item = s.num_witness * sizeof(Fr), sib = s.levels * 32;
-    const size_t per = PY_STAGE_BYTES / item ? PY_STAGE_BYTES / item : 1;  // payments per chunk
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
-        PyOut o;
-        SWM_TRY(py_chunk(ctx, c, tree, msgs + PY_MSG_LEN * base, sigs + 64 * base, sender_leaves + PY_LEAF_LEN * base,
-                         recipient_leaves + PY_LEAF_LEN * base, sender_sib ? sender_sib + sib * base : nullptr,
-                         recipient_sib ? recipient_sib + sib * base : nullptr, n, &o));
-        SWM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t*>(witness) + base * item, o.w, n * item, hipMemcpyDeviceToHost, ctx->stream));
-        if (flags) SWM_HIP(ctx, hipMemcpyAsync(flags + base, o.flags, n, hipMemcpyDeviceToHost, ctx->stream));
-        if (sender_roots) SWM_HIP(ctx, hipMemcpyAsync(sender_roots + 32 * base, o.roots_s, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-        if (recipient_roots) SWM_HIP(ctx, hipMemcpyAsync(recipient_roots + 32 * base, o.roots_r, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-        SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffers are reused by the next chunk
-    }
-    return SWM_OK;
-}
-
 // the prover over item `i` of a chunk's device witnesses; public input one, root, sender, recipient, amount
 int py_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size_t num_constraints, const Fr& root_mont, const uint8_t* msg,
                   const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
     uint64_t amount = 0;
     for (int k = 0; k < 8; k++) amount |= (uint64_t)msg[2 + k] << (8 * k);
     const Fr inst[5] = {fp_one<Fr>(), root_mont, fp_from_u64<Fr>(msg[0]), fp_from_u64<Fr>(msg[1]), fp_from_u64<Fr>(amount)};
-    swm_r1cs cs = {};
-    cs.num_instance = 5;
-    cs.num_witness = num_witness;
-    cs.num_constraints = num_constraints;
-    cs.instance = reinterpret_cast<const uint64_t*>(inst);
-    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
-    struct DevWitnessScope {
-        swm_ctx* c;
-        ~DevWitnessScope() { c->witness_dev = nullptr; }
-    } scope{ctx};
-    ctx->witness_dev = d_w;
-    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+    return prove_device_witness(ctx, pk, 5, num_witness, num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
 }
 
 // the root of a resident tree (its last node, d_root) in Montgomery form; synchronises the stream
@@ -312,6 +265,15 @@ int py_root_mont(swm_ctx* ctx, const uint8_t* d_root, Fr* root_mont) {
     *root_mont = fp_from_std(r);
     return SWM_OK;
 }
+
+struct PaymentUnit {  // what ledger_witness_host.h drives
+    using Circuit = swm_payment_circuit;
+    using Tree = swm_poseidon_tree;
+    static constexpr const char* name = "payment";
+    static constexpr auto run = py_run;
+    static constexpr auto check_tree = py_check_tree;
+    static const uint8_t* root_node(const Tree* t) { return t->d_nodes + 32 * (t->num_nodes() - 1); }
+};
 
 }  // namespace swm
 
@@ -335,115 +297,42 @@ int swm_payment_circuit_create(swm_ctx* ctx, const swm_schnorr* schnorr, const s
     return SWM_OK;
 }
 
-void swm_payment_circuit_destroy(swm_ctx* ctx, swm_payment_circuit* c) {
-    if (!c) return;
-    DeviceGuard guard(ctx);
-    if (ctx) drain_streams(ctx);
-    delete c;
-}
+void swm_payment_circuit_destroy(swm_ctx* ctx, swm_payment_circuit* c) { destroy_circuit(ctx, c); }
 
 int swm_payment_witness(swm_ctx* ctx, const swm_payment_circuit* c, const uint8_t* messages, const uint8_t* signatures,
                         const uint8_t* sender_leaves, const uint8_t* recipient_leaves, const uint8_t* sender_siblings,
                         const uint8_t* recipient_siblings, size_t count, uint64_t* witness, uint8_t* flags, uint8_t* sender_roots,
                         uint8_t* recipient_roots) {
-    if (!ctx || !c || (count && (!messages || !signatures || !sender_leaves || !recipient_leaves || !sender_siblings || !recipient_siblings || !witness)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_witness: bad arguments");
-    if (!count) return SWM_OK;
-    SWM_TRY(py_check(ctx, "payment_witness", c->shape.height, messages, sender_leaves, sender_siblings, recipient_siblings, count));
-    SWM_ON_DEVICE(ctx);
-    return py_drained(ctx, py_host(ctx, c, nullptr, messages, signatures, sender_leaves, recipient_leaves, sender_siblings, recipient_siblings,
-                                   count, witness, flags, sender_roots, recipient_roots));
+    return payment_witness<PaymentUnit>(ctx, c, messages, signatures, sender_leaves, recipient_leaves, sender_siblings, recipient_siblings, count,
+                                        witness, flags, sender_roots, recipient_roots);
 }
 
 int swm_payment_witness_at(swm_ctx* ctx, const swm_payment_circuit* c, const swm_poseidon_tree* tree, const uint8_t* messages,
                            const uint8_t* signatures, const uint8_t* sender_leaves, const uint8_t* recipient_leaves, size_t count,
                            uint64_t* witness, uint8_t* flags) {
-    if (!ctx || !c || !tree || (count && (!messages || !signatures || !sender_leaves || !recipient_leaves || !witness)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_witness_at: bad arguments");
-    SWM_TRY(py_check_tree(ctx, "payment_witness_at", c, tree));
-    if (!count) return SWM_OK;
-    SWM_TRY(py_check(ctx, "payment_witness_at", c->shape.height, messages, sender_leaves, nullptr, nullptr, count));
-    SWM_ON_DEVICE(ctx);
-    return py_drained(ctx, py_host(ctx, c, tree, messages, signatures, sender_leaves, recipient_leaves, nullptr, nullptr, count, witness, flags,
-                                   nullptr, nullptr));
+    return payment_witness_at<PaymentUnit>(ctx, c, tree, messages, signatures, sender_leaves, recipient_leaves, count, witness, flags);
 }
 
 int swm_payment_witness_dev(swm_ctx* ctx, const swm_payment_circuit* c, const swm_poseidon_tree* tree, const void* d_messages,
                             const void* d_signatures, const void* d_sender_leaves, const void* d_recipient_leaves,
                             const void* d_sender_siblings, const void* d_recipient_siblings, size_t count, void* d_witness, void* d_flags,
                             void* d_status, void* d_sender_roots, void* d_recipient_roots) {
-    if (!ctx || !c || (count && (!d_messages || !d_signatures || !d_sender_leaves || !d_recipient_leaves || !d_witness || !d_flags || !d_status)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_witness_dev: bad arguments");
-    if (count && !tree && (!d_sender_siblings || !d_recipient_siblings))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_witness_dev: neither a tree nor two sibling arrays");
-    if (tree) SWM_TRY(py_check_tree(ctx, "payment_witness_dev", c, tree));
-    if (((uintptr_t)d_signatures | (uintptr_t)d_sender_siblings | (uintptr_t)d_recipient_siblings | (uintptr_t)d_status |
-         (uintptr_t)d_sender_roots | (uintptr_t)d_recipient_roots) & 3 || ((uintptr_t)d_witness & 15))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_witness_dev: signatures, siblings, status and roots must be 4-byte aligned, the "
-                       "witness 16-byte aligned");
-    SWM_ON_DEVICE(ctx);
-    return py_run(ctx, c, tree, (const uint8_t*)d_messages, (const uint8_t*)d_signatures, (const uint8_t*)d_sender_leaves,
-                  (const uint8_t*)d_recipient_leaves, (const uint8_t*)d_sender_siblings, (const uint8_t*)d_recipient_siblings, count, (Fr*)d_witness,
-                  (uint8_t*)d_flags, (uint32_t*)d_status, (uint32_t*)d_sender_roots, (uint32_t*)d_recipient_roots);
+    return payment_witness_dev<PaymentUnit>(ctx, c, tree, d_messages, d_signatures, d_sender_leaves, d_recipient_leaves, d_sender_siblings,
+                                            d_recipient_siblings, count, d_witness, d_flags, d_status, d_sender_roots, d_recipient_roots);
 }
 
 int swm_payment_prove_at(swm_ctx* ctx, const swm_pk* pk, const swm_payment_circuit* c, const swm_poseidon_tree* tree, const uint8_t message[10],
                          const uint8_t signature[64], const uint8_t sender_leaf[72], const uint8_t recipient_leaf[72], swm_rng* rng,
                          unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
-    if (!ctx || !pk || !c || !tree || !message || !signature || !sender_leaf || !recipient_leaf || !rng || !proof_out || !len)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_prove_at: bad arguments");
-    SWM_TRY(py_check_tree(ctx, "payment_prove_at", c, tree));
-    SWM_TRY(py_check(ctx, "payment_prove_at", c->shape.height, message, sender_leaf, nullptr, nullptr, 1));
-    PyOut o;
-    Fr root;
-    {
-        SWM_ON_DEVICE(ctx);
-        SWM_TRY(py_drained(ctx, py_chunk(ctx, c, tree, message, signature, sender_leaf, recipient_leaf, nullptr, nullptr, 1, &o)));
-        // its synchronisation: the inputs were staged from the caller's buffers
-        SWM_TRY(py_root_mont(ctx, tree->d_nodes + 32 * (tree->num_nodes() - 1), &root));
-    }
-    return py_prove_item(ctx, pk, c->shape.num_witness, c->shape.num_constraints, root, message, o.w, rng, flags, proof_out, cap, len);
+    return payment_prove_at<PaymentUnit>(ctx, pk, c, tree, message, signature, sender_leaf, recipient_leaf, rng, flags, proof_out, cap, len);
 }
 
 int swm_payment_prove_many_at(swm_ctx* ctx, const swm_pk* pk, const swm_payment_circuit* c, const swm_poseidon_tree* tree,
                               const uint8_t* messages, const uint8_t* signatures, const uint8_t* sender_leaves, const uint8_t* recipient_leaves,
                               size_t count, swm_rng* rng, unsigned flags, uint8_t* proofs_out, size_t proof_cap, size_t* lens,
                               uint8_t* item_flags) {
-    if (!ctx || !pk || !c || !tree || !rng || (count && (!messages || !signatures || !sender_leaves || !recipient_leaves || !proofs_out || !lens ||
-                                                         !item_flags)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "payment_prove_many_at: bad arguments");
-    SWM_TRY(py_check_tree(ctx, "payment_prove_many_at", c, tree));
-    if (!count) return SWM_OK;
-    SWM_TRY(py_check(ctx, "payment_prove_many_at", c->shape.height, messages, sender_leaves, nullptr, nullptr, count));
-    const PaymentShape& s = c->shape;
-    const size_t item = s.num_witness * sizeof(Fr);
-    const size_t per = PY_STAGE_BYTES / item ? PY_STAGE_BYTES / item : 1;
-    for (size_t i = 0; i < count; i++) {  // whatever ends the call, every entry of the two arrays has been written
-        lens[i] = 0;
-        item_flags[i] = 0;
-    }
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
-        PyOut o;
-        Fr root;
-        {
-            SWM_ON_DEVICE(ctx);
-            SWM_TRY(py_drained(ctx, py_chunk(ctx, c, tree, messages + PY_MSG_LEN * base, signatures + 64 * base, sender_leaves + PY_LEAF_LEN * base,
-                                             recipient_leaves + PY_LEAF_LEN * base, nullptr, nullptr, n, &o)));
-            SWM_HIP(ctx, hipMemcpyAsync(item_flags + base, o.flags, n, hipMemcpyDeviceToHost, ctx->stream));
-            SWM_TRY(py_root_mont(ctx, tree->d_nodes + 32 * (tree->num_nodes() - 1), &root));
-        }
-        for (size_t i = 0; i < n; i++) {
-            if (item_flags[base + i] != 3) continue;  // reported, not proved: its system is unsatisfied
-            size_t len = 0;
-            const int rc = py_prove_item(ctx, pk, s.num_witness, s.num_constraints, root, messages + PY_MSG_LEN * (base + i), o.w + i * s.num_witness,
-                                         rng, flags, proofs_out + (base + i) * proof_cap, proof_cap, &len);
-            if (rc == SWM_ERR_UNSATISFIED) continue;  // flags 3 and a leaf that is not the tree's: no proof, lens stays 0, the block goes on
-            if (rc != SWM_OK) return rc;
-            lens[base + i] = len;
-        }
-    }
-    return SWM_OK;
+    return payment_prove_many_at<PaymentUnit>(ctx, pk, c, tree, messages, signatures, sender_leaves, recipient_leaves, count, rng, flags,
+                                              proofs_out, proof_cap, lens, item_flags);
 }
 
 }  // extern "C"

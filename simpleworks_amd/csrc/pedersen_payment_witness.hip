@@ -42,6 +42,7 @@
 #include "pedersen.h"
 #include "schnorr.h"
 #include "swmarlin.h"
+#include "ledger_witness_host.h"
 #include "witness_runs.h"
 
 struct swm_pedersen_payment_circuit {
@@ -261,39 +262,16 @@ static int pp_check_tree(swm_ctx* ctx, const char* what, const swm_pedersen_paym
     return SWM_OK;
 }
 
-// n payments staged and run; the results stay in "payment.w"
-static int pp_chunk(swm_ctx* ctx, const swm_pedersen_payment_circuit* c, const swm_merkle_tree* tree, const uint8_t* msgs, const uint8_t* sigs,
-                    const uint8_t* sender_leaves, const uint8_t* recipient_leaves, const uint8_t* sender_sib, const uint8_t* recipient_sib, size_t n,
-                    PyOut* out) {
-    PyStaged in;
-    SWM_TRY(py_stage(ctx, c->shape.levels, msgs, sigs, sender_leaves, recipient_leaves, sender_sib, recipient_sib, n, &in));
-    SWM_TRY(py_out(ctx, c->shape.num_witness, n, out));
-    return pp_run(ctx, c, tree, in.msgs, in.sigs, in.sender_leaves, in.recipient_leaves, in.sender_sib, in.recipient_sib, n, out->w, out->flags,
-                  out->status, out->roots_s, out->roots_r);
-}
+static_assert(PP_MSG_LEN == PY_MSG_LEN && PP_LEAF_LEN == PY_LEAF_LEN, "the payment driver's message and leaf");
 
-static int pp_host(swm_ctx* ctx, const swm_pedersen_payment_circuit* c, const swm_merkle_tree* tree, const uint8_t* msgs, const uint8_t* sigs,
-                   const uint8_t* sender_leaves, const uint8_t* recipient_leaves, const uint8_t* sender_sib, const uint8_t* recipient_sib,
-                   size_t count, uint64_t* witness, uint8_t* flags, uint8_t* sender_roots, uint8_t* recipient_roots) {
-    const PedersenPaymentShape& s = c->shape;
-    const size_t item = s.num_witness * sizeof(Fr), sib = s.levels * 32;
-    const size_t per = PY_STAGE_BYTES / item ? PY_STAGE_BYTES / item : 1;  // payments per chunk
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
-        PyOut o;
-        SWM_TRY(pp_chunk(ctx, c, tree, msgs + PP_MSG_LEN * base, sigs + 64 * base, sender_leaves + PP_LEAF_LEN * base,
-                         recipient_leaves + PP_LEAF_LEN * base, sender_sib ? sender_sib + sib * base : nullptr,
-                         recipient_sib ? recipient_sib + sib * base : nullptr, n, &o));
-        SWM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t*>(witness) + base * item, o.w, n * item, hipMemcpyDeviceToHost, ctx->stream));
-        if (flags) SWM_HIP(ctx, hipMemcpyAsync(flags + base, o.flags, n, hipMemcpyDeviceToHost, ctx->stream));
-        if (sender_roots) SWM_HIP(ctx, hipMemcpyAsync(sender_roots + 32 * base, o.roots_s, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-        if (recipient_roots) SWM_HIP(ctx, hipMemcpyAsync(recipient_roots + 32 * base, o.roots_r, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-        SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffers are reused by the next chunk
-    }
-    return SWM_OK;
-}
-
-static const uint8_t* pp_root_node(const swm_merkle_tree* t) { return t->d_nodes + 32 * (t->num_nodes() - 1); }
+struct PedersenPaymentUnit {  // what ledger_witness_host.h drives
+    using Circuit = swm_pedersen_payment_circuit;
+    using Tree = swm_merkle_tree;
+    static constexpr const char* name = "pedersen_payment";
+    static constexpr auto run = pp_run;
+    static constexpr auto check_tree = pp_check_tree;
+    static const uint8_t* root_node(const Tree* t) { return t->d_nodes + 32 * (t->num_nodes() - 1); }
+};
 
 }  // namespace swm
 
@@ -324,114 +302,44 @@ int swm_pedersen_payment_circuit_create(swm_ctx* ctx, const swm_schnorr* schnorr
     return SWM_OK;
 }
 
-void swm_pedersen_payment_circuit_destroy(swm_ctx* ctx, swm_pedersen_payment_circuit* c) {
-    if (!c) return;
-    DeviceGuard guard(ctx);
-    if (ctx) drain_streams(ctx);
-    delete c;
-}
+void swm_pedersen_payment_circuit_destroy(swm_ctx* ctx, swm_pedersen_payment_circuit* c) { destroy_circuit(ctx, c); }
 
 int swm_pedersen_payment_witness(swm_ctx* ctx, const swm_pedersen_payment_circuit* c, const uint8_t* messages, const uint8_t* signatures,
                                  const uint8_t* sender_leaves, const uint8_t* sender_siblings, const uint8_t* recipient_leaves,
                                  const uint8_t* recipient_siblings, size_t count, uint64_t* witness, uint8_t* flags, uint8_t* sender_roots,
                                  uint8_t* recipient_roots) {
-    if (!ctx || !c || (count && (!messages || !signatures || !sender_leaves || !recipient_leaves || !sender_siblings || !recipient_siblings || !witness)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_payment_witness: bad arguments");
-    if (!count) return SWM_OK;
-    SWM_TRY(py_check(ctx, "pedersen_payment_witness", c->shape.height, messages, sender_leaves, sender_siblings, recipient_siblings, count));
-    SWM_ON_DEVICE(ctx);
-    return py_drained(ctx, pp_host(ctx, c, nullptr, messages, signatures, sender_leaves, recipient_leaves, sender_siblings, recipient_siblings,
-                                   count, witness, flags, sender_roots, recipient_roots));
+    return payment_witness<PedersenPaymentUnit>(ctx, c, messages, signatures, sender_leaves, recipient_leaves, sender_siblings, recipient_siblings,
+                                                count, witness, flags, sender_roots, recipient_roots);
 }
 
 int swm_pedersen_payment_witness_at(swm_ctx* ctx, const swm_pedersen_payment_circuit* c, const swm_merkle_tree* tree, const uint8_t* messages,
                                     const uint8_t* signatures, const uint8_t* sender_leaves, const uint8_t* recipient_leaves, size_t count,
                                     uint64_t* witness, uint8_t* flags) {
-    if (!ctx || !c || !tree || (count && (!messages || !signatures || !sender_leaves || !recipient_leaves || !witness)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_payment_witness_at: bad arguments");
-    SWM_TRY(pp_check_tree(ctx, "pedersen_payment_witness_at", c, tree));
-    if (!count) return SWM_OK;
-    SWM_TRY(py_check(ctx, "pedersen_payment_witness_at", c->shape.height, messages, sender_leaves, nullptr, nullptr, count));
-    SWM_ON_DEVICE(ctx);
-    return py_drained(ctx, pp_host(ctx, c, tree, messages, signatures, sender_leaves, recipient_leaves, nullptr, nullptr, count, witness, flags,
-                                   nullptr, nullptr));
+    return payment_witness_at<PedersenPaymentUnit>(ctx, c, tree, messages, signatures, sender_leaves, recipient_leaves, count, witness, flags);
 }
 
 int swm_pedersen_payment_witness_dev(swm_ctx* ctx, const swm_pedersen_payment_circuit* c, const swm_merkle_tree* tree, const void* d_messages,
                                      const void* d_signatures, const void* d_sender_leaves, const void* d_recipient_leaves,
                                      const void* d_sender_siblings, const void* d_recipient_siblings, size_t count, void* d_witness,
                                      void* d_flags, void* d_status, void* d_sender_roots, void* d_recipient_roots) {
-    if (!ctx || !c || (count && (!d_messages || !d_signatures || !d_sender_leaves || !d_recipient_leaves || !d_witness || !d_flags || !d_status)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_payment_witness_dev: bad arguments");
-    if (count && !tree && (!d_sender_siblings || !d_recipient_siblings))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_payment_witness_dev: neither a tree nor two sibling arrays");
-    if (tree) SWM_TRY(pp_check_tree(ctx, "pedersen_payment_witness_dev", c, tree));
-    if (((uintptr_t)d_signatures | (uintptr_t)d_sender_siblings | (uintptr_t)d_recipient_siblings | (uintptr_t)d_status |
-         (uintptr_t)d_sender_roots | (uintptr_t)d_recipient_roots) & 3 || ((uintptr_t)d_witness & 15))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_payment_witness_dev: signatures, siblings, status and roots must be 4-byte aligned, "
-                       "the witness 16-byte aligned");
-    SWM_ON_DEVICE(ctx);
-    return pp_run(ctx, c, tree, (const uint8_t*)d_messages, (const uint8_t*)d_signatures, (const uint8_t*)d_sender_leaves,
-                  (const uint8_t*)d_recipient_leaves, (const uint8_t*)d_sender_siblings, (const uint8_t*)d_recipient_siblings, count, (Fr*)d_witness,
-                  (uint8_t*)d_flags, (uint32_t*)d_status, (uint32_t*)d_sender_roots, (uint32_t*)d_recipient_roots);
+    return payment_witness_dev<PedersenPaymentUnit>(ctx, c, tree, d_messages, d_signatures, d_sender_leaves, d_recipient_leaves, d_sender_siblings,
+                                                    d_recipient_siblings, count, d_witness, d_flags, d_status, d_sender_roots,
+                                                    d_recipient_roots);
 }
 
 int swm_pedersen_payment_prove_at(swm_ctx* ctx, const swm_pk* pk, const swm_pedersen_payment_circuit* c, const swm_merkle_tree* tree,
                                   const uint8_t message[10], const uint8_t signature[64], const uint8_t sender_leaf[72],
                                   const uint8_t recipient_leaf[72], swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
-    if (!ctx || !pk || !c || !tree || !message || !signature || !sender_leaf || !recipient_leaf || !rng || !proof_out || !len)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_payment_prove_at: bad arguments");
-    SWM_TRY(pp_check_tree(ctx, "pedersen_payment_prove_at", c, tree));
-    SWM_TRY(py_check(ctx, "pedersen_payment_prove_at", c->shape.height, message, sender_leaf, nullptr, nullptr, 1));
-    PyOut o;
-    Fr root;
-    {
-        SWM_ON_DEVICE(ctx);
-        SWM_TRY(py_drained(ctx, pp_chunk(ctx, c, tree, message, signature, sender_leaf, recipient_leaf, nullptr, nullptr, 1, &o)));
-        SWM_TRY(py_root_mont(ctx, pp_root_node(tree), &root));  // its synchronisation: the inputs were staged from the caller's buffers
-    }
-    return py_prove_item(ctx, pk, c->shape.num_witness, c->shape.num_constraints, root, message, o.w, rng, flags, proof_out, cap, len);
+    return payment_prove_at<PedersenPaymentUnit>(ctx, pk, c, tree, message, signature, sender_leaf, recipient_leaf, rng, flags, proof_out, cap,
+                                                 len);
 }
 
 int swm_pedersen_payment_prove_many_at(swm_ctx* ctx, const swm_pk* pk, const swm_pedersen_payment_circuit* c, const swm_merkle_tree* tree,
                                        const uint8_t* messages, const uint8_t* signatures, const uint8_t* sender_leaves,
                                        const uint8_t* recipient_leaves, size_t count, swm_rng* rng, unsigned flags, uint8_t* proofs_out,
                                        size_t proof_cap, size_t* lens, uint8_t* item_flags) {
-    if (!ctx || !pk || !c || !tree || !rng || (count && (!messages || !signatures || !sender_leaves || !recipient_leaves || !proofs_out || !lens ||
-                                                         !item_flags)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_payment_prove_many_at: bad arguments");
-    SWM_TRY(pp_check_tree(ctx, "pedersen_payment_prove_many_at", c, tree));
-    if (!count) return SWM_OK;
-    SWM_TRY(py_check(ctx, "pedersen_payment_prove_many_at", c->shape.height, messages, sender_leaves, nullptr, nullptr, count));
-    const PedersenPaymentShape& s = c->shape;
-    const size_t item = s.num_witness * sizeof(Fr);
-    const size_t per = PY_STAGE_BYTES / item ? PY_STAGE_BYTES / item : 1;
-    for (size_t i = 0; i < count; i++) {  // whatever ends the call, every entry of the two arrays has been written
-        lens[i] = 0;
-        item_flags[i] = 0;
-    }
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
-        PyOut o;
-        Fr root;
-        {
-            SWM_ON_DEVICE(ctx);
-            SWM_TRY(py_drained(ctx, pp_chunk(ctx, c, tree, messages + PP_MSG_LEN * base, signatures + 64 * base, sender_leaves + PP_LEAF_LEN * base,
-                                             recipient_leaves + PP_LEAF_LEN * base, nullptr, nullptr, n, &o)));
-            SWM_HIP(ctx, hipMemcpyAsync(item_flags + base, o.flags, n, hipMemcpyDeviceToHost, ctx->stream));
-            SWM_TRY(py_root_mont(ctx, pp_root_node(tree), &root));
-        }
-        for (size_t i = 0; i < n; i++) {
-            if (item_flags[base + i] != 3) continue;  // reported, not proved: its system is unsatisfied
-            size_t len = 0;
-            const int rc = py_prove_item(ctx, pk, s.num_witness, s.num_constraints, root, messages + PP_MSG_LEN * (base + i), o.w + i * s.num_witness,
-                                         rng, flags, proofs_out + (base + i) * proof_cap, proof_cap, &len);
-            if (rc == SWM_ERR_UNSATISFIED) continue;  // flags 3 and a leaf that is not the tree's: no proof, lens stays 0, the block goes on
-            if (rc != SWM_OK) return rc;
-            lens[base + i] = len;
-        }
-    }
-    return SWM_OK;
+    return payment_prove_many_at<PedersenPaymentUnit>(ctx, pk, c, tree, messages, signatures, sender_leaves, recipient_leaves, count, rng, flags,
+                                                      proofs_out, proof_cap, lens, item_flags);
 }
 
 }  // extern "C"

@@ -43,6 +43,7 @@
 #include "pedersen.h"
 #include "schnorr.h"
 #include "swmarlin.h"
+#include "ledger_witness_host.h"
 #include "witness_runs.h"
 
 struct swm_pedersen_transfer_circuit {
@@ -273,21 +274,10 @@ static int pt_check_tree(swm_ctx* ctx, const char* what, const swm_pedersen_tran
     return SWM_OK;
 }
 
-static int pt_drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
-    if (rc != SWM_OK) drain_streams(ctx);
-    return rc;
-}
-
-struct PtBlock {  // the caller's arrays of a whole block; roots may be NULL
-    const uint8_t *msgs, *sigs;
-    uint8_t *old_roots, *new_roots, *flags;
-    uint32_t* status;
-};
-
 // Chunk [base, base + n) of a block: staged, run, its small results copied out and waited for.  The witnesses stay in
 // "ptransfer.w" (*d_w).  d_accounts: the table on the device ("ptransfer.accounts"), uploaded by the caller.
 static int pt_chunk(swm_ctx* ctx, const char* what, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree, uint8_t* d_accounts,
-                    const PtBlock& b, size_t base, size_t n, Fr** d_w) {
+                    const TransferBlock& b, size_t base, size_t n, Fr** d_w) {
     const size_t item = c->shape.num_witness * sizeof(Fr);
     uint8_t *d_in = nullptr, *d_out = nullptr;
     SWM_TRY(scratch(ctx, "stage.a", n * (64 + PP_MSG_LEN) + 16, (void**)&d_in));
@@ -309,56 +299,17 @@ static int pt_chunk(swm_ctx* ctx, const char* what, const swm_pedersen_transfer_
     return SWM_OK;
 }
 
-static int pt_upload_accounts(swm_ctx* ctx, const uint8_t* accounts, size_t bytes, uint8_t** d_accounts) {
-    SWM_TRY(scratch(ctx, "ptransfer.accounts", bytes + 16, (void**)d_accounts));
-    SWM_HIP(ctx, hipMemcpyAsync(*d_accounts, accounts, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return SWM_OK;
-}
+static_assert(PT_FLAG_APPLIED == TRANSFER_FLAG_APPLIED, "the block driver proves what the advance kernel applied");
+static_assert(PP_MSG_LEN == PY_MSG_LEN && PP_LEAF_LEN == PY_LEAF_LEN, "the block driver's message and leaf");
 
-// The block in chunks (host/pedersen_transfer_shape.h: the plan).  witness (may be NULL): the host copy of every item; pk (may be
-// NULL): one proof per applied transfer.
-static int pt_block(swm_ctx* ctx, const char* what, const swm_pk* pk, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree,
-                    uint8_t* accounts, const PtBlock& b, size_t count, uint64_t* witness, swm_rng* rng, unsigned prove_flags, uint8_t* proofs_out,
-                    size_t proof_cap, size_t* lens) {
-    const PedersenTransferShape& s = c->shape;
-    const size_t item = s.num_witness * sizeof(Fr), table_bytes = PP_LEAF_LEN << s.levels;
-    std::vector<PtChunk> plan;
-    if (!pedersen_transfer_plan(item, count, PT_STAGE_BYTES, &plan)) return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: no plan", what);
-    std::vector<uint8_t> roots;  // the prover needs the root pairs whether the caller asked for them or not
-    PtBlock blk = b;
-    if (pk && (!b.old_roots || !b.new_roots)) {
-        roots.resize(64 * count);
-        if (!b.old_roots) blk.old_roots = roots.data();
-        if (!b.new_roots) blk.new_roots = roots.data() + 32 * count;
-    }
-    uint8_t* d_accounts = nullptr;
-    {
-        SWM_ON_DEVICE(ctx);
-        SWM_TRY(pt_drained(ctx, pt_upload_accounts(ctx, accounts, table_bytes, &d_accounts)));
-    }
-    for (const PtChunk& ch : plan) {
-        Fr* d_w = nullptr;
-        {
-            SWM_ON_DEVICE(ctx);
-            SWM_TRY(pt_drained(ctx, pt_chunk(ctx, what, c, tree, d_accounts, blk, ch.base, ch.count, &d_w)));
-            // the tree is advanced from here on: the table goes back with it, whatever the prover does below
-            SWM_HIP(ctx, hipMemcpyAsync(accounts, d_accounts, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
-            if (witness)
-                SWM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t*>(witness) + ch.base * item, d_w, ch.count * item, hipMemcpyDeviceToHost,
-                                            ctx->stream));
-            SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        for (size_t i = ch.base; pk && i < ch.base + ch.count; i++) {
-            if (!(blk.flags[i] & PT_FLAG_APPLIED)) continue;
-            size_t len = 0;
-            SWM_TRY(transfer_prove_item(ctx, pk, s.num_witness, s.num_constraints, blk.old_roots + 32 * i, blk.new_roots + 32 * i,
-                                        b.msgs + PP_MSG_LEN * i, d_w + (i - ch.base) * s.num_witness, rng, prove_flags,
-                                        proofs_out + i * proof_cap, proof_cap, &len));
-            lens[i] = len;
-        }
-    }
-    return SWM_OK;
-}
+struct PedersenTransferUnit {  // what ledger_witness_host.h drives
+    using Circuit = swm_pedersen_transfer_circuit;
+    using Tree = swm_merkle_tree;
+    static constexpr const char* name = "pedersen_transfer";
+    static constexpr const char* accounts_scratch = "ptransfer.accounts";
+    static constexpr auto check_tree = pt_check_tree;
+    static constexpr auto chunk = pt_chunk;
+};
 
 }  // namespace swm
 
@@ -389,43 +340,21 @@ int swm_pedersen_transfer_circuit_create(swm_ctx* ctx, const swm_schnorr* schnor
     return SWM_OK;
 }
 
-void swm_pedersen_transfer_circuit_destroy(swm_ctx* ctx, swm_pedersen_transfer_circuit* c) {
-    if (!c) return;
-    DeviceGuard guard(ctx);
-    if (ctx) drain_streams(ctx);
-    delete c;
-}
+void swm_pedersen_transfer_circuit_destroy(swm_ctx* ctx, swm_pedersen_transfer_circuit* c) { destroy_circuit(ctx, c); }
 
 int swm_pedersen_transfer_witness_at(swm_ctx* ctx, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree, uint8_t* accounts_inout,
                                      const uint8_t* messages, const uint8_t* signatures, size_t count, uint64_t* witnesses_out,
                                      uint8_t* old_roots, uint8_t* new_roots, uint8_t* flags, uint32_t* status) {
-    if (!ctx || !c || !tree || !accounts_inout ||
-        (count && (!messages || !signatures || !witnesses_out || !old_roots || !new_roots || !flags || !status)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_transfer_witness_at: bad arguments");
-    SWM_TRY(pt_check_tree(ctx, "pedersen_transfer_witness_at", c, tree));
-    if (!count) return SWM_OK;
-    if (count > 0x7FFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_transfer_witness_at: %zu transfers in one call", count);
-    const PtBlock b = {messages, signatures, old_roots, new_roots, flags, status};
-    return pt_block(ctx, "pedersen_transfer_witness_at", nullptr, c, tree, accounts_inout, b, count, witnesses_out, nullptr, 0, nullptr, 0, nullptr);
+    return transfer_witness_at<PedersenTransferUnit>(ctx, c, tree, accounts_inout, messages, signatures, count, witnesses_out, old_roots,
+                                                     new_roots, flags, status);
 }
 
 int swm_pedersen_transfer_prove_many_at(swm_ctx* ctx, const swm_pk* pk, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree,
                                         uint8_t* accounts_inout, const uint8_t* messages, const uint8_t* signatures, size_t count,
                                         swm_rng* rng, unsigned prove_flags, uint8_t* proofs_out, size_t proof_cap, size_t* lens,
                                         uint8_t* old_roots, uint8_t* new_roots, uint8_t* flags, uint32_t* status) {
-    if (!ctx || !pk || !c || !tree || !accounts_inout || !rng || (count && (!messages || !signatures || !proofs_out || !lens || !flags || !status)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_transfer_prove_many_at: bad arguments");
-    SWM_TRY(pt_check_tree(ctx, "pedersen_transfer_prove_many_at", c, tree));
-    if (!count) return SWM_OK;
-    if (count > 0x7FFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_transfer_prove_many_at: %zu transfers in one call", count);
-    for (size_t i = 0; i < count; i++) {  // whatever ends the call, every entry has been written
-        lens[i] = 0;
-        flags[i] = 0;
-        status[i] = 0;
-    }
-    const PtBlock b = {messages, signatures, old_roots, new_roots, flags, status};
-    return pt_block(ctx, "pedersen_transfer_prove_many_at", pk, c, tree, accounts_inout, b, count, nullptr, rng, prove_flags, proofs_out,
-                    proof_cap, lens);
+    return transfer_prove_many_at<PedersenTransferUnit>(ctx, pk, c, tree, accounts_inout, messages, signatures, count, rng, prove_flags,
+                                                        proofs_out, proof_cap, lens, old_roots, new_roots, flags, status);
 }
 
 int swm_pedersen_transfer_prove_at(swm_ctx* ctx, const swm_pk* pk, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree,

@@ -44,6 +44,7 @@
 #include "poseidon.h"
 #include "poseidon_permute.cuh"
 #include "swmarlin.h"
+#include "witness_host.h"
 
 namespace swm {
 
@@ -158,10 +159,6 @@ static int poseidon_host(swm_ctx* ctx, const swm_poseidon* p, const uint8_t* in,
     SWM_HIP(ctx, hipMemcpyAsync(out, d_out, count * n_out * 32, hipMemcpyDeviceToHost, ctx->stream));
     SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SWM_OK;
-}
-static int drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
-    if (rc != SWM_OK) drain_streams(ctx);
-    return rc;
 }
 
 }  // namespace swm

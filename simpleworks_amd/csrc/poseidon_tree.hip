@@ -27,6 +27,7 @@
 #include "merkle_nodes.cuh"
 #include "poseidon_tree.h"
 #include "swmarlin.h"
+#include "witness_host.h"
 
 namespace swm {
 
@@ -255,11 +256,6 @@ static int pt_update_args(swm_ctx* ctx, const swm_poseidon_tree* t, const uint64
     }
 }
 
-static int pt_drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
-    if (rc != SWM_OK) drain_streams(ctx);
-    return rc;
-}
-
 static int pt_paths_host(swm_ctx* ctx, const swm_poseidon_tree* t, const uint64_t* indices, size_t count, uint8_t* siblings) {
     const size_t bytes = count * t->levels() * 32, words = bytes / 4;
     uint8_t *d_in = nullptr, *d_out = nullptr;
@@ -395,7 +391,7 @@ int swm_poseidon_tree_paths(swm_ctx* ctx, const swm_poseidon_tree* t, const uint
                            (unsigned long long)indices[p], t->n());
     if (!count) return SWM_OK;
     SWM_ON_DEVICE(ctx);
-    return pt_drained(ctx, pt_paths_host(ctx, t, indices, count, siblings));
+    return drained(ctx, pt_paths_host(ctx, t, indices, count, siblings));
 }
 
 int swm_poseidon_verify_paths(swm_ctx* ctx, const swm_poseidon* params, size_t height, const uint8_t* roots, size_t root_stride,
@@ -410,7 +406,7 @@ int swm_poseidon_verify_paths(swm_ctx* ctx, const swm_poseidon* params, size_t h
     SWM_TRY(pt_check_params(ctx, "poseidon_verify_paths", height, leaf_len));
     if (!count) return SWM_OK;
     SWM_ON_DEVICE(ctx);
-    return pt_drained(ctx, pt_verify_host(ctx, params, height, roots, root_stride, leaves, leaf_len, indices, siblings, count, ok, status));
+    return drained(ctx, pt_verify_host(ctx, params, height, roots, root_stride, leaves, leaf_len, indices, siblings, count, ok, status));
 }
 
 }  // extern "C"

@@ -33,6 +33,7 @@
 #include "merkle_nodes.cuh"
 #include "swmarlin.h"
 #include "witness_runs.h"
+#include "witness_host.h"
 
 namespace swm {
 
@@ -215,14 +216,6 @@ static int ptw_check_tree(swm_ctx* ctx, const char* what, const swm_poseidon_tre
     return SWM_OK;
 }
 
-// The host forms hold at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
-static constexpr size_t PTW_STAGE_BYTES = (size_t)1 << 30;
-
-static int ptw_drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
-    if (rc != SWM_OK) drain_streams(ctx);
-    return rc;
-}
-
 // indices | siblings | leaves of n paths into "stage.a"
 static int ptw_stage(swm_ctx* ctx, const PoseidonTreeShape& s, const uint8_t* leaves, const uint64_t* indices, const uint8_t* siblings, size_t n,
                      const uint8_t** d_leaves, const uint64_t** d_indices, const uint8_t** d_siblings) {
@@ -242,9 +235,8 @@ static int ptw_host(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const swm_
                     const uint64_t* indices, const uint8_t* siblings, size_t count, uint64_t* witness, uint8_t* roots) {
     const PoseidonTreeShape& s = c->shape;
     const size_t item = s.num_witness * sizeof(Fr);
-    const size_t per = PTW_STAGE_BYTES / item ? PTW_STAGE_BYTES / item : 1;  // paths per chunk
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
+    for (const WitnessChunk ch : WitnessChunks(witness_stage_items(ctx, item), count)) {
+        const size_t base = ch.base, n = ch.count;
         const uint8_t *d_leaves, *d_siblings;
         const uint64_t* d_indices;
         uint8_t* d_out = nullptr;
@@ -284,18 +276,7 @@ static int ptw_prove(swm_ctx* ctx, const swm_pk* pk, const swm_poseidon_tree_cir
     (void)ps_load_std(root, &r);  // canonical: the caller checked it
     inst[1] = fp_from_std(r);
     for (size_t i = 0; i < 8 * s.leaf_len; i++) inst[2 + i] = (leaf[i >> 3] >> (i & 7)) & 1 ? fp_one<Fr>() : fp_zero<Fr>();
-    swm_r1cs cs = {};
-    cs.num_instance = s.num_instance;
-    cs.num_witness = s.num_witness;
-    cs.num_constraints = s.num_constraints;
-    cs.instance = reinterpret_cast<const uint64_t*>(inst.data());
-    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
-    struct DevWitnessScope {
-        swm_ctx* c;
-        ~DevWitnessScope() { c->witness_dev = nullptr; }
-    } scope{ctx};
-    ctx->witness_dev = d_w;
-    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+    return prove_device_witness(ctx, pk, s.num_instance, s.num_witness, s.num_constraints, inst.data(), d_w, rng, flags, proof_out, cap, len);
 }
 
 }  // namespace swm
@@ -318,10 +299,7 @@ int swm_poseidon_tree_circuit_create(swm_ctx* ctx, const swm_poseidon* params, s
 }
 
 void swm_poseidon_tree_circuit_destroy(swm_ctx* ctx, swm_poseidon_tree_circuit* c) {
-    if (!c) return;
-    DeviceGuard guard(ctx);
-    if (ctx) drain_streams(ctx);
-    delete c;
+    destroy_circuit(ctx, c);
 }
 
 int swm_poseidon_tree_witness(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const uint8_t* leaves, const uint64_t* indices,
@@ -332,7 +310,7 @@ int swm_poseidon_tree_witness(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, 
     if (count > 0x7FFFFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "poseidon_tree_witness: %zu paths in one call", count);
     SWM_TRY(ptw_check_paths(ctx, "poseidon_tree_witness", c->shape, indices, siblings, count));
     SWM_ON_DEVICE(ctx);
-    return ptw_drained(ctx, ptw_host(ctx, c, nullptr, leaves, indices, siblings, count, witness, roots));
+    return drained(ctx, ptw_host(ctx, c, nullptr, leaves, indices, siblings, count, witness, roots));
 }
 
 int swm_poseidon_tree_witness_at(swm_ctx* ctx, const swm_poseidon_tree_circuit* c, const swm_poseidon_tree* tree, const uint8_t* leaves,
@@ -344,7 +322,7 @@ int swm_poseidon_tree_witness_at(swm_ctx* ctx, const swm_poseidon_tree_circuit* 
     if (count > 0x7FFFFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "poseidon_tree_witness_at: %zu paths in one call", count);
     SWM_TRY(ptw_check_paths(ctx, "poseidon_tree_witness_at", c->shape, indices, nullptr, count));
     SWM_ON_DEVICE(ctx);
-    return ptw_drained(ctx, ptw_host(ctx, c, tree, leaves, indices, nullptr, count, witness, nullptr));
+    return drained(ctx, ptw_host(ctx, c, tree, leaves, indices, nullptr, count, witness, nullptr));
 }
 
 int swm_poseidon_tree_prove(swm_ctx* ctx, const swm_pk* pk, const swm_poseidon_tree_circuit* c, const uint8_t root[32], const uint8_t* leaf,
@@ -357,7 +335,7 @@ int swm_poseidon_tree_prove(swm_ctx* ctx, const swm_pk* pk, const swm_poseidon_t
     Fr* d_w = nullptr;
     {
         SWM_ON_DEVICE(ctx);
-        SWM_TRY(ptw_drained(ctx, ptw_one(ctx, c, nullptr, leaf, index, siblings, &d_w)));
+        SWM_TRY(drained(ctx, ptw_one(ctx, c, nullptr, leaf, index, siblings, &d_w)));
     }
     return ptw_prove(ctx, pk, c, root, leaf, d_w, rng, flags, proof_out, cap, len);
 }
@@ -372,7 +350,7 @@ int swm_poseidon_tree_prove_at(swm_ctx* ctx, const swm_pk* pk, const swm_poseido
     uint8_t root[32];
     {
         SWM_ON_DEVICE(ctx);
-        SWM_TRY(ptw_drained(ctx, ptw_one(ctx, c, tree, leaf, index, nullptr, &d_w)));
+        SWM_TRY(drained(ctx, ptw_one(ctx, c, tree, leaf, index, nullptr, &d_w)));
         SWM_HIP(ctx, hipMemcpyAsync(root, tree->d_nodes + 32 * (tree->num_nodes() - 1), 32, hipMemcpyDeviceToHost, ctx->stream));
         SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }

@@ -40,6 +40,7 @@
 #include "poseidon.h"
 #include "poseidon_record.cuh"
 #include "swmarlin.h"
+#include "witness_host.h"
 
 struct swm_poseidon_circuit {
     const swm_poseidon* params = nullptr;
@@ -168,21 +169,12 @@ static int pw_check_elements(swm_ctx* ctx, const char* what, const PoseidonShape
     return SWM_OK;
 }
 
-// The host form holds at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
-static constexpr size_t PW_STAGE_BYTES = (size_t)1 << 30;
-
-static int pw_drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
-    if (rc != SWM_OK) drain_streams(ctx);
-    return rc;
-}
-
 static int poseidon_witness_host(swm_ctx* ctx, const swm_poseidon_circuit* c, const uint8_t* inputs, size_t count, uint64_t* witness,
                                  uint8_t* outputs) {
     const PoseidonShape& s = c->shape;
     const size_t item = s.num_witness * sizeof(Fr), in_item = pw_item_bytes(s), out_item = 32 * s.n_out;
-    const size_t per = PW_STAGE_BYTES / item ? PW_STAGE_BYTES / item : 1;  // items per chunk
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
+    for (const WitnessChunk ch : WitnessChunks(witness_stage_items(ctx, item), count)) {
+        const size_t base = ch.base, n = ch.count;
         uint8_t *d_in = nullptr, *d_out = nullptr;
         SWM_TRY(scratch(ctx, "stage.a", n * in_item + 32, (void**)&d_in));
         SWM_TRY(scratch(ctx, "poseidon.w", n * item + n * out_item, (void**)&d_out));
@@ -231,10 +223,7 @@ int swm_poseidon_circuit_create(swm_ctx* ctx, const swm_poseidon* params, int by
 }
 
 void swm_poseidon_circuit_destroy(swm_ctx* ctx, swm_poseidon_circuit* c) {
-    if (!c) return;
-    DeviceGuard guard(ctx);
-    if (ctx) drain_streams(ctx);
-    delete c;
+    destroy_circuit(ctx, c);
 }
 
 int swm_poseidon_witness_dev(swm_ctx* ctx, const swm_poseidon_circuit* c, const void* d_inputs, size_t count, void* d_witness, void* d_outputs,
@@ -244,7 +233,7 @@ int swm_poseidon_witness_dev(swm_ctx* ctx, const swm_poseidon_circuit* c, const 
     if (((uintptr_t)d_witness & 15) || ((uintptr_t)d_outputs & 3) || ((uintptr_t)d_status & 3) || (!c->shape.bytes && ((uintptr_t)d_inputs & 3)))
         return set_err(ctx, SWM_ERR_INVALID_ARG, "poseidon_witness: the witness must be 16-byte aligned, elements, outputs and status 4-byte aligned");
     SWM_ON_DEVICE(ctx);
-    return pw_drained(ctx, poseidon_witness_run(ctx, c, (const uint8_t*)d_inputs, count, (Fr*)d_witness, d_outputs, d_status));
+    return drained(ctx, poseidon_witness_run(ctx, c, (const uint8_t*)d_inputs, count, (Fr*)d_witness, d_outputs, d_status));
 }
 
 int swm_poseidon_witness(swm_ctx* ctx, const swm_poseidon_circuit* c, const uint8_t* inputs, size_t count, uint64_t* witness, uint8_t* outputs) {
@@ -254,7 +243,7 @@ int swm_poseidon_witness(swm_ctx* ctx, const swm_poseidon_circuit* c, const uint
     if (count > 0x7FFFFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "poseidon_witness: %zu items in one call", count);
     SWM_TRY(pw_check_elements(ctx, "poseidon_witness", c->shape, inputs, count));
     SWM_ON_DEVICE(ctx);
-    return pw_drained(ctx, poseidon_witness_host(ctx, c, inputs, count, witness, outputs));
+    return drained(ctx, poseidon_witness_host(ctx, c, inputs, count, witness, outputs));
 }
 
 int swm_poseidon_prove(swm_ctx* ctx, const swm_pk* pk, const swm_poseidon_circuit* c, const uint8_t* input, swm_rng* rng, unsigned flags,
@@ -267,7 +256,7 @@ int swm_poseidon_prove(swm_ctx* ctx, const swm_pk* pk, const swm_poseidon_circui
     uint8_t digest[32 * PC_MAX_OUT];
     {
         SWM_ON_DEVICE(ctx);
-        SWM_TRY(pw_drained(ctx, poseidon_witness_one(ctx, c, input, &d_w, digest)));
+        SWM_TRY(drained(ctx, poseidon_witness_one(ctx, c, input, &d_w, digest)));
     }
     // public input: one, then the outputs (in the prover's Montgomery form)
     Fr inst[1 + PC_MAX_OUT];
@@ -278,18 +267,7 @@ int swm_poseidon_prove(swm_ctx* ctx, const swm_pk* pk, const swm_poseidon_circui
         inst[1 + j] = fp_from_std(v);
     }
     memcpy(outputs, digest, 32 * s.n_out);
-    swm_r1cs cs = {};
-    cs.num_instance = s.num_instance;
-    cs.num_witness = s.num_witness;
-    cs.num_constraints = s.num_constraints;
-    cs.instance = reinterpret_cast<const uint64_t*>(inst);
-    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
-    struct DevWitnessScope {
-        swm_ctx* c;
-        ~DevWitnessScope() { c->witness_dev = nullptr; }
-    } scope{ctx};
-    ctx->witness_dev = d_w;
-    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+    return prove_device_witness(ctx, pk, s.num_instance, s.num_witness, s.num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
 }
 
 }  // extern "C"

@@ -31,6 +31,7 @@
 #include "frinv.cuh"
 #include "host/program_shape.h"
 #include "swmarlin.h"
+#include "witness_host.h"
 
 struct swm_program {
     swm::ProgramShape shape;
@@ -337,17 +338,10 @@ static int program_run(swm_ctx* ctx, const swm_program* p, const uint8_t* d_in, 
     return SWM_OK;
 }
 
-// The host form holds at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
-static constexpr size_t PG_STAGE_BYTES = (size_t)1 << 30;
-
-static int pg_drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
-    if (rc != SWM_OK) drain_streams(ctx);
-    return rc;
-}
-
-static size_t pg_items_per_chunk(const ProgramShape& s) {
-    const size_t item = s.num_witness * sizeof(Fr);
-    return item && PG_STAGE_BYTES / item ? PG_STAGE_BYTES / item : item ? 1 : (size_t)1 << 20;
+// items per chunk; a program with no witnesses has nothing to fit the stage: 2^20 items at a time
+static size_t pg_items_per_chunk(const swm_ctx* ctx, const ProgramShape& s) {
+    const size_t fit = witness_stage_items(ctx, s.num_witness * sizeof(Fr));
+    return fit ? fit : (size_t)1 << 20;
 }
 
 struct PgOut {  // "program.w": witnesses | outputs | status
@@ -371,9 +365,9 @@ static int pg_chunk(swm_ctx* ctx, const swm_program* p, const uint8_t* inputs, s
 static int program_witness_host(swm_ctx* ctx, const swm_program* p, const uint8_t* inputs, size_t count, uint64_t* witness, uint8_t* outputs,
                                 uint8_t* status) {
     const ProgramShape& s = p->shape;
-    const size_t item = s.num_witness * sizeof(Fr), per = pg_items_per_chunk(s);
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
+    const size_t item = s.num_witness * sizeof(Fr);
+    for (const WitnessChunk ch : WitnessChunks(pg_items_per_chunk(ctx, s), count)) {
+        const size_t base = ch.base, n = ch.count;
         PgOut o;
         SWM_TRY(pg_chunk(ctx, p, inputs ? inputs + base * s.input_bytes : nullptr, n, &o));
         if (item) SWM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t*>(witness) + base * item, o.w, n * item, hipMemcpyDeviceToHost, ctx->stream));
@@ -404,18 +398,7 @@ static int pg_prove_item(swm_ctx* ctx, const swm_pk* pk, const ProgramShape& s, 
         pg_push_bits(inst, output, pg_width(t));
         output += pg_bytes(t);
     }
-    swm_r1cs cs = {};
-    cs.num_instance = s.num_instance;
-    cs.num_witness = s.num_witness;
-    cs.num_constraints = s.num_constraints;
-    cs.instance = reinterpret_cast<const uint64_t*>(inst.data());
-    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
-    struct DevWitnessScope {
-        swm_ctx* c;
-        ~DevWitnessScope() { c->witness_dev = nullptr; }
-    } scope{ctx};
-    ctx->witness_dev = d_w;
-    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+    return prove_device_witness(ctx, pk, s.num_instance, s.num_witness, s.num_constraints, inst.data(), d_w, rng, flags, proof_out, cap, len);
 }
 
 }  // namespace swm
@@ -459,14 +442,12 @@ int swm_program_create(swm_ctx* ctx, const uint8_t* tape, size_t len, swm_progra
 }
 
 void swm_program_destroy(swm_ctx* ctx, swm_program* p) {
-    if (!p) return;
-    DeviceGuard guard(ctx);
-    if (ctx) drain_streams(ctx);
-    if (p->d_exec) (void)hipFree(p->d_exec);
-    if (p->d_desc) (void)hipFree(p->d_desc);
-    if (p->d_block_first) (void)hipFree(p->d_block_first);
-    if (p->d_eq_slots) (void)hipFree(p->d_eq_slots);
-    delete p;
+    destroy_circuit(ctx, p, [](swm_program* q) {
+        if (q->d_exec) (void)hipFree(q->d_exec);
+        if (q->d_desc) (void)hipFree(q->d_desc);
+        if (q->d_block_first) (void)hipFree(q->d_block_first);
+        if (q->d_eq_slots) (void)hipFree(q->d_eq_slots);
+    });
 }
 
 int swm_program_witness(swm_ctx* ctx, const swm_program* p, const uint8_t* inputs, size_t count, uint64_t* witness, uint8_t* outputs,
@@ -478,7 +459,7 @@ int swm_program_witness(swm_ctx* ctx, const swm_program* p, const uint8_t* input
     if (!count) return SWM_OK;
     if (count > 0x7FFFFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "program_witness: %zu items in one call", count);
     SWM_ON_DEVICE(ctx);
-    return pg_drained(ctx, program_witness_host(ctx, p, inputs, count, witness, outputs, status));
+    return drained(ctx, program_witness_host(ctx, p, inputs, count, witness, outputs, status));
 }
 
 int swm_program_witness_dev(swm_ctx* ctx, const swm_program* p, const void* d_inputs, size_t count, void* d_witness, void* d_outputs,
@@ -489,7 +470,7 @@ int swm_program_witness_dev(swm_ctx* ctx, const swm_program* p, const void* d_in
         return set_err(ctx, SWM_ERR_INVALID_ARG, "program_witness_dev: bad arguments");
     if ((uintptr_t)d_witness & 15) return set_err(ctx, SWM_ERR_INVALID_ARG, "program_witness_dev: the witness must be 16-byte aligned");
     SWM_ON_DEVICE(ctx);
-    return pg_drained(ctx, program_run(ctx, p, (const uint8_t*)d_inputs, count, d_witness, (uint8_t*)d_outputs, (uint8_t*)d_status));
+    return drained(ctx, program_run(ctx, p, (const uint8_t*)d_inputs, count, d_witness, (uint8_t*)d_outputs, (uint8_t*)d_status));
 }
 
 int swm_program_prove(swm_ctx* ctx, const swm_pk* pk, const swm_program* p, const uint8_t* input, swm_rng* rng, unsigned flags,
@@ -501,7 +482,7 @@ int swm_program_prove(swm_ctx* ctx, const swm_pk* pk, const swm_program* p, cons
     std::vector<uint8_t> host(s.output_bytes + 1);
     {
         SWM_ON_DEVICE(ctx);
-        SWM_TRY(pg_drained(ctx, pg_chunk(ctx, p, input, 1, &o)));
+        SWM_TRY(drained(ctx, pg_chunk(ctx, p, input, 1, &o)));
         SWM_HIP(ctx, hipMemcpyAsync(host.data(), o.out, s.output_bytes + 1, hipMemcpyDeviceToHost, ctx->stream));  // outputs | status
         SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -524,13 +505,12 @@ int swm_program_prove_many(swm_ctx* ctx, const swm_pk* pk, const swm_program* p,
         status[i] = 0;
     }
     if (count > 0x7FFFFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "program_prove_many: %zu items in one call", count);
-    const size_t per = pg_items_per_chunk(s);
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
+    for (const WitnessChunk ch : WitnessChunks(pg_items_per_chunk(ctx, s), count)) {
+        const size_t base = ch.base, n = ch.count;
         PgOut o;
         {
             SWM_ON_DEVICE(ctx);
-            SWM_TRY(pg_drained(ctx, pg_chunk(ctx, p, inputs ? inputs + base * s.input_bytes : nullptr, n, &o)));
+            SWM_TRY(drained(ctx, pg_chunk(ctx, p, inputs ? inputs + base * s.input_bytes : nullptr, n, &o)));
             if (s.output_bytes)
                 SWM_HIP(ctx, hipMemcpyAsync(outputs + base * s.output_bytes, o.out, n * s.output_bytes, hipMemcpyDeviceToHost, ctx->stream));
             SWM_HIP(ctx, hipMemcpyAsync(status + base, o.status, n, hipMemcpyDeviceToHost, ctx->stream));

@@ -34,6 +34,7 @@
 #include "schnorr.h"
 #include "swmarlin.h"
 #include "witness_runs.h"
+#include "witness_host.h"
 
 namespace swm {
 
@@ -318,9 +319,6 @@ static int schnorr_stage_inputs(swm_ctx* ctx, const swm_schnorr_circuit* c, cons
     return SWM_OK;
 }
 
-// The host form holds at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
-static constexpr size_t SV_STAGE_BYTES = (size_t)1 << 30;
-
 }  // namespace swm
 
 using namespace swm;
@@ -340,10 +338,7 @@ int swm_schnorr_circuit_create(swm_ctx* ctx, const swm_schnorr* params, size_t m
 }
 
 void swm_schnorr_circuit_destroy(swm_ctx* ctx, swm_schnorr_circuit* c) {
-    if (!c) return;
-    DeviceGuard guard(ctx);
-    if (ctx) drain_streams(ctx);
-    delete c;
+    destroy_circuit(ctx, c);
 }
 
 int swm_schnorr_witness_dev(swm_ctx* ctx, const swm_schnorr_circuit* c, const void* d_public_keys, const void* d_messages,
@@ -365,9 +360,8 @@ int swm_schnorr_witness(swm_ctx* ctx, const swm_schnorr_circuit* c, const uint8_
     SWM_TRY(schnorr_check_keys(ctx, public_keys_xy, count));
     SWM_ON_DEVICE(ctx);
     const size_t item = c->shape.num_witness * sizeof(Fr), ml = c->shape.msg_len;
-    const size_t per = SV_STAGE_BYTES / item ? SV_STAGE_BYTES / item : 1;  // signatures per chunk
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
+    for (const WitnessChunk ch : WitnessChunks(witness_stage_items(ctx, item), count)) {
+        const size_t base = ch.base, n = ch.count;
         const uint8_t *d_keys, *d_msgs, *d_sigs;
         SWM_TRY(schnorr_stage_inputs(ctx, c, public_keys_xy + 64 * base, ml ? messages + ml * base : nullptr, signatures + 64 * base, n, &d_keys,
                                      &d_msgs, &d_sigs));
@@ -397,18 +391,7 @@ int swm_schnorr_prove(swm_ctx* ctx, const swm_pk* pk, const swm_schnorr_circuit*
         SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     const Fr inst = fp_one<Fr>();  // no public input (transaction.rs verifies with an empty vector)
-    swm_r1cs cs = {};
-    cs.num_instance = s.num_instance;
-    cs.num_witness = s.num_witness;
-    cs.num_constraints = s.num_constraints;
-    cs.instance = reinterpret_cast<const uint64_t*>(&inst);
-    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
-    struct DevWitnessScope {
-        swm_ctx* c;
-        ~DevWitnessScope() { c->witness_dev = nullptr; }
-    } scope{ctx};
-    ctx->witness_dev = d_w;
-    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+    return prove_device_witness(ctx, pk, s.num_instance, s.num_witness, s.num_constraints, &inst, d_w, rng, flags, proof_out, cap, len);
 }
 
 }  // extern "C"

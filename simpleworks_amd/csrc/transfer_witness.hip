@@ -42,6 +42,7 @@
 #include "poseidon_tree.h"
 #include "schnorr.h"
 #include "swmarlin.h"
+#include "ledger_witness_host.h"
 #include "witness_runs.h"
 
 struct swm_transfer_circuit {
@@ -320,23 +321,9 @@ static int tr_check_tree(swm_ctx* ctx, const char* what, const swm_transfer_circ
     return SWM_OK;
 }
 
-static int tr_drained(swm_ctx* ctx, int rc) {  // an error leaves nothing of this call queued behind it
-    if (rc != SWM_OK) drain_streams(ctx);
-    return rc;
-}
-
-// The host forms hold at most this many bytes of witnesses on the device at a time; a larger block goes in chunks, in order.
-static constexpr size_t TR_STAGE_BYTES = (size_t)1 << 30;
-
-struct TrBlock {  // the caller's arrays of a whole block; roots may be NULL
-    const uint8_t *msgs, *sigs;
-    uint8_t *old_roots, *new_roots, *flags;
-    uint32_t* status;
-};
-
 // Chunk [base, base + n) of a block: staged, run, its small results copied out and waited for.  The witnesses stay in
 // "transfer.w" (*d_w).  d_accounts: the table on the device ("transfer.accounts"), uploaded by the caller.
-static int tr_chunk(swm_ctx* ctx, const char* what, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* d_accounts, const TrBlock& b,
+static int tr_chunk(swm_ctx* ctx, const char* what, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* d_accounts, const TransferBlock& b,
                     size_t base, size_t n, Fr** d_w) {
     const TransferShape& s = c->shape;
     const size_t item = s.num_witness * sizeof(Fr);
@@ -359,19 +346,6 @@ static int tr_chunk(swm_ctx* ctx, const char* what, const swm_transfer_circuit* 
     return SWM_OK;
 }
 
-static int tr_upload_accounts(swm_ctx* ctx, const swm_transfer_circuit* c, const uint8_t* accounts, uint8_t** d_accounts) {
-    const size_t bytes = PY_LEAF_LEN << c->shape.levels;
-    SWM_TRY(scratch(ctx, "transfer.accounts", bytes + 16, (void**)d_accounts));
-    SWM_HIP(ctx, hipMemcpyAsync(*d_accounts, accounts, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return SWM_OK;
-}
-
-static int tr_download_accounts(swm_ctx* ctx, const swm_transfer_circuit* c, const uint8_t* d_accounts, uint8_t* accounts) {
-    SWM_HIP(ctx, hipMemcpyAsync(accounts, d_accounts, PY_LEAF_LEN << c->shape.levels, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SWM_OK;
-}
-
 // the prover over one item of a chunk's device witnesses; public input one, old_root, new_root, sender, recipient, amount
 int transfer_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size_t num_constraints, const uint8_t* old_root, const uint8_t* new_root,
                         const uint8_t* msg, const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
@@ -381,68 +355,19 @@ int transfer_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size
     (void)ps_load_std(old_root, &r0);  // nodes of the tree: canonical
     (void)ps_load_std(new_root, &r1);
     const Fr inst[6] = {fp_one<Fr>(), fp_from_std(r0), fp_from_std(r1), fp_from_u64<Fr>(msg[0]), fp_from_u64<Fr>(msg[1]), fp_from_u64<Fr>(amount)};
-    swm_r1cs cs = {};
-    cs.num_instance = TR_INSTANCE;
-    cs.num_witness = num_witness;
-    cs.num_constraints = num_constraints;
-    cs.instance = reinterpret_cast<const uint64_t*>(inst);
-    cs.witness = reinterpret_cast<const uint64_t*>(d_w);  // never read on the host: the context carries the device source
-    struct DevWitnessScope {
-        swm_ctx* c;
-        ~DevWitnessScope() { c->witness_dev = nullptr; }
-    } scope{ctx};
-    ctx->witness_dev = d_w;
-    return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
+    return prove_device_witness(ctx, pk, TR_INSTANCE, num_witness, num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
 }
 
-static int tr_prove_item(swm_ctx* ctx, const swm_pk* pk, const swm_transfer_circuit* c, const uint8_t* old_root, const uint8_t* new_root,
-                         const uint8_t* msg, const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
-    return transfer_prove_item(ctx, pk, c->shape.num_witness, c->shape.num_constraints, old_root, new_root, msg, d_w, rng, flags, proof_out, cap,
-                               len);
-}
+static_assert(TR_FLAG_APPLIED == TRANSFER_FLAG_APPLIED, "the block driver proves what the advance kernel applied");
 
-// The block in chunks.  witness (may be NULL): the host copy of every item; pk (may be NULL): one proof per applied transfer.
-static int tr_block(swm_ctx* ctx, const char* what, const swm_pk* pk, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* accounts,
-                    const TrBlock& b, size_t count, uint64_t* witness, swm_rng* rng, unsigned prove_flags, uint8_t* proofs_out, size_t proof_cap,
-                    size_t* lens) {
-    const TransferShape& s = c->shape;
-    const size_t item = s.num_witness * sizeof(Fr);
-    const size_t per = TR_STAGE_BYTES / item ? TR_STAGE_BYTES / item : 1;
-    std::vector<uint8_t> roots;  // the prover needs the root pairs whether the caller asked for them or not
-    TrBlock blk = b;
-    if (pk && (!b.old_roots || !b.new_roots)) {
-        roots.resize(64 * count);
-        if (!b.old_roots) blk.old_roots = roots.data();
-        if (!b.new_roots) blk.new_roots = roots.data() + 32 * count;
-    }
-    uint8_t* d_accounts = nullptr;
-    {
-        SWM_ON_DEVICE(ctx);
-        SWM_TRY(tr_drained(ctx, tr_upload_accounts(ctx, c, accounts, &d_accounts)));
-    }
-    for (size_t base = 0; base < count; base += per) {
-        const size_t n = count - base < per ? count - base : per;
-        Fr* d_w = nullptr;
-        {
-            SWM_ON_DEVICE(ctx);
-            SWM_TRY(tr_drained(ctx, tr_chunk(ctx, what, c, tree, d_accounts, blk, base, n, &d_w)));
-            // the tree is advanced from here on: the table goes back with it, whatever the prover does below
-            SWM_TRY(tr_drained(ctx, tr_download_accounts(ctx, c, d_accounts, accounts)));
-            if (witness) {
-                SWM_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t*>(witness) + base * item, d_w, n * item, hipMemcpyDeviceToHost, ctx->stream));
-                SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            }
-        }
-        for (size_t i = base; pk && i < base + n; i++) {
-            if (!(blk.flags[i] & TR_FLAG_APPLIED)) continue;
-            size_t len = 0;
-            SWM_TRY(tr_prove_item(ctx, pk, c, blk.old_roots + 32 * i, blk.new_roots + 32 * i, b.msgs + PY_MSG_LEN * i,
-                                  d_w + (i - base) * s.num_witness, rng, prove_flags, proofs_out + i * proof_cap, proof_cap, &len));
-            lens[i] = len;
-        }
-    }
-    return SWM_OK;
-}
+struct TransferUnit {  // what ledger_witness_host.h drives
+    using Circuit = swm_transfer_circuit;
+    using Tree = swm_poseidon_tree;
+    static constexpr const char* name = "transfer";
+    static constexpr const char* accounts_scratch = "transfer.accounts";
+    static constexpr auto check_tree = tr_check_tree;
+    static constexpr auto chunk = tr_chunk;
+};
 
 }  // namespace swm
 
@@ -466,42 +391,21 @@ int swm_transfer_circuit_create(swm_ctx* ctx, const swm_schnorr* schnorr, const 
     return SWM_OK;
 }
 
-void swm_transfer_circuit_destroy(swm_ctx* ctx, swm_transfer_circuit* c) {
-    if (!c) return;
-    DeviceGuard guard(ctx);
-    if (ctx) drain_streams(ctx);
-    delete c;
-}
+void swm_transfer_circuit_destroy(swm_ctx* ctx, swm_transfer_circuit* c) { destroy_circuit(ctx, c); }
 
 int swm_transfer_witness_at(swm_ctx* ctx, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* accounts_inout, const uint8_t* messages,
                             const uint8_t* signatures, size_t count, uint64_t* witnesses_out, uint8_t* old_roots, uint8_t* new_roots,
                             uint8_t* flags, uint32_t* status) {
-    if (!ctx || !c || !tree || !accounts_inout ||
-        (count && (!messages || !signatures || !witnesses_out || !old_roots || !new_roots || !flags || !status)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "transfer_witness_at: bad arguments");
-    SWM_TRY(tr_check_tree(ctx, "transfer_witness_at", c, tree));
-    if (!count) return SWM_OK;
-    if (count > 0x7FFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "transfer_witness_at: %zu transfers in one call", count);
-    const TrBlock b = {messages, signatures, old_roots, new_roots, flags, status};
-    return tr_block(ctx, "transfer_witness_at", nullptr, c, tree, accounts_inout, b, count, witnesses_out, nullptr, 0, nullptr, 0, nullptr);
+    return transfer_witness_at<TransferUnit>(ctx, c, tree, accounts_inout, messages, signatures, count, witnesses_out, old_roots, new_roots, flags,
+                                             status);
 }
 
 int swm_transfer_prove_many_at(swm_ctx* ctx, const swm_pk* pk, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* accounts_inout,
                                const uint8_t* messages, const uint8_t* signatures, size_t count, swm_rng* rng, unsigned prove_flags,
                                uint8_t* proofs_out, size_t proof_cap, size_t* lens, uint8_t* old_roots, uint8_t* new_roots, uint8_t* flags,
                                uint32_t* status) {
-    if (!ctx || !pk || !c || !tree || !accounts_inout || !rng || (count && (!messages || !signatures || !proofs_out || !lens || !flags || !status)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "transfer_prove_many_at: bad arguments");
-    SWM_TRY(tr_check_tree(ctx, "transfer_prove_many_at", c, tree));
-    if (!count) return SWM_OK;
-    if (count > 0x7FFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "transfer_prove_many_at: %zu transfers in one call", count);
-    for (size_t i = 0; i < count; i++) {  // whatever ends the call, every entry has been written
-        lens[i] = 0;
-        flags[i] = 0;
-        status[i] = 0;
-    }
-    const TrBlock b = {messages, signatures, old_roots, new_roots, flags, status};
-    return tr_block(ctx, "transfer_prove_many_at", pk, c, tree, accounts_inout, b, count, nullptr, rng, prove_flags, proofs_out, proof_cap, lens);
+    return transfer_prove_many_at<TransferUnit>(ctx, pk, c, tree, accounts_inout, messages, signatures, count, rng, prove_flags, proofs_out,
+                                                proof_cap, lens, old_roots, new_roots, flags, status);
 }
 
 int swm_transfer_prove_at(swm_ctx* ctx, const swm_pk* pk, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* accounts_inout,

@@ -3,6 +3,7 @@
 // item i's block at d_witness + i * stride; the stand-alone circuits pass their own num_witness as the stride, a composed circuit
 // its larger one with d_witness moved to the block's first element.  And the parts of a payment's witness pass that do not depend
 // on the account tree's hash (payment_witness.hip defines them; pedersen_payment_witness.hip calls them with its own offsets).
+// Kernel launchers only: the host layer above them is witness_host.h and ledger_witness_host.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -56,27 +57,6 @@ int payment_prep_run(swm_ctx* ctx, const uint8_t* d_msgs, const uint8_t* d_sende
 int payment_bits_run(swm_ctx* ctx, size_t n, size_t stride, size_t balance_at, size_t recipient_bits_at, unsigned levels, const uint8_t* d_msgs,
                      const uint8_t* d_sender_leaves, const uint8_t* d_recipient_leaves, const uint32_t* d_sender_sib,
                      const uint32_t* d_recipient_sib, const uint8_t* d_sig_ok, Fr* d_w, uint8_t* d_flags, uint32_t* d_status);
-// the host forms' checks: what the device form reports per item (the sibling arrays may be NULL)
-int py_check(swm_ctx* ctx, const char* what, size_t height, const uint8_t* msgs, const uint8_t* sender_leaves, const uint8_t* sender_sib,
-             const uint8_t* recipient_sib, size_t count);
-int py_drained(swm_ctx* ctx, int rc);  // an error leaves nothing of this call queued behind it
-
-struct PyStaged {
-    const uint8_t *msgs, *sigs, *sender_leaves, *recipient_leaves, *sender_sib, *recipient_sib;
-};
-// signatures | sender leaves | recipient leaves | the two sibling arrays (may be NULL) | messages of n payments into "stage.a"
-int py_stage(swm_ctx* ctx, size_t levels, const uint8_t* msgs, const uint8_t* sigs, const uint8_t* sender_leaves,
-             const uint8_t* recipient_leaves, const uint8_t* sender_sib, const uint8_t* recipient_sib, size_t n, PyStaged* out);
-
-// The host forms hold at most this many bytes of witnesses on the device at a time; a larger batch goes in chunks.
-static constexpr size_t PY_STAGE_BYTES = (size_t)1 << 30;
-
-struct PyOut {  // "payment.w": witnesses | sender roots | recipient roots | status | flags
-    Fr* w;
-    uint32_t *roots_s, *roots_r, *status;
-    uint8_t* flags;
-};
-int py_out(swm_ctx* ctx, size_t num_witness, size_t n, PyOut* out);
 
 // ---- Pedersen sections (pedersen_payment_witness.hip): the leaf stages and the level stages of every section of n items, one
 // launch each.  Section k of item i: the 72-byte leaf at leaves + 72 i, cur_0 .. cur_L at dig + dig_stride i (words), the L
@@ -104,16 +84,5 @@ int transfer_prep_run(swm_ctx* ctx, const uint8_t* d_msgs, const uint8_t* d_acco
 // sender new | recipient in the tree of R1 | recipient new), R1 = the last of the sender's new digests (n x (levels + 1) x 8 words).
 int transfer_bits_run(swm_ctx* ctx, size_t n, size_t stride, size_t balance_at, size_t sum_at, size_t r1_at, size_t recipient_bits_at,
                       unsigned levels, const uint8_t* d_leaves, const uint32_t* d_sender_new_dig, Fr* d_w);
-
-// the prover over one transfer's device witnesses; public input one, old_root, new_root (32 canonical bytes each), sender,
-// recipient, amount
-int transfer_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size_t num_constraints, const uint8_t* old_root, const uint8_t* new_root,
-                        const uint8_t* msg, const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len);
-
-// the prover over one item's device witnesses; public input one, root, sender, recipient, amount
-int py_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size_t num_constraints, const Fr& root_mont, const uint8_t* msg,
-                  const Fr* d_w, swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len);
-// a resident tree's root (d_root: its last node) in Montgomery form; synchronises the stream
-int py_root_mont(swm_ctx* ctx, const uint8_t* d_root, Fr* root_mont);
 
 }  // namespace swm

@@ -1,11 +1,12 @@
 // pedersen_transfer_shape_check.cpp — csrc/host/pedersen_transfer_shape.h printed for every height and both salt settings, held to
-// the formulas and to a cover of [0, num_witness) by its groups, and its chunk planner on small caps.  Built with
+// the formulas and to a cover of [0, num_witness) by its groups, and the chunk planner every circuit unit cuts a batch by
+// (csrc/host/witness_chunks.h) on small caps and on the library's own.  Built with
 // -fsanitize=address,undefined and run by tests/test_pedersen_transfer_circuit_host.py, which compares every printed line with
 // workloads.pedersen_transfer_circuit_layout and with its own plan.
 // One line per shape: "shape height salted num_instance num_witness num_constraints balance diff sender sender_update r1
 // recipient_bits recipient sum recipient_update membership_witnesses update_witnesses section_rows update_rows pack_row
 // sender_root_row sender_r1_row recipient_r1_row sum_pack_row new_root_row"; one line per plan: "plan item_bytes count cap_bytes
-// base:count ..."; then "ok <cases checked>".
+// base:count ..."; "stage <WITNESS_STAGE_BYTES>"; then "ok <cases checked>".
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "host/pedersen_transfer_shape.h"
+#include "host/witness_chunks.h"
 
 using namespace swm;
 
@@ -92,11 +94,11 @@ static void refused(size_t height, bool salted) {
 // every plan: consecutive chunks from 0 that cover [0, count), each within the cap unless it holds one transfer, all but the last
 // equally long
 static void plan(size_t item_bytes, size_t count, size_t cap_bytes) {
-    std::vector<PtChunk> chunks(3);  // stale entries must go
-    if (!pedersen_transfer_plan(item_bytes, count, cap_bytes, &chunks)) fail("plan refused", item_bytes, count);
+    std::vector<WitnessChunk> chunks(3);  // stale entries must go
+    if (!witness_chunk_plan(item_bytes, count, cap_bytes, &chunks)) fail("plan refused", item_bytes, count);
     size_t next = 0;
     for (size_t i = 0; i < chunks.size(); i++) {
-        const PtChunk& c = chunks[i];
+        const WitnessChunk& c = chunks[i];
         if (c.base != next || c.count == 0) fail("chunks not consecutive", item_bytes, count);
         if (c.count > 1 && c.count > cap_bytes / item_bytes) fail("a chunk above the cap", item_bytes, count);
         if (i + 1 < chunks.size() && c.count != chunks[0].count) fail("a short chunk before the last", item_bytes, count);
@@ -104,7 +106,7 @@ static void plan(size_t item_bytes, size_t count, size_t cap_bytes) {
     }
     if (next != count || (count == 0) != chunks.empty()) fail("the chunks do not cover the block", item_bytes, count);
     printf("plan %zu %zu %zu", item_bytes, count, cap_bytes);
-    for (const PtChunk& c : chunks) printf(" %zu:%zu", c.base, c.count);
+    for (const WitnessChunk& c : chunks) printf(" %zu:%zu", c.base, c.count);
     printf("\n");
     checked++;
 }
@@ -122,12 +124,14 @@ int main() {
     for (size_t count : {(size_t)0, (size_t)1, (size_t)2, (size_t)3, (size_t)7, (size_t)8, (size_t)9, (size_t)65})
         for (size_t cap : {(size_t)0, item - 1, item, 2 * item - 1, 2 * item, 3 * item + 5, 8 * item, 100 * item}) plan(item, count, cap);
     if (!pedersen_transfer_shape(9, false, &s)) fail("height 9", 9, 0);
-    plan(32 * s.num_witness, 1000, PT_STAGE_BYTES);  // the library's own cap
+    plan(32 * s.num_witness, 1000, WITNESS_STAGE_BYTES);  // the library's own cap
     plan(1, 5, SIZE_MAX);
     plan(SIZE_MAX, 3, SIZE_MAX - 1);
-    std::vector<PtChunk> none(2);
-    if (pedersen_transfer_plan(0, 4, 100, &none) || !none.empty() || pedersen_transfer_chunk_items(0, 100) != 0) fail("item_bytes 0", 0, 4);
+    std::vector<WitnessChunk> none(2);
+    if (witness_chunk_plan(0, 4, 100, &none) || !none.empty() || witness_chunk_items(0, 100) != 0) fail("item_bytes 0", 0, 4);
+    for (const WitnessChunk c : WitnessChunks(0, 4)) fail("a chunk of no items", c.base, c.count);
     checked++;
+    printf("stage %zu\n", (size_t)WITNESS_STAGE_BYTES);
     printf("ok %zu\n", checked);
     return 0;
 }

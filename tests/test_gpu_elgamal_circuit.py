@@ -219,6 +219,27 @@ def test_a_batch_of_300_on_both_paths(EG, G, oracle, params, circuit, resident):
         assert ct[i].tobytes() == want_ct
 
 
+@pytest.mark.parametrize("count,chunk", [(7, 3), (3, 1)])
+def test_batch_across_a_chunk_seam(EG, G, oracle, params, circuit, count, chunk):
+    """The host forms with their stage cap moved (swm_selftest_witness_stage): 7 items at a cap of 3 items' witness bytes + 5 go in
+    chunks of 3, 3 and 1, 3 items at a cap one byte short of an item one by one (a cap below one item once meant no progress: this
+    unit had no floor of one item).  Every witness and ciphertext the builder's; the resident key's path gives the same words."""
+    items = [_valid(G, i % 3) for i in (2, 0, 1, 0, 2, 1, 0)][:count]
+    cap = 3 * 32 * NW + 5 if chunk == 3 else 32 * NW - 1
+    with circuit.ctx.selftest_witness_stage(cap):
+        _check_batch(oracle, circuit, items)
+        key0 = _valid(G, 0)[0]
+        keys, msgs, rs = _arrays([(key0,) + it[1:] for it in items])
+        resident = EG.ResidentKey(E.point_from_bytes(key0), params.ctx)
+        try:
+            w_to, ct_to = circuit.witness_many(resident, msgs, rs)
+        finally:
+            resident.free()
+        w, ct = circuit.witness_many(keys, msgs, rs)
+    assert np.array_equal(w_to, w) and np.array_equal(ct_to, ct)
+    assert np.array_equal(ct, EG.encrypt_many(params, keys, msgs, rs))
+
+
 def test_device_form_with_a_bad_item_in_the_middle(EG, G, oracle, params, circuit):
     from simpleworks_amd._lib import DeviceBuffer, SwmError
     ctx = circuit.ctx

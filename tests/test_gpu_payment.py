@@ -225,6 +225,26 @@ def test_whole_witness_from_all_three_entries(M, ref, oracle, circuits, world, d
     assert np.array_equal(dev_at[0], at) and list(dev_at[1]) == list(flags) and not dev_at[2].any()
 
 
+@pytest.mark.parametrize("count,chunk", [(7, 3), (3, 1)])
+def test_witness_across_a_chunk_seam(oracle, circuits, world, device_trees, count, chunk):
+    """Both host forms with their stage cap moved (swm_selftest_witness_stage): 7 payments at a cap of 3 payments' witness bytes + 5
+    go in chunks of 3, 3 and 1, 3 payments at a cap one byte short of a payment one by one.  Height 2, whose two payments
+    alternate through the batch, so that neighbours differ; witnesses, flags and roots are the one-chunk test's."""
+    payments, leaves, levels = world(2)
+    assert len(payments) == 2
+    ps = [payments[k % 2] for k in range(count)]      # A B A | B A B | A: a chunk read or written at another chunk's base shows
+    c = circuits(2)
+    item = 32 * c.shape()[1]
+    with c.ctx.selftest_witness_stage(3 * item + 5 if chunk == 3 else item - 1):
+        witness, flags, roots_s, roots_r = c.witness_many(_tuples(ps), [p["sender_path"] for p in ps], [p["recipient_path"] for p in ps])
+        at, at_flags = c.witness_at(device_trees(2), _tuples(ps))
+    assert witness.shape == (count, c.shape()[1], 4) and list(flags) == [p["flag"] for p in ps] == list(at_flags)
+    assert roots_s == [levels[-1][0]] * count == roots_r
+    for k, p in enumerate(ps):
+        _same(witness[k], oracle(2, None, p)[0], "item %d: %s" % (k, p["name"]))
+    assert np.array_equal(at, witness)
+
+
 @pytest.fixture(scope="module")
 def system(M, W, ref_params, world):
     """The builder's system of the valid payment at height 4, packed once: its matrices serve every payment of that shape."""
@@ -383,6 +403,23 @@ def test_block_of_proofs_equals_single_calls(M, circuits, world, device_trees, k
                 M.generate_payment_proof(pk, c, tree, q["message"], q["signature"], q["sender_leaf"], q["recipient_leaf"], rng)
             assert e.value.code == -5
     assert M.generate_payment_proofs(pk, c, tree, [], M.generate_rand()) == ([], [])
+
+
+def test_block_of_proofs_across_chunk_seams(M, circuits, world, device_trees, keys):
+    """swm_payment_prove_many_at with the stage cap one byte short of a payment (swm_selftest_witness_stage): every payment is a
+    chunk of its own, and proofs and lengths are those of three single calls from the same rng state."""
+    payments = world(4)[0]
+    pk, _ = keys
+    c, tree = circuits(4), device_trees(4)
+    block = [payments[0], payments[2], payments[7]]
+    assert pk.ctx is c.ctx      # the prover's context is the one whose cap moves
+    with c.ctx.selftest_witness_stage(32 * c.shape()[1] - 1):
+        proofs, flags = M.generate_payment_proofs(pk, c, tree, _tuples(block), M.generate_rand())
+    assert flags == [3, 3, 3]
+    rng = M.generate_rand()
+    for q, proof in zip(block, proofs):
+        single = M.generate_payment_proof(pk, c, tree, q["message"], q["signature"], q["sender_leaf"], q["recipient_leaf"], rng)
+        assert proof == single and len(single) > 0, q["name"]
 
 
 def test_ledger_over_a_poseidon_tree(M, L, ref_params):

@@ -258,6 +258,38 @@ def test_item_i_of_a_block_equals_the_single_call(circuits, world, count):
     assert np.array_equal(host, block[0]) and list(flags) == [p["flag"] for p in ps]
 
 
+@pytest.fixture(scope="module")
+def seam_pool(M, params, world):
+    """Seven payments at height 2 with the builder's witness of each: valid both ways, to oneself, an amount of zero, a flipped
+    signature, an overdraft."""
+    tree, leaves = world(2)
+    ps = [_payment(tree, leaves, SECRETS[0], 0, 1, 300), _payment(tree, leaves, SECRETS[1], 1, 0, 5),
+          _payment(tree, leaves, SECRETS[0], 0, 0, 1000), _payment(tree, leaves, SECRETS[1], 1, 1, 0),
+          _payment(tree, leaves, SECRETS[0], 0, 1, 1, flip_signature=True), _payment(tree, leaves, SECRETS[1], 1, 0, 6),
+          _payment(tree, leaves, SECRETS[0], 0, 1, 7)]
+    return [(p, _oracle(M, params, 2, p)[0]) for p in ps]
+
+
+@pytest.mark.parametrize("count,chunk", [(7, 3), (3, 1)])
+def test_witness_across_a_chunk_seam(circuits, world, seam_pool, count, chunk):
+    """Both host forms with their stage cap moved (swm_selftest_witness_stage): 7 payments at a cap of 3 payments' witness bytes + 5
+    go in chunks of 3, 3 and 1, 3 payments at a cap one byte short of a payment one by one.  Height 2; witnesses, flags and roots
+    are what one chunk gives: the builder's, the model's, the tree's."""
+    tree, _ = world(2)
+    ps = [p for p, _ in seam_pool[:count]]
+    c = circuits(2)
+    item = 32 * c.shape()[1]
+    with c.ctx.selftest_witness_stage(3 * item + 5 if chunk == 3 else item - 1):
+        witness, flags, roots_s, roots_r = c.witness_many(_tuples(ps), [p["sender_path"] for p in ps], [p["recipient_path"] for p in ps])
+        at, at_flags = c.witness_at(tree, _tuples(ps))
+    assert witness.shape == (count, c.shape()[1], 4) and list(flags) == [p["flag"] for p in ps] == list(at_flags)
+    assert [p["flag"] for p in seam_pool[4][0:1]] == [2] and seam_pool[5][0]["flag"] == 1
+    assert roots_s == [tree.root()] * count == roots_r
+    for k, (_, w) in enumerate(seam_pool[:count]):
+        _same(witness[k], w, "payment %d" % k)
+    assert np.array_equal(at, witness)
+
+
 def test_refusals(W, L, circuits, world, crh, sig_params):
     from simpleworks_amd import hash as H
     from simpleworks_amd._lib import SwmError
@@ -379,6 +411,23 @@ def test_block_of_proofs_goes_on_after_each_failure(M, circuits, world, system, 
     assert M.verify_proof(vk, [root, 3, 0, 5], M.MarlinProof(proofs[3]), M.generate_rand())
     assert not M.verify_proof(vk, [root, 0, 3, 300], M.MarlinProof(proofs[3]), M.generate_rand())
     assert M.generate_pedersen_payment_proofs(pk, c, tree, [], M.generate_rand()) == ([], [])
+
+
+def test_block_of_proofs_across_chunk_seams(M, circuits, world, system, keys):
+    """swm_pedersen_payment_prove_many_at with the stage cap one byte short of a payment (swm_selftest_witness_stage): every
+    payment is a chunk of its own, and proofs and lengths are those of three single calls from the same rng state."""
+    tree, leaves = world(3)
+    pk, _ = keys
+    c = circuits(3)
+    block = [system[0], _payment(tree, leaves, SECRETS[1], 3, 0, 5), _payment(tree, leaves, SECRETS[0], 0, 0, 1000)]
+    assert pk.ctx is c.ctx      # the prover's context is the one whose cap moves
+    with c.ctx.selftest_witness_stage(32 * c.shape()[1] - 1):
+        proofs, flags = M.generate_pedersen_payment_proofs(pk, c, tree, _tuples(block), M.generate_rand())
+    assert flags == [3, 3, 3]
+    rng = M.generate_rand()
+    for q, proof in zip(block, proofs):
+        single = M.generate_pedersen_payment_proof(pk, c, tree, q["message"], q["signature"], q["sender_leaf"], q["recipient_leaf"], rng)
+        assert proof == single and len(single) > 0
 
 
 def test_ledger_over_its_default_pedersen_tree(M, L):

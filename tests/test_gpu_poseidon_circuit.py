@@ -160,6 +160,17 @@ def test_batch_counts_at_the_lane_and_workgroup_edges(oracle, circuits, count):
     _check_bytes(oracle, circuits(input_len=11), [P.poseidon_input(11, i) for i in range(count)])
 
 
+@pytest.mark.parametrize("count,chunk", [(7, 3), (3, 1)])
+def test_bytes_form_across_a_chunk_seam(oracle, circuits, count, chunk):
+    """The host form with its stage cap moved (swm_selftest_witness_stage): 7 items at a cap of 3 items' witness bytes + 5 go in
+    chunks of 3, 3 and 1, 3 items at a cap one byte short of an item one by one.  11 bytes: the shortest input of this module at
+    which items differ."""
+    c = circuits(input_len=11)
+    item = 32 * c.shape()[1]
+    with c.ctx.selftest_witness_stage(3 * item + 5 if chunk == 3 else item - 1):
+        _check_bytes(oracle, c, [P.poseidon_input(11, i) for i in range(count)])
+
+
 def test_a_thousand_items_against_the_native_hash(oracle, sponge, circuits):
     msgs = [P.poseidon_input(55, i) for i in range(1000)]
     _, outputs = _check_bytes(oracle, circuits(input_len=55), msgs, items=(0, 63, 64, 999))

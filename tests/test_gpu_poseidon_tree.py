@@ -324,6 +324,27 @@ def test_witness_treeless_and_at(oracle, circuits, model_tree, device_trees, cou
     assert np.array_equal(at, witness)
 
 
+@pytest.mark.parametrize("count,chunk", [(7, 3), (3, 1)])
+def test_witness_across_a_chunk_seam(oracle, circuits, model_tree, device_trees, count, chunk):
+    """Both host forms with their stage cap moved (swm_selftest_witness_stage): 7 paths at a cap of 3 paths' witness bytes + 5 go in
+    chunks of 3, 3 and 1, 3 paths at a cap one byte short of a path one by one.  Height 2, one-byte leaves; every witness the
+    builder's, every root the model's, the resident tree's form the same words."""
+    height, leaf_len, n = 2, 1, 2
+    leaves, want = model_tree(leaf_len, n)
+    indices = [(11 * p + n - 1) % n for p in range(count)]
+    sib = [T.path(want, i) for i in indices]
+    mine = [leaves[i] for i in indices]
+    c = circuits(height, leaf_len)
+    item = 32 * c.shape()[1]
+    with c.ctx.selftest_witness_stage(3 * item + 5 if chunk == 3 else item - 1):
+        witness, roots = c.witness_many(mine, indices, sib)
+        at = c.witness_at(device_trees(leaf_len, n), mine, indices)
+    assert witness.shape == (count, c.shape()[1], 4) and roots == [want[-1][0]] * count
+    for p in range(count):
+        _same(witness[p], oracle(mine[p], indices[p], sib[p])[0], "path %d" % p)
+    assert np.array_equal(at, witness)
+
+
 def test_witness_refusals(HASH, sponge, circuits, model_tree, device_trees):
     from simpleworks_amd._lib import SwmError
     leaves, want = model_tree(55, 32)

@@ -125,6 +125,23 @@ def test_mixed_program_batches(PG, mixed, model, count):
     assert np.array_equal(w2, witness) and o2 == outputs and np.array_equal(s2, status)
 
 
+@pytest.mark.parametrize("count,chunk", [(7, 3), (3, 1)])
+def test_mixed_program_across_a_chunk_seam(PG, mixed, model, count, chunk):
+    """The host form with its stage cap moved (swm_selftest_witness_stage): 7 items at a cap of 3 items' witness bytes + 5 go in
+    chunks of 3, 3 and 1, 3 items at a cap one byte short of an item one by one.  Item 1 underflows: its status lands on its own
+    index whichever chunk holds it; witnesses, outputs and status are the one-chunk run's."""
+    gold = GOLDEN["mixed"]
+    item = 32 * mixed.shape()[1]
+    rows = PM.mixed_inputs(count, underflow=(1,))
+    with mixed.ctx.selftest_witness_stage(3 * item + 5 if chunk == 3 else item - 1):
+        witness, outputs, status = _run(PG, mixed, [p for p, _ in rows], [s for _, s in rows])
+    assert status.tolist() == [PM.UNDERFLOW if i == 1 else 0 for i in range(count)]
+    assert [PM.hexes(o) for i, o in enumerate(outputs) if i != 1] == [gold["outputs"][i] for i in range(count) if i != 1]
+    assert outputs == [PM.mixed_eval(pub, priv)[0] for pub, priv in rows]
+    for i, (pub, priv) in enumerate(rows):
+        _same(witness[i], model(mixed.tape, pub, priv), "item %d of %d" % (i, count))
+
+
 def test_refused_items_set_their_status_alone(PG, mixed, model):
     """A batch of 65 in which item 31 underflows and item 64 divides by zero: only their status bytes are set, every other item is
     what it is in the batch without them, and their own witnesses are the builder's — the documented wrapped values."""
@@ -281,3 +298,18 @@ def test_proofs_of_a_batch_with_one_refused_item(M, W, mixed, mixed_keys):
         assert proofs[i] == single and out == outputs[i]
         assert M.verify_proof(vk, W.program_public_inputs(mixed.tape, rows[i][0], out), M.MarlinProof(single), M.generate_rand())
     assert M.generate_program_proofs(pk, mixed, [], [], M.generate_rand()) == ([], [], [])
+
+
+def test_proofs_of_a_batch_across_chunk_seams(M, mixed, mixed_keys):
+    """swm_program_prove_many with the stage cap one byte short of an item (swm_selftest_witness_stage): every item is a chunk of its
+    own, and the proofs are those of three single calls from the same rng state."""
+    pk, _ = mixed_keys
+    rows = PM.mixed_inputs(3)
+    assert pk.ctx is mixed.ctx      # the prover's context is the one whose cap moves
+    with mixed.ctx.selftest_witness_stage(32 * mixed.shape()[1] - 1):
+        proofs, outputs, status = M.generate_program_proofs(pk, mixed, [p for p, _ in rows], [s for _, s in rows], M.generate_rand())
+    assert status == [0, 0, 0] and outputs == [PM.mixed_eval(pub, priv)[0] for pub, priv in rows]
+    rng = M.generate_rand()
+    for i in range(3):
+        single, out = M.generate_program_proof(pk, mixed, rows[i][0], rows[i][1], rng)
+        assert proofs[i] == single and len(single) > 0 and out == outputs[i]

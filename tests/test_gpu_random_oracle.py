@@ -194,6 +194,21 @@ def test_witness_of_unaligned_items(RO, oracle):
         assert digests[i].tobytes() == digest
 
 
+@pytest.mark.parametrize("count,chunk", [(7, 3), (3, 1)])
+def test_witness_across_a_chunk_seam(RO, oracle, count, chunk):
+    """The host form with its stage cap moved (swm_selftest_witness_stage): 7 items at a cap of 3 items' witness bytes + 5 go in
+    chunks of 3, 3 and 1, 3 items at a cap one byte short of an item one by one.  One byte of input, the shortest at which items
+    differ; every item's witness and digest are the builder's, as in one chunk."""
+    c = RO.Blake2sCircuit(1)
+    item = 32 * c.shape()[1]
+    a = (37 * np.arange(count, dtype=np.uint8) + 1).reshape(count, 1)
+    with c.ctx.selftest_witness_stage(3 * item + 5 if chunk == 3 else item - 1):
+        witness, digests = c.witness_many(a)
+    assert witness.shape == (count, c.shape()[1], 4) and np.array_equal(digests, digests_of(a))
+    for i in range(count):
+        _same(witness[i], oracle(a[i].tobytes())[0], "item %d of %d" % (i, count))
+
+
 def test_witness_device_form_and_an_empty_batch(RO, ctx, oracle):
     count, length = 3, 65
     a = batch(count, length, seed=4)

@@ -157,6 +157,24 @@ def test_batches_mix_valid_and_tampered(G, oracle, circuits):
     assert w0.shape[0] == 0 and ok0.size == 0
 
 
+@pytest.mark.parametrize("count,chunk", [(7, 3), (3, 1)])
+def test_batch_across_a_chunk_seam(G, oracle, circuits, count, chunk):
+    """The host form with its stage cap moved (swm_selftest_witness_stage): 7 items at a cap of 3 items' witness bytes + 5 go in
+    chunks of 3, 3 and 1, 3 items at a cap one byte short of an item one by one.  The empty message; valid and tampered items on
+    both sides of each seam, every witness the builder's and ok per item."""
+    _, key, msg, sig = _valid(G, 0)
+    _, key2, msg2, sig2 = _valid(G, 14)
+    flip_e = sig[:40] + bytes([sig[40] ^ 0x10]) + sig[41:]
+    flip_s = bytes([sig[0] ^ 1]) + sig[1:]
+    items = [(key, msg, sig), (key, msg, flip_e), (key2, msg, sig), (key, msg, flip_s), (key2, msg2, sig2), _valid(G, 28)[1:],
+             _valid(G, 42)[1:]][:count]
+    assert not _valid(G, 28)[0] and not _valid(G, 42)[0] and _valid(G, 28)[2] == _valid(G, 42)[2] == b""
+    c = circuits(0)
+    item = 32 * c.shape()[1]
+    with c.ctx.selftest_witness_stage(3 * item + 5 if chunk == 3 else item - 1):
+        _check_batch(oracle, c, False, items, [True, False, False, False, True, True, True][:count])
+
+
 def test_device_form_with_an_off_curve_key_in_the_middle(G, oracle, circuits):
     from simpleworks_amd._lib import DeviceBuffer, SwmError
     c = circuits(0)

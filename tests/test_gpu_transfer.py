@@ -222,6 +222,45 @@ def test_a_dependent_chain_in_one_block(W, circuits, world, fresh_tree, oracle):
         _check_item(W, c, oracle, height, "chain", block[k], w[k])
 
 
+@pytest.fixture(scope="module")
+def chain7(ref):
+    """The dependent chain and one more transfer out of the account the chain's last one credited: seven in all."""
+    first, block, table, levels = TM.transfers(ref, 4, which=TM.CHAIN + [("one to three", 1, 3, 5, None)])
+    assert [t["applied"] for t in block] == [True, True, False, False, True, True, True]
+    return first, block, table, levels
+
+
+@pytest.mark.parametrize("count,chunk", [(7, 3), (3, 1)])
+def test_the_dependent_chain_across_chunk_seams(W, circuits, chain7, fresh_tree, oracle, count, chunk):
+    """The host form with its stage cap moved (swm_selftest_witness_stage): the chain's 7 transfers at a cap of 3 transfers' witness
+    bytes + 5 go in chunks of 3, 3 and 1, its first 3 at a cap one byte short of a transfer one by one.  Transfer i + 1 is
+    witnessed against the state transfer i left, so a seam that lost the table or the tree would show: roots, flags, status, the
+    table and every node as the chain test compares them, every witness the one-chunk run's, the first of each later chunk the
+    builder's."""
+    height = 4
+    first, block = chain7[0], chain7[1][:count]
+    table = block[-1]["table"]
+    c, tree, twin, whole = circuits(height), fresh_tree(height, first), fresh_tree(height, first), fresh_tree(height, first)
+    item = 32 * c.shape()[1]
+    with c.ctx.selftest_witness_stage(3 * item + 5 if chunk == 3 else item - 1):
+        w, after, old, new, flags, status = c.witness_at(tree, first, _pairs(block))
+    assert list(flags) == [t["flag"] for t in block] and not status.any()
+    assert old == [t["public"][0] for t in block] and new == [t["public"][1] for t in block]
+    assert all(new[i] == old[i + 1] for i in range(count - 1))
+    assert new[-1] == tree.root() and after == table and (count < 7 or (after == chain7[2] and tree.root() == chain7[3][-1][0]))
+    for t in block:
+        if t["applied"]:
+            s, r = t["message"][0], t["message"][1]
+            twin.update(s, t["table"][s])
+            twin.update(r, t["table"][r])
+    assert np.array_equal(c.ctx.poseidon_tree_nodes(tree.h), c.ctx.poseidon_tree_nodes(twin.h))
+    w1, after1, old1, new1, flags1, status1 = c.witness_at(whole, first, _pairs(block))      # one chunk: the default cap
+    assert np.array_equal(w, w1) and after1 == after and (old1, new1) == (old, new)
+    assert np.array_equal(flags1, flags) and np.array_equal(status1, status)
+    for k in ((3, 6) if chunk == 3 else (1, 2)):
+        _check_item(W, c, oracle, height, "chain7", block[k], w[k])
+
+
 def _block_of_65():
     """65 transfers among accounts 1, 2, 3 whose outcomes depend on their order; items 0, 63 and 64 are refused."""
     ring = [(1, 2), (2, 3), (3, 1)]
@@ -342,6 +381,25 @@ def test_block_of_proofs_equals_single_calls(M, L, circuits, world, fresh_tree, 
             assert not L.verify_transfer(vk, [pub[0], pub[0]] + pub[2:], proof, M.generate_rand())
     assert accounts == table
     assert M.generate_transfer_proofs(pk, c, tree, table, [], M.generate_rand())[0] == []
+
+
+def test_block_of_proofs_across_chunk_seams(M, circuits, chain7, fresh_tree, keys):
+    """swm_transfer_prove_many_at with the stage cap one byte short of a transfer (swm_selftest_witness_stage): every transfer is a
+    chunk of its own, and proofs, public inputs and the table are those of three single calls from the same rng state."""
+    first, block = chain7[0], chain7[1][:3]
+    pk, _ = keys
+    c, tree, twin = circuits(4), fresh_tree(4, first), fresh_tree(4, first)
+    assert pk.ctx is c.ctx      # the prover's context is the one whose cap moves
+    with c.ctx.selftest_witness_stage(32 * c.shape()[1] - 1):
+        proofs, public, flags, status, after = M.generate_transfer_proofs(pk, c, tree, first, _pairs(block), M.generate_rand())
+    assert flags == [t["flag"] for t in block] and status == [0, 0, 0] and after == block[-1]["table"]
+    assert [p is not None for p in proofs] == [True, True, False] and public == [t["public"] for t in block]
+    rng = M.generate_rand()
+    accounts = first
+    for t, proof, pub in zip(block, proofs, public):
+        single, pub1, _, _, accounts = M.generate_transfer_proof(pk, c, twin, accounts, t["message"], t["signature"], rng)
+        assert single == proof and pub1 == pub, t["name"]
+    assert accounts == after and tree.root() == twin.root()
 
 
 def test_the_ledger_applies_a_block(M, L, ref_params):

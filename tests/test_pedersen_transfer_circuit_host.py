@@ -3,7 +3,7 @@ order (tests/pedersen_transfer_model.py), the circuit's specification workloads.
 Python integers at heights 2 and 3 — a valid transfer, a wrong new_root, a wrong R1, an overflow, an overdraft, a recipient sibling
 taken from the old tree — and every refusal of a block at height 4, its sender side against build_pedersen_payment, its layout
 against the built system, and its SHAPE and chunk plan as the library states them without a GPU
-(swm_pedersen_transfer_circuit_shape, csrc/host/pedersen_transfer_shape.h)."""
+(swm_pedersen_transfer_circuit_shape, csrc/host/pedersen_transfer_shape.h, csrc/host/witness_chunks.h)."""
 import ctypes
 import os
 import shutil
@@ -328,7 +328,8 @@ def _plan(item_bytes, count, cap_bytes):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_shape_header_and_chunk_planner_under_asan_ubsan(tmp_path):
-    """csrc/host/pedersen_transfer_shape.h — counts, offsets, named rows and the chunk planner — printed by a stand-alone program
+    """csrc/host/pedersen_transfer_shape.h — counts, offsets, named rows — and the chunk planner of csrc/host/witness_chunks.h,
+    which every circuit unit cuts a batch by, printed by a stand-alone program
     (tests/native/pedersen_transfer_shape_check.cpp) built with -fsanitize=address,undefined: every shape line against the layout,
     every plan line against the plan computed here (small caps: below one transfer, exactly k transfers, one byte short of k)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -366,3 +367,5 @@ def test_shape_header_and_chunk_planner_under_asan_ubsan(tmp_path):
     # the library's own cap at height 9: floor(1 GiB / (32 x 200274)) = 167 transfers per chunk
     big = by_args[32 * 200274, 1000, 1 << 30]
     assert big[0] == "0:167" and big[-1] == "835:165" and len(big) == 6
+    # ... which is written once, in witness_chunks.h
+    assert [l for l in lines if l.startswith("stage ")] == ["stage %d" % (1 << 30)]
