@@ -18,6 +18,38 @@
  *   - the caller owns every host buffer for the duration of a call; the library never retains host pointers.
  *   - functions suffixed _dev take DEVICE pointers (hipMalloc'd or a torch tensor's data_ptr) and enqueue on the
  *     context's stream without a host copy of the bulk data; the plain forms take HOST pointers and stage.
+ *   - stream order of the _dev forms (held by tests/test_gpu_stream_order.py on a caller-owned stream).  Every launch and copy of
+ *     a _dev entry point is ordered behind what is already queued on the context's stream — the library's auxiliary streams fork
+ *     from it and join it again — so a caller may queue an input's upload before the call and an output's read after it on that
+ *     stream, with no host wait in between.  A call that has to replace a scratch buffer by a larger one waits for the context's
+ *     streams first; a call that finds its buffers large enough does not.  What each entry does before it returns:
+ *       swm_batch_inverse_fr_dev                returns without waiting.
+ *       swm_blake2s_hash_dev                    returns without waiting.
+ *       swm_blake2s_witness_dev                 returns without waiting.
+ *       swm_elgamal_witness_dev                 returns without waiting.
+ *       swm_elgamal_witness_to_dev              returns without waiting.
+ *       swm_merkle_tree_build_dev               returns without waiting.
+ *       swm_merkle_tree_create_from_leaves_dev  returns without waiting (it allocates the node buffer).
+ *       swm_merkle_tree_paths_dev               returns without waiting.
+ *       swm_merkle_tree_update_dev              returns without waiting when at most 4 distinct leaves are touched; above that it
+ *                                               uploads an index list from its own frame and waits for the stream.  `indices` is
+ *                                               the caller's again as soon as the call has returned, in both cases.
+ *       swm_merkle_verify_paths_dev             returns without waiting.
+ *       swm_merkle_witness_dev                  returns without waiting.
+ *       swm_msm_g1_dev                          waits: out_jac is a host value.
+ *       swm_ntt_fr_dev                          returns without waiting (the first call of a size builds its twiddle tables with
+ *                                               a blocking copy).
+ *       swm_ntt_fr_sharded_dev                  waits for the stream before it returns, with one rank as with several.
+ *       swm_payment_witness_dev                 returns without waiting.
+ *       swm_pedersen_hash_dev                   returns without waiting.
+ *       swm_pedersen_payment_witness_dev        returns without waiting.
+ *       swm_poseidon_hash_bytes_dev             returns without waiting.
+ *       swm_poseidon_hash_fr_dev                returns without waiting.
+ *       swm_poseidon_witness_dev                returns without waiting.
+ *       swm_program_witness_dev                 returns without waiting.
+ *       swm_schnorr_witness_dev                 returns without waiting.
+ *       swm_spmv_fr_dev                         waits: the row statistics that pick its schedule are read back to the host.
+ *       swm_vec_mul_fr_dev                      returns without waiting; d_out may be d_a.
  *   - a context is bound to one GPU and one HIP stream; use one context per host thread.
  *   - there is NO CPU fallback: every compute entry point fails with SWM_ERR_NO_DEVICE when no gfx950 GPU is usable.
  */
@@ -52,7 +84,9 @@ void swm_destroy(swm_ctx *ctx);
 /* detail of the last failure on this context; ctx == NULL: of the last context-free call (verify, codecs) on the
  * calling thread */
 const char *swm_last_error(swm_ctx *ctx);
-/* Enqueue on an externally owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL restores the own stream. */
+/* Enqueue on an externally owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL restores the own stream.
+ * Waits for what the context has queued on the stream it leaves, so nothing of the library is pending there afterwards; from
+ * then on the library touches the new stream only (and its own auxiliary streams, which fork from it and join it). */
 int swm_set_stream(swm_ctx *ctx, void *hip_stream);
 int swm_synchronize(swm_ctx *ctx);
 /* device memory helpers so that a caller without a HIP binding can keep operands resident in HBM */

@@ -548,6 +548,11 @@ class Context:
         self._check(self.lib.swm_vec_mul_fr(self.h, _p64(a), _p64(b), _p64(out), a.shape[0]), "swm_vec_mul_fr")
         return out
 
+    def vec_mul_fr_dev(self, d_a, d_b, d_out, n):
+        """d_out[i] = d_a[i] * d_b[i] over n Montgomery elements on the device (DeviceBuffer or raw addresses); d_out may be d_a."""
+        p = self._dev_ptr
+        self._check(self.lib.swm_vec_mul_fr_dev(self.h, p(d_a), p(d_b), p(d_out), n), "swm_vec_mul_fr_dev")
+
     # ---- Pedersen CRH + Merkle tree (include/swmarlin.h; simpleworks_amd/hash.py is the caller-facing mirror)
     def pedersen_create(self, generators_xy, num_windows, window_size):
         """generators_xy: num_windows * window_size affine points, 64 bytes each (x || y, little-endian standard form)."""
@@ -570,6 +575,11 @@ class Context:
         self._check(self.lib.swm_pedersen_hash(self.h, handle, a.ctypes.data, a.shape[1], a.shape[0], out.ctypes.data),
                     "swm_pedersen_hash")
         return out
+
+    def pedersen_hash_dev(self, handle, d_inputs, input_len, count, d_digests):
+        """count inputs of input_len bytes back to back on the device -> count x 32 digest bytes (DeviceBuffer or raw addresses)."""
+        p = self._dev_ptr
+        self._check(self.lib.swm_pedersen_hash_dev(self.h, handle, p(d_inputs), input_len, count, p(d_digests)), "swm_pedersen_hash_dev")
 
     def merkle_tree_build(self, leaf_handle, two_to_one_handle, leaves):
         """leaves: uint8 [n, leaf_len] -> uint8 [2 n - 1, 32]: n leaf digests | n / 2 | ... | root."""

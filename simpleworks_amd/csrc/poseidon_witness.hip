@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(PS_LANES) poseidon_witness_kernel(const uint4*
             }
         }
     }
-    if (!BYTES && status && act) status[item] = bad ? 1u : 0u;
+    if (status && act) status[item] = bad ? 1u : 0u;  // (the bytes form refuses nothing: its items are all "computed", 0)
     if (BYTES) {
         // the bit section: the wave walks its items, the lanes walk the bits — lane l writes witness l, l + 64, ... of the item
         const Fr f_one = fp_one<Fr>();
