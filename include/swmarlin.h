@@ -998,6 +998,54 @@ int swm_pedersen_transfer_prove_at(swm_ctx *ctx, const swm_pk *pk, const swm_ped
                                    unsigned prove_flags, uint8_t *proof_out, size_t cap, size_t *len, uint8_t old_root[32],
                                    uint8_t new_root[32], uint8_t *flag, uint32_t *status);
 
+/* ---------------------------------------------------------------------------------------------- Rollup: one proof for a block of transfers
+ * The assignment of the rollup circuit (simpleworks_amd/workloads.py, build_rollup over the Poseidon account tree,
+ * build_pedersen_rollup over the Pedersen one) synthesised on the GPU: ONE statement old_root -> new_root through N transfers applied
+ * in order; the roots in between are witnesses.  There is no handle of its own: a rollup takes a transfer circuit and N = count,
+ * 1 <= N <= 64.  With W_t, R_t the transfer circuit's num_witness and num_constraints:  num_instance = 3 + 3 N (one, old_root,
+ * new_root, then sender_k, recipient_k, amount_k);  num_witness = N (W_t + 1) - 1: section k is transfer k's W_t witnesses at
+ * k (W_t + 1), and for k < N - 1 the root after transfer k follows at offset W_t of the section;  num_constraints = N R_t: section k is
+ * the transfer's rows with old_root read as that root (the instance's for k = 0), new_root as the next one (the instance's for k =
+ * N - 1) and sender, recipient, amount as those of index k.  N = 1 is the transfer circuit's own system.
+ * swm_rollup_circuit_shape / swm_pedersen_rollup_circuit_shape need no GPU; they refuse what the transfer circuit's shape call
+ * refuses and an n outside 1 .. 64.
+ * swm_rollup_witness_at / swm_pedersen_rollup_witness_at: circuit, tree, accounts_inout, messages (count x 10 bytes) and signatures
+ * (count x 64) as swm_transfer_witness_at takes them; a tree that is not the circuit's, a count outside 1 .. 64 and a block whose
+ * witness_out exceeds 1 GiB (a block is one vector: it is never chunked) are refused with SWM_ERR_INVALID_ARG before anything runs,
+ * and so is, by the pass itself, a table that is not the tree's leaf level; tree and table are then as they were.  The pass is
+ * swm_transfer_witness_at's at a section stride of W_t + 1, one kernel more links the sections.  ALL OR NOTHING: *applied = 1 when every
+ * transfer was applied; the tree then holds new_root and accounts_inout the balances after the block.  *applied = 0 when any
+ * transfer was refused: THE BLOCK IS ROLLED BACK, the tree's nodes and accounts_inout are byte for byte what they were before the
+ * call, and new_root = old_root.  flags and status (one per transfer, the bits of swm_transfer_witness_at) are what the SEQUENTIAL
+ * pass met: transfer i was tried against the state transfers 0 .. i-1 left, those of them that the pass applied included, so in a
+ * rolled-back block bit 4 of flags[i] means "was applied during the pass", not "is applied now".  witness_out: num_witness x 4
+ * Montgomery limbs, written whatever the verdict (a rolled-back block's is that of the pass: an unsatisfied system); old_root,
+ * new_root: 32 canonical bytes each.  The entry returns after everything it queued has completed.
+ * swm_rollup_prove_at / swm_pedersen_rollup_prove_at: the same pass, then ONE prover call over the block's vector where it lies on
+ * the device, with the 3 + 3 N public inputs above.  A key that is not that of a block of `count` transfers of this circuit is
+ * refused with SWM_ERR_MISMATCH before anything runs.  A rolled-back block: *len = 0, *applied = 0, SWM_OK, tree and table as they
+ * were.  THE TREE IS ADVANCED BEFORE THE PROOF IS MADE, as for transfers: a prover error after that ends the call with its code and
+ * tree and table stay advanced.  The entry waits for the pass before it proves and returns when the proof is on the host. */
+int swm_rollup_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64_t alpha, size_t height, int salted, size_t n,
+                             size_t *num_instance, size_t *num_witness, size_t *num_constraints);
+int swm_pedersen_rollup_circuit_shape(size_t height, int salted, size_t n, size_t *num_instance, size_t *num_witness,
+                                      size_t *num_constraints);
+int swm_rollup_witness_at(swm_ctx *ctx, const swm_transfer_circuit *circuit, swm_poseidon_tree *tree, uint8_t *accounts_inout,
+                          const uint8_t *messages, const uint8_t *signatures, size_t count, uint64_t *witness_out, uint8_t old_root[32],
+                          uint8_t new_root[32], uint8_t *flags, uint32_t *status, int *applied);
+int swm_rollup_prove_at(swm_ctx *ctx, const swm_pk *pk, const swm_transfer_circuit *circuit, swm_poseidon_tree *tree,
+                        uint8_t *accounts_inout, const uint8_t *messages, const uint8_t *signatures, size_t count, swm_rng *rng,
+                        unsigned prove_flags, uint8_t *proof_out, size_t cap, size_t *len, uint8_t old_root[32], uint8_t new_root[32],
+                        uint8_t *flags, uint32_t *status, int *applied);
+int swm_pedersen_rollup_witness_at(swm_ctx *ctx, const swm_pedersen_transfer_circuit *circuit, swm_merkle_tree *tree,
+                                   uint8_t *accounts_inout, const uint8_t *messages, const uint8_t *signatures, size_t count,
+                                   uint64_t *witness_out, uint8_t old_root[32], uint8_t new_root[32], uint8_t *flags, uint32_t *status,
+                                   int *applied);
+int swm_pedersen_rollup_prove_at(swm_ctx *ctx, const swm_pk *pk, const swm_pedersen_transfer_circuit *circuit, swm_merkle_tree *tree,
+                                 uint8_t *accounts_inout, const uint8_t *messages, const uint8_t *signatures, size_t count, swm_rng *rng,
+                                 unsigned prove_flags, uint8_t *proof_out, size_t cap, size_t *len, uint8_t old_root[32],
+                                 uint8_t new_root[32], uint8_t *flags, uint32_t *status, int *applied);
+
 /* ---------------------------------------------------------------------------------------------- Blake2s random oracle
  * The reference's random oracle, unkeyed BLAKE2s-256 (RFC 7693), batched: one GPU lane per hash.  Replaces, on the GPU,
  *   src/schnorr_signature/blake2s.rs, examples/simple-payments/random_oracle/blake2s/mod.rs      RO::evaluate(&(), input)

@@ -224,6 +224,17 @@ ABI = {
                                    + [ctypes.c_void_p] * 5),
     "swm_transfer_prove_at": (_int, [_vp, _vp, _vp, _vp] + [ctypes.c_void_p] * 3 + [_vp, ctypes.c_uint, ctypes.c_void_p, _sz]
                               + [ctypes.c_void_p] * 5),
+    "swm_rollup_circuit_shape": (_int, [_sz, _sz, ctypes.c_uint64, _sz, _int, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz),
+                                         ctypes.POINTER(_sz)]),
+    "swm_pedersen_rollup_circuit_shape": (_int, [_sz, _int, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "swm_rollup_witness_at": (_int, [_vp, _vp, _vp] + [ctypes.c_void_p] * 3 + [_sz] + [ctypes.c_void_p] * 5 + [ctypes.POINTER(_int)]),
+    "swm_pedersen_rollup_witness_at": (_int, [_vp, _vp, _vp] + [ctypes.c_void_p] * 3 + [_sz] + [ctypes.c_void_p] * 5 + [ctypes.POINTER(_int)]),
+    "swm_rollup_prove_at": (_int, [_vp, _vp, _vp, _vp] + [ctypes.c_void_p] * 3 + [_sz, _vp, ctypes.c_uint, ctypes.c_void_p, _sz,
+                                                                                   ctypes.POINTER(_sz)] + [ctypes.c_void_p] * 4
+                            + [ctypes.POINTER(_int)]),
+    "swm_pedersen_rollup_prove_at": (_int, [_vp, _vp, _vp, _vp] + [ctypes.c_void_p] * 3 + [_sz, _vp, ctypes.c_uint, ctypes.c_void_p, _sz,
+                                                                                            ctypes.POINTER(_sz)] + [ctypes.c_void_p] * 4
+                                     + [ctypes.POINTER(_int)]),
     "swm_blake2s_hash": (_int, [_vp, ctypes.c_void_p, _sz, _sz, ctypes.c_void_p]),
     "swm_blake2s_hash_dev": (_int, [_vp, _vp, _sz, _sz, _vp]),
     "swm_blake2s_circuit_shape": (_int, [_sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
@@ -1225,6 +1236,37 @@ class Context:
                                                               witness.ctypes.data, old.ctypes.data, new.ctypes.data, flags.ctypes.data,
                                                               status.ctypes.data), "swm_pedersen_transfer_witness_at")
         return witness, acc, old, new, flags, status
+
+    # ---- Rollup: one vector for a block of transfers over either tree (simpleworks_amd/ledger.py, RollupCircuit / PedersenRollupCircuit)
+    def rollup_witness_at(self, handle, tree_handle, num_witness, accounts, messages, signatures, guard=0, fill=None,
+                          _entry="swm_rollup_witness_at"):
+        """accounts uint8 [2^L, 72], messages uint8 [count, 10], signatures uint8 [count, 64]; num_witness: the BLOCK's -> (witness uint64
+        [num_witness + guard, 4] Montgomery limbs, accounts after the block (as they were when it was rolled back), old root uint8 [32],
+        new root, flags uint8 [count], status uint32 [count], applied bool).  guard: elements behind the vector, filled with 0xFF as
+        the vector is (a test's way to see a store past the end); fill: a byte for the other outputs."""
+        m = self._rows(messages, 10)
+        n = m.shape[0]
+        sig = self._rows(signatures, 64, n)
+        acc = np.array(accounts, dtype=np.uint8, order="C", copy=True)
+        assert acc.ndim == 2 and acc.shape[1] == 72
+        witness = np.empty((num_witness + guard, 4), dtype=np.uint64)
+        if guard:
+            witness.view(np.uint8).fill(0xFF)
+        old, new = np.empty(32, dtype=np.uint8), np.empty(32, dtype=np.uint8)
+        flags, status = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32)
+        if fill is not None:
+            for a in (old, new, flags, status):
+                a.view(np.uint8).fill(fill)
+        applied = ctypes.c_int(-1)
+        self._check(getattr(self.lib, _entry)(self.h, handle, tree_handle, acc.ctypes.data, m.ctypes.data, sig.ctypes.data, n,
+                                              witness.ctypes.data, old.ctypes.data, new.ctypes.data, flags.ctypes.data, status.ctypes.data,
+                                              ctypes.byref(applied)), _entry)
+        return witness, acc, old, new, flags, status, bool(applied.value)
+
+    def pedersen_rollup_witness_at(self, handle, tree_handle, num_witness, accounts, messages, signatures, guard=0, fill=None):
+        """rollup_witness_at against a resident Pedersen tree (a hash.DeviceMerkleTree's handle) and a Pedersen transfer circuit."""
+        return self.rollup_witness_at(handle, tree_handle, num_witness, accounts, messages, signatures, guard, fill,
+                                      "swm_pedersen_rollup_witness_at")
 
     # ---- Blake2s random oracle and its circuit's witness (include/swmarlin.h; simpleworks_amd/random_oracle.py is the caller-facing
     # mirror).  A device buffer is a DeviceBuffer or a raw device address (an int: a tensor's data_ptr()).

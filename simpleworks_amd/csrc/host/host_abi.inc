@@ -16,6 +16,7 @@
 #include "pedersen_payment_shape.h"
 #include "transfer_shape.h"
 #include "pedersen_transfer_shape.h"
+#include "rollup_shape.h"
 #include "program_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
@@ -352,6 +353,44 @@ int swm_pedersen_transfer_circuit_shape(size_t height, int salted, size_t* num_i
     if (!pedersen_transfer_shape(height, salted != 0, &s))
         return set_err(none, SWM_ERR_INVALID_ARG, "pedersen_transfer_circuit_shape: height %zu (%zu <= height <= %zu)", height,
                        (size_t)PP_MIN_HEIGHT, (size_t)PP_MAX_HEIGHT);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// The rollup circuit's shape: n sections of the transfer circuit of the same arguments, linked (rollup_shape.h; the layout is
+// build_rollup's)
+int swm_rollup_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64_t alpha, size_t height, int salted, size_t n,
+                             size_t* num_instance, size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "rollup_circuit_shape: NULL output");
+    TransferShape t;
+    RollupShape s;
+    if (!transfer_shape(full_rounds, partial_rounds, alpha, height, salted != 0, &t) || !rollup_shape(t.num_witness, t.num_constraints, n, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG,
+                       "rollup_circuit_shape: %zu transfers of %zu + %zu rounds, alpha %llu, height %zu (%zu <= transfers <= %zu, and what "
+                       "transfer_circuit_shape takes)",
+                       n, full_rounds, partial_rounds, (unsigned long long)alpha, height, (size_t)RU_MIN_TRANSFERS, (size_t)RU_MAX_TRANSFERS);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// The same over a Pedersen account tree (the layout is build_pedersen_rollup's)
+int swm_pedersen_rollup_circuit_shape(size_t height, int salted, size_t n, size_t* num_instance, size_t* num_witness,
+                                      size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "pedersen_rollup_circuit_shape: NULL output");
+    PedersenTransferShape t;
+    RollupShape s;
+    if (!pedersen_transfer_shape(height, salted != 0, &t) || !rollup_shape(t.num_witness, t.num_constraints, n, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG, "pedersen_rollup_circuit_shape: %zu transfers at height %zu (%zu <= transfers <= %zu, %zu <= "
+                       "height <= %zu)", n, height, (size_t)RU_MIN_TRANSFERS, (size_t)RU_MAX_TRANSFERS, (size_t)PP_MIN_HEIGHT,
+                       (size_t)PP_MAX_HEIGHT);
     *num_instance = s.num_instance;
     *num_witness = s.num_witness;
     *num_constraints = s.num_constraints;

@@ -2523,6 +2523,14 @@ void is_satisfied_impl(swm_ctx* ctx, const swm_r1cs* cs, int* ok, size_t* first_
 
 }  // namespace
 
+// witness_host.h: prove_shape's comparison from the counts alone, for a unit that changes state before it calls the prover
+namespace swm {
+bool pk_takes_shape(const swm_pk* pk, size_t num_instance, size_t num_witness, size_t num_constraints) {
+    const size_t inst = HDomain(num_instance).size, nv = inst + num_witness, side = nv > num_constraints ? nv : num_constraints;
+    return side == pk->info.num_constraints && side == pk->info.num_variables && inst == pk->info.num_instance_variables;
+}
+}  // namespace swm
+
 // ================================================================================================ C ABI
 #include "host/host_abi.inc"  // SWM_GUARD + every entry point that needs no GPU (rng, verifier, proof / vk codecs, hashes)
 

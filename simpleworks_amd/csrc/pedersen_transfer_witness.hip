@@ -44,14 +44,8 @@
 #include "schnorr.h"
 #include "swmarlin.h"
 #include "ledger_witness_host.h"
+#include "transfer_units.h"
 #include "witness_runs.h"
-
-struct swm_pedersen_transfer_circuit {
-    swm_schnorr_circuit schnorr;  // over PP_MSG_LEN bytes
-    const swm_pedersen* leaf = nullptr;
-    const swm_pedersen* inner = nullptr;
-    swm::PedersenTransferShape shape;
-};
 
 namespace swm {
 
@@ -222,9 +216,10 @@ static size_t pt_aux_bytes(size_t n, size_t levels) {
     return 64 * n + 4 * (4 * n * (levels + 1) * 8 + 2 * n * levels * 8) + 16 * n + 64 * n + 4 * n + 8 + 4 * PP_LEAF_LEN * n + 2 * n + 64;
 }
 
-// n transfers on device buffers, in order: d_accounts and the tree's nodes are advanced.  d_w 16-byte aligned.
+// n transfers on device buffers, in order: d_accounts and the tree's nodes are advanced.  d_w 16-byte aligned; item i's witnesses
+// from d_w + i * stride (stride >= the shape's num_witness: a block's own driver passes that, the rollup's one more).
 static int pt_run(swm_ctx* ctx, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree, uint8_t* d_accounts, const uint8_t* d_msgs,
-                  const uint8_t* d_sigs, size_t n, Fr* d_w, PtOut* out) {
+                  const uint8_t* d_sigs, size_t n, Fr* d_w, size_t stride, PtOut* out) {
     const PedersenTransferShape& s = c->shape;
     const unsigned levels = (unsigned)s.levels, n_leaves = 1u << levels;
     uint8_t* aux = nullptr;
@@ -243,7 +238,7 @@ static int pt_run(swm_ctx* ctx, const swm_pedersen_transfer_circuit* c, swm_merk
     const Fr k2d = fp_from_u64<Fr>(2 * ED_D);
     SWM_HIP(ctx, hipMemsetAsync(O.verdict, 0, 4, ctx->stream));
     SWM_TRY(transfer_prep_run(ctx, d_msgs, d_accounts, n, levels, d_keys));
-    SWM_TRY(schnorr_witness_run(ctx, &c->schnorr, aux, d_msgs, d_sigs, n, d_w, s.num_witness, d_sig_ok, O.status));
+    SWM_TRY(schnorr_witness_run(ctx, &c->schnorr, aux, d_msgs, d_sigs, n, d_w, stride, d_sig_ok, O.status));
     const unsigned lanes = lanes_for(n_leaves);
     SWM_LAUNCH(ctx, "pedersen_transfer_check", pedersen_transfer_check_kernel, dim3((unsigned)(((size_t)n_leaves * lanes + 255) / 256)), dim3(256),
                0, pt_rows(c->leaf), c->leaf->num_windows, reinterpret_cast<const uint32_t*>(tree->d_nodes), (const uint8_t*)d_accounts, n_leaves,
@@ -256,18 +251,18 @@ static int pt_run(swm_ctx* ctx, const swm_pedersen_transfer_circuit* c, swm_merk
     const size_t dig = n * (levels + 1) * 8, sib = n * levels * 8, leaves = PP_LEAF_LEN * n;
     const size_t at[4] = {s.sender_at, s.sender_update_at, s.recipient_at, s.recipient_update_at};
     PpArgs A = {};
-    A.stride = s.num_witness;
+    A.stride = stride;
     A.dig_stride = (size_t)(levels + 1) * 8;
     A.levels = levels;
     A.sections = 4;
     for (int k = 0; k < 4; k++) A.s[k] = {O.leaves + k * leaves, O.dig + k * dig, O.sib + (k / 2) * sib, O.idx + (k / 2) * n, at[k], (unsigned)(k & 1)};
     SWM_TRY(pp_record_run(ctx, c->leaf, c->inner, A, n, d_w));
-    SWM_TRY(transfer_bits_run(ctx, n, s.num_witness, s.balance_at, s.sum_at, s.r1_at, s.recipient_bits_at, levels, O.leaves, O.dig + dig, d_w));
+    SWM_TRY(transfer_bits_run(ctx, n, stride, s.balance_at, s.sum_at, s.r1_at, s.recipient_bits_at, levels, O.leaves, O.dig + dig, d_w));
     *out = O;
     return SWM_OK;
 }
 
-static int pt_check_tree(swm_ctx* ctx, const char* what, const swm_pedersen_transfer_circuit* c, const swm_merkle_tree* t) {
+int pedersen_transfer_check_tree(swm_ctx* ctx, const char* what, const swm_pedersen_transfer_circuit* c, const swm_merkle_tree* t) {
     if (t->leaf != c->leaf || t->inner != c->inner || t->height != c->shape.height || t->leaf_len != PP_LEAF_LEN)
         return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: a tree of height %zu with %zu-byte leaves for a circuit of height %zu with %zu-byte leaves, "
                        "or other parameters", what, t->height, t->leaf_len, c->shape.height, (size_t)PP_LEAF_LEN);
@@ -285,7 +280,7 @@ static int pt_chunk(swm_ctx* ctx, const char* what, const swm_pedersen_transfer_
     SWM_HIP(ctx, hipMemcpyAsync(d_in + 64 * n, b.msgs + PP_MSG_LEN * base, PP_MSG_LEN * n, hipMemcpyHostToDevice, ctx->stream));
     SWM_TRY(scratch(ctx, "ptransfer.w", n * item + 16, (void**)&d_out));
     PtOut O;
-    SWM_TRY(pt_run(ctx, c, tree, d_accounts, d_in + 64 * n, d_in, n, (Fr*)d_out, &O));
+    SWM_TRY(pt_run(ctx, c, tree, d_accounts, d_in + 64 * n, d_in, n, (Fr*)d_out, c->shape.num_witness, &O));
     uint32_t verdict = 0;
     SWM_HIP(ctx, hipMemcpyAsync(&verdict, O.verdict, 4, hipMemcpyDeviceToHost, ctx->stream));
     SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -299,6 +294,14 @@ static int pt_chunk(swm_ctx* ctx, const char* what, const swm_pedersen_transfer_
     return SWM_OK;
 }
 
+int pedersen_transfer_run_strided(swm_ctx* ctx, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree, uint8_t* d_accounts,
+                                  const uint8_t* d_msgs, const uint8_t* d_sigs, size_t n, Fr* d_w, size_t stride, TransferRunOut* out) {
+    PtOut O;
+    SWM_TRY(pt_run(ctx, c, tree, d_accounts, d_msgs, d_sigs, n, d_w, stride, &O));
+    *out = TransferRunOut{O.roots, O.flags, O.status, O.verdict};
+    return SWM_OK;
+}
+
 static_assert(PT_FLAG_APPLIED == TRANSFER_FLAG_APPLIED, "the block driver proves what the advance kernel applied");
 static_assert(PP_MSG_LEN == PY_MSG_LEN && PP_LEAF_LEN == PY_LEAF_LEN, "the block driver's message and leaf");
 
@@ -307,7 +310,7 @@ struct PedersenTransferUnit {  // what ledger_witness_host.h drives
     using Tree = swm_merkle_tree;
     static constexpr const char* name = "pedersen_transfer";
     static constexpr const char* accounts_scratch = "ptransfer.accounts";
-    static constexpr auto check_tree = pt_check_tree;
+    static constexpr auto check_tree = pedersen_transfer_check_tree;
     static constexpr auto chunk = pt_chunk;
 };
 

@@ -43,13 +43,8 @@
 #include "schnorr.h"
 #include "swmarlin.h"
 #include "ledger_witness_host.h"
+#include "transfer_units.h"
 #include "witness_runs.h"
-
-struct swm_transfer_circuit {
-    swm_schnorr_circuit schnorr;      // over PY_MSG_LEN bytes
-    swm_poseidon_tree_circuit tree;   // over PY_LEAF_LEN bytes
-    swm::TransferShape shape;
-};
 
 namespace swm {
 
@@ -281,9 +276,10 @@ static size_t tr_aux_bytes(size_t n, size_t levels) {
     return 64 * n + 4 * (4 * n * (levels + 1) * 8 + 2 * n * levels * 8) + 16 * n + 64 * n + 4 * n + 8 + 4 * PY_LEAF_LEN * n + 2 * n + 64;
 }
 
-// n transfers on device buffers, in order: d_accounts and the tree's nodes are advanced.  d_w 16-byte aligned.
+// n transfers on device buffers, in order: d_accounts and the tree's nodes are advanced.  d_w 16-byte aligned; item i's witnesses
+// from d_w + i * stride (stride >= the shape's num_witness: a block's own driver passes that, the rollup's one more).
 static int tr_run(swm_ctx* ctx, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* d_accounts, const uint8_t* d_msgs,
-                  const uint8_t* d_sigs, size_t n, Fr* d_w, TrOut* out) {
+                  const uint8_t* d_sigs, size_t n, Fr* d_w, size_t stride, TrOut* out) {
     const TransferShape& s = c->shape;
     const swm_poseidon* p = c->tree.params;
     const unsigned levels = (unsigned)s.levels;
@@ -301,20 +297,20 @@ static int tr_run(swm_ctx* ctx, const swm_transfer_circuit* c, swm_poseidon_tree
     O.flags = O.leaves + 4 * PY_LEAF_LEN * n;
     uint8_t* d_sig_ok = O.flags + n;
     SWM_TRY(transfer_prep_run(ctx, d_msgs, d_accounts, n, levels, d_keys));
-    SWM_TRY(schnorr_witness_run(ctx, &c->schnorr, aux, d_msgs, d_sigs, n, d_w, s.num_witness, d_sig_ok, O.status));
+    SWM_TRY(schnorr_witness_run(ctx, &c->schnorr, aux, d_msgs, d_sigs, n, d_w, stride, d_sig_ok, O.status));
     SWM_LAUNCH(ctx, "transfer_advance", transfer_advance_kernel, dim3(1), dim3(TR_LANES), pt_lds(p), pt_table(p), pt_params(p), levels, n,
                reinterpret_cast<uint32_t*>(tree->d_nodes), d_accounts, d_msgs, (const uint8_t*)d_sig_ok, O);
     const size_t dig = n * (levels + 1) * 8, sib = n * levels * 8, leaves = PY_LEAF_LEN * n;
     const size_t at[4] = {s.sender_at, s.sender_update_at, s.recipient_at, s.recipient_update_at};
     for (int k = 0; k < 4; k++)
         SWM_TRY(ptw_record(ctx, &c->tree, O.leaves + k * leaves, O.idx + (k / 2) * n, O.dig + k * dig, O.sib + (k / 2) * sib, n, d_w + at[k],
-                           s.num_witness, k % 2 == 0));
-    SWM_TRY(transfer_bits_run(ctx, n, s.num_witness, s.balance_at, s.sum_at, s.r1_at, s.recipient_bits_at, levels, O.leaves, O.dig + dig, d_w));
+                           stride, k % 2 == 0));
+    SWM_TRY(transfer_bits_run(ctx, n, stride, s.balance_at, s.sum_at, s.r1_at, s.recipient_bits_at, levels, O.leaves, O.dig + dig, d_w));
     *out = O;
     return SWM_OK;
 }
 
-static int tr_check_tree(swm_ctx* ctx, const char* what, const swm_transfer_circuit* c, const swm_poseidon_tree* t) {
+int transfer_check_tree(swm_ctx* ctx, const char* what, const swm_transfer_circuit* c, const swm_poseidon_tree* t) {
     if (t->params != c->tree.params || t->height != c->shape.height || t->leaf_len != PY_LEAF_LEN)
         return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: a tree of height %zu with %zu-byte leaves for a circuit of height %zu with %zu-byte leaves, "
                        "or other parameters", what, t->height, t->leaf_len, c->shape.height, (size_t)PY_LEAF_LEN);
@@ -333,7 +329,7 @@ static int tr_chunk(swm_ctx* ctx, const char* what, const swm_transfer_circuit* 
     SWM_HIP(ctx, hipMemcpyAsync(d_in + 64 * n, b.msgs + PY_MSG_LEN * base, PY_MSG_LEN * n, hipMemcpyHostToDevice, ctx->stream));
     SWM_TRY(scratch(ctx, "transfer.w", n * item + 16, (void**)&d_out));
     TrOut O;
-    SWM_TRY(tr_run(ctx, c, tree, d_accounts, d_in + 64 * n, d_in, n, (Fr*)d_out, &O));
+    SWM_TRY(tr_run(ctx, c, tree, d_accounts, d_in + 64 * n, d_in, n, (Fr*)d_out, s.num_witness, &O));
     uint32_t verdict = 0;
     SWM_HIP(ctx, hipMemcpyAsync(&verdict, O.verdict, 4, hipMemcpyDeviceToHost, ctx->stream));
     if (b.old_roots) SWM_HIP(ctx, hipMemcpyAsync(b.old_roots + 32 * base, O.roots, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -358,6 +354,14 @@ int transfer_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size
     return prove_device_witness(ctx, pk, TR_INSTANCE, num_witness, num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
 }
 
+int transfer_run_strided(swm_ctx* ctx, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* d_accounts, const uint8_t* d_msgs,
+                         const uint8_t* d_sigs, size_t n, Fr* d_w, size_t stride, TransferRunOut* out) {
+    TrOut O;
+    SWM_TRY(tr_run(ctx, c, tree, d_accounts, d_msgs, d_sigs, n, d_w, stride, &O));
+    *out = TransferRunOut{O.roots, O.flags, O.status, O.verdict};
+    return SWM_OK;
+}
+
 static_assert(TR_FLAG_APPLIED == TRANSFER_FLAG_APPLIED, "the block driver proves what the advance kernel applied");
 
 struct TransferUnit {  // what ledger_witness_host.h drives
@@ -365,7 +369,7 @@ struct TransferUnit {  // what ledger_witness_host.h drives
     using Tree = swm_poseidon_tree;
     static constexpr const char* name = "transfer";
     static constexpr const char* accounts_scratch = "transfer.accounts";
-    static constexpr auto check_tree = tr_check_tree;
+    static constexpr auto check_tree = transfer_check_tree;
     static constexpr auto chunk = tr_chunk;
 };
 

@@ -39,6 +39,10 @@ inline int prove_device_witness(swm_ctx* ctx, const swm_pk* pk, size_t num_insta
     return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
 }
 
+// Whether the prover would take a system of these counts under `pk` (marlin.hip: what prove_shape compares, SWM_ERR_MISMATCH
+// otherwise).  For a unit that changes state before it proves: it asks first.
+bool pk_takes_shape(const swm_pk* pk, size_t num_instance, size_t num_witness, size_t num_constraints);
+
 // The end of a circuit handle: nothing queued on the context still reads it.  free_device: its device arrays, if it has any.
 template <class T, class FreeDevice>
 void destroy_circuit(swm_ctx* ctx, T* c, FreeDevice free_device) {

@@ -246,6 +246,63 @@ class PedersenTransferCircuit:
             pass
 
 
+class RollupCircuit(TransferCircuit):
+    """The rollup of `transfers` transfers over resident Schnorr and Poseidon parameters: ONE vector (workloads.build_rollup's) for a
+    block applied in order, all or nothing.  There is no handle of its own: it is a swm_transfer_circuit and a count."""
+
+    def __init__(self, sig_params, sponge, height, transfers):
+        super().__init__(sig_params, sponge, height)
+        self.transfers = int(transfers)
+
+    def transfer_shape(self):
+        return TransferCircuit.shape(self)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints) of the block."""
+        from .marlin import rollup_circuit_shape
+        return rollup_circuit_shape(self.sponge.params, self.height, self.transfers, self.sig_params.salt is not None)
+
+    _witness_entry = "rollup_witness_at"
+
+    def witness_at(self, tree, accounts, transfers, guard=0, fill=None):
+        """Against a tree whose leaf level is the table `accounts`: (witness uint64 [num_witness + guard, 4], accounts after the block
+        as bytes, old root, new root as ints, flags uint8 [count], status uint32 [count], applied).  A block with a refused transfer
+        is rolled back: applied False, the tree and the accounts as they were, new root = old root."""
+        acc = np.frombuffer(b"".join(bytes(a) for a in accounts), dtype=np.uint8).reshape(-1, LEAF_LEN)
+        if acc.shape[0] != 1 << (self.height - 1):
+            raise ValueError("the account table is 2^(height - 1) leaves of %d bytes" % LEAF_LEN)
+        if len(transfers) != self.transfers:
+            raise ValueError("a block of this circuit is %d transfers" % self.transfers)
+        msgs = np.frombuffer(b"".join(bytes(t[0]) for t in transfers), dtype=np.uint8).reshape(len(transfers), -1)
+        sigs = np.frombuffer(b"".join(bytes(t[1]) for t in transfers), dtype=np.uint8).reshape(len(transfers), -1)
+        if msgs.shape[1] != MESSAGE_LEN or sigs.shape[1] != 64:
+            raise ValueError("a transfer is a %d-byte message and a 64-byte signature" % MESSAGE_LEN)
+        w, acc, old, new, flags, status, applied = getattr(self.ctx, self._witness_entry)(self.h, tree.h, self.shape()[1], acc, msgs, sigs,
+                                                                                          guard, fill)
+        return (w, [a.tobytes() for a in acc], int.from_bytes(old.tobytes(), "little"), int.from_bytes(new.tobytes(), "little"), flags,
+                status, applied)
+
+
+class PedersenRollupCircuit(PedersenTransferCircuit):
+    """RollupCircuit over the reference's Pedersen account tree (workloads.build_pedersen_rollup's vector): a
+    swm_pedersen_transfer_circuit and a count."""
+
+    def __init__(self, sig_params, leaf_crh, two_to_one_crh, height, transfers):
+        super().__init__(sig_params, leaf_crh, two_to_one_crh, height)
+        self.transfers = int(transfers)
+
+    def transfer_shape(self):
+        return PedersenTransferCircuit.shape(self)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints) of the block."""
+        from .marlin import pedersen_rollup_circuit_shape
+        return pedersen_rollup_circuit_shape(self.height, self.transfers, self.sig_params.salt is not None)
+
+    _witness_entry = "pedersen_rollup_witness_at"
+    witness_at = RollupCircuit.witness_at
+
+
 class State:
     """ledger::State.  The account tree is a hash.DeviceMerkleTree, or with account_tree="poseidon" a hash.PoseidonMerkleTree over
     parameters.poseidon; ids are AccountId(u8), the first one handed out is 1."""
@@ -277,6 +334,9 @@ class State:
         self._transfer_keys = None   # (TransferCircuit, proving key, verifying key), the same
         self._pedersen_payment_keys = None   # (PedersenPaymentCircuit, proving key, verifying key), for a Pedersen account tree
         self._pedersen_transfer_keys = None  # (PedersenTransferCircuit, proving key, verifying key), the same
+        self._rollup_keys = {}       # transfers per block -> (RollupCircuit or PedersenRollupCircuit, proving key, verifying key)
+        self._rollup_circuits = {}   # transfers per block -> the circuit alone (no keys are needed to apply a block unproved)
+        self._rollup_transfer_system = None  # the ONE packed transfer system every block size is relabelled from
 
     def root(self):
         return self.account_merkle_tree.root()
@@ -485,12 +545,95 @@ class State:
             info.balance = int.from_bytes(table[i][64:], "little")
         return [(bool(f & 16), proof, pub) for f, proof, pub in zip(flags, proofs, public)]
 
+    def _rollup_circuit(self, n):
+        n = int(n)
+        if n not in self._rollup_circuits:
+            sig, height = self.parameters.sig_params, self.account_merkle_tree.height()
+            if self.account_tree == "pedersen":
+                self._rollup_circuits[n] = PedersenRollupCircuit(sig, self.parameters.leaf_crh, self.parameters.two_to_one_crh, height, n)
+            else:
+                self._rollup_circuits[n] = RollupCircuit(sig, self.parameters.poseidon, height, n)
+        return self._rollup_circuits[n]
+
+    def _rollup_keys_for(self, n, rng):
+        from . import marlin as M
+        from . import workloads as W
+        n = int(n)
+        if not 1 <= n <= W.ROLLUP_MAX_TRANSFERS:
+            raise ValueError("rollup_keys: 1 <= transfers <= %d" % W.ROLLUP_MAX_TRANSFERS)
+        if n not in self._rollup_keys:
+            sig = self.parameters.sig_params
+            height = self.account_merkle_tree.height()
+            if self._rollup_transfer_system is None:
+                leaf = AccountInformation(sig.generator, 0).to_bytes_le()
+                if self.account_tree == "pedersen":
+                    params = W.MerkleParams(generators=(self.parameters.leaf_crh.generators, self.parameters.two_to_one_crh.generators))
+                    cs, _ = W.pedersen_transfer_circuit(params, height, bytes(MESSAGE_LEN), bytes(64), leaf, [0] * (height - 1), leaf,
+                                                        [0] * (height - 1), sig.generator, sig.salt, old_root=0, new_root=0, r1=0)
+                else:
+                    cs, _ = W.transfer_circuit(self.parameters.poseidon.params, height, bytes(MESSAGE_LEN), bytes(64), leaf,
+                                               [0] * (height - 1), leaf, [0] * (height - 1), sig.generator, sig.salt)
+                self._rollup_transfer_system = cs.pack()
+            packed = W.rollup_system(self._rollup_transfer_system, n)     # no builder per section
+            nnz = max(int(m[0][-1]) for m in packed.mats)
+            srs = M.MarlinInst.universal_setup(packed.num_constraints, packed.instance.shape[0] + packed.witness.shape[0], nnz, rng, sig.ctx)
+            try:
+                pk, vk = M.MarlinInst.index_from_constraint_system(srs, packed)
+            finally:
+                srs.free()
+            self._rollup_keys[n] = (self._rollup_circuit(n), pk, vk)
+        return self._rollup_keys[n]
+
+    def rollup_keys(self, n, rng):
+        """The rollup of n transfers over this ledger's Poseidon account tree with its Marlin keys, derived once per n: ONE transfer
+        system is built and relabelled n times (workloads.rollup_system), so the keys of a block cost the builder one transfer."""
+        if self.account_tree != "poseidon":
+            raise ValueError("rollup_keys: the rollup circuit is over a Poseidon account tree (a Pedersen state: pedersen_rollup_keys)")
+        return self._rollup_keys_for(n, rng)
+
+    def pedersen_rollup_keys(self, n, rng):
+        """rollup_keys over this ledger's Pedersen account tree."""
+        if self.account_tree != "pedersen":
+            raise ValueError("pedersen_rollup_keys: the Pedersen rollup circuit is over a Pedersen account tree")
+        return self._rollup_keys_for(n, rng)
+
+    def apply_rollup(self, pp, txs, rng, prove=True):
+        """A block of transactions applied in order, ALL OR NOTHING, and (with prove) ONE proof that the root before the block
+        becomes the root after it, under rollup_keys(len(txs), rng) / pedersen_rollup_keys: the block has exactly as many transfers
+        as the key.  -> (applied, proof or None, public inputs): workloads.rollup_public_inputs(old_root, new_root, messages).  A
+        block with a refused transaction is rolled back: applied False, no proof, the state as it was, equal roots.  As under
+        apply_transactions a payment to oneself is refused."""
+        from . import marlin as M
+        from . import workloads as W
+        txs = list(txs)
+        if not txs:
+            raise ValueError("apply_rollup: an empty block")
+        pedersen = self.account_tree == "pedersen"
+        block = [(tx.message(), tx.signature.to_bytes()) for tx in txs]
+        tree = self.account_merkle_tree
+        if prove:
+            circuit, pk, _ = self._rollup_keys_for(len(txs), rng)
+            prover = M.generate_pedersen_rollup_proof if pedersen else M.generate_rollup_proof
+            proof, public, _, _, table, applied = prover(pk, circuit, tree, self.account_table(), block, rng)
+        else:
+            _, table, old, new, _, _, applied = self._rollup_circuit(len(txs)).witness_at(tree, self.account_table(), block)
+            proof, public = None, W.rollup_public_inputs(old, new, [m for m, _ in block])
+        if applied:
+            for i, info in self.id_to_account_info.items():
+                info.balance = int.from_bytes(table[i][64:], "little")
+        return applied, proof, public
+
     def free(self):
         for keys in (self._proof_keys, self._payment_keys, self._transfer_keys, self._pedersen_payment_keys, self._pedersen_transfer_keys):
             if keys is not None:
                 keys[0].free()
                 keys[1].free()
         self._proof_keys = self._payment_keys = self._transfer_keys = self._pedersen_payment_keys = self._pedersen_transfer_keys = None
+        for _, pk, _ in self._rollup_keys.values():
+            pk.free()
+        for circuit in self._rollup_circuits.values():
+            circuit.free()
+        self._rollup_keys, self._rollup_circuits, self._rollup_transfer_system = {}, {}, None
         self.account_merkle_tree.free()
 
 
@@ -511,6 +654,13 @@ def verify_payment(vk, public_inputs, proof, rng):
 def verify_transfer(vk, public_inputs, proof, rng):
     """The verifier of a transfer proof over either account tree: public_inputs = [old_root, new_root, sender, recipient, amount]
     (workloads.transfer_public_inputs = pedersen_transfer_public_inputs)."""
+    from . import marlin as M
+    return M.verify_proof(vk, [int(v) for v in public_inputs], proof if isinstance(proof, M.MarlinProof) else M.MarlinProof(proof), rng)
+
+
+def verify_rollup(vk, public_inputs, proof, rng):
+    """The verifier of a rollup proof over either account tree: public_inputs = [old_root, new_root, sender_0, recipient_0, amount_0,
+    ...] (workloads.rollup_public_inputs), vk that of a block of as many transfers."""
     from . import marlin as M
     return M.verify_proof(vk, [int(v) for v in public_inputs], proof if isinstance(proof, M.MarlinProof) else M.MarlinProof(proof), rng)
 

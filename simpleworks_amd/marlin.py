@@ -776,6 +776,62 @@ def generate_pedersen_transfer_proof(proving_key, circuit, tree, accounts, messa
     return generate_transfer_proof(proving_key, circuit, tree, accounts, message, signature, rng, uncompressed, "swm_pedersen_transfer_prove_at")
 
 
+def rollup_circuit_shape(params, height, transfers, salted=False):
+    """swm_rollup_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the rollup of `transfers` transfers over a
+    Poseidon account tree of that height — what workloads.build_rollup emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_rollup_circuit_shape(params.full_rounds, params.partial_rounds, params.alpha, height, 1 if salted else 0,
+                                                   transfers, ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)),
+           "swm_rollup_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def pedersen_rollup_circuit_shape(height, transfers, salted=False):
+    """swm_pedersen_rollup_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the rollup of `transfers` transfers
+    over a Pedersen account tree of that height — what workloads.build_pedersen_rollup emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_pedersen_rollup_circuit_shape(height, 1 if salted else 0, transfers, ctypes.byref(ni), ctypes.byref(nw),
+                                                            ctypes.byref(nc)), "swm_pedersen_rollup_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_rollup_proof(proving_key, circuit, tree, accounts, transfers, rng, uncompressed=False, _entry="swm_rollup_prove_at"):
+    """swm_rollup_prove_at: the block `transfers` ((message, signature) each) applied IN ORDER to the resident account tree `tree` (a
+    hash.PoseidonMerkleTree) and to the account table `accounts`, ALL OR NOTHING, and ONE proof for the block under the key of a
+    rollup of len(transfers) transfers (`circuit`: a ledger.TransferCircuit or RollupCircuit).  The tree is advanced before the proof
+    is made.  Returns (proof or None, public, flags, status, accounts after the block, applied): a block with a refused transfer is
+    rolled back — no proof, applied False, tree and accounts as they were, public = rollup_public_inputs with new_root = old_root —
+    and flags / status are what the sequential pass met."""
+    import numpy as np
+    from . import workloads as W
+    ctx = proving_key.ctx
+    count = len(transfers)
+    acc = np.array([np.frombuffer(bytes(a), dtype=np.uint8) for a in accounts], dtype=np.uint8, order="C")
+    if acc.ndim != 2 or acc.shape[1] != 72 or acc.shape[0] != 1 << (circuit.height - 1):
+        raise ValueError("the account table is 2^(height - 1) leaves of 72 bytes")
+    msgs, sigs = [bytes(t[0]) for t in transfers], [bytes(t[1]) for t in transfers]
+    if not count or any(len(m) != 10 for m in msgs) or any(len(s) != 64 for s in sigs):
+        raise ValueError("a block is at least one transfer, each a 10-byte message and a 64-byte signature")
+    m_b = (ctypes.c_uint8 * (10 * count)).from_buffer_copy(b"".join(msgs))
+    s_b = (ctypes.c_uint8 * (64 * count)).from_buffer_copy(b"".join(sigs))
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    old, new = (ctypes.c_uint8 * 32)(), (ctypes.c_uint8 * 32)()
+    flags, status = (ctypes.c_uint8 * count)(), (ctypes.c_uint32 * count)()
+    applied = ctypes.c_int(0)
+    _check(getattr(ctx.lib, _entry)(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, m_b, s_b, count, rng.h,
+                                    1 if uncompressed else 0, buf, len(buf), ctypes.byref(n), old, new, flags, status,
+                                    ctypes.byref(applied)), _entry, ctx)
+    public = W.rollup_public_inputs(int.from_bytes(bytes(old), "little"), int.from_bytes(bytes(new), "little"), msgs)
+    return (bytes(buf[: n.value]) if n.value else None, public, list(flags), list(status), [bytes(a) for a in acc], bool(applied.value))
+
+
+def generate_pedersen_rollup_proof(proving_key, circuit, tree, accounts, transfers, rng, uncompressed=False):
+    """swm_pedersen_rollup_prove_at: generate_rollup_proof over the reference's Pedersen account tree — `tree` a
+    hash.DeviceMerkleTree with 72-byte leaves, `circuit` a ledger.PedersenTransferCircuit or PedersenRollupCircuit."""
+    return generate_rollup_proof(proving_key, circuit, tree, accounts, transfers, rng, uncompressed, "swm_pedersen_rollup_prove_at")
+
+
 def blake2s_circuit_shape(input_len):
     """swm_blake2s_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the Blake2s hash circuit over input_len
     bytes — what workloads.build_blake2s_hash emits."""

@@ -2271,6 +2271,199 @@ class PedersenTransferValidation:
 
 
 # ===================================================================================================================
+# The rollup: ONE statement for a block of N transfers applied in order, old_root -> new_root, over either account tree.  N
+# sections of the transfer circuit (build_transfer / build_pedersen_transfer) linked through N - 1 WITNESSED roots: the
+# intermediate roots appear nowhere in the public input.  build_rollup / build_pedersen_rollup are the layout contract of
+# csrc/host/rollup_shape.h and csrc/rollup_witness.hip.  With W_t, R_t the witness and row counts of the transfer circuit for that
+# tree, height and salt:
+#   instance  one, old_root, new_root, then sender_k, recipient_k, amount_k for k = 0 .. N - 1               3 + 3 N
+#   witness   N sections at a stride of W_t + 1: section k is the transfer's W_t witnesses in its order, and for k < N - 1 one
+#             witness root_{k+1} follows at offset W_t of the section                                         N (W_t + 1) - 1
+#   rows      section k is the transfer's R_t rows in its order; its old_root variable is the instance's for k = 0 and the witness
+#             root_k otherwise, its new_root variable the instance's for k = N - 1 and the witness root_{k+1} otherwise, its
+#             sender, recipient and amount those of index k.  No row is added.                                N R_t
+# N = 1 is the transfer circuit's system verbatim.  1 <= N <= 64.  A root_k that is not the root transfer k - 1 left fails exactly
+# the last row of section k - 1 and the sender's root row of section k; every refusal of the transfer circuit keeps its meaning,
+# inside its own section.  rollup_system makes the same matrices by relabelling ONE transfer system N times: no per-section
+# builder runs, so keys at height 9 are derived in the time of one transfer's.
+# ===================================================================================================================
+ROLLUP_MAX_TRANSFERS = 64
+
+
+def _rollup_layout(transfer_layout, n):
+    n = int(n)
+    if not 1 <= n <= ROLLUP_MAX_TRANSFERS:
+        raise ValueError("rollup circuit: 1 <= transfers <= %d" % ROLLUP_MAX_TRANSFERS)
+    w, r = transfer_layout["num_witness"], transfer_layout["num_constraints"]
+    lay = {"transfer": transfer_layout, "transfers": n, "stride": w + 1, "root_at": w,
+           "sections": [k * (w + 1) for k in range(n)], "section_rows": [k * r for k in range(n)],
+           "roots": {k: (k - 1) * (w + 1) + w for k in range(1, n)},        # root_k, the root after transfer k - 1
+           "item_instance": [3 + 3 * k for k in range(n)],
+           "num_instance": 3 + 3 * n, "num_witness": n * (w + 1) - 1, "num_constraints": n * r}
+    for name in ("pack_row", "tie_rows", "sender_root_row", "sender_r1_row", "recipient_r1_row", "sum_pack_row", "new_root_row"):
+        lay[name] = [k * r + transfer_layout[name] for k in range(n)]
+    return lay
+
+
+def rollup_circuit_layout(params, height, transfers, salted=False):
+    """The section stride, the sections' first witnesses and rows, the witnesses root_k ("roots": k -> index, 1 <= k < N), the
+    instance index of each transfer's (sender, recipient, amount) and the transfer circuit's named rows per section (lists), with
+    the three counts, as csrc/host/rollup_shape.h states them.  "transfer" is transfer_circuit_layout's."""
+    return _rollup_layout(transfer_circuit_layout(params, height, salted), transfers)
+
+
+def pedersen_rollup_circuit_layout(height, transfers, salted=False):
+    """rollup_circuit_layout over pedersen_transfer_circuit_layout."""
+    return _rollup_layout(pedersen_transfer_circuit_layout(height, salted), transfers)
+
+
+def rollup_public_inputs(old_root, new_root, messages):
+    """The 2 + 3 N public inputs of the rollup circuit, in instance order: old_root, new_root (ints), then sender, recipient and
+    amount out of each 10-byte message."""
+    out = [int(old_root) % R_MODULUS, int(new_root) % R_MODULUS]
+    for m in messages:
+        out += payment_public_inputs(0, m)[1:]
+    return out
+
+
+
+class _RollupSection:
+    """What a transfer builder sees of the block's constraint system: its five input variables are handed out from `inputs` (the
+    values it gives them are kept in `public`), everything else is the block's own."""
+
+    def __init__(self, cs, inputs):
+        self.cs, self.inputs, self.public = cs, list(inputs), []
+        self.witness = cs.witness
+        self.one, self.new_witness_variable, self.enforce_constraint = cs.one, cs.new_witness_variable, cs.enforce_constraint
+
+    def new_input_variable(self, value):
+        self.public.append(int(value) % R_MODULUS)
+        return self.inputs[len(self.public) - 1]
+
+
+def _build_rollup(cs, build_section, item_witness, transfers, old_root, new_root, roots):
+    transfers = list(transfers)
+    n = len(transfers)
+    if not 1 <= n <= ROLLUP_MAX_TRANSFERS:
+        raise ValueError("rollup circuit: 1 <= transfers <= %d" % ROLLUP_MAX_TRANSFERS)
+    if len(cs.instance) != 1 or cs.witness:
+        raise ValueError("rollup circuit: the block lays out the whole system")
+    roots = dict(roots or {})
+    if any(not 1 <= k < n for k in roots):
+        raise ValueError("rollup circuit: root_k is a witness for 1 <= k < transfers")
+    first = len(cs.instance)
+    old_i, new_i = cs.new_input_variable(0), cs.new_input_variable(0)
+    items = [[cs.new_input_variable(0) for _ in range(3)] for _ in range(n)]
+    before = old_i
+    public = []
+    for k, t in enumerate(transfers):
+        base = len(cs.witness)
+        after = new_i if k == n - 1 else ("w", base + item_witness)      # root_{k+1}: allocated behind the section
+        section = _RollupSection(cs, [before, after] + items[k])
+        build_section(section, t)
+        assert len(cs.witness) - base == item_witness and len(section.public) == 5
+        public.append(section.public)
+        if k < n - 1:
+            assert cs.new_witness_variable(roots.get(k + 1, section.public[1])) == after
+        before = after
+    cs.instance[first] = public[0][0] if old_root is None else int(old_root) % R_MODULUS
+    cs.instance[first + 1] = public[-1][1] if new_root is None else int(new_root) % R_MODULUS
+    for k, vars_k in enumerate(items):
+        for (_, i), v in zip(vars_k, public[k][2:]):
+            cs.instance[i] = v
+    return cs.instance[first:]
+
+
+def _rollup_transfer_args(t):
+    if isinstance(t, dict):
+        return [t[k] for k in ("message", "signature", "sender_leaf", "sender_path", "recipient_leaf", "recipient_path")], t.get("r1")
+    t = tuple(t)
+    if len(t) not in (6, 7):
+        raise ValueError("rollup circuit: a transfer is (message, signature, sender leaf, sender siblings, recipient leaf, recipient "
+                         "siblings[, r1]) or a dict of them")
+    return list(t[:6]), (t[6] if len(t) == 7 else None)
+
+
+def build_rollup(cs, generator, salt, params, height, transfers, old_root=None, new_root=None, roots=None):
+    """Emits the rollup circuit over a Poseidon account tree into the empty `cs`.  transfers: per transfer build_transfer's
+    (message, signature, sender_leaf, sender_siblings, recipient_leaf, recipient_siblings[, r1]) — a tuple, or a dict with the keys
+    message, signature, sender_leaf, sender_path, recipient_leaf, recipient_path and optionally r1 — each against the tree as the
+    transfers before it left it.  old_root, new_root override the two public roots, roots = {k: value} the witness root_k (1 <= k <
+    N), which otherwise are the walked values: root_k the new root section k - 1 walks to.  Returns the public inputs [old_root,
+    new_root, sender_0, recipient_0, amount_0, ...]."""
+    item_witness = transfer_circuit_layout(params, height, salt is not None)["num_witness"]
+
+    def section(sub, t):
+        args, r1 = _rollup_transfer_args(t)
+        build_transfer(sub, generator, salt, params, height, *args, r1=r1)
+    return _build_rollup(cs, section, item_witness, transfers, old_root, new_root, roots)
+
+
+def build_pedersen_rollup(cs, generator, salt, merkle_params, height, transfers, old_root=None, new_root=None, roots=None):
+    """build_rollup over build_pedersen_transfer: the same arguments with merkle_params in the place of params."""
+    item_witness = pedersen_transfer_circuit_layout(height, salt is not None)["num_witness"]
+
+    def section(sub, t):
+        args, r1 = _rollup_transfer_args(t)
+        build_pedersen_transfer(sub, generator, salt, merkle_params, height, *args, r1=r1)
+    return _build_rollup(cs, section, item_witness, transfers, old_root, new_root, roots)
+
+
+def rollup_circuit(params, height, transfers, generator=ED_GENERATOR, salt=None, old_root=None, new_root=None, roots=None):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs)."""
+    cs = ConstraintSystem()
+    public = build_rollup(cs, generator, salt, params, height, transfers, old_root, new_root, roots)
+    return cs, public
+
+
+def pedersen_rollup_circuit(merkle_params, height, transfers, generator=ED_GENERATOR, salt=None, old_root=None, new_root=None,
+                            roots=None):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs)."""
+    cs = ConstraintSystem()
+    public = build_pedersen_rollup(cs, generator, salt, merkle_params, height, transfers, old_root, new_root, roots)
+    return cs, public
+
+
+def rollup_system(packed_transfer_system, n):
+    """The matrices of the rollup of n transfers out of ONE packed transfer system (either tree's: anything with .pack() whose
+    instance is one, old_root, new_root, sender, recipient, amount), by relabelling its columns once per section: what
+    build_rollup's system packs to, entry for entry, without running a builder per section.  The assignment of the result is one
+    and zeros: it is for MarlinInst.index, not for the prover.  n = 1 gives the transfer system's own matrices."""
+    n = int(n)
+    if not 1 <= n <= ROLLUP_MAX_TRANSFERS:
+        raise ValueError("rollup system: 1 <= transfers <= %d" % ROLLUP_MAX_TRANSFERS)
+    t = packed_transfer_system.pack()
+    if t.instance.shape[0] != 6:
+        raise ValueError("rollup system: a transfer system has six instance variables")
+    w, rows = t.witness.shape[0], t.num_constraints
+    ninst, stride = 3 + 3 * n, w + 1
+    if ninst + n * stride - 1 >= 1 << 32 or n * rows >= 1 << 32:
+        raise ValueError("rollup system: the block does not fit 32-bit indices")
+    mats = []
+    for rowptr, col, val in t.mats:
+        nnz = col.shape[0]
+        row_of = np.repeat(np.arange(rows, dtype=np.int64), np.diff(rowptr.astype(np.int64)))
+        cols, vals, row_ids = [], [], []
+        for k in range(n):
+            relabel = np.empty(6 + w, dtype=np.int64)
+            relabel[0] = 0
+            relabel[1] = 1 if k == 0 else ninst + k * stride - 1                 # root_k
+            relabel[2] = 2 if k == n - 1 else ninst + (k + 1) * stride - 1       # root_{k+1}
+            relabel[3:6] = 3 + 3 * k + np.arange(3)
+            relabel[6:] = ninst + k * stride + np.arange(w)
+            cols.append(relabel[col.astype(np.int64)])
+            row_ids.append(row_of + k * rows)
+            vals.append(val)
+        cols, row_ids = np.concatenate(cols), np.concatenate(row_ids)
+        order = np.lexsort((cols, row_ids))          # within a row by column, as ConstraintSystem.pack orders a row
+        new_rowptr = np.concatenate([rowptr.astype(np.int64)[:-1] + k * nnz for k in range(n)] + [np.array([n * nnz], dtype=np.int64)])
+        mats.append((new_rowptr.astype(np.uint32), cols[order].astype(np.uint32), np.concatenate(vals)[order]))
+    instance = np.zeros((ninst, 4), dtype=np.uint64)
+    instance[0] = t.instance[0]
+    return PackedR1cs(instance, np.zeros((n * stride - 1, 4), dtype=np.uint64), *mats)
+
+
+# ===================================================================================================================
 # Integer programs: the reference's gadget vocabulary (src/gadgets/{uint8,uint16,uint32,uint64,uint128,boolean}.rs behind the
 # traits of src/gadgets/traits.rs, plus ark's enforce_equal / is_eq / conditionally_select) as ONE circuit per program.  A
 # program is a straight-line TAPE of typed instructions over SSA registers; all executions of one program share it, so the

@@ -353,6 +353,27 @@ extern "C" {
                                           tree: *mut swm_merkle_tree, accounts_inout: *mut u8, message: *const u8, signature: *const u8,
                                           rng: *mut swm_rng, prove_flags: c_uint, proof_out: *mut u8, cap: usize, len: *mut usize,
                                           old_root: *mut u8, new_root: *mut u8, flag: *mut u8, status: *mut u32) -> c_int;
+    // the rollup: ONE vector and ONE proof for a block of 1 .. 64 transfers over either tree, all or nothing (a transfer circuit and a count)
+    pub fn swm_rollup_circuit_shape(full_rounds: usize, partial_rounds: usize, alpha: u64, height: usize, salted: c_int, n: usize,
+                                    num_instance: *mut usize, num_witness: *mut usize, num_constraints: *mut usize) -> c_int;
+    pub fn swm_pedersen_rollup_circuit_shape(height: usize, salted: c_int, n: usize, num_instance: *mut usize, num_witness: *mut usize,
+                                             num_constraints: *mut usize) -> c_int;
+    pub fn swm_rollup_witness_at(ctx: *mut swm_ctx, circuit: *const swm_transfer_circuit, tree: *mut swm_poseidon_tree,
+                                 accounts_inout: *mut u8, messages: *const u8, signatures: *const u8, count: usize, witness_out: *mut u64,
+                                 old_root: *mut u8, new_root: *mut u8, flags: *mut u8, status: *mut u32, applied: *mut c_int) -> c_int;
+    pub fn swm_rollup_prove_at(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_transfer_circuit, tree: *mut swm_poseidon_tree,
+                               accounts_inout: *mut u8, messages: *const u8, signatures: *const u8, count: usize, rng: *mut swm_rng,
+                               prove_flags: c_uint, proof_out: *mut u8, cap: usize, len: *mut usize, old_root: *mut u8,
+                               new_root: *mut u8, flags: *mut u8, status: *mut u32, applied: *mut c_int) -> c_int;
+    pub fn swm_pedersen_rollup_witness_at(ctx: *mut swm_ctx, circuit: *const swm_pedersen_transfer_circuit, tree: *mut swm_merkle_tree,
+                                          accounts_inout: *mut u8, messages: *const u8, signatures: *const u8, count: usize,
+                                          witness_out: *mut u64, old_root: *mut u8, new_root: *mut u8, flags: *mut u8, status: *mut u32,
+                                          applied: *mut c_int) -> c_int;
+    pub fn swm_pedersen_rollup_prove_at(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_pedersen_transfer_circuit,
+                                        tree: *mut swm_merkle_tree, accounts_inout: *mut u8, messages: *const u8, signatures: *const u8,
+                                        count: usize, rng: *mut swm_rng, prove_flags: c_uint, proof_out: *mut u8, cap: usize,
+                                        len: *mut usize, old_root: *mut u8, new_root: *mut u8, flags: *mut u8, status: *mut u32,
+                                        applied: *mut c_int) -> c_int;
     // the transfer circuit: a block of transfers applied in order, the resident tree and the account table advanced on the GPU
     pub fn swm_transfer_circuit_shape(full_rounds: usize, partial_rounds: usize, alpha: u64, height: usize, salted: c_int,
                                       num_instance: *mut usize, num_witness: *mut usize, num_constraints: *mut usize) -> c_int;
