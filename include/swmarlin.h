@@ -1228,8 +1228,16 @@ int swm_selftest_fr29(swm_ctx *ctx, int op, const uint32_t *a9, const uint32_t *
  *     whose lane sits out reads back as bytes 0xA5   15 te28_store_384(a)
  *   16 te28_quad_from_row(row a, neg)   17 te28_quad_madd_row(a one coordinate per lane, row b, neg)   18 te28_quad_add(out, a, b)
  *   19 te28_quad_add(out, a, a)   20 te28_quad_store_identity(out)
- * out_jac (optional, ops 9 - 14 and 16 - 20 only): n x 18 uint64, g1_to_jacobian(g1te_to_xyzz(te28_store_384(out[i]))) computed
- * on the device — the Weierstrass point a twisted Edwards result stands for.  status (optional): n words, written by ops 7 and 8. */
+ * Ops 21 - 26 are the 29-bit limb form of the table rows and of msm_accumulate_te (csrc/fq29.cuh).  Their accumulators are RAW
+ * slots of the 29-bit domain: four integers (X, Y, T, Z) whose value is a field element times 2^406, read as thirteen 29-bit
+ * limbs of which the last takes bits 348 and up (any representative below 2^380); results are written the same way.
+ *   21 msm_te_convert<29-bit rows>: as op 8, out = n rows of thirteen 29-bit limbs per coordinate (coordinate x 2^406, canonical)
+ *   22 te29_from_row(row a, neg)   23 te29_madd_row(raw acc a, row b, neg)
+ *   24 te29_quad_from_row(row a, neg)   25 te29_quad_madd_row(raw a one coordinate per lane, row b, neg)
+ *   26 te29_to_slot on the four coordinates of raw acc a (the accumulation's epilogue): out = a slot of the 28-bit domain
+ * out_jac (optional, ops 9 - 14, 16 - 20 and 22 - 26 only): n x 18 uint64, g1_to_jacobian(g1te_to_xyzz(te28_store_384(out[i])))
+ * computed on the device — the Weierstrass point a twisted Edwards result stands for (ops 22 - 25: of out[i] taken through
+ * te29_to_slot first).  status (optional): n words, written by ops 7 and 8. */
 int swm_selftest_p28(swm_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, const uint32_t *flags, uint64_t *out,
                      uint64_t *out_jac, uint32_t *status, size_t n);
 /* Device self-test of the polynomial drivers of the prover (csrc/devops.cuh) on host data in the memory (Montgomery) form,

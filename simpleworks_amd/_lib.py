@@ -1366,13 +1366,14 @@ class Context:
     P28_OPS = {"dbl": 0, "add": 1, "add_ool": 2, "slot_add": 3, "slot_add_inplace": 4, "slot_dbl": 5, "store_384": 6, "madd28": 7,
                "rows": 8, "te_from_row": 9, "te_madd_row": 10, "te_slot_add": 11, "te_slot_add_inplace": 12, "te_slot_add_self": 13,
                "te_slot_add_sync": 14, "te_store_384": 15, "quad_from_row": 16, "quad_madd_row": 17, "quad_add": 18,
-               "quad_add_self": 19, "quad_store_identity": 20}
+               "quad_add_self": 19, "quad_store_identity": 20, "rows29": 21, "te29_from_row": 22, "te29_madd_row": 23,
+               "te29_quad_from_row": 24, "te29_quad_madd_row": 25, "te29_to_slot": 26}
 
     def selftest_p28(self, op, a, b=None, flags=None, backmap=False, n=None):
         """swm_selftest_p28: one routine of the MSM's 28-bit point layer per element, on raw slots (n x 24 uint64; "rows": a = n x 12
-        uint64 affine points).  Returns (out n x 24 uint64, status n uint32, jac n x 18 uint64 or None when backmap is off)."""
+        uint64 affine points, "rows29" likewise; the te29_* ops: raw accumulators of the 29-bit domain, include/swmarlin.h).  Returns (out n x 24 uint64, status n uint32, jac n x 18 uint64 or None when backmap is off)."""
         if a is not None:
-            a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 12 if op == "rows" else 24)
+            a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 12 if op in ("rows", "rows29") else 24)
             n = a.shape[0]
         if n is None:
             raise ValueError("selftest_p28: an op without operand a needs n")

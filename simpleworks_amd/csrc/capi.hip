@@ -927,9 +927,10 @@ int swm_selftest_fr29(swm_ctx* ctx, int op, const uint32_t* a9, const uint32_t* 
 }
 int swm_selftest_p28(swm_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, const uint32_t* flags, uint64_t* out, uint64_t* out_jac,
                      uint32_t* status, size_t n) {
-    const bool rows = op == 8, te = (op >= 9 && op <= 14) || (op >= 16 && op <= 20);
-    const bool two = op == 1 || op == 2 || op == 3 || op == 4 || op == 7 || op == 10 || op == 11 || op == 12 || op == 14 || op == 17 || op == 18;
-    if (!ctx || op < 0 || op > 20 || (n && (!out || (op != 20 && !a) || (two && !b))) || (out_jac && !te)) return SWM_ERR_INVALID_ARG;
+    const bool rows = op == 8 || op == 21, te = (op >= 9 && op <= 14) || (op >= 16 && op <= 20) || (op >= 22 && op <= 26);
+    const bool two = op == 1 || op == 2 || op == 3 || op == 4 || op == 7 || op == 10 || op == 11 || op == 12 || op == 14 || op == 17 || op == 18 ||
+                     op == 23 || op == 25;
+    if (!ctx || op < 0 || op > 26 || (n && (!out || (op != 20 && !a) || (two && !b))) || (out_jac && !te)) return SWM_ERR_INVALID_ARG;
     SWM_ON_DEVICE(ctx);
     if (n == 0) return SWM_OK;
     const size_t in_bytes = n * (rows ? 96 : 192), out_bytes = n * 192;

@@ -424,6 +424,9 @@ __device__ __forceinline__ void p28_store_384(XYZZ& m, const P28& p) {
 }
 
 // ------------------------------------------------------------------------------------------------ twisted Edwards points in the 28-bit domain
+// The bucket stage adds in this domain (te28_slot_add, te28_quad_add, te28_store_384).  The ROW functions below — te28_load_coord,
+// te28_madd_row, te28_from_row and their quad forms — are no longer what msm_accumulate_te runs (fq29.cuh: the same law on
+// thirteen 29-bit limbs); they stay, bit for bit, for ops 9, 10, 16 and 17 of swm_selftest_p28 and tools/ubench/te28_bench.hip.
 // (the curve form, its constants and the reason for it: g1.cuh, "twisted Edwards form").  Coordinates are field elements
 // times 2^392; every coordinate of a point at rest is N (what fq28_mul returns).  In memory a point is a G1XYZZ whose
 // slots hold X, Y, T, Z (x, y, zz, zzz).  The law is unified: no identity / doubling / cancellation cases anywhere.

@@ -267,8 +267,10 @@ __device__ inline bool g1_in_subgroup_dev(const G1Affine& p) {
 // only for base sets known to lie in the prime-order subgroup (msm_table_build_te); it is what the precomputed-table
 // MSM accumulates and reduces in.  A TE point travels in a G1XYZZ-sized slot: x -> X, y -> Y, zz -> T, zzz -> Z.
 // One table row: affine, already in the form the mixed addition consumes — (y - x, y + x, 2 d x y), each coordinate times
-// 2^8 (Montgomery radix 2^392) as the FOURTEEN 28-BIT LIMBS the accumulation multiplies (fq28.cuh), in a 64-byte sector of
-// its own (limbs 14 and 15 are padding).  r04; r03 kept the coordinates packed (3 x 48 B): every row then cost 84
+// 2^22 (Montgomery radix 2^406) as the THIRTEEN 29-BIT LIMBS the accumulation multiplies (fq29.cuh), canonical, in a 64-byte
+// sector of its own (words 13 - 15 are padding).  (Until the 29-bit form: times 2^8, radix 2^392, fourteen 28-bit limbs of
+// fq28.cuh — msm_te_convert<false> still writes those rows for the te28_* functions of the self-test.)  The sector layout
+// is r04's; r03 kept the coordinates packed (3 x 48 B): every row then cost 84
 // shift / mask instructions to unpack and straddled 64-byte sectors (144-B rows: 25 % over-fetch), and the sign of a digit
 // cost two 14-limb selects where it now costs the choice of the ADDRESS the first two coordinates are loaded from.
 // 192 B per row instead of 144 B: 13 x 3 M rows = 7.5 GB per 2^20 key (5.6 GB before) of the 288 GB.

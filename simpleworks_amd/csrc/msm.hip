@@ -26,6 +26,7 @@
 #include "context.h"
 #include "fill.cuh"
 #include "fq28.cuh"
+#include "fq29.cuh"
 #include "g1.cuh"
 #include "msm.h"
 #include <atomic>
@@ -795,9 +796,19 @@ __global__ void __launch_bounds__(256) msm_table_normalize(const G1XYZZ* __restr
 }
 
 // affine points on y^2 = x^3 + 1 (plain form, radix 2^384) -> twisted Edwards table rows (y - x, y + x, 2 d x y), each
-// coordinate x 2^8 like the XYZZ table.  x = f (x_w + 1)/y_w, y = (u - 1)/(u + 1), u = s (x_w + 1): one inversion per
-// TAB_NORM_CHUNK points (of the product of their y_w (u + 1)).  The identity (0, 0) becomes the row (1, 1, 0) of (0, 1).
+// coordinate x 2^22 (Montgomery radix 2^406) as the thirteen 29-bit limbs msm_accumulate_te multiplies (fq29.cuh) — or, LIMB29
+// off, x 2^8 as fourteen 28-bit limbs: the rows of the te28_* functions, kept for the self-test.
+// x = f (x_w + 1)/y_w, y = (u - 1)/(u + 1), u = s (x_w + 1): one inversion per TAB_NORM_CHUNK points (of the product of their
+// y_w (u + 1)).  The identity (0, 0) becomes the row (1, 1, 0) of (0, 1).
 // A point with y_w (u + 1) = 0 (order 2, or mapped to infinity: never in the prime-order subgroup) raises *bad.
+template <int N>  // one coordinate's N limbs, zero padded, as the four 16-byte stores of its sector
+__device__ __forceinline__ void te_store_sector(uint4* o, const uint32_t (&l)[N]) {
+    o[0] = make_uint4(l[0], l[1], l[2], l[3]);
+    o[1] = make_uint4(l[4], l[5], l[6], l[7]);
+    o[2] = make_uint4(l[8], l[9], l[10], l[11]);
+    o[3] = make_uint4(l[12], N > 13 ? l[N - 1] : 0u, 0u, 0u);
+}
+template <bool LIMB29>
 __global__ void __launch_bounds__(256) msm_te_convert(const G1Affine* __restrict__ in, size_t n, Fq* __restrict__ pref,
                                                       G1TE* __restrict__ out, uint32_t* __restrict__ bad) {
     size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -815,10 +826,10 @@ __global__ void __launch_bounds__(256) msm_te_convert(const G1Affine* __restrict
         else acc = fp_mul(acc, den);
     }
     Fq inv = fp_inv(acc);
-    const uint32_t k256[12] = SWM_FQ_SCALE256_MONT;
-    Fq c256, one256;
+    const uint32_t k256[12] = SWM_FQ_SCALE256_MONT, k22[12] = SWM_FQ_SCALE22_MONT;
+    Fq c256, one256;  // the scale of the limb form (2^8, or 2^22 for LIMB29) and one in it
 #pragma unroll
-    for (int j = 0; j < 12; j++) c256.v[j] = k256[j];
+    for (int j = 0; j < 12; j++) c256.v[j] = LIMB29 ? k22[j] : k256[j];
     one256 = fp_mul(one, c256);
     for (size_t i = hi; i-- > lo;) {
         G1Affine p = in[i];
@@ -837,21 +848,17 @@ __global__ void __launch_bounds__(256) msm_te_convert(const G1Affine* __restrict
             ypx = fp_mul(fp_add(yt, xt), c256);
             kt = fp_mul(fp_mul(fq_const(TeParams::K2D), fp_mul(xt, yt)), c256);
         }
-        // canonical values split into the 28-bit limbs the accumulation multiplies, one 64-byte sector per coordinate
-        const Fq28 l0 = fq28_unpack(ymx), l1 = fq28_unpack(ypx), l2 = fq28_unpack(kt);
+        // canonical values split into the limbs the accumulation multiplies, one 64-byte sector per coordinate
         uint4* o = reinterpret_cast<uint4*>(&out[i]);
-        o[0] = make_uint4(l0.l[0], l0.l[1], l0.l[2], l0.l[3]);
-        o[1] = make_uint4(l0.l[4], l0.l[5], l0.l[6], l0.l[7]);
-        o[2] = make_uint4(l0.l[8], l0.l[9], l0.l[10], l0.l[11]);
-        o[3] = make_uint4(l0.l[12], l0.l[13], 0u, 0u);
-        o[4] = make_uint4(l1.l[0], l1.l[1], l1.l[2], l1.l[3]);
-        o[5] = make_uint4(l1.l[4], l1.l[5], l1.l[6], l1.l[7]);
-        o[6] = make_uint4(l1.l[8], l1.l[9], l1.l[10], l1.l[11]);
-        o[7] = make_uint4(l1.l[12], l1.l[13], 0u, 0u);
-        o[8] = make_uint4(l2.l[0], l2.l[1], l2.l[2], l2.l[3]);
-        o[9] = make_uint4(l2.l[4], l2.l[5], l2.l[6], l2.l[7]);
-        o[10] = make_uint4(l2.l[8], l2.l[9], l2.l[10], l2.l[11]);
-        o[11] = make_uint4(l2.l[12], l2.l[13], 0u, 0u);
+        if (LIMB29) {
+            te_store_sector<13>(o, fq29_unpack(ymx).l);
+            te_store_sector<13>(o + 4, fq29_unpack(ypx).l);
+            te_store_sector<13>(o + 8, fq29_unpack(kt).l);
+        } else {
+            te_store_sector<14>(o, fq28_unpack(ymx).l);
+            te_store_sector<14>(o + 4, fq28_unpack(ypx).l);
+            te_store_sector<14>(o + 8, fq28_unpack(kt).l);
+        }
     }
 }
 // [r]P = O and P on the curve, for every point that is not the identity (0, 0): double-and-add over the 253 bits of r
@@ -1208,10 +1215,11 @@ __global__ void __launch_bounds__(256, 3) msm_accumulate(const G1Affine* __restr
 }
 
 // The same kernel over a twisted Edwards table (msm_table_build_te): rows are the affine triples (y - x, y + x, 2 d x y), each
-// coordinate as the fourteen 28-bit limbs the multiplier takes, in a 64-byte sector of its own (192 B per row, consumed as loaded);
-// the accumulator is an extended point and every addition is the UNIFIED 7-product law of te28_madd_row — no doubling /
-// cancellation test, no cold path: 3 223 VALU instructions per addition of which 2 646 are multiply-adds (SQ pass, r04:
-// profiles/r04_pmc_sq_msm_accumulate.json; XYZZ: 4 817), 139 VGPRs, no scratch, three waves per SIMD.  Rows go HBM -> registers,
+// coordinate as the thirteen 29-bit limbs the multiplier takes (fq29.cuh), in a 64-byte sector of its own (192 B per row, consumed
+// as loaded); the accumulator is an extended point and every addition is the UNIFIED 7-product law of te29_madd_row — no doubling /
+// cancellation test, no cold path: 2 359 of its instructions are multiply-adds (7 x 337; on fourteen 28-bit limbs, r04: 3 223 VALU
+// instructions of which 2 646 multiply-adds, SQ pass profiles/r04_pmc_sq_msm_accumulate.json; XYZZ: 4 817), no scratch.  The epilogue
+// takes each coordinate into the 28-bit domain of the bucket stage (te29_to_slot: four products per segment).  Rows go HBM -> registers,
 // not through LDS: the kernel is issue-bound, a row is read once by one lane.  It is the one kernel of a
 // proof WITHOUT an issue priority (ff.cuh SWM_LIGHT_KERNEL): the filler everything else runs beside.  Partial sums leave as
 // extended points (X, Y, T, Z in the four slots of a G1XYZZ).  Algorithmic bytes per point: 96 B base + 32 B scalar.
@@ -1231,29 +1239,29 @@ __global__ void __launch_bounds__(256, SWM_TE_EARLY_LOADS ? 3 : 4) msm_accumulat
             te28_store_identity(partial[seg]);
             continue;
         }
-        T28 acc;
+        T29 acc;
         {
             const uint32_t ent = sorted[k0];
             const G1TE* row = rows + (ent & 0x7fffffffu);
-            acc = te28_from_row(te28_load_coord(row->ymx), te28_load_coord(row->ypx), te28_load_coord(row->kt), (ent >> 31) != 0);
+            acc = te29_from_row(te29_load_coord(row->ymx), te29_load_coord(row->ypx), te29_load_coord(row->kt), (ent >> 31) != 0);
         }
         // the entry of the NEXT addition is read while this one computes (index clamped to the segment: no branch), so that an
         // addition waits for one memory round trip — its row — and not for two in a row
         uint32_t ent = sorted[k0 + min(1u, len - 1) * stride];
         for (uint32_t j = 1; j < len; j++) {
             const uint32_t next = sorted[k0 + min(j + 1, len - 1) * stride];
-            te28_madd_row(acc, rows + (ent & 0x7fffffffu), (ent >> 31) != 0);
+            te29_madd_row(acc, rows + (ent & 0x7fffffffu), (ent >> 31) != 0);
             ent = next;
         }
-        partial[seg].x = fq28_pack(acc.x);
-        partial[seg].y = fq28_pack(acc.y);
-        partial[seg].zz = fq28_pack(acc.t);
-        partial[seg].zzz = fq28_pack(acc.z);
+        partial[seg].x = te29_to_slot(acc.x);
+        partial[seg].y = te29_to_slot(acc.y);
+        partial[seg].zz = te29_to_slot(acc.t);
+        partial[seg].zzz = te29_to_slot(acc.z);
     }
 }
 
 // The accumulation of SMALL MSMs (low-latency schedule, r04): four lanes per segment, the accumulator one coordinate per lane
-// (te28_quad_madd_row): the chain of a segment of 8 entries is 16 products long instead of 50, on a chip that such a job
+// (te29_quad_madd_row): the chain of a segment of 8 entries is 16 products long instead of 50, on a chip that such a job
 // cannot fill anyway.  Same partial sums, bit for bit.
 __global__ void __launch_bounds__(256) msm_accumulate_te_quad(const G1TE* __restrict__ rows, const uint32_t* __restrict__ sorted,
                                                               const uint32_t* __restrict__ seg_start,
@@ -1270,14 +1278,14 @@ __global__ void __launch_bounds__(256) msm_accumulate_te_quad(const G1TE* __rest
             continue;
         }
         uint32_t ent = sorted[k0];
-        Fq28 own = te28_quad_from_row(rows + (ent & 0x7fffffffu), (ent >> 31) != 0, q);
+        Fq29 own = te29_quad_from_row(rows + (ent & 0x7fffffffu), (ent >> 31) != 0, q);
         ent = sorted[k0 + min(1u, len - 1) * stride];
         for (uint32_t j = 1; j < len; j++) {
             const uint32_t next = sorted[k0 + min(j + 1, len - 1) * stride];
-            te28_quad_madd_row(own, rows + (ent & 0x7fffffffu), (ent >> 31) != 0, q);
+            te29_quad_madd_row(own, rows + (ent & 0x7fffffffu), (ent >> 31) != 0, q);
             ent = next;
         }
-        reinterpret_cast<Fq*>(&partial[seg])[q] = fq28_pack(own);  // X, Y, T (slot zz), Z (slot zzz)
+        reinterpret_cast<Fq*>(&partial[seg])[q] = te29_to_slot(own);  // X, Y, T (slot zz), Z (slot zzz)
     }
 }
 
@@ -1890,7 +1898,7 @@ static int msm_table_rows(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsi
                 hipLaunchKernelGGL(msm_table_normalize, dim3(gridn), dim3(256), 0, ctx->stream, (const G1XYZZ*)x, n, pref, cur);
                 src = cur;
             }
-            if (te) hipLaunchKernelGGL(msm_te_convert, dim3(gridn), dim3(256), 0, ctx->stream, src, n, pref, (G1TE*)(tab + w * row), d_bad);
+            if (te) hipLaunchKernelGGL(msm_te_convert<true>, dim3(gridn), dim3(256), 0, ctx->stream, src, n, pref, (G1TE*)(tab + w * row), d_bad);
             if (hipGetLastError() != hipSuccess) rc = set_err(ctx, SWM_ERR_HIP, "msm table: launch failed");
             if (rc == SWM_OK && !te) rc = msm_scale_bases_run(ctx, src, n, (G1Affine*)(tab + w * row));
         }
@@ -3115,8 +3123,30 @@ enum : int {
     P28T_DBL = 0, P28T_ADD, P28T_ADD_OOL, P28T_SLOT_ADD, P28T_SLOT_ADD_INPLACE, P28T_SLOT_DBL, P28T_STORE_384, P28T_MADD28,
     P28T_ROWS, P28T_TE_FROM_ROW, P28T_TE_MADD_ROW, P28T_TE_SLOT_ADD, P28T_TE_SLOT_ADD_INPLACE, P28T_TE_SLOT_ADD_SELF,
     P28T_TE_SLOT_ADD_SYNC, P28T_TE_STORE_384, P28T_QUAD_FROM_ROW, P28T_QUAD_MADD_ROW, P28T_QUAD_ADD, P28T_QUAD_ADD_SELF,
-    P28T_QUAD_STORE_IDENTITY, P28T_COUNT
+    P28T_QUAD_STORE_IDENTITY, P28T_ROWS29, P28T_TE29_FROM_ROW, P28T_TE29_MADD_ROW, P28T_TE29_QUAD_FROM_ROW, P28T_TE29_QUAD_MADD_ROW,
+    P28T_TE29_TO_SLOT, P28T_COUNT
 };
+// The te29 ops (fq29.cuh) take and return RAW accumulators of the 29-bit domain: four 12-word integers, a field element times
+// 2^406 each, any representative whose thirteenth limb (bits 348 ..) fits 32 bits.
+__device__ __forceinline__ Fq29 fq29_unpack_raw(const Fq& a) {
+    Fq29 r = fq29_unpack(a);
+    r.l[12] = (a.v[10] >> 28) | (a.v[11] << 4);
+    return r;
+}
+__device__ __forceinline__ T29 t29_load(const G1XYZZ& m) {
+    T29 r;
+    r.x = fq29_unpack_raw(m.x);
+    r.y = fq29_unpack_raw(m.y);
+    r.t = fq29_unpack_raw(m.zz);
+    r.z = fq29_unpack_raw(m.zzz);
+    return r;
+}
+__device__ __forceinline__ void t29_store(G1XYZZ& m, const T29& p) {  // (fq29_pack keeps a top limb above 2^29: it is shifted, not masked)
+    m.x = fq29_pack(p.x);
+    m.y = fq29_pack(p.y);
+    m.zz = fq29_pack(p.t);
+    m.zzz = fq29_pack(p.z);
+}
 __device__ __forceinline__ T28 t28_load(const G1XYZZ& m) {
     T28 r;
     r.x = fq28_unpack(m.x);
@@ -3221,6 +3251,25 @@ __global__ void __launch_bounds__(256) selftest_p28_kernel(int op, const G1XYZZ*
     case P28T_TE_STORE_384:
         te28_store_384(out[i], a[i]);
         break;
+    case P28T_TE29_FROM_ROW: {
+        const G1TE* row = reinterpret_cast<const G1TE*>(&a[i]);
+        t29_store(out[i], te29_from_row(te29_load_coord(row->ymx), te29_load_coord(row->ypx), te29_load_coord(row->kt), neg));
+        break;
+    }
+    case P28T_TE29_MADD_ROW: {
+        T29 acc = t29_load(a[i]);
+        te29_madd_row(acc, reinterpret_cast<const G1TE*>(&b[i]), neg);
+        t29_store(out[i], acc);
+        break;
+    }
+    case P28T_TE29_TO_SLOT: {  // the epilogue of msm_accumulate_te
+        const T29 acc = t29_load(a[i]);
+        out[i].x = te29_to_slot(acc.x);
+        out[i].y = te29_to_slot(acc.y);
+        out[i].zz = te29_to_slot(acc.t);
+        out[i].zzz = te29_to_slot(acc.z);
+        break;
+    }
     default:
         break;
     }
@@ -3251,28 +3300,47 @@ __global__ void __launch_bounds__(256) selftest_p28_quad_kernel(int op, const G1
     case P28T_QUAD_STORE_IDENTITY:
         te28_quad_store_identity(&out[i], q);
         break;
+    case P28T_TE29_QUAD_FROM_ROW:
+        reinterpret_cast<Fq*>(&out[i])[q] = fq29_pack(te29_quad_from_row(reinterpret_cast<const G1TE*>(&a[i]), neg, q));
+        break;
+    case P28T_TE29_QUAD_MADD_ROW: {
+        Fq29 own = fq29_unpack_raw(reinterpret_cast<const Fq*>(&a[i])[q]);
+        te29_quad_madd_row(own, reinterpret_cast<const G1TE*>(&b[i]), neg, q);
+        reinterpret_cast<Fq*>(&out[i])[q] = fq29_pack(own);
+        break;
+    }
     default:
         break;
     }
 }
 // a twisted Edwards slot of the 28-bit domain -> the Weierstrass point it stands for, by the maps the bucket stage and the host
 // fold apply to a total (te28_store_384, g1te_to_xyzz), as a Jacobian point in the memory form
-__global__ void __launch_bounds__(256) selftest_p28_backmap_kernel(const G1XYZZ* slots, G1Jac* out, size_t n) {
+// (from29: the slots hold a raw accumulator of the 29-bit domain, taken through the accumulation's epilogue first)
+__global__ void __launch_bounds__(256) selftest_p28_backmap_kernel(const G1XYZZ* slots, G1Jac* out, size_t n, bool from29) {
     const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
     if (i >= n) return;
-    G1XYZZ m;
-    te28_store_384(m, slots[i]);
+    G1XYZZ m, s = slots[i];
+    if (from29) {
+        const T29 acc = t29_load(s);
+        s.x = te29_to_slot(acc.x);
+        s.y = te29_to_slot(acc.y);
+        s.zz = te29_to_slot(acc.t);
+        s.zzz = te29_to_slot(acc.z);
+    }
+    te28_store_384(m, s);
     out[i] = g1_to_jacobian(g1te_to_xyzz(m));
 }
 int selftest_p28_run(swm_ctx* ctx, int op, const void* da, const void* db, const uint32_t* d_flags, void* d_out, void* d_jac,
                      void* d_pref, uint32_t* d_status, size_t n) {
     if (op < 0 || op >= P28T_COUNT) return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_p28: no such op");
     const unsigned grid = (unsigned)((n + 255) / 256);
-    if (op == P28T_ROWS) {
+    const bool quad = (op >= P28T_QUAD_FROM_ROW && op <= P28T_QUAD_STORE_IDENTITY) || op == P28T_TE29_QUAD_FROM_ROW ||
+                      op == P28T_TE29_QUAD_MADD_ROW;
+    if (op == P28T_ROWS || op == P28T_ROWS29) {
         const unsigned gridn = (unsigned)(((n + TAB_NORM_CHUNK - 1) / TAB_NORM_CHUNK + 255) / 256);
-        SWM_LAUNCH(ctx, "selftest_p28_rows", msm_te_convert, dim3(gridn), dim3(256), 0, (const G1Affine*)da, n, (Fq*)d_pref, (G1TE*)d_out,
-                   d_status);
-    } else if (op >= P28T_QUAD_FROM_ROW) {
+        SWM_LAUNCH(ctx, "selftest_p28_rows", op == P28T_ROWS29 ? msm_te_convert<true> : msm_te_convert<false>, dim3(gridn), dim3(256), 0,
+                   (const G1Affine*)da, n, (Fq*)d_pref, (G1TE*)d_out, d_status);
+    } else if (quad) {
         SWM_LAUNCH(ctx, "selftest_p28_quad", selftest_p28_quad_kernel, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, op,
                    (const G1XYZZ*)da, (const G1XYZZ*)db, d_flags, (G1XYZZ*)d_out, n);
     } else {
@@ -3280,7 +3348,8 @@ int selftest_p28_run(swm_ctx* ctx, int op, const void* da, const void* db, const
                    (G1XYZZ*)d_out, d_status, n);
     }
     if (d_jac)
-        SWM_LAUNCH(ctx, "selftest_p28_backmap", selftest_p28_backmap_kernel, dim3(grid), dim3(256), 0, (const G1XYZZ*)d_out, (G1Jac*)d_jac, n);
+        SWM_LAUNCH(ctx, "selftest_p28_backmap", selftest_p28_backmap_kernel, dim3(grid), dim3(256), 0, (const G1XYZZ*)d_out, (G1Jac*)d_jac, n,
+                   op >= P28T_TE29_FROM_ROW && op <= P28T_TE29_QUAD_MADD_ROW);
     return SWM_OK;
 }
 
