@@ -17,6 +17,7 @@
 #include "transfer_shape.h"
 #include "pedersen_transfer_shape.h"
 #include "rollup_shape.h"
+#include "account_update_shape.h"
 #include "program_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
@@ -391,6 +392,25 @@ int swm_pedersen_rollup_circuit_shape(size_t height, int salted, size_t n, size_
         return set_err(none, SWM_ERR_INVALID_ARG, "pedersen_rollup_circuit_shape: %zu transfers at height %zu (%zu <= transfers <= %zu, %zu <= "
                        "height <= %zu)", n, height, (size_t)RU_MIN_TRANSFERS, (size_t)RU_MAX_TRANSFERS, (size_t)PP_MIN_HEIGHT,
                        (size_t)PP_MAX_HEIGHT);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// The account-update circuit's shape (account_update_shape.h; the layout is build_account_update's)
+int swm_account_update_circuit_shape(size_t full_rounds, size_t partial_rounds, uint64_t alpha, size_t height, size_t* num_instance,
+                                     size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "account_update_circuit_shape: NULL output");
+    AccountUpdateShape s;
+    if (!account_update_shape(full_rounds, partial_rounds, alpha, height, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG,
+                       "account_update_circuit_shape: %zu + %zu rounds, alpha %llu, height %zu (full rounds even and >= 2, at most %zu rounds, "
+                       "alpha 2 .. %llu, %zu <= height <= %zu)",
+                       full_rounds, partial_rounds, (unsigned long long)alpha, height, (size_t)PC_MAX_ROUNDS, (unsigned long long)PC_MAX_ALPHA,
+                       (size_t)PY_MIN_HEIGHT, (size_t)PY_MAX_HEIGHT);
     *num_instance = s.num_instance;
     *num_witness = s.num_witness;
     *num_constraints = s.num_constraints;

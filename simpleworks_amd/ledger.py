@@ -15,6 +15,8 @@ checks.
 
 The tree is hash.DeviceMerkleTree (csrc/merkle_tree.hip): register and update_balance are tree.update, two launches each
 whatever the height; the signature scheme is schnorr.py; the proof of the signature circuit is marlin.generate_schnorr_proof.
+Over a Poseidon account tree both also exist PROVED (register_proved, update_balance_proved, apply_updates: the account-update
+circuit, workloads.build_account_update), so that the proofs of a ledger chain from State::new's blank root.
 
 Where this departs from the reference, on purpose:
   * The CRH shapes are those of src/merkle_tree/common.rs and hash.py — 144 and 128 windows of 4 bits.  ledger.rs:57-74 declares
@@ -246,6 +248,52 @@ class PedersenTransferCircuit:
             pass
 
 
+class AccountUpdateCircuit:
+    """The account-update circuit over resident Poseidon parameters (swm_account_update_circuit): synthesises the witness vector of
+    workloads.build_account_update for a block of registrations and balance updates applied in order, and advances the tree and the
+    account table through the block.  An operation is (id, kind, 64 key bytes, balance): kind 0 sets a balance (the key bytes are
+    not read), kind 1 registers key || balance.  Refers to the parameter set: keep it alive."""
+
+    def __init__(self, sponge, height):
+        self.ctx, self.sponge, self.height = sponge.ctx, sponge, height
+        self.h = self.ctx.account_update_circuit_create(sponge.h, height)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        from .marlin import account_update_circuit_shape
+        return account_update_circuit_shape(self.sponge.params, self.height)
+
+    def witness_at(self, tree, accounts, ops, guard=0):
+        """Against a hash.PoseidonMerkleTree whose leaf level is the table `accounts` (2^L leaves of 72 bytes, all-zero = no
+        account): (witness uint64 [count, num_witness, 4] — with guard > 0 the flat [count * num_witness + guard, 4], the guard
+        elements 0xFF bytes as before the call —, accounts after the block as bytes, old roots, new roots as ints, flags uint8
+        [count] (bit 0: applied), status uint32 [count]).  The tree is advanced; a refused operation's witness is all zero."""
+        acc = np.frombuffer(b"".join(bytes(a) for a in accounts), dtype=np.uint8).reshape(-1, LEAF_LEN)
+        if acc.shape[0] != 1 << (self.height - 1):
+            raise ValueError("the account table is 2^(height - 1) leaves of %d bytes" % LEAF_LEN)
+        ops = [(int(i), int(k), bytes(key), int(b)) for i, k, key, b in ops]
+        if any(not 0 <= i <= 255 or len(key) != 64 or not 0 <= b <= U64_MAX for i, _, key, b in ops):
+            raise ValueError("an operation is (id as one byte, kind, 64 key bytes, balance as u64)")
+        n, nw = len(ops), self.shape()[1]
+        keys = np.frombuffer(b"".join(o[2] for o in ops), dtype=np.uint8).reshape(n, 64)
+        w, acc, old, new, flags, status = self.ctx.account_update_witness_at(
+            self.h, tree.h, nw, acc, np.array([o[0] for o in ops], dtype=np.uint8), np.array([o[1] for o in ops], dtype=np.uint8), keys,
+            np.array([o[3] for o in ops], dtype=np.uint64), guard)
+        ints = lambda rows: [int.from_bytes(r.tobytes(), "little") for r in rows]
+        return (w if guard else w.reshape(n, nw, 4)), [a.tobytes() for a in acc], ints(old), ints(new), flags, status
+
+    def free(self):
+        if self.h:
+            self.ctx.account_update_circuit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class RollupCircuit(TransferCircuit):
     """The rollup of `transfers` transfers over resident Schnorr and Poseidon parameters: ONE vector (workloads.build_rollup's) for a
     block applied in order, all or nothing.  There is no handle of its own: it is a swm_transfer_circuit and a count."""
@@ -334,6 +382,8 @@ class State:
         self._transfer_keys = None   # (TransferCircuit, proving key, verifying key), the same
         self._pedersen_payment_keys = None   # (PedersenPaymentCircuit, proving key, verifying key), for a Pedersen account tree
         self._pedersen_transfer_keys = None  # (PedersenTransferCircuit, proving key, verifying key), the same
+        self._update_keys = None     # (AccountUpdateCircuit, proving key, verifying key), for a Poseidon account tree
+        self._update_circuit = None  # the circuit alone (no keys are needed to apply a block unproved)
         self._rollup_keys = {}       # transfers per block -> (RollupCircuit or PedersenRollupCircuit, proving key, verifying key)
         self._rollup_circuits = {}   # transfers per block -> the circuit alone (no keys are needed to apply a block unproved)
         self._rollup_transfer_system = None  # the ONE packed transfer system every block size is relabelled from
@@ -499,6 +549,101 @@ class State:
             self._pedersen_transfer_keys = (PedersenTransferCircuit(sig, leaf_crh, inner_crh, height), pk, vk)
         return self._pedersen_transfer_keys
 
+    def update_keys(self, rng):
+        """The account-update circuit (this ledger's Poseidon parameters and tree height) with its Marlin keys, derived once as
+        transfer_keys derives the transfer circuit's: one key serves registrations and balance updates."""
+        if self.account_tree != "poseidon":
+            raise ValueError("update_keys: the account-update circuit is over a Poseidon account tree")
+        if self._update_keys is None:
+            from . import marlin as M
+            from . import workloads as W
+            sponge = self.parameters.poseidon
+            height = self.account_merkle_tree.height()
+            cs, _ = W.account_update_circuit(sponge.params, height, 0, self.parameters.sig_params.generator, 0, 0, 1, [0] * (height - 1))
+            packed = cs.pack()
+            nnz = max(int(m[0][-1]) for m in packed.mats)
+            srs = M.MarlinInst.universal_setup(cs.num_constraints, len(cs.instance) + len(cs.witness), nnz, rng, sponge.ctx)
+            try:
+                pk, vk = M.MarlinInst.index_from_constraint_system(srs, packed)
+            finally:
+                srs.free()
+            self._update_keys = (AccountUpdateCircuit(sponge, height), pk, vk)
+        return self._update_keys
+
+    def apply_updates(self, pp, ops, rng, prove=True):
+        """A block of registrations and balance updates applied in order, each one proved: one witness pass on the GPU advances the
+        account tree through the whole block, then (with prove) one proof per applied operation under update_keys(rng), whose public
+        inputs are workloads.account_update_public_inputs (old_root, new_root, id, key_x, key_y, old_balance, new_balance, fresh).
+        An operation is ("register", id, public key) — the initial balance is 0, as State::register's — or ("balance", id, amount).
+        A Poseidon state only.  -> a list of (applied, proof or None, public inputs), one per operation; a refused operation (an
+        occupied or out-of-range id, an account that does not exist, a key that is not canonical) leaves the state as it was and
+        publishes equal roots.  next_available_account, pub_key_to_id and id_to_account_info follow the applied operations."""
+        if self.account_tree != "poseidon":
+            raise ValueError("apply_updates: the account-update circuit is over a Poseidon account tree")
+        from . import marlin as M
+        ops = list(ops)
+        if not ops:
+            return []
+        block = []
+        for what, acc, value in ops:
+            if what == "register":
+                block.append((int(acc), 1, schnorr.point_bytes(value), 0))
+            elif what == "balance":
+                block.append((int(acc), 0, bytes(64), int(value)))
+            else:
+                raise ValueError("apply_updates: an operation is (\"register\", id, public key) or (\"balance\", id, amount)")
+        tree = self.account_merkle_tree
+        table = self.account_table()
+        if prove:
+            circuit, pk, _ = self.update_keys(rng)
+            proofs, public, flags, _, _ = M.generate_account_update_proofs(pk, circuit, tree, table, block, rng)
+        else:
+            if self._update_keys is not None:
+                circuit = self._update_keys[0]
+            else:
+                if self._update_circuit is None:
+                    self._update_circuit = AccountUpdateCircuit(self.parameters.poseidon, tree.height())
+                circuit = self._update_circuit
+            _, _, old, new, flags, _ = circuit.witness_at(tree, table, block)
+            proofs, public = [None] * len(ops), []
+            for op, o, n, f in zip(block, old, new, flags):
+                public.append(M._account_update_public(table, op, o, n))
+                if f & 1:
+                    table[op[0]] = (op[2] if op[1] else table[op[0]][:64]) + op[3].to_bytes(8, "little")
+        for (what, acc, value), f in zip(ops, flags):
+            if not f & 1:
+                continue
+            if what == "register":
+                self.pub_key_to_id[value] = acc
+                self.id_to_account_info[acc] = AccountInformation(value, 0)
+                if self.next_available_account is not None and acc >= self.next_available_account:
+                    self.next_available_account = acc + 1 if acc < 255 else None     # checked_increment
+            else:
+                self.id_to_account_info[acc].balance = int(value)
+        return [(bool(f & 1), proof, pub) for f, proof, pub in zip(flags, proofs, public)]
+
+    def register_proved(self, public_key, rng):
+        """register with its proof: -> (the new account's id, proof bytes, public inputs), or None when the u8 ids have run out.
+        IndexError past the last leaf, as register."""
+        acc = self.next_available_account
+        if acc is None:
+            return None
+        if acc >= 1 << (self.account_merkle_tree.height() - 1):
+            raise IndexError("register: account %d is past the last leaf of the account tree" % acc)
+        applied, proof, public = self.apply_updates(self.parameters, [("register", acc, public_key)], rng)[0]
+        if not applied:
+            raise ValueError("register_proved: the registration of account %d was refused" % acc)
+        return acc, proof, public
+
+    def update_balance_proved(self, acc, new_amount, rng):
+        """update_balance with its proof: -> (proof bytes, public inputs), or None when there is no such account."""
+        if acc not in self.id_to_account_info:
+            return None
+        applied, proof, public = self.apply_updates(self.parameters, [("balance", acc, new_amount)], rng)[0]
+        if not applied:
+            raise ValueError("update_balance_proved: the update of account %d was refused" % acc)
+        return proof, public
+
     def account_table(self):
         """All 2^L leaves of the account tree as the state holds them, 72 bytes each; all-zero where there is no account."""
         blank = bytes(LEAF_LEN)
@@ -624,11 +769,16 @@ class State:
         return applied, proof, public
 
     def free(self):
-        for keys in (self._proof_keys, self._payment_keys, self._transfer_keys, self._pedersen_payment_keys, self._pedersen_transfer_keys):
+        for keys in (self._proof_keys, self._payment_keys, self._transfer_keys, self._pedersen_payment_keys, self._pedersen_transfer_keys,
+                     self._update_keys):
             if keys is not None:
                 keys[0].free()
                 keys[1].free()
         self._proof_keys = self._payment_keys = self._transfer_keys = self._pedersen_payment_keys = self._pedersen_transfer_keys = None
+        self._update_keys = None
+        if self._update_circuit is not None:
+            self._update_circuit.free()
+            self._update_circuit = None
         for _, pk, _ in self._rollup_keys.values():
             pk.free()
         for circuit in self._rollup_circuits.values():
@@ -654,6 +804,13 @@ def verify_payment(vk, public_inputs, proof, rng):
 def verify_transfer(vk, public_inputs, proof, rng):
     """The verifier of a transfer proof over either account tree: public_inputs = [old_root, new_root, sender, recipient, amount]
     (workloads.transfer_public_inputs = pedersen_transfer_public_inputs)."""
+    from . import marlin as M
+    return M.verify_proof(vk, [int(v) for v in public_inputs], proof if isinstance(proof, M.MarlinProof) else M.MarlinProof(proof), rng)
+
+
+def verify_update(vk, public_inputs, proof, rng):
+    """The verifier of an account-update proof: public_inputs = [old_root, new_root, id, key_x, key_y, old_balance, new_balance, fresh]
+    (workloads.account_update_public_inputs), vk that of State.update_keys."""
     from . import marlin as M
     return M.verify_proof(vk, [int(v) for v in public_inputs], proof if isinstance(proof, M.MarlinProof) else M.MarlinProof(proof), rng)
 

@@ -776,6 +776,98 @@ def generate_pedersen_transfer_proof(proving_key, circuit, tree, accounts, messa
     return generate_transfer_proof(proving_key, circuit, tree, accounts, message, signature, rng, uncompressed, "swm_pedersen_transfer_prove_at")
 
 
+def account_update_circuit_shape(params, height):
+    """swm_account_update_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the account-update circuit over a
+    Poseidon account tree of that height — what workloads.build_account_update emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_account_update_circuit_shape(params.full_rounds, params.partial_rounds, params.alpha, height,
+                                                           ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)),
+           "swm_account_update_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def _account_update_table(accounts, circuit):
+    import numpy as np
+    acc = np.array([np.frombuffer(bytes(a), dtype=np.uint8) for a in accounts], dtype=np.uint8, order="C")
+    if acc.ndim != 2 or acc.shape[1] != 72 or acc.shape[0] != 1 << (circuit.height - 1):
+        raise ValueError("the account table is 2^(height - 1) leaves of 72 bytes")
+    return acc
+
+
+def _account_update_public(table, op, old_root, new_root):
+    """The public inputs of one operation against the table it met (workloads.account_update_public_inputs)."""
+    from . import workloads as W
+    index, kind, key, balance = op
+    leaf = table[index] if index < len(table) else bytes(72)
+    if not kind:
+        key = leaf[:64]
+    old_balance = 0 if kind else int.from_bytes(leaf[64:], "little")
+    point = (int.from_bytes(key[:32], "little"), int.from_bytes(key[32:], "little"))
+    return W.account_update_public_inputs(old_root, new_root, index, point, old_balance, balance, kind)
+
+
+def generate_account_update_proofs(proving_key, circuit, tree, accounts, ops, rng, uncompressed=False):
+    """swm_account_update_prove_many_at: the block `ops` ((id, kind, 64 key bytes, balance) each; kind 0 = set balance, 1 =
+    register) applied IN ORDER to the resident account tree `tree` (a hash.PoseidonMerkleTree) and to the account table `accounts`
+    (2^L leaves of 72 bytes, all-zero = no account): one witness pass over the whole block, then one prover call per applied
+    operation.  The tree is advanced before the proofs are made.  Returns (proofs, public, flags, status, accounts after the block):
+    proofs[i] is the proof bytes or None for a refused operation, public[i] = workloads.account_update_public_inputs(...) of the
+    operation against the table it met (equal roots for a refused one), flags and status as include/swmarlin.h lists them."""
+    import numpy as np
+    ctx = proving_key.ctx
+    count = len(ops)
+    acc = _account_update_table(accounts, circuit)
+    if not count:
+        return [], [], [], [], [bytes(a) for a in acc]
+    ops = [(int(i), int(k), bytes(key), int(b)) for i, k, key, b in ops]
+    if any(not 0 <= i <= 255 or k not in (0, 1) or len(key) != 64 or not 0 <= b < 1 << 64 for i, k, key, b in ops):
+        raise ValueError("an operation is (id as one byte, kind 0 or 1, 64 key bytes, balance as u64)")
+    ids = (ctypes.c_uint8 * count).from_buffer_copy(bytes(o[0] for o in ops))
+    kinds = (ctypes.c_uint8 * count).from_buffer_copy(bytes(o[1] for o in ops))
+    keys = (ctypes.c_uint8 * (64 * count)).from_buffer_copy(b"".join(o[2] for o in ops))
+    bal = (ctypes.c_uint8 * (8 * count)).from_buffer_copy(b"".join(o[3].to_bytes(8, "little") for o in ops))
+    cap = 4096
+    out = (ctypes.c_uint8 * (cap * count))()
+    lens = (ctypes.c_size_t * count)()
+    old, new = (ctypes.c_uint8 * (32 * count))(), (ctypes.c_uint8 * (32 * count))()
+    flags, status = (ctypes.c_uint8 * count)(), (ctypes.c_uint32 * count)()
+    before = [bytes(a) for a in acc]
+    _check(ctx.lib.swm_account_update_prove_many_at(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, ids, kinds, keys, bal, count,
+                                                    rng.h, 1 if uncompressed else 0, out, cap, lens, old, new, flags, status),
+           "swm_account_update_prove_many_at", ctx)
+    raw, old, new = bytes(out), bytes(old), bytes(new)
+    public = []
+    for i, op in enumerate(ops):       # the table each operation met: the applied ones before it replayed on the host
+        o, n = int.from_bytes(old[32 * i:32 * i + 32], "little"), int.from_bytes(new[32 * i:32 * i + 32], "little")
+        public.append(_account_update_public(before, op, o, n))
+        if flags[i] & 1:
+            key = op[2] if op[1] else before[op[0]][:64]
+            before[op[0]] = key + op[3].to_bytes(8, "little")
+    return ([raw[cap * i:cap * i + lens[i]] if lens[i] else None for i in range(count)], public, list(flags), list(status),
+            [bytes(a) for a in acc])
+
+
+def generate_account_update_proof(proving_key, circuit, tree, accounts, op, rng, uncompressed=False):
+    """swm_account_update_prove_at: one operation (id, kind, 64 key bytes, balance); returns (proof or None, public inputs, flag,
+    status, accounts after it)."""
+    ctx = proving_key.ctx
+    acc = _account_update_table(accounts, circuit)
+    op = (int(op[0]), int(op[1]), bytes(op[2]), int(op[3]))
+    if not 0 <= op[0] <= 255 or op[1] not in (0, 1) or len(op[2]) != 64 or not 0 <= op[3] < 1 << 64:
+        raise ValueError("an operation is (id as one byte, kind 0 or 1, 64 key bytes, balance as u64)")
+    key = (ctypes.c_uint8 * 64).from_buffer_copy(op[2])
+    buf = (ctypes.c_uint8 * 4096)()
+    n = ctypes.c_size_t(0)
+    old, new = (ctypes.c_uint8 * 32)(), (ctypes.c_uint8 * 32)()
+    flag, status = ctypes.c_uint8(0), ctypes.c_uint32(0)
+    before = [bytes(a) for a in acc]
+    _check(ctx.lib.swm_account_update_prove_at(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, op[0], op[1], key, op[3], rng.h,
+                                               1 if uncompressed else 0, buf, len(buf), ctypes.byref(n), old, new, ctypes.byref(flag),
+                                               ctypes.byref(status)), "swm_account_update_prove_at", ctx)
+    public = _account_update_public(before, op, int.from_bytes(bytes(old), "little"), int.from_bytes(bytes(new), "little"))
+    return (bytes(buf[: n.value]) if n.value else None, public, flag.value, status.value, [bytes(a) for a in acc])
+
+
 def rollup_circuit_shape(params, height, transfers, salted=False):
     """swm_rollup_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the rollup of `transfers` transfers over a
     Poseidon account tree of that height — what workloads.build_rollup emits."""

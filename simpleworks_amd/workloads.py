@@ -1599,13 +1599,17 @@ def payment_public_inputs(root, message):
     return [int(root) % R_MODULUS, message[0], message[1], int.from_bytes(message[2:], "little")]
 
 
-def _py_membership(cs, one, params, leaf_bits, id_bits, index, siblings, root_v, keep=None):
+def _py_membership(cs, one, params, leaf_bits, id_bits, index, siblings, root_v, keep=None, start=None):
     """One membership block: the witness section of build_poseidon_membership over leaf bits that already are variables, the
     eight rows that tie the index bits to the id bits, and build_poseidon_membership's rows after its booleanity rows.
-    Returns the walked root's value.  keep (a list): receives the b_l and the s_l, for a block that walks the same path again."""
+    Returns the walked root's value.  keep (a list): receives the b_l and the s_l, for a block that walks the same path again.
+    start (a function): the levels walk from another digest than the leaf's: start(h), called with the leaf digest once the leaf
+    chain and its rows are out, emits what ties the two and returns the digest to walk from (a _PsLC)."""
     levels = len(siblings)
     values = _PsNullSystem()
     c = _ps_leaf_digest(values, None, params, [(None, v) for _, v in leaf_bits], PAYMENT_LEAF_LEN).value
+    if start is not None:
+        c = start(None).value
     cur_values = []
     for lvl, s in enumerate(siblings):
         cur_values.append(c)
@@ -1625,6 +1629,8 @@ def _py_membership(cs, one, params, leaf_bits, id_bits, index, siblings, root_v,
         else:
             cs.enforce_constraint([(1, id_bits[lvl])], [(1, one)], [])
     cur = _ps_leaf_digest(cs, one, params, leaf_bits, PAYMENT_LEAF_LEN)
+    if start is not None:
+        cur = start(cur)
     for lvl in range(levels):
         b, s, d = dirs[lvl], sibs[lvl], deltas[lvl]
         cs.enforce_constraint(b.terms, [(1, one), (R_MODULUS - 1, b.terms[0][1])], [])
@@ -1925,6 +1931,161 @@ class TransferValidation:
     def generate_constraints(self, cs):
         build_transfer(cs, self.generator, self.salt, self.params, self.height, self.message, self.signature, self.sender_leaf,
                        self.sender_path, self.recipient_leaf, self.recipient_path, old_root=self.old_root, new_root=self.new_root)
+
+
+# ===================================================================================================================
+# The two other state changes of the reference's ledger as ONE circuit: State::register (ledger.rs:131-150) and
+# State::update_balance (:166-173) over a Poseidon account tree.  "The leaf at `id` becomes key || new_balance (72 bytes as
+# AccountInformation::to_bytes_le writes them), every other leaf stays; the old leaf is key || old_balance when fresh = 0 and the
+# blank leaf when fresh = 1."  The blank leaf's level-0 node is the zero digest (as the resident tree holds it), not the hash of 72
+# zero bytes, so the old side's leaf hash h is MASKED: cur_0 = (1 - fresh) h, and the membership block walks from cur_0.  There is
+# no Schnorr block and no on-curve row: register takes any key, a leaf is bytes.  build_account_update is the layout contract of
+# csrc/host/account_update_shape.h and csrc/account_update_witness.hip.  With L, C, M = 3 L + (2 + L) C and U = M - 2 L as above:
+#   instance  one, old_root, new_root, id, key_x, key_y, old_balance, new_balance, fresh
+#   witness   512 key bits (x then y, least significant first) | 64 bits of old_balance | 64 of new_balance | 8 id bits       648
+#             cur_0                                                                                                       1
+#             the old leaf's membership block against old_root: b_l | s_l | d_l | the leaf chain of h over key || old_balance
+#             | L level chains walked from cur_0 (a membership block's own order: the leaf chain stays where it is)          M
+#             the update block over key || new_balance on the same b_l and s_l, its root row against new_root               U
+#   rows      648 booleanity rows | pack(key bits 0..255) = key_x, pack(256..511) = key_y, pack(old) = old_balance, pack(new) =
+#             new_balance, pack(id bits) = id | fresh (1 - fresh) = 0 | fresh pack(old) = 0 | the membership block: eight index
+#             rows, the leaf chain, fresh h = h - cur_0, per level booleanity, the delta row and C chain rows, the root row | the
+#             update block: the leaf chain, per level the delta row and C chain rows, the root row
+#                                                            655 + (8 + 2 C + 1 + L (2 + C) + 1) + (2 C + L (1 + C) + 1)
+# The key is packed UNREDUCED and with no strict-canonical check, the caveat of the Schnorr block's `dec` bits: key_x = x mod r for
+# whatever 256 bits the leaf holds, so two leaves whose coordinates differ by r publish the same key (the library's entry refuses
+# to register a coordinate >= r).  The leaf hash is always computed and recorded honestly; fresh only masks it: fresh = 1 on an
+# occupied leaf or fresh = 0 on a blank one walks to another root than old_root and fails the membership's root row.  A registration
+# cannot claim an old balance (its own row); one whose new leaf is all-zero is a satisfied no-op and is refused by the library.
+# ===================================================================================================================
+ACCOUNT_UPDATE_BITS = 512 + 64 + 64 + 8      # 648 booleans ahead of cur_0
+
+
+def account_update_circuit_layout(params, height):
+    """Offsets of the witness groups and the named rows of build_account_update and its three counts, as
+    csrc/host/account_update_shape.h states them."""
+    if not 2 <= height <= 9:
+        raise ValueError("account update circuit: 2 <= height <= 9 (an account id is one byte)")
+    mb = poseidon_membership_layout(params, height, PAYMENT_LEAF_LEN)
+    levels, c, m = mb["levels"], mb["permutation_values"], mb["num_witness"]
+    u = m - 2 * levels
+    lay = {"membership": mb, "levels": levels, "membership_witnesses": m, "update_witnesses": u,
+           "update": {"deltas": 0, "leaf": levels, "level0": levels + 2 * c}}
+    lay.update(key_bits=0, old_balance=512, new_balance=576, id_bits=640, cur0=ACCOUNT_UPDATE_BITS, old=ACCOUNT_UPDATE_BITS + 1)
+    lay["new"] = lay["old"] + m
+    lay["num_instance"] = 9
+    lay["num_witness"] = lay["new"] + u
+    lay["pack_rows"] = ACCOUNT_UPDATE_BITS            # key_x, key_y, old_balance, new_balance, id
+    lay["fresh_row"] = lay["pack_rows"] + 5
+    lay["fresh_balance_row"] = lay["fresh_row"] + 1
+    lay["old_rows"] = lay["fresh_balance_row"] + 1
+    lay["mask_row"] = lay["old_rows"] + 8 + 2 * c
+    lay["old_root_row"] = lay["mask_row"] + 1 + levels * (2 + c)
+    lay["new_rows"] = lay["old_root_row"] + 1
+    lay["new_root_row"] = lay["new_rows"] + 2 * c + levels * (1 + c)
+    lay["num_constraints"] = lay["new_root_row"] + 1
+    return lay
+
+
+def account_update_public_inputs(old_root, new_root, index, key, old_balance, new_balance, fresh):
+    """The eight public inputs of the account-update circuit, in instance order: old_root, new_root, id, key_x, key_y, old_balance,
+    new_balance, fresh.  key: (x, y) as ints; a registration's old_balance is 0."""
+    return [int(old_root) % R_MODULUS, int(new_root) % R_MODULUS, int(index), int(key[0]) % R_MODULUS, int(key[1]) % R_MODULUS,
+            int(old_balance), int(new_balance), int(fresh) % R_MODULUS]
+
+
+def _au_walk_from(params, digest, index, siblings):
+    """The root a walk from a given level-0 digest leads to."""
+    values = _PsNullSystem()
+    c = digest
+    for lvl, s in enumerate(siblings):
+        a, b = (s, c) if (index >> lvl) & 1 else (c, s)
+        c = _ps_permute(values, None, params, [_PsLC({}, a), _PsLC({}, b), _PsLC()])[0].value
+    return c
+
+
+def build_account_update(cs, params, height, index, key, old_balance, new_balance, fresh, siblings, old_root=None, new_root=None):
+    """Emits the account-update circuit into `cs`.  params: a hash.PoseidonParameters; index: the account id, one byte (an id at or
+    above 2^(height - 1) is taken by its low bits and fails an index row); key: (x, y), ints below 2^256; the two balances: u64;
+    fresh: 1 for a registration (the old leaf is blank), 0 for a balance update (any other value is taken as it is: the witness
+    cur_0 = (1 - fresh) h stays honest and the booleanity row fails); siblings: ints, bottom up, height - 1 of them.  old_root,
+    new_root override the two public roots, which otherwise are the walked values.  Returns the public inputs [old_root, new_root,
+    id, key_x, key_y, old_balance, new_balance, fresh]."""
+    levels = height - 1
+    if not 2 <= height <= 9 or len(siblings) != levels:
+        raise ValueError("account update circuit: 2 <= height <= 9 and a path of height - 1 siblings")
+    index, old_balance, new_balance, fresh = int(index), int(old_balance), int(new_balance), int(fresh)
+    x, y = int(key[0]), int(key[1])
+    if not 0 <= index <= 255 or not 0 <= x < 1 << 256 or not 0 <= y < 1 << 256:
+        raise ValueError("account update circuit: an id of one byte and key coordinates of 32 bytes")
+    if not 0 <= old_balance <= (1 << 64) - 1 or not 0 <= new_balance <= (1 << 64) - 1:
+        raise ValueError("account update circuit: a balance is a u64")
+    siblings = [int(s) % R_MODULUS for s in siblings]
+    walked = index & ((1 << levels) - 1)
+    key_values = [(byte >> i) & 1 for byte in x.to_bytes(32, "little") + y.to_bytes(32, "little") for i in range(8)]
+    old_values, new_values = [(old_balance >> i) & 1 for i in range(64)], [(new_balance >> i) & 1 for i in range(64)]
+    h_v = _ps_leaf_digest(_PsNullSystem(), None, params, [(None, v) for v in key_values + old_values], PAYMENT_LEAF_LEN).value
+    cur0_v = (1 - fresh) * h_v % R_MODULUS
+    old_v = _au_walk_from(params, cur0_v, walked, siblings)
+    new_v = _tr_walk(params, [(None, v) for v in key_values + new_values], walked, siblings)[-1]
+    old_root = old_v if old_root is None else int(old_root) % R_MODULUS
+    new_root = new_v if new_root is None else int(new_root) % R_MODULUS
+    one = cs.one()
+    public = account_update_public_inputs(old_root, new_root, index, (x, y), old_balance, new_balance, fresh)
+    old_i, new_i, id_i, kx_i, ky_i, ob_i, nb_i, fresh_i = [cs.new_input_variable(v) for v in public]
+
+    def boolean(v):
+        var = cs.new_witness_variable(v)
+        cs.enforce_constraint([(1, var)], [(1, one), (R_MODULUS - 1, var)], [])
+        return var
+
+    def pack(bits):
+        return [((1 << i) % R_MODULUS, b) for i, b in enumerate(bits)]
+    key_bits = [(boolean(v), v) for v in key_values]
+    old_bits = [(boolean(v), v) for v in old_values]
+    new_bits = [(boolean(v), v) for v in new_values]
+    id_bits = [boolean((index >> i) & 1) for i in range(8)]
+    cur0 = _PsLC({cs.new_witness_variable(cur0_v): 1}, cur0_v)
+    # the booleans are the public input
+    cs.enforce_constraint(pack([b for b, _ in key_bits[:256]]), [(1, one)], [(1, kx_i)])
+    cs.enforce_constraint(pack([b for b, _ in key_bits[256:]]), [(1, one)], [(1, ky_i)])
+    cs.enforce_constraint(pack([b for b, _ in old_bits]), [(1, one)], [(1, ob_i)])
+    cs.enforce_constraint(pack([b for b, _ in new_bits]), [(1, one)], [(1, nb_i)])
+    cs.enforce_constraint(pack(id_bits), [(1, one)], [(1, id_i)])
+    # fresh is a bit, and a registration claims no old balance
+    cs.enforce_constraint([(1, fresh_i)], [(1, one), (R_MODULUS - 1, fresh_i)], [])
+    cs.enforce_constraint([(1, fresh_i)], pack([b for b, _ in old_bits]), [])
+
+    def start(h):
+        if h is not None:       # fresh h = h - cur_0
+            cs.enforce_constraint([(1, fresh_i)], h.terms, _PsLC(h.coeffs, h.value).add(R_MODULUS - 1, cur0).terms)
+        return cur0
+    # the old leaf in the old tree, then the new leaf up the same path
+    path = []
+    _py_membership(cs, one, params, key_bits + old_bits, id_bits, walked, siblings, [(1, old_i)], keep=path, start=start)
+    _tr_update(cs, one, params, key_bits + new_bits, path[0], path[1], [(1, new_i)])
+    return public
+
+
+def account_update_circuit(params, height, index, key, old_balance, new_balance, fresh, siblings, old_root=None, new_root=None):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs)."""
+    cs = ConstraintSystem()
+    public = build_account_update(cs, params, height, index, key, old_balance, new_balance, fresh, siblings, old_root, new_root)
+    return cs, public
+
+
+class AccountUpdate:
+    """The ConstraintSynthesizer of the account-update statement for MarlinInst.index / prove: constants = the sponge parameters,
+    public = old_root, new_root, id, key, old_balance, new_balance, fresh, witness = the leaf's path."""
+
+    def __init__(self, params, height, old_root, new_root, index, key, old_balance, new_balance, fresh, path):
+        self.params, self.height, self.old_root, self.new_root = params, height, old_root, new_root
+        self.index, self.key, self.old_balance, self.new_balance, self.fresh = index, key, old_balance, new_balance, fresh
+        self.path = list(path)
+
+    def generate_constraints(self, cs):
+        build_account_update(cs, self.params, self.height, self.index, self.key, self.old_balance, self.new_balance, self.fresh,
+                             self.path, old_root=self.old_root, new_root=self.new_root)
 
 
 # ===================================================================================================================
