@@ -1285,9 +1285,15 @@ int swm_selftest_fr29(swm_ctx *ctx, int op, const uint32_t *a9, const uint32_t *
  *   22 te29_from_row(row a, neg)   23 te29_madd_row(raw acc a, row b, neg)
  *   24 te29_quad_from_row(row a, neg)   25 te29_quad_madd_row(raw a one coordinate per lane, row b, neg)
  *   26 te29_to_slot on the four coordinates of raw acc a (the accumulation's epilogue): out = a slot of the 28-bit domain
- * out_jac (optional, ops 9 - 14, 16 - 20 and 22 - 26 only): n x 18 uint64, g1_to_jacobian(g1te_to_xyzz(te28_store_384(out[i])))
- * computed on the device — the Weierstrass point a twisted Edwards result stands for (ops 22 - 25: of out[i] taken through
- * te29_to_slot first).  status (optional): n words, written by ops 7 and 8. */
+ * Ops 27 - 36 are the general addition of the 29-bit domain (csrc/fq29.cuh: what the one-lane bucket stage runs).  a, b and out are raw
+ * slots as for ops 22 - 25; the device moves them into unpacked 208-byte points (TE29Pt) for the routine and the result back.
+ *   27 te29_slot_add(out, a, b)   28 the same with dst == pa   29 with dst == pq   30 te29_slot_add(out, a, a)
+ *   31 te29_slot_add_sync(out, a, b, act, barrier on): a slot whose lane sits out reads back as bytes 0xA5
+ *   32 te29_quad_add(out, a, b)   33 te29_quad_add(out, a, a)   34 te29_store_identity(out)   35 te29_quad_store_identity(out)
+ *   36 te29_store_384(a): out = the point in canonical radix-2^384 coordinates, the form te28_store_384 (op 15) writes
+ * out_jac (optional, ops 9 - 14, 16 - 20 and 22 - 35 only): n x 18 uint64, g1_to_jacobian(g1te_to_xyzz(te28_store_384(out[i])))
+ * computed on the device — the Weierstrass point a twisted Edwards result stands for (ops 22 - 25 and 27 - 35: of out[i] taken
+ * through te29_to_slot first).  status (optional): n words, written by ops 7 and 8. */
 int swm_selftest_p28(swm_ctx *ctx, int op, const uint64_t *a, const uint64_t *b, const uint32_t *flags, uint64_t *out,
                      uint64_t *out_jac, uint32_t *status, size_t n);
 /* Device self-test of the polynomial drivers of the prover (csrc/devops.cuh) on host data in the memory (Montgomery) form,
@@ -1335,6 +1341,10 @@ int swm_selftest_spmv_plan(swm_ctx *ctx, const uint32_t *rowptr, const uint32_t 
 int swm_selftest_msm_jobs(swm_ctx *ctx, const swm_bases *const *sets, size_t nsets, const uint64_t *scalars, const size_t *vec_off,
                           size_t nvec, int scalars_montgomery, const uint64_t *jobs, size_t k, int defer_tail, size_t pipe_min,
                           uint64_t *out_jac, uint64_t *twins);
+/* Jobs whose bucket stage each kernel has run on this context so far: out[0] the quad stage (msm_bucket_reduce<RB, FormTEQuad>, partial
+ * sums in 28-bit slots), out[1] msm_bucket_reduce_low, out[2] msm_bucket_reduce<256, FormTE29> (both on raw 29-bit partial sums),
+ * out[3] msm_bucket_reduce<256, FormXYZZ>.  For tests that hold a job shape to the path it is meant to take.  Needs no GPU work. */
+int swm_selftest_msm_tail_counts(swm_ctx *ctx, uint64_t out[4]);
 /* The bulk Fr sampler of the prover (sample_fr_bulk) on a generator handle: `need` elements drawn into a device buffer and
  * downloaded to out_mont (n x 4 uint64, Montgomery form), advancing rng as `need` successive swm_rng_rand_fr calls would. */
 int swm_selftest_sample_fr(swm_ctx *ctx, swm_rng *rng, size_t need, uint64_t *out_mont);

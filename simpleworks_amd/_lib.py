@@ -277,6 +277,7 @@ ABI = {
     "swm_selftest_sample_fr": (_int, [_vp, _vp, _sz, _u64p]),
     "swm_selftest_msm_jobs": (_int, [_vp, ctypes.POINTER(_vp), _sz, _u64p, ctypes.POINTER(_sz), _sz, _int, _u64p, _sz, _int, _sz,
                                      _u64p, _u64p]),
+    "swm_selftest_msm_tail_counts": (_int, [_vp, _u64p]),
     "swm_verify_proofs_batch": (_int, [_vp, _vp, _u64p, _sz, _vp, ctypes.POINTER(_sz), _sz, ctypes.c_uint, _vp,
                                        ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "swm_selftest_verify_batch": (_int, [_vp, _vp, _u64p, _sz, _vp, ctypes.POINTER(_sz), _sz, ctypes.c_uint, _vp,
@@ -1409,7 +1410,10 @@ class Context:
                "rows": 8, "te_from_row": 9, "te_madd_row": 10, "te_slot_add": 11, "te_slot_add_inplace": 12, "te_slot_add_self": 13,
                "te_slot_add_sync": 14, "te_store_384": 15, "quad_from_row": 16, "quad_madd_row": 17, "quad_add": 18,
                "quad_add_self": 19, "quad_store_identity": 20, "rows29": 21, "te29_from_row": 22, "te29_madd_row": 23,
-               "te29_quad_from_row": 24, "te29_quad_madd_row": 25, "te29_to_slot": 26}
+               "te29_quad_from_row": 24, "te29_quad_madd_row": 25, "te29_to_slot": 26, "te29_slot_add": 27,
+               "te29_slot_add_inplace_a": 28, "te29_slot_add_inplace_q": 29, "te29_slot_add_self": 30, "te29_slot_add_sync": 31,
+               "te29_quad_add": 32, "te29_quad_add_self": 33, "te29_store_identity": 34, "te29_quad_store_identity": 35,
+               "te29_store_384": 36}
 
     def selftest_p28(self, op, a, b=None, flags=None, backmap=False, n=None):
         """swm_selftest_p28: one routine of the MSM's 28-bit point layer per element, on raw slots (n x 24 uint64; "rows": a = n x 12
@@ -1540,6 +1544,12 @@ class Context:
                                                    _p64(spec), spec.shape[0], self.MSM_DEFER[defer_tail], pipe_min, _p64(out),
                                                    _p64(twins)), "swm_selftest_msm_jobs")
         return out[:spec.shape[0]], int(twins[0])
+
+    def selftest_msm_tail_counts(self):
+        """swm_selftest_msm_tail_counts: jobs per bucket-stage kernel on this context so far, as a dict quad / low / te29 / xyzz."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.swm_selftest_msm_tail_counts(self.h, _p64(out)), "swm_selftest_msm_tail_counts")
+        return dict(zip(("quad", "low", "te29", "xyzz"), (int(v) for v in out)))
 
     @contextlib.contextmanager
     def selftest_witness_stage(self, nbytes):

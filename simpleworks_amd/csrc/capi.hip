@@ -927,10 +927,11 @@ int swm_selftest_fr29(swm_ctx* ctx, int op, const uint32_t* a9, const uint32_t* 
 }
 int swm_selftest_p28(swm_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, const uint32_t* flags, uint64_t* out, uint64_t* out_jac,
                      uint32_t* status, size_t n) {
-    const bool rows = op == 8 || op == 21, te = (op >= 9 && op <= 14) || (op >= 16 && op <= 20) || (op >= 22 && op <= 26);
+    const bool rows = op == 8 || op == 21, te = (op >= 9 && op <= 14) || (op >= 16 && op <= 20) || (op >= 22 && op <= 35);
     const bool two = op == 1 || op == 2 || op == 3 || op == 4 || op == 7 || op == 10 || op == 11 || op == 12 || op == 14 || op == 17 || op == 18 ||
-                     op == 23 || op == 25;
-    if (!ctx || op < 0 || op > 26 || (n && (!out || (op != 20 && !a) || (two && !b))) || (out_jac && !te)) return SWM_ERR_INVALID_ARG;
+                     op == 23 || op == 25 || op == 27 || op == 28 || op == 29 || op == 31 || op == 32;
+    const bool no_a = op == 20 || op == 34 || op == 35;  // the identity stores
+    if (!ctx || op < 0 || op > 36 || (n && (!out || (!no_a && !a) || (two && !b))) || (out_jac && !te)) return SWM_ERR_INVALID_ARG;
     SWM_ON_DEVICE(ctx);
     if (n == 0) return SWM_OK;
     const size_t in_bytes = n * (rows ? 96 : 192), out_bytes = n * 192;
@@ -1075,6 +1076,11 @@ int swm_selftest_msm_jobs(swm_ctx* ctx, const swm_bases* const* sets, size_t nse
     }
     for (size_t i = 0; i < k; i++) write_jac(res[i], out_jac + 18 * i);
     *twins = ctx->stat_msm_twins - twins_before;
+    return SWM_OK;
+}
+int swm_selftest_msm_tail_counts(swm_ctx* ctx, uint64_t out[4]) {
+    if (!ctx || !out) return SWM_ERR_INVALID_ARG;
+    for (int i = 0; i < 4; i++) out[i] = ctx->stat_msm_tails[i];
     return SWM_OK;
 }
 

@@ -82,6 +82,7 @@ struct swm_ctx {
     // work log since the last swm_profile_reset (the prove() byte count is the sum over logged calls)
     uint64_t stat_msm_digits = 0;  // points x windows (zero digits included)
     uint64_t stat_msm_twins = 0;   // jobs that took the sort of their twin (msm.h: MsmTwin)
+    uint64_t stat_msm_tails[4] = {0, 0, 0, 0};  // jobs per bucket-stage kernel: quad | low-LDS | one-lane twisted Edwards (wide / thin) | XYZZ
     uint64_t stat_msm_adds = 0;    // NON-ZERO digits = bucket entries = the mixed additions msm_accumulate performs (counted by
                                    // the sort on the device; collected in msm_finish)
     uint64_t stat_msm_zero_points = 0;  // MSM points with a zero scalar or an identity base (nothing but their scalar is read)

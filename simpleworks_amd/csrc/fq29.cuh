@@ -5,8 +5,11 @@
 // against 378 (404 instructions against 447), and every limb-wise addition, load and select is 13 long instead of 14.
 // What it costs: a column of thirteen products of 29-bit limbs leaves less room in the 64-bit accumulator than fourteen of
 // 28-bit ones, so two of the eight operands of the mixed addition's second round are carry-normalised first (below).
-// Everything downstream of the accumulation (bucket stage, host fold, wire formats) stays in the 28-bit domain: the
-// accumulation's epilogue converts (te29_to_slot).
+// The domain no longer ends at the accumulation: a job whose bucket stage works one lane per chain (msm_bucket_reduce<256, FormTE29>,
+// msm_bucket_reduce_low) gets its partial sums as they stand in the accumulator — unpacked, no product spent on them — and adds them
+// by the general addition at the end of this file (te29_slot_add); the workgroup results leave through te29_store_384 in the
+// canonical radix-2^384 form the host fold and the wire formats always saw.  Only the quad bucket stage of small jobs (FormTEQuad)
+// still adds in the 28-bit domain: for those jobs the accumulation's epilogue converts (te29_to_slot).
 //
 // Representation.  value = sum l[i] 2^(29 i); Montgomery radix 2^406 = 2^(29 x 14): FOURTEEN reduction steps for thirteen
 // limbs, so that a product of two operands of several p comes back below p (1 + 2^-23) — with thirteen steps (radix 2^377,
@@ -40,6 +43,8 @@ struct Fq29Consts {
     static constexpr uint32_t TWO[13] = SWM_FQ29_TWO;
     static constexpr uint32_t INVD[13] = SWM_FQ29_TE_INVD;
     static constexpr uint32_t TO392[13] = SWM_FQ29_TO392;
+    static constexpr uint32_t K2D[13] = SWM_FQ29_TE_2D;
+    static constexpr uint32_t TO384[13] = SWM_FQ29_TO384;
     static constexpr uint32_t SPREAD2[13] = SWM_FQ29_SPREAD2;
     static constexpr uint32_t SPREAD4[13] = SWM_FQ29_SPREAD4;
 };
@@ -316,6 +321,249 @@ __device__ __forceinline__ Fq29 te29_quad_from_row(const G1TE* __restrict__ rp, 
 #pragma unroll
     for (int i = 0; i < 13; i++) r.l[i] = q < 2 ? d.l[i] : (q == 2 ? t.l[i] : Fq29Consts::TWO[i]);
     return r;
+}
+
+// ------------------------------------------------------------------------------------------------ the general addition (bucket stage)
+// A point at rest in MEMORY (a partial sum in HBM, an LDS slot of the bucket stage): X | Y | T | Z, thirteen limbs each, unpacked —
+// 4 x 13 x 4 B = 208 B, thirteen 128-bit words, the stride of the bucket stage's padded 28-bit slot (msm.hip RedSlot), so the
+// LDS budget and the bank layout of its 128-bit accesses are those of the 28-bit form; nothing is packed or unpacked on the way.
+// A coordinate is 52 bytes and starts on a 16-byte boundary only every fourth time, so the one-lane forms move a point as two
+// runs of whole 128-bit words: words 0 .. 27 (X, Y and the first two limbs of T) and words 28 .. 51 (the rest of T, and Z).
+// Accepted forms of an operand:  all four coordinates N (what an addition leaves);  X normalised below 3p, Y normalised below 2p,
+// T: N, Z: C (what te29_from_row leaves for a one-entry segment);  the identity (0 : 1 : 0 : 1), Y = Z = the constant ONE.
+struct alignas(16) TE29Pt {
+    uint32_t w[52];
+};
+static_assert(sizeof(TE29Pt) == 208, "point stride");
+__device__ __forceinline__ void te29_pt_load_xy(const TE29Pt* p, Fq29& x, Fq29& y, uint32_t (&t01)[2]) {
+    uint32_t w[28];
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+        const uint4 v = reinterpret_cast<const uint4*>(p->w)[k];
+        w[4 * k] = v.x, w[4 * k + 1] = v.y, w[4 * k + 2] = v.z, w[4 * k + 3] = v.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 13; i++) x.l[i] = w[i], y.l[i] = w[13 + i];
+    t01[0] = w[26], t01[1] = w[27];
+}
+__device__ __forceinline__ void te29_pt_load_tz(const TE29Pt* p, const uint32_t (&t01)[2], Fq29& t, Fq29& z) {
+    uint32_t w[24];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        const uint4 v = reinterpret_cast<const uint4*>(p->w)[7 + k];
+        w[4 * k] = v.x, w[4 * k + 1] = v.y, w[4 * k + 2] = v.z, w[4 * k + 3] = v.w;
+    }
+    t.l[0] = t01[0], t.l[1] = t01[1];
+#pragma unroll
+    for (int i = 2; i < 13; i++) t.l[i] = w[i - 2];
+#pragma unroll
+    for (int i = 0; i < 13; i++) z.l[i] = w[11 + i];
+}
+__device__ __forceinline__ void te29_pt_store_xy(TE29Pt* p, const Fq29& x, const Fq29& y, uint32_t t0, uint32_t t1) {
+    uint32_t w[28];
+#pragma unroll
+    for (int i = 0; i < 13; i++) w[i] = x.l[i], w[13 + i] = y.l[i];
+    w[26] = t0, w[27] = t1;
+#pragma unroll
+    for (int k = 0; k < 7; k++) reinterpret_cast<uint4*>(p->w)[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+}
+__device__ __forceinline__ void te29_pt_store_tz(TE29Pt* p, const Fq29& t, const Fq29& z) {
+    uint32_t w[24];
+#pragma unroll
+    for (int i = 2; i < 13; i++) w[i - 2] = t.l[i];
+#pragma unroll
+    for (int i = 0; i < 13; i++) w[11 + i] = z.l[i];
+#pragma unroll
+    for (int k = 0; k < 6; k++) reinterpret_cast<uint4*>(p->w)[7 + k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+}
+// an accumulator at rest (msm_accumulate_te's, after any number of additions) as it is: the limbs are normalised already
+__device__ __forceinline__ void te29_pt_store(TE29Pt* p, const T29& a) {
+    te29_pt_store_xy(p, a.x, a.y, a.t.l[0], a.t.l[1]);
+    te29_pt_store_tz(p, a.t, a.z);
+}
+__device__ __forceinline__ T29 te29_pt_load(const TE29Pt* p) {
+    T29 r;
+    uint32_t t01[2];
+    te29_pt_load_xy(p, r.x, r.y, t01);
+    te29_pt_load_tz(p, t01, r.t, r.z);
+    return r;
+}
+__device__ __forceinline__ void te29_store_identity(TE29Pt* p) {
+    T29 r;
+#pragma unroll
+    for (int i = 0; i < 13; i++) r.x.l[i] = r.t.l[i] = 0, r.y.l[i] = r.z.l[i] = Fq29Consts::ONE[i];
+    te29_pt_store(p, r);
+}
+// one coordinate per lane of a quad: plain 32-bit accesses (a coordinate is not a run of whole 128-bit words)
+__device__ __forceinline__ Fq29 te29_pt_load_coord(const TE29Pt* p, unsigned c) {
+    Fq29 r;
+#pragma unroll
+    for (int i = 0; i < 13; i++) r.l[i] = p->w[13 * c + i];
+    return r;
+}
+__device__ __forceinline__ void te29_pt_store_coord(TE29Pt* p, unsigned c, const Fq29& v) {
+#pragma unroll
+    for (int i = 0; i < 13; i++) p->w[13 * c + i] = v.l[i];
+}
+__device__ __forceinline__ void te29_quad_store_identity(TE29Pt* p, unsigned q) {
+    Fq29 v;
+#pragma unroll
+    for (int i = 0; i < 13; i++) v.l[i] = (q & 1u) ? Fq29Consts::ONE[i] : 0u;
+    te29_pt_store_coord(p, q, v);
+}
+// First round of the general addition: A = (Y1 - X1)(Y2 - X2), B = (Y1 + X1)(Y2 + X2), C = 2d T1 T2 and Z1 Z2 (te29_efgh doubles it).
+// Bounds (limbs below the top one | value; tools/check_te29.py `tail` prints the columns):
+//   Y - X + 4p   raw: < 2^29 + SPREAD4_i <= 3 2^29 - 2 | < 6p      (SPREAD4: X may be te29_from_row's, below 3p)
+//   Y + X        raw: < 2^30                           | < 5p
+// Two raw differences multiply to 1.45 x 2^64 in the worst column and two raw sums to 1.05 x 2^64, so the FIRST operand's difference and
+// sum are carry-normalised (top limb then <= that of 6p resp. 5p): A at most 0.76 x 2^64, B 0.64 x 2^64.  T and Z are N: T1 T2,
+// Z1 Z2 and (T1 T2) 2d (the constant: C) at most 0.30 x 2^64.  All operands below 8p -> A, B, C and Z1 Z2: N, what te29_efgh takes with
+// D = 2 Z1 Z2 in the place of 2 Z1: its second-round products are bounded where it stands (a point that is ADDED: F G at most 0.85 x 2^64).
+// The same evaluation at build time (check_te29.py's column_bound: every a_i, b_i and m_i at its maximum, the carry rule's 2^29 - 1
+// included).
+constexpr bool te29_columns_fit(const uint32_t (&amax)[13], const uint32_t (&bmax)[13]) {
+    unsigned __int128 carry = 0;
+    for (int k = 0; k < 26; k++) {
+        unsigned __int128 acc = carry;
+        for (int i = (k > 12 ? k - 12 : 0); i <= (k < 12 ? k : 12); i++) acc += (uint64_t)amax[i] * bmax[k - i];
+        for (int i = (k > 12 ? k - 12 : 0); i < (k < 14 ? k : 14); i++) acc += (uint64_t)M29Q * Fq29Consts::P[k - i];
+        if (k < 14) acc += M29Q;
+        if (acc >= ((unsigned __int128)1 << 64) - (1u << 29)) return false;
+        carry = acc >> 29;
+    }
+    return true;
+}
+// The operand maxima are the tool's own: te29_bounds_gen.inc is written by `python tools/check_te29.py header` from its
+// tail_operands() and held to it by tests/test_te29_tail_bounds.py, so the build asserts what the tool prints.
+struct Te29Bound {
+    const char* name;
+    uint32_t a[13], b[13];
+};
+#include "te29_bounds_gen.inc"
+constexpr Te29Bound TE29_TAIL_BOUNDS[] = {SWM_TE29_TAIL_BOUNDS};
+constexpr bool te29_slot_add_bounds_ok() {
+    for (const Te29Bound& r : TE29_TAIL_BOUNDS)
+        if (!te29_columns_fit(r.a, r.b)) return false;
+    return sizeof(TE29_TAIL_BOUNDS) / sizeof(TE29_TAIL_BOUNDS[0]) == 10;  // nine products and the store's
+}
+static_assert(te29_slot_add_bounds_ok(), "te29_slot_add: a column of one of its nine products can reach 2^64 - 2^29");
+template <class M>
+__device__ __forceinline__ void te29_add_ab(Fq29& A, Fq29& B, const Fq29& ax, const Fq29& ay, const Fq29& qx, const Fq29& qy) {
+    A = M::mul(fq29_normalize(FQ29_SUB(ay, ax, SPREAD4)), FQ29_SUB(qy, qx, SPREAD4));
+    B = M::mul(fq29_normalize(fq29_add(ay, ax)), fq29_add(qy, qx));
+}
+// *dst = *pa + *pq: the unified 9-product law of te28_slot_add on points at rest, streamed as that one is — every load precedes the
+// first store, so dst may be pa or pq, and pa == pq is doubling.  The result has all four coordinates N.  Against the 28-bit step:
+// nine products of 404 instead of 447 instructions, no unpacking of eight coordinates or packing of four, four carry
+// normalisations (two here, two in te29_efgh) of 36 instructions each.
+template <class M = Mul29Asm>
+__device__ __forceinline__ void te29_slot_add(TE29Pt* dst, const TE29Pt* pa, const TE29Pt* pq) {
+    Fq29 A, B, C, ZZ;
+    {
+        uint32_t at01[2], qt01[2];
+        {
+            Fq29 ax, ay, qx, qy;
+            te29_pt_load_xy(pa, ax, ay, at01);
+            te29_pt_load_xy(pq, qx, qy, qt01);
+            te29_add_ab<M>(A, B, ax, ay, qx, qy);
+        }
+        Fq29 at, az, qt, qz;
+        te29_pt_load_tz(pa, at01, at, az);
+        te29_pt_load_tz(pq, qt01, qt, qz);
+        C = M::mul(M::mul(at, qt), fq29_const(Fq29Consts::K2D));
+        ZZ = M::mul(az, qz);
+    }
+    Fq29 E, F, G, H;
+    te29_efgh(E, F, G, H, A, B, C, ZZ, false);
+    const Fq29 T3 = M::mul(E, H);
+    te29_pt_store_xy(dst, M::mul(E, F), M::mul(G, H), T3.l[0], T3.l[1]);
+    te29_pt_store_tz(dst, T3, M::mul(F, G));
+}
+// te29_slot_add for steps in which a lane reads ANOTHER lane's slot that the same step rewrites (te28_slot_add_sync: the in-place
+// suffix scan of msm_bucket_reduce_low): every load of the workgroup precedes the barrier, every store follows it.  Same limbs.
+template <class M = Mul29Asm>
+__device__ __forceinline__ void te29_slot_add_sync(TE29Pt* dst, const TE29Pt* pa, const TE29Pt* pq, bool act, bool barrier = true) {
+    Fq29 E, F, G, H;
+#pragma unroll
+    for (int i = 0; i < 13; i++) E.l[i] = F.l[i] = G.l[i] = H.l[i] = 0;
+    if (act) {
+        Fq29 A, B, C, ZZ;
+        uint32_t at01[2], qt01[2];
+        {
+            Fq29 ax, ay, qx, qy;
+            te29_pt_load_xy(pa, ax, ay, at01);
+            te29_pt_load_xy(pq, qx, qy, qt01);
+            te29_add_ab<M>(A, B, ax, ay, qx, qy);
+        }
+        Fq29 at, az, qt, qz;
+        te29_pt_load_tz(pa, at01, at, az);
+        te29_pt_load_tz(pq, qt01, qt, qz);
+        C = M::mul(M::mul(at, qt), fq29_const(Fq29Consts::K2D));
+        ZZ = M::mul(az, qz);
+        te29_efgh(E, F, G, H, A, B, C, ZZ, false);
+    }
+    if (barrier) __syncthreads();  // (uniform over the workgroup; false for steps in which every lane works on slots of its own)
+    if (act) {
+        const Fq29 T3 = M::mul(E, H);
+        te29_pt_store_xy(dst, M::mul(E, F), M::mul(G, H), T3.l[0], T3.l[1]);
+        te29_pt_store_tz(dst, T3, M::mul(F, G));
+    }
+}
+// The same addition by a quad of lanes (te28_quad_add): three rounds of one product per lane — (A, B, T1 T2, Z1 Z2), then 2d (T1 T2)
+// on lane 2, then (X3, Y3, T3, Z3) — every lane storing one coordinate.  Every lane normalises its first operand: on lanes 2 and 3
+// that is a coordinate with normalised limbs already, which the carry chain leaves as it is.  Same formulas, same limbs as
+// te29_slot_add.  All lanes of the quad are handed the same pointers; one wave, lock step: the loads precede the stores.
+template <class M = Mul29Asm>
+__device__ __forceinline__ void te29_quad_add(TE29Pt* dst, const TE29Pt* pa, const TE29Pt* pq, unsigned q) {
+    const unsigned ia = q < 2 ? 1u : q;  // lanes 0, 1: Y and X; lane 2: T; lane 3: Z
+    const Fq29 a1 = te29_pt_load_coord(pa, ia), b1 = te29_pt_load_coord(pa, 0), a2 = te29_pt_load_coord(pq, ia), b2 = te29_pt_load_coord(pq, 0);
+    Fq29 u, v;
+#pragma unroll
+    for (int i = 0; i < 13; i++) {
+        const uint32_t sp = Fq29Consts::SPREAD4[i];
+        const uint32_t t1 = q == 0 ? sp - b1.l[i] : (q == 1 ? b1.l[i] : 0u), t2 = q == 0 ? sp - b2.l[i] : (q == 1 ? b2.l[i] : 0u);
+        u.l[i] = a1.l[i] + t1;
+        v.l[i] = a2.l[i] + t2;
+    }
+    Fq29 p1 = M::mul(fq29_normalize(u), v);
+    const Fq29 p2 = M::mul(p1, fq29_const(Fq29Consts::K2D));  // only lane 2 keeps it: C = 2d T1 T2
+#pragma unroll
+    for (int i = 0; i < 13; i++) p1.l[i] = q == 2 ? p2.l[i] : p1.l[i];
+    const Fq29 A = te29_quad_get<0>(p1), B = te29_quad_get<1>(p1), C = te29_quad_get<2>(p1), ZZ = te29_quad_get<3>(p1);
+    Fq29 E, F, G, H, l, r;  // lane 0: E F, lane 1: G H, lane 2: E H, lane 3: F G
+    te29_efgh(E, F, G, H, A, B, C, ZZ, false);
+#pragma unroll
+    for (int i = 0; i < 13; i++) {
+        l.l[i] = q == 1 ? G.l[i] : (q == 3 ? F.l[i] : E.l[i]);
+        r.l[i] = q == 0 ? F.l[i] : (q == 3 ? G.l[i] : H.l[i]);
+    }
+    te29_pt_store_coord(dst, q, M::mul(l, r));  // X3, Y3, T3, Z3
+}
+// value below p (1 + 2^-23) with normalised limbs -> below p
+__device__ __forceinline__ Fq29 fq29_canonical(const Fq29& a) {
+    Fq29 d;
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 13; i++) {
+        const uint32_t t = a.l[i] - Fq29Consts::P[i] - borrow;  // |a_i - p_i - borrow| < 2^30: bit 31 is the sign
+        d.l[i] = t & M29Q;
+        borrow = t >> 31;
+    }
+    Fq29 r;
+#pragma unroll
+    for (int i = 0; i < 13; i++) r.l[i] = borrow ? a.l[i] : d.l[i];
+    return r;
+}
+// 29-bit domain (x 2^406) -> radix 2^384, canonical, packed: what te28_store_384 gives for the same point (the host folds in that
+// form).  One product per coordinate by 2^384 mod p; operand: a coordinate at rest (below 3p, normalised limbs), column at most
+// 0.33 x 2^64, result N.
+__device__ __forceinline__ void te29_store_384(G1XYZZ& m, const TE29Pt& slot) {
+    const T29 p = te29_pt_load(&slot);
+    const Fq29 k = fq29_const(Fq29Consts::TO384);
+    m.x = fq29_pack(fq29_canonical(fq29_mul(p.x, k)));
+    m.y = fq29_pack(fq29_canonical(fq29_mul(p.y, k)));
+    m.zz = fq29_pack(fq29_canonical(fq29_mul(p.t, k)));
+    m.zzz = fq29_pack(fq29_canonical(fq29_mul(p.z, k)));
 }
 
 }  // namespace swm

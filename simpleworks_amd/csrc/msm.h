@@ -132,7 +132,8 @@ struct MsmJob {
     bool needs_acc_wait = false;
     hipStream_t stream = nullptr;
     hipEvent_t acc_done = nullptr;
-    G1XYZZ *d_partial = nullptr, *d_acc = nullptr;
+    bool raw = false;  // d_partial and d_acc hold raw points of the 29-bit domain (fq29.cuh TE29Pt, 208 B), not 28-bit slots
+    void *d_partial = nullptr, *d_acc = nullptr;
     const uint32_t *d_seg_off = nullptr, *d_hist = nullptr, *d_status = nullptr, *d_entries = nullptr;
     uint32_t seg = 0;  // segment bound of the accumulation: bucket b owns the partial sums d_seg_off[b] .. + ceil(d_hist[b] / seg)
     G1XYZZ* host = nullptr;  // pinned slot receiving nwin * red_blocks (A, R) pairs

@@ -1218,25 +1218,31 @@ __global__ void __launch_bounds__(256, 3) msm_accumulate(const G1Affine* __restr
 // coordinate as the thirteen 29-bit limbs the multiplier takes (fq29.cuh), in a 64-byte sector of its own (192 B per row, consumed
 // as loaded); the accumulator is an extended point and every addition is the UNIFIED 7-product law of te29_madd_row — no doubling /
 // cancellation test, no cold path: 2 359 of its instructions are multiply-adds (7 x 337; on fourteen 28-bit limbs, r04: 3 223 VALU
-// instructions of which 2 646 multiply-adds, SQ pass profiles/r04_pmc_sq_msm_accumulate.json; XYZZ: 4 817), no scratch.  The epilogue
-// takes each coordinate into the 28-bit domain of the bucket stage (te29_to_slot: four products per segment).  Rows go HBM -> registers,
-// not through LDS: the kernel is issue-bound, a row is read once by one lane.  It is the one kernel of a
-// proof WITHOUT an issue priority (ff.cuh SWM_LIGHT_KERNEL): the filler everything else runs beside.  Partial sums leave as
-// extended points (X, Y, T, Z in the four slots of a G1XYZZ).  Algorithmic bytes per point: 96 B base + 32 B scalar.
+// instructions of which 2 646 multiply-adds, SQ pass profiles/r04_pmc_sq_msm_accumulate.json; XYZZ: 4 817), no scratch.  Rows go
+// HBM -> registers, not through LDS: the kernel is issue-bound, a row is read once by one lane.  It is the
+// one kernel of a proof WITHOUT an issue priority (ff.cuh SWM_LIGHT_KERNEL): the filler everything else runs beside.  Algorithmic
+// bytes per point: 96 B base + 32 B scalar.  Partial sums leave as extended points in the form of the job's bucket stage
+// (MsmShape::raw).  RAW: the accumulator as it stands, a TE29Pt of thirteen 128-bit words, no arithmetic — the one-lane stages add
+// in the same domain.  Otherwise (a quad stage) X, Y, T, Z in the four slots of a G1XYZZ, each coordinate taken into the 28-bit
+// domain by te29_to_slot: four products per segment.
+template <bool RAW>
 __global__ void __launch_bounds__(256, SWM_TE_EARLY_LOADS ? 3 : 4) msm_accumulate_te(const G1TE* __restrict__ rows,
                                                            const uint32_t* __restrict__ sorted,
                                                            const uint32_t* __restrict__ seg_start,
                                                            const uint32_t* __restrict__ seg_len,
                                                            const uint32_t* __restrict__ order,
                                                            const uint32_t* __restrict__ nseg_ptr,
-                                                           G1XYZZ* __restrict__ partial) {
+                                                           void* __restrict__ partial_) {
+    G1XYZZ* __restrict__ partial = reinterpret_cast<G1XYZZ*>(partial_);
+    TE29Pt* __restrict__ partial29 = reinterpret_cast<TE29Pt*>(partial_);
     const uint32_t nseg_total = *nseg_ptr;
     for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < nseg_total; t += gridDim.x * blockDim.x) {
         const uint32_t seg = order[t];
         // entries of the segment: sorted[k0 + j * stride], j < len (stride 1 unless the bucket's segments interleave)
         const uint32_t k0 = seg_start[seg], sl = seg_len[seg], len = sl & 0xffu, stride = max(1u, sl >> 8);
         if (len == 0) {
-            te28_store_identity(partial[seg]);
+            if constexpr (RAW) te29_store_identity(&partial29[seg]);
+            else te28_store_identity(partial[seg]);
             continue;
         }
         T29 acc;
@@ -1253,28 +1259,36 @@ __global__ void __launch_bounds__(256, SWM_TE_EARLY_LOADS ? 3 : 4) msm_accumulat
             te29_madd_row(acc, rows + (ent & 0x7fffffffu), (ent >> 31) != 0);
             ent = next;
         }
-        partial[seg].x = te29_to_slot(acc.x);
-        partial[seg].y = te29_to_slot(acc.y);
-        partial[seg].zz = te29_to_slot(acc.t);
-        partial[seg].zzz = te29_to_slot(acc.z);
+        if constexpr (RAW) {
+            te29_pt_store(&partial29[seg], acc);
+        } else {
+            partial[seg].x = te29_to_slot(acc.x);
+            partial[seg].y = te29_to_slot(acc.y);
+            partial[seg].zz = te29_to_slot(acc.t);
+            partial[seg].zzz = te29_to_slot(acc.z);
+        }
     }
 }
 
 // The accumulation of SMALL MSMs (low-latency schedule, r04): four lanes per segment, the accumulator one coordinate per lane
 // (te29_quad_madd_row): the chain of a segment of 8 entries is 16 products long instead of 50, on a chip that such a job
 // cannot fill anyway.  Same partial sums, bit for bit.
+template <bool RAW>
 __global__ void __launch_bounds__(256) msm_accumulate_te_quad(const G1TE* __restrict__ rows, const uint32_t* __restrict__ sorted,
                                                               const uint32_t* __restrict__ seg_start,
                                                               const uint32_t* __restrict__ seg_len,
                                                               const uint32_t* __restrict__ order,
-                                                              const uint32_t* __restrict__ nseg_ptr, G1XYZZ* __restrict__ partial) {
+                                                              const uint32_t* __restrict__ nseg_ptr, void* __restrict__ partial_) {
+    G1XYZZ* __restrict__ partial = reinterpret_cast<G1XYZZ*>(partial_);
+    TE29Pt* __restrict__ partial29 = reinterpret_cast<TE29Pt*>(partial_);
     const uint32_t nseg_total = *nseg_ptr;
     const unsigned q = threadIdx.x & 3u;
     for (uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 2; t < nseg_total; t += (gridDim.x * blockDim.x) >> 2) {
         const uint32_t seg = order[t];
         const uint32_t k0 = seg_start[seg], sl = seg_len[seg], len = sl & 0xffu, stride = max(1u, sl >> 8);
         if (len == 0) {
-            te28_quad_store_identity(&partial[seg], q);
+            if constexpr (RAW) te29_quad_store_identity(&partial29[seg], q);
+            else te28_quad_store_identity(&partial[seg], q);
             continue;
         }
         uint32_t ent = sorted[k0];
@@ -1285,11 +1299,14 @@ __global__ void __launch_bounds__(256) msm_accumulate_te_quad(const G1TE* __rest
             te29_quad_madd_row(own, rows + (ent & 0x7fffffffu), (ent >> 31) != 0, q);
             ent = next;
         }
-        reinterpret_cast<Fq*>(&partial[seg])[q] = te29_to_slot(own);  // X, Y, T (slot zz), Z (slot zzz)
+        if constexpr (RAW) te29_pt_store_coord(&partial29[seg], q, own);
+        else reinterpret_cast<Fq*>(&partial[seg])[q] = te29_to_slot(own);  // X, Y, T (slot zz), Z (slot zzz)
     }
 }
 
-// ---------------------------------------------------------------------------------------------- bucket stage (28-bit domain)
+// ---------------------------------------------------------------------------------------------- bucket stage
+// (XYZZ and the quad twisted Edwards form add in the 28-bit domain, fq28.cuh; the one-lane twisted Edwards stages in the 29-bit
+// domain of the accumulation, fq29.cuh "the general addition": FormTE29 below)
 // Register budget of the bucket stage: a general addition keeps two points (2 x 56 VGPRs) plus ~8 temporaries
 // (112 VGPRs) live; a third live point spills to scratch, i.e. to HBM-backed private memory with nothing to hide the
 // latency at one wave per SIMD (measured: 5x slower).  So each lane parks the point it is not currently adding in LDS
@@ -1406,8 +1423,16 @@ static_assert(sizeof(RedSlot) == 208, "slot stride");
 struct alignas(16) PlainSlot {
     G1XYZZ p;
 };
+// ... and of the 29-bit twisted Edwards form: the unpacked point IS 208 bytes (fq29.cuh TE29Pt), same stride, same banks.
+struct alignas(16) Red29Slot {
+    TE29Pt p;
+};
+static_assert(sizeof(Red29Slot) == sizeof(RedSlot), "slot stride");
+// Pt: a point at rest (partial sum, LDS slot); quad_add: the four-lane step of a QUAD_TREE form; slot_add_sync: msm_bucket_reduce_low's.
+// A job's partial sums are G1XYZZ slots of the 28-bit domain for the XYZZ and the quad forms, raw TE29Pt for FormTE29 (MsmShape::raw).
 struct FormXYZZ {
     using Slot = RedSlot;
+    using Pt = G1XYZZ;
     static constexpr int LANES = 1;
     static constexpr bool QUAD_TREE = false;
     static __device__ __forceinline__ void slot_add(G1XYZZ* dst, const G1XYZZ* pa, const G1XYZZ* pq, unsigned = 0) { p28_slot_add(dst, pa, pq); }
@@ -1416,20 +1441,27 @@ struct FormXYZZ {
     static __device__ __forceinline__ void store_identity(G1XYZZ& m, unsigned = 0) { p28_store(m, p28_identity()); }
     static __device__ __forceinline__ void store_384(G1XYZZ& m, const G1XYZZ& slot) { p28_store_384(m, p28_load(slot)); }
 };
-struct FormTE {
-    using Slot = RedSlot;
+// The one-lane twisted Edwards stage: thirteen 29-bit limbs, slots and partial sums unpacked (fq29.cuh, "the general addition").
+struct FormTE29 {
+    using Slot = Red29Slot;
+    using Pt = TE29Pt;
     static constexpr int LANES = 1;
-    static constexpr bool QUAD_TREE = true;  // the narrow steps of the final tree switch to four lanes per sum
-    static __device__ __forceinline__ void slot_add(G1XYZZ* dst, const G1XYZZ* pa, const G1XYZZ* pq, unsigned = 0) { te28_slot_add(dst, pa, pq); }
-    static __device__ __forceinline__ void slot_dbl(G1XYZZ* dst, const G1XYZZ* pa, unsigned = 0) { te28_slot_add(dst, pa, pa); }  // unified law
-    static __device__ __forceinline__ void copy(G1XYZZ* dst, const G1XYZZ* src, unsigned = 0) { *dst = *src; }
-    static __device__ __forceinline__ void store_identity(G1XYZZ& m, unsigned = 0) { te28_store_identity(m); }
-    static __device__ __forceinline__ void store_384(G1XYZZ& m, const G1XYZZ& slot) { te28_store_384(m, slot); }
+    static constexpr bool QUAD_TREE = true;
+    static __device__ __forceinline__ void slot_add(TE29Pt* dst, const TE29Pt* pa, const TE29Pt* pq, unsigned = 0) { te29_slot_add(dst, pa, pq); }
+    static __device__ __forceinline__ void slot_add_sync(TE29Pt* dst, const TE29Pt* pa, const TE29Pt* pq, bool act, bool barrier) {
+        te29_slot_add_sync(dst, pa, pq, act, barrier);
+    }
+    static __device__ __forceinline__ void quad_add(TE29Pt* dst, const TE29Pt* pa, const TE29Pt* pq, unsigned q) { te29_quad_add(dst, pa, pq, q); }
+    static __device__ __forceinline__ void slot_dbl(TE29Pt* dst, const TE29Pt* pa, unsigned = 0) { te29_slot_add(dst, pa, pa); }
+    static __device__ __forceinline__ void copy(TE29Pt* dst, const TE29Pt* src, unsigned = 0) { *dst = *src; }
+    static __device__ __forceinline__ void store_identity(TE29Pt& m, unsigned = 0) { te29_store_identity(&m); }
+    static __device__ __forceinline__ void store_384(G1XYZZ& m, const TE29Pt& slot) { te29_store_384(m, slot); }
 };
 // Twisted Edwards with every chain worked by a quad of lanes (te28_quad_add: three products per lane and step instead of
 // nine): the bucket stage of SMALL MSMs, where the chain's latency is all there is.
 struct FormTEQuad {
     using Slot = PlainSlot;
+    using Pt = G1XYZZ;
     static constexpr int LANES = 4;
     static constexpr bool QUAD_TREE = false;
     static __device__ __forceinline__ void slot_add(G1XYZZ* dst, const G1XYZZ* pa, const G1XYZZ* pq, unsigned q) { te28_quad_add(dst, pa, pq, q); }
@@ -1439,17 +1471,26 @@ struct FormTEQuad {
     static __device__ __forceinline__ void store_384(G1XYZZ& m, const G1XYZZ& slot) { te28_store_384(m, slot); }
 };
 
+// What msm_big_bucket_sum runs ahead of a QUAD stage: that job's partial sums are 28-bit slots, folded one lane per sum.
+struct FormTEFold28 {
+    using Pt = G1XYZZ;
+    static __device__ __forceinline__ void slot_add(G1XYZZ* dst, const G1XYZZ* pa, const G1XYZZ* pq) { te28_slot_add(dst, pa, pq); }
+    static __device__ __forceinline__ void store_identity(G1XYZZ& m) { te28_store_identity(m); }
+};
+
 // Oversized buckets (> BIG_NSEG segments: structured scalars) are folded first, one workgroup each: strided partial
 // sums + LDS tree; the result replaces the bucket's first partial.
 template <class Form>
-__global__ void __launch_bounds__(RED_BLOCK) msm_big_bucket_sum(G1XYZZ* __restrict__ partial,
+__global__ void __launch_bounds__(RED_BLOCK) msm_big_bucket_sum(void* __restrict__ partial_,
                                                                 const uint32_t* __restrict__ seg_off,
                                                                 const uint32_t* __restrict__ hist, uint32_t SEG,
                                                                 const uint32_t* __restrict__ big_count,
                                                                 const uint32_t* __restrict__ big_list, unsigned log_g) {
     SWM_TAIL_KERNEL();
+    using Pt = typename Form::Pt;
+    Pt* __restrict__ partial = reinterpret_cast<Pt*>(partial_);  // the job's partial sums in the form's point (MsmShape::raw)
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    G1XYZZ* sm = reinterpret_cast<G1XYZZ*>(smem_raw);
+    Pt* sm = reinterpret_cast<Pt*>(smem_raw);
     const uint32_t nbig = *big_count;
     // 2^log_g lanes per listed bucket (a whole workgroup for the oversized buckets of structured scalars; 4 .. 64 lanes
     // in the low-latency schedule of small MSMs, where EVERY bucket with more than two segments is folded here)
@@ -1497,11 +1538,11 @@ __global__ void __launch_bounds__(RED_BLOCK) msm_big_bucket_sum(G1XYZZ* __restri
 // jobs of a round share one chain latency instead of paying it one after the other.
 static constexpr int TAIL_MAX = 4;
 struct TailJob {
-    const G1XYZZ* partial;
+    const void* partial;  // points of the launch's form (Form::Pt): 28-bit slots, or raw 29-bit points when the job is MsmJob::raw
     const uint32_t *seg_off, *hist;  // first segment and entry count of every bucket: its segments are seg_off[b] .. + ceil(hist[b] / seg)
     uint32_t seg;
     G1XYZZ* out;
-    G1XYZZ* acc;  // msm_bucket_reduce_low: the weighted sums of the lanes, one slot per lane in HBM / L2 (red_blocks x RB per window)
+    void* acc;  // msm_bucket_reduce_low: the weighted sums of the lanes, one slot per lane in HBM / L2 (red_blocks x RB per window)
     unsigned log_m, red_blocks, big_nseg;
     unsigned blk_lo, blk_hi, blk_low;   // workgroups of this rank's bucket share (MsmJob); the others only emit the identity
     const uint32_t *status, *entries;  // device status words of the job, forwarded to ...
@@ -1516,9 +1557,10 @@ template <int RB, class Form>
 __global__ void __launch_bounds__(RB * Form::LANES) msm_bucket_reduce(TailBatch batch) {
     SWM_TAIL_KERNEL();
     using Slot = typename Form::Slot;
+    using Pt = typename Form::Pt;
     const TailJob& job = batch.j[blockIdx.z];
     if (blockIdx.x >= job.red_blocks || blockIdx.y >= job.L.nwin) return;
-    const G1XYZZ* __restrict__ partial = job.partial;
+    const Pt* __restrict__ partial = reinterpret_cast<const Pt*>(job.partial);
     const uint32_t* __restrict__ seg_off = job.seg_off;
     const WinLayout& L = job.L;
     const unsigned log_m = job.log_m;
@@ -1571,9 +1613,9 @@ __global__ void __launch_bounds__(RB * Form::LANES) msm_bucket_reduce(TailBatch 
 #pragma unroll 1
     for (;;) {
         // one micro-operation per iteration: *dst = *pa + *pq (act), or *dst = *pa (copy: inactive lane of a scan step)
-        G1XYZZ* dst = &sm_run[t].p;
-        const G1XYZZ* pa = &sm_run[t].p;
-        const G1XYZZ* pq = &sm_run[t].p;
+        Pt* dst = &sm_run[t].p;
+        const Pt* pa = &sm_run[t].p;
+        const Pt* pq = &sm_run[t].p;
         bool act = false, copy = false;
         if (phase == WALK) {
             // (r06) the walk has no meeting point but its end: a lane works on slots of its own, so every WAVE walks at its own
@@ -1632,10 +1674,10 @@ __global__ void __launch_bounds__(RB * Form::LANES) msm_bucket_reduce(TailBatch 
         } else {
             if (d == 0) break;
             if constexpr (Form::QUAD_TREE) {
-                // a tree step with at most RB / 4 sums left: four lanes per sum (te28_quad_add), a third of the step's latency
+                // a tree step with at most RB / 4 sums left: four lanes per sum (te29_quad_add), a third of the step's latency
                 if (d <= RB / 4) {
                     const uint32_t c = threadIdx.x >> 2;
-                    if (c < d) te28_quad_add(&sm_acc[c].p, &sm_acc[c].p, &sm_acc[c + d].p, threadIdx.x & 3u);
+                    if (c < d) Form::quad_add(&sm_acc[c].p, &sm_acc[c].p, &sm_acc[c + d].p, threadIdx.x & 3u);
                     __syncthreads();
                     d >>= 1;
                     continue;
@@ -1675,11 +1717,11 @@ __global__ void __launch_bounds__(RB * Form::LANES) msm_bucket_reduce(TailBatch 
 // ONE workgroup per CU and one wave per SIMD, where a lone wave issues an instruction every ~5.5 cycles (SQ utilisation 0.62,
 // profiles/r04_pmc_sq_msm_bucket_reduce_and_sort.json) and nothing else that wants LDS fits beside it.  Here
 //   * the running sum is ONE slot per lane: the suffix scan works in place, every lane's loads ahead of a barrier and its
-//     stores behind it (te28_slot_add_sync) — the unified law reads all eight input coordinates before it writes any;
+//     stores behind it (te29_slot_add_sync) — the unified law reads all eight input coordinates before it writes any;
 //   * the weighted sum of a lane lives in HBM / L2 (job.acc: touched once per bucket, 384 B per step against ~4 400
 //     instructions) and moves into the lane's LDS slot with the step that folds the suffix into it; the tree runs there;
-// (256 + 1) x 192 B = 49 KB per workgroup, 171 VGPRs: two workgroups per CU by registers (three: 35 spills, slower), and a stage
-// no longer owns its CU.  Same micro-operations in the same order per lane as msm_bucket_reduce<RB, FormTE>: the same limbs, the
+// (256 + 1) x 208 B = 53 KB per workgroup, 164 VGPRs: two workgroups per CU by registers (three: 35 spills, slower), and a stage
+// no longer owns its CU.  Same micro-operations in the same order per lane as msm_bucket_reduce<RB, FormTE29>: the same limbs, the
 // same workgroup results.
 // Where it is used (measured, CHANGELOG r05): in the JOINT stage of a round's deferred jobs (up to 10^6 points each), one
 // workgroup per CU — 0.1 - 0.3 ms per mid-size proof; NOT for the thin stages that run beside the accumulations of large jobs
@@ -1692,21 +1734,24 @@ __global__ void __launch_bounds__(RB, SWM_LOW_WAVES) msm_bucket_reduce_low(TailB
     SWM_TAIL_KERNEL();
     const TailJob& job = batch.j[blockIdx.z];
     if (blockIdx.x >= job.red_blocks || blockIdx.y >= job.L.nwin) return;
-    const G1XYZZ* __restrict__ partial = job.partial;
+    using Form = FormTE29;  // (one-lane twisted Edwards jobs only: raw partial sums, 29-bit slots)
+    using Slot = Form::Slot;
+    using Pt = Form::Pt;
+    const Pt* __restrict__ partial = reinterpret_cast<const Pt*>(job.partial);
     const uint32_t* __restrict__ seg_off = job.seg_off;
     const WinLayout& L = job.L;
     const unsigned log_m = job.log_m;
     G1XYZZ* __restrict__ out = job.out;
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    RedSlot* sm_run = reinterpret_cast<RedSlot*>(smem_raw);  // RB + 1 padded slots (RedSlot: no bank conflicts)
-    RedSlot* sm_tree = sm_run + 1;
+    Slot* sm_run = reinterpret_cast<Slot*>(smem_raw);  // RB + 1 slots of 208 B (Red29Slot: no bank conflicts)
+    Slot* sm_tree = sm_run + 1;
     const uint32_t w = blockIdx.y, t = threadIdx.x;
     if (!((blockIdx.x >= job.blk_lo && blockIdx.x < job.blk_hi) || blockIdx.x < job.blk_low)) {
         if (t == 0) {
-            te28_store_identity(sm_run[0].p);
+            Form::store_identity(sm_run[0].p);
             size_t o = ((size_t)w * job.red_blocks + blockIdx.x) * 2;
-            te28_store_384(out[o], sm_run[0].p);
-            te28_store_384(out[o + 1], sm_run[0].p);
+            Form::store_384(out[o], sm_run[0].p);
+            Form::store_384(out[o + 1], sm_run[0].p);
             if (blockIdx.x == 0 && w == 0 && job.host_flags) {
                 job.host_flags[0] = job.status[0];
                 job.host_flags[1] = *job.entries;
@@ -1715,13 +1760,13 @@ __global__ void __launch_bounds__(RB, SWM_LOW_WAVES) msm_bucket_reduce_low(TailB
         }
         return;
     }
-    G1XYZZ* __restrict__ my_acc = job.acc + ((size_t)w * job.red_blocks + blockIdx.x) * RB + t;
+    Pt* __restrict__ my_acc = reinterpret_cast<Pt*>(job.acc) + ((size_t)w * job.red_blocks + blockIdx.x) * RB + t;
     const uint32_t B = 1u << (L.c[w] - 1), m = 1u << log_m;
     const uint32_t lo = (blockIdx.x * RB + t) << log_m;
     const uint32_t base = L.boff[w];
-    te28_store_identity(sm_run[t].p);
-    if (t == 0) te28_store_identity(sm_run[RB].p);
-    te28_store_identity(*my_acc);
+    Form::store_identity(sm_run[t].p);
+    if (t == 0) Form::store_identity(sm_run[RB].p);
+    Form::store_identity(*my_acc);
     uint32_t b = min(lo + m, B), s = 0, e = 0;
     bool walking = lo < B;
     if (walking) {
@@ -1736,9 +1781,9 @@ __global__ void __launch_bounds__(RB, SWM_LOW_WAVES) msm_bucket_reduce_low(TailB
     __syncthreads();
 #pragma unroll 1
     for (;;) {
-        G1XYZZ* dst = &sm_run[t].p;
-        const G1XYZZ* pa = &sm_run[t].p;
-        const G1XYZZ* pq = &sm_run[t].p;
+        Pt* dst = &sm_run[t].p;
+        const Pt* pa = &sm_run[t].p;
+        const Pt* pq = &sm_run[t].p;
         bool act = false;
         if (phase == WALK) {
             // (r06) the walk has no meeting point but its end: a lane works on slots of its own, so every WAVE walks at its own
@@ -1776,7 +1821,7 @@ __global__ void __launch_bounds__(RB, SWM_LOW_WAVES) msm_bucket_reduce_low(TailB
             d <<= 1;
         } else if (phase == SHIFT) {  // slot_t <- m Suffix_t for t >= 1, in place; slot 0 keeps R_blk = Suffix_0 (m Suffix_0 is never needed)
 #pragma unroll 1
-            for (unsigned i = 0; i < log_m; i++) te28_slot_add_sync(&sm_run[t].p, &sm_run[t].p, &sm_run[t].p, t >= 1, false);
+            for (unsigned i = 0; i < log_m; i++) Form::slot_add_sync(&sm_run[t].p, &sm_run[t].p, &sm_run[t].p, t >= 1, false);
             __syncthreads();  // the fold reads the NEIGHBOUR's doubled slot
             phase = FOLD;
             continue;
@@ -1791,9 +1836,9 @@ __global__ void __launch_bounds__(RB, SWM_LOW_WAVES) msm_bucket_reduce_low(TailB
             d = RB / 2;
         } else {  // tree over the slots 1 .. RB
             if (d == 0) break;
-            if (d <= RB / 4) {  // narrow tree steps: four lanes per sum (te28_quad_add)
+            if (d <= RB / 4) {  // narrow tree steps: four lanes per sum (te29_quad_add)
                 const uint32_t c = threadIdx.x >> 2;
-                if (c < d) te28_quad_add(&sm_tree[c].p, &sm_tree[c].p, &sm_tree[c + d].p, threadIdx.x & 3u);
+                if (c < d) Form::quad_add(&sm_tree[c].p, &sm_tree[c].p, &sm_tree[c + d].p, threadIdx.x & 3u);
                 __syncthreads();
                 d >>= 1;
                 continue;
@@ -1808,13 +1853,13 @@ __global__ void __launch_bounds__(RB, SWM_LOW_WAVES) msm_bucket_reduce_low(TailB
         // other lanes in the NEXT step (trailing barrier); a walk step touches the lane's own slots only (the vote at the top
         // of the loop is the workgroup's only meeting point there)
         const bool walk = phase == WALK;
-        te28_slot_add_sync(dst, pa, pq, act, phase == SCAN);
+        Form::slot_add_sync(dst, pa, pq, act, phase == SCAN);
         if (!walk) __syncthreads();
     }
     if (threadIdx.x == 0) {
         size_t o = ((size_t)w * job.red_blocks + blockIdx.x) * 2;
-        te28_store_384(out[o], sm_tree[0].p);
-        te28_store_384(out[o + 1], sm_run[0].p);
+        Form::store_384(out[o], sm_tree[0].p);
+        Form::store_384(out[o + 1], sm_run[0].p);
         if (blockIdx.x == 0 && w == 0 && job.host_flags) {
             job.host_flags[0] = job.status[0];
             job.host_flags[1] = *job.entries;
@@ -2065,7 +2110,7 @@ static constexpr size_t SLOT_FLAGS_OFF = SLOT_BYTES - 16;
 
 // ---- shape: every decision about one MSM, made by msm_shape (which says what each field is); the bucket-stage fields are MsmJob's.
 struct MsmShape {
-    bool flat, te, lat, quad, low, quad_acc, one_stream, two_level;
+    bool flat, te, lat, quad, low, quad_acc, one_stream, two_level, raw;
     int lane;
     WinLayout pl, rl;
     size_t total, wpart_n, nseg_max;
@@ -2132,6 +2177,10 @@ static int msm_shape(swm_ctx* ctx, size_t n, const MsmTable& tab, int lane, bool
     // low-LDS kernel 128 per job (two workgroups per CU) measured SLOWER per launch: 1.43 against 1.06 ms for four 2^19-bucket jobs.
     static constexpr unsigned joint_blocks = 64u;
     s.low = s.te && !s.quad && s.rb == 256 && low_on;
+    // Form of the job's partial sums: raw points of the 29-bit domain (TE29Pt, 208 B) when its bucket stage is a one-lane twisted
+    // Edwards one (msm_bucket_reduce<256, FormTE29> or msm_bucket_reduce_low, whichever a later re-shaping picks); the 28-bit slots
+    // of the accumulation's epilogue for a quad stage (FormTEQuad), and XYZZ points otherwise.
+    s.raw = s.te && !s.quad;
     // (low-latency schedule: the bucket stages of a round's four MSMs run in one launch and have to be resident together)
     const unsigned max_blocks = s.quad ? quad_blocks : (s.flat ? (defer_tail ? joint_blocks : (s.low ? low_blocks : 256u)) : 16u);
     s.max_blocks = s.low ? std::max(max_blocks, low_blocks) : std::max(max_blocks, 256u);
@@ -2326,7 +2375,8 @@ struct MsmBuffers {
     uint32_t *flat_cnt, *flat_win_off, *flat_cur, *flat_off, *flat_seg_off;
     uint32_t *seg_start, *seg_len, *order, *bucket_off, *seg_off, *digits, *sorted, *tot_cnt, *tot_seg, *big_list;
     uint2* pairs;
-    G1XYZZ *partial, *acc;  // partial[nseg_max] (then room for wpart_n points); the low-LDS bucket stage's sums, one point per lane
+    // partial[nseg_max] (then room for wpart_n points); the low-LDS bucket stage's sums, one point per lane — G1XYZZ, or TE29Pt (MsmShape::raw)
+    void *partial, *acc;
 };
 // follow: the segment descriptors are the twin pair's own ("msmT.segs"), not the lane's
 static int msm_buffers(swm_ctx* ctx, const MsmShape& s, const MsmZeroLayout& z, int slot, bool follow, MsmBuffers* out) {
@@ -2355,8 +2405,9 @@ static int msm_buffers(swm_ctx* ctx, const MsmShape& s, const MsmZeroLayout& z, 
     SWM_TRY(msm_buffer(ctx, BUF_SCAN_TOT, slot, s.lane, (size_t)(s.scan_tiles + 1) * 8, (void**)&b.tot_cnt));
     b.tot_seg = b.tot_cnt + s.scan_tiles + 1;
     SWM_TRY(msm_buffer(ctx, BUF_BIG_LIST, slot, s.lane, (size_t)s.pl.NB * 4, (void**)&b.big_list));
-    SWM_TRY(msm_buffer(ctx, BUF_POINTS, slot, s.lane, (s.nseg_max + s.wpart_n) * sizeof(G1XYZZ), (void**)&b.partial));
-    if (s.low) SWM_TRY(msm_buffer(ctx, BUF_ACC, slot, s.lane, (size_t)s.rl.nwin * s.max_blocks * 256 * sizeof(G1XYZZ), (void**)&b.acc));
+    const size_t pt = s.raw ? sizeof(TE29Pt) : sizeof(G1XYZZ);  // stride of the job's points at rest (208 B raw, 192 B slots)
+    SWM_TRY(msm_buffer(ctx, BUF_POINTS, slot, s.lane, (s.nseg_max + s.wpart_n) * pt, &b.partial));
+    if (s.low) SWM_TRY(msm_buffer(ctx, BUF_ACC, slot, s.lane, (size_t)s.rl.nwin * s.max_blocks * 256 * pt, &b.acc));
     return SWM_OK;
 }
 
@@ -2579,19 +2630,23 @@ static int msm_accumulate_stage(swm_ctx* ctx, const MsmShape& s, const MsmBuffer
     unsigned acc_grid = (unsigned)((s.nseg_max + 255) / 256);
     const dim3 big_grid(std::min<unsigned>((s.pl.NB + (RED_BLOCK >> s.log_g) - 1) / (RED_BLOCK >> s.log_g), s.lat ? 2048 : 512));
     if (s.te) {
+        // (either kernel can feed either tail: the epilogue follows the form of the job's partial sums, not the kernel)
         if (s.quad_acc)
-            SWM_LAUNCH(ctx, "msm_accumulate", msm_accumulate_te_quad, dim3((unsigned)((s.nseg_max + 63) / 64)), dim3(256), 0, tab.te,
-                       b.sorted, b.seg_start, b.seg_len, b.order, nseg_live, b.partial);
+            SWM_LAUNCH(ctx, "msm_accumulate", s.raw ? msm_accumulate_te_quad<true> : msm_accumulate_te_quad<false>,
+                       dim3((unsigned)((s.nseg_max + 63) / 64)), dim3(256), 0, tab.te, b.sorted, b.seg_start, b.seg_len, b.order, nseg_live,
+                       b.partial);
         else
-            SWM_LAUNCH(ctx, "msm_accumulate", msm_accumulate_te, dim3(acc_grid), dim3(256), 0, tab.te, b.sorted, b.seg_start, b.seg_len,
-                       b.order, nseg_live, b.partial);
+            SWM_LAUNCH(ctx, "msm_accumulate", s.raw ? msm_accumulate_te<true> : msm_accumulate_te<false>, dim3(acc_grid), dim3(256), 0,
+                       tab.te, b.sorted, b.seg_start, b.seg_len, b.order, nseg_live, b.partial);
     } else {
         SWM_LAUNCH(ctx, "msm_accumulate", msm_accumulate, dim3(acc_grid), dim3(256), 0,
                    s.flat ? (const G1Affine*)nullptr : d_bases, s.flat ? tab.t28 : d_bases28, b.sorted, b.seg_start, b.seg_len, b.order,
-                   nseg_live, b.partial);
+                   nseg_live, (G1XYZZ*)b.partial);
     }
-    SWM_LAUNCH(ctx, "msm_big_bucket_sum", s.te ? msm_big_bucket_sum<FormTE> : msm_big_bucket_sum<FormXYZZ>, big_grid, dim3(RED_BLOCK),
-               RED_BLOCK * sizeof(G1XYZZ), b.partial, b.seg_off, b.hist, s.SEG, b.big_count, b.big_list, s.log_g);
+    SWM_LAUNCH(ctx, "msm_big_bucket_sum",
+               s.raw ? msm_big_bucket_sum<FormTE29> : (s.te ? msm_big_bucket_sum<FormTEFold28> : msm_big_bucket_sum<FormXYZZ>), big_grid,
+               dim3(RED_BLOCK), RED_BLOCK * (s.raw ? sizeof(TE29Pt) : sizeof(G1XYZZ)), b.partial, b.seg_off, b.hist, s.SEG, b.big_count,
+               b.big_list, s.log_g);
     return SWM_OK;
 }
 int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine* d_bases28, const void* d_scalars, size_t n,
@@ -2650,6 +2705,7 @@ int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine*
     job->te = s.te;
     job->quad = s.quad;
     job->low = s.low;
+    job->raw = s.raw;
     job->max_blocks = s.max_blocks;
     job->stream = st_tail;
     job->pl = s.rl;
@@ -2787,6 +2843,8 @@ int msm_launch_tails(swm_ctx* ctx, MsmJob** jobs, int k) {
         max_win = std::max(max_win, j->pl.nwin);
     }
     const bool te = jobs[0]->te;  // every job of a launch has the same point form (msm_flush_tails groups them)
+    // (jobs per stage kernel, for tests that hold a shape to the path it is meant to take: quad | low-LDS | wide / thin | XYZZ)
+    ctx->stat_msm_tails[jobs[0]->quad ? 0 : (te && jobs[0]->low ? 1 : (te ? 2 : 3))] += (uint64_t)k;
     if (jobs[0]->quad) {
         const size_t lds = (3 * (size_t)jobs[0]->rb + 1) * sizeof(PlainSlot);
         const dim3 grid(max_red, max_win, (unsigned)k);
@@ -2799,11 +2857,11 @@ int msm_launch_tails(swm_ctx* ctx, MsmJob** jobs, int k) {
         }
     } else if (te && jobs[0]->low) {
         SWM_LAUNCH(ctx, "msm_bucket_reduce", (msm_bucket_reduce_low<256>), dim3(max_red, max_win, (unsigned)k), dim3(RED_BLOCK),
-                   (RED_BLOCK + 1) * sizeof(RedSlot), batch);
+                   (RED_BLOCK + 1) * sizeof(Red29Slot), batch);
     } else if (te) {
-        SWM_TRY(allow_big_lds(ctx, 7, (const void*)msm_bucket_reduce<256, FormTE>, (3 * RED_BLOCK + 1) * sizeof(RedSlot)));
-        SWM_LAUNCH(ctx, "msm_bucket_reduce", (msm_bucket_reduce<256, FormTE>), dim3(max_red, max_win, (unsigned)k), dim3(RED_BLOCK),
-                   (3 * RED_BLOCK + 1) * sizeof(RedSlot), batch);
+        SWM_TRY(allow_big_lds(ctx, 7, (const void*)msm_bucket_reduce<256, FormTE29>, (3 * RED_BLOCK + 1) * sizeof(Red29Slot)));
+        SWM_LAUNCH(ctx, "msm_bucket_reduce", (msm_bucket_reduce<256, FormTE29>), dim3(max_red, max_win, (unsigned)k), dim3(RED_BLOCK),
+                   (3 * RED_BLOCK + 1) * sizeof(Red29Slot), batch);
     } else {
         SWM_TRY(allow_big_lds(ctx, 2, (const void*)msm_bucket_reduce<256, FormXYZZ>, (3 * RED_BLOCK + 1) * sizeof(RedSlot)));
         SWM_LAUNCH(ctx, "msm_bucket_reduce", (msm_bucket_reduce<256, FormXYZZ>), dim3(max_red, max_win, (unsigned)k), dim3(RED_BLOCK),
@@ -3124,7 +3182,11 @@ enum : int {
     P28T_ROWS, P28T_TE_FROM_ROW, P28T_TE_MADD_ROW, P28T_TE_SLOT_ADD, P28T_TE_SLOT_ADD_INPLACE, P28T_TE_SLOT_ADD_SELF,
     P28T_TE_SLOT_ADD_SYNC, P28T_TE_STORE_384, P28T_QUAD_FROM_ROW, P28T_QUAD_MADD_ROW, P28T_QUAD_ADD, P28T_QUAD_ADD_SELF,
     P28T_QUAD_STORE_IDENTITY, P28T_ROWS29, P28T_TE29_FROM_ROW, P28T_TE29_MADD_ROW, P28T_TE29_QUAD_FROM_ROW, P28T_TE29_QUAD_MADD_ROW,
-    P28T_TE29_TO_SLOT, P28T_COUNT
+    P28T_TE29_TO_SLOT,
+    // the general addition of the 29-bit domain (fq29.cuh): a, b, out are raw points in the transport form of the te29_* ops above
+    // (twelve words per coordinate, fq29_unpack_raw / fq29_pack), moved into TE29Pt memory for the routine under test
+    P28T_TE29_SLOT_ADD, P28T_TE29_SLOT_ADD_INPLACE_A, P28T_TE29_SLOT_ADD_INPLACE_Q, P28T_TE29_SLOT_ADD_SELF, P28T_TE29_SLOT_ADD_SYNC,
+    P28T_TE29_QUAD_ADD, P28T_TE29_QUAD_ADD_SELF, P28T_TE29_STORE_IDENTITY, P28T_TE29_QUAD_STORE_IDENTITY, P28T_TE29_STORE_384, P28T_COUNT
 };
 // The te29 ops (fq29.cuh) take and return RAW accumulators of the 29-bit domain: four 12-word integers, a field element times
 // 2^406 each, any representative whose thirteenth limb (bits 348 ..) fits 32 bits.
@@ -3313,6 +3375,61 @@ __global__ void __launch_bounds__(256) selftest_p28_quad_kernel(int op, const G1
         break;
     }
 }
+// The general addition of the 29-bit domain on points at rest: ws holds 3 n TE29Pt (a | b | out).  Four lanes per element: each moves
+// one coordinate in and out; lane 0 of the quad runs the one-lane routines, all four the quad ones.  Workgroup barriers separate the
+// three steps (the routines read what other lanes wrote), so every lane stays to the end.
+__global__ void __launch_bounds__(256) selftest_te29_tail_kernel(int op, const G1XYZZ* a, const G1XYZZ* b, const uint32_t* flags, G1XYZZ* out,
+                                                                 TE29Pt* ws, size_t n) {
+    const size_t i = (blockIdx.x * (size_t)256 + threadIdx.x) >> 2;
+    const unsigned q = threadIdx.x & 3u;
+    const bool live = i < n;
+    const size_t j = live ? i : 0;
+    TE29Pt *pa = ws + j, *pb = ws + n + j, *po = ws + 2 * n + j;
+    if (live) {
+        if (a) te29_pt_store_coord(pa, q, fq29_unpack_raw(reinterpret_cast<const Fq*>(&a[j])[q]));
+        if (b) te29_pt_store_coord(pb, q, fq29_unpack_raw(reinterpret_cast<const Fq*>(&b[j])[q]));
+        for (int k = 0; k < 13; k++) po->w[13 * q + k] = 0xA5A5A5A5u;
+    }
+    __syncthreads();
+    const bool one = live && q == 0;
+    switch (op) {
+    case P28T_TE29_SLOT_ADD:
+        if (one) te29_slot_add(po, pa, pb);
+        break;
+    case P28T_TE29_SLOT_ADD_INPLACE_A:
+        if (one) te29_slot_add(pa, pa, pb), *po = *pa;
+        break;
+    case P28T_TE29_SLOT_ADD_INPLACE_Q:
+        if (one) te29_slot_add(pb, pa, pb), *po = *pb;
+        break;
+    case P28T_TE29_SLOT_ADD_SELF:
+        if (one) te29_slot_add(po, pa, pa);
+        break;
+    case P28T_TE29_SLOT_ADD_SYNC:  // every lane of the workgroup reaches the barrier inside; flag bit 0 = the element takes part
+        te29_slot_add_sync(po, pa, pb, one && (flags[j] & 1u) != 0, true);
+        break;
+    case P28T_TE29_QUAD_ADD:
+        if (live) te29_quad_add(po, pa, pb, q);
+        break;
+    case P28T_TE29_QUAD_ADD_SELF:
+        if (live) te29_quad_add(po, pa, pa, q);
+        break;
+    case P28T_TE29_STORE_IDENTITY:
+        if (one) te29_store_identity(po);
+        break;
+    case P28T_TE29_QUAD_STORE_IDENTITY:
+        if (live) te29_quad_store_identity(po, q);
+        break;
+    case P28T_TE29_STORE_384:
+        if (one) te29_store_384(out[j], *pa);
+        break;
+    default:
+        break;
+    }
+    __syncthreads();
+    const bool sat_out = op == P28T_TE29_SLOT_ADD_SYNC && (flags[j] & 1u) == 0;  // its slot keeps what the caller filled it with
+    if (live && !sat_out && op != P28T_TE29_STORE_384) reinterpret_cast<Fq*>(&out[j])[q] = fq29_pack(te29_pt_load_coord(po, q));
+}
 // a twisted Edwards slot of the 28-bit domain -> the Weierstrass point it stands for, by the maps the bucket stage and the host
 // fold apply to a total (te28_store_384, g1te_to_xyzz), as a Jacobian point in the memory form
 // (from29: the slots hold a raw accumulator of the 29-bit domain, taken through the accumulation's epilogue first)
@@ -3340,6 +3457,11 @@ int selftest_p28_run(swm_ctx* ctx, int op, const void* da, const void* db, const
         const unsigned gridn = (unsigned)(((n + TAB_NORM_CHUNK - 1) / TAB_NORM_CHUNK + 255) / 256);
         SWM_LAUNCH(ctx, "selftest_p28_rows", op == P28T_ROWS29 ? msm_te_convert<true> : msm_te_convert<false>, dim3(gridn), dim3(256), 0,
                    (const G1Affine*)da, n, (Fq*)d_pref, (G1TE*)d_out, d_status);
+    } else if (op >= P28T_TE29_SLOT_ADD) {
+        TE29Pt* ws = nullptr;
+        SWM_TRY(scratch(ctx, "stage.t29", 3 * n * sizeof(TE29Pt) + 64, (void**)&ws));
+        SWM_LAUNCH(ctx, "selftest_te29_tail", selftest_te29_tail_kernel, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, op,
+                   (const G1XYZZ*)da, (const G1XYZZ*)db, d_flags, (G1XYZZ*)d_out, ws, n);
     } else if (quad) {
         SWM_LAUNCH(ctx, "selftest_p28_quad", selftest_p28_quad_kernel, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, op,
                    (const G1XYZZ*)da, (const G1XYZZ*)db, d_flags, (G1XYZZ*)d_out, n);
@@ -3349,7 +3471,8 @@ int selftest_p28_run(swm_ctx* ctx, int op, const void* da, const void* db, const
     }
     if (d_jac)
         SWM_LAUNCH(ctx, "selftest_p28_backmap", selftest_p28_backmap_kernel, dim3(grid), dim3(256), 0, (const G1XYZZ*)d_out, (G1Jac*)d_jac, n,
-                   op >= P28T_TE29_FROM_ROW && op <= P28T_TE29_QUAD_MADD_ROW);
+                   (op >= P28T_TE29_FROM_ROW && op <= P28T_TE29_QUAD_MADD_ROW) ||
+                       (op >= P28T_TE29_SLOT_ADD && op <= P28T_TE29_QUAD_STORE_IDENTITY));
     return SWM_OK;
 }
 

@@ -4,7 +4,12 @@ te29_madd_row / te29_quad_madd_row through their shared te29_efgh, te29_to_slot)
 column sum — with the `+ 2^29 - 1` of the asm multiplier's carry rule — is checked for wrap-around, and the results are compared
 with the group law computed with Python integers on y^2 = x^3 + 1.  worst_case() evaluates the column sums of every product with
 each limb at its documented maximum (interval bounds, the real constants).  The sibling of tools/check_te28.py.
-CPU only; run: python tools/check_te29.py [chains]"""
+`tail`: the same for the general addition the one-lane bucket stage runs (te29_slot_add and its sync / quad forms, te29_store_384):
+worst_case_tail() for the nine products and the store's, and bucket stages emulated step by step — running sum, weighted sum,
+scan, the shift phase's doublings, fold, tree — on partial sums of every accepted form and on extremal slots.
+`header`: writes tail_operands(), the operand maxima of those products, as csrc/te29_bounds_gen.inc, which fq29.cuh evaluates in a
+static_assert: one table for the tool and the build.
+CPU only; run: python tools/check_te29.py [chains]   |   python tools/check_te29.py tail [chains]   |   python tools/check_te29.py header"""
 import os, random, sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import check_te28 as c28
@@ -231,7 +236,229 @@ def run_extremal(steps=6):
     return n
 
 
+# ------------------------------------------------------------------------------------------------ the general addition (bucket stage)
+# te29_slot_add / te29_slot_add_sync / te29_quad_add and te29_store_384 of fq29.cuh: points at rest in memory, four coordinates of
+# thirteen limbs.  Accepted operand forms: all four N (what an addition leaves); te29_from_row's (X normalised in (p, 3p), Y
+# normalised below 2p, T: N, Z: the constant); the identity (0 : 1 : 0 : 1).
+K2D = limbs(2 * te_d * R406 % Q)
+TO384 = limbs((1 << 384) % Q)
+IDENT = [limbs(0), ONE, limbs(0), ONE]
+TOP = BITS * (NL - 1)
+
+
+def at_rest(p):
+    """asserts p is a point a slot may hold: limbs below the top one under 2^29, X < 3p, Y < 2p, T and Z: N"""
+    for c, bound in zip(p, (3 * Q, 2 * Q, N_MAX, N_MAX)):
+        assert all(x <= M29 for x in c[:NL - 1]) and val(c) < bound, "operand form"
+    return p
+
+
+def slot_add(a, q):
+    """te29_slot_add: nine products, (Y1 - X1 + 4p) and (Y1 + X1) of the FIRST operand carry-normalised, the second operand's raw"""
+    (ax, ay, at, az), (qx, qy, qt, qz) = at_rest(a), at_rest(q)
+    A = mul(normalize(sub(ay, ax, SPREAD4)), sub(qy, qx, SPREAD4))
+    B = mul(normalize(add(ay, ax)), add(qy, qx))
+    C = mul(mul(at, qt), K2D)
+    ZZ = mul(az, qz)
+    E, F, G, H = efgh(A, B, C, ZZ, False)
+    return at_rest([mul(E, F), mul(G, H), mul(E, H), mul(F, G)])
+
+
+def store_384(p):
+    """te29_store_384: canonical coordinates in radix 2^384"""
+    out = []
+    for c in at_rest(p):
+        r = val(mul(c, TO384))
+        r -= Q if r >= Q else 0
+        assert 0 <= r < Q and r == val(c) * inv(R406) * (1 << 384) % Q
+        out.append(r)
+    return out
+
+
+def tail_operands(norm_first=True):
+    """(a_max, b_max) of each of the nine products of te29_slot_add and of te29_store_384's: every limb at the maximum of the widest
+    accepted operand form (which covers doubling and the identity: they are operands of those forms)"""
+    full = [M29] * (NL - 1)
+    canon = full + [Q >> TOP]
+    nmax = full + [N_MAX >> TOP]
+    x1 = full + [3 * Q >> TOP]
+    y1 = full + [2 * Q >> TOP]
+    plus = lambda a, b: [x + y for x, y in zip(a, b)]
+    nrm = lambda top: full + [top >> TOP]
+    d_raw, s_raw = plus(y1, SPREAD4), plus(y1, x1)          # Y - X + 4p (X down to 0), Y + X
+    # second round (te29_efgh, a point that is added): A, B, C: N and D = 2 Z1 Z2 with Z1 Z2: N
+    D = plus(nmax, nmax)
+    E, H, F, G = plus(nmax, SPREAD2), nrm(3 * Q), nrm(5 * Q), plus(D, nmax)
+    return {"A (Y1-X1+4p)(Y2-X2+4p)": (nrm(6 * Q) if norm_first else d_raw, d_raw),
+            "B (Y1+X1)(Y2+X2)": (nrm(5 * Q) if norm_first else s_raw, s_raw),
+            "T1 T2": (nmax, nmax), "(T1 T2) 2d": (nmax, canon), "Z1 Z2": (nmax, nmax),
+            "E F": (E, F), "G H": (G, H), "E H": (E, H), "F G": (F, G), "coord 2^384": (x1, canon)}
+
+
+def worst_case_tail(verbose=False, norm_first=True):
+    """column bound of each product of tail_operands()"""
+    out = {k: column_bound(a, b) for k, (a, b) in tail_operands(norm_first).items()}
+    second = worst_case("FH")                                # the mixed addition's second round has the same operands
+    assert all(out[k] == second[k] for k in ("E F", "G H", "E H", "F G"))
+    if verbose:
+        for k, b in out.items():
+            print("  %-24s %.3f x 2^64" % (k, b))
+    return out
+
+
+def bounds_header():
+    """csrc/te29_bounds_gen.inc: tail_operands() as the table fq29.cuh evaluates at build time (te29_slot_add_bounds_ok)"""
+    rows = ["// generated by tools/check_te29.py (python tools/check_te29.py header): operand maxima of the nine products of te29_slot_add and of",
+            "// te29_store_384's, {name, a_max[13], b_max[13]} — tools/check_te29.py tail_operands(); tests/test_te29_tail_bounds.py holds",
+            "// this file to the tool.", "#define SWM_TE29_TAIL_BOUNDS \\"]
+    items = list(tail_operands().items())
+    for n, (k, (a, b)) in enumerate(items):
+        arr = lambda l: "{" + ", ".join("0x%08xu" % x for x in l) + "}"
+        rows.append('    {"%s", %s, \\' % (k, arr(a)))
+        rows.append("     %s}%s" % (arr(b), ", \\" if n + 1 < len(items) else ""))
+    return "\n".join(rows) + "\n"
+
+
+def nl(v):
+    """limbs of a value that may exceed 2^377: the top limb takes what is left (a normalised coordinate)"""
+    return [(v >> (BITS * i)) & M29 for i in range(NL - 1)] + [v >> TOP]
+
+
+def extremal_points():
+    """slots that are no curve points: every coordinate at the edge of its accepted form, in value and in limb pattern"""
+    def edge(bound):
+        top = (bound - 1) >> TOP
+        return [nl(bound - 1), [M29] * (NL - 1) + [top - 1], [M29] * (NL - 1) + [0], nl(0), nl(1)]
+    xs, ys, ns = edge(3 * Q), edge(2 * Q), edge(N_MAX)
+    return [[xs[i], ys[i], ns[i], ns[i]] for i in range(5)] + [[xs[0], ys[4], ns[1], ns[3]], [xs[3], ys[0], ns[0], ns[1]], IDENT]
+
+
+def bucket_stage(parts, lanes, log_m, wref):
+    """The micro-operations of msm_bucket_reduce on 2^log_m buckets per lane: running sum, weighted sum, suffix scan, the shift
+    phase's doublings, the fold and the tree — all by slot_add.  parts[b]: the partial sums of bucket b (slots); wref[b]: the
+    bucket's sum on the Weierstrass curve, or None when the points are extremal slots (then only wrap-around is checked).
+    Returns (A, R) of the workgroup and the number of additions."""
+    m, n = 1 << log_m, 0
+    run, acc = [IDENT] * lanes, [IDENT] * lanes
+    ref_run, ref_acc = [None] * lanes, [None] * lanes
+    check = wref is not None
+    for t in range(lanes):
+        for b in range((t + 1) * m - 1, t * m - 1, -1):
+            for p in parts[b]:
+                run[t] = slot_add(run[t], p)
+                n += 1
+            acc[t] = slot_add(acc[t], run[t])
+            n += 1
+            if check:
+                ref_run[t] = g1_add(ref_run[t], wref[b])
+                ref_acc[t] = g1_add(ref_acc[t], ref_run[t])
+                assert to_w(run[t]) == ref_run[t] and to_w(acc[t]) == ref_acc[t], "walk mismatch"
+    d = 1
+    while d < lanes:                                         # inclusive suffix scan (Hillis-Steele)
+        nxt, nref = list(run), list(ref_run)
+        for t in range(lanes - d):
+            nxt[t] = slot_add(run[t], run[t + d])
+            nref[t] = g1_add(ref_run[t], ref_run[t + d]) if check else None
+            n += 1
+        run, ref_run = nxt, nref
+        d <<= 1
+    r_blk, ref_r = run[0], ref_run[0]
+    sh = run[1:] + [IDENT]
+    ref_sh = ref_run[1:] + [None]
+    for _ in range(log_m):                                   # the shift phase: doublings, pa == pq
+        sh = [slot_add(p, p) for p in sh]
+        ref_sh = [g1_add(p, p) for p in ref_sh] if check else ref_sh
+        n += lanes
+    acc = [slot_add(a, s) for a, s in zip(acc, sh)]          # fold
+    ref_acc = [g1_add(a, s) for a, s in zip(ref_acc, ref_sh)] if check else ref_acc
+    n += lanes
+    d = lanes // 2
+    while d:                                                 # tree
+        for t in range(d):
+            acc[t] = slot_add(acc[t], acc[t + d])
+            ref_acc[t] = g1_add(ref_acc[t], ref_acc[t + d]) if check else None
+            n += 1
+        d >>= 1
+    if check:
+        assert to_w(r_blk) == ref_r and to_w(acc[0]) == ref_acc[0], "stage mismatch"
+        # the workgroup's results as the weighted sum of its buckets
+        want_a = want_r = None
+        for b in range(lanes * m):
+            want_r = g1_add(want_r, wref[b])
+            want_a = g1_add(want_a, g1_mul_fast(wref[b], b + 1) if wref[b] is not None else None)
+        assert ref_r == want_r and ref_acc[0] == want_a
+    for p in (r_blk, acc[0]):
+        store_384(p)
+    return acc[0], r_blk, n
+
+
+def run_tail(chains=3):
+    """bucket stages on real points — partial sums of every accepted form: one-entry segments (te29_from_row), longer ones (after
+    te29_madd_row), empty ones (the identity), a bucket that cancels, a bucket whose two partial sums are equal — and on extremal
+    slots; plus every pair of extremal slots through one addition, either way round and doubled.  Returns the additions emulated."""
+    n = 0
+    for c in range(chains):
+        lanes, log_m = 4, 1
+        parts, wref = [], []
+        for b in range(lanes << log_m):
+            kind = (b + c) % 5
+            segs, ref = [], None
+            for s in range((0, 2, 1, 1, 1)[kind]):              # kind 0: an empty bucket, the identity
+                pts = [g1_mul_fast(G, random.randrange(1, R)) for _ in range(1 if kind == 2 else 3)]
+                signs = [random.random() < 0.5 for _ in pts]
+                a, r = run_chain(pts, signs)
+                segs.append(a)
+                ref = g1_add(ref, r)
+            if kind == 3:                                    # the same partial sum twice: the unified law doubles
+                segs.append(segs[0])
+                ref = g1_add(ref, ref)
+            if kind == 4:                                    # P + (-P): the bucket's running sum returns to where it was
+                P = g1_mul_fast(G, random.randrange(1, R))
+                segs += [from_row(*row_of(P), False), from_row(*row_of(P), True)]
+            if not segs:
+                segs = [IDENT]
+            parts.append(segs)
+            wref.append(ref)
+        n += bucket_stage(parts, lanes, log_m, wref)[2]
+    ext = extremal_points()
+    for a in ext:
+        for q in ext:
+            r = slot_add(a, q)
+            r = slot_add(r, r)
+            slot_add(q, r)
+            n += 3
+    n += bucket_stage([[ext[b % len(ext)], ext[(3 * b + 1) % len(ext)]] for b in range(8)], 4, 1, None)[2]
+    return n
+
+
+def tail_main(chains=3, verbose=True):
+    """the general addition: emulated chains and worst-case columns; returns (worst column as a fraction of 2^64, additions)"""
+    random.seed(2929)
+    peak[0] = 0
+    n = run_tail(chains)
+    wc = worst_case_tail(verbose)
+    worst = max(wc.values())
+    if verbose:
+        print("te29 general addition OK: %d additions on points and extremal slots; no uint32 / uint64 wrap; peak column %.3f x 2^64"
+              % (n, peak[0] / LIM))
+        print("worst column of the nine products and of te29_store_384: %.3f x 2^64 (limit %.9f)" % (worst, (LIM - (1 << BITS)) / LIM))
+        raw = worst_case_tail(False, norm_first=False)
+        print("  with neither first-round operand normalised: A %.3f, B %.3f x 2^64  -> overflow"
+              % (raw["A (Y1-X1+4p)(Y2-X2+4p)"], raw["B (Y1+X1)(Y2+X2)"]))
+    assert worst * LIM < LIM - (1 << BITS) and peak[0] < LIM - (1 << BITS)
+    return worst, n
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "header":
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "simpleworks_amd", "csrc", "te29_bounds_gen.inc")
+        with open(path, "w") as f:
+            f.write(bounds_header())
+        print("wrote", os.path.normpath(path))
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "tail":
+        tail_main(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
+        return
     chains = int(sys.argv[1]) if len(sys.argv) > 1 else 6
     random.seed(29)
     n_add = 0
