@@ -1341,6 +1341,34 @@ int swm_selftest_spmv_plan(swm_ctx *ctx, const uint32_t *rowptr, const uint32_t 
 int swm_selftest_msm_jobs(swm_ctx *ctx, const swm_bases *const *sets, size_t nsets, const uint64_t *scalars, const size_t *vec_off,
                           size_t nvec, int scalars_montgomery, const uint64_t *jobs, size_t k, int defer_tail, size_t pipe_min,
                           uint64_t *out_jac, uint64_t *twins);
+/* Device self-test of the SORT STAGE of the G1 MSM (csrc/msm.hip): one job is taken through the host functions msm_enqueue runs, in
+ * its order — shape, zeroed block, buffers, digits, the flat or the per-window sort with its segment descriptors, the ordering of
+ * the segments by length — on the context's stream, and stops there: nothing is accumulated.  Before the sort (here only) the job's
+ * sorted, seg_start, seg_len, order and big_list arrays, and the second sorted array of a lead, are filled with bytes 0xFF, so that
+ * a word the stage never wrote reads back as 0xFFFFFFFF.  No other MSM job of the context may be in flight.
+ * set, offset, n: the job, n scalars over the points offset .. offset + n of a resident base set, with the set's table and infinity
+ * mask as swm_msm_g1_dev hands them over.  scalars: n x 4 uint64 (Montgomery form when scalars_montgomery != 0, else standard
+ * form).  defer_tail != 0: shaped as a job that leaves its bucket stage to the joint launch of a round.  follow_set (or NULL),
+ * follow_offset: the job that would follow this one as its twin; the job then sorts as a LEAD when the library pairs the two
+ * (shape[6]) and writes the second sorted array, with the rows of that job's table.
+ * shape: 96 uint64 — [0] flat schedule, [1] twisted Edwards rows, [2] low-latency variant, [3] quad bucket stage, [4] raw 29-bit
+ * partial sums, [5] buckets of several segments are cut round-robin (seg_len = length | stride << 8), [6] sorts as a LEAD,
+ * [7] windows, [8] NB = buckets, [9] total = n x windows, [10] SEG = segment bound, [11] big_nseg: buckets with MORE segments are
+ * listed and folded ahead of the bucket stage, [12] log_g: log2 of the lanes that fold one, [13] flat_fb, [14] flat_bins: log2
+ * buckets per coarse bin and the number of bins, [15] nseg_max: segment indices a job may use, [16] rows per window of the table
+ * (0: none); [32 + w] the width of window w.
+ * arrays: NULL — the shape alone is returned, nothing runs — or 10 pointers to host arrays sized from the shape, each of which may
+ * be NULL: hist [NB] entries per bucket, bucket_off [NB] first entry, seg_off [NB] first segment index, sorted [total] the entries
+ * (table row, or point index without a table, sign of the digit in bit 31), seg_start, seg_len, order [nseg_max each], len_hist
+ * [SEG + 1]: class i counts the segments of SEG - i entries, big_list [NB], sorted2 [total] (written for a LEAD only).
+ * words: 8 uint32 — [0] the bound on segment indices the stage hands to msm_seg_order, [1] nseg_live: segments that hold entries =
+ * the valid prefix of order, [2] big_count: the valid prefix of big_list, [3] != 0: a scalar was not a canonical field element,
+ * [4] points that contribute nothing (zero scalar or identity base), [5] entries the sort placed.
+ * SWM_ERR_INVALID_ARG: a NULL context, set or shape; arrays without scalars or words; n = 0; offset + n beyond the set, or
+ * follow_offset + n beyond follow_set.  SWM_ERR_INTERNAL: MSM jobs of the context are in flight. */
+int swm_selftest_msm_sort(swm_ctx *ctx, const swm_bases *set, size_t offset, size_t n, const uint64_t *scalars, int scalars_montgomery,
+                          int defer_tail, const swm_bases *follow_set, size_t follow_offset, uint64_t shape[96],
+                          uint32_t *const *arrays, uint32_t words[8]);
 /* Jobs whose bucket stage each kernel has run on this context so far: out[0] the quad stage (msm_bucket_reduce<RB, FormTEQuad>, partial
  * sums in 28-bit slots), out[1] msm_bucket_reduce_low, out[2] msm_bucket_reduce<256, FormTE29> (both on raw 29-bit partial sums),
  * out[3] msm_bucket_reduce<256, FormXYZZ>.  For tests that hold a job shape to the path it is meant to take.  Needs no GPU work. */

@@ -277,6 +277,7 @@ ABI = {
     "swm_selftest_sample_fr": (_int, [_vp, _vp, _sz, _u64p]),
     "swm_selftest_msm_jobs": (_int, [_vp, ctypes.POINTER(_vp), _sz, _u64p, ctypes.POINTER(_sz), _sz, _int, _u64p, _sz, _int, _sz,
                                      _u64p, _u64p]),
+    "swm_selftest_msm_sort": (_int, [_vp, _vp, _sz, _sz, _u64p, _int, _int, _vp, _sz, _u64p, ctypes.POINTER(_u32p), _u32p]),
     "swm_selftest_msm_tail_counts": (_int, [_vp, _u64p]),
     "swm_verify_proofs_batch": (_int, [_vp, _vp, _u64p, _sz, _vp, ctypes.POINTER(_sz), _sz, ctypes.c_uint, _vp,
                                        ctypes.POINTER(_int), ctypes.POINTER(_int)]),
@@ -1544,6 +1545,39 @@ class Context:
                                                    _p64(spec), spec.shape[0], self.MSM_DEFER[defer_tail], pipe_min, _p64(out),
                                                    _p64(twins)), "swm_selftest_msm_jobs")
         return out[:spec.shape[0]], int(twins[0])
+
+    MSM_SORT_SHAPE = ("flat", "te", "lat", "quad", "raw", "interleave", "lead", "nwin", "NB", "total", "SEG", "big_nseg", "log_g",
+                      "flat_fb", "flat_bins", "nseg_max", "tstride")
+    MSM_SORT_ARRAYS = ("hist", "bucket_off", "seg_off", "sorted", "seg_start", "seg_len", "order", "len_hist", "big_list", "sorted2")
+    MSM_SORT_WORDS = ("seg_bound", "nseg_live", "big_count", "bad_scalar", "zero_points", "entries")
+
+    def selftest_msm_sort(self, bases, scalars, offset=0, montgomery=False, defer_tail=False, follow=None, shape_only=False):
+        """swm_selftest_msm_sort: one MSM job over bases[offset : offset + n] up to and including msm_seg_order.  follow: None, or
+        (Bases, offset) of the job that would follow this one as its twin.  Returns (shape, arrays): shape a dict of the fields
+        MSM_SORT_SHAPE plus "c" (the window widths); arrays a dict of uint32 arrays MSM_SORT_ARRAYS (sorted2 only for a lead) and of
+        the integers MSM_SORT_WORDS — None with shape_only, which launches nothing."""
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        n = sc.shape[0]
+        fset, foff = (follow[0].h, follow[1]) if follow else (None, 0)
+        raw = np.zeros(96, dtype=np.uint64)
+        self._check(self.lib.swm_selftest_msm_sort(self.h, bases.h, offset, n, None, 0, 1 if defer_tail else 0, fset, foff, _p64(raw),
+                                                   None, None), "swm_selftest_msm_sort")
+        shape = {k: int(raw[i]) for i, k in enumerate(self.MSM_SORT_SHAPE)}
+        shape["c"] = [int(v) for v in raw[32:32 + shape["nwin"]]]
+        if shape_only:
+            return shape, None
+        size = {"hist": shape["NB"], "bucket_off": shape["NB"], "seg_off": shape["NB"], "sorted": shape["total"],
+                "seg_start": shape["nseg_max"], "seg_len": shape["nseg_max"], "order": shape["nseg_max"], "len_hist": shape["SEG"] + 1,
+                "big_list": shape["NB"], "sorted2": shape["total"] if shape["lead"] else 0}
+        arrays = {k: np.zeros(size[k], dtype=np.uint32) for k in self.MSM_SORT_ARRAYS}
+        ptrs = (_u32p * 10)(*[_p32(arrays[k]) if size[k] else None for k in self.MSM_SORT_ARRAYS])
+        words = np.zeros(8, dtype=np.uint32)
+        self._check(self.lib.swm_selftest_msm_sort(self.h, bases.h, offset, n, _p64(sc), 1 if montgomery else 0, 1 if defer_tail else 0,
+                                                   fset, foff, _p64(raw), ptrs, _p32(words)), "swm_selftest_msm_sort")
+        if not shape["lead"]:
+            del arrays["sorted2"]
+        arrays.update({k: int(words[i]) for i, k in enumerate(self.MSM_SORT_WORDS)})
+        return shape, arrays
 
     def selftest_msm_tail_counts(self):
         """swm_selftest_msm_tail_counts: jobs per bucket-stage kernel on this context so far, as a dict quad / low / te29 / xyzz."""

@@ -1078,6 +1078,53 @@ int swm_selftest_msm_jobs(swm_ctx* ctx, const swm_bases* const* sets, size_t nse
     *twins = ctx->stat_msm_twins - twins_before;
     return SWM_OK;
 }
+// One job up to and including msm_seg_order (msm.hip: msm_selftest_sort), its shape and the arrays the stage leaves.
+int swm_selftest_msm_sort(swm_ctx* ctx, const swm_bases* set, size_t offset, size_t n, const uint64_t* scalars, int scalars_montgomery,
+                          int defer_tail, const swm_bases* follow_set, size_t follow_offset, uint64_t shape[96],
+                          uint32_t* const* arrays, uint32_t words[8]) {
+    if (!ctx || !set || !shape || n == 0 || (arrays && (!scalars || !words)))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_sort: bad arguments");
+    if (offset > set->n || n > set->n - offset)
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_sort: %zu scalars at offset %zu exceed %zu bases", n, offset, set->n);
+    if (follow_set && (follow_offset > follow_set->n || n > follow_set->n - follow_offset))
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_sort: leads %zu scalars at offset %zu of a set of %zu bases", n,
+                       follow_offset, follow_set->n);
+    SWM_ON_DEVICE(ctx);
+    auto table_of = [](const swm_bases* b, size_t off) {  // as swm_msm_g1_dev
+        return b->table_c ? MsmTable{b->d_te ? nullptr : reinterpret_cast<const G1Affine*>(b->d_points28), b->n, b->table_c, off,
+                                     reinterpret_cast<const G1TE*>(b->d_te)}
+                          : MsmTable();
+    };
+    const MsmTable tab = table_of(set, offset), tab2 = follow_set ? table_of(follow_set, follow_offset) : MsmTable();
+    void* d = nullptr;
+    if (arrays) {
+        SWM_TRY(scratch(ctx, "stage.scalars", n * 32 + 32, &d));
+        SWM_HIP(ctx, hipMemcpyAsync(d, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    }
+    MsmSortDump dump = MsmSortDump();
+    if (arrays) {
+        uint32_t** const to[10] = {&dump.hist,    &dump.bucket_off, &dump.seg_off,  &dump.sorted,  &dump.seg_start,
+                                   &dump.seg_len, &dump.order,      &dump.len_hist, &dump.big_list, &dump.sorted2};
+        for (int i = 0; i < 10; i++) *to[i] = arrays[i];
+    }
+    const int rc = msm_selftest_sort(ctx, d, n, scalars_montgomery, MsmInfMask{set->d_inf_mask, offset}, defer_tail != 0, tab,
+                                     follow_set ? &tab2 : nullptr, &dump, arrays != nullptr);
+    if (rc != SWM_OK) {  // scratch must not be reused under kernels still in flight
+        drain_streams(ctx);
+        return rc;
+    }
+    memset(shape, 0, 96 * sizeof(uint64_t));
+    const uint64_t head[17] = {dump.flat,    dump.te,       dump.lat,   dump.quad,    dump.raw,       dump.interleave, dump.lead, dump.pl.nwin,
+                               dump.pl.NB,   dump.total,    dump.SEG,   dump.big_nseg, dump.log_g,    dump.flat_fb,    dump.flat_bins,
+                               dump.nseg_max, dump.tstride};
+    memcpy(shape, head, sizeof(head));
+    for (unsigned w = 0; w < dump.pl.nwin; w++) shape[32 + w] = dump.pl.c[w];
+    if (arrays) {
+        const uint32_t tail[8] = {dump.seg_bound, dump.status[3], dump.status[0], dump.status[1], dump.status[2], dump.entries, 0, 0};
+        memcpy(words, tail, sizeof(tail));
+    }
+    return SWM_OK;
+}
 int swm_selftest_msm_tail_counts(swm_ctx* ctx, uint64_t out[4]) {
     if (!ctx || !out) return SWM_ERR_INVALID_ARG;
     for (int i = 0; i < 4; i++) out[i] = ctx->stat_msm_tails[i];

@@ -168,6 +168,20 @@ int msm_finish_many(swm_ctx* ctx, MsmJob** jobs, int k, G1XYZZ* results);  // a 
 HostPool* host_pool_of(swm_ctx* ctx);
 int msm_run(swm_ctx* ctx, const G1Affine* d_bases, const G1Affine* d_bases28, const void* d_scalars, size_t n, int mont,
             G1XYZZ* result, MsmInfMask inf = MsmInfMask(), MsmTable tab = MsmTable());
+// What msm_selftest_sort (msm.hip, "sort self-test") reports: the job's shape, and — host arrays of the caller, sized from the shape,
+// each optional — the arrays its sort stage leaves on the device.  len_hist: SEG + 1 counts, class i = segments of SEG - i entries.
+struct MsmSortDump {
+    bool flat, te, lat, quad, raw, interleave, lead;
+    WinLayout pl;
+    size_t total, nseg_max;
+    uint32_t SEG, big_nseg, log_g, flat_fb, flat_bins, tstride;
+    uint32_t *hist, *bucket_off, *seg_off, *sorted, *seg_start, *seg_len, *order, *len_hist, *big_list, *sorted2;
+    uint32_t status[4];  // oversized buckets | a scalar was not canonical | points that contribute nothing | segments with entries
+    uint32_t seg_bound, entries;  // the segment-index bound handed to msm_seg_order; entries the sort placed
+};
+// tab2: the table (with its offset) of a follower, or null; run = false: the shape fields alone, nothing is launched
+int msm_selftest_sort(swm_ctx* ctx, const void* d_scalars, size_t n, int mont, MsmInfMask inf, bool defer_tail, MsmTable tab,
+                      const MsmTable* tab2, MsmSortDump* out, bool run);
 // One op of the point-layer self-test (msm.hip, "point-layer self-test"; include/swmarlin.h: swm_selftest_p28) on n elements of
 // device buffers: d_jac (optional) receives the Weierstrass image of every twisted Edwards result, d_pref is msm_te_convert's
 // scratch (n field elements), d_status one word per element (zeroed by the caller).

@@ -2535,6 +2535,22 @@ static int msm_twin_copy_stage(swm_ctx* ctx, const MsmShape& s, const MsmZeroLay
     ctx->stat_msm_twins++;
     return SWM_OK;
 }
+// do the segments of a bucket with more than SEG entries take its entries round-robin (FlatSegOut::interleave)?
+static bool msm_interleaves(const MsmShape& s) { return s.flat && s.te; }
+// The job's zeroed block (MsmZeroLayout): counts, cursors, status words.
+static int msm_zero_stage(swm_ctx* ctx, const MsmZeroLayout& z, const MsmBuffers& b) {
+    SWM_HIP(ctx, zero_fill_async(b.hist, z.words * 4, ctx->stream));  // (a kernel with issue priority, not the runtime's fill: fill.cuh)
+    return SWM_OK;
+}
+// Signed-digit recoding of the scalars into b.digits; the status words (big_count + 1, + 2) were zeroed with the histogram.
+static int msm_digits_stage(swm_ctx* ctx, const MsmShape& s, const MsmBuffers& b, const void* d_scalars, size_t n, int mont,
+                            const MsmInfMask& inf, const MsmTable& tab) {
+    const unsigned grid_n = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16);
+    SWM_LAUNCH(ctx, "msm_digits", msm_digits, dim3(grid_n), dim3(256), 0, reinterpret_cast<const Fr*>(d_scalars), n, mont, s.pl,
+               b.digits, inf.mask, inf.first, b.big_count + 1, s.dshard, tab.scalar_stride != 1 ? tab.blk_log : 31u,
+               tab.scalar_stride != 1 ? tab.bstride : (size_t)0);
+    return SWM_OK;
+}
 // Flat schedule: two-level counting sort over the shared bucket set; the fine counts written by msm_flat_bin_sort are the
 // histogram the scans consume, and the bins are contiguous bucket ranges, so `sorted` is in bucket order.
 // lead (a twin pair's LEAD, filled in but for `ready`): the bin sort also writes the sorted array of lead->tab2, and lead->sorted
@@ -2568,7 +2584,7 @@ static int msm_sort_flat(swm_ctx* ctx, const MsmShape& s, const MsmBuffers& b, c
     // (bucket / segment offsets, segment descriptors, the length histogram and the list of oversized buckets come out of
     // the bin sort: no scans over the bucket histogram, no msm_seg_desc)
     const FlatSegOut fso{b.hist,    b.bucket_off, b.seg_off, b.seg_start, b.seg_len, b.len_hist,
-                         b.big_count, b.big_list, s.SEG,     s.big_nseg,  s.te ? 1u : 0u};
+                         b.big_count, b.big_list, s.SEG,     s.big_nseg,  msm_interleaves(s) ? 1u : 0u};
     TwinOut two{nullptr, 1u, 0u, 0u};
     if (lead) {
         // (the array is read by the accumulation of the previous pair's follower)
@@ -2614,19 +2630,29 @@ static int msm_sort_windows(swm_ctx* ctx, const MsmShape& s, const MsmBuffers& b
                b.bucket_off, b.cursor, b.sorted, s.two_level ? (const uint32_t*)b.two_level_bad : (const uint32_t*)nullptr);
     return SWM_OK;
 }
-// Stage A: segments ordered by length, one partial sum per segment (msm_accumulate*), oversized buckets folded ahead of the
-// bucket stage (msm_big_bucket_sum).
-static int msm_accumulate_stage(swm_ctx* ctx, const MsmShape& s, const MsmBuffers& b, const MsmTable& tab, const G1Affine* d_bases,
-                                const G1Affine* d_bases28) {
+// Segment planning: the descriptors (per-window schedule: msm_seg_desc; the flat schedule's bin sort has written them) and the
+// segments ordered by length, longest first, with the count of those that hold entries (msm_seg_order).
+static uint32_t* msm_nseg_live(const MsmBuffers& b) { return b.big_count + 3; }  // segments that hold entries = lanes of work for the accumulation
+// segment indices in use (a device word): the flat schedule's bins hand them out by capacity, the per-window schedule densely
+static const uint32_t* msm_seg_space(const MsmShape& s, const MsmBuffers& b) { return s.flat ? b.flat_seg_off + s.flat_bins : b.seg_off + s.pl.NB; }
+// entries the sort placed (a device word)
+static const uint32_t* msm_entries_word(const MsmShape& s, const MsmBuffers& b) { return s.flat ? b.flat_off + s.flat_bins : b.bucket_off + s.pl.NB; }
+static int msm_seg_order_stage(swm_ctx* ctx, const MsmShape& s, const MsmBuffers& b) {
     unsigned grid_s = (unsigned)((s.nseg_max + ORD_THREADS - 1) / ORD_THREADS);
-    // segment indices in use (a device word): the flat schedule's bins hand them out by capacity, the per-window schedule densely
-    const uint32_t* seg_space = s.flat ? b.flat_seg_off + s.flat_bins : b.seg_off + s.pl.NB;
-    uint32_t* nseg_live = b.big_count + 3;  // segments that hold entries = lanes of work for the accumulation
     if (!s.flat)
         SWM_LAUNCH(ctx, "msm_seg_order", msm_seg_desc, dim3(grid_s), dim3(ORD_THREADS), 0, b.bucket_off, b.seg_off, s.pl.NB, s.SEG,
                    b.seg_start, b.seg_len, b.len_hist);
     SWM_LAUNCH(ctx, "msm_seg_order", msm_seg_order, dim3((unsigned)((s.nseg_max + ORD2_THREADS * ORD2_U - 1) / (ORD2_THREADS * ORD2_U))),
-               dim3(ORD2_THREADS), 0, b.seg_len, seg_space, s.SEG, (const uint32_t*)b.len_hist, b.len_cursor, nseg_live, b.order);
+               dim3(ORD2_THREADS), 0, b.seg_len, msm_seg_space(s, b), s.SEG, (const uint32_t*)b.len_hist, b.len_cursor, msm_nseg_live(b),
+               b.order);
+    return SWM_OK;
+}
+// Stage A: segments ordered by length, one partial sum per segment (msm_accumulate*), oversized buckets folded ahead of the
+// bucket stage (msm_big_bucket_sum).
+static int msm_accumulate_stage(swm_ctx* ctx, const MsmShape& s, const MsmBuffers& b, const MsmTable& tab, const G1Affine* d_bases,
+                                const G1Affine* d_bases28) {
+    SWM_TRY(msm_seg_order_stage(ctx, s, b));
+    const uint32_t* nseg_live = msm_nseg_live(b);
     unsigned acc_grid = (unsigned)((s.nseg_max + 255) / 256);
     const dim3 big_grid(std::min<unsigned>((s.pl.NB + (RED_BLOCK >> s.log_g) - 1) / (RED_BLOCK >> s.log_g), s.lat ? 2048 : 512));
     if (s.te) {
@@ -2734,14 +2760,11 @@ int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine*
     MsmBuffers b;
     SWM_TRY(msm_buffers(ctx, s, z, slot, follow != nullptr, &b));
     job->d_acc = b.acc;
-    SWM_HIP(ctx, zero_fill_async(b.hist, z.words * 4, ctx->stream));  // (a kernel with issue priority, not the runtime's fill: fill.cuh)
+    SWM_TRY(msm_zero_stage(ctx, z, b));
     if (follow) {
         SWM_TRY(msm_twin_copy_stage(ctx, s, z, &b, follow, slot));
     } else {
-        const unsigned grid_n = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16);
-        SWM_LAUNCH(ctx, "msm_digits", msm_digits, dim3(grid_n), dim3(256), 0, reinterpret_cast<const Fr*>(d_scalars), n, mont, s.pl,
-                   b.digits, inf.mask, inf.first, b.big_count + 1 /* zeroed with the histogram */, s.dshard,
-                   tab.scalar_stride != 1 ? tab.blk_log : 31u, tab.scalar_stride != 1 ? tab.bstride : (size_t)0);
+        SWM_TRY(msm_digits_stage(ctx, s, b, d_scalars, n, mont, inf, tab));
         if (lead)  // what the follower takes: the arrays of this job's slot, ready once the bin sort has recorded `sorted`
             job->twin = {false, d_scalars, mont, s.lane, twin.tab2, b.hist, b.seg_start, b.seg_off, b.big_list, geom, ctx->sort_event[slot]};
         if (s.flat) SWM_TRY(msm_sort_flat(ctx, s, b, tab, n, lead ? &job->twin : nullptr));
@@ -2759,7 +2782,7 @@ int msm_enqueue(swm_ctx* ctx, int lane, const G1Affine* d_bases, const G1Affine*
     job->d_hist = b.hist;
     job->seg = s.SEG;
     job->d_status = b.big_count + 1;
-    job->d_entries = s.flat ? b.flat_off + s.flat_bins : b.bucket_off + s.pl.NB;  // entries the sort placed
+    job->d_entries = msm_entries_word(s, b);
     job->active = true;
     job->tail_pending = true;
     ctx->slot_busy[slot] = true;
@@ -3171,6 +3194,77 @@ int msm_run(swm_ctx* ctx, const G1Affine* d_bases, const G1Affine* d_bases28, co
     MsmJob job;
     SWM_TRY(msm_enqueue(ctx, -1, d_bases, d_bases28, d_scalars, n, mont, &job, inf, false, tab));
     return msm_finish(ctx, &job, result);
+}
+
+// ---------------------------------------------------------------------------------------------- sort self-test
+// One job up to and including msm_seg_order, through the functions msm_enqueue runs and in its order, on the context's stream;
+// then everything the stage left for the accumulation and the bucket stage is downloaded (include/swmarlin.h:
+// swm_selftest_msm_sort).  lane -1 as msm_run, lane 0 with a follower's table (a LEAD needs a lane: msm_twin_match).  The job takes
+// no result slot: it uses the scratch of the slot the next job will get, which must be free, and has synchronised when it returns.
+int msm_selftest_sort(swm_ctx* ctx, const void* d_scalars, size_t n, int mont, MsmInfMask inf, bool defer_tail, MsmTable tab,
+                      const MsmTable* tab2, MsmSortDump* out, bool run) {
+    if (n == 0 || n >= (1ull << 31)) return set_err(ctx, SWM_ERR_INVALID_ARG, "selftest_msm_sort: n must be in [1, 2^31)");
+    MsmShape s;
+    SWM_TRY(msm_shape(ctx, n, tab, tab2 ? 0 : -1, defer_tail, &s));
+    const MsmZeroLayout z = msm_zero_layout(s);
+    const MsmSortGeom geom{z.words, s.nseg_max, s.SEG, s.big_nseg, s.flat_bins};
+    MsmTwin twin;
+    if (tab2) {
+        twin.role = MsmTwin::LEAD;
+        twin.tab2 = *tab2;
+    }
+    bool lead = false;
+    (void)msm_twin_match(nullptr, s, geom, d_scalars, n, mont, inf, tab, twin, &lead);
+    out->flat = s.flat, out->te = s.te, out->lat = s.lat, out->quad = s.quad, out->raw = s.raw, out->interleave = msm_interleaves(s);
+    out->lead = lead;
+    out->pl = s.pl;
+    out->total = s.total, out->nseg_max = s.nseg_max;
+    out->SEG = s.SEG, out->big_nseg = s.big_nseg, out->log_g = s.log_g, out->flat_fb = s.flat_fb, out->flat_bins = s.flat_bins;
+    out->tstride = (uint32_t)tab.stride;
+    if (!run) return SWM_OK;
+    const int slot = ctx->next_slot;
+    if (ctx->slot_busy[slot] || ctx->msm_since_wait) return set_err(ctx, SWM_ERR_INTERNAL, "selftest_msm_sort: MSM jobs in flight");
+    MsmBuffers b;
+    SWM_TRY(msm_buffers(ctx, s, z, slot, false, &b));
+    // words the stage never writes read back as 0xFFFFFFFF
+    uint32_t* sorted2 = nullptr;
+    SWM_HIP(ctx, hipMemsetAsync(b.sorted, 0xFF, s.total * 4, ctx->stream));
+    SWM_HIP(ctx, hipMemsetAsync(b.seg_start, 0xFF, s.nseg_max * 12, ctx->stream));  // seg_start | seg_len | order
+    SWM_HIP(ctx, hipMemsetAsync(b.big_list, 0xFF, (size_t)s.pl.NB * 4, ctx->stream));
+    MsmTwinSrc src;
+    if (lead) {
+        SWM_TRY(scratch(ctx, "msmT.sorted", s.total * 4, (void**)&sorted2));  // (the buffer msm_sort_flat asks for)
+        SWM_HIP(ctx, hipMemsetAsync(sorted2, 0xFF, s.total * 4, ctx->stream));
+        if (!ctx->sort_event[slot]) SWM_HIP(ctx, hipEventCreateWithFlags(&ctx->sort_event[slot], hipEventDisableTiming));
+        src = {false, d_scalars, mont, s.lane, twin.tab2, b.hist, b.seg_start, b.seg_off, b.big_list, geom, ctx->sort_event[slot]};
+    }
+    SWM_TRY(msm_zero_stage(ctx, z, b));
+    SWM_TRY(msm_digits_stage(ctx, s, b, d_scalars, n, mont, inf, tab));
+    if (s.flat) SWM_TRY(msm_sort_flat(ctx, s, b, tab, n, lead ? &src : nullptr));
+    else SWM_TRY(msm_sort_windows(ctx, s, b, n));
+    SWM_TRY(msm_seg_order_stage(ctx, s, b));
+    const size_t NB = s.pl.NB;
+    auto down = [&](void* to, const void* from, size_t words) {
+        return to && words ? hipMemcpyAsync(to, from, words * 4, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+    };
+    std::vector<uint32_t> lens((size_t)(s.SEG + 1) * LEN_STRIDE);
+    SWM_HIP(ctx, down(out->hist, b.hist, NB));
+    SWM_HIP(ctx, down(out->bucket_off, b.bucket_off, NB));
+    SWM_HIP(ctx, down(out->seg_off, b.seg_off, NB));
+    SWM_HIP(ctx, down(out->sorted, b.sorted, s.total));
+    SWM_HIP(ctx, down(out->seg_start, b.seg_start, s.nseg_max));
+    SWM_HIP(ctx, down(out->seg_len, b.seg_len, s.nseg_max));
+    SWM_HIP(ctx, down(out->order, b.order, s.nseg_max));
+    SWM_HIP(ctx, down(out->big_list, b.big_list, NB));
+    if (lead) SWM_HIP(ctx, down(out->sorted2, sorted2, s.total));
+    SWM_HIP(ctx, down(lens.data(), b.len_hist, lens.size()));
+    SWM_HIP(ctx, down(out->status, b.big_count, 4));  // big_count | bad scalar | points that contribute nothing | live segments
+    SWM_HIP(ctx, down(&out->seg_bound, msm_seg_space(s, b), 1));
+    SWM_HIP(ctx, down(&out->entries, msm_entries_word(s, b), 1));
+    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (out->len_hist)
+        for (uint32_t i = 0; i <= s.SEG; i++) out->len_hist[i] = lens[(size_t)i * LEN_STRIDE];
+    return SWM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- point-layer self-test

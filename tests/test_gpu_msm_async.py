@@ -30,6 +30,7 @@ import sys
 import numpy as np
 import pytest
 
+from msm_sort_model import signed_digits, twin_map  # noqa: F401  (moved to the sort model; used and re-exported here)
 from oracle_lib import Oracle, golden, h2i, ints_to_limbs, limbs_to_ints, R
 from test_gpu_msm_schedules import FLAT_BIN_CAP, ROOT, Refs, buckets, equal, witness_mix
 
@@ -72,37 +73,6 @@ def bin_counts(sc, g):
     """entries per coarse bin of the ONE bucket set all windows of a flat job share"""
     bk = buckets(sc, g["nwin"])
     return np.bincount(bk[bk >= 0] >> g["flat_fb"], minlength=g["flat_bins"])
-
-
-def signed_digits(sc, nwin):
-    """buckets() with the signs: int64 [nwin, n], the digits of for_each_digit"""
-    sc = np.ascontiguousarray(sc, dtype=np.uint64)
-    base, extra = divmod(254, nwin)
-    out = np.empty((nwin, sc.shape[0]), dtype=np.int64)
-    carry = np.zeros(sc.shape[0], dtype=np.int64)
-    bit = 0
-    for w in range(nwin):
-        c = base + (1 if w < extra else 0)
-        limb, sh = divmod(bit, 64)
-        v = sc[:, limb] >> np.uint64(sh)
-        if sh + c > 64 and limb + 1 < 4:
-            v = v | (sc[:, limb + 1] << np.uint64(64 - sh))
-        d = (v & np.uint64((1 << c) - 1)).astype(np.int64) + carry
-        carry = (d > (1 << (c - 1))).astype(np.int64)
-        out[w] = d - (carry << c)
-        bit += c
-    return out
-
-
-def twin_map(e, tstride, dstride, doff):
-    """TwinOut::map of msm.hip on uint32 arrays, with the kernel's wrapped 32-bit arithmetic: dstride and doff are the wrapped
-    differences msm_sort_flat computes."""
-    e = np.asarray(e, dtype=np.uint32)
-    row = e & np.uint32(0x7FFFFFFF)
-    w = row // np.uint32(tstride)
-    with np.errstate(over="ignore"):
-        moved = row + w * np.uint32(dstride) + np.uint32(doff)
-    return (e & np.uint32(0x80000000)) | (moved & np.uint32(0x7FFFFFFF))
 
 
 def twin_deltas(lead, follow):

@@ -30,6 +30,7 @@ import sys
 import numpy as np
 import pytest
 
+from msm_sort_model import buckets  # noqa: F401  (the digit model lives there; this module and its importers use it from here)
 from oracle_lib import Oracle, golden, h2i, ints_to_limbs, limbs_to_ints, p64, R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -195,28 +196,6 @@ def witness_mix(n):
 def witness_262144(refs):
     st = witness_mix(262144)
     return st, refs.affine(refs.msm(st))
-
-
-def buckets(sc, nwin):
-    """The signed-digit recoding of msm.hip (for_each_digit) on the layout of msm_windows: int64 [nwin, n] with the bucket index
-    |digit| - 1 of every digit, -1 for a zero digit.  sc: (n, 4) uint64, standard form."""
-    sc = np.ascontiguousarray(sc, dtype=np.uint64)
-    base, extra = divmod(254, nwin)
-    out = np.empty((nwin, sc.shape[0]), dtype=np.int64)
-    carry = np.zeros(sc.shape[0], dtype=np.int64)
-    bit = 0
-    for w in range(nwin):
-        c = base + (1 if w < extra else 0)
-        limb, sh = divmod(bit, 64)
-        v = sc[:, limb] >> np.uint64(sh)
-        if sh + c > 64 and limb + 1 < 4:
-            v = v | (sc[:, limb + 1] << np.uint64(64 - sh))
-        d = (v & np.uint64((1 << c) - 1)).astype(np.int64) + carry
-        neg = d > (1 << (c - 1))
-        carry = neg.astype(np.int64)
-        out[w] = np.where(neg, (1 << c) - d, d) - 1
-        bit += c
-    return out
 
 
 def test_digit_model_matches_the_recoding():

@@ -13,11 +13,19 @@ Shapes, each the smallest that takes its path (the table's width follows the siz
   * 513 points on a set of their own (c = 11): a quad bucket stage, partial sums still 28-bit slots through the epilogue.
 Each test also holds its jobs to the stage kernel named above, through the context's per-kernel job counts.
 
+The occupancy ladders of tests/msm_sort_model.py — vectors whose buckets hold EXACTLY 1, 2, SEG - 1 .. 2 SEG + 1 entries, big_nseg
+and big_nseg + 1 segments, FLAT_WIDE_NS and one more, G - 1 .. 2 G + 1 segments for the lane group G of msm_big_bucket_sum, one
+bucket of negative digits only — run through whole MSMs in the four table regimes (quad; low-latency one lane, deferred and not;
+throughput).  tests/test_gpu_msm_sort.py holds the sort's arrays on these vectors to the model; here the three places that must
+agree on `ns > big_nseg` (the list, the fold of msm_big_bucket_sum, the walk of msm_bucket_reduce / _low / the quad form over a
+listed bucket's first partial sum only) and the fold's strided loop around ns = G have to add up to the oracle's point.
+
 There is no run-time switch back to 28-bit slots for one-lane jobs and so no child-process leg: that stage is no longer in the
 library."""
 import numpy as np
 import pytest
 
+import msm_sort_model as M
 from oracle_lib import Oracle, golden, h2i, ints_to_limbs
 from test_gpu_msm_te29 import HOLES, affine, scalars_for
 
@@ -104,3 +112,38 @@ def test_quad_tail_keeps_28_bit_slots(env):
         small.free()
     assert tails_run(ctx, before) == {"quad": 1, "low": 0, "te29": 0, "xyzz": 0}
     assert got == oracle_point(orc, b, sc)
+
+
+# regime -> (job of msm_sort_model.JOBS whose ladder it runs, defer_tail, the bucket-stage kernel it must take)
+LADDERS = {"quad": ("quad_513", None, "quad"), "low_latency_deferred": ("lat_2p15_offset", "on", "low"),
+           "low_latency": ("lat_2p15", "off", "te29"), "throughput": ("throughput", "off", "te29")}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("regime", list(LADDERS))
+def test_ladder_msm_equals_the_oracle(env, regime):
+    orc, ctx, bases, bh = env
+    name, defer, kernel = LADDERS[regime]
+    job = M.JOBS[name]
+    n, off = job["n"], job["offset"]
+    b = np.ascontiguousarray(bases[off:off + n])
+    shape = M.job_shape(name)
+    sc, rung = M.ladder(shape, n, 2980 + len(name), job["rungs"], skip=~b.any(axis=1))
+    model = M.Model(sc, shape, offset=off, skip=~b.any(axis=1))
+    targets = M.rung_targets(shape)
+    assert {k: int(model.count[v]) for k, v in rung.items()} == {k: targets[k] for k in job["rungs"]}
+    assert {rung["ns=big+1,first+1"]} <= model.big and rung["ns=big"] not in model.big
+    before = ctx.selftest_msm_tail_counts()
+    if defer is None:
+        small = ctx.srs_upload(b)
+        try:
+            got = affine(orc, ctx, ctx.msm_g1(small, sc))
+        finally:
+            small.free()
+    else:
+        jacs, _ = ctx.selftest_msm_jobs([bh], [sc], [(0, off, 0, n, None)], defer_tail=defer)
+        got = affine(orc, ctx, jacs[0])
+    want = {"quad": 0, "low": 0, "te29": 0, "xyzz": 0}
+    want[kernel] = 1
+    assert tails_run(ctx, before) == want
+    assert got == oracle_point(orc, b, sc), regime
