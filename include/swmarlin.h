@@ -1261,7 +1261,7 @@ int swm_selftest_fr_inv(const uint64_t *a_mont, uint64_t *out_mont, size_t n, un
  * spread9 is read by op 7 only. */
 int swm_selftest_fr29(swm_ctx *ctx, int op, const uint32_t *a9, const uint32_t *b9, const uint32_t *spread9, uint32_t *out9,
                       size_t n);
-/* Device self-test of the MSM's 28-bit point layer (csrc/fq28.cuh and the streamed forms of csrc/msm.hip), one GPU lane per
+/* Device self-test of the MSM's 28-bit point layer (csrc/fq28.cuh and the streamed forms of csrc/msm_points.cuh; the kernels: csrc/msm_selftest.hip), one GPU lane per
  * element (the quad ops: one quad of lanes per element), 256-lane workgroups, on host buffers.  Operands and results are RAW slots
  * of the 28-bit domain: a, b, out hold n x 4 x 6 uint64 — the in-memory G1XYZZ of the bucket stage, four integers < 2^384 whose
  * value is a field element times 2^392 (XYZZ: x, y, zz, zzz; twisted Edwards: X, Y, T, Z) — so the caller chooses the
@@ -1341,7 +1341,7 @@ int swm_selftest_spmv_plan(swm_ctx *ctx, const uint32_t *rowptr, const uint32_t 
 int swm_selftest_msm_jobs(swm_ctx *ctx, const swm_bases *const *sets, size_t nsets, const uint64_t *scalars, const size_t *vec_off,
                           size_t nvec, int scalars_montgomery, const uint64_t *jobs, size_t k, int defer_tail, size_t pipe_min,
                           uint64_t *out_jac, uint64_t *twins);
-/* Device self-test of the SORT STAGE of the G1 MSM (csrc/msm.hip): one job is taken through the host functions msm_enqueue runs, in
+/* Device self-test of the SORT STAGE of the G1 MSM (csrc/msm_sort.hip, driven by csrc/msm.hip): one job is taken through the host functions msm_enqueue runs, in
  * its order — shape, zeroed block, buffers, digits, the flat or the per-window sort with its segment descriptors, the ordering of
  * the segments by length — on the context's stream, and stops there: nothing is accumulated.  Before the sort (here only) the job's
  * sorted, seg_start, seg_len, order and big_list arrays, and the second sorted array of a lead, are filled with bytes 0xFF, so that

@@ -1,6 +1,6 @@
 // capi.hip — the extern "C" boundary of libswmarlin.so (declared in include/swmarlin.h).
 // Host-side plumbing only: argument checks, staging of host buffers into HBM, status codes.  The kernels live in
-// msm.hip / ntt.hip / vec.hip.  Nothing here falls back to a CPU implementation: without a usable gfx950 device
+// msm.hip (and its units) / ntt.hip / vec.hip.  Nothing here falls back to a CPU implementation: without a usable gfx950 device
 // swm_init fails with SWM_ERR_NO_DEVICE and every compute entry point needs a context.
 #include <dlfcn.h>
 #include <stdarg.h>

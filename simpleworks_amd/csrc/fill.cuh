@@ -1,4 +1,4 @@
-// fill.cuh — device memory cleared by a kernel of this library (shared by devops.cuh and msm.hip)
+// fill.cuh — device memory cleared by a kernel of this library (shared by devops.cuh and msm.hip, the MSM's driver)
 #pragma once
 #include <stdint.h>
 #include <algorithm>

@@ -9,7 +9,7 @@
 //
 // Representation.  value = sum l[i] 2^(28 i); Montgomery radix R' = 2^392 (NOT the 2^384 of the memory format: inputs
 // are pre-scaled by 2^8 once, outputs are scaled back with one multiplication per coordinate).
-// Bounds (checked case by case at the call sites, see g1_28 in msm.hip):
+// Bounds (checked case by case at the call sites, see madd28 and the streamed forms in msm_points.cuh):
 //   N  "normalised": limbs < 2^28 (top limb < 2^15), value < 2p         — what mul28 returns
 //   D  "lazy":       limbs < 2^30,                    value < 128 p      — what mul28 accepts for BOTH operands:
 //        column sum <= 14 * 2^60 + 14 * 2^56 + 2^37 < 2^64;  a b / 2^392 < 2^14 p^2 / 2^392 < p / 2  =>  result < 1.5 p

@@ -325,7 +325,7 @@ __device__ __forceinline__ Fq29 te29_quad_from_row(const G1TE* __restrict__ rp, 
 
 // ------------------------------------------------------------------------------------------------ the general addition (bucket stage)
 // A point at rest in MEMORY (a partial sum in HBM, an LDS slot of the bucket stage): X | Y | T | Z, thirteen limbs each, unpacked —
-// 4 x 13 x 4 B = 208 B, thirteen 128-bit words, the stride of the bucket stage's padded 28-bit slot (msm.hip RedSlot), so the
+// 4 x 13 x 4 B = 208 B, thirteen 128-bit words, the stride of the bucket stage's padded 28-bit slot (msm_points.cuh RedSlot), so the
 // LDS budget and the bank layout of its 128-bit accesses are those of the 28-bit form; nothing is packed or unpacked on the way.
 // A coordinate is 52 bytes and starts on a 16-byte boundary only every fourth time, so the one-lane forms move a point as two
 // runs of whole 128-bit words: words 0 .. 27 (X, Y and the first two limbs of T) and words 28 .. 51 (the rest of T, and Z).

@@ -1,4 +1,6 @@
-// msm.h — internal interface of the G1 MSM (msm.hip): synchronous and enqueue/finish forms.
+// msm.h — internal interface of the G1 MSM: synchronous and enqueue/finish forms (the driver, msm.hip), base sets and tables
+// (msm_table.hip), window layouts (msm_sort.hip), the point-layer self-test (msm_selftest.hip).  What those units share among
+// themselves is msm_stages.h.
 #pragma once
 #include "context.h"
 #include "g1.cuh"
@@ -66,7 +68,7 @@ int msm_table_build_te(swm_ctx* ctx, const G1Affine* d_points, size_t n, unsigne
 int msm_normalize_run(swm_ctx* ctx, const G1XYZZ* in, size_t n, Fq* pref, G1Affine* out);
 // *ok = every point is the identity (0, 0) or lies on the curve and in the prime-order subgroup ([r]P = O)
 int msm_subgroup_check(swm_ctx* ctx, const G1Affine* d_points, size_t n, bool* ok);
-// scaled copy + the best table that fits for a resident base set (see msm.hip); frees nothing of the caller's
+// scaled copy + the best table that fits for a resident base set (see msm_table.hip); frees nothing of the caller's
 int msm_install_bases(swm_ctx* ctx, const G1Affine* d_points, size_t n, bool in_subgroup, G1Affine** d28, G1TE** te, unsigned* c,
                       uint32_t* d_inf_mask = nullptr);
 // HBM left for a table of `bytes` bytes? (hipMemGetInfo, keeping a quarter of the free memory for the prover's temporaries)
@@ -91,7 +93,7 @@ struct MsmTwin {
     MsmTable tab2;           // LEAD: the table (with the offset) of the job that follows
     MsmJob* lead = nullptr;  // FOLLOW: the job whose sort this one takes over
 };
-// the geometry of a job's sorted array and descriptors (msm.hip: MsmShape, MsmZeroLayout): a follower takes the lead's arrays
+// the geometry of a job's sorted array and descriptors (msm_stages.h: MsmShape, MsmZeroLayout): a follower takes the lead's arrays
 // only when its own geometry is the same
 struct MsmSortGeom {
     size_t zero_words = 0, nseg_max = 0;
@@ -182,7 +184,7 @@ struct MsmSortDump {
 // tab2: the table (with its offset) of a follower, or null; run = false: the shape fields alone, nothing is launched
 int msm_selftest_sort(swm_ctx* ctx, const void* d_scalars, size_t n, int mont, MsmInfMask inf, bool defer_tail, MsmTable tab,
                       const MsmTable* tab2, MsmSortDump* out, bool run);
-// One op of the point-layer self-test (msm.hip, "point-layer self-test"; include/swmarlin.h: swm_selftest_p28) on n elements of
+// One op of the point-layer self-test (msm_selftest.hip; include/swmarlin.h: swm_selftest_p28) on n elements of
 // device buffers: d_jac (optional) receives the Weierstrass image of every twisted Edwards result, d_pref is msm_te_convert's
 // scratch (n field elements), d_status one word per element (zeroed by the caller).
 int selftest_p28_run(swm_ctx* ctx, int op, const void* da, const void* db, const uint32_t* d_flags, void* d_out, void* d_jac,

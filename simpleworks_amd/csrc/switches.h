@@ -72,7 +72,7 @@ struct SwitchDecl {
     Switch id; const char* name; SwKind kind; long def, lo, hi; SwClass cls; SwWhen when;
 };
 constexpr SwitchDecl SWITCHES[] = {
-    // MSM (msm.hip)
+    // MSM (msm.hip and its units: msm_sort.hip, msm_table.hip, msm_stages.hip)
     {SW_MSM_TABLE_C, "SWM_MSM_TABLE_C", K_OPT, 0, 8, 22, C_PATH, W_ONCE},       // one table width for every base set; 0: the width rule decides
     {SW_MSM_TE, "SWM_MSM_TE", K_INT, 1, 0, 1, C_PATH, W_ONCE},                  // 0: XYZZ tables everywhere (the form of sets outside the subgroup)
     {SW_MSM_NO_TABLE, "SWM_MSM_NO_TABLE", K_FLAG, 0, 0, 1, C_PATH, W_ONCE},     // the per-window schedule for every set (what table-less sets run)

@@ -1,4 +1,4 @@
-"""A digit model of the MSM's sort stage (csrc/msm.hip: msm_digits, msm_flat_partition / msm_flat_bin_sort or msm_hist / msm_scan_* /
+"""A digit model of the MSM's sort stage (csrc/msm_sort.hip: msm_digits, msm_flat_partition / msm_flat_bin_sort or msm_hist / msm_scan_* /
 msm_seg_desc / msm_scatter, msm_seg_order) in plain numpy and Python integers, a checker that holds the arrays the stage leaves on
 the device (swm_selftest_msm_sort) to it, and scalar vectors whose buckets sit exactly on the entry counts the stage branches on.
 No device, no library.
@@ -15,7 +15,7 @@ big_list, the order of the segments inside one length class, where a bucket's en
 import numpy as np
 
 R = 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001   # the scalar field of BLS12-377
-FLAT_WIDE_NS = 16     # msm.hip: a bucket with more segments is written by the whole workgroup of msm_flat_bin_sort
+FLAT_WIDE_NS = 16     # msm_sort.hip: a bucket with more segments is written by the whole workgroup of msm_flat_bin_sort
 UNWRITTEN = 0xFFFFFFFF
 
 
@@ -27,7 +27,7 @@ def window_widths(nwin):
 
 
 def signed_digits(sc, nwin):
-    """The signed-digit recoding of msm.hip (for_each_digit) on the layout of msm_windows: int64 [nwin, n], digit w of scalar i.
+    """The signed-digit recoding of msm_sort.hip (for_each_digit) on the layout of msm_windows: int64 [nwin, n], digit w of scalar i.
     sc: (n, 4) uint64, standard form."""
     sc = np.ascontiguousarray(sc, dtype=np.uint64)
     out = np.empty((nwin, sc.shape[0]), dtype=np.int64)
@@ -65,7 +65,7 @@ def per_window_c(n):
 
 
 def twin_map(e, tstride, dstride, doff):
-    """TwinOut::map of msm.hip on uint32 arrays, with the kernel's wrapped 32-bit arithmetic: dstride and doff are the wrapped
+    """TwinOut::map of msm_sort.hip on uint32 arrays, with the kernel's wrapped 32-bit arithmetic: dstride and doff are the wrapped
     differences msm_sort_flat computes."""
     e = np.asarray(e, dtype=np.uint32)
     row = e & np.uint32(0x7FFFFFFF)

@@ -37,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_BASES = 393217                     # the first size on the c = 16 plan of msm_plan: the largest MSM below
 N_RAGGED = 262144 + 8192 * 3 + 1     # last partition tile: one digit; last 65536-digit sort tile: not full
 CUTS = (0, 100003, 131072, 262143, 262144, 262145, N_RAGGED, N_BASES)   # the uniform reference is computed per chunk
-# constants of csrc/msm.hip that the preconditions are stated in
+# constants of csrc/msm_sort.hip and csrc/msm_stages.h that the preconditions are stated in
 BIN_CAP, FLAT_BIN_CAP, FLAT_WIDE_NS, FLAT_WIDE_Q = 24576, 32768, 16, 32
 TWO_LEVEL_KERNELS = ("msm_bin_check", "msm_partition", "msm_bin_sort")
 PER_WINDOW_KERNELS = ("msm_hist", "msm_scatter", "msm_accumulate", "msm_big_bucket_sum", "msm_bucket_reduce")

@@ -1,4 +1,4 @@
-"""Whole MSMs whose bucket stage adds in the 29-bit domain (csrc/fq29.cuh te29_slot_add; msm.hip FormTE29, MsmShape::raw) against the
+"""Whole MSMs whose bucket stage adds in the 29-bit domain (csrc/fq29.cuh te29_slot_add; msm_points.cuh FormTE29, msm_stages.h MsmShape::raw) against the
 CPU oracle, on subgroup bases [tau^i]G with the scalar vectors of tests/test_gpu_msm_te29.py (0, 1, r - 1, extreme digits of every
 table width, scalars repeated 1, 2, 128 and 300 times, identity bases under some of them) plus one scalar repeated 4173 times: with
 the 128-entry segments of a large job that is a bucket of 33 segments, more than BIG_NSEG = 16, which msm_big_bucket_sum folds

@@ -1,4 +1,4 @@
-"""The MSM's 28-bit point layer (csrc/fq28.cuh, the streamed forms and madd28 / msm_te_convert of csrc/msm.hip) routine by routine on
+"""The MSM's 28-bit point layer (csrc/fq28.cuh, the streamed forms and madd28 of csrc/msm_points.cuh, msm_te_convert of csrc/msm_table.hip) routine by routine on
 the device, through swm_selftest_p28, on operands chosen limb for limb.
 
 Reference: the group law on Python integers (pyref.bls12_377: g1_add, g1_neg, fq_sqrt) — never the 32-bit device adders, never an

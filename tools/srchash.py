@@ -8,8 +8,8 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "simpleworks_amd", "csrc")
 INC = os.path.join(ROOT, "include")
-# translation unit of each measured kernel (launch geometry and kernels live in the same file)
-UNITS = {"msm_accumulate": "msm.hip", "ntt_pass": "ntt.hip", "spmv": "spmv.hip"}
+# translation unit of each measured kernel (the kernel and its launch live in the same file)
+UNITS = {"msm_accumulate": "msm_stages.hip", "ntt_pass": "ntt.hip", "spmv": "spmv.hip"}
 
 
 def include_closure(unit):
