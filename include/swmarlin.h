@@ -1231,7 +1231,7 @@ int swm_selftest_witness_stage(swm_ctx *ctx, size_t bytes);
 int swm_selftest_mul(swm_ctx *ctx, int which, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);
 /* out[i] = jacobian(a[i] (+) b[i]) with a, b affine (n x 12 limbs): exercises the mixed/XYZZ adders incl. doubling. */
 int swm_selftest_g1_add(swm_ctx *ctx, const uint64_t *a_xy, const uint64_t *b_xy, uint64_t *out_jac, size_t n);
-/* The point kernels of the uncompressed key forms (csrc/marlin.hip), one GPU lane per point, on host buffers.  Ops:
+/* The point kernels of the uncompressed key forms (csrc/marlin_keycodec.hip), one GPU lane per point, on host buffers.  Ops:
  *   0 g1_encode_uncompressed_kernel: in = n x 12 uint64 (affine Montgomery x, y; (0, 0) = the identity), out = n x 96 bytes
  *   1 g1_decode_uncompressed_kernel<checked>: in = n x 96 bytes, out = n x 12 uint64; *bad = the OR over all points of
  *     1 (flags 0xC0 or a coordinate >= q), 2 (not on the curve), 4 (not in the prime-order subgroup); a refused point reads (0, 0)

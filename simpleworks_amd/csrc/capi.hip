@@ -988,7 +988,7 @@ int swm_selftest_mul_throughput(swm_ctx* ctx, int which, size_t threads, int ite
     (void)hipEventDestroy(e1);
     return SWM_OK;
 }
-// One round of asynchronous MSM jobs, enqueued the way commit_enqueue (marlin.hip) enqueues the commitments of a prover round:
+// One round of asynchronous MSM jobs, enqueued the way commit_enqueue (marlin_commit.hip) enqueues the commitments of a prover round:
 // lanes from a running counter that a follower hands back, the twin roles of msm.h, then msm_flush_tails and msm_finish_many.
 int swm_selftest_msm_jobs(swm_ctx* ctx, const swm_bases* const* sets, size_t nsets, const uint64_t* scalars, const size_t* vec_off,
                           size_t nvec, int scalars_montgomery, const uint64_t* jobs, size_t k, int defer_tail, size_t pipe_min,

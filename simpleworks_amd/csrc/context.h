@@ -57,7 +57,7 @@ struct swm_ctx {
     hipEvent_t fork_event = nullptr;
     void* pinned = nullptr;
     void* pinned_dev = nullptr;  // device address of `pinned`
-    void* h2d_stage = nullptr;   // small pinned staging area for the witness upload of small proofs (marlin.hip, upload_small)
+    void* h2d_stage = nullptr;   // small pinned staging area for the witness upload of small proofs (marlin_prove.hip, upload_small)
     size_t h2d_stage_used = 0;
     // device source of the witness for the NEXT proof on this context (upload_witness copies from it instead of from
     // swm_r1cs::witness); set and cleared by prove_device_witness (witness_host.h) around its call of the prover, null everywhere else

@@ -192,6 +192,18 @@ inline DVec dv_ntt_from(swm_ctx* ctx, const Fr* src, size_t len, unsigned log_n,
     return v;
 }
 
+// u_k = p0 + c^k p1 + c^2k p2 (k = 0, 1, 2; c = w_4, c^2 = -1; what ntt_cosets_inv leaves) -> the three blocks p0, p1, p2
+struct Cosets3 {
+    Fr p0, p1, p2;
+};
+__device__ __forceinline__ Cosets3 cosets3_solve(const Fr& u0, const Fr& u1, const Fr& u2, const Fr& iota, const Fr& half) {
+    const Fr p1 = fp_mul(fp_sub(u0, u2), half);
+    const Fr e = fp_mul(fp_add(u0, u2), half);  // p0 + p2
+    const Fr d = fp_sub(u1, fp_mul(iota, p1));  // p0 - p2
+    return {fp_mul(fp_add(e, d), half), p1, fp_mul(fp_sub(e, d), half)};
+}
+inline Fr fr_half() { return fp_inv(fp_from_u64<Fr>(2)); }
+
 // ------------------------------------------------------------------------------------------------ suffix recurrence
 // In place: a[k] <- a[k] + z * a[k + m] (k descending), i.e. a[k] = sum_{i >= 0} z^i a_old[k + i m].
 // m = 1, z = point: synthetic division (quotient of p / (X - z) = a[1..], p(z) = a[0]).

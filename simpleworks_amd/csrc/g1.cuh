@@ -192,7 +192,7 @@ SWM_HD bool g1_is_on_curve(const G1Affine& p) {
 }
 
 // ------------------------------------------------------------------------------------------------ square root in Fq
-// (shared by the device point decoders: g1_decompress_kernel in marlin.hip, the batch verifier's point check in verify.hip)
+// (shared by the device point decoders: g1_decompress_kernel in marlin_keycodec.hip, the batch verifier's point check in verify.hip)
 struct FqSqrtConsts {
     static constexpr uint32_t HALF[12] = SWM_FQ_PM1_HALF;
     static constexpr uint32_t T[12] = SWM_FQ_TS_T;
@@ -230,7 +230,7 @@ __device__ bool fq_sqrt_dev(const Fq& a, Fq* out) {
 }
 
 // ------------------------------------------------------------------------------------------------ point decoding
-// The two tests every device point decoder shares (g1_decompress_kernel and the g1_decode_uncompressed_kernel pair in marlin.hip,
+// The two tests every device point decoder shares (g1_decompress_kernel and the g1_decode_uncompressed_kernel pair in marlin_keycodec.hip,
 // verify_points_kernel in verify.hip), and the status bits they report.
 enum : uint32_t { G1_BAD_ENCODING = 1, G1_OFF_CURVE = 2, G1_OFF_SUBGROUP = 4 };
 // a < q for 12 words in STANDARD form (Fp::deserialize refuses anything else, in every mode of ark-serialize)

@@ -1,6 +1,6 @@
 // pk_codec.h — the part of the proving-key codec (ark-serialize layout of ark-marlin's IndexProverKey) that needs no
 // GPU: the verifying key, the index info, the three matrices and the SHAPES of the derived tables in front of the committer
-// key.  Shared by marlin.hip (pk_deserialize continues with the committer key, whose points are decompressed and checked on
+// key.  Shared by marlin_keycodec.hip (pk_deserialize continues with the committer key, whose points are decompressed and checked on
 // the device) and by the sanitizer harness tests/native/host_fuzz.cpp.  Every malformed input is a MarlinError.
 #pragma once
 #include <algorithm>

@@ -81,14 +81,14 @@ constexpr SwitchDecl SWITCHES[] = {
     {SW_MSM_TWIN, "SWM_MSM_TWIN", K_INT, 1, 0, 1, C_PATH, W_ONCE},              // 0: the shifted commitment of a pair sorts for itself
     // points below which a job's bucket stage joins its round's joint launch; -1 (outside the range): not set, the table form's own bound
     {SW_MSM_BATCH_BELOW, "SWM_MSM_BATCH_BELOW", K_OPT, -1, 0, 1L << 31, C_PATH, W_ONCE},
-    // prover (marlin.hip, ntt.hip, devops.cuh)
+    // prover (marlin_prove.hip, ntt.hip, devops.cuh)
     {SW_PROVE_ONE_STREAM_LOG, "SWM_PROVE_ONE_STREAM_LOG", K_INT, 19, 0, 47, C_PATH, W_ONCE},  // proofs below 2^this constraints: one stream per lane
     {SW_MASK_PIECES, "SWM_MASK_PIECES", K_INT, 3, 1, 3, C_PATH, W_ONCE},        // caller-owned generator: the mask commitment in this many pieces
     {SW_NTT_LAZY, "SWM_NTT_LAZY", K_INT, 1, 0, 1, C_PATH, W_ONCE},              // 0: the 8 x 32-bit transform instead of the 9 x 29-bit lazy one
     {SW_NTT_PASS_TABLES, "SWM_NTT_PASS_TABLES", K_INT, 1, 0, 1, C_PATH, W_ONCE},  // 0: twiddles from the two-level tables
     {SW_RALPHA_TRANSFORMS, "SWM_RALPHA_TRANSFORMS", K_FLAG, 0, 0, 1, C_PATH, W_LIVE},  // r(alpha, X) by two transforms (the closed form's 2^-231 case)
     {SW_SAMPLE_TIGHT, "SWM_SAMPLE_TIGHT", K_FLAG, 0, 0, 1, C_PATH, W_LIVE},     // the bulk sampler draws no spare candidates: its retry branch runs
-    // one proof over several ranks (marlin.hip, capi.hip)
+    // one proof over several ranks (marlin_commit.hip, marlin_prove.hip, capi.hip)
     {SW_SHARD_FORCE, "SWM_SHARD_FORCE", K_FLAG, 0, 0, 1, C_SHARDING, W_LIVE},   // test hook: the exchange path with a world of one
     {SW_SHARD_RANGE, "SWM_SHARD_RANGE", K_FLAG, 0, 0, 1, C_SHARDING, W_LIVE},   // commitments split by point range
     {SW_SHARD_BUCKETS, "SWM_SHARD_BUCKETS", K_FLAG, 0, 0, 1, C_SHARDING, W_LIVE},  // ... by bucket range

@@ -39,7 +39,7 @@ inline int prove_device_witness(swm_ctx* ctx, const swm_pk* pk, size_t num_insta
     return swm_generate_proof_ex(ctx, pk, &cs, rng, flags, proof_out, cap, len);
 }
 
-// Whether the prover would take a system of these counts under `pk` (marlin.hip: what prove_shape compares, SWM_ERR_MISMATCH
+// Whether the prover would take a system of these counts under `pk` (marlin_prove.hip: what prove_shape compares, SWM_ERR_MISMATCH
 // otherwise).  For a unit that changes state before it proves: it asks first.
 bool pk_takes_shape(const swm_pk* pk, size_t num_instance, size_t num_witness, size_t num_constraints);
 

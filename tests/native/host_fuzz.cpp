@@ -28,7 +28,7 @@ void drain_streams(swm_ctx*) {}
 using namespace swm;
 #include "host/host_abi.inc"
 
-// the host part of swm_pk_deserialize (marlin.hip: pk_deserialize up to the committer key) under the library's guard
+// the host part of swm_pk_deserialize (marlin_keycodec.hip: pk_deserialize up to the committer key) under the library's guard
 static int pk_prefix_status(const uint8_t* bytes, size_t len, size_t* consumed) {
     swm_ctx* none = nullptr;
     SWM_GUARD(none, {

@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the prover's pieces that stopped computing what is already known (csrc/devops.cuh, csrc/marlin.hip):
+"""GPU tests (-m gpu) of the prover's pieces that stopped computing what is already known (csrc/devops.cuh, csrc/marlin_prove.hip):
 the division by (X - z) out of place (no copy in front, the source left alone, the buffer's tail cleared), polynomial
 evaluation at the tile edges with extremal coefficients and points (the kernels every proof's evaluations and the openings'
 values come from), and whole proofs over the shapes at which round 1 (no transform of x), round 3 (zero on

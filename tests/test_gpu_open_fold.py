@@ -1,4 +1,4 @@
-"""The opening round's folded witnesses (marlin.hip, open_combinations / SWM_OPEN_FOLD): under a committer key whose shifted powers
+"""The opening round's folded witnesses (marlin_prove.hip, open_combinations / SWM_OPEN_FOLD): under a committer key whose shifted powers
 are a sub-range of its powers, a query point's shifted witness is added into the plain quotient at its offset and the point
 costs ONE MSM job instead of two.  The proof bytes must not move, the job count must drop by exactly one per query point, and a
 key with shifted powers on a table of their own must keep the two-job path.

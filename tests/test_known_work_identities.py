@@ -1,4 +1,4 @@
-"""The field identities the prover relies on where it does not compute a value it already has (csrc/marlin.hip: round1_polys,
+"""The field identities the prover relies on where it does not compute a value it already has (csrc/marlin_prove.hip: round1_polys,
 round3_polys, round3_a_minus_bf), on Python integers and the model's own index (oracle/pyref), no GPU:
 
 * round 1: interpolation over H is linear and deg x < |X| <= |H|, so interp_H(z) - x = interp_H(z - x on H): x is never

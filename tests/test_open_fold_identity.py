@@ -1,4 +1,4 @@
-"""Why the opening round may fold a shifted witness into the plain one (marlin.hip, open_combinations): under an SRS of the
+"""Why the opening round may fold a shifted witness into the plain one (marlin_prove.hip, open_combinations): under an SRS of the
 circuit's own degree the shifted powers are the top of the powers, so
     MSM(powers, wq) + MSM(powers from off on, k sq) = MSM(powers, wq + X^off k sq),      off = max_degree - degree bound,
 the scalars adding in Fr because G1 has order r.  CPU only: the Python model proves the synthetic circuit at 2^8, its pc_open calls

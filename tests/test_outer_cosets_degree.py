@@ -1,4 +1,4 @@
-"""The degree bound behind round 2 on three cosets of H (marlin.hip, SWM_OUTER_COSETS): q_1 - mask, interpolated from the 4|H|
+"""The degree bound behind round 2 on three cosets of H (marlin_prove.hip, SWM_OUTER_COSETS): q_1 - mask, interpolated from the 4|H|
 product domain the way the model does it, has no coefficient at index >= 3|H|, so its values on the cosets 0, 1, 2 of H determine
 it.  CPU only: round 1 and round 2 of the Python model (oracle/pyref/marlin.py prove) with random challenges and blinding values
 in place of the commitments and the transcript, on circuits of 2^8 ... 2^12 constraints, |X| = 4 and |X| = 8."""
