@@ -233,6 +233,14 @@ ABI = {
                                          + [ctypes.c_void_p] * 5),
     "swm_account_update_prove_at": (_int, [_vp, _vp, _vp, _vp, ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_void_p,
                                            ctypes.c_uint64, _vp, ctypes.c_uint, ctypes.c_void_p, _sz] + [ctypes.c_void_p] * 5),
+    "swm_pedersen_account_update_circuit_shape": (_int, [_sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "swm_pedersen_account_update_circuit_create": (_int, [_vp, _vp, _vp, _sz, ctypes.POINTER(_vp)]),
+    "swm_pedersen_account_update_circuit_destroy": (None, [_vp, _vp]),
+    "swm_pedersen_account_update_witness_at": (_int, [_vp, _vp, _vp] + [ctypes.c_void_p] * 5 + [_sz] + [ctypes.c_void_p] * 5),
+    "swm_pedersen_account_update_prove_many_at": (_int, [_vp, _vp, _vp, _vp] + [ctypes.c_void_p] * 5
+                                                  + [_sz, _vp, ctypes.c_uint, ctypes.c_void_p, _sz] + [ctypes.c_void_p] * 5),
+    "swm_pedersen_account_update_prove_at": (_int, [_vp, _vp, _vp, _vp, ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_void_p,
+                                                    ctypes.c_uint64, _vp, ctypes.c_uint, ctypes.c_void_p, _sz] + [ctypes.c_void_p] * 5),
     "swm_rollup_circuit_shape": (_int, [_sz, _sz, ctypes.c_uint64, _sz, _int, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz),
                                          ctypes.POINTER(_sz)]),
     "swm_pedersen_rollup_circuit_shape": (_int, [_sz, _int, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
@@ -1229,7 +1237,8 @@ class Context:
         if self.h and handle:
             self.lib.swm_account_update_circuit_destroy(self.h, handle)
 
-    def account_update_witness_at(self, handle, tree_handle, num_witness, accounts, ids, kinds, keys_xy, balances, guard=0):
+    def account_update_witness_at(self, handle, tree_handle, num_witness, accounts, ids, kinds, keys_xy, balances, guard=0,
+                                  _entry="swm_account_update_witness_at"):
         """accounts uint8 [2^L, 72] (all-zero = no account), ids uint8 [count], kinds uint8 [count] (0 = set balance, 1 = register),
         keys_xy uint8 [count, 64], balances uint64 [count] -> (witness uint64 [count * num_witness + guard, 4] Montgomery limbs, the
         `guard` elements past the end filled with 0xFF bytes before the call, accounts after the block, old roots uint8 [count, 32],
@@ -1245,11 +1254,26 @@ class Context:
         witness = np.full((n * num_witness + guard, 4), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
         old, new = np.empty((n, 32), dtype=np.uint8), np.empty((n, 32), dtype=np.uint8)
         flags, status = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32)
-        self._check(self.lib.swm_account_update_witness_at(self.h, handle, tree_handle, acc.ctypes.data, i.ctypes.data, k.ctypes.data,
-                                                           keys.ctypes.data, b.ctypes.data, n, witness.ctypes.data, old.ctypes.data,
-                                                           new.ctypes.data, flags.ctypes.data, status.ctypes.data),
-                    "swm_account_update_witness_at")
+        self._check(getattr(self.lib, _entry)(self.h, handle, tree_handle, acc.ctypes.data, i.ctypes.data, k.ctypes.data, keys.ctypes.data,
+                                              b.ctypes.data, n, witness.ctypes.data, old.ctypes.data, new.ctypes.data, flags.ctypes.data,
+                                              status.ctypes.data), _entry)
         return witness, acc, old, new, flags, status
+
+    # ---- The same over the Pedersen account tree (simpleworks_amd/ledger.py, PedersenAccountUpdateCircuit, is the mirror)
+    def pedersen_account_update_circuit_create(self, leaf_handle, inner_handle, height):
+        h = _vp()
+        self._check(self.lib.swm_pedersen_account_update_circuit_create(self.h, leaf_handle, inner_handle, height, ctypes.byref(h)),
+                    "swm_pedersen_account_update_circuit_create")
+        return h
+
+    def pedersen_account_update_circuit_destroy(self, handle):
+        if self.h and handle:
+            self.lib.swm_pedersen_account_update_circuit_destroy(self.h, handle)
+
+    def pedersen_account_update_witness_at(self, handle, tree_handle, num_witness, accounts, ids, kinds, keys_xy, balances, guard=0):
+        """account_update_witness_at's arguments and results against a resident Pedersen tree (a hash.DeviceMerkleTree's handle)."""
+        return self.account_update_witness_at(handle, tree_handle, num_witness, accounts, ids, kinds, keys_xy, balances, guard,
+                                              "swm_pedersen_account_update_witness_at")
 
     # ---- Transfer circuit witness over the Pedersen account tree (simpleworks_amd/ledger.py, PedersenTransferCircuit, is the mirror)
     def pedersen_transfer_circuit_create(self, schnorr_handle, leaf_handle, inner_handle, height):

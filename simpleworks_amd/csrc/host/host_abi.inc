@@ -18,6 +18,7 @@
 #include "pedersen_transfer_shape.h"
 #include "rollup_shape.h"
 #include "account_update_shape.h"
+#include "pedersen_account_update_shape.h"
 #include "program_shape.h"
 // (SWM_GUARD: host/host_handles.h)
 
@@ -411,6 +412,22 @@ int swm_account_update_circuit_shape(size_t full_rounds, size_t partial_rounds, 
                        "alpha 2 .. %llu, %zu <= height <= %zu)",
                        full_rounds, partial_rounds, (unsigned long long)alpha, height, (size_t)PC_MAX_ROUNDS, (unsigned long long)PC_MAX_ALPHA,
                        (size_t)PY_MIN_HEIGHT, (size_t)PY_MAX_HEIGHT);
+    *num_instance = s.num_instance;
+    *num_witness = s.num_witness;
+    *num_constraints = s.num_constraints;
+    return SWM_OK;
+}
+
+// The account-update circuit's shape over a Pedersen account tree (pedersen_account_update_shape.h; the layout is
+// build_pedersen_account_update's)
+int swm_pedersen_account_update_circuit_shape(size_t height, size_t* num_instance, size_t* num_witness, size_t* num_constraints) {
+    swm_ctx* none = nullptr;
+    if (!num_instance || !num_witness || !num_constraints)
+        return set_err(none, SWM_ERR_INVALID_ARG, "pedersen_account_update_circuit_shape: NULL output");
+    PedersenAccountUpdateShape s;
+    if (!pedersen_account_update_shape(height, &s))
+        return set_err(none, SWM_ERR_INVALID_ARG, "pedersen_account_update_circuit_shape: height %zu (%zu <= height <= %zu)", height,
+                       (size_t)PP_MIN_HEIGHT, (size_t)PP_MAX_HEIGHT);
     *num_instance = s.num_instance;
     *num_witness = s.num_witness;
     *num_constraints = s.num_constraints;

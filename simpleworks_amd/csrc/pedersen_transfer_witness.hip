@@ -211,6 +211,14 @@ __global__ void __launch_bounds__(PT_LANES) pedersen_transfer_advance_kernel(con
 
 static const EdRow* pt_rows(const swm_pedersen* p) { return reinterpret_cast<const EdRow*>(p->d_table); }
 
+int pedersen_transfer_check_run(swm_ctx* ctx, const swm_pedersen* leaf, const uint32_t* d_nodes, const uint8_t* d_accounts, unsigned n_leaves,
+                                uint32_t* d_verdict) {
+    const unsigned lanes = lanes_for(n_leaves);
+    SWM_LAUNCH(ctx, "pedersen_transfer_check", pedersen_transfer_check_kernel, dim3((unsigned)(((size_t)n_leaves * lanes + 255) / 256)), dim3(256),
+               0, pt_rows(leaf), leaf->num_windows, d_nodes, d_accounts, n_leaves, lanes, fp_from_u64<Fr>(2 * ED_D), d_verdict);
+    return SWM_OK;
+}
+
 // "ptransfer.aux" for n transfers: every piece a multiple of 8 bytes but the last two
 static size_t pt_aux_bytes(size_t n, size_t levels) {
     return 64 * n + 4 * (4 * n * (levels + 1) * 8 + 2 * n * levels * 8) + 16 * n + 64 * n + 4 * n + 8 + 4 * PP_LEAF_LEN * n + 2 * n + 64;
@@ -239,10 +247,7 @@ static int pt_run(swm_ctx* ctx, const swm_pedersen_transfer_circuit* c, swm_merk
     SWM_HIP(ctx, hipMemsetAsync(O.verdict, 0, 4, ctx->stream));
     SWM_TRY(transfer_prep_run(ctx, d_msgs, d_accounts, n, levels, d_keys));
     SWM_TRY(schnorr_witness_run(ctx, &c->schnorr, aux, d_msgs, d_sigs, n, d_w, stride, d_sig_ok, O.status));
-    const unsigned lanes = lanes_for(n_leaves);
-    SWM_LAUNCH(ctx, "pedersen_transfer_check", pedersen_transfer_check_kernel, dim3((unsigned)(((size_t)n_leaves * lanes + 255) / 256)), dim3(256),
-               0, pt_rows(c->leaf), c->leaf->num_windows, reinterpret_cast<const uint32_t*>(tree->d_nodes), (const uint8_t*)d_accounts, n_leaves,
-               lanes, k2d, O.verdict);
+    SWM_TRY(pedersen_transfer_check_run(ctx, c->leaf, reinterpret_cast<const uint32_t*>(tree->d_nodes), d_accounts, n_leaves, O.verdict));
     SWM_LAUNCH(ctx, "pedersen_transfer_advance", pedersen_transfer_advance_kernel, dim3(1), dim3(PT_LANES), 0, pt_rows(c->leaf),
                c->leaf->num_windows, pt_rows(c->inner), c->inner->num_windows, levels, n, reinterpret_cast<uint32_t*>(tree->d_nodes), d_accounts,
                d_msgs, (const uint8_t*)d_sig_ok, k2d, O);

@@ -77,6 +77,12 @@ struct PpArgs {
 };
 int pp_record_run(swm_ctx* ctx, const swm_pedersen* leaf, const swm_pedersen* inner, const PpArgs& A, size_t n, Fr* d_w);
 
+// ---- an account table against a Pedersen tree's leaf level (pedersen_transfer_witness.hip: pedersen_transfer_check_kernel): the
+// digest of each of the n_leaves 72-byte entries against node h; a leaf that differs stores 1 into *d_verdict, which the caller has
+// cleared in stream order.  One launch.
+int pedersen_transfer_check_run(swm_ctx* ctx, const swm_pedersen* leaf, const uint32_t* d_nodes, const uint8_t* d_accounts, unsigned n_leaves,
+                                uint32_t* d_verdict);
+
 // ---- a block of transfers (transfer_witness.hip), whatever the tree hashes with
 // The senders' keys out of the account table (2^levels leaves of 72 bytes): 16 words per transfer for the Schnorr kernel.
 int transfer_prep_run(swm_ctx* ctx, const uint8_t* d_msgs, const uint8_t* d_accounts, size_t n, unsigned levels, uint32_t* d_keys);

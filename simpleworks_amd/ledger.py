@@ -15,8 +15,9 @@ checks.
 
 The tree is hash.DeviceMerkleTree (csrc/merkle_tree.hip): register and update_balance are tree.update, two launches each
 whatever the height; the signature scheme is schnorr.py; the proof of the signature circuit is marlin.generate_schnorr_proof.
-Over a Poseidon account tree both also exist PROVED (register_proved, update_balance_proved, apply_updates: the account-update
-circuit, workloads.build_account_update), so that the proofs of a ledger chain from State::new's blank root.
+Both also exist PROVED (register_proved, update_balance_proved over either tree; a block through apply_updates over a Poseidon
+account tree, workloads.build_account_update, and through apply_pedersen_updates over the Pedersen one,
+workloads.build_pedersen_account_update), so that the proofs of a ledger chain from State::new's blank root.
 
 Where this departs from the reference, on purpose:
   * The CRH shapes are those of src/merkle_tree/common.rs and hash.py — 144 and 128 windows of 4 bits.  ledger.rs:57-74 declares
@@ -276,11 +277,13 @@ class AccountUpdateCircuit:
             raise ValueError("an operation is (id as one byte, kind, 64 key bytes, balance as u64)")
         n, nw = len(ops), self.shape()[1]
         keys = np.frombuffer(b"".join(o[2] for o in ops), dtype=np.uint8).reshape(n, 64)
-        w, acc, old, new, flags, status = self.ctx.account_update_witness_at(
+        w, acc, old, new, flags, status = getattr(self.ctx, self._witness_entry)(
             self.h, tree.h, nw, acc, np.array([o[0] for o in ops], dtype=np.uint8), np.array([o[1] for o in ops], dtype=np.uint8), keys,
             np.array([o[3] for o in ops], dtype=np.uint64), guard)
         ints = lambda rows: [int.from_bytes(r.tobytes(), "little") for r in rows]
         return (w if guard else w.reshape(n, nw, 4)), [a.tobytes() for a in acc], ints(old), ints(new), flags, status
+
+    _witness_entry = "account_update_witness_at"
 
     def free(self):
         if self.h:
@@ -292,6 +295,30 @@ class AccountUpdateCircuit:
             self.free()
         except Exception:
             pass
+
+
+class PedersenAccountUpdateCircuit(AccountUpdateCircuit):
+    """The account-update circuit over the two Pedersen CRHs of the reference's account tree (swm_pedersen_account_update_circuit):
+    synthesises the witness vector of workloads.build_pedersen_account_update for a block of registrations and balance updates
+    applied in order, and advances the tree (a hash.DeviceMerkleTree with 72-byte leaves) and the account table through the block.
+    The operations and the results are AccountUpdateCircuit's.  Refers to the two parameter sets: keep them alive."""
+
+    def __init__(self, leaf_crh, two_to_one_crh, height):
+        self.ctx, self.height = leaf_crh.ctx, height
+        self.leaf_crh, self.two_to_one_crh = leaf_crh, two_to_one_crh
+        self.h = self.ctx.pedersen_account_update_circuit_create(leaf_crh.h, two_to_one_crh.h, height)
+
+    def shape(self):
+        """(num_instance, num_witness, num_constraints)."""
+        from .marlin import pedersen_account_update_circuit_shape
+        return pedersen_account_update_circuit_shape(self.height)
+
+    _witness_entry = "pedersen_account_update_witness_at"
+
+    def free(self):
+        if self.h:
+            self.ctx.pedersen_account_update_circuit_destroy(self.h)
+            self.h = None
 
 
 class RollupCircuit(TransferCircuit):
@@ -384,6 +411,8 @@ class State:
         self._pedersen_transfer_keys = None  # (PedersenTransferCircuit, proving key, verifying key), the same
         self._update_keys = None     # (AccountUpdateCircuit, proving key, verifying key), for a Poseidon account tree
         self._update_circuit = None  # the circuit alone (no keys are needed to apply a block unproved)
+        self._pedersen_update_keys = None     # (PedersenAccountUpdateCircuit, proving key, verifying key), for a Pedersen account tree
+        self._pedersen_update_circuit = None  # the circuit alone
         self._rollup_keys = {}       # transfers per block -> (RollupCircuit or PedersenRollupCircuit, proving key, verifying key)
         self._rollup_circuits = {}   # transfers per block -> the circuit alone (no keys are needed to apply a block unproved)
         self._rollup_transfer_system = None  # the ONE packed transfer system every block size is relabelled from
@@ -570,6 +599,29 @@ class State:
             self._update_keys = (AccountUpdateCircuit(sponge, height), pk, vk)
         return self._update_keys
 
+    def pedersen_update_keys(self, rng):
+        """The account-update circuit over this ledger's Pedersen account tree (its two CRHs and tree height) with its Marlin keys,
+        derived once as update_keys derives the Poseidon form's: one key serves registrations and balance updates."""
+        if self.account_tree != "pedersen":
+            raise ValueError("pedersen_update_keys: the Pedersen account-update circuit is over a Pedersen account tree")
+        if self._pedersen_update_keys is None:
+            from . import marlin as M
+            from . import workloads as W
+            leaf_crh, inner_crh = self.parameters.leaf_crh, self.parameters.two_to_one_crh
+            height = self.account_merkle_tree.height()
+            params = W.MerkleParams(generators=(leaf_crh.generators, inner_crh.generators))
+            cs, _ = W.pedersen_account_update_circuit(params, height, 0, self.parameters.sig_params.generator, 0, 0, 1, [0] * (height - 1),
+                                                      old_root=0, new_root=0)
+            packed = cs.pack()
+            nnz = max(int(m[0][-1]) for m in packed.mats)
+            srs = M.MarlinInst.universal_setup(cs.num_constraints, len(cs.instance) + len(cs.witness), nnz, rng, leaf_crh.ctx)
+            try:
+                pk, vk = M.MarlinInst.index_from_constraint_system(srs, packed)
+            finally:
+                srs.free()
+            self._pedersen_update_keys = (PedersenAccountUpdateCircuit(leaf_crh, inner_crh, height), pk, vk)
+        return self._pedersen_update_keys
+
     def apply_updates(self, pp, ops, rng, prove=True):
         """A block of registrations and balance updates applied in order, each one proved: one witness pass on the GPU advances the
         account tree through the whole block, then (with prove) one proof per applied operation under update_keys(rng), whose public
@@ -580,6 +632,17 @@ class State:
         publishes equal roots.  next_available_account, pub_key_to_id and id_to_account_info follow the applied operations."""
         if self.account_tree != "poseidon":
             raise ValueError("apply_updates: the account-update circuit is over a Poseidon account tree")
+        return self._apply_update_block(ops, rng, prove, False)
+
+    def apply_pedersen_updates(self, pp, ops, rng, prove=True):
+        """apply_updates over this ledger's Pedersen account tree (workloads.build_pedersen_account_update): the same operations and
+        the same results, the proofs under pedersen_update_keys(rng); verify_update with pedersen_update_keys(rng)[2] serves.  A
+        Pedersen state only."""
+        if self.account_tree != "pedersen":
+            raise ValueError("apply_pedersen_updates: the Pedersen account-update circuit is over a Pedersen account tree")
+        return self._apply_update_block(ops, rng, prove, True)
+
+    def _apply_update_block(self, ops, rng, prove, pedersen):
         from . import marlin as M
         ops = list(ops)
         if not ops:
@@ -595,10 +658,19 @@ class State:
         tree = self.account_merkle_tree
         table = self.account_table()
         if prove:
-            circuit, pk, _ = self.update_keys(rng)
-            proofs, public, flags, _, _ = M.generate_account_update_proofs(pk, circuit, tree, table, block, rng)
+            circuit, pk, _ = self.pedersen_update_keys(rng) if pedersen else self.update_keys(rng)
+            prover = M.generate_pedersen_account_update_proofs if pedersen else M.generate_account_update_proofs
+            proofs, public, flags, _, _ = prover(pk, circuit, tree, table, block, rng)
         else:
-            if self._update_keys is not None:
+            if pedersen:
+                if self._pedersen_update_keys is not None:
+                    circuit = self._pedersen_update_keys[0]
+                else:
+                    if self._pedersen_update_circuit is None:
+                        self._pedersen_update_circuit = PedersenAccountUpdateCircuit(self.parameters.leaf_crh, self.parameters.two_to_one_crh,
+                                                                                     tree.height())
+                    circuit = self._pedersen_update_circuit
+            elif self._update_keys is not None:
                 circuit = self._update_keys[0]
             else:
                 if self._update_circuit is None:
@@ -630,7 +702,7 @@ class State:
             return None
         if acc >= 1 << (self.account_merkle_tree.height() - 1):
             raise IndexError("register: account %d is past the last leaf of the account tree" % acc)
-        applied, proof, public = self.apply_updates(self.parameters, [("register", acc, public_key)], rng)[0]
+        applied, proof, public = self._apply_update_block([("register", acc, public_key)], rng, True, self.account_tree == "pedersen")[0]
         if not applied:
             raise ValueError("register_proved: the registration of account %d was refused" % acc)
         return acc, proof, public
@@ -639,7 +711,7 @@ class State:
         """update_balance with its proof: -> (proof bytes, public inputs), or None when there is no such account."""
         if acc not in self.id_to_account_info:
             return None
-        applied, proof, public = self.apply_updates(self.parameters, [("balance", acc, new_amount)], rng)[0]
+        applied, proof, public = self._apply_update_block([("balance", acc, new_amount)], rng, True, self.account_tree == "pedersen")[0]
         if not applied:
             raise ValueError("update_balance_proved: the update of account %d was refused" % acc)
         return proof, public
@@ -770,15 +842,16 @@ class State:
 
     def free(self):
         for keys in (self._proof_keys, self._payment_keys, self._transfer_keys, self._pedersen_payment_keys, self._pedersen_transfer_keys,
-                     self._update_keys):
+                     self._update_keys, self._pedersen_update_keys):
             if keys is not None:
                 keys[0].free()
                 keys[1].free()
         self._proof_keys = self._payment_keys = self._transfer_keys = self._pedersen_payment_keys = self._pedersen_transfer_keys = None
-        self._update_keys = None
-        if self._update_circuit is not None:
-            self._update_circuit.free()
-            self._update_circuit = None
+        self._update_keys = self._pedersen_update_keys = None
+        for name in ("_update_circuit", "_pedersen_update_circuit"):
+            if getattr(self, name) is not None:
+                getattr(self, name).free()
+                setattr(self, name, None)
         for _, pk, _ in self._rollup_keys.values():
             pk.free()
         for circuit in self._rollup_circuits.values():
@@ -810,7 +883,7 @@ def verify_transfer(vk, public_inputs, proof, rng):
 
 def verify_update(vk, public_inputs, proof, rng):
     """The verifier of an account-update proof: public_inputs = [old_root, new_root, id, key_x, key_y, old_balance, new_balance, fresh]
-    (workloads.account_update_public_inputs), vk that of State.update_keys."""
+    (workloads.account_update_public_inputs), vk that of State.update_keys or, over a Pedersen account tree, State.pedersen_update_keys."""
     from . import marlin as M
     return M.verify_proof(vk, [int(v) for v in public_inputs], proof if isinstance(proof, M.MarlinProof) else M.MarlinProof(proof), rng)
 

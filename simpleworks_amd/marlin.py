@@ -806,7 +806,8 @@ def _account_update_public(table, op, old_root, new_root):
     return W.account_update_public_inputs(old_root, new_root, index, point, old_balance, balance, kind)
 
 
-def generate_account_update_proofs(proving_key, circuit, tree, accounts, ops, rng, uncompressed=False):
+def generate_account_update_proofs(proving_key, circuit, tree, accounts, ops, rng, uncompressed=False,
+                                   _entry="swm_account_update_prove_many_at"):
     """swm_account_update_prove_many_at: the block `ops` ((id, kind, 64 key bytes, balance) each; kind 0 = set balance, 1 =
     register) applied IN ORDER to the resident account tree `tree` (a hash.PoseidonMerkleTree) and to the account table `accounts`
     (2^L leaves of 72 bytes, all-zero = no account): one witness pass over the whole block, then one prover call per applied
@@ -832,9 +833,8 @@ def generate_account_update_proofs(proving_key, circuit, tree, accounts, ops, rn
     old, new = (ctypes.c_uint8 * (32 * count))(), (ctypes.c_uint8 * (32 * count))()
     flags, status = (ctypes.c_uint8 * count)(), (ctypes.c_uint32 * count)()
     before = [bytes(a) for a in acc]
-    _check(ctx.lib.swm_account_update_prove_many_at(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, ids, kinds, keys, bal, count,
-                                                    rng.h, 1 if uncompressed else 0, out, cap, lens, old, new, flags, status),
-           "swm_account_update_prove_many_at", ctx)
+    _check(getattr(ctx.lib, _entry)(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, ids, kinds, keys, bal, count, rng.h,
+                                    1 if uncompressed else 0, out, cap, lens, old, new, flags, status), _entry, ctx)
     raw, old, new = bytes(out), bytes(old), bytes(new)
     public = []
     for i, op in enumerate(ops):       # the table each operation met: the applied ones before it replayed on the host
@@ -847,7 +847,7 @@ def generate_account_update_proofs(proving_key, circuit, tree, accounts, ops, rn
             [bytes(a) for a in acc])
 
 
-def generate_account_update_proof(proving_key, circuit, tree, accounts, op, rng, uncompressed=False):
+def generate_account_update_proof(proving_key, circuit, tree, accounts, op, rng, uncompressed=False, _entry="swm_account_update_prove_at"):
     """swm_account_update_prove_at: one operation (id, kind, 64 key bytes, balance); returns (proof or None, public inputs, flag,
     status, accounts after it)."""
     ctx = proving_key.ctx
@@ -861,11 +861,32 @@ def generate_account_update_proof(proving_key, circuit, tree, accounts, op, rng,
     old, new = (ctypes.c_uint8 * 32)(), (ctypes.c_uint8 * 32)()
     flag, status = ctypes.c_uint8(0), ctypes.c_uint32(0)
     before = [bytes(a) for a in acc]
-    _check(ctx.lib.swm_account_update_prove_at(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, op[0], op[1], key, op[3], rng.h,
-                                               1 if uncompressed else 0, buf, len(buf), ctypes.byref(n), old, new, ctypes.byref(flag),
-                                               ctypes.byref(status)), "swm_account_update_prove_at", ctx)
+    _check(getattr(ctx.lib, _entry)(ctx.h, proving_key.h, circuit.h, tree.h, acc.ctypes.data, op[0], op[1], key, op[3], rng.h,
+                                    1 if uncompressed else 0, buf, len(buf), ctypes.byref(n), old, new, ctypes.byref(flag),
+                                    ctypes.byref(status)), _entry, ctx)
     public = _account_update_public(before, op, int.from_bytes(bytes(old), "little"), int.from_bytes(bytes(new), "little"))
     return (bytes(buf[: n.value]) if n.value else None, public, flag.value, status.value, [bytes(a) for a in acc])
+
+
+def pedersen_account_update_circuit_shape(height):
+    """swm_pedersen_account_update_circuit_shape (no GPU): (num_instance, num_witness, num_constraints) of the account-update circuit
+    over a Pedersen account tree of that height — what workloads.build_pedersen_account_update emits."""
+    ni, nw, nc = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load_library().swm_pedersen_account_update_circuit_shape(height, ctypes.byref(ni), ctypes.byref(nw), ctypes.byref(nc)),
+           "swm_pedersen_account_update_circuit_shape")
+    return ni.value, nw.value, nc.value
+
+
+def generate_pedersen_account_update_proofs(proving_key, circuit, tree, accounts, ops, rng, uncompressed=False):
+    """swm_pedersen_account_update_prove_many_at: generate_account_update_proofs over the reference's Pedersen account tree — `tree` a
+    hash.DeviceMerkleTree with 72-byte leaves, `circuit` a ledger.PedersenAccountUpdateCircuit.  The same arguments and results."""
+    return generate_account_update_proofs(proving_key, circuit, tree, accounts, ops, rng, uncompressed,
+                                          "swm_pedersen_account_update_prove_many_at")
+
+
+def generate_pedersen_account_update_proof(proving_key, circuit, tree, accounts, op, rng, uncompressed=False):
+    """swm_pedersen_account_update_prove_at: one operation; returns (proof or None, public inputs, flag, status, accounts after it)."""
+    return generate_account_update_proof(proving_key, circuit, tree, accounts, op, rng, uncompressed, "swm_pedersen_account_update_prove_at")
 
 
 def rollup_circuit_shape(params, height, transfers, salted=False):

@@ -2432,6 +2432,144 @@ class PedersenTransferValidation:
 
 
 # ===================================================================================================================
+# The account-update statement over the Pedersen account tree: build_account_update's statement ("the leaf at `id` becomes key ||
+# new_balance, every other leaf stays; the old leaf is key || old_balance when fresh = 0 and the blank leaf when fresh = 1") and
+# its instance, over build_pedersen_transfer's sections.  Over this tree the blank leaf is an honest member — the Pedersen hash of
+# 72 zero bytes is the identity's x = 0, MerkleTree::blank's leaf digest — so there is no cur_0, no masked digest and no `start`
+# hook: fresh masks the LEAF BITS, o_i = (1 - fresh) k_i.  build_pedersen_account_update is the layout contract of
+# csrc/host/pedersen_account_update_shape.h and csrc/pedersen_account_update_witness.hip.  With L = height - 1, M = 3450 + 3581 L
+# and U = 3450 + 3579 L:
+#   instance  one, old_root, new_root, id, key_x, key_y, old_balance, new_balance, fresh
+#   witness   512 key bits | 64 bits of old_balance | 64 of new_balance | 8 id bits                                       648
+#             512 masked key bits o_i (a product of two booleans: no booleanity row)                                      512
+#             the old leaf's membership section over o || old_balance bits, against old_root                              M
+#             the update section over key bits || new_balance bits on that section's (dir_l, s_l)                         U
+#   rows      648 booleanity rows | five packing rows | fresh (1 - fresh) = 0 | fresh pack(old) = 0 | 512 mask rows
+#             fresh k_i = k_i - o_i | the membership section (3459 + 3588 L, its last the root row) | the update section
+#             (3451 + 3587 L, its last the root row against new_root)                       1167 + 3459 + 3588 L + 3451 + 3587 L
+# Every witness is computed honestly whatever the inputs claim (fresh = 2 leaves o_i = -k_i: the mask rows hold, the booleanity row
+# of fresh fails, and a section over bits that are no bits is still walked by the same formulas).  The key is packed unreduced,
+# build_account_update's caveat.
+# ===================================================================================================================
+PEDERSEN_ACCOUNT_UPDATE_LOOSE = ACCOUNT_UPDATE_BITS + 512       # 1160: the booleans and the masked key bits
+
+
+def pedersen_account_update_circuit_layout(height):
+    """Offsets of the witness groups and the named rows of build_pedersen_account_update and its three counts, as
+    csrc/host/pedersen_account_update_shape.h states them.  "update" holds an update section's own offsets."""
+    if not 2 <= height <= 9:
+        raise ValueError("pedersen account update circuit: 2 <= height <= 9 (an account id is one byte)")
+    levels = height - 1
+    m = PEDERSEN_PAYMENT_LEAF_WITNESSES + PEDERSEN_PAYMENT_LEVEL_WITNESSES * levels
+    u = PEDERSEN_PAYMENT_LEAF_WITNESSES + PEDERSEN_TRANSFER_LEVEL_WITNESSES * levels
+    section_rows = PEDERSEN_PAYMENT_LEAF_WITNESSES + PEDERSEN_PAYMENT_LEVEL_ROWS * levels + 8 + 1
+    update_rows = PEDERSEN_PAYMENT_LEAF_WITNESSES + PEDERSEN_TRANSFER_LEVEL_ROWS * levels + 1
+    lay = {"levels": levels, "membership_witnesses": m, "update_witnesses": u, "section_rows": section_rows, "update_rows": update_rows,
+           "update": {"leaf": 0, "level0": PEDERSEN_PAYMENT_LEAF_WITNESSES, "level_witnesses": PEDERSEN_TRANSFER_LEVEL_WITNESSES,
+                      "level_rows": PEDERSEN_TRANSFER_LEVEL_ROWS}}
+    lay.update(key_bits=0, old_balance=512, new_balance=576, id_bits=640, masked_bits=ACCOUNT_UPDATE_BITS,
+               old=PEDERSEN_ACCOUNT_UPDATE_LOOSE)
+    lay["new"] = lay["old"] + m
+    lay["num_instance"] = 9
+    lay["num_witness"] = lay["new"] + u
+    lay["pack_rows"] = ACCOUNT_UPDATE_BITS            # key_x, key_y, old_balance, new_balance, id
+    lay["fresh_row"] = lay["pack_rows"] + 5
+    lay["fresh_balance_row"] = lay["fresh_row"] + 1
+    lay["mask_rows"] = lay["fresh_balance_row"] + 1
+    lay["old_rows"] = lay["mask_rows"] + 512
+    lay["old_root_row"] = lay["old_rows"] + section_rows - 1
+    lay["new_rows"] = lay["old_root_row"] + 1
+    lay["new_root_row"] = lay["new_rows"] + update_rows - 1
+    lay["num_constraints"] = lay["new_root_row"] + 1
+    return lay
+
+
+def build_pedersen_account_update(cs, merkle_params, height, index, key, old_balance, new_balance, fresh, siblings, old_root=None,
+                                  new_root=None):
+    """Emits the account-update circuit over a Pedersen account tree into `cs`.  merkle_params as build_pedersen_payment's; the
+    other arguments and the result as build_account_update's: index one byte (an id at or above 2^(height - 1) is taken by its low
+    bits and fails an index row), key (x, y) below 2^256, two u64 balances, fresh 1 for a registration and 0 for a balance update
+    (any other value is taken as it is: o_i = (1 - fresh) k_i stays honest and the booleanity row fails), siblings bottom up.
+    old_root, new_root override the two public roots, which otherwise are the walked values.  Returns the public inputs [old_root,
+    new_root, id, key_x, key_y, old_balance, new_balance, fresh]."""
+    levels = height - 1
+    if not 2 <= height <= 9 or len(siblings) != levels:
+        raise ValueError("pedersen account update circuit: 2 <= height <= 9 and a path of height - 1 siblings")
+    if (merkle_params.digest_bits != 256 or len(merkle_params.leaf_gens[0]) != 4 or len(merkle_params.inner_gens[0]) != 4
+            or len(merkle_params.leaf_gens) < 2 * PAYMENT_LEAF_LEN or len(merkle_params.inner_gens) < 128):
+        raise ValueError("pedersen account update circuit: 256-bit digests, 144 leaf and 128 two-to-one windows of 4 bits")
+    index, old_balance, new_balance, fresh = int(index), int(old_balance), int(new_balance), int(fresh)
+    x, y = int(key[0]), int(key[1])
+    if not 0 <= index <= 255 or not 0 <= x < 1 << 256 or not 0 <= y < 1 << 256:
+        raise ValueError("pedersen account update circuit: an id of one byte and key coordinates of 32 bytes")
+    if not 0 <= old_balance <= (1 << 64) - 1 or not 0 <= new_balance <= (1 << 64) - 1:
+        raise ValueError("pedersen account update circuit: a balance is a u64")
+    siblings = [int(s) % R_MODULUS for s in siblings]
+    walked = index & ((1 << levels) - 1)
+    key_values = _pp_leaf_bits(x.to_bytes(32, "little") + y.to_bytes(32, "little"))
+    old_values, new_values = [(old_balance >> i) & 1 for i in range(64)], [(new_balance >> i) & 1 for i in range(64)]
+    masked_values = [(1 - fresh) * v % R_MODULUS for v in key_values]
+
+    def walk(leaf_values):  # the root a section over these leaf values leads to: the sections' own formulas, nothing recorded
+        path = [(_LC([], (walked >> lvl) & 1), _LC([], s)) for lvl, s in enumerate(siblings)]
+        return _pt_update(_PsNullSystem(), None, merkle_params, [_LC([], v) for v in leaf_values], path).value
+    old_root = walk(masked_values + old_values) if old_root is None else int(old_root) % R_MODULUS
+    new_root = walk(key_values + new_values) if new_root is None else int(new_root) % R_MODULUS
+    one = cs.one()
+    public = account_update_public_inputs(old_root, new_root, index, (x, y), old_balance, new_balance, fresh)
+    old_i, new_i, id_i, kx_i, ky_i, ob_i, nb_i, fresh_i = [cs.new_input_variable(v) for v in public]
+
+    def pack(bits):
+        return [((1 << i) % R_MODULUS, b.terms[0][1]) for i, b in enumerate(bits)]
+    key_bits = [_boolean_witness(cs, one, v) for v in key_values]
+    old_bits = [_boolean_witness(cs, one, v) for v in old_values]
+    new_bits = [_boolean_witness(cs, one, v) for v in new_values]
+    id_bits = [_boolean_witness(cs, one, (index >> i) & 1) for i in range(8)]
+    masked = [_LC([(1, cs.new_witness_variable(v))], v) for v in masked_values]
+    # the booleans are the public input
+    cs.enforce_constraint(pack(key_bits[:256]), [(1, one)], [(1, kx_i)])
+    cs.enforce_constraint(pack(key_bits[256:]), [(1, one)], [(1, ky_i)])
+    cs.enforce_constraint(pack(old_bits), [(1, one)], [(1, ob_i)])
+    cs.enforce_constraint(pack(new_bits), [(1, one)], [(1, nb_i)])
+    cs.enforce_constraint(pack(id_bits), [(1, one)], [(1, id_i)])
+    # fresh is a bit, and a registration claims no old balance
+    cs.enforce_constraint([(1, fresh_i)], [(1, one), (R_MODULUS - 1, fresh_i)], [])
+    cs.enforce_constraint([(1, fresh_i)], pack(old_bits), [])
+    # a registration's old leaf is blank: fresh k_i = k_i - o_i
+    for k, o in zip(key_bits, masked):
+        cs.enforce_constraint([(1, fresh_i)], k.terms, k.minus(o).terms)
+    # the old leaf in the old tree, then the new leaf up the same path
+    path = []
+    _pp_membership(cs, one, merkle_params, masked + old_bits, [b.terms[0][1] for b in id_bits], walked, siblings, [(1, old_i)], keep=path)
+    cur = _pt_update(cs, one, merkle_params, key_bits + new_bits, path)
+    cs.enforce_constraint(cur.terms, [(1, one)], [(1, new_i)])
+    return public
+
+
+def pedersen_account_update_circuit(merkle_params, height, index, key, old_balance, new_balance, fresh, siblings, old_root=None,
+                                    new_root=None):
+    """The circuit as a ConstraintSystem; returns (cs, public_inputs)."""
+    cs = ConstraintSystem()
+    public = build_pedersen_account_update(cs, merkle_params, height, index, key, old_balance, new_balance, fresh, siblings, old_root,
+                                           new_root)
+    return cs, public
+
+
+class PedersenAccountUpdate:
+    """The ConstraintSynthesizer of the account-update statement over a Pedersen account tree for MarlinInst.index / prove:
+    constants = the two CRH parameter sets, public = old_root, new_root, id, key, old_balance, new_balance, fresh, witness = the
+    leaf's path."""
+
+    def __init__(self, merkle_params, height, old_root, new_root, index, key, old_balance, new_balance, fresh, path):
+        self.merkle_params, self.height, self.old_root, self.new_root = merkle_params, height, old_root, new_root
+        self.index, self.key, self.old_balance, self.new_balance, self.fresh = index, key, old_balance, new_balance, fresh
+        self.path = list(path)
+
+    def generate_constraints(self, cs):
+        build_pedersen_account_update(cs, self.merkle_params, self.height, self.index, self.key, self.old_balance, self.new_balance,
+                                      self.fresh, self.path, old_root=self.old_root, new_root=self.new_root)
+
+# ===================================================================================================================
 # The rollup: ONE statement for a block of N transfers applied in order, old_root -> new_root, over either account tree.  N
 # sections of the transfer circuit (build_transfer / build_pedersen_transfer) linked through N - 1 WITNESSED roots: the
 # intermediate roots appear nowhere in the public input.  build_rollup / build_pedersen_rollup are the layout contract of

@@ -23,6 +23,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 #[repr(C)] pub struct swm_transfer_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_pedersen_transfer_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_account_update_circuit { _p: [u8; 0] }
+#[repr(C)] pub struct swm_pedersen_account_update_circuit { _p: [u8; 0] }
 #[repr(C)] pub struct swm_program { _p: [u8; 0] }
 
 pub const SWM_OK: c_int = 0;
@@ -413,6 +414,26 @@ extern "C" {
                                        tree: *mut swm_poseidon_tree, accounts_inout: *mut u8, id: u8, kind: u8, key_xy: *const u8,
                                        balance: u64, rng: *mut swm_rng, prove_flags: c_uint, proof_out: *mut u8, cap: usize,
                                        len: *mut usize, old_root: *mut u8, new_root: *mut u8, flag: *mut u8, status: *mut u32) -> c_int;
+    // the same over the reference's Pedersen account tree (a swm_merkle_tree with 72-byte leaves)
+    pub fn swm_pedersen_account_update_circuit_shape(height: usize, num_instance: *mut usize, num_witness: *mut usize,
+                                                     num_constraints: *mut usize) -> c_int;
+    pub fn swm_pedersen_account_update_circuit_create(ctx: *mut swm_ctx, leaf: *const swm_pedersen, two_to_one: *const swm_pedersen,
+                                                      height: usize, out: *mut *mut swm_pedersen_account_update_circuit) -> c_int;
+    pub fn swm_pedersen_account_update_circuit_destroy(ctx: *mut swm_ctx, circuit: *mut swm_pedersen_account_update_circuit);
+    pub fn swm_pedersen_account_update_witness_at(ctx: *mut swm_ctx, circuit: *const swm_pedersen_account_update_circuit,
+                                                  tree: *mut swm_merkle_tree, accounts_inout: *mut u8, ids: *const u8, kinds: *const u8,
+                                                  keys_xy: *const u8, balances: *const u8, count: usize, witnesses_out: *mut u64,
+                                                  old_roots: *mut u8, new_roots: *mut u8, flags: *mut u8, status: *mut u32) -> c_int;
+    pub fn swm_pedersen_account_update_prove_many_at(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_pedersen_account_update_circuit,
+                                                     tree: *mut swm_merkle_tree, accounts_inout: *mut u8, ids: *const u8, kinds: *const u8,
+                                                     keys_xy: *const u8, balances: *const u8, count: usize, rng: *mut swm_rng,
+                                                     prove_flags: c_uint, proofs_out: *mut u8, proof_cap: usize, lens: *mut usize,
+                                                     old_roots: *mut u8, new_roots: *mut u8, flags: *mut u8, status: *mut u32) -> c_int;
+    pub fn swm_pedersen_account_update_prove_at(ctx: *mut swm_ctx, pk: *const swm_pk, circuit: *const swm_pedersen_account_update_circuit,
+                                                tree: *mut swm_merkle_tree, accounts_inout: *mut u8, id: u8, kind: u8, key_xy: *const u8,
+                                                balance: u64, rng: *mut swm_rng, prove_flags: c_uint, proof_out: *mut u8, cap: usize,
+                                                len: *mut usize, old_root: *mut u8, new_root: *mut u8, flag: *mut u8,
+                                                status: *mut u32) -> c_int;
     // the Blake2s random oracle, batched, and its circuit's witness (no handle: the shape follows from input_len)
     pub fn swm_blake2s_hash(ctx: *mut swm_ctx, inputs: *const u8, input_len: usize, count: usize, digests: *mut u8) -> c_int;
     pub fn swm_blake2s_hash_dev(ctx: *mut swm_ctx, d_inputs: *const c_void, input_len: usize, count: usize,

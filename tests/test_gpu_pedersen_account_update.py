@@ -1,0 +1,457 @@
+"""The Pedersen account-update circuit's witness and proof entries (csrc/pedersen_account_update_witness.hip) and
+State.apply_pedersen_updates on the GPU, against the circuit's specification workloads.build_pedersen_account_update run on the CPU
+over the blocks of tests/pedersen_account_update_model.py: whole witness vectors in Montgomery limbs with 0xFF guard elements behind
+them, root pairs, flags, status words, the account table and every node of the tree after a block; heights 2, 3, 4 and 9; blocks of
+1, 2, 64 and 65 against a twin tree taken through the applied operations by swm_merkle_tree_update; each refusal in the middle of a
+block; a table that is not the tree's; a chunk seam inside a block of 5; proof bytes against generate_proof on the builder's
+system; and the chain of proofs from State::new's blank Pedersen root through registrations, balance updates and a block of
+transfers to the state's root."""
+import os
+
+import numpy as np
+import pytest
+
+import pedersen_account_update_model as AM
+import pedersen_payment_model as PM
+
+pytestmark = pytest.mark.gpu
+
+R = AM.R
+POSEIDON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "poseidon_params.json")
+GUARD = 3
+
+
+class _WitnessOnly:
+    """The builder's vocabulary, keeping the assignment and dropping the rows."""
+
+    def __init__(self):
+        self.witness = []
+        self.public = []
+
+    @staticmethod
+    def one():
+        return ("i", 0)
+
+    def new_input_variable(self, value):
+        self.public.append(int(value) % R)
+        return ("i", len(self.public))
+
+    def new_witness_variable(self, value):
+        self.witness.append(int(value) % R)
+        return ("w", len(self.witness) - 1)
+
+    def enforce_constraint(self, a, b, c):
+        pass
+
+
+def _same(got, want, what):
+    assert got.shape == want.shape, what
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert bad.size == 0, "%s: %d witnesses differ, the first at %d" % (what, bad.size, bad[0])
+
+
+def _node_rows(levels):
+    return np.frombuffer(b"".join(v.to_bytes(32, "little") for level in levels for v in level), dtype=np.uint8).reshape(-1, 32)
+
+
+def _nodes(c, tree):
+    return c.ctx.merkle_tree_nodes(tree.h).reshape(-1, 32)
+
+
+@pytest.fixture(scope="module")
+def M():
+    from simpleworks_amd import marlin
+    return marlin
+
+
+@pytest.fixture(scope="module")
+def W():
+    from simpleworks_amd import workloads
+    return workloads
+
+
+@pytest.fixture(scope="module")
+def L():
+    from simpleworks_amd import ledger
+    return ledger
+
+
+@pytest.fixture(scope="module")
+def params(W):
+    return W.MerkleParams()
+
+
+@pytest.fixture(scope="module")
+def crh(params):
+    from simpleworks_amd import hash as H
+    made = (H.PedersenCRH(params.leaf_gens), H.PedersenCRH(params.inner_gens))
+    yield made
+    for c in made:
+        c.free()
+
+
+@pytest.fixture(scope="module")
+def circuits(L, crh):
+    made = {}
+
+    def get(height):
+        if height not in made:
+            made[height] = L.PedersenAccountUpdateCircuit(crh[0], crh[1], height)
+        return made[height]
+    yield get
+    for c in made.values():
+        c.free()
+
+
+@pytest.fixture
+def fresh_tree(crh):
+    """table -> a resident tree whose leaf level is that table; freed after the test."""
+    from simpleworks_amd import hash as H
+    made = []
+
+    def get(height, table):
+        tree = H.DeviceMerkleTree.blank(crh[0], crh[1], height, 72)
+        held = [i for i, leaf in enumerate(table) if any(leaf)]
+        if held:
+            tree.update_many(held, [table[i] for i in held])
+        made.append(tree)
+        return tree
+    yield get
+    for t in made:
+        t.free()
+
+
+@pytest.fixture(scope="module")
+def oracle(M, W, params):
+    """(height, operation of the model) -> the builder's witness as Montgomery limbs; built once per distinct input."""
+    seen = {}
+
+    def get(height, t):
+        k = (height, t["id"], t["key"], t["old_balance"], t["new_balance"], t["fresh"], tuple(t["path"]))
+        if k not in seen:
+            cs = _WitnessOnly()
+            public = W.build_pedersen_account_update(cs, params, height, t["id"], t["key"], t["old_balance"], t["new_balance"], t["fresh"],
+                                                     t["path"], old_root=t["old_root"], new_root=t["new_root"])
+            assert public == cs.public
+            seen[k] = M._to_mont_limbs(cs.witness)
+        return seen[k]
+    return get
+
+
+@pytest.fixture(scope="module")
+def world(params):
+    """height -> (blank table, the dependence block applied from the blank tree, final table, final levels), made once."""
+    seen = {}
+
+    def get(height):
+        if height not in seen:
+            table, levels = AM.blank(params, height)
+            seen[height] = (table,) + AM.apply(params, height, table, levels, AM.dependences(height))
+        return seen[height]
+    return get
+
+
+def _run(c, tree, table, ops, guard=GUARD):
+    """witness_at with guard elements: -> (witness [count, num_witness, 4], table, old, new, flags, status); the guard is checked."""
+    nw = c.shape()[1]
+    w, after, old, new, flags, status = c.witness_at(tree, table, ops, guard=guard)
+    assert w.shape == (len(ops) * nw + guard, 4)
+    assert (w[len(ops) * nw:] == np.uint64(0xFFFFFFFFFFFFFFFF)).all(), "the guard elements behind the last witness were written"
+    return w[:len(ops) * nw].reshape(len(ops), nw, 4), after, old, new, flags, status
+
+
+def _check_block(oracle, height, block, got, what, witnessed=None):
+    """Roots, flags, status and the witness vectors of a block (all, or those at the indices `witnessed`) against model and builder."""
+    w, _, old, new, flags, status = got
+    assert list(status) == [t["status"] for t in block], what
+    assert [int(f) for f in flags] == [t["flag"] for t in block], what
+    assert old == [t["old_root"] for t in block] and new == [t["new_root"] for t in block], what
+    for k, t in enumerate(block):
+        if not t["applied"]:
+            assert not w[k].any() and old[k] == new[k], "%s, item %d: a refused operation's witness is zero, its roots equal" % (what, k)
+        elif witnessed is None or k in witnessed:
+            _same(w[k], oracle(height, t), "%s, item %d" % (what, k))
+
+
+@pytest.mark.parametrize("height", [2, 3, 4])
+def test_whole_witness_vectors_of_the_dependence_block(M, params, circuits, world, fresh_tree, oracle, height):
+    """From the blank tree: a registration followed by a balance update of the same leaf, the leftmost and the rightmost leaf, two
+    sibling leaves (the second's path shares every level but the lowest with the first's, its sibling is the first's new digest)."""
+    table, block, final, levels = world(height)
+    assert all(t["applied"] for t in block)
+    if height > 2:
+        a, b = next((i, j) for i, s in enumerate(block) for j, t in enumerate(block) if j == i + 1 and s["id"] ^ t["id"] == 1)
+        assert block[b]["path"][0] == PM.leaf_digest(params, block[a]["new_leaf"]) and block[b]["path"][1:] == block[a]["path"][1:]
+    c, tree = circuits(height), fresh_tree(height, table)
+    assert c.shape() == M.pedersen_account_update_circuit_shape(height)
+    got = _run(c, tree, table, [t["op"] for t in block])
+    _check_block(oracle, height, block, got, "dependences at height %d" % height)
+    _, after, old, new, _, _ = got
+    assert old[0] == PM.tree(params, height, {})[-1][0] and all(new[i] == old[i + 1] for i in range(len(block) - 1))
+    assert after == final and new[-1] == tree.root() == levels[-1][0]
+    assert np.array_equal(_nodes(c, tree), _node_rows(levels))
+
+
+def test_a_block_of_two_at_height_9(params, circuits, fresh_tree, oracle):
+    """The largest tree: a registration of the rightmost leaf and the balance update of the same leaf."""
+    height = 9
+    table, levels = AM.blank(params, height)
+    block, final, levels = AM.apply(params, height, table, levels, AM.dependences(height)[:2])
+    c, tree = circuits(height), fresh_tree(height, table)
+    assert c.shape() == (9, 65340, 65477)
+    got = _run(c, tree, table, [t["op"] for t in block])
+    _check_block(oracle, height, block, got, "two operations at height 9")
+    assert got[1] == final and tree.root() == levels[-1][0] and got[3][0] == got[2][1]
+    assert np.array_equal(_nodes(c, tree), _node_rows(levels))
+
+
+@pytest.fixture(scope="module")
+def block65(params):
+    table, levels = AM.blank(params, 3)
+    block, final, levels = AM.apply(params, 3, table, levels, AM.block_of(65, 3))
+    assert [k for k, t in enumerate(block) if not t["applied"]] == [9, 63]
+    return table, block
+
+
+@pytest.mark.parametrize("count", [1, 2, 64, 65])
+def test_counts_against_a_twin_tree(circuits, fresh_tree, oracle, block65, count):
+    """Blocks of 1, 2, 64 and 65 at height 3: roots, flags and status of every item against the model, the first and the last item's
+    witness against the builder, and every node against a twin tree taken through the applied operations by swm_merkle_tree_update."""
+    table, block = block65
+    block = block[:count]
+    c, tree, twin = circuits(3), fresh_tree(3, table), fresh_tree(3, table)
+    got = _run(c, tree, table, [t["op"] for t in block])
+    _check_block(oracle, 3, block, got, "%d operations" % count, witnessed={0, count - 1})
+    assert got[1] == block[-1]["table"] and tree.root() == block[-1]["new_root"]
+    for t in block:
+        if t["applied"]:
+            twin.update(t["id"], t["new_leaf"])
+    assert np.array_equal(_nodes(c, tree), _nodes(c, twin))
+
+
+@pytest.mark.parametrize("which", range(7))
+def test_each_refusal_in_the_middle_of_a_block(params, circuits, fresh_tree, oracle, which):
+    """[a registration, the refusal, a balance update of the account the first one made]: the refused item's status bit stands
+    alone, its witness is zero and its roots are equal; the operations around it are as if it were not there; tree nodes and table
+    equal those of a twin tree taken through the applied operations alone by swm_merkle_tree_update."""
+    height = 3
+    held, cases = AM.refusals(height)
+    name, bad, st = cases[which]
+    table, levels = AM.blank(params, height)
+    _, first, levels = AM.apply(params, height, table, levels, [(held, AM.REGISTER, AM.key(held), 0), (held, AM.SET, AM.NO_KEY, 100)])
+    ops = [(3, AM.REGISTER, AM.key(3), 0), bad, (3, AM.SET, AM.NO_KEY, 55)]
+    block, final, after_levels = AM.apply(params, height, first, levels, ops)
+    assert [t["status"] for t in block] == [0, st, 0] and bin(st).count("1") == 1, name
+    c, tree, twin = circuits(height), fresh_tree(height, first), fresh_tree(height, first)
+    got = _run(c, tree, first, ops)
+    _check_block(oracle, height, block, got, name)
+    assert int(got[5][1]) == st and int(got[4][1]) == 0
+    assert got[1] == final and got[3][0] == got[2][1] == got[3][1] == got[2][2]
+    for t in block:
+        if t["applied"]:
+            twin.update(t["id"], t["new_leaf"])
+    assert np.array_equal(_nodes(c, tree), _nodes(c, twin))
+    assert np.array_equal(_nodes(c, tree), _node_rows(after_levels))
+
+
+def test_tables_trees_and_kinds_that_are_refused(L, params, circuits, fresh_tree, crh):
+    """Any difference between the table and the tree's leaf level refuses the call and leaves both byte for byte: the entry is called
+    through ctypes here, so that the caller's table is seen after the refusal.  So do a kind above 1 and a tree of another height."""
+    from simpleworks_amd._lib import SwmError
+    height = 3
+    table, levels = AM.blank(params, height)
+    _, first, levels = AM.apply(params, height, table, levels, [(1, AM.REGISTER, AM.key(1), 3), (2, AM.REGISTER, AM.key(2), 0)])
+    c, tree = circuits(height), fresh_tree(height, first)
+    nw = c.shape()[1]
+    before = _nodes(c, tree).copy()
+    ops = [(3, AM.REGISTER, AM.key(3), 0), (1, AM.SET, AM.NO_KEY, 9)]
+    for wrong in ([first[k] if k != 1 else first[1][:64] + (4).to_bytes(8, "little") for k in range(len(first))],      # a balance
+                  [first[k] if k != 0 else first[1] for k in range(len(first))],                                    # a leaf the tree holds blank
+                  [first[k] if k != 2 else bytes(72) for k in range(len(first))]):                                  # blank where the tree holds one
+        acc = np.frombuffer(b"".join(wrong), dtype=np.uint8).reshape(-1, 72).copy()
+        kept = acc.copy()
+        ids, kinds = np.array([o[0] for o in ops], dtype=np.uint8), np.array([o[1] for o in ops], dtype=np.uint8)
+        keys = np.frombuffer(b"".join(o[2] for o in ops), dtype=np.uint8).copy()
+        bal = np.array([o[3] for o in ops], dtype="<u8")
+        w = np.zeros((2 * nw, 4), dtype=np.uint64)
+        old, new = np.zeros((2, 32), dtype=np.uint8), np.zeros((2, 32), dtype=np.uint8)
+        flags, status = np.zeros(2, dtype=np.uint8), np.zeros(2, dtype=np.uint32)
+        rc = c.ctx.lib.swm_pedersen_account_update_witness_at(c.ctx.h, c.h, tree.h, acc.ctypes.data, ids.ctypes.data, kinds.ctypes.data,
+                                                              keys.ctypes.data, bal.ctypes.data, 2, w.ctypes.data, old.ctypes.data,
+                                                              new.ctypes.data, flags.ctypes.data, status.ctypes.data)
+        assert rc == -1 and b"account table" in c.ctx.lib.swm_last_error(c.ctx.h)
+        assert np.array_equal(acc, kept) and np.array_equal(_nodes(c, tree), before)
+    with pytest.raises(SwmError) as e:       # a kind that is neither
+        c.witness_at(tree, first, [(3, 2, AM.key(3), 0)])
+    assert e.value.code == -1 and "kind 2" in str(e.value)
+    with pytest.raises(SwmError) as e:       # a tree of another height
+        circuits(2).witness_at(tree, first[:2], ops[:1])
+    assert e.value.code == -1
+    assert np.array_equal(_nodes(c, tree), before)
+    for h in (1, 10):
+        with pytest.raises(SwmError):
+            L.PedersenAccountUpdateCircuit(crh[0], crh[1], h)
+    # and the same call with the right table goes through
+    _, after, old, new, flags, _ = c.witness_at(tree, first, ops)
+    assert list(flags) == [1, 1] and new[0] == old[1] and after[3] == AM.key(3) + bytes(8)
+
+
+def test_a_chunk_seam_inside_a_block_of_five(circuits, world, fresh_tree, oracle):
+    """The host form with its stage cap moved (swm_selftest_witness_stage): five operations at a cap of 2 items' witness bytes + 5 go
+    in chunks of 2, 2 and 1.  Operation i + 1 is witnessed against the state operation i left, so a seam that lost the table or the
+    tree would show."""
+    height = 3
+    table, block, _, _ = world(height)
+    block = block[:5]
+    c, tree, whole = circuits(height), fresh_tree(height, table), fresh_tree(height, table)
+    item = 32 * c.shape()[1]
+    with c.ctx.selftest_witness_stage(2 * item + 5):
+        got = _run(c, tree, table, [t["op"] for t in block])
+    _check_block(oracle, height, block, got, "chunks of 2, 2 and 1")
+    assert got[1] == block[-1]["table"] and tree.root() == block[-1]["new_root"]
+    one = _run(c, whole, table, [t["op"] for t in block])      # one chunk: the default cap
+    assert np.array_equal(got[0], one[0]) and got[1:4] == one[1:4]
+    assert np.array_equal(_nodes(c, tree), _nodes(c, whole))
+
+
+@pytest.fixture(scope="module")
+def system(W, params, world):
+    """The builder's systems of the block's first two operations at height 3 (a registration, then the balance update of the same
+    leaf); the first one's matrices serve every operation."""
+    out = []
+    for t in world(3)[1][:2]:
+        cs, public = AM.build(params, 3, t)
+        assert public[:2] == [t["old_root"], t["new_root"]]
+        out.append((cs, public))
+    return out, out[0][0].pack()
+
+
+@pytest.fixture(scope="module")
+def keys(M, system):
+    (cs, _), packed = system[0][0], system[1]
+    nnz = max(int(m[0][-1]) for m in packed.mats)
+    srs = M.MarlinInst.universal_setup(cs.num_constraints, len(cs.instance) + len(cs.witness), nnz, M.generate_rand())
+    pk, vk = M.MarlinInst.index_from_constraint_system(srs, packed)
+    srs.free()
+    yield pk, vk
+    pk.free()
+
+
+def test_proof_equals_the_builders(M, W, L, circuits, world, fresh_tree, system, keys):
+    """swm_pedersen_account_update_prove_at is byte-identical to generate_proof on the builder's system from the same rng state, for
+    the registration and for the balance update under the ONE key; verify_update accepts the proof with its eight public inputs and
+    rejects it with each of them changed in turn; a key of another shape gives SWM_ERR_MISMATCH with the tree untouched."""
+    from simpleworks_amd import serialization as Ser
+    table, block = world(3)[:2]
+    pk, vk = keys
+    c, tree = circuits(3), fresh_tree(3, table)
+    accounts = table
+    for t, (cs, want_public) in zip(block[:2], system[0]):
+        want = Ser.serialize_proof(M.generate_proof(cs, pk, M.generate_rand()))
+        got, public, flag, status, accounts = M.generate_pedersen_account_update_proof(pk, c, tree, accounts, t["op"], M.generate_rand())
+        assert got == want and public == want_public and (flag, status) == (1, 0) and accounts == t["table"]
+        assert tree.root() == t["new_root"]
+        assert L.verify_update(vk, public, got, M.generate_rand())
+        for k in range(8):
+            other = list(public)
+            other[k] = (other[k] + 1) % R
+            assert not L.verify_update(vk, other, got, M.generate_rand()), k
+    # a refused operation has no proof and leaves tree and table alone
+    none, public, flag, status, again = M.generate_pedersen_account_update_proof(pk, c, tree, accounts, block[0]["op"], M.generate_rand())
+    assert none is None and public[0] == public[1] == block[1]["new_root"] and (flag, status) == (0, AM.ST_OCCUPIED) and again == accounts
+    # a key of another shape: refused before anything runs
+    small = W.synthetic_circuit(32, 3, 5)
+    srs = M.generate_universal_srs(64, 64, 256, M.generate_rand())
+    other_pk, _ = M.generate_proving_and_verifying_keys(srs, small)
+    srs.free()
+    try:
+        before = _nodes(c, tree).copy()
+        with pytest.raises(M.MarlinError) as e:
+            M.generate_pedersen_account_update_proof(other_pk, c, tree, accounts, block[2]["op"], M.generate_rand())
+        assert e.value.code == -8
+        with pytest.raises(M.MarlinError) as e:
+            M.generate_pedersen_account_update_proofs(other_pk, c, tree, accounts, [block[2]["op"]], M.generate_rand())
+        assert e.value.code == -8
+        assert np.array_equal(_nodes(c, tree), before) and tree.root() == block[1]["new_root"]
+    finally:
+        other_pk.free()
+
+
+def test_block_of_proofs_equals_single_calls(M, L, circuits, world, fresh_tree, keys):
+    """swm_pedersen_account_update_prove_many_at over [a registration, a refused one, the balance update]: lens = 0 for the refused
+    one, and proofs, public inputs and the table are those of three single calls from the same rng state."""
+    table, block = world(3)[:2]
+    pk, vk = keys
+    ops = [block[0]["op"], block[0]["op"], block[1]["op"]]
+    c, tree, twin = circuits(3), fresh_tree(3, table), fresh_tree(3, table)
+    proofs, public, flags, status, after = M.generate_pedersen_account_update_proofs(pk, c, tree, table, ops, M.generate_rand())
+    assert flags == [1, 0, 1] and status == [0, AM.ST_OCCUPIED, 0] and after == block[1]["table"]
+    assert [p is not None for p in proofs] == [True, False, True] and tree.root() == block[1]["new_root"]
+    assert public[1][0] == public[1][1] == public[0][1] == public[2][0]
+    rng = M.generate_rand()
+    accounts = table
+    for op, proof, pub in zip(ops, proofs, public):
+        single, pub1, _, _, accounts = M.generate_pedersen_account_update_proof(pk, c, twin, accounts, op, rng)
+        assert single == proof and pub1 == pub
+        if proof is not None:
+            assert L.verify_update(vk, pub, proof, M.generate_rand())
+    assert accounts == after
+    assert M.generate_pedersen_account_update_proofs(pk, c, tree, after, [], M.generate_rand())[0] == []
+
+
+def test_the_chain_from_the_blank_pedersen_root(M, L, params):
+    """A default (Pedersen) State at height 3 from its blank root: three register_proved, two update_balance_proved, then one block
+    through apply_pedersen_transactions.  Every proof verifies, each proof's new_root is the next one's old_root, the first old_root
+    is State::new's blank root and the last new_root is state.root()."""
+    from simpleworks_amd import hash as H, schnorr
+    rng = M.generate_rand()
+    pp = L.Parameters.sample(rng, poseidon=H.PoseidonParameters.from_json(POSEIDON))
+    state, twin = L.State(8, pp), L.State(8, pp)
+    try:
+        assert state.account_tree == "pedersen" and state.account_merkle_tree.height() == 3
+        blank_root = state.root()
+        assert blank_root == twin.root()
+        people = [schnorr.keygen(pp.sig_params, rng) for _ in range(3)]
+        links = []      # (verifying key, verifier, public inputs, proof)
+        vk = state.pedersen_update_keys(rng)[2]
+        for pub_key, _ in people:
+            acc, proof, public = state.register_proved(pub_key, rng)
+            assert acc == twin.register(pub_key) and public[2:] == [acc, pub_key[0], pub_key[1], 0, 0, 1]
+            links.append((vk, L.verify_update, public, proof))
+        for acc, amount in ((1, 10), (3, (1 << 64) - 2)):
+            proof, public = state.update_balance_proved(acc, amount, rng)
+            assert twin.update_balance(acc, amount) is True
+            assert public[2:] == [acc, people[acc - 1][0][0], people[acc - 1][0][1], 0, amount, 0]
+            links.append((vk, L.verify_update, public, proof))
+        assert state.update_balance_proved(0, 1, rng) is None and state.next_available_account == twin.next_available_account == 4
+        assert state.pub_key_to_id == twin.pub_key_to_id and state.root() == twin.root()
+        txs = [L.Transaction.create(pp, 1, 2, 4, people[0][1], rng), L.Transaction.create(pp, 2, 3, 1, people[1][1], rng)]
+        got = state.apply_pedersen_transactions(pp, txs, rng, prove=True)
+        tvk = state.pedersen_transfer_keys(rng)[2]
+        for tx, (applied, proof, public) in zip(txs, got):
+            assert applied and twin.apply_transaction(pp, tx, rng, prove=False) is True
+            links.append((tvk, L.verify_transfer, public, proof))
+        root = blank_root
+        for key, verify, public, proof in links:
+            assert proof is not None and verify(key, public, proof, rng)
+            assert public[0] == root and public[1] != root
+            root = public[1]
+        assert root == state.root() == twin.root()
+        assert {i: a.balance for i, a in state.id_to_account_info.items()} == {i: a.balance for i, a in twin.id_to_account_info.items()}
+        # a block through apply_pedersen_updates without proofs: a refused registration in the middle leaves the books as they were
+        got = state.apply_pedersen_updates(pp, [("balance", 2, 77), ("register", 2, people[0][0]), ("balance", 0, 1)], rng, prove=False)
+        assert [g[:2] for g in got] == [(True, None), (False, None), (False, None)] and got[1][2][0] == got[1][2][1] == state.root()
+        assert twin.update_balance(2, 77) is True and state.root() == twin.root() and state.id_to_account_info[2].balance == 77
+        assert state.pub_key_to_id == twin.pub_key_to_id and state.next_available_account == 4
+        poseidon = L.State(8, pp, account_tree="poseidon")
+        try:
+            with pytest.raises(ValueError):
+                poseidon.apply_pedersen_updates(pp, [("balance", 1, 1)], rng)
+            with pytest.raises(ValueError):
+                poseidon.pedersen_update_keys(rng)
+        finally:
+            poseidon.free()
+    finally:
+        state.free()
+        twin.free()
+        pp.free()
