@@ -923,7 +923,9 @@ int swm_pedersen_payment_prove_many_at(swm_ctx *ctx, const swm_pk *pk, const swm
  * swm_transfer_witness_at: `tree` is a resident tree of the circuit's parameters and height with 72-byte leaves (otherwise
  * SWM_ERR_INVALID_ARG); accounts_inout is the account table, ALL 2^L leaves of 72 bytes in id order, an all-zero leaf = no account.
  * One launch hashes the table and compares it with the tree's leaf level (an all-zero leaf against the zero digest): any
- * difference refuses the WHOLE call with SWM_ERR_INVALID_ARG and leaves tree and table as they were.  Then transfer i is witnessed
+ * difference refuses the WHOLE call with SWM_ERR_INVALID_ARG and leaves tree and table as they were.  After a refused table the
+ * caller's old_roots, new_roots, flags and status hold what they held on entry (in _prove_many_at the zeros written at entry, and
+ * lens stays zero).  Then transfer i is witnessed
  * against the tree and the table as transfers 0 .. i-1 left them, and APPLIED to both exactly when flags[i] has bits 0 .. 3 set and
  * status[i] is 0.  flags (one byte per transfer): bit 0 = the signature verifies under the sender leaf's key, bit 1 = amount <=
  * balance, bit 2 = rbalance + amount < 2^64, bit 3 = both leaves hold an account, bit 4 = applied.  status (uint32 per transfer): bit
@@ -1063,7 +1065,8 @@ int swm_pedersen_rollup_prove_at(swm_ctx *ctx, const swm_pk *pk, const swm_peder
  * SWM_ERR_INVALID_ARG); accounts_inout is the account table, ALL 2^L leaves of 72 bytes in id order, an all-zero leaf = no account.
  * One launch hashes the table and compares it with the tree's leaf level (an all-zero leaf against the zero digest): any
  * difference refuses the WHOLE call with SWM_ERR_INVALID_ARG and leaves tree and table as they were; so does a kind above 1,
- * before anything runs.  Operation i is ids[i] (1 byte), kinds[i] (1 byte: 0 = set balance, 1 = register), keys_xy[i] (64 bytes,
+ * before anything runs.  After a refused table the caller's old_roots, new_roots, flags and status hold what they held on entry (in
+ * _prove_many_at the zeros written at entry, and lens stays zero).  Operation i is ids[i] (1 byte), kinds[i] (1 byte: 0 = set balance, 1 = register), keys_xy[i] (64 bytes,
  * read for a registration only; a balance update keeps the leaf's key) and balances[i] (8 bytes little-endian: the new balance, or a
  * registration's initial balance).  It is witnessed against tree and table as operations 0 .. i-1 left them and APPLIED to both
  * exactly when status[i] is 0; flags[i] bit 0 = applied.  status (uint32 per operation): bit 0 = a registration's key coordinate

@@ -23,6 +23,9 @@
 // hashes the new leaf and walks it to the root, P_leaf + L dependent permutations, writing each digest into the nodes (in LDS) after
 // the level's loads.  A refused one hashes nothing, writes nothing and leaves zero digests for the update block.  Every lane of the
 // wave computes the same; lane 0 stores.
+//
+// The host layer (chunks, the verdict-first results step, the block loop, the entries) is ledger_witness_host.h's over
+// AccountUpdateUnit; this unit also defines account_update_prove_item, the prover call of both trees' units.
 #include <hip/hip_runtime.h>
 
 #include <string.h>
@@ -33,11 +36,12 @@
 #include "context.h"
 #include "ff.cuh"
 #include "host/account_update_shape.h"
+#include "ledger_bytes.cuh"
+#include "ledger_witness_host.h"
 #include "merkle_nodes.cuh"
 #include "poseidon.h"
 #include "poseidon_tree.h"
 #include "swmarlin.h"
-#include "witness_host.h"
 #include "witness_runs.h"
 
 struct swm_account_update_circuit {
@@ -49,29 +53,11 @@ namespace swm {
 
 static constexpr unsigned AU_LANES = 256;                              // phase 0: a lane per leaf, ids are one byte
 static constexpr unsigned AU_MAX_LEAVES = 1u << (PY_MAX_HEIGHT - 1);   // 256
-static constexpr unsigned AU_FLAG_APPLIED = 1;
-static constexpr unsigned AU_ST_KEY = 1, AU_ST_ID = 2, AU_ST_OCCUPIED = 4, AU_ST_BLANK = 8, AU_ST_ZERO = 16;
-static constexpr unsigned AU_KIND_REGISTER = 1;  // kinds[i]: 0 = set balance, 1 = register
-
-__device__ __forceinline__ uint64_t au_load_u64(const uint8_t* b) {
-    uint64_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) v |= (uint64_t)b[k] << (8 * k);
-    return v;
-}
 
 __device__ __forceinline__ bool au_blank(const uint8_t* leaf) {
     unsigned any = 0;
     for (unsigned k = 0; k < PY_LEAF_LEN; k++) any |= leaf[k];
     return any == 0;
-}
-
-__device__ __forceinline__ bool au_canonical(const uint8_t* b) {  // 32 little-endian bytes below r
-    Fr x;
-#pragma unroll
-    for (int w = 0; w < 8; w++)
-        x.v[w] = (uint32_t)b[4 * w] | (uint32_t)b[4 * w + 1] << 8 | (uint32_t)b[4 * w + 2] << 16 | (uint32_t)b[4 * w + 3] << 24;
-    return pt_canonical(x);
 }
 
 __device__ __forceinline__ Fr au_select(bool c, const Fr& a, const Fr& b) {
@@ -81,22 +67,8 @@ __device__ __forceinline__ Fr au_select(bool c, const Fr& a, const Fr& b) {
     return x;
 }
 
-struct AuIn {  // the block on the device, n = count
-    const uint8_t *ids, *kinds, *keys, *balances;  // n | n | 64 n | 8 n bytes
-};
-
-struct AuOut {              // what the advance kernel leaves for the record launches and the bits kernel
-    uint32_t* dig;          // 2 x n x (L + 1) x 8 words: the old path's nodes | the new leaf's walk
-    uint32_t* sib;          // n x L x 8 words: one sibling array, it serves both
-    uint8_t* leaves;        // 2 x n x 72 bytes: key || old_balance | key || new_balance
-    uint64_t* idx;          // n: the id masked to the tree
-    uint32_t* roots;        // 2 x n x 8 words: old roots | new roots
-    uint8_t* flags;         // n
-    uint32_t* status;       // n
-    uint32_t* verdict;      // 1: nonzero when the table is not the tree's
-};
-
-// One workgroup.  nodes, accounts: read, and written back at the end unless the call is refused.
+// One workgroup.  nodes, accounts: read, and written back at the end unless the call is refused.  O.leaves: key || old_balance |
+// key || new_balance.
 __global__ void __launch_bounds__(AU_LANES) account_update_advance_kernel(const uint4* __restrict__ table, PtParams P, unsigned levels,
                                                                           size_t count, uint32_t* __restrict__ nodes,
                                                                           uint8_t* __restrict__ accounts, AuIn I, AuOut O) {
@@ -136,7 +108,7 @@ __global__ void __launch_bounds__(AU_LANES) account_update_advance_kernel(const 
         const uint8_t* leaf = s_acc + PY_LEAF_LEN * m;
         const uint8_t* key = kind == AU_KIND_REGISTER ? I.keys + 64 * t : leaf;
         const bool blank = au_blank(leaf);
-        const uint64_t old_value = kind == AU_KIND_REGISTER ? 0 : au_load_u64(leaf + 64), new_value = au_load_u64(I.balances + 8 * t);
+        const uint64_t old_value = kind == AU_KIND_REGISTER ? 0 : le_load_u64(leaf + 64), new_value = le_load_u64(I.balances + 8 * t);
         uint8_t* out_old = O.leaves + PY_LEAF_LEN * t;
         uint8_t* out_new = O.leaves + PY_LEAF_LEN * (count + t);
         unsigned any = 0;
@@ -153,7 +125,7 @@ __global__ void __launch_bounds__(AU_LANES) account_update_advance_kernel(const 
         unsigned st = 0;
         if (id >> levels) st = AU_ST_ID;  // there is no leaf to say more about
         else if (kind == AU_KIND_REGISTER)
-            st = (au_canonical(key) && au_canonical(key + 32) ? 0u : AU_ST_KEY) | (blank ? 0u : AU_ST_OCCUPIED) | (any ? 0u : AU_ST_ZERO);
+            st = (le_below_r(key) && le_below_r(key + 32) ? 0u : AU_ST_KEY) | (blank ? 0u : AU_ST_OCCUPIED) | (any ? 0u : AU_ST_ZERO);
         else
             st = blank ? AU_ST_BLANK : 0u;
         const bool applied = st == 0;  // the same in every lane
@@ -238,11 +210,6 @@ __global__ void __launch_bounds__(AU_LANES) account_update_bits_kernel(AuBitsArg
     q[1] = make_uint4(v.v[4], v.v[5], v.v[6], v.v[7]);
 }
 
-// "account_update.aux" for n operations: every piece a multiple of 8 bytes but the last two
-static size_t au_aux_bytes(size_t n, size_t levels) {
-    return 4 * (2 * n * (levels + 1) * 8 + n * levels * 8) + 8 * n + 64 * n + 4 * n + 8 + 2 * PY_LEAF_LEN * n + n + 64;
-}
-
 // n operations on device buffers, in order: d_accounts and the tree's nodes are advanced.  d_w 16-byte aligned; item i's witnesses
 // from d_w + i * stride (stride >= the shape's num_witness).
 static int au_run(swm_ctx* ctx, const swm_account_update_circuit* c, swm_poseidon_tree* tree, uint8_t* d_accounts, const AuIn& in, size_t n,
@@ -250,17 +217,8 @@ static int au_run(swm_ctx* ctx, const swm_account_update_circuit* c, swm_poseido
     const AccountUpdateShape& s = c->shape;
     const swm_poseidon* p = c->tree.params;
     const unsigned levels = (unsigned)s.levels;
-    uint8_t* aux = nullptr;
-    SWM_TRY(scratch(ctx, "account_update.aux", au_aux_bytes(n, levels), (void**)&aux));
     AuOut O;
-    O.dig = reinterpret_cast<uint32_t*>(aux);
-    O.sib = O.dig + 2 * n * (levels + 1) * 8;
-    O.idx = reinterpret_cast<uint64_t*>(O.sib + n * levels * 8);
-    O.roots = reinterpret_cast<uint32_t*>(O.idx + n);
-    O.status = O.roots + 16 * n;
-    O.verdict = O.status + n;
-    O.leaves = reinterpret_cast<uint8_t*>(O.verdict + 2);
-    O.flags = O.leaves + 2 * PY_LEAF_LEN * n;
+    SWM_TRY(account_update_aux(ctx, "account_update.aux", n, levels, &O));
     SWM_LAUNCH(ctx, "account_update_advance", account_update_advance_kernel, dim3(1), dim3(AU_LANES), pt_lds(p), pt_table(p), pt_params(p),
                levels, n, reinterpret_cast<uint32_t*>(tree->d_nodes), d_accounts, in, O);
     const size_t dig = n * (levels + 1) * 8, leaves = PY_LEAF_LEN * n;
@@ -274,51 +232,6 @@ static int au_run(swm_ctx* ctx, const swm_account_update_circuit* c, swm_poseido
     SWM_LAUNCH(ctx, "account_update_bits", account_update_bits_kernel, dim3((unsigned)((s.num_witness * n + AU_LANES - 1) / AU_LANES)),
                dim3(AU_LANES), 0, A, in.ids, (const uint8_t*)O.leaves, (const uint32_t*)O.dig, (const uint8_t*)O.flags, d_w);
     *out = O;
-    return SWM_OK;
-}
-
-static int au_check_tree(swm_ctx* ctx, const char* what, const swm_account_update_circuit* c, const swm_poseidon_tree* t) {
-    if (t->params != c->tree.params || t->height != c->shape.height || t->leaf_len != PY_LEAF_LEN)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: a tree of height %zu with %zu-byte leaves for a circuit of height %zu with %zu-byte leaves, "
-                       "or other parameters", what, t->height, t->leaf_len, c->shape.height, (size_t)PY_LEAF_LEN);
-    return SWM_OK;
-}
-
-struct AuBlock {  // the caller's arrays of a whole block; roots may be NULL
-    const uint8_t *ids, *kinds, *keys, *balances;
-    uint8_t *old_roots, *new_roots, *flags;
-    uint32_t* status;
-};
-
-// Chunk [base, base + n) of a block: staged, run, its small results copied out and waited for.  The witnesses stay in
-// "account_update.w" (*d_w).  leaves (may be NULL): the chunk's 2 x n x 72 leaf bytes, for the prover's public input.
-static int au_chunk(swm_ctx* ctx, const char* what, const swm_account_update_circuit* c, swm_poseidon_tree* tree, uint8_t* d_accounts,
-                    const AuBlock& b, size_t base, size_t n, Fr** d_w, uint8_t* leaves) {
-    const size_t item = c->shape.num_witness * sizeof(Fr);
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    SWM_TRY(scratch(ctx, "stage.a", n * (64 + 8 + 2) + 16, (void**)&d_in));
-    AuIn in;
-    in.keys = d_in;
-    in.balances = d_in + 64 * n;
-    in.ids = d_in + 72 * n;
-    in.kinds = d_in + 73 * n;
-    SWM_HIP(ctx, hipMemcpyAsync(d_in, b.keys + 64 * base, 64 * n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(d_in + 64 * n, b.balances + 8 * base, 8 * n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(d_in + 72 * n, b.ids + base, n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(d_in + 73 * n, b.kinds + base, n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_TRY(scratch(ctx, "account_update.w", n * item + 16, (void**)&d_out));
-    AuOut O;
-    SWM_TRY(au_run(ctx, c, tree, d_accounts, in, n, (Fr*)d_out, c->shape.num_witness, &O));
-    uint32_t verdict = 0;
-    SWM_HIP(ctx, hipMemcpyAsync(&verdict, O.verdict, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (b.old_roots) SWM_HIP(ctx, hipMemcpyAsync(b.old_roots + 32 * base, O.roots, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (b.new_roots) SWM_HIP(ctx, hipMemcpyAsync(b.new_roots + 32 * base, O.roots + 8 * n, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (leaves) SWM_HIP(ctx, hipMemcpyAsync(leaves, O.leaves, 2 * PY_LEAF_LEN * n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(b.flags + base, O.flags, n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(b.status + base, O.status, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (verdict) return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: the account table is not the tree's leaf level", what);
-    *d_w = (Fr*)d_out;
     return SWM_OK;
 }
 
@@ -338,10 +251,11 @@ static Fr au_key_mont(const uint8_t* b) {
     return fp_from_std(s);
 }
 
-// the prover over one item's device witnesses; public input one, old_root, new_root, id, key_x, key_y, old_balance, new_balance, fresh
-static int au_prove_item(swm_ctx* ctx, const swm_pk* pk, const AccountUpdateShape& s, const uint8_t* old_root, const uint8_t* new_root,
-                         unsigned id, unsigned kind, const uint8_t* old_leaf, const uint8_t* new_leaf, const Fr* d_w, swm_rng* rng,
-                         unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
+// the prover over one item's device witnesses, for both trees; public input one, old_root, new_root, id, key_x, key_y, old_balance,
+// new_balance, fresh
+int account_update_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size_t num_constraints, const uint8_t* old_root,
+                              const uint8_t* new_root, unsigned id, unsigned kind, const uint8_t* old_leaf, const uint8_t* new_leaf, const Fr* d_w,
+                              swm_rng* rng, unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
     uint64_t old_balance = 0, new_balance = 0;
     for (int k = 0; k < 8; k++) {
         old_balance |= (uint64_t)old_leaf[64 + k] << (8 * k);
@@ -353,76 +267,20 @@ static int au_prove_item(swm_ctx* ctx, const swm_pk* pk, const AccountUpdateShap
     const Fr inst[AU_INSTANCE] = {fp_one<Fr>(), fp_from_std(r0), fp_from_std(r1), fp_from_u64<Fr>(id), au_key_mont(new_leaf),
                                   au_key_mont(new_leaf + 32), fp_from_u64<Fr>(old_balance), fp_from_u64<Fr>(new_balance),
                                   fp_from_u64<Fr>(kind)};
-    return prove_device_witness(ctx, pk, AU_INSTANCE, s.num_witness, s.num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
+    return prove_device_witness(ctx, pk, AU_INSTANCE, num_witness, num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
 }
 
-// the account table (2^levels leaves of 72 bytes) into the unit's scratch buffer
-static int au_upload_accounts(swm_ctx* ctx, const uint8_t* accounts, size_t bytes, uint8_t** d_accounts) {
-    SWM_TRY(scratch(ctx, "account_update.accounts", bytes + 16, (void**)d_accounts));
-    SWM_HIP(ctx, hipMemcpyAsync(*d_accounts, accounts, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return SWM_OK;
-}
-
-// the table after a chunk and (witness not NULL) the chunk's witnesses back to the host, waited for
-static int au_download(swm_ctx* ctx, uint8_t* accounts, const uint8_t* d_accounts, size_t table_bytes, uint8_t* witness, const Fr* d_w,
-                       size_t witness_bytes) {
-    SWM_HIP(ctx, hipMemcpyAsync(accounts, d_accounts, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (witness) SWM_HIP(ctx, hipMemcpyAsync(witness, d_w, witness_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SWM_OK;
-}
-
-// The block in chunks.  witness (may be NULL): the host copy of every item; pk (may be NULL): one proof per applied operation.
-static int au_block(swm_ctx* ctx, const char* what, const swm_pk* pk, const swm_account_update_circuit* c, swm_poseidon_tree* tree,
-                    uint8_t* accounts, const AuBlock& b, size_t count, uint64_t* witness, swm_rng* rng, unsigned prove_flags,
-                    uint8_t* proofs_out, size_t proof_cap, size_t* lens) {
-    const AccountUpdateShape& s = c->shape;
-    const size_t num_witness = s.num_witness, item = num_witness * sizeof(Fr), table_bytes = PY_LEAF_LEN << s.levels;
-    std::vector<uint8_t> roots, leaves;  // the prover needs the root pairs whether the caller asked for them or not
-    AuBlock blk = b;
-    if (pk && (!b.old_roots || !b.new_roots)) {
-        roots.resize(64 * count);
-        if (!b.old_roots) blk.old_roots = roots.data();
-        if (!b.new_roots) blk.new_roots = roots.data() + 32 * count;
+struct AccountUpdateUnit {  // what ledger_witness_host.h drives
+    using Circuit = swm_account_update_circuit;
+    using Tree = swm_poseidon_tree;
+    static constexpr const char* name = "account_update";
+    static constexpr const char* accounts_scratch = "account_update.accounts";
+    static constexpr const char* witness_scratch = "account_update.w";
+    static constexpr auto run = au_run;
+    static int check_tree(swm_ctx* ctx, const char* what, const Circuit* c, const Tree* t) {
+        return ledger_check_tree(ctx, what, c->tree.params, c->shape.height, t);
     }
-    uint8_t* d_accounts = nullptr;
-    {
-        SWM_ON_DEVICE(ctx);
-        SWM_TRY(drained(ctx, au_upload_accounts(ctx, accounts, table_bytes, &d_accounts)));
-    }
-    for (const WitnessChunk ch : WitnessChunks(witness_stage_items(ctx, item), count)) {
-        Fr* d_w = nullptr;
-        if (pk) leaves.resize(2 * PY_LEAF_LEN * ch.count);
-        {
-            SWM_ON_DEVICE(ctx);
-            SWM_TRY(drained(ctx, au_chunk(ctx, what, c, tree, d_accounts, blk, ch.base, ch.count, &d_w, pk ? leaves.data() : nullptr)));
-            // the tree is advanced from here on: the table goes back with it, whatever the prover does below
-            SWM_TRY(drained(ctx, au_download(ctx, accounts, d_accounts, table_bytes,
-                                             witness ? reinterpret_cast<uint8_t*>(witness) + ch.base * item : nullptr, d_w, ch.count * item)));
-        }
-        for (size_t i = ch.base; pk && i < ch.base + ch.count; i++) {
-            if (!(blk.flags[i] & AU_FLAG_APPLIED)) continue;
-            const size_t k = i - ch.base;
-            size_t len = 0;
-            SWM_TRY(au_prove_item(ctx, pk, s, blk.old_roots + 32 * i, blk.new_roots + 32 * i, b.ids[i], b.kinds[i], leaves.data() + PY_LEAF_LEN * k,
-                                  leaves.data() + PY_LEAF_LEN * (ch.count + k), d_w + k * num_witness, rng, prove_flags,
-                                  proofs_out + i * proof_cap, proof_cap, &len));
-            lens[i] = len;
-        }
-    }
-    return SWM_OK;
-}
-
-// what both block entries refuse before anything runs
-static int au_check_block(swm_ctx* ctx, const char* what, const swm_account_update_circuit* c, const swm_poseidon_tree* tree,
-                          const uint8_t* kinds, size_t count) {
-    SWM_TRY(au_check_tree(ctx, what, c, tree));
-    if (count > 0x7FFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: %zu operations in one call", what, count);
-    for (size_t i = 0; i < count; i++)
-        if (kinds[i] > AU_KIND_REGISTER)
-            return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: operation %zu: kind %u (0 = set balance, 1 = register)", what, i, (unsigned)kinds[i]);
-    return SWM_OK;
-}
+};
 
 }  // namespace swm
 
@@ -449,48 +307,24 @@ void swm_account_update_circuit_destroy(swm_ctx* ctx, swm_account_update_circuit
 int swm_account_update_witness_at(swm_ctx* ctx, const swm_account_update_circuit* c, swm_poseidon_tree* tree, uint8_t* accounts_inout,
                                   const uint8_t* ids, const uint8_t* kinds, const uint8_t* keys_xy, const uint8_t* balances, size_t count,
                                   uint64_t* witnesses_out, uint8_t* old_roots, uint8_t* new_roots, uint8_t* flags, uint32_t* status) {
-    const char* what = "account_update_witness_at";
-    if (!ctx || !c || !tree || !accounts_inout ||
-        (count && (!ids || !kinds || !keys_xy || !balances || !witnesses_out || !old_roots || !new_roots || !flags || !status)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: bad arguments", what);
-    SWM_TRY(au_check_block(ctx, what, c, tree, kinds, count));
-    if (!count) return SWM_OK;
-    const AuBlock b = {ids, kinds, keys_xy, balances, old_roots, new_roots, flags, status};
-    return au_block(ctx, what, nullptr, c, tree, accounts_inout, b, count, witnesses_out, nullptr, 0, nullptr, 0, nullptr);
+    return account_update_witness_at<AccountUpdateUnit>(ctx, c, tree, accounts_inout, ids, kinds, keys_xy, balances, count, witnesses_out, old_roots,
+                                                        new_roots, flags, status);
 }
 
 int swm_account_update_prove_many_at(swm_ctx* ctx, const swm_pk* pk, const swm_account_update_circuit* c, swm_poseidon_tree* tree,
                                      uint8_t* accounts_inout, const uint8_t* ids, const uint8_t* kinds, const uint8_t* keys_xy,
                                      const uint8_t* balances, size_t count, swm_rng* rng, unsigned prove_flags, uint8_t* proofs_out,
                                      size_t proof_cap, size_t* lens, uint8_t* old_roots, uint8_t* new_roots, uint8_t* flags, uint32_t* status) {
-    const char* what = "account_update_prove_many_at";
-    if (!ctx || !pk || !c || !tree || !accounts_inout || !rng ||
-        (count && (!ids || !kinds || !keys_xy || !balances || !proofs_out || !lens || !flags || !status)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: bad arguments", what);
-    SWM_TRY(au_check_block(ctx, what, c, tree, kinds, count));
-    // the tree is advanced before the proofs are made: a key of another shape is refused while nothing has changed
-    if (!pk_takes_shape(pk, c->shape.num_instance, c->shape.num_witness, c->shape.num_constraints))
-        return set_err(ctx, SWM_ERR_MISMATCH, "%s: the proving key is not that of this circuit", what);
-    if (!count) return SWM_OK;
-    for (size_t i = 0; i < count; i++) {  // whatever ends the call, every entry has been written
-        lens[i] = 0;
-        flags[i] = 0;
-        status[i] = 0;
-    }
-    const AuBlock b = {ids, kinds, keys_xy, balances, old_roots, new_roots, flags, status};
-    return au_block(ctx, what, pk, c, tree, accounts_inout, b, count, nullptr, rng, prove_flags, proofs_out, proof_cap, lens);
+    return account_update_prove_many_at<AccountUpdateUnit>(ctx, pk, c, tree, accounts_inout, ids, kinds, keys_xy, balances, count, rng, prove_flags,
+                                                           proofs_out, proof_cap, lens, old_roots, new_roots, flags, status);
 }
 
 int swm_account_update_prove_at(swm_ctx* ctx, const swm_pk* pk, const swm_account_update_circuit* c, swm_poseidon_tree* tree,
                                 uint8_t* accounts_inout, uint8_t id, uint8_t kind, const uint8_t key_xy[64], uint64_t balance, swm_rng* rng,
                                 unsigned prove_flags, uint8_t* proof_out, size_t cap, size_t* len, uint8_t old_root[32], uint8_t new_root[32],
                                 uint8_t* flag, uint32_t* status) {
-    if (!key_xy || !proof_out || !len || !old_root || !new_root || !flag || !status)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "account_update_prove_at: bad arguments");
-    uint8_t b[8];
-    for (int k = 0; k < 8; k++) b[k] = (uint8_t)(balance >> (8 * k));
-    return swm_account_update_prove_many_at(ctx, pk, c, tree, accounts_inout, &id, &kind, key_xy, b, 1, rng, prove_flags, proof_out, cap, len,
-                                            old_root, new_root, flag, status);
+    return account_update_prove_at<AccountUpdateUnit>(ctx, pk, c, tree, accounts_inout, id, kind, key_xy, balance, rng, prove_flags, proof_out,
+                                                      cap, len, old_root, new_root, flag, status);
 }
 
 }  // extern "C"

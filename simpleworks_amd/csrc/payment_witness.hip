@@ -29,6 +29,7 @@
 #include "context.h"
 #include "ff.cuh"
 #include "host/payment_shape.h"
+#include "ledger_bytes.cuh"
 #include "poseidon.h"
 #include "poseidon_tree.h"
 #include "schnorr.h"
@@ -69,13 +70,6 @@ struct PyArgs {
     unsigned levels;
 };
 
-__device__ __forceinline__ uint64_t py_load_u64(const uint8_t* b) {
-    uint64_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) v |= (uint64_t)b[k] << (8 * k);
-    return v;
-}
-
 __device__ __forceinline__ bool py_canonical(const uint32_t* p) {
     Fr x, r;
 #pragma unroll
@@ -103,7 +97,7 @@ __global__ void __launch_bounds__(PY_LANES) payment_bits_kernel(PyArgs A, const 
     unsigned bit;
     size_t at;
     if (e < 2 * PY_AMOUNT_BITS) {
-        const uint64_t balance = py_load_u64(sender_leaves + PY_LEAF_LEN * item + 64), amount = py_load_u64(msg + 2);
+        const uint64_t balance = le_load_u64(sender_leaves + PY_LEAF_LEN * item + 64), amount = le_load_u64(msg + 2);
         const uint64_t v = e < PY_AMOUNT_BITS ? balance : balance - amount;
         bit = (unsigned)(v >> (e & 63)) & 1u;
         at = A.balance_at + e;  // diff follows balance
@@ -200,10 +194,10 @@ int py_check(swm_ctx* ctx, const char* what, size_t height, const uint8_t* msgs,
     return SWM_OK;
 }
 
-static int py_check_tree(swm_ctx* ctx, const char* what, const swm_payment_circuit* c, const swm_poseidon_tree* t) {
-    if (t->params != c->tree.params || t->height != c->shape.height || t->leaf_len != PY_LEAF_LEN)
+int ledger_check_tree(swm_ctx* ctx, const char* what, const swm_poseidon* params, size_t height, const swm_poseidon_tree* t) {
+    if (t->params != params || t->height != height || t->leaf_len != PY_LEAF_LEN)
         return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: a tree of height %zu with %zu-byte leaves for a circuit of height %zu with %zu-byte leaves, "
-                       "or other parameters", what, t->height, t->leaf_len, c->shape.height, (size_t)PY_LEAF_LEN);
+                       "or other parameters", what, t->height, t->leaf_len, height, (size_t)PY_LEAF_LEN);
     return SWM_OK;
 }
 
@@ -271,7 +265,9 @@ struct PaymentUnit {  // what ledger_witness_host.h drives
     using Tree = swm_poseidon_tree;
     static constexpr const char* name = "payment";
     static constexpr auto run = py_run;
-    static constexpr auto check_tree = py_check_tree;
+    static int check_tree(swm_ctx* ctx, const char* what, const Circuit* c, const Tree* t) {
+        return ledger_check_tree(ctx, what, c->tree.params, c->shape.height, t);
+    }
     static const uint8_t* root_node(const Tree* t) { return t->d_nodes + 32 * (t->num_nodes() - 1); }
 };
 

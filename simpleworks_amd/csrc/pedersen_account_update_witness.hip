@@ -23,6 +23,9 @@
 // over the wave's 64 lanes) and walks it to the root (128 windows per level): 1 + L dependent hashes, each level's node written
 // after a barrier that follows that level's reads.  A refused one hashes nothing, writes neither nodes nor table, and leaves the
 // gathered old path in both digest arrays, so that the record launches read initialised memory.
+//
+// The host layer (chunks, the verdict-first results step, the block loop, the entries, the prover call) is ledger_witness_host.h's
+// over PedersenAccountUpdateUnit, with the vocabulary (AuIn, AuOut, flag, status and kind constants) account_update_witness.hip uses.
 #include <hip/hip_runtime.h>
 
 #include <string.h>
@@ -33,12 +36,13 @@
 #include "context.h"
 #include "ff.cuh"
 #include "host/pedersen_account_update_shape.h"
+#include "ledger_bytes.cuh"
+#include "ledger_witness_host.h"
 #include "merkle_nodes.cuh"
 #include "merkle_tree.h"
 #include "pedersen.cuh"
 #include "pedersen.h"
 #include "swmarlin.h"
-#include "witness_host.h"
 #include "witness_runs.h"
 
 struct swm_pedersen_account_update_circuit {
@@ -52,47 +56,14 @@ namespace swm {
 static constexpr unsigned PAU_LANES = 64;                                  // one wave: a Pedersen hash takes it whole
 static constexpr unsigned PAU_BITS_LANES = 256;
 static constexpr unsigned PAU_MAX_LEAVES = 1u << (PP_MAX_HEIGHT - 1);      // 256
-static constexpr unsigned PAU_FLAG_APPLIED = 1;
-static constexpr unsigned PAU_ST_KEY = 1, PAU_ST_ID = 2, PAU_ST_OCCUPIED = 4, PAU_ST_BLANK = 8, PAU_ST_ZERO = 16;
-static constexpr unsigned PAU_KIND_REGISTER = 1;  // kinds[i]: 0 = set balance, 1 = register
+static_assert(PP_LEAF_LEN == PY_LEAF_LEN && PAU_INSTANCE == 9, "the block driver's leaf, the prover's public input");
 
-__device__ __forceinline__ uint64_t pau_load_u64(const uint8_t* b) {
-    uint64_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) v |= (uint64_t)b[k] << (8 * k);
-    return v;
-}
-
-__device__ __forceinline__ bool pau_canonical(const uint8_t* b) {  // 32 little-endian bytes below r
-    Fr x, r;
-#pragma unroll
-    for (int w = 0; w < 8; w++) {
-        x.v[w] = (uint32_t)b[4 * w] | (uint32_t)b[4 * w + 1] << 8 | (uint32_t)b[4 * w + 2] << 16 | (uint32_t)b[4 * w + 3] << 24;
-        r.v[w] = FrParams::P[w];
-    }
-    return fp_cmp_std(x, r) < 0;
-}
-
-struct PauIn {  // the block on the device, n = count
-    const uint8_t *ids, *kinds, *keys, *balances;  // n | n | 64 n | 8 n bytes
-};
-
-struct PauOut {             // what the advance kernel leaves for the record launches and the bits kernel
-    uint32_t* dig;          // 2 x n x (L + 1) x 8 words: the old path's nodes | the new leaf's walk
-    uint32_t* sib;          // n x L x 8 words: one sibling array, it serves both
-    uint8_t* leaves;        // 2 x n x 72 bytes: the old leaf (72 zero bytes for a registration) | key || new_balance
-    uint64_t* idx;          // n: the id masked to the tree
-    uint32_t* roots;        // 2 x n x 8 words: old roots | new roots
-    uint8_t* flags;         // n
-    uint32_t* status;       // n
-    uint32_t* verdict;      // 1: nonzero when the table is not the tree's (the check kernel's)
-};
-
-// One workgroup, one wave.  nodes, accounts: read, and written back at the end unless the call is refused.
+// One workgroup, one wave.  nodes, accounts: read, and written back at the end unless the call is refused.  O.leaves: the old leaf
+// (72 zero bytes for a registration) | key || new_balance; O.verdict is the check kernel's.
 __global__ void __launch_bounds__(PAU_LANES) pedersen_account_update_advance_kernel(const EdRow* __restrict__ leaf_table, unsigned leaf_windows,
                                                                                     const EdRow* __restrict__ inner_table, unsigned inner_windows,
                                                                                     unsigned levels, size_t count, uint32_t* __restrict__ nodes,
-                                                                                    uint8_t* __restrict__ accounts, PauIn I, Fr k2d, PauOut O) {
+                                                                                    uint8_t* __restrict__ accounts, AuIn I, Fr k2d, AuOut O) {
     __shared__ uint32_t s_nodes[(2 * PAU_MAX_LEAVES - 1) * 8];
     __shared__ uint8_t s_acc[PAU_MAX_LEAVES * PP_LEAF_LEN];
     __shared__ uint32_t s_msg[16];           // left || right of the level's hash
@@ -108,21 +79,21 @@ __global__ void __launch_bounds__(PAU_LANES) pedersen_account_update_advance_ker
 #pragma unroll 1
     for (size_t t = 0; t < count; t++) {
         const unsigned id = I.ids[t], kind = I.kinds[t], m = id & mask;
-        const bool reg = kind == PAU_KIND_REGISTER;
+        const bool reg = kind == AU_KIND_REGISTER;
         const uint8_t* leaf = s_acc + PP_LEAF_LEN * m;
         const uint8_t* key = reg ? I.keys + 64 * t : leaf;
-        const uint64_t new_value = pau_load_u64(I.balances + 8 * t);
+        const uint64_t new_value = le_load_u64(I.balances + 8 * t);
         // the decision: every lane reads the same bytes and takes the same one
         unsigned held = 0, any = 0;
         for (unsigned k = 0; k < PP_LEAF_LEN; k++) held |= leaf[k];
         for (unsigned k = 0; k < 64; k++) any |= key[k];
         any |= new_value != 0;
         unsigned st = 0;
-        if (id >> levels) st = PAU_ST_ID;  // there is no leaf to say more about
+        if (id >> levels) st = AU_ST_ID;  // there is no leaf to say more about
         else if (reg)
-            st = (pau_canonical(key) && pau_canonical(key + 32) ? 0u : PAU_ST_KEY) | (held ? PAU_ST_OCCUPIED : 0u) | (any ? 0u : PAU_ST_ZERO);
+            st = (le_below_r(key) && le_below_r(key + 32) ? 0u : AU_ST_KEY) | (held ? AU_ST_OCCUPIED : 0u) | (any ? 0u : AU_ST_ZERO);
         else
-            st = held ? 0u : PAU_ST_BLANK;
+            st = held ? 0u : AU_ST_BLANK;
         const bool applied = st == 0;
         for (unsigned k = lane; k < PP_LEAF_LEN; k += PAU_LANES) {
             const uint8_t o = reg ? (uint8_t)0 : leaf[k], n = k < 64 ? key[k] : (uint8_t)(new_value >> (8 * (k - 64)));
@@ -189,7 +160,7 @@ __global__ void __launch_bounds__(PAU_LANES) pedersen_account_update_advance_ker
             for (unsigned k = lane; k < PP_LEAF_LEN; k += PAU_LANES) s_acc[PP_LEAF_LEN * m + k] = s_leaf[k];
         }
         if (lane == 0) {
-            O.flags[t] = applied ? (uint8_t)PAU_FLAG_APPLIED : (uint8_t)0;
+            O.flags[t] = applied ? (uint8_t)AU_FLAG_APPLIED : (uint8_t)0;
             O.status[t] = st;
         }
         __syncthreads();  // the root and the table as this operation leaves them
@@ -216,7 +187,7 @@ __global__ void __launch_bounds__(PAU_BITS_LANES) pedersen_account_update_bits_k
     const size_t item = (i >> 1) / A.num_witness;
     const unsigned e = (unsigned)((i >> 1) % A.num_witness), half = (unsigned)(i & 1);
     bool set = false;
-    if (flags[item] & PAU_FLAG_APPLIED) {
+    if (flags[item] & AU_FLAG_APPLIED) {
         if (e >= PAU_LOOSE_WITNESSES) return;
         const uint8_t* old_leaf = leaves + PP_LEAF_LEN * item;
         const uint8_t* new_leaf = leaves + PP_LEAF_LEN * (A.count + item);
@@ -235,28 +206,14 @@ __global__ void __launch_bounds__(PAU_BITS_LANES) pedersen_account_update_bits_k
 
 static const EdRow* pau_rows(const swm_pedersen* p) { return reinterpret_cast<const EdRow*>(p->d_table); }
 
-// "paccount_update.aux" for n operations: every piece a multiple of 8 bytes but the last two
-static size_t pau_aux_bytes(size_t n, size_t levels) {
-    return 4 * (2 * n * (levels + 1) * 8 + n * levels * 8) + 8 * n + 64 * n + 4 * n + 8 + 2 * PP_LEAF_LEN * n + n + 64;
-}
-
 // n operations on device buffers, in order: d_accounts and the tree's nodes are advanced.  d_w 16-byte aligned; item i's witnesses
 // from d_w + i * stride (stride >= the shape's num_witness).
-static int pau_run(swm_ctx* ctx, const swm_pedersen_account_update_circuit* c, swm_merkle_tree* tree, uint8_t* d_accounts, const PauIn& in,
-                   size_t n, Fr* d_w, size_t stride, PauOut* out) {
+static int pau_run(swm_ctx* ctx, const swm_pedersen_account_update_circuit* c, swm_merkle_tree* tree, uint8_t* d_accounts, const AuIn& in,
+                   size_t n, Fr* d_w, size_t stride, AuOut* out) {
     const PedersenAccountUpdateShape& s = c->shape;
     const unsigned levels = (unsigned)s.levels, n_leaves = 1u << levels;
-    uint8_t* aux = nullptr;
-    SWM_TRY(scratch(ctx, "paccount_update.aux", pau_aux_bytes(n, levels), (void**)&aux));
-    PauOut O;
-    O.dig = reinterpret_cast<uint32_t*>(aux);
-    O.sib = O.dig + 2 * n * (levels + 1) * 8;
-    O.idx = reinterpret_cast<uint64_t*>(O.sib + n * levels * 8);
-    O.roots = reinterpret_cast<uint32_t*>(O.idx + n);
-    O.status = O.roots + 16 * n;
-    O.verdict = O.status + n;
-    O.leaves = reinterpret_cast<uint8_t*>(O.verdict + 2);
-    O.flags = O.leaves + 2 * PP_LEAF_LEN * n;
+    AuOut O;
+    SWM_TRY(account_update_aux(ctx, "paccount_update.aux", n, levels, &O));
     uint32_t* d_nodes = reinterpret_cast<uint32_t*>(tree->d_nodes);
     SWM_HIP(ctx, hipMemsetAsync(O.verdict, 0, 4, ctx->stream));
     SWM_TRY(pedersen_transfer_check_run(ctx, c->leaf, d_nodes, d_accounts, n_leaves, O.verdict));
@@ -284,158 +241,17 @@ static int pau_run(swm_ctx* ctx, const swm_pedersen_account_update_circuit* c, s
     return SWM_OK;
 }
 
-static int pau_check_tree(swm_ctx* ctx, const char* what, const swm_pedersen_account_update_circuit* c, const swm_merkle_tree* t) {
-    if (t->leaf != c->leaf || t->inner != c->inner || t->height != c->shape.height || t->leaf_len != PP_LEAF_LEN)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: a tree of height %zu with %zu-byte leaves for a circuit of height %zu with %zu-byte leaves, "
-                       "or other parameters", what, t->height, t->leaf_len, c->shape.height, (size_t)PP_LEAF_LEN);
-    return SWM_OK;
-}
-
-struct PauBlock {  // the caller's arrays of a whole block; roots may be NULL
-    const uint8_t *ids, *kinds, *keys, *balances;
-    uint8_t *old_roots, *new_roots, *flags;
-    uint32_t* status;
+struct PedersenAccountUpdateUnit {  // what ledger_witness_host.h drives
+    using Circuit = swm_pedersen_account_update_circuit;
+    using Tree = swm_merkle_tree;
+    static constexpr const char* name = "pedersen_account_update";
+    static constexpr const char* accounts_scratch = "paccount_update.accounts";
+    static constexpr const char* witness_scratch = "paccount_update.w";
+    static constexpr auto run = pau_run;
+    static int check_tree(swm_ctx* ctx, const char* what, const Circuit* c, const Tree* t) {
+        return ledger_check_tree(ctx, what, c->leaf, c->inner, c->shape.height, t);
+    }
 };
-
-// Chunk [base, base + n) of a block: staged, run, its small results copied out and waited for.  The witnesses stay in
-// "paccount_update.w" (*d_w).  leaves (may be NULL): the chunk's 2 x n x 72 leaf bytes, for the prover's public input.
-static int pau_chunk(swm_ctx* ctx, const char* what, const swm_pedersen_account_update_circuit* c, swm_merkle_tree* tree, uint8_t* d_accounts,
-                     const PauBlock& b, size_t base, size_t n, Fr** d_w, uint8_t* leaves) {
-    const size_t item = c->shape.num_witness * sizeof(Fr);
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    SWM_TRY(scratch(ctx, "stage.a", n * (64 + 8 + 2) + 16, (void**)&d_in));
-    PauIn in;
-    in.keys = d_in;
-    in.balances = d_in + 64 * n;
-    in.ids = d_in + 72 * n;
-    in.kinds = d_in + 73 * n;
-    SWM_HIP(ctx, hipMemcpyAsync(d_in, b.keys + 64 * base, 64 * n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(d_in + 64 * n, b.balances + 8 * base, 8 * n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(d_in + 72 * n, b.ids + base, n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(d_in + 73 * n, b.kinds + base, n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_TRY(scratch(ctx, "paccount_update.w", n * item + 16, (void**)&d_out));
-    PauOut O;
-    SWM_TRY(pau_run(ctx, c, tree, d_accounts, in, n, (Fr*)d_out, c->shape.num_witness, &O));
-    uint32_t verdict = 0;
-    SWM_HIP(ctx, hipMemcpyAsync(&verdict, O.verdict, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (verdict) return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: the account table is not the tree's leaf level", what);
-    if (b.old_roots) SWM_HIP(ctx, hipMemcpyAsync(b.old_roots + 32 * base, O.roots, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (b.new_roots) SWM_HIP(ctx, hipMemcpyAsync(b.new_roots + 32 * base, O.roots + 8 * n, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (leaves) SWM_HIP(ctx, hipMemcpyAsync(leaves, O.leaves, 2 * PP_LEAF_LEN * n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(b.flags + base, O.flags, n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(b.status + base, O.status, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *d_w = (Fr*)d_out;
-    return SWM_OK;
-}
-
-// 32 little-endian bytes as a field element: whatever they hold, reduced (the circuit packs the key's bits unreduced)
-static Fr pau_key_mont(const uint8_t* b) {
-    Fr s, r;
-    for (int i = 0; i < 8; i++) {
-        s.v[i] = (uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 | (uint32_t)b[4 * i + 3] << 24;
-        r.v[i] = FrParams::P[i];
-    }
-    while (fp_cmp_std(s, r) >= 0) {  // at most 2^256 / r = 13 rounds
-        uint64_t borrow = 0;
-        for (int i = 0; i < 8; i++) {
-            const uint64_t d = (uint64_t)s.v[i] - r.v[i] - borrow;
-            s.v[i] = (uint32_t)d;
-            borrow = (d >> 32) & 1;
-        }
-    }
-    return fp_from_std(s);
-}
-
-static Fr pau_root_mont(const uint8_t* b) {  // a node of the tree: canonical
-    Fr s;
-    for (int i = 0; i < 8; i++) s.v[i] = (uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 | (uint32_t)b[4 * i + 3] << 24;
-    return fp_from_std(s);
-}
-
-// the prover over one item's device witnesses; public input one, old_root, new_root, id, key_x, key_y, old_balance, new_balance, fresh
-static int pau_prove_item(swm_ctx* ctx, const swm_pk* pk, const PedersenAccountUpdateShape& s, const uint8_t* old_root, const uint8_t* new_root,
-                          unsigned id, unsigned kind, const uint8_t* old_leaf, const uint8_t* new_leaf, const Fr* d_w, swm_rng* rng,
-                          unsigned flags, uint8_t* proof_out, size_t cap, size_t* len) {
-    uint64_t old_balance = 0, new_balance = 0;
-    for (int k = 0; k < 8; k++) {
-        old_balance |= (uint64_t)old_leaf[64 + k] << (8 * k);
-        new_balance |= (uint64_t)new_leaf[64 + k] << (8 * k);
-    }
-    const Fr inst[PAU_INSTANCE] = {fp_one<Fr>(), pau_root_mont(old_root), pau_root_mont(new_root), fp_from_u64<Fr>(id), pau_key_mont(new_leaf),
-                                   pau_key_mont(new_leaf + 32), fp_from_u64<Fr>(old_balance), fp_from_u64<Fr>(new_balance),
-                                   fp_from_u64<Fr>(kind)};
-    return prove_device_witness(ctx, pk, PAU_INSTANCE, s.num_witness, s.num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
-}
-
-// the account table (2^levels leaves of 72 bytes) into the unit's scratch buffer
-static int pau_upload_accounts(swm_ctx* ctx, const uint8_t* accounts, size_t bytes, uint8_t** d_accounts) {
-    SWM_TRY(scratch(ctx, "paccount_update.accounts", bytes + 16, (void**)d_accounts));
-    SWM_HIP(ctx, hipMemcpyAsync(*d_accounts, accounts, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return SWM_OK;
-}
-
-// the table after a chunk and (witness not NULL) the chunk's witnesses back to the host, waited for
-static int pau_download(swm_ctx* ctx, uint8_t* accounts, const uint8_t* d_accounts, size_t table_bytes, uint8_t* witness, const Fr* d_w,
-                        size_t witness_bytes) {
-    SWM_HIP(ctx, hipMemcpyAsync(accounts, d_accounts, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (witness) SWM_HIP(ctx, hipMemcpyAsync(witness, d_w, witness_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SWM_OK;
-}
-
-// The block in chunks.  witness (may be NULL): the host copy of every item; pk (may be NULL): one proof per applied operation.
-static int pau_block(swm_ctx* ctx, const char* what, const swm_pk* pk, const swm_pedersen_account_update_circuit* c, swm_merkle_tree* tree,
-                     uint8_t* accounts, const PauBlock& b, size_t count, uint64_t* witness, swm_rng* rng, unsigned prove_flags,
-                     uint8_t* proofs_out, size_t proof_cap, size_t* lens) {
-    const PedersenAccountUpdateShape& s = c->shape;
-    const size_t num_witness = s.num_witness, item = num_witness * sizeof(Fr), table_bytes = PP_LEAF_LEN << s.levels;
-    std::vector<uint8_t> roots, leaves;  // the prover needs the root pairs whether the caller asked for them or not
-    PauBlock blk = b;
-    if (pk && (!b.old_roots || !b.new_roots)) {
-        roots.resize(64 * count);
-        if (!b.old_roots) blk.old_roots = roots.data();
-        if (!b.new_roots) blk.new_roots = roots.data() + 32 * count;
-    }
-    uint8_t* d_accounts = nullptr;
-    {
-        SWM_ON_DEVICE(ctx);
-        SWM_TRY(drained(ctx, pau_upload_accounts(ctx, accounts, table_bytes, &d_accounts)));
-    }
-    for (const WitnessChunk ch : WitnessChunks(witness_stage_items(ctx, item), count)) {
-        Fr* d_w = nullptr;
-        if (pk) leaves.resize(2 * PP_LEAF_LEN * ch.count);
-        {
-            SWM_ON_DEVICE(ctx);
-            SWM_TRY(drained(ctx, pau_chunk(ctx, what, c, tree, d_accounts, blk, ch.base, ch.count, &d_w, pk ? leaves.data() : nullptr)));
-            // the tree is advanced from here on: the table goes back with it, whatever the prover does below
-            SWM_TRY(drained(ctx, pau_download(ctx, accounts, d_accounts, table_bytes,
-                                              witness ? reinterpret_cast<uint8_t*>(witness) + ch.base * item : nullptr, d_w, ch.count * item)));
-        }
-        for (size_t i = ch.base; pk && i < ch.base + ch.count; i++) {
-            if (!(blk.flags[i] & PAU_FLAG_APPLIED)) continue;
-            const size_t k = i - ch.base;
-            size_t len = 0;
-            SWM_TRY(pau_prove_item(ctx, pk, s, blk.old_roots + 32 * i, blk.new_roots + 32 * i, b.ids[i], b.kinds[i], leaves.data() + PP_LEAF_LEN * k,
-                                   leaves.data() + PP_LEAF_LEN * (ch.count + k), d_w + k * num_witness, rng, prove_flags,
-                                   proofs_out + i * proof_cap, proof_cap, &len));
-            lens[i] = len;
-        }
-    }
-    return SWM_OK;
-}
-
-// what both block entries refuse before anything runs
-static int pau_check_block(swm_ctx* ctx, const char* what, const swm_pedersen_account_update_circuit* c, const swm_merkle_tree* tree,
-                           const uint8_t* kinds, size_t count) {
-    SWM_TRY(pau_check_tree(ctx, what, c, tree));
-    if (count > 0x7FFFFFu) return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: %zu operations in one call", what, count);
-    for (size_t i = 0; i < count; i++)
-        if (kinds[i] > PAU_KIND_REGISTER)
-            return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: operation %zu: kind %u (0 = set balance, 1 = register)", what, i, (unsigned)kinds[i]);
-    return SWM_OK;
-}
 
 }  // namespace swm
 
@@ -450,12 +266,7 @@ int swm_pedersen_account_update_circuit_create(swm_ctx* ctx, const swm_pedersen*
     if (!pedersen_account_update_shape(height, &shape))
         return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_account_update_circuit_create: height %zu (%zu <= height <= %zu)", height,
                        (size_t)PP_MIN_HEIGHT, (size_t)PP_MAX_HEIGHT);
-    if (leaf->window_size != 4 || inner->window_size != 4)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_account_update_circuit_create: windows of %u and %u bits (4 is required)",
-                       leaf->window_size, inner->window_size);
-    if (leaf->num_windows < PP_LEAF_WINDOWS || inner->num_windows < PP_INNER_WINDOWS)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_account_update_circuit_create: %u leaf and %u two-to-one windows (at least %zu and "
-                       "%zu are required)", leaf->num_windows, inner->num_windows, (size_t)PP_LEAF_WINDOWS, (size_t)PP_INNER_WINDOWS);
+    SWM_TRY(pedersen_tree_crh_check(ctx, "pedersen_account_update_circuit_create", leaf, inner));
     std::unique_ptr<swm_pedersen_account_update_circuit> c(new swm_pedersen_account_update_circuit);
     c->leaf = leaf;
     c->inner = inner;
@@ -470,14 +281,8 @@ int swm_pedersen_account_update_witness_at(swm_ctx* ctx, const swm_pedersen_acco
                                            uint8_t* accounts_inout, const uint8_t* ids, const uint8_t* kinds, const uint8_t* keys_xy,
                                            const uint8_t* balances, size_t count, uint64_t* witnesses_out, uint8_t* old_roots,
                                            uint8_t* new_roots, uint8_t* flags, uint32_t* status) {
-    const char* what = "pedersen_account_update_witness_at";
-    if (!ctx || !c || !tree || !accounts_inout ||
-        (count && (!ids || !kinds || !keys_xy || !balances || !witnesses_out || !old_roots || !new_roots || !flags || !status)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: bad arguments", what);
-    SWM_TRY(pau_check_block(ctx, what, c, tree, kinds, count));
-    if (!count) return SWM_OK;
-    const PauBlock b = {ids, kinds, keys_xy, balances, old_roots, new_roots, flags, status};
-    return pau_block(ctx, what, nullptr, c, tree, accounts_inout, b, count, witnesses_out, nullptr, 0, nullptr, 0, nullptr);
+    return account_update_witness_at<PedersenAccountUpdateUnit>(ctx, c, tree, accounts_inout, ids, kinds, keys_xy, balances, count, witnesses_out,
+                                                                old_roots, new_roots, flags, status);
 }
 
 int swm_pedersen_account_update_prove_many_at(swm_ctx* ctx, const swm_pk* pk, const swm_pedersen_account_update_circuit* c,
@@ -485,34 +290,16 @@ int swm_pedersen_account_update_prove_many_at(swm_ctx* ctx, const swm_pk* pk, co
                                               const uint8_t* keys_xy, const uint8_t* balances, size_t count, swm_rng* rng,
                                               unsigned prove_flags, uint8_t* proofs_out, size_t proof_cap, size_t* lens, uint8_t* old_roots,
                                               uint8_t* new_roots, uint8_t* flags, uint32_t* status) {
-    const char* what = "pedersen_account_update_prove_many_at";
-    if (!ctx || !pk || !c || !tree || !accounts_inout || !rng ||
-        (count && (!ids || !kinds || !keys_xy || !balances || !proofs_out || !lens || !flags || !status)))
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: bad arguments", what);
-    SWM_TRY(pau_check_block(ctx, what, c, tree, kinds, count));
-    // the tree is advanced before the proofs are made: a key of another shape is refused while nothing has changed
-    if (!pk_takes_shape(pk, c->shape.num_instance, c->shape.num_witness, c->shape.num_constraints))
-        return set_err(ctx, SWM_ERR_MISMATCH, "%s: the proving key is not that of this circuit", what);
-    if (!count) return SWM_OK;
-    for (size_t i = 0; i < count; i++) {  // whatever ends the call, every entry has been written
-        lens[i] = 0;
-        flags[i] = 0;
-        status[i] = 0;
-    }
-    const PauBlock b = {ids, kinds, keys_xy, balances, old_roots, new_roots, flags, status};
-    return pau_block(ctx, what, pk, c, tree, accounts_inout, b, count, nullptr, rng, prove_flags, proofs_out, proof_cap, lens);
+    return account_update_prove_many_at<PedersenAccountUpdateUnit>(ctx, pk, c, tree, accounts_inout, ids, kinds, keys_xy, balances, count, rng,
+                                                                   prove_flags, proofs_out, proof_cap, lens, old_roots, new_roots, flags, status);
 }
 
 int swm_pedersen_account_update_prove_at(swm_ctx* ctx, const swm_pk* pk, const swm_pedersen_account_update_circuit* c, swm_merkle_tree* tree,
                                          uint8_t* accounts_inout, uint8_t id, uint8_t kind, const uint8_t key_xy[64], uint64_t balance,
                                          swm_rng* rng, unsigned prove_flags, uint8_t* proof_out, size_t cap, size_t* len,
                                          uint8_t old_root[32], uint8_t new_root[32], uint8_t* flag, uint32_t* status) {
-    if (!key_xy || !proof_out || !len || !old_root || !new_root || !flag || !status)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_account_update_prove_at: bad arguments");
-    uint8_t b[8];
-    for (int k = 0; k < 8; k++) b[k] = (uint8_t)(balance >> (8 * k));
-    return swm_pedersen_account_update_prove_many_at(ctx, pk, c, tree, accounts_inout, &id, &kind, key_xy, b, 1, rng, prove_flags, proof_out, cap,
-                                                     len, old_root, new_root, flag, status);
+    return account_update_prove_at<PedersenAccountUpdateUnit>(ctx, pk, c, tree, accounts_inout, id, kind, key_xy, balance, rng, prove_flags,
+                                                              proof_out, cap, len, old_root, new_root, flag, status);
 }
 
 }  // extern "C"

@@ -255,10 +255,19 @@ static int pp_run(swm_ctx* ctx, const swm_pedersen_payment_circuit* c, const swm
                             tree ? nullptr : d_sib_s, tree ? nullptr : d_sib_r, d_sig_ok, d_w, d_flags, d_status);
 }
 
-static int pp_check_tree(swm_ctx* ctx, const char* what, const swm_pedersen_payment_circuit* c, const swm_merkle_tree* t) {
-    if (t->leaf != c->leaf || t->inner != c->inner || t->height != c->shape.height || t->leaf_len != PP_LEAF_LEN)
+int ledger_check_tree(swm_ctx* ctx, const char* what, const swm_pedersen* leaf, const swm_pedersen* inner, size_t height, const swm_merkle_tree* t) {
+    if (t->leaf != leaf || t->inner != inner || t->height != height || t->leaf_len != PP_LEAF_LEN)
         return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: a tree of height %zu with %zu-byte leaves for a circuit of height %zu with %zu-byte leaves, "
-                       "or other parameters", what, t->height, t->leaf_len, c->shape.height, (size_t)PP_LEAF_LEN);
+                       "or other parameters", what, t->height, t->leaf_len, height, (size_t)PP_LEAF_LEN);
+    return SWM_OK;
+}
+
+int pedersen_tree_crh_check(swm_ctx* ctx, const char* what, const swm_pedersen* leaf, const swm_pedersen* inner) {
+    if (leaf->window_size != 4 || inner->window_size != 4)
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: windows of %u and %u bits (4 is required)", what, leaf->window_size, inner->window_size);
+    if (leaf->num_windows < PP_LEAF_WINDOWS || inner->num_windows < PP_INNER_WINDOWS)
+        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: %u leaf and %u two-to-one windows (at least %zu and %zu are required)", what,
+                       leaf->num_windows, inner->num_windows, (size_t)PP_LEAF_WINDOWS, (size_t)PP_INNER_WINDOWS);
     return SWM_OK;
 }
 
@@ -269,7 +278,9 @@ struct PedersenPaymentUnit {  // what ledger_witness_host.h drives
     using Tree = swm_merkle_tree;
     static constexpr const char* name = "pedersen_payment";
     static constexpr auto run = pp_run;
-    static constexpr auto check_tree = pp_check_tree;
+    static int check_tree(swm_ctx* ctx, const char* what, const Circuit* c, const Tree* t) {
+        return ledger_check_tree(ctx, what, c->leaf, c->inner, c->shape.height, t);
+    }
     static const uint8_t* root_node(const Tree* t) { return t->d_nodes + 32 * (t->num_nodes() - 1); }
 };
 
@@ -286,12 +297,7 @@ int swm_pedersen_payment_circuit_create(swm_ctx* ctx, const swm_schnorr* schnorr
     if (!pedersen_payment_shape(height, schnorr->has_salt, &shape))
         return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_payment_circuit_create: height %zu (%zu <= height <= %zu)", height,
                        (size_t)PP_MIN_HEIGHT, (size_t)PP_MAX_HEIGHT);
-    if (leaf->window_size != 4 || inner->window_size != 4)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_payment_circuit_create: windows of %u and %u bits (4 is required)", leaf->window_size,
-                       inner->window_size);
-    if (leaf->num_windows < PP_LEAF_WINDOWS || inner->num_windows < PP_INNER_WINDOWS)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_payment_circuit_create: %u leaf and %u two-to-one windows (at least %zu and %zu are "
-                       "required)", leaf->num_windows, inner->num_windows, (size_t)PP_LEAF_WINDOWS, (size_t)PP_INNER_WINDOWS);
+    SWM_TRY(pedersen_tree_crh_check(ctx, "pedersen_payment_circuit_create", leaf, inner));
     std::unique_ptr<swm_pedersen_payment_circuit> c(new swm_pedersen_payment_circuit);
     c->schnorr.params = schnorr;
     c->schnorr.shape = shape.schnorr;

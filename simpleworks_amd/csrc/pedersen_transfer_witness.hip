@@ -27,6 +27,9 @@
 // wave's running digests above.  An applied transfer writes nodes and table as it walks; a refused one walks the same way and
 // writes neither.  Within a level every read of the nodes and of the two running digests comes before a barrier and every write
 // after it.
+//
+// The host layer (chunks, the verdict-first results step, the block loop, the entries) is ledger_witness_host.h's over
+// PedersenTransferUnit, which is transfer_units.h's PedersenTransfers and a name.
 #include <hip/hip_runtime.h>
 
 #include <string.h>
@@ -37,6 +40,7 @@
 #include "context.h"
 #include "ff.cuh"
 #include "host/pedersen_transfer_shape.h"
+#include "ledger_bytes.cuh"
 #include "merkle_nodes.cuh"
 #include "merkle_tree.h"
 #include "pedersen.cuh"
@@ -78,13 +82,6 @@ __global__ void __launch_bounds__(256) pedersen_transfer_check_kernel(const EdRo
     }
 }
 
-__device__ __forceinline__ uint64_t pt_load_u64(const uint8_t* b) {
-    uint64_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) v |= (uint64_t)b[k] << (8 * k);
-    return v;
-}
-
 __device__ __forceinline__ bool pt_blank(const uint8_t* leaf) {
     unsigned any = 0;
     for (unsigned k = 0; k < PP_LEAF_LEN; k++) any |= leaf[k];
@@ -124,12 +121,12 @@ __global__ void __launch_bounds__(PT_LANES) pedersen_transfer_advance_kernel(con
     for (size_t t = 0; t < count; t++) {
         const uint8_t* msg = msgs + PP_MSG_LEN * t;
         const unsigned sid = msg[0], rid = msg[1], s = sid & mask, r = rid & mask;
-        const uint64_t amount = pt_load_u64(msg + 2);
+        const uint64_t amount = le_load_u64(msg + 2);
         const uint8_t* s_leaf_old = s_acc + PP_LEAF_LEN * s;
-        const uint64_t balance = pt_load_u64(s_leaf_old + 64), diff = balance - amount;
+        const uint64_t balance = le_load_u64(s_leaf_old + 64), diff = balance - amount;
         // the recipient's leaf in the tree of R1: the table's, or the debited leaf when it pays itself
         const uint8_t* r_leaf_old = s_acc + PP_LEAF_LEN * r;
-        const uint64_t rbalance = s == r ? diff : pt_load_u64(r_leaf_old + 64), sum = rbalance + amount;
+        const uint64_t rbalance = s == r ? diff : le_load_u64(r_leaf_old + 64), sum = rbalance + amount;
         unsigned flag = (sig_ok[t] ? PT_FLAG_SIG : 0u) | (amount <= balance ? PT_FLAG_BALANCE : 0u) | (sum >= rbalance ? PT_FLAG_SUM : 0u) |
                         (!pt_blank(s_leaf_old) && !pt_blank(r_leaf_old) ? PT_FLAG_ACCOUNTS : 0u);
         const unsigned st = (O.status[t] & PT_ST_KEY) | ((sid | rid) >> levels ? PT_ST_ID : 0u) | (sid == rid ? PT_ST_SELF : 0u);
@@ -226,8 +223,8 @@ static size_t pt_aux_bytes(size_t n, size_t levels) {
 
 // n transfers on device buffers, in order: d_accounts and the tree's nodes are advanced.  d_w 16-byte aligned; item i's witnesses
 // from d_w + i * stride (stride >= the shape's num_witness: a block's own driver passes that, the rollup's one more).
-static int pt_run(swm_ctx* ctx, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree, uint8_t* d_accounts, const uint8_t* d_msgs,
-                  const uint8_t* d_sigs, size_t n, Fr* d_w, size_t stride, PtOut* out) {
+int pedersen_transfer_run_strided(swm_ctx* ctx, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree, uint8_t* d_accounts,
+                                  const uint8_t* d_msgs, const uint8_t* d_sigs, size_t n, Fr* d_w, size_t stride, BlockRunOut* out) {
     const PedersenTransferShape& s = c->shape;
     const unsigned levels = (unsigned)s.levels, n_leaves = 1u << levels;
     uint8_t* aux = nullptr;
@@ -263,60 +260,14 @@ static int pt_run(swm_ctx* ctx, const swm_pedersen_transfer_circuit* c, swm_merk
     for (int k = 0; k < 4; k++) A.s[k] = {O.leaves + k * leaves, O.dig + k * dig, O.sib + (k / 2) * sib, O.idx + (k / 2) * n, at[k], (unsigned)(k & 1)};
     SWM_TRY(pp_record_run(ctx, c->leaf, c->inner, A, n, d_w));
     SWM_TRY(transfer_bits_run(ctx, n, stride, s.balance_at, s.sum_at, s.r1_at, s.recipient_bits_at, levels, O.leaves, O.dig + dig, d_w));
-    *out = O;
-    return SWM_OK;
-}
-
-int pedersen_transfer_check_tree(swm_ctx* ctx, const char* what, const swm_pedersen_transfer_circuit* c, const swm_merkle_tree* t) {
-    if (t->leaf != c->leaf || t->inner != c->inner || t->height != c->shape.height || t->leaf_len != PP_LEAF_LEN)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: a tree of height %zu with %zu-byte leaves for a circuit of height %zu with %zu-byte leaves, "
-                       "or other parameters", what, t->height, t->leaf_len, c->shape.height, (size_t)PP_LEAF_LEN);
-    return SWM_OK;
-}
-
-// Chunk [base, base + n) of a block: staged, run, its small results copied out and waited for.  The witnesses stay in
-// "ptransfer.w" (*d_w).  d_accounts: the table on the device ("ptransfer.accounts"), uploaded by the caller.
-static int pt_chunk(swm_ctx* ctx, const char* what, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree, uint8_t* d_accounts,
-                    const TransferBlock& b, size_t base, size_t n, Fr** d_w) {
-    const size_t item = c->shape.num_witness * sizeof(Fr);
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    SWM_TRY(scratch(ctx, "stage.a", n * (64 + PP_MSG_LEN) + 16, (void**)&d_in));
-    SWM_HIP(ctx, hipMemcpyAsync(d_in, b.sigs + 64 * base, 64 * n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(d_in + 64 * n, b.msgs + PP_MSG_LEN * base, PP_MSG_LEN * n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_TRY(scratch(ctx, "ptransfer.w", n * item + 16, (void**)&d_out));
-    PtOut O;
-    SWM_TRY(pt_run(ctx, c, tree, d_accounts, d_in + 64 * n, d_in, n, (Fr*)d_out, c->shape.num_witness, &O));
-    uint32_t verdict = 0;
-    SWM_HIP(ctx, hipMemcpyAsync(&verdict, O.verdict, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (verdict) return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: the account table is not the tree's leaf level", what);
-    if (b.old_roots) SWM_HIP(ctx, hipMemcpyAsync(b.old_roots + 32 * base, O.roots, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (b.new_roots) SWM_HIP(ctx, hipMemcpyAsync(b.new_roots + 32 * base, O.roots + 8 * n, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(b.flags + base, O.flags, n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(b.status + base, O.status, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *d_w = (Fr*)d_out;
-    return SWM_OK;
-}
-
-int pedersen_transfer_run_strided(swm_ctx* ctx, const swm_pedersen_transfer_circuit* c, swm_merkle_tree* tree, uint8_t* d_accounts,
-                                  const uint8_t* d_msgs, const uint8_t* d_sigs, size_t n, Fr* d_w, size_t stride, TransferRunOut* out) {
-    PtOut O;
-    SWM_TRY(pt_run(ctx, c, tree, d_accounts, d_msgs, d_sigs, n, d_w, stride, &O));
-    *out = TransferRunOut{O.roots, O.flags, O.status, O.verdict};
+    *out = BlockRunOut{O.roots, O.flags, O.status, O.verdict};
     return SWM_OK;
 }
 
 static_assert(PT_FLAG_APPLIED == TRANSFER_FLAG_APPLIED, "the block driver proves what the advance kernel applied");
-static_assert(PP_MSG_LEN == PY_MSG_LEN && PP_LEAF_LEN == PY_LEAF_LEN, "the block driver's message and leaf");
 
-struct PedersenTransferUnit {  // what ledger_witness_host.h drives
-    using Circuit = swm_pedersen_transfer_circuit;
-    using Tree = swm_merkle_tree;
+struct PedersenTransferUnit : PedersenTransfers {  // what ledger_witness_host.h drives
     static constexpr const char* name = "pedersen_transfer";
-    static constexpr const char* accounts_scratch = "ptransfer.accounts";
-    static constexpr auto check_tree = pedersen_transfer_check_tree;
-    static constexpr auto chunk = pt_chunk;
 };
 
 }  // namespace swm
@@ -332,12 +283,7 @@ int swm_pedersen_transfer_circuit_create(swm_ctx* ctx, const swm_schnorr* schnor
     if (!pedersen_transfer_shape(height, schnorr->has_salt, &shape))
         return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_transfer_circuit_create: height %zu (%zu <= height <= %zu)", height,
                        (size_t)PP_MIN_HEIGHT, (size_t)PP_MAX_HEIGHT);
-    if (leaf->window_size != 4 || inner->window_size != 4)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_transfer_circuit_create: windows of %u and %u bits (4 is required)", leaf->window_size,
-                       inner->window_size);
-    if (leaf->num_windows < PP_LEAF_WINDOWS || inner->num_windows < PP_INNER_WINDOWS)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "pedersen_transfer_circuit_create: %u leaf and %u two-to-one windows (at least %zu and %zu are "
-                       "required)", leaf->num_windows, inner->num_windows, (size_t)PP_LEAF_WINDOWS, (size_t)PP_INNER_WINDOWS);
+    SWM_TRY(pedersen_tree_crh_check(ctx, "pedersen_transfer_circuit_create", leaf, inner));
     std::unique_ptr<swm_pedersen_transfer_circuit> c(new swm_pedersen_transfer_circuit);
     c->schnorr.params = schnorr;
     c->schnorr.shape = shape.payment.schnorr;

@@ -73,7 +73,7 @@ int rollup_pass(swm_ctx* ctx, const char* what, const typename U::Circuit* c, ty
     const size_t n = s.transfers, levels = c->shape.levels, table_bytes = PY_LEAF_LEN << levels, node_bytes = tree->num_nodes() * 32;
     const size_t w_bytes = s.num_witness * sizeof(Fr);
     uint8_t *d_accounts = nullptr, *d_in = nullptr, *d_out = nullptr, *d_snap = nullptr;
-    SWM_TRY(transfer_upload_accounts(ctx, U::accounts_scratch, accounts, table_bytes, &d_accounts));
+    SWM_TRY(block_upload_accounts(ctx, U::accounts_scratch, accounts, table_bytes, &d_accounts));
     SWM_TRY(scratch(ctx, "stage.a", n * (64 + PY_MSG_LEN) + 16, (void**)&d_in));
     SWM_HIP(ctx, hipMemcpyAsync(d_in, b.sigs, 64 * n, hipMemcpyHostToDevice, ctx->stream));
     SWM_HIP(ctx, hipMemcpyAsync(d_in + 64 * n, b.msgs, PY_MSG_LEN * n, hipMemcpyHostToDevice, ctx->stream));
@@ -81,7 +81,7 @@ int rollup_pass(swm_ctx* ctx, const char* what, const typename U::Circuit* c, ty
     SWM_TRY(scratch(ctx, "rollup.snapshot", node_bytes + 16, (void**)&d_snap));  // the nodes | the verdict word
     uint32_t* d_verdict = reinterpret_cast<uint32_t*>(d_snap + node_bytes);
     SWM_HIP(ctx, hipMemcpyAsync(d_snap, tree->d_nodes, node_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    TransferRunOut O;
+    BlockRunOut O;
     SWM_TRY(U::run(ctx, c, tree, d_accounts, d_in + 64 * n, d_in, n, (Fr*)d_out, s.stride, &O));
     SWM_LAUNCH(ctx, "rollup_link", rollup_link_kernel, dim3(1), dim3(RU_LANES), 0, O.roots + 8 * n, O.flags, O.status, (unsigned)n, s.stride,
                s.root_at, (Fr*)d_out, d_verdict);
@@ -180,22 +180,12 @@ int rollup_prove_at(swm_ctx* ctx, const swm_pk* pk, const typename U::Circuit* c
                                 len);
 }
 
-struct RollupUnit {
-    using Circuit = swm_transfer_circuit;
-    using Tree = swm_poseidon_tree;
+struct RollupUnit : PoseidonTransfers {
     static constexpr const char* name = "rollup";
-    static constexpr const char* accounts_scratch = "transfer.accounts";
-    static constexpr auto check_tree = transfer_check_tree;
-    static constexpr auto run = transfer_run_strided;
 };
 
-struct PedersenRollupUnit {
-    using Circuit = swm_pedersen_transfer_circuit;
-    using Tree = swm_merkle_tree;
+struct PedersenRollupUnit : PedersenTransfers {
     static constexpr const char* name = "pedersen_rollup";
-    static constexpr const char* accounts_scratch = "ptransfer.accounts";
-    static constexpr auto check_tree = pedersen_transfer_check_tree;
-    static constexpr auto run = pedersen_transfer_run_strided;
 };
 
 }  // namespace swm

@@ -27,6 +27,9 @@
 // An applied transfer writes its digests into the nodes (in LDS) as it walks: the recipient lane at every level, the sender lane up
 // to d.  A refused one walks the same way, for its witness, and writes nothing.  s == r has no d: the recipient lane's path in
 // the tree of R1 is the sender lane's throughout (the sequential no-op); it is never applied.
+//
+// The host layer (chunks, the verdict-first results step, the block loop, the entries) is ledger_witness_host.h's over TransferUnit,
+// which is transfer_units.h's PoseidonTransfers (circuit, tree, scratch names, tree check, transfer_run_strided) and a name.
 #include <hip/hip_runtime.h>
 
 #include <string.h>
@@ -37,6 +40,7 @@
 #include "context.h"
 #include "ff.cuh"
 #include "host/transfer_shape.h"
+#include "ledger_bytes.cuh"
 #include "merkle_nodes.cuh"
 #include "poseidon.h"
 #include "poseidon_tree.h"
@@ -63,13 +67,6 @@ __global__ void __launch_bounds__(TR_LANES) transfer_prep_kernel(const uint8_t* 
     const unsigned sender = msgs[PY_MSG_LEN * item] & ((1u << levels) - 1);
     const uint8_t* b = accounts + PY_LEAF_LEN * sender + 4 * word;
     keys[i] = (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24;
-}
-
-__device__ __forceinline__ uint64_t tr_load_u64(const uint8_t* b) {
-    uint64_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) v |= (uint64_t)b[k] << (8 * k);
-    return v;
 }
 
 __device__ __forceinline__ bool tr_blank(const uint8_t* leaf) {
@@ -136,12 +133,12 @@ __global__ void __launch_bounds__(TR_LANES) transfer_advance_kernel(const uint4*
     for (size_t t = 0; t < count; t++) {
         const uint8_t* msg = msgs + PY_MSG_LEN * t;
         const unsigned sid = msg[0], rid = msg[1], s = sid & mask, r = rid & mask;
-        const uint64_t amount = tr_load_u64(msg + 2);
+        const uint64_t amount = le_load_u64(msg + 2);
         const uint8_t* s_leaf = s_acc + PY_LEAF_LEN * s;
-        const uint64_t balance = tr_load_u64(s_leaf + 64), diff = balance - amount;
+        const uint64_t balance = le_load_u64(s_leaf + 64), diff = balance - amount;
         // the recipient's leaf in the tree of R1: the table's, or the debited leaf when it pays itself
         const uint8_t* r_leaf = s_acc + PY_LEAF_LEN * r;
-        const uint64_t rbalance = s == r ? diff : tr_load_u64(r_leaf + 64), sum = rbalance + amount;
+        const uint64_t rbalance = s == r ? diff : le_load_u64(r_leaf + 64), sum = rbalance + amount;
         unsigned flag = (sig_ok[t] ? TR_FLAG_SIG : 0u) | (amount <= balance ? TR_FLAG_BALANCE : 0u) | (sum >= rbalance ? TR_FLAG_SUM : 0u) |
                         (!tr_blank(s_leaf) && !tr_blank(r_leaf) ? TR_FLAG_ACCOUNTS : 0u);
         const unsigned st = (O.status[t] & TR_ST_KEY) | ((sid | rid) >> levels ? TR_ST_ID : 0u) | (sid == rid ? TR_ST_SELF : 0u);
@@ -278,8 +275,8 @@ static size_t tr_aux_bytes(size_t n, size_t levels) {
 
 // n transfers on device buffers, in order: d_accounts and the tree's nodes are advanced.  d_w 16-byte aligned; item i's witnesses
 // from d_w + i * stride (stride >= the shape's num_witness: a block's own driver passes that, the rollup's one more).
-static int tr_run(swm_ctx* ctx, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* d_accounts, const uint8_t* d_msgs,
-                  const uint8_t* d_sigs, size_t n, Fr* d_w, size_t stride, TrOut* out) {
+int transfer_run_strided(swm_ctx* ctx, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* d_accounts, const uint8_t* d_msgs,
+                         const uint8_t* d_sigs, size_t n, Fr* d_w, size_t stride, BlockRunOut* out) {
     const TransferShape& s = c->shape;
     const swm_poseidon* p = c->tree.params;
     const unsigned levels = (unsigned)s.levels;
@@ -306,39 +303,7 @@ static int tr_run(swm_ctx* ctx, const swm_transfer_circuit* c, swm_poseidon_tree
         SWM_TRY(ptw_record(ctx, &c->tree, O.leaves + k * leaves, O.idx + (k / 2) * n, O.dig + k * dig, O.sib + (k / 2) * sib, n, d_w + at[k],
                            stride, k % 2 == 0));
     SWM_TRY(transfer_bits_run(ctx, n, stride, s.balance_at, s.sum_at, s.r1_at, s.recipient_bits_at, levels, O.leaves, O.dig + dig, d_w));
-    *out = O;
-    return SWM_OK;
-}
-
-int transfer_check_tree(swm_ctx* ctx, const char* what, const swm_transfer_circuit* c, const swm_poseidon_tree* t) {
-    if (t->params != c->tree.params || t->height != c->shape.height || t->leaf_len != PY_LEAF_LEN)
-        return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: a tree of height %zu with %zu-byte leaves for a circuit of height %zu with %zu-byte leaves, "
-                       "or other parameters", what, t->height, t->leaf_len, c->shape.height, (size_t)PY_LEAF_LEN);
-    return SWM_OK;
-}
-
-// Chunk [base, base + n) of a block: staged, run, its small results copied out and waited for.  The witnesses stay in
-// "transfer.w" (*d_w).  d_accounts: the table on the device ("transfer.accounts"), uploaded by the caller.
-static int tr_chunk(swm_ctx* ctx, const char* what, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* d_accounts, const TransferBlock& b,
-                    size_t base, size_t n, Fr** d_w) {
-    const TransferShape& s = c->shape;
-    const size_t item = s.num_witness * sizeof(Fr);
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    SWM_TRY(scratch(ctx, "stage.a", n * (64 + PY_MSG_LEN) + 16, (void**)&d_in));
-    SWM_HIP(ctx, hipMemcpyAsync(d_in, b.sigs + 64 * base, 64 * n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(d_in + 64 * n, b.msgs + PY_MSG_LEN * base, PY_MSG_LEN * n, hipMemcpyHostToDevice, ctx->stream));
-    SWM_TRY(scratch(ctx, "transfer.w", n * item + 16, (void**)&d_out));
-    TrOut O;
-    SWM_TRY(tr_run(ctx, c, tree, d_accounts, d_in + 64 * n, d_in, n, (Fr*)d_out, s.num_witness, &O));
-    uint32_t verdict = 0;
-    SWM_HIP(ctx, hipMemcpyAsync(&verdict, O.verdict, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (b.old_roots) SWM_HIP(ctx, hipMemcpyAsync(b.old_roots + 32 * base, O.roots, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (b.new_roots) SWM_HIP(ctx, hipMemcpyAsync(b.new_roots + 32 * base, O.roots + 8 * n, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(b.flags + base, O.flags, n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipMemcpyAsync(b.status + base, O.status, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
-    SWM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (verdict) return set_err(ctx, SWM_ERR_INVALID_ARG, "%s: the account table is not the tree's leaf level", what);
-    *d_w = (Fr*)d_out;
+    *out = BlockRunOut{O.roots, O.flags, O.status, O.verdict};
     return SWM_OK;
 }
 
@@ -354,23 +319,10 @@ int transfer_prove_item(swm_ctx* ctx, const swm_pk* pk, size_t num_witness, size
     return prove_device_witness(ctx, pk, TR_INSTANCE, num_witness, num_constraints, inst, d_w, rng, flags, proof_out, cap, len);
 }
 
-int transfer_run_strided(swm_ctx* ctx, const swm_transfer_circuit* c, swm_poseidon_tree* tree, uint8_t* d_accounts, const uint8_t* d_msgs,
-                         const uint8_t* d_sigs, size_t n, Fr* d_w, size_t stride, TransferRunOut* out) {
-    TrOut O;
-    SWM_TRY(tr_run(ctx, c, tree, d_accounts, d_msgs, d_sigs, n, d_w, stride, &O));
-    *out = TransferRunOut{O.roots, O.flags, O.status, O.verdict};
-    return SWM_OK;
-}
-
 static_assert(TR_FLAG_APPLIED == TRANSFER_FLAG_APPLIED, "the block driver proves what the advance kernel applied");
 
-struct TransferUnit {  // what ledger_witness_host.h drives
-    using Circuit = swm_transfer_circuit;
-    using Tree = swm_poseidon_tree;
+struct TransferUnit : PoseidonTransfers {  // what ledger_witness_host.h drives
     static constexpr const char* name = "transfer";
-    static constexpr const char* accounts_scratch = "transfer.accounts";
-    static constexpr auto check_tree = transfer_check_tree;
-    static constexpr auto chunk = tr_chunk;
 };
 
 }  // namespace swm

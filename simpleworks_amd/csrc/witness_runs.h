@@ -3,7 +3,8 @@
 // item i's block at d_witness + i * stride; the stand-alone circuits pass their own num_witness as the stride, a composed circuit
 // its larger one with d_witness moved to the block's first element.  And the parts of a payment's witness pass that do not depend
 // on the account tree's hash (payment_witness.hip defines them; pedersen_payment_witness.hip calls them with its own offsets).
-// Kernel launchers only: the host layer above them is witness_host.h and ledger_witness_host.h.
+// Kernel launchers only: the host layer above them is witness_host.h and, for payments, transfers and account updates over either
+// tree, ledger_witness_host.h (which also holds the tree and CRH checks of the ledger circuits).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -242,13 +242,15 @@ def test_a_table_that_is_not_the_trees_is_refused(L, ref, circuits, fresh_tree, 
         keys = np.frombuffer(b"".join(o[2] for o in ops), dtype=np.uint8).copy()
         bal = np.array([o[3] for o in ops], dtype="<u8")
         w = np.zeros((2 * nw, 4), dtype=np.uint64)
-        old, new = np.zeros((2, 32), dtype=np.uint8), np.zeros((2, 32), dtype=np.uint8)
-        flags, status = np.zeros(2, dtype=np.uint8), np.zeros(2, dtype=np.uint32)
+        old, new = np.full((2, 32), 0xA5, dtype=np.uint8), np.full((2, 32), 0xA5, dtype=np.uint8)
+        flags, status = np.full(2, 0xA5, dtype=np.uint8), np.full(2, 0xA5A5A5A5, dtype=np.uint32)
         rc = c.ctx.lib.swm_account_update_witness_at(c.ctx.h, c.h, tree.h, acc.ctypes.data, ids.ctypes.data, kinds.ctypes.data, keys.ctypes.data,
                                                      bal.ctypes.data, 2, w.ctypes.data, old.ctypes.data, new.ctypes.data, flags.ctypes.data,
                                                      status.ctypes.data)
         assert rc == -1 and b"account table" in c.ctx.lib.swm_last_error(c.ctx.h)
         assert np.array_equal(acc, kept) and np.array_equal(c.ctx.poseidon_tree_nodes(tree.h), before)
+        for out in (old, new, flags, status):    # nothing is copied out after a refused table
+            assert np.all(out.view(np.uint8) == 0xA5)
     with pytest.raises(SwmError) as e:       # a kind that is neither
         c.witness_at(tree, first, [(2, 2, AM.key(2), 0)])
     assert e.value.code == -1 and "kind 2" in str(e.value)

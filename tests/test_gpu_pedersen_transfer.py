@@ -307,6 +307,19 @@ def test_a_table_that_is_not_the_trees_is_refused(L, circuits, world, fresh_tree
             c.witness_at(tree, wrong, _pairs(block[:2]))
         assert e.value.code == -1 and "account table" in str(e.value)
         assert np.array_equal(c.ctx.merkle_tree_nodes(tree.h), before)
+    # the entry itself at height 2, two transfers: a refused table leaves the caller's result arrays byte for byte
+    small, pairs = world(2)[0], _pairs(world(2)[1][:2])
+    c2, tree2 = circuits(2), fresh_tree(2, small)
+    acc = np.frombuffer(small[0][:64] + bytes([small[0][64] ^ 1]) + small[0][65:] + small[1], dtype=np.uint8).copy()
+    msgs, sigs = (np.frombuffer(b"".join(p[k] for p in pairs), dtype=np.uint8).copy() for k in (0, 1))
+    w = np.zeros((2 * c2.shape()[1], 4), dtype=np.uint64)
+    old, new = np.full((2, 32), 0xA5, dtype=np.uint8), np.full((2, 32), 0xA5, dtype=np.uint8)
+    flags, status = np.full(2, 0xA5, dtype=np.uint8), np.full(2, 0xA5A5A5A5, dtype=np.uint32)
+    rc = c2.ctx.lib.swm_pedersen_transfer_witness_at(c2.ctx.h, c2.h, tree2.h, acc.ctypes.data, msgs.ctypes.data, sigs.ctypes.data, 2,
+                                                     w.ctypes.data, old.ctypes.data, new.ctypes.data, flags.ctypes.data, status.ctypes.data)
+    assert rc == -1 and b"account table" in c2.ctx.lib.swm_last_error(c2.ctx.h)
+    for out in (old, new, flags, status):
+        assert np.all(out.view(np.uint8) == 0xA5)
     with pytest.raises(SwmError):       # a tree of another height
         circuits(2).witness_at(tree, first[:2], _pairs(block[:1]))
     for h in (1, 10):
